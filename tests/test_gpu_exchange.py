@@ -128,9 +128,10 @@ def _run_records(rng, g):
 
 
 def _random_local(rng, pass_slots, max_groups, runs=False):
+    """max_groups: a bound (random record counts up to it) or a tuple of exact record counts, one per pass slot."""
     loc = {}
-    for s in pass_slots:
-        g = int(rng.integers(0, max_groups + 1))
+    for k, s in enumerate(pass_slots):
+        g = int(rng.integers(0, max_groups + 1)) if isinstance(max_groups, int) else int(max_groups[k])
         rec = _run_records(rng, g) if runs else rng.integers(0, 2 ** 32, (g, 3), dtype=np.uint64).astype(np.uint32)
         m = rng.integers(0, 2 ** 32, g, dtype=np.uint64).astype(np.uint32)
         m[rng.random(g) < 0.3] = 0
@@ -139,13 +140,17 @@ def _random_local(rng, pass_slots, max_groups, runs=False):
 
 
 @pytest.mark.parametrize("world,pass_slots,max_groups,runs", [(1, (0, 1), 300, False), (3, (0, 1), 2000, True), (8, (0, 1, 2, 3), 700, True), (64, (0,), 40, False),
-                                                              (2, (1, 3), 100000, False), (2, (0, 1), 150000, True)])
+                                                              (2, (1, 3), 100000, False), (2, (0, 1), 150000, True),
+                                                              (3, (0, 1, 2, 3), (1023, 1024, 1025, 2049), True),
+                                                              (2, (0, 1, 2, 3), (2049, 1025, 1024, 1023), False)])
 def test_pack_unpack_kernels_equal_numpy_protocol(dev, world, pass_slots, max_groups, runs):
     """runs False: random record words (every record its own run: the encoding must stay lossless); True: records the way
-    the instance pass emits them, with a run capacity below the group capacity."""
+    the instance pass emits them, with a run capacity below the group capacity.  A tuple of max_groups gives every pass
+    slot exactly that many records: one short of a pack tile (kPackTile = 1024 records), one tile, one tile and one
+    record, two tiles and one record."""
     from exchange_ref import runs_of_records_np
     rng = np.random.default_rng(world * 1000 + len(pass_slots))
-    S = max_groups * len(pass_slots) + 3
+    S = (max_groups if isinstance(max_groups, int) else max(max_groups)) * len(pass_slots) + 3
     locals_ = [_random_local(rng, pass_slots, max_groups, runs) for _ in range(world)]
     if world > 1:
         locals_[1] = {s: (np.zeros((0, 3), np.uint32), np.zeros(0, np.uint32), 0) for s in pass_slots}    # an empty rank
