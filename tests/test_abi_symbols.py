@@ -3,6 +3,7 @@ No compute calls here (no GPU)."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 
@@ -63,6 +64,26 @@ def test_product_does_not_import_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), os.path.join(dp, f)
                 assert not re.search(r"#\s*include\s*[<\"][^>\"]*oracle", src), os.path.join(dp, f)
                 assert "libtr_oracle" not in src and "pyoracle" not in src, os.path.join(dp, f)
+
+
+def test_product_does_not_load_the_probe():
+    """lib/libtrhip_probe.so (tests/hip/) is test-only: no product source names it, libtrhip.so neither links nor exports it."""
+    pkg = os.path.join(ROOT, "toyrenderer_amd")
+    for dp, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith((".py", ".cpp", ".h", ".hip")):
+                src = open(os.path.join(dp, f), errors="replace").read()
+                for word in ("libtrhip_probe", "cull_arith_probe", "fp_ref.h", "tests/hip"):
+                    assert word not in src, (os.path.join(dp, f), word)
+    mk = open(os.path.join(pkg, "csrc", "Makefile")).read()
+    link = re.search(r"^\$\(LIBDIR\)/libtrhip\.so:(.*)$", mk, flags=re.M).group(1)
+    assert "PROBE" not in link and "probe" not in link
+    from toyrenderer_amd import rhi
+    lib = rhi.load()
+    for name in ("probe_unary", "probe_filtered", "probe_ref_div"):
+        assert not hasattr(lib, name), name
+    needed = subprocess.run(["readelf", "-d", rhi.LIB_PATH], capture_output=True, text=True).stdout
+    assert "probe" not in needed
 
 
 def test_host_library_exports_every_declared_symbol():

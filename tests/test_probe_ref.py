@@ -1,0 +1,242 @@
+"""The references of the GPU arithmetic probes (tests/hip/fp_ref.h, host copies exported by lib/libtrhip_probe.so)
+against exact rational arithmetic, and how the probe is built.  No GPU."""
+import ctypes as C
+import os
+import random
+import re
+import subprocess
+from decimal import Decimal, getcontext
+from fractions import Fraction
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "toyrenderer_amd", "csrc")
+PROBE_PATH = os.path.join(ROOT, "toyrenderer_amd", "lib", "libtrhip_probe.so")
+
+NAN = 0x7FC00000
+INF = 0x7F800000
+
+
+def _lib():
+    lib = C.CDLL(PROBE_PATH)
+    u32 = C.c_uint32
+    for name in ("probe_ref_sqrt", "probe_ref_rcp", "probe_ref_rsq"):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [u32], u32
+    lib.probe_ref_div.argtypes, lib.probe_ref_div.restype = [u32, u32], u32
+    lib.probe_ref_ulp_dist.argtypes, lib.probe_ref_ulp_dist.restype = [u32, u32], C.c_uint64
+    lib.probe_ref_floor_log2.argtypes, lib.probe_ref_floor_log2.restype = [u32], C.c_int
+    return lib
+
+
+def f32(b):
+    return Fraction(float(np.array([b], np.uint32).view(np.float32)[0]))
+
+
+def is_nan(b):
+    return (b & 0x7FFFFFFF) > INF
+
+
+def rn32(q):
+    """binary32 pattern of RN-even(q) for a non-negative rational q (subnormals and overflow included)."""
+    if q == 0:
+        return 0
+    e = q.numerator.bit_length() - q.denominator.bit_length()
+    if Fraction(2) ** e > q:
+        e -= 1
+    e = max(e, -126)
+    ulp = Fraction(2) ** (e - 23)
+    n, rem = divmod(q, ulp)
+    n = int(n)
+    if rem * 2 > ulp or (rem * 2 == ulp and n & 1):
+        n += 1
+    v = n * ulp
+    if v >= Fraction(2) ** 128:
+        return INF
+    return int(np.array([float(v)], np.float32).view(np.uint32)[0])
+
+
+def rn32_root(x, inverse):
+    """RN(sqrt(x)) or RN(1 / sqrt(x)) of a positive rational x, through a 120-digit decimal (far from any midpoint)."""
+    getcontext().prec = 120
+    d = Decimal(x.numerator) / Decimal(x.denominator)
+    s = d.sqrt()
+    if inverse:
+        s = Decimal(1) / s
+    return rn32(Fraction(s))
+
+
+def signed(sign, b):
+    return (0x80000000 if sign else 0) | b
+
+
+def ref_div(n, d):
+    if is_nan(n) or is_nan(d):
+        return NAN
+    s = (n ^ d) >> 31
+    an, ad = n & 0x7FFFFFFF, d & 0x7FFFFFFF
+    if (an == 0 and ad == 0) or (an == INF and ad == INF):
+        return NAN
+    if an == INF or ad == 0:
+        return signed(s, INF)
+    if an == 0 or ad == INF:
+        return signed(s, 0)
+    return signed(s, rn32(f32(an) / f32(ad)))
+
+
+def ref_rcp(x):
+    return ref_div(0x3F800000, x)
+
+
+def ref_sqrt(x):
+    if is_nan(x):
+        return NAN
+    if x & 0x7FFFFFFF == 0:
+        return x
+    if x >> 31:
+        return NAN
+    if x == INF:
+        return INF
+    return rn32_root(f32(x), False)
+
+
+def ref_rsq(x):
+    if is_nan(x):
+        return NAN
+    if x & 0x7FFFFFFF == 0:
+        return (x & 0x80000000) | INF
+    if x >> 31:
+        return NAN
+    if x == INF:
+        return 0
+    return rn32_root(f32(x), True)
+
+
+def same(got, ref):
+    return is_nan(got) if is_nan(ref) else got == ref
+
+
+def _patterns(rng, n):
+    specials = [0, 0x80000000, 1, 0x80000001, 0x007FFFFF, 0x00800000, 0x3F800000, 0x3F7FFFFF, 0x3F800001, 0x7F7FFFFF,
+                0xFF7FFFFF, INF, 0xFF800000, NAN, 0x7F800001, 0xFFC00000, 0x0F800000, 0x0F7FFFFF, 0x7E800000, 0x7E800001]
+    out = list(specials)
+    while len(out) < n:
+        k = rng.random()
+        if k < 0.6:
+            out.append(rng.getrandbits(32))
+        elif k < 0.8:                                                      # subnormal
+            out.append(rng.getrandbits(23) | (rng.getrandbits(1) << 31))
+        else:                                                              # near 1, exponent edges
+            out.append((rng.choice([0x3F800000, 0x00800000, 0x7F000000, 0x0F800000]) + rng.randint(-3, 3)) & 0xFFFFFFFF)
+    return out
+
+
+def _midpoint_inputs(rng, n, power):
+    """Inputs x with f(x) = x^(-1/power) close to a midpoint m of binary32: x = RN(m^-power) and its neighbours."""
+    out = []
+    for _ in range(n):
+        e = rng.randint(-60, 60)
+        mant = (1 << 24) | rng.getrandbits(23)
+        m = Fraction(2 * mant + 1, 1 << 25) * Fraction(2) ** e               # a midpoint (25 significant bits)
+        x = rn32(1 / m ** power)
+        for k in (-2, -1, 0, 1, 2):
+            out.append((x + k) & 0x7FFFFFFF)
+    return out
+
+
+def test_sqrt_reference_is_correctly_rounded():
+    lib = _lib()
+    rng = random.Random(1)
+    xs = _patterns(rng, 3000)
+    # near-midpoint squares: x = RN(m^2) and neighbours
+    for _ in range(400):
+        mant = (1 << 24) | rng.getrandbits(23)
+        m = Fraction(2 * mant + 1, 1 << 25) * Fraction(2) ** rng.randint(-70, 60)
+        x = rn32(m * m)
+        xs += [(x + k) & 0x7FFFFFFF for k in (-1, 0, 1)]
+    for x in xs:
+        assert same(lib.probe_ref_sqrt(x), ref_sqrt(x)), hex(x)
+    assert lib.probe_ref_sqrt(0x80000000) == 0x80000000               # sqrt(-0) = -0
+    assert lib.probe_ref_sqrt(INF) == INF
+
+
+def test_rcp_reference_is_correctly_rounded_incl_near_midpoints():
+    lib = _lib()
+    rng = random.Random(2)
+    xs = _patterns(rng, 2000) + _midpoint_inputs(rng, 600, 1)
+    xs += [x | 0x80000000 for x in xs[::3]]
+    for x in xs:
+        assert same(lib.probe_ref_rcp(x), ref_rcp(x)), hex(x)
+    assert lib.probe_ref_rcp(0x80000000) == 0xFF800000 and lib.probe_ref_rcp(0xFF800000) == 0x80000000
+
+
+def test_rsq_reference_is_correctly_rounded_incl_near_midpoints():
+    lib = _lib()
+    rng = random.Random(3)
+    xs = _patterns(rng, 2000) + _midpoint_inputs(rng, 600, 2)
+    for x in xs:
+        assert same(lib.probe_ref_rsq(x), ref_rsq(x)), hex(x)
+    assert lib.probe_ref_rsq(0x80000000) == 0xFF800000 and lib.probe_ref_rsq(0) == INF and lib.probe_ref_rsq(INF) == 0
+    assert is_nan(lib.probe_ref_rsq(0xBF800000))
+
+
+def test_div_reference_is_correctly_rounded_incl_exact_ties():
+    lib = _lib()
+    rng = random.Random(4)
+    ps = _patterns(rng, 3000)
+    pairs = list(zip(ps, ps[::-1])) + [(rng.getrandbits(32), rng.getrandbits(32)) for _ in range(2000)]
+    # exact midpoints (subnormal quotients): k 2^-149 / 2^j, k odd -> ties to even
+    pairs += [(k, 0x40000000 + (j << 23)) for k in (1, 3, 5, 7, 0x7FFFFF, 0x12345) for j in range(3)]
+    # overflow boundary: FLT_MAX / (1 - 2^-25 .. ) and 2^127 * 1.99... / 0.5
+    pairs += [(0x7F7FFFFF, 0x3F7FFFFF), (0x7F7FFFFF, 0x3F000000), (0x7F7FFFFF, 0x3F800000), (0x7F7FFFFF, 0x3F7FFFFE)]
+    for n, d in pairs:
+        assert same(lib.probe_ref_div(n, d), ref_div(n, d)), (hex(n), hex(d))
+    assert lib.probe_ref_div(3, 0x40000000) == 2                     # 1.5 * 2^-149 -> 2 * 2^-149 (even)
+    assert lib.probe_ref_div(1, 0x40000000) == 0                     # 0.5 * 2^-149 -> +0 (even)
+    assert lib.probe_ref_div(0x80000001, 0x40000000) == 0x80000000   # -0
+    assert lib.probe_ref_div(0x7F7FFFFF, 0x3F000000) == INF
+
+
+def test_ulp_distance_and_floor_log2():
+    lib = _lib()
+    assert lib.probe_ref_ulp_dist(0x3F800000, 0x3F800001) == 1
+    assert lib.probe_ref_ulp_dist(0, 0x80000000) == 1
+    assert lib.probe_ref_ulp_dist(1, 0x80000001) == 3
+    assert lib.probe_ref_ulp_dist(0x7F7FFFFF, INF) == 1
+    rng = random.Random(5)
+    for _ in range(3000):
+        x = rng.randint(0x3F800000, 0x7F7FFFFF)
+        q = f32(x)
+        e = q.numerator.bit_length() - q.denominator.bit_length()
+        if Fraction(2) ** e > q:
+            e -= 1
+        assert lib.probe_ref_floor_log2(x) == e, hex(x)
+    assert lib.probe_ref_floor_log2(0x3F800000) == 0
+    for k in range(1, 128):
+        p = (k + 127) << 23                                              # 2^k
+        assert lib.probe_ref_floor_log2(p) == k and lib.probe_ref_floor_log2(p - 1) == k - 1, k
+
+
+def test_probe_built_with_the_product_flags():
+    """The probe compiles from the product's Makefile with the same $(CXXFLAGS) as libtrhip.so, as part of `all`."""
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"^all:.*\$\(LIBDIR\)/libtrhip_probe\.so", mk, flags=re.M)
+    out = subprocess.run(["make", "-n", "-B", "-C", CSRC, "../lib/libtrhip_probe.so", "../lib/obj/k_basepass_as.o"],
+                         capture_output=True, text=True, check=True).stdout
+    probe = [ln for ln in out.splitlines() if "cull_arith_probe.hip" in ln]
+    kern = [ln for ln in out.splitlines() if "k_basepass_as.hip" in ln]
+    assert len(probe) == 1 and len(kern) == 1
+    flags = re.search(r"^CXXFLAGS\s*:=\s*(.*)$", mk, flags=re.M).group(1).split()
+    for f in flags:
+        f = f.replace("$(ARCH)", "gfx950")
+        assert f in probe[0].split(), f
+        assert f in kern[0].split(), f
+    for f in ("-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950"):
+        assert f in probe[0].split()
+
+
+def test_probe_exports_every_bound_launcher():
+    from tests.test_gpu_primitives import PROBE_LAUNCHERS
+    lib = C.CDLL(PROBE_PATH)
+    for name in PROBE_LAUNCHERS:
+        assert hasattr(lib, name), name

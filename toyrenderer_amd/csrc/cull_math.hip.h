@@ -54,10 +54,11 @@ __device__ __forceinline__ v2f splat2(float x) { return v2f{ x, x }; }
 
 // Correctly rounded square roots of two values.  For x in [2^-96, FLT_MAX] the 8-operation sequence below
 // (v_rsq_f32, one coupled Newton step on (sqrt, 1/(2 sqrt)), one residual correction; 6 of the 8 packed) returns
-// exactly the IEEE result -- verified EXHAUSTIVELY on gfx950 against the compiler's expansion for all 1 879 048 192
-// floats of that range (tools/sqrt_exhaustive.hip; below 2^-96 it does not hold, which is why the compiler's 16-
-// operation expansion rescales).  Anything outside the range anywhere in the wave (zero, tiny, negative, inf, NaN)
-// sends the whole wave through the compiler's sqrt.
+// exactly the IEEE result -- checked EXHAUSTIVELY on gfx950 against a correctly rounded fp64 reference for all
+// 1 879 048 192 floats of that range, both lanes (tests/test_gpu_primitives.py::test_sqrt_sequence_correctly_rounded_on_its_range;
+// below 2^-96 it does not hold -- the negative control there -- which is why the compiler's 16-operation expansion
+// rescales).  Anything outside the range anywhere in the wave (zero, tiny, negative, inf, NaN) sends the whole wave
+// through the compiler's sqrt (every pattern: test_sqrt2_every_pattern).
 __device__ __forceinline__ v2f sqrt2(v2f x)
 {
 #ifdef TR_EXPERIMENT_FAST_MATH
@@ -337,7 +338,7 @@ __device__ __forceinline__ bool occlusionVisible(F3 c, float r, float nearPlane,
 }
 
 // x / 255.0f for x in [0,255], correctly rounded (== IEEE division; verified exhaustively by
-// tests/test_gpu_primitives.py): one Newton correction of x * RN(1/255).
+// tests/test_gpu_primitives.py::test_byte_decode_all_256): one Newton correction of x * RN(1/255).
 __device__ __forceinline__ float u8Unorm(uint32_t x)
 {
     const float r = 0x1.010102p-8f;          // RN(1/255)
@@ -665,7 +666,7 @@ __device__ __forceinline__ void stepQuotients(lmask active, F3 c, float r, uint3
 // leaves the normal range).  Bx = 1.125 / P00 + 0.25 holds every sphere with 8 r <= c.z that touches the frustum.
 //
 // Error bound (u = 2^-24; rho = |r| / c.z <= 1/8; beta = |c.x| / c.z <= B; lengths in units of c.z; q = the quotient's real
-// value; v_rsq_f32 / v_rcp_f32 within 1 ulp = 2 u):
+// value; v_rsq_f32 / v_rcp_f32 within 1 ulp = 2 u, measured on every normal input by tests/test_gpu_primitives.py):
 //   Z  = fma(cz, cz, -RN(r r)) = Z* (1 + eZ), |eZ| <= (rho^2 / (1 - rho^2) + 1) u <= 1.016 u; Z* >= 63/64
 //   X  = fma(cx, cx, Z)        = X* (1 + eX), |eX| <= 2.016 u                  (both are the REFERENCE's values: shared)
 //   reference:  v = RN(sqrt X) = sqrt(X) (1 + d),  |d| <= u;     fast:  v' = RN(X rsq(X)) = sqrt(X) (1 + d'), |d'| <= 3 u
