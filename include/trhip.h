@@ -32,6 +32,7 @@ typedef struct trhip_buffer_t*  trhip_buffer;
 typedef struct trhip_texture_t* trhip_texture;
 typedef struct trhip_cmdlist_t* trhip_cmdlist;
 typedef struct trhip_timer_t*   trhip_timer;
+typedef struct trhip_pipeline_stats_t* trhip_pipeline_stats;
 
 enum {
     TRHIP_OK = 0,
@@ -127,7 +128,8 @@ int  trhip_texture_upload(trhip_texture tex, uint32_t mip, const void* src, uint
 int  trhip_texture_download(trhip_texture tex, uint32_t mip, void* dst, uint64_t bytes);
 
 /* Contents changed behind the back end's back.  The back end keeps derived, private copies of some bound resources (the
- * instance cull cache, the meshlet cull stream of the buffer bound at t4 of basepass_AS_Main, an HZB's footprint-min table)
+ * instance cull cache, the meshlet cull stream of the buffer bound at t4 of basepass_AS_Main and, once a pipeline statistics
+ * query has covered that pass, its triangle-count bytes, an HZB's footprint-min table)
  * and rebuilds them when the source's version counter moves.  The counter moves for every write the back end SEES:
  * trhip_*_upload, a UAV use in an executed command list, trhip_*_bind_memory.  A write it cannot see -- through the raw
  * pointer of trhip_buffer_wrap / trhip_*_device_ptr (a torch kernel, hipMemcpy), through a second wrap of the same memory,
@@ -200,6 +202,33 @@ int  trhip_queue_execute(trhip_device dev, const trhip_cmdlist* lists, uint32_t 
 int  trhip_timer_create(trhip_device dev, trhip_timer* out);
 void trhip_timer_release(trhip_timer t);
 int  trhip_timer_get_ms(trhip_timer t, float* ms);   /* waits for the end event (getTimerQueryTime) */
+
+/* ---- pipeline statistics queries: nvrhi::PipelineStatisticsQuery (BasePassRenderers.cpp:178-179,202-207,546-549) ------
+ * 14 counters in the field order of D3D12_QUERY_DATA_PIPELINE_STATISTICS1 (112 bytes).  They count what the reference's
+ * pipeline would have invoked for the dispatches recorded between begin and end, not what HIP launched:
+ *   ASInvocations  basepass_AS_Main LATE_CULL=*: 32 x G, G = min(X, validRecords, record capacity) (X read on the device)
+ *   MSInvocations  the same dispatch: 96 (kMeshletShaderThreadGroupSize) x visible meshlets (its draw args word 0)
+ *   MSPrimitives   the same dispatch: sum over its visible meshlets of (m_VertexAndTriangleCount >> 8) & 0xFF
+ *   CSInvocations  groups x the reference entry's [numthreads]: gpuculling_CS_GPUCulling 32 (the late pass is indirect: its
+ *                  groups are read on the device), gpuculling_CS_BuildLateCullIndirectArgs 1, minmaxdownsample_CS_Main 64,
+ *                  ffx_spd_downsample_pass_CS * 256, updateinstanceconsts_* 32, giprobevisualization_* 32
+ *   all others     0: no fixed-function stage is modelled; basepass_MS_Main_depth adds nothing (its mesh work is counted by
+ *                  the AS dispatch that fed it), nor do the back end's own visibility_CS_* shaders.
+ * Begin zeroes the counters when it executes, so a list executed twice yields the same values again.  Begin and end must be
+ * recorded into the same command list, which holds at most one open query (else TRHIP_ERR_STATE; closing a list with a
+ * query open is TRHIP_ERR_STATE too).  With several devices each counts the dispatches of its own lists. */
+typedef struct {
+    uint64_t IAVertices, IAPrimitives, VSInvocations, GSInvocations, GSPrimitives, CInvocations, CPrimitives, PSInvocations,
+             HSInvocations, DSInvocations, CSInvocations, ASInvocations, MSInvocations, MSPrimitives;
+} trhip_pipeline_statistics;
+
+int  trhip_pipeline_stats_create(trhip_device dev, trhip_pipeline_stats* out);   /* createPipelineStatisticsQuery */
+void trhip_pipeline_stats_release(trhip_pipeline_stats q);
+int  trhip_cmd_begin_pipeline_stats(trhip_cmdlist cl, trhip_pipeline_stats q);   /* ::beginPipelineStatisticsQuery */
+int  trhip_cmd_end_pipeline_stats(trhip_cmdlist cl, trhip_pipeline_stats q);     /* ::endPipelineStatisticsQuery   */
+/* getPipelineStatistics: waits for the end of the last executed end; TRHIP_ERR_STATE if the query was never ended in an
+ * executed list. */
+int  trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics* out);
 
 /* ---- per-shader GPU profile: PROFILE_GPU_SCOPED in AddComputePass (Graphic.cpp:899) ----------
  * When enabled, every dispatch executed is bracketed by HIP events on the device stream and

@@ -13,6 +13,8 @@
 
 #include <stdint.h>
 
+#include "trhip.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -78,6 +80,14 @@ int  trhost_hzb_info(uint32_t* width, uint32_t* height, uint32_t* mips);
  * instance -> probe index). */
 int  trhost_load_gi_probes(const float* positions, const float* states, uint32_t num_probes, float probe_radius, int hide_inactive);
 int  trhost_gi_probe_buffers(void** positions, void** draw_args, void** instance_to_probe);
+
+/* Pipeline statistics of the base pass (BasePassRenderers.cpp:178-220,546-549; counters: include/trhip.h).  Off by default;
+ * once on, every frame's RenderBasePass brackets itself with one of two queries and first reads the query of two frames
+ * earlier, as the reference does.  trhost_pipeline_statistics: last_shown = that value of the last frame (the reference's
+ * m_LastPipelineStatistics: frame N - 2, zeros in the first two frames); latest = the last executed frame's own query
+ * (waits for it; zeros if no frame has recorded one).  Either pointer may be NULL.  Per device: each rank counts its own. */
+int  trhost_set_pipeline_statistics(int enable);
+int  trhost_pipeline_statistics(trhip_pipeline_statistics* last_shown, trhip_pipeline_statistics* latest);
 
 int  trhost_frame(void);       /* Graphic::Update: record every pass, submit, (asynchronous)       */
 int  trhost_wait_idle(void);

@@ -1,0 +1,300 @@
+"""Pipeline statistics queries (include/trhip.h trhip_pipeline_stats_*) on the GPU: every counter equals, exactly, what
+tests/pipeline_stats_ref.py derives from the CPU oracle's frame and the scene arrays; and a frame recorded without a query
+is the frame of before (no stats command, the same output words)."""
+import numpy as np
+import pytest
+
+from toyrenderer_amd import synth
+
+from . import pipeline_stats_ref as psr
+from .test_gpu_parity import SMALL, _compare_frame, _oracle_hzb, _upload_hzb
+
+pytestmark = pytest.mark.gpu
+
+VIEW = synth.make_view(eye=(0.5, 0.2, 1.0), yaw=0.03, prev_eye=(0.0, 0.0, 0.0), prev_yaw=0.0, render=(640, 360))
+D_PREV = synth.gen_depth(VIEW, num_occluders=60, seed=11, scale=3.0)
+D_CUR = synth.gen_depth(VIEW, num_occluders=40, seed=12, scale=3.0)
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from toyrenderer_amd import rhi
+    d = rhi.Device(0)
+    yield d
+    d.destroy()
+
+
+def _setup(dev, oracle, spec_or_scene, cap, flags, depth_prev, depth_cur, view=VIEW, **kw):
+    from toyrenderer_amd.frame import FrameDriver, GpuScene
+    scene = synth.make_scene(spec_or_scene) if isinstance(spec_or_scene, synth.SceneSpec) else spec_or_scene
+    gs = GpuScene(dev, scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
+    drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=flags, **kw)
+    hzb = _oracle_hzb(oracle, view, depth_prev)
+    if depth_prev is not None:
+        _upload_hzb(drv, hzb)
+    if depth_cur is not None:
+        drv.depth.upload_mip(0, depth_cur)
+    return scene, gs, drv, hzb
+
+
+def _expected(oracle, scene_dict, view, hzb, depth_cur, cap, flags):
+    ref = oracle.frame(scene_dict, view.as_dict(), hzb, depth_cur, cullingFlags=flags, maxGroups=cap, record_capacity=cap)
+    return ref, psr.frame_stats(ref, scene_dict, flags=flags, record_capacity=cap, hzb_dims=view.hzb_dims)
+
+
+def _case(dev, oracle, spec, cap, flags, depth_prev=D_PREV, depth_cur=D_CUR, view=VIEW):
+    """One frame with a query around the whole list: (stats, expected, ref, profile)."""
+    scene, gs, drv, hzb = _setup(dev, oracle, spec, cap, flags, depth_prev, depth_cur, view)
+    q = dev.create_pipeline_stats()
+    try:
+        dev.profile_reset()
+        dev.profile_enable(True)
+        try:
+            drv.record(q)
+            drv.run()
+            got = drv.results()
+            stats = q.get()
+            prof = dev.profile()
+        finally:
+            dev.profile_enable(False)
+    finally:
+        q.release(); drv.release(); gs.release()
+    ref, want = _expected(oracle, scene.as_oracle(), view, hzb, depth_cur, cap, flags)
+    _compare_frame(got, ref)
+    assert stats == want, {k: (stats[k], want[k]) for k in psr.FIELDS if stats[k] != want[k]}
+    return stats, want, ref, prof
+
+
+@pytest.mark.parametrize("flags", range(8))
+def test_every_culling_flag_combination(dev, oracle, flags):
+    stats, want, ref, prof = _case(dev, oracle, SMALL, 65535, flags)
+    assert all(ref.passRan[s] for s in ((0, 1, 2, 3) if flags & 2 else (0, 2))), "all four slots must run"
+    assert stats["ASInvocations"] > 0 and stats["MSPrimitives"] > 0 and stats["CSInvocations"] > 0
+    assert "basepass_AS_Main LATE_CULL=0#stats" in prof
+
+
+def test_q2_overflow(dev, oracle):
+    spec = synth.SceneSpec(num_meshes=10, num_instances=500, meshlets_lod0=90, jitter_meshlets=True, max_lods=1, seed=77)
+    stats, want, ref, _ = _case(dev, oracle, spec, 257, 1, depth_prev=None, depth_cur=None)
+    assert ref.dispatchArgs[0][0] > 257 and ref.validRecords[0] < 257
+    assert stats["ASInvocations"] == 32 * int(ref.validRecords[0])
+
+
+def test_empty_early_pass(dev, oracle):
+    """HZB near everywhere: the early meshlet pass has no groups (G = 0), the late pass gets every instance."""
+    near = np.ones((VIEW.renderH, VIEW.renderW), np.float32)
+    far = np.zeros((VIEW.renderH, VIEW.renderW), np.float32)
+    spec = synth.SceneSpec(num_meshes=8, num_instances=200, meshlets_lod0=40, max_lods=1, seed=21, z_near=20.0, z_far=60.0,
+                           box_x=4.0, box_y=3.0)
+    stats, want, ref, _ = _case(dev, oracle, spec, 65535, 2, depth_prev=near, depth_cur=far)
+    assert ref.passRan[0] and ref.dispatchArgs[0][0] == 0 and ref.drawArgs[1][0] > 0
+
+
+@pytest.mark.parametrize("cap", [(1 << 19) - 1, 1 << 19])
+def test_both_sides_of_the_list_build_switch(dev, oracle, cap):
+    """2^17 + 1 instances of one group each: an early pass of >= 2^17 entries (footprint-table kernel, deferred mode,
+    tile-ordered processing list) next to a short texel late pass.  Capacity 2^19 - 1: one-launch list build and stats command
+    on the main stream; 2^19: count / scan / expand and the stats command on the side stream."""
+    n = (1 << 17) + 1
+    spec = synth.SceneSpec(num_meshes=16, num_instances=n, meshlets_lod0=32, max_lods=1, seed=n)
+    stats, want, ref, prof = _case(dev, oracle, spec, cap, 7)
+    assert ref.dispatchArgs[0][0] > 0 and ref.dispatchArgs[1][0] > 0
+    ops = {k.split("#", 1)[1] for k in prof if k.startswith("basepass_AS_Main LATE_CULL=0#")}
+    assert "stats" in ops and (("expand" in ops) == (cap >= 1 << 19)), sorted(ops)
+
+
+def _new_triangle_counts(ml, seed):
+    ml2 = ml.copy()
+    rng = np.random.default_rng(seed)
+    nt = rng.integers(1, 200, len(ml2)).astype(np.uint32)
+    ml2["m_VertexAndTriangleCount"] = (ml2["m_VertexAndTriangleCount"] & np.uint32(0xFFFF00FF)) | (nt << 8)
+    return ml2
+
+
+@pytest.mark.parametrize("how", ["upload", "out_of_band"])
+def test_meshlet_buffer_rewritten_between_frames(dev, oracle, how):
+    """The byte array of triangle counts follows the meshlet buffer's version: an upload, or a write through a second
+    handle on the same memory followed by trhip_buffer_mark_written, must change MSPrimitives in the next frame."""
+    scene, gs, drv, hzb = _setup(dev, oracle, SMALL, 65535, 7, D_PREV, D_CUR)
+    q = dev.create_pipeline_stats()
+    alias = None
+    try:
+        drv.record(q); drv.run(); drv.results()
+        s1 = q.get()
+        _, w1 = _expected(oracle, scene.as_oracle(), VIEW, hzb, D_CUR, 65535, 7)
+        assert s1 == w1
+        ml2 = _new_triangle_counts(scene.meshlets, 3)
+        if how == "upload":
+            gs.meshlets.upload(ml2)
+        else:
+            alias = dev.wrap_buffer(gs.meshlets.ptr, ml2.nbytes, name="meshlets alias", stride=32)
+            alias.upload(ml2)
+            gs.meshlets.mark_written()
+        scene2 = scene.as_oracle(); scene2["meshlets"] = ml2
+        hzb2 = _oracle_hzb(oracle, VIEW, D_CUR)
+        drv.record(q); drv.run(); drv.results()
+        s2 = q.get()
+        _, w2 = _expected(oracle, scene2, VIEW, hzb2, D_CUR, 65535, 7)
+        assert s2 == w2
+        assert s2["MSPrimitives"] != s1["MSPrimitives"]
+    finally:
+        if alias is not None:
+            alias.release()
+        q.release(); drv.release(); gs.release()
+
+
+def test_list_executed_twice_gives_equal_values(dev, oracle):
+    """Begin zeroes the counters when it executes: the second execution reports the same values, not twice them.  The
+    frozen culling camera keeps the HZB, so both executions compute the same frame."""
+    scene, gs, drv, hzb = _setup(dev, oracle, SMALL, 1 << 19, 7, D_PREV, D_CUR, freeze_culling_camera=True)
+    q = dev.create_pipeline_stats()
+    try:
+        drv.record(q)
+        drv.run()
+        s1 = q.get()
+        drv.run()
+        s2 = q.get()
+        assert s1 == s2 and s1["ASInvocations"] > 0
+        ref = oracle.frame(scene.as_oracle(), VIEW.as_dict(), hzb, D_CUR, cullingFlags=7, freeze=True, maxGroups=1 << 19,
+                           record_capacity=1 << 19)
+        assert s1 == psr.frame_stats(ref, scene.as_oracle(), flags=7, record_capacity=1 << 19, hzb_dims=VIEW.hzb_dims, freeze=True)
+    finally:
+        q.release(); drv.release(); gs.release()
+
+
+def test_begin_end_misuse_is_a_state_error(dev):
+    from toyrenderer_amd import rhi
+    L = rhi.load()
+    TRHIP_ERR_STATE = -4
+    q1, q2 = dev.create_pipeline_stats(), dev.create_pipeline_stats()
+    a, b = dev.create_command_list(), dev.create_command_list()
+    try:
+        v = rhi.PipelineStatistics()
+        assert L.trhip_pipeline_stats_get(q1.h, v) == TRHIP_ERR_STATE          # never executed
+        a.open(); b.open()
+        assert L.trhip_cmd_end_pipeline_stats(a.h, q1.h) == TRHIP_ERR_STATE    # end without begin
+        a.begin_pipeline_stats(q1)
+        assert L.trhip_cmd_begin_pipeline_stats(a.h, q2.h) == TRHIP_ERR_STATE  # a second open query in one list
+        assert L.trhip_cmd_begin_pipeline_stats(a.h, q1.h) == TRHIP_ERR_STATE
+        assert L.trhip_cmd_end_pipeline_stats(a.h, q2.h) == TRHIP_ERR_STATE    # not the open one
+        assert L.trhip_cmd_end_pipeline_stats(b.h, q1.h) == TRHIP_ERR_STATE    # begun in another list
+        assert L.trhip_cmd_close(a.h) == TRHIP_ERR_STATE                       # closed with the query open
+        a.end_pipeline_stats(q1)
+        a.close(); b.close()
+        assert L.trhip_pipeline_stats_get(q1.h, v) == TRHIP_ERR_STATE          # recorded, not executed
+        dev.execute(a)
+        assert q1.get() == psr.zeros()                                         # an empty bracket counts nothing
+    finally:
+        a.release(); b.release(); q1.release(); q2.release()
+
+
+def test_raster_depth_changes_no_counter(dev, oracle, tmp_path):
+    """basepass_MS_Main_depth adds nothing (its mesh work is the AS dispatch's), and the depth it rasterises is bit-identical
+    with and without a query."""
+    from .scene_gen import write_city_gltf
+    from toyrenderer_amd import gltf_lite
+    from toyrenderer_amd import interop as I
+    from toyrenderer_amd.frame import FrameDriver, GpuScene
+    s = gltf_lite.load(write_city_gltf(tmp_path))
+    inst = s.instances.copy()
+    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
+    sc = dict(s.as_oracle()); sc["instances"] = inst
+    cam = s.cameras[0]
+    render = (1280, 720)
+    P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
+    V = synth.world_to_view((0.2, 0.0, -0.2), cam.orientation)
+    view = synth.View(V, V.copy(), P, float(np.float32(cam.znear)), *render)
+    depths, stats = [], None
+    for with_query in (True, False):
+        gs = GpuScene(dev, inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
+        gs.set_geometry(s.vertices, s.meshletVertexIds, s.meshletTriangles)
+        drv = FrameDriver(dev, gs, view, record_capacity=4096, culling_flags=7, raster_depth=True)
+        q = dev.create_pipeline_stats() if with_query else None
+        try:
+            drv.record(q); drv.run(); drv.results()
+            depths.append(drv.depth.download_mip(0).view(np.uint32).copy())
+            if q is not None:
+                stats = q.get()
+        finally:
+            if q is not None:
+                q.release()
+            drv.release(); gs.release()
+    assert np.array_equal(depths[0], depths[1]), "depth differs with a query"
+    hzb = oracle.HzbTexture(*view.hzb_dims)
+    depth = np.zeros((render[1], render[0]), np.float32)
+    geo = (I.world_to_clip(V, P), s.vertices, s.meshletVertexIds, s.meshletTriangles)
+    ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=7, record_capacity=4096, raster=geo)
+    assert np.array_equal(depth.view(np.uint32), depths[0])
+    assert stats == psr.frame_stats(ref, sc, flags=7, record_capacity=4096, hzb_dims=view.hzb_dims)
+    assert stats["MSPrimitives"] > 0
+
+
+@pytest.mark.parametrize("cap", [65535, 1 << 19])
+def test_statistics_off_records_todays_list(dev, oracle, cap):
+    """Without a query no stats command is recorded, and every slot's outputs are word for word those of the run with one."""
+    outs = []
+    for with_query in (False, True):
+        scene, gs, drv, hzb = _setup(dev, oracle, SMALL, cap, 7, D_PREV, D_CUR)
+        q = dev.create_pipeline_stats() if with_query else None
+        try:
+            dev.profile_reset()
+            dev.profile_enable(True)
+            try:
+                drv.record(q); drv.run()
+                got = drv.results()
+                prof = dev.profile()
+            finally:
+                dev.profile_enable(False)
+            outs.append(got)
+            stats_ops = [k for k in prof if k.endswith("#stats")]
+            assert bool(stats_ops) == with_query, stats_ops
+        finally:
+            if q is not None:
+                q.release()
+            drv.release(); gs.release()
+    for s in range(4):
+        a, b = outs[0][s], outs[1][s]
+        assert (a is None) == (b is None)
+        if a is None:
+            continue
+        for k in ("dispatchArgs", "records", "visMask", "visibleList", "drawArgs"):
+            assert np.array_equal(np.asarray(a[k]).view(np.uint8), np.asarray(b[k]).view(np.uint8)), (s, k)
+        assert a["validRecords"] == b["validRecords"]
+    assert outs[0]["lateCount"] == outs[1]["lateCount"]
+
+
+def test_host_path_reads_the_query_of_two_frames_earlier(oracle):
+    """BasePassRenderer through the host mirror, statistics on, four frames of a moving camera: after frame N the value the
+    frame showed (the reference's m_LastPipelineStatistics) is frame N - 2's (zeros for frames 0 and 1) and the latest is frame
+    N's own."""
+    from toyrenderer_amd import host
+    scene = synth.make_scene(SMALL)
+    d_prev = synth.gen_depth(VIEW, num_occluders=60, seed=11, scale=3.0)
+    d_cur = synth.gen_depth(VIEW, num_occluders=40, seed=12, scale=3.0)
+    hzb = oracle.HzbTexture(*VIEW.hzb_dims)
+    hzb.build_from_depth(d_prev)
+    r = host.Renderer(render=(640, 360))
+    try:
+        r.load_scene(scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
+        r.set_culling(7)
+        r.upload_hzb(hzb.texels, hzb.offsets)
+        r.upload_depth(d_cur)
+        r.set_pipeline_statistics(True)
+        want = []
+        prev = (0.0, 0.0, 0.0)
+        for f in range(4):
+            eye = (0.5 - 0.1 * f, 0.2, 1.0 + 0.2 * f)
+            view = synth.make_view(eye=eye, yaw=0.03 * f, prev_eye=prev, prev_yaw=0.03 * max(f - 1, 0), render=(640, 360))
+            prev = eye
+            r.set_camera(view)
+            r.frame()
+            got = r.results()
+            ref, w = _expected(oracle, scene.as_oracle(), view, hzb, d_cur, 65535, 7)
+            _compare_frame(got, ref)
+            want.append(w)
+            shown, latest = r.pipeline_statistics()
+            assert shown == (want[f - 2] if f >= 2 else psr.zeros()), f
+            assert latest == w, f
+        assert want[0] != want[3]
+    finally:
+        r.shutdown()

@@ -170,6 +170,9 @@ protected:
     RenderGraph::ResourceHandle m_VisibleMeshletListBufferRDGBufferHandle[kNumPassSlots];
     RenderGraph::ResourceHandle m_VisibleMeshletDrawArgsBufferRDGBufferHandle[kNumPassSlots];
 
+    nvrhi::PipelineStatisticsQueryHandle m_PipelineStatisticsQuery[2];       // :178-179
+    nvrhi::PipelineStatistics m_LastPipelineStatistics;
+
     bool m_DoFrustumCulling = true;
     bool m_bDoOcclusionCulling = true;
     bool m_bDoMeshletConeCulling = true;
@@ -463,8 +466,52 @@ public:
         m_SPDHelper.Execute(commandList, renderGraph, depthStencilBuffer, g_Scene->m_HZB, reductionType);
     }
 
+    // the last frame's query, read back now (trhost_pipeline_statistics); m_LastPipelineStatistics is the one shown (N - 2)
+    nvrhi::PipelineStatistics LatestPipelineStatistics() const
+    {
+        return g_Graphic.m_NVRHIDevice->getPipelineStatistics(m_PipelineStatisticsQuery[g_Graphic.m_FrameCounter % 2]);
+    }
+    const nvrhi::PipelineStatistics& LastPipelineStatistics() const { return m_LastPipelineStatistics; }
+    void ReleasePipelineStatisticsQueries()                                  // before the device goes (trhost_shutdown)
+    {
+        m_PipelineStatisticsQuery[0] = nullptr; m_PipelineStatisticsQuery[1] = nullptr;
+        m_LastPipelineStatistics = nvrhi::PipelineStatistics{};
+    }
+    std::string m_ImguiText;                                                  // what UpdateImgui would draw (there is no ImGui here)
+
+    void Initialize() override
+    {
+        for (uint32_t i = 0; i < 2; ++i)                                      // :202-207
+        {
+            m_PipelineStatisticsQuery[i] = g_Graphic.m_NVRHIDevice->createPipelineStatisticsQuery();
+        }
+    }
+
+    bool HasImguiControls() const override { return true; }
+
+    void UpdateImgui() override                                              // :210-220, as text
+    {
+        char buf[512];
+        snprintf(buf, sizeof buf,
+                 "Primitives Invocations: %llu\nPrimitives Primitives: %llu\nPS Invocations: %llu\nCS Invocations: %llu\n"
+                 "AS Invocations: %llu\nMS Invocations: %llu\nMS Primitives: %llu\n",
+                 (unsigned long long)m_LastPipelineStatistics.CInvocations, (unsigned long long)m_LastPipelineStatistics.CPrimitives,
+                 (unsigned long long)m_LastPipelineStatistics.PSInvocations, (unsigned long long)m_LastPipelineStatistics.CSInvocations,
+                 (unsigned long long)m_LastPipelineStatistics.ASInvocations, (unsigned long long)m_LastPipelineStatistics.MSInvocations,
+                 (unsigned long long)m_LastPipelineStatistics.MSPrimitives);
+        m_ImguiText = buf;
+    }
+
     void RenderBasePass(nvrhi::CommandListHandle commandList, const RenderGraph& renderGraph, const RenderBasePassParams& params)
     {
+        nvrhi::DeviceHandle device = g_Graphic.m_NVRHIDevice;
+
+        // :546-549.  Deviation: the queries are recorded only once trhost_set_pipeline_statistics(1) has switched them on
+        // (off by default: the frame is then exactly the frame without them).
+        const bool stats = g_Graphic.m_bPipelineStatistics;
+        if (stats) m_LastPipelineStatistics = device->getPipelineStatistics(m_PipelineStatisticsQuery[g_Graphic.m_FrameCounter % 2]);
+        AUTO_SCOPE([&]{ if (stats) commandList->beginPipelineStatisticsQuery(m_PipelineStatisticsQuery[g_Graphic.m_FrameCounter % 2]); }, [&]{ if (stats) commandList->endPipelineStatisticsQuery(m_PipelineStatisticsQuery[g_Graphic.m_FrameCounter % 2]); });
+
         for (PassOutputs& o : m_Outputs) o = PassOutputs{};
 
         m_CullingFlags = m_DoFrustumCulling ? kCullingFlagFrustumCullingEnable : 0;                 // :551-553
@@ -517,6 +564,7 @@ public:
 
     void Initialize() override
     {
+        BasePassRenderer::Initialize();
         nvrhi::TextureDesc desc;                                              // :600-610
         desc.width = GetNextPow2(g_Graphic.m_RenderResolution.x) >> 1;
         desc.height = GetNextPow2(g_Graphic.m_RenderResolution.y) >> 1;
@@ -587,6 +635,13 @@ bool GetVisibilityPassBuffers(uint32_t slot, VisibilityPassBuffers* out)
     return true;
 }
 
+void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest)
+{
+    GBufferRenderer* r = static_cast<GBufferRenderer*>(g_GBufferRenderer);
+    if (lastShown) *lastShown = r->LastPipelineStatistics();
+    if (latest) *latest = r->LatestPipelineStatistics();
+}
+
 nvrhi::TextureHandle GetLastDepthBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_LastDepthBuffer; }
 
 void ReleaseVisibilityPassBuffers()
@@ -596,6 +651,7 @@ void ReleaseVisibilityPassBuffers()
     r->m_LastLateCullInstanceCountBuffer = nullptr;
     r->m_LastLateCullDispatchIndirectArgsBuffer = nullptr;
     r->m_CurrentDepthBuffer = nullptr; r->m_LastDepthBuffer = nullptr;
+    r->ReleasePipelineStatisticsQueries();
     for (ShardLateCall& c : g_ShardLateCalls) c = ShardLateCall{};
     SetShardLateExchange(nullptr, nullptr);
 }

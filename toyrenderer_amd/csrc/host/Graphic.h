@@ -95,6 +95,7 @@ public:
     Vector2U m_RenderResolution{ 0, 0 };
     uint32_t m_FrameCounter = 0;
     int m_DeviceIndex = 0;
+    bool m_bPipelineStatistics = false;                                       // the base pass's statistics queries (trhost_set_pipeline_statistics); off by default
     bool m_bEnableGPUTimers = true;                                          // per-renderer timer queries (RenderGraph.cpp:262-281); instrumentation only
     float m_LastRecordMs = 0.f, m_LastSubmitMs = 0.f;                      // host time of the last Update(): recording, submission
     // this build: capacity of the amplification-record buffer.  The reference hard-codes
@@ -177,6 +178,10 @@ constexpr uint32_t ComputeNbMips(uint32_t width, uint32_t height)
 // times come from the back end's profile, trhip_profile_*)
 #define PROFILE_GPU_SCOPED(cmdList, NAME) nvrhi::utils::ScopedMarker TR_CONCAT(scopedMarker_, __LINE__){ cmdList, NAME }
 #define PROFILE_FUNCTION()
+// PCH.h AUTO_SCOPE: onEnter() now, onExit() when the enclosing scope ends
+template <typename F> struct ScopeExit { F f; ~ScopeExit() { f(); } };
+template <typename F> ScopeExit<F> MakeScopeExit(F f) { return ScopeExit<F>{ f }; }
+#define AUTO_SCOPE(onEnter, onExit) auto TR_CONCAT(autoScope_, __LINE__) = ((onEnter)(), MakeScopeExit(onExit))
 #define SCOPED_COMMAND_LIST(commandList, NAME) \
     ScopedCommandList TR_CONCAT(scopedCommandList_, __LINE__){ commandList, NAME, false, false }
 #define SCOPED_COMMAND_LIST_AUTO_QUEUE(commandList, NAME) \

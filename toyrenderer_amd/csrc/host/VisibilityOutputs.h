@@ -35,6 +35,8 @@ void ReleaseGIProbeCullBuffers();
 
 // Depth attachment of the last recorded base pass (read-back for tests; null before the first frame).
 nvrhi::TextureHandle GetLastDepthBuffer();
+// the base pass's pipeline statistics: the value its frame N showed (the query of frame N - 2) and the last executed frame's (waits)
+void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest);
 
 // Native per-frame driver of the multi-GPU exchange (ShardExchange.cpp; C facade in trhost.h).
 struct trhost_exchange_desc;

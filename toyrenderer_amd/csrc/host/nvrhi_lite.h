@@ -228,11 +228,33 @@ private:
     trhip_timer m_Native;
 };
 
+// nvrhi::PipelineStatistics: the fields of D3D12_QUERY_DATA_PIPELINE_STATISTICS1, laid out as trhip_pipeline_statistics
+struct PipelineStatistics
+{
+    uint64_t IAVertices = 0, IAPrimitives = 0, VSInvocations = 0, GSInvocations = 0, GSPrimitives = 0, CInvocations = 0,
+             CPrimitives = 0, PSInvocations = 0, HSInvocations = 0, DSInvocations = 0, CSInvocations = 0, ASInvocations = 0,
+             MSInvocations = 0, MSPrimitives = 0;
+};
+static_assert(sizeof(PipelineStatistics) == sizeof(trhip_pipeline_statistics), "PipelineStatistics layout");
+
+class IPipelineStatisticsQuery : public IResource
+{
+public:
+    explicit IPipelineStatisticsQuery(trhip_pipeline_stats q) : m_Native(q) {}
+    ~IPipelineStatisticsQuery() override { trhip_pipeline_stats_release(m_Native); }
+    trhip_pipeline_stats native() const { return m_Native; }
+    bool m_Recorded = false;
+
+private:
+    trhip_pipeline_stats m_Native;
+};
+
 using HeapHandle = RefCountPtr<IHeap>;
 using BufferHandle = RefCountPtr<IBuffer>;
 using TextureHandle = RefCountPtr<ITexture>;
 using SamplerHandle = RefCountPtr<ISampler>;
 using TimerQueryHandle = RefCountPtr<ITimerQuery>;
+using PipelineStatisticsQueryHandle = RefCountPtr<IPipelineStatisticsQuery>;
 
 // ---- binding sets (Graphic.cpp:488-518; items used: BasePassRenderers.cpp:351-362,463-479,521-526) ---
 struct BindingSetItem
@@ -325,6 +347,8 @@ public:
     }
     void beginTimerQuery(ITimerQuery* q) { keep(q); throwIfFailed(trhip_cmd_begin_timer(m_Native, q->native()), "ICommandList::beginTimerQuery"); }
     void endTimerQuery(ITimerQuery* q) { q->m_Recorded = true; throwIfFailed(trhip_cmd_end_timer(m_Native, q->native()), "ICommandList::endTimerQuery"); }
+    void beginPipelineStatisticsQuery(IPipelineStatisticsQuery* q) { keep(q); throwIfFailed(trhip_cmd_begin_pipeline_stats(m_Native, q->native()), "ICommandList::beginPipelineStatisticsQuery"); }
+    void endPipelineStatisticsQuery(IPipelineStatisticsQuery* q) { q->m_Recorded = true; throwIfFailed(trhip_cmd_end_pipeline_stats(m_Native, q->native()), "ICommandList::endPipelineStatisticsQuery"); }
     void beginMarker(const char* name) { throwIfFailed(trhip_cmd_begin_marker(m_Native, name), "ICommandList::beginMarker"); }
     void endMarker() { throwIfFailed(trhip_cmd_end_marker(m_Native), "ICommandList::endMarker"); }
 
@@ -478,6 +502,19 @@ public:
         return ms * 1e-3f;
     }
     void resetTimerQuery(ITimerQuery* q) { if (q) q->m_Recorded = false; }
+    PipelineStatisticsQueryHandle createPipelineStatisticsQuery()
+    {
+        trhip_pipeline_stats q = nullptr;
+        throwIfFailed(trhip_pipeline_stats_create(m_Native, &q), "IDevice::createPipelineStatisticsQuery");
+        return PipelineStatisticsQueryHandle(new IPipelineStatisticsQuery(q));
+    }
+    PipelineStatistics getPipelineStatistics(IPipelineStatisticsQuery* q)   // waits; zeros for a query not yet ended in an executed list
+    {
+        PipelineStatistics s;
+        if (!q || !q->m_Recorded) return s;
+        if (trhip_pipeline_stats_get(q->native(), reinterpret_cast<trhip_pipeline_statistics*>(&s)) != TRHIP_OK) return PipelineStatistics{};
+        return s;
+    }
 
 private:
     static constexpr size_t kQueueEvents = 16;

@@ -157,6 +157,21 @@ int trhost_set_culling(int frustum, int occlusion, int cone, int freeze_culling_
     });
 }
 
+int trhost_set_pipeline_statistics(int enable)
+{
+    return guarded([&] { g_Graphic.m_bPipelineStatistics = enable != 0; });
+}
+
+int trhost_pipeline_statistics(trhip_pipeline_statistics* last_shown, trhip_pipeline_statistics* latest)
+{
+    return guarded([&] {
+        nvrhi::PipelineStatistics a, b;
+        GetBasePassPipelineStatistics(last_shown ? &a : nullptr, latest ? &b : nullptr);
+        if (last_shown) memcpy(last_shown, &a, sizeof *last_shown);
+        if (latest) memcpy(latest, &b, sizeof *latest);
+    });
+}
+
 int trhost_set_gpu_timers(int enable)
 {
     return guarded([&] { g_Graphic.m_bEnableGPUTimers = enable != 0; });

@@ -1647,6 +1647,8 @@ int recordASMain(trhip::DispatchCtx& ctx)
     // when the list build is long (>= 2^19 groups of capacity), not for small passes.
     ctx.cl->flushHeldSide();                            // (the early pass's held list expansion goes in front of this pass's list build)
     emitListBuild(ctx, a, "", a.recordCapacity >= (1u << 19), ctx.argsBuffer->ptr);
+    if (ctx.cl->openStats)                              // a pipeline statistics query is open: this pass's AS / MS counts, beside the list build
+        return trhip::statsEmitAS(ctx, a, meshlets, records, instances, meshData, a.recordCapacity >= (1u << 19));
     return TRHIP_OK;
 }
 

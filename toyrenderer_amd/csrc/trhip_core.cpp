@@ -195,6 +195,8 @@ void trhip_cmdlist_t::resetRecording()
     heldBuffers.clear();
     heldTextures.clear();
     markers.clear();
+    openStats = nullptr;
+    statsHostCS = 0;
     useMarks.clear();
     openClearBatch.reset();
     openClearOp = SIZE_MAX;
@@ -455,6 +457,7 @@ void trhip_buffer_release(trhip_buffer b)
         if (b->sidecar) { (void)hipSetDevice(b->dev->index); (void)hipFree(b->sidecar); }
         if (b->cullCache) { (void)hipSetDevice(b->dev->index); (void)b->dev->syncAll(); (void)hipFree(b->cullCache); }
         if (b->cullStream) { (void)hipSetDevice(b->dev->index); (void)b->dev->syncAll(); (void)hipFree(b->cullStream); }
+        if (b->triCounts) { (void)hipSetDevice(b->dev->index); (void)b->dev->syncAll(); (void)hipFree(b->triCounts); }
         if (b->heap) trhip_heap_release(b->heap);
         delete b;
     }
@@ -633,6 +636,7 @@ int trhip_cmd_close(trhip_cmdlist cl)
     if (!cl) return fail(TRHIP_ERR_INVALID, "cmdlist is null");
     if (!cl->open) return fail(TRHIP_ERR_STATE, "cmd_close: not open");
     if (!cl->markers.empty()) return fail(TRHIP_ERR_STATE, "cmd_close: %zu marker(s) still open", cl->markers.size());
+    if (cl->openStats) return fail(TRHIP_ERR_STATE, "cmd_close: a pipeline statistics query is still open");
     cl->flushHeldSide();
     cl->open = false;
     // by command index (a clear merged into an earlier launch is noted against that launch)
@@ -800,7 +804,13 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
         }
     }
     DispatchCtx ctx{ cl, e->name.c_str(), e->variant, b, nb, push, pushBytes, indirect, args, argsOff, gx, gy, gz };
-    return e->fn(ctx);
+    int rc = e->fn(ctx);
+    if (rc != TRHIP_OK || !cl->openStats) return rc;
+    // an open pipeline statistics query: CS invocations of this dispatch (basepass_AS_Main counts its own, recordASMain)
+    const uint32_t threads = statsCSThreads(name);
+    if (!threads) return TRHIP_OK;
+    if (!indirect) { cl->statsHostCS += (uint64_t)gx * gy * gz * threads; return TRHIP_OK; }
+    return statsEmitIndirectCS(cl, args, argsOff, threads);
 }
 
 int trhip_cmd_dispatch(trhip_cmdlist cl, const char* name, const trhip_binding* b, uint32_t nb, const void* push, uint32_t pushBytes,
@@ -830,6 +840,46 @@ int trhip_cmd_end_timer(trhip_cmdlist cl, trhip_timer t)
     if (!t) return fail(TRHIP_ERR_INVALID, "timer is null");
     cl->ops.push_back({ "", [t](hipStream_t s) { TRHIP_HIP(hipEventRecord(t->e1, s)); t->ended = true; return (int)TRHIP_OK; } });
     cl->ops.back().kind = "timer";
+    return TRHIP_OK;
+}
+
+int trhip_cmd_begin_pipeline_stats(trhip_cmdlist cl, trhip_pipeline_stats q)
+{
+    TRHIP_RECORDING(cl);
+    if (!q) return fail(TRHIP_ERR_INVALID, "pipeline statistics query is null");
+    if (q->dev != cl->dev) return fail(TRHIP_ERR_INVALID, "begin_pipeline_stats: the query belongs to another device");
+    if (cl->openStats) return fail(TRHIP_ERR_STATE, "begin_pipeline_stats: this command list already has a query open");
+    cl->openStats = q;
+    cl->statsHostCS = 0;
+    cl->peephole = trhip_cmdlist_t::Peephole();
+    cl->use(q->counters, cl->ops.size(), true);        // after the side-stream work of an earlier execution that added to it
+    cl->ops.push_back({ "", [q](hipStream_t s) {
+        TRHIP_HIP(hipMemsetAsync(q->counters, 0, sizeof(trhip_pipeline_statistics), s));
+        q->began = true; q->ended = false;
+        return (int)TRHIP_OK; } });
+    cl->ops.back().kind = "pipeline_stats";
+    return TRHIP_OK;
+}
+
+int trhip_cmd_end_pipeline_stats(trhip_cmdlist cl, trhip_pipeline_stats q)
+{
+    TRHIP_RECORDING(cl);
+    if (!q) return fail(TRHIP_ERR_INVALID, "pipeline statistics query is null");
+    if (cl->openStats != q) return fail(TRHIP_ERR_STATE, "end_pipeline_stats: the query is not open in this command list");
+    const uint64_t hostCS = cl->statsHostCS;
+    cl->openStats = nullptr;
+    cl->statsHostCS = 0;
+    cl->peephole = trhip_cmdlist_t::Peephole();
+    cl->use(q->counters, cl->ops.size(), true);        // after the side-stream stats commands of this recording: the event covers them
+    cl->ops.push_back({ "", [q, hostCS](hipStream_t s) {
+        if (hostCS) {
+            int rc = statsLaunchAdd(q->counters + kStatCS, hostCS, s);
+            if (rc != TRHIP_OK) return rc;
+        }
+        TRHIP_HIP(hipEventRecord(q->done, s));
+        q->ended = true;
+        return (int)TRHIP_OK; } });
+    cl->ops.back().kind = "pipeline_stats";
     return TRHIP_OK;
 }
 
@@ -1029,6 +1079,40 @@ int trhip_timer_get_ms(trhip_timer t, float* ms)
     if (!t->began || !t->ended) return fail(TRHIP_ERR_STATE, "timer_get_ms: timer was not begun and ended in an executed list");
     TRHIP_HIP(hipEventSynchronize(t->e1));
     TRHIP_HIP(hipEventElapsedTime(ms, t->e0, t->e1));
+    return TRHIP_OK;
+}
+
+// ---- pipeline statistics queries ------------------------------------------------------------------
+int trhip_pipeline_stats_create(trhip_device dev, trhip_pipeline_stats* out)
+{
+    if (!dev || !out) return fail(TRHIP_ERR_INVALID, "pipeline_stats_create: null argument");
+    TRHIP_HIP(hipSetDevice(dev->index));
+    auto q = std::make_unique<trhip_pipeline_stats_t>();
+    q->dev = dev;
+    TRHIP_HIP(hipMalloc(&q->counters, sizeof(trhip_pipeline_statistics)));
+    TRHIP_HIP(hipMemset(q->counters, 0, sizeof(trhip_pipeline_statistics)));
+    TRHIP_HIP(hipEventCreateWithFlags(&q->done, hipEventDisableTiming));
+    *out = q.release();
+    return TRHIP_OK;
+}
+
+void trhip_pipeline_stats_release(trhip_pipeline_stats q)
+{
+    if (!q) return;
+    (void)hipSetDevice(q->dev->index);
+    (void)q->dev->syncAll();                     // executed lists may still add to it
+    (void)hipFree(q->counters);
+    (void)hipEventDestroy(q->done);
+    delete q;
+}
+
+int trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics* out)
+{
+    if (!q || !out) return fail(TRHIP_ERR_INVALID, "pipeline_stats_get: null argument");
+    if (!q->began || !q->ended) return fail(TRHIP_ERR_STATE, "pipeline_stats_get: query was not begun and ended in an executed list");
+    TRHIP_HIP(hipSetDevice(q->dev->index));
+    TRHIP_HIP(hipEventSynchronize(q->done));
+    TRHIP_HIP(hipMemcpy(out, q->counters, sizeof(trhip_pipeline_statistics), hipMemcpyDeviceToHost));
     return TRHIP_OK;
 }
 

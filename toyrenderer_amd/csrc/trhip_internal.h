@@ -120,6 +120,12 @@ struct trhip_buffer_t
     void* cullStream = nullptr;
     uint64_t cullStreamBytes = 0;
     uint64_t cullStreamVersion = 0;
+    // Meshlet buffers only, and only once a pipeline statistics query has covered a basepass_AS_Main dispatch: the TRIANGLE
+    // COUNTS, one byte per meshlet ((m_VertexAndTriangleCount >> 8) & 0xFF, k_pipeline_stats.hip).  Kept exactly like the cull
+    // stream: rebuilt when the buffer's version moves.
+    void* triCounts = nullptr;
+    uint64_t triCountsBytes = 0;
+    uint64_t triCountsVersion = 0;
     std::atomic<int> rc{1};
 };
 
@@ -159,8 +165,23 @@ struct trhip_timer_t
     bool began = false, ended = false;
 };
 
+struct MeshletCullArgs;                           // meshlet_exact.hip.h
+
+// A pipeline statistics query (include/trhip.h): trhip_pipeline_statistics on the device, zeroed by the begin command and
+// added to by the commands recorded up to the end command, whose completion `done` marks.
+struct trhip_pipeline_stats_t
+{
+    trhip_device_t* dev = nullptr;
+    unsigned long long* counters = nullptr;      // device: 14 x u64 in the order of trhip_pipeline_statistics
+    hipEvent_t done = nullptr;
+    bool began = false, ended = false;
+};
+
 namespace trhip
 {
+
+// Indices into trhip_pipeline_statistics (the counters a dispatch can move).
+enum : uint32_t { kStatCS = 10, kStatAS = 11, kStatMS = 12, kStatMSPrim = 13, kStatWords = 14 };
 
 struct Op
 {
@@ -182,6 +203,10 @@ struct trhip_cmdlist_t
     std::vector<trhip_buffer_t*> heldBuffers;
     std::vector<trhip_texture_t*> heldTextures;
     std::vector<std::string> markers;
+    // The pipeline statistics query open in this recording (nullptr: none) and the CS invocations of its direct dispatches,
+    // known on the host and added once by the end command.
+    trhip_pipeline_stats_t* openStats = nullptr;
+    uint64_t statsHostCS = 0;
 
     struct ScratchBlock { void* ptr; size_t bytes; size_t used; };
     std::vector<ScratchBlock> scratch;
@@ -312,6 +337,16 @@ inline uint32_t tableMinGroups()
     static const uint32_t v = [] { const char* e = getenv("TRHIP_TABLE_MIN_GROUPS"); return e ? (uint32_t)strtoul(e, nullptr, 0) : (1u << 17); }();
     return v;
 }
+
+// Pipeline statistics (k_pipeline_stats.hip).  csThreads: the [numthreads] product of the reference entry behind a shader name
+// that counts as CSInvocations (0: none).  emitIndirectCS: a command that adds groups(args) x threads to the open query.
+// emitAS: the command that adds a basepass_AS_Main pass's AS / MS invocations and MS primitives to the open query, behind
+// its cull (on the side stream when `side`, beside the list build).
+uint32_t statsCSThreads(const char* shaderName);
+int statsLaunchAdd(unsigned long long* counter, uint64_t value, hipStream_t s);
+int statsEmitIndirectCS(trhip_cmdlist_t* cl, trhip_buffer_t* args, uint32_t argsOffset, uint32_t threads);
+int statsEmitAS(const DispatchCtx& ctx, const ::MeshletCullArgs& a, trhip_buffer_t* meshlets, trhip_buffer_t* records,
+                trhip_buffer_t* instances, trhip_buffer_t* meshData, bool side);
 
 using RecordFn = int (*)(DispatchCtx&);
 void registerShader(const char* name, RecordFn fn, int variant);

@@ -222,9 +222,13 @@ class FrameDriver:
                     ((self.hzb_w + 63) // 64, (self.hzb_h + 63) // 64, 1), push=spd)
 
     # ---- BasePassRenderer::RenderBasePass (:544-588) --------------------------------------------
-    def record(self):
+    def record(self, query: rhi.PipelineStatsQuery | None = None):
+        """query: a pipeline statistics query bracketing the whole list (begin after open, end before close), as the
+        reference brackets RenderBasePass (:546-549); None records the list without one."""
         cl = self.cl
         cl.open()
+        if query is not None:
+            cl.begin_pipeline_stats(query)
         occ = bool(self.flags & 2)
         self.ran = [False] * 4
 
@@ -244,6 +248,8 @@ class FrameDriver:
             self._generate_hzb(cl)
         else:
             do(2, False, True)
+        if query is not None:
+            cl.end_pipeline_stats(query)
         cl.close()
         return cl
 

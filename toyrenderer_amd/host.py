@@ -10,6 +10,7 @@ import numpy as np
 
 from . import interop as I
 from . import rhi
+from .rhi import PipelineStatistics
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtoyrenderer_host.so")
@@ -20,6 +21,7 @@ HOST_SYMBOLS = [
     "trhost_upload_hzb_mip", "trhost_download_hzb_mip", "trhost_hzb_info", "trhost_frame", "trhost_wait_idle",
     "trhost_pass_buffers", "trhost_instance_buffer", "trhost_device", "trhost_render_graph_stats", "trhost_renderer_times",
     "trhost_heap_sim", "trhost_set_shard_late_exchange", "trhost_set_gpu_timers",
+    "trhost_set_pipeline_statistics", "trhost_pipeline_statistics",
     "trhost_rccl_allgather", "trhost_exchange_create", "trhost_exchange_run", "trhost_exchange_wait", "trhost_exchange_outputs",
     "trhost_exchange_destroy", "trhost_load_geometry", "trhost_set_raster_depth", "trhost_download_depth",
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
@@ -87,6 +89,8 @@ def load() -> C.CDLL:
     L.trhost_render_graph_stats.argtypes = [C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
     L.trhost_renderer_times.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.trhost_set_gpu_timers.argtypes = [C.c_int]
+    L.trhost_set_pipeline_statistics.argtypes = [C.c_int]
+    L.trhost_pipeline_statistics.argtypes = [C.POINTER(PipelineStatistics), C.POINTER(PipelineStatistics)]
     L.trhost_exchange_create.argtypes = [C.POINTER(ExchangeDesc)]
     L.trhost_scene_list_sizes.argtypes = [C.POINTER(u32), C.POINTER(u32)]
     L.trhost_load_gi_probes.argtypes = [vp, vp, u32, C.c_float, C.c_int]
@@ -240,6 +244,17 @@ class Renderer:
 
     def wait_idle(self):
         _check(load().trhost_wait_idle())
+
+    def set_pipeline_statistics(self, enable: bool = True):
+        """The base pass brackets every frame with a pipeline statistics query (include/trhost.h); off by default."""
+        _check(load().trhost_set_pipeline_statistics(int(bool(enable))))
+
+    def pipeline_statistics(self):
+        """(last_shown, latest) as {field: int} dicts: the value the last frame showed (its query of two frames earlier)
+        and the last executed frame's own query (waits for it)."""
+        a, b = PipelineStatistics(), PipelineStatistics()
+        _check(load().trhost_pipeline_statistics(C.byref(a), C.byref(b)))
+        return a.as_dict(), b.as_dict()
 
     def set_gpu_timers(self, enable: bool):
         _check(load().trhost_set_gpu_timers(int(bool(enable))))

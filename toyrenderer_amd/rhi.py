@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "trhip_cmd_begin_timer", "trhip_cmd_end_timer", "trhip_cmd_begin_marker", "trhip_cmd_end_marker",
     "trhip_queue_execute",
     "trhip_timer_create", "trhip_timer_release", "trhip_timer_get_ms",
+    "trhip_pipeline_stats_create", "trhip_pipeline_stats_release", "trhip_cmd_begin_pipeline_stats",
+    "trhip_cmd_end_pipeline_stats", "trhip_pipeline_stats_get",
     "trhip_profile_enable", "trhip_profile_filter", "trhip_profile_reset", "trhip_profile_count", "trhip_profile_entry",
     "trhip_launch_shard_late_info",
     "trhip_stream_create", "trhip_stream_create_priority", "trhip_stream_destroy", "trhip_stream_synchronize", "trhip_event_create", "trhip_event_destroy",
@@ -58,6 +60,19 @@ class TextureDesc(C.Structure):
 class Binding(C.Structure):
     _fields_ = [("type", C.c_uint32), ("slot", C.c_uint32), ("resource", C.c_void_p), ("baseMip", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+# trhip_pipeline_statistics: D3D12_QUERY_DATA_PIPELINE_STATISTICS1's fields, in its order (include/trhip.h)
+PIPELINE_STATISTICS_FIELDS = ("IAVertices", "IAPrimitives", "VSInvocations", "GSInvocations", "GSPrimitives", "CInvocations",
+                              "CPrimitives", "PSInvocations", "HSInvocations", "DSInvocations", "CSInvocations", "ASInvocations",
+                              "MSInvocations", "MSPrimitives")
+
+
+class PipelineStatistics(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in PIPELINE_STATISTICS_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f in PIPELINE_STATISTICS_FIELDS}
 
 
 class TrhipError(RuntimeError):
@@ -147,6 +162,12 @@ def load() -> C.CDLL:
     L.trhip_queue_execute.argtypes = [vp, C.POINTER(vp), u32]
     L.trhip_timer_create.argtypes = [vp, C.POINTER(vp)]
     L.trhip_timer_get_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    L.trhip_pipeline_stats_create.argtypes = [vp, C.POINTER(vp)]
+    L.trhip_pipeline_stats_release.argtypes = [vp]
+    L.trhip_pipeline_stats_release.restype = None
+    L.trhip_cmd_begin_pipeline_stats.argtypes = [vp, vp]
+    L.trhip_cmd_end_pipeline_stats.argtypes = [vp, vp]
+    L.trhip_pipeline_stats_get.argtypes = [vp, C.POINTER(PipelineStatistics)]
     L.trhip_profile_enable.argtypes = [vp, i32]
     L.trhip_profile_filter.argtypes = [vp, C.c_char_p]
     L.trhip_profile_reset.argtypes = [vp]
@@ -270,6 +291,23 @@ class Timer:
             self.h = None
 
 
+class PipelineStatsQuery:
+    """nvrhi::IPipelineStatisticsQuery: trhip_pipeline_stats (include/trhip.h)."""
+    def __init__(self, dev, handle):
+        self.dev, self.h = dev, handle
+
+    def get(self) -> dict:
+        """Waits for the last executed end; {field: int} in trhip_pipeline_statistics order."""
+        v = PipelineStatistics()
+        _check(load().trhip_pipeline_stats_get(self.h, C.byref(v)))
+        return v.as_dict()
+
+    def release(self):
+        if self.h:
+            load().trhip_pipeline_stats_release(self.h)
+            self.h = None
+
+
 class CommandList:
     def __init__(self, dev: "Device", handle):
         self.dev, self.h = dev, handle
@@ -329,6 +367,8 @@ class CommandList:
 
     def begin_timer(self, t: Timer): _check(load().trhip_cmd_begin_timer(self.h, t.h))
     def end_timer(self, t: Timer): _check(load().trhip_cmd_end_timer(self.h, t.h))
+    def begin_pipeline_stats(self, q: PipelineStatsQuery): _check(load().trhip_cmd_begin_pipeline_stats(self.h, q.h))
+    def end_pipeline_stats(self, q: PipelineStatsQuery): _check(load().trhip_cmd_end_pipeline_stats(self.h, q.h))
     def begin_marker(self, name: str): _check(load().trhip_cmd_begin_marker(self.h, name.encode()))
     def end_marker(self): _check(load().trhip_cmd_end_marker(self.h))
 
@@ -395,6 +435,11 @@ class Device:
         h = C.c_void_p()
         _check(load().trhip_timer_create(self.h, C.byref(h)))
         return Timer(self, h)
+
+    def create_pipeline_stats(self) -> PipelineStatsQuery:
+        h = C.c_void_p()
+        _check(load().trhip_pipeline_stats_create(self.h, C.byref(h)))
+        return PipelineStatsQuery(self, h)
 
     def execute(self, *lists: CommandList):
         arr = (C.c_void_p * len(lists))(*[cl.h for cl in lists])
