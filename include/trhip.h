@@ -43,8 +43,9 @@ enum {
     TRHIP_ERR_NO_DEVICE = -5
 };
 
-/* nvrhi::Format subset used on the path (GraphicConstants.h:26-28). */
-enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2 };
+/* nvrhi::Format subset used on the path (GraphicConstants.h:25-28).  RG32_UINT (the visibility buffer: each texel one
+ * little-endian u64) and RG16_FLOAT (the motion target, GBufferMotion) have one mip only. */
+enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4 };
 
 /* ---- error / introspection ---------------------------------------------------------------- */
 const char* trhip_last_error(void);          /* thread-local text of the last failure          */
@@ -58,7 +59,14 @@ uint32_t    trhip_abi_version(void);
  * "basepass_MS_Main_depth" (basepass.hlsl:124-188 + raster + depth test, depth only): b0 BasePassConstants,
  * t0 instances, t1 vertices (RawVertexFormat, 20 B), t2 mesh data, t4 meshlets, t5 meshlet vertex ids,
  * t6 packed meshlet triangles, t7 amplification records, t9 visible list, u0 (texture) R32_FLOAT depth;
- * dispatched indirectly on the visible list's draw args. */
+ * dispatched indirectly on the visible list's draw args.
+ * "basepass_MS_Main_visibility": the same bindings, plus u1 (texture) RG32_UINT visibility buffer (render resolution, mip 0) and
+ * push constants {uint32 passSlot} (0..3); each covered sample also max-merges (depthBits << 32) | passSlot << 30 |
+ * listPosition << 7 | triangle into u1 (equal depth: the larger payload wins).  Visible-list capacity at most 2^23 entries.
+ * "basepass_PS_Main_motion" (basepass.hlsl:226-237, GBufferMotion): a direct dispatch of [numthreads(8, 8, 1)] groups over
+ * the screen; b0 BasePassConstants (m_PrevWorldToClip set), t0 t1 t2 t4 t5 t6 as above, t10..t13 the four slots' records,
+ * t14..t17 their visible lists, t18 (texture) the visibility buffer, u0 (texture) RG16_FLOAT motion target: the screen-space
+ * motion to the previous frame, in pixels, of every pixel with a nonzero visibility texel (others are left as they are). */
 uint32_t    trhip_shader_count(void);
 const char* trhip_shader_name(uint32_t index);
 int         trhip_shader_exists(const char* name);
@@ -167,7 +175,8 @@ int  trhip_cmd_close(trhip_cmdlist cl);                               /* ::close
  * On a volatile constant buffer this sets the version later dispatches in this list see. */
 int  trhip_cmd_write_buffer(trhip_cmdlist cl, trhip_buffer buf, uint64_t dst_offset, const void* src, uint64_t bytes);
 int  trhip_cmd_clear_buffer_u32(trhip_cmdlist cl, trhip_buffer buf, uint32_t value);   /* ::clearBufferUInt   */
-int  trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value);    /* ::clearTextureFloat */
+int  trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value);    /* ::clearTextureFloat (16-bit formats: the fp16 of value, RNE; not RG32_UINT) */
+int  trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value); /* ::clearTextureUInt: RG32_UINT, value in every 32-bit channel word */
 int  trhip_cmd_copy_buffer(trhip_cmdlist cl, trhip_buffer dst, uint64_t dst_offset, trhip_buffer src, uint64_t src_offset, uint64_t bytes); /* ::copyBuffer */
 /* Multi-GPU hook (no counterpart in the reference, which is single-GPU: GraphicRHI.cpp:165).
  * fn(user, hip_stream) is called on the submitting thread while the list is executed, in order with

@@ -68,6 +68,15 @@ int  trhost_upload_depth(const float* depth, uint32_t width, uint32_t height);
 int  trhost_load_geometry(const void* vertices, uint64_t num_vertices, const uint32_t* meshlet_vertex_ids, uint64_t num_vertex_ids,
                           const uint32_t* meshlet_triangles, uint64_t num_triangles);
 int  trhost_set_raster_depth(int enable);
+/* Per-pixel visibility buffer and motion target (implies raster depth): every pass rasterises through
+ * "basepass_MS_Main_visibility" into GBufferRenderer's VisibilityBuffer (RG32_UINT: per texel one u64,
+ * depthBits << 32 | passSlot << 30 | listPosition << 7 | triangle, 0 = nothing drawn), and "basepass_PS_Main_motion" resolves
+ * GBufferMotion (RG16_FLOAT: previous position minus pixel centre, pixels) once after the last pass, with
+ * m_PrevWorldToClip = the last frame's raster camera.  Refused with max_meshlet_groups above 2^18 and with a shard exchange.
+ * The downloads read the last frame's targets (render resolution; 8 and 4 bytes per texel), after wait_idle. */
+int  trhost_set_visibility_buffer(int enable);
+int  trhost_download_visibility(uint64_t* texels, uint64_t bytes);
+int  trhost_download_motion(uint16_t* halves, uint64_t bytes);
 int  trhost_download_depth(float* depth, uint64_t bytes);
 int  trhost_upload_hzb_mip(uint32_t mip, const uint16_t* texels, uint64_t bytes);
 int  trhost_download_hzb_mip(uint32_t mip, uint16_t* texels, uint64_t bytes);

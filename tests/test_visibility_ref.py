@@ -1,0 +1,178 @@
+"""The test reference of the visibility buffer and the motion target (tests/visibility_ref.c), checked on the CPU:
+its depth words equal the oracle's rasteriser bit for bit, the payload decodes, the draw order does not matter, the
+motion of a static scene is (close to) zero and a camera translation gives the analytic shift.  Also: the back end
+declares and exports the new entry points."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import visibility_ref as VR  # noqa: E402
+from scene_gen import all_meshlets_visible  # noqa: E402
+from toyrenderer_amd import gltf_lite, synth  # noqa: E402
+from visibility_scenes import city, consts, hostile_soup, inside_view, with_duplicates  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def vr(tmp_path_factory):
+    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
+
+
+def _both(oracle, vr, k, sc, v, vid, tri, rec, lst, slot=0, order=None):
+    H, W = int(k["m_OutputResolution"][0][1]), int(k["m_OutputResolution"][0][0])
+    ref = np.zeros((H, W), np.float32)
+    oracle.raster_depth(k, sc, v, vid, tri, rec, lst, ref)
+    depth, vis = np.zeros((H, W), np.float32), np.zeros((H, W), np.uint64)
+    VR.raster(vr, k, VR.Geometry(sc, v, vid, tri), rec, lst, slot, depth, vis, order)
+    return ref, depth, vis
+
+
+def test_depth_words_equal_the_oracle_on_the_cornell_fixture(oracle, vr):
+    from test_gltf_cornell import _fixture
+    _, s, camera = _fixture()
+    inst = s.instances.copy()
+    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
+    sc = dict(s.as_oracle()); sc["instances"] = inst
+    view = gltf_lite.view_of(camera, (320, 180))
+    rec, lst = all_meshlets_visible(s)
+    ref, depth, vis = _both(oracle, vr, consts(view), sc, s.vertices, s.meshletVertexIds, s.meshletTriangles, rec, lst)
+    assert np.count_nonzero(ref) > 0.5 * ref.size
+    assert np.array_equal((vis >> np.uint64(32)).astype(np.uint32), ref.view(np.uint32))
+    assert np.array_equal(depth.view(np.uint32), ref.view(np.uint32))
+
+
+@pytest.mark.parametrize("inside", [False, True])
+def test_depth_words_equal_the_oracle_on_a_generated_city(tmp_path, oracle, vr, inside):
+    s, sc = city(tmp_path, oracle)
+    view = inside_view(s.cameras[0]) if inside else gltf_lite.view_of(s.cameras[0], (480, 270))
+    rec, lst = all_meshlets_visible(s)
+    ref, _, vis = _both(oracle, vr, consts(view), sc, s.vertices, s.meshletVertexIds, s.meshletTriangles, rec, lst)
+    assert np.count_nonzero(ref) > 0
+    assert np.array_equal((vis >> np.uint64(32)).astype(np.uint32), ref.view(np.uint32))
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_hostile_soup_depth_and_out_of_contract_triangles(oracle, vr, seed):
+    sc, v, vid, tri, rec, lst = hostile_soup(seed)
+    view = synth.make_view(render=(320, 200))
+    ref, depth, vis = _both(oracle, vr, consts(view), sc, v, vid, tri, rec, lst)
+    assert np.count_nonzero(ref) > 1000
+    assert np.array_equal(depth.view(np.uint32), ref.view(np.uint32))
+    hi = (vis >> np.uint64(32)).astype(np.uint32)
+    # a texel's depth is never above the depth buffer; it is below only where a triangle >= 128 is in front
+    assert np.all(hi <= ref.view(np.uint32))
+    _, _, _, t = VR.decode(vis[vis != 0])
+    assert t.max() < 128
+    # without the out-of-contract meshlets the two agree everywhere
+    big = (sc["meshlets"]["m_VertexAndTriangleCount"] >> 8) & 0xFF >= 128
+    assert big.any()
+    keep = np.array([not big[(rec[e >> 5]["m_MeshletGroupOffset"] + (e & 31))] for e in lst])
+    ref2, _, vis2 = _both(oracle, vr, consts(view), sc, v, vid, tri, rec, lst[keep])
+    assert np.array_equal((vis2 >> np.uint64(32)).astype(np.uint32), ref2.view(np.uint32))
+
+
+def test_payload_round_trips():
+    rng = np.random.default_rng(3)
+    n = 1000
+    d = rng.uniform(1e-6, 1.0, n).astype(np.float32)
+    slot, pos, tri = rng.integers(0, 4, n), rng.integers(0, 1 << 23, n), rng.integers(0, 128, n)
+    slot[:2], pos[:2], tri[:2] = (0, 3), (0, (1 << 23) - 1), (0, 127)
+    got = VR.decode(VR.encode(d, slot, pos, tri))
+    assert np.array_equal(got[0].view(np.uint32), d.view(np.uint32))
+    assert np.array_equal(got[1], slot) and np.array_equal(got[2], pos) and np.array_equal(got[3], tri)
+
+
+def test_draw_order_does_not_change_the_buffer(tmp_path, oracle, vr):
+    """Draw orders forward, shuffled and reversed give one buffer.  Instances 0..3 are duplicated at the end of the
+    instance list with identical matrices: exact depth ties, which the larger payload (the duplicates' later list
+    positions) wins whatever the order."""
+    s, sc = city(tmp_path, oracle)
+    view = gltf_lite.view_of(s.cameras[0], (480, 270))
+    sc, rec, lst, n = with_duplicates(s, sc, 4)
+    geo = VR.Geometry(sc, s.vertices, s.meshletVertexIds, s.meshletTriangles)
+    out = []
+    for order in (None, np.random.default_rng(1).permutation(len(lst)), np.arange(len(lst))[::-1]):
+        depth, vis = np.zeros((270, 480), np.float32), np.zeros((270, 480), np.uint64)
+        VR.raster(vr, consts(view), geo, rec, lst, 1, depth, vis, order)
+        out.append(vis)
+    assert np.array_equal(out[0], out[1]) and np.array_equal(out[0], out[2])
+    _, slot, pos, _ = VR.decode(out[0][out[0] != 0])
+    assert np.all(slot == 1)
+    inst_of = rec["m_InstanceConstIdx"][lst[pos] >> 5]
+    assert not np.isin(inst_of, np.arange(4)).any(), "a duplicated instance's texel went to the original"
+    assert (inst_of >= n).any()
+
+
+def test_static_scene_has_near_zero_motion(tmp_path, oracle, vr):
+    """Camera and instances unchanged: the exact motion is 0.  The interpolation weights of sliver triangles lose
+    precision (e_i / w_i of nearly collinear edges), so the bound is statistical: 99.9 % of covered pixels move less
+    than 1/64 px and every one less than 1 px."""
+    s, sc = city(tmp_path, oracle)
+    view = gltf_lite.view_of(s.cameras[0], (640, 360))
+    rec, lst = all_meshlets_visible(s)
+    k = consts(view, view.worldToView)
+    geo = VR.Geometry(sc, s.vertices, s.meshletVertexIds, s.meshletTriangles)
+    depth, vis = np.zeros((360, 640), np.float32), np.zeros((360, 640), np.uint64)
+    VR.raster(vr, k, geo, rec, lst, 0, depth, vis)
+    m = VR.motion(vr, k, geo, [rec, None, None, None], [lst, None, None, None], vis)
+    cov = vis != 0
+    mag = np.abs(m[cov]).max(axis=1)
+    assert cov.sum() > 0.2 * cov.size
+    assert np.all(m[~cov] == 0)
+    assert np.mean(mag < 1 / 64) >= 0.999, np.quantile(mag, [0.5, 0.999])
+    assert mag.max() < 1.0
+
+
+def test_camera_translation_gives_the_analytic_shift(tmp_path, oracle, vr):
+    """The previous camera sits `t` to the left (view -x): a point at view depth z appears P00 * t / z * W / 2 pixels
+    further left in the previous frame; z = near / depth for the reverse-Z infinite projection."""
+    s, sc = city(tmp_path, oracle)
+    render = (640, 360)
+    cam = s.cameras[0]
+    P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
+    V = synth.world_to_view((0.0, 0.0, 0.0), cam.orientation)
+    t = 0.05
+    Vprev = V.copy(); Vprev[3, 0] += np.float32(t)               # row vectors: p_view = p_world * V; +t in view x
+    view = synth.View(V, Vprev, P, float(np.float32(cam.znear)), *render)
+    rec, lst = all_meshlets_visible(s)
+    k = consts(view)
+    geo = VR.Geometry(sc, s.vertices, s.meshletVertexIds, s.meshletTriangles)
+    depth, vis = np.zeros((360, 640), np.float32), np.zeros((360, 640), np.uint64)
+    VR.raster(vr, k, geo, rec, lst, 0, depth, vis)
+    m = VR.motion(vr, k, geo, [rec, None, None, None], [lst, None, None, None], vis)
+    cov = vis != 0
+    z = np.float64(view.nearPlane) / depth[cov].astype(np.float64)
+    expect_x = P[0, 0] * t / z * render[0] / 2
+    err = np.abs(m[cov][:, 0] - expect_x)
+    assert np.quantile(err, 0.999) < 1 / 32 + 1e-3 * np.abs(expect_x).max()
+    assert np.quantile(np.abs(m[cov][:, 1]), 0.999) < 1 / 32
+    assert np.abs(expect_x).max() > 1.0, "the case must move pixels"
+
+
+def test_half_store_rounds_to_nearest_even():
+    x = np.array([1.0 + 2 ** -11, 1.0 + 3 * 2 ** -11, 65520.0, -1e-8, np.nan], np.float32)
+    assert list(VR.to_half_bits(x)) == [0x3C00, 0x3C02, 0x7C00, 0x8000, 0x7E00]
+
+
+def test_exports_and_declarations():
+    from toyrenderer_amd import rhi
+    h = open(os.path.join(ROOT, "include", "trhip.h")).read()
+    assert re.search(r"TRHIP_FORMAT_RG32_UINT\s*=\s*3", h) and re.search(r"TRHIP_FORMAT_RG16_FLOAT\s*=\s*4", h)
+    assert "trhip_cmd_clear_texture_u32(" in h and "trhip_cmd_clear_texture_u32" in rhi.ABI_SYMBOLS
+    assert rhi.FORMAT_RG32_UINT == 3 and rhi.FORMAT_RG16_FLOAT == 4
+    lib = rhi.load()
+    assert hasattr(lib, "trhip_cmd_clear_texture_u32") and lib.trhip_abi_version() == 1
+    t = open(os.path.join(ROOT, "include", "trhost.h")).read()
+    from toyrenderer_amd import host
+    for f in ("trhost_set_visibility_buffer", "trhost_download_visibility", "trhost_download_motion"):
+        assert f + "(" in t and f in host.HOST_SYMBOLS and hasattr(host.load(), f), f
+    for m in ("set_visibility_buffer", "download_visibility", "download_motion"):
+        assert callable(getattr(host.Renderer, m, None)), m
+    names = set(rhi.shader_names())
+    assert {"basepass_MS_Main_depth", "basepass_MS_Main_visibility", "basepass_PS_Main_motion"} <= names

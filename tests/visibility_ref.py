@@ -1,0 +1,106 @@
+"""ctypes wrapper of tests/visibility_ref.c, the test reference of the visibility buffer and the motion target.
+
+The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from toyrenderer_amd import interop as I
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+_LIB = {}
+
+
+def load(tmpdir) -> C.CDLL:
+    out = os.path.join(str(tmpdir), "libvisibility_ref.so")
+    if out not in _LIB:
+        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "oracle"),
+                               os.path.join(HERE, "visibility_ref.c"), "-o", out, "-lm"])
+        lib = C.CDLL(out)
+        lib.vr_raster.argtypes = [C.c_void_p] * 9 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.vr_raster.restype = None
+        lib.vr_motion.argtypes = [C.c_void_p] * 11
+        lib.vr_motion.restype = None
+        _LIB[out] = lib
+    return _LIB[out]
+
+
+def _p(a):
+    return a.ctypes.data if a is not None else None
+
+
+def decode(texel):
+    """(depth float32, slot, list position, triangle) of texels (u64 array)."""
+    t = np.asarray(texel, np.uint64)
+    lo = (t & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    depth = (t >> np.uint64(32)).astype(np.uint32).view(np.float32)
+    return depth, lo >> 30, (lo >> 7) & 0x7FFFFF, lo & 127
+
+
+def encode(depth, slot, pos, tri):
+    d = np.asarray(depth, np.float32).view(np.uint32).astype(np.uint64)
+    lo = (np.asarray(slot, np.uint64) << np.uint64(30)) | (np.asarray(pos, np.uint64) << np.uint64(7)) | np.asarray(tri, np.uint64)
+    return (d << np.uint64(32)) | lo
+
+
+class Geometry:
+    def __init__(self, scene: dict, vertices, vertex_ids, triangles):
+        self.instances = np.ascontiguousarray(scene["instances"])
+        self.meshData = np.ascontiguousarray(scene["meshData"])
+        self.meshlets = np.ascontiguousarray(scene["meshlets"])
+        self.vertices = np.ascontiguousarray(vertices, I.RawVertexFormat)
+        self.vertexIds = np.ascontiguousarray(vertex_ids, np.uint32)
+        self.triangles = np.ascontiguousarray(triangles, np.uint32)
+
+    def args(self):
+        return [_p(self.instances), _p(self.meshData), _p(self.meshlets), _p(self.vertices), _p(self.vertexIds), _p(self.triangles)]
+
+
+def raster(lib, consts, geo: Geometry, records, visible_list, slot, depth, vis, order=None):
+    """Max-merges one slot's listed meshlets into depth (float32 [H, W]) and vis (uint64 [H, W]), in place."""
+    k = np.ascontiguousarray(consts)
+    rec = np.ascontiguousarray(records)
+    lst = np.ascontiguousarray(visible_list, np.uint32)
+    order = None if order is None else np.ascontiguousarray(order, np.uint32)
+    assert depth.dtype == np.float32 and vis.dtype == np.uint64 and depth.flags.c_contiguous and vis.flags.c_contiguous
+    lib.vr_raster(_p(k), *geo.args(), _p(rec), _p(lst), len(lst), _p(order), int(slot), _p(depth), _p(vis))
+
+
+def motion(lib, consts, geo: Geometry, records4, lists4, vis):
+    """float32 [H, W, 2] motion of every texel (0 where vis is 0); records4 / lists4: the four slots' arrays."""
+    k = np.ascontiguousarray(consts)
+    H, W = vis.shape
+    out = np.zeros((H, W, 2), np.float32)
+    recs = [np.ascontiguousarray(r if r is not None and len(r) else np.zeros(1, I.MeshletAmplificationData)) for r in records4]
+    lsts = [np.ascontiguousarray(x if x is not None and len(x) else np.zeros(1, np.uint32), np.uint32) for x in lists4]
+    rp = (C.c_void_p * 4)(*[_p(r) for r in recs])
+    lp = (C.c_void_p * 4)(*[_p(x) for x in lsts])
+    lib.vr_motion(_p(k), *geo.args(), C.addressof(rp), C.addressof(lp), _p(np.ascontiguousarray(vis, np.uint64)), _p(out))
+    return out
+
+
+def to_half_bits(m):
+    """fp16 store of the motion kernel: round to nearest even, one NaN (0x7E00)."""
+    h = np.asarray(m, np.float32).astype(np.float16).view(np.uint16).copy()
+    h[np.isnan(m)] = 0x7E00
+    return h
+
+
+def frame_visibility(lib, consts, geo: Geometry, ref, W, H):
+    """Visibility buffer of a pyoracle.frame(raster=...) result: every slot that ran, its records and visible list."""
+    vis = np.zeros((H, W), np.uint64)
+    depth = np.zeros((H, W), np.float32)
+    for s in range(4):
+        if ref.passRan[s]:
+            n = min(int(ref.drawArgs[s][0]), len(ref.visibleList[s]))
+            raster(lib, consts, geo, ref.records[s], ref.visibleList[s][:n], s, depth, vis)
+    return vis, depth
+
+
+def frame_motion(lib, consts, geo: Geometry, ref, vis):
+    recs = [ref.records[s] if ref.passRan[s] else None for s in range(4)]
+    lsts = [ref.visibleList[s] if ref.passRan[s] else None for s in range(4)]
+    return motion(lib, consts, geo, recs, lsts, vis)

@@ -156,6 +156,7 @@ public:
     PassOutputs m_Outputs[kNumPassSlots];
     nvrhi::BufferHandle m_LastLateCullInstanceCountBuffer, m_LastLateCullDispatchIndirectArgsBuffer;
     nvrhi::TextureHandle m_CurrentDepthBuffer, m_LastDepthBuffer;     // depth attachment of the pass being recorded / of the last frame (read-back)
+    nvrhi::TextureHandle m_VisibilityBuffer, m_MotionBuffer;           // RG32_UINT / RG16_FLOAT at render resolution (m_bVisibilityBuffer)
 
 protected:
     RenderGraph::ResourceHandle m_LateCullDispatchIndirectArgsRDGBufferHandle;
@@ -390,6 +391,7 @@ public:
             // one wave per visible meshlet, dispatched on the draw arguments the cull just wrote.
             check(g_Graphic.m_GlobalVertexBuffer && m_CurrentDepthBuffer);
             basePassConstants.m_WorldToClip = MultiplyNoFMA(g_Scene->m_View.m_CullingWorldToView, g_Scene->m_View.m_ViewToClip);   // :447
+            if (g_Scene->m_bVisibilityBuffer) basePassConstants.m_PrevWorldToClip = PrevWorldToClip();
             nvrhi::BufferHandle rasterConstants = g_Graphic.CreateConstantBuffer(commandList, basePassConstants);
             nvrhi::BindingSetDesc rasterBindings;
             rasterBindings.bindings = {
@@ -407,6 +409,15 @@ public:
             Graphic::ComputePassParams rasterPass;
             rasterPass.m_CommandList = commandList;
             rasterPass.m_ShaderName = "basepass_MS_Main_depth";
+            const uint32_t passSlot = (uint32_t)slot;
+            if (g_Scene->m_bVisibilityBuffer) {                               // + the per-pixel identity: u1, push constant {passSlot}
+                check(m_VisibilityBuffer);
+                rasterBindings.bindings.push_back(nvrhi::BindingSetItem::Texture_UAV(1, m_VisibilityBuffer));
+                rasterBindings.bindings.push_back(nvrhi::BindingSetItem::PushConstants(1, sizeof(passSlot)));
+                rasterPass.m_ShaderName = "basepass_MS_Main_visibility";
+                rasterPass.m_PushConstantsData = &passSlot;
+                rasterPass.m_PushConstantsBytes = sizeof(passSlot);
+            }
             rasterPass.m_BindingSetDesc = rasterBindings;
             rasterPass.m_IndirectArgsBuffer = visibleDrawArgsBuffer;
             g_Graphic.AddComputePass(rasterPass);
@@ -419,6 +430,43 @@ public:
         out.m_MeshletVisibilityMaskBuffer = visMaskBuffer;
         out.m_VisibleMeshletListBuffer = visibleListBuffer;
         out.m_VisibleMeshletDrawArgsBuffer = visibleDrawArgsBuffer;
+    }
+
+    // The matrix the raster used the frame before: the reference's m_PrevWorldToClip = m_WorldToClip (Scene.cpp:116-118)
+    // applied to this build's raster camera.
+    static Matrix PrevWorldToClip() { return MultiplyNoFMA(g_Scene->m_View.m_CullingPrevWorldToView, g_Scene->m_View.m_PrevViewToClip); }
+
+    // GBufferMotion of every pixel the base pass drew (basepass.hlsl:226-237), once after the last raster.
+    void ResolveMotion(nvrhi::CommandListHandle commandList)
+    {
+        using Item = nvrhi::BindingSetItem;
+        BasePassConstants k{};
+        k.m_WorldToView = g_Scene->m_View.m_CullingWorldToView;
+        k.m_WorldToClip = MultiplyNoFMA(g_Scene->m_View.m_CullingWorldToView, g_Scene->m_View.m_ViewToClip);
+        k.m_PrevWorldToClip = PrevWorldToClip();
+        k.m_NearPlane = g_Scene->m_View.m_ZNearP;
+        k.m_OutputResolution = g_Graphic.m_RenderResolution;
+        Graphic::ComputePassParams p;
+        p.m_CommandList = commandList;
+        p.m_ShaderName = "basepass_PS_Main_motion";
+        p.m_BindingSetDesc.bindings = {
+            Item::ConstantBuffer(0, g_Graphic.CreateConstantBuffer(commandList, k)),
+            Item::StructuredBuffer_SRV(0, g_Scene->m_InstanceConstsBuffer),
+            Item::StructuredBuffer_SRV(1, g_Graphic.m_GlobalVertexBuffer),
+            Item::StructuredBuffer_SRV(2, g_Graphic.m_GlobalMeshDataBuffer),
+            Item::StructuredBuffer_SRV(4, g_Graphic.m_GlobalMeshletDataBuffer),
+            Item::StructuredBuffer_SRV(5, g_Graphic.m_GlobalMeshletVertexOffsetsBuffer),
+            Item::StructuredBuffer_SRV(6, g_Graphic.m_GlobalMeshletIndicesBuffer),
+            Item::Texture_SRV(18, m_VisibilityBuffer),
+            Item::Texture_UAV(0, m_MotionBuffer),
+        };
+        for (uint32_t s = 0; s < kNumPassSlots; ++s) {                        // a slot that did not run: the dummy buffer
+            const PassOutputs& o = m_Outputs[s];
+            p.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_SRV(10 + s, o.m_bRan ? o.m_MeshletAmplificationDataBuffer : g_CommonResources.DummyUIntStructuredBuffer));
+            p.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_SRV(14 + s, o.m_bRan ? o.m_VisibleMeshletListBuffer : g_CommonResources.DummyUIntStructuredBuffer));
+        }
+        p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Graphic.m_RenderResolution, 8);
+        g_Graphic.AddComputePass(p);
     }
 
     void GenerateHZB(nvrhi::CommandListHandle commandList, const RenderGraph& renderGraph, const RenderBasePassParams& params)
@@ -531,6 +579,14 @@ public:
         m_LastDepthBuffer = hzbParams.m_DepthBuffer;
         if (g_Scene->m_bRasterDepth)                                                                 // the base pass starts from a cleared depth buffer
             commandList->clearTextureFloat(params.m_DepthBuffer, nvrhi::AllSubresources, nvrhi::Color{ GraphicConstants::kFarDepth });
+        if (g_Scene->m_bVisibilityBuffer) {
+            // list positions are per rank under a shard exchange, not global; and a payload holds positions below 2^23
+            if (g_ShardLateExchange.fn) throw nvrhi::Error("visibility buffer + shard exchange: list positions are per rank, not global");
+            if (g_Graphic.m_MaxMeshletGroups > (1u << 18)) throw nvrhi::Error("visibility buffer: max_meshlet_groups above 2^18 (list positions must stay below 2^23)");
+            check(m_VisibilityBuffer && m_MotionBuffer);
+            commandList->clearTextureUInt(m_VisibilityBuffer, nvrhi::AllSubresources, 0);                   // 0 = nothing drawn
+            commandList->clearTextureFloat(m_MotionBuffer, nvrhi::AllSubresources, nvrhi::Color{ 0.0f });
+        }
 
         GPUCulling(commandList, renderGraph, kEarlyOpaque, false /* bLateCull */, false /* bAlphaMaskPrimitives */);          // :565-566
         RenderInstances(commandList, renderGraph, kEarlyOpaque, false, false);
@@ -547,11 +603,15 @@ public:
                 GPUCulling(commandList, renderGraph, kLateAlphaMask, true, true);
                 RenderInstances(commandList, renderGraph, kLateAlphaMask, true, true);
             }
+            if (g_Scene->m_bVisibilityBuffer) ResolveMotion(commandList);
             GenerateHZB(commandList, renderGraph, hzbParams);
-        } else if (m_NumSlotsThisFrame == kNumPassSlots) {
-            // cull & render for alpha mask primitives, but no occlusion culling (:583-587)
-            GPUCulling(commandList, renderGraph, kEarlyAlphaMask, false, true);
-            RenderInstances(commandList, renderGraph, kEarlyAlphaMask, false, true);
+        } else {
+            if (m_NumSlotsThisFrame == kNumPassSlots) {
+                // cull & render for alpha mask primitives, but no occlusion culling (:583-587)
+                GPUCulling(commandList, renderGraph, kEarlyAlphaMask, false, true);
+                RenderInstances(commandList, renderGraph, kEarlyAlphaMask, false, true);
+            }
+            if (g_Scene->m_bVisibilityBuffer) ResolveMotion(commandList);
         }
     }
 };
@@ -611,6 +671,19 @@ public:
     {
         if (g_Scene->m_NumPrimitives == 0) return;                            // :668-671
         nvrhi::TextureHandle depthStencilBuffer = renderGraph.GetTexture(g_DepthStencilBufferRDGTextureHandle);
+        if (g_Scene->m_bVisibilityBuffer && !m_VisibilityBuffer) {
+            // the per-pixel targets, owned here (GBufferMotion: GraphicConstants.h:25, RG16_FLOAT)
+            nvrhi::TextureDesc desc;
+            desc.width = g_Graphic.m_RenderResolution.x;
+            desc.height = g_Graphic.m_RenderResolution.y;
+            desc.isUAV = true;
+            desc.format = nvrhi::Format::RG32_UINT;
+            desc.debugName = "VisibilityBuffer";
+            m_VisibilityBuffer = g_Graphic.m_NVRHIDevice->createTexture(desc);
+            desc.format = nvrhi::Format::RG16_FLOAT;
+            desc.debugName = "GBufferMotion";
+            m_MotionBuffer = g_Graphic.m_NVRHIDevice->createTexture(desc);
+        }
         RenderBasePassParams params;                                          // :691-695
         params.m_DepthBuffer = depthStencilBuffer;
         RenderBasePass(commandList, renderGraph, params);
@@ -643,6 +716,8 @@ void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::
 }
 
 nvrhi::TextureHandle GetLastDepthBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_LastDepthBuffer; }
+nvrhi::TextureHandle GetVisibilityBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_VisibilityBuffer; }
+nvrhi::TextureHandle GetMotionBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_MotionBuffer; }
 
 void ReleaseVisibilityPassBuffers()
 {
@@ -651,6 +726,7 @@ void ReleaseVisibilityPassBuffers()
     r->m_LastLateCullInstanceCountBuffer = nullptr;
     r->m_LastLateCullDispatchIndirectArgsBuffer = nullptr;
     r->m_CurrentDepthBuffer = nullptr; r->m_LastDepthBuffer = nullptr;
+    r->m_VisibilityBuffer = nullptr; r->m_MotionBuffer = nullptr;
     r->ReleasePipelineStatisticsQueries();
     for (ShardLateCall& c : g_ShardLateCalls) c = ShardLateCall{};
     SetShardLateExchange(nullptr, nullptr);

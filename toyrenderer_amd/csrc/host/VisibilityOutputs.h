@@ -35,6 +35,9 @@ void ReleaseGIProbeCullBuffers();
 
 // Depth attachment of the last recorded base pass (read-back for tests; null before the first frame).
 nvrhi::TextureHandle GetLastDepthBuffer();
+// GBufferRenderer's visibility buffer (RG32_UINT) and motion target (RG16_FLOAT); null until a frame ran with them on.
+nvrhi::TextureHandle GetVisibilityBuffer();
+nvrhi::TextureHandle GetMotionBuffer();
 // the base pass's pipeline statistics: the value its frame N showed (the query of frame N - 2) and the last executed frame's (waits)
 void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest);
 

@@ -92,7 +92,7 @@ private:
 using ResourceHandle = RefCountPtr<IResource>;
 
 // ---- enums / small structs -----------------------------------------------------------------------
-enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8 };        // GraphicConstants.h:26-28
+enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT };   // GraphicConstants.h:25-28
 enum class ResourceStates : uint32_t { Unknown = 0, ShaderResource, UnorderedAccess, IndirectArgument, DepthRead, DepthWrite, CopyDest };
 enum class CommandQueue : uint8_t { Graphics = 0, Compute, Copy, Count };
 enum class HeapType : uint8_t { DeviceLocal };
@@ -311,6 +311,7 @@ public:
     }
     void clearBufferUInt(IBuffer* b, uint32_t value) { keep(b); throwIfFailed(trhip_cmd_clear_buffer_u32(m_Native, b->native(), value), "ICommandList::clearBufferUInt"); }
     void clearTextureFloat(ITexture* t, TextureSubresourceSet, const Color& c) { keep(t); throwIfFailed(trhip_cmd_clear_texture_f32(m_Native, t->native(), c.r), "ICommandList::clearTextureFloat"); }
+    void clearTextureUInt(ITexture* t, TextureSubresourceSet, uint32_t v) { keep(t); throwIfFailed(trhip_cmd_clear_texture_u32(m_Native, t->native(), v), "ICommandList::clearTextureUInt"); }
     void copyBuffer(IBuffer* dst, uint64_t dstOff, IBuffer* src, uint64_t srcOff, uint64_t bytes)
     {
         keep(dst); keep(src);
@@ -422,7 +423,8 @@ public:
         trhip_texture_desc n{};
         n.width = d.width; n.height = d.height; n.mipLevels = d.mipLevels; n.isUAV = d.isUAV; n.isVirtual = d.isVirtual; n.debugName = d.debugName.c_str();
         // depth (D24S8 in the reference, GraphicConstants.h:26) is carried as 32-bit float depth here
-        n.format = d.format == Format::R16_FLOAT ? TRHIP_FORMAT_R16_FLOAT : TRHIP_FORMAT_R32_FLOAT;
+        n.format = d.format == Format::R16_FLOAT ? TRHIP_FORMAT_R16_FLOAT : d.format == Format::RG32_UINT ? TRHIP_FORMAT_RG32_UINT
+                 : d.format == Format::RG16_FLOAT ? TRHIP_FORMAT_RG16_FLOAT : TRHIP_FORMAT_R32_FLOAT;
         trhip_texture t = nullptr;
         throwIfFailed(trhip_texture_create(m_Native, &n, &t), "IDevice::createTexture");
         return TextureHandle(new ITexture(t, d));

@@ -107,6 +107,35 @@ int trhost_set_raster_depth(int enable)
     });
 }
 
+int trhost_set_visibility_buffer(int enable)
+{
+    return guarded([&] {
+        check(!enable || g_Graphic.m_GlobalVertexBuffer);      // trhost_load_geometry first
+        if (enable && g_Graphic.m_MaxMeshletGroups > (1u << 18))
+            throw nvrhi::Error("trhost_set_visibility_buffer: max_meshlet_groups above 2^18 (list positions must stay below 2^23)");
+        g_Scene->m_bVisibilityBuffer = enable != 0;
+        if (enable) g_Scene->m_bRasterDepth = true;            // implies raster depth
+    });
+}
+
+int trhost_download_visibility(uint64_t* texels, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetVisibilityBuffer();
+        check(t && texels);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, texels, bytes), "trhost_download_visibility");
+    });
+}
+
+int trhost_download_motion(uint16_t* halves, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetMotionBuffer();
+        check(t && halves);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, halves, bytes), "trhost_download_motion");
+    });
+}
+
 int trhost_download_depth(float* depth, uint64_t bytes)
 {
     return guarded([&] {
@@ -180,6 +209,8 @@ int trhost_set_gpu_timers(int enable)
 int trhost_set_limits(uint32_t max_meshlet_groups, uint64_t max_transient_resource_bytes)
 {
     return guarded([&] {
+        if (max_meshlet_groups && g_Scene && g_Scene->m_bVisibilityBuffer && max_meshlet_groups > (1u << 18))
+            throw nvrhi::Error("trhost_set_limits: max_meshlet_groups above 2^18 with the visibility buffer on");
         if (max_meshlet_groups) g_Graphic.m_MaxMeshletGroups = max_meshlet_groups;
         if (max_transient_resource_bytes) RenderGraph::ms_MaxHeapBlockSize = max_transient_resource_bytes;
     });
@@ -276,7 +307,11 @@ int trhost_set_shard_late_exchange(trhost_shard_late_fn fn, void* user)
 
 int trhost_exchange_create(const trhost_exchange_desc* desc)
 {
-    return guarded([&] { check(desc); ShardExchangeCreate(*desc); });
+    return guarded([&] {
+        check(desc);
+        if (g_Scene && g_Scene->m_bVisibilityBuffer) throw nvrhi::Error("trhost_exchange_create: the visibility buffer is on (list positions are per rank)");
+        ShardExchangeCreate(*desc);
+    });
 }
 int trhost_exchange_run(void) { return guarded([&] { ShardExchangeRun(); }); }
 int trhost_exchange_wait(void) { return guarded([&] { ShardExchangeWait(); }); }

@@ -19,6 +19,18 @@
 // 256x256-pixel coarse bin, which "main" fills while it queues.  Without the second launch a dozen
 // waves walked the 10^4-pixel boxes of a near wall while the chip idled (3.2 ms per pass at 3840x2160,
 // tools/raster_time.py).  Every pixel value is computed by the same operations whichever launch produces it.
+//
+// "basepass_MS_Main_visibility": the same two launches and the same arithmetic, instantiated with a second sink.  Every
+// covered sample of triangle t of visible-list entry v of pass slot s (push constant) also does one 64-bit atomic max of
+// (depthBits << 32) | s << 30 | v << 7 | t into u1, the RG32_UINT visibility buffer.  TIE RULE (a convention, parity
+// unpinned: hardware resolves ties by draw order): on equal depth the larger payload wins, so the result does not depend
+// on the draw order, as the depth does not.  The texel is 0 where nothing was drawn (depth > 0 on every written sample).
+// Triangles with index >= 128 (out of contract: kMaxMeshletTriangles is 96) write depth but no visibility texel; a list
+// capacity above 2^23 entries is refused at record time.  The tile launch keeps a 64x64 tile of u64 beside the depth tile
+// in LDS; its far-depth early-out reads the visibility words and stays a strict "<", so a triangle that can tie the kept
+// depth is still drawn (it can win the payload).  The depth instantiation keeps its kernels, launches, op names and
+// arithmetic; the compiler schedules and allocates its registers slightly differently (tiles: 58 VGPRs instead of 55).
+// tools/raster_time.py at 3840x2160, per launch, before / after the template: main 142.4 / 146.7 us, tiles 179.4 / 176.5 us.
 #include "cull_math.hip.h"
 #include "trhip_internal.h"
 
@@ -68,6 +80,17 @@ struct RasterArgs
     uint32_t binsX, binsY;
 };
 
+// The visibility sink's extra state (nullptr / 0 in the depth instantiation, where it is never read).
+struct VisArgs
+{
+    unsigned long long* vis;                                     // RG32_UINT as u64
+    unsigned long long* queuePayload;                            // scratch: [kQueueCapacity], (1 << 32 | payload) or 0 = no texel
+    uint32_t slotBits;                                           // passSlot << 30
+};
+
+constexpr uint32_t kVisTriangles = 128;                          // triangle indices with a visibility texel (7 bits)
+constexpr uint32_t kVisListCapacity = 1u << 23;                  // list positions (23 bits)
+
 // One triangle over the pixels [bx0, bx1] x [by0, by1], `threads` lanes striding over them from `first`; every covered
 // pixel goes to `sink(px, py, depthBits)`.  The arithmetic of orc_raster_depth, operation for operation.
 template <typename Sink>
@@ -88,7 +111,8 @@ __device__ __forceinline__ void coverBox(float x0, float y0, float d0, float x1,
     }
 }
 
-__global__ __launch_bounds__(kBlock) void rasterDepthKernel(RasterArgs a)
+template <bool Vis>
+__device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& va)
 {
     __shared__ float s_x[kWaves][64], s_y[kWaves][64], s_d[kWaves][64];
     __shared__ BigTriangle s_tri[kWaves][64];
@@ -175,6 +199,7 @@ __global__ __launch_bounds__(kBlock) void rasterDepthKernel(RasterArgs a)
                 const uint32_t slot = first + (uint32_t)__popcll(bigMask & ((1ull << lane) - 1ull));
                 if (big && slot < kQueueCapacity) {
                     a.queue[slot] = q;
+                    if constexpr (Vis) va.queuePayload[slot] = t < kVisTriangles ? (1ull << 32) | (va.slotBits | v << 7 | t) : 0ull;
                     // its index goes to every coarse bin the box touches
                     const uint32_t cx0 = (q.boxX & 0xFFFFu) >> kBinShift, cx1 = (q.boxX >> 16) >> kBinShift;
                     const uint32_t cy0 = (q.boxY & 0xFFFFu) >> kBinShift, cy1 = (q.boxY >> 16) >> kBinShift;
@@ -199,8 +224,20 @@ __global__ __launch_bounds__(kBlock) void rasterDepthKernel(RasterArgs a)
                 for (unsigned long long mrem = smallMask; mrem; mrem &= mrem - 1ull) {
                     const BigTriangle c = st[__builtin_ctzll(mrem)];
                     const uint32_t bx0 = c.boxX & 0xFFFFu, by0 = c.boxY & 0xFFFFu;
-                    coverBox(c.x0, c.y0, c.d0, c.x1, c.y1, c.d1, c.x2, c.y2, c.d2, c.sgn, bx0, by0, (c.boxX >> 16) - bx0 + 1u, (c.boxY >> 16) - by0 + 1u, lane, 64u,
-                             [depth, W](uint32_t px, uint32_t py, uint32_t bits) { atomicMax(&depth[(uint64_t)py * W + px], bits); });
+                    if constexpr (Vis) {
+                        const uint32_t tri = tb + (uint32_t)__builtin_ctzll(mrem);
+                        const bool texel = tri < kVisTriangles;
+                        const unsigned long long payload = va.slotBits | v << 7 | tri;
+                        unsigned long long* vis = va.vis;
+                        coverBox(c.x0, c.y0, c.d0, c.x1, c.y1, c.d1, c.x2, c.y2, c.d2, c.sgn, bx0, by0, (c.boxX >> 16) - bx0 + 1u, (c.boxY >> 16) - by0 + 1u, lane, 64u,
+                                 [depth, vis, W, texel, payload](uint32_t px, uint32_t py, uint32_t bits) {
+                                     const uint64_t i = (uint64_t)py * W + px;
+                                     atomicMax(&depth[i], bits);
+                                     if (texel) atomicMax(&vis[i], (unsigned long long)bits << 32 | payload); });
+                    } else {
+                        coverBox(c.x0, c.y0, c.d0, c.x1, c.y1, c.d1, c.x2, c.y2, c.d2, c.sgn, bx0, by0, (c.boxX >> 16) - bx0 + 1u, (c.boxY >> 16) - by0 + 1u, lane, 64u,
+                                 [depth, W](uint32_t px, uint32_t py, uint32_t bits) { atomicMax(&depth[(uint64_t)py * W + px], bits); });
+                    }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                       // st is rewritten by the next 64 triangles
                 __builtin_amdgcn_wave_barrier();
@@ -213,16 +250,21 @@ __global__ __launch_bounds__(kBlock) void rasterDepthKernel(RasterArgs a)
     }
 }
 
+__global__ __launch_bounds__(kBlock) void rasterDepthKernel(RasterArgs a) { rasterMain<false>(a, VisArgs{}); }
+__global__ __launch_bounds__(kBlock) void rasterVisibilityKernel(RasterArgs a, VisArgs va) { rasterMain<true>(a, va); }
+
 
 // The queued triangles, by screen tile.  Rounds of at most kTileList triangles: collect (all threads scan the queue,
 // LDS append), rasterise into the LDS tile, next round; then merge.  A tile is owned by one workgroup and this launch
 // follows "main" on the stream, so the merge needs no atomics.
-__global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a)
+template <bool Vis>
+__device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& va)
 {
     __shared__ uint32_t s_depth[kTile * kTile];
     __shared__ uint32_t s_list[kTileList];
     __shared__ uint32_t s_count;
     __shared__ uint32_t s_waveMin[kWaves];
+    __shared__ unsigned long long s_vis[Vis ? kTile * kTile : 1];                       // 32 KB beside the 16 KB depth tile (visibility only)
     const uint32_t tid = threadIdx.x;
     uint32_t n = *a.queueCount;
     n = n < kQueueCapacity ? n : kQueueCapacity;
@@ -232,6 +274,8 @@ __global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a)
         const uint32_t tx0 = (tile % tilesX) * kTile, ty0 = (tile / tilesX) * kTile;
         const uint32_t tx1 = min(tx0 + kTile, a.width) - 1u, ty1 = min(ty0 + kTile, a.height) - 1u;
         for (uint32_t i = tid; i < kTile * kTile; i += kBlock) s_depth[i] = 0u;
+        if constexpr (Vis)
+            for (uint32_t i = tid; i < kTile * kTile; i += kBlock) s_vis[i] = 0ull;
         bool any = false;
         float tileFar = 0.0f;                                                            // farthest depth in the tile (0 = something still uncovered)
         // candidates: the list of the tile's coarse bin, or the whole queue when that list overflowed
@@ -270,7 +314,13 @@ __global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a)
                 if ((k & 31u) == 0u && (k != 0u || any)) {
                     uint32_t mn = 0xFFFFFFFFu;
                     const uint32_t w = tx1 - tx0 + 1u, h = ty1 - ty0 + 1u;
-                    for (uint32_t i = tid; i < w * h; i += kBlock) { const uint32_t y = i / w, x = i - y * w; mn = min(mn, s_depth[y * kTile + x]); }
+                    if constexpr (Vis) {
+                        // the far depth of the TEXELS: a depth written by an out-of-contract triangle alone must not hide
+                        // the triangles that can still win the texel below it
+                        for (uint32_t i = tid; i < w * h; i += kBlock) { const uint32_t y = i / w, x = i - y * w; mn = min(mn, (uint32_t)(s_vis[y * kTile + x] >> 32)); }
+                    } else {
+                        for (uint32_t i = tid; i < w * h; i += kBlock) { const uint32_t y = i / w, x = i - y * w; mn = min(mn, s_depth[y * kTile + x]); }
+                    }
 #pragma unroll
                     for (int d = 32; d >= 1; d >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, d));
                     __syncthreads();                                                     // the previous value has been read by everyone
@@ -282,8 +332,19 @@ __global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a)
                 if (cm::max_(cm::max_(q.d0, q.d1), q.d2) * 0x1.00001p+0f < tileFar) continue;     // NaN or inf: never skipped
                 const uint32_t bx0 = max(q.boxX & 0xFFFFu, tx0), bx1 = min(q.boxX >> 16, tx1);
                 const uint32_t by0 = max(q.boxY & 0xFFFFu, ty0), by1 = min(q.boxY >> 16, ty1);
-                coverBox(q.x0, q.y0, q.d0, q.x1, q.y1, q.d1, q.x2, q.y2, q.d2, q.sgn, bx0, by0, bx1 - bx0 + 1u, by1 - by0 + 1u, tid, kBlock,
-                         [tx0, ty0](uint32_t px, uint32_t py, uint32_t bits) { atomicMax(&s_depth[(py - ty0) * kTile + (px - tx0)], bits); });
+                if constexpr (Vis) {
+                    const unsigned long long qp = va.queuePayload[s_list[k]];
+                    const bool texel = (qp >> 32) != 0ull;
+                    const unsigned long long payload = qp & 0xFFFFFFFFull;
+                    coverBox(q.x0, q.y0, q.d0, q.x1, q.y1, q.d1, q.x2, q.y2, q.d2, q.sgn, bx0, by0, bx1 - bx0 + 1u, by1 - by0 + 1u, tid, kBlock,
+                             [tx0, ty0, texel, payload](uint32_t px, uint32_t py, uint32_t bits) {
+                                 const uint32_t i = (py - ty0) * kTile + (px - tx0);
+                                 atomicMax(&s_depth[i], bits);
+                                 if (texel) atomicMax(&s_vis[i], (unsigned long long)bits << 32 | payload); });
+                } else {
+                    coverBox(q.x0, q.y0, q.d0, q.x1, q.y1, q.d1, q.x2, q.y2, q.d2, q.sgn, bx0, by0, bx1 - bx0 + 1u, by1 - by0 + 1u, tid, kBlock,
+                             [tx0, ty0](uint32_t px, uint32_t py, uint32_t bits) { atomicMax(&s_depth[(py - ty0) * kTile + (px - tx0)], bits); });
+                }
             }
             __syncthreads();
         }
@@ -293,13 +354,21 @@ __global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a)
                 const uint32_t y = i / w, x = i - y * w;
                 const uint32_t v = s_depth[y * kTile + x];
                 if (v) { uint32_t* g = &a.depth[(uint64_t)(ty0 + y) * a.width + tx0 + x]; if (v > *g) *g = v; }
+                if constexpr (Vis) {
+                    const unsigned long long t = s_vis[y * kTile + x];
+                    if (t) { unsigned long long* g = &va.vis[(uint64_t)(ty0 + y) * a.width + tx0 + x]; if (t > *g) *g = t; }
+                }
             }
         }
         __syncthreads();
     }
 }
 
-int recordRasterDepth(trhip::DispatchCtx& ctx)
+__global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a) { rasterTiles<false>(a, VisArgs{}); }
+__global__ __launch_bounds__(kBlock) void rasterVisibilityTilesKernel(RasterArgs a, VisArgs va) { rasterTiles<true>(a, va); }
+
+template <bool Vis>
+int recordRaster(trhip::DispatchCtx& ctx)
 {
     // Binding set of BasePassRenderers.cpp:463-479 (t0 instances, t1 vertices, t2 mesh data, t4 meshlets, t5 meshlet
     // vertex ids, t6 meshlet triangles, t7 amplification records) + the outputs of the cull half: t9 visible list,
@@ -337,11 +406,34 @@ int recordRasterDepth(trhip::DispatchCtx& ctx)
     a.depth = (uint32_t*)depth->ptr;
     a.width = depth->width; a.height = depth->height;
     TRHIP_REQUIRE(a.width <= 0xFFFFu && a.height <= 0xFFFFu, "%s: depth buffer %ux%u: at most 65535 pixels per side", ctx.shaderName, a.width, a.height);
+    VisArgs va = {};
+    if constexpr (Vis) {
+        // + u1 = the visibility buffer (RG32_UINT, render resolution), push constants {uint32 passSlot}
+        uint32_t visMip = 0;
+        trhip_texture_t* vis = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 1, &visMip);
+        TRHIP_REQUIRE(vis && visMip == 0 && vis->format == TRHIP_FORMAT_RG32_UINT, "%s: needs Texture_UAV u1 = the RG32_UINT visibility buffer, mip 0", ctx.shaderName);
+        TRHIP_REQUIRE(vis->width == depth->width && vis->height == depth->height,
+                      "%s: visibility buffer %ux%u does not match m_OutputResolution and the depth buffer %ux%u", ctx.shaderName, vis->width, vis->height, depth->width, depth->height);
+        bool pushBound = false;
+        for (uint32_t i = 0; i < ctx.numBindings; ++i) pushBound |= ctx.bindings[i].type == TRHIP_BIND_PUSH_CONSTANTS;
+        TRHIP_REQUIRE(pushBound && ctx.push && ctx.pushBytes >= 4, "%s: push constants {uint32 passSlot} (4 bytes) missing", ctx.shaderName);
+        uint32_t slot;
+        memcpy(&slot, ctx.push, 4);
+        TRHIP_REQUIRE(slot <= 3u, "%s: pass slot %u: 0..3 (early opaque, late opaque, early alpha mask, late alpha mask)", ctx.shaderName, slot);
+        TRHIP_REQUIRE(list->byteSize / 4 <= kVisListCapacity, "%s: visible list of %llu entries: the visibility payload holds list positions below 2^23",
+                      ctx.shaderName, (unsigned long long)(list->byteSize / 4));
+        va.vis = (unsigned long long*)vis->ptr;
+        va.slotBits = slot << 30;
+    }
     // queue of the triangles that are large on screen: scratch of this command; its counter is zeroed by the recording's
     // first clear launch
     a.queue = (BigTriangle*)ctx.scratch((size_t)kQueueCapacity * sizeof(BigTriangle));
     a.queueCount = (uint32_t*)ctx.scratch(16);
     TRHIP_REQUIRE(a.queue && a.queueCount, "%s: scratch allocation failed", ctx.shaderName);
+    if constexpr (Vis) {
+        va.queuePayload = (unsigned long long*)ctx.scratch((size_t)kQueueCapacity * 8);
+        TRHIP_REQUIRE(va.queuePayload, "%s: scratch allocation failed", ctx.shaderName);
+    }
     a.binsX = (a.width + (1u << kBinShift) - 1u) >> kBinShift;
     a.binsY = (a.height + (1u << kBinShift) - 1u) >> kBinShift;
     const uint32_t bins = a.binsX * a.binsY;
@@ -352,17 +444,27 @@ int recordRasterDepth(trhip::DispatchCtx& ctx)
     if (rc == TRHIP_OK) rc = ctx.cl->recordClearWords(a.binCount, bins, 0, true);
     if (rc != TRHIP_OK) return rc;
     const uint32_t grid = ctx.computeUnits() * 4u;
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(rasterDepthKernel, dim3(grid), dim3(kBlock), 0, s, a);
-        return trhip::launchStatus("rasterDepthKernel"); });
     const uint32_t tiles = ((a.width + kTile - 1) / kTile) * ((a.height + kTile - 1) / kTile);
     const uint32_t tileGrid = tiles < ctx.computeUnits() * 8u ? tiles : ctx.computeUnits() * 8u;
-    ctx.emit("tiles", [a, tileGrid](hipStream_t s) {
-        TRHIP_LAUNCH(rasterTilesKernel, dim3(tileGrid), dim3(kBlock), 0, s, a);
-        return trhip::launchStatus("rasterTilesKernel"); });
+    if constexpr (Vis) {
+        ctx.emit("main", [a, va, grid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterVisibilityKernel, dim3(grid), dim3(kBlock), 0, s, a, va);
+            return trhip::launchStatus("rasterVisibilityKernel"); });
+        ctx.emit("tiles", [a, va, tileGrid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterVisibilityTilesKernel, dim3(tileGrid), dim3(kBlock), 0, s, a, va);
+            return trhip::launchStatus("rasterVisibilityTilesKernel"); });
+    } else {
+        ctx.emit("main", [a, grid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterDepthKernel, dim3(grid), dim3(kBlock), 0, s, a);
+            return trhip::launchStatus("rasterDepthKernel"); });
+        ctx.emit("tiles", [a, tileGrid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterTilesKernel, dim3(tileGrid), dim3(kBlock), 0, s, a);
+            return trhip::launchStatus("rasterTilesKernel"); });
+    }
     return TRHIP_OK;
 }
 
-trhip::ShaderRegistrar r0("basepass_MS_Main_depth", recordRasterDepth, 0);
+trhip::ShaderRegistrar r0("basepass_MS_Main_depth", recordRaster<false>, 0);
+trhip::ShaderRegistrar r1("basepass_MS_Main_visibility", recordRaster<true>, 0);
 
 } // namespace

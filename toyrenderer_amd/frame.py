@@ -67,12 +67,17 @@ class FrameDriver:
 
     def __init__(self, dev: rhi.Device, scene: GpuScene, view, *, record_capacity: int, list_capacity: int | None = None,
                  culling_flags: int = 7, force_mesh_lod: int = -1, freeze_culling_camera: bool = False, alloc=None,
-                 shard_late=None, raster_depth: bool = False):
+                 shard_late=None, raster_depth: bool = False, visibility: bool = False):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
-        frame is submitted: phase 0 after each early instance cull, phase 1 before each late one (include/trhost.h)."""
-        self.raster_depth = bool(raster_depth)       # depth = the visible meshlets rasterised ("basepass_MS_Main_depth"), cleared per frame
+        frame is submitted: phase 0 after each early instance cull, phase 1 before each late one (include/trhost.h).
+        visibility: rasterise through "basepass_MS_Main_visibility" (implies raster_depth) into self.visibility (RG32_UINT)
+        and resolve self.motion (RG16_FLOAT, "basepass_PS_Main_motion") after the last slot; m_PrevWorldToClip is set."""
+        if visibility and shard_late is not None:
+            raise ValueError("visibility buffer with a shard exchange: list positions are per rank, not global")
+        self.visibility_on = bool(visibility)
+        self.raster_depth = bool(raster_depth) or self.visibility_on       # depth = the visible meshlets rasterised ("basepass_MS_Main_depth"), cleared per frame
         assert not self.raster_depth or scene.vertices is not None, "raster_depth needs GpuScene.set_geometry()"
         self.shard_late = shard_late
         self.shardInfo = [dev.create_buffer(8, f"ShardLateInfo{b}") for b in (0, 1)] if shard_late is not None else None
@@ -91,6 +96,10 @@ class FrameDriver:
         init = dev.create_command_list()
         init.open(); init.clear_texture_f32(self.hzb, 0.0); init.clear_texture_f32(self.depth, 0.0); init.close()
         dev.execute(init); dev.wait_idle(); init.release()
+        self.visibility = self.motion = None
+        if self.visibility_on:                       # GBufferRenderer's visibility buffer + GBufferMotion, render resolution
+            self.visibility = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RG32_UINT, "VisibilityBuffer")
+            self.motion = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RG16_FLOAT, "GBufferMotion")
         # BasePassRenderer::Setup (:223-296); one set of outputs per pass slot (DESIGN.md "Outputs")
         n = max(scene.numInstances, 1)
 
@@ -144,6 +153,8 @@ class FrameDriver:
         k["m_P11"] = v.viewToClip[1, 1]
         k["m_NearPlane"] = v.nearPlane
         k["m_OutputResolution"] = (v.renderW, v.renderH)
+        if self.visibility_on:                                                           # Scene.cpp:116-118 on this build's raster camera
+            k["m_PrevWorldToClip"] = I.world_to_clip(v.prevWorldToView, v.viewToClip)
         return k
 
     # ---- BasePassRenderer::GPUCulling (:298-404) ------------------------------------------------
@@ -201,7 +212,22 @@ class FrameDriver:
         if self.raster_depth:                                                            # the mesh + pixel stage of the same draw: depth only
             b = [CB(0, cb), SRV(0, sc.instances), SRV(1, sc.vertices), SRV(2, sc.meshData), SRV(4, sc.meshlets), SRV(5, sc.meshletVertexIds),
                  SRV(6, sc.meshletTriangles), SRV(7, self.records[slot]), SRV(9, self.visibleList[slot]), TEX_UAV(0, self.depth, 0)]
-            cl.dispatch_indirect("basepass_MS_Main_depth", b, self.drawArgs[slot])
+            if self.visibility_on:                                                       # + u1 = visibility buffer, push = pass slot
+                cl.dispatch_indirect("basepass_MS_Main_visibility", b + [TEX_UAV(1, self.visibility, 0), PUSH(1)], self.drawArgs[slot],
+                                     push=np.array([slot], np.uint32))
+            else:
+                cl.dispatch_indirect("basepass_MS_Main_depth", b, self.drawArgs[slot])
+
+    def _resolve_motion(self, cl):
+        """GBufferMotion of every pixel the base pass drew (basepass.hlsl:226-237), once after the last slot."""
+        sc, v = self.scene, self.view
+        cb = cl.constant_buffer(self._basepass_consts(False), "BasePassConstants")
+        b = [CB(0, cb), SRV(0, sc.instances), SRV(1, sc.vertices), SRV(2, sc.meshData), SRV(4, sc.meshlets), SRV(5, sc.meshletVertexIds),
+             SRV(6, sc.meshletTriangles), TEX_SRV(18, self.visibility), TEX_UAV(0, self.motion, 0)]
+        for s in range(4):                                                               # slots without buffers: an empty stand-in
+            b += [SRV(10 + s, self.records[s] if s < self.num_slots else self.dummy),
+                  SRV(14 + s, self.visibleList[s] if s < self.num_slots else self.dummy)]
+        cl.dispatch("basepass_PS_Main_motion", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
 
     # ---- BasePassRenderer::GenerateHZB (:505-542) + SPD::Execute (FFXHelpers.cpp:36-115) --------
     def _generate_hzb(self, cl):
@@ -234,6 +260,9 @@ class FrameDriver:
 
         if self.raster_depth:
             cl.clear_texture_f32(self.depth, 0.0)                                        # depth cleared to far at the start of the base pass
+        if self.visibility_on:
+            cl.clear_texture_u32(self.visibility, 0)                                     # 0 = nothing drawn
+            cl.clear_texture_f32(self.motion, 0.0)
 
         def do(slot, late, am):
             self.ran[slot] = self._gpu_culling(cl, slot, late, am)
@@ -245,9 +274,13 @@ class FrameDriver:
             do(1, True, False)
             do(2, False, True)
             do(3, True, True)
+            if self.visibility_on:
+                self._resolve_motion(cl)
             self._generate_hzb(cl)
         else:
             do(2, False, True)
+            if self.visibility_on:
+                self._resolve_motion(cl)
         if query is not None:
             cl.end_pipeline_stats(query)
         cl.close()
@@ -284,3 +317,6 @@ class FrameDriver:
         for b in (self.lateArgs, self.lateCount, self.lateIds, self.spdAtomic, self.dummy, *(self.shardInfo or ())):
             b.release()
         self.hzb.release(); self.depth.release()
+        for t in (self.visibility, self.motion):
+            if t is not None:
+                t.release()

@@ -24,6 +24,7 @@ HOST_SYMBOLS = [
     "trhost_set_pipeline_statistics", "trhost_pipeline_statistics",
     "trhost_rccl_allgather", "trhost_exchange_create", "trhost_exchange_run", "trhost_exchange_wait", "trhost_exchange_outputs",
     "trhost_exchange_destroy", "trhost_load_geometry", "trhost_set_raster_depth", "trhost_download_depth",
+    "trhost_set_visibility_buffer", "trhost_download_visibility", "trhost_download_motion",
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
 ]
@@ -80,6 +81,9 @@ def load() -> C.CDLL:
     L.trhost_load_scene_cached.argtypes = [C.c_char_p, vp, u32, vp, u32, vp, u32]
     L.trhost_set_raster_depth.argtypes = [C.c_int]
     L.trhost_download_depth.argtypes = [vp, u64]
+    L.trhost_set_visibility_buffer.argtypes = [C.c_int]
+    L.trhost_download_visibility.argtypes = [vp, u64]
+    L.trhost_download_motion.argtypes = [vp, u64]
     L.trhost_upload_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_download_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_hzb_info.argtypes = [C.POINTER(u32)] * 3
@@ -218,6 +222,24 @@ class Renderer:
     def set_raster_depth(self, on: bool = True):
         """The frame rasterises the depth of its own visible meshlets instead of taking the uploaded depth image."""
         _check(load().trhost_set_raster_depth(int(on)))
+
+    def set_visibility_buffer(self, on: bool = True):
+        """Per-pixel visibility buffer + motion target (implies raster depth; include/trhost.h)."""
+        _check(load().trhost_set_visibility_buffer(int(on)))
+
+    def download_visibility(self) -> np.ndarray:
+        """The last frame's visibility buffer: uint64 [H, W]."""
+        self.wait_idle()
+        v = np.empty((self.render[1], self.render[0]), np.uint64)
+        _check(load().trhost_download_visibility(v.ctypes.data, v.nbytes))
+        return v
+
+    def download_motion(self) -> np.ndarray:
+        """The last frame's motion target: float16 [H, W, 2] (pixels)."""
+        self.wait_idle()
+        m = np.empty((self.render[1], self.render[0], 2), np.float16)
+        _check(load().trhost_download_motion(m.ctypes.data, m.nbytes))
+        return m
 
     def download_depth(self) -> np.ndarray:
         self.wait_idle()

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("TRHIP_LIB") or os.path.join(_HERE, "lib", "libtrhip.s
 
 FORMAT_R16_FLOAT = 1
 FORMAT_R32_FLOAT = 2
+FORMAT_RG32_UINT = 3      # visibility buffer: one u64 per texel
+FORMAT_RG16_FLOAT = 4     # motion target: two fp16 per texel
 
 BIND_CONSTANT_BUFFER, BIND_PUSH_CONSTANTS, BIND_STRUCTURED_SRV, BIND_STRUCTURED_UAV, BIND_TEXTURE_SRV, BIND_TEXTURE_UAV, BIND_SAMPLER = range(7)
 
@@ -31,7 +33,7 @@ ABI_SYMBOLS = [
     "trhip_buffer_upload", "trhip_buffer_download", "trhip_texture_upload", "trhip_texture_download",
     "trhip_buffer_mark_written", "trhip_texture_mark_written",
     "trhip_cmd_create", "trhip_cmd_release", "trhip_cmd_open", "trhip_cmd_close", "trhip_cmd_write_buffer",
-    "trhip_cmd_clear_buffer_u32", "trhip_cmd_clear_texture_f32", "trhip_cmd_copy_buffer", "trhip_cmd_copy_texture", "trhip_cmd_host_callback", "trhip_cmd_dispatch", "trhip_cmd_dispatch_indirect",
+    "trhip_cmd_clear_buffer_u32", "trhip_cmd_clear_texture_f32", "trhip_cmd_clear_texture_u32", "trhip_cmd_copy_buffer", "trhip_cmd_copy_texture", "trhip_cmd_host_callback", "trhip_cmd_dispatch", "trhip_cmd_dispatch_indirect",
     "trhip_cmd_begin_timer", "trhip_cmd_end_timer", "trhip_cmd_begin_marker", "trhip_cmd_end_marker",
     "trhip_queue_execute",
     "trhip_timer_create", "trhip_timer_release", "trhip_timer_get_ms",
@@ -139,6 +141,7 @@ def load() -> C.CDLL:
     L.trhip_cmd_write_buffer.argtypes = [vp, vp, u64, vp, u64]
     L.trhip_cmd_clear_buffer_u32.argtypes = [vp, vp, u32]
     L.trhip_cmd_clear_texture_f32.argtypes = [vp, vp, C.c_float]
+    L.trhip_cmd_clear_texture_u32.argtypes = [vp, vp, u32]
     L.trhip_cmd_copy_buffer.argtypes = [vp, vp, u64, vp, u64, u64]
     L.trhip_cmd_copy_texture.argtypes = [vp, vp, vp]
     L.trhip_cmd_host_callback.argtypes = [vp, HOST_FN, vp]
@@ -229,7 +232,10 @@ class Texture:
         return max(self.w >> k, 1), max(self.hgt >> k, 1)
 
     def _dtype(self):
-        return np.uint16 if self.format == FORMAT_R16_FLOAT else np.float32
+        return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16}.get(self.format, np.float32)
+
+    def _shape(self, mw: int, mh: int):
+        return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw)
 
     def upload_mip(self, k: int, arr: np.ndarray):
         arr = np.ascontiguousarray(arr, self._dtype())
@@ -237,7 +243,7 @@ class Texture:
 
     def download_mip(self, k: int) -> np.ndarray:
         mw, mh = self.mip_dims(k)
-        out = np.empty((mh, mw), self._dtype())
+        out = np.empty(self._shape(mw, mh), self._dtype())
         _check(load().trhip_texture_download(self.h, k, out.ctypes.data, out.nbytes))
         return out
 
@@ -333,6 +339,9 @@ class CommandList:
 
     def clear_texture_f32(self, tex: Texture, value: float):
         _check(load().trhip_cmd_clear_texture_f32(self.h, tex.h, value))
+
+    def clear_texture_u32(self, tex: Texture, value: int):
+        _check(load().trhip_cmd_clear_texture_u32(self.h, tex.h, value))
 
     def copy_buffer(self, dst: Buffer, src: Buffer, nbytes: int, dst_offset: int = 0, src_offset: int = 0):
         _check(load().trhip_cmd_copy_buffer(self.h, dst.h, dst_offset, src.h, src_offset, nbytes))
