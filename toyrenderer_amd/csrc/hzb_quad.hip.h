@@ -94,7 +94,7 @@ inline QuadArgs quadArgs(const trhip_texture_t* tex)
     QuadArgs a;
     memset(&a, 0, sizeof a);
     a.base = (const _Float16*)tex->ptr;
-    a.out = (_Float16*)tex->quad;
+    a.out = (_Float16*)tex->quad.ptr;
     a.width = tex->width; a.height = tex->height; a.mips = tex->mips; a.total = tex->quadTotal;
     uint32_t strips = 0;
     for (uint32_t i = 0; i < tex->mips; ++i) {

@@ -1467,35 +1467,16 @@ __global__ __launch_bounds__(256) void meshletStreamKernel(const MeshletData* __
     }
 }
 
-int meshletStreamEnsure(trhip_buffer_t* meshlets)
-{
-    const uint64_t n = meshlets->byteSize / sizeof(MeshletData);
-    const uint64_t need = meshletStreamBytes(n);
-    if (meshlets->cullStreamBytes < need) {
-        TRHIP_HIP(hipSetDevice(meshlets->dev->index));
-        if (meshlets->cullStream) {
-            int rc = meshlets->dev->syncAll();
-            if (rc != TRHIP_OK) return rc;
-            (void)hipFree(meshlets->cullStream);
-            meshlets->cullStream = nullptr; meshlets->cullStreamBytes = 0;
-        }
-        TRHIP_HIP(hipMalloc(&meshlets->cullStream, (size_t)need));
-        meshlets->cullStreamBytes = need;
-        meshlets->cullStreamVersion = 0;
-    }
-    return TRHIP_OK;
-}
-
 // at submission time, on the stream of the cull that follows: no-op unless the meshlet buffer was written since the stream was built
 int meshletStreamLaunchBuild(trhip_buffer_t* meshlets, hipStream_t s)
 {
-    const uint64_t v = meshlets->version;
-    if (meshlets->cullStreamVersion == v) return TRHIP_OK;
+    const trhip::Stamp from = { meshlets->version };
+    if (meshlets->cullStream.current(from)) return TRHIP_OK;
     const uint64_t n = meshlets->byteSize / sizeof(MeshletData);
     const uint64_t blocks = (n + 255u) / 256u;
     TRHIP_LAUNCH(meshletStreamKernel, dim3((uint32_t)(blocks < 65536u ? (blocks ? blocks : 1u) : 65536u)), dim3(256), 0, s,
-                       (const MeshletData*)meshlets->ptr, n, meshletStreamLayout(meshlets->cullStream, n));
-    meshlets->cullStreamVersion = v;
+                       (const MeshletData*)meshlets->ptr, n, meshletStreamLayout(meshlets->cullStream.ptr, n));
+    meshlets->cullStream.markBuilt(from);
     return trhip::launchStatus("meshletStreamKernel");
 }
 
@@ -1543,7 +1524,7 @@ int recordASMain(trhip::DispatchCtx& ctx)
             if (useTable) {
                 rc = trhip::hzbQuadEnsure(hzb);
                 if (rc != TRHIP_OK) return rc;
-                a.quad.base = (const _Float16*)hzb->quad;
+                a.quad.base = (const _Float16*)hzb->quad.ptr;
                 a.quad.total = hzb->quadTotal;
                 for (uint32_t m = 0; m < hzb->mips; ++m) a.quad.offset[m] = hzb->quadOffset[m];
             }
@@ -1552,9 +1533,9 @@ int recordASMain(trhip::DispatchCtx& ctx)
     if (rc != TRHIP_OK) return rc;
     a.meshlets = (const MeshletData*)meshlets->ptr;
     TRHIP_REQUIRE(meshlets->byteSize >= sizeof(MeshletData), "%s: empty meshlet buffer", ctx.shaderName);
-    rc = meshletStreamEnsure(meshlets);
+    rc = meshlets->cullStream.allocate(meshlets->dev, meshletStreamBytes(meshlets->byteSize / sizeof(MeshletData)));
     if (rc != TRHIP_OK) return rc;
-    a.stream = meshletStreamLayout(meshlets->cullStream, meshlets->byteSize / sizeof(MeshletData));
+    a.stream = meshletStreamLayout(meshlets->cullStream.ptr, meshlets->byteSize / sizeof(MeshletData));
     a.records = (const MeshletAmplificationData*)records->ptr;
     a.dispatchArgs = (const uint32_t*)((const char*)ctx.argsBuffer->ptr + ctx.argsOffset);
     a.argsWords = (ctx.argsBuffer->byteSize - ctx.argsOffset) >= 16 ? 4u : 3u;
@@ -1571,14 +1552,14 @@ int recordASMain(trhip::DispatchCtx& ctx)
     a.listCapacity = lcap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lcap;
     a.drawArgs = (uint32_t*)drawArgs->ptr;
     static const bool noPerm = getenv("TRHIP_AS_NO_PERM") != nullptr;                // experiments: process the records in list order
-    if (!noPerm && records->sidecar && records->sidecarBytes >= 256 + (uint64_t)a.recordCapacity * 16) {
-        a.permHeader = (const uint32_t*)records->sidecar;
+    if (!noPerm && records->order.ptr && records->order.bytes >= 256 + (uint64_t)a.recordCapacity * 16) {
+        a.permHeader = (const uint32_t*)records->order.ptr;
         a.perm = (const uint4*)(a.permHeader + 64);
     }
     rc = trhip::instanceCacheEnsure(instances);
     if (rc != TRHIP_OK) return rc;
     a.numInstances = (uint32_t)(instances->byteSize / sizeof(BasePassInstanceConstants));
-    a.cache = instanceCacheLayout(instances->cullCache, a.numInstances);
+    a.cache = instanceCacheLayout(instances->cullCache.ptr, a.numInstances);
     a.maxBatches = (a.recordCapacity + kBatch - 1) / kBatch;
     a.batchSum = (uint32_t*)(a.recordCapacity >= (1u << 19) ? ctx.scratchSide((size_t)a.maxBatches * 4)   // only the list build uses it
                                                             : ctx.scratch((size_t)a.maxBatches * 4));
@@ -1599,15 +1580,12 @@ int recordASMain(trhip::DispatchCtx& ctx)
     const uint32_t needBlocks = (a.recordCapacity + kCullBatch * kCullWaves - 1) / (kCullBatch * kCullWaves);
     if (grid > needBlocks) grid = needBlocks;
     if (grid == 0) grid = 1;
-    // the list build's group count: a word of back-end private memory that lives with the mask buffer (its sidecar): written by
-    // the cull on the main stream, read by the list build, possibly on the side stream -- the same address in every recording,
-    // so the hazard tracking orders the next frame's cull after this frame's list build through it
-    if (!visMask->sidecar) {
-        TRHIP_HIP(hipSetDevice(visMask->dev->index));
-        TRHIP_HIP(hipMalloc(&visMask->sidecar, 256));
-        visMask->sidecarBytes = 256;
-    }
-    a.listGroups = (uint32_t*)visMask->sidecar;
+    // the list build's group count: a word of back-end private memory that lives with the mask buffer (trhip_buffer_t::listCount):
+    // written by the cull on the main stream, read by the list build, possibly on the side stream -- the same address in every
+    // recording, so the hazard tracking orders the next frame's cull after this frame's list build through it
+    rc = visMask->listCount.allocate(visMask->dev, 256);
+    if (rc != TRHIP_OK) return rc;
+    a.listGroups = (uint32_t*)visMask->listCount.ptr;
     ctx.cl->use(a.listGroups, ctx.cl->ops.size(), true);
     if (useTable) a.bands = cm::projBands(k->m_P00, k->m_P11, hzb->width, hzb->height);
     static const bool noShortPass = getenv("TRHIP_NO_SHORT_PASS") != nullptr;          // tests: the texel kernel's batch path on small passes too
@@ -1615,7 +1593,7 @@ int recordASMain(trhip::DispatchCtx& ctx)
     const uint32_t flags = k->m_CullingFlags & 7u;
     trhip_texture_t* quadOwner = useTable ? hzb : nullptr;
     const bool table = useTable;
-    if (quadOwner) ctx.cl->use(quadOwner->quad, ctx.cl->ops.size(), false);     // the kernel reads the table: ordered after a side-stream rebuild
+    if (quadOwner) ctx.cl->use(quadOwner->quad.ptr, ctx.cl->ops.size(), false); // the kernel reads the table: ordered after a side-stream rebuild
     ctx.emit("cull", [a, grid, flags, quadOwner, table, instances, meshData, meshlets](hipStream_t s) {
         // A virtual buffer bound to other memory after this list was recorded (trhip_buffer_bind_memory): the recorded pointers
         // are the old memory's, the derived stream would be built from the new one.  nvrhi rebuilds binding sets on such a

@@ -56,8 +56,8 @@ struct InstanceCullArgs
     uint32_t* bases;                // [0] X before the pass, [1] late count before the pass
     uint32_t numBlocks;
     // screen-tile binning of the submitted instances (PROCESSING order of the meshlet pass only; the
-    // record order above is untouched): a counting sort by tile, see "Large passes" below; perm lives in the records
-    // buffer's sidecar: {valid, count, ...} header (64 words) followed by one 16-byte entry per group.
+    // record order above is untouched): a counting sort by tile, see "Large passes" below; perm lives with the records
+    // buffer (trhip_buffer_t::order): {valid, count, ...} header (64 words) followed by one 16-byte entry per group.
     uint32_t* tileHist;             // large passes: [workgroup][kNumTiles] groups per tile -> (scan) groups of the tile in earlier workgroups
     uint32_t* tileTotal;            // [kNumTiles]
     uint16_t* tileOf;               // per entry
@@ -727,10 +727,10 @@ std::function<int(hipStream_t)> fusedEarlyLaunch(const InstanceCullArgs& a, trhi
         trhip::QuadArgs q;
         memset(&q, 0, sizeof q);
         uint32_t strips = 0;
-        if (quadOwner && quadOwner->quadBuiltVersion != quadOwner->version) {            // (submission order: every earlier write of the HZB is counted)
+        if (quadOwner && !quadOwner->quad.current({ quadOwner->version })) {           // (submission order: every earlier write of the HZB is counted)
             q = trhip::quadArgs(quadOwner);
             strips = q.firstStrip[q.mips];
-            quadOwner->quadBuiltVersion = quadOwner->version;
+            quadOwner->quad.markBuilt({ quadOwner->version });
         }
         TRHIP_LAUNCH(instanceFusedKernel<0>, dim3(a.numBlocks + strips), dim3(kBlock), 0, s, a, q);
         return trhip::launchStatus("instanceFusedKernel"); };
@@ -752,11 +752,11 @@ std::function<int(hipStream_t)> scanEarlyLaunch(const InstanceCullArgs& a, trhip
         memset(&q, 0, sizeof q);
         uint32_t extra = 0, stripEnd = 0;
         if (share) share->stale = false;
-        if (quadOwner && quadOwner->quadBuiltVersion != quadOwner->version) {            // (submission order: every earlier write of the HZB is counted)
+        if (quadOwner && !quadOwner->quad.current({ quadOwner->version })) {           // (submission order: every earlier write of the HZB is counted)
             q = trhip::quadArgs(quadOwner);
             stripEnd = share ? quadScanStrips(q.firstStrip[q.mips]) : q.firstStrip[q.mips];
             extra = (stripEnd + kScanStripsPerGroup - 1u) / kScanStripsPerGroup;
-            quadOwner->quadBuiltVersion = quadOwner->version;
+            quadOwner->quad.markBuilt({ quadOwner->version });
             if (share) share->stale = true;
         }
         TRHIP_LAUNCH(instanceScanKernel<0>, dim3(1 + kScanTileGroups + extra), dim3(kScanThreads), 0, s, a, q, stripEnd);
@@ -824,7 +824,7 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
     // instance cull cache: (re)built, in submission order, when the instance or the mesh buffer has been written
     rc = trhip::instanceCacheEnsure(instances);
     if (rc != TRHIP_OK) return rc;
-    a.cache = instanceCacheLayout(instances->cullCache, instances->byteSize / sizeof(BasePassInstanceConstants));
+    a.cache = instanceCacheLayout(instances->cullCache.ptr, instances->byteSize / sizeof(BasePassInstanceConstants));
     a.numInstances = (uint32_t)(instances->byteSize / sizeof(BasePassInstanceConstants));
     ctx.emit("instance_cache", [instances, meshData](hipStream_t s) { return trhip::instanceCacheLaunchBuild(instances, meshData, s); });
     static const bool noFused = getenv("TRHIP_NO_FUSED_INSTANCE") != nullptr;          // tests: the three-kernel path on small passes
@@ -840,20 +840,12 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
     a.tileOf = (uint16_t*)ctx.scratch((size_t)nMax * 2);
     a.lodSel = (uint2*)ctx.scratch((size_t)nMax * 8);
     TRHIP_REQUIRE(a.word && a.localOff && a.blockGroups && a.blockLateSubmit && a.bases && a.tileHist && a.tileTotal && a.tileOf && a.lodSel, "%s: scratch allocation failed", ctx.shaderName);
-    // sidecar of the amplification buffer: header + one u32 per record slot
-    {
-        const uint64_t need = (uint64_t)kPermHeaderWords * 4 + (uint64_t)a.maxGroups * 16;
-        if (records->sidecarBytes < need) {
-            if (records->sidecar) { (void)hipStreamSynchronize(ctx.cl->dev->stream); (void)hipFree(records->sidecar); records->sidecar = nullptr; records->sidecarBytes = 0; }
-            void* p = nullptr;
-            TRHIP_HIP(hipMalloc(&p, (size_t)need));
-            records->sidecar = p;
-            records->sidecarBytes = need;
-        }
-        a.permHeader = (uint32_t*)records->sidecar;
-        a.perm = (uint4*)(a.permHeader + kPermHeaderWords);
-        a.permCapacity = a.maxGroups;
-    }
+    // processing order, with the amplification buffer: header + one 16-byte entry per record slot
+    rc = records->order.allocate(records->dev, (uint64_t)kPermHeaderWords * 4 + (uint64_t)a.maxGroups * 16);
+    if (rc != TRHIP_OK) return rc;
+    a.permHeader = (uint32_t*)records->order.ptr;
+    a.perm = (uint4*)(a.permHeader + kPermHeaderWords);
+    a.permCapacity = a.maxGroups;
     // The early meshlet cull that follows this pass resolves its HZB lookups through the footprint-min table of
     // this same HZB (hzb_quad.hip.h): bring the table up to date with extra workgroups of this pass's own scan / fused launch.
     static const bool noInlineQuad = getenv("TRHIP_NO_INLINE_QUAD") != nullptr;         // experiments: its own launch on the side stream, beside the instance pass
@@ -873,7 +865,7 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
         a.fusedStatus = (unsigned long long*)mem;
         a.fusedTicket = mem + (size_t)a.numBlocks * kFusedStatusStride * 2;
         trhip_texture_t* quadOwner = inlineQuad ? hzb : nullptr;
-        if (quadOwner) ctx.cl->use(quadOwner->quad, ctx.cl->ops.size(), true);           // this command (re)writes the table
+        if (quadOwner) ctx.cl->use(quadOwner->quad.ptr, ctx.cl->ops.size(), true);       // this command (re)writes the table
         if (LATE) ctx.emit("fused", [a](hipStream_t s) {
             trhip::QuadArgs q;
             memset(&q, 0, sizeof q);
@@ -889,7 +881,7 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
         return trhip::launchStatus("instanceClassifyKernel"); });
     trhip_texture_t* quadOwner = inlineQuad ? hzb : nullptr;
     std::shared_ptr<QuadShare> share = quadOwner ? std::make_shared<QuadShare>() : nullptr;
-    if (quadOwner) ctx.cl->use(quadOwner->quad, ctx.cl->ops.size(), true);               // the scan command (re)writes the table (and the emit command behind it)
+    if (quadOwner) ctx.cl->use(quadOwner->quad.ptr, ctx.cl->ops.size(), true);           // the scan command (re)writes the table (and the emit command behind it)
     if (LATE) ctx.emit("scan", [a](hipStream_t s) {
         trhip::QuadArgs q;
         memset(&q, 0, sizeof q);
@@ -897,7 +889,7 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
         return trhip::launchStatus("instanceScanKernel"); });
     else ctx.emit("scan", scanEarlyLaunch(a, quadOwner, share));
     const size_t scanOp = ctx.cl->ops.size() - 1;
-    if (quadOwner) ctx.cl->use(quadOwner->quad, ctx.cl->ops.size(), true);               // the emit command writes the rest of the table
+    if (quadOwner) ctx.cl->use(quadOwner->quad.ptr, ctx.cl->ops.size(), true);           // the emit command writes the rest of the table
     ctx.emit("emit", [a, quadOwner, share](hipStream_t s) {
         trhip::QuadArgs q;
         memset(&q, 0, sizeof q);
@@ -959,31 +951,19 @@ int instanceCacheEnsure(trhip_buffer_t* instances)
 {
     const uint64_t n = instances->byteSize / sizeof(BasePassInstanceConstants);
     TRHIP_REQUIRE(n >= 1 && n <= 0xFFFFFFFFull, "instance cull cache: instance buffer '%s' size out of range", instances->name.c_str());
-    if (instances->cullCacheBytes < n * kInstanceCacheBytesPerInstance) {
-        TRHIP_HIP(hipSetDevice(instances->dev->index));
-        if (instances->cullCache) {
-            int rc = instances->dev->syncAll();
-            if (rc != TRHIP_OK) return rc;
-            (void)hipFree(instances->cullCache);
-            instances->cullCache = nullptr; instances->cullCacheBytes = 0;
-        }
-        TRHIP_HIP(hipMalloc(&instances->cullCache, (size_t)(n * kInstanceCacheBytesPerInstance)));
-        instances->cullCacheBytes = n * kInstanceCacheBytesPerInstance;
-        instances->cullCacheInstVersion = 0;
-    }
-    return TRHIP_OK;
+    return instances->cullCache.allocate(instances->dev, n * kInstanceCacheBytesPerInstance);
 }
 
 int instanceCacheLaunchBuild(trhip_buffer_t* instances, trhip_buffer_t* meshData, hipStream_t s)
 {
-    const uint64_t vi = instances->version, vm = meshData->version;
-    if (instances->cullCacheInstVersion == vi && instances->cullCacheMeshVersion == vm && instances->cullCacheMesh == meshData->ptr) return TRHIP_OK;
+    const Stamp from = { instances->version, meshData->ptr, meshData->version };
+    if (instances->cullCache.current(from)) return TRHIP_OK;
     const uint32_t n = (uint32_t)(instances->byteSize / sizeof(BasePassInstanceConstants));
     const uint64_t numMeshes = meshData->byteSize / sizeof(MeshData);
     TRHIP_LAUNCH(instanceCacheKernel, dim3((n + 255u) / 256u), dim3(256), 0, s, (const BasePassInstanceConstants*)instances->ptr, n,
                        (const MeshData*)meshData->ptr, (uint32_t)(numMeshes > 0xFFFFFFFFull ? 0xFFFFFFFFull : numMeshes),
-                       instanceCacheLayout(instances->cullCache, n));
-    instances->cullCacheInstVersion = vi; instances->cullCacheMeshVersion = vm; instances->cullCacheMesh = meshData->ptr;
+                       instanceCacheLayout(instances->cullCache.ptr, n));
+    instances->cullCache.markBuilt(from);
     return launchStatus("instanceCacheKernel");
 }
 

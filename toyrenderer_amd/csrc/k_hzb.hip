@@ -367,23 +367,16 @@ int hzbQuadEnsure(trhip_texture_t* tex)
     }
     TRHIP_REQUIRE(total < (1ull << 31), "footprint-min table: HZB %ux%u too large", tex->width, tex->height);
     tex->quadTotal = (uint32_t)total;
-    if (tex->quadBytes < total * 2) {
-        TRHIP_HIP(hipSetDevice(tex->dev->index));
-        if (tex->quad) { int rc = tex->dev->syncAll(); if (rc != TRHIP_OK) return rc; (void)hipFree(tex->quad); tex->quad = nullptr; tex->quadBytes = 0; }
-        TRHIP_HIP(hipMalloc(&tex->quad, (size_t)total * 2));
-        tex->quadBytes = total * 2;
-        tex->quadBuiltVersion = 0;
-    }
-    return TRHIP_OK;
+    return tex->quad.allocate(tex->dev, total * 2);
 }
 
 int hzbQuadLaunchBuild(trhip_texture_t* tex, hipStream_t s)
 {
-    const uint64_t v = tex->version;                   // called while commands are submitted: every earlier write is counted
-    if (tex->quadBuiltVersion == v) return TRHIP_OK;   // nothing wrote the HZB since the last build
+    const Stamp from = { tex->version };               // called while commands are submitted: every earlier write is counted
+    if (tex->quad.current(from)) return TRHIP_OK;      // nothing wrote the HZB since the last build
     const QuadArgs a = quadArgs(tex);
     TRHIP_LAUNCH(hzbQuadBuildKernel, dim3(a.firstStrip[a.mips]), dim3(256), 0, s, a);
-    tex->quadBuiltVersion = v;
+    tex->quad.markBuilt(from);
     return launchStatus("hzbQuadBuildKernel");
 }
 
@@ -391,7 +384,7 @@ int hzbQuadEmitBuild(const DispatchCtx& ctx, trhip_texture_t* tex)
 {
     int rc = hzbQuadEnsure(tex);
     if (rc != TRHIP_OK) return rc;
-    ctx.emitSide("footprint_min", [tex](hipStream_t s) { return hzbQuadLaunchBuild(tex, s); }, { { tex->ptr, false }, { tex->quad, true } });
+    ctx.emitSide("footprint_min", [tex](hipStream_t s) { return hzbQuadLaunchBuild(tex, s); }, { { tex->ptr, false }, { tex->quad.ptr, true } });
     return TRHIP_OK;
 }
 

@@ -8,9 +8,9 @@
 //   * an indirect one: one tiny launch right behind it reads its arguments (statsIndirectKernel);
 //   * basepass_AS_Main: one launch behind its cull (statsASKernel) adds 32 x G amplification invocations, 96 mesh invocations
 //     per visible meshlet and the triangle count of every visible meshlet.  The counts come from a derived array of ONE
-//     BYTE per meshlet of the buffer bound at t4 (trhip_buffer_t::triCounts), built on the device like the meshlet cull
-//     stream and rebuilt when the buffer's version moves: the 32-byte MeshletData of the visible meshlets would be a gather
-//     of ~1.8 GB per frame at C3, the bytes are ~36 B per group.
+//     BYTE per meshlet of the buffer bound at t4 (trhip_buffer_t::triCounts, derived data like the meshlet cull stream:
+//     rebuilt on the device when the buffer's version moves): the 32-byte MeshletData of the visible meshlets would be a
+//     gather of ~1.8 GB per frame at C3, the bytes are ~36 B per group.
 // Sums of integers: the order of the atomics does not matter, the results are exact.
 #include <cstring>
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kStatsBlock) void statsASKernel(StatsASArgs s)
         cnt = cnt < 32u ? cnt : 32u;
         if (first + cnt > a.numMeshlets) cnt = (uint32_t)(a.numMeshlets - first);
         mask &= cnt >= 32u ? 0xFFFFFFFFu : (1u << cnt) - 1u;
-        // bytes [first, first + 32) lie in the 9 dwords from first & ~3 (the array is padded: triCountsEnsure)
+        // bytes [first, first + 32) lie in the 9 dwords from first & ~3 (the array is padded: statsEmitAS)
         const uint32_t* w = reinterpret_cast<const uint32_t*>(s.tri) + (first >> 2);
         const uint32_t sh = (uint32_t)(first & 3u);
         uint32_t words[9];
@@ -116,35 +116,16 @@ __global__ __launch_bounds__(kStatsBlock) void statsASKernel(StatsASArgs s)
     }
 }
 
-int triCountsEnsure(trhip_buffer_t* meshlets)
-{
-    const uint64_t n = meshlets->byteSize / sizeof(MeshletData);
-    const uint64_t need = ((n + 255u) & ~uint64_t(255)) + 256u;       // + padding: statsASKernel reads 9 dwords per group
-    if (meshlets->triCountsBytes < need) {
-        TRHIP_HIP(hipSetDevice(meshlets->dev->index));
-        if (meshlets->triCounts) {
-            int rc = meshlets->dev->syncAll();
-            if (rc != TRHIP_OK) return rc;
-            (void)hipFree(meshlets->triCounts);
-            meshlets->triCounts = nullptr; meshlets->triCountsBytes = 0;
-        }
-        TRHIP_HIP(hipMalloc(&meshlets->triCounts, (size_t)need));
-        meshlets->triCountsBytes = need;
-        meshlets->triCountsVersion = 0;
-    }
-    return TRHIP_OK;
-}
-
 // at submission time, on the stream of the stats command: no-op unless the meshlet buffer was written since the array was built
 int triCountsLaunchBuild(trhip_buffer_t* meshlets, hipStream_t s)
 {
-    const uint64_t v = meshlets->version;
-    if (meshlets->triCountsVersion == v) return TRHIP_OK;
+    const trhip::Stamp from = { meshlets->version };
+    if (meshlets->triCounts.current(from)) return TRHIP_OK;
     const uint64_t n = meshlets->byteSize / sizeof(MeshletData);
     const uint64_t blocks = (n + 255u) / 256u;
     TRHIP_LAUNCH(triCountsKernel, dim3((uint32_t)(blocks < 65536u ? (blocks ? blocks : 1u) : 65536u)), dim3(256), 0, s,
-                 (const MeshletData*)meshlets->ptr, n, (uint8_t*)meshlets->triCounts);
-    meshlets->triCountsVersion = v;
+                 (const MeshletData*)meshlets->ptr, n, (uint8_t*)meshlets->triCounts.ptr);
+    meshlets->triCounts.markBuilt(from);
     return trhip::launchStatus("triCountsKernel");
 }
 
@@ -190,12 +171,13 @@ int statsEmitAS(const DispatchCtx& ctx, const ::MeshletCullArgs& a, trhip_buffer
                 trhip_buffer_t* instances, trhip_buffer_t* meshData, bool side)
 {
     trhip_cmdlist_t* cl = ctx.cl;
-    int rc = triCountsEnsure(meshlets);
+    const uint64_t n = meshlets->byteSize / sizeof(MeshletData);
+    int rc = meshlets->triCounts.allocate(meshlets->dev, ((n + 255u) & ~uint64_t(255)) + 256u);   // + padding: statsASKernel reads 9 dwords per group
     if (rc != TRHIP_OK) return rc;
     StatsASArgs s;
     memset(&s, 0, sizeof s);
     s.a = a;
-    s.tri = (const uint8_t*)meshlets->triCounts;
+    s.tri = (const uint8_t*)meshlets->triCounts.ptr;
     s.counters = cl->openStats->counters;
     uint64_t grid = ((uint64_t)a.recordCapacity + kStatsBlock - 1) / kStatsBlock;
     if (grid > (uint64_t)ctx.computeUnits() * 8u) grid = (uint64_t)ctx.computeUnits() * 8u;
@@ -212,10 +194,10 @@ int statsEmitAS(const DispatchCtx& ctx, const ::MeshletCullArgs& a, trhip_buffer
         // beside the list build: every allocation it reads, so that a later main-stream write waits for it, and the ones it
         // writes, so that the end command (and the next execution's begin) wait for it
         ctx.emitSide("stats", std::move(fn), { { a.listGroups, false }, { a.visMask, false }, { records->ptr, false }, { instances->ptr, false },
-                                               { meshData->ptr, false }, { meshlets->ptr, false }, { meshlets->triCounts, true },
+                                               { meshData->ptr, false }, { meshlets->ptr, false }, { meshlets->triCounts.ptr, true },
                                                { s.counters, true } });
     } else {
-        cl->use(meshlets->triCounts, cl->ops.size(), true);
+        cl->use(meshlets->triCounts.ptr, cl->ops.size(), true);
         cl->use(s.counters, cl->ops.size(), true);
         ctx.emit("stats", std::move(fn));
     }

@@ -177,12 +177,11 @@ int recordUpdateInstanceConsts(trhip::DispatchCtx& ctx)
         // the world matrix are re-written from the new one; LOD tables and mesh-space spheres do not change), and the
         // next cull pass finds nothing to rebuild.  A changed mesh buffer is still caught there (its own version).
         const uint64_t now = instances->version;
-        const bool refresh = instances->cullCache && instances->cullCacheMesh && instances->cullCacheInstVersion + 1 == now &&
-                             instances->cullCacheBytes >= (instances->byteSize / sizeof(BasePassInstanceConstants)) * kInstanceCacheBytesPerInstance &&
-                             !getenv("TRHIP_NO_CACHE_REFRESH");
-        const InstanceCullCache cache = refresh ? instanceCacheLayout(instances->cullCache, instances->byteSize / sizeof(BasePassInstanceConstants)) : InstanceCullCache{};
+        const trhip::Stamp was = instances->cullCache.built;       // was.other: the mesh table it was built from (null: never built)
+        const bool refresh = was.other && was.version + 1 == now && !getenv("TRHIP_NO_CACHE_REFRESH");
+        const InstanceCullCache cache = refresh ? instanceCacheLayout(instances->cullCache.ptr, instances->byteSize / sizeof(BasePassInstanceConstants)) : InstanceCullCache{};
         TRHIP_LAUNCH(updateInstanceConstsKernel, dim3((n + kUpdBlock - 1) / kUpdBlock), dim3(kUpdBlock), 0, s, np, numNodes, pn, ip, first, n, refresh, cache);
-        if (refresh) instances->cullCacheInstVersion = now;
+        if (refresh) instances->cullCache.markBuilt({ now, was.other, was.otherVersion });
         return trhip::launchStatus("updateInstanceConstsKernel"); });
     return TRHIP_OK;
 }

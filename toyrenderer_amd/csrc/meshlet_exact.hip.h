@@ -42,8 +42,8 @@ struct MeshletCullArgs
     uint32_t* batchSum;                           // per batch of 64 groups: visible meshlets
     uint32_t* superSum;                           // per 256 batches: visible meshlets -> exclusive prefix after the super scan
     uint32_t maxBatches;
-    // optional processing order written by the instance pass into the record buffer's sidecar
-    // (k_gpuculling.hip): {valid, count} header + a permutation of [0, count) sorted by screen tile
+    // optional processing order written by the instance pass into the record buffer's derived data (trhip_buffer_t::order,
+    // k_gpuculling.hip): {valid, count} header + a permutation of [0, count) sorted by screen tile
     const uint32_t* permHeader;
     const uint4* perm;                            // {record index, instance, first meshlet, count} in processing order
     InstanceCullCache cache;                      // world matrix, max scale, LOD table per instance (instance_cache.hip.h)

@@ -186,6 +186,28 @@ int trhip_device_t::syncAll()
     return TRHIP_OK;
 }
 
+int trhip::DerivedData::allocate(const trhip_device_t* dev, uint64_t size)
+{
+    if (ptr) return size <= bytes ? TRHIP_OK : fail(TRHIP_ERR_STATE, "derived data of %llu bytes asked to grow to %llu", (unsigned long long)bytes, (unsigned long long)size);
+    TRHIP_HIP(hipSetDevice(dev->index));
+    void* p = nullptr;
+    TRHIP_HIP(hipMalloc(&p, (size_t)size));
+    ptr = p;
+    bytes = size;
+    return TRHIP_OK;
+}
+
+void trhip::freeDerived(trhip_device_t* dev, std::initializer_list<DerivedData*> all)
+{
+    bool any = false;
+    for (const DerivedData* d : all) any |= d->ptr != nullptr;
+    if (!any) return;
+    (void)hipSetDevice(dev->index);
+    (void)dev->syncAll();
+    for (const DerivedData* d : all)
+        if (d->ptr) (void)hipFree(d->ptr);
+}
+
 void trhip_cmdlist_t::resetRecording()
 {
     heldSide.clear();
@@ -454,10 +476,7 @@ void trhip_buffer_release(trhip_buffer b)
     if (!b) return;
     if (b->rc.fetch_sub(1) == 1) {
         if (b->owns && b->ptr) { (void)hipSetDevice(b->dev->index); (void)hipFree(b->ptr); }
-        if (b->sidecar) { (void)hipSetDevice(b->dev->index); (void)hipFree(b->sidecar); }
-        if (b->cullCache) { (void)hipSetDevice(b->dev->index); (void)b->dev->syncAll(); (void)hipFree(b->cullCache); }
-        if (b->cullStream) { (void)hipSetDevice(b->dev->index); (void)b->dev->syncAll(); (void)hipFree(b->cullStream); }
-        if (b->triCounts) { (void)hipSetDevice(b->dev->index); (void)b->dev->syncAll(); (void)hipFree(b->triCounts); }
+        trhip::freeDerived(b->dev, { &b->cullCache, &b->cullStream, &b->triCounts, &b->order, &b->listCount });
         if (b->heap) trhip_heap_release(b->heap);
         delete b;
     }
@@ -524,7 +543,7 @@ void trhip_texture_release(trhip_texture t)
     if (!t) return;
     if (t->rc.fetch_sub(1) == 1) {
         if (t->owns && t->ptr) { (void)hipSetDevice(t->dev->index); (void)hipFree(t->ptr); }
-        if (t->quad) { (void)hipSetDevice(t->dev->index); (void)t->dev->syncAll(); (void)hipFree(t->quad); }
+        trhip::freeDerived(t->dev, { &t->quad });
         if (t->heap) trhip_heap_release(t->heap);
         delete t;
     }

@@ -88,6 +88,39 @@ struct trhip_heap_t
     std::atomic<int> rc{1};
 };
 
+namespace trhip
+{
+
+// What derived data was last built from: the version of its owner (trhip_buffer_t::version) and, for data that also reads a
+// second resource (the instance cull cache reads the mesh table), that resource's pointer and version.  Versions start at 1,
+// so the zero stamp is never current.
+struct Stamp
+{
+    uint64_t version = 0;
+    const void* other = nullptr;
+    uint64_t otherVersion = 0;
+    bool operator==(const Stamp& s) const { return version == s.version && other == s.other && otherVersion == s.otherVersion; }
+};
+
+// Back-end private device memory DERIVED from a buffer or texture the caller owns, and freed with it (freeDerived).  Its size
+// is a function of the owner's, which never changes after creation, so it is allocated once, by the first pass that needs it.
+// Data rebuilt from the owner's contents is rebuilt exactly when the stamp of its sources is no longer `built`.
+struct DerivedData
+{
+    void* ptr = nullptr;
+    uint64_t bytes = 0;
+    Stamp built;
+
+    int allocate(const trhip_device_t* dev, uint64_t size);
+    bool current(const Stamp& s) const { return built == s; }
+    void markBuilt(const Stamp& s) { built = s; }
+};
+
+// An owner's release: drains both streams of the device once (commands in flight may still use the data), then frees them.
+void freeDerived(trhip_device_t* dev, std::initializer_list<DerivedData*> all);
+
+} // namespace trhip
+
 struct trhip_buffer_t
 {
     trhip_device_t* dev = nullptr;
@@ -99,33 +132,25 @@ struct trhip_buffer_t
     bool owns = false;
     trhip_heap_t* heap = nullptr;
     std::vector<uint8_t> shadow; // current version of a volatile constant buffer (record time)
-    // Back-end private companion allocation (device memory, freed with the buffer).  Used by the
-    // instance-cull pass to hand the meshlet-cull pass a screen-tile-sorted PROCESSING order of the
-    // amplification records it wrote into this buffer (k_gpuculling.hip / k_basepass_as.hip).
-    void* sidecar = nullptr;
-    uint64_t sidecarBytes = 0;
-    // Bumped, in SUBMISSION order, by every command that writes the buffer (trhip_queue_execute) and by uploads:
-    // derived data (the instance cull cache below, the HZB footprint-min table) records the version it was built
-    // from and is rebuilt when that is no longer the current one.
+    // Bumped, in SUBMISSION order, by every command that writes the buffer (trhip_queue_execute), by uploads and by
+    // bind_memory: the derived data below records the version it was built from (trhip::Stamp).
     std::atomic<uint64_t> version{1};
-    // Instance buffers only: the INSTANCE CULL CACHE (k_gpuculling.hip), a compact SoA restatement of what the
-    // instance cull reads per instance (world-space bounding sphere, max scale, LOD table) -- 88 B instead of the
-    // 300 B of AoS instance + mesh records it would otherwise pull through HBM every frame.
-    void* cullCache = nullptr;
-    uint64_t cullCacheBytes = 0;
-    uint64_t cullCacheInstVersion = 0, cullCacheMeshVersion = 0;
-    const void* cullCacheMesh = nullptr;
-    // Meshlet buffers only: the MESHLET CULL STREAM (k_basepass_as.hip), the 20 bytes of each 32-byte MeshletData the cull
-    // reads (bounding sphere, cone word) as two dense arrays; rebuilt when the buffer's version moves.
-    void* cullStream = nullptr;
-    uint64_t cullStreamBytes = 0;
-    uint64_t cullStreamVersion = 0;
-    // Meshlet buffers only, and only once a pipeline statistics query has covered a basepass_AS_Main dispatch: the TRIANGLE
-    // COUNTS, one byte per meshlet ((m_VertexAndTriangleCount >> 8) & 0xFF, k_pipeline_stats.hip).  Kept exactly like the cull
-    // stream: rebuilt when the buffer's version moves.
-    void* triCounts = nullptr;
-    uint64_t triCountsBytes = 0;
-    uint64_t triCountsVersion = 0;
+    // Derived data (trhip::DerivedData); which of it a buffer has depends on what it is bound as.
+    // Instance buffers: the INSTANCE CULL CACHE (k_gpuculling.hip), a compact SoA restatement of what the instance cull reads
+    // per instance (world-space bounding sphere, max scale, LOD table) -- 88 B instead of the 300 B of AoS instance + mesh
+    // records it would otherwise pull through HBM every frame.  Built from this buffer and the mesh table.
+    trhip::DerivedData cullCache;
+    // Meshlet buffers: the MESHLET CULL STREAM (k_basepass_as.hip), the 20 bytes of each 32-byte MeshletData the cull reads
+    // (bounding sphere, cone word) as two dense arrays.
+    trhip::DerivedData cullStream;
+    // Meshlet buffers, once a pipeline statistics query has covered a basepass_AS_Main dispatch: the TRIANGLE COUNTS, one
+    // byte per meshlet ((m_VertexAndTriangleCount >> 8) & 0xFF, k_pipeline_stats.hip).
+    trhip::DerivedData triCounts;
+    // Amplification record buffers: the screen-tile-sorted PROCESSING ORDER of the records the instance pass wrote into this
+    // buffer, which the meshlet cull follows (k_gpuculling.hip / k_basepass_as.hip).  Rewritten by every instance pass: no stamp.
+    trhip::DerivedData order;
+    // Mask buffers: the list build's GROUP COUNT word, written by the meshlet cull (k_basepass_as.hip).  No stamp.
+    trhip::DerivedData listCount;
     std::atomic<int> rc{1};
 };
 
@@ -141,15 +166,13 @@ struct trhip_texture_t
     void* ptr = nullptr;
     bool owns = false;
     trhip_heap_t* heap = nullptr;
-    // Back-end private companion of an R16F min-HZB: the FOOTPRINT-MIN TABLE (k_hzb.hip).  For every mip and
+    // Derived data (trhip::DerivedData) of an R16F min-HZB: the FOOTPRINT-MIN TABLE (k_hzb.hip).  For every mip and
     // every possible bilinear footprint origin (x0,y0) in [-1,w-1]x[-1,h-1] it holds the min of the 2x2
     // edge-clamped footprint, so the meshlet cull kernel resolves SampleLevel(min-reduction) with ONE 2-byte
-    // load.  It is current while quadBuiltVersion == version (see trhip_buffer_t::version).
-    void* quad = nullptr;
-    uint64_t quadBytes = 0;
+    // load.  Built from `version` (see trhip_buffer_t::version).
+    trhip::DerivedData quad;
     uint32_t quadOffset[16] = {};              // first entry of mip k; mip k has ((w_k >> 3) + 1) * ((h_k >> 3) + 1) blocks of 8 x 8 entries
     uint32_t quadTotal = 0;
-    uint64_t quadBuiltVersion = 0;
     std::atomic<uint64_t> version{1};
     std::atomic<int> rc{1};
 
