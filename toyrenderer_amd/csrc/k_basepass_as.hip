@@ -1410,10 +1410,6 @@ void emitListBuild(const trhip::DispatchCtx& ctx, const MeshletCullArgs& a, cons
     }
     const uint32_t needBlocks = (a.maxBatches + kWaves - 1) / kWaves;
     uint32_t gridSmall = ctx.computeUnits() * 8u;      // count / expand: light kernels, one wave per 64 groups
-    if (side) {                                         // experiment: TRHIP_EXPAND_BLOCKS_PER_CU (side-stream list builds only)
-        static const int perCU = [] { const char* e = getenv("TRHIP_EXPAND_BLOCKS_PER_CU"); return e ? atoi(e) : 0; }();
-        if (perCU > 0) gridSmall = ctx.computeUnits() * (uint32_t)perCU;
-    }
     if (gridSmall > needBlocks) gridSmall = needBlocks;
     if (gridSmall == 0) gridSmall = 1;
     const std::string p = prefix;
@@ -1424,19 +1420,10 @@ void emitListBuild(const trhip::DispatchCtx& ctx, const MeshletCullArgs& a, cons
     emit(p + "scan", [a](hipStream_t s) {
         TRHIP_LAUNCH(visSuperScanKernel, dim3(1), dim3(1024), 0, s, a);
         return trhip::launchStatus("visSuperScanKernel"); });
-    // Experiment (TRHIP_DEFER_EXPAND=1; off): the expansion of a LARGE EARLY pass (122 MB of stores on C3, 26 us) HELD BACK -- it
-    // enters the side stream behind the late meshlet cull (recordASMain flushes it in front of the late list build) instead of
-    // beside the late instance pass and the late meshlet cull.  Measured (profiles/r4/experiments.md): those two drop from 11 +
-    // 30 to 9 + 10 us, but the expansion then runs beside the second HZB build (13 + 5 -> 14 + 17 us), pushes the late list build
-    // and the next frame's table rebuild into the next frame's instance pass (emit 16 -> 25 us): frame 0.470 -> 0.480 ms.  The
-    // stores have to happen somewhere in the 0.13 ms of latency-bound launches around the cull kernel.
-    static const bool deferExpand = [] { const char* e = getenv("TRHIP_DEFER_EXPAND"); return e ? atoi(e) != 0 : false; }();
-    auto expandFn = [a, gridSmall](hipStream_t s) {
+    // Holding a large early pass's expansion back behind the late cull measured slower.
+    emit(p + "expand", [a, gridSmall](hipStream_t s) {
         TRHIP_LAUNCH(visExpandKernel, dim3(gridSmall), dim3(kBlock), 0, s, a);
-        return trhip::launchStatus("visExpandKernel"); };
-    if (side && deferExpand && ctx.variant == 0 && prefix[0] == 0)
-        ctx.emitSideHeld("expand", std::move(expandFn), { { a.listGroups ? (const void*)a.listGroups : argsBase, false }, { a.visMask, false }, { a.visibleList, true }, { a.drawArgs, true } });
-    else emit(p + "expand", std::move(expandFn));
+        return trhip::launchStatus("visExpandKernel"); });
 }
 
 template <bool F, bool O, bool C>
@@ -1506,8 +1493,8 @@ int recordASMain(trhip::DispatchCtx& ctx)
     a.k = *k;
     const bool occlusion = (k->m_CullingFlags & kCullingFlagOcclusionCullingEnable) != 0;
     // LATE_CULL=1 follows an HZB rebuild and covers only what the early phase rejected: texel path, no table.
-    // Small passes (capacity below 2^19 groups) also take the texel path: the table rebuild is a fixed ~20 us per
-    // frame on the side stream and pays off only when the pass is long (same rule in k_gpuculling.hip).
+    // Small passes (capacity below 2^17 groups, trhip::tableMinGroups) also take the texel path: the table rebuild is a fixed
+    // cost per frame (extra workgroups of the instance pass) and pays off only when the pass is long (same rule in k_gpuculling.hip).
     const bool useTable = occlusion && ctx.variant == 0 && records->byteSize / sizeof(MeshletAmplificationData) >= trhip::tableMinGroups();
     int rc = TRHIP_OK;
     {
@@ -1551,8 +1538,7 @@ int recordASMain(trhip::DispatchCtx& ctx)
     const uint64_t lcap = visList->byteSize / 4;
     a.listCapacity = lcap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lcap;
     a.drawArgs = (uint32_t*)drawArgs->ptr;
-    static const bool noPerm = getenv("TRHIP_AS_NO_PERM") != nullptr;                // experiments: process the records in list order
-    if (!noPerm && records->order.ptr && records->order.bytes >= 256 + (uint64_t)a.recordCapacity * 16) {
+    if (records->order.ptr && records->order.bytes >= 256 + (uint64_t)a.recordCapacity * 16) {
         a.permHeader = (const uint32_t*)records->order.ptr;
         a.perm = (const uint4*)(a.permHeader + 64);
     }
@@ -1574,8 +1560,7 @@ int recordASMain(trhip::DispatchCtx& ctx)
     // workgroups to fill the chip and let them stride over the chunks.
     // Five workgroups per CU: 31.7 KB of LDS each (13.8 KB of per-record data, 10 KB of ring, 5 KB of deferred list) and 96
     // VGPRs.  (LDS: the allocation granule makes 32 000 bytes the limit for five -- 32 720 ran four per CU, 11 % slower.)
-    uint32_t blocksPerCU = TR_CULL_WAVES_PER_EU;
-    if (const char* e = getenv("TRHIP_AS_BLOCKS_PER_CU")) blocksPerCU = (uint32_t)atoi(e) ? (uint32_t)atoi(e) : blocksPerCU;   // tuning experiments
+    const uint32_t blocksPerCU = TR_CULL_WAVES_PER_EU;
     uint32_t grid = ctx.computeUnits() * blocksPerCU;
     const uint32_t needBlocks = (a.recordCapacity + kCullBatch * kCullWaves - 1) / (kCullBatch * kCullWaves);
     if (grid > needBlocks) grid = needBlocks;
@@ -1588,7 +1573,7 @@ int recordASMain(trhip::DispatchCtx& ctx)
     a.listGroups = (uint32_t*)visMask->listCount.ptr;
     ctx.cl->use(a.listGroups, ctx.cl->ops.size(), true);
     if (useTable) a.bands = cm::projBands(k->m_P00, k->m_P11, hzb->width, hzb->height);
-    static const bool noShortPass = getenv("TRHIP_NO_SHORT_PASS") != nullptr;          // tests: the texel kernel's batch path on small passes too
+    static const bool noShortPass = getenv("TRHIP_NO_SHORT_PASS") != nullptr;          // tests: the texel kernel's batch path on small passes too (test_texel_kernel_batch_path_on_small_passes)
     a.shortPassRounds = noShortPass ? 0u : kShortPassRounds;
     const uint32_t flags = k->m_CullingFlags & 7u;
     trhip_texture_t* quadOwner = useTable ? hzb : nullptr;
@@ -1623,7 +1608,6 @@ int recordASMain(trhip::DispatchCtx& ctx)
         return trhip::launchStatus("meshletCullKernel"); });
     // The side stream costs two events and two cross-stream waits per run (~20 us of host time): worth it
     // when the list build is long (>= 2^19 groups of capacity), not for small passes.
-    ctx.cl->flushHeldSide();                            // (the early pass's held list expansion goes in front of this pass's list build)
     emitListBuild(ctx, a, "", a.recordCapacity >= (1u << 19), ctx.argsBuffer->ptr);
     if (ctx.cl->openStats)                              // a pipeline statistics query is open: this pass's AS / MS counts, beside the list build
         return trhip::statsEmitAS(ctx, a, meshlets, records, instances, meshData, a.recordCapacity >= (1u << 19));

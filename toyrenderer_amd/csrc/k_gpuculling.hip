@@ -736,7 +736,8 @@ std::function<int(hipStream_t)> fusedEarlyLaunch(const InstanceCullArgs& a, trhi
         return trhip::launchStatus("instanceFusedKernel"); };
 }
 
-// Share of the table's strips built in the scan launch (the rest in the emit launch): TRHIP_QUAD_SCAN_PERCENT, experiments
+// Share of the table's strips built in the scan launch (the rest in the emit launch).  tests: TRHIP_QUAD_SCAN_PERCENT
+// (test_footprint_table_strips_split_between_scan_and_emit)
 inline uint32_t quadScanStrips(uint32_t all)
 {
     static const uint32_t pct = [] { const char* e = getenv("TRHIP_QUAD_SCAN_PERCENT"); const int v = e ? atoi(e) : 50; return (uint32_t)(v < 0 ? 0 : v > 100 ? 100 : v); }();
@@ -827,7 +828,7 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
     a.cache = instanceCacheLayout(instances->cullCache.ptr, instances->byteSize / sizeof(BasePassInstanceConstants));
     a.numInstances = (uint32_t)(instances->byteSize / sizeof(BasePassInstanceConstants));
     ctx.emit("instance_cache", [instances, meshData](hipStream_t s) { return trhip::instanceCacheLaunchBuild(instances, meshData, s); });
-    static const bool noFused = getenv("TRHIP_NO_FUSED_INSTANCE") != nullptr;          // tests: the three-kernel path on small passes
+    static const bool noFused = getenv("TRHIP_NO_FUSED_INSTANCE") != nullptr;          // tests: the three-kernel path on small passes (test_three_kernel_instance_pass_on_small_scenes, size-boundary reruns)
     const bool fusedPath = (nMax <= kFusedMaxEntries || (LATE && (nMax + kBlock - 1) / kBlock <= kFusedLateMaxTiles)) && !noFused;
     a.numBlocks = fusedPath ? (nMax + kBlock - 1) / kBlock : (nMax + kBigChunk - 1) / kBigChunk;
     a.word = (uint32_t*)ctx.scratch((size_t)nMax * 4);
@@ -848,11 +849,9 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
     a.permCapacity = a.maxGroups;
     // The early meshlet cull that follows this pass resolves its HZB lookups through the footprint-min table of
     // this same HZB (hzb_quad.hip.h): bring the table up to date with extra workgroups of this pass's own scan / fused launch.
-    static const bool noInlineQuad = getenv("TRHIP_NO_INLINE_QUAD") != nullptr;         // experiments: its own launch on the side stream, beside the instance pass
     const bool wantTable = !LATE && occlusion && a.maxGroups >= trhip::tableMinGroups(); // the rule of recordASMain (k_basepass_as.hip)
-    const bool inlineQuad = wantTable && !noInlineQuad;                                 // extra workgroups of the fused launch (small pass) / of the scan launch (large pass) build it
     if (wantTable) {
-        rc = inlineQuad ? trhip::hzbQuadEnsure(hzb) : trhip::hzbQuadEmitBuild(ctx, hzb);
+        rc = trhip::hzbQuadEnsure(hzb);
         if (rc != TRHIP_OK) return rc;
     }
 
@@ -864,7 +863,7 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
         if (rc != TRHIP_OK) return rc;
         a.fusedStatus = (unsigned long long*)mem;
         a.fusedTicket = mem + (size_t)a.numBlocks * kFusedStatusStride * 2;
-        trhip_texture_t* quadOwner = inlineQuad ? hzb : nullptr;
+        trhip_texture_t* quadOwner = wantTable ? hzb : nullptr;
         if (quadOwner) ctx.cl->use(quadOwner->quad.ptr, ctx.cl->ops.size(), true);       // this command (re)writes the table
         if (LATE) ctx.emit("fused", [a](hipStream_t s) {
             trhip::QuadArgs q;
@@ -879,7 +878,7 @@ int recordGPUCulling(trhip::DispatchCtx& ctx)
     ctx.emit("classify", [a](hipStream_t s) {
         TRHIP_LAUNCH(instanceClassifyKernel<LATE>, dim3(a.numBlocks), dim3(kBigThreads), 0, s, a);
         return trhip::launchStatus("instanceClassifyKernel"); });
-    trhip_texture_t* quadOwner = inlineQuad ? hzb : nullptr;
+    trhip_texture_t* quadOwner = wantTable ? hzb : nullptr;
     std::shared_ptr<QuadShare> share = quadOwner ? std::make_shared<QuadShare>() : nullptr;
     if (quadOwner) ctx.cl->use(quadOwner->quad.ptr, ctx.cl->ops.size(), true);           // the scan command (re)writes the table (and the emit command behind it)
     if (LATE) ctx.emit("scan", [a](hipStream_t s) {

@@ -380,14 +380,6 @@ int hzbQuadLaunchBuild(trhip_texture_t* tex, hipStream_t s)
     return launchStatus("hzbQuadBuildKernel");
 }
 
-int hzbQuadEmitBuild(const DispatchCtx& ctx, trhip_texture_t* tex)
-{
-    int rc = hzbQuadEnsure(tex);
-    if (rc != TRHIP_OK) return rc;
-    ctx.emitSide("footprint_min", [tex](hipStream_t s) { return hzbQuadLaunchBuild(tex, s); }, { { tex->ptr, false }, { tex->quad.ptr, true } });
-    return TRHIP_OK;
-}
-
 } // namespace trhip
 
 namespace

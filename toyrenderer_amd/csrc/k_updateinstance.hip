@@ -178,6 +178,7 @@ int recordUpdateInstanceConsts(trhip::DispatchCtx& ctx)
         // next cull pass finds nothing to rebuild.  A changed mesh buffer is still caught there (its own version).
         const uint64_t now = instances->version;
         const trhip::Stamp was = instances->cullCache.built;       // was.other: the mesh table it was built from (null: never built)
+        // tests: TRHIP_NO_CACHE_REFRESH (test_animated_transforms_then_cull sets it in-process: read per submission, not cached)
         const bool refresh = was.other && was.version + 1 == now && !getenv("TRHIP_NO_CACHE_REFRESH");
         const InstanceCullCache cache = refresh ? instanceCacheLayout(instances->cullCache.ptr, instances->byteSize / sizeof(BasePassInstanceConstants)) : InstanceCullCache{};
         TRHIP_LAUNCH(updateInstanceConstsKernel, dim3((n + kUpdBlock - 1) / kUpdBlock), dim3(kUpdBlock), 0, s, np, numNodes, pn, ip, first, n, refresh, cache);

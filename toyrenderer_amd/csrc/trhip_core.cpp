@@ -97,15 +97,6 @@ void DispatchCtx::emitSide(const char* kernelName, std::function<int(hipStream_t
     for (const Op::Access& t : touched) if (t.ptr) cl->ops.back().touched.push_back(t);
 }
 
-void DispatchCtx::emitSideHeld(const char* kernelName, std::function<int(hipStream_t)> fn, std::initializer_list<Op::Access> touched) const
-{
-    if (!cl->dev->sideStream) { emit(kernelName, std::move(fn)); return; }
-    Op op{ std::string(shaderName) + "#" + kernelName, std::move(fn) };
-    op.lane = 1;
-    for (const Op::Access& t : touched) if (t.ptr) op.touched.push_back(t);
-    cl->heldSide.push_back(std::move(op));
-}
-
 } // namespace trhip
 
 using namespace trhip;
@@ -210,7 +201,6 @@ void trhip::freeDerived(trhip_device_t* dev, std::initializer_list<DerivedData*>
 
 void trhip_cmdlist_t::resetRecording()
 {
-    heldSide.clear();
     ops.clear();
     for (trhip_buffer_t* b : heldBuffers) trhip_buffer_release(b);
     for (trhip_texture_t* t : heldTextures) trhip_texture_release(t);
@@ -316,16 +306,14 @@ static int deviceCreate(int index, void* stream, bool external, trhip_device* ou
         TRHIP_HIP(hipStreamCreateWithFlags(&dev->stream, hipStreamNonBlocking));
         dev->ownsStream = true;
     }
-    if (!getenv("TRHIP_NO_SIDE_STREAM")) {             // see trhip_device_t::sideStream
+    if (!getenv("TRHIP_NO_SIDE_STREAM")) {             // see trhip_device_t::sideStream; tests: test_c2_without_the_side_stream
         // High priority: HIP multiplexes the streams of one priority class onto a few hardware queues (4 by default)
         // round robin; in a process with many streams (torch, RCCL) the side stream otherwise lands on the SAME
         // hardware queue as the main stream sooner or later and its kernels serialise with it (seen at 2-8 ranks:
         // +0.06..0.16 ms per frame).  A different priority class is a different queue.
         int lowest = 0, highest = 0;
         TRHIP_HIP(hipDeviceGetStreamPriorityRange(&lowest, &highest));
-        int sidePriority = highest;
-        if (const char* e = getenv("TRHIP_SIDE_PRIORITY")) sidePriority = atoi(e) < 0 ? highest : atoi(e) > 0 ? lowest : 0;   // experiments
-        TRHIP_HIP(hipStreamCreateWithPriority(&dev->sideStream, hipStreamNonBlocking, sidePriority));
+        TRHIP_HIP(hipStreamCreateWithPriority(&dev->sideStream, hipStreamNonBlocking, highest));
         TRHIP_HIP(hipEventCreateWithFlags(&dev->evFork, hipEventDisableTiming));
         for (hipEvent_t& e : dev->runDone) TRHIP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
@@ -658,7 +646,6 @@ int trhip_cmd_close(trhip_cmdlist cl)
     if (!cl->open) return fail(TRHIP_ERR_STATE, "cmd_close: not open");
     if (!cl->markers.empty()) return fail(TRHIP_ERR_STATE, "cmd_close: %zu marker(s) still open", cl->markers.size());
     if (cl->openStats) return fail(TRHIP_ERR_STATE, "cmd_close: a pipeline statistics query is still open");
-    cl->flushHeldSide();
     cl->open = false;
     // by command index (a clear merged into an earlier launch is noted against that launch)
     std::stable_sort(cl->useMarks.begin(), cl->useMarks.end(), [](const trhip_cmdlist_t::UseMark& a, const trhip_cmdlist_t::UseMark& b) { return a.op < b.op; });
@@ -674,7 +661,6 @@ int trhip_cmd_close(trhip_cmdlist cl)
 int trhip_cmd_write_buffer(trhip_cmdlist cl, trhip_buffer buf, uint64_t off, const void* src, uint64_t bytes)
 {
     TRHIP_RECORDING(cl);
-    if (buf && cl->heldConflicts(buf->ptr, true)) cl->flushHeldSide();   // (a volatile constant buffer has no memory of its own: never a conflict)
     if (!buf || !src) return fail(TRHIP_ERR_INVALID, "write_buffer: null argument");
     if (off + bytes > buf->byteSize) return fail(TRHIP_ERR_INVALID, "write_buffer(%s): %llu+%llu exceeds %llu bytes", buf->name.c_str(), (unsigned long long)off, (unsigned long long)bytes, (unsigned long long)buf->byteSize);
     if (buf->isVolatileConstant) {
@@ -695,7 +681,6 @@ int trhip_cmd_write_buffer(trhip_cmdlist cl, trhip_buffer buf, uint64_t off, con
 int trhip_cmd_clear_buffer_u32(trhip_cmdlist cl, trhip_buffer buf, uint32_t value)
 {
     TRHIP_RECORDING(cl);
-    if (buf && cl->heldConflicts(buf->ptr, true)) cl->flushHeldSide();
     if (!buf) return fail(TRHIP_ERR_INVALID, "clear_buffer: null buffer");
     if (!buf->ptr) return fail(TRHIP_ERR_STATE, "clear_buffer(%s): no memory bound", buf->name.c_str());
     if (buf->byteSize % 4) return fail(TRHIP_ERR_INVALID, "clear_buffer(%s): size not a multiple of 4", buf->name.c_str());
@@ -711,7 +696,6 @@ int trhip_cmd_clear_buffer_u32(trhip_cmdlist cl, trhip_buffer buf, uint32_t valu
 int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value)
 {
     TRHIP_RECORDING(cl);
-    if (tex && cl->heldConflicts(tex->ptr, true)) cl->flushHeldSide();
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RG32_UINT)
@@ -739,7 +723,6 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
 int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value)
 {
     TRHIP_RECORDING(cl);
-    if (tex && cl->heldConflicts(tex->ptr, true)) cl->flushHeldSide();
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
     if (tex->format != TRHIP_FORMAT_RG32_UINT)
@@ -755,7 +738,6 @@ int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t va
 int trhip_cmd_copy_buffer(trhip_cmdlist cl, trhip_buffer dst, uint64_t dstOff, trhip_buffer src, uint64_t srcOff, uint64_t bytes)
 {
     TRHIP_RECORDING(cl);
-    cl->flushHeldSide();                               // (held side ops: nothing is assumed about what this command touches)
     if (!dst || !src) return fail(TRHIP_ERR_INVALID, "copy_buffer: null buffer");
     if (!dst->ptr || !src->ptr) return fail(TRHIP_ERR_STATE, "copy_buffer: a buffer has no memory bound");
     if (dstOff + bytes > dst->byteSize || srcOff + bytes > src->byteSize) return fail(TRHIP_ERR_INVALID, "copy_buffer(%s <- %s): range exceeds a buffer", dst->name.c_str(), src->name.c_str());
@@ -770,7 +752,6 @@ int trhip_cmd_copy_buffer(trhip_cmdlist cl, trhip_buffer dst, uint64_t dstOff, t
 int trhip_cmd_host_callback(trhip_cmdlist cl, trhip_host_fn fn, void* user)
 {
     TRHIP_RECORDING(cl);
-    cl->flushHeldSide();                               // (held side ops: nothing is assumed about what this command touches)
     if (!fn) return fail(TRHIP_ERR_INVALID, "host_callback: null function");
     cl->ops.push_back({ "", [fn, user](hipStream_t s) { fn(user, (void*)s); return (int)TRHIP_OK; } });
     cl->ops.back().kind = "host_callback";
@@ -780,7 +761,6 @@ int trhip_cmd_host_callback(trhip_cmdlist cl, trhip_host_fn fn, void* user)
 int trhip_cmd_copy_texture(trhip_cmdlist cl, trhip_texture dst, trhip_texture src)
 {
     TRHIP_RECORDING(cl);
-    cl->flushHeldSide();                               // (held side ops: nothing is assumed about what this command touches)
     if (!dst || !src) return fail(TRHIP_ERR_INVALID, "copy_texture: null texture");
     if (!dst->ptr || !src->ptr) return fail(TRHIP_ERR_STATE, "copy_texture: a texture has no memory bound");
     if (dst->width != src->width || dst->height != src->height || dst->mips != src->mips || dst->format != src->format)
@@ -802,20 +782,6 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
     const ShaderEntry* e = findShader(name);
     if (!e) return fail(TRHIP_ERR_UNKNOWN_SHADER, "dispatch: unknown shader '%s'", name);
     if (nb && !b) return fail(TRHIP_ERR_INVALID, "dispatch(%s): bindings is null", name);
-    if (!cl->heldSide.empty()) {                        // a held side op that touches one of this command's resources goes first
-        bool conflict = indirect && args && cl->heldConflicts(args->ptr, false);
-        for (uint32_t i = 0; i < nb && !conflict; ++i) {
-            if (!b[i].resource) continue;
-            switch (b[i].type) {
-            case TRHIP_BIND_CONSTANT_BUFFER: case TRHIP_BIND_STRUCTURED_SRV: case TRHIP_BIND_STRUCTURED_UAV:
-                conflict = cl->heldConflicts(((trhip_buffer_t*)b[i].resource)->ptr, b[i].type == TRHIP_BIND_STRUCTURED_UAV); break;
-            case TRHIP_BIND_TEXTURE_SRV: case TRHIP_BIND_TEXTURE_UAV:
-                conflict = cl->heldConflicts(((trhip_texture_t*)b[i].resource)->ptr, b[i].type == TRHIP_BIND_TEXTURE_UAV); break;
-            default: break;
-            }
-        }
-        if (conflict) cl->flushHeldSide();
-    }
     if (indirect) {
         if (!args || !args->ptr) return fail(TRHIP_ERR_INVALID, "dispatch_indirect(%s): no argument buffer", name);
         if (argsOff % 4 || argsOff + 12 > args->byteSize) return fail(TRHIP_ERR_INVALID, "dispatch_indirect(%s): bad argument offset %u", name, argsOff);
@@ -975,7 +941,6 @@ int trhip_queue_execute(trhip_device dev, const trhip_cmdlist* lists, uint32_t n
         dev->mainWaitedUpTo = need;                    // the side stream is in order: earlier runs are covered too
         return TRHIP_OK;
     };
-    static const bool g_tapForks = getenv("TRHIP_NO_FORK_TAP") == nullptr;       // experiments: forks by marker packets, as in rounds 1-3
     auto nextIsSide = [&](uint32_t li, size_t oi) -> bool {                       // the command after (li, oi), across list boundaries
         if (!dev->sideStream) return false;
         for (++oi; li < n; ++li, oi = 0)
@@ -1021,10 +986,10 @@ int trhip_queue_execute(trhip_device dev, const trhip_cmdlist* lists, uint32_t n
             hipEvent_t e0 = nullptr, e1 = nullptr;
             if (prof) { e0 = dev->acquireEvent(); e1 = dev->acquireEvent(); TRHIP_HIP(hipEventRecord(e0, stream)); }
             const auto h0 = g_hostProfile.on ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point{};
-            // the next command forks the side stream from here: let this command's kernel carry the fork event (LaunchTap)
+            // the next command forks the side stream from here: let this command's kernel carry the fork event (LaunchTap's rule)
             trhip::LaunchTap tap;
             dev->forkSignalled = false;
-            const bool tapped = !side && !prof && g_tapForks && nextIsSide(i, oi);
+            const bool tapped = !side && !prof && strcmp(op.kind, "host_callback") != 0 && nextIsSide(i, oi);
             if (tapped) { tap.onStream = stream; tap.stopEvent = dev->evFork; trhip::g_launchTap = &tap; }
             int rc = op.fn(stream);
             trhip::g_launchTap = nullptr;

@@ -210,7 +210,7 @@ struct Op
 {
     std::string name;                       // profile key ("" = not profiled)
     std::function<int(hipStream_t)> fn;
-    const char* kind = "dispatch";          // what the op is, for the host-side submission profile (TRHIP_HOST_PROFILE=1)
+    const char* kind = "dispatch";          // what the op is, for the host-side submission profile (TRHIP_HOST_PROFILE=1) and the fork rule (LaunchTap)
     uint8_t lane = 0;                       // 0 main stream, 1 side stream (see DispatchCtx::emitSide)
     struct Access { const void* ptr; bool write; };
     std::vector<Access> touched;            // side ops: allocations read / written (base pointers)
@@ -279,28 +279,6 @@ struct trhip_cmdlist_t
     // use marks of both stay attached to it).  Cleared by any other command.
     struct Peephole { size_t op = SIZE_MAX; const char* kind = nullptr; std::shared_ptr<void> data; } peephole;
 
-    // HELD side ops: a side-stream op whose results nothing in this recording needs may be held back and put into the stream
-    // LATER than where it was recorded -- behind the next command that forks the side stream anyway -- so that it overlaps a
-    // different part of the frame (the early pass's list expansion, 122 MB of stores on C3, ran beside the latency-bound late
-    // phase and tripled its kernels' times).  It is flushed, i.e. appended at the current position, before any command that uses
-    // a resource it touches (recordDispatch, clears, copies check their operands), by whoever wants it in front of its own side
-    // ops, and when the recording is closed.
-    std::vector<trhip::Op> heldSide;
-    bool heldConflicts(const void* ptr, bool write) const
-    {
-        for (const trhip::Op& op : heldSide)
-            for (const trhip::Op::Access& t : op.touched)
-                if (t.ptr == ptr && (t.write || write)) return true;
-        return false;
-    }
-    void flushHeldSide()
-    {
-        if (heldSide.empty()) return;
-        for (trhip::Op& op : heldSide) ops.push_back(std::move(op));
-        heldSide.clear();
-        openClearBatch.reset(); openClearOp = SIZE_MAX;
-        peephole = Peephole{};
-    }
     void* scratchAlloc(size_t bytes);       // device memory valid until the list is re-opened/released
     void* scratchAllocSide(size_t bytes);   // same, from an arena only side-stream ops use (they are in order among themselves)
     std::vector<ScratchBlock> sideScratch;
@@ -336,14 +314,10 @@ struct DispatchCtx
     // Same, on the device's side stream, ordered after everything recorded before it.  `touched`: every
     // device allocation the op reads or writes that a later command could also use (base pointers).
     void emitSide(const char* kernelName, std::function<int(hipStream_t)> fn, std::initializer_list<Op::Access> touched) const;
-    // Same, HELD (trhip_cmdlist_t::heldSide): enters the stream at the next flush, not here.
-    void emitSideHeld(const char* kernelName, std::function<int(hipStream_t)> fn, std::initializer_list<Op::Access> touched) const;
 };
 
-// Footprint-min table of an HZB (trhip_texture_t::quad), k_hzb.hip.  ensure: allocate + lay out (record time);
-// emit: a command that rebuilds it (side stream when there is one); launch: rebuild right now on `s`.
+// Footprint-min table of an HZB (trhip_texture_t::quad), k_hzb.hip.  ensure: allocate + lay out (record time); launch: rebuild on `s`.
 int hzbQuadEnsure(trhip_texture_t* tex);
-int hzbQuadEmitBuild(const DispatchCtx& ctx, trhip_texture_t* tex);
 int hzbQuadLaunchBuild(trhip_texture_t* tex, hipStream_t s);
 
 // Instance cull cache (instance_cache.hip.h, k_gpuculling.hip).  ensure: allocate (record time); launch: rebuild on
@@ -352,9 +326,9 @@ int instanceCacheEnsure(trhip_buffer_t* instances);
 int instanceCacheLaunchBuild(trhip_buffer_t* instances, trhip_buffer_t* meshData, hipStream_t s);
 
 // Record capacity (groups) from which the early meshlet cull resolves its HZB lookups through the footprint-min table
-// (rebuilt per frame: on the side stream beside a large instance pass, by extra workgroups of a small one's launch) instead of
-// the texels.  2^17: a rank's share of C3 at 8 ranks (390 k groups: 53 instead of 75 us for its early cull); real assets below
-// that keep the texel path.  TRHIP_TABLE_MIN_GROUPS overrides (tuning).
+// (rebuilt per frame by extra workgroups of the early instance pass's own launches) instead of the texels.  2^17: a rank's
+// share of C3 at 8 ranks (390 k groups: 53 instead of 75 us for its early cull); real assets below that keep the texel path.
+// TRHIP_TABLE_MIN_GROUPS overrides (tuning); tests/test_gpu_size_boundaries.py reads the default from the line below.
 inline uint32_t tableMinGroups()
 {
     static const uint32_t v = [] { const char* e = getenv("TRHIP_TABLE_MIN_GROUPS"); return e ? (uint32_t)strtoul(e, nullptr, 0) : (1u << 17); }();
@@ -386,6 +360,9 @@ struct ShaderRegistrar
 // it sets a tap; EVERY launch of that command on that stream (every launch of the back end goes through TRHIP_LAUNCH) is
 // given the fork event as its stop event -- like a re-recorded event it ends up standing for the last of them (checked by
 // tools/sync_cost.hip: two launches, one event, the waiter sees the second one's result).
+// THE RULE: a tapped op's last TRHIP_LAUNCH must be its last work on that stream (work behind it is outside the fork).  An op
+// that launches nothing (a copy) forks with a marker event, and so does a host callback: the caller's code may launch through
+// TRHIP_LAUNCH (trhip_launch_shard_late_info) and then enqueue more, so trhip_queue_execute never taps it.
 struct LaunchTap { hipStream_t onStream = nullptr; hipEvent_t stopEvent = nullptr; int launches = 0; };
 extern thread_local LaunchTap* g_launchTap;
 #define TRHIP_LAUNCH(kernel, grid, block, shmem, stream, ...)                                                       \
