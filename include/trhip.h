@@ -44,8 +44,10 @@ enum {
 };
 
 /* nvrhi::Format subset used on the path (GraphicConstants.h:25-28).  RG32_UINT (the visibility buffer: each texel one
- * little-endian u64) and RG16_FLOAT (the motion target, GBufferMotion) have one mip only. */
-enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4 };
+ * little-endian u64), RG16_FLOAT (the motion target, GBufferMotion) and RGBA32_UINT (GBufferA, GraphicConstants.h:24: 16 bytes per
+ * texel, little-endian words x, y, z, w) have one mip only. */
+enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4,
+       TRHIP_FORMAT_RGBA32_UINT = 5 };
 
 /* ---- error / introspection ---------------------------------------------------------------- */
 const char* trhip_last_error(void);          /* thread-local text of the last failure          */
@@ -66,7 +68,13 @@ uint32_t    trhip_abi_version(void);
  * "basepass_PS_Main_motion" (basepass.hlsl:226-237, GBufferMotion): a direct dispatch of [numthreads(8, 8, 1)] groups over
  * the screen; b0 BasePassConstants (m_PrevWorldToClip set), t0 t1 t2 t4 t5 t6 as above, t10..t13 the four slots' records,
  * t14..t17 their visible lists, t18 (texture) the visibility buffer, u0 (texture) RG16_FLOAT motion target: the screen-space
- * motion to the previous frame, in pixels, of every pixel with a nonzero visibility texel (others are left as they are). */
+ * motion to the previous frame, in pixels, of every pixel with a nonzero visibility texel (others are left as they are).
+ * "basepass_PS_Main_GBuffer" (basepass.hlsl:231-253, both targets of the reference's pixel shader, texture-free materials):
+ * dispatched as the motion shader, same bindings, plus t3 MaterialData (124-byte stride; the first 32 bytes are read, the
+ * texture flags ignored), u0 (texture) RGBA32_UINT GBufferA and u1 (texture) the RG16_FLOAT motion target, both required.
+ * Per pixel with a nonzero texel: u0 = PackGBuffer(albedo + debug byte by m_DebugMode 2 / 3 / 12, interpolated vertex
+ * normal, emissive, roughness 1, metallic 0), u1 = the words "basepass_PS_Main_motion" writes.  A pixel whose chain of
+ * indices leaves a bound buffer (m_MaterialDataIdx included) is left as it is in both targets. */
 uint32_t    trhip_shader_count(void);
 const char* trhip_shader_name(uint32_t index);
 int         trhip_shader_exists(const char* name);
@@ -175,8 +183,8 @@ int  trhip_cmd_close(trhip_cmdlist cl);                               /* ::close
  * On a volatile constant buffer this sets the version later dispatches in this list see. */
 int  trhip_cmd_write_buffer(trhip_cmdlist cl, trhip_buffer buf, uint64_t dst_offset, const void* src, uint64_t bytes);
 int  trhip_cmd_clear_buffer_u32(trhip_cmdlist cl, trhip_buffer buf, uint32_t value);   /* ::clearBufferUInt   */
-int  trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value);    /* ::clearTextureFloat (16-bit formats: the fp16 of value, RNE; not RG32_UINT) */
-int  trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value); /* ::clearTextureUInt: RG32_UINT, value in every 32-bit channel word */
+int  trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value);    /* ::clearTextureFloat (16-bit formats: the fp16 of value, RNE; not the UINT formats) */
+int  trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value); /* ::clearTextureUInt: RG32_UINT / RGBA32_UINT, value in every 32-bit channel word */
 int  trhip_cmd_copy_buffer(trhip_cmdlist cl, trhip_buffer dst, uint64_t dst_offset, trhip_buffer src, uint64_t src_offset, uint64_t bytes); /* ::copyBuffer */
 /* Multi-GPU hook (no counterpart in the reference, which is single-GPU: GraphicRHI.cpp:165).
  * fn(user, hip_stream) is called on the submitting thread while the list is executed, in order with

@@ -77,6 +77,16 @@ int  trhost_set_raster_depth(int enable);
 int  trhost_set_visibility_buffer(int enable);
 int  trhost_download_visibility(uint64_t* texels, uint64_t bytes);
 int  trhost_download_motion(uint16_t* halves, uint64_t bytes);
+/* GBufferA for texture-free materials (implies the visibility buffer, same refusals): "basepass_PS_Main_GBuffer" resolves
+ * GBufferRenderer's GBufferA (RGBA32_UINT: PackGBuffer's x, y, z, w per texel, 16 bytes; 0 = nothing drawn) and GBufferMotion
+ * in one dispatch in the place of "basepass_PS_Main_motion".  trhost_load_materials uploads MaterialData[count] (124-byte
+ * stride, Graphic::m_GlobalMaterialDataBuffer; BasePassInstanceConstants::m_MaterialDataIdx indexes it) and refuses a material
+ * whose m_MaterialFlags names a texture; it comes before trhost_set_gbuffer(1).  trhost_set_debug_view_mode sets
+ * Scene::m_DebugViewMode -> m_DebugMode (2 ColorizeInstances, 3 ColorizeMeshlets, 12 MeshLOD fill GBufferA's debug byte). */
+int  trhost_load_materials(const void* materials, uint32_t count);
+int  trhost_set_gbuffer(int enable);
+int  trhost_set_debug_view_mode(uint32_t mode);
+int  trhost_download_gbuffer_a(uint32_t* words, uint64_t bytes);
 int  trhost_download_depth(float* depth, uint64_t bytes);
 int  trhost_upload_hzb_mip(uint32_t mip, const uint16_t* texels, uint64_t bytes);
 int  trhost_download_hzb_mip(uint32_t mip, uint16_t* texels, uint64_t bytes);

@@ -19,6 +19,18 @@ static constexpr uint32_t kCullingFlagFrustumCullingEnable = (1u << 0);
 static constexpr uint32_t kCullingFlagOcclusionCullingEnable = (1u << 1);
 static constexpr uint32_t kCullingFlagMeshletConeCullingEnable = (1u << 2);
 
+// ShaderInterop.h:10-13
+static constexpr uint32_t MaterialFlag_UseAlbedoTexture = (1u << 0);
+static constexpr uint32_t MaterialFlag_UseNormalTexture = (1u << 1);
+static constexpr uint32_t MaterialFlag_UseMetallicRoughnessTexture = (1u << 2);
+static constexpr uint32_t MaterialFlag_UseEmissiveTexture = (1u << 3);
+static constexpr uint32_t kMaterialFlagAnyTexture = 0xFu;
+
+// ShaderInterop.h:27-37 (the debug views that write GBufferA's debug byte)
+static constexpr uint32_t kDeferredLightingDebugMode_ColorizeInstances = 2;
+static constexpr uint32_t kDeferredLightingDebugMode_ColorizeMeshlets = 3;
+static constexpr uint32_t kDeferredLightingDebugMode_MeshLOD = 12;
+
 // ShaderInterop.h:19-24
 static constexpr uint32_t kMaxMeshletVertices = 64;
 static constexpr uint32_t kMaxMeshletTriangles = 96;
@@ -57,6 +69,31 @@ struct BasePassInstanceConstants
     uint32_t m_MeshDataIdx;
     uint32_t m_MaterialDataIdx;
     float PAD0[2];
+};
+
+// ShaderInterop.h:150-158
+struct TextureData
+{
+    uint32_t m_GlobalIndex;
+    uint32_t m_IsWrapSampler;
+    uint32_t m_DescriptorIndex;
+    uint32_t m_FeedbackTextureDescriptorIndex;
+    uint32_t m_MinMapTextureDescriptorIndex;
+};
+
+// ShaderInterop.h:160-172.  The G-buffer resolve (k_gbuffer.hip) reads the first 32 bytes only: texture-free materials.
+struct MaterialData
+{
+    Vector4 m_ConstAlbedo;
+    float m_ConstEmissive[3];
+    float m_AlphaCutoff;
+    TextureData m_AlbedoTexture;
+    TextureData m_NormalTexture;
+    TextureData m_MetallicRoughnessTexture;
+    TextureData m_EmissiveTexture;
+    uint32_t m_MaterialFlags;
+    float m_ConstRoughness;                  // Q13: never read by the reference's shader (roughness 1, metallic 0 without a texture)
+    float m_ConstMetallic;
 };
 
 // ShaderInterop.h:117-122
@@ -214,6 +251,10 @@ static_assert(offsetof(BasePassConstants, m_NearPlane) == 224);
 static_assert(offsetof(BasePassConstants, m_CullingFlags) == 228);
 static_assert(sizeof(BasePassInstanceConstants) == 144);
 static_assert(offsetof(BasePassInstanceConstants, m_MeshDataIdx) == 128);
+static_assert(sizeof(TextureData) == 20);
+static_assert(sizeof(MaterialData) == 124);
+static_assert(offsetof(MaterialData, m_ConstEmissive) == 16 && offsetof(MaterialData, m_AlphaCutoff) == 28);
+static_assert(offsetof(MaterialData, m_AlbedoTexture) == 32 && offsetof(MaterialData, m_MaterialFlags) == 112);
 static_assert(sizeof(DispatchIndirectArguments) == 12);
 static_assert(sizeof(GPUCullingPassConstants) == 180);
 static_assert(offsetof(GPUCullingPassConstants, m_Frustum) == 16);

@@ -157,6 +157,7 @@ public:
     nvrhi::BufferHandle m_LastLateCullInstanceCountBuffer, m_LastLateCullDispatchIndirectArgsBuffer;
     nvrhi::TextureHandle m_CurrentDepthBuffer, m_LastDepthBuffer;     // depth attachment of the pass being recorded / of the last frame (read-back)
     nvrhi::TextureHandle m_VisibilityBuffer, m_MotionBuffer;           // RG32_UINT / RG16_FLOAT at render resolution (m_bVisibilityBuffer)
+    nvrhi::TextureHandle m_GBufferA;                                    // RGBA32_UINT at render resolution (m_bGBuffer; GraphicConstants.h:24)
 
 protected:
     RenderGraph::ResourceHandle m_LateCullDispatchIndirectArgsRDGBufferHandle;
@@ -437,7 +438,10 @@ public:
     static Matrix PrevWorldToClip() { return MultiplyNoFMA(g_Scene->m_View.m_CullingPrevWorldToView, g_Scene->m_View.m_PrevViewToClip); }
 
     // GBufferMotion of every pixel the base pass drew (basepass.hlsl:226-237), once after the last raster.
-    void ResolveMotion(nvrhi::CommandListHandle commandList)
+    // bGBuffer (ResolveGBuffer): "basepass_PS_Main_GBuffer" instead -- GBufferA at u0, the motion target at u1, materials at t3,
+    // m_DebugMode from the scene's debug view (BasePassRenderers.cpp:455) -- one dispatch for both targets.
+    void ResolveGBuffer(nvrhi::CommandListHandle commandList) { ResolveMotion(commandList, true); }
+    void ResolveMotion(nvrhi::CommandListHandle commandList, bool bGBuffer = false)
     {
         using Item = nvrhi::BindingSetItem;
         BasePassConstants k{};
@@ -446,9 +450,10 @@ public:
         k.m_PrevWorldToClip = PrevWorldToClip();
         k.m_NearPlane = g_Scene->m_View.m_ZNearP;
         k.m_OutputResolution = g_Graphic.m_RenderResolution;
+        if (bGBuffer) k.m_DebugMode = g_Scene->m_DebugViewMode;
         Graphic::ComputePassParams p;
         p.m_CommandList = commandList;
-        p.m_ShaderName = "basepass_PS_Main_motion";
+        p.m_ShaderName = bGBuffer ? "basepass_PS_Main_GBuffer" : "basepass_PS_Main_motion";
         p.m_BindingSetDesc.bindings = {
             Item::ConstantBuffer(0, g_Graphic.CreateConstantBuffer(commandList, k)),
             Item::StructuredBuffer_SRV(0, g_Scene->m_InstanceConstsBuffer),
@@ -458,8 +463,13 @@ public:
             Item::StructuredBuffer_SRV(5, g_Graphic.m_GlobalMeshletVertexOffsetsBuffer),
             Item::StructuredBuffer_SRV(6, g_Graphic.m_GlobalMeshletIndicesBuffer),
             Item::Texture_SRV(18, m_VisibilityBuffer),
-            Item::Texture_UAV(0, m_MotionBuffer),
+            Item::Texture_UAV(bGBuffer ? 1 : 0, m_MotionBuffer),
         };
+        if (bGBuffer) {
+            check(g_Graphic.m_GlobalMaterialDataBuffer && m_GBufferA);
+            p.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_SRV(3, g_Graphic.m_GlobalMaterialDataBuffer));   // :469
+            p.m_BindingSetDesc.bindings.push_back(Item::Texture_UAV(0, m_GBufferA));
+        }
         for (uint32_t s = 0; s < kNumPassSlots; ++s) {                        // a slot that did not run: the dummy buffer
             const PassOutputs& o = m_Outputs[s];
             p.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_SRV(10 + s, o.m_bRan ? o.m_MeshletAmplificationDataBuffer : g_CommonResources.DummyUIntStructuredBuffer));
@@ -586,6 +596,10 @@ public:
             check(m_VisibilityBuffer && m_MotionBuffer);
             commandList->clearTextureUInt(m_VisibilityBuffer, nvrhi::AllSubresources, 0);                   // 0 = nothing drawn
             commandList->clearTextureFloat(m_MotionBuffer, nvrhi::AllSubresources, nvrhi::Color{ 0.0f });
+            if (g_Scene->m_bGBuffer) {
+                check(m_GBufferA);
+                commandList->clearTextureUInt(m_GBufferA, nvrhi::AllSubresources, 0);
+            }
         }
 
         GPUCulling(commandList, renderGraph, kEarlyOpaque, false /* bLateCull */, false /* bAlphaMaskPrimitives */);          // :565-566
@@ -603,7 +617,7 @@ public:
                 GPUCulling(commandList, renderGraph, kLateAlphaMask, true, true);
                 RenderInstances(commandList, renderGraph, kLateAlphaMask, true, true);
             }
-            if (g_Scene->m_bVisibilityBuffer) ResolveMotion(commandList);
+            if (g_Scene->m_bVisibilityBuffer) ResolveMotion(commandList, g_Scene->m_bGBuffer);
             GenerateHZB(commandList, renderGraph, hzbParams);
         } else {
             if (m_NumSlotsThisFrame == kNumPassSlots) {
@@ -611,7 +625,7 @@ public:
                 GPUCulling(commandList, renderGraph, kEarlyAlphaMask, false, true);
                 RenderInstances(commandList, renderGraph, kEarlyAlphaMask, false, true);
             }
-            if (g_Scene->m_bVisibilityBuffer) ResolveMotion(commandList);
+            if (g_Scene->m_bVisibilityBuffer) ResolveMotion(commandList, g_Scene->m_bGBuffer);
         }
     }
 };
@@ -684,6 +698,15 @@ public:
             desc.debugName = "GBufferMotion";
             m_MotionBuffer = g_Graphic.m_NVRHIDevice->createTexture(desc);
         }
+        if (g_Scene->m_bGBuffer && !m_GBufferA) {                             // GBufferRenderer::Setup (:622-632)
+            nvrhi::TextureDesc desc;
+            desc.width = g_Graphic.m_RenderResolution.x;
+            desc.height = g_Graphic.m_RenderResolution.y;
+            desc.isUAV = true;
+            desc.format = GraphicConstants::kGBufferAFormat;
+            desc.debugName = "GBufferA";
+            m_GBufferA = g_Graphic.m_NVRHIDevice->createTexture(desc);
+        }
         RenderBasePassParams params;                                          // :691-695
         params.m_DepthBuffer = depthStencilBuffer;
         RenderBasePass(commandList, renderGraph, params);
@@ -718,6 +741,7 @@ void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::
 nvrhi::TextureHandle GetLastDepthBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_LastDepthBuffer; }
 nvrhi::TextureHandle GetVisibilityBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_VisibilityBuffer; }
 nvrhi::TextureHandle GetMotionBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_MotionBuffer; }
+nvrhi::TextureHandle GetGBufferA() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_GBufferA; }
 
 void ReleaseVisibilityPassBuffers()
 {
@@ -726,7 +750,7 @@ void ReleaseVisibilityPassBuffers()
     r->m_LastLateCullInstanceCountBuffer = nullptr;
     r->m_LastLateCullDispatchIndirectArgsBuffer = nullptr;
     r->m_CurrentDepthBuffer = nullptr; r->m_LastDepthBuffer = nullptr;
-    r->m_VisibilityBuffer = nullptr; r->m_MotionBuffer = nullptr;
+    r->m_VisibilityBuffer = nullptr; r->m_MotionBuffer = nullptr; r->m_GBufferA = nullptr;
     r->ReleasePipelineStatisticsQueries();
     for (ShardLateCall& c : g_ShardLateCalls) c = ShardLateCall{};
     SetShardLateExchange(nullptr, nullptr);

@@ -83,6 +83,7 @@ void Graphic::Shutdown()
     m_GlobalMeshDataBuffer = nullptr;
     m_GlobalMeshletDataBuffer = nullptr;
     m_GlobalVertexBuffer = nullptr; m_GlobalMeshletVertexOffsetsBuffer = nullptr; m_GlobalMeshletIndicesBuffer = nullptr;
+    m_GlobalMaterialDataBuffer = nullptr;
     m_PendingCommandLists.clear();
     for (auto& pool : m_FreeCommandLists) pool.clear();
     m_AllCommandLists.clear();

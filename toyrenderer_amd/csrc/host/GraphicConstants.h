@@ -10,6 +10,8 @@ static constexpr bool kInversedDepthBuffer = true;
 static constexpr bool kInfiniteDepthBuffer = true;
 static constexpr float kNearDepth = kInversedDepthBuffer ? 1.0f : 0.0f;
 static constexpr float kFarDepth = 1.0f - kNearDepth;
+static constexpr nvrhi::Format kGBufferAFormat = nvrhi::Format::RGBA32_UINT;
+static constexpr nvrhi::Format kGBufferMotionFormat = nvrhi::Format::RG16_FLOAT;
 static constexpr nvrhi::Format kDepthStencilFormat = nvrhi::Format::D24S8;
 static constexpr nvrhi::Format kHZBFormat = nvrhi::Format::R16_FLOAT;
 } // namespace GraphicConstants

@@ -144,6 +144,22 @@ void Scene::LoadGeometry(const void* vertices, uint64_t numVertices, const uint3
     g_Graphic.m_GlobalMeshletIndicesBuffer = make("GlobalMeshletIndicesBuffer", meshletTriangles, numTriangles * 4u, 4u);
 }
 
+void Scene::LoadMaterials(const void* materials, uint32_t numMaterials)
+{
+    const interop::MaterialData* m = (const interop::MaterialData*)materials;
+    for (uint32_t i = 0; i < numMaterials; ++i)
+        if (m[i].m_MaterialFlags & interop::kMaterialFlagAnyTexture)
+            throw std::runtime_error("materials: material " + std::to_string(i) + " uses a texture (m_MaterialFlags): textured materials are not supported");
+    nvrhi::BufferDesc d;
+    d.byteSize = numMaterials ? (uint64_t)numMaterials * sizeof(interop::MaterialData) : sizeof(interop::MaterialData);
+    d.structStride = sizeof(interop::MaterialData);
+    d.debugName = "GlobalMaterialDataBuffer";
+    d.initialState = nvrhi::ResourceStates::ShaderResource;
+    nvrhi::BufferHandle b = g_Graphic.m_NVRHIDevice->createBuffer(d);
+    if (numMaterials) nvrhi::throwIfFailed(trhip_buffer_upload(b->native(), 0, materials, (uint64_t)numMaterials * sizeof(interop::MaterialData)), "Scene material upload");
+    g_Graphic.m_GlobalMaterialDataBuffer = b;
+}
+
 void Scene::LoadNodes(const void* nodes, uint32_t numNodes, const uint32_t* primitiveToNode)
 {
     // UpdateInstanceConstsRenderer::CreateNodeTransformsBuffer (BasePassRenderers.cpp:64-104)

@@ -89,6 +89,12 @@ public:
     // "basepass_MS_Main_visibility" into GBufferRenderer's VisibilityBuffer, and "basepass_PS_Main_motion" resolves
     // GBufferMotion once after the last pass.
     bool m_bVisibilityBuffer = false;
+    // GBufferA (trhost_set_gbuffer; implies m_bVisibilityBuffer): "basepass_PS_Main_GBuffer" resolves GBufferA and
+    // GBufferMotion in one dispatch in the place of "basepass_PS_Main_motion".  Needs LoadMaterials.
+    bool m_bGBuffer = false;
+    uint32_t m_DebugViewMode = 0;                    // Scene.h: feeds BasePassConstants::m_DebugMode (BasePassRenderers.cpp:455)
+    // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.
+    void LoadMaterials(const void* materials, uint32_t numMaterials);
     // `<scene>_CachedData.bin` version 3 (SceneLoading.cpp:57-79 layout, :706-781 LoadCachedData): meshes, meshlets and
     // the mesh-shader geometry come from the file, instances and id lists from the caller (the glTF side of the reference).
     void LoadCachedData(const char* path, const void* instances, uint32_t numInstances, const uint32_t* opaqueIds, uint32_t numOpaque,

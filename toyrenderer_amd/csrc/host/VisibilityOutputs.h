@@ -38,6 +38,8 @@ nvrhi::TextureHandle GetLastDepthBuffer();
 // GBufferRenderer's visibility buffer (RG32_UINT) and motion target (RG16_FLOAT); null until a frame ran with them on.
 nvrhi::TextureHandle GetVisibilityBuffer();
 nvrhi::TextureHandle GetMotionBuffer();
+// GBufferRenderer's GBufferA (RGBA32_UINT); null until a frame ran with the G-buffer on.
+nvrhi::TextureHandle GetGBufferA();
 // the base pass's pipeline statistics: the value its frame N showed (the query of frame N - 2) and the last executed frame's (waits)
 void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest);
 

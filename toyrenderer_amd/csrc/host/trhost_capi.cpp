@@ -118,6 +118,40 @@ int trhost_set_visibility_buffer(int enable)
     });
 }
 
+int trhost_load_materials(const void* materials, uint32_t count)
+{
+    return guarded([&] {
+        check(g_Scene && (materials || !count));
+        g_Scene->LoadMaterials(materials, count);
+    });
+}
+
+int trhost_set_gbuffer(int enable)
+{
+    return guarded([&] {
+        check(!enable || g_Graphic.m_GlobalVertexBuffer);      // trhost_load_geometry first
+        if (enable && !g_Graphic.m_GlobalMaterialDataBuffer) throw nvrhi::Error("trhost_set_gbuffer: no materials (trhost_load_materials first)");
+        if (enable && g_Graphic.m_MaxMeshletGroups > (1u << 18))
+            throw nvrhi::Error("trhost_set_gbuffer: max_meshlet_groups above 2^18 (list positions must stay below 2^23)");
+        g_Scene->m_bGBuffer = enable != 0;
+        if (enable) { g_Scene->m_bVisibilityBuffer = true; g_Scene->m_bRasterDepth = true; }   // implies the visibility buffer
+    });
+}
+
+int trhost_set_debug_view_mode(uint32_t mode)
+{
+    return guarded([&] { check(g_Scene); g_Scene->m_DebugViewMode = mode; });
+}
+
+int trhost_download_gbuffer_a(uint32_t* words, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetGBufferA();
+        check(t && words);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, words, bytes), "trhost_download_gbuffer_a");
+    });
+}
+
 int trhost_download_visibility(uint64_t* texels, uint64_t bytes)
 {
     return guarded([&] {

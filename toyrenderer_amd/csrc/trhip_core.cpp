@@ -478,14 +478,15 @@ int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_te
     if (!dev || !d || !out) return fail(TRHIP_ERR_INVALID, "texture_create: null argument");
     if (d->width == 0 || d->height == 0 || d->mipLevels == 0 || d->mipLevels > 16)
         return fail(TRHIP_ERR_INVALID, "texture_create: bad dimensions %ux%u mips %u", d->width, d->height, d->mipLevels);
-    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && d->format != TRHIP_FORMAT_RG32_UINT && d->format != TRHIP_FORMAT_RG16_FLOAT)
+    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && d->format != TRHIP_FORMAT_RG32_UINT && d->format != TRHIP_FORMAT_RG16_FLOAT &&
+        d->format != TRHIP_FORMAT_RGBA32_UINT)
         return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u", d->format);
-    if ((d->format == TRHIP_FORMAT_RG32_UINT || d->format == TRHIP_FORMAT_RG16_FLOAT) && d->mipLevels != 1)
-        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT textures have one mip, got %u", d->mipLevels);
+    if ((d->format == TRHIP_FORMAT_RG32_UINT || d->format == TRHIP_FORMAT_RG16_FLOAT || d->format == TRHIP_FORMAT_RGBA32_UINT) && d->mipLevels != 1)
+        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT textures have one mip, got %u", d->mipLevels);
     auto t = std::make_unique<trhip_texture_t>();
     t->dev = dev;
     t->width = d->width; t->height = d->height; t->mips = d->mipLevels; t->format = d->format;
-    t->texelBytes = d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT ? 8 : 4;
+    t->texelBytes = d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT ? 8 : d->format == TRHIP_FORMAT_RGBA32_UINT ? 16 : 4;
     t->isUAV = d->isUAV != 0; t->isVirtual = d->isVirtual != 0;
     t->name = d->debugName ? d->debugName : "";
     uint64_t off = 0;
@@ -698,8 +699,8 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
-    if (tex->format == TRHIP_FORMAT_RG32_UINT)
-        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): RG32_UINT is cleared with clear_texture_u32", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_RG32_UINT || tex->format == TRHIP_FORMAT_RGBA32_UINT)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): RG32_UINT / RGBA32_UINT are cleared with clear_texture_u32", tex->name.c_str());
     void* p = tex->ptr;
     cl->hold(tex, true);
     if (tex->format == TRHIP_FORMAT_R32_FLOAT) {
@@ -719,14 +720,15 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
     return TRHIP_OK;
 }
 
-// nvrhi clearTextureUInt: the value goes into every 32-bit channel word (RG32_UINT: both words of each texel).
+// nvrhi clearTextureUInt: the value goes into every 32-bit channel word (RG32_UINT: both words of each texel,
+// RGBA32_UINT: all four).
 int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value)
 {
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
-    if (tex->format != TRHIP_FORMAT_RG32_UINT)
-        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): needs an RG32_UINT texture", tex->name.c_str());
+    if (tex->format != TRHIP_FORMAT_RG32_UINT && tex->format != TRHIP_FORMAT_RGBA32_UINT)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): needs an RG32_UINT or RGBA32_UINT texture", tex->name.c_str());
     void* p = tex->ptr;
     cl->hold(tex, true);
     const size_t n = (size_t)(tex->totalBytes / 4);

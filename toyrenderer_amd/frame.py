@@ -48,6 +48,7 @@ class GpuScene:
         self.alphaMaskIds = dev.buffer_from(np.asarray(alphaMaskIds, np.uint32), "AlphaMaskInstanceIDsBuffer", uav=False)
         self.numOpaque, self.numAlphaMask = len(opaqueIds), len(alphaMaskIds)
         self.vertices = self.meshletVertexIds = self.meshletTriangles = None
+        self.materials = None
 
     def set_geometry(self, vertices, meshletVertexIds, meshletTriangles):
         """The buffers the mesh shader reads (basepass.hlsl t1, t5, t6): lets the frame rasterise its own depth
@@ -56,8 +57,20 @@ class GpuScene:
         self.meshletVertexIds = self.dev.buffer_from(np.ascontiguousarray(meshletVertexIds, np.uint32), "GlobalMeshletVertexIdxOffsetsBuffer", uav=False)
         self.meshletTriangles = self.dev.buffer_from(np.ascontiguousarray(meshletTriangles, np.uint32), "GlobalMeshletIndicesBuffer", uav=False)
 
+    def set_materials(self, materials):
+        """The MaterialData buffer (basepass.hlsl t3, Graphic::m_GlobalMaterialDataBuffer) that FrameDriver(gbuffer=True)
+        resolves GBufferA from.  Texture-free materials only: the resolve has no texture sampling."""
+        materials = np.ascontiguousarray(materials, I.MaterialData)
+        if np.any(materials["m_MaterialFlags"] & I.kMaterialFlagAnyTexture):
+            raise ValueError("set_materials: a material uses a texture (m_MaterialFlags): textured materials are not supported")
+        if self.materials is not None:
+            self.materials.release()
+        self.materials = self.dev.buffer_from(materials, "GlobalMaterialDataBuffer", uav=False, min_bytes=124)
+        self.numMaterials = len(materials)
+
     def release(self):
-        for b in (self.instances, self.meshData, self.meshlets, self.opaqueIds, self.alphaMaskIds, self.vertices, self.meshletVertexIds, self.meshletTriangles):
+        for b in (self.instances, self.meshData, self.meshlets, self.opaqueIds, self.alphaMaskIds, self.vertices, self.meshletVertexIds, self.meshletTriangles,
+                  self.materials):
             if b is not None:
                 b.release()
 
@@ -67,15 +80,24 @@ class FrameDriver:
 
     def __init__(self, dev: rhi.Device, scene: GpuScene, view, *, record_capacity: int, list_capacity: int | None = None,
                  culling_flags: int = 7, force_mesh_lod: int = -1, freeze_culling_camera: bool = False, alloc=None,
-                 shard_late=None, raster_depth: bool = False, visibility: bool = False):
+                 shard_late=None, raster_depth: bool = False, visibility: bool = False, gbuffer: bool = False,
+                 debug_mode: int = 0):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
         frame is submitted: phase 0 after each early instance cull, phase 1 before each late one (include/trhost.h).
         visibility: rasterise through "basepass_MS_Main_visibility" (implies raster_depth) into self.visibility (RG32_UINT)
-        and resolve self.motion (RG16_FLOAT, "basepass_PS_Main_motion") after the last slot; m_PrevWorldToClip is set."""
+        and resolve self.motion (RG16_FLOAT, "basepass_PS_Main_motion") after the last slot; m_PrevWorldToClip is set.
+        gbuffer: implies visibility; one "basepass_PS_Main_GBuffer" dispatch in the place of the motion resolve writes
+        self.gbufferA (RGBA32_UINT) and self.motion.  Needs GpuScene.set_materials().  debug_mode: m_DebugMode (2, 3 and 12
+        fill GBufferA's debug byte)."""
+        visibility = bool(visibility) or bool(gbuffer)
         if visibility and shard_late is not None:
-            raise ValueError("visibility buffer with a shard exchange: list positions are per rank, not global")
+            raise ValueError(("G-buffer" if gbuffer else "visibility buffer") + " with a shard exchange: list positions are per rank, not global")
+        if gbuffer and scene.materials is None:
+            raise ValueError("gbuffer=True needs GpuScene.set_materials()")
+        self.gbuffer_on = bool(gbuffer)
+        self.debug_mode = int(debug_mode)
         self.visibility_on = bool(visibility)
         self.raster_depth = bool(raster_depth) or self.visibility_on       # depth = the visible meshlets rasterised ("basepass_MS_Main_depth"), cleared per frame
         assert not self.raster_depth or scene.vertices is not None, "raster_depth needs GpuScene.set_geometry()"
@@ -96,7 +118,9 @@ class FrameDriver:
         init = dev.create_command_list()
         init.open(); init.clear_texture_f32(self.hzb, 0.0); init.clear_texture_f32(self.depth, 0.0); init.close()
         dev.execute(init); dev.wait_idle(); init.release()
-        self.visibility = self.motion = None
+        self.visibility = self.motion = self.gbufferA = None
+        if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
+            self.gbufferA = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA32_UINT, "GBufferA")
         if self.visibility_on:                       # GBufferRenderer's visibility buffer + GBufferMotion, render resolution
             self.visibility = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RG32_UINT, "VisibilityBuffer")
             self.motion = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RG16_FLOAT, "GBufferMotion")
@@ -155,6 +179,8 @@ class FrameDriver:
         k["m_OutputResolution"] = (v.renderW, v.renderH)
         if self.visibility_on:                                                           # Scene.cpp:116-118 on this build's raster camera
             k["m_PrevWorldToClip"] = I.world_to_clip(v.prevWorldToView, v.viewToClip)
+        if self.gbuffer_on:
+            k["m_DebugMode"] = self.debug_mode                                           # BasePassRenderers.cpp:455
         return k
 
     # ---- BasePassRenderer::GPUCulling (:298-404) ------------------------------------------------
@@ -223,11 +249,15 @@ class FrameDriver:
         sc, v = self.scene, self.view
         cb = cl.constant_buffer(self._basepass_consts(False), "BasePassConstants")
         b = [CB(0, cb), SRV(0, sc.instances), SRV(1, sc.vertices), SRV(2, sc.meshData), SRV(4, sc.meshlets), SRV(5, sc.meshletVertexIds),
-             SRV(6, sc.meshletTriangles), TEX_SRV(18, self.visibility), TEX_UAV(0, self.motion, 0)]
+             SRV(6, sc.meshletTriangles), TEX_SRV(18, self.visibility)]
         for s in range(4):                                                               # slots without buffers: an empty stand-in
             b += [SRV(10 + s, self.records[s] if s < self.num_slots else self.dummy),
                   SRV(14 + s, self.visibleList[s] if s < self.num_slots else self.dummy)]
-        cl.dispatch("basepass_PS_Main_motion", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
+        if self.gbuffer_on:                                                              # PS_Main_GBuffer: SV_Target0 + SV_Target1 in one dispatch
+            b += [SRV(3, sc.materials), TEX_UAV(0, self.gbufferA, 0), TEX_UAV(1, self.motion, 0)]
+            cl.dispatch("basepass_PS_Main_GBuffer", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
+            return
+        cl.dispatch("basepass_PS_Main_motion", b + [TEX_UAV(0, self.motion, 0)], ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
 
     # ---- BasePassRenderer::GenerateHZB (:505-542) + SPD::Execute (FFXHelpers.cpp:36-115) --------
     def _generate_hzb(self, cl):
@@ -263,6 +293,8 @@ class FrameDriver:
         if self.visibility_on:
             cl.clear_texture_u32(self.visibility, 0)                                     # 0 = nothing drawn
             cl.clear_texture_f32(self.motion, 0.0)
+        if self.gbuffer_on:
+            cl.clear_texture_u32(self.gbufferA, 0)
 
         def do(slot, late, am):
             self.ran[slot] = self._gpu_culling(cl, slot, late, am)
@@ -317,6 +349,6 @@ class FrameDriver:
         for b in (self.lateArgs, self.lateCount, self.lateIds, self.spdAtomic, self.dummy, *(self.shardInfo or ())):
             b.release()
         self.hzb.release(); self.depth.release()
-        for t in (self.visibility, self.motion):
+        for t in (self.visibility, self.motion, self.gbufferA):
             if t is not None:
                 t.release()

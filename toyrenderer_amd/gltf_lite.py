@@ -55,6 +55,8 @@ class LoadedScene:
     vertices: np.ndarray           # RawVertexFormat: the global vertex buffer (positions; packed normals when present)
     meshletVertexIds: np.ndarray   # per meshlet vertex: index into the global vertex buffer
     meshletTriangles: np.ndarray   # packed a | b << 8 | c << 16 (Visual.cpp:396-403)
+    materials: np.ndarray = None   # MaterialData[n + 1]: the glTF's materials, then the default material (SceneLoading.cpp:396-537)
+    primMaterial: np.ndarray = None   # u32 per primitive: index into materials (n where the primitive names none)
 
     def as_oracle(self) -> dict:
         return dict(instances=self.instances, meshData=self.meshData, meshlets=self.meshlets,
@@ -354,6 +356,69 @@ def build_lod_chain(positions: np.ndarray, indices: np.ndarray, simplifier=simpl
     return out
 
 
+# ----------------------------------------------------------------------------------------------- materials
+_KINDA_SMALL_NUMBER = np.float32(1e-4)                 # MathUtilities.h:35
+_DEFAULT_ALBEDO = (1.0, 0.078, 0.576, 1.0)             # Visual.h:138, the material of a primitive that names none
+
+
+def _no_textures(row):
+    for t in ("m_AlbedoTexture", "m_NormalTexture", "m_MetallicRoughnessTexture", "m_EmissiveTexture"):
+        for f in ("m_GlobalIndex", "m_DescriptorIndex", "m_FeedbackTextureDescriptorIndex", "m_MinMapTextureDescriptorIndex"):
+            row[t][f] = 0xFFFFFFFF                     # SetTextureData without a texture (SceneLoading.cpp:486-497)
+
+
+def material_table(gltf_materials: list) -> np.ndarray:
+    """MaterialData[n + 1] as SceneLoader::LoadMaterials fills it (SceneLoading.cpp:396-537) for materials WITHOUT
+    textures: the G-buffer resolve has no texture sampling, so a material that names a texture raises.  The default
+    material comes last, at index n."""
+    n = len(gltf_materials)
+    out = np.zeros(n + 1, I.MaterialData)
+    for i, m in enumerate(gltf_materials):
+        row = out[i]
+        _no_textures(row)
+        name = m.get("name", "Un-Named Material")
+        ext = m.get("extensions", {})
+        sg = ext.get("KHR_materials_pbrSpecularGlossiness")
+        mr = m.get("pbrMetallicRoughness")
+        named = [k for k in ("emissiveTexture", "normalTexture") if k in m]
+        if sg is not None:
+            named += [k for k in ("diffuseTexture", "specularGlossinessTexture") if k in sg]
+        elif mr is not None:
+            named += [k for k in ("baseColorTexture", "metallicRoughnessTexture") if k in mr]
+        if named:
+            raise ValueError(f"glTF-lite: material {i} [{name}] names a texture ({', '.join(named)}): textured materials are not supported")
+        row["m_AlphaCutoff"] = m.get("alphaCutoff", 0.5)
+        e = np.asarray(m.get("emissiveFactor", (0.0, 0.0, 0.0)), np.float32)
+        if np.float32(np.float32(e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) > _KINDA_SMALL_NUMBER:              # :402-410
+            if "KHR_materials_emissive_strength" in ext:
+                e = e * np.float32(ext["KHR_materials_emissive_strength"].get("emissiveStrength", 1.0))
+            row["m_ConstEmissive"] = e
+        if sg is not None:                                                                                    # :417-433
+            row["m_ConstAlbedo"] = sg.get("diffuseFactor", (1.0, 1.0, 1.0, 1.0))
+            row["m_ConstMetallic"] = max(np.asarray(sg.get("specularFactor", (1.0, 1.0, 1.0)), np.float32))
+            row["m_ConstRoughness"] = np.float32(1.0) - np.float32(sg.get("glossinessFactor", 1.0))
+        elif mr is not None:                                                                                  # :434-450
+            row["m_ConstAlbedo"] = mr.get("baseColorFactor", (1.0, 1.0, 1.0, 1.0))
+            row["m_ConstMetallic"] = mr.get("metallicFactor", 1.0)
+            row["m_ConstRoughness"] = mr.get("roughnessFactor", 1.0)
+        else:                                                                                                 # :451-456
+            row["m_ConstAlbedo"] = (1.0, 1.0, 1.0, 1.0)
+            row["m_ConstRoughness"] = 1.0
+        if "KHR_materials_transmission" in ext:                                                               # :458-470
+            row["m_ConstAlbedo"][3] = np.float32(1.0) - np.float32(ext["KHR_materials_transmission"].get("transmissionFactor", 0.0))
+    _no_textures(out[n])                                                                                      # :531-536
+    out[n]["m_ConstAlbedo"] = _DEFAULT_ALBEDO
+    out[n]["m_ConstRoughness"] = 1.0
+    return out
+
+
+def apply_materials(scene: "LoadedScene") -> np.ndarray:
+    """A copy of scene.instances with m_MaterialDataIdx = scene.primMaterial (load() itself leaves the field 0)."""
+    inst = scene.instances.copy()
+    inst["m_MaterialDataIdx"] = scene.primMaterial
+    return inst
+
+
 # ----------------------------------------------------------------------------------------------- loader
 def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
     """lods=False: LOD 0 only (no simplification)."""
@@ -413,7 +478,8 @@ def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
                 q = np.round((nrm * 0.5 + 0.5) * 1023.0).astype(np.uint32)
                 vrows["m_PackedNormal"] = (q[:, 0] << 20) | (q[:, 1] << 10) | q[:, 2]
             vtx.append(vrows)
-            prims.append((len(md_rows), mat.get("alphaMode", "OPAQUE") == "MASK"))
+            prims.append((len(md_rows), mat.get("alphaMode", "OPAQUE") == "MASK",
+                          prim["material"] if "material" in prim and prim["material"] < len(materials) else len(materials)))
             md_rows.append(row)
             vertex_base += len(pos)
         mesh_prims.append(prims)
@@ -447,10 +513,10 @@ def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
             rot = _quat_mul(rot, r)
         return pos, rot
 
-    inst_rows, prim_to_node, opaque, alpha, cameras = [], [], [], [], []
+    inst_rows, prim_to_node, opaque, alpha, cameras, prim_material = [], [], [], [], [], []
     for i, n in enumerate(nodes_in):
         if "mesh" in n:
-            for mesh_idx, is_mask in mesh_prims[n["mesh"]]:
+            for mesh_idx, is_mask, material_idx in mesh_prims[n["mesh"]]:
                 pid = len(inst_rows)
                 r = np.zeros((), I.BasePassInstanceConstants)
                 r["m_WorldMatrix"] = np.eye(4, dtype=np.float32)
@@ -458,6 +524,7 @@ def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
                 r["m_MeshDataIdx"] = mesh_idx
                 inst_rows.append(r)
                 prim_to_node.append(i)
+                prim_material.append(material_idx)
                 (alpha if is_mask else opaque).append(pid)             # Scene.cpp:282-362 buckets
         if "camera" in n:
             c = g["cameras"][n["camera"]]
@@ -470,7 +537,8 @@ def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
         return np.array(rows, dt) if rows else np.zeros(0, dt)
     return LoadedScene(stack(inst_rows, I.BasePassInstanceConstants), stack(md_rows, I.MeshData), stack(ml_rows, I.MeshletData),
                        np.array(opaque, np.uint32), np.array(alpha, np.uint32), nodes, np.array(prim_to_node, np.uint32), cameras,
-                       np.concatenate(vtx) if vtx else np.zeros(0, I.RawVertexFormat), np.array(mvid, np.uint32), np.array(mtri, np.uint32))
+                       np.concatenate(vtx) if vtx else np.zeros(0, I.RawVertexFormat), np.array(mvid, np.uint32), np.array(mtri, np.uint32),
+                       material_table(materials), np.array(prim_material, np.uint32))
 
 
 def view_of(camera: Camera, render=(1920, 1080)):

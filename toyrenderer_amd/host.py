@@ -25,6 +25,7 @@ HOST_SYMBOLS = [
     "trhost_rccl_allgather", "trhost_exchange_create", "trhost_exchange_run", "trhost_exchange_wait", "trhost_exchange_outputs",
     "trhost_exchange_destroy", "trhost_load_geometry", "trhost_set_raster_depth", "trhost_download_depth",
     "trhost_set_visibility_buffer", "trhost_download_visibility", "trhost_download_motion",
+    "trhost_load_materials", "trhost_set_gbuffer", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
 ]
@@ -84,6 +85,10 @@ def load() -> C.CDLL:
     L.trhost_set_visibility_buffer.argtypes = [C.c_int]
     L.trhost_download_visibility.argtypes = [vp, u64]
     L.trhost_download_motion.argtypes = [vp, u64]
+    L.trhost_load_materials.argtypes = [vp, u32]
+    L.trhost_set_gbuffer.argtypes = [C.c_int]
+    L.trhost_set_debug_view_mode.argtypes = [u32]
+    L.trhost_download_gbuffer_a.argtypes = [vp, u64]
     L.trhost_upload_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_download_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_hzb_info.argtypes = [C.POINTER(u32)] * 3
@@ -240,6 +245,25 @@ class Renderer:
         m = np.empty((self.render[1], self.render[0], 2), np.float16)
         _check(load().trhost_download_motion(m.ctypes.data, m.nbytes))
         return m
+
+    def load_materials(self, materials):
+        """MaterialData[] for the G-buffer resolve (texture-free materials; include/trhost.h)."""
+        m = np.ascontiguousarray(materials, I.MaterialData)
+        _check(load().trhost_load_materials(m.ctypes.data, len(m)))
+
+    def set_gbuffer(self, on: bool = True):
+        """GBufferA + motion through one "basepass_PS_Main_GBuffer" dispatch (implies the visibility buffer)."""
+        _check(load().trhost_set_gbuffer(int(on)))
+
+    def set_debug_view_mode(self, mode: int):
+        _check(load().trhost_set_debug_view_mode(int(mode)))
+
+    def download_gbuffer_a(self) -> np.ndarray:
+        """The last frame's GBufferA: uint32 [H, W, 4]."""
+        self.wait_idle()
+        g = np.empty((self.render[1], self.render[0], 4), np.uint32)
+        _check(load().trhost_download_gbuffer_a(g.ctypes.data, g.nbytes))
+        return g
 
     def download_depth(self) -> np.ndarray:
         self.wait_idle()

@@ -15,6 +15,14 @@ kCullingFlagOcclusionCullingEnable = 2
 kCullingFlagMeshletConeCullingEnable = 4
 kMaxNumMeshLODs = 8
 kInvalidMeshLOD = 0xFF
+MaterialFlag_UseAlbedoTexture = 1 << 0                      # ShaderInterop.h:10-13
+MaterialFlag_UseNormalTexture = 1 << 1
+MaterialFlag_UseMetallicRoughnessTexture = 1 << 2
+MaterialFlag_UseEmissiveTexture = 1 << 3
+kMaterialFlagAnyTexture = 0xF
+kDeferredLightingDebugMode_ColorizeInstances = 2            # ShaderInterop.h:27-37: the views that write GBufferA's debug byte
+kDeferredLightingDebugMode_ColorizeMeshlets = 3
+kDeferredLightingDebugMode_MeshLOD = 12
 
 BasePassInstanceConstants = np.dtype([
     ("m_WorldMatrix", np.float32, (4, 4)), ("m_PrevWorldMatrix", np.float32, (4, 4)),
@@ -53,12 +61,20 @@ GIProbeVisualizationUpdateConsts = np.dtype([                                   
 NodeLocalTransform = np.dtype([
     ("m_ParentNodeIdx", np.uint32), ("m_Position", np.float32, (3,)), ("m_Rotation", np.float32, (4,)),
     ("m_Scale", np.float32, (3,)), ("PAD0", np.uint32)])
+TextureData = np.dtype([                                                                                                   # ShaderInterop.h:150-158
+    ("m_GlobalIndex", np.uint32), ("m_IsWrapSampler", np.uint32), ("m_DescriptorIndex", np.uint32),
+    ("m_FeedbackTextureDescriptorIndex", np.uint32), ("m_MinMapTextureDescriptorIndex", np.uint32)])
+MaterialData = np.dtype([                                                                                                  # ShaderInterop.h:160-172
+    ("m_ConstAlbedo", np.float32, (4,)), ("m_ConstEmissive", np.float32, (3,)), ("m_AlphaCutoff", np.float32),
+    ("m_AlbedoTexture", TextureData), ("m_NormalTexture", TextureData), ("m_MetallicRoughnessTexture", TextureData),
+    ("m_EmissiveTexture", TextureData), ("m_MaterialFlags", np.uint32), ("m_ConstRoughness", np.float32), ("m_ConstMetallic", np.float32)])
 UpdateInstanceConstsPassConstants = np.dtype([("m_NumInstances", np.uint32)])
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
     "MeshletAmplificationData": 12, "DispatchIndirectArguments": 12, "GPUCullingPassConstants": 180,
     "BasePassConstants": 256, "MinMaxDownsampleConsts": 12, "NodeLocalTransform": 48,
+    "TextureData": 20, "MaterialData": 124,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)

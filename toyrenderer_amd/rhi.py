@@ -17,6 +17,7 @@ FORMAT_R16_FLOAT = 1
 FORMAT_R32_FLOAT = 2
 FORMAT_RG32_UINT = 3      # visibility buffer: one u64 per texel
 FORMAT_RG16_FLOAT = 4     # motion target: two fp16 per texel
+FORMAT_RGBA32_UINT = 5    # GBufferA: four u32 per texel (x, y, z, w)
 
 BIND_CONSTANT_BUFFER, BIND_PUSH_CONSTANTS, BIND_STRUCTURED_SRV, BIND_STRUCTURED_UAV, BIND_TEXTURE_SRV, BIND_TEXTURE_UAV, BIND_SAMPLER = range(7)
 
@@ -232,10 +233,10 @@ class Texture:
         return max(self.w >> k, 1), max(self.hgt >> k, 1)
 
     def _dtype(self):
-        return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16}.get(self.format, np.float32)
+        return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32}.get(self.format, np.float32)
 
     def _shape(self, mw: int, mh: int):
-        return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw)
+        return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw, 4) if self.format == FORMAT_RGBA32_UINT else (mh, mw)
 
     def upload_mip(self, k: int, arr: np.ndarray):
         arr = np.ascontiguousarray(arr, self._dtype())

@@ -230,6 +230,24 @@ def gen_instances(spec: SceneSpec, begin: int = 0, end: int | None = None, chunk
     return out
 
 
+def materials(seed: int, n: int = 64) -> np.ndarray:
+    """n texture-free MaterialData rows for the synthetic scenes, whose instances draw m_MaterialDataIdx from [0, 64):
+    seeded albedo in [0, 1), one material in four emissive (up to 8), no texture (all texture words 0xFFFFFFFF)."""
+    r = np.random.default_rng([seed, 0x3A7E])
+    out = np.zeros(n, I.MaterialData)
+    out["m_ConstAlbedo"][:, :3] = r.random((n, 3), dtype=np.float32)
+    out["m_ConstAlbedo"][:, 3] = 1.0
+    emissive = r.random((n, 3), dtype=np.float32) * np.float32(8.0)
+    emissive[r.integers(0, 4, n) != 0] = 0.0
+    out["m_ConstEmissive"] = emissive
+    out["m_AlphaCutoff"] = 0.5
+    out["m_ConstRoughness"] = 1.0
+    for t in ("m_AlbedoTexture", "m_NormalTexture", "m_MetallicRoughnessTexture", "m_EmissiveTexture"):
+        for f in ("m_GlobalIndex", "m_DescriptorIndex", "m_FeedbackTextureDescriptorIndex", "m_MinMapTextureDescriptorIndex"):
+            out[t][f] = 0xFFFFFFFF
+    return out
+
+
 def gen_id_lists(spec: SceneSpec):
     """Opaque / alpha-mask primitive id lists (Scene.cpp:282-362): a partition of [0, N)."""
     ids = np.arange(spec.num_instances, dtype=np.uint32)
