@@ -165,6 +165,16 @@ struct MeshletAmplificationData
     uint32_t m_MeshletGroupOffset;
 };
 
+// ShaderInterop.h:278-283: the global vertex buffer.  The mesh stage (mesh_stage.hip.h) reads the position; the G-buffer
+// resolve also reads the normal.
+struct RawVertexFormat
+{
+    float m_Position[3];
+    uint32_t m_PackedNormal;                 // R10G10B10A2
+    uint16_t m_TexCoord[2];                  // half2
+};
+static_assert(sizeof(RawVertexFormat) == 20 && offsetof(RawVertexFormat, m_PackedNormal) == 12, "RawVertexFormat");
+
 // ShaderInterop.h:108-115
 struct DrawIndexedIndirectArguments
 {

@@ -338,6 +338,26 @@ public:
         m_LastLateCullDispatchIndirectArgsBuffer = lateCullDispatchIndirectArgsBuffer;
     }
 
+    // The matrix the raster used the frame before: the reference's m_PrevWorldToClip = m_WorldToClip (Scene.cpp:116-118)
+    // applied to this build's raster camera.
+    static Matrix PrevWorldToClip() { return MultiplyNoFMA(g_Scene->m_View.m_CullingPrevWorldToView, g_Scene->m_View.m_PrevViewToClip); }
+
+    // What the mesh stage reads wherever it runs (csrc/mesh_stage.hip.h): b0 and the geometry at t0, t1, t2, t4, t5, t6.
+    // The rasters and the resolve append their own.
+    static std::vector<nvrhi::BindingSetItem> MeshStageBindings(nvrhi::BufferHandle constants)
+    {
+        using Item = nvrhi::BindingSetItem;
+        return {
+            Item::ConstantBuffer(0, constants),
+            Item::StructuredBuffer_SRV(0, g_Scene->m_InstanceConstsBuffer),
+            Item::StructuredBuffer_SRV(1, g_Graphic.m_GlobalVertexBuffer),
+            Item::StructuredBuffer_SRV(2, g_Graphic.m_GlobalMeshDataBuffer),
+            Item::StructuredBuffer_SRV(4, g_Graphic.m_GlobalMeshletDataBuffer),
+            Item::StructuredBuffer_SRV(5, g_Graphic.m_GlobalMeshletVertexOffsetsBuffer),
+            Item::StructuredBuffer_SRV(6, g_Graphic.m_GlobalMeshletIndicesBuffer),
+        };
+    }
+
     void RenderInstances(nvrhi::CommandListHandle commandList, const RenderGraph& renderGraph, PassSlot slot, bool bIsLateCull, bool bAlphaMaskPrimitives)
     {
         HOST_PROFILE_SCOPE("BasePassRenderer::RenderInstances");
@@ -393,33 +413,23 @@ public:
             check(g_Graphic.m_GlobalVertexBuffer && m_CurrentDepthBuffer);
             basePassConstants.m_WorldToClip = MultiplyNoFMA(g_Scene->m_View.m_CullingWorldToView, g_Scene->m_View.m_ViewToClip);   // :447
             if (g_Scene->m_bVisibilityBuffer) basePassConstants.m_PrevWorldToClip = PrevWorldToClip();
-            nvrhi::BufferHandle rasterConstants = g_Graphic.CreateConstantBuffer(commandList, basePassConstants);
-            nvrhi::BindingSetDesc rasterBindings;
-            rasterBindings.bindings = {
-                nvrhi::BindingSetItem::ConstantBuffer(0, rasterConstants),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(0, g_Scene->m_InstanceConstsBuffer),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(1, g_Graphic.m_GlobalVertexBuffer),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(2, g_Graphic.m_GlobalMeshDataBuffer),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(4, g_Graphic.m_GlobalMeshletDataBuffer),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(5, g_Graphic.m_GlobalMeshletVertexOffsetsBuffer),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(6, g_Graphic.m_GlobalMeshletIndicesBuffer),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(7, meshletAmplificationDataBuffer),
-                nvrhi::BindingSetItem::StructuredBuffer_SRV(9, visibleListBuffer),
-                nvrhi::BindingSetItem::Texture_UAV(0, m_CurrentDepthBuffer),
-            };
             Graphic::ComputePassParams rasterPass;
+            std::vector<Item>& rasterBindings = rasterPass.m_BindingSetDesc.bindings;
+            rasterBindings = MeshStageBindings(g_Graphic.CreateConstantBuffer(commandList, basePassConstants));
+            rasterBindings.push_back(Item::StructuredBuffer_SRV(7, meshletAmplificationDataBuffer));
+            rasterBindings.push_back(Item::StructuredBuffer_SRV(9, visibleListBuffer));
+            rasterBindings.push_back(Item::Texture_UAV(0, m_CurrentDepthBuffer));
             rasterPass.m_CommandList = commandList;
             rasterPass.m_ShaderName = "basepass_MS_Main_depth";
             const uint32_t passSlot = (uint32_t)slot;
             if (g_Scene->m_bVisibilityBuffer) {                               // + the per-pixel identity: u1, push constant {passSlot}
                 check(m_VisibilityBuffer);
-                rasterBindings.bindings.push_back(nvrhi::BindingSetItem::Texture_UAV(1, m_VisibilityBuffer));
-                rasterBindings.bindings.push_back(nvrhi::BindingSetItem::PushConstants(1, sizeof(passSlot)));
+                rasterBindings.push_back(Item::Texture_UAV(1, m_VisibilityBuffer));
+                rasterBindings.push_back(Item::PushConstants(1, sizeof(passSlot)));
                 rasterPass.m_ShaderName = "basepass_MS_Main_visibility";
                 rasterPass.m_PushConstantsData = &passSlot;
                 rasterPass.m_PushConstantsBytes = sizeof(passSlot);
             }
-            rasterPass.m_BindingSetDesc = rasterBindings;
             rasterPass.m_IndirectArgsBuffer = visibleDrawArgsBuffer;
             g_Graphic.AddComputePass(rasterPass);
         }
@@ -432,10 +442,6 @@ public:
         out.m_VisibleMeshletListBuffer = visibleListBuffer;
         out.m_VisibleMeshletDrawArgsBuffer = visibleDrawArgsBuffer;
     }
-
-    // The matrix the raster used the frame before: the reference's m_PrevWorldToClip = m_WorldToClip (Scene.cpp:116-118)
-    // applied to this build's raster camera.
-    static Matrix PrevWorldToClip() { return MultiplyNoFMA(g_Scene->m_View.m_CullingPrevWorldToView, g_Scene->m_View.m_PrevViewToClip); }
 
     // GBufferMotion of every pixel the base pass drew (basepass.hlsl:226-237), once after the last raster.
     // bGBuffer (ResolveGBuffer): "basepass_PS_Main_GBuffer" instead -- GBufferA at u0, the motion target at u1, materials at t3,
@@ -454,17 +460,9 @@ public:
         Graphic::ComputePassParams p;
         p.m_CommandList = commandList;
         p.m_ShaderName = bGBuffer ? "basepass_PS_Main_GBuffer" : "basepass_PS_Main_motion";
-        p.m_BindingSetDesc.bindings = {
-            Item::ConstantBuffer(0, g_Graphic.CreateConstantBuffer(commandList, k)),
-            Item::StructuredBuffer_SRV(0, g_Scene->m_InstanceConstsBuffer),
-            Item::StructuredBuffer_SRV(1, g_Graphic.m_GlobalVertexBuffer),
-            Item::StructuredBuffer_SRV(2, g_Graphic.m_GlobalMeshDataBuffer),
-            Item::StructuredBuffer_SRV(4, g_Graphic.m_GlobalMeshletDataBuffer),
-            Item::StructuredBuffer_SRV(5, g_Graphic.m_GlobalMeshletVertexOffsetsBuffer),
-            Item::StructuredBuffer_SRV(6, g_Graphic.m_GlobalMeshletIndicesBuffer),
-            Item::Texture_SRV(18, m_VisibilityBuffer),
-            Item::Texture_UAV(bGBuffer ? 1 : 0, m_MotionBuffer),
-        };
+        p.m_BindingSetDesc.bindings = MeshStageBindings(g_Graphic.CreateConstantBuffer(commandList, k));
+        p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(18, m_VisibilityBuffer));
+        p.m_BindingSetDesc.bindings.push_back(Item::Texture_UAV(bGBuffer ? 1 : 0, m_MotionBuffer));
         if (bGBuffer) {
             check(g_Graphic.m_GlobalMaterialDataBuffer && m_GBufferA);
             p.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_SRV(3, g_Graphic.m_GlobalMaterialDataBuffer));   // :469

@@ -5,9 +5,10 @@
 // base pass's last raster.
 //
 // CONVENTION (parity unpinned; restated in tests/visibility_ref.c): per pixel with a nonzero texel, decode slot, list
-// position and triangle; recompute the three vertices' screen positions and clip w with the raster's exact operations and
-// the edge functions at the pixel centre; interpolate prevWorld = mulPoint(position, m_PrevWorldMatrix) with perspective
-// weights q_i = e_i / w_i, s = (q0 + q1) + q2, per component fma(q2, P2, fma(q1, P1, q0 * P0)) / s; prevClip = the
+// position and triangle; recompute the three vertices' screen positions and clip w and the edge functions at the pixel
+// centre with the functions the raster calls (mesh_stage.hip.h); interpolate prevWorld = mulPoint(position,
+// m_PrevWorldMatrix) with perspective weights q_i = e_i / w_i, s = (q0 + q1) + q2, per component
+// fma(q2, P2, fma(q1, P1, q0 * P0)) / s; prevClip = the
 // 4-column chain of orc_raster_depth's mul_point4; ClipXYToUV = xy * (0.5, -0.5) + 0.5 as a multiply then an add.  Both
 // components are stored as fp16, round to nearest even (a NaN as 0x7E00).  Pixels without a texel keep their value.
 //

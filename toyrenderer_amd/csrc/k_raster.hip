@@ -4,6 +4,9 @@
 // position * world * worldToClip; PSO BasePassRenderers.cpp:481-495, reverse-Z depth GREATER).  SURVEY.md 8(f) rank 1:
 // it closes the two-phase loop with depth the path produced itself instead of a synthetic depth image.
 //
+// The geometry block, the chain from a visible-list entry to its meshlet, the vertex transform, the edge function and the
+// visibility texel's format are those of mesh_stage.hip.h, which the resolve (visibility_resolve.hip.h) shares.
+//
 // The rasteriser has no source to restate: its rules are this build's CONVENTION (parity unpinned), stated once in
 // oracle/tr_oracle.h (orc_raster_depth) and followed here operation for operation -- no near clipping (a triangle with a
 // vertex at w <= near is dropped), pixel-centre samples, inclusive edge functions on both windings, depth interpolated
@@ -22,7 +25,7 @@
 //
 // "basepass_MS_Main_visibility": the same two launches and the same arithmetic, instantiated with a second sink.  Every
 // covered sample of triangle t of visible-list entry v of pass slot s (push constant) also does one 64-bit atomic max of
-// (depthBits << 32) | s << 30 | v << 7 | t into u1, the RG32_UINT visibility buffer.  TIE RULE (a convention, parity
+// (depthBits << 32) | packVisibility(s, v, t) into u1, the RG32_UINT visibility buffer.  TIE RULE (a convention, parity
 // unpinned: hardware resolves ties by draw order): on equal depth the larger payload wins, so the result does not depend
 // on the draw order, as the depth does not.  The texel is 0 where nothing was drawn (depth > 0 on every written sample).
 // Triangles with index >= 128 (out of contract: kMaxMeshletTriangles is 96) write depth but no visibility texel; a list
@@ -31,10 +34,9 @@
 // depth is still drawn (it can win the payload).  The depth instantiation keeps its kernels, launches, op names and
 // arithmetic; the compiler schedules and allocates its registers slightly differently (tiles: 58 VGPRs instead of 55).
 // tools/raster_time.py at 3840x2160, per launch, before / after the template: main 142.4 / 146.7 us, tiles 179.4 / 176.5 us.
-#include "cull_math.hip.h"
-#include "trhip_internal.h"
+#include "mesh_stage.hip.h"
 
-using namespace interop;
+using namespace mesh;
 
 namespace
 {
@@ -54,20 +56,10 @@ struct BigTriangle                              // 48 bytes
     uint32_t boxX, boxY;                        // x0 | x1 << 16, y0 | y1 << 16 (inclusive pixel bounds)
 };
 
-__device__ __forceinline__ float edgeFn(float ax, float ay, float bx, float by, float px, float py)
-{
-    return cm::fma_(bx - ax, py - ay, -((by - ay) * (px - ax)));
-}
-
 struct RasterArgs
 {
     BasePassConstants k;
-    const BasePassInstanceConstants* instances; uint32_t numInstances;
-    const MeshData* meshData; uint32_t numMeshes;
-    const MeshletData* meshlets; uint64_t numMeshlets;
-    const char* vertices; uint64_t numVertices;                 // RawVertexFormat, 20-byte stride
-    const uint32_t* vertexIds; uint64_t numVertexIds;
-    const uint32_t* triangles; uint64_t numTriangles;
+    Geometry geo;
     const MeshletAmplificationData* records; uint32_t recordCapacity;
     const uint32_t* visibleList; uint32_t listCapacity;
     const uint32_t* drawArgs;                                    // {numVisible, 1, 1}
@@ -85,11 +77,8 @@ struct VisArgs
 {
     unsigned long long* vis;                                     // RG32_UINT as u64
     unsigned long long* queuePayload;                            // scratch: [kQueueCapacity], (1 << 32 | payload) or 0 = no texel
-    uint32_t slotBits;                                           // passSlot << 30
+    uint32_t slotBits;                                           // visSlotBits(passSlot)
 };
-
-constexpr uint32_t kVisTriangles = 128;                          // triangle indices with a visibility texel (7 bits)
-constexpr uint32_t kVisListCapacity = 1u << 23;                  // list positions (23 bits)
 
 // One triangle over the pixels [bx0, bx1] x [by0, by1], `threads` lanes striding over them from `first`; every covered
 // pixel goes to `sink(px, py, depthBits)`.  The arithmetic of orc_raster_depth, operation for operation.
@@ -124,34 +113,18 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
     const float halfW = 0.5f * (float)W, halfH = 0.5f * (float)H;
     const cm::M43 clipXYZ = cm::loadM43(a.k.m_WorldToClip);
     for (uint32_t v = blockIdx.x * kWaves + wave; v < V; v += gridDim.x * kWaves) {
-        const uint32_t e = a.visibleList[v], g = e >> 5, m = e & 31u;
-        if (g >= a.recordCapacity) continue;
-        const MeshletAmplificationData rec = a.records[g];                               // basepass.hlsl:138-142
-        if (rec.m_InstanceConstIdx >= a.numInstances) continue;
-        const BasePassInstanceConstants& inst = a.instances[rec.m_InstanceConstIdx];
-        if (inst.m_MeshDataIdx >= a.numMeshes) continue;
-        const uint32_t lodIdx = rec.m_MeshLOD < kMaxNumMeshLODs ? rec.m_MeshLOD : kMaxNumMeshLODs - 1u;
-        const MeshLODData lod = a.meshData[inst.m_MeshDataIdx].m_MeshLODDatas[lodIdx];
-        const uint64_t mi = (uint64_t)lod.m_MeshletDataBufferIdx + rec.m_MeshletGroupOffset + m;
-        if (mi >= a.numMeshlets) continue;
-        const MeshletData ml = a.meshlets[mi];
-        uint32_t nv = ml.m_VertexAndTriangleCount & 0xFFu, nt = (ml.m_VertexAndTriangleCount >> 8) & 0xFFu;   // :144-145
-        nv = nv < 64u ? nv : 64u;                                                        // kMaxMeshletVertices
-        if ((uint64_t)ml.m_MeshletVertexIDsBufferIdx + nv > a.numVertexIds || (uint64_t)ml.m_MeshletIndexIDsBufferIdx + nt > a.numTriangles) continue;
-        const cm::M43 Wm = cm::loadM43(inst.m_WorldMatrix);
+        withMeshlet(a.visibleList[v], a.records, a.recordCapacity, a.geo, [&](const Meshlet& ml) {   // the rest of the iteration, not indented
+        const uint32_t nv = ml.nv, nt = ml.nt;
+        const cm::M43 Wm = cm::loadM43(ml.inst->m_WorldMatrix);
         // ---- vertices (:149-158): lane l transforms vertex l ------------------------------------------------
         bool ok = false;
         if (lane < nv) {
-            const uint32_t vid = a.vertexIds[ml.m_MeshletVertexIDsBufferIdx + lane];
-            if (vid < a.numVertices) {
-                const float* p = reinterpret_cast<const float*>(a.vertices + (uint64_t)vid * 20u);
-                const cm::F3 wp = cm::mulPoint({ p[0], p[1], p[2] }, Wm);
-                const cm::F3 c = cm::mulPoint(wp, clipXYZ);
-                const float w = cm::fma_(wp.z, a.k.m_WorldToClip.m[2][3], cm::fma_(wp.y, a.k.m_WorldToClip.m[1][3], wp.x * a.k.m_WorldToClip.m[0][3])) + a.k.m_WorldToClip.m[3][3];
-                ok = w > a.k.m_NearPlane;
-                sx[lane] = cm::fma_(c.x / w, halfW, halfW);
-                sy[lane] = cm::fma_(-(c.y / w), halfH, halfH);
-                sd[lane] = c.z / w;
+            const uint32_t vid = a.geo.vertexIds[ml.vertexIdsAt + lane];
+            if (vid < a.geo.numVertices) {
+                const float* p = vertexAt(a.geo, vid).m_Position;
+                const ScreenVertex s = toScreen({ p[0], p[1], p[2] }, Wm, clipXYZ, a.k.m_WorldToClip, halfW, halfH);
+                ok = s.w > a.k.m_NearPlane;
+                sx[lane] = s.sx; sy[lane] = s.sy; sd[lane] = s.depth;
             }
         }
         const unsigned long long okMask = __ballot(ok);
@@ -168,7 +141,7 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
             BigTriangle q = {};
             uint32_t bw = 0, bh = 0;
             if (t < nt) {
-                const uint32_t packed = a.triangles[ml.m_MeshletIndexIDsBufferIdx + t];
+                const uint32_t packed = a.geo.triangles[ml.trianglesAt + t];
                 const uint32_t ia = packed & 0xFFu, ib = (packed >> 8) & 0xFFu, ic = (packed >> 16) & 0xFFu;
                 if (ia < nv && ib < nv && ic < nv && ((okMask >> ia) & (okMask >> ib) & (okMask >> ic) & 1ull)) {
                     q.x0 = sx[ia]; q.y0 = sy[ia]; q.x1 = sx[ib]; q.y1 = sy[ib]; q.x2 = sx[ic]; q.y2 = sy[ic];
@@ -199,7 +172,7 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
                 const uint32_t slot = first + (uint32_t)__popcll(bigMask & ((1ull << lane) - 1ull));
                 if (big && slot < kQueueCapacity) {
                     a.queue[slot] = q;
-                    if constexpr (Vis) va.queuePayload[slot] = t < kVisTriangles ? (1ull << 32) | (va.slotBits | v << 7 | t) : 0ull;
+                    if constexpr (Vis) va.queuePayload[slot] = t < kVisTriangles ? (1ull << 32) | packVisibility(va.slotBits, v, t) : 0ull;
                     // its index goes to every coarse bin the box touches
                     const uint32_t cx0 = (q.boxX & 0xFFFFu) >> kBinShift, cx1 = (q.boxX >> 16) >> kBinShift;
                     const uint32_t cy0 = (q.boxY & 0xFFFFu) >> kBinShift, cy1 = (q.boxY >> 16) >> kBinShift;
@@ -224,20 +197,15 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
                 for (unsigned long long mrem = smallMask; mrem; mrem &= mrem - 1ull) {
                     const BigTriangle c = st[__builtin_ctzll(mrem)];
                     const uint32_t bx0 = c.boxX & 0xFFFFu, by0 = c.boxY & 0xFFFFu;
-                    if constexpr (Vis) {
-                        const uint32_t tri = tb + (uint32_t)__builtin_ctzll(mrem);
-                        const bool texel = tri < kVisTriangles;
-                        const unsigned long long payload = va.slotBits | v << 7 | tri;
-                        unsigned long long* vis = va.vis;
-                        coverBox(c.x0, c.y0, c.d0, c.x1, c.y1, c.d1, c.x2, c.y2, c.d2, c.sgn, bx0, by0, (c.boxX >> 16) - bx0 + 1u, (c.boxY >> 16) - by0 + 1u, lane, 64u,
-                                 [depth, vis, W, texel, payload](uint32_t px, uint32_t py, uint32_t bits) {
-                                     const uint64_t i = (uint64_t)py * W + px;
-                                     atomicMax(&depth[i], bits);
-                                     if (texel) atomicMax(&vis[i], (unsigned long long)bits << 32 | payload); });
-                    } else {
-                        coverBox(c.x0, c.y0, c.d0, c.x1, c.y1, c.d1, c.x2, c.y2, c.d2, c.sgn, bx0, by0, (c.boxX >> 16) - bx0 + 1u, (c.boxY >> 16) - by0 + 1u, lane, 64u,
-                                 [depth, W](uint32_t px, uint32_t py, uint32_t bits) { atomicMax(&depth[(uint64_t)py * W + px], bits); });
-                    }
+                    const uint32_t tri = tb + (uint32_t)__builtin_ctzll(mrem);
+                    const bool texel = tri < kVisTriangles;
+                    const unsigned long long payload = packVisibility(va.slotBits, v, tri);
+                    unsigned long long* vis = va.vis;
+                    coverBox(c.x0, c.y0, c.d0, c.x1, c.y1, c.d1, c.x2, c.y2, c.d2, c.sgn, bx0, by0, (c.boxX >> 16) - bx0 + 1u, (c.boxY >> 16) - by0 + 1u, lane, 64u,
+                             [=](uint32_t px, uint32_t py, uint32_t bits) {
+                                 const uint64_t i = (uint64_t)py * W + px;
+                                 atomicMax(&depth[i], bits);
+                                 if constexpr (Vis) if (texel) atomicMax(&vis[i], (unsigned long long)bits << 32 | payload); });
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                       // st is rewritten by the next 64 triangles
                 __builtin_amdgcn_wave_barrier();
@@ -247,6 +215,7 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                           // the LDS slice is reused by the next meshlet
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        });                                                                              // withMeshlet: an entry out of bounds skips all of the above
     }
 }
 
@@ -332,19 +301,15 @@ __device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& 
                 if (cm::max_(cm::max_(q.d0, q.d1), q.d2) * 0x1.00001p+0f < tileFar) continue;     // NaN or inf: never skipped
                 const uint32_t bx0 = max(q.boxX & 0xFFFFu, tx0), bx1 = min(q.boxX >> 16, tx1);
                 const uint32_t by0 = max(q.boxY & 0xFFFFu, ty0), by1 = min(q.boxY >> 16, ty1);
-                if constexpr (Vis) {
-                    const unsigned long long qp = va.queuePayload[s_list[k]];
-                    const bool texel = (qp >> 32) != 0ull;
-                    const unsigned long long payload = qp & 0xFFFFFFFFull;
-                    coverBox(q.x0, q.y0, q.d0, q.x1, q.y1, q.d1, q.x2, q.y2, q.d2, q.sgn, bx0, by0, bx1 - bx0 + 1u, by1 - by0 + 1u, tid, kBlock,
-                             [tx0, ty0, texel, payload](uint32_t px, uint32_t py, uint32_t bits) {
-                                 const uint32_t i = (py - ty0) * kTile + (px - tx0);
-                                 atomicMax(&s_depth[i], bits);
-                                 if (texel) atomicMax(&s_vis[i], (unsigned long long)bits << 32 | payload); });
-                } else {
-                    coverBox(q.x0, q.y0, q.d0, q.x1, q.y1, q.d1, q.x2, q.y2, q.d2, q.sgn, bx0, by0, bx1 - bx0 + 1u, by1 - by0 + 1u, tid, kBlock,
-                             [tx0, ty0](uint32_t px, uint32_t py, uint32_t bits) { atomicMax(&s_depth[(py - ty0) * kTile + (px - tx0)], bits); });
-                }
+                unsigned long long qp = 0ull;                                              // (1 << 32 | payload), or 0 = no texel
+                if constexpr (Vis) qp = va.queuePayload[s_list[k]];
+                const bool texel = (qp >> 32) != 0ull;
+                const unsigned long long payload = qp & 0xFFFFFFFFull;
+                coverBox(q.x0, q.y0, q.d0, q.x1, q.y1, q.d1, q.x2, q.y2, q.d2, q.sgn, bx0, by0, bx1 - bx0 + 1u, by1 - by0 + 1u, tid, kBlock,
+                         [=](uint32_t px, uint32_t py, uint32_t bits) {
+                             const uint32_t i = (py - ty0) * kTile + (px - tx0);
+                             atomicMax(&s_depth[i], bits);
+                             if constexpr (Vis) if (texel) atomicMax(&s_vis[i], (unsigned long long)bits << 32 | payload); });
             }
             __syncthreads();
         }
@@ -370,38 +335,25 @@ __global__ __launch_bounds__(kBlock) void rasterVisibilityTilesKernel(RasterArgs
 template <bool Vis>
 int recordRaster(trhip::DispatchCtx& ctx)
 {
-    // Binding set of BasePassRenderers.cpp:463-479 (t0 instances, t1 vertices, t2 mesh data, t4 meshlets, t5 meshlet
-    // vertex ids, t6 meshlet triangles, t7 amplification records) + the outputs of the cull half: t9 visible list,
-    // indirect args = its draw args; u0 = the depth buffer (R32_FLOAT).
+    // Binding set of BasePassRenderers.cpp:463-479 (the geometry of mesh_stage.hip.h, t7 amplification records) + the
+    // outputs of the cull half: t9 visible list, indirect args = its draw args; u0 = the depth buffer (R32_FLOAT).
     const BasePassConstants* k = (const BasePassConstants*)ctx.constants(0, sizeof(BasePassConstants));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (BasePassConstants, 256 bytes) missing", ctx.shaderName);
-    trhip_buffer_t* instances = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 0);
-    trhip_buffer_t* vertices = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 1);
-    trhip_buffer_t* meshData = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 2);
-    trhip_buffer_t* meshlets = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 4);
-    trhip_buffer_t* vids = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 5);
-    trhip_buffer_t* tris = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 6);
+    RasterArgs a;
+    memset(&a, 0, sizeof a);
+    a.k = *k;
+    if (const int rc = bindGeometry(ctx, a.geo)) return rc;
     trhip_buffer_t* records = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 7);
     trhip_buffer_t* list = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 9);
     uint32_t mip = 0;
     trhip_texture_t* depth = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 0, &mip);
-    TRHIP_REQUIRE(instances && vertices && meshData && meshlets && vids && tris && records && list,
-                  "%s: needs SRVs t0 (instances), t1 (vertices), t2 (mesh data), t4 (meshlets), t5 (meshlet vertex ids), t6 (meshlet triangles), t7 (records), t9 (visible list)", ctx.shaderName);
+    TRHIP_REQUIRE(records && list, "%s: needs SRVs t7 (records), t9 (visible list)", ctx.shaderName);
     TRHIP_REQUIRE(depth && mip == 0 && depth->format == TRHIP_FORMAT_R32_FLOAT, "%s: needs Texture_UAV u0 = the R32_FLOAT depth buffer, mip 0", ctx.shaderName);
     TRHIP_REQUIRE(ctx.indirect && ctx.argsBuffer->byteSize - ctx.argsOffset >= 12, "%s: dispatched indirectly on the visible list's draw args", ctx.shaderName);
     TRHIP_REQUIRE(k->m_OutputResolution.x == depth->width && k->m_OutputResolution.y == depth->height,
                   "%s: m_OutputResolution %ux%u does not match the depth buffer %ux%u", ctx.shaderName, k->m_OutputResolution.x, k->m_OutputResolution.y, depth->width, depth->height);
-    RasterArgs a;
-    memset(&a, 0, sizeof a);
-    a.k = *k;
-    a.instances = (const BasePassInstanceConstants*)instances->ptr; a.numInstances = (uint32_t)std::min<uint64_t>(instances->byteSize / sizeof(BasePassInstanceConstants), 0xFFFFFFFFull);
-    a.meshData = (const MeshData*)meshData->ptr; a.numMeshes = (uint32_t)std::min<uint64_t>(meshData->byteSize / sizeof(MeshData), 0xFFFFFFFFull);
-    a.meshlets = (const MeshletData*)meshlets->ptr; a.numMeshlets = meshlets->byteSize / sizeof(MeshletData);
-    a.vertices = (const char*)vertices->ptr; a.numVertices = vertices->byteSize / 20u;
-    a.vertexIds = (const uint32_t*)vids->ptr; a.numVertexIds = vids->byteSize / 4;
-    a.triangles = (const uint32_t*)tris->ptr; a.numTriangles = tris->byteSize / 4;
-    a.records = (const MeshletAmplificationData*)records->ptr; a.recordCapacity = (uint32_t)std::min<uint64_t>(records->byteSize / sizeof(MeshletAmplificationData), 0xFFFFFFFFull);
-    a.visibleList = (const uint32_t*)list->ptr; a.listCapacity = (uint32_t)std::min<uint64_t>(list->byteSize / 4, 0xFFFFFFFFull);
+    a.records = (const MeshletAmplificationData*)records->ptr; a.recordCapacity = elements32(records, sizeof(MeshletAmplificationData));
+    a.visibleList = (const uint32_t*)list->ptr; a.listCapacity = elements32(list, 4);
     a.drawArgs = (const uint32_t*)((const char*)ctx.argsBuffer->ptr + ctx.argsOffset);
     a.depth = (uint32_t*)depth->ptr;
     a.width = depth->width; a.height = depth->height;
@@ -423,7 +375,7 @@ int recordRaster(trhip::DispatchCtx& ctx)
         TRHIP_REQUIRE(list->byteSize / 4 <= kVisListCapacity, "%s: visible list of %llu entries: the visibility payload holds list positions below 2^23",
                       ctx.shaderName, (unsigned long long)(list->byteSize / 4));
         va.vis = (unsigned long long*)vis->ptr;
-        va.slotBits = slot << 30;
+        va.slotBits = visSlotBits(slot);
     }
     // queue of the triangles that are large on screen: scratch of this command; its counter is zeroed by the recording's
     // first clear launch

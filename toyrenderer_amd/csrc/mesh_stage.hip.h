@@ -1,0 +1,115 @@
+// mesh_stage.hip.h -- the one statement of the base pass's mesh stage, shared by the rasters (k_raster.hip) and the
+// resolve from the visibility buffer (visibility_resolve.hip.h): which buffers hold the geometry and how a record binds
+// them, how a visible-list entry leads to its meshlet, how a vertex gets to the screen, what the edge function is, and
+// what a visibility texel means.  GBufferMotion and GBufferA are bit-exact because the resolve recomputes the winning
+// triangle with the raster's operations; they are the raster's operations because both call these.
+// Restated independently, on purpose, in oracle/tr_oracle.c, tests/visibility_ref.c and tests/gbuffer_ref.c.
+#pragma once
+
+#include "cull_math.hip.h"
+#include "trhip_internal.h"
+
+namespace mesh
+{
+
+using namespace interop;
+
+// ---- geometry: t0 instances, t1 vertices, t2 mesh data, t4 meshlets, t5 meshlet vertex ids, t6 meshlet triangles -----
+// (BasePassRenderers.cpp:463-479).  Nested right after the constants in the kernels' argument blocks.
+struct Geometry
+{
+    const BasePassInstanceConstants* instances; uint32_t numInstances;
+    const MeshData* meshData; uint32_t numMeshes;
+    const MeshletData* meshlets; uint64_t numMeshlets;
+    const char* vertices; uint64_t numVertices;                 // RawVertexFormat
+    const uint32_t* vertexIds; uint64_t numVertexIds;
+    const uint32_t* triangles; uint64_t numTriangles;
+};
+
+// Elements of `stride` bytes in a buffer, saturated to 32 bits.
+inline uint32_t elements32(const trhip_buffer_t* b, size_t stride) { return (uint32_t)std::min<uint64_t>(b->byteSize / stride, 0xFFFFFFFFull); }
+
+inline int bindGeometry(const trhip::DispatchCtx& ctx, Geometry& g)
+{
+    trhip_buffer_t* instances = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 0);
+    trhip_buffer_t* vertices = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 1);
+    trhip_buffer_t* meshData = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 2);
+    trhip_buffer_t* meshlets = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 4);
+    trhip_buffer_t* vids = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 5);
+    trhip_buffer_t* tris = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 6);
+    TRHIP_REQUIRE(instances && vertices && meshData && meshlets && vids && tris,
+                  "%s: needs SRVs t0 (instances), t1 (vertices), t2 (mesh data), t4 (meshlets), t5 (meshlet vertex ids), t6 (meshlet triangles)", ctx.shaderName);
+    g.instances = (const BasePassInstanceConstants*)instances->ptr; g.numInstances = elements32(instances, sizeof(BasePassInstanceConstants));
+    g.meshData = (const MeshData*)meshData->ptr; g.numMeshes = elements32(meshData, sizeof(MeshData));
+    g.meshlets = (const MeshletData*)meshlets->ptr; g.numMeshlets = meshlets->byteSize / sizeof(MeshletData);
+    g.vertices = (const char*)vertices->ptr; g.numVertices = vertices->byteSize / sizeof(RawVertexFormat);
+    g.vertexIds = (const uint32_t*)vids->ptr; g.numVertexIds = vids->byteSize / 4;
+    g.triangles = (const uint32_t*)tris->ptr; g.numTriangles = tris->byteSize / 4;
+    return TRHIP_OK;
+}
+
+// ---- visible-list entry -> record -> instance -> LOD -> meshlet (basepass.hlsl:138-145) ----------------------------
+struct Meshlet
+{
+    MeshletAmplificationData rec;
+    const BasePassInstanceConstants* inst;
+    uint32_t lane;                                               // the meshlet's index in its group of 32
+    uint32_t vertexIdsAt, trianglesAt;                           // first element in Geometry::vertexIds / ::triangles
+    uint32_t nv, nt;                                             // nv clamped to kMaxMeshletVertices
+};
+
+// Runs body(meshlet) unless an index on the way is out of bounds.  [vertexIdsAt, + nv) and [trianglesAt, + nt) are then in
+// bounds; the vertex ids themselves are not checked (vertexAt's caller does).  A continuation, because a function that
+// returns false and fills a struct costs the rasters registers or time (profiles/mesh_stage/README.md).
+template <typename Body>
+__device__ __forceinline__ void withMeshlet(uint32_t entry, const MeshletAmplificationData* records, uint32_t recordCapacity, const Geometry& g, Body body)
+{
+    const uint32_t group = entry >> 5, m = entry & 31u;
+    if (group >= recordCapacity) return;
+    const MeshletAmplificationData rec = records[group];
+    if (rec.m_InstanceConstIdx >= g.numInstances) return;
+    const BasePassInstanceConstants& inst = g.instances[rec.m_InstanceConstIdx];
+    if (inst.m_MeshDataIdx >= g.numMeshes) return;
+    const uint32_t lodIdx = rec.m_MeshLOD < kMaxNumMeshLODs ? rec.m_MeshLOD : kMaxNumMeshLODs - 1u;
+    const MeshLODData lod = g.meshData[inst.m_MeshDataIdx].m_MeshLODDatas[lodIdx];
+    const uint64_t mi = (uint64_t)lod.m_MeshletDataBufferIdx + rec.m_MeshletGroupOffset + m;
+    if (mi >= g.numMeshlets) return;
+    const MeshletData ml = g.meshlets[mi];
+    uint32_t nv = ml.m_VertexAndTriangleCount & 0xFFu, nt = (ml.m_VertexAndTriangleCount >> 8) & 0xFFu;
+    nv = nv < kMaxMeshletVertices ? nv : kMaxMeshletVertices;
+    if ((uint64_t)ml.m_MeshletVertexIDsBufferIdx + nv > g.numVertexIds || (uint64_t)ml.m_MeshletIndexIDsBufferIdx + nt > g.numTriangles) return;
+    body(Meshlet{ rec, &inst, m, ml.m_MeshletVertexIDsBufferIdx, ml.m_MeshletIndexIDsBufferIdx, nv, nt });
+}
+
+// vid < g.numVertices
+__device__ __forceinline__ const RawVertexFormat& vertexAt(const Geometry& g, uint32_t vid) { return *reinterpret_cast<const RawVertexFormat*>(g.vertices + (uint64_t)vid * sizeof(RawVertexFormat)); }
+
+// ---- object space -> screen (basepass.hlsl:149-158; the operations of orc_raster_depth, one for one) ----------------
+struct ScreenVertex { float sx, sy, depth, w; };
+
+__device__ __forceinline__ ScreenVertex toScreen(cm::F3 position, const cm::M43& world, const cm::M43& clipXYZ, const Matrix& worldToClip, float halfW, float halfH)
+{
+    const cm::F3 wp = cm::mulPoint(position, world);
+    const cm::F3 c = cm::mulPoint(wp, clipXYZ);
+    const float w = cm::fma_(wp.z, worldToClip.m[2][3], cm::fma_(wp.y, worldToClip.m[1][3], wp.x * worldToClip.m[0][3])) + worldToClip.m[3][3];
+    return { cm::fma_(c.x / w, halfW, halfW), cm::fma_(-(c.y / w), halfH, halfH), c.z / w, w };
+}
+
+__device__ __forceinline__ float edgeFn(float ax, float ay, float bx, float by, float px, float py) { return cm::fma_(bx - ax, py - ay, -((by - ay) * (px - ax))); }
+
+// ---- visibility texel: (depthBits << 32) | slot << 30 | listPosition << 7 | triangle ---------------------------------
+constexpr uint32_t kVisTriangleBits = 7, kVisListBits = 23;
+constexpr uint32_t kVisTriangles = 1u << kVisTriangleBits;       // triangle indices with a visibility texel
+constexpr uint32_t kVisListCapacity = 1u << kVisListBits;        // list positions
+static_assert(kVisTriangleBits + kVisListBits == 30, "two bits are left for the pass slot");
+
+struct VisTexel { uint32_t slot, listPosition, triangle; };
+
+__host__ __device__ __forceinline__ uint32_t visSlotBits(uint32_t slot) { return slot << (kVisTriangleBits + kVisListBits); }
+__device__ __forceinline__ uint32_t packVisibility(uint32_t slotBits, uint32_t listPosition, uint32_t triangle) { return slotBits | listPosition << kVisTriangleBits | triangle; }
+__device__ __forceinline__ VisTexel unpackVisibility(uint32_t payload)
+{
+    return { payload >> (kVisTriangleBits + kVisListBits), (payload >> kVisTriangleBits) & (kVisListCapacity - 1u), payload & (kVisTriangles - 1u) };
+}
+
+} // namespace mesh

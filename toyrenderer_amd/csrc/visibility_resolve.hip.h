@@ -1,8 +1,9 @@
 // visibility_resolve.hip.h -- the one resolve from the visibility buffer, shared by "basepass_PS_Main_motion"
 // (k_motion.hip: the motion target alone) and "basepass_PS_Main_GBuffer" (k_gbuffer.hip: GBufferA and the motion
 // target, the two render targets of the reference's PS_Main_GBuffer, basepass.hlsl:231-253).  The texel decode, the
-// bounds checks, the raster's vertex arithmetic, the edge functions and the motion words exist once, here; the G-buffer
-// half is compiled in by the template argument only.
+// fetch chain with its bounds checks, the vertex arithmetic and the edge function are the raster's own (mesh_stage.hip.h);
+// the checks only a resolve needs, the interpolation and the motion words exist once, here; the G-buffer half is compiled
+// in by the template argument only.
 //
 // CONVENTION of the G-buffer half (parity unpinned; restated in tests/gbuffer_ref.c).  With q_i = e_i / w_i
 // and s = (q0 + q1) + q2 of the motion resolve:
@@ -20,41 +21,29 @@
 //             12 (float)m_MeshLOD / 255.0f, else 0.
 #pragma once
 
-#include "cull_math.hip.h"
-#include "trhip_internal.h"
+#include "mesh_stage.hip.h"
 
 namespace vres
 {
 
-using namespace interop;
+using namespace mesh;
 
 constexpr uint32_t kTileW = 16, kTileH = 16;   // one workgroup per 16x16 pixels: a wave covers 16x4 neighbouring pixels
 constexpr uint32_t kBlock = kTileW * kTileH;
 constexpr uint32_t kGroupSide = 8;              // the reference entry's [numthreads(8, 8, 1)]: group counts cover the screen
-constexpr uint32_t kMaterialStride = 124;       // sizeof(MaterialData); the first 32 bytes are read
 
 struct ResolveArgs
 {
     BasePassConstants k;
-    const BasePassInstanceConstants* instances; uint32_t numInstances;
-    const MeshData* meshData; uint32_t numMeshes;
-    const MeshletData* meshlets; uint64_t numMeshlets;
-    const char* vertices; uint64_t numVertices;                 // RawVertexFormat, 20-byte stride
-    const uint32_t* vertexIds; uint64_t numVertexIds;
-    const uint32_t* triangles; uint64_t numTriangles;
+    Geometry geo;
     const MeshletAmplificationData* records[4]; uint32_t recordCapacity[4];
     const uint32_t* lists[4]; uint32_t listCapacity[4];
     const unsigned long long* vis;                               // RG32_UINT as u64
     uint32_t* motion;                                            // RG16_FLOAT: x in the low half, y in the high half
-    const char* materials; uint32_t numMaterials;                // MaterialData, 124-byte stride (G-buffer only)
+    const char* materials; uint32_t numMaterials;                // MaterialData, the first 32 bytes are read (G-buffer only)
     uint4* gbufferA;                                             // RGBA32_UINT (G-buffer only)
     uint32_t width, height;
 };
-
-__device__ __forceinline__ float edgeFn(float ax, float ay, float bx, float by, float px, float py)
-{
-    return cm::fma_(bx - ax, py - ay, -((by - ay) * (px - ax)));
-}
 
 __device__ __forceinline__ uint32_t toHalfBits(float f)
 {
@@ -132,90 +121,74 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GBUFFER 
     const uint64_t i = (uint64_t)py * a.width + px;
     const unsigned long long texel = a.vis[i];
     if (!texel) return;
-    const uint32_t payload = (uint32_t)texel;
-    const uint32_t slot = payload >> 30, v = (payload >> 7) & 0x7FFFFFu, t = payload & 127u;
-    if (v >= a.listCapacity[slot]) return;
-    const uint32_t e = a.lists[slot][v], g = e >> 5, m = e & 31u;
-    if (g >= a.recordCapacity[slot]) return;
-    const MeshletAmplificationData rec = a.records[slot][g];
-    if (rec.m_InstanceConstIdx >= a.numInstances) return;
-    const BasePassInstanceConstants& inst = a.instances[rec.m_InstanceConstIdx];
-    if (inst.m_MeshDataIdx >= a.numMeshes) return;
-    if (GBUFFER && inst.m_MaterialDataIdx >= a.numMaterials) return;
-    const uint32_t lodIdx = rec.m_MeshLOD < kMaxNumMeshLODs ? rec.m_MeshLOD : kMaxNumMeshLODs - 1u;
-    const MeshLODData lod = a.meshData[inst.m_MeshDataIdx].m_MeshLODDatas[lodIdx];
-    const uint64_t mi = (uint64_t)lod.m_MeshletDataBufferIdx + rec.m_MeshletGroupOffset + m;
-    if (mi >= a.numMeshlets) return;
-    const MeshletData ml = a.meshlets[mi];
-    uint32_t nv = ml.m_VertexAndTriangleCount & 0xFFu;
-    const uint32_t nt = (ml.m_VertexAndTriangleCount >> 8) & 0xFFu;
-    nv = nv < 64u ? nv : 64u;
-    if (t >= nt || (uint64_t)ml.m_MeshletIndexIDsBufferIdx + nt > a.numTriangles || (uint64_t)ml.m_MeshletVertexIDsBufferIdx + nv > a.numVertexIds) return;
-    const uint32_t packed = a.triangles[ml.m_MeshletIndexIDsBufferIdx + t];
-    const uint32_t idx[3] = { packed & 0xFFu, (packed >> 8) & 0xFFu, (packed >> 16) & 0xFFu };
-    if (idx[0] >= nv || idx[1] >= nv || idx[2] >= nv) return;
-    const cm::M43 Wm = cm::loadM43(inst.m_WorldMatrix), Pm = cm::loadM43(inst.m_PrevWorldMatrix);
-    const cm::M43 clipXYZ = cm::loadM43(a.k.m_WorldToClip);
-    float sx[3], sy[3], w[3];
-    cm::F3 prev[3];
-    uint32_t packedNormal[3];
-    bool ok = true;
-    for (int j = 0; j < 3; ++j) {                                                   // the raster's vertex arithmetic
-        const uint32_t vid = a.vertexIds[ml.m_MeshletVertexIDsBufferIdx + idx[j]];
-        if (vid >= a.numVertices) { ok = false; break; }
-        const float* p = reinterpret_cast<const float*>(a.vertices + (uint64_t)vid * 20u);
-        const cm::F3 pos = { p[0], p[1], p[2] };
-        if (GBUFFER) packedNormal[j] = reinterpret_cast<const uint32_t*>(p)[3];     // RawVertexFormat::m_PackedNormal, same record
-        const cm::F3 wp = cm::mulPoint(pos, Wm);
-        const cm::F3 c = cm::mulPoint(wp, clipXYZ);
-        w[j] = cm::fma_(wp.z, a.k.m_WorldToClip.m[2][3], cm::fma_(wp.y, a.k.m_WorldToClip.m[1][3], wp.x * a.k.m_WorldToClip.m[0][3])) + a.k.m_WorldToClip.m[3][3];
-        sx[j] = cm::fma_(c.x / w[j], halfW, halfW);
-        sy[j] = cm::fma_(-(c.y / w[j]), halfH, halfH);
-        prev[j] = cm::mulPoint(pos, Pm);
-    }
-    if (!ok) return;
-    const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
-    const float area = edgeFn(sx[0], sy[0], sx[1], sy[1], sx[2], sy[2]);
-    const float sgn = area < 0.0f ? -1.0f : 1.0f;
-    const float e0 = sgn * edgeFn(sx[1], sy[1], sx[2], sy[2], cx, cy), e1 = sgn * edgeFn(sx[2], sy[2], sx[0], sy[0], cx, cy), e2 = sgn * edgeFn(sx[0], sy[0], sx[1], sy[1], cx, cy);
-    const float q0 = e0 / w[0], q1 = e1 / w[1], q2 = e2 / w[2];
-    const float s = (q0 + q1) + q2;
-    const float P[3] = { cm::fma_(q2, prev[2].x, cm::fma_(q1, prev[1].x, q0 * prev[0].x)) / s,
-                         cm::fma_(q2, prev[2].y, cm::fma_(q1, prev[1].y, q0 * prev[0].y)) / s,
-                         cm::fma_(q2, prev[2].z, cm::fma_(q1, prev[1].z, q0 * prev[0].z)) / s };
-    float clip[4];
-    for (int j = 0; j < 4; ++j)
-        clip[j] = cm::fma_(P[2], a.k.m_PrevWorldToClip.m[2][j], cm::fma_(P[1], a.k.m_PrevWorldToClip.m[1][j], P[0] * a.k.m_PrevWorldToClip.m[0][j])) + a.k.m_PrevWorldToClip.m[3][j];
-    float mx = 0.0f, my = 0.0f;
-    if (clip[3] > 0.0f) {                                                            // basepass.hlsl:230-237
-        const float ux = (clip[0] / clip[3]) * 0.5f + 0.5f, uy = (clip[1] / clip[3]) * -0.5f + 0.5f;
-        mx = ux * (float)a.width - cx;
-        my = uy * (float)a.height - cy;
-    }
-    a.motion[i] = toHalfBits(mx) | toHalfBits(my) << 16;                            // SV_Target1
-    if (GBUFFER) {                                                                   // SV_Target0
-        const cm::F3 adj0 = cm::cross3(Wm.r1, Wm.r2), adj1 = cm::cross3(Wm.r2, Wm.r0), adj2 = cm::cross3(Wm.r0, Wm.r1);   // MakeAdjugateMatrix
-        cm::F3 N[3];
-        for (int j = 0; j < 3; ++j) {                                                // basepass.hlsl:162-167
-            const cm::F3 n = cm::mulVec(unpackNormal(packedNormal[j]), adj0, adj1, adj2);
-            const float len = cm::sqrt_(cm::dot3(n, n));
-            N[j] = { n.x / len, n.y / len, n.z / len };
+    const VisTexel id = unpackVisibility((uint32_t)texel);
+    if (id.listPosition >= a.listCapacity[id.slot]) return;
+    withMeshlet(a.lists[id.slot][id.listPosition], a.records[id.slot], a.recordCapacity[id.slot], a.geo, [&](const Meshlet& ml) {   // a return below leaves the pixel as it is
+        const BasePassInstanceConstants& inst = *ml.inst;
+        if ((GBUFFER && inst.m_MaterialDataIdx >= a.numMaterials) || id.triangle >= ml.nt) return;
+        const uint32_t packed = a.geo.triangles[ml.trianglesAt + id.triangle];
+        const uint32_t idx[3] = { packed & 0xFFu, (packed >> 8) & 0xFFu, (packed >> 16) & 0xFFu };
+        if (idx[0] >= ml.nv || idx[1] >= ml.nv || idx[2] >= ml.nv) return;
+        const cm::M43 Wm = cm::loadM43(inst.m_WorldMatrix), Pm = cm::loadM43(inst.m_PrevWorldMatrix);
+        const cm::M43 clipXYZ = cm::loadM43(a.k.m_WorldToClip);
+        float sx[3], sy[3], w[3];
+        cm::F3 prev[3];
+        uint32_t packedNormal[3];
+        bool ok = true;
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t vid = a.geo.vertexIds[ml.vertexIdsAt + idx[j]];
+            if (vid >= a.geo.numVertices) { ok = false; break; }
+            const RawVertexFormat& vtx = vertexAt(a.geo, vid);
+            const cm::F3 pos = { vtx.m_Position[0], vtx.m_Position[1], vtx.m_Position[2] };
+            if (GBUFFER) packedNormal[j] = vtx.m_PackedNormal;
+            const ScreenVertex sv = toScreen(pos, Wm, clipXYZ, a.k.m_WorldToClip, halfW, halfH);
+            w[j] = sv.w; sx[j] = sv.sx; sy[j] = sv.sy;
+            prev[j] = cm::mulPoint(pos, Pm);
         }
-        const cm::F3 normal = { cm::fma_(q2, N[2].x, cm::fma_(q1, N[1].x, q0 * N[0].x)) / s,
-                                cm::fma_(q2, N[2].y, cm::fma_(q1, N[1].y, q0 * N[0].y)) / s,
-                                cm::fma_(q2, N[2].z, cm::fma_(q1, N[1].z, q0 * N[0].z)) / s };
-        float debugValue = 0.0f;                                                     // basepass.hlsl:238-249
-        if (a.k.m_DebugMode == kDeferredLightingDebugMode_ColorizeInstances) debugValue = quickRandomFloat(rec.m_InstanceConstIdx);
-        else if (a.k.m_DebugMode == kDeferredLightingDebugMode_ColorizeMeshlets) debugValue = quickRandomFloat(rec.m_MeshletGroupOffset + m);
-        else if (a.k.m_DebugMode == kDeferredLightingDebugMode_MeshLOD) debugValue = (float)rec.m_MeshLOD / 255.0f;
-        const float* mat = reinterpret_cast<const float*>(a.materials + (uint64_t)inst.m_MaterialDataIdx * kMaterialStride);   // albedo rgb(a), emissive rgb
-        uint4 out;
-        out.x = packRGBA8(mat[0], mat[1], mat[2], debugValue);
-        out.y = packOctUnorm2x16(normal);
-        out.z = packR9G9B9E5(mat[4], mat[5], mat[6]);
-        out.w = packRGBA8(1.0f, 0.0f, 0.0f, 0.0f);                                   // roughness 1, metallic 0 (Q13)
-        a.gbufferA[i] = out;                                                         // one 16-byte store per lane
-    }
+        if (!ok) return;
+        const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
+        const float area = edgeFn(sx[0], sy[0], sx[1], sy[1], sx[2], sy[2]);
+        const float sgn = area < 0.0f ? -1.0f : 1.0f;
+        const float e0 = sgn * edgeFn(sx[1], sy[1], sx[2], sy[2], cx, cy), e1 = sgn * edgeFn(sx[2], sy[2], sx[0], sy[0], cx, cy), e2 = sgn * edgeFn(sx[0], sy[0], sx[1], sy[1], cx, cy);
+        const float q0 = e0 / w[0], q1 = e1 / w[1], q2 = e2 / w[2];
+        const float s = (q0 + q1) + q2;
+        const float P[3] = { cm::fma_(q2, prev[2].x, cm::fma_(q1, prev[1].x, q0 * prev[0].x)) / s,
+                             cm::fma_(q2, prev[2].y, cm::fma_(q1, prev[1].y, q0 * prev[0].y)) / s,
+                             cm::fma_(q2, prev[2].z, cm::fma_(q1, prev[1].z, q0 * prev[0].z)) / s };
+        float clip[4];
+        for (int j = 0; j < 4; ++j)
+            clip[j] = cm::fma_(P[2], a.k.m_PrevWorldToClip.m[2][j], cm::fma_(P[1], a.k.m_PrevWorldToClip.m[1][j], P[0] * a.k.m_PrevWorldToClip.m[0][j])) + a.k.m_PrevWorldToClip.m[3][j];
+        float mx = 0.0f, my = 0.0f;
+        if (clip[3] > 0.0f) {                                                            // basepass.hlsl:230-237
+            const float ux = (clip[0] / clip[3]) * 0.5f + 0.5f, uy = (clip[1] / clip[3]) * -0.5f + 0.5f;
+            mx = ux * (float)a.width - cx;
+            my = uy * (float)a.height - cy;
+        }
+        a.motion[i] = toHalfBits(mx) | toHalfBits(my) << 16;                            // SV_Target1
+        if (GBUFFER) {                                                                   // SV_Target0
+            const cm::F3 adj0 = cm::cross3(Wm.r1, Wm.r2), adj1 = cm::cross3(Wm.r2, Wm.r0), adj2 = cm::cross3(Wm.r0, Wm.r1);   // MakeAdjugateMatrix
+            cm::F3 N[3];
+            for (int j = 0; j < 3; ++j) {                                                // basepass.hlsl:162-167
+                const cm::F3 n = cm::mulVec(unpackNormal(packedNormal[j]), adj0, adj1, adj2);
+                const float len = cm::sqrt_(cm::dot3(n, n));
+                N[j] = { n.x / len, n.y / len, n.z / len };
+            }
+            const cm::F3 normal = { cm::fma_(q2, N[2].x, cm::fma_(q1, N[1].x, q0 * N[0].x)) / s,
+                                    cm::fma_(q2, N[2].y, cm::fma_(q1, N[1].y, q0 * N[0].y)) / s,
+                                    cm::fma_(q2, N[2].z, cm::fma_(q1, N[1].z, q0 * N[0].z)) / s };
+            float debugValue = 0.0f;                                                     // basepass.hlsl:238-249
+            if (a.k.m_DebugMode == kDeferredLightingDebugMode_ColorizeInstances) debugValue = quickRandomFloat(ml.rec.m_InstanceConstIdx);
+            else if (a.k.m_DebugMode == kDeferredLightingDebugMode_ColorizeMeshlets) debugValue = quickRandomFloat(ml.rec.m_MeshletGroupOffset + ml.lane);
+            else if (a.k.m_DebugMode == kDeferredLightingDebugMode_MeshLOD) debugValue = (float)ml.rec.m_MeshLOD / 255.0f;
+            const float* mat = reinterpret_cast<const float*>(a.materials + (uint64_t)inst.m_MaterialDataIdx * sizeof(MaterialData));   // albedo rgb(a), emissive rgb
+            uint4 out;
+            out.x = packRGBA8(mat[0], mat[1], mat[2], debugValue);
+            out.y = packOctUnorm2x16(normal);
+            out.z = packR9G9B9E5(mat[4], mat[5], mat[6]);
+            out.w = packRGBA8(1.0f, 0.0f, 0.0f, 0.0f);                                   // roughness 1, metallic 0 (Q13)
+            a.gbufferA[i] = out;                                                         // one 16-byte store per lane
+        }
+    });                                                                              // withMeshlet: nothing may follow, a chain out of bounds ends the pixel too
 }
 
 // Records the resolve: validates the bindings and emits one direct dispatch.  GBUFFER: + t3 materials, u0 = GBufferA
@@ -225,14 +198,10 @@ int recordResolve(trhip::DispatchCtx& ctx)
 {
     const BasePassConstants* k = (const BasePassConstants*)ctx.constants(0, sizeof(BasePassConstants));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (BasePassConstants, 256 bytes) missing", ctx.shaderName);
-    trhip_buffer_t* instances = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 0);
-    trhip_buffer_t* vertices = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 1);
-    trhip_buffer_t* meshData = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 2);
-    trhip_buffer_t* meshlets = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 4);
-    trhip_buffer_t* vids = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 5);
-    trhip_buffer_t* tris = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 6);
-    TRHIP_REQUIRE(instances && vertices && meshData && meshlets && vids && tris,
-                  "%s: needs SRVs t0 (instances), t1 (vertices), t2 (mesh data), t4 (meshlets), t5 (meshlet vertex ids), t6 (meshlet triangles)", ctx.shaderName);
+    ResolveArgs a;
+    memset(&a, 0, sizeof a);
+    a.k = *k;
+    if (const int rc = bindGeometry(ctx, a.geo)) return rc;
     trhip_buffer_t* records[4];
     trhip_buffer_t* lists[4];
     for (uint32_t s = 0; s < 4; ++s) {
@@ -260,26 +229,17 @@ int recordResolve(trhip::DispatchCtx& ctx)
     }
     TRHIP_REQUIRE(!ctx.indirect && (uint64_t)ctx.gx * kGroupSide >= W && (uint64_t)ctx.gy * kGroupSide >= H,
                   "%s: a direct dispatch of 8x8-pixel groups covering %ux%u", ctx.shaderName, W, H);
-    ResolveArgs a;
-    memset(&a, 0, sizeof a);
-    a.k = *k;
-    a.instances = (const BasePassInstanceConstants*)instances->ptr; a.numInstances = (uint32_t)std::min<uint64_t>(instances->byteSize / sizeof(BasePassInstanceConstants), 0xFFFFFFFFull);
-    a.meshData = (const MeshData*)meshData->ptr; a.numMeshes = (uint32_t)std::min<uint64_t>(meshData->byteSize / sizeof(MeshData), 0xFFFFFFFFull);
-    a.meshlets = (const MeshletData*)meshlets->ptr; a.numMeshlets = meshlets->byteSize / sizeof(MeshletData);
-    a.vertices = (const char*)vertices->ptr; a.numVertices = vertices->byteSize / 20u;
-    a.vertexIds = (const uint32_t*)vids->ptr; a.numVertexIds = vids->byteSize / 4;
-    a.triangles = (const uint32_t*)tris->ptr; a.numTriangles = tris->byteSize / 4;
     for (uint32_t s = 0; s < 4; ++s) {
         a.records[s] = (const MeshletAmplificationData*)records[s]->ptr;
-        a.recordCapacity[s] = (uint32_t)std::min<uint64_t>(records[s]->byteSize / sizeof(MeshletAmplificationData), 0xFFFFFFFFull);
+        a.recordCapacity[s] = elements32(records[s], sizeof(MeshletAmplificationData));
         a.lists[s] = (const uint32_t*)lists[s]->ptr;
-        a.listCapacity[s] = (uint32_t)std::min<uint64_t>(lists[s]->byteSize / 4, 0xFFFFFFFFull);
+        a.listCapacity[s] = elements32(lists[s], 4);
     }
     a.vis = (const unsigned long long*)vis->ptr;
     a.motion = (uint32_t*)motion->ptr;
     if (GBUFFER) {
         a.materials = (const char*)materials->ptr;
-        a.numMaterials = (uint32_t)std::min<uint64_t>(materials->byteSize / kMaterialStride, 0xFFFFFFFFull);
+        a.numMaterials = elements32(materials, sizeof(MaterialData));
         a.gbufferA = (uint4*)gbufferA->ptr;
     }
     a.width = W; a.height = H;

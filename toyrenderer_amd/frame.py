@@ -222,6 +222,12 @@ class FrameDriver:
             return False
         return True
 
+    def _mesh_stage_bindings(self, cb):
+        """What the raster and the resolve both read (csrc/mesh_stage.hip.h): b0 and the geometry at t0, t1, t2, t4, t5, t6."""
+        sc = self.scene
+        return [CB(0, cb), SRV(0, sc.instances), SRV(1, sc.vertices), SRV(2, sc.meshData), SRV(4, sc.meshlets), SRV(5, sc.meshletVertexIds),
+                SRV(6, sc.meshletTriangles)]
+
     # ---- BasePassRenderer::RenderInstances (:406-503), cull half --------------------------------
     def _render_instances(self, cl, slot: int, late: bool, alpha_mask: bool):
         sc = self.scene
@@ -236,8 +242,7 @@ class FrameDriver:
             bindings.append(TEX_SRV(8, self.hzb))
         cl.dispatch_indirect(f"basepass_AS_Main LATE_CULL={int(late)}", bindings, self.dispatchArgs[slot])   # :497-502
         if self.raster_depth:                                                            # the mesh + pixel stage of the same draw: depth only
-            b = [CB(0, cb), SRV(0, sc.instances), SRV(1, sc.vertices), SRV(2, sc.meshData), SRV(4, sc.meshlets), SRV(5, sc.meshletVertexIds),
-                 SRV(6, sc.meshletTriangles), SRV(7, self.records[slot]), SRV(9, self.visibleList[slot]), TEX_UAV(0, self.depth, 0)]
+            b = self._mesh_stage_bindings(cb) + [SRV(7, self.records[slot]), SRV(9, self.visibleList[slot]), TEX_UAV(0, self.depth, 0)]
             if self.visibility_on:                                                       # + u1 = visibility buffer, push = pass slot
                 cl.dispatch_indirect("basepass_MS_Main_visibility", b + [TEX_UAV(1, self.visibility, 0), PUSH(1)], self.drawArgs[slot],
                                      push=np.array([slot], np.uint32))
@@ -248,8 +253,7 @@ class FrameDriver:
         """GBufferMotion of every pixel the base pass drew (basepass.hlsl:226-237), once after the last slot."""
         sc, v = self.scene, self.view
         cb = cl.constant_buffer(self._basepass_consts(False), "BasePassConstants")
-        b = [CB(0, cb), SRV(0, sc.instances), SRV(1, sc.vertices), SRV(2, sc.meshData), SRV(4, sc.meshlets), SRV(5, sc.meshletVertexIds),
-             SRV(6, sc.meshletTriangles), TEX_SRV(18, self.visibility)]
+        b = self._mesh_stage_bindings(cb) + [TEX_SRV(18, self.visibility)]
         for s in range(4):                                                               # slots without buffers: an empty stand-in
             b += [SRV(10 + s, self.records[s] if s < self.num_slots else self.dummy),
                   SRV(14 + s, self.visibleList[s] if s < self.num_slots else self.dummy)]
