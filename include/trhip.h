@@ -45,9 +45,12 @@ enum {
 
 /* nvrhi::Format subset used on the path (GraphicConstants.h:25-28).  RG32_UINT (the visibility buffer: each texel one
  * little-endian u64), RG16_FLOAT (the motion target, GBufferMotion) and RGBA32_UINT (GBufferA, GraphicConstants.h:24: 16 bytes per
- * texel, little-endian words x, y, z, w) have one mip only. */
+ * texel, little-endian words x, y, z, w) have one mip only.  So do the deferred lighting pass's formats: R11G11B10_FLOAT
+ * (LightingOutput, GraphicConstants::kLightingOutputFormat: 4 bytes per texel, R in bits 0-10, G in bits 11-21, B in bits 22-31;
+ * unsigned floats of 5 exponent bits with 6, 6 and 5 mantissa bits), R8_UNORM (the shadow mask) and R8_UINT (the SSAO texture),
+ * one byte per texel each. */
 enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4,
-       TRHIP_FORMAT_RGBA32_UINT = 5 };
+       TRHIP_FORMAT_RGBA32_UINT = 5, TRHIP_FORMAT_R11G11B10_FLOAT = 6, TRHIP_FORMAT_R8_UNORM = 7, TRHIP_FORMAT_R8_UINT = 8 };
 
 /* ---- error / introspection ---------------------------------------------------------------- */
 const char* trhip_last_error(void);          /* thread-local text of the last failure          */
@@ -74,7 +77,15 @@ uint32_t    trhip_abi_version(void);
  * texture flags ignored), u0 (texture) RGBA32_UINT GBufferA and u1 (texture) the RG16_FLOAT motion target, both required.
  * Per pixel with a nonzero texel: u0 = PackGBuffer(albedo + debug byte by m_DebugMode 2 / 3 / 12, interpolated vertex
  * normal, emissive, roughness 1, metallic 0), u1 = the words "basepass_PS_Main_motion" writes.  A pixel whose chain of
- * indices leaves a bound buffer (m_MaterialDataIdx included) is left as it is in both targets. */
+ * indices leaves a bound buffer (m_MaterialDataIdx included) is left as it is in both targets.
+ * "deferredlighting_PS_Main" and "deferredlighting_PS_Main_Debug" (deferredlighting.hlsl, DeferredLightingRenderer.cpp: the
+ * directional light and the debug views, without DDGI): a direct dispatch of [numthreads(8, 8, 1)] groups over the screen;
+ * b0 DeferredLightingConsts (112 bytes; m_bRTDDGIEnabled must be 0, m_DebugMode must not be 10), t0 (texture) RGBA32_UINT
+ * GBufferA, t1 RG16_FLOAT GBufferMotion (required by _Debug only), t2 R32_FLOAT depth, t3 R8_UINT SSAO (optional: unbound
+ * reads 255), t4 R8_UNORM shadow mask (optional: unbound reads 1.0), u0 (texture) R11G11B10_FLOAT LightingOutput; every
+ * texture of the size m_LightingOutputResolution; samplers and bindings at t5..t8 are accepted and ignored.  A pixel is
+ * written iff its depth is > 0.0f (the stand-in for the reference's stencil test on the opaque bit); every other texel of u0
+ * keeps its value.  The arithmetic convention is stated in csrc/k_deferredlighting.hip. */
 uint32_t    trhip_shader_count(void);
 const char* trhip_shader_name(uint32_t index);
 int         trhip_shader_exists(const char* name);
@@ -183,8 +194,8 @@ int  trhip_cmd_close(trhip_cmdlist cl);                               /* ::close
  * On a volatile constant buffer this sets the version later dispatches in this list see. */
 int  trhip_cmd_write_buffer(trhip_cmdlist cl, trhip_buffer buf, uint64_t dst_offset, const void* src, uint64_t bytes);
 int  trhip_cmd_clear_buffer_u32(trhip_cmdlist cl, trhip_buffer buf, uint32_t value);   /* ::clearBufferUInt   */
-int  trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value);    /* ::clearTextureFloat (16-bit formats: the fp16 of value, RNE; not the UINT formats) */
-int  trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value); /* ::clearTextureUInt: RG32_UINT / RGBA32_UINT, value in every 32-bit channel word */
+int  trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value);    /* ::clearTextureFloat (16-bit formats: the fp16 of value, RNE; R11G11B10_FLOAT: the pack of value in all three channels; R8_UNORM: round(saturate(value) * 255); not the UINT formats) */
+int  trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value); /* ::clearTextureUInt: RG32_UINT / RGBA32_UINT, value in every 32-bit channel word; R8_UINT, the low byte */
 int  trhip_cmd_copy_buffer(trhip_cmdlist cl, trhip_buffer dst, uint64_t dst_offset, trhip_buffer src, uint64_t src_offset, uint64_t bytes); /* ::copyBuffer */
 /* Multi-GPU hook (no counterpart in the reference, which is single-GPU: GraphicRHI.cpp:165).
  * fn(user, hip_stream) is called on the submitting thread while the list is executed, in order with

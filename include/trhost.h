@@ -87,6 +87,19 @@ int  trhost_load_materials(const void* materials, uint32_t count);
 int  trhost_set_gbuffer(int enable);
 int  trhost_set_debug_view_mode(uint32_t mode);
 int  trhost_download_gbuffer_a(uint32_t* words, uint64_t bytes);
+/* Deferred lighting from GBufferA (DeferredLightingRenderer.cpp; implies the G-buffer, same refusals): after GBufferRenderer one
+ * "deferredlighting_PS_Main" dispatch ("deferredlighting_PS_Main_Debug" while trhost_set_debug_view_mode is not 0; mode 10 needs
+ * the DDGI volume and fails the frame) writes LightingOutput (R11G11B10_FLOAT at render resolution, 4 bytes per texel, cleared to
+ * 0 every frame; written where depth > 0).  trhost_set_directional_light sets Scene::m_DirLightVec, used as given, and
+ * m_DirLightStrength (default (0, -1, 0), 1).  trhost_upload_shadow_mask uploads the R8_UNORM mask at render resolution
+ * (width * height bytes); NULL means white.  trhost_get_deferred_lighting_consts copies the 112 bytes of DeferredLightingConsts
+ * the last frame uploaded (m_ClipToWorld = the inverse of m_WorldToView * m_ViewToClip in double precision, rounded once;
+ * m_CameraOrigin = the eye of m_WorldToView). */
+int  trhost_set_deferred_lighting(int enable);
+int  trhost_set_directional_light(const float vec[3], float strength);
+int  trhost_upload_shadow_mask(const uint8_t* texels, uint64_t bytes);
+int  trhost_download_lighting_output(uint32_t* words, uint64_t bytes);
+int  trhost_get_deferred_lighting_consts(void* out112);
 int  trhost_download_depth(float* depth, uint64_t bytes);
 int  trhost_upload_hzb_mip(uint32_t mip, const uint16_t* texels, uint64_t bytes);
 int  trhost_download_hzb_mip(uint32_t mip, uint16_t* texels, uint64_t bytes);

@@ -1,0 +1,361 @@
+"""The test reference of the deferred lighting pass (tests/lighting_ref.c) pinned by something other than itself, on the CPU:
+the R11G11B10 store against the format's definition in exact rationals, the software exp2 against float64 within the bound
+its source derives, the unpack functions against numpy and rationals, the lit chain against an independent float64
+restatement written from the HLSL, the debug views against closed forms, and the struct layout and declarations."""
+import math
+import os
+import re
+import subprocess
+import sys
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import gbuffer_ref as GR  # noqa: E402
+import lighting_ref as LR  # noqa: E402
+import lighting_scenes as LS  # noqa: E402
+from toyrenderer_amd import interop as I  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def lr(tmp_path_factory):
+    return LR.load(tmp_path_factory.mktemp("lighting_ref"))
+
+
+@pytest.fixture(scope="module")
+def gr(tmp_path_factory):
+    return GR.load(tmp_path_factory.mktemp("gbuffer_ref"))
+
+
+# ---- the R11G11B10_FLOAT store -------------------------------------------------------------------------------------------
+def _decode(code: int, m: int) -> Fraction:
+    """The format's definition: 5 exponent bits (bias 15), m mantissa bits, no sign."""
+    e, f = code >> m, code & ((1 << m) - 1)
+    if e == 0:
+        return Fraction(f, 1 << m) * Fraction(1, 1 << 14)
+    return (1 + Fraction(f, 1 << m)) * (Fraction(2) ** (e - 15))
+
+
+@pytest.mark.parametrize("m,largest", [(6, 65024), (5, 64512)])
+def test_pack_meets_the_formats_definition(lr, m, largest):
+    finite = 31 << m                                             # codes below the infinity pattern
+    values = [_decode(c, m) for c in range(finite)]
+    assert values[-1] == largest and all(a < b for a, b in zip(values, values[1:]))
+    as_f32 = np.array([float(v) for v in values], F)
+    assert all(Fraction(float(x)) == v for x, v in zip(as_f32, values)), "every decodable value is a float32"
+    assert np.array_equal(LR.pack_ufloat(lr, as_f32, m), np.arange(finite, dtype=np.uint32)), "every decodable value packs to itself"
+    mids = [(a + b) / 2 for a, b in zip(values, values[1:])]
+    mid32 = np.array([float(v) for v in mids], F)
+    assert all(Fraction(float(x)) == v for x, v in zip(mid32, mids)), "every midpoint is a float32"
+    lo = np.arange(finite - 1, dtype=np.uint32)
+    assert np.array_equal(LR.pack_ufloat(lr, mid32, m), lo + (lo & 1)), "a midpoint goes to the even neighbour"
+    assert np.array_equal(LR.pack_ufloat(lr, np.nextafter(mid32, F(0)), m), lo), "just below a midpoint: the lower neighbour"
+    assert np.array_equal(LR.pack_ufloat(lr, np.nextafter(mid32, F(np.inf)), m), lo + 1), "just above a midpoint: the upper neighbour"
+    top, inf, nan = finite - 1, finite, finite | ((1 << m) - 1)
+    above = np.array([largest, np.nextafter(F(largest), F(np.inf)), (largest + 2.0 ** (16 - m - 1)), 65535.0, 65536.0, 1e30, 3.4028235e38], F)
+    assert np.all(LR.pack_ufloat(lr, above, m) == top), "finite values above the largest finite give the largest finite"
+    special = np.array([np.inf, np.nan, -np.nan, -0.0, 0.0, -1.0, -1e-40, -np.inf, -3.4028235e38], F)
+    assert LR.pack_ufloat(lr, special, m).tolist() == [inf, nan, nan, 0, 0, 0, 0, 0, 0]
+    tiny = np.array([1e-45, 2.0 ** -(15 + m), np.nextafter(F(2.0 ** -(15 + m)), F(1)), 2.0 ** -(14 + m)], F)   # half the smallest subnormal ties to 0
+    assert LR.pack_ufloat(lr, tiny, m).tolist() == [0, 0, 1, 1]
+    rng = np.random.default_rng(21)                                 # random values: the nearest decodable value, found in exact rationals
+    x = np.exp2(rng.uniform(-22.0, 16.0, 20000)).astype(F)
+    got = LR.pack_ufloat(lr, x, m)
+    v64 = np.array([float(v) for v in values])
+    for xi, gi in zip(x.tolist(), got.tolist()):
+        j = int(np.searchsorted(v64, xi))
+        cands = [c for c in (j - 1, j) if 0 <= c < finite]
+        fx = Fraction(xi)
+        best = min(cands, key=lambda c: (abs(values[c] - fx), c & 1))
+        assert gi == best or fx > largest and gi == top, (xi, gi, best)
+
+
+def test_pack_r11g11b10_places_the_channels(lr):
+    w = LR.pack_r11g11b10(lr, [[1.0, 0.5, 2.0], [np.nan, -1.0, np.inf], [65024.0, 1e9, 64512.0]])
+    assert w.tolist() == [(15 << 6) | (14 << 6) << 11 | (16 << 5) << 22, 0x7FF | 0 << 11 | (31 << 5) << 22, 0x7BF | 0x7BF << 11 | 0x3DF << 22]
+
+
+# ---- the software exp2 -----------------------------------------------------------------------------------------------------
+def test_software_exp2_is_within_its_derived_bound(lr):
+    """10^6 seeded inputs in [-9.28, 0], the ends and every integer: |lr_exp2(x) - 2^x| <= LR_EXP2_BOUND * 2^ceil(x), the bound
+    of the error analysis next to the coefficients (2.46 * 2^-25).  float64 exp2 stands for 2^x: its own error is 2^-53 relative."""
+    rng = np.random.default_rng(22)
+    x = np.concatenate([rng.uniform(-9.28, 0.0, 1_000_000).astype(F), np.array([F(-9.28), 0.0, -0.0], F), -np.arange(0, 10, dtype=F),
+                        np.nextafter(-np.arange(0, 10, dtype=F), F(-20)), np.nextafter(-np.arange(1, 10, dtype=F), F(0)), (F(-9.28) * np.array([1e-5, 1.0], F))])
+    got = LR.exp2(lr, x).astype(np.float64)
+    want = np.exp2(x.astype(np.float64))
+    scale = np.exp2(np.ceil(x.astype(np.float64)))
+    err = np.abs(got - want) / scale
+    bound = LR.exp2_bound(lr)
+    assert bound == 2.46 * 2.0 ** -25
+    print(f"largest error {err.max():.4e} = {err.max() / 2.0 ** -25:.4f} * 2^-25 (bound {bound / 2.0 ** -25:.2f} * 2^-25); in ulps of the result {np.max(np.abs(got - want) / np.spacing(want.astype(F)).astype(np.float64)):.3f}")
+    assert err.max() <= bound
+    ints = -np.arange(0, 10, dtype=F)
+    assert np.array_equal(LR.exp2(lr, ints), np.exp2(ints)), "integers give exact powers of two"
+
+
+def test_exp2_range_reduction_is_exact():
+    """f = x - ceil(x) is exact in float32 for every x in [-9.28, 0] tried (floor would not be: x = -9.28e-5 gives 1 + x)."""
+    rng = np.random.default_rng(23)
+    x = np.concatenate([rng.uniform(-9.28, 0.0, 1_000_000), -np.exp2(rng.uniform(-40.0, 0.0, 200_000))]).astype(F)
+    f = (x - np.ceil(x)).astype(F)
+    assert np.array_equal(f.astype(np.float64), x.astype(np.float64) - np.ceil(x.astype(np.float64)))
+    xs = F(-9.28e-5)
+    assert np.float64(F(xs - np.floor(xs))) != np.float64(xs) - np.floor(np.float64(xs))
+
+
+# ---- the unpack functions --------------------------------------------------------------------------------------------------
+def test_unorm_unpacks_equal_numpy(lr):
+    b = np.arange(256, dtype=np.uint32)
+    assert np.array_equal(LR.unpack_unorm8(lr, b), b.astype(F) * (F(1.0) / F(255.0)))
+    u = np.arange(65536, dtype=np.uint32)
+    assert np.array_equal(LR.unpack_unorm16(lr, u), u.astype(F) * (F(1.0) / F(65535.0)))
+    assert LR.unpack_unorm8(lr, [255])[0] == F(1.0) and LR.unpack_unorm16(lr, [65535])[0] == F(1.0)
+
+
+def test_octahedral_unpack_returns_the_packed_direction(lr, gr):
+    """2e6 seeded unit vectors through gr_pack_oct and lr_unpack_oct: within sqrt(18) / 65535 + 2^-20 of the input, the bound
+    tests/test_gbuffer_ref.py derives for the round trip; and the unpack equals its numpy float32 restatement word for word."""
+    rng = np.random.default_rng(15)
+    n = rng.normal(size=(2_000_000, 3))
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    n32 = n.astype(F)
+    words = GR.pack_oct(gr, n32)
+    back = LR.unpack_oct(lr, words)
+    unit = n32.astype(np.float64) / np.linalg.norm(n32.astype(np.float64), axis=1, keepdims=True)
+    err = np.linalg.norm(back.astype(np.float64) - unit, axis=1)
+    print("largest round-trip error:", err.max())
+    assert err.max() <= np.sqrt(18.0) / 65535.0 + 2.0 ** -20
+    words = np.concatenate([words[:200_000], np.array([0, 0xFFFFFFFF, 0x80008000, 0x0000FFFF, 0xFFFF0000, 0x7FFF7FFF], np.uint32)])
+    k = F(1.0) / F(65535.0)
+    with np.errstate(all="ignore"):
+        fx = ((words & 0xFFFF).astype(F) * k) * F(2) - F(1)
+        fy = ((words >> 16).astype(F) * k) * F(2) - F(1)
+        z = (F(1) - np.abs(fx)) - np.abs(fy)
+        t = np.fmin(np.fmax(-z, F(0)), F(1))
+        x, y = fx + np.where(fx >= 0, -t, t), fy + np.where(fy >= 0, -t, t)
+        dot = np.array([I.fmaf(c, c, I.fmaf(b, b, F(a * a))) for a, b, c in zip(x[-2000:], y[-2000:], z[-2000:])], F)
+        ln = np.sqrt(dot)
+        want = np.stack([x[-2000:] / ln, y[-2000:] / ln, z[-2000:] / ln], 1)
+    assert np.array_equal(LR.unpack_oct(lr, words[-2000:]).view(np.uint32), want.view(np.uint32))
+
+
+def test_r9g9b9e5_unpack_is_exact(lr):
+    rng = np.random.default_rng(24)
+    words = np.concatenate([rng.integers(0, 1 << 32, 20000, dtype=np.uint64).astype(np.uint32),
+                            np.array([(e << 27) | m for e in range(32) for m in (0, 1, 0x1FF, 0x7FFFFFF, 0x155 | 0x0AA << 9 | 0x1FF << 18)], np.uint32)])
+    got = LR.unpack_r9g9b9e5(lr, words)
+    for w, c in zip(words.tolist(), got.tolist()):
+        e = (w >> 27) - 24
+        want = [Fraction((w >> s) & 0x1FF) * Fraction(2) ** e for s in (0, 9, 18)]
+        assert [Fraction(x) for x in c] == want, hex(w)
+
+
+# ---- the lit chain against float64 ------------------------------------------------------------------------------------------
+def f64_lit(k, g, depth, shadow):
+    """deferredlighting.hlsl PS_Main without DDGI, restated from the HLSL in numpy float64 over a whole image."""
+    k = k[0]
+    W, H = (int(x) for x in k["m_LightingOutputResolution"])
+    g = g.astype(np.uint64)
+    byte = lambda w, s: ((w >> s) & 0xFF).astype(np.float64) / 255.0                                  # noqa: E731
+    albedo = np.stack([byte(g[..., 0], 0), byte(g[..., 0], 8), byte(g[..., 0], 16)], -1)
+    f = np.stack([(g[..., 1] & 0xFFFF), (g[..., 1] >> 16)], -1).astype(np.float64) / 65535.0 * 2.0 - 1.0
+    n = np.concatenate([f, (1.0 - np.abs(f[..., :1]) - np.abs(f[..., 1:]))], -1)
+    t = np.clip(-n[..., 2], 0.0, 1.0)
+    n[..., 0] += np.where(n[..., 0] >= 0, -t, t)
+    n[..., 1] += np.where(n[..., 1] >= 0, -t, t)
+    with np.errstate(all="ignore"):
+        N = n / np.linalg.norm(n, axis=-1, keepdims=True)
+        emissive = np.stack([(g[..., 2] >> s) & 0x1FF for s in (0, 9, 18)], -1).astype(np.float64) * np.exp2((g[..., 2] >> 27).astype(np.float64) - 24.0)[..., None]
+        rough, metal = byte(g[..., 3], 0), byte(g[..., 3], 8)
+        px, py = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+        uv = np.stack([(px + 0.5) / W, (py + 0.5) / H], -1)
+        clip = uv * np.array([2.0, -2.0]) + np.array([-1.0, 1.0])
+        hom = np.concatenate([clip, depth.astype(np.float64)[..., None], np.ones((H, W, 1))], -1) @ k["m_ClipToWorld"].astype(np.float64)
+        world = hom[..., :3] / hom[..., 3:]
+        diffuse_color = albedo * (1.0 - metal)[..., None]
+        dielectric = 0.08 * 0.5
+        f0 = dielectric + metal[..., None] * (albedo - dielectric)
+        V = k["m_CameraOrigin"].astype(np.float64) - world
+        V /= np.linalg.norm(V, axis=-1, keepdims=True)
+        L = k["m_DirectionalLightVector"].astype(np.float64)
+        Hv = V + L
+        Hv /= np.linalg.norm(Hv, axis=-1, keepdims=True)
+        sat = lambda x: np.clip(x, 0.0, 1.0)                                                            # noqa: E731
+        NdotV = sat(np.abs((N * V).sum(-1)) + 1e-5)
+        NdotL, NdotH, VdotH = sat((N * L).sum(-1)), sat((N * Hv).sum(-1)), sat((V * Hv).sum(-1))
+        a = rough * rough
+        a2 = np.clip(a * a, 0.0001, 1.0)
+        d = (NdotH * a2 - NdotH) * NdotH + 1.0
+        D = a2 / (math.pi * d * d)
+        vis = 0.5 / (NdotL * (NdotV * (1.0 - a2) + a2) + NdotV * (NdotL * (1.0 - a2) + a2))
+        Fc = (1.0 - VdotH) ** 5
+        Fr = Fc[..., None] + (1.0 - Fc)[..., None] * f0
+        r4 = rough[..., None] * np.array([-1.0, -0.0275, -0.572, 0.022]) + np.array([1.0, 0.0425, 1.04, -0.04])
+        a004 = np.minimum(r4[..., 0] * r4[..., 0], np.exp2(-9.28 * NdotV)) * r4[..., 0] + r4[..., 1]
+        env = f0 * (-1.04 * a004 + r4[..., 2])[..., None] + (1.04 * a004 + r4[..., 3])[..., None]
+        spec = (D * vis)[..., None] * Fr + env
+        lit = (diffuse_color / math.pi + spec) * NdotL[..., None] * np.float64(k["m_DirectionalLightStrength"])
+        return lit * (shadow.astype(np.float64) / 255.0)[..., None] + emissive, emissive
+
+
+def f64_pack(v, m):
+    """Code of the nearest decodable value (ties to even) of finite float64 values up to the largest finite; negatives give 0."""
+    v = np.maximum(np.asarray(v, np.float64), 0.0)
+    e = np.maximum(np.floor(np.log2(np.maximum(v, 2.0 ** -40))), -14.0)
+    e = np.where(v >= np.exp2(e + 1), e + 1, np.where(v < np.exp2(e), np.maximum(e - 1, -14.0), e))    # log2's rounding at binade edges
+    q = np.rint(v / np.exp2(e - m))                                                                    # exact scaling; rint ties to even
+    sub = v < 2.0 ** -14
+    code = np.where(sub, q, (e + 15) * (1 << m) + (q - (1 << m)))                                       # a carry to 2^(m+1) lands on the next exponent
+    return code.astype(np.int64)
+
+
+# Tolerance of the lit chain, relative to lightStrength + |emissive|: the float32 reference was measured against the float64
+# restatement on this file's seeded inputs (the print below) and the assertion is the next power of two at or above twice that
+# maximum, the factor two being the margin for other seeds.  Measured 2.43e-2 (roughness byte 18, on a specular peak: D_GGX's
+# d = (NdotH * a2 - NdotH) * NdotH + 1 cancels to about a2 = 1e-4 there, so the 1e-7 of NdotH is 1e-3 of d and twice that of D);
+# 2 * 2.43e-2 = 4.86e-2, next power of two 2^-4.  Both numbers are in DESIGN.md 9.
+LIT_TOLERANCE = 2.0 ** -4
+
+
+def test_lit_chain_against_float64(lr, gr):
+    """Every roughness byte (x), metallic 0 / 128 / 255 (rows), random normals over the sphere (so views from grazing to head-on),
+    every shadow byte: the float3 before the store against float64, then the packed words: none differs from the float64
+    result's pack by more than one step."""
+    W, H = 256, 192
+    rng = np.random.default_rng(25)
+    g = LS.gbuffer_image(W, H, 25)
+    g[..., 3] = np.arange(W, dtype=np.uint32)[None, :] | (np.array([0, 128, 255], np.uint32)[np.arange(H) % 3][:, None] << 8)
+    nrm = rng.normal(size=(H, W, 3)).astype(F)
+    g[..., 1] = GR.pack_oct(gr, nrm.reshape(-1, 3)).reshape(H, W)
+    g[..., 2] = np.where(rng.random((H, W)) < 0.7, 0, rng.integers(0, 1 << 27, (H, W), dtype=np.uint64).astype(np.uint32) | np.uint32(14 << 27))   # emissive below 0.5
+    depth = rng.uniform(0.002, 1.0, (H, W)).astype(F)
+    shadow = LS.byte_image(W, H, 25)
+    m, eye = LS.camera((W, H))
+    worst, steps = 0.0, np.zeros(3, np.int64)
+    total = 0
+    for light, strength in (((0.0, -1.0, 0.0), 1.0), (LS.LIGHTS[1][1], 3.0), ((0.6, 0.0, 0.8), 0.5)):
+        k = LR.consts(m, eye, light, strength, (W, H))
+        words, rgb = LR.lighting(lr, k, g, depth, shadow=shadow, want_rgb=True)
+        want, emissive = f64_lit(k, g, depth, shadow)
+        assert np.all(np.isfinite(rgb)) and np.all(np.isfinite(want))
+        rel = np.abs(rgb.astype(np.float64) - want).max(-1) / (strength + np.linalg.norm(emissive, axis=-1))
+        worst = max(worst, float(rel.max()))
+        for c, (mb, shift) in enumerate(((6, 0), (6, 11), (5, 22))):
+            got = ((words >> shift) & ((1 << (mb + 5)) - 1)).astype(np.int64)
+            diff = np.abs(got - f64_pack(np.minimum(want[..., c], 65024.0 if mb == 6 else 64512.0), mb))
+            for s in range(3):
+                steps[s] += int(np.count_nonzero(diff == s)) if s < 2 else int(np.count_nonzero(diff >= 2))
+        total += 3 * W * H
+        assert np.count_nonzero(words) > 0.5 * W * H                           # the half facing the light, and the emissive texels
+    print(f"largest error relative to lightStrength + |emissive|: {worst:.3e}; channels equal {steps[0] / total:.4%}, one step off {steps[1] / total:.4%}, more {steps[2]}")
+    assert steps[2] == 0, "a packed channel differs from the float64 result by more than one step"
+    assert worst <= LIT_TOLERANCE, (worst, LIT_TOLERANCE)
+
+
+# ---- the debug views against closed forms ----------------------------------------------------------------------------------
+def _debug(lr, mode, g, **kw):
+    H, W = g.shape[:2]
+    m, eye = LS.camera((W, H))
+    k = LR.consts(m, eye, (0.0, -1.0, 0.0), 1.0, (W, H), debug_mode=mode)
+    return LR.lighting(lr, k, g, np.ones((H, W), F), debug=True, **kw)
+
+
+def test_debug_views_return_the_stored_bytes(lr, gr):
+    b = np.arange(256, dtype=np.uint32)
+    g = np.zeros((1, 256, 4), np.uint32)
+    g[0, :, 0] = b | ((b * 7) & 0xFF) << 8 | ((255 - b) << 16) | (b << 24)
+    g[0, :, 1] = 0x80008000
+    g[0, :, 3] = b | ((b * 3) & 0xFF) << 8
+    unit = b.astype(F) * (F(1.0) / F(255.0))
+    pick = lambda idx: unit[idx]                                                                        # noqa: E731
+    assert np.array_equal(_debug(lr, 4, g)[0], LR.pack_r11g11b10(lr, np.stack([pick(b), pick((b * 7) & 0xFF), pick(255 - b)], 1))), "albedo"
+    assert np.array_equal(_debug(lr, 8, g)[0], LR.pack_r11g11b10(lr, np.stack([unit] * 3, 1))), "roughness"
+    assert np.array_equal(_debug(lr, 7, g)[0], LR.pack_r11g11b10(lr, np.stack([pick((b * 3) & 0xFF)] * 3, 1))), "metalness"
+    assert np.all(_debug(lr, 14, g) == 0) and np.all(_debug(lr, 0xFFFFFFFF, g) == 0) and np.all(_debug(lr, 0, g) == 0), "modes outside the chain give 0"
+    ssao = b.astype(np.uint8).reshape(1, 256)
+    assert np.array_equal(_debug(lr, 9, g, ssao=ssao)[0], LR.pack_r11g11b10(lr, np.stack([b.astype(F) / F(255.0)] * 3, 1))), "ambient occlusion"
+    assert np.all(_debug(lr, 9, g) == LR.pack_r11g11b10(lr, [[1.0, 1.0, 1.0]])[0]), "SSAO unbound reads 255"
+    sh = np.fmax(F(0.05), b.astype(F) / F(255.0))
+    assert np.array_equal(_debug(lr, 11, g, shadow=ssao)[0], LR.pack_r11g11b10(lr, np.stack([sh] * 3, 1))), "shadow mask"
+    up = LR.pack_r11g11b10(lr, [[0.0, 0.0, 1.0]])[0]                                                  # the normal word 0x80008000 is +z up to rounding
+    assert np.all(np.abs(((_debug(lr, 5, g)[0] >> 22).astype(np.int64) - int(up >> 22))) <= 1)
+    mot = np.zeros((1, 256, 2), np.float16); mot[0, :, 0] = np.arange(256) - 100; mot[0, :, 1] = 0.5 * np.arange(256)
+    want = np.stack([mot[0, :, 0].astype(F) / F(256.0), mot[0, :, 1].astype(F) / F(1.0), np.zeros(256, F)], 1)
+    assert np.array_equal(_debug(lr, 13, g, motion=mot)[0], LR.pack_r11g11b10(lr, want)), "motion vectors"
+    seeds = (unit * F(255.0)).astype(np.uint32)                                                        # modes 2 and 3: three draws of the LCG
+    cols = []
+    s = seeds.astype(np.uint64)
+    for _ in range(3):
+        s = (s * np.uint64(1664525) + np.uint64(1013904223)) & np.uint64(0xFFFFFFFF)
+        cols.append(((s & np.uint64(0xFFFFFF)).astype(F) / F(16777216.0)))
+    for mode in (2, 3):
+        assert np.array_equal(_debug(lr, mode, g)[0], LR.pack_r11g11b10(lr, np.stack(cols, 1))), f"mode {mode}"
+
+
+def test_mesh_lod_view_tabulated_over_every_debug_byte(lr, gr):
+    """Mode 12 for all 256 debug bytes.  The resolve stores byte k for LOD k (tests/test_gbuffer_ref.py: every LOD byte lands
+    on itself); the lighting pass reads back uint(byte * (1.0f / 255.0f) * 255.0f), tabulated here against the bytes."""
+    b = np.arange(256, dtype=np.uint32)
+    g = np.zeros((1, 256, 4), np.uint32)
+    g[0, :, 0] = b << 24
+    g[0, :, 1] = 0x80008000
+    index = ((b.astype(F) * (F(1.0) / F(255.0))) * F(255.0)).astype(np.uint32)
+    table = np.array([[1, 0, 0], [1, .5, 0], [1, 1, 0], [.5, 1, 0], [0, 1, 0], [0, .5, 1], [0, 0, 1], [.5, 0, 1]], F)
+    want = np.where((index < 8)[:, None], table[np.minimum(index, 7)], F(0))
+    assert np.array_equal(_debug(lr, 12, g)[0], LR.pack_r11g11b10(lr, want))
+    stored = GR.pack_rgba8(gr, np.stack([np.zeros(8, F)] * 3 + [GR.mesh_lod_value(gr, np.arange(8, dtype=np.uint32))], 1)) >> 24
+    print("LOD -> stored byte -> table entry read back:", [(k, int(stored[k]), int(index[stored[k]])) for k in range(8)])
+    print("debug bytes whose index differs from the byte:", [int(x) for x in b[index != b]][:16], "...", int(np.count_nonzero(index != b)), "of 256")
+    assert np.array_equal(stored, np.arange(8)), "the resolve stores byte k for LOD k"
+    assert np.array_equal(index, b), "every byte reads back as itself: LOD k shows table entry k, so there is no Q14"
+
+
+# ---- layout and declarations ------------------------------------------------------------------------------------------------
+def test_deferred_lighting_consts_layout(tmp_path):
+    """A g++-compiled probe prints sizeof / offsetof of interop::DeferredLightingConsts (csrc/ShaderInterop.h): 112 bytes, every
+    field where the numpy dtype and tests/lighting_ref.c have it."""
+    fields = list(I.DeferredLightingConsts.names)
+    lines = ['#include <cstdio>', '#include "ShaderInterop.h"', "int main() {", '    printf("sizeof %zu\\n", sizeof(interop::DeferredLightingConsts));']
+    lines += [f'    printf("{f} %zu\\n", offsetof(interop::DeferredLightingConsts, {f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    src = tmp_path / "probe.cpp"
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "probe"
+    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "toyrenderer_amd", "csrc"), str(src), "-o", str(exe)])
+    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    assert int(out["sizeof"]) == 112 == I.DeferredLightingConsts.itemsize
+    want = dict(m_ClipToWorld=0, m_CameraOrigin=64, m_SSAOEnabled=76, m_DebugMode=80, m_DirectionalLightVector=84, m_DirectionalLightStrength=96,
+                m_LightingOutputResolution=100, m_bRTDDGIEnabled=108)
+    for f in fields:
+        assert int(out[f]) == I.DeferredLightingConsts.fields[f][1] == want[f], f
+
+
+def test_exports_and_declarations():
+    from toyrenderer_amd import host, rhi
+    t = open(os.path.join(ROOT, "include", "trhost.h")).read()
+    for decl in (r"int\s+trhost_set_deferred_lighting\s*\(\s*int\s+\w+\s*\)\s*;",
+                 r"int\s+trhost_set_directional_light\s*\(\s*const\s+float\s+\w+\[3\]\s*,\s*float\s+\w+\s*\)\s*;",
+                 r"int\s+trhost_upload_shadow_mask\s*\(\s*const\s+uint8_t\s*\*\s*\w+\s*,\s*uint64_t\s+\w+\s*\)\s*;",
+                 r"int\s+trhost_download_lighting_output\s*\(\s*uint32_t\s*\*\s*\w+\s*,\s*uint64_t\s+\w+\s*\)\s*;",
+                 r"int\s+trhost_get_deferred_lighting_consts\s*\(\s*void\s*\*\s*\w+\s*\)\s*;"):
+        assert re.search(decl, t), decl
+    for f in ("trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
+              "trhost_get_deferred_lighting_consts"):
+        assert f in host.HOST_SYMBOLS and hasattr(host.load(), f), f
+    for m in ("set_deferred_lighting", "set_directional_light", "upload_shadow_mask", "download_lighting_output", "deferred_lighting_consts"):
+        assert callable(getattr(host.Renderer, m, None)), m
+    assert all(n in rhi.ABI_SYMBOLS for n in ("trhip_cmd_clear_texture_f32", "trhip_cmd_clear_texture_u32", "trhip_cmd_copy_texture"))
+    h = open(os.path.join(ROOT, "include", "trhip.h")).read()
+    for name, value in (("R11G11B10_FLOAT", 6), ("R8_UNORM", 7), ("R8_UINT", 8)):
+        assert re.search(rf"TRHIP_FORMAT_{name}\s*=\s*{value}\b", h) and getattr(rhi, "FORMAT_" + name) == value
+    assert "deferredlighting_PS_Main_Debug" in h
+    assert {"deferredlighting_PS_Main", "deferredlighting_PS_Main_Debug"} <= set(rhi.shader_names())
+    mk = open(os.path.join(ROOT, "toyrenderer_amd", "csrc", "Makefile")).read()
+    assert "k_deferredlighting.hip" in re.search(r"^SRCS\s*:=(.*)$", mk, flags=re.M).group(1)

@@ -26,10 +26,20 @@ static constexpr uint32_t MaterialFlag_UseMetallicRoughnessTexture = (1u << 2);
 static constexpr uint32_t MaterialFlag_UseEmissiveTexture = (1u << 3);
 static constexpr uint32_t kMaterialFlagAnyTexture = 0xFu;
 
-// ShaderInterop.h:27-37 (the debug views that write GBufferA's debug byte)
+// ShaderInterop.h:26-38 (2, 3 and 12 also write GBufferA's debug byte; 10 needs the DDGI volume and is refused)
+static constexpr uint32_t kDeferredLightingDebugMode_LightingOnly = 1;
 static constexpr uint32_t kDeferredLightingDebugMode_ColorizeInstances = 2;
 static constexpr uint32_t kDeferredLightingDebugMode_ColorizeMeshlets = 3;
+static constexpr uint32_t kDeferredLightingDebugMode_Albedo = 4;
+static constexpr uint32_t kDeferredLightingDebugMode_Normal = 5;
+static constexpr uint32_t kDeferredLightingDebugMode_Emissive = 6;
+static constexpr uint32_t kDeferredLightingDebugMode_Metalness = 7;
+static constexpr uint32_t kDeferredLightingDebugMode_Roughness = 8;
+static constexpr uint32_t kDeferredLightingDebugMode_AmbientOcclusion = 9;
+static constexpr uint32_t kDeferredLightingDebugMode_Ambient = 10;
+static constexpr uint32_t kDeferredLightingDebugMode_ShadowMask = 11;
 static constexpr uint32_t kDeferredLightingDebugMode_MeshLOD = 12;
+static constexpr uint32_t kDeferredLightingDebugMode_MotionVectors = 13;
 
 // ShaderInterop.h:19-24
 static constexpr uint32_t kMaxMeshletVertices = 64;
@@ -95,6 +105,23 @@ struct MaterialData
     float m_ConstRoughness;                  // Q13: never read by the reference's shader (roughness 1, metallic 0 without a texture)
     float m_ConstMetallic;
 };
+
+// ShaderInterop.h:86-98
+struct DeferredLightingConsts
+{
+    Matrix m_ClipToWorld;
+    float m_CameraOrigin[3];
+    uint32_t m_SSAOEnabled;
+    uint32_t m_DebugMode;
+    float m_DirectionalLightVector[3];
+    float m_DirectionalLightStrength;
+    Vector2U m_LightingOutputResolution;
+    uint32_t m_bRTDDGIEnabled;
+};
+static_assert(sizeof(DeferredLightingConsts) == 112 && offsetof(DeferredLightingConsts, m_CameraOrigin) == 64 && offsetof(DeferredLightingConsts, m_SSAOEnabled) == 76, "DeferredLightingConsts");
+static_assert(offsetof(DeferredLightingConsts, m_DebugMode) == 80 && offsetof(DeferredLightingConsts, m_DirectionalLightVector) == 84, "DeferredLightingConsts");
+static_assert(offsetof(DeferredLightingConsts, m_DirectionalLightStrength) == 96 && offsetof(DeferredLightingConsts, m_LightingOutputResolution) == 100 &&
+              offsetof(DeferredLightingConsts, m_bRTDDGIEnabled) == 108, "DeferredLightingConsts");
 
 // ShaderInterop.h:117-122
 struct DispatchIndirectArguments

@@ -683,8 +683,18 @@ public:
     {
         if (g_Scene->m_NumPrimitives == 0) return;                            // :668-671
         nvrhi::TextureHandle depthStencilBuffer = renderGraph.GetTexture(g_DepthStencilBufferRDGTextureHandle);
+        CreatePixelTargets();
+        RenderBasePassParams params;                                          // :691-695
+        params.m_DepthBuffer = depthStencilBuffer;
+        RenderBasePass(commandList, renderGraph, params);
+    }
+
+    // The per-pixel targets, owned here and created on first use.  Render calls it; so does a later renderer's Setup that reads
+    // them (DeferredLightingRenderer: Setup is single-threaded, Render is not).
+    void CreatePixelTargets()
+    {
         if (g_Scene->m_bVisibilityBuffer && !m_VisibilityBuffer) {
-            // the per-pixel targets, owned here (GBufferMotion: GraphicConstants.h:25, RG16_FLOAT)
+            // GBufferMotion: GraphicConstants.h:25, RG16_FLOAT
             nvrhi::TextureDesc desc;
             desc.width = g_Graphic.m_RenderResolution.x;
             desc.height = g_Graphic.m_RenderResolution.y;
@@ -705,9 +715,6 @@ public:
             desc.debugName = "GBufferA";
             m_GBufferA = g_Graphic.m_NVRHIDevice->createTexture(desc);
         }
-        RenderBasePassParams params;                                          // :691-695
-        params.m_DepthBuffer = depthStencilBuffer;
-        RenderBasePass(commandList, renderGraph, params);
     }
 };
 DEFINE_RENDERER(GBufferRenderer);
@@ -740,6 +747,7 @@ nvrhi::TextureHandle GetLastDepthBuffer() { return static_cast<GBufferRenderer*>
 nvrhi::TextureHandle GetVisibilityBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_VisibilityBuffer; }
 nvrhi::TextureHandle GetMotionBuffer() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_MotionBuffer; }
 nvrhi::TextureHandle GetGBufferA() { return static_cast<GBufferRenderer*>(g_GBufferRenderer)->m_GBufferA; }
+void CreateGBufferPixelTargets() { static_cast<GBufferRenderer*>(g_GBufferRenderer)->CreatePixelTargets(); }
 
 void ReleaseVisibilityPassBuffers()
 {

@@ -12,6 +12,8 @@ static constexpr float kNearDepth = kInversedDepthBuffer ? 1.0f : 0.0f;
 static constexpr float kFarDepth = 1.0f - kNearDepth;
 static constexpr nvrhi::Format kGBufferAFormat = nvrhi::Format::RGBA32_UINT;
 static constexpr nvrhi::Format kGBufferMotionFormat = nvrhi::Format::RG16_FLOAT;
+static constexpr nvrhi::Format kLightingOutputFormat = nvrhi::Format::R11G11B10_FLOAT;
+static constexpr nvrhi::Format kShadowMaskFormat = nvrhi::Format::R8_UNORM;
 static constexpr nvrhi::Format kDepthStencilFormat = nvrhi::Format::D24S8;
 static constexpr nvrhi::Format kHZBFormat = nvrhi::Format::R16_FLOAT;
 } // namespace GraphicConstants

@@ -67,6 +67,11 @@ inline Vector4 CullingFrustumOf(const Matrix& viewToClip)
     return Vector4{ sideways.x, sideways.z, upright.y, upright.z };
 }
 
+// Inverse of a * b for m_ClipToWorld = (WorldToView * ViewToClip)^-1: product and inverse (cofactors over the determinant) in
+// double precision, every element rounded once to float32.  The reference calls DirectXMath's float32 XMMatrixInverse, which
+// is absent here; toyrenderer_amd/interop.py clip_to_world is the same definition through numpy.
+Matrix InverseOfProduct(const Matrix& a, const Matrix& b);
+
 // MathUtilities.cpp:3-38
 void ModifyPerspectiveMatrix(Matrix& mat, float nearPlane, float farPlane, bool bReverseZ, bool bInfiniteZ);
 // XMMatrixPerspectiveFovRH (SimpleMath.inl:2193-2199)

@@ -16,6 +16,7 @@
 
 extern IRenderer* g_UpdateInstanceConstsRenderer;
 extern IRenderer* g_GBufferRenderer;
+extern IRenderer* g_DeferredLightingRenderer;
 extern IRenderer* g_GIDebugRenderer;
 
 void View::Update()
@@ -31,6 +32,10 @@ void View::Update()
         ModifyPerspectiveMatrix(m_ViewToClip, m_ZNearP, kKindaBigNumber, GraphicConstants::kInversedDepthBuffer, GraphicConstants::kInfiniteDepthBuffer);
     }
     // TAA jitter (:127-131) is out of scope (no TAA renderer)
+
+    for (int j = 0; j < 3; ++j)                                               // m_Eye (:133): see Scene.h; the sum GIRenderer.cpp's constants use
+        m_Eye[j] = -(m_WorldToView.m[3][0] * m_WorldToView.m[j][0] + m_WorldToView.m[3][1] * m_WorldToView.m[j][1] + m_WorldToView.m[3][2] * m_WorldToView.m[j][2]);
+    m_ClipToWorld = InverseOfProduct(m_WorldToView, m_ViewToClip);            // :135-137
 
     if (!g_Scene->m_bFreezeCullingCamera) {                                   // :139-144
         m_CullingPrevWorldToView = m_PrevWorldToView;
@@ -212,6 +217,7 @@ void Scene::Update()
         HOST_PROFILE_SCOPE("RenderGraph::AddRenderer x2 (Setup)");
         m_RenderGraph->AddRenderer(g_UpdateInstanceConstsRenderer);
         m_RenderGraph->AddRenderer(g_GBufferRenderer);
+        if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
         m_RenderGraph->AddRenderer(g_GIDebugRenderer);                        // :509 (after the base pass: it reads this frame's HZB)
     }
     { HOST_PROFILE_SCOPE("RenderGraph::Compile"); m_RenderGraph->Compile(); }                            // :515
@@ -227,6 +233,7 @@ void Scene::Shutdown()
     m_NodeLocalTransformsBuffer = m_PrimitiveIDToNodeIDBuffer = nullptr;
     m_HZB = nullptr;
     m_SyntheticDepth = nullptr;
+    m_ShadowMaskTexture = nullptr;
     m_GIProbePositionsBuffer = m_GIProbeStatesBuffer = nullptr;
     m_NumGIProbes = 0; m_bShowGIProbes = false;
 }

@@ -25,6 +25,11 @@ public:
     Matrix m_WorldToView{}, m_PrevWorldToView{};
     Matrix m_ViewToClip{}, m_PrevViewToClip{};
     Matrix m_CullingWorldToView{}, m_CullingPrevWorldToView{};   // frozen by m_bFreezeCullingCamera
+    // Scene.h:60-66, what DeferredLightingRenderer reads.  m_Eye: the point m_WorldToView maps to the view-space origin,
+    // -t * R^T of the rigid transform [R | t] (the camera arrives as a matrix here, not as eye + orientation);
+    // m_ClipToWorld: the inverse of m_WorldToView * m_ViewToClip, in double precision, rounded once (MathUtilities.h).
+    float m_Eye[3] = { 0.0f, 0.0f, 0.0f };
+    Matrix m_ClipToWorld{};
 
     // The reference derives m_WorldToView from eye/orientation with DirectXMath (absent here) in
     // View::Update; this build takes the camera matrix from the application instead.
@@ -92,7 +97,13 @@ public:
     // GBufferA (trhost_set_gbuffer; implies m_bVisibilityBuffer): "basepass_PS_Main_GBuffer" resolves GBufferA and
     // GBufferMotion in one dispatch in the place of "basepass_PS_Main_motion".  Needs LoadMaterials.
     bool m_bGBuffer = false;
-    uint32_t m_DebugViewMode = 0;                    // Scene.h: feeds BasePassConstants::m_DebugMode (BasePassRenderers.cpp:455)
+    uint32_t m_DebugViewMode = 0;                    // Scene.h: feeds BasePassConstants::m_DebugMode (BasePassRenderers.cpp:455) and DeferredLightingConsts::m_DebugMode
+    // Deferred lighting (trhost_set_deferred_lighting; implies m_bGBuffer): DeferredLightingRenderer runs after GBufferRenderer,
+    // "deferredlighting_PS_Main" or, with m_DebugViewMode != 0, "deferredlighting_PS_Main_Debug", into its LightingOutput.
+    bool m_bDeferredLighting = false;
+    float m_DirLightVec[3] = { 0.0f, -1.0f, 0.0f };  // Scene.h:134-136: used as given (the reference derives it from two angles)
+    float m_DirLightStrength = 1.0f;
+    nvrhi::TextureHandle m_ShadowMaskTexture;        // R8_UNORM at render resolution, or null: the pass reads 1.0 (the reference's WhiteTexture)
     // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.
     void LoadMaterials(const void* materials, uint32_t numMaterials);
     // `<scene>_CachedData.bin` version 3 (SceneLoading.cpp:57-79 layout, :706-781 LoadCachedData): meshes, meshlets and

@@ -40,6 +40,13 @@ nvrhi::TextureHandle GetVisibilityBuffer();
 nvrhi::TextureHandle GetMotionBuffer();
 // GBufferRenderer's GBufferA (RGBA32_UINT); null until a frame ran with the G-buffer on.
 nvrhi::TextureHandle GetGBufferA();
+// Creates GBufferRenderer's per-pixel targets that the scene's flags ask for and that do not exist yet (Setup phase only).
+void CreateGBufferPixelTargets();
+// DeferredLightingRenderer's LightingOutput (R11G11B10_FLOAT) and the DeferredLightingConsts of the last recorded frame; null /
+// false until a frame ran with deferred lighting on.
+nvrhi::TextureHandle GetLightingOutput();
+bool GetLastDeferredLightingConsts(void* out112);
+void ReleaseDeferredLightingOutputs();
 // the base pass's pipeline statistics: the value its frame N showed (the query of frame N - 2) and the last executed frame's (waits)
 void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest);
 

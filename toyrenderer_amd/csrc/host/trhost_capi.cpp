@@ -8,6 +8,7 @@
 
 #include "../../../include/trhost.h"
 #include "Graphic.h"
+#include "GraphicConstants.h"
 #include "RenderGraph.h"
 #include "Scene.h"
 #include "VisibilityOutputs.h"
@@ -56,6 +57,7 @@ void trhost_shutdown(void)
         ShardExchangeDestroy();
         ReleaseVisibilityPassBuffers();
         ReleaseGIProbeCullBuffers();
+        ReleaseDeferredLightingOutputs();
         g_Graphic.Shutdown();
     });
     s_Initialized = false;
@@ -140,7 +142,70 @@ int trhost_set_gbuffer(int enable)
 
 int trhost_set_debug_view_mode(uint32_t mode)
 {
-    return guarded([&] { check(g_Scene); g_Scene->m_DebugViewMode = mode; });
+    return guarded([&] {
+        check(g_Scene);
+        if (mode == interop::kDeferredLightingDebugMode_Ambient && g_Scene->m_bDeferredLighting)
+            throw nvrhi::Error("trhost_set_debug_view_mode: mode 10 (Ambient) needs the DDGI volume, which deferredlighting_PS_Main_Debug does not have");
+        g_Scene->m_DebugViewMode = mode;
+    });
+}
+
+int trhost_set_deferred_lighting(int enable)
+{
+    return guarded([&] {
+        check(!enable || g_Graphic.m_GlobalVertexBuffer);      // trhost_load_geometry first
+        if (enable && !g_Graphic.m_GlobalMaterialDataBuffer) throw nvrhi::Error("trhost_set_deferred_lighting: no materials (trhost_load_materials first)");
+        if (enable && g_Graphic.m_MaxMeshletGroups > (1u << 18))
+            throw nvrhi::Error("trhost_set_deferred_lighting: max_meshlet_groups above 2^18 (list positions must stay below 2^23)");
+        if (enable && g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient)
+            throw nvrhi::Error("trhost_set_deferred_lighting: debug view mode 10 (Ambient) needs the DDGI volume, which deferredlighting_PS_Main_Debug does not have");
+        g_Scene->m_bDeferredLighting = enable != 0;
+        if (enable) { g_Scene->m_bGBuffer = true; g_Scene->m_bVisibilityBuffer = true; g_Scene->m_bRasterDepth = true; }   // implies the G-buffer
+    });
+}
+
+int trhost_set_directional_light(const float vec[3], float strength)
+{
+    return guarded([&] {
+        check(g_Scene && vec);
+        memcpy(g_Scene->m_DirLightVec, vec, sizeof g_Scene->m_DirLightVec);
+        g_Scene->m_DirLightStrength = strength;
+    });
+}
+
+int trhost_upload_shadow_mask(const uint8_t* texels, uint64_t bytes)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!texels) { g_Scene->m_ShadowMaskTexture = nullptr; return; }      // white
+        if (!g_Scene->m_ShadowMaskTexture) {
+            nvrhi::TextureDesc desc;
+            desc.width = g_Graphic.m_RenderResolution.x;
+            desc.height = g_Graphic.m_RenderResolution.y;
+            desc.format = GraphicConstants::kShadowMaskFormat;
+            desc.debugName = "Shadow Mask";
+            g_Scene->m_ShadowMaskTexture = g_Graphic.m_NVRHIDevice->createTexture(desc);
+        }
+        nvrhi::throwIfFailed(trhip_texture_upload(g_Scene->m_ShadowMaskTexture->native(), 0, texels, bytes), "trhost_upload_shadow_mask");
+    });
+}
+
+int trhost_download_lighting_output(uint32_t* words, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetLightingOutput();
+        if (!t) throw nvrhi::Error("trhost_download_lighting_output: no frame ran with deferred lighting on");
+        check(words);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, words, bytes), "trhost_download_lighting_output");
+    });
+}
+
+int trhost_get_deferred_lighting_consts(void* out112)
+{
+    return guarded([&] {
+        check(out112);
+        if (!GetLastDeferredLightingConsts(out112)) throw nvrhi::Error("trhost_get_deferred_lighting_consts: no frame ran with deferred lighting on");
+    });
 }
 
 int trhost_download_gbuffer_a(uint32_t* words, uint64_t bytes)

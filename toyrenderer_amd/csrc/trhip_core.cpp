@@ -3,8 +3,10 @@
 // reference makes on the visibility path.  Kernels live in k_*.hip and register themselves by
 // the reference's shader-name strings.
 #include "trhip_internal.h"
+#include "r11g11b10.hip.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 
 #include <algorithm>
@@ -478,15 +480,15 @@ int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_te
     if (!dev || !d || !out) return fail(TRHIP_ERR_INVALID, "texture_create: null argument");
     if (d->width == 0 || d->height == 0 || d->mipLevels == 0 || d->mipLevels > 16)
         return fail(TRHIP_ERR_INVALID, "texture_create: bad dimensions %ux%u mips %u", d->width, d->height, d->mipLevels);
-    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && d->format != TRHIP_FORMAT_RG32_UINT && d->format != TRHIP_FORMAT_RG16_FLOAT &&
-        d->format != TRHIP_FORMAT_RGBA32_UINT)
+    if (d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT)
         return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u", d->format);
-    if ((d->format == TRHIP_FORMAT_RG32_UINT || d->format == TRHIP_FORMAT_RG16_FLOAT || d->format == TRHIP_FORMAT_RGBA32_UINT) && d->mipLevels != 1)
-        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT textures have one mip, got %u", d->mipLevels);
+    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && d->mipLevels != 1)
+        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT textures have one mip, got %u", d->mipLevels);
     auto t = std::make_unique<trhip_texture_t>();
     t->dev = dev;
     t->width = d->width; t->height = d->height; t->mips = d->mipLevels; t->format = d->format;
-    t->texelBytes = d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT ? 8 : d->format == TRHIP_FORMAT_RGBA32_UINT ? 16 : 4;
+    t->texelBytes = d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT ? 8 : d->format == TRHIP_FORMAT_RGBA32_UINT ? 16 :
+                    d->format == TRHIP_FORMAT_R8_UNORM || d->format == TRHIP_FORMAT_R8_UINT ? 1 : 4;
     t->isUAV = d->isUAV != 0; t->isVirtual = d->isVirtual != 0;
     t->name = d->debugName ? d->debugName : "";
     uint64_t off = 0;
@@ -699,15 +701,22 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
-    if (tex->format == TRHIP_FORMAT_RG32_UINT || tex->format == TRHIP_FORMAT_RGBA32_UINT)
-        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): RG32_UINT / RGBA32_UINT are cleared with clear_texture_u32", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_RG32_UINT || tex->format == TRHIP_FORMAT_RGBA32_UINT || tex->format == TRHIP_FORMAT_R8_UINT)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): RG32_UINT / RGBA32_UINT / R8_UINT are cleared with clear_texture_u32", tex->name.c_str());
     void* p = tex->ptr;
     cl->hold(tex, true);
-    if (tex->format == TRHIP_FORMAT_R32_FLOAT) {
+    if (tex->format == TRHIP_FORMAT_R32_FLOAT || tex->format == TRHIP_FORMAT_R11G11B10_FLOAT) {
         uint32_t bits;
         memcpy(&bits, &value, 4);
+        if (tex->format == TRHIP_FORMAT_R11G11B10_FLOAT) bits = trhip::packR11G11B10(value, value, value);
         size_t n = (size_t)(tex->totalBytes / 4);
         cl->ops.push_back({ "", [p, n, bits](hipStream_t s) { TRHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)bits, n, s)); return (int)TRHIP_OK; } });
+        cl->ops.back().kind = "clear_texture";
+    } else if (tex->format == TRHIP_FORMAT_R8_UNORM) {
+        const float sat = value != value ? 0.0f : value < 0.0f ? 0.0f : value > 1.0f ? 1.0f : value;
+        const int byte = (int)std::nearbyint(sat * 255.0f);       // D3D float -> unorm: round to nearest
+        size_t n = (size_t)tex->totalBytes;
+        cl->ops.push_back({ "", [p, n, byte](hipStream_t s) { TRHIP_HIP(hipMemsetAsync(p, byte, n, s)); return (int)TRHIP_OK; } });
         cl->ops.back().kind = "clear_texture";
     } else {
         _Float16 h = (_Float16)value; // round-to-nearest-even
@@ -721,16 +730,23 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
 }
 
 // nvrhi clearTextureUInt: the value goes into every 32-bit channel word (RG32_UINT: both words of each texel,
-// RGBA32_UINT: all four).
+// RGBA32_UINT: all four); R8_UINT takes its low byte.
 int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t value)
 {
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
-    if (tex->format != TRHIP_FORMAT_RG32_UINT && tex->format != TRHIP_FORMAT_RGBA32_UINT)
-        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): needs an RG32_UINT or RGBA32_UINT texture", tex->name.c_str());
+    if (tex->format != TRHIP_FORMAT_RG32_UINT && tex->format != TRHIP_FORMAT_RGBA32_UINT && tex->format != TRHIP_FORMAT_R8_UINT)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): needs an RG32_UINT, RGBA32_UINT or R8_UINT texture", tex->name.c_str());
     void* p = tex->ptr;
     cl->hold(tex, true);
+    if (tex->format == TRHIP_FORMAT_R8_UINT) {
+        const int byte = (int)(value & 0xFFu);
+        const size_t bytes = (size_t)tex->totalBytes;
+        cl->ops.push_back({ "", [p, bytes, byte](hipStream_t s) { TRHIP_HIP(hipMemsetAsync(p, byte, bytes, s)); return (int)TRHIP_OK; } });
+        cl->ops.back().kind = "clear_texture";
+        return TRHIP_OK;
+    }
     const size_t n = (size_t)(tex->totalBytes / 4);
     cl->ops.push_back({ "", [p, n, value](hipStream_t s) { TRHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)value, n, s)); return (int)TRHIP_OK; } });
     cl->ops.back().kind = "clear_texture";

@@ -81,7 +81,8 @@ class FrameDriver:
     def __init__(self, dev: rhi.Device, scene: GpuScene, view, *, record_capacity: int, list_capacity: int | None = None,
                  culling_flags: int = 7, force_mesh_lod: int = -1, freeze_culling_camera: bool = False, alloc=None,
                  shard_late=None, raster_depth: bool = False, visibility: bool = False, gbuffer: bool = False,
-                 debug_mode: int = 0):
+                 debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
+                 shadow_mask=None, ssao=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -90,13 +91,26 @@ class FrameDriver:
         and resolve self.motion (RG16_FLOAT, "basepass_PS_Main_motion") after the last slot; m_PrevWorldToClip is set.
         gbuffer: implies visibility; one "basepass_PS_Main_GBuffer" dispatch in the place of the motion resolve writes
         self.gbufferA (RGBA32_UINT) and self.motion.  Needs GpuScene.set_materials().  debug_mode: m_DebugMode (2, 3 and 12
-        fill GBufferA's debug byte)."""
+        fill GBufferA's debug byte).
+        lighting: implies gbuffer; one "deferredlighting_PS_Main" dispatch ("deferredlighting_PS_Main_Debug" when debug_mode != 0)
+        after the G-buffer resolve writes self.lighting_output (R11G11B10_FLOAT), cleared to 0 with the other targets.
+        dir_light = ((x, y, z), strength): m_DirectionalLightVector as given and m_DirectionalLightStrength; camera_origin:
+        m_CameraOrigin (the eye of view.worldToView; a View does not carry it); shadow_mask / ssao: rhi.Texture (R8_UNORM /
+        R8_UINT, render resolution) or None = unbound (1.0 / 255).  self.lighting_consts holds the 112 bytes of the last record()."""
+        gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
         if visibility and shard_late is not None:
-            raise ValueError(("G-buffer" if gbuffer else "visibility buffer") + " with a shard exchange: list positions are per rank, not global")
+            raise ValueError(("deferred lighting" if lighting else "G-buffer" if gbuffer else "visibility buffer") + " with a shard exchange: list positions are per rank, not global")
         if gbuffer and scene.materials is None:
-            raise ValueError("gbuffer=True needs GpuScene.set_materials()")
+            raise ValueError(("lighting=True" if lighting else "gbuffer=True") + " needs GpuScene.set_materials()")
+        if lighting and int(debug_mode) == I.kDeferredLightingDebugMode_Ambient:
+            raise ValueError("debug_mode 10 (Ambient) needs the DDGI volume, which is not built")
         self.gbuffer_on = bool(gbuffer)
+        self.lighting_on = bool(lighting)
+        self.dir_light = (tuple(float(x) for x in dir_light[0]), float(dir_light[1]))
+        self.camera_origin = tuple(float(x) for x in camera_origin)
+        self.shadow_mask, self.ssao = shadow_mask, ssao
+        self.lighting_consts = None
         self.debug_mode = int(debug_mode)
         self.visibility_on = bool(visibility)
         self.raster_depth = bool(raster_depth) or self.visibility_on       # depth = the visible meshlets rasterised ("basepass_MS_Main_depth"), cleared per frame
@@ -118,7 +132,9 @@ class FrameDriver:
         init = dev.create_command_list()
         init.open(); init.clear_texture_f32(self.hzb, 0.0); init.clear_texture_f32(self.depth, 0.0); init.close()
         dev.execute(init); dev.wait_idle(); init.release()
-        self.visibility = self.motion = self.gbufferA = None
+        self.visibility = self.motion = self.gbufferA = self.lighting_output = None
+        if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
+            self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
             self.gbufferA = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA32_UINT, "GBufferA")
         if self.visibility_on:                       # GBufferRenderer's visibility buffer + GBufferMotion, render resolution
@@ -263,6 +279,30 @@ class FrameDriver:
             return
         cl.dispatch("basepass_PS_Main_motion", b + [TEX_UAV(0, self.motion, 0)], ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
 
+    # ---- DeferredLightingRenderer::Render (DeferredLightingRenderer.cpp:59-120) ---------------------
+    def _lighting_consts(self) -> np.ndarray:
+        v = self.view
+        k = np.zeros(1, I.DeferredLightingConsts)
+        k["m_ClipToWorld"] = I.clip_to_world(v.worldToView, v.viewToClip)
+        k["m_CameraOrigin"] = self.camera_origin
+        k["m_SSAOEnabled"] = int(self.ssao is not None)
+        k["m_DebugMode"] = self.debug_mode
+        k["m_DirectionalLightVector"] = self.dir_light[0]
+        k["m_DirectionalLightStrength"] = self.dir_light[1]
+        k["m_LightingOutputResolution"] = (v.renderW, v.renderH)
+        return k
+
+    def _deferred_lighting(self, cl):
+        v = self.view
+        self.lighting_consts = self._lighting_consts()
+        cb = cl.constant_buffer(self.lighting_consts, "DeferredLightingConsts")
+        b = [CB(0, cb), TEX_SRV(0, self.gbufferA), TEX_SRV(1, self.motion), TEX_SRV(2, self.depth), TEX_UAV(0, self.lighting_output, 0), SAMPLER(0), SAMPLER(1)]
+        if self.ssao is not None:
+            b.append(TEX_SRV(3, self.ssao))
+        if self.shadow_mask is not None:
+            b.append(TEX_SRV(4, self.shadow_mask))
+        cl.dispatch("deferredlighting_PS_Main_Debug" if self.debug_mode != 0 else "deferredlighting_PS_Main", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
+
     # ---- BasePassRenderer::GenerateHZB (:505-542) + SPD::Execute (FFXHelpers.cpp:36-115) --------
     def _generate_hzb(self, cl):
         if self.freeze:
@@ -299,6 +339,8 @@ class FrameDriver:
             cl.clear_texture_f32(self.motion, 0.0)
         if self.gbuffer_on:
             cl.clear_texture_u32(self.gbufferA, 0)
+        if self.lighting_on:
+            cl.clear_texture_f32(self.lighting_output, 0.0)                              # the reference's per-frame clear (Scene.cpp:42-70)
 
         def do(slot, late, am):
             self.ran[slot] = self._gpu_culling(cl, slot, late, am)
@@ -319,6 +361,8 @@ class FrameDriver:
                 self._resolve_motion(cl)
         if query is not None:
             cl.end_pipeline_stats(query)
+        if self.lighting_on:                                                             # the next renderer after GBufferRenderer
+            self._deferred_lighting(cl)
         cl.close()
         return cl
 
@@ -353,6 +397,6 @@ class FrameDriver:
         for b in (self.lateArgs, self.lateCount, self.lateIds, self.spdAtomic, self.dummy, *(self.shardInfo or ())):
             b.release()
         self.hzb.release(); self.depth.release()
-        for t in (self.visibility, self.motion, self.gbufferA):
+        for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output):
             if t is not None:
                 t.release()

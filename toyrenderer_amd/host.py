@@ -28,6 +28,8 @@ HOST_SYMBOLS = [
     "trhost_load_materials", "trhost_set_gbuffer", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
+    "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
+    "trhost_get_deferred_lighting_consts",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # trhost_allgather_fn
@@ -89,6 +91,11 @@ def load() -> C.CDLL:
     L.trhost_set_gbuffer.argtypes = [C.c_int]
     L.trhost_set_debug_view_mode.argtypes = [u32]
     L.trhost_download_gbuffer_a.argtypes = [vp, u64]
+    L.trhost_set_deferred_lighting.argtypes = [C.c_int]
+    L.trhost_set_directional_light.argtypes = [vp, C.c_float]
+    L.trhost_upload_shadow_mask.argtypes = [vp, u64]
+    L.trhost_download_lighting_output.argtypes = [vp, u64]
+    L.trhost_get_deferred_lighting_consts.argtypes = [vp]
     L.trhost_upload_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_download_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_hzb_info.argtypes = [C.POINTER(u32)] * 3
@@ -264,6 +271,35 @@ class Renderer:
         g = np.empty((self.render[1], self.render[0], 4), np.uint32)
         _check(load().trhost_download_gbuffer_a(g.ctypes.data, g.nbytes))
         return g
+
+    def set_deferred_lighting(self, on: bool = True):
+        """DeferredLightingRenderer after GBufferRenderer (implies the G-buffer; include/trhost.h)."""
+        _check(load().trhost_set_deferred_lighting(int(on)))
+
+    def set_directional_light(self, vec, strength: float):
+        v = np.ascontiguousarray(vec, np.float32).reshape(3)
+        _check(load().trhost_set_directional_light(v.ctypes.data, float(strength)))
+
+    def upload_shadow_mask(self, mask):
+        """uint8 [H, W] R8_UNORM shadow mask at render resolution; None = white."""
+        if mask is None:
+            _check(load().trhost_upload_shadow_mask(None, 0))
+            return
+        m = np.ascontiguousarray(mask, np.uint8)
+        _check(load().trhost_upload_shadow_mask(m.ctypes.data, m.nbytes))
+
+    def download_lighting_output(self) -> np.ndarray:
+        """The last frame's LightingOutput: uint32 [H, W] R11G11B10_FLOAT words."""
+        self.wait_idle()
+        w = np.empty((self.render[1], self.render[0]), np.uint32)
+        _check(load().trhost_download_lighting_output(w.ctypes.data, w.nbytes))
+        return w
+
+    def deferred_lighting_consts(self) -> np.ndarray:
+        """The DeferredLightingConsts (1 element) the last frame uploaded."""
+        k = np.zeros(1, I.DeferredLightingConsts)
+        _check(load().trhost_get_deferred_lighting_consts(k.ctypes.data))
+        return k
 
     def download_depth(self) -> np.ndarray:
         self.wait_idle()

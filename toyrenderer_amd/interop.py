@@ -23,6 +23,7 @@ kMaterialFlagAnyTexture = 0xF
 kDeferredLightingDebugMode_ColorizeInstances = 2            # ShaderInterop.h:27-37: the views that write GBufferA's debug byte
 kDeferredLightingDebugMode_ColorizeMeshlets = 3
 kDeferredLightingDebugMode_MeshLOD = 12
+kDeferredLightingDebugMode_Ambient = 10                     # needs the DDGI volume: refused by the lighting pass
 
 BasePassInstanceConstants = np.dtype([
     ("m_WorldMatrix", np.float32, (4, 4)), ("m_PrevWorldMatrix", np.float32, (4, 4)),
@@ -69,12 +70,16 @@ MaterialData = np.dtype([                                                       
     ("m_AlbedoTexture", TextureData), ("m_NormalTexture", TextureData), ("m_MetallicRoughnessTexture", TextureData),
     ("m_EmissiveTexture", TextureData), ("m_MaterialFlags", np.uint32), ("m_ConstRoughness", np.float32), ("m_ConstMetallic", np.float32)])
 UpdateInstanceConstsPassConstants = np.dtype([("m_NumInstances", np.uint32)])
+DeferredLightingConsts = np.dtype([                                                                                        # ShaderInterop.h:86-98
+    ("m_ClipToWorld", np.float32, (4, 4)), ("m_CameraOrigin", np.float32, (3,)), ("m_SSAOEnabled", np.uint32), ("m_DebugMode", np.uint32),
+    ("m_DirectionalLightVector", np.float32, (3,)), ("m_DirectionalLightStrength", np.float32), ("m_LightingOutputResolution", np.uint32, (2,)),
+    ("m_bRTDDGIEnabled", np.uint32)])
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
     "MeshletAmplificationData": 12, "DispatchIndirectArguments": 12, "GPUCullingPassConstants": 180,
     "BasePassConstants": 256, "MinMaxDownsampleConsts": 12, "NodeLocalTransform": 48,
-    "TextureData": 20, "MaterialData": 124,
+    "TextureData": 20, "MaterialData": 124, "DeferredLightingConsts": 112,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)
@@ -97,6 +102,31 @@ def world_to_clip(world_to_view, view_to_clip) -> np.ndarray:
             for k_ in (1, 2, 3):
                 acc = np.float32(acc + np.float32(a[i, k_] * b[k_, j]))
             out[i, j] = acc
+    return out
+
+
+def clip_to_world(world_to_view, view_to_clip) -> np.ndarray:
+    """m_ClipToWorld: the inverse of WorldToView * ViewToClip in float64, every element rounded once to float32 (the reference
+    uses DirectXMath's float32 inverse, absent here).  The operation order is part of the definition and is the one of
+    csrc/host/MathUtilities.cpp InverseOfProduct, so that both host sides hand the GPU the same 16 numbers: the product summed
+    left to right, cofactors as 3x3 determinants, the determinant along row 0, cofactor / determinant + 0.0.  A camera's
+    structural zeros come out as exact zeros (a LAPACK inverse leaves 1e-17 there)."""
+    a = np.asarray(world_to_view, np.float32).reshape(4, 4).astype(np.float64)
+    b = np.asarray(view_to_clip, np.float32).reshape(4, 4).astype(np.float64)
+    m = [[((a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j]) + a[i, 3] * b[3, j] for j in range(4)] for i in range(4)]
+    cof = [[None] * 4 for _ in range(4)]
+    for i in range(4):
+        for j in range(4):
+            r, c = [k for k in range(4) if k != i], [k for k in range(4) if k != j]
+            e = lambda y, x: m[r[y]][c[x]]                                                          # noqa: E731
+            d = (e(0, 0) * (e(1, 1) * e(2, 2) - e(1, 2) * e(2, 1)) - e(0, 1) * (e(1, 0) * e(2, 2) - e(1, 2) * e(2, 0))) + e(0, 2) * (e(1, 0) * e(2, 1) - e(1, 1) * e(2, 0))
+            cof[i][j] = -d if (i + j) & 1 else d
+    det = ((m[0][0] * cof[0][0] + m[0][1] * cof[0][1]) + m[0][2] * cof[0][2]) + m[0][3] * cof[0][3]
+    out = np.zeros((4, 4), np.float32)
+    with np.errstate(all="ignore"):
+        for i in range(4):
+            for j in range(4):
+                out[j, i] = np.float32(cof[i][j] / det + np.float64(0.0))
     return out
 
 

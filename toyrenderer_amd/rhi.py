@@ -18,6 +18,9 @@ FORMAT_R32_FLOAT = 2
 FORMAT_RG32_UINT = 3      # visibility buffer: one u64 per texel
 FORMAT_RG16_FLOAT = 4     # motion target: two fp16 per texel
 FORMAT_RGBA32_UINT = 5    # GBufferA: four u32 per texel (x, y, z, w)
+FORMAT_R11G11B10_FLOAT = 6  # LightingOutput: one u32 per texel, R bits 0-10, G 11-21, B 22-31
+FORMAT_R8_UNORM = 7       # shadow mask: one byte per texel
+FORMAT_R8_UINT = 8        # SSAO texture: one byte per texel
 
 BIND_CONSTANT_BUFFER, BIND_PUSH_CONSTANTS, BIND_STRUCTURED_SRV, BIND_STRUCTURED_UAV, BIND_TEXTURE_SRV, BIND_TEXTURE_UAV, BIND_SAMPLER = range(7)
 
@@ -233,7 +236,8 @@ class Texture:
         return max(self.w >> k, 1), max(self.hgt >> k, 1)
 
     def _dtype(self):
-        return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32}.get(self.format, np.float32)
+        return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32,
+                FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8}.get(self.format, np.float32)
 
     def _shape(self, mw: int, mh: int):
         return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw, 4) if self.format == FORMAT_RGBA32_UINT else (mh, mw)
