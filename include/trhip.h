@@ -48,9 +48,12 @@ enum {
  * texel, little-endian words x, y, z, w) have one mip only.  So do the deferred lighting pass's formats: R11G11B10_FLOAT
  * (LightingOutput, GraphicConstants::kLightingOutputFormat: 4 bytes per texel, R in bits 0-10, G in bits 11-21, B in bits 22-31;
  * unsigned floats of 5 exponent bits with 6, 6 and 5 mantissa bits), R8_UNORM (the shadow mask) and R8_UINT (the SSAO texture),
- * one byte per texel each. */
+ * one byte per texel each.  RGBA8_UNORM (the back buffer, GraphicRHI.cpp:214: 4 bytes per texel, R in the low byte, one mip) is
+ * created, uploaded, downloaded and copied; both clears refuse it, because "postprocess_PS_PostProcess" writes every texel.
+ * Its value is 10, not 9: 9 is not a format and stays refused with "unsupported format". */
 enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4,
-       TRHIP_FORMAT_RGBA32_UINT = 5, TRHIP_FORMAT_R11G11B10_FLOAT = 6, TRHIP_FORMAT_R8_UNORM = 7, TRHIP_FORMAT_R8_UINT = 8 };
+       TRHIP_FORMAT_RGBA32_UINT = 5, TRHIP_FORMAT_R11G11B10_FLOAT = 6, TRHIP_FORMAT_R8_UNORM = 7, TRHIP_FORMAT_R8_UINT = 8,
+       TRHIP_FORMAT_RGBA8_UNORM = 10 };
 
 /* ---- error / introspection ---------------------------------------------------------------- */
 const char* trhip_last_error(void);          /* thread-local text of the last failure          */
@@ -85,7 +88,17 @@ uint32_t    trhip_abi_version(void);
  * reads 255), t4 R8_UNORM shadow mask (optional: unbound reads 1.0), u0 (texture) R11G11B10_FLOAT LightingOutput; every
  * texture of the size m_LightingOutputResolution; samplers and bindings at t5..t8 are accepted and ignored.  A pixel is
  * written iff its depth is > 0.0f (the stand-in for the reference's stencil test on the opaque bit); every other texel of u0
- * keeps its value.  The arithmetic convention is stated in csrc/k_deferredlighting.hip. */
+ * keeps its value.  The arithmetic convention is stated in csrc/k_deferredlighting.hip.
+ * "adaptluminance_CS_GenerateLuminanceHistogram" (adaptluminance.hlsl, AdaptLuminanceRenderer.cpp): a direct dispatch of
+ * [numthreads(16, 16, 1)] groups covering m_SrcColorDims; push constants GenerateLuminanceHistogramParameters (16 bytes), t0
+ * (texture) the R11G11B10_FLOAT colour, u0 a structured UAV of at least 256 uint32.  It ADDS to u0: the caller clears it.
+ * "adaptluminance_CS_AdaptExposure": a dispatch of (1, 1, 1); push constants AdaptExposureParameters (20 bytes), t0 the
+ * histogram, u0 the one-float luminance buffer (read and written), u1 (texture) the 1 x 1 R32_FLOAT exposure texture.
+ * "postprocess_PS_PostProcess" (postprocess.hlsl, PostProcessRenderer.cpp): a direct dispatch of [numthreads(8, 8, 1)] groups
+ * over m_OutputDims; b0 or push constants PostProcessParameters (24 bytes), t0 (texture) the R11G11B10_FLOAT colour, t1 the
+ * luminance buffer (required only when m_ManualExposure == 0), t2 (texture) R11G11B10_FLOAT bloom (optional: unbound reads
+ * (0, 0, 0)), u0 (texture) the RGBA8_UNORM target; samplers are accepted and ignored.  Every texel is written, alpha 255.
+ * The arithmetic convention of the three is stated in csrc/k_postprocess.hip. */
 uint32_t    trhip_shader_count(void);
 const char* trhip_shader_name(uint32_t index);
 int         trhip_shader_exists(const char* name);

@@ -100,6 +100,28 @@ int  trhost_set_directional_light(const float vec[3], float strength);
 int  trhost_upload_shadow_mask(const uint8_t* texels, uint64_t bytes);
 int  trhost_download_lighting_output(uint32_t* words, uint64_t bytes);
 int  trhost_get_deferred_lighting_consts(void* out112);
+/* Auto exposure and tone mapping (AdaptLuminanceRenderer.cpp, PostProcessRenderer.cpp; implies deferred lighting, same refusals):
+ * after DeferredLightingRenderer the frame clears the luminance histogram and runs "adaptluminance_CS_GenerateLuminanceHistogram"
+ * and "adaptluminance_CS_AdaptExposure" (with a manual exposure > 0: one write of it into the luminance buffer instead), then
+ * "postprocess_PS_PostProcess" into the back buffer (RGBA8_UNORM at render resolution, 4 bytes per texel, R in the low byte).
+ * trhost_set_exposure: Scene::m_ManualExposureOverride and m_MiddleGray (defaults 0, 0.18).  trhost_set_auto_exposure: the
+ * luminance limits and the speed per millisecond (defaults 0.004, 12, 0.0025); trhost_set_frame_time_ms: the mirror of
+ * Engine::m_CPUCappedFrameTimeMs (default 16; there is no clock here); m_AdaptationSpeed = clamp(speed * ms, 0, 1) is formed in the
+ * renderer.  trhost_upload_bloom: the R11G11B10_FLOAT bloom texture at render resolution and its strength; NULL switches bloom
+ * off.  trhost_get_scene_luminance waits for the device and reads the adapted luminance and the exposure texel as they are now
+ * (the reference's two-frame-late read-backs are not modelled); trhost_reset_exposure sets both back to 1.0.
+ * trhost_get_post_process_consts copies the parameter structs of the last frame: 16 bytes GenerateLuminanceHistogramParameters,
+ * 20 bytes AdaptExposureParameters (both as of the last frame that adapted; *adapt_ran tells whether the last one did) and 24
+ * bytes PostProcessParameters; any pointer may be NULL. */
+int  trhost_set_post_process(int enable);
+int  trhost_set_exposure(float manual, float middle_gray);
+int  trhost_set_auto_exposure(float min_lum, float max_lum, float speed_per_ms);
+int  trhost_set_frame_time_ms(float ms);
+int  trhost_upload_bloom(const uint32_t* words, uint64_t bytes, float strength);
+int  trhost_download_back_buffer(uint32_t* words, uint64_t bytes);
+int  trhost_get_scene_luminance(float* luminance, float* exposure);
+int  trhost_reset_exposure(void);
+int  trhost_get_post_process_consts(void* histogram16, void* adapt20, void* post24, int* adapt_ran);
 int  trhost_download_depth(float* depth, uint64_t bytes);
 int  trhost_upload_hzb_mip(uint32_t mip, const uint16_t* texels, uint64_t bytes);
 int  trhost_download_hzb_mip(uint32_t mip, uint16_t* texels, uint64_t bytes);

@@ -1,0 +1,481 @@
+"""tests/postprocess_ref.c, the reference the GPU tests compare "adaptluminance_CS_GenerateLuminanceHistogram",
+"adaptluminance_CS_AdaptExposure" and "postprocess_PS_PostProcess" with word for word, pinned by means other than itself: the
+format's definition in exact rationals, float64 for the transcendental functions and for both chains (restated here from the
+HLSL in numpy float64), exact integers for the histogram sum, and a g++ probe for the layouts.  No GPU."""
+import math
+import os
+import subprocess
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+from tests import lighting_ref as LR
+from tests import postprocess_ref as PR
+from toyrenderer_amd import interop as I
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+U = 2.0 ** -24                                                   # binary32 unit roundoff
+
+
+@pytest.fixture(scope="module")
+def pr(tmp_path_factory):
+    return PR.load(tmp_path_factory.mktemp("postprocess_ref"))
+
+
+@pytest.fixture(scope="module")
+def lr(tmp_path_factory):
+    return LR.load(tmp_path_factory.mktemp("lighting_ref_for_post"))
+
+
+# ---- the load ---------------------------------------------------------------------------------------------------------------
+def _decode(code: int, m: int):
+    """The format's definition: None = NaN."""
+    e, f = code >> m, code & ((1 << m) - 1)
+    if e == 31:
+        return math.inf if f == 0 else None
+    if e == 0:
+        return Fraction(f, 1 << m) * Fraction(1, 1 << 14)
+    return (1 + Fraction(f, 1 << m)) * (Fraction(2) ** (e - 15))
+
+
+@pytest.mark.parametrize("m", [6, 5])
+def test_decode_meets_the_formats_definition_for_every_code(pr, lr, m):
+    codes = np.arange(32 << m, dtype=np.uint32)
+    got = PR.unpack_ufloat(pr, codes, m)
+    for c, g in zip(codes.tolist(), got.tolist()):
+        want = _decode(c, m)
+        if want is None:
+            assert math.isnan(g), c
+        elif want == math.inf:
+            assert g == math.inf, c
+        else:
+            assert Fraction(g) == want, (c, g)
+    finite = 31 << m
+    assert np.array_equal(LR.pack_ufloat(lr, got[:finite + 1], m), codes[:finite + 1]), "pack(decode(c)) == c for every finite code and +inf"
+    assert np.all(LR.pack_ufloat(lr, got[finite + 1:], m) == (32 << m) - 1), "a NaN code packs to the NaN pattern"
+    assert np.array_equal(got[finite + 1:].view(np.uint32), np.uint32(0x7F800000) | (codes[finite + 1:] & np.uint32((1 << m) - 1)) << np.uint32(23 - m))
+
+
+def test_constants_are_the_stated_words(pr):
+    k = PR.constants(pr)
+    want = dict(lumR="0x1.b38cdap-3", lumG="0x1.6e2974p-1", lumB="0x1.279aaep-4", startCompression="0x1.851eb8p-1", d="0x1.eb851ep-3", dd="0x1.d7dbf4p-5",
+                desaturation="0x1.333334p-3", invGamma="0x1.d1745cp-2")
+    for n, h in want.items():
+        assert float(k[n]) == float.fromhex(h), (n, float(k[n]).hex())
+    assert k["lumR"] == F(0.212671) and k["lumG"] == F(0.715160) and k["lumB"] == F(0.072169)
+    assert k["startCompression"] == F(0.8 - 0.04) and k["d"] == F(1.0 - (0.8 - 0.04)) and k["dd"] == k["d"] * k["d"]
+    assert k["d"] != F(1.0) - k["startCompression"], "the folded literal is not the binary32 difference: the rule matters"
+    assert k["invGamma"] == F(1.0) / F(2.2)
+
+
+# ---- log2, exp2, pow --------------------------------------------------------------------------------------------------------
+def _report(name, err, unit=2.0 ** -25):
+    print(f"{name}: largest error {err:.4e} = {err / unit:.4f} * 2^-25")
+
+
+def test_software_log2_is_within_its_derived_bound(pr):
+    """10^6 seeded inputs log-uniform over [0.005, 3 * 65024], the ends, every power of two in it, +inf, and the pow side's
+    domain (0, 1] down to the subnormals: |pr_log2(x) - log2 x| <= PR_LOG2_BOUND + 2^-24 |pr_log2(x)|.  float64 log2 stands for
+    the truth: its own error is 2^-53 relative."""
+    rng = np.random.default_rng(31)
+    lo, hi = F(0.005), F(3.0 * 65024.0)
+    pows = np.exp2(np.arange(-7, 18)).astype(F)
+    x = np.concatenate([np.exp2(rng.uniform(math.log2(0.005), math.log2(3 * 65024.0), 1_000_000)).astype(F), [lo, hi], pows, np.nextafter(pows, F(0)), np.nextafter(pows, F(1e9)),
+                        np.exp2(rng.uniform(-149.0, 0.5, 500_000)).astype(F), np.exp2(np.arange(-149, 1)).astype(F), rng.uniform(0.7, 1.42, 500_000).astype(F)])
+    x = x[x > 0]
+    got = PR.log2(pr, x).astype(np.float64)
+    want = np.log2(x.astype(np.float64))
+    err = np.abs(got - want)
+    b = PR.bound(pr, "PR_LOG2_BOUND")
+    assert b == 1.45 * 2.0 ** -25
+    hist = (x >= lo) & (x <= hi)
+    _report("log2 on [0.005, 195072]", np.max((err - U * np.abs(got))[hist]))
+    _report("log2 on (0, 1.42]", np.max((err - U * np.abs(got))[~hist]))
+    assert np.all(err <= b + U * np.abs(got))
+    p = np.exp2(np.arange(-149, 18)).astype(F)
+    assert np.array_equal(PR.log2(pr, p), np.arange(-149, 18).astype(F)), "powers of two are exact, subnormal ones included"
+    assert PR.log2(pr, [np.inf])[0] == np.inf
+
+
+ADAPT_LO, ADAPT_HI = math.log2(0.004) - 0.05, math.log2(12.0) + 0.05      # the adapt pass's argument range with the default luminances
+
+
+def test_software_exp2_is_within_its_derived_bound(pr):
+    """10^6 seeded inputs over the adapt pass's argument range [log2 min, log2 max] and over the pow side's [-68, 0.2], the ends
+    and every integer: |pr_exp2(x) - 2^x| <= PR_EXP2_BOUND * 2^rint(x)."""
+    rng = np.random.default_rng(32)
+    ints = np.arange(-68, 5, dtype=F)
+    x = np.concatenate([rng.uniform(ADAPT_LO, ADAPT_HI, 1_000_000).astype(F), rng.uniform(-68.0, 0.2, 500_000).astype(F), rng.uniform(-0.5, 0.5, 200_000).astype(F),
+                        [F(ADAPT_LO), F(ADAPT_HI), 0.0, -0.0], ints, ints + F(0.5), np.nextafter(ints + F(0.5), F(99)), np.nextafter(ints + F(0.5), F(-99))])
+    got = PR.exp2(pr, x).astype(np.float64)
+    want = np.exp2(x.astype(np.float64))
+    err = np.abs(got - want) / np.exp2(np.rint(x.astype(np.float64)))
+    b = PR.bound(pr, "PR_EXP2_BOUND")
+    assert b == 2.9 * 2.0 ** -25
+    _report("exp2, relative to 2^rint(x)", err.max())
+    assert err.max() <= b
+    assert np.array_equal(PR.exp2(pr, ints), np.exp2(ints)), "integers give exact powers of two"
+    assert np.isnan(PR.exp2(pr, [np.nan, np.inf, -np.inf])).all(), "the stated NaN / infinity rule"
+    assert PR.exp2(pr, [400.0])[0] == np.inf and PR.exp2(pr, [-400.0])[0] == 0.0
+
+
+def test_exp2_range_reduction_is_exact_on_both_signs(pr):
+    """f = x - rint(x) is exact in float32 for a seeded million inputs of either sign, 0 < x < 1 included, where the lighting
+    pass's x - ceil(x) is not."""
+    rng = np.random.default_rng(33)
+    x = np.concatenate([rng.uniform(ADAPT_LO, ADAPT_HI, 600_000), rng.uniform(0.0, 1.0, 300_000), np.exp2(rng.uniform(-40.0, 0.0, 100_000)),
+                        -np.exp2(rng.uniform(-40.0, 6.0, 100_000)), rng.uniform(-68.0, 0.0, 100_000)]).astype(F)
+    f = PR.exp2_reduced(pr, x)
+    x64 = x.astype(np.float64)
+    assert np.array_equal(f.astype(np.float64), x64 - np.rint(x64))
+    assert np.all(np.abs(f) <= 0.5)
+    xs = F(9.28e-5)
+    assert np.float64(F(xs - np.ceil(xs))) != np.float64(xs) - np.ceil(np.float64(xs)), "ceil is inexact for a small positive x"
+
+
+def test_pow_gamma_is_within_its_derived_bound(pr):
+    """pow(x, 1 / 2.2f) on [0, 1]: 10^6 seeded inputs, uniform and log-uniform down to the subnormals, both ends: relative error
+    against x^k in float64 (k the rounded constant) <= PR_POW_BOUND_A + PR_POW_BOUND_B |log2 x|; zero, negative and NaN give 0."""
+    rng = np.random.default_rng(34)
+    x = np.concatenate([rng.uniform(0.0, 1.0, 500_000).astype(F), np.exp2(rng.uniform(-149.0, 0.0, 500_000)).astype(F), [F(1.0), np.nextafter(F(1.0), F(0)), F(2.0 ** -149)]])
+    x = x[x > 0]
+    k = float(F(1.0) / F(2.2))
+    got = PR.pow_gamma(pr, x).astype(np.float64)
+    want = x.astype(np.float64) ** k
+    rel = np.abs(got - want) / want
+    a, b = PR.bound(pr, "PR_POW_BOUND_A"), PR.bound(pr, "PR_POW_BOUND_B")
+    lg = np.abs(np.log2(x.astype(np.float64)))
+    print(f"pow: largest relative error {rel.max():.4e}; largest share of its bound {np.max(rel / (a + b * lg)):.3f}; largest absolute error {np.max(np.abs(got - want)):.4e}")
+    assert np.all(rel <= a + b * lg)
+    assert PR.pow_gamma(pr, [1.0])[0] == 1.0
+    assert np.array_equal(PR.pow_gamma(pr, [0.0, -0.0, -1.0, -np.inf, np.nan]).view(np.uint32), np.zeros(5, np.uint32))
+
+
+# ---- the histogram bin against float64 ---------------------------------------------------------------------------------------
+def _decode64(words):
+    """The three channels in float64 (exact), NaN and infinity included."""
+    def chan(c, m):
+        e, f = (c >> m).astype(np.int64), (c & ((1 << m) - 1)).astype(np.float64)
+        v = np.where(e == 0, f * 2.0 ** (-14 - m), (1.0 + f * 2.0 ** -m) * np.exp2((e - 15).astype(np.float64)))
+        return np.where(e == 31, np.where(f == 0, np.inf, np.nan), v)
+    w = np.asarray(words, np.uint32).astype(np.int64)
+    return np.stack([chan(w & 0x7FF, 6), chan((w >> 11) & 0x7FF, 6), chan(w >> 22, 5)], -1)
+
+
+def _bin64(words, k):
+    """adaptluminance.hlsl:23-37 in float64 (the pass constants are the float32 words the pass gets).  Returns (bin, t):
+    t = logLum * 254 + 1 before the truncation (NaN where the luminance test fails)."""
+    c = _decode64(words)
+    with np.errstate(all="ignore"):
+        lum = c[..., 0] * 0.212671 + c[..., 1] * 0.715160 + c[..., 2] * 0.072169
+        lit = lum >= float(F(0.005))
+        t = np.clip((np.log2(np.where(lit, lum, 1.0)) - float(k["m_MinLogLuminance"][0])) * float(k["m_InverseLogLuminanceRange"][0]), 0.0, 1.0) * 254.0 + 1.0
+    t = np.where(lit, t, np.nan)
+    return np.where(lit, np.floor(np.nan_to_num(t)), 0).astype(np.uint32), t, lum
+
+
+def _words_near_the_luminance_test(pr):
+    """Every word whose float32 luminance lies within 8 float32 steps of 0.005f: for every red and green code below the
+    threshold, the blue codes next to the one that closes the gap (the luminance grows with every code)."""
+    rc = np.arange(0, 31 << 6, dtype=np.uint32)
+    r = PR.unpack_ufloat(pr, rc, 6).astype(np.float64)
+    bc = np.arange(0, 31 << 5, dtype=np.uint32)
+    b = PR.unpack_ufloat(pr, bc, 5).astype(np.float64)
+    small_r, small_g = rc[r * 0.212671 <= 0.0051], rc[r * 0.715160 <= 0.0051]
+    R, G = np.meshgrid(small_r, small_g, indexing="ij")
+    need = (0.005 - (r[R] * 0.212671 + r[G] * 0.715160)) / 0.072169
+    j = np.searchsorted(b, need.ravel())
+    cand = []
+    for dj in (-2, -1, 0, 1):
+        jj = np.clip(j + dj, 0, len(bc) - 1)
+        cand.append((R.ravel() | G.ravel() << 11 | bc[jj] << 22).astype(np.uint32))
+    words = np.unique(np.concatenate(cand))
+    lum = PR.luminance(pr, words)
+    steps = np.abs(lum.view(np.int32).astype(np.int64) - int(F(0.005).view(np.int32)))
+    return words[steps <= 8]
+
+
+# The band of t = logLum * 254 + 1 inside which the float32 bin may differ from float64's.  With the default luminances
+# invRange = 0.0866 and |log2 lum| <= 17.6: log2's bound PR_LOG2_BOUND + 2^-24 * 17.6 = 1.09e-6; the float32 luminance (three
+# roundings, positive terms: 3 * 2^-24 relative, 2^-25 for the constants) moves log2 by 3.5 * 2^-24 / ln 2 = 3.0e-7; the
+# subtraction of minLog rounds by half an ulp of at most 32: 9.5e-7.  Together 2.34e-6, times invRange * 254 = 22.0: 5.2e-5.
+# The product with invRange, the product with 254 (values <= 254) and the sum (<= 255) round by 2^-24 * 254 * 2 + 2^-17 =
+# 3.8e-5.  Band 9.0e-5 -> 1e-4.
+BIN_BAND = 1e-4
+
+
+def test_histogram_bin_against_float64(pr):
+    """2 M seeded words over all 2^32, the words around the luminance test and the special patterns.  The float32 bin differs
+    from float64's by at most one, and only where float64's t lies within BIN_BAND of an integer."""
+    k = PR.histogram_params((1, 1))
+    near = _words_near_the_luminance_test(pr)
+    assert len(near) > 0
+    words = np.concatenate([PR.seeded_words(2_000_000, 35), near, PR.SPECIAL_WORDS, PR.straddling_words(pr)])
+    got = PR.bins(pr, words, k).astype(np.int64)
+    want, t, lum64 = _bin64(words, k)
+    want = want.astype(np.int64)
+    # THE LUMINANCE TEST IS A JUMP: lum >= 0.005f separates bin 0 from bin 8 (with the default luminances), so "differs by at
+    # most one" cannot hold for a word whose float32 luminance (three roundings) and float64 luminance fall on different sides
+    # of it.  Such a word is allowed only where the float64 luminance lies within the float32 chain's error of the threshold
+    # (3.5 * 2^-24 relative, see BIN_BAND), and its float32 bin must then be what float64 gives for the other side of the test;
+    # it is counted and taken out of the one-step rule, which holds for every other word.
+    lum32 = PR.luminance(pr, words)
+    with np.errstate(invalid="ignore"):
+        straddle = (lum32 >= F(0.005)) != (lum64 >= float(F(0.005)))
+    thr = float(F(0.005))
+    assert np.all(np.abs(lum64[straddle] - thr) <= 3.5 * U * thr), (words[straddle], lum64[straddle])
+    at_threshold = int(np.floor(np.clip((math.log2(thr) - float(k["m_MinLogLuminance"][0])) * float(k["m_InverseLogLuminanceRange"][0]), 0, 1) * 254.0 + 1.0))
+    assert np.all(np.isin(got[straddle], (0, at_threshold))) and np.all(np.isin(want[straddle], (0, at_threshold)))
+    print(f"words on different sides of the luminance test in float32 and float64: {int(straddle.sum())} ({[hex(int(w)) for w in words[straddle]]}), bins 0 / {at_threshold}")
+    got, want, t, words = got[~straddle], want[~straddle], t[~straddle], words[~straddle]
+    diff = got != want
+    print(f"words around the luminance test: {len(near)}; bins that differ from float64's: {int(diff.sum())} of {len(words)} ({diff.mean():.3e})")
+    assert np.all(np.abs(got - want) <= 1), (words[np.abs(got - want) > 1][:8], got[np.abs(got - want) > 1][:8], want[np.abs(got - want) > 1][:8])
+    with np.errstate(invalid="ignore"):
+        assert np.all(np.abs(t[diff] - np.rint(t[diff])) <= BIN_BAND)
+    assert got.min() >= 0 and got.max() <= 255
+    sp = PR.bins(pr, PR.SPECIAL_WORDS, k)
+    assert sp[0] == 0 and np.all(sp[6:9] == 255) and np.all(sp[9:] == 0), "black -> 0, +inf -> 255, NaN -> 0"
+
+
+# ---- the post chain against float64 ------------------------------------------------------------------------------------------
+def _post64(k, colour, bloom, luminance):
+    """postprocess.hlsl:23-69 in float64.  Returns (bytes [..., 3] as float64's rounding gives them, c * 255 + 0.5 before the
+    truncation, v = the scaled colour before the tone curve, peak before the compression)."""
+    c = _decode64(colour)
+    b = _decode64(bloom) if bloom is not None else np.zeros_like(c)
+    s = float(k["m_BloomStrength"][0])
+    with np.errstate(all="ignore"):
+        rgb = c + s * (b - c)
+        scene = float(k["m_ManualExposure"][0])
+        if scene == 0.0:
+            scene = float(F(luminance))
+        v = rgb * (float(k["m_MiddleGray"][0]) / scene) if scene != 0.0 else rgb * np.inf
+        sc, desat = 0.8 - 0.04, 0.15
+        x = np.min(v, -1, keepdims=True)
+        offset = np.where(x < 0.08, x - 6.25 * x * x, 0.04)
+        w = v - offset
+        peak = np.max(w, -1, keepdims=True)
+        d = 1.0 - sc
+        new_peak = 1.0 - d * d / (peak + d - sc)
+        wc = w * (new_peak / peak)
+        g = 1.0 - 1.0 / (desat * (peak - new_peak) + 1.0)
+        wc = wc + g * (new_peak - wc)
+        out = np.where(peak < sc, w, wc)
+        srgb = np.where(out > 0, np.power(np.where(out > 0, out, 1.0), 1.0 / 2.2), 0.0)
+        srgb = np.where(np.isnan(out), 0.0, srgb)
+        t = np.clip(srgb, 0.0, 1.0) * 255.0 + 0.5
+    return np.floor(t).astype(np.int64), t, v, np.broadcast_to(peak, v.shape), out
+
+
+def _byte_band(pr, v, peak, out, lerp_units=6):
+    """How far float32's c * 255 + 0.5 may lie from float64's, per channel.  E bounds the absolute error of the value handed to
+    pow: the bloom lerp (colour and bloom within a factor of two here: 6u relative, u = 2^-24), the exposure scale (2u), the
+    offset (6.25 x, its product with x, the difference: at most 10u x with x <= v) and the subtraction (u) leave at most
+    48u v -- relative to the value BEFORE the offset, because the offset cancels: the minimum channel keeps 6.25 x^2 of x.  Past
+    the start of the compression (peak >= 0.76; 0.75 here, the branch being continuous) newPeak, g = 1 - 1 / (..) and the last
+    lerp add absolute roundings of numbers <= 1: 8u, and v counts only up to 2 because the ratio newPeak / peak undoes the rest.
+    pow moves by at most (c + E)^k - (c - E)^k (it is concave) and adds its own relative PR_POW_BOUND_A + PR_POW_BOUND_B
+    |log2 c|; the products with 255 and the sum with 0.5 round by 3u * 256.  lerp_units: the bloom lerp's share of the 48u, 6 for a
+    bloom within a factor of two of the colour; an independent bloom at strength 0.1 needs 22 (the difference and its product round
+    by at most 2u of the larger of the two, the sum by u of the result, and the result is at least 0.1 of the larger: 21u)."""
+    a, b = PR.bound(pr, "PR_POW_BOUND_A"), PR.bound(pr, "PR_POW_BOUND_B")
+    k = 1.0 / 2.2
+    with np.errstate(all="ignore"):
+        E = (42 + lerp_units) * U * np.minimum(np.abs(v), 2.0) + np.where(peak >= 0.75, 8 * U, 0.0)
+        c = np.clip(np.nan_to_num(out, nan=0.0, posinf=1.0), 0.0, 2.0)
+        hi, lo = (c + E) ** k, np.maximum(c - E, 0.0) ** k
+        rel = a + b * np.abs(np.log2(np.maximum(c, 2.0 ** -149)))
+    return 255.0 * ((hi - lo) + rel * hi) + 3 * U * 256
+
+
+def _check_post(pr, k, colour, bloom, luminance, label, lerp_units=6):
+    got = PR.post(pr, k, colour, bloom=bloom, luminance_in=luminance)
+    assert np.all(got >> 24 == 255)
+    gb = np.stack([got & 0xFF, (got >> 8) & 0xFF, (got >> 16) & 0xFF], -1).astype(np.int64)
+    want, t, v, peak, out = _post64(k, colour, bloom, luminance)
+    diff = gb != want
+    assert np.all(np.abs(gb - want) <= 1), (label, colour[np.any(np.abs(gb - want) > 1, -1)][:4], gb[np.abs(gb - want) > 1][:4], want[np.abs(gb - want) > 1][:4])
+    band = _byte_band(pr, v, peak, out, lerp_units)
+    assert np.all(np.abs(t[diff] - np.rint(t[diff])) <= band[diff]), (label, np.max(np.abs(t[diff] - np.rint(t[diff])) / band[diff]))
+    return int(diff.sum()), diff.size
+
+
+EXPOSURES = [("manual 0.05", 0.05, 1.0), ("manual 1", 1.0, 1.0), ("manual 20", 20.0, 1.0), ("auto 0.004", 0.0, 0.004), ("auto 1", 0.0, 1.0), ("auto 12", 0.0, 12.0)]
+
+
+def _bloom_near(colour, seed):
+    """Bloom texels within a factor of two of the colour's (each channel code moved by up to one exponent step).  lerp as written,
+    x + s * (y - x), carries half an ulp of x whatever the result's size: with a bloom 2^24 times darker than the colour and
+    s = 1 float32 returns 0 where float64 returns the bloom.  That conditioning belongs to the expression, not to this build, and
+    is kept out of the comparison with float64; the GPU tests use independent bloom words, an exact comparison needing no such care."""
+    rng = np.random.default_rng(seed)
+    c = np.asarray(colour, np.uint32).astype(np.int64)
+    r = np.clip((c & 0x7FF) + rng.integers(-64, 65, c.shape), 0, (31 << 6) - 1)
+    g = np.clip(((c >> 11) & 0x7FF) + rng.integers(-64, 65, c.shape), 0, (31 << 6) - 1)
+    b = np.clip((c >> 22) + rng.integers(-32, 33, c.shape), 0, (31 << 5) - 1)
+    return (r | g << 11 | b << 22).astype(np.uint32)
+
+
+def test_post_chain_against_float64(pr):
+    """A grey ramp over all 2048 codes (the finite ones) and 3 x 49 152 seeded colour texels under six exposures, then bloom
+    strengths 0, 0.1 and 1 (bloom near the colour), and strength 0.1 with an independent bloom: no byte more than one step from float64's, and a differing byte only where float64's c * 255 + 0.5
+    lies within the derived band of an integer (_byte_band)."""
+    ramp = np.array([PR.grey(c) for c in range(31 << 6)], np.uint32)
+    texels = [PR.seeded_finite_words(49152, 36 + i) for i in range(3)]
+    differing = total = 0
+    for label, manual, lum in EXPOSURES:
+        k = PR.post_params((1, 1), manual=manual)
+        for name, colour in [("ramp", ramp)] + [(f"texels {i}", t) for i, t in enumerate(texels)]:
+            d, n = _check_post(pr, k, colour, None, lum, f"{label} {name}")
+            differing += d; total += n
+    for strength in (0.0, 0.1, 1.0):
+        for manual, lum in ((1.0, 1.0), (0.0, 0.5)):
+            k = PR.post_params((1, 1), manual=manual, bloom_strength=strength)
+            for i, colour in enumerate([ramp] + texels):
+                d, n = _check_post(pr, k, colour, _bloom_near(colour, 40 + i), lum, f"bloom {strength} manual {manual} set {i}")
+                differing += d; total += n
+    # a dark bloom under a bright colour and the reverse, at the strength where lerp stays well conditioned: independent words
+    for manual, lum in ((1.0, 1.0), (0.0, 0.5)):
+        k = PR.post_params((1, 1), manual=manual, bloom_strength=0.1)
+        for i, colour in enumerate(texels):
+            d, n = _check_post(pr, k, colour, PR.seeded_finite_words(len(colour), 45 + i), lum, f"independent bloom 0.1 manual {manual} set {i}", lerp_units=22)
+            differing += d; total += n
+    print(f"bytes that differ from float64's: {differing} of {total} ({differing / total:.3e})")
+
+
+def test_post_special_inputs_word_by_word(pr):
+    """What the convention defines: zero, subnormal codes, the largest finite, +inf, NaN, a zero luminance."""
+    k1 = PR.post_params((1, 1), manual=1.0)
+    black = 0xFF000000
+    got = PR.post(pr, k1, PR.SPECIAL_WORDS)
+    assert got[0] == black, "zero"
+    assert np.all(got[6:] == black), "+inf (the curve makes NaN of it) and NaN are stored as 0"
+    assert got[5] == 0xFFFFFFFF, "the largest finite colour is white"
+    sub, _, _, _, _ = _post64(k1, PR.SPECIAL_WORDS[1:5], None, 1.0)
+    gb = np.stack([got[1:5] & 0xFF, (got[1:5] >> 8) & 0xFF, (got[1:5] >> 16) & 0xFF], -1)
+    assert np.array_equal(gb, sub), "subnormal codes: float64's bytes"
+    assert np.all(gb[:3] == 0), "a single smallest subnormal stays byte 0"
+    # the smallest subnormal under a strong exposure is visible: the load does not flush it
+    k_bright = PR.post_params((1, 1), manual=1e-6)
+    assert PR.post(pr, k_bright, [PR.grey(1)])[0] & 0xFF > 0
+    # a zero scene luminance: the scale is +inf; every colour, black included, is stored as 0
+    k0 = PR.post_params((1, 1), manual=0.0)
+    assert np.all(PR.post(pr, k0, np.concatenate([PR.SPECIAL_WORDS, PR.seeded_words(1000, 41)]), luminance_in=0.0) == black)
+    # a NaN bloom channel at strength 0 still poisons its channel: lerp is always evaluated
+    k = PR.post_params((1, 1), manual=1.0, bloom_strength=0.0)
+    w = PR.post(pr, k, [PR.grey(15 << 6)], bloom=[0x7FF])[0]
+    assert w & 0xFF == 0 and (w >> 8) & 0xFF > 0
+
+
+# ---- CS_AdaptExposure ---------------------------------------------------------------------------------------------------------
+def _adapt64(k, hist, last):
+    """adaptluminance.hlsl:63-95 with exact integers for the sum and float64 for the rest."""
+    total = sum(int(c) * i for i, c in enumerate(hist.tolist())) & 0xFFFFFFFF
+    avg = float(F(total)) / max(float(F(int(k["m_NbPixels"][0]))) - float(F(int(hist[0]))), 1.0) - 1.0
+    lum = 2.0 ** (avg / 254.0 * float(k["m_LogLuminanceRange"][0]) + float(k["m_MinLogLuminance"][0]))
+    adapted = float(last) + (lum - float(last)) * float(k["m_AdaptationSpeed"][0])
+    mg = float(k["m_MiddleGray"][0])
+    return adapted, mg / (adapted * (1.0 - mg)), total
+
+
+# avg carries two roundings of numbers <= 255 (3.0e-5), which the division by 254 and the product with the range (11.55) turn
+# into 1.4e-6 of the exponent; those two operations and the sum with minLog (half an ulp of 8) add 1.2e-6: 2.6e-6 of the exponent
+# is 1.8e-6 of the luminance; exp2's bound adds 1.3e-7 and the recurrence three roundings: below 2^-18 = 3.8e-6.
+ADAPT_TOLERANCE = 2.0 ** -18
+
+
+@pytest.mark.parametrize("name", list(PR.ADAPT_HISTOGRAMS))
+@pytest.mark.parametrize("speed", [0.0, 0.04, 1.0])
+def test_adapt_exposure_on_constructed_histograms(pr, name, speed):
+    hist, n = PR.ADAPT_HISTOGRAMS[name]
+    k = PR.adapt_params(n, speed)
+    for last in (1.0, 0.004, 12.0):
+        lum, exposure = PR.adapt_exposure(pr, k, hist, last)
+        want_lum, want_exp, total = _adapt64(k, hist, last)
+        # the recurrence last + (lum - last) * speed rounds at the size of the larger of the two: an absolute tolerance; the
+        # exposure divides by the adapted luminance and carries the same error relatively, plus its own three roundings
+        tol = ADAPT_TOLERANCE * max(want_lum, float(last))
+        assert abs(float(lum) - want_lum) <= tol, (name, speed, last, lum, want_lum)
+        assert abs(float(exposure) - want_exp) <= (tol / want_lum * 1.001 + 3 * U) * want_exp
+        if speed == 0.0:
+            assert lum == F(last), "speed 0 keeps the luminance bit for bit"
+    if name == "weighted sum wraps uint32":
+        assert 17_000_000 * 255 + 123 * 17 >= 1 << 32 and total == (17_000_000 * 255 + 123 * 17) - (1 << 32)
+    if name in ("all zero", "everything in bin 0") and speed == 1.0:
+        lo, hi = I.log_luminance_range(0.004, 12.0)
+        want = 2.0 ** (-1.0 / 254.0 * float(F(hi - lo)) + float(lo))          # max(.., 1) applies: avg = 0 / 1 - 1
+        assert abs(float(PR.adapt_exposure(pr, k, hist, 1.0)[0]) - want) <= ADAPT_TOLERANCE * 1.0      # from 1.0: the recurrence rounds at the size of 1
+
+
+def test_adapt_exposure_recurrence_over_twenty_steps(pr):
+    """20 steps from 1.0 at speed 0.04 against the float64 recurrence.  The step is a contraction by 1 - speed, so the per-step
+    error d accumulates to at most d / speed: ADAPT_TOLERANCE for the target plus 3 * 2^-24 / 0.04 for the roundings."""
+    hist, n = PR.ADAPT_HISTOGRAMS["mid bins"]
+    k = PR.adapt_params(n, 0.04)
+    lum, lum64 = F(1.0), 1.0
+    for step in range(20):
+        lum, _ = PR.adapt_exposure(pr, k, hist, lum)
+        lum64, _, _ = _adapt64(k, hist, lum64)
+        assert abs(float(lum) - lum64) <= (ADAPT_TOLERANCE + 3 * U / 0.04) * lum64, step
+    target = _adapt64(PR.adapt_params(n, 1.0), hist, 1.0)[0]
+    assert abs(lum64 - target) < abs(1.0 - target) * 0.96 ** 19.5
+
+
+# ---- layout and host constants -------------------------------------------------------------------------------------------------
+WANT_LAYOUT = {
+    "GenerateLuminanceHistogramParameters": (16, dict(m_SrcColorDims=0, m_MinLogLuminance=8, m_InverseLogLuminanceRange=12)),
+    "AdaptExposureParameters": (20, dict(m_MinLogLuminance=0, m_LogLuminanceRange=4, m_AdaptationSpeed=8, m_NbPixels=12, m_MiddleGray=16)),
+    "PostProcessParameters": (24, dict(m_OutputDims=0, m_ManualExposure=8, m_MiddleGray=12, m_WhitePoint=16, m_BloomStrength=20)),
+}
+
+
+def test_parameter_struct_layouts(tmp_path):
+    """A g++-compiled probe prints sizeof / offsetof of the three structs of csrc/ShaderInterop.h: every field where the numpy
+    dtypes and tests/postprocess_ref.c have it."""
+    lines = ['#include <cstdio>', '#include "ShaderInterop.h"', "int main() {"]
+    for s, (_, fields) in WANT_LAYOUT.items():
+        lines.append(f'    printf("{s} %zu\\n", sizeof(interop::{s}));')
+        lines += [f'    printf("{s}.{f} %zu\\n", offsetof(interop::{s}, {f}));' for f in fields]
+    lines += ["    return 0;", "}"]
+    src = tmp_path / "probe.cpp"
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "probe"
+    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "toyrenderer_amd", "csrc"), str(src), "-o", str(exe)])
+    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    for s, (size, fields) in WANT_LAYOUT.items():
+        dt = getattr(I, s)
+        assert int(out[s]) == size == dt.itemsize == I.SIZES[s]
+        assert list(dt.names) == list(fields)
+        for f, off in fields.items():
+            assert int(out[f"{s}.{f}"]) == dt.fields[f][1] == off, (s, f)
+
+
+def test_host_and_python_log_luminance_constants_agree(tmp_path):
+    """The host mirror's expression (csrc/host/AdaptLuminanceRenderer.cpp: (float)std::log2((double)luminance)) compiled by g++
+    gives the words of interop.log_luminance_range, for the defaults and a few other limits."""
+    src_text = open(os.path.join(ROOT, "toyrenderer_amd", "csrc", "host", "AdaptLuminanceRenderer.cpp")).read()
+    import re
+    assert len(re.findall(r"\(float\)\s*std::log2\(\s*\(double\)\s*g_Scene->m_M(?:in|ax)imumLuminance\s*\)", src_text)) == 2
+    limits = [0.004, 12.0, 0.001, 1.0, 0.3, 100.0]
+    lines = ["#include <cmath>", "#include <cstdio>", "#include <cstring>", "#include <cstdint>", "int main() {", "    const float v[] = { " + ", ".join(f"{x}f" for x in limits) + " };",
+             "    for (float x : v) { const float l = (float)std::log2((double)x); uint32_t u; memcpy(&u, &l, 4); printf(\"%08x\\n\", u); }", "    return 0;", "}"]
+    src = tmp_path / "log_probe.cpp"
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "log_probe"
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", str(src), "-o", str(exe)])
+    got = [int(x, 16) for x in subprocess.check_output([str(exe)]).decode().split()]
+    want = [int(I.log_luminance_range(x, x)[0].view(np.uint32)) for x in limits]
+    assert got == want
+
+
+def test_default_log_luminance_constants():
+    """log2 in float64 of the float32 luminance, rounded once: the words FrameDriver hands the passes by default."""
+    lo, hi = I.log_luminance_range(0.004, 12.0)
+    assert lo.dtype == F and hi.dtype == F
+    assert float(lo) == float.fromhex("-0x1.fdcf68p+2") and float(hi) == float.fromhex("0x1.cae00ep+1")
+    assert Fraction(float(lo)) != Fraction(math.log2(0.004)), "the float32 0.004 is not the decimal: the order of the roundings matters"
+    k = PR.histogram_params((3, 2))
+    assert k["m_InverseLogLuminanceRange"][0] == F(1.0) / F(hi - lo) and tuple(k["m_SrcColorDims"][0]) == (3, 2)

@@ -123,6 +123,37 @@ static_assert(offsetof(DeferredLightingConsts, m_DebugMode) == 80 && offsetof(De
 static_assert(offsetof(DeferredLightingConsts, m_DirectionalLightStrength) == 96 && offsetof(DeferredLightingConsts, m_LightingOutputResolution) == 100 &&
               offsetof(DeferredLightingConsts, m_bRTDDGIEnabled) == 108, "DeferredLightingConsts");
 
+// ShaderInterop.h:124-129: push constants of "adaptluminance_CS_GenerateLuminanceHistogram"
+struct GenerateLuminanceHistogramParameters
+{
+    Vector2U m_SrcColorDims;
+    float m_MinLogLuminance;                // log2 of the luminance that maps to bin 1
+    float m_InverseLogLuminanceRange;       // 1 / (log2 max - log2 min)
+};
+static_assert(sizeof(GenerateLuminanceHistogramParameters) == 16 && offsetof(GenerateLuminanceHistogramParameters, m_MinLogLuminance) == 8, "GenerateLuminanceHistogramParameters");
+
+// ShaderInterop.h:40-47: push constants of "adaptluminance_CS_AdaptExposure"
+struct AdaptExposureParameters
+{
+    float m_MinLogLuminance;
+    float m_LogLuminanceRange;
+    float m_AdaptationSpeed;                // already clamped to [0, 1]: speed per ms times the frame time
+    uint32_t m_NbPixels;
+    float m_MiddleGray;
+};
+static_assert(sizeof(AdaptExposureParameters) == 20 && offsetof(AdaptExposureParameters, m_NbPixels) == 12 && offsetof(AdaptExposureParameters, m_MiddleGray) == 16, "AdaptExposureParameters");
+
+// ShaderInterop.h:234-241: push constants of "postprocess_PS_PostProcess"
+struct PostProcessParameters
+{
+    Vector2U m_OutputDims;
+    float m_ManualExposure;                 // 0: the scene luminance comes from the luminance buffer
+    float m_MiddleGray;
+    float m_WhitePoint;                     // not read by the entry
+    float m_BloomStrength;
+};
+static_assert(sizeof(PostProcessParameters) == 24 && offsetof(PostProcessParameters, m_ManualExposure) == 8 && offsetof(PostProcessParameters, m_BloomStrength) == 20, "PostProcessParameters");
+
 // ShaderInterop.h:117-122
 struct DispatchIndirectArguments
 {

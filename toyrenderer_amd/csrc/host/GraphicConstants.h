@@ -14,6 +14,7 @@ static constexpr nvrhi::Format kGBufferAFormat = nvrhi::Format::RGBA32_UINT;
 static constexpr nvrhi::Format kGBufferMotionFormat = nvrhi::Format::RG16_FLOAT;
 static constexpr nvrhi::Format kLightingOutputFormat = nvrhi::Format::R11G11B10_FLOAT;
 static constexpr nvrhi::Format kShadowMaskFormat = nvrhi::Format::R8_UNORM;
+static constexpr nvrhi::Format kBackBufferFormat = nvrhi::Format::RGBA8_UNORM;    // GraphicRHI.cpp:214, the swap chain's
 static constexpr nvrhi::Format kDepthStencilFormat = nvrhi::Format::D24S8;
 static constexpr nvrhi::Format kHZBFormat = nvrhi::Format::R16_FLOAT;
 } // namespace GraphicConstants

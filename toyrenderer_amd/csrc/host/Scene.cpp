@@ -17,6 +17,8 @@
 extern IRenderer* g_UpdateInstanceConstsRenderer;
 extern IRenderer* g_GBufferRenderer;
 extern IRenderer* g_DeferredLightingRenderer;
+extern IRenderer* g_AdaptLuminanceRenderer;
+extern IRenderer* g_PostProcessRenderer;
 extern IRenderer* g_GIDebugRenderer;
 
 void View::Update()
@@ -218,6 +220,10 @@ void Scene::Update()
         m_RenderGraph->AddRenderer(g_UpdateInstanceConstsRenderer);
         m_RenderGraph->AddRenderer(g_GBufferRenderer);
         if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
+        if (m_bPostProcess) {                                                 // :505, :507 (sky, bloom, transparents and TAA between them are not built)
+            m_RenderGraph->AddRenderer(g_AdaptLuminanceRenderer);
+            m_RenderGraph->AddRenderer(g_PostProcessRenderer);
+        }
         m_RenderGraph->AddRenderer(g_GIDebugRenderer);                        // :509 (after the base pass: it reads this frame's HZB)
     }
     { HOST_PROFILE_SCOPE("RenderGraph::Compile"); m_RenderGraph->Compile(); }                            // :515
@@ -234,6 +240,9 @@ void Scene::Shutdown()
     m_HZB = nullptr;
     m_SyntheticDepth = nullptr;
     m_ShadowMaskTexture = nullptr;
+    m_BloomTexture = nullptr;
+    m_LuminanceBuffer = nullptr;
+    m_ExposureTexture = nullptr;
     m_GIProbePositionsBuffer = m_GIProbeStatesBuffer = nullptr;
     m_NumGIProbes = 0; m_bShowGIProbes = false;
 }

@@ -104,6 +104,18 @@ public:
     float m_DirLightVec[3] = { 0.0f, -1.0f, 0.0f };  // Scene.h:134-136: used as given (the reference derives it from two angles)
     float m_DirLightStrength = 1.0f;
     nvrhi::TextureHandle m_ShadowMaskTexture;        // R8_UNORM at render resolution, or null: the pass reads 1.0 (the reference's WhiteTexture)
+    // Auto exposure and tone mapping (trhost_set_post_process; implies m_bDeferredLighting): AdaptLuminanceRenderer and
+    // PostProcessRenderer run after DeferredLightingRenderer and turn LightingOutput into the RGBA8_UNORM back buffer.
+    bool m_bPostProcess = false;
+    float m_ManualExposureOverride = 0.0f;           // Scene.h: > 0 switches the histogram and the adaptation off
+    float m_MiddleGray = 0.18f;
+    // AdaptLuminanceRenderer.cpp:19-21 (members of the renderer there; here where the facade can set them)
+    float m_MinimumLuminance = 0.004f, m_MaximumLuminance = 12.0f, m_AutoExposureSpeed = 0.0025f;
+    float m_CPUCappedFrameTimeMs = 16.0f;            // Engine::m_CPUCappedFrameTimeMs: set by the application (trhost_set_frame_time_ms), no clock here
+    nvrhi::TextureHandle m_BloomTexture;             // R11G11B10_FLOAT at render resolution, or null: the pass reads black (the reference's BlackTexture)
+    float m_BloomStrength = 0.0f;
+    nvrhi::BufferHandle m_LuminanceBuffer;           // Scene.h: one float, the adapted luminance; survives across frames
+    nvrhi::TextureHandle m_ExposureTexture;          // 1 x 1 R32_FLOAT
     // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.
     void LoadMaterials(const void* materials, uint32_t numMaterials);
     // `<scene>_CachedData.bin` version 3 (SceneLoading.cpp:57-79 layout, :706-781 LoadCachedData): meshes, meshlets and

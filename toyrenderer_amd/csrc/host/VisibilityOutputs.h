@@ -47,6 +47,14 @@ void CreateGBufferPixelTargets();
 nvrhi::TextureHandle GetLightingOutput();
 bool GetLastDeferredLightingConsts(void* out112);
 void ReleaseDeferredLightingOutputs();
+
+// PostProcessRenderer's back buffer (RGBA8_UNORM), AdaptLuminanceRenderer's histogram and the three parameter structs of the last
+// recorded frame (adaptRan: the two adapt dispatches were recorded, i.e. no manual exposure); null / false until a frame ran
+// with post-processing on.  ResetExposure writes 1.0 into the luminance buffer and the exposure texel (kInitialExposure).
+nvrhi::TextureHandle GetBackBuffer();
+bool GetLastPostProcessConsts(void* histogram16, void* adapt20, void* post24, int* adaptRan);
+void ResetExposure();
+void ReleasePostProcessOutputs();
 // the base pass's pipeline statistics: the value its frame N showed (the query of frame N - 2) and the last executed frame's (waits)
 void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest);
 

@@ -92,7 +92,7 @@ private:
 using ResourceHandle = RefCountPtr<IResource>;
 
 // ---- enums / small structs -----------------------------------------------------------------------
-enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT };   // GraphicConstants.h:24-28, :31 (lighting output), shadow mask, SSAO
+enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT, RGBA8_UNORM };   // GraphicConstants.h:24-28, :31 (lighting output), shadow mask, SSAO, the back buffer (GraphicRHI.cpp:214)
 enum class ResourceStates : uint32_t { Unknown = 0, ShaderResource, UnorderedAccess, IndirectArgument, DepthRead, DepthWrite, CopyDest };
 enum class CommandQueue : uint8_t { Graphics = 0, Compute, Copy, Count };
 enum class HeapType : uint8_t { DeviceLocal };
@@ -426,7 +426,7 @@ public:
         n.format = d.format == Format::R16_FLOAT ? TRHIP_FORMAT_R16_FLOAT : d.format == Format::RG32_UINT ? TRHIP_FORMAT_RG32_UINT
                  : d.format == Format::RG16_FLOAT ? TRHIP_FORMAT_RG16_FLOAT : d.format == Format::RGBA32_UINT ? TRHIP_FORMAT_RGBA32_UINT
                  : d.format == Format::R11G11B10_FLOAT ? TRHIP_FORMAT_R11G11B10_FLOAT : d.format == Format::R8_UNORM ? TRHIP_FORMAT_R8_UNORM
-                 : d.format == Format::R8_UINT ? TRHIP_FORMAT_R8_UINT : TRHIP_FORMAT_R32_FLOAT;
+                 : d.format == Format::R8_UINT ? TRHIP_FORMAT_R8_UINT : d.format == Format::RGBA8_UNORM ? TRHIP_FORMAT_RGBA8_UNORM : TRHIP_FORMAT_R32_FLOAT;
         trhip_texture t = nullptr;
         throwIfFailed(trhip_texture_create(m_Native, &n, &t), "IDevice::createTexture");
         return TextureHandle(new ITexture(t, d));

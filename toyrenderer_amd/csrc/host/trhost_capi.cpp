@@ -58,6 +58,7 @@ void trhost_shutdown(void)
         ReleaseVisibilityPassBuffers();
         ReleaseGIProbeCullBuffers();
         ReleaseDeferredLightingOutputs();
+        ReleasePostProcessOutputs();
         g_Graphic.Shutdown();
     });
     s_Initialized = false;
@@ -205,6 +206,88 @@ int trhost_get_deferred_lighting_consts(void* out112)
     return guarded([&] {
         check(out112);
         if (!GetLastDeferredLightingConsts(out112)) throw nvrhi::Error("trhost_get_deferred_lighting_consts: no frame ran with deferred lighting on");
+    });
+}
+
+int trhost_set_post_process(int enable)
+{
+    return guarded([&] {
+        check(!enable || g_Graphic.m_GlobalVertexBuffer);      // trhost_load_geometry first
+        if (enable && !g_Graphic.m_GlobalMaterialDataBuffer) throw nvrhi::Error("trhost_set_post_process: no materials (trhost_load_materials first)");
+        if (enable && g_Graphic.m_MaxMeshletGroups > (1u << 18))
+            throw nvrhi::Error("trhost_set_post_process: max_meshlet_groups above 2^18 (list positions must stay below 2^23)");
+        if (enable && g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient)
+            throw nvrhi::Error("trhost_set_post_process: debug view mode 10 (Ambient) needs the DDGI volume, which deferredlighting_PS_Main_Debug does not have");
+        g_Scene->m_bPostProcess = enable != 0;
+        if (enable) { g_Scene->m_bDeferredLighting = true; g_Scene->m_bGBuffer = true; g_Scene->m_bVisibilityBuffer = true; g_Scene->m_bRasterDepth = true; }   // implies deferred lighting
+    });
+}
+
+int trhost_set_exposure(float manual, float middle_gray)
+{
+    return guarded([&] { check(g_Scene); g_Scene->m_ManualExposureOverride = manual; g_Scene->m_MiddleGray = middle_gray; });
+}
+
+int trhost_set_auto_exposure(float min_lum, float max_lum, float speed_per_ms)
+{
+    return guarded([&] {
+        check(g_Scene);
+        g_Scene->m_MinimumLuminance = min_lum; g_Scene->m_MaximumLuminance = max_lum; g_Scene->m_AutoExposureSpeed = speed_per_ms;
+    });
+}
+
+int trhost_set_frame_time_ms(float ms)
+{
+    return guarded([&] { check(g_Scene); g_Scene->m_CPUCappedFrameTimeMs = ms; });
+}
+
+int trhost_upload_bloom(const uint32_t* words, uint64_t bytes, float strength)
+{
+    return guarded([&] {
+        check(g_Scene);
+        g_Scene->m_BloomStrength = strength;
+        if (!words) { g_Scene->m_BloomTexture = nullptr; return; }            // bloom off: black, strength 0
+        if (!g_Scene->m_BloomTexture) {
+            nvrhi::TextureDesc desc;
+            desc.width = g_Graphic.m_RenderResolution.x;
+            desc.height = g_Graphic.m_RenderResolution.y;
+            desc.format = GraphicConstants::kLightingOutputFormat;
+            desc.debugName = "Bloom";
+            g_Scene->m_BloomTexture = g_Graphic.m_NVRHIDevice->createTexture(desc);
+        }
+        nvrhi::throwIfFailed(trhip_texture_upload(g_Scene->m_BloomTexture->native(), 0, words, bytes), "trhost_upload_bloom");
+    });
+}
+
+int trhost_download_back_buffer(uint32_t* words, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetBackBuffer();
+        if (!t) throw nvrhi::Error("trhost_download_back_buffer: no frame ran with post-processing on");
+        check(words);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, words, bytes), "trhost_download_back_buffer");
+    });
+}
+
+int trhost_get_scene_luminance(float* luminance, float* exposure)
+{
+    return guarded([&] {
+        if (!g_Scene->m_LuminanceBuffer) throw nvrhi::Error("trhost_get_scene_luminance: no frame ran with post-processing on");
+        g_Graphic.m_NVRHIDevice->waitForIdle();
+        if (luminance) nvrhi::throwIfFailed(trhip_buffer_download(g_Scene->m_LuminanceBuffer->native(), 0, luminance, sizeof(float)), "trhost_get_scene_luminance");
+        if (exposure) nvrhi::throwIfFailed(trhip_texture_download(g_Scene->m_ExposureTexture->native(), 0, exposure, sizeof(float)), "trhost_get_scene_luminance");
+    });
+}
+
+int trhost_reset_exposure(void)
+{
+    return guarded([&] { check(g_Scene); ResetExposure(); });
+}
+
+int trhost_get_post_process_consts(void* histogram16, void* adapt20, void* post24, int* adapt_ran)
+{
+    return guarded([&] {
+        if (!GetLastPostProcessConsts(histogram16, adapt20, post24, adapt_ran)) throw nvrhi::Error("trhost_get_post_process_consts: no frame ran with post-processing on");
     });
 }
 

@@ -480,10 +480,10 @@ int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_te
     if (!dev || !d || !out) return fail(TRHIP_ERR_INVALID, "texture_create: null argument");
     if (d->width == 0 || d->height == 0 || d->mipLevels == 0 || d->mipLevels > 16)
         return fail(TRHIP_ERR_INVALID, "texture_create: bad dimensions %ux%u mips %u", d->width, d->height, d->mipLevels);
-    if (d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT)
+    if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && d->format != TRHIP_FORMAT_RGBA8_UNORM)
         return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u", d->format);
     if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && d->mipLevels != 1)
-        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT textures have one mip, got %u", d->mipLevels);
+        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT / RGBA8_UNORM textures have one mip, got %u", d->mipLevels);
     auto t = std::make_unique<trhip_texture_t>();
     t->dev = dev;
     t->width = d->width; t->height = d->height; t->mips = d->mipLevels; t->format = d->format;
@@ -703,6 +703,8 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RG32_UINT || tex->format == TRHIP_FORMAT_RGBA32_UINT || tex->format == TRHIP_FORMAT_R8_UINT)
         return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): RG32_UINT / RGBA32_UINT / R8_UINT are cleared with clear_texture_u32", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_RGBA8_UNORM)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): an RGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
     void* p = tex->ptr;
     cl->hold(tex, true);
     if (tex->format == TRHIP_FORMAT_R32_FLOAT || tex->format == TRHIP_FORMAT_R11G11B10_FLOAT) {
@@ -736,6 +738,8 @@ int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t va
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_RGBA8_UNORM)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): an RGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
     if (tex->format != TRHIP_FORMAT_RG32_UINT && tex->format != TRHIP_FORMAT_RGBA32_UINT && tex->format != TRHIP_FORMAT_R8_UINT)
         return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): needs an RG32_UINT, RGBA32_UINT or R8_UINT texture", tex->name.c_str());
     void* p = tex->ptr;

@@ -82,7 +82,8 @@ class FrameDriver:
                  culling_flags: int = 7, force_mesh_lod: int = -1, freeze_culling_camera: bool = False, alloc=None,
                  shard_late=None, raster_depth: bool = False, visibility: bool = False, gbuffer: bool = False,
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
-                 shadow_mask=None, ssao=None):
+                 shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
+                 bloom=(None, 0.0)):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -96,17 +97,33 @@ class FrameDriver:
         after the G-buffer resolve writes self.lighting_output (R11G11B10_FLOAT), cleared to 0 with the other targets.
         dir_light = ((x, y, z), strength): m_DirectionalLightVector as given and m_DirectionalLightStrength; camera_origin:
         m_CameraOrigin (the eye of view.worldToView; a View does not carry it); shadow_mask / ssao: rhi.Texture (R8_UNORM /
-        R8_UINT, render resolution) or None = unbound (1.0 / 255).  self.lighting_consts holds the 112 bytes of the last record()."""
+        R8_UINT, render resolution) or None = unbound (1.0 / 255).  self.lighting_consts holds the 112 bytes of the last record().
+        post: implies lighting (and carries its refusals); after the lighting dispatch the frame runs AdaptLuminanceRenderer and
+        PostProcessRenderer: with a manual exposure of 0, a clear of the 256-word histogram, "adaptluminance_CS_GenerateLuminanceHistogram"
+        and "adaptluminance_CS_AdaptExposure"; with a manual exposure > 0, one write of it into self.luminance instead
+        (AdaptLuminanceRenderer.cpp:149-153); then always "postprocess_PS_PostProcess" into self.back_buffer (RGBA8_UNORM).
+        exposure = (manual, middle_gray): m_ManualExposureOverride and m_MiddleGray; auto_exposure = (min_luminance, max_luminance,
+        adaptation_speed): the speed is the already clamped m_AdaptationSpeed of one frame (the reference's 0.0025 per ms times the
+        frame time; the driver has no clock); bloom = (rhi.Texture or None, strength): an R11G11B10_FLOAT texture at render
+        resolution, None = unbound = black.  self.luminance (one float, 1.0 at construction and after reset_exposure()) and
+        self.exposure_texture (1 x 1 R32_FLOAT) survive across record() and frames.  self.post_consts holds the three parameter
+        structs of the last record() (histogram, adapt, post; the first two None with a manual exposure)."""
+        lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
         if visibility and shard_late is not None:
-            raise ValueError(("deferred lighting" if lighting else "G-buffer" if gbuffer else "visibility buffer") + " with a shard exchange: list positions are per rank, not global")
+            raise ValueError(("post-processing" if post else "deferred lighting" if lighting else "G-buffer" if gbuffer else "visibility buffer") + " with a shard exchange: list positions are per rank, not global")
         if gbuffer and scene.materials is None:
-            raise ValueError(("lighting=True" if lighting else "gbuffer=True") + " needs GpuScene.set_materials()")
+            raise ValueError(("post=True" if post else "lighting=True" if lighting else "gbuffer=True") + " needs GpuScene.set_materials()")
         if lighting and int(debug_mode) == I.kDeferredLightingDebugMode_Ambient:
             raise ValueError("debug_mode 10 (Ambient) needs the DDGI volume, which is not built")
         self.gbuffer_on = bool(gbuffer)
         self.lighting_on = bool(lighting)
+        self.post_on = bool(post)
+        self.manual_exposure, self.middle_gray = np.float32(exposure[0]), np.float32(exposure[1])
+        self.min_luminance, self.max_luminance, self.adaptation_speed = (np.float32(x) for x in auto_exposure)
+        self.bloom, self.bloom_strength = bloom[0], np.float32(bloom[1])
+        self.post_consts = None
         self.dir_light = (tuple(float(x) for x in dir_light[0]), float(dir_light[1]))
         self.camera_origin = tuple(float(x) for x in camera_origin)
         self.shadow_mask, self.ssao = shadow_mask, ssao
@@ -133,6 +150,13 @@ class FrameDriver:
         init.open(); init.clear_texture_f32(self.hzb, 0.0); init.clear_texture_f32(self.depth, 0.0); init.close()
         dev.execute(init); dev.wait_idle(); init.release()
         self.visibility = self.motion = self.gbufferA = self.lighting_output = None
+        self.back_buffer = self.exposure_texture = self.luminance = self.histogram = None
+        if self.post_on:                             # AdaptLuminanceRenderer::Initialize (AdaptLuminanceRenderer.cpp:54-76) + the swap chain's format
+            self.back_buffer = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA8_UNORM, "Back Buffer")
+            self.exposure_texture = dev.create_texture(1, 1, 1, rhi.FORMAT_R32_FLOAT, "Exposure Texture")
+            self.luminance = dev.create_buffer(4, "Exposure Buffer")
+            self.histogram = dev.create_buffer(4 * 256, "Luminance Histogram")
+            self.reset_exposure()
         if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
@@ -303,6 +327,47 @@ class FrameDriver:
             b.append(TEX_SRV(4, self.shadow_mask))
         cl.dispatch("deferredlighting_PS_Main_Debug" if self.debug_mode != 0 else "deferredlighting_PS_Main", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
 
+    # ---- AdaptLuminanceRenderer::Render (AdaptLuminanceRenderer.cpp:119-215) + PostProcessRenderer::Render (:37-74) -----
+    def reset_exposure(self):
+        """The adapted luminance and the exposure texel back to kInitialExposure = 1.0."""
+        self.dev.wait_idle()
+        self.luminance.upload(np.array([1.0], np.float32))
+        self.exposure_texture.upload_mip(0, np.array([[1.0]], np.float32))
+
+    def _post_process(self, cl):
+        v = self.view
+        dims = (v.renderW, v.renderH)
+        hk = ak = None
+        if self.manual_exposure > 0.0:                                                   # :149-153
+            cl.write_buffer(self.luminance, np.array([self.manual_exposure], np.float32))
+        else:
+            lo, hi = I.log_luminance_range(self.min_luminance, self.max_luminance)      # :155-156
+            cl.clear_buffer_u32(self.histogram, 0)
+            hk = np.zeros(1, I.GenerateLuminanceHistogramParameters)
+            hk["m_SrcColorDims"] = dims
+            hk["m_MinLogLuminance"] = lo
+            hk["m_InverseLogLuminanceRange"] = np.float32(1.0) / np.float32(hi - lo)
+            cl.dispatch("adaptluminance_CS_GenerateLuminanceHistogram", [PUSH(0), TEX_SRV(0, self.lighting_output), UAV(0, self.histogram)],
+                        ((v.renderW + 15) // 16, (v.renderH + 15) // 16, 1), push=hk)
+            ak = np.zeros(1, I.AdaptExposureParameters)
+            ak["m_AdaptationSpeed"] = self.adaptation_speed
+            ak["m_MinLogLuminance"] = lo
+            ak["m_LogLuminanceRange"] = np.float32(hi - lo)
+            ak["m_NbPixels"] = v.renderW * v.renderH
+            ak["m_MiddleGray"] = self.middle_gray
+            cl.dispatch("adaptluminance_CS_AdaptExposure", [PUSH(0), SRV(0, self.histogram), UAV(0, self.luminance), TEX_UAV(1, self.exposure_texture, 0)],
+                        (1, 1, 1), push=ak)
+        pk = np.zeros(1, I.PostProcessParameters)
+        pk["m_OutputDims"] = dims
+        pk["m_ManualExposure"] = self.manual_exposure
+        pk["m_MiddleGray"] = self.middle_gray
+        pk["m_BloomStrength"] = self.bloom_strength if self.bloom is not None else 0.0  # m_bEnableBloom ? m_BloomStrength : 0
+        b = [PUSH(0), TEX_SRV(0, self.lighting_output), SRV(1, self.luminance), TEX_UAV(0, self.back_buffer, 0), SAMPLER(0)]
+        if self.bloom is not None:
+            b.append(TEX_SRV(2, self.bloom))
+        cl.dispatch("postprocess_PS_PostProcess", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1), push=pk)
+        self.post_consts = (hk, ak, pk)
+
     # ---- BasePassRenderer::GenerateHZB (:505-542) + SPD::Execute (FFXHelpers.cpp:36-115) --------
     def _generate_hzb(self, cl):
         if self.freeze:
@@ -363,6 +428,8 @@ class FrameDriver:
             cl.end_pipeline_stats(query)
         if self.lighting_on:                                                             # the next renderer after GBufferRenderer
             self._deferred_lighting(cl)
+        if self.post_on:                                                                 # Scene.cpp's order: adapt luminance, then post
+            self._post_process(cl)
         cl.close()
         return cl
 
@@ -397,6 +464,6 @@ class FrameDriver:
         for b in (self.lateArgs, self.lateCount, self.lateIds, self.spdAtomic, self.dummy, *(self.shardInfo or ())):
             b.release()
         self.hzb.release(); self.depth.release()
-        for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output):
+        for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram):
             if t is not None:
                 t.release()

@@ -30,6 +30,8 @@ HOST_SYMBOLS = [
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
     "trhost_get_deferred_lighting_consts",
+    "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
+    "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # trhost_allgather_fn
@@ -96,6 +98,15 @@ def load() -> C.CDLL:
     L.trhost_upload_shadow_mask.argtypes = [vp, u64]
     L.trhost_download_lighting_output.argtypes = [vp, u64]
     L.trhost_get_deferred_lighting_consts.argtypes = [vp]
+    L.trhost_set_post_process.argtypes = [C.c_int]
+    L.trhost_set_exposure.argtypes = [C.c_float, C.c_float]
+    L.trhost_set_auto_exposure.argtypes = [C.c_float, C.c_float, C.c_float]
+    L.trhost_set_frame_time_ms.argtypes = [C.c_float]
+    L.trhost_upload_bloom.argtypes = [vp, u64, C.c_float]
+    L.trhost_download_back_buffer.argtypes = [vp, u64]
+    L.trhost_get_scene_luminance.argtypes = [vp, vp]
+    L.trhost_reset_exposure.argtypes = []
+    L.trhost_get_post_process_consts.argtypes = [vp, vp, vp, vp]
     L.trhost_upload_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_download_hzb_mip.argtypes = [u32, vp, u64]
     L.trhost_hzb_info.argtypes = [C.POINTER(u32)] * 3
@@ -300,6 +311,51 @@ class Renderer:
         k = np.zeros(1, I.DeferredLightingConsts)
         _check(load().trhost_get_deferred_lighting_consts(k.ctypes.data))
         return k
+
+    def set_post_process(self, on: bool = True):
+        """AdaptLuminanceRenderer and PostProcessRenderer after DeferredLightingRenderer (implies deferred lighting; include/trhost.h)."""
+        _check(load().trhost_set_post_process(int(on)))
+
+    def set_exposure(self, manual: float = 0.0, middle_gray: float = 0.18):
+        _check(load().trhost_set_exposure(float(manual), float(middle_gray)))
+
+    def set_auto_exposure(self, min_luminance: float = 0.004, max_luminance: float = 12.0, speed_per_ms: float = 0.0025):
+        _check(load().trhost_set_auto_exposure(float(min_luminance), float(max_luminance), float(speed_per_ms)))
+
+    def set_frame_time_ms(self, ms: float):
+        _check(load().trhost_set_frame_time_ms(float(ms)))
+
+    def upload_bloom(self, words, strength: float = 0.0):
+        """uint32 [H, W] R11G11B10_FLOAT bloom texture at render resolution and its strength; None switches bloom off."""
+        if words is None:
+            _check(load().trhost_upload_bloom(None, 0, float(strength)))
+            return
+        w = np.ascontiguousarray(words, np.uint32)
+        _check(load().trhost_upload_bloom(w.ctypes.data, w.nbytes, float(strength)))
+
+    def download_back_buffer(self) -> np.ndarray:
+        """The last frame's back buffer: uint32 [H, W] RGBA8_UNORM words, R in the low byte."""
+        self.wait_idle()
+        w = np.empty((self.render[1], self.render[0]), np.uint32)
+        _check(load().trhost_download_back_buffer(w.ctypes.data, w.nbytes))
+        return w
+
+    def scene_luminance(self):
+        """(adapted luminance, exposure) as they are now, float32 scalars."""
+        lum, exp = np.zeros(1, np.float32), np.zeros(1, np.float32)
+        _check(load().trhost_get_scene_luminance(lum.ctypes.data, exp.ctypes.data))
+        return lum[0], exp[0]
+
+    def reset_exposure(self):
+        _check(load().trhost_reset_exposure())
+
+    def post_process_consts(self):
+        """(GenerateLuminanceHistogramParameters, AdaptExposureParameters, PostProcessParameters) of the last frame, 1 element
+        each; the first two are None when the last frame had a manual exposure."""
+        hk, ak, pk = np.zeros(1, I.GenerateLuminanceHistogramParameters), np.zeros(1, I.AdaptExposureParameters), np.zeros(1, I.PostProcessParameters)
+        ran = C.c_int(0)
+        _check(load().trhost_get_post_process_consts(hk.ctypes.data, ak.ctypes.data, pk.ctypes.data, C.addressof(ran)))
+        return (hk, ak, pk) if ran.value else (None, None, pk)
 
     def download_depth(self) -> np.ndarray:
         self.wait_idle()

@@ -74,12 +74,21 @@ DeferredLightingConsts = np.dtype([                                             
     ("m_ClipToWorld", np.float32, (4, 4)), ("m_CameraOrigin", np.float32, (3,)), ("m_SSAOEnabled", np.uint32), ("m_DebugMode", np.uint32),
     ("m_DirectionalLightVector", np.float32, (3,)), ("m_DirectionalLightStrength", np.float32), ("m_LightingOutputResolution", np.uint32, (2,)),
     ("m_bRTDDGIEnabled", np.uint32)])
+GenerateLuminanceHistogramParameters = np.dtype([                                                                          # ShaderInterop.h:124-129
+    ("m_SrcColorDims", np.uint32, (2,)), ("m_MinLogLuminance", np.float32), ("m_InverseLogLuminanceRange", np.float32)])
+AdaptExposureParameters = np.dtype([                                                                                       # ShaderInterop.h:40-47
+    ("m_MinLogLuminance", np.float32), ("m_LogLuminanceRange", np.float32), ("m_AdaptationSpeed", np.float32), ("m_NbPixels", np.uint32),
+    ("m_MiddleGray", np.float32)])
+PostProcessParameters = np.dtype([                                                                                         # ShaderInterop.h:234-241
+    ("m_OutputDims", np.uint32, (2,)), ("m_ManualExposure", np.float32), ("m_MiddleGray", np.float32), ("m_WhitePoint", np.float32),
+    ("m_BloomStrength", np.float32)])
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
     "MeshletAmplificationData": 12, "DispatchIndirectArguments": 12, "GPUCullingPassConstants": 180,
     "BasePassConstants": 256, "MinMaxDownsampleConsts": 12, "NodeLocalTransform": 48,
     "TextureData": 20, "MaterialData": 124, "DeferredLightingConsts": 112,
+    "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)
@@ -128,6 +137,16 @@ def clip_to_world(world_to_view, view_to_clip) -> np.ndarray:
             for j in range(4):
                 out[j, i] = np.float32(cof[i][j] / det + np.float64(0.0))
     return out
+
+
+def log_luminance_range(min_luminance, max_luminance):
+    """(minLogLum, maxLogLum) of AdaptLuminanceRenderer.cpp:155-156: log2 of the float32 luminance in float64, rounded once to
+    float32.  One definition for both host sides (csrc/host does the same two operations), so that the GPU is handed the same
+    words.  The pass constants derived from them are float32 operations: range = max - min, inverse = 1.0f / range."""
+    import math
+    lo = np.float32(math.log2(float(np.float32(min_luminance))))
+    hi = np.float32(math.log2(float(np.float32(max_luminance))))
+    return lo, hi
 
 
 def get_next_pow2(x: int) -> int:

@@ -21,6 +21,7 @@ FORMAT_RGBA32_UINT = 5    # GBufferA: four u32 per texel (x, y, z, w)
 FORMAT_R11G11B10_FLOAT = 6  # LightingOutput: one u32 per texel, R bits 0-10, G 11-21, B 22-31
 FORMAT_R8_UNORM = 7       # shadow mask: one byte per texel
 FORMAT_R8_UINT = 8        # SSAO texture: one byte per texel
+FORMAT_RGBA8_UNORM = 10   # back buffer: one u32 per texel, R in the low byte (9 is not a format)
 
 BIND_CONSTANT_BUFFER, BIND_PUSH_CONSTANTS, BIND_STRUCTURED_SRV, BIND_STRUCTURED_UAV, BIND_TEXTURE_SRV, BIND_TEXTURE_UAV, BIND_SAMPLER = range(7)
 
@@ -237,7 +238,7 @@ class Texture:
 
     def _dtype(self):
         return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32,
-                FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8}.get(self.format, np.float32)
+                FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8, FORMAT_RGBA8_UNORM: np.uint32}.get(self.format, np.float32)
 
     def _shape(self, mw: int, mh: int):
         return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw, 4) if self.format == FORMAT_RGBA32_UINT else (mh, mw)
