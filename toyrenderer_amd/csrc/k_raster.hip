@@ -31,8 +31,12 @@
 // Triangles with index >= 128 (out of contract: kMaxMeshletTriangles is 96) write depth but no visibility texel; a list
 // capacity above 2^23 entries is refused at record time.  The tile launch keeps a 64x64 tile of u64 beside the depth tile
 // in LDS; its far-depth early-out reads the visibility words and stays a strict "<", so a triangle that can tie the kept
-// depth is still drawn (it can win the payload).  The depth instantiation keeps its kernels, launches, op names and
-// arithmetic; the compiler schedules and allocates its registers slightly differently (tiles: 58 VGPRs instead of 55).
+// depth is still drawn (it can win the payload).  The early-out is taken only for a triangle whose largest vertex depth
+// lies in [kSkipMinDepth, kSkipMaxDepth) = [2^-30, 1 - 2^-21): the range in which its samples are proven to stay below
+// that depth times kSkipFactor (derivation at the constants; below it the products of weights and depths round in the
+// subnormal range and samples exceed the bound, tests/test_raster_path_scenes.py).  The depth instantiation keeps its
+// kernels, launches, op names and arithmetic; the compiler schedules and allocates its registers slightly differently
+// (tiles: 58 VGPRs instead of 55).
 // tools/raster_time.py at 3840x2160, per launch, before / after the template: main 142.4 / 146.7 us, tiles 179.4 / 176.5 us.
 #include "mesh_stage.hip.h"
 
@@ -49,6 +53,27 @@ constexpr uint32_t kQueueCapacity = 1u << 20;   // 48 MB; beyond it triangles ar
 constexpr uint32_t kTileList = 1024;            // queued triangles a tile handles per round
 constexpr uint32_t kBinShift = 8;               // coarse bins of 256x256 pixels (4x4 tiles): a tile scans its bin's list, not the whole queue
 constexpr uint32_t kBinCapacity = 1u << 16;     // queue indices per bin; a fuller bin makes its tiles scan the whole queue
+
+// The tile pass's far-depth early-out skips a queued triangle when M * kSkipFactor < tileFar, M = max(d0,d1,d2), and
+// M lies in [kSkipMinDepth, kSkipMaxDepth).  Inside that range every sample d of the triangle is < tileFar.  With
+// u = 2^-24, e_i >= 0 the weights of a covered centre, S = e0 + e1 + e2 exactly and den = fl(fl(e0 + e1) + e2):
+//   * Screen coordinates come from fma(x, half, half) with half >= 0.5, so each is 0 or at least 2^-25 in magnitude: a
+//     multiple of 2^-48.  Pixel centres are multiples of 2^-1.  The differences in edgeFn are then multiples of 2^-48,
+//     its two products and its result multiples of 2^-96 (rounding only coarsens): a weight is 0 or >= 2^-96, and
+//     den >= 2^-96 where den > 0.  The sums of the weights do not underflow: den >= S (1 - u)^2.
+//   * The numerator fma(e2, d2, fma(e1, d1, e0 * d0)) rounds three times, each time by at most u relative where the
+//     result is normal and by at most 2^-150 absolute where it is not.  Terms with d_i <= 0 only lower it, so it is at
+//     most S M (1 + u)^3 + 3 * 2^-150, and it stays finite because den is finite and M < 1 - 8u.
+//   * The division rounds once more: d <= M (1 + u)^4 / (1 - u)^2 + 3.01 * 2^-150 / den + 2^-150
+//                                      <= M (1 + 7u) + 2^-52.
+//     The last term is the one the normal range hides: it is at most 4u M exactly when M >= 2^-30.  Below that, or with
+//     a smaller den, a product e_i * d_i rounds in the subnormal range and a sample can exceed M by any factor.
+//   * So d <= M (1 + 11u) < M (1 + 16u)(1 - u) <= fl(M * kSkipFactor) < tileFar.  Strictly: the triangle cannot tie either.
+// A triangle outside the range is drawn: depth = near / w, so M < 2^-30 needs w > 2^30 near and M >= 1 - 2^-21 a vertex
+// within 2^-21 of the near plane.
+constexpr float kSkipFactor = 0x1.00001p+0f;    // 1 + 16u
+constexpr float kSkipMinDepth = 0x1p-30f;
+constexpr float kSkipMaxDepth = 0x1.fffffp-1f;  // 1 - 8u
 
 struct BigTriangle                              // 48 bytes
 {
@@ -278,8 +303,7 @@ __device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& 
             any |= m != 0;
             for (uint32_t k = 0; k < m; ++k) {
                 // Every 32 triangles: the farthest depth the tile holds so far.  A triangle none of whose samples can be
-                // nearer than that cannot change a maximum and is skipped (its samples are at most max(d0,d1,d2) times
-                // (1 + 6 * 2^-24): three roundings in the fma chain, two in the sum of the weights, one in the division).
+                // nearer than that cannot change a maximum and is skipped: see kSkipMinDepth for the bound on its samples.
                 if ((k & 31u) == 0u && (k != 0u || any)) {
                     uint32_t mn = 0xFFFFFFFFu;
                     const uint32_t w = tx1 - tx0 + 1u, h = ty1 - ty0 + 1u;
@@ -298,7 +322,8 @@ __device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& 
                     tileFar = __uint_as_float(min(min(s_waveMin[0], s_waveMin[1]), min(s_waveMin[2], s_waveMin[3])));   // depths are > 0: bit order = value order
                 }
                 const BigTriangle q = a.queue[s_list[k]];
-                if (cm::max_(cm::max_(q.d0, q.d1), q.d2) * 0x1.00001p+0f < tileFar) continue;     // NaN or inf: never skipped
+                const float far = cm::max_(cm::max_(q.d0, q.d1), q.d2);
+                if (far * kSkipFactor < tileFar && far >= kSkipMinDepth && far < kSkipMaxDepth) continue;   // NaN or inf: never skipped
                 const uint32_t bx0 = max(q.boxX & 0xFFFFu, tx0), bx1 = min(q.boxX >> 16, tx1);
                 const uint32_t by0 = max(q.boxY & 0xFFFFu, ty0), by1 = min(q.boxY >> 16, ty1);
                 unsigned long long qp = 0ull;                                              // (1 << 32 | payload), or 0 = no texel
