@@ -45,7 +45,9 @@ enum {
 
 /* nvrhi::Format subset used on the path (GraphicConstants.h:25-28).  RG32_UINT (the visibility buffer: each texel one
  * little-endian u64), RG16_FLOAT (the motion target, GBufferMotion) and RGBA32_UINT (GBufferA, GraphicConstants.h:24: 16 bytes per
- * texel, little-endian words x, y, z, w) have one mip only.  So do the deferred lighting pass's formats: R11G11B10_FLOAT
+ * texel, little-endian words x, y, z, w) have one mip only.  So do the deferred lighting pass's formats (with one exception: an
+ * R11G11B10_FLOAT texture created as a render target, isUAV & TRHIP_TEXTURE_RENDER_TARGET, may have a mip chain: the bloom
+ * texture of BloomRenderer.cpp:41-50, whose mips "bloom_PS_Downsample" / "bloom_PS_Upsample" write): R11G11B10_FLOAT
  * (LightingOutput, GraphicConstants::kLightingOutputFormat: 4 bytes per texel, R in bits 0-10, G in bits 11-21, B in bits 22-31;
  * unsigned floats of 5 exponent bits with 6, 6 and 5 mantissa bits), R8_UNORM (the shadow mask) and R8_UINT (the SSAO texture),
  * one byte per texel each.  RGBA8_UNORM (the back buffer, GraphicRHI.cpp:214: 4 bytes per texel, R in the low byte, one mip) is
@@ -98,7 +100,16 @@ uint32_t    trhip_abi_version(void);
  * over m_OutputDims; b0 or push constants PostProcessParameters (24 bytes), t0 (texture) the R11G11B10_FLOAT colour, t1 the
  * luminance buffer (required only when m_ManualExposure == 0), t2 (texture) R11G11B10_FLOAT bloom (optional: unbound reads
  * (0, 0, 0)), u0 (texture) the RGBA8_UNORM target; samplers are accepted and ignored.  Every texel is written, alpha 255.
- * The arithmetic convention of the three is stated in csrc/k_postprocess.hip. */
+ * A t2 with a mip chain (the generated bloom texture) is read at mip 0.
+ * The arithmetic convention of the three is stated in csrc/k_postprocess.hip.
+ * "bloom_PS_Downsample" and "bloom_PS_Upsample" (bloom.hlsl, BloomRenderer.cpp; the stand-ins of the full-screen passes of
+ * Graphic.cpp:832-860): a direct dispatch of [numthreads(8, 8, 1)] groups covering the destination mip; b0 or push constants
+ * BloomConsts (16 bytes: the downsample reads m_InvSourceResolution and m_bIsFirstDownsample, the upsample m_FilterRadius), t0
+ * (texture) the R11G11B10_FLOAT source, read at the binding's baseMip, u0 (texture) the R11G11B10_FLOAT destination at its
+ * baseMip, whose size is the viewport; samplers are accepted and ignored (linear clamp, filtered in software, is the only
+ * behaviour).  Every texel of the destination mip is written and no other (the upsample overwrites: BlendOpaque).  Refused at
+ * record time: another format at t0 or u0, a missing binding, a mip out of range, t0 and u0 naming the same mip of one texture.
+ * The arithmetic convention is stated in csrc/k_bloom.hip. */
 uint32_t    trhip_shader_count(void);
 const char* trhip_shader_name(uint32_t index);
 int         trhip_shader_exists(const char* name);
@@ -131,10 +142,13 @@ typedef struct {
 typedef struct {
     uint32_t    width, height, mipLevels;
     uint32_t    format;             /* TRHIP_FORMAT_*                                          */
-    uint32_t    isUAV;
+    uint32_t    isUAV;              /* bit 0: UAV; bit 1: TRHIP_TEXTURE_RENDER_TARGET                */
     uint32_t    isVirtual;
     const char* debugName;
 } trhip_texture_desc;
+/* nvrhi::TextureDesc::isRenderTarget, or'ed into isUAV: the texture's mips are the targets of full-screen passes, which this
+ * back end writes through Texture_UAV bindings.  Only such a texture of R11G11B10_FLOAT may have more than one mip. */
+#define TRHIP_TEXTURE_RENDER_TARGET 2u
 
 int  trhip_heap_create(trhip_device dev, uint64_t bytes, trhip_heap* out);     /* nvrhi createHeap */
 void trhip_heap_release(trhip_heap heap);
@@ -195,7 +209,7 @@ typedef struct {
     uint32_t type;       /* trhip_binding_type                                                  */
     uint32_t slot;
     void*    resource;   /* trhip_buffer or trhip_texture (NULL for push constants / sampler)   */
-    uint32_t baseMip;    /* Texture_UAV subresource                                             */
+    uint32_t baseMip;    /* Texture_UAV subresource; Texture_SRV: read by bloom_PS_* only       */
     uint32_t reserved;
 } trhip_binding;
 

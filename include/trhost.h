@@ -112,12 +112,23 @@ int  trhost_get_deferred_lighting_consts(void* out112);
  * (the reference's two-frame-late read-backs are not modelled); trhost_reset_exposure sets both back to 1.0.
  * trhost_get_post_process_consts copies the parameter structs of the last frame: 16 bytes GenerateLuminanceHistogramParameters,
  * 20 bytes AdaptExposureParameters (both as of the last frame that adapted; *adapt_ran tells whether the last one did) and 24
- * bytes PostProcessParameters; any pointer may be NULL. */
+ * bytes PostProcessParameters; any pointer may be NULL.
+ * Bloom generation (BloomRenderer.cpp; off by default): trhost_set_bloom(1, nbMips, filterRadius, strength) schedules
+ * BloomRenderer between DeferredLightingRenderer and AdaptLuminanceRenderer: nbMips - 1 "bloom_PS_Downsample" and as many
+ * "bloom_PS_Upsample" dispatches over an R11G11B10_FLOAT texture of nbMips mips, which "postprocess_PS_PostProcess" then reads
+ * at t2 with `strength` (the reference's defaults: 6, 0.005, 0.1).  Refused: post-processing off; nbMips < 2 or above
+ * floor(log2(min(W, H))) + 1; a radius that is negative or not finite; an uploaded bloom texture still set -- and while
+ * generation is on trhost_upload_bloom refuses a texture.  trhost_set_bloom(0, ...) switches it off.  trhost_download_bloom
+ * waits and copies one mip ((W >> mip) x (H >> mip) words); trhost_get_bloom_consts copies the 16 bytes of BloomConsts of pass
+ * `pass` < 2 * (nbMips - 1) of the last frame, downsamples first. */
 int  trhost_set_post_process(int enable);
 int  trhost_set_exposure(float manual, float middle_gray);
 int  trhost_set_auto_exposure(float min_lum, float max_lum, float speed_per_ms);
 int  trhost_set_frame_time_ms(float ms);
 int  trhost_upload_bloom(const uint32_t* words, uint64_t bytes, float strength);
+int  trhost_set_bloom(int enable, uint32_t nb_mips, float filter_radius, float strength);
+int  trhost_download_bloom(uint32_t mip, uint32_t* words, uint64_t bytes);
+int  trhost_get_bloom_consts(uint32_t pass, void* out16);
 int  trhost_download_back_buffer(uint32_t* words, uint64_t bytes);
 int  trhost_get_scene_luminance(float* luminance, float* exposure);
 int  trhost_reset_exposure(void);

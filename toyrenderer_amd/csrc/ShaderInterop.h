@@ -47,6 +47,7 @@ static constexpr uint32_t kMaxMeshletTriangles = 96;
 static constexpr uint32_t kMaxNumMeshLODs = 8;
 static constexpr uint32_t kInvalidMeshLOD = 0xFF;
 
+struct Vector2 { float x, y; };
 struct Vector2U { uint32_t x, y; };
 struct Vector3U { uint32_t x, y, z; };
 struct Vector4 { float x, y, z, w; };
@@ -153,6 +154,15 @@ struct PostProcessParameters
     float m_BloomStrength;
 };
 static_assert(sizeof(PostProcessParameters) == 24 && offsetof(PostProcessParameters, m_ManualExposure) == 8 && offsetof(PostProcessParameters, m_BloomStrength) == 20, "PostProcessParameters");
+
+// ShaderInterop.h:79-84: push constants (or b0) of "bloom_PS_Downsample" and "bloom_PS_Upsample"
+struct BloomConsts
+{
+    Vector2 m_InvSourceResolution;          // downsample: 1 / (W >> i, H >> i) of the mip read
+    float m_FilterRadius;                   // upsample: the tap distance in UV
+    uint32_t m_bIsFirstDownsample;          // downsample: the Karis-weighted branch
+};
+static_assert(sizeof(BloomConsts) == 16 && offsetof(BloomConsts, m_InvSourceResolution) == 0 && offsetof(BloomConsts, m_FilterRadius) == 8 && offsetof(BloomConsts, m_bIsFirstDownsample) == 12, "BloomConsts");
 
 // ShaderInterop.h:117-122
 struct DispatchIndirectArguments

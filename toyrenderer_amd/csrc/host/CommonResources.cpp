@@ -8,6 +8,7 @@ void CommonResources::Initialize()
     nvrhi::SamplerDesc point;
     point.minFilter = point.magFilter = point.mipFilter = false;
     PointClampSampler = device->createSampler(point);
+    LinearClampSampler = device->createSampler(nvrhi::SamplerDesc{});
     nvrhi::SamplerDesc minReduction;                                          // CommonResources.cpp:276-287,298
     minReduction.reductionType = nvrhi::SamplerReductionType::Minimum;
     LinearClampMinReductionSampler = device->createSampler(minReduction);

@@ -11,6 +11,7 @@ public:
     void Initialize();
 
     nvrhi::SamplerHandle PointClampSampler;
+    nvrhi::SamplerHandle LinearClampSampler;               // min/mag/mip linear, clamp: the bloom passes' sampler (BloomRenderer.cpp)
     nvrhi::SamplerHandle LinearClampMinReductionSampler;   // min/mag/mip linear, clamp, SamplerReductionType::Minimum
     nvrhi::BufferHandle DummyUIntStructuredBuffer;         // bound when occlusion culling is off (BasePassRenderers.cpp:318-320)
     nvrhi::TextureHandle BlackTexture;                     // bound as HZB when occlusion culling is off (:357)

@@ -2,8 +2,9 @@
 // PBRNeutralToneMapping and LinearToSRGB from LightingOutput into the RGBA8_UNORM back buffer, "postprocess_PS_PostProcess"
 // (csrc/k_postprocess.hip).
 //
-// Out of scope, as in the back end: TAA (the input is always LightingOutput) and bloom generation (the bloom texture is an input,
-// trhost_upload_bloom; without one t2 stays unbound: black, the reference's BlackTexture, and the strength is 0).  There is no
+// Out of scope, as in the back end: TAA (the input is always LightingOutput).  The bloom texture at t2 is BloomRenderer's when
+// generation is on (trhost_set_bloom), else the uploaded one (trhost_upload_bloom); without either t2 stays unbound: black, the
+// reference's BlackTexture, and the strength is 0.  There is no
 // swap chain: the back buffer is a texture owned here, read back by trhost_download_back_buffer.  The full-screen triangle is a
 // direct dispatch of 8x8 groups.
 #include "Graphic.h"
@@ -29,6 +30,8 @@ public:
     PostProcessParameters m_LastParams{};
     bool m_bHasLastParams = false;
 
+    static nvrhi::TextureHandle BloomTexture() { return g_Scene->m_bEnableBloom ? GetGeneratedBloomTexture() : g_Scene->m_BloomTexture; }
+
     bool Setup(RenderGraph& renderGraph) override
     {
         if (!g_Scene->m_bPostProcess || g_Scene->m_NumPrimitives == 0) return false;
@@ -41,7 +44,7 @@ public:
             desc.isUAV = true;                       // this build: the pass stores through a UAV
             m_BackBuffer = g_Graphic.m_NVRHIDevice->createTexture(desc);
         }
-        if (g_Scene->m_BloomTexture) renderGraph.AddExternalReadDependency(g_Scene->m_BloomTexture.Get());   // :20-23
+        if (BloomTexture()) renderGraph.AddExternalReadDependency(BloomTexture().Get());   // :20-23
         renderGraph.AddExternalReadDependency(GetLightingOutput().Get());     // :29-32
         renderGraph.AddExternalReadDependency(g_Scene->m_LuminanceBuffer.Get());
         renderGraph.AddExternalWriteDependency(m_BackBuffer.Get());
@@ -50,7 +53,8 @@ public:
 
     void Render(nvrhi::CommandListHandle commandList, const RenderGraph&) override
     {
-        const bool bloom = g_Scene->m_BloomTexture != nullptr;
+        const nvrhi::TextureHandle bloomTexture = BloomTexture();
+        const bool bloom = bloomTexture != nullptr;
         PostProcessParameters passParameters{};                               // :46-50
         passParameters.m_OutputDims = g_Graphic.m_RenderResolution;
         passParameters.m_ManualExposure = g_Scene->m_ManualExposureOverride;
@@ -65,7 +69,7 @@ public:
         p.m_ShaderName = "postprocess_PS_PostProcess";
         p.m_BindingSetDesc.bindings = { Item::PushConstants(0, sizeof(passParameters)), Item::Texture_SRV(0, GetLightingOutput()),
                                         Item::StructuredBuffer_SRV(1, g_Scene->m_LuminanceBuffer), Item::Texture_UAV(0, m_BackBuffer) };
-        if (bloom) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(2, g_Scene->m_BloomTexture));
+        if (bloom) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(2, bloomTexture));
         p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Graphic.m_RenderResolution, 8);
         p.m_PushConstantsData = &passParameters;
         p.m_PushConstantsBytes = sizeof(passParameters);

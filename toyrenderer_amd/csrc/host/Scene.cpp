@@ -17,6 +17,7 @@
 extern IRenderer* g_UpdateInstanceConstsRenderer;
 extern IRenderer* g_GBufferRenderer;
 extern IRenderer* g_DeferredLightingRenderer;
+extern IRenderer* g_BloomRenderer;
 extern IRenderer* g_AdaptLuminanceRenderer;
 extern IRenderer* g_PostProcessRenderer;
 extern IRenderer* g_GIDebugRenderer;
@@ -220,7 +221,8 @@ void Scene::Update()
         m_RenderGraph->AddRenderer(g_UpdateInstanceConstsRenderer);
         m_RenderGraph->AddRenderer(g_GBufferRenderer);
         if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
-        if (m_bPostProcess) {                                                 // :505, :507 (sky, bloom, transparents and TAA between them are not built)
+        if (m_bPostProcess && m_bEnableBloom) m_RenderGraph->AddRenderer(g_BloomRenderer);   // :503
+        if (m_bPostProcess) {                                                 // :505, :507 (sky, transparents and TAA between them are not built)
             m_RenderGraph->AddRenderer(g_AdaptLuminanceRenderer);
             m_RenderGraph->AddRenderer(g_PostProcessRenderer);
         }

@@ -114,6 +114,12 @@ public:
     float m_CPUCappedFrameTimeMs = 16.0f;            // Engine::m_CPUCappedFrameTimeMs: set by the application (trhost_set_frame_time_ms), no clock here
     nvrhi::TextureHandle m_BloomTexture;             // R11G11B10_FLOAT at render resolution, or null: the pass reads black (the reference's BlackTexture)
     float m_BloomStrength = 0.0f;
+    // Bloom generation (trhost_set_bloom; needs m_bPostProcess, excludes an uploaded m_BloomTexture): BloomRenderer runs between
+    // DeferredLightingRenderer and AdaptLuminanceRenderer and PostProcessRenderer binds its texture.  The mip count and the
+    // radius are members of the renderer in the reference (BloomRenderer.cpp:16-17, defaults 6 and 0.005f).
+    bool m_bEnableBloom = false;
+    uint32_t m_NbBloomMips = 6;
+    float m_BloomFilterRadius = 0.005f;
     nvrhi::BufferHandle m_LuminanceBuffer;           // Scene.h: one float, the adapted luminance; survives across frames
     nvrhi::TextureHandle m_ExposureTexture;          // 1 x 1 R32_FLOAT
     // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.

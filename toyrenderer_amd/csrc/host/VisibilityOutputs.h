@@ -55,6 +55,11 @@ nvrhi::TextureHandle GetBackBuffer();
 bool GetLastPostProcessConsts(void* histogram16, void* adapt20, void* post24, int* adaptRan);
 void ResetExposure();
 void ReleasePostProcessOutputs();
+// BloomRenderer's texture (R11G11B10_FLOAT, Scene::m_NbBloomMips mips) and the BloomConsts of pass `pass` of the last recorded
+// frame (downsamples first); null / false until a frame ran with bloom generation on.
+nvrhi::TextureHandle GetGeneratedBloomTexture();
+bool GetLastBloomConsts(uint32_t pass, void* out16);
+void ReleaseBloomOutputs();
 // the base pass's pipeline statistics: the value its frame N showed (the query of frame N - 2) and the last executed frame's (waits)
 void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest);
 

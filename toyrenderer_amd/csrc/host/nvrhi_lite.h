@@ -271,7 +271,10 @@ struct BindingSetItem
     static BindingSetItem PushConstants(uint32_t slot, uint32_t bytes) { BindingSetItem i; i.type = TRHIP_BIND_PUSH_CONSTANTS; i.slot = slot; i.pushBytes = bytes; return i; }
     static BindingSetItem StructuredBuffer_SRV(uint32_t slot, IBuffer* b) { BindingSetItem i; i.type = TRHIP_BIND_STRUCTURED_SRV; i.slot = slot; i.buffer = b; return i; }
     static BindingSetItem StructuredBuffer_UAV(uint32_t slot, IBuffer* b) { BindingSetItem i; i.type = TRHIP_BIND_STRUCTURED_UAV; i.slot = slot; i.buffer = b; return i; }
-    static BindingSetItem Texture_SRV(uint32_t slot, ITexture* t) { BindingSetItem i; i.type = TRHIP_BIND_TEXTURE_SRV; i.slot = slot; i.texture = t; return i; }
+    static BindingSetItem Texture_SRV(uint32_t slot, ITexture* t, Format = Format::UNKNOWN, TextureSubresourceSet s = TextureSubresourceSet{})
+    {
+        BindingSetItem i; i.type = TRHIP_BIND_TEXTURE_SRV; i.slot = slot; i.texture = t; i.baseMip = s.baseMipLevel; return i;
+    }
     static BindingSetItem Texture_UAV(uint32_t slot, ITexture* t, Format = Format::UNKNOWN, TextureSubresourceSet s = TextureSubresourceSet{})
     {
         BindingSetItem i; i.type = TRHIP_BIND_TEXTURE_UAV; i.slot = slot; i.texture = t; i.baseMip = s.baseMipLevel; return i;
@@ -421,7 +424,7 @@ public:
     TextureHandle createTexture(const TextureDesc& d)
     {
         trhip_texture_desc n{};
-        n.width = d.width; n.height = d.height; n.mipLevels = d.mipLevels; n.isUAV = d.isUAV; n.isVirtual = d.isVirtual; n.debugName = d.debugName.c_str();
+        n.width = d.width; n.height = d.height; n.mipLevels = d.mipLevels; n.isUAV = (d.isUAV ? 1u : 0u) | (d.isRenderTarget ? TRHIP_TEXTURE_RENDER_TARGET : 0u); n.isVirtual = d.isVirtual; n.debugName = d.debugName.c_str();
         // depth (D24S8 in the reference, GraphicConstants.h:26) is carried as 32-bit float depth here
         n.format = d.format == Format::R16_FLOAT ? TRHIP_FORMAT_R16_FLOAT : d.format == Format::RG32_UINT ? TRHIP_FORMAT_RG32_UINT
                  : d.format == Format::RG16_FLOAT ? TRHIP_FORMAT_RG16_FLOAT : d.format == Format::RGBA32_UINT ? TRHIP_FORMAT_RGBA32_UINT

@@ -2,6 +2,8 @@
 // bench.py) can drive the SAME code path a C++ application would: Graphic::Initialize ->
 // Scene::LoadFromArrays -> Graphic::Update per frame (Scene::Update -> RenderGraph -> renderers ->
 // AddComputePass -> C ABI -> HIP kernels).  Declared in include/trhost.h.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <exception>
 #include <string>
@@ -59,6 +61,7 @@ void trhost_shutdown(void)
         ReleaseGIProbeCullBuffers();
         ReleaseDeferredLightingOutputs();
         ReleasePostProcessOutputs();
+        ReleaseBloomOutputs();
         g_Graphic.Shutdown();
     });
     s_Initialized = false;
@@ -245,6 +248,10 @@ int trhost_upload_bloom(const uint32_t* words, uint64_t bytes, float strength)
 {
     return guarded([&] {
         check(g_Scene);
+        if (g_Scene->m_bEnableBloom) {
+            if (words) throw nvrhi::Error("trhost_upload_bloom: bloom generation is on (trhost_set_bloom): the renderer makes the texture itself");
+            return;                                                           // nothing uploaded to switch off
+        }
         g_Scene->m_BloomStrength = strength;
         if (!words) { g_Scene->m_BloomTexture = nullptr; return; }            // bloom off: black, strength 0
         if (!g_Scene->m_BloomTexture) {
@@ -256,6 +263,45 @@ int trhost_upload_bloom(const uint32_t* words, uint64_t bytes, float strength)
             g_Scene->m_BloomTexture = g_Graphic.m_NVRHIDevice->createTexture(desc);
         }
         nvrhi::throwIfFailed(trhip_texture_upload(g_Scene->m_BloomTexture->native(), 0, words, bytes), "trhost_upload_bloom");
+    });
+}
+
+int trhost_set_bloom(int enable, uint32_t nb_mips, float filter_radius, float strength)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!enable) { g_Scene->m_bEnableBloom = false; return; }             // the post pass reads black again, or a texture uploaded later
+        if (!g_Scene->m_bPostProcess) throw nvrhi::Error("trhost_set_bloom: post-processing is off (trhost_set_post_process first): nothing would read the texture");
+        if (g_Scene->m_BloomTexture) throw nvrhi::Error("trhost_set_bloom: an uploaded bloom texture is set (trhost_upload_bloom(NULL, 0, 0) first)");
+        const uint32_t smaller = std::min(g_Graphic.m_RenderResolution.x, g_Graphic.m_RenderResolution.y);
+        uint32_t most = 0;
+        while (smaller >> most) ++most;                                       // floor(log2(min(W, H))) + 1: every mip has a texel in both axes
+        if (nb_mips < 2 || nb_mips > most)
+            throw nvrhi::Error("trhost_set_bloom: " + std::to_string(nb_mips) + " mips: the chain needs at least 2 and a " + std::to_string(g_Graphic.m_RenderResolution.x) +
+                               "x" + std::to_string(g_Graphic.m_RenderResolution.y) + " image has at most " + std::to_string(most));
+        if (!(std::isfinite(filter_radius) && filter_radius >= 0.0f)) throw nvrhi::Error("trhost_set_bloom: the filter radius must be finite and >= 0");
+        g_Scene->m_bEnableBloom = true;
+        g_Scene->m_NbBloomMips = nb_mips;
+        g_Scene->m_BloomFilterRadius = filter_radius;
+        g_Scene->m_BloomStrength = strength;
+    });
+}
+
+int trhost_download_bloom(uint32_t mip, uint32_t* words, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetGeneratedBloomTexture();
+        if (!t) throw nvrhi::Error("trhost_download_bloom: no frame ran with bloom generation on");
+        check(words);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), mip, words, bytes), "trhost_download_bloom");
+    });
+}
+
+int trhost_get_bloom_consts(uint32_t pass, void* out16)
+{
+    return guarded([&] {
+        check(out16);
+        if (!GetLastBloomConsts(pass, out16)) throw nvrhi::Error("trhost_get_bloom_consts: pass " + std::to_string(pass) + " did not run in the last frame with bloom generation on");
     });
 }
 

@@ -1,8 +1,8 @@
 // k_postprocess.hip -- the two renderers between LightingOutput and the back buffer: "adaptluminance_CS_GenerateLuminanceHistogram"
 // and "adaptluminance_CS_AdaptExposure" (source/AdaptLuminanceRenderer.cpp, source/shaders/adaptluminance.hlsl) and
 // "postprocess_PS_PostProcess" (source/PostProcessRenderer.cpp, source/shaders/postprocess.hlsl: exposure, PBRNeutralToneMapping,
-// LinearToSRGB).  Sky, bloom generation, TAA, AO, the shadow mask and DDGI stay out of scope; bloom enters as an
-// optional input texture.
+// LinearToSRGB).  Sky, TAA, AO, the shadow mask and DDGI stay out of scope; bloom enters as an optional input
+// texture: the caller's, or the one k_bloom.hip generates (a mip chain, read at mip 0).
 //
 // CONVENTION (parity unpinned; restated in tests/postprocess_ref.c and DESIGN.md 3).  It extends the lighting convention
 // (k_deferredlighting.hip): IEEE binary32, no contraction, fma only where written, / correctly rounded, dot3 the fma chain,
@@ -324,7 +324,7 @@ int recordPostProcess(trhip::DispatchCtx& ctx)
         trhip_texture_t* t = ctx.texture(w.type, w.slot, &mip);
         if (!t && !w.required) continue;
         TRHIP_REQUIRE(t && t->format == w.format && (w.type != TRHIP_BIND_TEXTURE_UAV || mip == 0), "%s: needs %s", name, w.what);
-        TRHIP_REQUIRE(t->width == W && t->height == H && t->mips == 1, "%s: %s is %ux%u, m_OutputDims is %ux%u", name, w.what, t->width, t->height, W, H);
+        TRHIP_REQUIRE(t->width == W && t->height == H && (t->mips == 1 || (j == 1 && mip == 0)), "%s: %s is %ux%u, m_OutputDims is %ux%u", name, w.what, t->width, t->height, W, H);   // t2 may be the bloom chain: mip 0 is read
         tex[j] = t;
     }
     trhip_buffer_t* lum = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 1);

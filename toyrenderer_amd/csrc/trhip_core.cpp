@@ -482,7 +482,8 @@ int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_te
         return fail(TRHIP_ERR_INVALID, "texture_create: bad dimensions %ux%u mips %u", d->width, d->height, d->mipLevels);
     if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && d->format != TRHIP_FORMAT_RGBA8_UNORM)
         return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u", d->format);
-    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && d->mipLevels != 1)
+    const bool bloomChain = d->format == TRHIP_FORMAT_R11G11B10_FLOAT && (d->isUAV & TRHIP_TEXTURE_RENDER_TARGET);   // the bloom texture (BloomRenderer.cpp:41-50)
+    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && !bloomChain && d->mipLevels != 1)
         return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT / RGBA8_UNORM textures have one mip, got %u", d->mipLevels);
     auto t = std::make_unique<trhip_texture_t>();
     t->dev = dev;

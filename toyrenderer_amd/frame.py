@@ -83,7 +83,7 @@ class FrameDriver:
                  shard_late=None, raster_depth: bool = False, visibility: bool = False, gbuffer: bool = False,
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
-                 bloom=(None, 0.0)):
+                 bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -107,7 +107,16 @@ class FrameDriver:
         frame time; the driver has no clock); bloom = (rhi.Texture or None, strength): an R11G11B10_FLOAT texture at render
         resolution, None = unbound = black.  self.luminance (one float, 1.0 at construction and after reset_exposure()) and
         self.exposure_texture (1 x 1 R32_FLOAT) survive across record() and frames.  self.post_consts holds the three parameter
-        structs of the last record() (histogram, adapt, post; the first two None with a manual exposure)."""
+        structs of the last record() (histogram, adapt, post; the first two None with a manual exposure).
+        bloom_mips: 0 (the default) changes nothing.  >= 2 (needs post=True, and no external bloom texture): BloomRenderer
+        (BloomRenderer.cpp; the reference's defaults are 6 mips, radius 0.005, strength 0.1).  The driver owns self.bloom_texture,
+        an R11G11B10_FLOAT render target with that many mips; after the lighting dispatch and before the histogram clear it
+        records bloom_mips - 1 "bloom_PS_Downsample" dispatches (pass i reads mip i, LightingOutput for i = 0, and writes mip
+        i + 1) and bloom_mips - 1 "bloom_PS_Upsample" dispatches (each overwrites the next finer mip) and binds the texture,
+        read at mip 0, as the post pass's t2 with bloom_strength.  bloom_filter_radius: m_FilterRadius, in UV.  The count may
+        not exceed floor(log2(min(W, H))) + 1: every mip has at least one texel in both axes (the reference's slider allows
+        W >> k = 0; this project does not).  self.bloom_consts holds the BloomConsts of the last record(), downsamples first;
+        download_bloom(mip) reads a mip back."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -123,6 +132,22 @@ class FrameDriver:
         self.manual_exposure, self.middle_gray = np.float32(exposure[0]), np.float32(exposure[1])
         self.min_luminance, self.max_luminance, self.adaptation_speed = (np.float32(x) for x in auto_exposure)
         self.bloom, self.bloom_strength = bloom[0], np.float32(bloom[1])
+        self.bloom_mips = int(bloom_mips)
+        self.bloom_texture = self.bloom_consts = None
+        if self.bloom_mips != 0:
+            most = int(min(view.renderW, view.renderH)).bit_length()                     # floor(log2(min(W, H))) + 1
+            if self.bloom_mips < 2:
+                raise ValueError(f"bloom_mips = {self.bloom_mips}: the chain needs at least 2 mips (0 turns bloom generation off)")
+            if self.bloom_mips > most:
+                raise ValueError(f"bloom_mips = {self.bloom_mips}: a {view.renderW}x{view.renderH} image has at most {most} mips with a texel in both axes")
+            if not post:
+                raise ValueError("bloom_mips > 0 needs post=True: the post pass is what reads the bloom texture")
+            if bloom[0] is not None:
+                raise ValueError("bloom_mips > 0 together with an external bloom=(texture, strength): the driver generates the texture itself")
+            if not (np.isfinite(bloom_filter_radius) and bloom_filter_radius >= 0.0):
+                raise ValueError(f"bloom_filter_radius = {bloom_filter_radius}: needs a finite radius >= 0")
+            self.bloom_strength = np.float32(bloom_strength)
+        self.bloom_filter_radius = np.float32(bloom_filter_radius)
         self.post_consts = None
         self.dir_light = (tuple(float(x) for x in dir_light[0]), float(dir_light[1]))
         self.camera_origin = tuple(float(x) for x in camera_origin)
@@ -157,6 +182,9 @@ class FrameDriver:
             self.luminance = dev.create_buffer(4, "Exposure Buffer")
             self.histogram = dev.create_buffer(4 * 256, "Luminance Histogram")
             self.reset_exposure()
+        if self.bloom_mips:                          # BloomRenderer::Setup (BloomRenderer.cpp:41-50)
+            self.bloom_texture = dev.create_texture(view.renderW, view.renderH, self.bloom_mips, rhi.FORMAT_R11G11B10_FLOAT, "Bloom Texture",
+                                                    render_target=True)
         if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
@@ -327,6 +355,32 @@ class FrameDriver:
             b.append(TEX_SRV(4, self.shadow_mask))
         cl.dispatch("deferredlighting_PS_Main_Debug" if self.debug_mode != 0 else "deferredlighting_PS_Main", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
 
+    # ---- BloomRenderer::Render (BloomRenderer.cpp:57-141) ---------------------------------------------------------------
+    def _bloom(self, cl):
+        v, tex, n = self.view, self.bloom_texture, self.bloom_mips - 1
+        self.bloom_consts = np.zeros(2 * n, I.BloomConsts)
+
+        def groups(mip):
+            w, h = v.renderW >> mip, v.renderH >> mip
+            return ((w + 7) // 8, (h + 7) // 8, 1)
+        for i in range(n):                                                               # downsample: mip i -> mip i + 1
+            k = self.bloom_consts[i:i + 1]
+            k["m_bIsFirstDownsample"] = int(i == 0)
+            k["m_InvSourceResolution"] = (np.float32(1.0) / np.float32(v.renderW >> i), np.float32(1.0) / np.float32(v.renderH >> i))
+            src = TEX_SRV(0, self.lighting_output) if i == 0 else TEX_SRV(0, tex, i)
+            cl.dispatch("bloom_PS_Downsample", [PUSH(0), src, TEX_UAV(0, tex, i + 1), SAMPLER(0)], groups(i + 1), push=k)
+        for i in range(n):                                                               # upsample: mip n - i -> mip n - i - 1, overwritten
+            k = self.bloom_consts[n + i:n + i + 1]
+            k["m_FilterRadius"] = self.bloom_filter_radius
+            cl.dispatch("bloom_PS_Upsample", [PUSH(0), TEX_SRV(0, tex, n - i), TEX_UAV(0, tex, n - i - 1), SAMPLER(0)], groups(n - i - 1), push=k)
+
+    def download_bloom(self, mip: int = 0) -> np.ndarray:
+        """The words of one mip of the generated bloom texture, (H >> mip, W >> mip) uint32."""
+        if self.bloom_texture is None:
+            raise ValueError("download_bloom: bloom generation is off (bloom_mips = 0)")
+        self.dev.wait_idle()
+        return self.bloom_texture.download_mip(mip)
+
     # ---- AdaptLuminanceRenderer::Render (AdaptLuminanceRenderer.cpp:119-215) + PostProcessRenderer::Render (:37-74) -----
     def reset_exposure(self):
         """The adapted luminance and the exposure texel back to kInitialExposure = 1.0."""
@@ -361,10 +415,11 @@ class FrameDriver:
         pk["m_OutputDims"] = dims
         pk["m_ManualExposure"] = self.manual_exposure
         pk["m_MiddleGray"] = self.middle_gray
-        pk["m_BloomStrength"] = self.bloom_strength if self.bloom is not None else 0.0  # m_bEnableBloom ? m_BloomStrength : 0
+        bloom = self.bloom_texture if self.bloom_texture is not None else self.bloom     # generated, or the caller's
+        pk["m_BloomStrength"] = self.bloom_strength if bloom is not None else 0.0       # m_bEnableBloom ? m_BloomStrength : 0
         b = [PUSH(0), TEX_SRV(0, self.lighting_output), SRV(1, self.luminance), TEX_UAV(0, self.back_buffer, 0), SAMPLER(0)]
-        if self.bloom is not None:
-            b.append(TEX_SRV(2, self.bloom))
+        if bloom is not None:
+            b.append(TEX_SRV(2, bloom))
         cl.dispatch("postprocess_PS_PostProcess", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1), push=pk)
         self.post_consts = (hk, ak, pk)
 
@@ -428,6 +483,8 @@ class FrameDriver:
             cl.end_pipeline_stats(query)
         if self.lighting_on:                                                             # the next renderer after GBufferRenderer
             self._deferred_lighting(cl)
+        if self.bloom_mips:                                                              # Scene.cpp:503: between lighting and adapt luminance
+            self._bloom(cl)
         if self.post_on:                                                                 # Scene.cpp's order: adapt luminance, then post
             self._post_process(cl)
         cl.close()
@@ -464,6 +521,7 @@ class FrameDriver:
         for b in (self.lateArgs, self.lateCount, self.lateIds, self.spdAtomic, self.dummy, *(self.shardInfo or ())):
             b.release()
         self.hzb.release(); self.depth.release()
-        for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram):
+        for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
+                  self.bloom_texture):
             if t is not None:
                 t.release()

@@ -32,6 +32,7 @@ HOST_SYMBOLS = [
     "trhost_get_deferred_lighting_consts",
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
+    "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # trhost_allgather_fn
@@ -104,6 +105,9 @@ def load() -> C.CDLL:
     L.trhost_set_frame_time_ms.argtypes = [C.c_float]
     L.trhost_upload_bloom.argtypes = [vp, u64, C.c_float]
     L.trhost_download_back_buffer.argtypes = [vp, u64]
+    L.trhost_set_bloom.argtypes = [C.c_int, u32, C.c_float, C.c_float]
+    L.trhost_download_bloom.argtypes = [u32, vp, u64]
+    L.trhost_get_bloom_consts.argtypes = [u32, vp]
     L.trhost_get_scene_luminance.argtypes = [vp, vp]
     L.trhost_reset_exposure.argtypes = []
     L.trhost_get_post_process_consts.argtypes = [vp, vp, vp, vp]
@@ -332,6 +336,24 @@ class Renderer:
             return
         w = np.ascontiguousarray(words, np.uint32)
         _check(load().trhost_upload_bloom(w.ctypes.data, w.nbytes, float(strength)))
+
+    def set_bloom(self, enable: bool, mips: int = 6, filter_radius: float = 0.005, strength: float = 0.1):
+        """BloomRenderer on or off (needs set_post_process(True); excludes an uploaded bloom texture)."""
+        _check(load().trhost_set_bloom(int(bool(enable)), int(mips), float(filter_radius), float(strength)))
+
+    def download_bloom(self, mip: int = 0) -> np.ndarray:
+        """One mip of the generated bloom texture: uint32 [H >> mip, W >> mip] R11G11B10_FLOAT words."""
+        self.wait_idle()
+        w = np.empty((self.render[1] >> mip, self.render[0] >> mip), np.uint32)
+        _check(load().trhost_download_bloom(int(mip), w.ctypes.data, w.nbytes))
+        return w
+
+    def bloom_consts(self, passes: int) -> np.ndarray:
+        """The BloomConsts of the first `passes` bloom dispatches of the last frame, downsamples first."""
+        k = np.zeros(passes, I.BloomConsts)
+        for i in range(passes):
+            _check(load().trhost_get_bloom_consts(i, k[i:i + 1].ctypes.data))
+        return k
 
     def download_back_buffer(self) -> np.ndarray:
         """The last frame's back buffer: uint32 [H, W] RGBA8_UNORM words, R in the low byte."""

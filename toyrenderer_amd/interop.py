@@ -82,6 +82,7 @@ AdaptExposureParameters = np.dtype([                                            
 PostProcessParameters = np.dtype([                                                                                         # ShaderInterop.h:234-241
     ("m_OutputDims", np.uint32, (2,)), ("m_ManualExposure", np.float32), ("m_MiddleGray", np.float32), ("m_WhitePoint", np.float32),
     ("m_BloomStrength", np.float32)])
+BloomConsts = np.dtype([("m_InvSourceResolution", np.float32, (2,)), ("m_FilterRadius", np.float32), ("m_bIsFirstDownsample", np.uint32)])   # ShaderInterop.h:79-84
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
@@ -89,6 +90,7 @@ SIZES = {
     "BasePassConstants": 256, "MinMaxDownsampleConsts": 12, "NodeLocalTransform": 48,
     "TextureData": 20, "MaterialData": 124, "DeferredLightingConsts": 112,
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
+    "BloomConsts": 16,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)

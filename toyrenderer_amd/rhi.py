@@ -23,6 +23,8 @@ FORMAT_R8_UNORM = 7       # shadow mask: one byte per texel
 FORMAT_R8_UINT = 8        # SSAO texture: one byte per texel
 FORMAT_RGBA8_UNORM = 10   # back buffer: one u32 per texel, R in the low byte (9 is not a format)
 
+TEXTURE_RENDER_TARGET = 2   # or'ed into trhip_texture_desc.isUAV
+
 BIND_CONSTANT_BUFFER, BIND_PUSH_CONSTANTS, BIND_STRUCTURED_SRV, BIND_STRUCTURED_UAV, BIND_TEXTURE_SRV, BIND_TEXTURE_UAV, BIND_SAMPLER = range(7)
 
 # every symbol include/trhip.h declares (checked by tests/test_abi_symbols.py)
@@ -283,7 +285,7 @@ def CB(slot, buf): return bind(BIND_CONSTANT_BUFFER, slot, buf)
 def PUSH(slot): return bind(BIND_PUSH_CONSTANTS, slot)
 def SRV(slot, buf): return bind(BIND_STRUCTURED_SRV, slot, buf)
 def UAV(slot, buf): return bind(BIND_STRUCTURED_UAV, slot, buf)
-def TEX_SRV(slot, tex): return bind(BIND_TEXTURE_SRV, slot, tex)
+def TEX_SRV(slot, tex, mip=0): return bind(BIND_TEXTURE_SRV, slot, tex, mip)   # mip: read by bloom_PS_* only
 def TEX_UAV(slot, tex, mip=0): return bind(BIND_TEXTURE_UAV, slot, tex, mip)
 def SAMPLER(slot): return bind(BIND_SAMPLER, slot)
 
@@ -435,8 +437,9 @@ class Device:
             b.upload(arr)
         return b
 
-    def create_texture(self, w: int, h: int, mips: int, fmt: int, name="", uav=True) -> Texture:
-        d = TextureDesc(w, h, mips, fmt, int(uav), 0, name.encode())
+    def create_texture(self, w: int, h: int, mips: int, fmt: int, name="", uav=True, render_target=False) -> Texture:
+        """render_target: TRHIP_TEXTURE_RENDER_TARGET; only such an R11G11B10_FLOAT texture (the bloom chain) may have mips."""
+        d = TextureDesc(w, h, mips, fmt, int(bool(uav)) | (TEXTURE_RENDER_TARGET if render_target else 0), 0, name.encode())
         hd = C.c_void_p()
         _check(load().trhip_texture_create(self.h, C.byref(d), C.byref(hd)))
         return Texture(self, hd, w, h, mips, fmt, name)
