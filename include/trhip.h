@@ -102,6 +102,12 @@ uint32_t    trhip_abi_version(void);
  * (0, 0, 0)), u0 (texture) the RGBA8_UNORM target; samplers are accepted and ignored.  Every texel is written, alpha 255.
  * A t2 with a mip chain (the generated bloom texture) is read at mip 0.
  * The arithmetic convention of the three is stated in csrc/k_postprocess.hip.
+ * "sky_PS_HosekWilkieSky" (sky.hlsl, SkyRenderer.cpp; the stand-in of the full-screen pass at kFarDepth with its GreaterOrEqual
+ * depth test): a direct dispatch of [numthreads(8, 8, 1)] groups covering the target; b0 SkyPassParameters (256 bytes, a constant
+ * buffer), t0 (texture) the R32_FLOAT depth (the read-only depth attachment), u0 (texture) the R11G11B10_FLOAT target at mip 0,
+ * whose size is the resolution; samplers are accepted and ignored.  A texel is written iff its depth is <= 0.0f (NaN is skipped):
+ * the complement of the lighting pass.  Refused at record time: a missing or short b0, another format at t0 or u0, a missing
+ * binding, a mip other than 0, depth and target of different size.  The arithmetic convention is stated in csrc/k_sky.hip.
  * "bloom_PS_Downsample" and "bloom_PS_Upsample" (bloom.hlsl, BloomRenderer.cpp; the stand-ins of the full-screen passes of
  * Graphic.cpp:832-860): a direct dispatch of [numthreads(8, 8, 1)] groups covering the destination mip; b0 or push constants
  * BloomConsts (16 bytes: the downsample reads m_InvSourceResolution and m_bIsFirstDownsample, the upsample m_FilterRadius), t0

@@ -120,7 +120,15 @@ int  trhost_get_deferred_lighting_consts(void* out112);
  * floor(log2(min(W, H))) + 1; a radius that is negative or not finite; an uploaded bloom texture still set -- and while
  * generation is on trhost_upload_bloom refuses a texture.  trhost_set_bloom(0, ...) switches it off.  trhost_download_bloom
  * waits and copies one mip ((W >> mip) x (H >> mip) words); trhost_get_bloom_consts copies the 16 bytes of BloomConsts of pass
- * `pass` < 2 * (nbMips - 1) of the last frame, downsamples first. */
+ * `pass` < 2 * (nbMips - 1) of the last frame, downsamples first.
+ * The sky pass (SkyRenderer.cpp; off by default).  trhost_load_sky_dataset copies the Hosek-Wilkie RGB dataset, an input and not
+ * part of this library: rgb = 3 x 1080 doubles (per channel 2 albedos x 10 turbidities x 6 control points x 9 parameters), rad =
+ * 3 x 120 doubles; NULL unloads it and switches the pass off.  trhost_set_sky(1, turbidity, groundAlbedo) schedules SkyRenderer
+ * between DeferredLightingRenderer and BloomRenderer: one "sky_PS_HosekWilkieSky" dispatch that fills every texel of
+ * LightingOutput whose depth is <= 0 (the reference's defaults: 2.0 and (0.1, 0.1, 0.1)); the sun direction is the directional
+ * light vector as given.  Refused: no dataset loaded; deferred lighting off; a turbidity that is not finite or outside [1, 10];
+ * an albedo outside [0, 1].  trhost_set_sky(0, ...) switches it off.  trhost_get_sky_consts copies the 256 bytes of
+ * SkyPassParameters of the last frame and refuses if the pass did not run in it. */
 int  trhost_set_post_process(int enable);
 int  trhost_set_exposure(float manual, float middle_gray);
 int  trhost_set_auto_exposure(float min_lum, float max_lum, float speed_per_ms);
@@ -129,6 +137,9 @@ int  trhost_upload_bloom(const uint32_t* words, uint64_t bytes, float strength);
 int  trhost_set_bloom(int enable, uint32_t nb_mips, float filter_radius, float strength);
 int  trhost_download_bloom(uint32_t mip, uint32_t* words, uint64_t bytes);
 int  trhost_get_bloom_consts(uint32_t pass, void* out16);
+int  trhost_load_sky_dataset(const double* rgb, const double* rad);
+int  trhost_set_sky(int enable, float turbidity, const float ground_albedo[3]);
+int  trhost_get_sky_consts(void* out256);
 int  trhost_download_back_buffer(uint32_t* words, uint64_t bytes);
 int  trhost_get_scene_luminance(float* luminance, float* exposure);
 int  trhost_reset_exposure(void);

@@ -1,0 +1,270 @@
+/* sky_ref.c -- test reference of "sky_PS_HosekWilkieSky" (csrc/k_sky.hip), of the software arc cosine it uses
+ * (csrc/soft_math.hip.h acosSoft) and of HosekWilkieHelper::CalculateSkyParameters as both host sides state it
+ * (csrc/host/SkyRenderer.cpp, toyrenderer_amd/sky.py).  Compiled by the tests themselves with gcc -O2 -ffp-contract=off: only
+ * the fmaf calls written here fuse.
+ *
+ * CONVENTION (parity unpinned; the kernel's header states it, DESIGN.md 3 repeats it).  IEEE binary32 throughout, / and sqrtf
+ * correctly rounded.
+ *   written   : a pixel is written iff its depth is <= 0.0f (+0, -0, negative; NaN and every positive depth leave u0 as it is);
+ *   position  : uv = (px + 0.5f, py + 0.5f) / (float)resolution of the target; clip = (u * 2 + -1, v * -2 + 1); the row vector
+ *               (clip.x, clip.y, 0.9f, 1) times m_ClipToWorld, each column fmaf(0.9f, m[2][j], fmaf(clip.y, m[1][j],
+ *               clip.x * m[0][j])) + m[3][j]; world = xyz / w; V = normalize(world - m_CameraPosition),
+ *               dot3 = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)), normalize(v) = v / sqrtf(dot3(v, v));
+ *   angles    : cosTheta = fminf(fmaxf(V.y, 0), 1) (a NaN gives 0); cosGamma = dot3(V, m_SunLightDir); gamma = sk_acos(cosGamma)
+ *               (NaN outside [-1, 1]: a view ray that meets the sun direction to the last bit can give that);
+ *   exp(x)    : sk_exp2(x * 0x1.715476p+0f), sk_exp2 = the post pass's two-sided exp2 (tests/postprocess_ref.c pr_exp2), word
+ *               for word; pow(b, 1.5) = b * sqrtf(b) (negative base: NaN); pow(c, 256), c > 0: eight squarings;
+ *   channel   : chi = (1 + cg * cg) / pow((1 + H * H) - ((2 * cg) * H), 1.5);
+ *               hw = (1 + A * exp(B / (cosTheta + 0.01f))) * ((((C + D * exp(E * gamma)) + F * (cg * cg)) + G * chi) + I * sqrtf(cosTheta));
+ *               R = (-Z) * hw; if (cg > 0) R = R + pow(cg, 256) * 0.5f;
+ *   store     : R11G11B10_FLOAT per channel as tests/lighting_ref.c states it; alpha is dropped.
+ *
+ * RADIOMETRIC BOUND (tests/test_sky_ref.py evaluates it per pixel and channel).  u = 2^-24.  Against the same formula in
+ * binary64 from the same binary32 V, parameters and constants (0.01f, 0.9f are the binary32 numbers):
+ *   dcg       : cosGamma, three roundings of partials at most |V.s| summed: dcg <= 3 u * (|Vx sx| + |Vy sy| + |Vz sz|);
+ *   dgamma    : SK_ACOS_BOUND + min(dcg / sqrt(1 - c^2), (pi / sqrt 2) * sqrt(dcg)), c = min(|cg| + dcg, 1): the arc cosine is
+ *               Hoelder-1/2 with that constant, and Lipschitz away from +-1;
+ *   exp       : the argument y = RN(x * RN(log2 e)); RN(log2 e) is off by 0.22 u relatively.  e1: x = B / (ct + 0.01f) carries two
+ *               roundings: dy1 = 3.22 u |y1|.  e2: x = E * gamma: dy2 = 2.22 u |y2| + |E| * 1.4427 * dgamma.  The result moves by
+ *               ln 2 * dy relatively, and sk_exp2 adds 2.9 * 2^-25 / 0.7071 = 2.05 u relatively (PR_EXP2_BOUND over the smallest p);
+ *   chi       : b = (1 + H^2) - 2 cg H: db <= u (H^2 + (1 + H^2) + |2 cg H| + |b|) + 2 |H| dcg; chi moves by
+ *               1.5 db / |b| + 5 u + 2 dcg relatively (sqrt, the product b sqrt b, 1 + cg^2 twice, the division);
+ *   terms     : T = (C, D e2, F cg^2, G chi, I sqrt ct); each product rounds once; F cg^2 carries 2 u + 2 dcg / |cg|... taken
+ *               absolutely as |F| (2 u cg^2 + 2 |cg| dcg); sqrt ct u / 2; four additions of partials at most sum |T| each:
+ *               dsum <= sum |T_k| (rel_k + u) + 4 u sum |T|;
+ *   first     : 1 + A e1: dfirst <= |A e1| (rel e1 + u) + u (1 + |A e1|);
+ *   R         : two more products and the final addition: dR <= |Z| ((1 + |A e1|) dsum + sum |T| dfirst) + 3 u S + dsun,
+ *               S = |Z| (1 + |A e1|) sum |T| + sun, sun = 0.5 cg^256 with dsun = sun (256 u + 256 dcg / cg) + 2^-149.
+ *   First order; the test multiplies the whole by 1.01 for the second-order terms it drops.
+ */
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
+static float dot3(const float a[3], const float b[3]) { return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])); }
+
+/* ---- the R11G11B10_FLOAT store (tests/lighting_ref.c lr_pack_ufloat, word for word) ---------------------------------- */
+uint32_t sk_pack_ufloat(float v, uint32_t mbits)
+{
+    const uint32_t shift = 23u - mbits, inf = 31u << mbits, maxFinite = inf - 1u;
+    const uint32_t u = bits_of(v);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return inf | ((1u << mbits) - 1u);
+    if (u >> 31) return 0u;
+    if (u == 0x7F800000u) return inf;
+    if (u >= 0x38800000u) {
+        const uint32_t r = u - (112u << 23);
+        const uint32_t q = (r + ((1u << (shift - 1)) - 1u) + ((r >> shift) & 1u)) >> shift;
+        return q < maxFinite ? q : maxFinite;
+    }
+    return (uint32_t)rintf(v * (float)(1u << (14u + mbits)));
+}
+uint32_t sk_pack_r11g11b10(float r, float g, float b) { return sk_pack_ufloat(r, 6) | sk_pack_ufloat(g, 6) << 11 | sk_pack_ufloat(b, 5) << 22; }
+
+/* ---- two-sided exp2 (tests/postprocess_ref.c pr_exp2; derivation and PR_EXP2_BOUND = 2.9 * 2^-25 * 2^i there) ----------- */
+static const float kExp2C[7] = { 0x1.000000p+0f, 0x1.62e430p-1f, 0x1.ebfbe0p-3f, 0x1.c6af6cp-5f, 0x1.3b2a54p-7f, 0x1.5f0890p-10f, 0x1.44138ap-13f };
+float sk_exp2(float x)
+{
+    const float i = rintf(x), f = x - i;
+    float p = kExp2C[6];
+    for (int j = 5; j >= 0; --j) p = fmaf(p, f, kExp2C[j]);
+    return ldexpf(p, (int)fminf(fmaxf(i, -300.0f), 300.0f));
+}
+static float sk_exp(float x) { return sk_exp2(x * 0x1.715476p+0f); }
+
+/* ---- software arc cosine -------------------------------------------------------------------------------------------------
+ * asin(s) = s + s * z * P(z), z = s * s in [0, 0.25]; P is the degree-4 weighted least-squares fit of (asin(sqrt z) / sqrt z
+ * - 1) / z at 400 Chebyshev nodes of [0, 0.25] (weight s z, so that the error of the sum is what is minimised), coefficients
+ * rounded to binary32.  |s + s z P(z) - asin s| <= 0.038 * 2^-24 on 400 001 points, coefficients as rounded.
+ *   |x| <= 0.5: z = x * x, t = fmaf(x * z, P, x), result RN(pi / 2) - t;
+ *   |x| >  0.5: z = (1 - |x|) * 0.5 (exact: Sterbenz, then a power of two), s = sqrtf(z) <= 0.5, t = fmaf(s * z, P, s), r = 2 t
+ *               (exact); x > 0: r, else RN(pi) - r.  acos(1) = 0 and acos(-1) = RN(pi) exactly; !(|x| <= 1) gives NaN.
+ * ERROR, absolute, in units of 2^-24.  t: its fmaf rounds once, t <= 0.5236: 0.5; the product s * z carries two roundings and
+ * multiplies P <= 0.1875, the term is <= 0.0236: 0.047; P's four fmaf round by <= 2^-26 together, times |s z| <= 0.125: 0.03;
+ * truncation 0.038: t within 0.62.  For |x| > 0.5 add sqrtf's half ulp 2^-26 times asin' <= 1.1547: 0.289, and P read at z
+ * rather than RN(s)^2, 2^-23 relative: 0.054; t within 0.963, r within 1.93.  The last subtraction rounds by <= 2^-23 (results
+ * in [2, pi]): 2; RN(pi / 2) is off by 0.733 and RN(pi) by 1.467.  So |x| <= 0.5: 3.36; x > 0.5: 1.93; x < -0.5: 5.4.
+ * SK_ACOS_BOUND = 5.5 * 2^-24 (3.28e-7). */
+static const float kAcosC[5] = { 0x1.555626p-3f, 0x1.32ea80p-4f, 0x1.766edcp-5f, 0x1.7b4b14p-6f, 0x1.665bcap-5f };
+const double SK_ACOS_BOUND = 5.5 * 0x1p-24;
+
+static float acos_poly(float z)
+{
+    float p = kAcosC[4];
+    for (int j = 3; j >= 0; --j) p = fmaf(p, z, kAcosC[j]);
+    return p;
+}
+
+float sk_acos(float x)
+{
+    const float a = fabsf(x);
+    if (!(a <= 1.0f)) return nanf("");
+    if (a <= 0.5f) {
+        const float z = x * x;
+        return 0x1.921fb6p+0f - fmaf(x * z, acos_poly(z), x);
+    }
+    const float z = (1.0f - a) * 0.5f, s = sqrtf(z);
+    const float r = 2.0f * fmaf(s * z, acos_poly(z), s);
+    return x > 0.0f ? r : 0x1.921fb6p+1f - r;
+}
+
+/* max |sk_acos - acos| over every binary32 whose bits lie in [lo, hi] (one sign); *at receives the argument */
+double sk_acos_max_error(uint32_t lo, uint32_t hi, float* at)
+{
+    double worst = 0.0;
+    for (uint64_t b = lo; b <= hi; ++b) {
+        const float x = float_of((uint32_t)b);
+        const double e = fabs((double)sk_acos(x) - acos((double)x));
+        if (e > worst) { worst = e; if (at) *at = x; }
+    }
+    return worst;
+}
+
+/* ---- the pass ------------------------------------------------------------------------------------------------------------ */
+typedef struct
+{
+    float m_ClipToWorld[4][4];
+    float m_SunLightDir[3]; uint32_t PAD0;
+    float m_CameraPosition[3]; uint32_t PAD1;
+    float m_Params[10][4];
+} SkConsts;
+
+static float pow15(float b) { return b * sqrtf(b); }
+
+/* the view vector of one pixel */
+void sk_view_vector(const SkConsts* k, uint32_t W, uint32_t H, uint32_t px, uint32_t py, float V[3])
+{
+    const float u = ((float)px + 0.5f) / (float)W, v = ((float)py + 0.5f) / (float)H;
+    const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;
+    float h[4], d[3];
+    for (int j = 0; j < 4; ++j)
+        h[j] = fmaf(0.9f, k->m_ClipToWorld[2][j], fmaf(cy, k->m_ClipToWorld[1][j], cx * k->m_ClipToWorld[0][j])) + k->m_ClipToWorld[3][j];
+    for (int c = 0; c < 3; ++c) d[c] = h[c] / h[3] - k->m_CameraPosition[c];
+    const float len = sqrtf(dot3(d, d));
+    for (int c = 0; c < 3; ++c) V[c] = d[c] / len;
+}
+
+/* PS_HosekWilkieSky from the view vector: the float3 before the store */
+void sk_radiance(const SkConsts* k, const float V[3], float rgb[3])
+{
+    const float ct = fminf(fmaxf(V[1], 0.0f), 1.0f);
+    const float cg = dot3(V, k->m_SunLightDir);
+    const float gamma = sk_acos(cg);
+    const float cg2 = cg * cg, onePlusCg2 = 1.0f + cg2, twoCg = 2.0f * cg, invCt = ct + 0.01f, sqrtCt = sqrtf(ct);
+    float sun = 0.0f;
+    if (cg > 0.0f) {
+        float p = cg;
+        for (int i = 0; i < 8; ++i) p = p * p;
+        sun = p * 0.5f;
+    }
+    for (int c = 0; c < 3; ++c) {
+        const float A = k->m_Params[0][c], B = k->m_Params[1][c], C = k->m_Params[2][c], D = k->m_Params[3][c], E = k->m_Params[4][c];
+        const float F = k->m_Params[5][c], G = k->m_Params[6][c], H = k->m_Params[7][c], I = k->m_Params[8][c], Z = k->m_Params[9][c];
+        const float chi = onePlusCg2 / pow15((1.0f + H * H) - twoCg * H);
+        const float first = 1.0f + A * sk_exp(B / invCt);
+        const float hw = first * ((((C + D * sk_exp(E * gamma)) + F * cg2) + G * chi) + I * sqrtCt);
+        const float R = -Z * hw;
+        rgb[c] = cg > 0.0f ? R + sun : R;
+    }
+}
+
+/* One full-screen pass over a W x H target.  depth: float[H*W]; out: uint32[H*W] packed words, rgb: float[H*W*3], view:
+ * float[H*W*3]; each may be NULL.  Texels whose depth is not <= 0 keep what they hold. */
+void sk_sky(const SkConsts* k, uint32_t W, uint32_t H, const float* depth, uint32_t* out, float* rgb, float* view)
+{
+    for (uint32_t py = 0; py < H; ++py)
+        for (uint32_t px = 0; px < W; ++px) {
+            const uint64_t i = (uint64_t)py * W + px;
+            if (!(depth[i] <= 0.0f)) continue;
+            float V[3], c[3];
+            sk_view_vector(k, W, H, px, py, V);
+            sk_radiance(k, V, c);
+            if (out) out[i] = sk_pack_r11g11b10(c[0], c[1], c[2]);
+            if (rgb) memcpy(rgb + 3 * i, c, sizeof c);
+            if (view) memcpy(view + 3 * i, V, sizeof V);
+        }
+}
+
+/* ---- HosekWilkieHelper::CalculateSkyParameters (SkyRenderer.cpp:41-129) --------------------------------------------------
+ * The operations and types are the reference's, with its roundings to float (sun_theta, std::max<float>, 1.f / 3.0f, turbidityK,
+ * the (float) of each Evaluate).  acos and cos are the double functions of the C library rounded once to float, and pow is
+ * called through a pointer so that the compiler folds none of its calls: both host sides and this file then run the same
+ * library function on the same doubles.  Row 9: DirectXMath's polynomial Exp2 / Pow are not restated; the normalisation is
+ * evaluated in double from the 30 rounded floats (2^x as pow(2, x), pow(b, 1.5), the luminance dot left to right) and rounded
+ * once.  Its quirks are the reference's: no "1 +" in the first factor, F * gamma^2, gamma = 0 and cos gamma = 1,
+ * cos theta = cos(sun_theta), rows 7 and 8 from dataset columns 8 and 7, a base-two exponential. */
+static double libm_pow(double a, double b) { double (*volatile f)(double, double) = pow; return f(a, b); }
+
+static double evaluate_spline(const double* spline, size_t stride, double value)
+{
+    return 1 * libm_pow(1.0 - value, 5) * spline[0 * stride] +
+           5 * libm_pow(1.0 - value, 4) * libm_pow(value, 1) * spline[1 * stride] +
+           10 * libm_pow(1.0 - value, 3) * libm_pow(value, 2) * spline[2 * stride] +
+           10 * libm_pow(1.0 - value, 2) * libm_pow(value, 3) * spline[3 * stride] +
+           5 * libm_pow(1.0 - value, 1) * libm_pow(value, 4) * spline[4 * stride] +
+           1 * libm_pow(value, 5) * spline[5 * stride];
+}
+
+static double evaluate(const double* dataset, size_t stride, float turbidity, float albedo, float sun_theta)
+{
+    const float elevation = (float)(1.f - sun_theta / (3.14159265358979323846 * 0.5f));
+    const double elevationK = libm_pow(elevation > 0.f ? elevation : 0.f, 1.f / 3.0f);
+    int turbidity0 = (int)turbidity;
+    turbidity0 = turbidity0 < 1 ? 1 : turbidity0 > 10 ? 10 : turbidity0;
+    const int turbidity1 = turbidity0 + 1 < 10 ? turbidity0 + 1 : 10;
+    float turbidityK = turbidity - turbidity0;
+    turbidityK = turbidityK < 0.f ? 0.f : turbidityK > 1.f ? 1.f : turbidityK;
+    const double* datasetA0 = dataset;
+    const double* datasetA1 = dataset + stride * 6 * 10;
+    const double a0t0 = evaluate_spline(datasetA0 + stride * 6 * (turbidity0 - 1), stride, elevationK);
+    const double a1t0 = evaluate_spline(datasetA1 + stride * 6 * (turbidity0 - 1), stride, elevationK);
+    const double a0t1 = evaluate_spline(datasetA0 + stride * 6 * (turbidity1 - 1), stride, elevationK);
+    const double a1t1 = evaluate_spline(datasetA1 + stride * 6 * (turbidity1 - 1), stride, elevationK);
+    return a0t0 * (1.0f - albedo) * (1.0f - turbidityK) + a1t0 * albedo * (1.0f - turbidityK) + a0t1 * (1.0f - albedo) * turbidityK + a1t1 * albedo * turbidityK;
+}
+
+/* the reference's normalisation helper (SkyRenderer.cpp:73-95) of one channel, in double from the rounded rows */
+double sk_helper(const float p[10][3], int c, float cos_theta, float gamma, float cos_gamma)
+{
+    const double A = p[0][c], B = p[1][c], C = p[2][c], D = p[3][c], E = p[4][c], F = p[5][c], G = p[6][c], H = p[7][c], I = p[8][c];
+    const double chi = (double)(1.f + cos_gamma * cos_gamma) / libm_pow(H * H + 1.0 - H * (double)(2.0f * cos_gamma), 1.5);
+    const double temp1 = A * libm_pow(2.0, B * (double)(1.0f / (cos_theta + 0.01f)));
+    const double temp2 = C + D * libm_pow(2.0, E * (double)gamma) + F * (double)(gamma * gamma) + chi * G +
+                         I * (double)(float)sqrt((double)(cos_theta > 0.f ? cos_theta : 0.f));
+    return temp1 * temp2;
+}
+
+/* rgb: double[3][1080], rad: double[3][120]; out: float[10][3] (row, channel) */
+void sk_parameters(const double* rgb, const double* rad, float turbidity, const float albedo[3], const float sun_direction[3], float out[10][3])
+{
+    const float y = sun_direction[1] < 0.f ? 0.f : sun_direction[1] > 1.f ? 1.f : sun_direction[1];
+    const float sun_theta = (float)acos((double)y);
+    for (int i = 0; i < 3; ++i) {
+        const double* d = rgb + 1080 * i;
+        for (int r = 0; r < 7; ++r) out[r][i] = (float)evaluate(d + r, 9, turbidity, albedo[i], sun_theta);
+        out[7][i] = (float)evaluate(d + 8, 9, turbidity, albedo[i], sun_theta);
+        out[8][i] = (float)evaluate(d + 7, 9, turbidity, albedo[i], sun_theta);
+        out[9][i] = (float)evaluate(rad + 120 * i, 1, turbidity, albedo[i], sun_theta);
+    }
+    const float cos_theta = (float)cos((double)sun_theta);
+    double S[3];
+    for (int i = 0; i < 3; ++i) S[i] = sk_helper(out, i, cos_theta, 0.0f, 1.0f) * (double)out[9][i];
+    const double lum = S[0] * (double)0.2126f + S[1] * (double)0.7152f + S[2] * (double)0.0722f;
+    for (int i = 0; i < 3; ++i) out[9][i] = (float)((double)out[9][i] / lum);
+}
+
+/* array forms for the tests */
+void sk_acos_n(const float* x, uint64_t n, float* out) { for (uint64_t i = 0; i < n; ++i) out[i] = sk_acos(x[i]); }
+
+#ifdef SKY_REF_ACOS_DRIVER                     /* gcc -O2 -ffp-contract=off -DSKY_REF_ACOS_DRIVER sky_ref.c -lm: every binary32 in [-1, 1], once */
+int main(void)
+{
+    float atp = 0.0f, atn = 0.0f;
+    const double p = sk_acos_max_error(0x00000000u, 0x3F800000u, &atp), n = sk_acos_max_error(0x80000000u, 0xBF800000u, &atn);
+    printf("max |sk_acos - acos| over [0, 1]: %.4g (%.3f * 2^-24) at %a; over [-1, -0]: %.4g (%.3f * 2^-24) at %a; bound %.4g\n", p, p * 0x1p24, atp, n,
+           n * 0x1p24, atn, SK_ACOS_BOUND);
+    return (p <= SK_ACOS_BOUND && n <= SK_ACOS_BOUND) ? 0 : 1;
+}
+#endif

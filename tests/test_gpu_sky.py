@@ -1,0 +1,482 @@
+"""The sky pass on the GPU ("sky_PS_HosekWilkieSky", csrc/k_sky.hip), every word against tests/sky_ref.c: single passes through rhi
+bindings at sizes around every tile edge with every depth content, special directions, hostile constant blocks, whole frames
+through FrameDriver(sky=...) with the existing bloom and post references behind them, the C++ host mirror, and misuse.  The target
+is pre-filled with a sentinel so that a texel the pass must leave alone shows."""
+import json
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bloom_ref as BR  # noqa: E402
+import lighting_ref as LR  # noqa: E402
+import postprocess_ref as PR  # noqa: E402
+import sky_ref as SR  # noqa: E402
+from gbuffer_scenes import with_normals_and_materials  # noqa: E402
+from toyrenderer_amd import gltf_lite, sky, synth  # noqa: E402
+from toyrenderer_amd import interop as I  # noqa: E402
+from visibility_scenes import city  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+SENTINEL = SR.SENTINEL
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from toyrenderer_amd import rhi
+    d = rhi.Device(0)
+    yield d
+    d.destroy()
+
+
+@pytest.fixture(scope="module")
+def sk(tmp_path_factory):
+    return SR.load(tmp_path_factory.mktemp("sky_ref_gpu"))
+
+
+@pytest.fixture(scope="module")
+def bl(tmp_path_factory):
+    return BR.load(tmp_path_factory.mktemp("bloom_ref_for_sky"))
+
+
+@pytest.fixture(scope="module")
+def pr(tmp_path_factory):
+    return PR.load(tmp_path_factory.mktemp("postprocess_ref_for_sky"))
+
+
+@pytest.fixture(scope="module")
+def lr(tmp_path_factory):
+    return LR.load(tmp_path_factory.mktemp("lighting_ref_for_sky"))
+
+
+def _same(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
+
+
+def _kernel_constant(name):
+    src = open(os.path.join(ROOT, "toyrenderer_amd", "csrc", "k_sky.hip")).read()
+    return int(re.search(r"\b" + name + r" = (\d+)", src).group(1))
+
+
+class _Pass:
+    """One depth texture, one target and one command list of a size, reused over many dispatches."""
+
+    def __init__(self, dev, W, H):
+        from toyrenderer_amd import rhi
+        self.dev, self.W, self.H = dev, W, H
+        self.depth = dev.create_texture(W, H, 1, rhi.FORMAT_R32_FLOAT, "Depth Buffer")
+        self.target = dev.create_texture(W, H, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
+        self.cl = dev.create_command_list()
+        self.fill = np.full((H, W), SENTINEL, np.uint32)
+
+    def run(self, consts, depth, extra=()):
+        from toyrenderer_amd.rhi import CB, TEX_SRV, TEX_UAV
+        self.depth.upload_mip(0, np.ascontiguousarray(depth, F))
+        self.target.upload_mip(0, self.fill)
+        self.cl.open()
+        cb = self.cl.constant_buffer(np.ascontiguousarray(consts, I.SkyPassParameters), "SkyPassParameters")
+        self.cl.dispatch("sky_PS_HosekWilkieSky", [CB(0, cb), TEX_SRV(0, self.depth), TEX_UAV(0, self.target, 0), *extra], ((self.W + 7) // 8, (self.H + 7) // 8, 1))
+        self.cl.close()
+        self.dev.execute(self.cl); self.dev.wait_idle()
+        return self.target.download_mip(0)
+
+    def release(self):
+        self.cl.release(); self.depth.release(); self.target.release()
+
+
+# ---- 1. single passes -----------------------------------------------------------------------------------------------------------
+def _sizes():
+    """One below, at and one above the kernel's tile in both axes, two tiles each way (more than one workgroup in each axis), and
+    the issue's list."""
+    tw, th = _kernel_constant("kSkyTileW"), _kernel_constant("kSkyBlock") // _kernel_constant("kSkyTileW")
+    assert (tw, th) == (64, 4)
+    return [(tw - 1, th - 1), (tw, th), (tw + 1, th + 1), (2 * tw, 2 * th), (1, 1), (2, 2), (67, 35), (129, 3), (270, 135)]
+
+
+def _cameras():
+    """(configuration index, pitch, looking down): the seven configurations at the two pitches, plus a camera looking straight down."""
+    return [(c, p, False) for c in range(len(SR.CONFIGS)) for p in SR.PITCHES] + [(0, 0.0, True)]
+
+
+@pytest.mark.parametrize("size", _sizes(), ids=lambda s: f"{s[0]}x{s[1]}")
+def test_single_passes_match_the_reference(dev, sk, size):
+    """Every depth content under one configuration, and every configuration and camera over an all-sky depth: a texel is
+    overwritten iff depth <= 0, with the reference's word; every other keeps its sentinel."""
+    W, H = size
+    p = _Pass(dev, W, H)
+    try:
+        k = SR.block(SR.CONFIGS[0], W, H, 0.5)
+        for name, depth in SR.depth_images(W, H, seed=W + H).items():
+            want = SR.sky_pass(sk, k, depth)
+            with np.errstate(invalid="ignore"):
+                written = depth <= 0.0
+            assert np.array_equal(want == SENTINEL, ~written), name             # no sky word of the reference equals the sentinel
+            _same(p.run(k, depth), want, f"{W}x{H} depth {name}")
+        zero = np.zeros((H, W), F)
+        for c, pitch, down in _cameras():
+            k = SR.block(SR.CONFIGS[c], W, H, pitch, down=down)
+            want, view = SR.sky_pass(sk, k, zero, want_view=True)
+            if down:
+                assert np.all(view[..., 1] < 0)                                 # every V.y is clamped to 0
+            _same(p.run(k, zero), want, f"{W}x{H} configuration {c} pitch {pitch} down {down}")
+    finally:
+        p.release()
+
+
+def test_samplers_are_accepted_and_ignored(dev, sk):
+    from toyrenderer_amd.rhi import SAMPLER
+    p = _Pass(dev, 67, 35)
+    try:
+        k = SR.block(SR.CONFIGS[1], 67, 35)
+        depth = SR.depth_images(67, 35)["mix"]
+        _same(p.run(k, depth, extra=(SAMPLER(0), SAMPLER(3))), SR.sky_pass(sk, k, depth), "with samplers")
+    finally:
+        p.release()
+
+
+# ---- 2. special directions ------------------------------------------------------------------------------------------------------
+def test_special_directions(dev, sk):
+    """The sun exactly along one pixel's float V (whatever the reference gives there, NaN included, is pinned); a row with V.y = 0
+    exactly; a sun more than 90 degrees from every pixel (no disc term); cos gamma a small positive number (its squarings underflow)."""
+    W, H = 67, 35
+    p = _Pass(dev, W, H)
+    zero = np.zeros((H, W), F)
+    try:
+        base = SR.block(SR.CONFIGS[0], W, H, 0.5)
+        _, view = SR.sky_pass(sk, base, zero, want_view=True)
+        nan_seen = finite_seen = 0
+        for (py, px) in [(y, x) for y in range(0, H, 2) for x in range(0, W, 3)][:120]:
+            k = base.copy()
+            k["m_SunLightDir"] = view[py, px]
+            want, rgb = SR.sky_pass(sk, k, zero, want_rgb=True)
+            if np.isnan(rgb[py, px]).all():
+                nan_seen += 1
+                assert want[py, px] == BR.NAN_WORD
+            else:
+                finite_seen += 1
+                assert np.all(rgb[py, px] >= 0.49)                              # the disc term: 0.5 cos^256 with cos within 2^-23 of 1
+            _same(p.run(k, zero), want, f"sun along the view vector of pixel ({px}, {py})")
+            if nan_seen and finite_seen and nan_seen + finite_seen >= 12:
+                break
+        assert nan_seen and finite_seen, (nan_seen, finite_seen)                # both outcomes occur and both are pinned
+        # a level camera with an odd height: the middle row's clip y is 0 and its V.y is exactly 0
+        k = SR.block(SR.CONFIGS[0], W, H, 0.0)
+        k["m_CameraPosition"] = (0.0, 0.0, 0.0)
+        c2w, _ = SR.camera(W, H, eye=(0.0, 0.0, 0.0))
+        k["m_ClipToWorld"] = c2w
+        want, view = SR.sky_pass(sk, k, zero, want_view=True)
+        assert np.all(view[H // 2, :, 1] == 0.0)
+        _same(p.run(k, zero), want, "a row with V.y = 0")
+        # the sun behind the camera: gamma > 90 degrees everywhere
+        k = SR.block(SR.CONFIGS[0], W, H, 0.0)
+        k["m_SunLightDir"] = SR.unit((0.0, 0.3, 1.0))
+        want, view = SR.sky_pass(sk, k, zero, want_view=True)
+        assert np.all(view.reshape(-1, 3).astype(np.float64) @ k["m_SunLightDir"][0].astype(np.float64) < 0)
+        _same(p.run(k, zero), want, "gamma > 90 degrees")
+        # the sun perpendicular to the central column's rays: cos gamma is tiny, of either sign, along it
+        k["m_SunLightDir"] = (1.0, 0.0, 0.0)
+        want, view = SR.sky_pass(sk, k, zero, want_view=True)
+        cg = view[..., 0]
+        assert np.any((cg > 0) & (cg < 0.05)) and np.any(cg < 0)
+        _same(p.run(k, zero), want, "small cos gamma")
+    finally:
+        p.release()
+
+
+# ---- 3. hostile blocks ----------------------------------------------------------------------------------------------------------
+def test_hostile_blocks(dev, sk):
+    """Blocks no host would make go straight into b0: H = 1 and 1.5 (a zero and a negative base of the 3/2 power), infinite and NaN
+    rows, an m_ClipToWorld whose w column gives 0, a non-unit sun vector (cos gamma beyond 1: NaN).  The words are the reference's."""
+    W, H = 67, 35
+    p = _Pass(dev, W, H)
+    depth = SR.depth_images(W, H)["checkerboard"]
+    try:
+        blocks = {}
+        for name, h in (("H = 1", 1.0), ("H = 1.5", 1.5)):
+            k = SR.block(SR.CONFIGS[0], W, H, 0.5)
+            k["m_HosekParams"]["m_Params"][0, 7, :3] = h
+            blocks[name] = k
+        for row in range(10):
+            for name, v in (("inf", np.inf), ("-inf", -np.inf), ("nan", np.nan)):
+                k = SR.block(SR.CONFIGS[1], W, H, 0.0)
+                k["m_HosekParams"]["m_Params"][0, row, :3] = (v, k["m_HosekParams"]["m_Params"][0, row, 1], v)
+                blocks[f"row {row} {name}"] = k
+        k = SR.block(SR.CONFIGS[0], W, H)
+        k["m_ClipToWorld"][0, :, 3] = 0.0
+        blocks["w = 0"] = k
+        k = SR.block(SR.CONFIGS[0], W, H)
+        k["m_ClipToWorld"][0] = np.nan
+        blocks["NaN matrix"] = k
+        for scale in (1.7, 0.3, 0.0):
+            k = SR.block(SR.CONFIGS[0], W, H, 0.5)
+            k["m_SunLightDir"] = k["m_SunLightDir"] * F(scale)
+            blocks[f"sun x {scale}"] = k
+        k = SR.block(SR.CONFIGS[0], W, H)
+        k["m_CameraPosition"] = (np.inf, 0.0, 0.0)
+        blocks["camera at infinity"] = k
+        for name, k in blocks.items():
+            _same(p.run(k, depth), SR.sky_pass(sk, k, depth), name)
+    finally:
+        p.release()
+
+
+# ---- 4. frames ------------------------------------------------------------------------------------------------------------------
+def _cornell(oracle):
+    from test_gltf_cornell import _fixture
+    with open(os.path.join(ROOT, "tests", "golden", "cornell_materials.json")) as f:
+        cm = json.load(f)
+    _, s, camera = _fixture()
+    mats = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
+    s.materials, s.primMaterial = mats, np.array(cm["primitiveMaterial"], np.uint32)
+    inst = gltf_lite.apply_materials(s)
+    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
+    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
+    return s, inst, s.vertices, mats, camera, dict(dir_light=(tuple(float(x) for x in SR.unit((0.3, 0.8, -0.52))), 3.0),
+                                                   camera_origin=tuple(float(x) for x in camera.position), auto_exposure=(0.004, 12.0, 0.5))
+
+
+def _city(oracle, tmp_path):
+    s, sc = city(tmp_path, oracle)
+    v, sc, mats = with_normals_and_materials(s, sc)
+    return s, sc["instances"], v, mats, s.cameras[0], dict(dir_light=(tuple(float(x) for x in SR.unit((0.2, 0.35, -0.9))), 2.5))
+
+
+FRAMES = [("cornell", (320, 180), (2.0, (0.1, 0.1, 0.1))), ("city", (540, 270), (2.0, (0.1, 0.1, 0.1))), ("city", (67, 35), (4.0, (0.3, 0.2, 0.1)))]
+
+
+@pytest.mark.parametrize("scene,render,setting", FRAMES, ids=lambda v: str(v))
+def test_frames_match_the_reference(dev, oracle, sk, bl, pr, tmp_path, scene, render, setting):
+    """Three frames of FrameDriver(lighting, post, bloom_mips=6, sky) next to a sky=None driver: everything in front of the pass is
+    equal; LightingOutput is the sky=None image where depth > 0 and the reference sky elsewhere, nowhere 0 where the reference is
+    not; the histogram, the luminance, the bloom mips and the back buffer are the existing references fed that LightingOutput."""
+    from test_gpu_lighting import _gpu_scene
+    from test_gpu_postprocess import _bits, _post_chain_reference
+    from toyrenderer_amd.frame import FrameDriver
+    s, inst, vertices, mats, camera, kw = _cornell(oracle) if scene == "cornell" else _city(oracle, tmp_path)
+    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    view = gltf_lite.view_of(camera, render)
+    mips = min(6, BR.max_mips(*render))
+    common = dict(record_capacity=4096, culling_flags=7, lighting=True, post=True, bloom_mips=mips, **kw)
+    base = FrameDriver(dev, gs, view, **common)
+    drv = FrameDriver(dev, gs, view, sky=(SR.dataset(), *setting), **common)
+    qb, qd = dev.create_pipeline_stats(), dev.create_pipeline_stats()
+    try:
+        luminance = F(1.0)
+        for f in range(3):
+            for d, q in ((base, qb), (drv, qd)):
+                d.record(q); d.run(); d.results()
+            what = f"{scene} {render} frame {f}"
+            for name in ("gbufferA", "visibility"):
+                _same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
+            _same(drv.motion.download_mip(0).view(np.uint16), base.motion.download_mip(0).view(np.uint16), what + ": motion")
+            depth = drv.depth.download_mip(0)
+            _same(depth.view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
+            _same(drv.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
+            assert qd.get() == qb.get(), what + ": pipeline statistics"
+            sun = np.asarray(kw["dir_light"][0], F)
+            k = sky.pass_parameters(drv.lighting_consts["m_ClipToWorld"][0], sun, kw.get("camera_origin", (0.0, 0.0, 0.0)), sky.sky_parameters(SR.dataset(), setting[0], setting[1], sun))
+            assert drv.sky_consts.tobytes() == k.tobytes() and base.sky_consts is None
+            lit = base.lighting_output.download_mip(0)
+            want = SR.sky_pass(sk, k, depth, dest=lit)
+            got = drv.lighting_output.download_mip(0)
+            _same(got, want, what + ": LightingOutput")
+            _same(got[depth > 0], lit[depth > 0], what + ": lit texels")
+            assert not np.any((got == 0) & (want != 0))
+            if scene == "city":
+                assert np.count_nonzero(depth <= 0) > 0 and np.count_nonzero(got[depth <= 0]) > 0      # the view sees past the geometry
+            chain = BR.bloom_chain(bl, want, *render, mips, drv.bloom_filter_radius)
+            for m in range(mips):
+                _same(drv.download_bloom(m), chain[m], f"{what}: bloom mip {m}")
+            back, hist, luminance, _ = _post_chain_reference(pr, drv, want, luminance, bloom=chain[0])
+            _same(drv.histogram.download(np.uint32, 256), hist, what + ": histogram")
+            _same(drv.back_buffer.download_mip(0), back, what + ": back buffer")
+            assert _bits(drv.luminance.download(F, 1)).tolist() == _bits(luminance).tolist(), what
+            if np.count_nonzero(depth <= 0):
+                assert np.count_nonzero(drv.back_buffer.download_mip(0) != base.back_buffer.download_mip(0)) > 0
+    finally:
+        qb.release(); qd.release(); drv.release(); base.release(); gs.release()
+
+
+def test_sky_adds_one_dispatch_behind_the_lighting_dispatch(dev, oracle, tmp_path):
+    """sky=None records the parent's list, command for command, and launches the same kernels; sky=... adds exactly one dispatch
+    directly behind the lighting dispatch, in front of bloom and the histogram clear, under a debug view too."""
+    from test_gpu_bloom import _recorded
+    from test_gpu_lighting import _gpu_scene, _op_counts
+    from toyrenderer_amd.frame import FrameDriver
+    s, inst, vertices, mats, camera, kw = _city(oracle, tmp_path)
+    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    view = gltf_lite.view_of(camera, (320, 180))
+    seen, counts = {}, {}
+    try:
+        variants = (("parent", {}), ("none", dict(sky=None)), ("sky", dict(sky=(SR.dataset(),))), ("debug parent", dict(debug_mode=4)),
+                    ("debug sky", dict(debug_mode=4, sky=(SR.dataset(), 3.0, (0.2, 0.2, 0.2)))))
+        for name, extra in variants:
+            drv = FrameDriver(dev, gs, view, record_capacity=4096, post=True, bloom_mips=5, **extra, **kw)
+            try:
+                counts[name] = _op_counts(dev, drv)
+                seen[name] = _recorded(drv)
+            finally:
+                drv.release()
+        with pytest.raises(ValueError, match="lighting=True"):
+            FrameDriver(dev, gs, view, record_capacity=4096, gbuffer=True, sky=(SR.dataset(),), **kw)
+        for bad in ((SR.dataset(), 0.5), (SR.dataset(), 2.0, (0.1, 0.1, 1.5)), (None,), ()):
+            with pytest.raises(ValueError, match="sky"):
+                FrameDriver(dev, gs, view, record_capacity=4096, lighting=True, sky=bad, **kw)
+    finally:
+        gs.release()
+    assert seen["none"] == seen["parent"] and counts["none"] == counts["parent"]
+    assert counts["sky"] == {**counts["parent"], "sky_PS_HosekWilkieSky#main": 1}
+    for parent, with_sky, lighting in (("parent", "sky", "deferredlighting_PS_Main"), ("debug parent", "debug sky", "deferredlighting_PS_Main_Debug")):
+        at = seen[parent].index(("dispatch", lighting)) + 1
+        assert seen[parent][at] == ("dispatch", "bloom_PS_Downsample")
+        assert seen[with_sky] == seen[parent][:at] + [("dispatch", "sky_PS_HosekWilkieSky")] + seen[parent][at:]
+
+
+# ---- 5. the host mirror ---------------------------------------------------------------------------------------------------------
+def test_host_path_over_three_frames(oracle, sk, lr, tmp_path):
+    """The C++ host mirror with a moving camera and a moving sun: frame 0 sky on, frame 1 off, frame 2 on with another turbidity and
+    albedo.  trhost_get_sky_consts equals the Python block bit for bit; LightingOutput equals the lighting reference of the frame's
+    own GBufferA with the reference sky over it; the refusals of the facade each raise."""
+    from toyrenderer_amd import host
+    s, sc0 = city(tmp_path, oracle)
+    v, sc0, mats = with_normals_and_materials(s, sc0)
+    cam = s.cameras[0]
+    render = (540, 270)
+    P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
+    inst_in = s.instances.copy()
+    inst_in["m_MaterialDataIdx"] = sc0["instances"]["m_MaterialDataIdx"]
+    ds = SR.dataset()
+    r = host.Renderer(render=render, max_groups=4096)
+    try:
+        r.load_scene(inst_in, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
+        r.load_nodes(s.nodes, s.primToNode)
+        r.load_geometry(v, s.meshletVertexIds, s.meshletTriangles)
+        r.load_materials(mats)
+        with pytest.raises(host.HostError, match="no dataset"):
+            r.set_sky(True)
+        r.load_sky_dataset(ds)
+        with pytest.raises(host.HostError, match="deferred lighting is off"):
+            r.set_sky(True)
+        with pytest.raises(host.HostError, match="did not run"):
+            r.sky_consts()
+        r.set_deferred_lighting(True)
+        for t in (0.99, 10.5, float("nan"), float("inf")):
+            with pytest.raises(host.HostError, match="turbidity"):
+                r.set_sky(True, t)
+        for a in ((0.1, 0.1, 1.01), (-0.1, 0.1, 0.1), (0.1, float("nan"), 0.1)):
+            with pytest.raises(host.HostError, match="albedo"):
+                r.set_sky(True, 2.0, a)
+        r.load_sky_dataset(None)                                              # unloading refuses the pass again
+        with pytest.raises(host.HostError, match="no dataset"):
+            r.set_sky(True)
+        r.load_sky_dataset(ds)
+        r.set_culling(7)
+        r.set_node_transforms(s.nodes)
+        prevV = synth.world_to_view((0.0, 0.0, 0.0), cam.orientation)
+        settings = [(2.0, (0.1, 0.1, 0.1)), None, (6.5, (0.4, 0.3, 0.05))]
+        for f, setting in enumerate(settings):
+            V = synth.world_to_view((0.1 * f, 0.02 * f, -0.15 * f), cam.orientation)
+            view = synth.View(V, prevV, P, float(np.float32(cam.znear)), *render)
+            prevV = V
+            r.set_camera(view)
+            sun = SR.unit((0.2 * f - 0.3, 0.25 + 0.3 * f, -0.9))
+            r.set_directional_light(sun, 2.0 + f)
+            if setting is None:
+                r.set_sky(False)
+            else:
+                r.set_sky(True, *setting)
+            r.frame()
+            r.results()
+            lk = r.deferred_lighting_consts()
+            depth = r.download_depth()
+            lit = LR.lighting(lr, lk, r.download_gbuffer_a(), depth)
+            got = r.download_lighting_output()
+            if setting is None:
+                with pytest.raises(host.HostError, match="did not run"):
+                    r.sky_consts()
+                _same(got, lit, f"frame {f}: LightingOutput without the sky")
+                assert np.count_nonzero(got[depth <= 0]) == 0
+            else:
+                k = sky.pass_parameters(lk["m_ClipToWorld"][0], sun, lk["m_CameraOrigin"][0], sky.sky_parameters(ds, setting[0], setting[1], sun))
+                assert r.sky_consts().tobytes() == k.tobytes(), f
+                _same(got, SR.sky_pass(sk, k, depth, dest=lit), f"frame {f}: LightingOutput")
+                assert np.count_nonzero(depth <= 0) > 0 and np.count_nonzero(got[depth <= 0]) > 0
+    finally:
+        r.shutdown()
+
+
+# ---- 6. misuse at the back end --------------------------------------------------------------------------------------------------
+def test_misuse_is_refused(dev, sk):
+    """Each refusal happens while the command is recorded, so no kernel is launched; a good pass directly behind is correct."""
+    from toyrenderer_amd import rhi
+    from toyrenderer_amd.rhi import CB, PUSH, TEX_SRV, TEX_UAV
+    W, H = 32, 16
+    mk = lambda w, h, fmt, name: dev.create_texture(w, h, 1, fmt, name)                                  # noqa: E731
+    depth, target = mk(W, H, rhi.FORMAT_R32_FLOAT, "Depth Buffer"), mk(W, H, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
+    small, back, r8 = mk(W // 2, H, rhi.FORMAT_R11G11B10_FLOAT, "small"), mk(W, H, rhi.FORMAT_RGBA8_UNORM, "RGBA8"), mk(W, H, rhi.FORMAT_R8_UNORM, "R8")
+    chain = dev.create_texture(W, H, 3, rhi.FORMAT_R11G11B10_FLOAT, "chain", render_target=True)
+    args = dev.create_buffer(12, "args", stride=12, indirect=True)
+    cl = dev.create_command_list()
+    k = SR.block(SR.CONFIGS[0], W, H, 0.5)
+    groups = (4, 2, 1)
+    try:
+        dev.profile_reset(); dev.profile_enable(True)
+        cl.open()
+        cb = cl.constant_buffer(k, "SkyPassParameters")
+        short = cl.constant_buffer(k.view(np.uint32).reshape(-1)[:60].copy(), "short")
+        name = "sky_PS_HosekWilkieSky"
+        bad = [
+            ("256 bytes", [TEX_SRV(0, depth), TEX_UAV(0, target, 0)], groups, None),
+            ("256 bytes", [CB(0, short), TEX_SRV(0, depth), TEX_UAV(0, target, 0)], groups, None),
+            ("256 bytes", [PUSH(0), TEX_SRV(0, depth), TEX_UAV(0, target, 0)], groups, k.view(np.uint32).reshape(-1)[:32].copy()),
+            ("R32_FLOAT depth", [CB(0, cb), TEX_SRV(0, r8), TEX_UAV(0, target, 0)], groups, None),
+            ("R32_FLOAT depth", [CB(0, cb), TEX_UAV(0, target, 0)], groups, None),
+            ("R11G11B10_FLOAT LightingOutput", [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, back, 0)], groups, None),
+            ("R11G11B10_FLOAT LightingOutput", [CB(0, cb), TEX_SRV(0, depth)], groups, None),
+            ("mip", [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, chain, 1)], groups, None),
+            ("mip", [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, chain, 3)], groups, None),
+            ("mip", [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, target, 1)], groups, None),
+            ("covering 32x16", [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, target, 0)], (3, 2, 1), None),
+            ("covering 32x16", [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, target, 0)], (4, 1, 1), None),
+            ("t0 is 32x16, u0 is 16x16", [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, small, 0)], groups, None),
+        ]
+        for match, bindings, g, push in bad:
+            with pytest.raises(rhi.TrhipError, match=match):
+                cl.dispatch(name, bindings, g, push=push)
+        with pytest.raises(rhi.TrhipError, match="direct dispatch"):
+            cl.dispatch_indirect(name, [CB(0, cb), TEX_SRV(0, depth), TEX_UAV(0, target, 0)], args)
+        cl.close()
+        dev.execute(cl); dev.wait_idle()
+        assert not any(n.startswith("sky_") for n in dev.profile()), dev.profile()        # nothing was launched
+        dev.profile_enable(False)
+        d = SR.depth_images(W, H)["mix"]
+        depth.upload_mip(0, d)
+        target.upload_mip(0, np.full((H, W), SENTINEL, np.uint32))
+        cl.open()
+        cl.dispatch(name, [CB(0, cl.constant_buffer(k, "SkyPassParameters")), TEX_SRV(0, depth), TEX_UAV(0, target, 0)], groups)
+        cl.close()
+        dev.execute(cl); dev.wait_idle()
+        _same(target.download_mip(0), SR.sky_pass(sk, k, d), "a good pass after the refusals")
+        # mip 0 of a render-target chain is a valid target; its other mips keep their words
+        for m in range(3):
+            chain.upload_mip(m, np.full((H >> m, W >> m), SENTINEL + m, np.uint32))
+        cl.open()
+        cl.dispatch(name, [CB(0, cl.constant_buffer(k, "SkyPassParameters")), TEX_SRV(0, depth), TEX_UAV(0, chain, 0)], groups)
+        cl.close()
+        dev.execute(cl); dev.wait_idle()
+        _same(chain.download_mip(0), SR.sky_pass(sk, k, d), "mip 0 of a chain")
+        for m in (1, 2):
+            assert np.all(chain.download_mip(m) == SENTINEL + m)
+    finally:
+        dev.profile_enable(False)
+        cl.release(); args.release()
+        for t in (depth, target, small, back, r8, chain):
+            t.release()

@@ -164,6 +164,24 @@ struct BloomConsts
 };
 static_assert(sizeof(BloomConsts) == 16 && offsetof(BloomConsts, m_InvSourceResolution) == 0 && offsetof(BloomConsts, m_FilterRadius) == 8 && offsetof(BloomConsts, m_bIsFirstDownsample) == 12, "BloomConsts");
 
+// ShaderInterop.h:146-149, 297-305: the constant buffer b0 of "sky_PS_HosekWilkieSky".  Rows A B C D E F G H I Z; the shader
+// reads .xyz, .w is written as 0.
+struct HosekWilkieSkyParameters
+{
+    Vector4 m_Params[10];
+};
+struct SkyPassParameters
+{
+    Matrix m_ClipToWorld;
+    float m_SunLightDir[3];
+    uint32_t PAD0;
+    float m_CameraPosition[3];
+    uint32_t PAD1;
+    HosekWilkieSkyParameters m_HosekParams;
+};
+static_assert(sizeof(SkyPassParameters) == 256 && offsetof(SkyPassParameters, m_SunLightDir) == 64 && offsetof(SkyPassParameters, m_CameraPosition) == 80 &&
+              offsetof(SkyPassParameters, m_HosekParams) == 96, "SkyPassParameters");
+
 // ShaderInterop.h:117-122
 struct DispatchIndirectArguments
 {

@@ -17,6 +17,7 @@
 extern IRenderer* g_UpdateInstanceConstsRenderer;
 extern IRenderer* g_GBufferRenderer;
 extern IRenderer* g_DeferredLightingRenderer;
+extern IRenderer* g_SkyRenderer;
 extern IRenderer* g_BloomRenderer;
 extern IRenderer* g_AdaptLuminanceRenderer;
 extern IRenderer* g_PostProcessRenderer;
@@ -221,8 +222,9 @@ void Scene::Update()
         m_RenderGraph->AddRenderer(g_UpdateInstanceConstsRenderer);
         m_RenderGraph->AddRenderer(g_GBufferRenderer);
         if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
+        if (m_bDeferredLighting && m_bEnableSky) m_RenderGraph->AddRenderer(g_SkyRenderer);  // :502
         if (m_bPostProcess && m_bEnableBloom) m_RenderGraph->AddRenderer(g_BloomRenderer);   // :503
-        if (m_bPostProcess) {                                                 // :505, :507 (sky, transparents and TAA between them are not built)
+        if (m_bPostProcess) {                                                 // :505, :507 (transparents and TAA between them are not built)
             m_RenderGraph->AddRenderer(g_AdaptLuminanceRenderer);
             m_RenderGraph->AddRenderer(g_PostProcessRenderer);
         }

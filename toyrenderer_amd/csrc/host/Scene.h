@@ -120,6 +120,13 @@ public:
     bool m_bEnableBloom = false;
     uint32_t m_NbBloomMips = 6;
     float m_BloomFilterRadius = 0.005f;
+    // The sky pass (trhost_set_sky; needs m_bDeferredLighting and a dataset from trhost_load_sky_dataset): SkyRenderer runs between
+    // DeferredLightingRenderer and BloomRenderer and fills the texels of LightingOutput whose depth is <= 0.  Turbidity and ground
+    // albedo are members of the renderer in the reference (SkyRenderer.cpp:135-136, the defaults below).
+    bool m_bEnableSky = false;
+    float m_SkyTurbidity = 2.0f;
+    float m_GroundAlbedo[3] = { 0.1f, 0.1f, 0.1f };
+    std::vector<double> m_SkyDataset;                // 3 x 1080 RGB coefficients, then 3 x 120 radiance coefficients; empty: none loaded
     nvrhi::BufferHandle m_LuminanceBuffer;           // Scene.h: one float, the adapted luminance; survives across frames
     nvrhi::TextureHandle m_ExposureTexture;          // 1 x 1 R32_FLOAT
     // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.

@@ -60,6 +60,9 @@ void ReleasePostProcessOutputs();
 nvrhi::TextureHandle GetGeneratedBloomTexture();
 bool GetLastBloomConsts(uint32_t pass, void* out16);
 void ReleaseBloomOutputs();
+// The SkyPassParameters SkyRenderer uploaded in the last frame; false if the pass did not run in it.
+bool GetLastSkyConsts(void* out256);
+void ReleaseSkyOutputs();
 // the base pass's pipeline statistics: the value its frame N showed (the query of frame N - 2) and the last executed frame's (waits)
 void GetBasePassPipelineStatistics(nvrhi::PipelineStatistics* lastShown, nvrhi::PipelineStatistics* latest);
 

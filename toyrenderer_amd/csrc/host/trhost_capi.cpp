@@ -62,6 +62,7 @@ void trhost_shutdown(void)
         ReleaseDeferredLightingOutputs();
         ReleasePostProcessOutputs();
         ReleaseBloomOutputs();
+        ReleaseSkyOutputs();
         g_Graphic.Shutdown();
     });
     s_Initialized = false;
@@ -302,6 +303,43 @@ int trhost_get_bloom_consts(uint32_t pass, void* out16)
     return guarded([&] {
         check(out16);
         if (!GetLastBloomConsts(pass, out16)) throw nvrhi::Error("trhost_get_bloom_consts: pass " + std::to_string(pass) + " did not run in the last frame with bloom generation on");
+    });
+}
+
+int trhost_load_sky_dataset(const double* rgb, const double* rad)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!rgb || !rad) { g_Scene->m_SkyDataset.clear(); g_Scene->m_bEnableSky = false; return; }   // unloads, and with it the pass
+        for (uint32_t i = 0; i < 3 * 1080; ++i) if (!std::isfinite(rgb[i])) throw nvrhi::Error("trhost_load_sky_dataset: an RGB coefficient is not finite");
+        for (uint32_t i = 0; i < 3 * 120; ++i) if (!std::isfinite(rad[i])) throw nvrhi::Error("trhost_load_sky_dataset: a radiance coefficient is not finite");
+        g_Scene->m_SkyDataset.assign(rgb, rgb + 3 * 1080);
+        g_Scene->m_SkyDataset.insert(g_Scene->m_SkyDataset.end(), rad, rad + 3 * 120);
+    });
+}
+
+int trhost_set_sky(int enable, float turbidity, const float ground_albedo[3])
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!enable) { g_Scene->m_bEnableSky = false; return; }
+        if (g_Scene->m_SkyDataset.empty()) throw nvrhi::Error("trhost_set_sky: no dataset is loaded (trhost_load_sky_dataset first)");
+        if (!g_Scene->m_bDeferredLighting) throw nvrhi::Error("trhost_set_sky: deferred lighting is off (trhost_set_deferred_lighting first): there is no LightingOutput to fill");
+        if (!(std::isfinite(turbidity) && turbidity >= 1.0f && turbidity <= 10.0f)) throw nvrhi::Error("trhost_set_sky: the turbidity must be a finite number in [1, 10]");
+        check(ground_albedo);
+        for (int i = 0; i < 3; ++i)
+            if (!(ground_albedo[i] >= 0.0f && ground_albedo[i] <= 1.0f)) throw nvrhi::Error("trhost_set_sky: the ground albedo must lie in [0, 1]");
+        g_Scene->m_bEnableSky = true;
+        g_Scene->m_SkyTurbidity = turbidity;
+        memcpy(g_Scene->m_GroundAlbedo, ground_albedo, sizeof g_Scene->m_GroundAlbedo);
+    });
+}
+
+int trhost_get_sky_consts(void* out256)
+{
+    return guarded([&] {
+        check(out256);
+        if (!GetLastSkyConsts(out256)) throw nvrhi::Error("trhost_get_sky_consts: the sky pass did not run in the last frame");
     });
 }
 

@@ -1,4 +1,5 @@
-// soft_math.hip.h -- log2 and a two-sided exp2 in software, for the passes behind LightingOutput (k_postprocess.hip).
+// soft_math.hip.h -- log2, a two-sided exp2 and an arc cosine in software, for the passes behind LightingOutput
+// (k_postprocess.hip) and the sky pass (k_sky.hip; tests/sky_ref.c restates acosSoft word for word as sk_acos).
 // v_log_f32 and v_exp_f32 are good to 1 ulp only and cannot be restated on a CPU; these can, and tests/postprocess_ref.c
 // restates them word for word (pr_log2, pr_exp2) next to the derivation of the coefficients and of the error bounds.  The
 // lighting pass keeps its own exp2Soft (k_deferredlighting.hip): that one is proven for x <= 0 only and its words must not move.
@@ -11,6 +12,18 @@
 //             than x: representable).  p = the degree-6 Horner polynomial in fma, in [0x1.6a09e6p-1, 0x1.6a09e8p+0]; result
 //             ldexp(p, clamp(i, -300, 300)) (exact unless subnormal; the clamp makes NaN and huge arguments defined: NaN gives
 //             NaN, +inf gives NaN (inf - inf), -inf likewise).  |error| <= 2.9 * 2^-25 * 2^i.
+//   acosSoft(x): a = |x|; !(a <= 1) (outside [-1, 1], NaN) gives NaN.  asin(s) = s + s * z * P(z), z = s * s in [0, 0.25], P the
+//             degree-4 polynomial below: the weighted least-squares fit of (asin(sqrt z) / sqrt z - 1) / z at 400 Chebyshev nodes,
+//             coefficients rounded to binary32; |s + s z P(z) - asin s| <= 0.038 * 2^-24 on 400 001 points, coefficients as rounded.
+//               a <= 0.5: z = x * x, t = fma(x * z, P, x), result RN(pi / 2) - t;
+//               a >  0.5: z = (1 - a) * 0.5 (exact: Sterbenz, then a power of two), s = sqrt(z) <= 0.5, t = fma(s * z, P, s),
+//                         r = 2 * t (exact); x > 0: r, else RN(pi) - r.  acos(1) = 0 and acos(-1) = RN(pi) exactly.
+//             ERROR, absolute, in units of 2^-24.  t: its fma rounds once, t <= 0.5236: 0.5; the product s * z carries two
+//             roundings and multiplies P <= 0.1875, the term is <= 0.0236: 0.047; P's four fma round by <= 2^-26 together, times
+//             |s z| <= 0.125: 0.03; truncation 0.038: t within 0.62.  For a > 0.5 add sqrt's half ulp 2^-26 times asin' <= 1.1547:
+//             0.289, and P read at z rather than RN(s)^2, 2^-23 relative: 0.054; t within 0.963, r within 1.93.  The last
+//             subtraction rounds by <= 2^-23 (results in [2, pi]): 2; RN(pi / 2) is off by 0.733 and RN(pi) by 1.467.  So
+//             |x| <= 0.5: 3.36; x > 0.5: 1.93; x < -0.5: 5.4.  BOUND 5.5 * 2^-24 (3.28e-7); measured maximum in DESIGN.md 9.
 #pragma once
 
 #include "cull_math.hip.h"
@@ -59,6 +72,28 @@ __device__ __forceinline__ float exp2Signed(float x)
     p = cm::fma_(p, f, 1.0f);
     return __builtin_ldexpf(p, (int)cm::min_(cm::max_(i, -300.0f), 300.0f));
 #endif
+}
+
+__device__ __forceinline__ float acosPoly(float z)
+{
+    float p = 0x1.665bcap-5f;
+    p = cm::fma_(p, z, 0x1.7b4b14p-6f);
+    p = cm::fma_(p, z, 0x1.766edcp-5f);
+    p = cm::fma_(p, z, 0x1.32ea80p-4f);
+    return cm::fma_(p, z, 0x1.555626p-3f);
+}
+
+__device__ __forceinline__ float acosSoft(float x)
+{
+    const float a = __builtin_fabsf(x);
+    if (!(a <= 1.0f)) return __builtin_nanf("");
+    if (a <= 0.5f) {
+        const float z = x * x;
+        return 0x1.921fb6p+0f - cm::fma_(x * z, acosPoly(z), x);
+    }
+    const float z = (1.0f - a) * 0.5f, s = cm::sqrt_(z);
+    const float r = 2.0f * cm::fma_(s * z, acosPoly(z), s);
+    return x > 0.0f ? r : 0x1.921fb6p+1f - r;
 }
 
 } // namespace softmath

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import interop as I
 from . import rhi
+from . import sky as skymod
 from .rhi import CB, PUSH, SAMPLER, SRV, TEX_SRV, TEX_UAV, UAV
 
 SLOT_NAMES = ("early_opaque", "late_opaque", "early_alphamask", "late_alphamask")
@@ -83,7 +84,7 @@ class FrameDriver:
                  shard_late=None, raster_depth: bool = False, visibility: bool = False, gbuffer: bool = False,
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
-                 bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1):
+                 bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -116,7 +117,13 @@ class FrameDriver:
         read at mip 0, as the post pass's t2 with bloom_strength.  bloom_filter_radius: m_FilterRadius, in UV.  The count may
         not exceed floor(log2(min(W, H))) + 1: every mip has at least one texel in both axes (the reference's slider allows
         W >> k = 0; this project does not).  self.bloom_consts holds the BloomConsts of the last record(), downsamples first;
-        download_bloom(mip) reads a mip back."""
+        download_bloom(mip) reads a mip back.
+        sky: None (the default) changes nothing.  (dataset,) or (dataset, turbidity, ground_albedo) with a sky.HosekDataset
+        (needs lighting=True; the reference's defaults are turbidity 2.0 and ground albedo (0.1, 0.1, 0.1)): SkyRenderer
+        (SkyRenderer.cpp).  One "sky_PS_HosekWilkieSky" dispatch directly behind the lighting dispatch, in front of bloom and the
+        histogram clear, whatever debug_mode is, fills every texel of LightingOutput whose depth is <= 0.  The sun direction is
+        dir_light[0] as given, the camera position camera_origin, the matrix the lighting pass's m_ClipToWorld.
+        self.sky_consts holds the 256-byte SkyPassParameters of the last record()."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -149,6 +156,17 @@ class FrameDriver:
             self.bloom_strength = np.float32(bloom_strength)
         self.bloom_filter_radius = np.float32(bloom_filter_radius)
         self.post_consts = None
+        self.sky, self.sky_consts = None, None
+        if sky is not None:
+            if not lighting:
+                raise ValueError("sky=... needs lighting=True: the pass fills the texels of LightingOutput the lighting pass leaves")
+            sky = tuple(sky)
+            if not (1 <= len(sky) <= 3) or not isinstance(sky[0], skymod.HosekDataset):
+                raise ValueError("sky: needs (dataset, turbidity, ground_albedo) with a sky.HosekDataset first")
+            turbidity = sky[1] if len(sky) > 1 else skymod.DEFAULT_TURBIDITY
+            albedo = sky[2] if len(sky) > 2 else skymod.DEFAULT_GROUND_ALBEDO
+            skymod.check_settings(turbidity, albedo)
+            self.sky = (sky[0], np.float32(turbidity), tuple(np.float32(x) for x in albedo))
         self.dir_light = (tuple(float(x) for x in dir_light[0]), float(dir_light[1]))
         self.camera_origin = tuple(float(x) for x in camera_origin)
         self.shadow_mask, self.ssao = shadow_mask, ssao
@@ -355,6 +373,17 @@ class FrameDriver:
             b.append(TEX_SRV(4, self.shadow_mask))
         cl.dispatch("deferredlighting_PS_Main_Debug" if self.debug_mode != 0 else "deferredlighting_PS_Main", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
 
+    # ---- SkyRenderer::Render (SkyRenderer.cpp:163-208) -------------------------------------------------------------------
+    def _sky(self, cl):
+        v = self.view
+        dataset, turbidity, albedo = self.sky
+        sun = np.asarray(self.dir_light[0], np.float32)
+        params = skymod.sky_parameters(dataset, turbidity, albedo, sun)
+        self.sky_consts = skymod.pass_parameters(self.lighting_consts["m_ClipToWorld"][0], sun, self.camera_origin, params)
+        cb = cl.constant_buffer(self.sky_consts, "SkyPassParameters")
+        cl.dispatch("sky_PS_HosekWilkieSky", [CB(0, cb), TEX_SRV(0, self.depth), TEX_UAV(0, self.lighting_output, 0)],
+                    ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
+
     # ---- BloomRenderer::Render (BloomRenderer.cpp:57-141) ---------------------------------------------------------------
     def _bloom(self, cl):
         v, tex, n = self.view, self.bloom_texture, self.bloom_mips - 1
@@ -483,6 +512,8 @@ class FrameDriver:
             cl.end_pipeline_stats(query)
         if self.lighting_on:                                                             # the next renderer after GBufferRenderer
             self._deferred_lighting(cl)
+        if self.sky is not None:                                                         # Scene.cpp:502: between lighting and bloom
+            self._sky(cl)
         if self.bloom_mips:                                                              # Scene.cpp:503: between lighting and adapt luminance
             self._bloom(cl)
         if self.post_on:                                                                 # Scene.cpp's order: adapt luminance, then post

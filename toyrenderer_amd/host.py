@@ -33,6 +33,7 @@ HOST_SYMBOLS = [
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
+    "trhost_load_sky_dataset", "trhost_set_sky", "trhost_get_sky_consts",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # trhost_allgather_fn
@@ -108,6 +109,9 @@ def load() -> C.CDLL:
     L.trhost_set_bloom.argtypes = [C.c_int, u32, C.c_float, C.c_float]
     L.trhost_download_bloom.argtypes = [u32, vp, u64]
     L.trhost_get_bloom_consts.argtypes = [u32, vp]
+    L.trhost_load_sky_dataset.argtypes = [vp, vp]
+    L.trhost_set_sky.argtypes = [C.c_int, C.c_float, vp]
+    L.trhost_get_sky_consts.argtypes = [vp]
     L.trhost_get_scene_luminance.argtypes = [vp, vp]
     L.trhost_reset_exposure.argtypes = []
     L.trhost_get_post_process_consts.argtypes = [vp, vp, vp, vp]
@@ -347,6 +351,26 @@ class Renderer:
         w = np.empty((self.render[1] >> mip, self.render[0] >> mip), np.uint32)
         _check(load().trhost_download_bloom(int(mip), w.ctypes.data, w.nbytes))
         return w
+
+    def load_sky_dataset(self, dataset):
+        """A sky.HosekDataset (the Hosek-Wilkie RGB tables, an input of the integrator); None unloads it and switches the pass off."""
+        if dataset is None:
+            _check(load().trhost_load_sky_dataset(None, None))
+            return
+        rgb, rad = np.ascontiguousarray(dataset.rgb, np.float64), np.ascontiguousarray(dataset.rad, np.float64)
+        assert rgb.shape == (3, 1080) and rad.shape == (3, 120)
+        _check(load().trhost_load_sky_dataset(rgb.ctypes.data, rad.ctypes.data))
+
+    def set_sky(self, enable: bool, turbidity: float = 2.0, ground_albedo=(0.1, 0.1, 0.1)):
+        """SkyRenderer on or off (needs load_sky_dataset() and set_deferred_lighting(True))."""
+        a = np.ascontiguousarray(ground_albedo, np.float32).reshape(3)
+        _check(load().trhost_set_sky(int(bool(enable)), float(turbidity), a.ctypes.data))
+
+    def sky_consts(self) -> np.ndarray:
+        """The SkyPassParameters of the last frame; raises if the pass did not run in it."""
+        k = np.zeros(1, I.SkyPassParameters)
+        _check(load().trhost_get_sky_consts(k.ctypes.data))
+        return k
 
     def bloom_consts(self, passes: int) -> np.ndarray:
         """The BloomConsts of the first `passes` bloom dispatches of the last frame, downsamples first."""

@@ -83,6 +83,10 @@ PostProcessParameters = np.dtype([                                              
     ("m_OutputDims", np.uint32, (2,)), ("m_ManualExposure", np.float32), ("m_MiddleGray", np.float32), ("m_WhitePoint", np.float32),
     ("m_BloomStrength", np.float32)])
 BloomConsts = np.dtype([("m_InvSourceResolution", np.float32, (2,)), ("m_FilterRadius", np.float32), ("m_bIsFirstDownsample", np.uint32)])   # ShaderInterop.h:79-84
+HosekWilkieSkyParameters = np.dtype([("m_Params", np.float32, (10, 4))])                                                    # ShaderInterop.h:146-149
+SkyPassParameters = np.dtype([                                                                                             # ShaderInterop.h:297-305
+    ("m_ClipToWorld", np.float32, (4, 4)), ("m_SunLightDir", np.float32, (3,)), ("PAD0", np.uint32), ("m_CameraPosition", np.float32, (3,)),
+    ("PAD1", np.uint32), ("m_HosekParams", HosekWilkieSkyParameters)])
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
@@ -90,7 +94,7 @@ SIZES = {
     "BasePassConstants": 256, "MinMaxDownsampleConsts": 12, "NodeLocalTransform": 48,
     "TextureData": 20, "MaterialData": 124, "DeferredLightingConsts": 112,
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
-    "BloomConsts": 16,
+    "BloomConsts": 16, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)
