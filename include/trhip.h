@@ -108,6 +108,16 @@ uint32_t    trhip_abi_version(void);
  * whose size is the resolution; samplers are accepted and ignored.  A texel is written iff its depth is <= 0.0f (NaN is skipped):
  * the complement of the lighting pass.  Refused at record time: a missing or short b0, another format at t0 or u0, a missing
  * binding, a mip other than 0, depth and target of different size.  The arithmetic convention is stated in csrc/k_sky.hip.
+ * "ambientocclusion_CS_XeGTAO_PrefilterDepths", "ambientocclusion_CS_XeGTAO_MainPass DEBUG_OUTPUT_MODE=0" and
+ * "ambientocclusion_CS_XeGTAO_Denoise" (ambientocclusion.hlsl, XeGTAO.hlsli, AmbientOcclusionRenderer.cpp): direct dispatches.
+ * Prefilter: ceil(W / 16) x ceil(H / 16) groups; b0 GTAOConstants (96 bytes, a constant buffer), t0 (texture) the R32_FLOAT depth,
+ * u0..u4 mips 0..4 of one R16_FLOAT texture with exactly 5 mips at the depth's size.  Main: ceil(W / 8) x ceil(H / 8) groups; b0,
+ * b1 push constants XeGTAOMainPassConstantBuffer (68 bytes), t0 that chain, t2 GBufferA (RGBA32_UINT), u0 the working AO term
+ * (R8_UINT), u1 the edges (R8_UNORM); the reference's t1 (Hilbert table) and u2 (debug texture) are not read.  Denoise:
+ * ceil(W / 16) x ceil(H / 8) groups; b0, b1 push constants XeGTAODenoiseConstants (4 bytes), t0 the AO term (R8_UINT), t1 the
+ * edges, u0 the output (R8_UINT, another texture than t0).  Samplers are accepted and ignored.  Refused at record time: a missing
+ * binding, another format or size, a depth chain without 5 mips or u<k> not its mip k, a constant block of another size, groups
+ * that do not cover the target, an indirect dispatch.  The arithmetic convention is tests/gtao_ref.c's (csrc/k_ambientocclusion.hip).
  * "bloom_PS_Downsample" and "bloom_PS_Upsample" (bloom.hlsl, BloomRenderer.cpp; the stand-ins of the full-screen passes of
  * Graphic.cpp:832-860): a direct dispatch of [numthreads(8, 8, 1)] groups covering the destination mip; b0 or push constants
  * BloomConsts (16 bytes: the downsample reads m_InvSourceResolution and m_bIsFirstDownsample, the upsample m_FilterRadius), t0

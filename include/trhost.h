@@ -128,7 +128,15 @@ int  trhost_get_deferred_lighting_consts(void* out112);
  * LightingOutput whose depth is <= 0 (the reference's defaults: 2.0 and (0.1, 0.1, 0.1)); the sun direction is the directional
  * light vector as given.  Refused: no dataset loaded; deferred lighting off; a turbidity that is not finite or outside [1, 10];
  * an albedo outside [0, 1].  trhost_set_sky(0, ...) switches it off.  trhost_get_sky_consts copies the 256 bytes of
- * SkyPassParameters of the last frame and refuses if the pass did not run in it. */
+ * SkyPassParameters of the last frame and refuses if the pass did not run in it.
+ * Ambient occlusion (AmbientOcclusionRenderer.cpp, XeGTAO; off by default).  trhost_set_ambient_occlusion(1, quality,
+ * denoisePasses, radius, falloffRange, finalValuePower, depthMipSamplingOffset) schedules AmbientOcclusionRenderer between
+ * GBufferRenderer and DeferredLightingRenderer (the reference's defaults: 3, 3, 0.5, 0.615, 2.2, 3.3): the prefilter, the main
+ * pass and max(1, denoisePasses) denoise dispatches into the SSAO texture, which the lighting pass then binds at t3 with
+ * m_SSAOEnabled = 1 (only debug view 9 shows it).  Refused: the G-buffer off; quality or passes above 3; a radius that is negative
+ * or not finite; another setting that is not finite.  trhost_set_ambient_occlusion(0, ...) switches it off.  trhost_download_ssao
+ * waits and copies the W x H bytes of the SSAO texture; trhost_get_gtao_consts copies the 96 bytes of GTAOConstants of the last
+ * frame; both refuse if the pass did not run in it. */
 int  trhost_set_post_process(int enable);
 int  trhost_set_exposure(float manual, float middle_gray);
 int  trhost_set_auto_exposure(float min_lum, float max_lum, float speed_per_ms);
@@ -140,6 +148,10 @@ int  trhost_get_bloom_consts(uint32_t pass, void* out16);
 int  trhost_load_sky_dataset(const double* rgb, const double* rad);
 int  trhost_set_sky(int enable, float turbidity, const float ground_albedo[3]);
 int  trhost_get_sky_consts(void* out256);
+int  trhost_set_ambient_occlusion(int enable, uint32_t quality, uint32_t denoise_passes, float radius, float falloff_range, float final_value_power,
+                                  float depth_mip_sampling_offset);
+int  trhost_download_ssao(uint8_t* bytes, uint64_t size);
+int  trhost_get_gtao_consts(void* out96);
 int  trhost_download_back_buffer(uint32_t* words, uint64_t bytes);
 int  trhost_get_scene_luminance(float* luminance, float* exposure);
 int  trhost_reset_exposure(void);

@@ -1,0 +1,415 @@
+"""tests/gtao_ref.c, the definition of the ambient occlusion passes (csrc/k_ambientocclusion.hip), checked on the CPU: its binary16
+rounding against numpy, the software sine and cosine against float64, the Hilbert index against the table recurrence,
+GTAOUpdateConstants against a hand evaluation, the three passes against an independent float64 restatement in numpy, the ordering a
+crease and a wall must show, an all-sky image, and the interface the feature adds (structs, symbols, shader names)."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import gtao_ref as GR  # noqa: E402
+from toyrenderer_amd import gtao, synth  # noqa: E402
+from toyrenderer_amd import interop as I  # noqa: E402
+
+F = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# measured on the scenes of _restatement_scenes(): the largest and the mean difference, in bytes, of the final SSAO byte
+# between the binary16 reference and the float64 restatement, per quality level
+MEASURED_MAX = {0: 8, 1: 5, 2: 5, 3: 5}
+MEASURED_MEAN = {0: 0.360, 1: 0.403, 2: 0.358, 3: 0.434}             # recorded, not asserted
+
+
+@pytest.fixture(scope="module")
+def gt(tmp_path_factory):
+    return GR.load(tmp_path_factory.mktemp("gtao_ref"))
+
+
+# ---- 1. rounding ------------------------------------------------------------------------------------------------------------------
+def test_every_binary16_value_round_trips(gt):
+    w = np.arange(65536, dtype=np.uint16)
+    v = GR.half_value(gt, w)
+    ref = w.view(np.float16).astype(F)
+    nan = np.isnan(ref)
+    assert np.array_equal(np.isnan(v), nan)
+    assert np.array_equal(v[~nan].view(np.uint32), ref[~nan].view(np.uint32))             # the value of every word, signed zeros included
+    r = GR.r16(gt, v)
+    assert np.array_equal(r[~nan].view(np.uint32), v[~nan].view(np.uint32))               # rounding a binary16 value changes nothing
+    assert np.array_equal(GR.half_bits(gt, v)[~nan], w[~nan])
+    assert np.all(GR.half_bits(gt, v)[nan] == 0x7E00)                                     # every NaN is stored as one word
+
+
+def test_rounding_matches_numpy_on_a_million_values(gt):
+    rng = np.random.default_rng(0x16)
+    bits = rng.integers(0, 2 ** 32, 700_000, dtype=np.uint64).astype(np.uint32)
+    x = [bits.view(F)]
+    x.append(rng.uniform(-70000.0, 70000.0, 100_000).astype(F))                           # around the overflow edge
+    x.append((rng.uniform(-1.0, 1.0, 100_000) * 2.0 ** -14).astype(F))                    # subnormal results
+    h = rng.integers(0, 0x7C00, 50_000).astype(np.uint16)                                 # ties: exactly half way between two neighbours
+    lo, hi = h.view(np.float16).astype(np.float64), (h + 1).astype(np.uint16).view(np.float16).astype(np.float64)
+    mid = ((lo + hi) / 2.0)
+    x.append(np.concatenate([mid, -mid]).astype(F))
+    x.append(np.array([65504.0, 65519.996, 65520.0, 65520.004, -65520.0, 2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * 1.0000001, 0.0, -0.0, np.inf, -np.inf], F))
+    x = np.concatenate(x)
+    assert x.size >= 1_000_000
+    with np.errstate(over="ignore"):
+        want = x.astype(np.float16)
+    got = GR.r16(gt, x)
+    nan = np.isnan(x)
+    assert np.array_equal(np.isnan(got), nan)
+    assert np.array_equal(got[~nan].view(np.uint32), want.astype(F)[~nan].view(np.uint32))
+    assert np.array_equal(GR.half_bits(gt, got)[~nan], want.view(np.uint16)[~nan])
+
+
+# ---- 2. sine and cosine -------------------------------------------------------------------------------------------------------------
+def test_sin_cos_against_float64(gt, capsys):
+    """The derived bound holds on a million seeded arguments of [-3 pi, 3 pi] and, rounded to binary16, on every binary16 argument
+    of that range; the measured maxima are printed (DESIGN.md 9 records them)."""
+    bound = GR.sincos_bound(gt)
+    assert bound == 3.0 * 2.0 ** -24
+    rng = np.random.default_rng(0x51)
+    x = rng.uniform(-3.0 * math.pi, 3.0 * math.pi, 1_000_000).astype(F)
+    x64 = x.astype(np.float64)
+    es, ec = np.max(np.abs(GR.sin(gt, x) - np.sin(x64))), np.max(np.abs(GR.cos(gt, x) - np.cos(x64)))
+    w = np.arange(65536, dtype=np.uint16)
+    h = w.view(np.float16).astype(F)
+    h = h[np.abs(h) <= 3.0 * math.pi]
+    h64 = h.astype(np.float64)
+    hs = np.max(np.abs(GR.r16(gt, GR.sin(gt, h)).astype(np.float64) - np.sin(h64)))
+    hc = np.max(np.abs(GR.r16(gt, GR.cos(gt, h)).astype(np.float64) - np.cos(h64)))
+    with capsys.disabled():
+        print(f"\nsinSoft max error {es * 2 ** 24:.3f} * 2^-24, cosSoft {ec * 2 ** 24:.3f} * 2^-24; rounded to binary16 over {h.size} arguments: "
+              f"sin {hs * 2 ** 12:.4f} * 2^-12, cos {hc * 2 ** 12:.4f} * 2^-12")
+    assert es <= bound and ec <= bound
+    assert hs <= 2.0 ** -12 + bound and hc <= 2.0 ** -12 + bound
+
+
+def test_sin_cos_special_arguments(gt):
+    assert gt.gt_sin(0.0) == 0.0 and gt.gt_cos(0.0) == 1.0
+    assert gt.gt_sin(-0.0) == 0.0 and math.copysign(1.0, gt.gt_sin(-0.0)) == 1.0            # the reduction's fma(+0, P1, -0) is +0
+    for bad in (float("nan"), float("inf"), float("-inf"), 10.000001, -10.000001, 1e30):
+        assert math.isnan(gt.gt_sin(bad)) and math.isnan(gt.gt_cos(bad))
+    for edge in (10.0, -10.0):
+        assert abs(gt.gt_sin(edge) - math.sin(edge)) <= GR.sincos_bound(gt) and abs(gt.gt_cos(edge) - math.cos(edge)) <= GR.sincos_bound(gt)
+
+
+# ---- 3. the Hilbert index -----------------------------------------------------------------------------------------------------------
+def _hilbert_recurrence(x, y):
+    """XeGTAO::HilbertIndex as the table is filled: with its branches."""
+    index, level = 0, 32
+    while level > 0:
+        rx, ry = int((x & level) > 0), int((y & level) > 0)
+        index += level * level * ((3 * rx) ^ ry)
+        if ry == 0:
+            if rx == 1:
+                x, y = 63 - x, 63 - y
+            x, y = y, x
+        level //= 2
+    return index
+
+
+def test_hilbert_index_equals_the_table(gt):
+    table = np.array([[_hilbert_recurrence(x, y) for x in range(64)] for y in range(64)])
+    got = np.array([[gt.gt_hilbert(x, y) for x in range(64)] for y in range(64)])
+    assert np.array_equal(got, table)
+    assert sorted(table.ravel().tolist()) == list(range(4096))                            # a curve: every index once
+    assert gt.gt_hilbert(64 + 5, 128 + 9) == table[9, 5]                                   # pixel % 64
+
+
+# ---- 4. the constants -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("render", [(1920, 1080), (512, 512)], ids=["16:9", "1:1"])
+def test_update_constants_equals_a_hand_evaluation(render):
+    W, H = render
+    view = synth.make_view(render=render, near=0.1)
+    P = view.viewToClip
+    k = gtao.update_constants(W, H, gtao.check_settings(dict(radius=0.75)), P, 200)[0]
+    one, two = F(1.0), F(2.0)
+    tan_y = one / F(one / F(math.tan(0.5 * math.radians(45.0))))                          # 1 / P[1][1], P[1][1] = 1 / tan(fov / 2) in float32
+    tan_x = one / F(F(one / F(math.tan(0.5 * math.radians(45.0)))) / F(W / H))
+    assert k["ViewportSize"].tolist() == [W, H]
+    assert k["ViewportPixelSize"].tolist() == [one / F(W), one / F(H)]
+    assert k["DepthUnpackConsts"].tolist() == [F(-0.1), 0.0] and not np.signbit(k["DepthUnpackConsts"][1])   # no flip: -0.1 * 0 is not < 0
+    assert k["CameraTanHalfFOV"].tolist() == [tan_x, tan_y]
+    assert k["NDCToViewMul"].tolist() == [tan_x * two, tan_y * -two] and k["NDCToViewAdd"].tolist() == [-tan_x, tan_y]
+    assert k["NDCToViewMul_x_PixelSize"].tolist() == [F(tan_x * two) * (one / F(W)), F(tan_y * -two) * (one / F(H))]
+    assert (k["EffectRadius"], k["EffectFalloffRange"], k["FinalValuePower"], k["DepthMIPSamplingOffset"]) == (F(0.75), F(0.615), F(2.2), F(3.3))
+    assert (k["RadiusMultiplier"], k["SampleDistributionPower"], k["ThinOccluderCompensation"], k["Padding0"]) == (F(1.457), F(2.0), F(0.0), F(0.0))
+    assert k["DenoiseBlurBeta"] == F(1.2) and k["NoiseIndex"] == 200 % 64
+    off = gtao.update_constants(W, H, gtao.check_settings(dict(denoise_passes=0)), P, 200)[0]
+    assert off["DenoiseBlurBeta"] == F(1e4) and off["NoiseIndex"] == 0                     # denoise off: no temporal noise
+    flipped = P.copy()
+    flipped[2, 2] = 0.5                                                                    # a finite far plane of the other handedness: mul * add < 0
+    assert gtao.update_constants(W, H, gtao.check_settings({}), flipped, 0)[0]["DepthUnpackConsts"].tolist() == [F(-0.1), F(-0.5)]
+
+
+def test_settings_are_checked():
+    assert gtao.check_settings({}) == gtao.DEFAULTS
+    for bad in (dict(quality=4), dict(quality=-1), dict(quality=1.5), dict(denoise_passes=4), dict(radius=-0.1), dict(radius=float("nan")),
+                dict(radius=float("inf")), dict(final_value_power=float("nan")), dict(colour=1), 3):
+        with pytest.raises(ValueError, match="ao"):
+            gtao.check_settings(bad)
+
+
+# ---- 5. the independent restatement: float64 throughout, libm trigonometry, the same sampling rule ------------------------------------
+def _fast_acos64(x):
+    a = np.abs(x)
+    s = 1.0 - a
+    bits = (np.asarray(s, F).view(np.int32) >> 1) + np.int32(0x1FBD1DF5)
+    res = (-0.156583 * a + 1.570796) * bits.view(F).astype(np.float64)
+    return np.where(x >= 0, res, 3.141593 - res)
+
+
+def _falloff64(k, radius):
+    rng = 0.615 * radius
+    frm = radius * (1.0 - float(k["EffectFalloffRange"]))
+    with np.errstate(all="ignore"):
+        return -1.0 / rng, frm / rng + 1.0
+
+
+def _mip_filter64(k, d):
+    """d: (4, ...) depths -> the weighted average."""
+    mul, add = _falloff64(k, 0.75 * float(k["EffectRadius"]) * 1.457)
+    mx = np.max(d, axis=0)
+    w = np.clip((mx - d) * mul + add, 0.0, 1.0)
+    with np.errstate(all="ignore"):
+        return np.sum(w * d, axis=0) / np.sum(w, axis=0)
+
+
+def _restate_prefilter(k, depth):
+    """Five float64 mips; a mip texel outside the extent of the mip below is the clamped read the group would make."""
+    H, W = depth.shape
+    with np.errstate(all="ignore"):
+        z = float(k["DepthUnpackConsts"][0]) / (float(k["DepthUnpackConsts"][1]) - depth.astype(np.float64))
+    z = np.where(np.isnan(z), 0.0, np.clip(z, 0.0, 65504.0))
+    gw, gh = (W + 15) // 16 * 16, (H + 15) // 16 * 16                                      # what whole groups cover
+    yy, xx = np.minimum(np.arange(gh), H - 1), np.minimum(np.arange(gw), W - 1)
+    full = z[np.ix_(yy, xx)]
+    mips, cur = [z], full
+    for level in range(1, 5):
+        cur = _mip_filter64(k, np.stack([cur[0::2, 0::2], cur[0::2, 1::2], cur[1::2, 0::2], cur[1::2, 1::2]]))
+        mips.append(cur[:max(H >> level, 1), :max(W >> level, 1)])
+    return mips
+
+
+def _restate_main(k, push, mips, gbufferA, gt):
+    H, W = mips[0].shape
+    slices, steps = gtao.QUALITY[int(push["m_Quality"][0])]
+    py, px = np.mgrid[0:H, 0:W]
+    psx, psy = float(k["ViewportPixelSize"][0]), float(k["ViewportPixelSize"][1])
+    nx, ny = (px + 0.5) * psx, (py + 0.5) * psy
+    z0 = mips[0]
+    cl = lambda a, n: np.clip(a, 0, n - 1)                                                 # noqa: E731
+    zl, zr, zt, zb = z0[py, cl(px - 1, W)], z0[py, cl(px + 1, W)], z0[cl(py - 1, H), px], z0[cl(py + 1, H), px]
+    with np.errstate(all="ignore"):
+        e = np.stack([zl, zr, zt, zb]) - z0
+        slr, stb = (e[1] - e[0]) * 0.5, (e[3] - e[2]) * 0.5
+        adj = e + np.stack([slr, -slr, stb, -stb])
+        e = np.minimum(np.abs(e), np.abs(adj))
+        e = np.clip(1.25 - e / (z0 * 0.011), 0.0, 1.0)
+        e = np.where(np.isnan(e), 0.0, e)
+        packed = np.tensordot(np.array([64.0, 16.0, 4.0, 1.0]) / 255.0, np.rint(e * 2.9), 1)
+    edges = np.floor(np.clip(packed, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+    def view_pos(sx, sy, depth):
+        return np.stack([(float(k["NDCToViewMul"][0]) * sx + float(k["NDCToViewAdd"][0])) * depth, (float(k["NDCToViewMul"][1]) * sy + float(k["NDCToViewAdd"][1])) * depth, depth])
+
+    # the view-space normal: octahedron decode, the row vector times the matrix, z negated
+    g = gbufferA[..., 1]
+    fx, fy = (g & 0xFFFF) / 65535.0 * 2.0 - 1.0, (g >> 16) / 65535.0 * 2.0 - 1.0
+    n = np.stack([fx, fy, 1.0 - np.abs(fx) - np.abs(fy)])
+    t = np.clip(-n[2], 0.0, 1.0)
+    n[0] += np.where(n[0] >= 0, -t, t)
+    n[1] += np.where(n[1] >= 0, -t, t)
+    n /= np.linalg.norm(n, axis=0)
+    M = push["m_WorldToViewNoTranslate"][0].astype(np.float64)
+    normal = np.tensordot(M[:3, :3].T, n, 1) + M[3, :3, None, None]
+    normal[2] *= -1.0
+
+    z = z0 * 0.99920
+    center = view_pos(nx, ny, z)
+    with np.errstate(all="ignore"):
+        view_vec = -center / np.linalg.norm(center, axis=0)
+        radius = float(k["EffectRadius"]) * 1.457
+        fmul, fadd = _falloff64(k, radius)
+        ssr = radius / (z * float(k["NDCToViewMul_x_PixelSize"][0]))
+        vis = np.clip((10.0 - ssr) / 100.0, 0.0, 1.0) * 0.5
+        vis = np.where(np.isnan(vis), 0.0, vis)
+        min_s = 1.3 / ssr
+        idx = np.array([[gt.gt_hilbert(x % 64, y % 64) for x in range(W)] for y in range(H)], np.float64) + 288 * (int(k["NoiseIndex"]) % 64)
+        noise_slice, noise_sample = np.modf(0.5 + idx * 0.75487766624669276005)[0], np.modf(0.5 + idx * 0.5698402909980532659114)[0]
+        dot = lambda a, b: np.sum(a * b, axis=0)                                           # noqa: E731
+        for s in range(slices):
+            phi = (s + noise_slice) / slices * math.pi
+            cp, sp = np.cos(phi), np.sin(phi)
+            omega = np.stack([cp, -sp]) * ssr
+            direction = np.stack([cp, sp, np.zeros_like(cp)])
+            ortho = direction - dot(direction, view_vec) * view_vec
+            axis = np.cross(ortho, view_vec, axis=0)
+            axis /= np.linalg.norm(axis, axis=0)
+            proj = normal - axis * dot(normal, axis)
+            sign = np.sign(dot(ortho, proj))
+            plen = np.linalg.norm(proj, axis=0)
+            cos_norm = np.clip(dot(proj, view_vec) / plen, 0.0, 1.0)
+            cos_norm = np.where(np.isnan(cos_norm), 0.0, cos_norm)
+            nn = sign * _fast_acos64(cos_norm)
+            low0, low1 = np.cos(nn + math.pi / 2), np.cos(nn - math.pi / 2)
+            hc0, hc1 = low0.copy(), low1.copy()
+            for st in range(steps):
+                step_noise = np.modf(noise_sample + (s + st * steps) * 0.6180339887498948482)[0]
+                sv = ((st + step_noise) / steps) ** 2 + min_s
+                off = sv * omega
+                length = np.linalg.norm(off, axis=0)
+                mip = np.clip(np.where(length > 0, np.log2(np.where(length > 0, length, 1.0)), -np.inf) - float(k["DepthMIPSamplingOffset"]), 0.0, 5.0)
+                level = np.clip(np.floor(mip + 0.5), 0, 4).astype(int)
+                off = np.rint(off) * np.array([psx, psy])[:, None, None]
+                for side, (hc, low) in enumerate(((hc0, low0), (hc1, low1))):
+                    u, v = (nx + off[0], ny + off[1]) if side == 0 else (nx - off[0], ny - off[1])
+                    sz = np.zeros((H, W))
+                    for lv in range(5):
+                        mh, mw = mips[lv].shape
+                        tx = np.clip(np.nan_to_num(np.floor(u * mw), nan=0.0, posinf=1e9, neginf=-1e9), 0, mw - 1).astype(int)
+                        ty = np.clip(np.nan_to_num(np.floor(v * mh), nan=0.0, posinf=1e9, neginf=-1e9), 0, mh - 1).astype(int)
+                        sz = np.where(level == lv, mips[lv][ty, tx], sz)
+                    delta = view_pos(u, v, sz) - center
+                    dist = np.linalg.norm(delta, axis=0)
+                    weight = np.clip(dist * fmul + fadd, 0.0, 1.0)
+                    weight = np.where(np.isnan(weight), 0.0, weight)
+                    shc = dot(delta / dist, view_vec)
+                    shc = low + weight * (shc - low)
+                    np.copyto(hc, np.fmax(hc, shc))
+            plen = plen + 0.05 * (1.0 - plen)
+            h0, h1 = -_fast_acos64(hc1), _fast_acos64(hc0)
+            iarc0 = (cos_norm + 2.0 * h0 * np.sin(nn) - np.cos(2.0 * h0 - nn)) / 4.0
+            iarc1 = (cos_norm + 2.0 * h1 * np.sin(nn) - np.cos(2.0 * h1 - nn)) / 4.0
+            vis = vis + plen * (iarc0 + iarc1)
+        vis = vis / slices
+        vis = np.where(vis > 0, np.power(np.where(vis > 0, vis, 1.0), float(k["FinalValuePower"])), 0.0)
+        vis = np.fmax(0.03, vis)
+        vis = np.clip(vis / 1.5, 0.0, 1.0)
+    return np.floor(vis * 255.0 + 0.5).astype(np.uint8), edges
+
+
+def _restate_denoise(k, final, ao, edges):
+    H, W = ao.shape
+    py, px = np.mgrid[0:H, 0:W]
+    cl = lambda a, n: np.clip(a, 0, n - 1)                                                 # noqa: E731
+
+    def unpack(b):
+        p = np.floor(b / 255.0 * 255.5).astype(int)
+        return np.stack([((p >> 6) & 3) / 3.0, ((p >> 4) & 3) / 3.0, ((p >> 2) & 3) / 3.0, (p & 3) / 3.0])
+    at = lambda img, dx, dy: img[cl(py + dy, H), cl(px + dx, W)]                           # noqa: E731
+    eL, eT, eR, eB, eC = (unpack(at(edges, dx, dy).astype(np.float64)) for dx, dy in ((-1, 0), (0, -1), (1, 0), (0, 1), (0, 0)))
+    eC = eC * np.stack([eL[1], eR[0], eT[3], eB[2]])
+    edginess = np.clip(4.0 - 2.5 - np.sum(eC, axis=0), 0.0, 1.0) / (4.0 - 2.5) * 0.5
+    eC = np.clip(eC + edginess, 0.0, 1.0)
+    d = 0.85 * 0.5
+    wTL, wTR = d * (eC[0] * eL[2] + eC[2] * eT[0]), d * (eC[2] * eT[1] + eC[1] * eR[2])
+    wBL, wBR = d * (eC[3] * eB[0] + eC[0] * eL[3]), d * (eC[1] * eR[3] + eC[3] * eB[1])
+    vis = lambda dx, dy: at(ao, dx, dy).astype(np.float64) / 255.0                         # noqa: E731
+    blur = float(k["DenoiseBlurBeta"]) if final else float(k["DenoiseBlurBeta"]) / 5.0
+    sw = np.full((H, W), blur)
+    total = vis(0, 0) * sw
+    for (dx, dy), w in (((-1, 0), eC[0]), ((1, 0), eC[1]), ((0, -1), eC[2]), ((0, 1), eC[3]), ((-1, -1), wTL), ((1, -1), wTR), ((-1, 1), wBL), ((1, 1), wBR)):
+        total = total + w * vis(dx, dy)
+        sw = sw + w
+    out = total / sw * (1.5 if final else 1.0)
+    return np.minimum(np.floor(out * 255.0 + 0.5), 255).astype(np.uint8)
+
+
+def _restate_frame(k, push, depth, gbufferA, passes, gt):
+    mips = _restate_prefilter(k[0], np.asarray(depth))
+    ao, edges = _restate_main(k[0], push, mips, gbufferA, gt)
+    pp = [ao, None]
+    n = max(1, passes)
+    for i in range(n):
+        pp[1] = _restate_denoise(k[0], i == n - 1, pp[0], edges)
+        pp.reverse()
+    return pp[0], mips                                                                     # the finally-applied image: the last output
+
+
+def _restatement_scenes(quality):
+    W, H = 96, 54
+    k = GR.consts(W, H, dict(quality=quality))
+    scenes = {"crease": GR.crease_scene(k, W, H), "wall": GR.wall_scene(W, H)}
+    images = GR.depth_images(W, H, seed=77)
+    scenes["tilted"] = (images["tilted"], GR.random_gbuffer(W, H, seed=3))
+    scenes["step"] = (images["step"], GR.wall_scene(W, H)[1])
+    scenes["noise"] = (images["noise"], GR.random_gbuffer(W, H, seed=4))
+    return k, scenes
+
+
+@pytest.mark.parametrize("quality", range(4))
+def test_float64_restatement(gt, quality, capsys):
+    """What catches a mistake the C reference and the kernel would share: the three passes restated in float64 with libm's
+    trigonometry give the reference's final byte within the measured maximum + 1 (the byte covers libm differences) on every texel;
+    the differences come from the binary16 roundings flipping a snapped sample, a mip level or an edge code."""
+    k, scenes = _restatement_scenes(quality)
+    worst, total, count = 0, 0.0, 0
+    for name, (depth, g) in scenes.items():
+        ref = GR.frame(gt, k, GR.push(quality), depth, g, 3)
+        got, mips = _restate_frame(k, GR.push(quality), depth, g, 3, gt)                  # 3 passes: the final image is the SSAO texture's
+        chain0 = GR.half_value(gt, GR.chain_mip(ref["chain"], *depth.shape[::-1], 0)).astype(np.float64)
+        assert np.all(np.abs(chain0 - mips[0]) <= np.abs(mips[0]) * 2.0 ** -11 + 1e-30), name   # the depths agree to binary16's half ulp
+        diff = np.abs(got.astype(int) - ref["ssao"].astype(int))
+        worst, total, count = max(worst, int(diff.max())), total + float(diff.sum()), count + diff.size
+    with capsys.disabled():
+        print(f"\nquality {quality}: float64 restatement against the binary16 reference: max {worst} bytes, mean {total / count:.3f}")
+    assert worst <= MEASURED_MAX[quality] + 1
+
+
+# ---- 6. what the image must show -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("quality", range(4))
+def test_crease_is_darker_than_the_open_wall(gt, quality):
+    W, H = 160, 90
+    k = GR.consts(W, H, dict(quality=quality, denoise_passes=3))
+    depth, g = GR.crease_scene(k, W, H)
+    ssao = GR.frame(gt, k, GR.push(quality), depth, g, 3)["ssao"]
+    rows = slice(10, H - 10)
+    crease = ssao[rows, W // 2 - 1:W // 2 + 1]
+    assert np.all(crease.max(axis=1) < ssao[rows, W // 2 + 10]) and np.all(crease.max(axis=1) < ssao[rows, W // 2 - 11])
+    depth, g = GR.wall_scene(W, H)
+    wall = GR.frame(gt, k, GR.push(quality), depth, g, 3)["ssao"]
+    assert np.all(wall[10:H - 10, 10:W - 10] >= crease.max())
+
+
+# ---- 7. sky -----------------------------------------------------------------------------------------------------------------------------
+def test_all_sky(gt):
+    """A depth image that is all sky.  The arithmetic is the reference's: DepthUnpackConsts = (-near, +0), so a depth word of +0
+    gives -near / (0 - 0) = -inf and the clamp to [0, 65504] makes it view depth 0 in every mip -- not 65504, which needs the
+    quotient near / 0.  The passes then run on zeros: 0 / 0 = NaN in the edges and the radius, every NaN ends in a saturate, an
+    fmax or uint(), and the bytes are the same everywhere."""
+    W, H = 67, 35
+    k = GR.consts(W, H)
+    r = GR.frame(gt, k, GR.push(3), np.zeros((H, W), F), np.zeros((H, W, 4), np.uint32), 3)
+    assert np.all(r["chain"] == 0)                                                         # +0.0 in all five mips
+    assert np.unique(r["edges"]).tolist() == [0]
+    assert len(np.unique(r["working_after_main"])) == 1 and len(np.unique(r["ssao"])) == 1
+    assert r["working_after_main"][0, 0] == 5 and r["ssao"][0, 0] == 8                     # 0.03 / 1.5 * 255 + 0.5, and that times 1.5
+    near = GR.consts(W, H)
+    near["DepthUnpackConsts"] = (F(-0.1), F(-0.0))                                          # a block whose quotient is near / d: -near / (-0 - d)
+    chain = GR.prefilter(gt, near, np.zeros((H, W), F))
+    assert np.all(GR.chain_mip(chain, W, H, 0) == 0x7BFF)                                  # then mip 0 is 65504 everywhere,
+    assert np.all(GR.chain_mip(chain, W, H, 1) == 0x7C00)                                  # the filter's sum of four overflows binary16: +inf,
+    assert all(np.all(GR.chain_mip(chain, W, H, m) == 0x7E00) for m in range(2, 5))        # and inf - inf is NaN from mip 2 on, stored as 0x7E00
+
+
+# ---- 8. the interface ---------------------------------------------------------------------------------------------------------------------
+def test_interface():
+    from toyrenderer_amd import host, rhi
+    assert (I.GTAOConstants.itemsize, I.XeGTAOMainPassConstantBuffer.itemsize, I.XeGTAODenoiseConstants.itemsize) == (96, 68, 4)
+    assert I.GTAOConstants.fields["NoiseIndex"][1] == 92 and I.GTAOConstants.fields["EffectRadius"][1] == 56
+    new = {"trhost_set_ambient_occlusion", "trhost_download_ssao", "trhost_get_gtao_consts"}
+    assert new <= set(host.HOST_SYMBOLS)
+    header = open(os.path.join(ROOT, "include", "trhost.h")).read()
+    assert all(s + "(" in header for s in new)
+    assert {"ambientocclusion_CS_XeGTAO_PrefilterDepths", "ambientocclusion_CS_XeGTAO_MainPass DEBUG_OUTPUT_MODE=0",
+            "ambientocclusion_CS_XeGTAO_Denoise"} <= set(rhi.shader_names())
+    soft = open(os.path.join(ROOT, "toyrenderer_amd", "csrc", "soft_math.hip.h")).read()
+    ref = open(os.path.join(ROOT, "tests", "gtao_ref.c")).read()
+    for c in ("0x1.45f306p-1f", "0x1.921p+0f", "0x1.f6ap-13f", "0x1.110b46p-26f", "-0x1.55553cp-3f", "0x1.1104a6p-7f", "-0x1.98896ep-13f",
+              "0x1.55554ap-5f", "-0x1.6c0b94p-10f", "0x1.99bcaap-16f"):
+        assert c in soft and c in ref, c                                                  # sinSoft / cosSoft are restated word for word

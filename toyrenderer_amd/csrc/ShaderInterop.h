@@ -182,6 +182,44 @@ struct SkyPassParameters
 static_assert(sizeof(SkyPassParameters) == 256 && offsetof(SkyPassParameters, m_SunLightDir) == 64 && offsetof(SkyPassParameters, m_CameraPosition) == 80 &&
               offsetof(SkyPassParameters, m_HosekParams) == 96, "SkyPassParameters");
 
+// extern/xegtao/XeGTAO.h:59-83: the constant buffer b0 of the three "ambientocclusion_CS_XeGTAO_*" passes, filled by
+// GTAOUpdateConstants (csrc/host/AmbientOcclusionRenderer.cpp, toyrenderer_amd/gtao.py)
+struct GTAOConstants
+{
+    int32_t ViewportSize[2];
+    Vector2 ViewportPixelSize;              // 1 / ViewportSize
+    Vector2 DepthUnpackConsts;
+    Vector2 CameraTanHalfFOV;
+    Vector2 NDCToViewMul;
+    Vector2 NDCToViewAdd;
+    Vector2 NDCToViewMul_x_PixelSize;
+    float EffectRadius;
+    float EffectFalloffRange;
+    float RadiusMultiplier;                 // the four "default constants" are carried but not read: the passes compile them in
+    float Padding0;
+    float FinalValuePower;
+    float DenoiseBlurBeta;
+    float SampleDistributionPower;
+    float ThinOccluderCompensation;
+    float DepthMIPSamplingOffset;
+    int32_t NoiseIndex;
+};
+static_assert(sizeof(GTAOConstants) == 96 && offsetof(GTAOConstants, DepthUnpackConsts) == 16 && offsetof(GTAOConstants, EffectRadius) == 56 &&
+              offsetof(GTAOConstants, FinalValuePower) == 72 && offsetof(GTAOConstants, NoiseIndex) == 92, "GTAOConstants");
+
+// ShaderInterop.h:322-331: the push constants b1 of the main pass and of the denoise pass
+struct XeGTAOMainPassConstantBuffer
+{
+    Matrix m_WorldToViewNoTranslate;
+    uint32_t m_Quality;
+};
+struct XeGTAODenoiseConstants
+{
+    uint32_t m_FinalApply;
+};
+static_assert(sizeof(XeGTAOMainPassConstantBuffer) == 68 && offsetof(XeGTAOMainPassConstantBuffer, m_Quality) == 64, "XeGTAOMainPassConstantBuffer");
+static_assert(sizeof(XeGTAODenoiseConstants) == 4, "XeGTAODenoiseConstants");
+
 // ShaderInterop.h:117-122
 struct DispatchIndirectArguments
 {

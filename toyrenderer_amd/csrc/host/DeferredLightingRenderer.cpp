@@ -3,7 +3,7 @@
 // "deferredlighting_PS_Main" or, under a debug view, "deferredlighting_PS_Main_Debug" (csrc/k_deferredlighting.hip).
 //
 // Out of scope, as in the back end: DDGI (m_bRTDDGIEnabled stays 0, the volume descriptors and probe textures at t5..t8 are not
-// bound), AO generation (t3 stays unbound: 255) and shadow-mask generation (the mask is an input, trhost_upload_shadow_mask;
+// bound) and shadow-mask generation (the mask is an input, trhost_upload_shadow_mask;
 // without one t4 stays unbound: 1.0, the reference's WhiteTexture).  The full-screen triangle with its stencil test on the opaque
 // bit is a direct dispatch of 8x8 groups here; the kernel writes where depth > 0.
 #include "CommonResources.h"
@@ -26,6 +26,7 @@ public:
     DeferredLightingRenderer() : IRenderer("DeferredLightingRenderer") {}
 
     nvrhi::TextureHandle m_LightingOutput;           // kLightingOutputFormat at render resolution, owned here for read-back
+    nvrhi::TextureHandle m_SSAOTexture;              // AmbientOcclusionRenderer's output in this frame, or null: t3 stays unbound (255)
     DeferredLightingConsts m_LastConsts{};           // what the last Render uploaded (trhost_get_deferred_lighting_consts)
     bool m_bHasLastConsts = false;
 
@@ -46,6 +47,8 @@ public:
         renderGraph.AddExternalReadDependency(GetGBufferA().Get());           // :36-39
         renderGraph.AddExternalReadDependency(GetMotionBuffer().Get());
         renderGraph.AddReadDependency(g_DepthStencilBufferRDGTextureHandle);
+        m_SSAOTexture = GetScheduledSSAOTexture();                            // :41-44
+        if (m_SSAOTexture) renderGraph.AddExternalReadDependency(m_SSAOTexture.Get());
         if (g_Scene->m_ShadowMaskTexture) renderGraph.AddExternalReadDependency(g_Scene->m_ShadowMaskTexture.Get());   // :46-49
         renderGraph.AddExternalWriteDependency(m_LightingOutput.Get());
         return true;
@@ -59,7 +62,7 @@ public:
         memcpy(passConstants.m_CameraOrigin, view.m_Eye, sizeof view.m_Eye);
         memcpy(passConstants.m_DirectionalLightVector, g_Scene->m_DirLightVec, sizeof g_Scene->m_DirLightVec);
         passConstants.m_DirectionalLightStrength = g_Scene->m_DirLightStrength;
-        passConstants.m_SSAOEnabled = 0;
+        passConstants.m_SSAOEnabled = m_SSAOTexture ? 1 : 0;               // :69, m_bEnableAO
         passConstants.m_LightingOutputResolution = g_Graphic.m_RenderResolution;
         passConstants.m_DebugMode = g_Scene->m_DebugViewMode;
         passConstants.m_bRTDDGIEnabled = 0;
@@ -80,6 +83,7 @@ public:
             Item::Texture_SRV(2, renderGraph.GetTexture(g_DepthStencilBufferRDGTextureHandle)),
             Item::Texture_UAV(0, m_LightingOutput),
         };
+        if (m_SSAOTexture) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(3, m_SSAOTexture));   // :77
         if (g_Scene->m_ShadowMaskTexture) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(4, g_Scene->m_ShadowMaskTexture));
         p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Graphic.m_RenderResolution, 8);
         g_Graphic.AddComputePass(p);
@@ -101,5 +105,6 @@ void ReleaseDeferredLightingOutputs()
 {
     DeferredLightingRenderer* r = static_cast<DeferredLightingRenderer*>(g_DeferredLightingRenderer);
     r->m_LightingOutput = nullptr;
+    r->m_SSAOTexture = nullptr;
     r->m_bHasLastConsts = false;
 }

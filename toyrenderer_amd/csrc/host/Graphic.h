@@ -163,6 +163,7 @@ namespace ComputeShaderUtils
 {
 constexpr Vector3U GetGroupCount(uint32_t threadCount, uint32_t groupSize) { return Vector3U{ DivideAndRoundUp(threadCount, groupSize), 1, 1 }; }
 constexpr Vector3U GetGroupCount(Vector2U threadCount, uint32_t groupSize) { return Vector3U{ DivideAndRoundUp(threadCount.x, groupSize), DivideAndRoundUp(threadCount.y, groupSize), 1 }; }
+constexpr Vector3U GetGroupCount(Vector2U threadCount, Vector2U groupSize) { return Vector3U{ DivideAndRoundUp(threadCount.x, groupSize.x), DivideAndRoundUp(threadCount.y, groupSize.y), 1 }; }
 } // namespace ComputeShaderUtils
 
 // Graphic.h:227-231 (std::bit_width of the larger dimension)

@@ -16,6 +16,7 @@
 
 extern IRenderer* g_UpdateInstanceConstsRenderer;
 extern IRenderer* g_GBufferRenderer;
+extern IRenderer* g_AmbientOcclusionRenderer;
 extern IRenderer* g_DeferredLightingRenderer;
 extern IRenderer* g_SkyRenderer;
 extern IRenderer* g_BloomRenderer;
@@ -221,6 +222,7 @@ void Scene::Update()
         HOST_PROFILE_SCOPE("RenderGraph::AddRenderer x2 (Setup)");
         m_RenderGraph->AddRenderer(g_UpdateInstanceConstsRenderer);
         m_RenderGraph->AddRenderer(g_GBufferRenderer);
+        if (m_bGBuffer && m_bEnableAO) m_RenderGraph->AddRenderer(g_AmbientOcclusionRenderer);   // :499
         if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
         if (m_bDeferredLighting && m_bEnableSky) m_RenderGraph->AddRenderer(g_SkyRenderer);  // :502
         if (m_bPostProcess && m_bEnableBloom) m_RenderGraph->AddRenderer(g_BloomRenderer);   // :503

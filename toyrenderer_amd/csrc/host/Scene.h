@@ -127,6 +127,12 @@ public:
     float m_SkyTurbidity = 2.0f;
     float m_GroundAlbedo[3] = { 0.1f, 0.1f, 0.1f };
     std::vector<double> m_SkyDataset;                // 3 x 1080 RGB coefficients, then 3 x 120 radiance coefficients; empty: none loaded
+    // Ambient occlusion (trhost_set_ambient_occlusion; needs m_bGBuffer): AmbientOcclusionRenderer runs between GBufferRenderer and
+    // DeferredLightingRenderer, which then binds its SSAO texture at t3 with m_SSAOEnabled = 1.  The settings are members of the
+    // renderer in the reference (AmbientOcclusionRenderer.cpp:22, :36-37; XeGTAO::GTAOSettings' defaults below).
+    bool m_bEnableAO = false;
+    uint32_t m_AOQuality = 3, m_AODenoisePasses = 3;
+    float m_AORadius = 0.5f, m_AOFalloffRange = 0.615f, m_AOFinalValuePower = 2.2f, m_AODepthMIPSamplingOffset = 3.3f;
     nvrhi::BufferHandle m_LuminanceBuffer;           // Scene.h: one float, the adapted luminance; survives across frames
     nvrhi::TextureHandle m_ExposureTexture;          // 1 x 1 R32_FLOAT
     // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.

@@ -60,6 +60,12 @@ void ReleasePostProcessOutputs();
 nvrhi::TextureHandle GetGeneratedBloomTexture();
 bool GetLastBloomConsts(uint32_t pass, void* out16);
 void ReleaseBloomOutputs();
+// AmbientOcclusionRenderer: the SSAO texture of the last frame (null if the pass did not run in it), the one the frame being set
+// up will write (null if the pass is not scheduled in it), and the GTAOConstants the last frame uploaded.
+nvrhi::TextureHandle GetSSAOTexture();
+nvrhi::TextureHandle GetScheduledSSAOTexture();
+bool GetLastGTAOConsts(void* out96);
+void ReleaseAmbientOcclusionOutputs();
 // The SkyPassParameters SkyRenderer uploaded in the last frame; false if the pass did not run in it.
 bool GetLastSkyConsts(void* out256);
 void ReleaseSkyOutputs();

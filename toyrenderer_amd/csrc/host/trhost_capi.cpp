@@ -63,6 +63,7 @@ void trhost_shutdown(void)
         ReleasePostProcessOutputs();
         ReleaseBloomOutputs();
         ReleaseSkyOutputs();
+        ReleaseAmbientOcclusionOutputs();
         g_Graphic.Shutdown();
     });
     s_Initialized = false;
@@ -340,6 +341,46 @@ int trhost_get_sky_consts(void* out256)
     return guarded([&] {
         check(out256);
         if (!GetLastSkyConsts(out256)) throw nvrhi::Error("trhost_get_sky_consts: the sky pass did not run in the last frame");
+    });
+}
+
+int trhost_set_ambient_occlusion(int enable, uint32_t quality, uint32_t denoise_passes, float radius, float falloff_range, float final_value_power,
+                                 float depth_mip_sampling_offset)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!enable) { g_Scene->m_bEnableAO = false; return; }
+        if (!g_Scene->m_bGBuffer) throw nvrhi::Error("trhost_set_ambient_occlusion: the G-buffer is off (trhost_set_gbuffer or trhost_set_deferred_lighting first): the main pass reads GBufferA");
+        if (quality > 3) throw nvrhi::Error("trhost_set_ambient_occlusion: the quality level must be 0..3");
+        if (denoise_passes > 3) throw nvrhi::Error("trhost_set_ambient_occlusion: the denoise passes must be 0..3");
+        if (!(std::isfinite(radius) && radius >= 0.0f)) throw nvrhi::Error("trhost_set_ambient_occlusion: the radius must be finite and >= 0");
+        if (!std::isfinite(falloff_range) || !std::isfinite(final_value_power) || !std::isfinite(depth_mip_sampling_offset))
+            throw nvrhi::Error("trhost_set_ambient_occlusion: falloff range, final value power and depth mip sampling offset must be finite");
+        g_Scene->m_bEnableAO = true;
+        g_Scene->m_AOQuality = quality;
+        g_Scene->m_AODenoisePasses = denoise_passes;
+        g_Scene->m_AORadius = radius;
+        g_Scene->m_AOFalloffRange = falloff_range;
+        g_Scene->m_AOFinalValuePower = final_value_power;
+        g_Scene->m_AODepthMIPSamplingOffset = depth_mip_sampling_offset;
+    });
+}
+
+int trhost_download_ssao(uint8_t* bytes, uint64_t size)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetSSAOTexture();
+        if (!t) throw nvrhi::Error("trhost_download_ssao: the ambient occlusion pass did not run in the last frame");
+        check(bytes);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, bytes, size), "trhost_download_ssao");
+    });
+}
+
+int trhost_get_gtao_consts(void* out96)
+{
+    return guarded([&] {
+        check(out96);
+        if (!GetLastGTAOConsts(out96)) throw nvrhi::Error("trhost_get_gtao_consts: the ambient occlusion pass did not run in the last frame");
     });
 }
 

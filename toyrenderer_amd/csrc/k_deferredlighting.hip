@@ -2,7 +2,8 @@
 // after GBufferRenderer (source/DeferredLightingRenderer.cpp, source/shaders/deferredlighting.hlsl; EvaluateDirectionalLight,
 // DefaultLitBxDF and UnpackGBuffer of lightingcommon.hlsli), WITHOUT DDGI and with the shadow mask as an input: the directional
 // light and the debug views, closed arithmetic on GBufferA, depth, the motion target, the SSAO and the shadow-mask texels.
-// DDGI ambient, AO generation and shadow-mask generation are out of scope; the sky is k_sky.hip's.
+// DDGI ambient and shadow-mask generation are out of scope; the sky is k_sky.hip's, the SSAO texture
+// k_ambientocclusion.hip's.
 //
 // WHICH PIXELS: the reference draws where the stencil equals the opaque bit.  The stand-in: a pixel is written iff its depth
 // word is > 0.0f (NaN, +-0 and negative depths are skipped); every other texel of u0 keeps what it held.

@@ -24,6 +24,12 @@
 //             0.289, and P read at z rather than RN(s)^2, 2^-23 relative: 0.054; t within 0.963, r within 1.93.  The last
 //             subtraction rounds by <= 2^-23 (results in [2, pi]): 2; RN(pi / 2) is off by 0.733 and RN(pi) by 1.467.  So
 //             |x| <= 0.5: 3.36; x > 0.5: 1.93; x < -0.5: 5.4.  BOUND 5.5 * 2^-24 (3.28e-7); measured maximum in DESIGN.md 9.
+//   sinSoft(x), cosSoft(x), |x| <= 10 (the ambient occlusion pass, k_ambientocclusion.hip, forms |x| <= 3 pi; tests/gtao_ref.c restates
+//             them word for word as gt_sin / gt_cos next to the derivation of the coefficients): !(|x| <= 10) (larger, infinite,
+//             NaN) gives NaN.  k = rint(x * RN(2 / pi)); r = x - k * pi / 2 by three fma against 0x1.921p+0 + 0x1.f6ap-13 +
+//             0x1.110b46p-26 (the first two with 11 low zero bits: their products with k are exact); z = r * r; on |r| < 0.8
+//               sin r = fma(r * z, S(z), r), cos r = fma(z * z, C(z), fma(-0.5, z, 1)), S and C degree 2 in fma;
+//             the quadrant (k, + 1 for the cosine) & 3 picks S, C, -S, -C.  BOUND 3 * 2^-24 absolute.
 #pragma once
 
 #include "cull_math.hip.h"
@@ -95,5 +101,32 @@ __device__ __forceinline__ float acosSoft(float x)
     const float r = 2.0f * cm::fma_(s * z, acosPoly(z), s);
     return x > 0.0f ? r : 0x1.921fb6p+1f - r;
 }
+
+// quarter 0: sine, 1: cosine = sin(x + pi / 2)
+__device__ __forceinline__ float sinCosSoft(float x, int quarter)
+{
+    if (!(__builtin_fabsf(x) <= 10.0f)) return __builtin_nanf("");
+    const float k = __builtin_rintf(x * 0x1.45f306p-1f);
+    float r = cm::fma_(-k, 0x1.921p+0f, x);
+    r = cm::fma_(-k, 0x1.f6ap-13f, r);
+    r = cm::fma_(-k, 0x1.110b46p-26f, r);
+    const float z = r * r;
+    const int q = ((int)k + quarter) & 3;
+    float v;
+    if (q & 1) {
+        float p = 0x1.99bcaap-16f;
+        p = cm::fma_(p, z, -0x1.6c0b94p-10f);
+        p = cm::fma_(p, z, 0x1.55554ap-5f);
+        v = cm::fma_(z * z, p, cm::fma_(-0.5f, z, 1.0f));
+    } else {
+        float p = -0x1.98896ep-13f;
+        p = cm::fma_(p, z, 0x1.1104a6p-7f);
+        p = cm::fma_(p, z, -0x1.55553cp-3f);
+        v = cm::fma_(r * z, p, r);
+    }
+    return (q & 2) ? -v : v;
+}
+__device__ __forceinline__ float sinSoft(float x) { return sinCosSoft(x, 0); }
+__device__ __forceinline__ float cosSoft(float x) { return sinCosSoft(x, 1); }
 
 } // namespace softmath

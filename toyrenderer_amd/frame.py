@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import gtao as gtaomod
 from . import interop as I
 from . import rhi
 from . import sky as skymod
@@ -84,7 +85,7 @@ class FrameDriver:
                  shard_late=None, raster_depth: bool = False, visibility: bool = False, gbuffer: bool = False,
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
-                 bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None):
+                 bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -123,7 +124,20 @@ class FrameDriver:
         (SkyRenderer.cpp).  One "sky_PS_HosekWilkieSky" dispatch directly behind the lighting dispatch, in front of bloom and the
         histogram clear, whatever debug_mode is, fills every texel of LightingOutput whose depth is <= 0.  The sun direction is
         dir_light[0] as given, the camera position camera_origin, the matrix the lighting pass's m_ClipToWorld.
-        self.sky_consts holds the 256-byte SkyPassParameters of the last record()."""
+        self.sky_consts holds the 256-byte SkyPassParameters of the last record().
+        ao: None (the default) changes nothing.  A dict of settings, any of quality (0..3: Low, Medium, High, Ultra), denoise_passes
+        (0..3), radius, falloff_range, final_value_power, depth_mip_sampling_offset (the reference's defaults: 3, 3, 0.5, 0.615, 2.2,
+        3.3; needs gbuffer=True, which lighting implies; not together with an external ssao=): AmbientOcclusionRenderer
+        (AmbientOcclusionRenderer.cpp, XeGTAO).  The driver owns the working depth chain (R16_FLOAT, 5 mips), the working AO term
+        (R8_UINT), the edges (R8_UNORM) and self.ssao_texture (R8_UINT); after the G-buffer resolve and in front of the lighting
+        dispatch it records "ambientocclusion_CS_XeGTAO_PrefilterDepths", "ambientocclusion_CS_XeGTAO_MainPass DEBUG_OUTPUT_MODE=0"
+        and max(1, denoise_passes) "ambientocclusion_CS_XeGTAO_Denoise" dispatches ping-ponging between the working term and
+        self.ssao_texture, the last with m_FinalApply = 1; as in the reference, with 2 passes the finally-applied image lands in
+        the working term and self.ssao_texture holds the first pass's output.  With lighting the texture is the lighting pass's
+        t3 and m_SSAOEnabled is 1; only debug view 9 shows it (the non-debug pass multiplies the DDGI ambient term by it, and that
+        term is not built), so LightingOutput without a debug view does not change.  self.frame_counter (0; the caller may set it
+        before record()) feeds NoiseIndex as g_Graphic.m_FrameCounter % 256 does; self.gtao_consts holds the 96-byte GTAOConstants
+        of the last record(); download_ssao() reads self.ssao_texture back."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -167,6 +181,14 @@ class FrameDriver:
             albedo = sky[2] if len(sky) > 2 else skymod.DEFAULT_GROUND_ALBEDO
             skymod.check_settings(turbidity, albedo)
             self.sky = (sky[0], np.float32(turbidity), tuple(np.float32(x) for x in albedo))
+        self.ao = self.gtao_consts = None
+        self.frame_counter = 0
+        if ao is not None:
+            if not gbuffer:
+                raise ValueError("ao=... needs gbuffer=True (or lighting=True): the main pass reads the normals of GBufferA")
+            if ssao is not None:
+                raise ValueError("ao=... together with an external ssao= texture: the driver generates the texture itself")
+            self.ao = gtaomod.check_settings(ao)
         self.dir_light = (tuple(float(x) for x in dir_light[0]), float(dir_light[1]))
         self.camera_origin = tuple(float(x) for x in camera_origin)
         self.shadow_mask, self.ssao = shadow_mask, ssao
@@ -203,6 +225,13 @@ class FrameDriver:
         if self.bloom_mips:                          # BloomRenderer::Setup (BloomRenderer.cpp:41-50)
             self.bloom_texture = dev.create_texture(view.renderW, view.renderH, self.bloom_mips, rhi.FORMAT_R11G11B10_FLOAT, "Bloom Texture",
                                                     render_target=True)
+        self.ao_depth = self.ao_working = self.ao_edges = self.ssao_texture = None
+        if self.ao is not None:                      # AmbientOcclusionRenderer::Setup (AmbientOcclusionRenderer.cpp:85-127)
+            self.ao_depth = dev.create_texture(view.renderW, view.renderH, gtaomod.DEPTH_MIP_LEVELS, rhi.FORMAT_R16_FLOAT, "XeGTAO Working Depth Buffer")
+            self.ssao_texture = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R8_UINT, "SSAO Buffer")
+            self.ao_working = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R8_UINT, "Working SSAO Texture")
+            self.ao_edges = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R8_UNORM, "Working Edges Texture")
+            self.ssao = self.ssao_texture            # what the lighting pass binds as t3
         if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
@@ -373,6 +402,32 @@ class FrameDriver:
             b.append(TEX_SRV(4, self.shadow_mask))
         cl.dispatch("deferredlighting_PS_Main_Debug" if self.debug_mode != 0 else "deferredlighting_PS_Main", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
 
+    # ---- AmbientOcclusionRenderer::Render (AmbientOcclusionRenderer.cpp:129-248) ------------------------------------------
+    def _ambient_occlusion(self, cl):
+        v, W, H = self.view, self.view.renderW, self.view.renderH
+        self.gtao_consts = gtaomod.update_constants(W, H, self.ao, v.viewToClip, int(self.frame_counter) % 256)
+        cb = cl.constant_buffer(self.gtao_consts, "GTAOConstants")
+        cl.dispatch("ambientocclusion_CS_XeGTAO_PrefilterDepths",
+                    [CB(0, cb), TEX_SRV(0, self.depth), *[TEX_UAV(m, self.ao_depth, m) for m in range(gtaomod.DEPTH_MIP_LEVELS)], SAMPLER(0)],
+                    ((W + 15) // 16, (H + 15) // 16, 1))
+        cl.dispatch("ambientocclusion_CS_XeGTAO_MainPass DEBUG_OUTPUT_MODE=0",
+                    [CB(0, cb), PUSH(1), TEX_SRV(0, self.ao_depth), TEX_SRV(2, self.gbufferA), TEX_UAV(0, self.ao_working, 0), TEX_UAV(1, self.ao_edges, 0), SAMPLER(0)],
+                    ((W + 7) // 8, (H + 7) // 8, 1), push=gtaomod.main_pass_constants(v.worldToView, self.ao["quality"]))
+        ping_pong = [self.ao_working, self.ssao_texture]
+        passes = max(1, self.ao["denoise_passes"])   # without denoising one last pass still writes the term into the output texture
+        for i in range(passes):
+            cl.dispatch("ambientocclusion_CS_XeGTAO_Denoise",
+                        [CB(0, cb), PUSH(1), TEX_SRV(0, ping_pong[0]), TEX_SRV(1, self.ao_edges), TEX_UAV(0, ping_pong[1], 0), SAMPLER(0)],
+                        ((W + 15) // 16, (H + 7) // 8, 1), push=gtaomod.denoise_constants(i == passes - 1))
+            ping_pong.reverse()
+
+    def download_ssao(self) -> np.ndarray:
+        """The bytes of the generated SSAO texture, (H, W) uint8."""
+        if self.ssao_texture is None:
+            raise ValueError("download_ssao: AO generation is off (ao=None)")
+        self.dev.wait_idle()
+        return self.ssao_texture.download_mip(0)
+
     # ---- SkyRenderer::Render (SkyRenderer.cpp:163-208) -------------------------------------------------------------------
     def _sky(self, cl):
         v = self.view
@@ -510,7 +565,9 @@ class FrameDriver:
                 self._resolve_motion(cl)
         if query is not None:
             cl.end_pipeline_stats(query)
-        if self.lighting_on:                                                             # the next renderer after GBufferRenderer
+        if self.ao is not None:                                                          # Scene.cpp's order: behind GBufferRenderer, in front of lighting
+            self._ambient_occlusion(cl)
+        if self.lighting_on:
             self._deferred_lighting(cl)
         if self.sky is not None:                                                         # Scene.cpp:502: between lighting and bloom
             self._sky(cl)
@@ -553,6 +610,6 @@ class FrameDriver:
             b.release()
         self.hzb.release(); self.depth.release()
         for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
-                  self.bloom_texture):
+                  self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture):
             if t is not None:
                 t.release()

@@ -34,6 +34,7 @@ HOST_SYMBOLS = [
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
     "trhost_load_sky_dataset", "trhost_set_sky", "trhost_get_sky_consts",
+    "trhost_set_ambient_occlusion", "trhost_download_ssao", "trhost_get_gtao_consts",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # trhost_allgather_fn
@@ -112,6 +113,9 @@ def load() -> C.CDLL:
     L.trhost_load_sky_dataset.argtypes = [vp, vp]
     L.trhost_set_sky.argtypes = [C.c_int, C.c_float, vp]
     L.trhost_get_sky_consts.argtypes = [vp]
+    L.trhost_set_ambient_occlusion.argtypes = [C.c_int, u32, u32, C.c_float, C.c_float, C.c_float, C.c_float]
+    L.trhost_download_ssao.argtypes = [vp, u64]
+    L.trhost_get_gtao_consts.argtypes = [vp]
     L.trhost_get_scene_luminance.argtypes = [vp, vp]
     L.trhost_reset_exposure.argtypes = []
     L.trhost_get_post_process_consts.argtypes = [vp, vp, vp, vp]
@@ -370,6 +374,25 @@ class Renderer:
         """The SkyPassParameters of the last frame; raises if the pass did not run in it."""
         k = np.zeros(1, I.SkyPassParameters)
         _check(load().trhost_get_sky_consts(k.ctypes.data))
+        return k
+
+    def set_ambient_occlusion(self, enable: bool, quality: int = 3, denoise_passes: int = 3, radius: float = 0.5, falloff_range: float = 0.615,
+                              final_value_power: float = 2.2, depth_mip_sampling_offset: float = 3.3):
+        """AmbientOcclusionRenderer on or off (needs set_gbuffer(True) or set_deferred_lighting(True)); the defaults are the reference's."""
+        _check(load().trhost_set_ambient_occlusion(int(bool(enable)), int(quality), int(denoise_passes), float(radius), float(falloff_range),
+                                                   float(final_value_power), float(depth_mip_sampling_offset)))
+
+    def download_ssao(self) -> np.ndarray:
+        """The last frame's SSAO texture: uint8 [H, W]; raises if the pass did not run in it."""
+        self.wait_idle()
+        b = np.empty((self.render[1], self.render[0]), np.uint8)
+        _check(load().trhost_download_ssao(b.ctypes.data, b.nbytes))
+        return b
+
+    def gtao_consts(self) -> np.ndarray:
+        """The GTAOConstants of the last frame; raises if the pass did not run in it."""
+        k = np.zeros(1, I.GTAOConstants)
+        _check(load().trhost_get_gtao_consts(k.ctypes.data))
         return k
 
     def bloom_consts(self, passes: int) -> np.ndarray:

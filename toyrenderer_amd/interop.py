@@ -87,6 +87,15 @@ HosekWilkieSkyParameters = np.dtype([("m_Params", np.float32, (10, 4))])        
 SkyPassParameters = np.dtype([                                                                                             # ShaderInterop.h:297-305
     ("m_ClipToWorld", np.float32, (4, 4)), ("m_SunLightDir", np.float32, (3,)), ("PAD0", np.uint32), ("m_CameraPosition", np.float32, (3,)),
     ("PAD1", np.uint32), ("m_HosekParams", HosekWilkieSkyParameters)])
+GTAOConstants = np.dtype([                                                                                                 # extern/xegtao/XeGTAO.h:59-83
+    ("ViewportSize", np.int32, (2,)), ("ViewportPixelSize", np.float32, (2,)), ("DepthUnpackConsts", np.float32, (2,)),
+    ("CameraTanHalfFOV", np.float32, (2,)), ("NDCToViewMul", np.float32, (2,)), ("NDCToViewAdd", np.float32, (2,)),
+    ("NDCToViewMul_x_PixelSize", np.float32, (2,)), ("EffectRadius", np.float32), ("EffectFalloffRange", np.float32),
+    ("RadiusMultiplier", np.float32), ("Padding0", np.float32), ("FinalValuePower", np.float32), ("DenoiseBlurBeta", np.float32),
+    ("SampleDistributionPower", np.float32), ("ThinOccluderCompensation", np.float32), ("DepthMIPSamplingOffset", np.float32),
+    ("NoiseIndex", np.int32)])
+XeGTAOMainPassConstantBuffer = np.dtype([("m_WorldToViewNoTranslate", np.float32, (4, 4)), ("m_Quality", np.uint32)])          # ShaderInterop.h:322-326
+XeGTAODenoiseConstants = np.dtype([("m_FinalApply", np.uint32)])                                                             # ShaderInterop.h:328-331
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
@@ -95,6 +104,7 @@ SIZES = {
     "TextureData": 20, "MaterialData": 124, "DeferredLightingConsts": 112,
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
     "BloomConsts": 16, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
+    "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)
