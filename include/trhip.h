@@ -118,6 +118,9 @@ uint32_t    trhip_abi_version(void);
  * edges, u0 the output (R8_UINT, another texture than t0).  Samplers are accepted and ignored.  Refused at record time: a missing
  * binding, another format or size, a depth chain without 5 mips or u<k> not its mip k, a constant block of another size, groups
  * that do not cover the target, an indirect dispatch.  The arithmetic convention is tests/gtao_ref.c's (csrc/k_ambientocclusion.hip).
+ * "raytracing_CS_RefitTLAS" (the back end's own name; stands in for buildTopLevelAccelStructFromBuffer, BasePassRenderers.cpp:159-160)
+ * and "shadowmask_CS_ShadowMask" (shadowmask.hlsl, ShadowMaskRenderer::TraceShadows without denoising): see "acceleration
+ * structure" below for the buffers and the bindings.  The arithmetic convention is tests/shadowmask_ref.c's (csrc/k_shadowmask.hip).
  * "bloom_PS_Downsample" and "bloom_PS_Upsample" (bloom.hlsl, BloomRenderer.cpp; the stand-ins of the full-screen passes of
  * Graphic.cpp:832-860): a direct dispatch of [numthreads(8, 8, 1)] groups covering the destination mip; b0 or push constants
  * BloomConsts (16 bytes: the downsample reads m_InvSourceResolution and m_bIsFirstDownsample, the upsample m_FilterRadius), t0
@@ -300,6 +303,49 @@ int  trhip_cmd_end_pipeline_stats(trhip_cmdlist cl, trhip_pipeline_stats q);    
 /* getPipelineStatistics: waits for the end of the last executed end; TRHIP_ERR_STATE if the query was never ended in an
  * executed list. */
 int  trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics* out);
+
+/* ---- acceleration structure: nvrhi::rt::AccelStruct (Visual.cpp:509-542 Mesh::BuildBLAS, Scene.cpp:430-470 the TLAS) ----------
+ * DXR's structure is opaque; this one is the project's own and lives in ordinary structured buffers that the caller creates,
+ * fills from the two host-side builders below (no device needed) and binds.  DESIGN.md 13 has the reasoning.
+ *
+ * NODES (trhip_accel_node, 32 bytes), both levels: a binary tree in depth-first preorder.  Node i's first child is i + 1, its
+ * second child is nodes[i + 1].skip, nodes[i].skip is the first node behind i's subtree (the node count for the last), so a
+ * walk needs no stack: box hit on an inner node -> i + 1, else -> skip.  leaf = 0xFFFFFFFF: inner.  BLAS leaf: first | (count - 1)
+ * << 30, `count` (1..4) entries of the mesh's triangle order from `first`.  TLAS leaf: the instance index (one instance per leaf).
+ * Depth <= trhip_accel_max_depth() = 56 for every input (median split where the midpoint split degenerates).
+ * BLAS, per mesh, object space, built once: trhip_blas_build over the mesh's LOD-0 index list (indices relative to the mesh's first
+ * vertex, as m_GlobalIndexBufferIdx addresses them).  tri_order receives the triangle ids (index / 3) in leaf order; a triangle
+ * with a non-finite vertex is in no leaf and is never hit.  Every box is moved outward by 2^-16 times the mesh's largest
+ * |coordinate|.  All meshes' nodes and orders are concatenated; trhip_blas_header (16 bytes) per mesh says where: node_offset
+ * (skip and child indices are relative to it), num_nodes (0: nothing to hit), tri_offset, num_tris.  Same input, same bytes.
+ * TLAS, per scene: trhip_tlas_build makes the topology from the instances' rest transforms (m_WorldMatrix of the 144-byte
+ * records) and flags[i] (0: not in the structure, 1: ForceOpaque, 2: ForceNonOpaque; Scene.cpp:454), fills one trhip_tlas_instance
+ * (64 bytes) per instance (flags, leaf_node or 0xFFFFFFFF, the matrix zero) and lists the inner nodes by height: level_nodes
+ * [level_offsets[h - 1], level_offsets[h]) are the nodes of height h = 1..num_levels (level_offsets: trhip_accel_max_depth() + 2
+ * words; level_nodes: as many words as nodes).
+ * "raytracing_CS_RefitTLAS", recorded every frame behind "updateinstanceconsts_*": a direct dispatch of 64-thread groups covering
+ * m_NumInstances; push constants { m_NumInstances, m_NumNodes, m_NumLevels } (12 bytes); t0 instances, t1 BLAS headers, t2 BLAS
+ * nodes, t3 level_offsets, t4 level_nodes, u0 the TLAS nodes, u1 the TLAS instances.  Per instance in the structure it writes the
+ * object-from-world 3x4 (rows of p_object = (p_world, 1) * M) and the leaf's box: the BLAS root box's 8 corners through
+ * m_WorldMatrix, moved outward by 2^-12 times the largest |coordinate|; then every inner box, height by height.
+ * "shadowmask_CS_ShadowMask": a direct dispatch of [numthreads(8, 8, 1)] groups covering m_OutputResolution; b0 ShadowMaskConsts
+ * (112 bytes, a constant buffer; m_bDoDenoising must be 0), t0 (texture) R32_FLOAT depth, t1 the TLAS nodes, t2 (texture) GBufferA,
+ * t3 instances, t4 vertices, t5 materials, t6 indices, t7 mesh data, t8 (texture) RGBA8_UNORM 128 x 128 blue noise, u0 (texture)
+ * R8_UNORM mask, u1 (texture) R16_FLOAT linear view depth, and the structure's other buffers: t9 TLAS instances, t10 BLAS
+ * headers, t11 BLAS nodes, t12 triangle order.  Samplers are accepted and ignored.  A texel of depth 0.0f gets u1 = 65504 and
+ * keeps u0; any other gets u0 = 0 (occluded) or 255 and u1 = fp16(|worldPosition - m_CameraPosition|).  An index read on the
+ * device that leaves its buffer ends that instance's (or triangle's) test; it is never followed. */
+typedef struct { float lo[3]; uint32_t skip; float hi[3]; uint32_t leaf; } trhip_accel_node;
+typedef struct { uint32_t node_offset, num_nodes, tri_offset, num_tris; } trhip_blas_header;
+typedef struct { float object_from_world[12]; uint32_t flags, leaf_node, reserved[2]; } trhip_tlas_instance;
+uint32_t trhip_accel_max_depth(void);
+uint32_t trhip_blas_leaf_capacity(void);
+uint32_t trhip_accel_max_nodes(uint32_t num_primitives);     /* 2 n - 1: the node capacity a build of n primitives needs */
+int  trhip_blas_build(const void* vertices, uint32_t vertex_stride, uint32_t num_vertices, const uint32_t* indices, uint32_t num_indices,
+                      trhip_accel_node* nodes, uint32_t node_capacity, uint32_t* tri_order, uint32_t* num_nodes, uint32_t* num_tris, uint32_t* depth);
+int  trhip_tlas_build(const void* instances, uint32_t num_instances, const uint32_t* flags, const trhip_blas_header* headers, uint32_t num_meshes,
+                      const trhip_accel_node* blas_nodes, uint32_t num_blas_nodes, trhip_accel_node* nodes, uint32_t node_capacity,
+                      trhip_tlas_instance* records, uint32_t* level_nodes, uint32_t* level_offsets, uint32_t* num_nodes, uint32_t* num_levels);
 
 /* ---- per-shader GPU profile: PROFILE_GPU_SCOPED in AddComputePass (Graphic.cpp:899) ----------
  * When enabled, every dispatch executed is bracketed by HIP events on the device stream and

@@ -136,7 +136,18 @@ int  trhost_get_deferred_lighting_consts(void* out112);
  * m_SSAOEnabled = 1 (only debug view 9 shows it).  Refused: the G-buffer off; quality or passes above 3; a radius that is negative
  * or not finite; another setting that is not finite.  trhost_set_ambient_occlusion(0, ...) switches it off.  trhost_download_ssao
  * waits and copies the W x H bytes of the SSAO texture; trhost_get_gtao_consts copies the 96 bytes of GTAOConstants of the last
- * frame; both refuse if the pass did not run in it. */
+ * frame; both refuse if the pass did not run in it.
+ * Ray-traced sun shadows (ShadowMaskRenderer.cpp TraceShadows without denoising; off by default).  trhost_load_raytracing(indices,
+ * numIndices, indexCounts, numMeshes), after the scene, its geometry and its materials: the global index buffer (each mesh's LOD-0
+ * list at m_GlobalIndexBufferIdx, relative to its first vertex) and one index count per mesh (MeshSpecificData); it builds every
+ * mesh's BLAS and the TLAS topology from the instance buffer's current matrices (include/trhip.h, "acceleration structure").
+ * trhost_upload_blue_noise: the 128 x 128 RGBA8 image (65536 bytes), an input.  trhost_set_shadow_mask(1, soft, sunAngularDiameter,
+ * rayStartOffset) schedules ShadowMaskRenderer between AmbientOcclusionRenderer and DeferredLightingRenderer (the reference's
+ * defaults: 1, 0.533 degrees, 0.01 below a scene radius of 3 and 0.1 above): the TLAS refit and the trace into the shadow mask,
+ * which the lighting pass then binds at t4.  Refused: the G-buffer off; no structure; no noise; an uploaded shadow mask; a diameter
+ * outside [0, 180) or an offset that is negative or not finite.  trhost_set_shadow_mask(0, ...) switches it off.
+ * trhost_download_shadow_mask waits and copies the W x H bytes of the mask; trhost_get_shadow_mask_consts copies the 112 bytes of
+ * ShadowMaskConsts of the last frame; both refuse if the pass did not run in it. */
 int  trhost_set_post_process(int enable);
 int  trhost_set_exposure(float manual, float middle_gray);
 int  trhost_set_auto_exposure(float min_lum, float max_lum, float speed_per_ms);
@@ -152,6 +163,11 @@ int  trhost_set_ambient_occlusion(int enable, uint32_t quality, uint32_t denoise
                                   float depth_mip_sampling_offset);
 int  trhost_download_ssao(uint8_t* bytes, uint64_t size);
 int  trhost_get_gtao_consts(void* out96);
+int  trhost_load_raytracing(const uint32_t* indices, uint64_t num_indices, const uint32_t* index_counts, uint32_t num_meshes);
+int  trhost_upload_blue_noise(const uint8_t* rgba, uint64_t bytes);
+int  trhost_set_shadow_mask(int enable, int soft, float sun_angular_diameter, float ray_start_offset);
+int  trhost_download_shadow_mask(uint8_t* bytes, uint64_t size);
+int  trhost_get_shadow_mask_consts(void* out112);
 int  trhost_download_back_buffer(uint32_t* words, uint64_t bytes);
 int  trhost_get_scene_luminance(float* luminance, float* exposure);
 int  trhost_reset_exposure(void);

@@ -1,0 +1,263 @@
+"""Seeded scenes, cameras and images for the shadow mask tests (tests/test_shadowmask_ref.py on the CPU, tests/test_gpu_shadowmask.py
+on the GPU): a few hundred triangles at most, so that brute force over every texel takes milliseconds.
+
+A scene is a dict: vertices (RawVertexFormat), indices (uint32, per mesh relative to its first vertex), meshData (m_GlobalVertexBufferIdx
+and m_GlobalIndexBufferIdx set), index_counts (uint32 per mesh), instances (BasePassInstanceConstants), opaqueIds, alphaMaskIds,
+materials (MaterialData).  CASES lists what both test files run."""
+import os
+
+import numpy as np
+
+from toyrenderer_amd import accel, synth
+from toyrenderer_amd import interop as I
+
+F = np.float32
+HERE = os.path.dirname(os.path.abspath(__file__))
+L = 4                                               # the BLAS leaf capacity (asserted against the builder by the CPU tests)
+
+
+# ---- meshes: (positions float32 [n, 3], indices uint32 [3 t]) ------------------------------------------------------------------------
+def strip(n_tris, seed=0, size=1.0):
+    """n_tris triangles of a jittered ribbon in the plane y = 0, about `size` wide."""
+    rng = np.random.default_rng([seed, n_tris])
+    n = n_tris + 2
+    x = np.linspace(-size, size, (n + 1) // 2)
+    p = np.zeros((n, 3), F)
+    p[0::2, 0], p[1::2, 0] = x[:len(p[0::2])], x[:len(p[1::2])]
+    p[0::2, 2], p[1::2, 2] = -0.5 * size, 0.5 * size
+    p[:, 1] = rng.uniform(-0.05, 0.05, n) * size
+    idx = np.array([(i, i + 1, i + 2) if i % 2 == 0 else (i + 1, i, i + 2) for i in range(n_tris)], np.uint32)
+    return p, idx.reshape(-1)
+
+
+def blob(n_tris, seed):
+    """n_tris random triangles of edge about 0.4 in the unit cube around the origin."""
+    rng = np.random.default_rng([seed, 77])
+    c = rng.uniform(-1.0, 1.0, (n_tris, 1, 3))
+    p = (c + rng.uniform(-0.2, 0.2, (n_tris, 3, 3))).astype(F).reshape(-1, 3)
+    return p, np.arange(3 * n_tris, dtype=np.uint32)
+
+
+def with_degenerates(seed=3):
+    """A blob of 24 triangles with zero-area ones among them: a repeated vertex, three collinear points, three equal points; and a
+    triangle with a NaN and one with an infinite vertex (never hit; left out of the tree)."""
+    p, idx = blob(24, seed)
+    p = p.copy()
+    p[3 * 2 + 1] = p[3 * 2]                                          # repeated vertex
+    p[3 * 5 + 2] = p[3 * 5] + (p[3 * 5 + 1] - p[3 * 5]) * F(0.5)     # collinear
+    p[3 * 9 + 1] = p[3 * 9 + 2] = p[3 * 9]                           # a point
+    p[3 * 13, 1] = np.nan
+    p[3 * 17 + 2, 0] = np.inf
+    return p, idx
+
+
+def tetrahedron():
+    p = np.array([(1, 1, 1), (1, -1, -1), (-1, 1, -1), (-1, -1, 1)], F) * F(0.5)
+    return p, np.array([0, 1, 2, 0, 3, 1, 0, 2, 3, 1, 3, 2], np.uint32)
+
+
+def quad(half=1.0):
+    p = np.array([(-half, 0, -half), (half, 0, -half), (half, 0, half), (-half, 0, half)], F)
+    return p, np.array([0, 1, 2, 0, 2, 3], np.uint32)
+
+
+def collinear_growing(n=4096):
+    """The hostile mesh of the depth bound: n zero-area triangles on one line whose size grows geometrically, so that a midpoint split
+    peels off one triangle per level."""
+    x = np.cumsum(np.geomspace(1e-6, 1e3, n + 2)).astype(F)
+    p = np.zeros((n + 2, 3), F)
+    p[:, 0] = x
+    idx = np.stack([np.arange(n), np.arange(n) + 1, np.arange(n) + 2], 1).astype(np.uint32)
+    return p, idx.reshape(-1)
+
+
+# ---- scenes ------------------------------------------------------------------------------------------------------------------------------
+def rotation(axis, angle):
+    a = np.asarray(axis, np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+
+
+def world_matrix(scale=(1, 1, 1), axis=(0, 1, 0), angle=0.0, position=(0, 0, 0)):
+    """Row vectors: scale, then rotate, then translate (a negative scale mirrors)."""
+    W = np.eye(4)
+    W[:3, :3] = np.diag(np.asarray(scale, np.float64)) @ rotation(axis, angle)
+    W[3, :3] = position
+    return W.astype(F)
+
+
+def materials(n=4):
+    m = synth.materials(5, n)
+    m["m_ConstAlbedo"][:, 3] = 1.0
+    m["m_AlphaCutoff"] = 0.5
+    return m
+
+
+def make_scene(meshes, placements, mats=None):
+    """meshes: [(positions, indices)]; placements: [(mesh index, world matrix, material index, "opaque" | "alpha" | None)]."""
+    v = np.zeros(sum(len(p) for p, _ in meshes), I.RawVertexFormat)
+    md = np.zeros(len(meshes), I.MeshData)
+    counts = np.zeros(len(meshes), np.uint32)
+    idx, vat, iat = [], 0, 0
+    for m, (p, i) in enumerate(meshes):
+        v["m_Position"][vat:vat + len(p)] = p
+        md["m_GlobalVertexBufferIdx"][m], md["m_GlobalIndexBufferIdx"][m], md["m_NumLODs"][m] = vat, iat, 1
+        counts[m] = len(i)
+        idx.append(np.asarray(i, np.uint32))
+        vat += len(p); iat += len(i)
+    inst = np.zeros(len(placements), I.BasePassInstanceConstants)
+    opaque, alpha = [], []
+    for k, (m, W, mat, lst) in enumerate(placements):
+        inst["m_WorldMatrix"][k] = inst["m_PrevWorldMatrix"][k] = W
+        inst["m_MeshDataIdx"][k], inst["m_MaterialDataIdx"][k] = m, mat
+        if lst == "opaque":
+            opaque.append(k)
+        elif lst == "alpha":
+            alpha.append(k)
+    return dict(vertices=v, indices=np.concatenate(idx) if idx else np.zeros(0, np.uint32), meshData=md, index_counts=counts, instances=inst,
+                opaqueIds=np.array(opaque, np.uint32), alphaMaskIds=np.array(alpha, np.uint32), materials=materials() if mats is None else mats)
+
+
+def single(mesh, scale=(6.0, 1.0, 8.0), position=(0.0, 4.0, -7.0), **kw):
+    """One instance of one mesh, above the region the test camera looks at."""
+    return make_scene([mesh], [(0, world_matrix(scale=scale, axis=(0.2, 1.0, 0.1), angle=0.4, position=position, **kw), 0, "opaque")])
+
+
+def scattered(n, seed=11):
+    """n instances of three small meshes between the camera's region and the light: every third rotated, every fourth scaled
+    non-uniformly, every fifth mirrored; a tenth of them in the alpha-mask list (materials 2 and 3: below and above the cutoff)."""
+    rng = np.random.default_rng([seed, n])
+    meshes = [tetrahedron(), blob(9, seed), strip(5, seed)]
+    mats = materials()
+    mats["m_ConstAlbedo"][2, 3], mats["m_ConstAlbedo"][3, 3] = 0.25, 0.75
+    placements = []
+    for i in range(n):
+        scale = np.array([1.3, 1.3, 1.3]) * rng.uniform(0.6, 1.4)
+        if i % 4 == 1:
+            scale = scale * np.array([2.0, 0.4, 1.0])
+        if i % 5 == 2:
+            scale = scale * np.array([1.0, -1.0, 1.0])
+        W = world_matrix(scale=scale, axis=rng.normal(size=3), angle=rng.uniform(0, 6.28) if i % 3 else 0.0,
+                         position=(rng.uniform(-6, 6), rng.uniform(-1, 6), rng.uniform(-13, -2)))
+        lst, mat = ("alpha", 2 + (i // 10) % 2) if i % 10 == 7 else ("opaque", i % 2)
+        placements.append((i % 3, W, mat, lst))
+    return make_scene(meshes, placements, mats)
+
+
+def cornell():
+    """tests/golden/cornell_scene.npz with its rest transforms applied and its index buffer rebuilt from the LOD-0 meshlets: all
+    walls coplanar and axis-aligned, so every wall's box has no thickness."""
+    import json
+
+    from test_gltf_cornell import _fixture
+    from toyrenderer_amd import cached_scene, gltf_lite
+    with open(os.path.join(HERE, "golden", "cornell_materials.json")) as f:
+        cm = json.load(f)
+    _, s, camera = _fixture()
+    s.materials = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
+    s.primMaterial = np.array(cm["primitiveMaterial"], np.uint32)
+    inst = gltf_lite.apply_materials(s)
+    inst["m_WorldMatrix"] = inst["m_PrevWorldMatrix"] = node_world_matrices(s.nodes)[s.primToNode]
+    c = cached_scene.from_scene(s)
+    return dict(vertices=s.vertices, indices=c.indices, meshData=c.meshData, index_counts=c.meshSpecific["m_NumIndices"], instances=inst, opaqueIds=s.opaqueIds,
+                alphaMaskIds=s.alphaMaskIds, materials=s.materials, loaded=s, camera=camera, cached=c)
+
+
+def node_world_matrices(nodes):
+    """MakeWorldMatrix up the parent chain in float64, rounded once (the tests that need the kernel's bits run the kernel)."""
+    def local(n):
+        x, y, z, w = (float(v) for v in n["m_Rotation"])
+        R = np.array([[1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * z * w, 2 * x * z - 2 * y * w], [2 * x * y - 2 * z * w, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * x * w],
+                      [2 * x * z + 2 * y * w, 2 * y * z - 2 * x * w, 1 - 2 * x * x - 2 * y * y]])
+        M = np.eye(4)
+        M[:3, :3] = R
+        S = np.diag(np.append(n["m_Scale"].astype(np.float64), 1.0))
+        T = np.eye(4); T[3, :3] = n["m_Position"]
+        return M @ S @ T
+    out = np.zeros((len(nodes), 4, 4), F)
+    for i in range(len(nodes)):
+        W, p = local(nodes[i]), int(nodes[i]["m_ParentNodeIdx"])
+        while p != 0xFFFFFFFF:
+            W, p = W @ local(nodes[p]), int(nodes[p]["m_ParentNodeIdx"])
+        out[i] = W
+    return out
+
+
+# ---- camera, images, constants ---------------------------------------------------------------------------------------------------------
+EYE = (0.0, 1.5, 4.0)
+
+
+def noise_image(seed=1):
+    """uint8 [128, 128, 4]: random bytes, with the byte pairs that make MapToCone's offset (0, 0) impossible in bytes (127.5) left
+    out and the corners 0 and 255 among the first texels."""
+    rng = np.random.default_rng([seed, 128])
+    n = rng.integers(0, 256, (128, 128, 4), dtype=np.uint64).astype(np.uint8)
+    n[0, 0, :2], n[0, 1, :2], n[0, 2, :2], n[0, 3, :2] = (0, 0), (255, 255), (0, 255), (255, 0)
+    return n
+
+
+def images(W, H, seed, far_share=0.1):
+    """(depth float32 [H, W], GBufferA uint32 [H, W, 4]): positions 2 to 12 units in front of the camera (reverse-Z, infinite far:
+    depth = near / distance along the view axis), a share of far texels (0.0f; one of them -0.0f), random normal words."""
+    rng = np.random.default_rng([seed, W, H])
+    depth = (F(0.1) / rng.uniform(2.0, 12.0, (H, W)).astype(F)).astype(F)
+    far = rng.random((H, W)) < far_share
+    depth[far] = 0.0
+    flat = depth.reshape(-1)
+    if len(flat) > 3:
+        flat[1], flat[2] = 0.0, -0.0
+    g = rng.integers(0, 1 << 32, (H, W, 4), dtype=np.uint64).astype(np.uint32)
+    return depth, g
+
+
+def consts(W, H, light=(0.0, -1.0, 0.0), soft=True, frame_counter=0, ray_start_offset=0.01, diameter=accel.DEFAULT_SUN_ANGULAR_DIAMETER, eye=EYE, yaw=0.0):
+    v = synth.make_view(eye=eye, yaw=yaw, render=(W, H))
+    s = dict(soft=soft, sun_angular_diameter=diameter, ray_start_offset=ray_start_offset)
+    return accel.shadow_consts(I.clip_to_world(v.worldToView, v.viewToClip), light, eye, W, H, s, frame_counter)
+
+
+def unit(v):
+    v = np.asarray(v, np.float64)
+    return tuple(float(x) for x in (v / np.linalg.norm(v)).astype(F))
+
+
+# The light vector is the direction TOWARDS the sun (the ray's direction).
+LIGHTS = {"down": (0.0, -1.0, 0.0), "up": (0.0, 1.0, 0.0), "x": (1.0, 0.0, 0.0), "negzero": (-0.0, 1.0, -0.0), "generic": unit((0.3, 0.8, -0.52))}
+SIZES = [(1, 1), (7, 5), (8, 8), (9, 9), (67, 35)]
+TLAS_COUNTS = [1, 2, 3, 64, 65, 257]
+BLAS_SHAPES = {"one triangle": lambda: single(strip(1)), "L": lambda: single(strip(L)), "L+1": lambda: single(strip(L + 1)), "2L+1": lambda: single(strip(2 * L + 1)),
+               "degenerate": lambda: single(with_degenerates(), scale=(4.0, 2.0, 5.0)), "cornell": cornell}
+
+# (name, scene maker, (W, H), light, soft, frame counter)
+CASES = []
+for _name, _mk in BLAS_SHAPES.items():
+    CASES.append((f"blas {_name}", _mk, (67, 35), "generic" if _name == "cornell" else "up", True, 3))
+for _n in TLAS_COUNTS:
+    CASES.append((f"tlas {_n}", (lambda n=_n: scattered(n)), (67, 35), "generic", True, 5))
+for _s in SIZES:
+    CASES.append((f"size {_s[0]}x{_s[1]}", (lambda: scattered(40)), _s, "generic", False, 0))
+for _l in LIGHTS:
+    for _soft in (False, True):
+        CASES.append((f"light {_l} soft {_soft}", (lambda: scattered(65)), (33, 17), _l, _soft, 7))
+for _f in (0, 1, 255, 256):
+    CASES.append((f"frame {_f}", (lambda: scattered(33)), (33, 17), "generic", True, _f))
+
+
+def case_inputs(case):
+    """(scene, consts, depth, gbuffer, noise) of one CASES entry; the Cornell case looks through the fixture's own camera."""
+    name, mk, (W, H), light, soft, frame = case
+    sc = mk()
+    seed = sum(ord(c) for c in name)
+    depth, g = images(W, H, seed)
+    if "camera" in sc:
+        from toyrenderer_amd import gltf_lite
+        cam = sc["camera"]
+        v = gltf_lite.view_of(cam, (W, H))
+        k = accel.shadow_consts(I.clip_to_world(v.worldToView, v.viewToClip), LIGHTS[light], cam.position, W, H,
+                                dict(soft=soft, sun_angular_diameter=accel.DEFAULT_SUN_ANGULAR_DIAMETER, ray_start_offset=0.01), frame)
+        rng = np.random.default_rng(seed)
+        depth = np.where(depth == 0, depth, (F(cam.znear) / rng.uniform(4.05, 5.95, (H, W))).astype(F))       # inside the box
+    else:
+        k = consts(W, H, LIGHTS[light], soft, frame)
+    return sc, k, depth, g, noise_image()

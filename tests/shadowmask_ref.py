@@ -1,0 +1,114 @@
+"""ctypes wrapper of tests/shadowmask_ref.c, the definition of "shadowmask_CS_ShadowMask" and "raytracing_CS_RefitTLAS"
+(csrc/k_shadowmask.hip): brute force over every triangle (the definition of the mask), the walk of the product's node arrays with the
+kernel's box test, and the refit.  The acceleration structure itself comes from the product's builder (toyrenderer_amd/accel.py).
+
+The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from toyrenderer_amd import accel
+from toyrenderer_amd import interop as I
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+F = np.float32
+_LIB = {}
+SENTINEL8 = 0xA7                                   # pre-fill of the mask: neither 0 nor 255
+SENTINEL16 = 0xFE5A                                # pre-fill of the linear view depth: a NaN word, which the pass never stores
+BRUTE, WALK = 0, 1
+
+
+class _Scene(C.Structure):
+    _fields_ = [("instances", C.c_void_p), ("flags", C.c_void_p), ("numInstances", C.c_uint32),
+                ("vertices", C.c_void_p), ("numVertices", C.c_uint32),
+                ("materials", C.c_void_p), ("numMaterials", C.c_uint32),
+                ("indices", C.c_void_p), ("numIndices", C.c_uint32),
+                ("meshes", C.c_void_p), ("meshIndexCounts", C.c_void_p), ("numMeshes", C.c_uint32),
+                ("tlasNodes", C.c_void_p), ("numTlasNodes", C.c_uint32),
+                ("tlasInstances", C.c_void_p), ("headers", C.c_void_p),
+                ("blasNodes", C.c_void_p), ("numBlasNodes", C.c_uint32),
+                ("triOrder", C.c_void_p), ("numTriOrder", C.c_uint32)]
+
+
+def load(tmpdir) -> C.CDLL:
+    out = os.path.join(str(tmpdir), "libshadowmask_ref.so")
+    if out not in _LIB:
+        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "shadowmask_ref.c"), "-o", out, "-lm"])
+        lib = C.CDLL(out)
+        vp, u32 = C.c_void_p, C.c_uint32
+        lib.sm_half_bits.argtypes = [C.c_float]
+        lib.sm_half_bits.restype = C.c_uint16
+        lib.sm_object_from_world.argtypes = [vp, vp]
+        lib.sm_object_from_world.restype = None
+        lib.sm_refit.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, u32, vp]
+        lib.sm_refit.restype = None
+        lib.sm_texel_ray.argtypes = [vp, u32, u32, C.c_float, vp, vp, vp, vp, vp]
+        lib.sm_trace.argtypes = [vp, C.POINTER(_Scene), vp, vp, vp, C.c_int, vp, vp, vp]
+        lib.sm_trace.restype = None
+        _LIB[out] = lib
+    return _LIB[out]
+
+
+class Accel:
+    """The structure of one scene dict (tests/shadow_scenes.py): built by the product's builder from the scene's rest transforms."""
+
+    def __init__(self, scene: dict):
+        self.scene = scene
+        self.blas = accel.build_scene_blas(scene["vertices"], scene["indices"], scene["meshData"], scene["index_counts"])
+        self.flags = accel.instance_flags(len(scene["instances"]), scene["opaqueIds"], scene["alphaMaskIds"])
+        self.tlas = accel.build_tlas(scene["instances"], self.flags, self.blas)
+
+
+def refit(lib, acc: Accel, instances=None):
+    """(TLAS nodes, TLAS instance records) after "raytracing_CS_RefitTLAS" on `instances` (default: the scene's own)."""
+    inst = np.ascontiguousarray(acc.scene["instances"] if instances is None else instances, I.BasePassInstanceConstants)
+    nodes, records = acc.tlas["nodes"].copy(), acc.tlas["records"].copy()
+    h, bn = np.ascontiguousarray(acc.blas["headers"]), np.ascontiguousarray(acc.blas["nodes"])
+    lib.sm_refit(inst.ctypes.data, len(inst), h.ctypes.data, len(h), bn.ctypes.data, len(bn), acc.tlas["level_offsets"].ctypes.data,
+                 acc.tlas["level_nodes"].ctypes.data, acc.tlas["num_levels"], nodes.ctypes.data, len(nodes), records.ctypes.data)
+    return nodes, records
+
+
+def trace(lib, k, acc: Accel, depth, gbuffer, noise, mode, instances=None, nodes=None, records=None, mask=None, lvd=None):
+    """The pass over one image: (mask uint8 [H, W], linear view depth words uint16 [H, W], (box tests, triangle tests)).  mode BRUTE
+    is the definition; WALK walks `nodes` / `records` (default: the refit of `instances`)."""
+    sc = acc.scene
+    k = np.ascontiguousarray(k, I.ShadowMaskConsts)
+    W, H = (int(x) for x in k["m_OutputResolution"][0])
+    inst = np.ascontiguousarray(sc["instances"] if instances is None else instances, I.BasePassInstanceConstants)
+    if mode == WALK and nodes is None:
+        nodes, records = refit(lib, acc, inst)
+    if nodes is None:
+        nodes, records = acc.tlas["nodes"], acc.tlas["records"]
+    keep = [inst, np.ascontiguousarray(acc.flags, np.uint32), np.ascontiguousarray(sc["vertices"], I.RawVertexFormat), np.ascontiguousarray(sc["materials"], I.MaterialData),
+            np.ascontiguousarray(sc["indices"], np.uint32), np.ascontiguousarray(sc["meshData"], I.MeshData), np.ascontiguousarray(acc.blas["index_counts"], np.uint32),
+            np.ascontiguousarray(nodes, I.AccelNode), np.ascontiguousarray(records, I.TLASInstance), np.ascontiguousarray(acc.blas["headers"]),
+            np.ascontiguousarray(acc.blas["nodes"]), np.ascontiguousarray(acc.blas["tri_order"], np.uint32)]
+    p = [a.ctypes.data for a in keep]
+    s = _Scene(p[0], p[1], len(inst), p[2], len(keep[2]), p[3], len(keep[3]), p[4], len(keep[4]), p[5], p[6], len(keep[5]), p[7], len(keep[7]), p[8], p[9], p[10],
+               len(keep[10]), p[11], len(keep[11]))
+    depth = np.ascontiguousarray(depth, F).reshape(H, W)
+    g = np.ascontiguousarray(gbuffer, np.uint32).reshape(H, W, 4)
+    nz = np.ascontiguousarray(accel.noise_words(noise))
+    mask = np.full((H, W), SENTINEL8, np.uint8) if mask is None else np.ascontiguousarray(mask, np.uint8).copy()
+    lvd = np.full((H, W), SENTINEL16, np.uint16) if lvd is None else np.ascontiguousarray(lvd, np.uint16).copy()
+    counters = np.zeros(2, np.uint64)
+    lib.sm_trace(k.ctypes.data, C.byref(s), depth.ctypes.data, g.ctypes.data, nz.ctypes.data, mode, mask.ctypes.data, lvd.ctypes.data, counters.ctypes.data)
+    return mask, lvd, (int(counters[0]), int(counters[1]))
+
+
+def texel_rays(lib, k, depth, gbuffer, noise):
+    """(valid bool [H, W], origin float32 [H, W, 3], direction float32 [H, W, 3], world position float32 [H, W, 3]) of every texel."""
+    k = np.ascontiguousarray(k, I.ShadowMaskConsts)
+    W, H = (int(x) for x in k["m_OutputResolution"][0])
+    depth = np.ascontiguousarray(depth, F).reshape(H, W)
+    g = np.ascontiguousarray(gbuffer, np.uint32).reshape(H, W, 4)
+    nz = np.ascontiguousarray(accel.noise_words(noise))
+    valid, o, d, w = np.zeros((H, W), bool), np.zeros((H, W, 3), F), np.zeros((H, W, 3), F), np.zeros((H, W, 3), F)
+    for y in range(H):
+        for x in range(W):
+            valid[y, x] = bool(lib.sm_texel_ray(k.ctypes.data, x, y, C.c_float(float(depth[y, x])), g[y, x].ctypes.data, nz.ctypes.data, o[y, x].ctypes.data,
+                                                d[y, x].ctypes.data, w[y, x].ctypes.data))
+    return valid, o, d, w

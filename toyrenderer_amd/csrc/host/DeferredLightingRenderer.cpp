@@ -3,8 +3,8 @@
 // "deferredlighting_PS_Main" or, under a debug view, "deferredlighting_PS_Main_Debug" (csrc/k_deferredlighting.hip).
 //
 // Out of scope, as in the back end: DDGI (m_bRTDDGIEnabled stays 0, the volume descriptors and probe textures at t5..t8 are not
-// bound) and shadow-mask generation (the mask is an input, trhost_upload_shadow_mask;
-// without one t4 stays unbound: 1.0, the reference's WhiteTexture).  The full-screen triangle with its stencil test on the opaque
+// bound).  The shadow mask at t4 is ShadowMaskRenderer's when that pass is scheduled, else an uploaded one
+// (trhost_upload_shadow_mask), else t4 stays unbound: 1.0, the reference's WhiteTexture.  The full-screen triangle with its stencil test on the opaque
 // bit is a direct dispatch of 8x8 groups here; the kernel writes where depth > 0.
 #include "CommonResources.h"
 #include "Graphic.h"
@@ -27,6 +27,7 @@ public:
 
     nvrhi::TextureHandle m_LightingOutput;           // kLightingOutputFormat at render resolution, owned here for read-back
     nvrhi::TextureHandle m_SSAOTexture;              // AmbientOcclusionRenderer's output in this frame, or null: t3 stays unbound (255)
+    nvrhi::TextureHandle m_ShadowMask;               // ShadowMaskRenderer's output in this frame, else the uploaded mask, else null: t4 stays unbound (1.0)
     DeferredLightingConsts m_LastConsts{};           // what the last Render uploaded (trhost_get_deferred_lighting_consts)
     bool m_bHasLastConsts = false;
 
@@ -49,7 +50,9 @@ public:
         renderGraph.AddReadDependency(g_DepthStencilBufferRDGTextureHandle);
         m_SSAOTexture = GetScheduledSSAOTexture();                            // :41-44
         if (m_SSAOTexture) renderGraph.AddExternalReadDependency(m_SSAOTexture.Get());
-        if (g_Scene->m_ShadowMaskTexture) renderGraph.AddExternalReadDependency(g_Scene->m_ShadowMaskTexture.Get());   // :46-49
+        m_ShadowMask = GetScheduledShadowMaskTexture();                        // :46-49
+        if (!m_ShadowMask) m_ShadowMask = g_Scene->m_ShadowMaskTexture;
+        if (m_ShadowMask) renderGraph.AddExternalReadDependency(m_ShadowMask.Get());
         renderGraph.AddExternalWriteDependency(m_LightingOutput.Get());
         return true;
     }
@@ -84,7 +87,7 @@ public:
             Item::Texture_UAV(0, m_LightingOutput),
         };
         if (m_SSAOTexture) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(3, m_SSAOTexture));   // :77
-        if (g_Scene->m_ShadowMaskTexture) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(4, g_Scene->m_ShadowMaskTexture));
+        if (m_ShadowMask) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(4, m_ShadowMask));
         p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Graphic.m_RenderResolution, 8);
         g_Graphic.AddComputePass(p);
     }
@@ -106,5 +109,6 @@ void ReleaseDeferredLightingOutputs()
     DeferredLightingRenderer* r = static_cast<DeferredLightingRenderer*>(g_DeferredLightingRenderer);
     r->m_LightingOutput = nullptr;
     r->m_SSAOTexture = nullptr;
+    r->m_ShadowMask = nullptr;
     r->m_bHasLastConsts = false;
 }

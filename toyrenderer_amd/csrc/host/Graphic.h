@@ -91,6 +91,7 @@ public:
     nvrhi::BufferHandle m_GlobalMeshletDataBuffer;
     // what the mesh shader reads (basepass.hlsl t1, t5, t6): only needed when the frame rasterises its own depth
     nvrhi::BufferHandle m_GlobalVertexBuffer, m_GlobalMeshletVertexOffsetsBuffer, m_GlobalMeshletIndicesBuffer;
+    nvrhi::BufferHandle m_GlobalIndexBuffer;               // Graphic.h:139: the meshes' LOD-0 index lists (shadowmask.hlsl t6); Scene::LoadRaytracing
     nvrhi::BufferHandle m_GlobalMaterialDataBuffer;        // Graphic.h:135: MaterialData[], basepass.hlsl t3 (texture-free materials)
 
     Vector2U m_RenderResolution{ 0, 0 };

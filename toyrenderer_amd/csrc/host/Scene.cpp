@@ -17,6 +17,7 @@
 extern IRenderer* g_UpdateInstanceConstsRenderer;
 extern IRenderer* g_GBufferRenderer;
 extern IRenderer* g_AmbientOcclusionRenderer;
+extern IRenderer* g_ShadowMaskRenderer;
 extern IRenderer* g_DeferredLightingRenderer;
 extern IRenderer* g_SkyRenderer;
 extern IRenderer* g_BloomRenderer;
@@ -154,6 +155,74 @@ void Scene::LoadGeometry(const void* vertices, uint64_t numVertices, const uint3
     g_Graphic.m_GlobalMeshletIndicesBuffer = make("GlobalMeshletIndicesBuffer", meshletTriangles, numTriangles * 4u, 4u);
 }
 
+void Scene::LoadRaytracing(const uint32_t* indices, uint64_t numIndices, const uint32_t* indexCounts, uint32_t numMeshes)
+{
+    // Mesh::BuildBLAS (Visual.cpp:509-542) for every mesh and Scene::CreateAccelerationStructures (Scene.cpp:430-470), through the
+    // back end's one builder.  The vertex, mesh and instance tables are read back from their buffers: the scene keeps no host copy.
+    if (!g_Graphic.m_GlobalVertexBuffer || !g_Graphic.m_GlobalMeshDataBuffer || !m_InstanceConstsBuffer) throw std::runtime_error("raytracing: load the scene and its geometry first");
+    auto readBack = [](nvrhi::BufferHandle b, uint64_t bytes) {
+        std::vector<uint8_t> v((size_t)bytes);
+        if (bytes) nvrhi::throwIfFailed(trhip_buffer_download(b->native(), 0, v.data(), bytes), "raytracing read-back");
+        return v;
+    };
+    const uint64_t numVertices = g_Graphic.m_GlobalVertexBuffer->getDesc().byteSize / 20u;
+    if (g_Graphic.m_GlobalMeshDataBuffer->getDesc().byteSize < (uint64_t)numMeshes * sizeof(interop::MeshData)) throw std::runtime_error("raytracing: more index counts than meshes");
+    const std::vector<uint8_t> vertices = readBack(g_Graphic.m_GlobalVertexBuffer, numVertices * 20u);
+    const std::vector<uint8_t> meshBytes = readBack(g_Graphic.m_GlobalMeshDataBuffer, (uint64_t)numMeshes * sizeof(interop::MeshData));
+    const std::vector<uint8_t> instances = readBack(m_InstanceConstsBuffer, (uint64_t)m_NumPrimitives * sizeof(interop::BasePassInstanceConstants));
+    const interop::MeshData* md = (const interop::MeshData*)meshBytes.data();
+    std::vector<trhip_blas_header> headers(numMeshes);
+    std::vector<trhip_accel_node> blasNodes;
+    std::vector<uint32_t> triOrder;
+    for (uint32_t m = 0; m < numMeshes; ++m) {
+        const uint64_t first = md[m].m_GlobalIndexBufferIdx, count = indexCounts[m], vbase = md[m].m_GlobalVertexBufferIdx;
+        if (count % 3 || first + count > numIndices) throw std::runtime_error("raytracing: mesh " + std::to_string(m) + ": its indices are not a list of whole triangles inside the index buffer");
+        if (vbase > numVertices) throw std::runtime_error("raytracing: mesh " + std::to_string(m) + ": its first vertex is outside the vertex buffer");
+        const uint32_t cap = trhip_accel_max_nodes((uint32_t)(count / 3));
+        std::vector<trhip_accel_node> nodes(cap ? cap : 1);
+        std::vector<uint32_t> order(count / 3 ? count / 3 : 1);
+        uint32_t numNodes = 0, numTris = 0;
+        nvrhi::throwIfFailed(trhip_blas_build(vertices.data() + vbase * 20u, 20u, (uint32_t)(numVertices - vbase), indices + first, (uint32_t)count, nodes.data(), cap, order.data(),
+                                              &numNodes, &numTris, nullptr), "trhip_blas_build");
+        headers[m] = { (uint32_t)blasNodes.size(), numNodes, (uint32_t)triOrder.size(), numTris };
+        blasNodes.insert(blasNodes.end(), nodes.begin(), nodes.begin() + numNodes);
+        triOrder.insert(triOrder.end(), order.begin(), order.begin() + numTris);
+    }
+    std::vector<uint32_t> flags(m_NumPrimitives, 0u);                         // Scene.cpp:454
+    for (uint32_t id : m_OpaquePrimitiveIDs) if (id < m_NumPrimitives) flags[id] = interop::kTLASInstanceForceOpaque;
+    for (uint32_t id : m_AlphaMaskPrimitiveIDs) if (id < m_NumPrimitives) flags[id] = interop::kTLASInstanceForceNonOpaque;
+    const uint32_t cap = trhip_accel_max_nodes(m_NumPrimitives);
+    std::vector<trhip_accel_node> nodes(cap ? cap : 1);
+    std::vector<trhip_tlas_instance> records(m_NumPrimitives ? m_NumPrimitives : 1);
+    std::vector<uint32_t> levelNodes(cap ? cap : 1), levelOffsets(trhip_accel_max_depth() + 2, 0u);
+    uint32_t numNodes = 0, numLevels = 0;
+    nvrhi::throwIfFailed(trhip_tlas_build(instances.data(), m_NumPrimitives, flags.data(), headers.data(), numMeshes, blasNodes.data(), (uint32_t)blasNodes.size(), nodes.data(), cap,
+                                          records.data(), levelNodes.data(), levelOffsets.data(), &numNodes, &numLevels), "trhip_tlas_build");
+    nvrhi::DeviceHandle device = g_Graphic.m_NVRHIDevice;
+    auto make = [&](const char* name, const void* src, uint64_t bytes, uint32_t stride, bool uav) {
+        nvrhi::BufferDesc d;
+        d.byteSize = bytes ? bytes : stride;
+        d.structStride = stride;
+        d.debugName = name;
+        d.canHaveUAVs = uav;
+        d.initialState = nvrhi::ResourceStates::ShaderResource;
+        nvrhi::BufferHandle b = device->createBuffer(d);
+        if (bytes) nvrhi::throwIfFailed(trhip_buffer_upload(b->native(), 0, src, bytes), "raytracing upload");
+        return b;
+    };
+    auto as = std::make_shared<nvrhi::rt::AccelStruct>();
+    as->numNodes = numNodes; as->numLevels = numLevels;
+    as->nodes = make("TLAS Nodes", nodes.data(), (uint64_t)numNodes * sizeof(trhip_accel_node), sizeof(trhip_accel_node), true);
+    as->instances = make("TLAS Instances", records.data(), (uint64_t)m_NumPrimitives * sizeof(trhip_tlas_instance), sizeof(trhip_tlas_instance), true);
+    as->levelNodes = make("TLAS Level Nodes", levelNodes.data(), (uint64_t)(numNodes ? numNodes : 1) * 4u, 4u, false);
+    as->levelOffsets = make("TLAS Level Offsets", levelOffsets.data(), levelOffsets.size() * 4u, 4u, false);
+    as->blasHeaders = make("BLAS Headers", headers.data(), (uint64_t)numMeshes * sizeof(trhip_blas_header), sizeof(trhip_blas_header), false);
+    as->blasNodes = make("BLAS Nodes", blasNodes.data(), blasNodes.size() * sizeof(trhip_accel_node), sizeof(trhip_accel_node), false);
+    as->triOrder = make("BLAS Triangle Order", triOrder.data(), triOrder.size() * 4u, 4u, false);
+    g_Graphic.m_GlobalIndexBuffer = make("GlobalIndexBuffer", indices, numIndices * 4u, 4u, false);
+    m_TLAS = as;
+}
+
 void Scene::LoadMaterials(const void* materials, uint32_t numMaterials)
 {
     const interop::MaterialData* m = (const interop::MaterialData*)materials;
@@ -223,6 +292,7 @@ void Scene::Update()
         m_RenderGraph->AddRenderer(g_UpdateInstanceConstsRenderer);
         m_RenderGraph->AddRenderer(g_GBufferRenderer);
         if (m_bGBuffer && m_bEnableAO) m_RenderGraph->AddRenderer(g_AmbientOcclusionRenderer);   // :499
+        if (m_bGBuffer && m_bEnableShadows) m_RenderGraph->AddRenderer(g_ShadowMaskRenderer);    // :500
         if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
         if (m_bDeferredLighting && m_bEnableSky) m_RenderGraph->AddRenderer(g_SkyRenderer);  // :502
         if (m_bPostProcess && m_bEnableBloom) m_RenderGraph->AddRenderer(g_BloomRenderer);   // :503
@@ -246,6 +316,8 @@ void Scene::Shutdown()
     m_HZB = nullptr;
     m_SyntheticDepth = nullptr;
     m_ShadowMaskTexture = nullptr;
+    m_TLAS.reset();
+    m_BlueNoise = nullptr;
     m_BloomTexture = nullptr;
     m_LuminanceBuffer = nullptr;
     m_ExposureTexture = nullptr;

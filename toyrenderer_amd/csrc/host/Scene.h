@@ -133,6 +133,15 @@ public:
     bool m_bEnableAO = false;
     uint32_t m_AOQuality = 3, m_AODenoisePasses = 3;
     float m_AORadius = 0.5f, m_AOFalloffRange = 0.615f, m_AOFinalValuePower = 2.2f, m_AODepthMIPSamplingOffset = 3.3f;
+    // Ray-traced sun shadows (trhost_load_raytracing, trhost_upload_blue_noise, trhost_set_shadow_mask; needs m_bGBuffer, excludes an
+    // uploaded m_ShadowMaskTexture): ShadowMaskRenderer runs between AmbientOcclusionRenderer and DeferredLightingRenderer, which
+    // then binds its mask at t4.  m_TLAS (Scene.h:157) holds the whole structure; the settings are members of the renderer in the
+    // reference (ShadowMaskRenderer.cpp:87-89), the ray start offset is its 0.01 / 0.1 by the scene's bounding radius (:274).
+    void LoadRaytracing(const uint32_t* indices, uint64_t numIndices, const uint32_t* indexCounts, uint32_t numMeshes);
+    nvrhi::rt::AccelStructHandle m_TLAS;
+    nvrhi::TextureHandle m_BlueNoise;                // CommonResources::BlueNoise: RGBA8_UNORM 128 x 128, an input
+    bool m_bEnableShadows = false, m_bEnableSoftShadows = true;
+    float m_SunAngularDiameter = 0.533f, m_ShadowRayStartOffset = 0.1f;
     nvrhi::BufferHandle m_LuminanceBuffer;           // Scene.h: one float, the adapted luminance; survives across frames
     nvrhi::TextureHandle m_ExposureTexture;          // 1 x 1 R32_FLOAT
     // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.

@@ -66,6 +66,12 @@ nvrhi::TextureHandle GetSSAOTexture();
 nvrhi::TextureHandle GetScheduledSSAOTexture();
 bool GetLastGTAOConsts(void* out96);
 void ReleaseAmbientOcclusionOutputs();
+// ShadowMaskRenderer: the mask of the last frame (null if the pass did not run in it), the one the frame being set up will write
+// (null if the pass is not scheduled in it), and the ShadowMaskConsts the last frame uploaded.
+nvrhi::TextureHandle GetShadowMaskTexture();
+nvrhi::TextureHandle GetScheduledShadowMaskTexture();
+bool GetLastShadowMaskConsts(void* out112);
+void ReleaseShadowMaskOutputs();
 // The SkyPassParameters SkyRenderer uploaded in the last frame; false if the pass did not run in it.
 bool GetLastSkyConsts(void* out256);
 void ReleaseSkyOutputs();

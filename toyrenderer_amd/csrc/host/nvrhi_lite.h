@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -256,6 +257,21 @@ using SamplerHandle = RefCountPtr<ISampler>;
 using TimerQueryHandle = RefCountPtr<ITimerQuery>;
 using PipelineStatisticsQueryHandle = RefCountPtr<IPipelineStatisticsQuery>;
 
+// ---- nvrhi::rt::AccelStruct (Scene.h:157 m_TLAS, Visual.h m_BLAS): DXR's structure is opaque; this one is the back end's own
+// (include/trhip.h, "acceleration structure") and lives in ordinary buffers.  One object holds the whole scene's structure: the TLAS
+// nodes and instance records (refit every frame) and, below them, every mesh's BLAS.
+namespace rt
+{
+struct AccelStruct
+{
+    BufferHandle nodes, instances;                   // trhip_accel_node[], trhip_tlas_instance[]
+    BufferHandle levelOffsets, levelNodes;           // the refit's schedule
+    BufferHandle blasHeaders, blasNodes, triOrder;   // trhip_blas_header per mesh, all meshes' nodes and triangle orders
+    uint32_t numNodes = 0, numLevels = 0;
+};
+using AccelStructHandle = std::shared_ptr<AccelStruct>;
+} // namespace rt
+
 // ---- binding sets (Graphic.cpp:488-518; items used: BasePassRenderers.cpp:351-362,463-479,521-526) ---
 struct BindingSetItem
 {
@@ -279,6 +295,8 @@ struct BindingSetItem
     {
         BindingSetItem i; i.type = TRHIP_BIND_TEXTURE_UAV; i.slot = slot; i.texture = t; i.baseMip = s.baseMipLevel; return i;
     }
+    // the TLAS nodes as a structured SRV; the structure's other buffers are bound beside it (include/trhip.h)
+    static BindingSetItem RayTracingAccelStruct(uint32_t slot, rt::AccelStruct* as) { return StructuredBuffer_SRV(slot, as->nodes); }
     static BindingSetItem Sampler(uint32_t slot, ISampler* s) { BindingSetItem i; i.type = TRHIP_BIND_SAMPLER; i.slot = slot; i.sampler = s; return i; }
 };
 

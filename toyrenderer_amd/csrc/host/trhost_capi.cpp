@@ -64,6 +64,7 @@ void trhost_shutdown(void)
         ReleaseBloomOutputs();
         ReleaseSkyOutputs();
         ReleaseAmbientOcclusionOutputs();
+        ReleaseShadowMaskOutputs();
         g_Graphic.Shutdown();
     });
     s_Initialized = false;
@@ -381,6 +382,67 @@ int trhost_get_gtao_consts(void* out96)
     return guarded([&] {
         check(out96);
         if (!GetLastGTAOConsts(out96)) throw nvrhi::Error("trhost_get_gtao_consts: the ambient occlusion pass did not run in the last frame");
+    });
+}
+
+int trhost_load_raytracing(const uint32_t* indices, uint64_t num_indices, const uint32_t* index_counts, uint32_t num_meshes)
+{
+    return guarded([&] {
+        check(g_Scene);
+        check((indices || !num_indices) && (index_counts || !num_meshes));
+        g_Scene->LoadRaytracing(indices, num_indices, index_counts, num_meshes);
+    });
+}
+
+int trhost_upload_blue_noise(const uint8_t* rgba, uint64_t bytes)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!rgba || bytes != 128u * 128u * 4u) throw nvrhi::Error("trhost_upload_blue_noise: needs the 128 x 128 RGBA8 image (65536 bytes)");
+        if (!g_Scene->m_BlueNoise) {
+            nvrhi::TextureDesc desc;
+            desc.width = desc.height = 128;
+            desc.format = nvrhi::Format::RGBA8_UNORM;
+            desc.debugName = "Blue Noise";
+            g_Scene->m_BlueNoise = g_Graphic.m_NVRHIDevice->createTexture(desc);
+        }
+        nvrhi::throwIfFailed(trhip_texture_upload(g_Scene->m_BlueNoise->native(), 0, rgba, bytes), "trhost_upload_blue_noise");
+    });
+}
+
+int trhost_set_shadow_mask(int enable, int soft, float sun_angular_diameter, float ray_start_offset)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!enable) { g_Scene->m_bEnableShadows = false; return; }
+        if (!g_Scene->m_bGBuffer) throw nvrhi::Error("trhost_set_shadow_mask: the G-buffer is off (trhost_set_gbuffer or trhost_set_deferred_lighting first): the rays start at its positions and normals");
+        if (!g_Scene->m_TLAS) throw nvrhi::Error("trhost_set_shadow_mask: no acceleration structure (trhost_load_raytracing first)");
+        if (!g_Scene->m_BlueNoise) throw nvrhi::Error("trhost_set_shadow_mask: no blue noise (trhost_upload_blue_noise first)");
+        if (g_Scene->m_ShadowMaskTexture) throw nvrhi::Error("trhost_set_shadow_mask: a shadow mask was uploaded (trhost_upload_shadow_mask(NULL, 0) removes it): the pass generates the texture itself");
+        if (!(std::isfinite(sun_angular_diameter) && sun_angular_diameter >= 0.0f && sun_angular_diameter < 180.0f)) throw nvrhi::Error("trhost_set_shadow_mask: the sun's angular diameter must be degrees in [0, 180)");
+        if (!(std::isfinite(ray_start_offset) && ray_start_offset >= 0.0f)) throw nvrhi::Error("trhost_set_shadow_mask: the ray start offset must be finite and >= 0");
+        g_Scene->m_bEnableShadows = true;
+        g_Scene->m_bEnableSoftShadows = soft != 0;
+        g_Scene->m_SunAngularDiameter = sun_angular_diameter;
+        g_Scene->m_ShadowRayStartOffset = ray_start_offset;
+    });
+}
+
+int trhost_download_shadow_mask(uint8_t* bytes, uint64_t size)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetShadowMaskTexture();
+        if (!t) throw nvrhi::Error("trhost_download_shadow_mask: the shadow mask pass did not run in the last frame");
+        check(bytes);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, bytes, size), "trhost_download_shadow_mask");
+    });
+}
+
+int trhost_get_shadow_mask_consts(void* out112)
+{
+    return guarded([&] {
+        check(out112);
+        if (!GetLastShadowMaskConsts(out112)) throw nvrhi::Error("trhost_get_shadow_mask_consts: the shadow mask pass did not run in the last frame");
     });
 }
 

@@ -2,8 +2,8 @@
 // after GBufferRenderer (source/DeferredLightingRenderer.cpp, source/shaders/deferredlighting.hlsl; EvaluateDirectionalLight,
 // DefaultLitBxDF and UnpackGBuffer of lightingcommon.hlsli), WITHOUT DDGI and with the shadow mask as an input: the directional
 // light and the debug views, closed arithmetic on GBufferA, depth, the motion target, the SSAO and the shadow-mask texels.
-// DDGI ambient and shadow-mask generation are out of scope; the sky is k_sky.hip's, the SSAO texture
-// k_ambientocclusion.hip's.
+// DDGI ambient is out of scope; the sky is k_sky.hip's, the SSAO texture k_ambientocclusion.hip's, the shadow mask
+// k_shadowmask.hip's.
 //
 // WHICH PIXELS: the reference draws where the stencil equals the opaque bit.  The stand-in: a pixel is written iff its depth
 // word is > 0.0f (NaN, +-0 and negative depths are skipped); every other texel of u0 keeps what it held.
@@ -53,6 +53,7 @@
 // spread, so the 64 x 1 row stays.  The debug entry in view 4: 47.6 us.  Code object: PS_Main 27 VGPRs, _Debug 22 VGPRs, 8 waves
 // per SIMD, no scratch, no LDS (-Rpass-analysis=kernel-resource-usage).
 #include "cull_math.hip.h"
+#include "gbuffer_unpack.hip.h"
 #include "r11g11b10.hip.h"
 #include "trhip_internal.h"
 
@@ -60,6 +61,7 @@ namespace
 {
 
 using namespace interop;
+using namespace gbuf;
 
 #ifndef TR_LIGHTING_TILE_W
 #define TR_LIGHTING_TILE_W 64                  // a wave = one 64 x 1 row segment; 16 gives the G-buffer resolve's 16 x 4 (tools/lighting_cost.py measures both)
@@ -79,13 +81,6 @@ struct LightingArgs
     uint32_t* out;                             // R11G11B10_FLOAT
 };
 
-__device__ __forceinline__ float saturate_(float x) { return cm::min_(cm::max_(x, 0.0f), 1.0f); }
-__device__ __forceinline__ cm::F3 normalize_(cm::F3 v)
-{
-    const float len = cm::sqrt_(cm::dot3(v, v));
-    return { cm::div_(v.x, len), cm::div_(v.y, len), cm::div_(v.z, len) };
-}
-
 // exp2 for x <= 0; coefficients and error analysis: tests/lighting_ref.c (kExp2C)
 __device__ __forceinline__ float exp2Soft(float x)
 {
@@ -103,29 +98,6 @@ __device__ __forceinline__ float exp2Soft(float x)
     p = cm::fma_(p, f, 1.0f);
     return __builtin_ldexpf(p, (int)i);
 #endif
-}
-
-__device__ __forceinline__ float unorm8(uint32_t byte) { return (float)byte * (1.0f / 255.0f); }
-__device__ __forceinline__ float unorm16(uint32_t u) { return (float)u * (1.0f / 65535.0f); }
-
-struct GBufferParams { cm::F3 albedo; float debugValue; cm::F3 normal, emissive; float roughness, metallic; };
-
-__device__ __forceinline__ GBufferParams unpackGBuffer(uint4 g)                                    // lightingcommon.hlsli:36-51
-{
-    GBufferParams p;
-    p.albedo = { unorm8(g.x & 0xFFu), unorm8((g.x >> 8) & 0xFFu), unorm8((g.x >> 16) & 0xFFu) };
-    p.debugValue = unorm8(g.x >> 24);
-    const float fx = unorm16(g.y & 0xFFFFu) * 2.0f - 1.0f, fy = unorm16(g.y >> 16) * 2.0f - 1.0f;   // packunpack.hlsli:17-26
-    cm::F3 n = { fx, fy, (1.0f - __builtin_fabsf(fx)) - __builtin_fabsf(fy) };
-    const float t = saturate_(-n.z);
-    n.x += n.x >= 0.0f ? -t : t;
-    n.y += n.y >= 0.0f ? -t : t;
-    p.normal = normalize_(n);
-    const int e = (int)(g.z >> 27) - 24;                                                           // packunpack.hlsli:247-251
-    p.emissive = { __builtin_ldexpf((float)(g.z & 0x1FFu), e), __builtin_ldexpf((float)((g.z >> 9) & 0x1FFu), e), __builtin_ldexpf((float)((g.z >> 18) & 0x1FFu), e) };
-    p.roughness = unorm8(g.w & 0xFFu);
-    p.metallic = unorm8((g.w >> 8) & 0xFFu);
-    return p;
 }
 
 __device__ __forceinline__ float quickRandomFloat(uint32_t& seed)                                  // random.hlsli:7-11

@@ -1,0 +1,451 @@
+// k_shadowmask.hip -- "shadowmask_CS_ShadowMask": ShadowMaskRenderer::TraceShadows without denoising (source/ShadowMaskRenderer.cpp
+// :253-305, source/shaders/shadowmask.hlsl CS_ShadowMask): one ray per pixel towards the sun through the scene's acceleration
+// structure; and "raytracing_CS_RefitTLAS", this build's stand-in for buildTopLevelAccelStructFromBuffer (BasePassRenderers.cpp
+// :159-160): the per-frame refit of that structure's top level.  The structure is the project's own (include/trhip.h,
+// "acceleration structure"; built on the host by accel_build.cpp).  DenoiseShadows, CS_PackNormalAndRoughness and the
+// penumbra packing are NRD and not built: a constant block with m_bDoDenoising != 0 is refused.
+//
+// BINDINGS of the trace: b0 ShadowMaskConsts (112 bytes), t0 R32_FLOAT depth, t1 the TLAS nodes, t2 GBufferA, t3 instances, t4
+// vertices, t5 materials, t6 indices, t7 mesh data, t8 RGBA8_UNORM 128 x 128 blue noise, u0 R8_UNORM mask, u1 R16_FLOAT linear view
+// depth; the structure's other buffers: t9 TLAS instances, t10 BLAS headers, t11 BLAS nodes, t12 triangle order.  Samplers are
+// accepted and ignored.  Of the refit: push constants RefitTLASConstants (12 bytes), t0 instances, t1 BLAS headers, t2 BLAS nodes,
+// t3 level offsets, t4 level nodes, u0 the TLAS nodes, u1 the TLAS instances.
+//
+// CONVENTION (tests/shadowmask_ref.c is the definition; the functions below repeat its functions word for word).  IEEE binary32,
+// no contraction, fma only where written, / and sqrt correctly rounded:
+//   worldPosition, UnpackGBuffer's normal, dot3, normalize as k_deferredlighting.hip states them (gbuffer_unpack.hip.h);
+//   noise = (float)byte / 255.0f of the blue noise texel's R and G at (px % 128, py % 128), + m_NoisePhase, fmod(x, 1) = x - trunc(x);
+//   MapToCone / CreateTangentVectors as the HLSL with softmath::cosSoft / sinSoft, RN(pi / 4) and RN(pi / 2), cross as cm::cross3,
+//             (n + u.x * t0) + u.y * t1; the direction is its normalize; origin = worldPosition + normal * m_RayStartOffset;
+//             TMin = m_RayStartOffset, TMax = 1e10f;
+//   the ray is moved to object space once per instance (mulPoint with the refit's object-from-world rows; the direction without the
+//             translation and not normalised); objectFromWorld: cofactors / determinant in the order written there;
+//   triHit:   the watertight test of Woop, Benthin and Wald in binary32 without the double fallback; two-sided; hit iff
+//             TMin < t < TMax.  A candidate on a ForceNonOpaque instance counts iff m_ConstAlbedo.w >= m_AlphaCutoff of the
+//             candidate's instance's material (the reference reads Committed* there: shadowmask.hlsl:113-116);
+//   boxHit:   conservative: per axis a direction component without a finite reciprocal asks lo <= origin <= hi only (the default
+//             light (0, -1, 0) makes every ray axis-parallel, Cornell's walls are boxes of no thickness: no inf * 0 here); else
+//             the slab's interval with both ends moved outward by 2^-18 of themselves; node boxes are padded by the builder (2^-16
+//             of the mesh's largest |coordinate|) and by the refit (2^-12 of the leaf's largest |coordinate|).  Any-hit over all
+//             triangles is order-independent, so the mask equals brute force for any tree as long as boxHit never rejects what
+//             triHit accepts: tests/test_shadowmask_ref.py walks the same arrays on the CPU and allows no differing texel;
+//   output:   depth == 0.0f: u1 = 0x7BFF, u0 untouched; else u0 = occluded ? 0 : 255, u1 = binary16 RNE of
+//             length(worldPosition - m_CameraPosition) (a NaN is stored as 0x7E00).
+//
+// KERNEL: one thread per pixel, a workgroup is one wave covering the reference's 8 x 8 tile, so the 64 rays of a wave start next
+// to each other.  NO STACK: the nodes are in depth-first preorder with skip links (trhip.h), the walk is `hit an inner box ->
+// i + 1, else -> skip`, so there is no per-lane array, nothing to overflow, no LDS and no scratch; a link that does not move
+// forward ends the walk (a corrupt buffer cannot spin).  Runtime-chosen vector components go through sel() (selects), not through
+// an indexed array.  Every index read on the device is checked against its buffer before it is followed.  A wave walks until its
+// last lane is done, and lanes that disagree on a box serialise both sides.  MEASURED (tools/shadowmask_cost.py, the generated city
+// of 2251 instances at 3840x2160, one MI355X; profiles/shadowmask/): the trace 1.92 ms with hard and 3.86 ms with soft shadows next to
+// a lighting pass of 0.10 ms, the refit 35 us.  Untuned: correctness came first.
+#include "cull_math.hip.h"
+#include "gbuffer_unpack.hip.h"
+#include "soft_math.hip.h"
+#include "trhip_internal.h"
+
+namespace
+{
+
+using namespace interop;
+using cm::F3;
+
+constexpr uint32_t kTileSide = 8;               // [numthreads(8, 8, 1)]
+constexpr uint32_t kRefitBlock = 64;
+constexpr float kSlack = 0x1p-18f, kTlasPad = 0x1p-12f, kFloatMax = 3.402823466e38f;
+
+struct TraceArgs
+{
+    ShadowMaskConsts k;
+    const float* depth;                        // R32_FLOAT
+    const uint4* gbufferA;                     // RGBA32_UINT
+    const uint32_t* noise;                     // RGBA8_UNORM, 128 x 128
+    uint8_t* mask;                             // R8_UNORM
+    uint16_t* lvd;                             // R16_FLOAT
+    const BasePassInstanceConstants* instances; uint32_t numInstances;
+    const uint8_t* vertices; uint32_t numVertices;            // 20-byte stride
+    const uint8_t* materials; uint32_t numMaterials;          // 124-byte stride
+    const uint32_t* indices; uint32_t numIndices;
+    const uint8_t* meshes; uint32_t numMeshes;                // 156-byte stride
+    const trhip_accel_node* tlasNodes; uint32_t numTlasNodes;
+    const trhip_tlas_instance* tlasInstances;
+    const trhip_blas_header* headers;
+    const trhip_accel_node* blasNodes; uint32_t numBlasNodes;
+    const uint32_t* triOrder; uint32_t numTriOrder;
+};
+
+__device__ __forceinline__ float sel(F3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
+
+// rows r0 r1 r2 r3 of p_object = (p_world, 1) * M, from the rows of m_WorldMatrix
+__device__ __forceinline__ void objectFromWorld(const float* w, float* out)
+{
+    const F3 a = { w[0], w[1], w[2] }, b = { w[4], w[5], w[6] }, c = { w[8], w[9], w[10] }, t = { w[12], w[13], w[14] };
+    const float c00 = b.y * c.z - b.z * c.y, c01 = b.z * c.x - b.x * c.z, c02 = b.x * c.y - b.y * c.x;
+    const float det = (a.x * c00 + a.y * c01) + a.z * c02;
+    float inv[3][3];
+    inv[0][0] = cm::div_(c00, det); inv[1][0] = cm::div_(c01, det); inv[2][0] = cm::div_(c02, det);
+    inv[0][1] = cm::div_(a.z * c.y - a.y * c.z, det); inv[1][1] = cm::div_(a.x * c.z - a.z * c.x, det); inv[2][1] = cm::div_(a.y * c.x - a.x * c.y, det);
+    inv[0][2] = cm::div_(a.y * b.z - a.z * b.y, det); inv[1][2] = cm::div_(a.z * b.x - a.x * b.z, det); inv[2][2] = cm::div_(a.x * b.y - a.y * b.x, det);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[3 * i + j] = inv[i][j];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) out[9 + j] = -((t.x * inv[0][j] + t.y * inv[1][j]) + t.z * inv[2][j]);
+}
+
+struct M34 { float m[12]; };
+
+__device__ __forceinline__ F3 mulPoint(F3 p, const M34& M, bool translate)
+{
+    const float* m = M.m;
+    F3 r = { cm::fma_(p.z, m[6], cm::fma_(p.y, m[3], p.x * m[0])), cm::fma_(p.z, m[7], cm::fma_(p.y, m[4], p.x * m[1])), cm::fma_(p.z, m[8], cm::fma_(p.y, m[5], p.x * m[2])) };
+    if (translate) { r.x = r.x + m[9]; r.y = r.y + m[10]; r.z = r.z + m[11]; }
+    return r;
+}
+
+// ---- "raytracing_CS_RefitTLAS" --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kRefitBlock) void refitLeavesKernel(const BasePassInstanceConstants* __restrict__ instances, uint32_t numInstances,
+                                                                 const trhip_blas_header* __restrict__ headers, uint32_t numMeshes,
+                                                                 const trhip_accel_node* __restrict__ blasNodes, uint32_t numBlasNodes,
+                                                                 trhip_accel_node* nodes, uint32_t numNodes, trhip_tlas_instance* records)
+{
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= numInstances) return;
+    const uint32_t flags = records[i].flags, leafNode = records[i].leaf_node;
+    if (!flags || leafNode >= numNodes) return;
+    float w[16];
+    const float4* src = reinterpret_cast<const float4*>(&instances[i].m_WorldMatrix);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const float4 v = src[r]; w[4 * r] = v.x; w[4 * r + 1] = v.y; w[4 * r + 2] = v.z; w[4 * r + 3] = v.w; }
+    float m[12];
+    objectFromWorld(w, m);
+#pragma unroll
+    for (int j = 0; j < 12; ++j) records[i].object_from_world[j] = m[j];
+    const uint32_t mesh = instances[i].m_MeshDataIdx;
+    float lo[3] = { kFloatMax, kFloatMax, kFloatMax }, hi[3] = { -kFloatMax, -kFloatMax, -kFloatMax };
+    if (mesh < numMeshes && headers[mesh].num_nodes && headers[mesh].node_offset < numBlasNodes) {
+        const trhip_accel_node root = blasNodes[headers[mesh].node_offset];
+        float largest = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const F3 p = { c & 1 ? root.hi[0] : root.lo[0], c & 2 ? root.hi[1] : root.lo[1], c & 4 ? root.hi[2] : root.lo[2] };
+            const float q[3] = { cm::fma_(p.z, w[8], cm::fma_(p.y, w[4], p.x * w[0])) + w[12], cm::fma_(p.z, w[9], cm::fma_(p.y, w[5], p.x * w[1])) + w[13],
+                                 cm::fma_(p.z, w[10], cm::fma_(p.y, w[6], p.x * w[2])) + w[14] };
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { lo[a] = cm::min_(lo[a], q[a]); hi[a] = cm::max_(hi[a], q[a]); largest = cm::max_(largest, __builtin_fabsf(q[a])); }
+        }
+        const float pad = kTlasPad * largest;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo[a] = lo[a] - pad; hi[a] = hi[a] + pad; }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { nodes[leafNode].lo[a] = lo[a]; nodes[leafNode].hi[a] = hi[a]; }
+}
+
+// One workgroup: the inner boxes height by height, children before parents.  A tree of n leaves has n - 1 inner nodes in at most
+// 56 heights; the barrier between two heights also orders this group's stores to global memory before its next loads.
+constexpr uint32_t kInnerBlock = 256;
+__global__ __launch_bounds__(kInnerBlock) void refitInnerKernel(const uint32_t* __restrict__ levelOffsets, const uint32_t* __restrict__ levelNodes, uint32_t numLevels,
+                                                                uint32_t numLevelNodes, trhip_accel_node* nodes, uint32_t numNodes)
+{
+    for (uint32_t l = 0; l < numLevels; ++l) {
+        const uint32_t begin = levelOffsets[l], end = levelOffsets[l + 1] < numLevelNodes ? levelOffsets[l + 1] : numLevelNodes;
+        for (uint32_t k = begin + threadIdx.x; k < end; k += kInnerBlock) {
+            const uint32_t n = levelNodes[k];
+            if (n >= numNodes || n + 1 >= numNodes) continue;
+            const uint32_t right = nodes[n + 1].skip;
+            if (right >= numNodes) continue;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                nodes[n].lo[a] = cm::min_(nodes[n + 1].lo[a], nodes[right].lo[a]);
+                nodes[n].hi[a] = cm::max_(nodes[n + 1].hi[a], nodes[right].hi[a]);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+int recordRefit(trhip::DispatchCtx& ctx)
+{
+    const char* name = ctx.shaderName;
+    const RefitTLASConstants* k = (const RefitTLASConstants*)ctx.constants(0, sizeof(RefitTLASConstants));
+    TRHIP_REQUIRE(k, "%s: push constants (RefitTLASConstants, 12 bytes) missing or of another size", name);
+    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 64-thread groups", name);
+    trhip_buffer_t* instances = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 0);
+    trhip_buffer_t* headers = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 1);
+    trhip_buffer_t* blasNodes = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 2);
+    trhip_buffer_t* levelOffsets = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 3);
+    trhip_buffer_t* levelNodes = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 4);
+    trhip_buffer_t* nodes = ctx.buffer(TRHIP_BIND_STRUCTURED_UAV, 0);
+    trhip_buffer_t* records = ctx.buffer(TRHIP_BIND_STRUCTURED_UAV, 1);
+    TRHIP_REQUIRE(instances && headers && blasNodes && levelOffsets && levelNodes && nodes && records,
+                  "%s: needs SRVs t0 (instances), t1 (BLAS headers), t2 (BLAS nodes), t3 (level offsets), t4 (level nodes) and UAVs u0 (TLAS nodes), u1 (TLAS instances)", name);
+    const uint32_t n = k->m_NumInstances;
+    TRHIP_REQUIRE((uint64_t)n * sizeof(BasePassInstanceConstants) <= instances->byteSize, "%s: %u instances exceed the instance buffer", name, n);
+    TRHIP_REQUIRE((uint64_t)n * sizeof(trhip_tlas_instance) <= records->byteSize, "%s: %u instances exceed the TLAS instance buffer", name, n);
+    TRHIP_REQUIRE((uint64_t)k->m_NumNodes * sizeof(trhip_accel_node) <= nodes->byteSize, "%s: %u nodes exceed the TLAS node buffer", name, k->m_NumNodes);
+    TRHIP_REQUIRE(((uint64_t)k->m_NumLevels + 1) * 4 <= levelOffsets->byteSize, "%s: %u levels exceed the level offset buffer", name, k->m_NumLevels);
+    TRHIP_REQUIRE((uint64_t)ctx.gx * kRefitBlock >= n, "%s: a direct dispatch of 64-thread groups covering %u instances", name, n);
+    if (!n || !k->m_NumNodes) return TRHIP_OK;
+    const RefitTLASConstants kk = *k;
+    const BasePassInstanceConstants* ip = (const BasePassInstanceConstants*)instances->ptr;
+    const trhip_blas_header* hp = (const trhip_blas_header*)headers->ptr;
+    const trhip_accel_node* bp = (const trhip_accel_node*)blasNodes->ptr;
+    const uint32_t numMeshes = (uint32_t)(headers->byteSize / sizeof(trhip_blas_header)), numBlasNodes = (uint32_t)(blasNodes->byteSize / sizeof(trhip_accel_node));
+    const uint32_t* lo = (const uint32_t*)levelOffsets->ptr; const uint32_t* ln = (const uint32_t*)levelNodes->ptr;
+    const uint32_t numLevelNodes = (uint32_t)(levelNodes->byteSize / 4);
+    trhip_accel_node* np = (trhip_accel_node*)nodes->ptr;
+    trhip_tlas_instance* rp = (trhip_tlas_instance*)records->ptr;
+    ctx.emit("main", [=](hipStream_t s) {
+        TRHIP_LAUNCH(refitLeavesKernel, dim3((kk.m_NumInstances + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, s, ip, kk.m_NumInstances, hp, numMeshes, bp, numBlasNodes,
+                     np, kk.m_NumNodes, rp);
+        if (kk.m_NumLevels)
+            TRHIP_LAUNCH(refitInnerKernel, dim3(1), dim3(kInnerBlock), 0, s, lo, ln, kk.m_NumLevels, numLevelNodes, np, kk.m_NumNodes);
+        return trhip::launchStatus("refitTLAS"); });
+    return TRHIP_OK;
+}
+
+// ---- the two tests (tests/shadowmask_ref.c: make_ray, sm_box_hit, sm_tri_hit) ---------------------------------------------------
+struct Ray { F3 o, d, inv; int kx, ky, kz; float Sx, Sy, Sz; };
+
+__device__ __forceinline__ Ray makeRay(F3 o, F3 d)
+{
+    Ray r;
+    r.o = o; r.d = d;
+    r.inv.x = cm::div_(1.0f, d.x); r.inv.y = cm::div_(1.0f, d.y); r.inv.z = cm::div_(1.0f, d.z);
+    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+    int kz = 0;
+    float m = ax;
+    if (ay > m) { kz = 1; m = ay; }
+    if (az > m) { kz = 2; }
+    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+    const float dz = sel(d, kz);
+    if (dz < 0.0f) { const int s = kx; kx = ky; ky = s; }
+    r.kx = kx; r.ky = ky; r.kz = kz;
+    r.Sx = cm::div_(sel(d, kx), dz); r.Sy = cm::div_(sel(d, ky), dz); r.Sz = cm::div_(1.0f, dz);
+    return r;
+}
+
+__device__ __forceinline__ bool boxHit(const trhip_accel_node& n, const Ray& r)
+{
+    float tenter = 0.0f, texit = __builtin_inff();
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float o = sel(r.o, a), inv = sel(r.inv, a);
+        if (!(__builtin_fabsf(inv) <= kFloatMax)) {
+            if (!(o >= n.lo[a] && o <= n.hi[a])) return false;
+        } else {
+            const float t0 = (n.lo[a] - o) * inv, t1 = (n.hi[a] - o) * inv;
+            float tn = cm::min_(t0, t1), tf = cm::max_(t0, t1);
+            tn = tn - __builtin_fabsf(tn) * kSlack; tf = tf + __builtin_fabsf(tf) * kSlack;
+            tenter = cm::max_(tenter, tn); texit = cm::min_(texit, tf);
+        }
+    }
+    return tenter <= texit;
+}
+
+__device__ __forceinline__ bool triHit(F3 v0, F3 v1, F3 v2, const Ray& r, float tmin, float tmax)
+{
+    const F3 A = { v0.x - r.o.x, v0.y - r.o.y, v0.z - r.o.z }, B = { v1.x - r.o.x, v1.y - r.o.y, v1.z - r.o.z }, C = { v2.x - r.o.x, v2.y - r.o.y, v2.z - r.o.z };
+    const float Akz = sel(A, r.kz), Bkz = sel(B, r.kz), Ckz = sel(C, r.kz);
+    const float Ax = sel(A, r.kx) - r.Sx * Akz, Ay = sel(A, r.ky) - r.Sy * Akz;
+    const float Bx = sel(B, r.kx) - r.Sx * Bkz, By = sel(B, r.ky) - r.Sy * Bkz;
+    const float Cx = sel(C, r.kx) - r.Sx * Ckz, Cy = sel(C, r.ky) - r.Sy * Ckz;
+    const float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f)) return false;
+    const float det = (U + V) + W;
+    if (det == 0.0f) return false;
+    const float Az = r.Sz * Akz, Bz = r.Sz * Bkz, Cz = r.Sz * Ckz;
+    const float T = (U * Az + V * Bz) + W * Cz;
+    const float t = cm::div_(T, det);
+    return t > tmin && t < tmax;
+}
+
+__device__ __forceinline__ float fmod1(float x) { return x - __builtin_truncf(x); }
+
+__device__ __forceinline__ F3 mapToCone(float sx, float sy, F3 n, float radius)                     // shadowmask.hlsl:24-63
+{
+    const float ox = 2.0f * sx - 1.0f, oy = 2.0f * sy - 1.0f;
+    if (ox == 0.0f && oy == 0.0f) return n;
+    float theta, r;
+    if (__builtin_fabsf(ox) > __builtin_fabsf(oy)) { r = ox; theta = 0x1.921fb6p-1f * cm::div_(oy, ox); }
+    else { r = oy; theta = 0x1.921fb6p+0f * (1.0f - 0.5f * cm::div_(ox, oy)); }
+    const float ux = (radius * r) * softmath::cosSoft(theta), uy = (radius * r) * softmath::sinSoft(theta);
+    const bool zUp = __builtin_fabsf(n.z) < 0.99999f;
+    const F3 up = { zUp ? 0.0f : 1.0f, 0.0f, zUp ? 1.0f : 0.0f };
+    const F3 t0 = gbuf::normalize_(cm::cross3(up, n)), t1 = cm::cross3(n, t0);
+    return { (n.x + ux * t0.x) + uy * t1.x, (n.y + ux * t0.y) + uy * t1.y, (n.z + ux * t0.z) + uy * t1.z };
+}
+
+__device__ __forceinline__ F3 vertexOf(const TraceArgs& a, uint64_t i)
+{
+    const float* p = reinterpret_cast<const float*>(a.vertices + i * sizeof(RawVertexFormat));
+    return { p[0], p[1], p[2] };
+}
+
+// the candidate counts: ForceOpaque always, ForceNonOpaque by the alpha test of its instance's material (GetCommonGBufferParams without textures)
+__device__ __forceinline__ bool commits(const TraceArgs& a, uint32_t inst, uint32_t flags)
+{
+    if (flags != kTLASInstanceForceNonOpaque) return true;
+    const uint32_t mat = a.instances[inst].m_MaterialDataIdx;
+    if (mat >= a.numMaterials) return false;
+    const MaterialData* m = reinterpret_cast<const MaterialData*>(a.materials + (uint64_t)mat * sizeof(MaterialData));
+    return m->m_ConstAlbedo.w >= m->m_AlphaCutoff;
+}
+
+__device__ __forceinline__ bool meshTriHit(const TraceArgs& a, const MeshData* md, uint32_t tri, const Ray& r, float tmin, float tmax)
+{
+    const uint64_t base = (uint64_t)md->m_GlobalIndexBufferIdx + 3ull * tri;
+    if (base + 3u > a.numIndices) return false;
+    F3 v[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint64_t vi = (uint64_t)md->m_GlobalVertexBufferIdx + a.indices[base + k];
+        if (vi >= a.numVertices) return false;
+        v[k] = vertexOf(a, vi);
+    }
+    return triHit(v[0], v[1], v[2], r, tmin, tmax);
+}
+
+__device__ bool occluded(const TraceArgs& a, F3 o, F3 d, float tmin, float tmax)                    // tests/shadowmask_ref.c: occluded_walk
+{
+    const Ray wr = makeRay(o, d);
+    uint32_t node = 0;
+    while (node < a.numTlasNodes) {
+        const trhip_accel_node n = a.tlasNodes[node];
+        uint32_t next = n.skip > node ? n.skip : a.numTlasNodes;
+        if (boxHit(n, wr)) {
+            if (n.leaf == kAccelInner) next = node + 1;
+            else if (n.leaf < a.numInstances) {
+                const uint32_t inst = n.leaf, flags = a.tlasInstances[inst].flags, mesh = a.instances[inst].m_MeshDataIdx;
+                if (flags && mesh < a.numMeshes) {
+                    const trhip_blas_header hd = a.headers[mesh];
+                    const MeshData* md = reinterpret_cast<const MeshData*>(a.meshes + (uint64_t)mesh * sizeof(MeshData));
+                    M34 M;
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) M.m[j] = a.tlasInstances[inst].object_from_world[j];
+                    const Ray r = makeRay(mulPoint(o, M, true), mulPoint(d, M, false));
+                    const uint32_t count = (uint64_t)hd.node_offset + hd.num_nodes <= a.numBlasNodes ? hd.num_nodes : 0u;
+                    uint32_t b = 0;
+                    while (b < count) {
+                        const trhip_accel_node bn = a.blasNodes[hd.node_offset + b];
+                        uint32_t bnext = bn.skip > b ? bn.skip : count;
+                        if (boxHit(bn, r)) {
+                            if (bn.leaf == kAccelInner) bnext = b + 1;
+                            else {
+                                const uint32_t first = bn.leaf & 0x3FFFFFFFu, cnt = (bn.leaf >> 30) + 1u;
+                                for (uint32_t j = 0; j < cnt; ++j) {
+                                    const uint64_t slot = (uint64_t)hd.tri_offset + first + j;
+                                    if (first + j >= hd.num_tris || slot >= a.numTriOrder) break;
+                                    if (meshTriHit(a, md, a.triOrder[slot], r, tmin, tmax) && commits(a, inst, flags)) return true;
+                                }
+                            }
+                        }
+                        b = bnext;
+                    }
+                }
+            }
+        }
+        node = next;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(kTileSide * kTileSide) void shadowMaskKernel(TraceArgs a)
+{
+    const ShadowMaskConsts& k = a.k;
+    const uint32_t W = k.m_OutputResolution.x, H = k.m_OutputResolution.y;
+    const uint32_t px = blockIdx.x * kTileSide + threadIdx.x, py = blockIdx.y * kTileSide + threadIdx.y;
+    if (px >= W || py >= H) return;
+    const uint64_t i = (uint64_t)py * W + px;
+    const float depth = a.depth[i];
+    if (depth == 0.0f) { a.lvd[i] = 0x7BFFu; return; }                                             // kFarDepth: u1 = kFP16Max, u0 untouched
+    const float u = cm::div_((float)px + 0.5f, (float)W), v = cm::div_((float)py + 0.5f, (float)H);
+    const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;                                      // UVToClipXY
+    float h[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        h[j] = cm::fma_(depth, k.m_ClipToWorld.m[2][j], cm::fma_(cy, k.m_ClipToWorld.m[1][j], cx * k.m_ClipToWorld.m[0][j])) + k.m_ClipToWorld.m[3][j];
+    const F3 wp = { cm::div_(h[0], h[3]), cm::div_(h[1], h[3]), cm::div_(h[2], h[3]) };
+    const F3 n = gbuf::unpackGBuffer(a.gbufferA[i]).normal;
+    const uint32_t texel = a.noise[(py % kBlueNoiseSize) * kBlueNoiseSize + (px % kBlueNoiseSize)];
+    const float sx = fmod1(cm::div_((float)(texel & 0xFFu), 255.0f) + k.m_NoisePhase), sy = fmod1(cm::div_((float)((texel >> 8) & 0xFFu), 255.0f) + k.m_NoisePhase);
+    const F3 light = { k.m_DirectionalLightDirection[0], k.m_DirectionalLightDirection[1], k.m_DirectionalLightDirection[2] };
+    const F3 d = gbuf::normalize_(mapToCone(sx, sy, light, k.m_TanSunAngularRadius));
+    const F3 o = { wp.x + n.x * k.m_RayStartOffset, wp.y + n.y * k.m_RayStartOffset, wp.z + n.z * k.m_RayStartOffset };
+    const bool occ = occluded(a, o, d, k.m_RayStartOffset, 1e10f);
+    a.mask[i] = occ ? 0u : 255u;
+    const F3 toCamera = { wp.x - k.m_CameraPosition[0], wp.y - k.m_CameraPosition[1], wp.z - k.m_CameraPosition[2] };
+    const float len = cm::sqrt_(cm::dot3(toCamera, toCamera));
+    a.lvd[i] = len != len ? (uint16_t)0x7E00u : __builtin_bit_cast(uint16_t, (_Float16)len);
+}
+
+int recordShadowMask(trhip::DispatchCtx& ctx)
+{
+    const char* name = ctx.shaderName;
+    const ShadowMaskConsts* k = (const ShadowMaskConsts*)ctx.constants(0, sizeof(ShadowMaskConsts));
+    TRHIP_REQUIRE(k, "%s: constant buffer b0 (ShadowMaskConsts, 112 bytes) missing or short", name);
+    TRHIP_REQUIRE(!k->m_bDoDenoising, "%s: m_bDoDenoising is set: the SIGMA denoiser and its penumbra packing are not built", name);
+    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 8x8-pixel groups", name);
+    const uint32_t W = k->m_OutputResolution.x, H = k->m_OutputResolution.y;
+    TRHIP_REQUIRE(W && H, "%s: m_OutputResolution %ux%u is empty", name, W, H);
+    TRHIP_REQUIRE((uint64_t)ctx.gx * kTileSide >= W && (uint64_t)ctx.gy * kTileSide >= H, "%s: a direct dispatch of 8x8-pixel groups covering %ux%u", name, W, H);
+    struct WantTex { uint32_t type, slot, format; const char* what; };
+    const WantTex wantTex[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R32_FLOAT, "Texture_SRV t0 = the R32_FLOAT depth buffer" },
+                                { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t2 = the RGBA32_UINT GBufferA" },
+                                { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R8_UNORM, "Texture_UAV u0 = the R8_UNORM shadow mask" },
+                                { TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R16_FLOAT, "Texture_UAV u1 = the R16_FLOAT linear view depth" } };
+    trhip_texture_t* tex[4] = {};
+    for (int j = 0; j < 4; ++j) {
+        uint32_t mip = 0;
+        trhip_texture_t* t = ctx.texture(wantTex[j].type, wantTex[j].slot, &mip);
+        TRHIP_REQUIRE(t && t->format == wantTex[j].format && mip == 0 && t->mips == 1, "%s: needs %s (one mip)", name, wantTex[j].what);
+        TRHIP_REQUIRE(t->width == W && t->height == H, "%s: %s is %ux%u, m_OutputResolution is %ux%u", name, wantTex[j].what, t->width, t->height, W, H);
+        tex[j] = t;
+    }
+    uint32_t noiseMip = 0;
+    trhip_texture_t* noise = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 8, &noiseMip);
+    TRHIP_REQUIRE(noise && noise->format == TRHIP_FORMAT_RGBA8_UNORM && noise->width == kBlueNoiseSize && noise->height == kBlueNoiseSize && noiseMip == 0 && noise->mips == 1,
+                  "%s: needs Texture_SRV t8 = the RGBA8_UNORM 128x128 blue noise", name);
+    struct WantBuf { uint32_t slot, stride; const char* what; };
+    const WantBuf wantBuf[] = { { 1, sizeof(trhip_accel_node), "t1 = the TLAS nodes" }, { 3, sizeof(BasePassInstanceConstants), "t3 = the instances" },
+                                { 4, sizeof(RawVertexFormat), "t4 = the vertices" }, { 5, sizeof(MaterialData), "t5 = the materials" }, { 6, 4, "t6 = the indices" },
+                                { 7, sizeof(MeshData), "t7 = the mesh data" }, { 9, sizeof(trhip_tlas_instance), "t9 = the TLAS instances" },
+                                { 10, sizeof(trhip_blas_header), "t10 = the BLAS headers" }, { 11, sizeof(trhip_accel_node), "t11 = the BLAS nodes" },
+                                { 12, 4, "t12 = the triangle order" } };
+    trhip_buffer_t* buf[10] = {};
+    uint32_t count[10] = {};
+    for (int j = 0; j < 10; ++j) {
+        buf[j] = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, wantBuf[j].slot);
+        TRHIP_REQUIRE(buf[j], "%s: needs StructuredBuffer_SRV %s", name, wantBuf[j].what);
+        const uint64_t c = buf[j]->byteSize / wantBuf[j].stride;
+        count[j] = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
+    }
+    TraceArgs a;
+    memset(&a, 0, sizeof a);
+    a.k = *k;
+    a.depth = (const float*)tex[0]->ptr; a.gbufferA = (const uint4*)tex[1]->ptr; a.mask = (uint8_t*)tex[2]->ptr; a.lvd = (uint16_t*)tex[3]->ptr;
+    a.noise = (const uint32_t*)noise->ptr;
+    a.tlasNodes = (const trhip_accel_node*)buf[0]->ptr; a.numTlasNodes = count[0];
+    a.instances = (const BasePassInstanceConstants*)buf[1]->ptr; a.numInstances = count[1] < count[6] ? count[1] : count[6];
+    a.vertices = (const uint8_t*)buf[2]->ptr; a.numVertices = count[2];
+    a.materials = (const uint8_t*)buf[3]->ptr; a.numMaterials = count[3];
+    a.indices = (const uint32_t*)buf[4]->ptr; a.numIndices = count[4];
+    a.meshes = (const uint8_t*)buf[5]->ptr; a.numMeshes = count[5] < count[7] ? count[5] : count[7];
+    a.tlasInstances = (const trhip_tlas_instance*)buf[6]->ptr;
+    a.headers = (const trhip_blas_header*)buf[7]->ptr;
+    a.blasNodes = (const trhip_accel_node*)buf[8]->ptr; a.numBlasNodes = count[8];
+    a.triOrder = (const uint32_t*)buf[9]->ptr; a.numTriOrder = count[9];
+    const dim3 grid((W + kTileSide - 1) / kTileSide, (H + kTileSide - 1) / kTileSide);
+    ctx.emit("main", [a, grid](hipStream_t s) {
+        TRHIP_LAUNCH(shadowMaskKernel, grid, dim3(kTileSide, kTileSide), 0, s, a);
+        return trhip::launchStatus("shadowMaskKernel"); });
+    return TRHIP_OK;
+}
+
+trhip::ShaderRegistrar r0("shadowmask_CS_ShadowMask", recordShadowMask, 0);
+trhip::ShaderRegistrar r1("raytracing_CS_RefitTLAS", recordRefit, 0);
+
+} // namespace

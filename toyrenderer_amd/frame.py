@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import accel as accelmod
 from . import gtao as gtaomod
 from . import interop as I
 from . import rhi
@@ -51,6 +52,7 @@ class GpuScene:
         self.numOpaque, self.numAlphaMask = len(opaqueIds), len(alphaMaskIds)
         self.vertices = self.meshletVertexIds = self.meshletTriangles = None
         self.materials = None
+        self.indices = self.rt = None
 
     def set_geometry(self, vertices, meshletVertexIds, meshletTriangles):
         """The buffers the mesh shader reads (basepass.hlsl t1, t5, t6): lets the frame rasterise its own depth
@@ -70,7 +72,45 @@ class GpuScene:
         self.materials = self.dev.buffer_from(materials, "GlobalMaterialDataBuffer", uav=False, min_bytes=124)
         self.numMaterials = len(materials)
 
+    def set_raytracing(self, indices, meshSpecific):
+        """The acceleration structure FrameDriver(shadows=...) traces (include/trhip.h, "acceleration structure"): `indices` is the
+        global index buffer (Graphic::m_GlobalIndexBuffer; each mesh's LOD-0 list at m_GlobalIndexBufferIdx, relative to its first
+        vertex), `meshSpecific` the MeshSpecificData table (cached_scene) or one index count per mesh.  Needs set_geometry() and
+        set_materials().  The BLAS of every mesh is built here, once, by the back end's builder; the TLAS topology comes from the
+        instance buffer's current m_WorldMatrix (the rest transforms) and the two instance lists (opaque: ForceOpaque, alpha mask:
+        ForceNonOpaque); its boxes and matrices are refit on the GPU by every recorded frame.  self.rt holds the buffers and the
+        host copies ("blas", "tlas", "flags")."""
+        if self.vertices is None or self.materials is None:
+            raise ValueError("set_raytracing needs GpuScene.set_geometry() and set_materials()")
+        dev = self.dev
+        vertices = self.vertices.download(I.RawVertexFormat, self.vertices.size // I.RawVertexFormat.itemsize)
+        mesh_data = self.meshData.download(I.MeshData, self.meshData.size // I.MeshData.itemsize)
+        instances = self.instances.download(I.BasePassInstanceConstants, self.numInstances)
+        indices = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        blas = accelmod.build_scene_blas(vertices, indices, mesh_data, meshSpecific)
+        flags = accelmod.instance_flags(self.numInstances, self.opaqueIds.download(np.uint32, self.numOpaque), self.alphaMaskIds.download(np.uint32, self.numAlphaMask))
+        tlas = accelmod.build_tlas(instances, flags, blas)
+        self.release_raytracing()
+        self.indices = dev.buffer_from(indices, "GlobalIndexBuffer", uav=False)
+        self.rt = dict(blas=blas, tlas=tlas, flags=flags,
+                       headers=dev.buffer_from(blas["headers"], "BLAS Headers", uav=False, min_bytes=16),
+                       blas_nodes=dev.buffer_from(blas["nodes"], "BLAS Nodes", uav=False, min_bytes=32),
+                       tri_order=dev.buffer_from(blas["tri_order"], "BLAS Triangle Order", uav=False),
+                       tlas_nodes=dev.buffer_from(tlas["nodes"], "TLAS Nodes", min_bytes=32),
+                       tlas_instances=dev.buffer_from(tlas["records"], "TLAS Instances", min_bytes=64),
+                       level_nodes=dev.buffer_from(tlas["level_nodes"], "TLAS Level Nodes", uav=False),
+                       level_offsets=dev.buffer_from(tlas["level_offsets"], "TLAS Level Offsets", uav=False))
+
+    def release_raytracing(self):
+        if self.rt is not None:
+            for b in self.rt.values():
+                if isinstance(b, rhi.Buffer):
+                    b.release()
+            self.indices.release()
+        self.indices = self.rt = None
+
     def release(self):
+        self.release_raytracing()
         for b in (self.instances, self.meshData, self.meshlets, self.opaqueIds, self.alphaMaskIds, self.vertices, self.meshletVertexIds, self.meshletTriangles,
                   self.materials):
             if b is not None:
@@ -85,7 +125,8 @@ class FrameDriver:
                  shard_late=None, raster_depth: bool = False, visibility: bool = False, gbuffer: bool = False,
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
-                 bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None):
+                 bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
+                 shadows=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -137,7 +178,18 @@ class FrameDriver:
         t3 and m_SSAOEnabled is 1; only debug view 9 shows it (the non-debug pass multiplies the DDGI ambient term by it, and that
         term is not built), so LightingOutput without a debug view does not change.  self.frame_counter (0; the caller may set it
         before record()) feeds NoiseIndex as g_Graphic.m_FrameCounter % 256 does; self.gtao_consts holds the 96-byte GTAOConstants
-        of the last record(); download_ssao() reads self.ssao_texture back."""
+        of the last record(); download_ssao() reads self.ssao_texture back.
+        shadows: None (the default) changes nothing.  A dict of settings: soft (True), sun_angular_diameter (0.533 degrees),
+        ray_start_offset (0.1; the reference picks 0.01 when the scene's bounding radius is below 3, else 0.1: the caller knows the
+        scene) and noise, the 128 x 128 x 4 uint8 blue noise image (required; an input as the Hosek dataset is).  Needs gbuffer=True
+        (which lighting implies) and GpuScene.set_raytracing(); not together with an external shadow_mask=: ShadowMaskRenderer::
+        TraceShadows without denoising (ShadowMaskRenderer.cpp:253-305).  The driver owns self.shadow_mask_texture (R8_UNORM) and
+        self.linear_view_depth (R16_FLOAT); behind the G-buffer resolve (and the AO passes), in front of the lighting dispatch, it
+        records "raytracing_CS_RefitTLAS" (the stand-in of the TLAS build behind updateinstanceconsts: the instance buffer's current
+        matrices) and "shadowmask_CS_ShadowMask", and binds the mask as the lighting pass's t4.  The light direction is dir_light[0]
+        as given, the camera position camera_origin, m_NoisePhase (self.frame_counter & 0xff) * 1.61803398875f, m_TanSunAngularRadius
+        tan(radians(d / 2)) evaluated in double and rounded once (0 without soft).  self.shadow_consts holds the 112-byte
+        ShadowMaskConsts of the last record(); download_shadow_mask() reads the mask back."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -189,6 +241,15 @@ class FrameDriver:
             if ssao is not None:
                 raise ValueError("ao=... together with an external ssao= texture: the driver generates the texture itself")
             self.ao = gtaomod.check_settings(ao)
+        self.shadows = self.shadow_consts = None
+        if shadows is not None:
+            if not gbuffer:
+                raise ValueError("shadows=... needs gbuffer=True (or lighting=True): the rays start at the G-buffer's positions and normals")
+            if shadow_mask is not None:
+                raise ValueError("shadows=... together with an external shadow_mask= texture: the driver generates the texture itself")
+            if scene.rt is None:
+                raise ValueError("shadows=... needs GpuScene.set_raytracing(): the acceleration structure the rays walk")
+            self.shadows = accelmod.check_settings(shadows)
         self.dir_light = (tuple(float(x) for x in dir_light[0]), float(dir_light[1]))
         self.camera_origin = tuple(float(x) for x in camera_origin)
         self.shadow_mask, self.ssao = shadow_mask, ssao
@@ -232,6 +293,13 @@ class FrameDriver:
             self.ao_working = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R8_UINT, "Working SSAO Texture")
             self.ao_edges = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R8_UNORM, "Working Edges Texture")
             self.ssao = self.ssao_texture            # what the lighting pass binds as t3
+        self.shadow_mask_texture = self.linear_view_depth = self.blue_noise = None
+        if self.shadows is not None:                 # ShadowMaskRenderer::Setup (ShadowMaskRenderer.cpp:187-251) + CommonResources::BlueNoise
+            self.shadow_mask_texture = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R8_UNORM, "Shadow Mask Texture")
+            self.linear_view_depth = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R16_FLOAT, "Linear View Depth")
+            self.blue_noise = dev.create_texture(I.kBlueNoiseSize, I.kBlueNoiseSize, 1, rhi.FORMAT_RGBA8_UNORM, "Blue Noise", uav=False)
+            self.blue_noise.upload_mip(0, accelmod.noise_words(self.shadows["noise"]))
+            self.shadow_mask = self.shadow_mask_texture      # what the lighting pass binds as t4
         if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
@@ -428,6 +496,31 @@ class FrameDriver:
         self.dev.wait_idle()
         return self.ssao_texture.download_mip(0)
 
+    # ---- the TLAS refit (BasePassRenderers.cpp:159-160) + ShadowMaskRenderer::TraceShadows (ShadowMaskRenderer.cpp:253-305) ---------
+    def _shadow_mask(self, cl):
+        v, sc, W, H = self.view, self.scene, self.view.renderW, self.view.renderH
+        rt = sc.rt
+        k = np.zeros(1, I.RefitTLASConstants)
+        k["m_NumInstances"], k["m_NumNodes"], k["m_NumLevels"] = sc.numInstances, len(rt["tlas"]["nodes"]), rt["tlas"]["num_levels"]
+        cl.dispatch("raytracing_CS_RefitTLAS",
+                    [PUSH(0), SRV(0, sc.instances), SRV(1, rt["headers"]), SRV(2, rt["blas_nodes"]), SRV(3, rt["level_offsets"]), SRV(4, rt["level_nodes"]),
+                     UAV(0, rt["tlas_nodes"]), UAV(1, rt["tlas_instances"])], (max((sc.numInstances + 63) // 64, 1), 1, 1), push=k)
+        self.shadow_consts = accelmod.shadow_consts(I.clip_to_world(v.worldToView, v.viewToClip), self.dir_light[0], self.camera_origin, W, H, self.shadows,
+                                                    self.frame_counter)
+        cb = cl.constant_buffer(self.shadow_consts, "ShadowMaskConsts")
+        cl.dispatch("shadowmask_CS_ShadowMask",
+                    [CB(0, cb), TEX_SRV(0, self.depth), SRV(1, rt["tlas_nodes"]), TEX_SRV(2, self.gbufferA), SRV(3, sc.instances), SRV(4, sc.vertices),
+                     SRV(5, sc.materials), SRV(6, sc.indices), SRV(7, sc.meshData), TEX_SRV(8, self.blue_noise), TEX_UAV(0, self.shadow_mask_texture, 0),
+                     TEX_UAV(1, self.linear_view_depth, 0), SRV(9, rt["tlas_instances"]), SRV(10, rt["headers"]), SRV(11, rt["blas_nodes"]),
+                     SRV(12, rt["tri_order"]), SAMPLER(0), SAMPLER(1)], ((W + 7) // 8, (H + 7) // 8, 1))
+
+    def download_shadow_mask(self) -> np.ndarray:
+        """The bytes of the generated shadow mask, (H, W) uint8."""
+        if self.shadow_mask_texture is None:
+            raise ValueError("download_shadow_mask: shadow generation is off (shadows=None)")
+        self.dev.wait_idle()
+        return self.shadow_mask_texture.download_mip(0)
+
     # ---- SkyRenderer::Render (SkyRenderer.cpp:163-208) -------------------------------------------------------------------
     def _sky(self, cl):
         v = self.view
@@ -567,6 +660,8 @@ class FrameDriver:
             cl.end_pipeline_stats(query)
         if self.ao is not None:                                                          # Scene.cpp's order: behind GBufferRenderer, in front of lighting
             self._ambient_occlusion(cl)
+        if self.shadows is not None:                                                     # Scene.cpp:500: behind AO, in front of lighting
+            self._shadow_mask(cl)
         if self.lighting_on:
             self._deferred_lighting(cl)
         if self.sky is not None:                                                         # Scene.cpp:502: between lighting and bloom
@@ -610,6 +705,7 @@ class FrameDriver:
             b.release()
         self.hzb.release(); self.depth.release()
         for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
-                  self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture):
+                  self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
+                  self.blue_noise):
             if t is not None:
                 t.release()

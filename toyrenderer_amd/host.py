@@ -35,6 +35,7 @@ HOST_SYMBOLS = [
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
     "trhost_load_sky_dataset", "trhost_set_sky", "trhost_get_sky_consts",
     "trhost_set_ambient_occlusion", "trhost_download_ssao", "trhost_get_gtao_consts",
+    "trhost_load_raytracing", "trhost_upload_blue_noise", "trhost_set_shadow_mask", "trhost_download_shadow_mask", "trhost_get_shadow_mask_consts",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # trhost_allgather_fn
@@ -116,6 +117,11 @@ def load() -> C.CDLL:
     L.trhost_set_ambient_occlusion.argtypes = [C.c_int, u32, u32, C.c_float, C.c_float, C.c_float, C.c_float]
     L.trhost_download_ssao.argtypes = [vp, u64]
     L.trhost_get_gtao_consts.argtypes = [vp]
+    L.trhost_load_raytracing.argtypes = [vp, u64, vp, u32]
+    L.trhost_upload_blue_noise.argtypes = [vp, u64]
+    L.trhost_set_shadow_mask.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float]
+    L.trhost_download_shadow_mask.argtypes = [vp, u64]
+    L.trhost_get_shadow_mask_consts.argtypes = [vp]
     L.trhost_get_scene_luminance.argtypes = [vp, vp]
     L.trhost_reset_exposure.argtypes = []
     L.trhost_get_post_process_consts.argtypes = [vp, vp, vp, vp]
@@ -393,6 +399,35 @@ class Renderer:
         """The GTAOConstants of the last frame; raises if the pass did not run in it."""
         k = np.zeros(1, I.GTAOConstants)
         _check(load().trhost_get_gtao_consts(k.ctypes.data))
+        return k
+
+    def load_raytracing(self, indices, mesh_specific):
+        """The acceleration structure of the ray-traced shadows: the global index buffer and the MeshSpecificData table (or one
+        index count per mesh).  After load_scene, load_geometry and load_materials."""
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        counts = np.asarray(mesh_specific)
+        counts = np.ascontiguousarray(counts["m_NumIndices"] if counts.dtype.names else counts, np.uint32)
+        _check(load().trhost_load_raytracing(idx.ctypes.data, len(idx), counts.ctypes.data, len(counts)))
+
+    def upload_blue_noise(self, noise):
+        n = np.ascontiguousarray(noise, np.uint8)
+        _check(load().trhost_upload_blue_noise(n.ctypes.data, n.nbytes))
+
+    def set_shadow_mask(self, enable: bool, soft: bool = True, sun_angular_diameter: float = 0.533, ray_start_offset: float = 0.1):
+        """ShadowMaskRenderer on or off (needs the G-buffer, load_raytracing and upload_blue_noise; not with an uploaded shadow mask)."""
+        _check(load().trhost_set_shadow_mask(int(bool(enable)), int(bool(soft)), float(sun_angular_diameter), float(ray_start_offset)))
+
+    def download_shadow_mask(self) -> np.ndarray:
+        """The last frame's shadow mask: uint8 [H, W]; raises if the pass did not run in it."""
+        self.wait_idle()
+        b = np.empty((self.render[1], self.render[0]), np.uint8)
+        _check(load().trhost_download_shadow_mask(b.ctypes.data, b.nbytes))
+        return b
+
+    def shadow_mask_consts(self) -> np.ndarray:
+        """The ShadowMaskConsts of the last frame; raises if the pass did not run in it."""
+        k = np.zeros(1, I.ShadowMaskConsts)
+        _check(load().trhost_get_shadow_mask_consts(k.ctypes.data))
         return k
 
     def bloom_consts(self, passes: int) -> np.ndarray:

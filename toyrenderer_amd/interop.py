@@ -96,6 +96,19 @@ GTAOConstants = np.dtype([                                                      
     ("NoiseIndex", np.int32)])
 XeGTAOMainPassConstantBuffer = np.dtype([("m_WorldToViewNoTranslate", np.float32, (4, 4)), ("m_Quality", np.uint32)])          # ShaderInterop.h:322-326
 XeGTAODenoiseConstants = np.dtype([("m_FinalApply", np.uint32)])                                                             # ShaderInterop.h:328-331
+ShadowMaskConsts = np.dtype([                                                                                              # ShaderInterop.h:285-295
+    ("m_ClipToWorld", np.float32, (4, 4)), ("m_DirectionalLightDirection", np.float32, (3,)), ("m_NoisePhase", np.float32),
+    ("m_CameraPosition", np.float32, (3,)), ("m_TanSunAngularRadius", np.float32), ("m_OutputResolution", np.uint32, (2,)),
+    ("m_bDoDenoising", np.uint32), ("m_RayStartOffset", np.float32)])
+# this build's acceleration structure (include/trhip.h, "acceleration structure")
+RefitTLASConstants = np.dtype([("m_NumInstances", np.uint32), ("m_NumNodes", np.uint32), ("m_NumLevels", np.uint32)])
+AccelNode = np.dtype([("lo", np.float32, (3,)), ("skip", np.uint32), ("hi", np.float32, (3,)), ("leaf", np.uint32)])
+BLASHeader = np.dtype([("node_offset", np.uint32), ("num_nodes", np.uint32), ("tri_offset", np.uint32), ("num_tris", np.uint32)])
+TLASInstance = np.dtype([("object_from_world", np.float32, (4, 3)), ("flags", np.uint32), ("leaf_node", np.uint32), ("reserved", np.uint32, (2,))])
+kAccelInner = 0xFFFFFFFF
+kTLASInstanceForceOpaque, kTLASInstanceForceNonOpaque = 1, 2
+kBlueNoiseSize = 128
+kDeferredLightingDebugMode_ShadowMask = 11
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
@@ -105,6 +118,7 @@ SIZES = {
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
     "BloomConsts": 16, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
     "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
+    "ShadowMaskConsts": 112, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)

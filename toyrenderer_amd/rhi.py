@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "trhip_cmd_end_pipeline_stats", "trhip_pipeline_stats_get",
     "trhip_profile_enable", "trhip_profile_filter", "trhip_profile_reset", "trhip_profile_count", "trhip_profile_entry",
     "trhip_launch_shard_late_info",
+    "trhip_accel_max_depth", "trhip_blas_leaf_capacity", "trhip_accel_max_nodes", "trhip_blas_build", "trhip_tlas_build",
     "trhip_stream_create", "trhip_stream_create_priority", "trhip_stream_destroy", "trhip_stream_synchronize", "trhip_event_create", "trhip_event_destroy",
     "trhip_event_record", "trhip_stream_wait_event",
 ]
@@ -185,6 +186,12 @@ def load() -> C.CDLL:
     L.trhip_texture_mark_written.argtypes = [vp]
     L.trhip_profile_count.argtypes = [vp, C.POINTER(u32)]
     L.trhip_profile_entry.argtypes = [vp, u32, C.POINTER(C.c_char_p), C.POINTER(u64), C.POINTER(C.c_double)]
+    for n in ("trhip_accel_max_depth", "trhip_blas_leaf_capacity", "trhip_accel_max_nodes"):
+        getattr(L, n).restype = u32
+    L.trhip_accel_max_nodes.argtypes = [u32]
+    pu32 = C.POINTER(u32)
+    L.trhip_blas_build.argtypes = [vp, u32, u32, vp, u32, vp, u32, vp, pu32, pu32, pu32]
+    L.trhip_tlas_build.argtypes = [vp, u32, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, pu32, pu32]
     _lib = L
     return L
 
