@@ -33,6 +33,7 @@ typedef struct trhip_texture_t* trhip_texture;
 typedef struct trhip_cmdlist_t* trhip_cmdlist;
 typedef struct trhip_timer_t*   trhip_timer;
 typedef struct trhip_pipeline_stats_t* trhip_pipeline_stats;
+typedef struct trhip_texture_table_t* trhip_texture_table;
 
 enum {
     TRHIP_OK = 0,
@@ -52,10 +53,14 @@ enum {
  * unsigned floats of 5 exponent bits with 6, 6 and 5 mantissa bits), R8_UNORM (the shadow mask) and R8_UINT (the SSAO texture),
  * one byte per texel each.  RGBA8_UNORM (the back buffer, GraphicRHI.cpp:214: 4 bytes per texel, R in the low byte, one mip) is
  * created, uploaded, downloaded and copied; both clears refuse it, because "postprocess_PS_PostProcess" writes every texel.
- * Its value is 10, not 9: 9 is not a format and stays refused with "unsupported format". */
+ * Its value is 10, not 9: 9 is not a format and stays refused with "unsupported format".
+ * SRGBA8_UNORM (11) has RGBA8_UNORM's layout; a sampling pass decodes R, G and B through the sRGB transfer function before
+ * filtering (trhip_srgb_table), alpha stays linear.  An RGBA8_UNORM or SRGBA8_UNORM texture created WITHOUT the UAV and
+ * render-target bits (isUAV == 0: a material texture, sampled only) may have a mip chain, uploaded per mip through
+ * trhip_texture_upload; one that a pass writes keeps one mip. */
 enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4,
        TRHIP_FORMAT_RGBA32_UINT = 5, TRHIP_FORMAT_R11G11B10_FLOAT = 6, TRHIP_FORMAT_R8_UNORM = 7, TRHIP_FORMAT_R8_UINT = 8,
-       TRHIP_FORMAT_RGBA8_UNORM = 10 };
+       TRHIP_FORMAT_RGBA8_UNORM = 10, TRHIP_FORMAT_SRGBA8_UNORM = 11 };
 
 /* ---- error / introspection ---------------------------------------------------------------- */
 const char* trhip_last_error(void);          /* thread-local text of the last failure          */
@@ -83,6 +88,18 @@ uint32_t    trhip_abi_version(void);
  * Per pixel with a nonzero texel: u0 = PackGBuffer(albedo + debug byte by m_DebugMode 2 / 3 / 12, interpolated vertex
  * normal, emissive, roughness 1, metallic 0), u1 = the words "basepass_PS_Main_motion" writes.  A pixel whose chain of
  * indices leaves a bound buffer (m_MaterialDataIdx included) is left as it is in both targets.
+ * With a texture table bound at t19 (TRHIP_BIND_TEXTURE_TABLE, the stand-in of ResourceDescriptorHeap[...]; optional) the same
+ * shader name records the TEXTURED kernel ("basepass_PS_Main_GBuffer#textured" in the profile, "#main" without a table): all
+ * 124 bytes of MaterialData are read, and each slot flagged in m_MaterialFlags (albedo, normal, metallic-roughness, emissive) is
+ * sampled through its m_DescriptorIndex with the 16x anisotropic wrap or clamp sampler (m_IsWrapSampler) in software:
+ * GetCommonGBufferParams (lightingcommon.hlsli:435-493) with derivatives from the triangle's plane, tangent-free normal mapping,
+ * u0.w = PackRGBA8(roughness, metallic, 0, 0).  The convention is stated in csrc/material_textures.hip.h and
+ * csrc/visibility_resolve.hip.h.  A flagged slot whose descriptor index is at or past the table's capacity, names an empty entry
+ * or an entry of a format other than RGBA8_UNORM / SRGBA8_UNORM leaves the pixel as it is in both targets.  Refused at record
+ * time: a table that holds a texture created with the UAV or render-target bit.
+ * That check covers the table's contents when the dispatch is recorded: trhip_texture_table_set rewrites an entry in place, so a
+ * UAV-capable texture set AFTERWARDS is sampled by the lists already recorded (read only; nothing is written through the table)
+ * and is refused by the next recording.  A texture table bound to any other shader, or at another slot, is refused.
  * "deferredlighting_PS_Main" and "deferredlighting_PS_Main_Debug" (deferredlighting.hlsl, DeferredLightingRenderer.cpp: the
  * directional light and the debug views, without DDGI): a direct dispatch of [numthreads(8, 8, 1)] groups over the screen;
  * b0 DeferredLightingConsts (112 bytes; m_bRTDDGIEnabled must be 0, m_DebugMode must not be 10), t0 (texture) RGBA32_UINT
@@ -200,6 +217,23 @@ int  trhip_buffer_download(trhip_buffer buf, uint64_t src_offset, void* dst, uin
 int  trhip_texture_upload(trhip_texture tex, uint32_t mip, const void* src, uint64_t bytes);
 int  trhip_texture_download(trhip_texture tex, uint32_t mip, void* dst, uint64_t bytes);
 
+/* ---- texture table: the stand-in of the bindless ResourceDescriptorHeap[descriptorIndex] (lightingcommon.hlsli:345) --------
+ * A device object of `capacity` entries; entry i maps descriptor index i to a texture's base pointer, width, height, mip count,
+ * format and per-mip offsets.  set / clear rewrite one entry synchronously (they wait for the device first, like the uploads); the
+ * table retains the textures it names until they are replaced, cleared or the table is released.  A texture of any format may
+ * be set (the shader that indexes the table decides what it can sample); it needs memory bound, and an entry is NOT refreshed by
+ * a later trhip_texture_bind_memory: set it again.  Bound as TRHIP_BIND_TEXTURE_TABLE; a command list retains the table. */
+int  trhip_texture_table_create(trhip_device dev, uint32_t capacity, trhip_texture_table* out);
+void trhip_texture_table_retain(trhip_texture_table table);
+void trhip_texture_table_release(trhip_texture_table table);
+uint32_t trhip_texture_table_capacity(trhip_texture_table table);
+int  trhip_texture_table_set(trhip_texture_table table, uint32_t index, trhip_texture tex);
+int  trhip_texture_table_clear(trhip_texture_table table, uint32_t index);
+/* The 256-entry sRGB-to-linear table of SRGBA8_UNORM (no device needed): out[i] = the sRGB transfer function of i / 255 evaluated
+ * in double precision (c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4)), rounded once to float.  The device keeps a
+ * copy from its first texture table on. */
+int  trhip_srgb_table(float* out);
+
 /* Contents changed behind the back end's back.  The back end keeps derived, private copies of some bound resources (the
  * instance cull cache, the meshlet cull stream of the buffer bound at t4 of basepass_AS_Main and, once a pipeline statistics
  * query has covered that pass, its triangle-count bytes, an HZB's footprint-min table)
@@ -220,14 +254,17 @@ typedef enum {
     TRHIP_BIND_STRUCTURED_UAV  = 3,  /* ::StructuredBuffer_UAV(slot, buf)   register(uN)        */
     TRHIP_BIND_TEXTURE_SRV     = 4,  /* ::Texture_SRV(slot, tex)            register(tN)        */
     TRHIP_BIND_TEXTURE_UAV     = 5,  /* ::Texture_UAV(slot, tex, fmt, {baseMip,1,0,1}) (uN)     */
-    TRHIP_BIND_SAMPLER         = 6   /* ::Sampler(slot, s): accepted and ignored (sampling is
+    TRHIP_BIND_SAMPLER         = 6,  /* ::Sampler(slot, s): accepted and ignored (sampling is
                                         done in software, see DESIGN.md "HZB sampling")         */
+    TRHIP_BIND_TEXTURE_TABLE   = 7   /* a trhip_texture_table at register(tN): what the shader
+                                        indexes as ResourceDescriptorHeap[...]; t19 of
+                                        "basepass_PS_Main_GBuffer", the first slot after t18     */
 } trhip_binding_type;
 
 typedef struct {
     uint32_t type;       /* trhip_binding_type                                                  */
     uint32_t slot;
-    void*    resource;   /* trhip_buffer or trhip_texture (NULL for push constants / sampler)   */
+    void*    resource;   /* trhip_buffer, trhip_texture or trhip_texture_table (NULL for push constants / sampler) */
     uint32_t baseMip;    /* Texture_UAV subresource; Texture_SRV: read by bloom_PS_* only       */
     uint32_t reserved;
 } trhip_binding;

@@ -81,9 +81,18 @@ int  trhost_download_motion(uint16_t* halves, uint64_t bytes);
  * GBufferRenderer's GBufferA (RGBA32_UINT: PackGBuffer's x, y, z, w per texel, 16 bytes; 0 = nothing drawn) and GBufferMotion
  * in one dispatch in the place of "basepass_PS_Main_motion".  trhost_load_materials uploads MaterialData[count] (124-byte
  * stride, Graphic::m_GlobalMaterialDataBuffer; BasePassInstanceConstants::m_MaterialDataIdx indexes it) and refuses a material
- * whose m_MaterialFlags names a texture; it comes before trhost_set_gbuffer(1).  trhost_set_debug_view_mode sets
+ * whose m_MaterialFlags names a texture that is not loaded (see trhost_create_material_texture); it comes before trhost_set_gbuffer(1).  trhost_set_debug_view_mode sets
  * Scene::m_DebugViewMode -> m_DebugMode (2 ColorizeInstances, 3 ColorizeMeshlets, 12 MeshLOD fill GBufferA's debug byte). */
 int  trhost_load_materials(const void* materials, uint32_t count);
+/* Textured materials.  trhost_create_material_texture uploads one material texture (format TRHIP_FORMAT_RGBA8_UNORM or
+ * TRHIP_FORMAT_SRGBA8_UNORM; `data`: the mips back to back, level k of max(width >> k, 1) x max(height >> k, 1) texels of 4 bytes
+ * R, G, B, A; `bytes` their sum) and returns its descriptor index (0, 1, ... in call order; -1 and trhost_last_error on failure):
+ * the value a flagged TextureData::m_DescriptorIndex names.  The host owns the texture table (the stand-in of the bindless heap,
+ * 4096 entries) and binds it at t19 of "basepass_PS_Main_GBuffer" whenever a loaded material has a texture flag; the resolve then
+ * samples (include/trhip.h).  trhost_load_materials accepts a textured material when every flagged slot's m_DescriptorIndex names a
+ * texture created before it and its m_FeedbackTextureDescriptorIndex and m_MinMapTextureDescriptorIndex are 0xFFFFFFFF; otherwise
+ * it fails with a message containing "texture".  The textures live until trhost_shutdown. */
+int  trhost_create_material_texture(uint32_t width, uint32_t height, uint32_t mips, uint32_t format, const void* data, uint64_t bytes);
 int  trhost_set_gbuffer(int enable);
 int  trhost_set_debug_view_mode(uint32_t mode);
 int  trhost_download_gbuffer_a(uint32_t* words, uint64_t bytes);

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Cost of textured materials: the fused "basepass_PS_Main_GBuffer" resolve of a generated city at 3840x2160, steady state, from the
+back-end profile, in three modes that alternate `rounds` times (default 3) in one call, each in its own process:
+  plain     texture-free materials, no table bound: "basepass_PS_Main_GBuffer#main" (the kernel of tools/gbuffer_cost.py's mode B);
+  textured  every material with all four textures out of 16 seeded 256 x 256 textures with full mip chains (base colour and
+            emissive sRGB), texture coordinates seeded from the positions (about a texel per pixel in the middle distance, wrap):
+            "basepass_PS_Main_GBuffer#textured";
+  baseline  `plain` with another build of the back end (--baseline-lib=PATH to its libtrhip.so, e.g. the parent commit's): shows
+            whether the texture-free kernel moved.  The margin to judge it by is the baseline's own spread over the rounds.
+usage: python tools/material_texture_cost.py [num_spheres] [width height] [--rounds=N] [--baseline-lib=PATH]"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+from pathlib import Path
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def run(mode: str, n: int, render):
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from scene_gen import write_city_gltf
+    from toyrenderer_amd import gltf_lite, rhi, synth
+    from toyrenderer_amd import interop as I
+    from toyrenderer_amd.frame import FrameDriver, GpuScene
+    with tempfile.TemporaryDirectory() as d:
+        s = gltf_lite.load(write_city_gltf(Path(d), num_spheres=n, num_cutouts=n // 8))
+    inst = s.instances.copy()                       # world matrices on the host: the transform pass is timed elsewhere
+    for i in range(len(inst)):
+        k = int(s.primToNode[i])
+        M = np.eye(4, dtype=np.float64)
+        while k != 0xFFFFFFFF:
+            t = s.nodes[k]
+            L = np.diag(list(t["m_Scale"]) + [1.0]) @ synth.quat_to_matrix(tuple(t["m_Rotation"]))
+            L[3, :3] = t["m_Position"]
+            M = M @ L
+            k = int(t["m_ParentNodeIdx"])
+        inst["m_WorldMatrix"][i] = M.astype(np.float32)
+    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
+    rng = np.random.default_rng(7)
+    inst["m_MaterialDataIdx"] = rng.integers(0, 64, len(inst), dtype=np.uint32)
+    v = s.vertices.copy()                           # the generated city has neither NORMAL nor TEXCOORD_0: seeded
+    v["m_PackedNormal"] = rng.integers(0, 1 << 30, len(v), dtype=np.uint64).astype(np.uint32)
+    v["m_TexCoord"] = (v["m_Position"][:, [0, 2]] * np.float32(2.0) + v["m_Position"][:, [1, 1]]).astype(np.float16).view(np.uint16)
+    dev = rhi.Device(0)
+    gs = GpuScene(dev, inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
+    gs.set_geometry(v, s.meshletVertexIds, s.meshletTriangles)
+    mats = synth.materials(7)
+    if mode == "textured":
+        textures = []
+        for t in range(16):
+            img = rng.integers(0, 256, (256, 256, 4), dtype=np.uint16).astype(np.uint8)
+            if t % 4 == 1:
+                img[..., :2] = 70 + img[..., :2] % 116                                   # a normal map: x, y inside the unit disc
+            textures.append((I.make_mips(img, srgb=t % 4 in (0, 3)), rhi.FORMAT_SRGBA8_UNORM if t % 4 in (0, 3) else rhi.FORMAT_RGBA8_UNORM))
+        gs.set_textures(textures)
+        mats["m_MaterialFlags"] = I.kMaterialFlagAnyTexture
+        for c, slot in enumerate(("m_AlbedoTexture", "m_NormalTexture", "m_MetallicRoughnessTexture", "m_EmissiveTexture")):
+            mats[slot]["m_DescriptorIndex"] = 4 * (np.arange(len(mats)) % 4) + c
+            mats[slot]["m_IsWrapSampler"] = 1
+    gs.set_materials(mats)
+    cam = s.cameras[0]
+    P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
+    V = synth.world_to_view((0.0, 0.0, 0.0), cam.orientation)
+    Vp = synth.world_to_view((-0.05, 0.0, 0.02), cam.orientation)
+    view = synth.View(V, Vp, P, float(np.float32(cam.znear)), *render)
+    drv = FrameDriver(dev, gs, view, record_capacity=1 << 16, culling_flags=7, gbuffer=True)
+    drv.record()
+    for _ in range(5):
+        drv.run()
+    dev.wait_idle()
+    dev.profile_reset(); dev.profile_enable(True)
+    frames = 20
+    for _ in range(frames):
+        drv.run()
+    dev.wait_idle()
+    prof = dev.profile()
+    dev.profile_enable(False)
+    covered = int(np.count_nonzero(drv.visibility.download_mip(0)))
+    print(f"[{mode}] {len(inst)} instances, render {render[0]}x{render[1]}, {frames} frames, {covered} covered pixels, {rhi.LIB_PATH}")
+    for name, (cnt, ms) in sorted(prof.items()):
+        if name.startswith("basepass_PS_Main"):
+            print(f"  {name:45s} {ms / frames * 1e3:9.1f} us per frame ({cnt // frames} launches)")
+    drv.release(); gs.release(); dev.destroy()
+
+
+if __name__ == "__main__":
+    opts = [a for a in sys.argv[1:] if a.startswith("--")]
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    n = int(args[0]) if args else 2000
+    render = (int(args[1]), int(args[2])) if len(args) > 2 else (3840, 2160)
+    mode = next((a.split("=", 1)[1] for a in opts if a.startswith("--mode=")), None)
+    rounds = int(next((a.split("=", 1)[1] for a in opts if a.startswith("--rounds=")), 3))
+    baseline = next((a.split("=", 1)[1] for a in opts if a.startswith("--baseline-lib=")), None)
+    if mode:
+        run(mode, n, render)
+    else:
+        modes = (["baseline"] if baseline else []) + ["plain", "textured"]
+        us = {m: [] for m in modes}
+        for r in range(rounds):
+            for m in modes:
+                env = dict(os.environ, TRHIP_LIB=os.path.abspath(baseline)) if m == "baseline" else dict(os.environ)
+                out = subprocess.check_output([sys.executable, os.path.abspath(__file__), f"--mode={'plain' if m == 'baseline' else m}", str(n), str(render[0]), str(render[1])],
+                                              env=env, timeout=300).decode()
+                sys.stdout.write(out); sys.stdout.flush()
+                us[m].append(float(re.search(r"basepass_PS_Main_GBuffer#\w+\s+([0-9.]+) us", out).group(1)))
+        for m in modes:
+            a = np.array(us[m])
+            print(f"{m:9s}: {' '.join(f'{x:.1f}' for x in a)} us; median {np.median(a):.1f}, spread {a.max() - a.min():.1f}")
+        print(f"textured - plain = {np.median(us['textured']) - np.median(us['plain']):.1f} us")
+        if baseline:
+            b = np.array(us["baseline"])
+            print(f"plain - baseline = {np.median(us['plain']) - np.median(b):+.1f} us against the baseline's own spread of {b.max() - b.min():.1f} us")

@@ -106,6 +106,14 @@ struct MaterialData
     float m_ConstRoughness;                  // Q13: never read by the reference's shader (roughness 1, metallic 0 without a texture)
     float m_ConstMetallic;
 };
+// The four TextureData members are indexed as an array, slot c behind flag bit c (visibility_resolve.hip.h, host/Scene.cpp).
+static_assert(offsetof(MaterialData, m_NormalTexture) == offsetof(MaterialData, m_AlbedoTexture) + sizeof(TextureData) &&
+              offsetof(MaterialData, m_MetallicRoughnessTexture) == offsetof(MaterialData, m_AlbedoTexture) + 2 * sizeof(TextureData) &&
+              offsetof(MaterialData, m_EmissiveTexture) == offsetof(MaterialData, m_AlbedoTexture) + 3 * sizeof(TextureData),
+              "MaterialData: albedo, normal, metallic-roughness, emissive TextureData back to back");
+static_assert(MaterialFlag_UseAlbedoTexture == 1u << 0 && MaterialFlag_UseNormalTexture == 1u << 1 && MaterialFlag_UseMetallicRoughnessTexture == 1u << 2 &&
+              MaterialFlag_UseEmissiveTexture == 1u << 3, "MaterialData: flag bit c belongs to texture slot c");
+
 
 // ShaderInterop.h:86-98
 struct DeferredLightingConsts

@@ -467,6 +467,8 @@ public:
             check(g_Graphic.m_GlobalMaterialDataBuffer && m_GBufferA);
             p.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_SRV(3, g_Graphic.m_GlobalMaterialDataBuffer));   // :469
             p.m_BindingSetDesc.bindings.push_back(Item::Texture_UAV(0, m_GBufferA));
+            if (g_Graphic.m_bAnyMaterialTextured)                             // ResourceDescriptorHeap[...]: the TEXTURED resolve (include/trhip.h, t19)
+                p.m_BindingSetDesc.bindings.push_back(Item::DescriptorTable(19, g_Graphic.m_SrvUavCbvDescriptorTable));
         }
         for (uint32_t s = 0; s < kNumPassSlots; ++s) {                        // a slot that did not run: the dummy buffer
             const PassOutputs& o = m_Outputs[s];

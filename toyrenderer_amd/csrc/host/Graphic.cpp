@@ -4,6 +4,8 @@
 
 #include "Graphic.h"
 
+#include <algorithm>
+
 #include "HostProfile.h"
 
 #include <chrono>
@@ -68,6 +70,35 @@ void Graphic::PostSceneLoad()
     ExecuteAllCommandLists();
 }
 
+// Texture::LoadFromFile + the SRV's slot in the bindless table (Visual.cpp, Graphic.h:111-113), from decoded texels: `data` holds
+// the mips back to back, level k of max(width >> k, 1) x max(height >> k, 1) x 4 bytes.  Returns the descriptor index.
+uint32_t Graphic::CreateMaterialTexture(uint32_t width, uint32_t height, uint32_t mips, nvrhi::Format format, const void* data, uint64_t bytes)
+{
+    if (format != nvrhi::Format::RGBA8_UNORM && format != nvrhi::Format::SRGBA8_UNORM)
+        throw nvrhi::Error("material texture: the format must be RGBA8_UNORM or SRGBA8_UNORM (block-compressed formats are not supported)");
+    if (!width || !height || !mips || mips > 16 || !data) throw nvrhi::Error("material texture: bad dimensions, mip count or data");
+    uint64_t need = 0;
+    for (uint32_t k = 0; k < mips; ++k) need += (uint64_t)std::max(width >> k, 1u) * std::max(height >> k, 1u) * 4u;
+    if (bytes != need) throw nvrhi::Error("material texture: " + std::to_string(mips) + " mips of " + std::to_string(width) + " x " + std::to_string(height) + " are " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
+    if (m_Textures.size() >= kMaxMaterialTextures) throw nvrhi::Error("material texture: the descriptor table is full");
+    if (!m_SrvUavCbvDescriptorTable) m_SrvUavCbvDescriptorTable = m_NVRHIDevice->createDescriptorTable(kMaxMaterialTextures);
+    nvrhi::TextureDesc d;
+    d.width = width; d.height = height; d.mipLevels = mips; d.format = format;
+    d.debugName = "Material Texture " + std::to_string(m_Textures.size());
+    d.initialState = nvrhi::ResourceStates::ShaderResource;
+    nvrhi::TextureHandle t = m_NVRHIDevice->createTexture(d);
+    const uint8_t* p = (const uint8_t*)data;
+    for (uint32_t k = 0; k < mips; ++k) {
+        const uint64_t n = (uint64_t)std::max(width >> k, 1u) * std::max(height >> k, 1u) * 4u;
+        nvrhi::throwIfFailed(trhip_texture_upload(t->native(), k, p, n), "material texture upload");
+        p += n;
+    }
+    const uint32_t index = (uint32_t)m_Textures.size();
+    m_NVRHIDevice->writeDescriptorTable(m_SrvUavCbvDescriptorTable, index, t);
+    m_Textures.push_back(t);
+    return index;
+}
+
 void Graphic::Shutdown()
 {
     if (!m_NVRHIDevice) return;
@@ -84,6 +115,9 @@ void Graphic::Shutdown()
     m_GlobalMeshletDataBuffer = nullptr;
     m_GlobalVertexBuffer = nullptr; m_GlobalMeshletVertexOffsetsBuffer = nullptr; m_GlobalMeshletIndicesBuffer = nullptr;
     m_GlobalMaterialDataBuffer = nullptr;
+    m_SrvUavCbvDescriptorTable = nullptr;
+    m_Textures.clear();
+    m_bAnyMaterialTextured = false;
     m_PendingCommandLists.clear();
     for (auto& pool : m_FreeCommandLists) pool.clear();
     m_AllCommandLists.clear();

@@ -92,7 +92,14 @@ public:
     // what the mesh shader reads (basepass.hlsl t1, t5, t6): only needed when the frame rasterises its own depth
     nvrhi::BufferHandle m_GlobalVertexBuffer, m_GlobalMeshletVertexOffsetsBuffer, m_GlobalMeshletIndicesBuffer;
     nvrhi::BufferHandle m_GlobalIndexBuffer;               // Graphic.h:139: the meshes' LOD-0 index lists (shadowmask.hlsl t6); Scene::LoadRaytracing
-    nvrhi::BufferHandle m_GlobalMaterialDataBuffer;        // Graphic.h:135: MaterialData[], basepass.hlsl t3 (texture-free materials)
+    nvrhi::BufferHandle m_GlobalMaterialDataBuffer;        // Graphic.h:135: MaterialData[], basepass.hlsl t3
+    // Graphic.h:127 m_Textures and the bindless SRV table GetIndexInHeap indexes (Graphic.h:111-113): the material textures in
+    // upload order and the table that maps a TextureData::m_DescriptorIndex to them (created by the first texture).
+    static constexpr uint32_t kMaxMaterialTextures = 4096;
+    std::vector<nvrhi::TextureHandle> m_Textures;
+    nvrhi::DescriptorTableHandle m_SrvUavCbvDescriptorTable;
+    bool m_bAnyMaterialTextured = false;                   // a loaded material has a texture flag: the base pass binds the table
+    uint32_t CreateMaterialTexture(uint32_t width, uint32_t height, uint32_t mips, nvrhi::Format format, const void* data, uint64_t bytes);
 
     Vector2U m_RenderResolution{ 0, 0 };
     uint32_t m_FrameCounter = 0;

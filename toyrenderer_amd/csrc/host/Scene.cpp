@@ -225,10 +225,21 @@ void Scene::LoadRaytracing(const uint32_t* indices, uint64_t numIndices, const u
 
 void Scene::LoadMaterials(const void* materials, uint32_t numMaterials)
 {
+    // a textured material: every flagged slot names a loaded texture (trhost_create_material_texture) and no streaming textures
     const interop::MaterialData* m = (const interop::MaterialData*)materials;
-    for (uint32_t i = 0; i < numMaterials; ++i)
-        if (m[i].m_MaterialFlags & interop::kMaterialFlagAnyTexture)
-            throw std::runtime_error("materials: material " + std::to_string(i) + " uses a texture (m_MaterialFlags): textured materials are not supported");
+    bool anyTextured = false;
+    for (uint32_t i = 0; i < numMaterials; ++i) {
+        const interop::TextureData* slots = &m[i].m_AlbedoTexture;
+        for (uint32_t c = 0; c < 4; ++c) {
+            if (!(m[i].m_MaterialFlags & (1u << c))) continue;
+            if (slots[c].m_DescriptorIndex >= g_Graphic.m_Textures.size())
+                throw std::runtime_error("materials: material " + std::to_string(i) + " uses a texture (m_MaterialFlags bit " + std::to_string(c) + ", m_DescriptorIndex " +
+                                         std::to_string(slots[c].m_DescriptorIndex) + ") that is not loaded: " + std::to_string(g_Graphic.m_Textures.size()) + " material textures");
+            if (slots[c].m_FeedbackTextureDescriptorIndex != 0xFFFFFFFFu || slots[c].m_MinMapTextureDescriptorIndex != 0xFFFFFFFFu)
+                throw std::runtime_error("materials: material " + std::to_string(i) + " names a sampler-feedback or min-mip texture: texture streaming is not supported");
+            anyTextured = true;
+        }
+    }
     nvrhi::BufferDesc d;
     d.byteSize = numMaterials ? (uint64_t)numMaterials * sizeof(interop::MaterialData) : sizeof(interop::MaterialData);
     d.structStride = sizeof(interop::MaterialData);
@@ -237,6 +248,7 @@ void Scene::LoadMaterials(const void* materials, uint32_t numMaterials)
     nvrhi::BufferHandle b = g_Graphic.m_NVRHIDevice->createBuffer(d);
     if (numMaterials) nvrhi::throwIfFailed(trhip_buffer_upload(b->native(), 0, materials, (uint64_t)numMaterials * sizeof(interop::MaterialData)), "Scene material upload");
     g_Graphic.m_GlobalMaterialDataBuffer = b;
+    g_Graphic.m_bAnyMaterialTextured = anyTextured;
 }
 
 void Scene::LoadNodes(const void* nodes, uint32_t numNodes, const uint32_t* primitiveToNode)

@@ -144,7 +144,7 @@ public:
     float m_SunAngularDiameter = 0.533f, m_ShadowRayStartOffset = 0.1f;
     nvrhi::BufferHandle m_LuminanceBuffer;           // Scene.h: one float, the adapted luminance; survives across frames
     nvrhi::TextureHandle m_ExposureTexture;          // 1 x 1 R32_FLOAT
-    // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088) for texture-free materials.
+    // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088); a textured material names textures of Graphic::CreateMaterialTexture.
     void LoadMaterials(const void* materials, uint32_t numMaterials);
     // `<scene>_CachedData.bin` version 3 (SceneLoading.cpp:57-79 layout, :706-781 LoadCachedData): meshes, meshlets and
     // the mesh-shader geometry come from the file, instances and id lists from the caller (the glTF side of the reference).

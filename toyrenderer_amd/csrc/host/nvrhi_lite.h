@@ -93,7 +93,7 @@ private:
 using ResourceHandle = RefCountPtr<IResource>;
 
 // ---- enums / small structs -----------------------------------------------------------------------
-enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT, RGBA8_UNORM };   // GraphicConstants.h:24-28, :31 (lighting output), shadow mask, SSAO, the back buffer (GraphicRHI.cpp:214)
+enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT, RGBA8_UNORM, SRGBA8_UNORM };   // GraphicConstants.h:24-28, :31 (lighting output), shadow mask, SSAO, the back buffer (GraphicRHI.cpp:214)
 enum class ResourceStates : uint32_t { Unknown = 0, ShaderResource, UnorderedAccess, IndirectArgument, DepthRead, DepthWrite, CopyDest };
 enum class CommandQueue : uint8_t { Graphics = 0, Compute, Copy, Count };
 enum class HeapType : uint8_t { DeviceLocal };
@@ -207,6 +207,19 @@ private:
     TextureDesc m_Desc;
 };
 
+// nvrhi::IDescriptorTable (Graphic.h: the bindless SRV table that ResourceDescriptorHeap[...] indexes): the back end's texture table
+class IDescriptorTable : public IResource
+{
+public:
+    explicit IDescriptorTable(trhip_texture_table t) : m_Native(t) {}
+    ~IDescriptorTable() override { trhip_texture_table_release(m_Native); }
+    trhip_texture_table native() const { return m_Native; }
+    uint32_t getCapacity() const { return trhip_texture_table_capacity(m_Native); }
+
+private:
+    trhip_texture_table m_Native;
+};
+
 class ISampler : public IResource
 {
 public:
@@ -254,6 +267,7 @@ using HeapHandle = RefCountPtr<IHeap>;
 using BufferHandle = RefCountPtr<IBuffer>;
 using TextureHandle = RefCountPtr<ITexture>;
 using SamplerHandle = RefCountPtr<ISampler>;
+using DescriptorTableHandle = RefCountPtr<IDescriptorTable>;
 using TimerQueryHandle = RefCountPtr<ITimerQuery>;
 using PipelineStatisticsQueryHandle = RefCountPtr<IPipelineStatisticsQuery>;
 
@@ -280,6 +294,7 @@ struct BindingSetItem
     IBuffer* buffer = nullptr;
     ITexture* texture = nullptr;
     ISampler* sampler = nullptr;
+    IDescriptorTable* table = nullptr;
     uint32_t baseMip = 0;
     uint32_t pushBytes = 0;
 
@@ -297,6 +312,8 @@ struct BindingSetItem
     }
     // the TLAS nodes as a structured SRV; the structure's other buffers are bound beside it (include/trhip.h)
     static BindingSetItem RayTracingAccelStruct(uint32_t slot, rt::AccelStruct* as) { return StructuredBuffer_SRV(slot, as->nodes); }
+    // the texture table at register(t<slot>): the stand-in of the bindless heap (include/trhip.h)
+    static BindingSetItem DescriptorTable(uint32_t slot, IDescriptorTable* t) { BindingSetItem i; i.type = TRHIP_BIND_TEXTURE_TABLE; i.slot = slot; i.table = t; return i; }
     static BindingSetItem Sampler(uint32_t slot, ISampler* s) { BindingSetItem i; i.type = TRHIP_BIND_SAMPLER; i.slot = slot; i.sampler = s; return i; }
 };
 
@@ -345,7 +362,7 @@ public:
     void setComputeState(const ComputeState& s)
     {
         m_State = s;
-        for (const BindingSetItem& i : s.bindings.bindings) { keep(i.buffer); keep(i.texture); }
+        for (const BindingSetItem& i : s.bindings.bindings) { keep(i.buffer); keep(i.texture); keep(i.table); }
         keep(s.indirectParams);
     }
     void setPushConstants(const void* data, size_t bytes) { m_Push.assign((const uint8_t*)data, (const uint8_t*)data + bytes); }
@@ -385,6 +402,7 @@ private:
             b.type = i.type; b.slot = i.slot; b.baseMip = i.baseMip;
             if (i.buffer) b.resource = i.buffer->native();
             else if (i.texture) b.resource = i.texture->native();
+            else if (i.table) b.resource = i.table->native();
             out.push_back(b);
         }
         return out;
@@ -447,12 +465,20 @@ public:
         n.format = d.format == Format::R16_FLOAT ? TRHIP_FORMAT_R16_FLOAT : d.format == Format::RG32_UINT ? TRHIP_FORMAT_RG32_UINT
                  : d.format == Format::RG16_FLOAT ? TRHIP_FORMAT_RG16_FLOAT : d.format == Format::RGBA32_UINT ? TRHIP_FORMAT_RGBA32_UINT
                  : d.format == Format::R11G11B10_FLOAT ? TRHIP_FORMAT_R11G11B10_FLOAT : d.format == Format::R8_UNORM ? TRHIP_FORMAT_R8_UNORM
-                 : d.format == Format::R8_UINT ? TRHIP_FORMAT_R8_UINT : d.format == Format::RGBA8_UNORM ? TRHIP_FORMAT_RGBA8_UNORM : TRHIP_FORMAT_R32_FLOAT;
+                 : d.format == Format::R8_UINT ? TRHIP_FORMAT_R8_UINT : d.format == Format::RGBA8_UNORM ? TRHIP_FORMAT_RGBA8_UNORM
+                 : d.format == Format::SRGBA8_UNORM ? TRHIP_FORMAT_SRGBA8_UNORM : TRHIP_FORMAT_R32_FLOAT;
         trhip_texture t = nullptr;
         throwIfFailed(trhip_texture_create(m_Native, &n, &t), "IDevice::createTexture");
         return TextureHandle(new ITexture(t, d));
     }
     SamplerHandle createSampler(const SamplerDesc& d) { return SamplerHandle(new ISampler(d)); }
+    DescriptorTableHandle createDescriptorTable(uint32_t capacity)
+    {
+        trhip_texture_table t = nullptr;
+        throwIfFailed(trhip_texture_table_create(m_Native, capacity, &t), "IDevice::createDescriptorTable");
+        return DescriptorTableHandle(new IDescriptorTable(t));
+    }
+    void writeDescriptorTable(IDescriptorTable* table, uint32_t index, ITexture* t) { throwIfFailed(trhip_texture_table_set(table->native(), index, t->native()), "IDevice::writeDescriptorTable"); }
     MemoryRequirements getBufferMemoryRequirements(IBuffer* b)
     {
         MemoryRequirements r;

@@ -135,6 +135,18 @@ int trhost_load_materials(const void* materials, uint32_t count)
     });
 }
 
+int trhost_create_material_texture(uint32_t width, uint32_t height, uint32_t mips, uint32_t format, const void* data, uint64_t bytes)
+{
+    int index = -1;
+    int rc = guarded([&] {
+        check(g_Scene);
+        if (format != TRHIP_FORMAT_RGBA8_UNORM && format != TRHIP_FORMAT_SRGBA8_UNORM)
+            throw nvrhi::Error("trhost_create_material_texture: format " + std::to_string(format) + ": a material texture is TRHIP_FORMAT_RGBA8_UNORM or TRHIP_FORMAT_SRGBA8_UNORM");
+        index = (int)g_Graphic.CreateMaterialTexture(width, height, mips, format == TRHIP_FORMAT_SRGBA8_UNORM ? nvrhi::Format::SRGBA8_UNORM : nvrhi::Format::RGBA8_UNORM, data, bytes);
+    });
+    return rc == 0 ? index : -1;
+}
+
 int trhost_set_gbuffer(int enable)
 {
     return guarded([&] {

@@ -4,6 +4,7 @@
 // the reference's shader-name strings.
 #include "trhip_internal.h"
 #include "r11g11b10.hip.h"
+#include "material_textures.hip.h"
 
 #include <chrono>
 #include <cmath>
@@ -65,6 +66,14 @@ trhip_texture_t* DispatchCtx::texture(uint32_t type, uint32_t slot, uint32_t* ba
             if (baseMip) *baseMip = bindings[i].baseMip;
             return (trhip_texture_t*)bindings[i].resource;
         }
+    return nullptr;
+}
+
+trhip_texture_table_t* DispatchCtx::textureTable(uint32_t slot) const
+{
+    for (uint32_t i = 0; i < numBindings; ++i)
+        if (bindings[i].type == TRHIP_BIND_TEXTURE_TABLE && bindings[i].slot == slot)
+            return (trhip_texture_table_t*)bindings[i].resource;
     return nullptr;
 }
 
@@ -206,8 +215,10 @@ void trhip_cmdlist_t::resetRecording()
     ops.clear();
     for (trhip_buffer_t* b : heldBuffers) trhip_buffer_release(b);
     for (trhip_texture_t* t : heldTextures) trhip_texture_release(t);
+    for (trhip_texture_table_t* t : heldTables) trhip_texture_table_release(t);
     heldBuffers.clear();
     heldTextures.clear();
+    heldTables.clear();
     markers.clear();
     openStats = nullptr;
     statsHostCS = 0;
@@ -336,6 +347,7 @@ void trhip_device_destroy(trhip_device dev)
     if (dev->sideStream) { (void)hipStreamSynchronize(dev->sideStream); (void)hipStreamDestroy(dev->sideStream); }
     if (dev->evFork) (void)hipEventDestroy(dev->evFork);
     for (hipEvent_t e : dev->runDone) if (e) (void)hipEventDestroy(e);
+    if (dev->srgbTable.ptr) (void)hipFree(dev->srgbTable.ptr);
     if (dev->ownsStream) (void)hipStreamDestroy(dev->stream);
     delete dev;
 }
@@ -480,11 +492,12 @@ int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_te
     if (!dev || !d || !out) return fail(TRHIP_ERR_INVALID, "texture_create: null argument");
     if (d->width == 0 || d->height == 0 || d->mipLevels == 0 || d->mipLevels > 16)
         return fail(TRHIP_ERR_INVALID, "texture_create: bad dimensions %ux%u mips %u", d->width, d->height, d->mipLevels);
-    if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && d->format != TRHIP_FORMAT_RGBA8_UNORM)
+    if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && d->format != TRHIP_FORMAT_RGBA8_UNORM && d->format != TRHIP_FORMAT_SRGBA8_UNORM)
         return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u", d->format);
     const bool bloomChain = d->format == TRHIP_FORMAT_R11G11B10_FLOAT && (d->isUAV & TRHIP_TEXTURE_RENDER_TARGET);   // the bloom texture (BloomRenderer.cpp:41-50)
-    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && !bloomChain && d->mipLevels != 1)
-        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT / RGBA8_UNORM textures have one mip, got %u", d->mipLevels);
+    const bool sampledChain = (d->format == TRHIP_FORMAT_RGBA8_UNORM || d->format == TRHIP_FORMAT_SRGBA8_UNORM) && d->isUAV == 0;   // a material texture
+    if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && !bloomChain && !sampledChain && d->mipLevels != 1)
+        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT textures and RGBA8_UNORM / SRGBA8_UNORM textures that a pass writes have one mip, got %u", d->mipLevels);
     auto t = std::make_unique<trhip_texture_t>();
     t->dev = dev;
     t->width = d->width; t->height = d->height; t->mips = d->mipLevels; t->format = d->format;
@@ -614,6 +627,94 @@ int trhip_texture_download(trhip_texture t, uint32_t mip, void* dst, uint64_t by
     return syncCopy(t->dev, dst, t->mipPtr(mip), bytes, hipMemcpyDeviceToHost);
 }
 
+// ---- texture table ---------------------------------------------------------------------------------
+int trhip_srgb_table(float* out)
+{
+    if (!out) return fail(TRHIP_ERR_INVALID, "srgb_table: out is null");
+    for (int i = 0; i < 256; ++i) {
+        const double c = (double)i / 255.0;
+        out[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
+    }
+    return TRHIP_OK;
+}
+
+int trhip_texture_table_create(trhip_device dev, uint32_t capacity, trhip_texture_table* out)
+{
+    if (!dev || !out) return fail(TRHIP_ERR_INVALID, "texture_table_create: null argument");
+    if (capacity == 0 || capacity > (1u << 20)) return fail(TRHIP_ERR_INVALID, "texture_table_create: capacity %u not in 1 .. 2^20", capacity);
+    TRHIP_HIP(hipSetDevice(dev->index));
+    {   // creation is rare: always under the lock; the pointer is published only after the table is filled
+        std::lock_guard<std::mutex> lock(dev->mutex);
+        if (!dev->srgbTable.ptr) {
+            float table[256];
+            trhip_srgb_table(table);
+            trhip::DerivedData filled;
+            int rc = filled.allocate(dev, sizeof table);
+            if (rc != TRHIP_OK) return rc;
+            hipError_t e = hipMemcpy(filled.ptr, table, sizeof table, hipMemcpyHostToDevice);
+            if (e != hipSuccess) { (void)hipFree(filled.ptr); return hipfail(e, "hipMemcpy(sRGB table)"); }
+            dev->srgbTable = filled;
+        }
+    }
+    auto t = std::make_unique<trhip_texture_table_t>();
+    t->dev = dev;
+    t->slots.assign(capacity, nullptr);
+    int rc = t->entries.allocate(dev, (uint64_t)capacity * sizeof(mtex::TableEntry));
+    if (rc != TRHIP_OK) return rc;
+    hipError_t e = hipMemset(t->entries.ptr, 0, (size_t)t->entries.bytes);
+    if (e != hipSuccess) { (void)hipFree(t->entries.ptr); return hipfail(e, "hipMemset(texture table)"); }
+    *out = t.release();
+    return TRHIP_OK;
+}
+
+void trhip_texture_table_retain(trhip_texture_table t) { if (t) t->rc.fetch_add(1); }
+
+void trhip_texture_table_release(trhip_texture_table t)
+{
+    if (!t) return;
+    if (t->rc.fetch_sub(1) == 1) {
+        trhip::freeDerived(t->dev, { &t->entries });
+        for (trhip_texture_t* e : t->slots) trhip_texture_release(e);
+        delete t;
+    }
+}
+
+uint32_t trhip_texture_table_capacity(trhip_texture_table t) { return t ? (uint32_t)t->slots.size() : 0; }
+
+static int tableWrite(trhip_texture_table_t* t, uint32_t index, trhip_texture_t* tex)
+{
+    mtex::TableEntry e;
+    memset(&e, 0, sizeof e);
+    if (tex) {
+        e.base = (const uint32_t*)tex->ptr;
+        e.width = tex->width; e.height = tex->height; e.mips = tex->mips; e.format = tex->format;
+        for (uint32_t k = 0; k < tex->mips; ++k) e.mipOffset[k] = (uint32_t)(tex->mipOffset[k] / 4u);
+    }
+    int rc = syncCopy(t->dev, (char*)t->entries.ptr + (uint64_t)index * sizeof e, &e, sizeof e, hipMemcpyHostToDevice);   // drains the device: nothing in flight reads the old entry
+    if (rc != TRHIP_OK) return rc;
+    trhip_texture_retain(tex);
+    trhip_texture_release(t->slots[index]);
+    t->slots[index] = tex;
+    return TRHIP_OK;
+}
+
+int trhip_texture_table_set(trhip_texture_table t, uint32_t index, trhip_texture tex)
+{
+    if (!t || !tex) return fail(TRHIP_ERR_INVALID, "texture_table_set: null argument");
+    if (index >= t->slots.size()) return fail(TRHIP_ERR_INVALID, "texture_table_set: index %u at or past the capacity %zu", index, t->slots.size());
+    if (tex->dev != t->dev) return fail(TRHIP_ERR_INVALID, "texture_table_set(%s): the texture belongs to another device", tex->name.c_str());
+    if (!tex->ptr) return fail(TRHIP_ERR_STATE, "texture_table_set(%s): no memory bound", tex->name.c_str());
+    if (tex->totalBytes / 4u > 0xFFFFFFFFull) return fail(TRHIP_ERR_INVALID, "texture_table_set(%s): more than 2^32 texels", tex->name.c_str());
+    return tableWrite(t, index, tex);
+}
+
+int trhip_texture_table_clear(trhip_texture_table t, uint32_t index)
+{
+    if (!t) return fail(TRHIP_ERR_INVALID, "texture_table_clear: null argument");
+    if (index >= t->slots.size()) return fail(TRHIP_ERR_INVALID, "texture_table_clear: index %u at or past the capacity %zu", index, t->slots.size());
+    return tableWrite(t, index, nullptr);
+}
+
 // ---- command lists -------------------------------------------------------------------------------
 int trhip_cmd_create(trhip_device dev, trhip_cmdlist* out)
 {
@@ -704,8 +805,8 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RG32_UINT || tex->format == TRHIP_FORMAT_RGBA32_UINT || tex->format == TRHIP_FORMAT_R8_UINT)
         return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): RG32_UINT / RGBA32_UINT / R8_UINT are cleared with clear_texture_u32", tex->name.c_str());
-    if (tex->format == TRHIP_FORMAT_RGBA8_UNORM)
-        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): an RGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_RGBA8_UNORM || tex->format == TRHIP_FORMAT_SRGBA8_UNORM)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): an RGBA8_UNORM / SRGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
     void* p = tex->ptr;
     cl->hold(tex, true);
     if (tex->format == TRHIP_FORMAT_R32_FLOAT || tex->format == TRHIP_FORMAT_R11G11B10_FLOAT) {
@@ -739,8 +840,8 @@ int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t va
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
-    if (tex->format == TRHIP_FORMAT_RGBA8_UNORM)
-        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): an RGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_RGBA8_UNORM || tex->format == TRHIP_FORMAT_SRGBA8_UNORM)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): an RGBA8_UNORM / SRGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
     if (tex->format != TRHIP_FORMAT_RG32_UINT && tex->format != TRHIP_FORMAT_RGBA32_UINT && tex->format != TRHIP_FORMAT_R8_UINT)
         return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): needs an RG32_UINT, RGBA32_UINT or R8_UINT texture", tex->name.c_str());
     void* p = tex->ptr;
@@ -827,6 +928,16 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
             if (!t->ptr) return fail(TRHIP_ERR_STATE, "dispatch(%s): texture '%s' has no memory bound", name, t->name.c_str());
             if (b[i].type == TRHIP_BIND_TEXTURE_UAV && b[i].baseMip >= t->mips) return fail(TRHIP_ERR_INVALID, "dispatch(%s): UAV mip %u out of range", name, b[i].baseMip);
             cl->hold(t, b[i].type == TRHIP_BIND_TEXTURE_UAV);
+            break; }
+        case TRHIP_BIND_TEXTURE_TABLE: {
+            trhip_texture_table_t* t = (trhip_texture_table_t*)b[i].resource;
+            if (!t) return fail(TRHIP_ERR_INVALID, "dispatch(%s): binding %u has no texture table", name, i);
+            if (t->dev != cl->dev) return fail(TRHIP_ERR_INVALID, "dispatch(%s): the texture table belongs to another device", name);
+            if (strcmp(name, "basepass_PS_Main_GBuffer") != 0 || b[i].slot != 19u)           // the one shader that indexes ResourceDescriptorHeap[...]
+                return fail(TRHIP_ERR_INVALID, "dispatch(%s): a texture table at t%u: only basepass_PS_Main_GBuffer declares one, at t19", name, b[i].slot);
+            trhip_texture_table_retain(t);
+            cl->heldTables.push_back(t);
+            for (trhip_texture_t* e : t->slots) cl->hold(e, false);
             break; }
         case TRHIP_BIND_PUSH_CONSTANTS: case TRHIP_BIND_SAMPLER: break;
         default: return fail(TRHIP_ERR_INVALID, "dispatch(%s): binding %u has unknown type %u", name, i, b[i].type);

@@ -44,6 +44,38 @@ struct ProfileAccum { uint64_t launches = 0; double totalMs = 0; };
 
 } // namespace trhip
 
+struct trhip_device_t;
+
+namespace trhip
+{
+
+// What derived data was last built from: the version of its owner (trhip_buffer_t::version) and, for data that also reads a
+// second resource (the instance cull cache reads the mesh table), that resource's pointer and version.  Versions start at 1,
+// so the zero stamp is never current.
+struct Stamp
+{
+    uint64_t version = 0;
+    const void* other = nullptr;
+    uint64_t otherVersion = 0;
+    bool operator==(const Stamp& s) const { return version == s.version && other == s.other && otherVersion == s.otherVersion; }
+};
+
+// Back-end private device memory DERIVED from a buffer or texture the caller owns, and freed with it (freeDerived).  Its size
+// is a function of the owner's, which never changes after creation, so it is allocated once, by the first pass that needs it.
+// Data rebuilt from the owner's contents is rebuilt exactly when the stamp of its sources is no longer `built`.
+struct DerivedData
+{
+    void* ptr = nullptr;
+    uint64_t bytes = 0;
+    Stamp built;
+
+    int allocate(const trhip_device_t* dev, uint64_t size);
+    bool current(const Stamp& s) const { return built == s; }
+    void markBuilt(const Stamp& s) { built = s; }
+};
+
+} // namespace trhip
+
 struct trhip_device_t
 {
     int index = 0;
@@ -78,6 +110,10 @@ struct trhip_device_t
 
     hipEvent_t acquireEvent();
     int drainProfile();
+
+    // The sRGB-to-linear TABLE of SRGBA8_UNORM textures (trhip_srgb_table: 256 floats), on the device from the first texture
+    // table on; the textured G-buffer resolve stages it in LDS (material_textures.hip.h).
+    trhip::DerivedData srgbTable;
 };
 
 struct trhip_heap_t
@@ -90,31 +126,6 @@ struct trhip_heap_t
 
 namespace trhip
 {
-
-// What derived data was last built from: the version of its owner (trhip_buffer_t::version) and, for data that also reads a
-// second resource (the instance cull cache reads the mesh table), that resource's pointer and version.  Versions start at 1,
-// so the zero stamp is never current.
-struct Stamp
-{
-    uint64_t version = 0;
-    const void* other = nullptr;
-    uint64_t otherVersion = 0;
-    bool operator==(const Stamp& s) const { return version == s.version && other == s.other && otherVersion == s.otherVersion; }
-};
-
-// Back-end private device memory DERIVED from a buffer or texture the caller owns, and freed with it (freeDerived).  Its size
-// is a function of the owner's, which never changes after creation, so it is allocated once, by the first pass that needs it.
-// Data rebuilt from the owner's contents is rebuilt exactly when the stamp of its sources is no longer `built`.
-struct DerivedData
-{
-    void* ptr = nullptr;
-    uint64_t bytes = 0;
-    Stamp built;
-
-    int allocate(const trhip_device_t* dev, uint64_t size);
-    bool current(const Stamp& s) const { return built == s; }
-    void markBuilt(const Stamp& s) { built = s; }
-};
 
 // An owner's release: drains both streams of the device once (commands in flight may still use the data), then frees them.
 void freeDerived(trhip_device_t* dev, std::initializer_list<DerivedData*> all);
@@ -181,6 +192,17 @@ struct trhip_texture_t
     void* mipPtr(uint32_t k) const { return (char*)ptr + mipOffset[k]; }
 };
 
+// The texture table (include/trhip.h): the stand-in of ResourceDescriptorHeap[...].  slots[i] is the retained texture behind
+// descriptor index i (nullptr: empty); `entries` its device-side form, capacity x mtex::TableEntry (material_textures.hip.h),
+// rewritten entry by entry, synchronously, by trhip_texture_table_set / _clear.
+struct trhip_texture_table_t
+{
+    trhip_device_t* dev = nullptr;
+    std::vector<trhip_texture_t*> slots;
+    trhip::DerivedData entries;
+    std::atomic<int> rc{1};
+};
+
 struct trhip_timer_t
 {
     trhip_device_t* dev = nullptr;
@@ -225,6 +247,7 @@ struct trhip_cmdlist_t
     std::vector<trhip::Op> ops;
     std::vector<trhip_buffer_t*> heldBuffers;
     std::vector<trhip_texture_t*> heldTextures;
+    std::vector<trhip_texture_table_t*> heldTables;
     std::vector<std::string> markers;
     // The pipeline statistics query open in this recording (nullptr: none) and the CS invocations of its direct dispatches,
     // known on the host and added once by the end command.
@@ -304,6 +327,7 @@ struct DispatchCtx
 
     trhip_buffer_t* buffer(uint32_t type, uint32_t slot) const;
     trhip_texture_t* texture(uint32_t type, uint32_t slot, uint32_t* baseMip = nullptr) const;
+    trhip_texture_table_t* textureTable(uint32_t slot) const;
     // Bytes of the constant buffer bound at b<slot> (volatile CB version at record time) or of
     // the push constants; nullptr if absent / wrong size.
     const void* constants(uint32_t slot, size_t bytes) const;

@@ -19,9 +19,29 @@
 //             uint(x) truncates, round = round half to even;
 //   debugValue by m_DebugMode: 2 QuickRandomFloat(m_InstanceConstIdx), 3 QuickRandomFloat(m_MeshletGroupOffset + lane),
 //             12 (float)m_MeshLOD / 255.0f, else 0.
+//
+// CONVENTION of the TEXTURED instantiation (a texture table bound at t19; parity unpinned; restated in
+// tests/material_textures_ref.c).  GetCommonGBufferParams (lightingcommon.hlsli:435-493) as written:
+//   uv, wp  = m_TexCoord (half2 -> float, exact) and mul(pos, World), interpolated as the normal: fma(q2, a2, fma(q1, a1, q0 * a0)) / s;
+//   ddx,ddy = the same interpolation of the SAME triangle with the edge functions re-evaluated at (cx + 1, cy) and at (cx, cy + 1)
+//             (the triangle's plane extended), minus the centre value: what a pixel quad lying inside one triangle yields.  A
+//             DEVIATION at triangle borders, where hardware differentiates across the helper lanes of the quad;
+//   samples = SampleMaterialValue of each slot flagged in m_MaterialFlags (material_textures.hip.h states the sampler);
+//   albedo  = m_ConstAlbedo * sample, roughness = mr.g, metallic = mr.b (defaults (0, 1, 0, 0) when unflagged), emissive =
+//             m_ConstEmissive * sample.rgb, w = PackRGBA8(roughness, metallic, 0, 0);
+//   normal  = with a normal map: TwoChannelNormalX2 (toyrenderer_common.hlsli:226-231: xy = 2.0f * n.xy - 1.0f, z = sqrt(1.0f -
+//             fma(y, y, x * x)), a NaN z is kept), CalculateTBNWithoutTangent (:235-247) from ddx / ddy of wp and uv (cm::cross3, the
+//             float2 x float2x3 product fma(b, r1, a * r0), normalize = v / sqrt(dot3)), mul(unpackedNormal, TBN) as cm::mulVec, then
+//             normalize, on the interpolated, not renormalised geometric normal;
+//   bounds  = a flagged slot whose m_DescriptorIndex is at or past the table's count, names an empty entry or an entry of another
+//             format ends the pixel untouched in both targets, like every other broken chain here.
+// Without a table recordResolve launches resolveKernel<GBUFFER> exactly as before: no word and no cost of a texture-free frame moves.
 #pragma once
 
+#include "material_textures.hip.h"
 #include "mesh_stage.hip.h"
+
+#include <type_traits>
 
 namespace vres
 {
@@ -31,6 +51,7 @@ using namespace mesh;
 constexpr uint32_t kTileW = 16, kTileH = 16;   // one workgroup per 16x16 pixels: a wave covers 16x4 neighbouring pixels
 constexpr uint32_t kBlock = kTileW * kTileH;
 constexpr uint32_t kGroupSide = 8;              // the reference entry's [numthreads(8, 8, 1)]: group counts cover the screen
+constexpr uint32_t kTexturedWaves = 4;          // waves per SIMD of the TEXTURED instantiation: 128 VGPRs (k_gbuffer.hip)
 
 struct ResolveArgs
 {
@@ -43,6 +64,13 @@ struct ResolveArgs
     const char* materials; uint32_t numMaterials;                // MaterialData, the first 32 bytes are read (G-buffer only)
     uint4* gbufferA;                                             // RGBA32_UINT (G-buffer only)
     uint32_t width, height;
+};
+
+// The TEXTURED instantiation's arguments: + the texture table bound at t19 and the device's sRGB table.
+struct TexturedArgs : ResolveArgs
+{
+    const mtex::TableEntry* table; uint32_t tableCount;
+    const float* srgb;                                           // 256 floats (trhip_device_t::srgbTable)
 };
 
 __device__ __forceinline__ uint32_t toHalfBits(float f)
@@ -112,9 +140,26 @@ __device__ __forceinline__ cm::F3 unpackNormal(uint32_t packed)                 
     return { x * 2.0f - 1.0f, y * 2.0f - 1.0f, z * 2.0f - 1.0f };
 }
 
-template <bool GBUFFER>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GBUFFER ? 8 : 1, 8))) void resolveKernel(ResolveArgs a)
+__device__ __forceinline__ float halfLo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)); }
+__device__ __forceinline__ float halfHi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
+__device__ __forceinline__ cm::F3 normalize3(cm::F3 v)
 {
+    const float len = cm::sqrt_(cm::dot3(v, v));
+    return { v.x / len, v.y / len, v.z / len };
+}
+
+// TEXTURED (with GBUFFER only): GetCommonGBufferParams with its four material textures; see the CONVENTION above.
+template <bool GBUFFER, bool TEXTURED = false>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TEXTURED ? kTexturedWaves : GBUFFER ? 8 : 1, TEXTURED ? kTexturedWaves : 8)))
+void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
+{
+    static_assert(GBUFFER || !TEXTURED, "the motion resolve samples nothing");
+    const float* tables = nullptr;
+    if constexpr (TEXTURED) {                                                            // before anyone leaves: a barrier inside
+        __shared__ float lds[mtex::kLdsFloats];
+        mtex::stageTables(lds, a.srgb, threadIdx.y * kTileW + threadIdx.x);
+        tables = lds;
+    }
     const float halfW = 0.5f * (float)a.width, halfH = 0.5f * (float)a.height;
     const uint32_t px = blockIdx.x * kTileW + threadIdx.x, py = blockIdx.y * kTileH + threadIdx.y;
     if (px >= a.width || py >= a.height) return;
@@ -129,11 +174,24 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GBUFFER 
         const uint32_t packed = a.geo.triangles[ml.trianglesAt + id.triangle];
         const uint32_t idx[3] = { packed & 0xFFu, (packed >> 8) & 0xFFu, (packed >> 16) & 0xFFu };
         if (idx[0] >= ml.nv || idx[1] >= ml.nv || idx[2] >= ml.nv) return;
+        const mtex::TableEntry* tex[4] = { nullptr, nullptr, nullptr, nullptr };         // albedo, normal, metallic-roughness, emissive
+        if constexpr (TEXTURED) {
+            const MaterialData& m = *reinterpret_cast<const MaterialData*>(a.materials + (uint64_t)inst.m_MaterialDataIdx * sizeof(MaterialData));
+            const TextureData* slots = &m.m_AlbedoTexture;
+            for (int c = 0; c < 4; ++c) {
+                if (!(m.m_MaterialFlags & (1u << c))) continue;
+                const uint32_t d = slots[c].m_DescriptorIndex;
+                if (d >= a.tableCount || !mtex::sampled(a.table[d])) return;             // past the table, empty, another format
+                tex[c] = a.table + d;
+            }
+        }
         const cm::M43 Wm = cm::loadM43(inst.m_WorldMatrix), Pm = cm::loadM43(inst.m_PrevWorldMatrix);
         const cm::M43 clipXYZ = cm::loadM43(a.k.m_WorldToClip);
         float sx[3], sy[3], w[3];
         cm::F3 prev[3];
         uint32_t packedNormal[3];
+        uint32_t texCoord[3];                                                            // TEXTURED: m_TexCoord, half2
+        cm::F3 wpos[3];                                                                  // TEXTURED: mul(pos, World)
         bool ok = true;
         for (int j = 0; j < 3; ++j) {
             const uint32_t vid = a.geo.vertexIds[ml.vertexIdsAt + idx[j]];
@@ -141,6 +199,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GBUFFER 
             const RawVertexFormat& vtx = vertexAt(a.geo, vid);
             const cm::F3 pos = { vtx.m_Position[0], vtx.m_Position[1], vtx.m_Position[2] };
             if (GBUFFER) packedNormal[j] = vtx.m_PackedNormal;
+            if constexpr (TEXTURED) {
+                texCoord[j] = *reinterpret_cast<const uint32_t*>(vtx.m_TexCoord);
+                wpos[j] = cm::mulPoint(pos, Wm);
+            }
             const ScreenVertex sv = toScreen(pos, Wm, clipXYZ, a.k.m_WorldToClip, halfW, halfH);
             w[j] = sv.w; sx[j] = sv.sx; sy[j] = sv.sy;
             prev[j] = cm::mulPoint(pos, Pm);
@@ -182,10 +244,47 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(GBUFFER 
             else if (a.k.m_DebugMode == kDeferredLightingDebugMode_MeshLOD) debugValue = (float)ml.rec.m_MeshLOD / 255.0f;
             const float* mat = reinterpret_cast<const float*>(a.materials + (uint64_t)inst.m_MaterialDataIdx * sizeof(MaterialData));   // albedo rgb(a), emissive rgb
             uint4 out;
-            out.x = packRGBA8(mat[0], mat[1], mat[2], debugValue);
-            out.y = packOctUnorm2x16(normal);
-            out.z = packR9G9B9E5(mat[4], mat[5], mat[6]);
-            out.w = packRGBA8(1.0f, 0.0f, 0.0f, 0.0f);                                   // roughness 1, metallic 0 (Q13)
+            if constexpr (TEXTURED) {
+                // uv at the centre, at (cx + 1, cy) and at (cx, cy + 1): the same triangle, its plane extended
+                const float ex0 = sgn * edgeFn(sx[1], sy[1], sx[2], sy[2], cx + 1.0f, cy), ex1 = sgn * edgeFn(sx[2], sy[2], sx[0], sy[0], cx + 1.0f, cy), ex2 = sgn * edgeFn(sx[0], sy[0], sx[1], sy[1], cx + 1.0f, cy);
+                const float ey0 = sgn * edgeFn(sx[1], sy[1], sx[2], sy[2], cx, cy + 1.0f), ey1 = sgn * edgeFn(sx[2], sy[2], sx[0], sy[0], cx, cy + 1.0f), ey2 = sgn * edgeFn(sx[0], sy[0], sx[1], sy[1], cx, cy + 1.0f);
+                const float qx0 = ex0 / w[0], qx1 = ex1 / w[1], qx2 = ex2 / w[2], qy0 = ey0 / w[0], qy1 = ey1 / w[1], qy2 = ey2 / w[2];
+                const float sX = (qx0 + qx1) + qx2, sY = (qy0 + qy1) + qy2;
+                const float u0 = halfLo(texCoord[0]), u1 = halfLo(texCoord[1]), u2 = halfLo(texCoord[2]);
+                const float v0 = halfHi(texCoord[0]), v1 = halfHi(texCoord[1]), v2 = halfHi(texCoord[2]);
+                const float u = cm::fma_(q2, u2, cm::fma_(q1, u1, q0 * u0)) / s, v = cm::fma_(q2, v2, cm::fma_(q1, v1, q0 * v0)) / s;
+                const float dudx = cm::fma_(qx2, u2, cm::fma_(qx1, u1, qx0 * u0)) / sX - u, dvdx = cm::fma_(qx2, v2, cm::fma_(qx1, v1, qx0 * v0)) / sX - v;
+                const float dudy = cm::fma_(qy2, u2, cm::fma_(qy1, u1, qy0 * u0)) / sY - u, dvdy = cm::fma_(qy2, v2, cm::fma_(qy1, v1, qy0 * v0)) / sY - v;
+                const MaterialData& m = *reinterpret_cast<const MaterialData*>(mat);
+                const TextureData* slots = &m.m_AlbedoTexture;
+                cm::F3 albedo = { 1.0f, 1.0f, 1.0f }, mr = { 0.0f, 1.0f, 0.0f }, emissive = { 1.0f, 1.0f, 1.0f }, shaded = normal;
+                if (tex[0]) albedo = mtex::sample(*tex[0], tables, slots[0].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                if (tex[1]) {
+                    const cm::F3 ns = mtex::sample(*tex[1], tables, slots[1].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                    const float nx = 2.0f * ns.x - 1.0f, ny = 2.0f * ns.y - 1.0f;                   // TwoChannelNormalX2
+                    const cm::F3 unpacked = { nx, ny, cm::sqrt_(1.0f - cm::fma_(ny, ny, nx * nx)) };
+                    cm::F3 pc, pxx, pyy;                                                             // the world position at the three points
+                    pc = { cm::fma_(q2, wpos[2].x, cm::fma_(q1, wpos[1].x, q0 * wpos[0].x)) / s, cm::fma_(q2, wpos[2].y, cm::fma_(q1, wpos[1].y, q0 * wpos[0].y)) / s, cm::fma_(q2, wpos[2].z, cm::fma_(q1, wpos[1].z, q0 * wpos[0].z)) / s };
+                    pxx = { cm::fma_(qx2, wpos[2].x, cm::fma_(qx1, wpos[1].x, qx0 * wpos[0].x)) / sX, cm::fma_(qx2, wpos[2].y, cm::fma_(qx1, wpos[1].y, qx0 * wpos[0].y)) / sX, cm::fma_(qx2, wpos[2].z, cm::fma_(qx1, wpos[1].z, qx0 * wpos[0].z)) / sX };
+                    pyy = { cm::fma_(qy2, wpos[2].x, cm::fma_(qy1, wpos[1].x, qy0 * wpos[0].x)) / sY, cm::fma_(qy2, wpos[2].y, cm::fma_(qy1, wpos[1].y, qy0 * wpos[0].y)) / sY, cm::fma_(qy2, wpos[2].z, cm::fma_(qy1, wpos[1].z, qy0 * wpos[0].z)) / sY };
+                    const cm::F3 dp1 = { pxx.x - pc.x, pxx.y - pc.y, pxx.z - pc.z }, dp2 = { pyy.x - pc.x, pyy.y - pc.y, pyy.z - pc.z };
+                    const cm::F3 m2 = cm::cross3(dp1, dp2), inv0 = cm::cross3(dp2, m2), inv1 = cm::cross3(m2, dp1);   // CalculateTBNWithoutTangent
+                    const cm::F3 t = normalize3({ cm::fma_(dudy, inv1.x, dudx * inv0.x), cm::fma_(dudy, inv1.y, dudx * inv0.y), cm::fma_(dudy, inv1.z, dudx * inv0.z) });
+                    const cm::F3 b = normalize3({ cm::fma_(dvdy, inv1.x, dvdx * inv0.x), cm::fma_(dvdy, inv1.y, dvdx * inv0.y), cm::fma_(dvdy, inv1.z, dvdx * inv0.z) });
+                    shaded = normalize3(cm::mulVec(unpacked, t, b, normal));
+                }
+                if (tex[2]) mr = mtex::sample(*tex[2], tables, slots[2].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                if (tex[3]) emissive = mtex::sample(*tex[3], tables, slots[3].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                out.x = packRGBA8(mat[0] * albedo.x, mat[1] * albedo.y, mat[2] * albedo.z, debugValue);
+                out.y = packOctUnorm2x16(shaded);
+                out.z = packR9G9B9E5(mat[4] * emissive.x, mat[5] * emissive.y, mat[6] * emissive.z);
+                out.w = packRGBA8(mr.y, mr.z, 0.0f, 0.0f);                               // roughness = mr.g, metallic = mr.b
+            } else {
+                out.x = packRGBA8(mat[0], mat[1], mat[2], debugValue);
+                out.y = packOctUnorm2x16(normal);
+                out.z = packR9G9B9E5(mat[4], mat[5], mat[6]);
+                out.w = packRGBA8(1.0f, 0.0f, 0.0f, 0.0f);                               // roughness 1, metallic 0 (Q13)
+            }
             a.gbufferA[i] = out;                                                         // one 16-byte store per lane
         }
     });                                                                              // withMeshlet: nothing may follow, a chain out of bounds ends the pixel too
@@ -198,7 +297,7 @@ int recordResolve(trhip::DispatchCtx& ctx)
 {
     const BasePassConstants* k = (const BasePassConstants*)ctx.constants(0, sizeof(BasePassConstants));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (BasePassConstants, 256 bytes) missing", ctx.shaderName);
-    ResolveArgs a;
+    TexturedArgs a;                                                                  // ResolveArgs + the table; sliced when none is bound
     memset(&a, 0, sizeof a);
     a.k = *k;
     if (const int rc = bindGeometry(ctx, a.geo)) return rc;
@@ -244,8 +343,24 @@ int recordResolve(trhip::DispatchCtx& ctx)
     }
     a.width = W; a.height = H;
     const dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(resolveKernel<GBUFFER>, grid, dim3(kTileW, kTileH), 0, s, a);
+    if constexpr (GBUFFER) {
+        if (trhip_texture_table_t* table = ctx.textureTable(19)) {                   // t19: the TEXTURED instantiation
+            for (size_t d = 0; d < table->slots.size(); ++d)
+                TRHIP_REQUIRE(!table->slots[d] || !table->slots[d]->isUAV, "%s: the texture table at t19 holds '%s' at index %zu, created with the UAV or render-target bit: a sampled texture is read only",
+                              ctx.shaderName, table->slots[d]->name.c_str(), d);
+            TRHIP_REQUIRE(table->entries.ptr && ctx.cl->dev->srgbTable.ptr, "%s: the texture table at t19 has no device data", ctx.shaderName);
+            a.table = (const mtex::TableEntry*)table->entries.ptr;
+            a.tableCount = (uint32_t)table->slots.size();
+            a.srgb = (const float*)ctx.cl->dev->srgbTable.ptr;
+            ctx.emit("textured", [a, grid](hipStream_t s) {
+                TRHIP_LAUNCH((resolveKernel<true, true>), grid, dim3(kTileW, kTileH), 0, s, a);
+                return trhip::launchStatus("resolveKernel<gbuffer, textured>"); });
+            return TRHIP_OK;
+        }
+    }
+    const ResolveArgs plain = a;
+    ctx.emit("main", [plain, grid](hipStream_t s) {
+        TRHIP_LAUNCH(resolveKernel<GBUFFER>, grid, dim3(kTileW, kTileH), 0, s, plain);
         return trhip::launchStatus(GBUFFER ? "resolveKernel<gbuffer>" : "resolveKernel<motion>"); });
     return TRHIP_OK;
 }

@@ -15,7 +15,7 @@ from . import gtao as gtaomod
 from . import interop as I
 from . import rhi
 from . import sky as skymod
-from .rhi import CB, PUSH, SAMPLER, SRV, TEX_SRV, TEX_UAV, UAV
+from .rhi import CB, PUSH, SAMPLER, SRV, TEX_SRV, TEX_TABLE, TEX_UAV, UAV
 
 SLOT_NAMES = ("early_opaque", "late_opaque", "early_alphamask", "late_alphamask")
 
@@ -52,6 +52,7 @@ class GpuScene:
         self.numOpaque, self.numAlphaMask = len(opaqueIds), len(alphaMaskIds)
         self.vertices = self.meshletVertexIds = self.meshletTriangles = None
         self.materials = None
+        self.textures, self.texture_table, self.textured = [], None, False
         self.indices = self.rt = None
 
     def set_geometry(self, vertices, meshletVertexIds, meshletTriangles):
@@ -61,16 +62,46 @@ class GpuScene:
         self.meshletVertexIds = self.dev.buffer_from(np.ascontiguousarray(meshletVertexIds, np.uint32), "GlobalMeshletVertexIdxOffsetsBuffer", uav=False)
         self.meshletTriangles = self.dev.buffer_from(np.ascontiguousarray(meshletTriangles, np.uint32), "GlobalMeshletIndicesBuffer", uav=False)
 
+    def set_textures(self, textures):
+        """The material textures and their table (the stand-in of ResourceDescriptorHeap[...], include/trhip.h): `textures` is a
+        list of (mips, format), mips a list of uint8 [h_k, w_k, 4] arrays (level k of max(w >> k, 1) x max(h >> k, 1); interop.make_mips
+        makes them from an image), format rhi.FORMAT_RGBA8_UNORM or rhi.FORMAT_SRGBA8_UNORM.  Returns their descriptor indices, which
+        m_DescriptorIndex of a flagged TextureData names.  Replaces an earlier set; call it before set_materials()."""
+        self.release_textures()
+        if len(textures) == 0:
+            return []
+        self.texture_table = self.dev.create_texture_table(len(textures))
+        for i, (mips, fmt) in enumerate(textures):
+            self.textures.append(self.dev.create_sampled_texture(mips, fmt, f"Material Texture {i}"))
+            self.texture_table.set(i, self.textures[-1])
+        return list(range(len(textures)))
+
+    def release_textures(self):
+        if self.texture_table is not None:
+            self.texture_table.release()
+        for t in self.textures:
+            t.release()
+        self.textures, self.texture_table = [], None
+
     def set_materials(self, materials):
         """The MaterialData buffer (basepass.hlsl t3, Graphic::m_GlobalMaterialDataBuffer) that FrameDriver(gbuffer=True)
-        resolves GBufferA from.  Texture-free materials only: the resolve has no texture sampling."""
+        resolves GBufferA from.  A material may use textures (m_MaterialFlags) when every flagged slot's m_DescriptorIndex names a
+        texture of set_textures() and its feedback and min-mip indices are 0xFFFFFFFF (no texture streaming); FrameDriver then binds
+        the texture table and the resolve samples them."""
         materials = np.ascontiguousarray(materials, I.MaterialData)
-        if np.any(materials["m_MaterialFlags"] & I.kMaterialFlagAnyTexture):
-            raise ValueError("set_materials: a material uses a texture (m_MaterialFlags): textured materials are not supported")
+        for bit, slot in enumerate(("m_AlbedoTexture", "m_NormalTexture", "m_MetallicRoughnessTexture", "m_EmissiveTexture")):
+            flagged = (materials["m_MaterialFlags"] >> bit) & 1 != 0
+            t = materials[slot][flagged]
+            if np.any(t["m_DescriptorIndex"] >= len(self.textures)):
+                raise ValueError(f"set_materials: a material uses a texture ({slot}.m_DescriptorIndex {int(t['m_DescriptorIndex'][t['m_DescriptorIndex'] >= len(self.textures)][0]):#x}) "
+                                 f"that set_textures() has not loaded ({len(self.textures)} textures)")
+            if np.any(t["m_FeedbackTextureDescriptorIndex"] != 0xFFFFFFFF) or np.any(t["m_MinMapTextureDescriptorIndex"] != 0xFFFFFFFF):
+                raise ValueError(f"set_materials: a material's texture ({slot}) names a sampler-feedback or min-mip texture: texture streaming is not supported")
         if self.materials is not None:
             self.materials.release()
         self.materials = self.dev.buffer_from(materials, "GlobalMaterialDataBuffer", uav=False, min_bytes=124)
         self.numMaterials = len(materials)
+        self.textured = bool(np.any(materials["m_MaterialFlags"] & I.kMaterialFlagAnyTexture))
 
     def set_raytracing(self, indices, meshSpecific):
         """The acceleration structure FrameDriver(shadows=...) traces (include/trhip.h, "acceleration structure"): `indices` is the
@@ -111,6 +142,7 @@ class GpuScene:
 
     def release(self):
         self.release_raytracing()
+        self.release_textures()
         for b in (self.instances, self.meshData, self.meshlets, self.opaqueIds, self.alphaMaskIds, self.vertices, self.meshletVertexIds, self.meshletTriangles,
                   self.materials):
             if b is not None:
@@ -442,6 +474,8 @@ class FrameDriver:
                   SRV(14 + s, self.visibleList[s] if s < self.num_slots else self.dummy)]
         if self.gbuffer_on:                                                              # PS_Main_GBuffer: SV_Target0 + SV_Target1 in one dispatch
             b += [SRV(3, sc.materials), TEX_UAV(0, self.gbufferA, 0), TEX_UAV(1, self.motion, 0)]
+            if sc.textured:                                                              # any loaded material has a texture flag: the TEXTURED kernel
+                b.append(TEX_TABLE(sc.texture_table))
             cl.dispatch("basepass_PS_Main_GBuffer", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))
             return
         cl.dispatch("basepass_PS_Main_motion", b + [TEX_UAV(0, self.motion, 0)], ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1))

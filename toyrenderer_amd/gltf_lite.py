@@ -57,6 +57,7 @@ class LoadedScene:
     meshletTriangles: np.ndarray   # packed a | b << 8 | c << 16 (Visual.cpp:396-403)
     materials: np.ndarray = None   # MaterialData[n + 1]: the glTF's materials, then the default material (SceneLoading.cpp:396-537)
     primMaterial: np.ndarray = None   # u32 per primitive: index into materials (n where the primitive names none)
+    textures: list = None             # load(images=...): [(mips, format)] in descriptor-index order, for GpuScene.set_textures / Renderer.load_textures
 
     def as_oracle(self) -> dict:
         return dict(instances=self.instances, meshData=self.meshData, meshlets=self.meshlets,
@@ -77,6 +78,18 @@ def _accessor(g: dict, blobs: list, idx: int) -> np.ndarray:
     else:
         arr = np.stack([np.frombuffer(buf, dt, n, off + i * stride) for i in range(a["count"])])
     return arr.copy()
+
+
+def _accessor_uv(g: dict, blobs: list, idx: int) -> np.ndarray:
+    """float32 [n, 2] of a TEXCOORD accessor: floats as they are, normalized unsigned bytes / shorts divided by their maximum
+    (cgltf_accessor_unpack_floats)."""
+    a = g["accessors"][idx]
+    raw = _accessor(g, blobs, idx)
+    if raw.dtype.kind == "f":
+        return raw.astype(np.float32)[:, :2]
+    if not a.get("normalized", False) or raw.dtype.kind != "u":
+        raise ValueError(f"glTF-lite: TEXCOORD_0 accessor {idx}: float, or normalized unsigned byte / short components only")
+    return (raw.astype(np.float32) / np.float32(np.iinfo(raw.dtype).max))[:, :2]
 
 
 def _quat_mul(a, b):
@@ -367,12 +380,48 @@ def _no_textures(row):
             row[t][f] = 0xFFFFFFFF                     # SetTextureData without a texture (SceneLoading.cpp:486-497)
 
 
-def material_table(gltf_materials: list) -> np.ndarray:
-    """MaterialData[n + 1] as SceneLoader::LoadMaterials fills it (SceneLoading.cpp:396-537) for materials WITHOUT
-    textures: the G-buffer resolve has no texture sampling, so a material that names a texture raises.  The default
-    material comes last, at index n."""
+_FORMAT_RGBA8_UNORM, _FORMAT_SRGBA8_UNORM = 10, 11       # rhi.FORMAT_*: base colour and emissive are sRGB, normal and metallic-roughness linear
+_GLTF_CLAMP_TO_EDGE, _GLTF_REPEAT = 33071, 10497
+
+
+def material_table(gltf_materials: list, gltf: dict | None = None, images=None, textures: list | None = None) -> np.ndarray:
+    """MaterialData[n + 1] as SceneLoader::LoadMaterials fills it (SceneLoading.cpp:396-537).  The default material comes
+    last, at index n.  Without `images` a material that names a texture raises, naming the key.  With images (one uint8
+    [h, w, 4] array, or a list of mips, per glTF image) baseColorTexture, normalTexture, metallicRoughnessTexture and
+    emissiveTexture set their flag, m_GlobalIndex (the glTF texture index), m_IsWrapSampler (the texture's sampler: REPEAT 1,
+    CLAMP_TO_EDGE 0, none 1 as Visual.h:124; mirrored or mixed modes raise as the reference asserts) and m_DescriptorIndex: the
+    position in `textures`, to which each (glTF texture, format) pair is appended once as (mips, format) -- base colour and
+    emissive SRGBA8_UNORM, the others RGBA8_UNORM; an image given without mips gets interop.make_mips'.  The
+    specular-glossiness textures stay refused."""
     n = len(gltf_materials)
     out = np.zeros(n + 1, I.MaterialData)
+    loaded = {}                                            # (glTF texture, format) -> descriptor index
+
+    def bind(row, slot, flag, view, key, srgb, i, name):
+        tex = (gltf or {}).get("textures", [])
+        if not isinstance(view, dict) or "index" not in view or view["index"] >= len(tex):
+            raise ValueError(f"glTF-lite: material {i} [{name}]: {key} names no texture of the file")
+        t = tex[view["index"]]
+        if "source" not in t or t["source"] >= len(images):
+            raise ValueError(f"glTF-lite: material {i} [{name}]: {key}: texture {view['index']} has no image among the {len(images)} given")
+        wrap = 1
+        if "sampler" in t:
+            smp = gltf.get("samplers", [])[t["sampler"]]
+            ws, wt = smp.get("wrapS", _GLTF_REPEAT), smp.get("wrapT", _GLTF_REPEAT)
+            if ws != wt or ws not in (_GLTF_REPEAT, _GLTF_CLAMP_TO_EDGE):
+                raise ValueError(f"glTF-lite: material {i} [{name}]: {key}: sampler {t['sampler']} wraps {ws} / {wt}: REPEAT or CLAMP_TO_EDGE on both axes only")
+            wrap = int(ws == _GLTF_REPEAT)
+        fmt = _FORMAT_SRGBA8_UNORM if srgb else _FORMAT_RGBA8_UNORM
+        if (view["index"], fmt) not in loaded:
+            img = images[t["source"]]
+            mips = [np.ascontiguousarray(m, np.uint8) for m in img] if isinstance(img, (list, tuple)) else I.make_mips(img, srgb)
+            loaded[(view["index"], fmt)] = len(textures)
+            textures.append((mips, fmt))
+        row["m_MaterialFlags"] |= flag
+        row[slot]["m_GlobalIndex"] = view["index"]
+        row[slot]["m_IsWrapSampler"] = wrap
+        row[slot]["m_DescriptorIndex"] = loaded[(view["index"], fmt)]
+
     for i, m in enumerate(gltf_materials):
         row = out[i]
         _no_textures(row)
@@ -381,12 +430,20 @@ def material_table(gltf_materials: list) -> np.ndarray:
         sg = ext.get("KHR_materials_pbrSpecularGlossiness")
         mr = m.get("pbrMetallicRoughness")
         named = [k for k in ("emissiveTexture", "normalTexture") if k in m]
+        refused = []
         if sg is not None:
-            named += [k for k in ("diffuseTexture", "specularGlossinessTexture") if k in sg]
+            refused = [k for k in ("diffuseTexture", "specularGlossinessTexture") if k in sg]
         elif mr is not None:
             named += [k for k in ("baseColorTexture", "metallicRoughnessTexture") if k in mr]
-        if named:
-            raise ValueError(f"glTF-lite: material {i} [{name}] names a texture ({', '.join(named)}): textured materials are not supported")
+        if refused or (named and images is None):
+            raise ValueError(f"glTF-lite: material {i} [{name}] names a texture ({', '.join(named + refused)}): " +
+                             ("the specular-glossiness textures are not supported" if refused else "pass load(..., images=[...]) to load textured materials"))
+        for key, slot, flag, srgb in (("baseColorTexture", "m_AlbedoTexture", I.MaterialFlag_UseAlbedoTexture, True),
+                                      ("normalTexture", "m_NormalTexture", I.MaterialFlag_UseNormalTexture, False),
+                                      ("metallicRoughnessTexture", "m_MetallicRoughnessTexture", I.MaterialFlag_UseMetallicRoughnessTexture, False),
+                                      ("emissiveTexture", "m_EmissiveTexture", I.MaterialFlag_UseEmissiveTexture, True)):
+            if key in named:
+                bind(row, slot, flag, (mr if key in ("baseColorTexture", "metallicRoughnessTexture") else m)[key], key, srgb, i, name)
         row["m_AlphaCutoff"] = m.get("alphaCutoff", 0.5)
         e = np.asarray(m.get("emissiveFactor", (0.0, 0.0, 0.0)), np.float32)
         if np.float32(np.float32(e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) > _KINDA_SMALL_NUMBER:              # :402-410
@@ -420,8 +477,10 @@ def apply_materials(scene: "LoadedScene") -> np.ndarray:
 
 
 # ----------------------------------------------------------------------------------------------- loader
-def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
-    """lods=False: LOD 0 only (no simplification)."""
+def load(path_or_gltf, blobs=None, lods: bool = True, images=None) -> LoadedScene:
+    """lods=False: LOD 0 only (no simplification).  images: one decoded image per glTF image (uint8 [h, w, 4], or its list of
+    mips); decoding PNG or JPEG is the caller's business.  With it the textured materials load (material_table) and
+    LoadedScene.textures lists what to upload; without it a material that names a texture raises."""
     if isinstance(path_or_gltf, dict):
         g = path_or_gltf
         blobs = list(blobs or [])
@@ -477,6 +536,8 @@ def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
                 nrm = np.clip(_accessor(g, blobs, prim["attributes"]["NORMAL"]).astype(np.float32), -1, 1)
                 q = np.round((nrm * 0.5 + 0.5) * 1023.0).astype(np.uint32)
                 vrows["m_PackedNormal"] = (q[:, 0] << 20) | (q[:, 1] << 10) | q[:, 2]
+            if "TEXCOORD_0" in prim["attributes"]:                                   # Half2 of the first UV set only (SceneLoading.cpp:623-629)
+                vrows["m_TexCoord"] = _accessor_uv(g, blobs, prim["attributes"]["TEXCOORD_0"]).astype(np.float16).view(np.uint16)
             vtx.append(vrows)
             prims.append((len(md_rows), mat.get("alphaMode", "OPAQUE") == "MASK",
                           prim["material"] if "material" in prim and prim["material"] < len(materials) else len(materials)))
@@ -535,10 +596,11 @@ def load(path_or_gltf, blobs=None, lods: bool = True) -> LoadedScene:
 
     def stack(rows, dt):
         return np.array(rows, dt) if rows else np.zeros(0, dt)
+    textures = [] if images is not None else None
     return LoadedScene(stack(inst_rows, I.BasePassInstanceConstants), stack(md_rows, I.MeshData), stack(ml_rows, I.MeshletData),
                        np.array(opaque, np.uint32), np.array(alpha, np.uint32), nodes, np.array(prim_to_node, np.uint32), cameras,
                        np.concatenate(vtx) if vtx else np.zeros(0, I.RawVertexFormat), np.array(mvid, np.uint32), np.array(mtri, np.uint32),
-                       material_table(materials), np.array(prim_material, np.uint32))
+                       material_table(materials, g, images, textures), np.array(prim_material, np.uint32), textures)
 
 
 def view_of(camera: Camera, render=(1920, 1080)):

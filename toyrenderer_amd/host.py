@@ -25,7 +25,7 @@ HOST_SYMBOLS = [
     "trhost_rccl_allgather", "trhost_exchange_create", "trhost_exchange_run", "trhost_exchange_wait", "trhost_exchange_outputs",
     "trhost_exchange_destroy", "trhost_load_geometry", "trhost_set_raster_depth", "trhost_download_depth",
     "trhost_set_visibility_buffer", "trhost_download_visibility", "trhost_download_motion",
-    "trhost_load_materials", "trhost_set_gbuffer", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
+    "trhost_load_materials", "trhost_create_material_texture", "trhost_set_gbuffer", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
@@ -94,6 +94,7 @@ def load() -> C.CDLL:
     L.trhost_download_visibility.argtypes = [vp, u64]
     L.trhost_download_motion.argtypes = [vp, u64]
     L.trhost_load_materials.argtypes = [vp, u32]
+    L.trhost_create_material_texture.argtypes = [u32, u32, u32, u32, vp, u64]
     L.trhost_set_gbuffer.argtypes = [C.c_int]
     L.trhost_set_debug_view_mode.argtypes = [u32]
     L.trhost_download_gbuffer_a.argtypes = [vp, u64]
@@ -282,8 +283,24 @@ class Renderer:
         _check(load().trhost_download_motion(m.ctypes.data, m.nbytes))
         return m
 
+    def create_material_texture(self, mips, fmt: int) -> int:
+        """One material texture from its mips (uint8 [h_k, w_k, 4] arrays), fmt rhi.FORMAT_RGBA8_UNORM or FORMAT_SRGBA8_UNORM; returns
+        the descriptor index a flagged TextureData.m_DescriptorIndex names (include/trhost.h)."""
+        mips = [np.ascontiguousarray(m, np.uint8) for m in mips]
+        if not mips or any(m.ndim != 3 or m.shape[2] != 4 for m in mips):
+            raise ValueError("mips: a non-empty list of uint8 [h, w, 4] arrays")
+        data = np.concatenate([m.reshape(-1) for m in mips])
+        index = load().trhost_create_material_texture(mips[0].shape[1], mips[0].shape[0], len(mips), int(fmt), data.ctypes.data, data.nbytes)
+        if index < 0:
+            _check(-1)
+        return index
+
+    def load_textures(self, textures):
+        """[(mips, format)] -> descriptor indices, as GpuScene.set_textures; before load_materials."""
+        return [self.create_material_texture(m, f) for m, f in textures]
+
     def load_materials(self, materials):
-        """MaterialData[] for the G-buffer resolve (texture-free materials; include/trhost.h)."""
+        """MaterialData[] for the G-buffer resolve; a textured material names textures created before (include/trhost.h)."""
         m = np.ascontiguousarray(materials, I.MaterialData)
         _check(load().trhost_load_materials(m.ctypes.data, len(m)))
 

@@ -221,3 +221,41 @@ def fmaf(a, b, c) -> np.float32:
     if err != 0 and np.isfinite(s) and (np.float64(s).view(np.int64) & 1) == 0:
         s = np.nextafter(s, np.inf if err > 0 else -np.inf)
     return np.float32(s)
+
+
+def srgb_to_linear(c):
+    """The sRGB transfer function (float64): what SRGBA8_UNORM texels are decoded with (rhi.srgb_table rounds it to float)."""
+    c = np.asarray(c, np.float64)
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
+
+
+def linear_to_srgb(x):
+    x = np.asarray(x, np.float64)
+    return np.where(x <= 0.0031308, x * 12.92, 1.055 * np.maximum(x, 0.0) ** (1.0 / 2.4) - 0.055)
+
+
+def make_mips(image, srgb: bool, levels: int | None = None):
+    """The mip chain of a uint8 [h, w, 4] image, level k of max(w >> k, 1) x max(h >> k, 1) texels (the back end's rule), down to
+    1 x 1 or `levels` levels: a 2 x 2 box in linear light, in float64, rounded once per level (half to even).  Texel (x, y) of a
+    level averages columns 2x and min(2x + 1, w - 1) and rows 2y and min(2y + 1, h - 1) of the level above, itself kept in
+    float64 (an odd last column or row is dropped, a 1-texel axis is repeated).  srgb: R, G and B are decoded with the sRGB
+    transfer function before the box and encoded after it; alpha is linear.  The reference ships its mips inside its DDS
+    files; an application with its own mips passes them instead."""
+    img = np.ascontiguousarray(image, np.uint8)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("image: uint8 [h, w, 4]")
+    lin = img.astype(np.float64) / 255.0
+    if srgb:
+        lin[..., :3] = srgb_to_linear(lin[..., :3])
+    out = [img.copy()]
+    while (lin.shape[0] > 1 or lin.shape[1] > 1) and (levels is None or len(out) < levels):
+        h, w = lin.shape[:2]
+        nh, nw = max(h >> 1, 1), max(w >> 1, 1)
+        y0, x0 = 2 * np.arange(nh), 2 * np.arange(nw)
+        y1, x1 = np.minimum(y0 + 1, h - 1), np.minimum(x0 + 1, w - 1)
+        lin = ((lin[y0][:, x0] + lin[y0][:, x1]) + (lin[y1][:, x0] + lin[y1][:, x1])) * 0.25
+        enc = lin.copy()
+        if srgb:
+            enc[..., :3] = linear_to_srgb(enc[..., :3])
+        out.append(np.rint(np.clip(enc, 0.0, 1.0) * 255.0).astype(np.uint8))
+    return out

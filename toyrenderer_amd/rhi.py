@@ -22,10 +22,12 @@ FORMAT_R11G11B10_FLOAT = 6  # LightingOutput: one u32 per texel, R bits 0-10, G 
 FORMAT_R8_UNORM = 7       # shadow mask: one byte per texel
 FORMAT_R8_UINT = 8        # SSAO texture: one byte per texel
 FORMAT_RGBA8_UNORM = 10   # back buffer: one u32 per texel, R in the low byte (9 is not a format)
+FORMAT_SRGBA8_UNORM = 11  # RGBA8_UNORM's layout; R, G, B decoded through the sRGB transfer function when sampled
 
 TEXTURE_RENDER_TARGET = 2   # or'ed into trhip_texture_desc.isUAV
 
-BIND_CONSTANT_BUFFER, BIND_PUSH_CONSTANTS, BIND_STRUCTURED_SRV, BIND_STRUCTURED_UAV, BIND_TEXTURE_SRV, BIND_TEXTURE_UAV, BIND_SAMPLER = range(7)
+BIND_CONSTANT_BUFFER, BIND_PUSH_CONSTANTS, BIND_STRUCTURED_SRV, BIND_STRUCTURED_UAV, BIND_TEXTURE_SRV, BIND_TEXTURE_UAV, BIND_SAMPLER, BIND_TEXTURE_TABLE = range(8)
+TEXTURE_TABLE_SLOT = 19   # t19 of "basepass_PS_Main_GBuffer": the first slot after the visibility buffer's t18
 
 # every symbol include/trhip.h declares (checked by tests/test_abi_symbols.py)
 ABI_SYMBOLS = [
@@ -39,6 +41,8 @@ ABI_SYMBOLS = [
     "trhip_texture_release", "trhip_texture_device_ptr", "trhip_texture_mip_info", "trhip_texture_size",
     "trhip_buffer_upload", "trhip_buffer_download", "trhip_texture_upload", "trhip_texture_download",
     "trhip_buffer_mark_written", "trhip_texture_mark_written",
+    "trhip_texture_table_create", "trhip_texture_table_retain", "trhip_texture_table_release", "trhip_texture_table_capacity",
+    "trhip_texture_table_set", "trhip_texture_table_clear", "trhip_srgb_table",
     "trhip_cmd_create", "trhip_cmd_release", "trhip_cmd_open", "trhip_cmd_close", "trhip_cmd_write_buffer",
     "trhip_cmd_clear_buffer_u32", "trhip_cmd_clear_texture_f32", "trhip_cmd_clear_texture_u32", "trhip_cmd_copy_buffer", "trhip_cmd_copy_texture", "trhip_cmd_host_callback", "trhip_cmd_dispatch", "trhip_cmd_dispatch_indirect",
     "trhip_cmd_begin_timer", "trhip_cmd_end_timer", "trhip_cmd_begin_marker", "trhip_cmd_end_marker",
@@ -123,8 +127,18 @@ def load() -> C.CDLL:
     L.trhip_buffer_wrap.argtypes = [vp, vp, C.POINTER(BufferDesc), C.POINTER(vp)]
     L.trhip_buffer_memory_requirements.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.trhip_buffer_bind_memory.argtypes = [vp, vp, u64]
+    # An older build named by TRHIP_LIB (tools/material_texture_cost.py --baseline-lib) has no texture table: its texture-free
+    # frames still run, TextureTable and srgb_table raise.  lib/libtrhip.so itself exports them (tests/test_abi_symbols.py).
+    has_tables = hasattr(L, "trhip_texture_table_create")
+    if has_tables:
+        L.trhip_texture_table_create.argtypes = [vp, u32, C.POINTER(vp)]
+        L.trhip_texture_table_capacity.argtypes = [vp]
+        L.trhip_texture_table_capacity.restype = u32
+        L.trhip_texture_table_set.argtypes = [vp, u32, vp]
+        L.trhip_texture_table_clear.argtypes = [vp, u32]
+        L.trhip_srgb_table.argtypes = [vp]
     for n in ("trhip_buffer_retain", "trhip_buffer_release", "trhip_texture_retain", "trhip_texture_release",
-              "trhip_cmd_release", "trhip_timer_release"):
+              "trhip_cmd_release", "trhip_timer_release") + (("trhip_texture_table_retain", "trhip_texture_table_release") if has_tables else ()):
         getattr(L, n).argtypes = [vp]
         getattr(L, n).restype = None
     L.trhip_buffer_device_ptr.argtypes = [vp]
@@ -201,6 +215,15 @@ def _check(rc: int):
         raise TrhipError(f"trhip error {rc}: {load().trhip_last_error().decode(errors='replace')}")
 
 
+def srgb_table() -> np.ndarray:
+    """trhip_srgb_table: the 256 floats SRGBA8_UNORM texels decode to (no device needed)."""
+    out = np.empty(256, np.float32)
+    if not hasattr(load(), "trhip_srgb_table"):
+        raise TrhipError(f"{LIB_PATH} has no trhip_srgb_table: a build from before textured materials")
+    _check(load().trhip_srgb_table(out.ctypes.data))
+    return out
+
+
 def shader_names():
     L = load()
     return [L.trhip_shader_name(i).decode() for i in range(L.trhip_shader_count())]
@@ -247,12 +270,15 @@ class Texture:
 
     def _dtype(self):
         return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32,
-                FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8, FORMAT_RGBA8_UNORM: np.uint32}.get(self.format, np.float32)
+                FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8, FORMAT_RGBA8_UNORM: np.uint32,
+                FORMAT_SRGBA8_UNORM: np.uint32}.get(self.format, np.float32)
 
     def _shape(self, mw: int, mh: int):
         return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw, 4) if self.format == FORMAT_RGBA32_UINT else (mh, mw)
 
     def upload_mip(self, k: int, arr: np.ndarray):
+        if self.format in (FORMAT_RGBA8_UNORM, FORMAT_SRGBA8_UNORM) and np.asarray(arr).dtype == np.uint8:   # [h, w, 4] bytes R, G, B, A
+            arr = np.ascontiguousarray(arr).reshape(-1).view(np.uint32)
         arr = np.ascontiguousarray(arr, self._dtype())
         _check(load().trhip_texture_upload(self.h, k, arr.ctypes.data, arr.nbytes))
 
@@ -295,6 +321,24 @@ def UAV(slot, buf): return bind(BIND_STRUCTURED_UAV, slot, buf)
 def TEX_SRV(slot, tex, mip=0): return bind(BIND_TEXTURE_SRV, slot, tex, mip)   # mip: read by bloom_PS_* only
 def TEX_UAV(slot, tex, mip=0): return bind(BIND_TEXTURE_UAV, slot, tex, mip)
 def SAMPLER(slot): return bind(BIND_SAMPLER, slot)
+def TEX_TABLE(table, slot=TEXTURE_TABLE_SLOT): return bind(BIND_TEXTURE_TABLE, slot, table)
+
+
+class TextureTable:
+    """trhip_texture_table: descriptor index -> texture, the stand-in of ResourceDescriptorHeap[...] (include/trhip.h)."""
+    def __init__(self, dev, handle, capacity: int):
+        self.dev, self.h, self.capacity = dev, handle, capacity
+
+    def set(self, index: int, tex: "Texture"):
+        _check(load().trhip_texture_table_set(self.h, index, tex.h))
+
+    def clear(self, index: int):
+        _check(load().trhip_texture_table_clear(self.h, index))
+
+    def release(self):
+        if self.h:
+            load().trhip_texture_table_release(self.h)
+            self.h = None
 
 
 class Timer:
@@ -450,6 +494,30 @@ class Device:
         hd = C.c_void_p()
         _check(load().trhip_texture_create(self.h, C.byref(d), C.byref(hd)))
         return Texture(self, hd, w, h, mips, fmt, name)
+
+    def create_texture_table(self, capacity: int) -> TextureTable:
+        h = C.c_void_p()
+        if not hasattr(load(), "trhip_texture_table_create"):
+            raise TrhipError(f"{LIB_PATH} has no texture table: a build from before textured materials")
+        _check(load().trhip_texture_table_create(self.h, capacity, C.byref(h)))
+        return TextureTable(self, h, capacity)
+
+    def create_sampled_texture(self, mips, fmt: int, name="") -> Texture:
+        """A material texture from its mip chain: mips = uint8 arrays [h_k, w_k, 4] (R, G, B, A), level k of
+        max(w >> k, 1) x max(h >> k, 1); fmt = FORMAT_RGBA8_UNORM or FORMAT_SRGBA8_UNORM.  Created without the UAV bit."""
+        if fmt not in (FORMAT_RGBA8_UNORM, FORMAT_SRGBA8_UNORM):
+            raise ValueError(f"a sampled texture is RGBA8_UNORM or SRGBA8_UNORM, not format {fmt}")
+        mips = [np.ascontiguousarray(m, np.uint8) for m in mips]
+        if not mips or any(m.ndim != 3 or m.shape[2] != 4 for m in mips):
+            raise ValueError("mips: a non-empty list of uint8 [h, w, 4] arrays")
+        h0, w0 = mips[0].shape[:2]
+        for k, m in enumerate(mips):
+            if m.shape[:2] != (max(h0 >> k, 1), max(w0 >> k, 1)):
+                raise ValueError(f"mip {k} is {m.shape[1]} x {m.shape[0]}, expected {max(w0 >> k, 1)} x {max(h0 >> k, 1)}")
+        t = self.create_texture(w0, h0, len(mips), fmt, name, uav=False)
+        for k, m in enumerate(mips):
+            t.upload_mip(k, m)
+        return t
 
     def create_command_list(self) -> CommandList:
         h = C.c_void_p()
