@@ -1,13 +1,12 @@
 // gbuffer_unpack.hip.h -- UnpackGBuffer (lightingcommon.hlsli:36-51) for the passes that read GBufferA: the lighting pass
-// (k_deferredlighting.hip, which states the convention) and the shadow mask's trace (k_shadowmask.hip, which reads the normal).
+// (k_deferredlighting.hip, which states UnpackGBuffer's convention) and the shadow mask's trace (k_shadowmask.hip, which reads the normal).
 #pragma once
 
-#include "cull_math.hip.h"
+#include "screen_pass.hip.h"
 
 namespace gbuf
 {
 
-__device__ __forceinline__ float saturate_(float x) { return cm::min_(cm::max_(x, 0.0f), 1.0f); }
 __device__ __forceinline__ cm::F3 normalize_(cm::F3 v)
 {
     const float len = cm::sqrt_(cm::dot3(v, v));
@@ -26,7 +25,7 @@ __device__ __forceinline__ GBufferParams unpackGBuffer(uint4 g)                 
     p.debugValue = unorm8(g.x >> 24);
     const float fx = unorm16(g.y & 0xFFFFu) * 2.0f - 1.0f, fy = unorm16(g.y >> 16) * 2.0f - 1.0f;   // packunpack.hlsli:17-26
     cm::F3 n = { fx, fy, (1.0f - __builtin_fabsf(fx)) - __builtin_fabsf(fy) };
-    const float t = saturate_(-n.z);
+    const float t = sp::saturate_(-n.z);
     n.x += n.x >= 0.0f ? -t : t;
     n.y += n.y >= 0.0f ? -t : t;
     p.normal = normalize_(n);

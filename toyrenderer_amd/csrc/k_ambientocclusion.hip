@@ -31,8 +31,8 @@
 // diverge.  -DTR_AO_EXPERIMENT_HW_TRIG (tools/ao_cost.py only, never the product, not bit-exact) replaces the software sine, cosine,
 // log2 and exp2 by the hardware's approximations to show what exactness costs.  Code object and measurements: profiles/ao/README.md.
 #include "cull_math.hip.h"
+#include "screen_pass.hip.h"
 #include "soft_math.hip.h"
-#include "trhip_internal.h"
 
 namespace
 {
@@ -72,9 +72,7 @@ __device__ __forceinline__ H3 hcross(H3 a, H3 b)
 }
 __device__ __forceinline__ hf hsign(hf x) { return x > (hf)0.0f ? (hf)1.0f : x < (hf)0.0f ? (hf)-1.0f : (hf)0.0f; }
 __device__ __forceinline__ uint32_t toUint(float x) { return !(x >= 0.0f) ? 0u : x >= 4294967296.0f ? 0xFFFFFFFFu : (uint32_t)x; }
-__device__ __forceinline__ float clampf(float x, float lo, float hi) { return cm::min_(cm::max_(x, lo), hi); }
-__device__ __forceinline__ hf halfOf(uint16_t w) { return __builtin_bit_cast(hf, w); }
-__device__ __forceinline__ uint16_t bitsOf(hf h) { return h != h ? (uint16_t)0x7E00u : __builtin_bit_cast(uint16_t, h); }   // every NaN is stored as one word
+using sp::halfOf;
 
 // the literals of XeGTAO.hlsli as binary16 (tests/gtao_ref.c has the same table)
 constexpr hf H_PI = (hf)0x1.92p+1f, H_PI_HALF = (hf)0x1.92p+0f, H_GOLDEN = (hf)0x1.3c8p-1f, H_0_9992 = (hf)0x1.ff8p-1f, H_1_3 = (hf)0x1.4ccp+0f;
@@ -140,7 +138,7 @@ struct PrefilterArgs
 
 __device__ __forceinline__ hf viewDepth(float d, const GTAOConstants& k)
 {
-    return r16(clampf(cm::div_(k.DepthUnpackConsts.x, k.DepthUnpackConsts.y - d), 0.0f, 65504.0f));
+    return r16(cm::clamp_(cm::div_(k.DepthUnpackConsts.x, k.DepthUnpackConsts.y - d), 0.0f, 65504.0f));
 }
 
 __device__ __forceinline__ void falloffTerms(const GTAOConstants& k, hf effectRadius, hf& mul, hf& add)
@@ -165,19 +163,19 @@ __device__ __forceinline__ hf mipFilter(hf d0, hf d1, hf d2, hf d3, hf mul, hf a
 __global__ __launch_bounds__(kAoGroup * kAoGroup) void aoPrefilterKernel(PrefilterArgs a)
 {
     __shared__ hf scratch[8][8];
-    const uint32_t tx = threadIdx.x, ty = threadIdx.y, bx = blockIdx.x * 8u + tx, by = blockIdx.y * 8u + ty, px = bx * 2u, py = by * 2u;
+    const uint32_t tx = threadIdx.x, ty = threadIdx.y, bx = blockIdx.x * kAoGroup + tx, by = blockIdx.y * kAoGroup + ty, px = bx * 2u, py = by * 2u;   // one 2 x 2 quad per thread
     const uint32_t W = a.w[0], H = a.h[0];
     const uint32_t x0 = clampi((int32_t)px, W), x1 = clampi((int32_t)px + 1, W), y0 = clampi((int32_t)py, H), y1 = clampi((int32_t)py + 1, H);
     const hf d0 = viewDepth(a.depth[(uint64_t)y0 * W + x0], a.k), d1 = viewDepth(a.depth[(uint64_t)y0 * W + x1], a.k);
     const hf d2 = viewDepth(a.depth[(uint64_t)y1 * W + x0], a.k), d3 = viewDepth(a.depth[(uint64_t)y1 * W + x1], a.k);
-    if (px < W && py < H) a.mip[0][(uint64_t)py * W + px] = bitsOf(d0);
-    if (px + 1u < W && py < H) a.mip[0][(uint64_t)py * W + px + 1u] = bitsOf(d1);
-    if (px < W && py + 1u < H) a.mip[0][(uint64_t)(py + 1u) * W + px] = bitsOf(d2);
-    if (px + 1u < W && py + 1u < H) a.mip[0][(uint64_t)(py + 1u) * W + px + 1u] = bitsOf(d3);
+    if (px < W && py < H) a.mip[0][(uint64_t)py * W + px] = sp::halfBits((float)d0);
+    if (px + 1u < W && py < H) a.mip[0][(uint64_t)py * W + px + 1u] = sp::halfBits((float)d1);
+    if (px < W && py + 1u < H) a.mip[0][(uint64_t)(py + 1u) * W + px] = sp::halfBits((float)d2);
+    if (px + 1u < W && py + 1u < H) a.mip[0][(uint64_t)(py + 1u) * W + px + 1u] = sp::halfBits((float)d3);
     hf mul, add;                                                           // XeGTAO_DepthMIPFilter's uniform terms
     falloffTerms(a.k, hmul(hmul((hf)0.75f, r16(a.k.EffectRadius)), H_1_457), mul, add);
     const hf dm1 = mipFilter(d0, d1, d2, d3, mul, add);
-    if (bx < a.w[1] && by < a.h[1]) a.mip[1][(uint64_t)by * a.w[1] + bx] = bitsOf(dm1);
+    if (bx < a.w[1] && by < a.h[1]) a.mip[1][(uint64_t)by * a.w[1] + bx] = sp::halfBits((float)dm1);
     scratch[tx][ty] = dm1;
     __syncthreads();
 #pragma unroll
@@ -186,7 +184,7 @@ __global__ __launch_bounds__(kAoGroup * kAoGroup) void aoPrefilterKernel(Prefilt
         if ((tx & (step - 1u)) == 0u && (ty & (step - 1u)) == 0u) {
             const hf v = mipFilter(scratch[tx][ty], scratch[tx + half][ty], scratch[tx][ty + half], scratch[tx + half][ty + half], mul, add);
             const uint32_t ox = bx >> (level - 1u), oy = by >> (level - 1u);
-            if (ox < a.w[level] && oy < a.h[level]) a.mip[level][(uint64_t)oy * a.w[level] + ox] = bitsOf(v);
+            if (ox < a.w[level] && oy < a.h[level]) a.mip[level][(uint64_t)oy * a.w[level] + ox] = sp::halfBits((float)v);
             scratch[tx][ty] = v;
         }
         __syncthreads();
@@ -228,9 +226,9 @@ __device__ __forceinline__ cm::F3 viewPosition(float sx, float sy, float depth, 
 }
 __device__ __forceinline__ float sampleLevel(const DepthChain& c, float u, float v, hf mip)
 {
-    const int level = (int)clampf(__builtin_floorf((float)mip + 0.5f), 0.0f, 4.0f);
+    const int level = (int)cm::clamp_(__builtin_floorf((float)mip + 0.5f), 0.0f, 4.0f);
     const uint32_t w = c.w[level], h = c.h[level];
-    const uint32_t x = (uint32_t)clampf(__builtin_floorf(u * (float)w), 0.0f, (float)(w - 1u)), y = (uint32_t)clampf(__builtin_floorf(v * (float)h), 0.0f, (float)(h - 1u));
+    const uint32_t x = (uint32_t)cm::clamp_(__builtin_floorf(u * (float)w), 0.0f, (float)(w - 1u)), y = (uint32_t)cm::clamp_(__builtin_floorf(v * (float)h), 0.0f, (float)(h - 1u));
     return (float)halfOf(c.mip[level][(uint64_t)y * w + x]);
 }
 
@@ -253,9 +251,9 @@ __device__ __forceinline__ cm::F3 viewNormal(uint4 g, const XeGTAOMainPassConsta
 
 __global__ __launch_bounds__(kAoGroup * kAoGroup) void aoMainKernel(MainArgs a)
 {
-    const uint32_t px = blockIdx.x * kAoGroup + threadIdx.x, py = blockIdx.y * kAoGroup + threadIdx.y;
-    const uint32_t W = a.chain.w[0], H = a.chain.h[0];
-    if (px >= W || py >= H) return;
+    const sp::Pixel at = sp::pixel<kAoGroup, kAoGroup>();
+    const uint32_t px = at.x, py = at.y, W = a.chain.w[0], H = a.chain.h[0];
+    if (!at.inside(W, H)) return;
     const GTAOConstants& k = a.k;
     const uint32_t quality = a.push.m_Quality < 4u ? a.push.m_Quality : 0u;
     const hf sliceCount = quality == 0u ? (hf)1.0f : quality == 1u ? (hf)2.0f : quality == 2u ? (hf)3.0f : (hf)9.0f;
@@ -319,7 +317,7 @@ __global__ __launch_bounds__(kAoGroup * kAoGroup) void aoMainKernel(MainArgs a)
             s = hadd(s, minS);
             hf offX = hmul(s, omegaX), offY = hmul(s, omegaY);
             const hf sampleOffsetLength = hsqrt(hdot2(offX, offY, offX, offY));
-            const hf mipLevel = r16(clampf((float)hlog2(sampleOffsetLength) - k.DepthMIPSamplingOffset, 0.0f, 5.0f));
+            const hf mipLevel = r16(cm::clamp_((float)hlog2(sampleOffsetLength) - k.DepthMIPSamplingOffset, 0.0f, 5.0f));
             offX = hmul(hrint(offX), pixelSizeX); offY = hmul(hrint(offY), pixelSizeY);
 
             const float u0 = nspx + (float)offX, v0 = nspy + (float)offY, u1 = nspx - (float)offX, v1 = nspy - (float)offY;
@@ -422,22 +420,17 @@ const GTAOConstants* gtaoConstants(trhip::DispatchCtx& ctx)
 // t0 of the main pass, u0..u4 of the prefilter: one R16_FLOAT texture of exactly 5 mips
 bool isDepthChain(const trhip_texture_t* t) { return t && t->format == TRHIP_FORMAT_R16_FLOAT && t->mips == 5; }
 
-bool isPlane(const trhip_texture_t* t, uint32_t format, uint32_t mip, uint32_t W, uint32_t H)
-{
-    return t && t->format == format && t->mips == 1 && mip == 0 && t->width == W && t->height == H;
-}
-
 int recordPrefilter(trhip::DispatchCtx& ctx)
 {
     const char* name = ctx.shaderName;
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 16x16-pixel groups", name);
     const GTAOConstants* k = gtaoConstants(ctx);
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (GTAOConstants, 96 bytes) missing or of another size", name);
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R32_FLOAT, "Texture_SRV t0 = the R32_FLOAT depth buffer (one mip)", true, sp::kOneMipAt0 } };
+    trhip_texture_t* depthAt[1];
+    if (const int rc = sp::bindTextures(ctx, want, depthAt)) return rc;
+    const trhip_texture_t* depth = depthAt[0];
     uint32_t mip = 0;
-    trhip_texture_t* depth = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 0, &mip);
-    TRHIP_REQUIRE(depth && depth->format == TRHIP_FORMAT_R32_FLOAT && depth->mips == 1 && mip == 0, "%s: needs Texture_SRV t0 = the R32_FLOAT depth buffer (one mip)", name);
-    PrefilterArgs a;
-    memset(&a, 0, sizeof a);
+    PrefilterArgs a = sp::zeroed<PrefilterArgs>();
     trhip_texture_t* chain = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 0, &mip);
     TRHIP_REQUIRE(isDepthChain(chain), "%s: needs Texture_UAV u0..u4 = mips 0..4 of one R16_FLOAT texture with 5 mips", name);
     TRHIP_REQUIRE(chain->width == depth->width && chain->height == depth->height, "%s: t0 is %ux%u, the working depth chain %ux%u", name, depth->width,
@@ -450,81 +443,65 @@ int recordPrefilter(trhip::DispatchCtx& ctx)
     }
     a.k = *k;
     a.depth = (const float*)depth->ptr;
-    const uint32_t gx = (a.w[0] + 15u) / 16u, gy = (a.h[0] + 15u) / 16u;
-    TRHIP_REQUIRE(ctx.gx >= gx && ctx.gy >= gy, "%s: a direct dispatch of 16x16-pixel groups covering %ux%u", name, a.w[0], a.h[0]);
-    const dim3 grid(gx, gy);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(aoPrefilterKernel, grid, dim3(kAoGroup, kAoGroup), 0, s, a);
-        return trhip::launchStatus("aoPrefilterKernel"); });
+    if (const int rc = sp::requireCover(ctx, 2u * kAoGroup, 2u * kAoGroup, a.w[0], a.h[0])) return rc;   // one 2 x 2 quad per thread
+    sp::launch(ctx, aoPrefilterKernel, "aoPrefilterKernel", sp::tiles(a.w[0], a.h[0], 2u * kAoGroup, 2u * kAoGroup), dim3(kAoGroup, kAoGroup), a);
     return TRHIP_OK;
 }
 
 int recordMain(trhip::DispatchCtx& ctx)
 {
     const char* name = ctx.shaderName;
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 8x8-pixel groups", name);
     const GTAOConstants* k = gtaoConstants(ctx);
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (GTAOConstants, 96 bytes) missing or of another size", name);
     const XeGTAOMainPassConstantBuffer* push = (const XeGTAOMainPassConstantBuffer*)ctx.constants(1, sizeof(XeGTAOMainPassConstantBuffer));
     TRHIP_REQUIRE(push && ctx.pushBytes == sizeof(XeGTAOMainPassConstantBuffer), "%s: push constants b1 (XeGTAOMainPassConstantBuffer, 68 bytes) missing or of another size", name);
-    uint32_t mip = 0, aoMip = 0, edgeMip = 0, gMip = 0;
+    uint32_t mip = 0;
     trhip_texture_t* chain = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 0, &mip);
     TRHIP_REQUIRE(isDepthChain(chain) && mip == 0, "%s: needs Texture_SRV t0 = the R16_FLOAT working depth chain with 5 mips", name);
     const uint32_t W = chain->width, H = chain->height;
-    trhip_texture_t* g = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 2, &gMip);
-    TRHIP_REQUIRE(isPlane(g, TRHIP_FORMAT_RGBA32_UINT, gMip, W, H), "%s: needs Texture_SRV t2 = GBufferA (RGBA32_UINT) of %ux%u", name, W, H);
-    trhip_texture_t* ao = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 0, &aoMip);
-    TRHIP_REQUIRE(isPlane(ao, TRHIP_FORMAT_R8_UINT, aoMip, W, H), "%s: needs Texture_UAV u0 = the working AO term (R8_UINT) of %ux%u", name, W, H);
-    trhip_texture_t* edges = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 1, &edgeMip);
-    TRHIP_REQUIRE(isPlane(edges, TRHIP_FORMAT_R8_UNORM, edgeMip, W, H), "%s: needs Texture_UAV u1 = the edges (R8_UNORM) of %ux%u", name, W, H);
-    MainArgs a;
-    memset(&a, 0, sizeof a);
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t2 = GBufferA (RGBA32_UINT)", true, sp::kOneMipAt0 },
+                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R8_UINT, "Texture_UAV u0 = the working AO term (R8_UINT)", true, sp::kOneMipAt0 },
+                                 { TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R8_UNORM, "Texture_UAV u1 = the edges (R8_UNORM)", true, sp::kOneMipAt0 } };
+    trhip_texture_t* tex[3];
+    if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "the working depth chain")) return rc;
+    MainArgs a = sp::zeroed<MainArgs>();
     a.k = *k;
     a.push = *push;
     for (uint32_t j = 0; j < 5; ++j) { a.chain.mip[j] = (const uint16_t*)chain->mipPtr(j); a.chain.w[j] = chain->mipW(j); a.chain.h[j] = chain->mipH(j); }
-    a.gbufferA = (const uint4*)g->ptr;
-    a.outAO = (uint8_t*)ao->ptr;
-    a.outEdges = (uint8_t*)edges->ptr;
-    const uint32_t gx = (W + kAoGroup - 1u) / kAoGroup, gy = (H + kAoGroup - 1u) / kAoGroup;
-    TRHIP_REQUIRE(ctx.gx >= gx && ctx.gy >= gy, "%s: a direct dispatch of 8x8-pixel groups covering %ux%u", name, W, H);
-    const dim3 grid(gx, gy);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(aoMainKernel, grid, dim3(kAoGroup, kAoGroup), 0, s, a);
-        return trhip::launchStatus("aoMainKernel"); });
+    a.gbufferA = (const uint4*)tex[0]->ptr;
+    a.outAO = (uint8_t*)tex[1]->ptr;
+    a.outEdges = (uint8_t*)tex[2]->ptr;
+    if (const int rc = sp::requireCover(ctx, kAoGroup, kAoGroup, W, H)) return rc;
+    sp::launch(ctx, aoMainKernel, "aoMainKernel", sp::tiles(W, H, kAoGroup, kAoGroup), dim3(kAoGroup, kAoGroup), a);
     return TRHIP_OK;
 }
 
 int recordDenoise(trhip::DispatchCtx& ctx)
 {
     const char* name = ctx.shaderName;
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 16x8-pixel groups", name);
     const GTAOConstants* k = gtaoConstants(ctx);
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (GTAOConstants, 96 bytes) missing or of another size", name);
     const XeGTAODenoiseConstants* push = (const XeGTAODenoiseConstants*)ctx.constants(1, sizeof(XeGTAODenoiseConstants));
     TRHIP_REQUIRE(push && ctx.pushBytes == sizeof(XeGTAODenoiseConstants), "%s: push constants b1 (XeGTAODenoiseConstants, 4 bytes) missing or of another size", name);
-    uint32_t srcMip = 0, edgeMip = 0, dstMip = 0;
-    trhip_texture_t* src = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 0, &srcMip);
-    TRHIP_REQUIRE(src && isPlane(src, TRHIP_FORMAT_R8_UINT, srcMip, src->width, src->height), "%s: needs Texture_SRV t0 = the AO term (R8_UINT)", name);
+    const sp::Binding wantSrc[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R8_UINT, "Texture_SRV t0 = the AO term (R8_UINT)", true, sp::kOneMipAt0 } };
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_R8_UNORM, "Texture_SRV t1 = the edges (R8_UNORM)", true, sp::kOneMipAt0 },
+                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R8_UINT, "Texture_UAV u0 = the output (R8_UINT)", true, sp::kOneMipAt0 } };
+    trhip_texture_t *bound[1], *tex[2];
+    if (const int rc = sp::bindTextures(ctx, wantSrc, bound)) return rc;                             // the size is the AO term's
+    const trhip_texture_t *src = bound[0];
     const uint32_t W = src->width, H = src->height;
-    trhip_texture_t* edges = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 1, &edgeMip);
-    TRHIP_REQUIRE(isPlane(edges, TRHIP_FORMAT_R8_UNORM, edgeMip, W, H), "%s: needs Texture_SRV t1 = the edges (R8_UNORM) of %ux%u", name, W, H);
-    trhip_texture_t* dst = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 0, &dstMip);
-    TRHIP_REQUIRE(isPlane(dst, TRHIP_FORMAT_R8_UINT, dstMip, W, H), "%s: needs Texture_UAV u0 = the output (R8_UINT) of %ux%u", name, W, H);
+    if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "t0")) return rc;
+    const trhip_texture_t *edges = tex[0], *dst = tex[1];
     TRHIP_REQUIRE(dst->ptr != src->ptr, "%s: t0 and u0 are the same texture", name);
-    DenoiseArgs a;
-    memset(&a, 0, sizeof a);
+    DenoiseArgs a = sp::zeroed<DenoiseArgs>();
     a.k = *k;
     a.finalApply = push->m_FinalApply;
     a.ao = (const uint8_t*)src->ptr;
     a.edges = (const uint8_t*)edges->ptr;
     a.out = (uint8_t*)dst->ptr;
     a.W = W; a.H = H;
-    const uint32_t gx = (W + 2u * kAoGroup - 1u) / (2u * kAoGroup), gy = (H + kAoGroup - 1u) / kAoGroup;
-    TRHIP_REQUIRE(ctx.gx >= gx && ctx.gy >= gy, "%s: a direct dispatch of 16x8-pixel groups covering %ux%u", name, W, H);
-    const dim3 grid(gx, gy);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(aoDenoiseKernel, grid, dim3(kAoGroup, kAoGroup), 0, s, a);
-        return trhip::launchStatus("aoDenoiseKernel"); });
+    if (const int rc = sp::requireCover(ctx, 2u * kAoGroup, kAoGroup, W, H)) return rc;             // two horizontal pixels per thread
+    sp::launch(ctx, aoDenoiseKernel, "aoDenoiseKernel", sp::tiles(W, H, 2u * kAoGroup, kAoGroup), dim3(kAoGroup, kAoGroup), a);
     return TRHIP_OK;
 }
 

@@ -3,9 +3,8 @@
 // bilinear taps at +- m_FilterRadius in UV, 3 x 3 tent; BlendOpaque, so the destination mip is OVERWRITTEN, not added to).
 // The texture it builds is what "postprocess_PS_PostProcess" reads at t2 (k_postprocess.hip).
 //
-// CONVENTION (parity unpinned; restated in tests/bloom_ref.c and DESIGN.md 3).  It extends the post-process convention
-// (k_postprocess.hip): IEEE binary32, no contraction, / correctly rounded, min / max = fmin / fmax (a NaN operand is dropped),
-// lerp(x, y, s) = x + s * (y - x) always evaluated, dot3 the fma chain, loads and stores through r11g11b10.hip.h.  New here:
+// CONVENTION (parity unpinned; restated in tests/bloom_ref.c and DESIGN.md 3).  The shared part (binary32 rules, lerp, dot3) is
+// stated in screen_pass.hip.h; min / max = fmin / fmax (a NaN operand is dropped), loads and stores through r11g11b10.hip.h.  Here:
 //   uv:       per axis ((float)p + 0.5f) / (float)destDim, p the destination texel, destDim the bound u0 mip's size;
 //   taps:     as the HLSL writes them: inUV.x - 2 * x, inUV.x - x, inUV.x, inUV.x + x, inUV.x + 2 * x and the same in y, with
 //             x, y = m_InvSourceResolution (downsample) or m_FilterRadius (upsample); 2 * x is an exact product;
@@ -23,7 +22,7 @@
 //   special:  inf - inf in a lerp gives NaN; max(NaN, 0.0001f) gives 0.0001f; a NaN is stored as the format's NaN code.
 // Every texel of the destination mip is written.
 //
-// KERNELS.  One thread per destination texel in the post pass's 64 x 1 wave mapping.  The 13 (9) taps share 5 (3) columns and
+// KERNELS.  One thread per destination texel in screen_pass.hip.h's tile.  The 13 (9) taps share 5 (3) columns and
 // 5 (3) rows, so the column / row indices and weights are computed once per axis: the same expressions, so the same words.
 // Texels are read straight from global memory through L1 / L2 with 4-byte loads and decoded per tap; no LDS.  Neighbouring
 // destination texels share most of their 52 (36) source texels, so the other design for the downsample stages a workgroup's
@@ -39,16 +38,16 @@
 // MEASURED: see profiles/bloom/README.md.
 #include "cull_math.hip.h"
 #include "r11g11b10.hip.h"
-#include "trhip_internal.h"
+#include "screen_pass.hip.h"
 
 namespace
 {
 
 using namespace interop;
 
-constexpr uint32_t kBloomTileW = 64, kBloomTileH = 4;                     // a wave = one 64 x 1 row segment of the destination mip
-constexpr uint32_t kBloomBlock = kBloomTileW * kBloomTileH;
-constexpr uint32_t kBloomGroupSide = 8;                                   // the full-screen pass's stand-in: [numthreads(8, 8, 1)] groups cover the destination
+constexpr uint32_t kBloomTileW = 64, kBloomTileH = 4;   // tests/test_gpu_bloom.py takes its sizes from these names: pinned to the shared tile
+static_assert(kBloomTileW == sp::kTileW && kBloomTileH == sp::kTileH, "the bloom kernels run in the shared tile");
+
 // The downsample's other design, for the cost comparison (profiles/bloom/): a workgroup stages the source footprint of its
 // kBloomLdsTileW x kBloomLdsTileH destination tile once in LDS, as raw words, and takes its taps from there.  The footprint is
 // derived from the tile's first and last destination texel through the same coordinate expression (every step of it is
@@ -81,7 +80,7 @@ __device__ __forceinline__ Axis axisOf(float uv, uint32_t dim)
     return { (uint32_t)cm::min_(cm::max_(t0, 0.0f), last), (uint32_t)cm::min_(cm::max_(t0 + 1.0f, 0.0f), last), f };
 }
 
-__device__ __forceinline__ float lerp_(float x, float y, float s) { return x + s * (y - x); }
+using sp::lerp_;
 __device__ __forceinline__ cm::F3 add(cm::F3 a, cm::F3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
 __device__ __forceinline__ cm::F3 mul(cm::F3 a, float s) { return { a.x * s, a.y * s, a.z * s }; }
 
@@ -161,11 +160,11 @@ __device__ __forceinline__ void downsampleTexel(const BloomArgs& a, const Source
     store(a, px, py, d);
 }
 
-__global__ __launch_bounds__(kBloomBlock) void bloomDownsampleKernel(BloomArgs a)
+__global__ __launch_bounds__(sp::kBlock) void bloomDownsampleKernel(BloomArgs a)
 {
-    const uint32_t px = blockIdx.x * kBloomTileW + threadIdx.x, py = blockIdx.y * kBloomTileH + threadIdx.y;
-    if (px >= a.dstW || py >= a.dstH) return;
-    downsampleTexel(a, GlobalSource{ a.src, a.srcW }, px, py);
+    const sp::Pixel at = sp::pixel();
+    if (!at.inside(a.dstW, a.dstH)) return;
+    downsampleTexel(a, GlobalSource{ a.src, a.srcW }, at.x, at.y);
 }
 
 // Cost comparison only unless TR_BLOOM_LDS_DOWNSAMPLE is set (profiles/bloom/).  The first and the last texel of the tile give
@@ -177,7 +176,7 @@ __device__ __forceinline__ void footprint(uint32_t first, uint32_t last, uint32_
     *hi = max(max(max(l.m2.i1, l.m1.i1), max(l.c.i1, l.p1.i1)), l.p2.i1);
 }
 
-__global__ __launch_bounds__(kBloomBlock) void bloomDownsampleLdsKernel(BloomArgs a)
+__global__ __launch_bounds__(sp::kBlock) void bloomDownsampleLdsKernel(BloomArgs a)
 {
     __shared__ uint32_t tile[kBloomLdsWords];
     const uint32_t tx = threadIdx.x % kBloomLdsTileW, ty = threadIdx.x / kBloomLdsTileW;
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(kBloomBlock) void bloomDownsampleLdsKernel(BloomArg
         if (inside) downsampleTexel(a, GlobalSource{ a.src, a.srcW }, px, py);
         return;
     }
-    for (uint32_t i = threadIdx.x; i < fw * fh; i += kBloomBlock) {
+    for (uint32_t i = threadIdx.x; i < fw * fh; i += sp::kBlock) {
         const uint32_t r = i / fw, c = i - r * fw;
         tile[i] = a.src[(uint64_t)(y0 + r) * a.srcW + x0 + c];
     }
@@ -199,10 +198,11 @@ __global__ __launch_bounds__(kBloomBlock) void bloomDownsampleLdsKernel(BloomArg
     if (inside) downsampleTexel(a, LdsSource{ tile, x0, y0, fw }, px, py);
 }
 
-__global__ __launch_bounds__(kBloomBlock) void bloomUpsampleKernel(BloomArgs a)               // bloom.hlsl:93-129
+__global__ __launch_bounds__(sp::kBlock) void bloomUpsampleKernel(BloomArgs a)               // bloom.hlsl:93-129
 {
-    const uint32_t px = blockIdx.x * kBloomTileW + threadIdx.x, py = blockIdx.y * kBloomTileH + threadIdx.y;
-    if (px >= a.dstW || py >= a.dstH) return;
+    const sp::Pixel at = sp::pixel();
+    if (!at.inside(a.dstW, a.dstH)) return;
+    const uint32_t px = at.x, py = at.y;
     const float u = cm::div_((float)px + 0.5f, (float)a.dstW), v = cm::div_((float)py + 0.5f, (float)a.dstH);
     const float r = a.k.m_FilterRadius;
     const GlobalSource s{ a.src, a.srcW };
@@ -223,38 +223,27 @@ int recordBloom(trhip::DispatchCtx& ctx)
     const bool up = ctx.variant != 0;
     const BloomConsts* k = (const BloomConsts*)ctx.constants(0, sizeof(BloomConsts));
     TRHIP_REQUIRE(k, "%s: b0 or push constants (BloomConsts, 16 bytes) missing", name);
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 8x8-pixel groups", name);
-    uint32_t srcMip = 0, dstMip = 0;
-    trhip_texture_t* src = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 0, &srcMip);
-    TRHIP_REQUIRE(src && src->format == TRHIP_FORMAT_R11G11B10_FLOAT, "%s: needs Texture_SRV t0 = the R11G11B10_FLOAT source texture", name);
-    TRHIP_REQUIRE(srcMip < src->mips, "%s: t0 mip %u out of range (the texture has %u)", name, srcMip, src->mips);
-    trhip_texture_t* dst = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 0, &dstMip);
-    TRHIP_REQUIRE(dst && dst->format == TRHIP_FORMAT_R11G11B10_FLOAT, "%s: needs Texture_UAV u0 = the R11G11B10_FLOAT destination texture", name);
-    TRHIP_REQUIRE(dstMip < dst->mips, "%s: u0 mip %u out of range (the texture has %u)", name, dstMip, dst->mips);
-    TRHIP_REQUIRE(src->mipPtr(srcMip) != dst->mipPtr(dstMip), "%s: t0 and u0 are the same mip %u of one texture", name, srcMip);
-    BloomArgs a;
-    memset(&a, 0, sizeof a);
-    a.src = (const uint32_t*)src->mipPtr(srcMip);
-    a.dst = (uint32_t*)dst->mipPtr(dstMip);
-    a.srcW = src->mipW(srcMip); a.srcH = src->mipH(srcMip);
-    a.dstW = dst->mipW(dstMip); a.dstH = dst->mipH(dstMip);
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_SRV t0 = the R11G11B10_FLOAT source texture", true, sp::kAnyMip },
+                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_UAV u0 = the R11G11B10_FLOAT destination texture", true, sp::kAnyMip } };
+    trhip_texture_t* tex[2];
+    uint32_t mip[2];
+    if (const int rc = sp::bindTextures(ctx, want, tex, 0, 0, nullptr, mip)) return rc;             // source and destination each have their mip's own size
+    const trhip_texture_t *src = tex[0], *dst = tex[1];
+    TRHIP_REQUIRE(src->mipPtr(mip[0]) != dst->mipPtr(mip[1]), "%s: t0 and u0 are the same mip %u of one texture", name, mip[0]);
+    BloomArgs a = sp::zeroed<BloomArgs>();
+    a.src = (const uint32_t*)src->mipPtr(mip[0]);
+    a.dst = (uint32_t*)dst->mipPtr(mip[1]);
+    a.srcW = src->mipW(mip[0]); a.srcH = src->mipH(mip[0]);
+    a.dstW = dst->mipW(mip[1]); a.dstH = dst->mipH(mip[1]);
     a.k = *k;
-    TRHIP_REQUIRE((uint64_t)ctx.gx * kBloomGroupSide >= a.dstW && (uint64_t)ctx.gy * kBloomGroupSide >= a.dstH,
-                  "%s: a direct dispatch of 8x8-pixel groups covering the %ux%u destination mip", name, a.dstW, a.dstH);
-    const dim3 grid((a.dstW + kBloomTileW - 1) / kBloomTileW, (a.dstH + kBloomTileH - 1) / kBloomTileH);
+    if (const int rc = sp::requireCover(ctx, sp::kGroupSide, sp::kGroupSide, a.dstW, a.dstH, " destination mip")) return rc;
+    const dim3 grid = sp::tiles(a.dstW, a.dstH), block(sp::kTileW, sp::kTileH);
     if (up)
-        ctx.emit("main", [a, grid](hipStream_t s) {
-            TRHIP_LAUNCH(bloomUpsampleKernel, grid, dim3(kBloomTileW, kBloomTileH), 0, s, a);
-            return trhip::launchStatus("bloomUpsampleKernel"); });
-    else if (TR_BLOOM_LDS_DOWNSAMPLE) {
-        const dim3 tiles((a.dstW + kBloomLdsTileW - 1) / kBloomLdsTileW, (a.dstH + kBloomLdsTileH - 1) / kBloomLdsTileH);
-        ctx.emit("main", [a, tiles](hipStream_t s) {
-            TRHIP_LAUNCH(bloomDownsampleLdsKernel, tiles, dim3(kBloomBlock), 0, s, a);
-            return trhip::launchStatus("bloomDownsampleLdsKernel"); });
-    } else
-        ctx.emit("main", [a, grid](hipStream_t s) {
-            TRHIP_LAUNCH(bloomDownsampleKernel, grid, dim3(kBloomTileW, kBloomTileH), 0, s, a);
-            return trhip::launchStatus("bloomDownsampleKernel"); });
+        sp::launch(ctx, bloomUpsampleKernel, "bloomUpsampleKernel", grid, block, a);
+    else if (TR_BLOOM_LDS_DOWNSAMPLE)
+        sp::launch(ctx, bloomDownsampleLdsKernel, "bloomDownsampleLdsKernel", sp::tiles(a.dstW, a.dstH, kBloomLdsTileW, kBloomLdsTileH), dim3(sp::kBlock), a);
+    else
+        sp::launch(ctx, bloomDownsampleKernel, "bloomDownsampleKernel", grid, block, a);
     return TRHIP_OK;
 }
 

@@ -8,16 +8,12 @@
 // WHICH PIXELS: the reference draws where the stencil equals the opaque bit.  The stand-in: a pixel is written iff its depth
 // word is > 0.0f (NaN, +-0 and negative depths are skipped); every other texel of u0 keeps what it held.
 //
-// CONVENTION (parity unpinned; restated in tests/lighting_ref.c and DESIGN.md 3).  IEEE binary32, no contraction, fma only
-// where written, / and sqrt correctly rounded:
-//   dot3 = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)); normalize(v) = v / sqrt(dot3(v, v)); rcp(x) = 1.0f / x;
-//   saturate(x) = fmin(fmax(x, 0), 1) (a NaN gives 0); lerp(x, y, s) = x + s * (y - x); uint(x) truncates;
+// CONVENTION (parity unpinned; restated in tests/lighting_ref.c and DESIGN.md 3).  The shared part (binary32 rules, saturate, lerp,
+// dot3, inUV, UVToClipXY, worldPosition) is stated in screen_pass.hip.h.  Here:
+//   normalize(v) = v / sqrt(dot3(v, v)); rcp(x) = 1.0f / x;
 //   UnpackGBuffer: RGBA8 (float)byte * (1.0f / 255.0f), unorm16 (float)u * (1.0f / 65535.0f), one multiply by the rounded
 //             constant each; UnpackOctadehron f = f * 2 - 1, z = (1 - |fx|) - |fy|, t = saturate(-z), x += (x >= 0 ? -t : t),
 //             y likewise, then normalize; UnpackR9G9B9E5 ldexp(mantissa, E - 24), exact;
-//   inUV = (px + 0.5f, py + 0.5f) / float2(resolution); UVToClipXY uv * (2, -2) + (-1, 1), multiply then add;
-//   worldPosition = xyz / w of the row vector (clipXY, depth, 1) times m_ClipToWorld, each column
-//             fma(depth, m[2][j], fma(clip.y, m[1][j], clip.x * m[0][j])) + m[3][j] (the motion resolve's 4-column product);
 //   PS_Main: ComputeDiffuseColor albedo * (1 - metallic); ComputeF0 lerp(0.08f * 0.5f, albedo, metallic); V = normalize(origin -
 //             worldPosition), L = the light vector as given (not normalised), H = normalize(V + L); NdotV = saturate(|N.V| + 1e-5f),
 //             NdotL, NdotH, VdotH saturated; a = r * r, a2 = fmin(fmax(a * a, 0.0001f), 1); D_GGX a2 / ((pi * d) * d) with
@@ -42,8 +38,7 @@
 //
 // KERNEL: one thread per pixel, no LDS.  The depth word is read first and a skipped pixel ends there (sky costs 4 B); a lit
 // pixel then reads GBufferA in one 16-byte load and the shadow byte, and stores 4 B: about 25 B against 17 correctly rounded
-// divisions and 3 square roots, so the arithmetic is the cost, as in k_gbuffer.hip.  A workgroup is 256 threads covering
-// kTileW x kTileH pixels, a wave kTileW-wide row segments.
+// divisions and 3 square roots, so the arithmetic is the cost, as in k_gbuffer.hip.  The tile is screen_pass.hip.h's.
 //
 // MEASURED (tools/lighting_cost.py, generated city of 2251 instances at 3840x2160, 8.29 M lit pixels, shadow mask bound, builds
 // alternated three times on one MI355X; profiles/lighting/): this kernel 103.0 us (spread 0.5), 99.4 us in a kernel trace of its
@@ -55,7 +50,7 @@
 #include "cull_math.hip.h"
 #include "gbuffer_unpack.hip.h"
 #include "r11g11b10.hip.h"
-#include "trhip_internal.h"
+#include "screen_pass.hip.h"
 
 namespace
 {
@@ -64,11 +59,10 @@ using namespace interop;
 using namespace gbuf;
 
 #ifndef TR_LIGHTING_TILE_W
-#define TR_LIGHTING_TILE_W 64                  // a wave = one 64 x 1 row segment; 16 gives the G-buffer resolve's 16 x 4 (tools/lighting_cost.py measures both)
+#define TR_LIGHTING_TILE_W sp::kTileW          // the shared tile; 16 gives the G-buffer resolve's 16 x 4 wave (tools/lighting_cost.py measures both)
 #endif
-constexpr uint32_t kBlock = 256, kTileW = TR_LIGHTING_TILE_W, kTileH = kBlock / kTileW;
-constexpr uint32_t kGroupSide = 8;             // the reference entry's [numthreads(8, 8, 1)]: group counts cover the screen
-static_assert(kTileW * kTileH == kBlock && (kTileW == 64 || kTileW == 16), "tile shape");
+constexpr uint32_t kTileW = TR_LIGHTING_TILE_W, kTileH = sp::kBlock / kTileW;
+static_assert(kTileW * kTileH == sp::kBlock && (kTileW == sp::kTileW || kTileW == 16), "tile shape");
 
 struct LightingArgs
 {
@@ -106,25 +100,18 @@ __device__ __forceinline__ float quickRandomFloat(uint32_t& seed)               
     return (float)(seed & 0x00FFFFFFu) / 16777216.0f;
 }
 
-__device__ __forceinline__ float halfToFloat(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }
-
 __device__ __forceinline__ cm::F3 litPixel(const LightingArgs& a, const GBufferParams& p, uint32_t px, uint32_t py, float depth, float shadow)
 {
     const DeferredLightingConsts& k = a.k;
-    const float u = cm::div_((float)px + 0.5f, (float)k.m_LightingOutputResolution.x), v = cm::div_((float)py + 0.5f, (float)k.m_LightingOutputResolution.y);
-    const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;                                      // UVToClipXY
-    float h[4];
-    for (int j = 0; j < 4; ++j)
-        h[j] = cm::fma_(depth, k.m_ClipToWorld.m[2][j], cm::fma_(cy, k.m_ClipToWorld.m[1][j], cx * k.m_ClipToWorld.m[0][j])) + k.m_ClipToWorld.m[3][j];
-    const cm::F3 world = { cm::div_(h[0], h[3]), cm::div_(h[1], h[3]), cm::div_(h[2], h[3]) };
+    const cm::F3 world = sp::worldPosition(k.m_ClipToWorld, px, py, k.m_LightingOutputResolution.x, k.m_LightingOutputResolution.y, depth);
     const float oneMinusMetal = 1.0f - p.metallic, dielectric = 0.08f * 0.5f;
     const cm::F3 diffuse = { p.albedo.x * oneMinusMetal, p.albedo.y * oneMinusMetal, p.albedo.z * oneMinusMetal };
     const cm::F3 f0 = { dielectric + p.metallic * (p.albedo.x - dielectric), dielectric + p.metallic * (p.albedo.y - dielectric), dielectric + p.metallic * (p.albedo.z - dielectric) };
     const cm::F3 V = normalize_({ k.m_CameraOrigin[0] - world.x, k.m_CameraOrigin[1] - world.y, k.m_CameraOrigin[2] - world.z });
     const cm::F3 L = { k.m_DirectionalLightVector[0], k.m_DirectionalLightVector[1], k.m_DirectionalLightVector[2] };
     const cm::F3 H = normalize_({ V.x + L.x, V.y + L.y, V.z + L.z });
-    const float NdotV = saturate_(__builtin_fabsf(cm::dot3(p.normal, V)) + 1e-5f), NdotL = saturate_(cm::dot3(p.normal, L));
-    const float NdotH = saturate_(cm::dot3(p.normal, H)), VdotH = saturate_(cm::dot3(V, H));
+    const float NdotV = sp::saturate_(__builtin_fabsf(cm::dot3(p.normal, V)) + 1e-5f), NdotL = sp::saturate_(cm::dot3(p.normal, L));
+    const float NdotH = sp::saturate_(cm::dot3(p.normal, H)), VdotH = sp::saturate_(cm::dot3(V, H));
     const float al = p.roughness * p.roughness, a2 = cm::min_(cm::max_(al * al, 0.0001f), 1.0f);
     const float d = (NdotH * a2 - NdotH) * NdotH + 1.0f;                                            // D_GGX
     const float D = cm::div_(a2, (0x1.921fb6p+1f * d) * d);
@@ -175,18 +162,18 @@ __device__ __forceinline__ cm::F3 debugPixel(const LightingArgs& a, const GBuffe
         return { r, g, b }; }
     case kDeferredLightingDebugMode_MotionVectors: {
         const uint32_t m = a.motion[i];
-        return { cm::div_(halfToFloat(m & 0xFFFFu), (float)k.m_LightingOutputResolution.x), cm::div_(halfToFloat(m >> 16), (float)k.m_LightingOutputResolution.y), 0.0f }; }
+        return { cm::div_((float)sp::halfOf(m), (float)k.m_LightingOutputResolution.x), cm::div_((float)sp::halfOf(m >> 16), (float)k.m_LightingOutputResolution.y), 0.0f }; }
     default: return { 0.0f, 0.0f, 0.0f };
     }
 }
 
 template <bool DEBUG>
-__global__ __launch_bounds__(kBlock) void lightingKernel(LightingArgs a)
+__global__ __launch_bounds__(sp::kBlock) void lightingKernel(LightingArgs a)
 {
     const uint32_t W = a.k.m_LightingOutputResolution.x, H = a.k.m_LightingOutputResolution.y;
-    const uint32_t px = blockIdx.x * kTileW + threadIdx.x, py = blockIdx.y * kTileH + threadIdx.y;
-    if (px >= W || py >= H) return;
-    const uint64_t i = (uint64_t)py * W + px;
+    const sp::Pixel at = sp::pixel<kTileW, kTileH>();
+    if (!at.inside(W, H)) return;
+    const uint64_t i = at.index(W);
     const float depth = a.depth[i];
     if (!(depth > 0.0f)) return;                                                                   // the stencil stand-in: sky costs 4 B
     const uint4 g = a.gbufferA[i];
@@ -195,7 +182,7 @@ __global__ __launch_bounds__(kBlock) void lightingKernel(LightingArgs a)
     a.out[i] = g.x ^ g.y ^ g.z ^ g.w ^ __builtin_bit_cast(uint32_t, shadow);
 #else
     const GBufferParams p = unpackGBuffer(g);
-    const cm::F3 rgb = DEBUG ? debugPixel(a, p, i, shadow) : litPixel(a, p, px, py, depth, shadow);
+    const cm::F3 rgb = DEBUG ? debugPixel(a, p, i, shadow) : litPixel(a, p, at.x, at.y, depth, shadow);
 #ifdef TR_LIGHTING_EXPERIMENT_TRUNC_STORE       // negative control only (profiles/lighting/): truncation instead of round to nearest even
     auto trunc = [](float v, uint32_t mbits) {
         const uint32_t u = __builtin_bit_cast(uint32_t, v), top = (31u << mbits) - 1u;
@@ -218,29 +205,18 @@ int recordLighting(trhip::DispatchCtx& ctx)
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (DeferredLightingConsts, 112 bytes) missing", name);
     TRHIP_REQUIRE(!k->m_bRTDDGIEnabled, "%s: m_bRTDDGIEnabled is set: DDGI ambient is not built", name);
     TRHIP_REQUIRE(k->m_DebugMode != kDeferredLightingDebugMode_Ambient, "%s: m_DebugMode 10 (Ambient) needs the DDGI volume, which is not built", name);
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 8x8-pixel groups", name);
     const uint32_t W = k->m_LightingOutputResolution.x, H = k->m_LightingOutputResolution.y;
     TRHIP_REQUIRE(W && H, "%s: m_LightingOutputResolution %ux%u is empty", name, W, H);
-    TRHIP_REQUIRE((uint64_t)ctx.gx * kGroupSide >= W && (uint64_t)ctx.gy * kGroupSide >= H, "%s: a direct dispatch of 8x8-pixel groups covering %ux%u", name, W, H);
-    struct Want { uint32_t type, slot, format; const char* what; bool required; };
-    const Want wants[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t0 = the RGBA32_UINT GBufferA", true },
-                           { TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RG16_FLOAT, "Texture_SRV t1 = the RG16_FLOAT GBufferMotion", DEBUG },
-                           { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_R32_FLOAT, "Texture_SRV t2 = the R32_FLOAT depth buffer", true },
-                           { TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_R8_UINT, "Texture_SRV t3 = the R8_UINT SSAO texture", false },
-                           { TRHIP_BIND_TEXTURE_SRV, 4, TRHIP_FORMAT_R8_UNORM, "Texture_SRV t4 = the R8_UNORM shadow mask", false },
-                           { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_UAV u0 = the R11G11B10_FLOAT LightingOutput, mip 0", true } };
-    trhip_texture_t* tex[6] = {};
-    for (int j = 0; j < 6; ++j) {
-        const Want& w = wants[j];
-        uint32_t mip = 0;
-        trhip_texture_t* t = ctx.texture(w.type, w.slot, &mip);
-        if (!t && !w.required) continue;
-        TRHIP_REQUIRE(t && t->format == w.format && (w.type != TRHIP_BIND_TEXTURE_UAV || mip == 0), "%s: needs %s", name, w.what);
-        TRHIP_REQUIRE(t->width == W && t->height == H && t->mips == 1, "%s: %s is %ux%u, m_LightingOutputResolution is %ux%u", name, w.what, t->width, t->height, W, H);
-        tex[j] = t;
-    }
-    LightingArgs a;
-    memset(&a, 0, sizeof a);
+    if (const int rc = sp::requireCover(ctx, sp::kGroupSide, sp::kGroupSide, W, H)) return rc;
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t0 = the RGBA32_UINT GBufferA", true, sp::kOneMip },
+                                 { TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RG16_FLOAT, "Texture_SRV t1 = the RG16_FLOAT GBufferMotion", DEBUG, sp::kOneMip },
+                                 { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_R32_FLOAT, "Texture_SRV t2 = the R32_FLOAT depth buffer", true, sp::kOneMip },
+                                 { TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_R8_UINT, "Texture_SRV t3 = the R8_UINT SSAO texture", false, sp::kOneMip },
+                                 { TRHIP_BIND_TEXTURE_SRV, 4, TRHIP_FORMAT_R8_UNORM, "Texture_SRV t4 = the R8_UNORM shadow mask", false, sp::kOneMip },
+                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_UAV u0 = the R11G11B10_FLOAT LightingOutput, mip 0", true, sp::kOneMipAt0 } };
+    trhip_texture_t* tex[6];
+    if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "m_LightingOutputResolution")) return rc;
+    LightingArgs a = sp::zeroed<LightingArgs>();
     a.k = *k;
     a.gbufferA = (const uint4*)tex[0]->ptr;
     a.motion = tex[1] ? (const uint32_t*)tex[1]->ptr : nullptr;
@@ -248,10 +224,7 @@ int recordLighting(trhip::DispatchCtx& ctx)
     a.ssao = tex[3] ? (const uint8_t*)tex[3]->ptr : nullptr;
     a.shadow = tex[4] ? (const uint8_t*)tex[4]->ptr : nullptr;
     a.out = (uint32_t*)tex[5]->ptr;
-    const dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(lightingKernel<DEBUG>, grid, dim3(kTileW, kTileH), 0, s, a);
-        return trhip::launchStatus(DEBUG ? "lightingKernel<debug>" : "lightingKernel<lit>"); });
+    sp::launch(ctx, lightingKernel<DEBUG>, DEBUG ? "lightingKernel<debug>" : "lightingKernel<lit>", sp::tiles(W, H, kTileW, kTileH), dim3(kTileW, kTileH), a);
     return TRHIP_OK;
 }
 

@@ -4,10 +4,8 @@
 // LinearToSRGB).  Sky, TAA, AO, the shadow mask and DDGI stay out of scope; bloom enters as an optional input
 // texture: the caller's, or the one k_bloom.hip generates (a mip chain, read at mip 0).
 //
-// CONVENTION (parity unpinned; restated in tests/postprocess_ref.c and DESIGN.md 3).  It extends the lighting convention
-// (k_deferredlighting.hip): IEEE binary32, no contraction, fma only where written, / correctly rounded, dot3 the fma chain,
-// min / max = fmin / fmax (a NaN operand is dropped), saturate(x) = fmin(fmax(x, 0), 1) (a NaN gives 0), lerp(x, y, s) =
-// x + s * (y - x) always evaluated (s = 0 included: an infinite x gives NaN), uint(x) truncates.
+// CONVENTION (parity unpinned; restated in tests/postprocess_ref.c and DESIGN.md 3).  The shared part (binary32 rules, saturate,
+// lerp, dot3) is stated in screen_pass.hip.h; min / max = fmin / fmax (a NaN operand is dropped).
 //   load:     R11G11B10_FLOAT decoded exactly (r11g11b10.hip.h), subnormal, inf and NaN codes included;
 //   RGBToLuminance: dot3(rgb, (0x1.b38cdap-3f, 0x1.6e2974p-1f, 0x1.279aaep-4f)): 0.212671, 0.715160, 0.072169 rounded once;
 //   log2, exp2: software (soft_math.hip.h): log2Soft for x > 0, exp2Signed for either sign;
@@ -38,7 +36,7 @@
 // lanes with the same bin adding once (its length, from its first lane: one shuffle and one ballot), and each workgroup ends
 // with one no-return global add per nonzero bin.  Counts are integers: every design gives the same words.
 // AdaptExposure: one 256-thread workgroup, the reference's LDS tree; thread 0 does the float arithmetic.  PostProcess: one
-// thread per pixel in the lighting kernel's 64 x 1 wave mapping, 4-byte loads of colour and bloom, one 4-byte store, no LDS.
+// thread per pixel in screen_pass.hip.h's tile, 4-byte loads of colour and bloom, one 4-byte store, no LDS.
 //
 // CODE OBJECT (-Rpass-analysis=kernel-resource-usage): histogramKernel 23 VGPRs, 1024 B LDS; adaptExposureKernel 8 VGPRs, 1024 B
 // LDS; postProcessKernel 12 VGPRs, no LDS; each 8 waves per SIMD, no scratch.
@@ -57,16 +55,16 @@
 // 4 255 129 words and 9 tests fail.
 #include "cull_math.hip.h"
 #include "r11g11b10.hip.h"
+#include "screen_pass.hip.h"
 #include "soft_math.hip.h"
-#include "trhip_internal.h"
 
 namespace
 {
 
 using namespace interop;
 
-constexpr uint32_t kBlock = 256, kTileW = 64, kTileH = kBlock / kTileW;   // the post pass: a wave = one 64 x 1 row segment
-constexpr uint32_t kPostGroupSide = 8, kHistGroupSide = 16;               // the reference entries' [numthreads]: group counts cover the image
+constexpr uint32_t kBlock = 256;                                          // the histogram's and the adapt pass's workgroup
+constexpr uint32_t kHistGroupSide = 16;                                   // the histogram entry's [numthreads(16, 16, 1)]: group counts cover the image
 constexpr uint32_t kHistGroupsPerCU = 4;                                  // a 3840 x 2160 image: 8100 vector trips over 1024 workgroups
 constexpr uint32_t kHistTexelsPerLane = 4, kHistWaves = kBlock / 64, kBins = 256;
 // The two answers to same-address LDS adds within a wave.  The defaults are the product: merged lanes measured faster, private
@@ -79,8 +77,6 @@ constexpr uint32_t kHistTexelsPerLane = 4, kHistWaves = kBlock / 64, kBins = 256
 #endif
 constexpr bool kHistPerWave = TR_HISTOGRAM_PER_WAVE != 0, kHistMergeLanes = TR_HISTOGRAM_MERGE_LANES != 0;
 
-__device__ __forceinline__ float saturate_(float x) { return cm::min_(cm::max_(x, 0.0f), 1.0f); }
-
 __device__ __forceinline__ float luminance(uint32_t word)
 {
     const trhip::Rgb c = trhip::unpackR11G11B10(word);
@@ -91,7 +87,7 @@ __device__ __forceinline__ uint32_t histogramBin(uint32_t word, float minLog, fl
 {
     const float lum = luminance(word);
     if (!(lum >= 0.005f)) return 0u;
-    const float logLum = saturate_((softmath::log2Soft(lum) - minLog) * invRange);
+    const float logLum = sp::saturate_((softmath::log2Soft(lum) - minLog) * invRange);
     return (uint32_t)(logLum * 254.0f + 1.0f);
 }
 
@@ -111,8 +107,8 @@ __global__ __launch_bounds__(kBlock) void histogramKernel(HistogramArgs a)
     const uint32_t t = threadIdx.y * kHistGroupSide + threadIdx.x;
     bins[t] = 0u;
     __syncthreads();
-    const uint32_t px = blockIdx.x * kHistGroupSide + threadIdx.x, py = blockIdx.y * kHistGroupSide + threadIdx.y;
-    if (px < a.width && py < a.height) atomicAdd(&bins[histogramBin(a.color[(uint64_t)py * a.width + px], a.minLog, a.invRange)], 1u);
+    const sp::Pixel at = sp::pixel<kHistGroupSide, kHistGroupSide>();
+    if (at.inside(a.width, a.height)) atomicAdd(&bins[histogramBin(a.color[at.index(a.width)], a.minLog, a.invRange)], 1u);
     __syncthreads();
     atomicAdd(&a.histogram[t], bins[t]);
 }
@@ -168,31 +164,27 @@ int recordHistogram(trhip::DispatchCtx& ctx)
     const char* name = ctx.shaderName;
     const GenerateLuminanceHistogramParameters* k = (const GenerateLuminanceHistogramParameters*)ctx.constants(0, sizeof(GenerateLuminanceHistogramParameters));
     TRHIP_REQUIRE(k, "%s: push constants (GenerateLuminanceHistogramParameters, 16 bytes) missing", name);
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 16x16-pixel groups", name);
     const uint32_t W = k->m_SrcColorDims.x, H = k->m_SrcColorDims.y;
     TRHIP_REQUIRE(W && H, "%s: m_SrcColorDims %ux%u is empty", name, W, H);
-    TRHIP_REQUIRE((uint64_t)ctx.gx * kHistGroupSide >= W && (uint64_t)ctx.gy * kHistGroupSide >= H, "%s: a direct dispatch of 16x16-pixel groups covering %ux%u", name, W, H);
-    trhip_texture_t* color = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 0);
-    TRHIP_REQUIRE(color && color->format == TRHIP_FORMAT_R11G11B10_FLOAT, "%s: needs Texture_SRV t0 = the R11G11B10_FLOAT colour", name);
-    TRHIP_REQUIRE(color->width == W && color->height == H && color->mips == 1, "%s: t0 is %ux%u, m_SrcColorDims is %ux%u", name, color->width, color->height, W, H);
+    if (const int rc = sp::requireCover(ctx, kHistGroupSide, kHistGroupSide, W, H)) return rc;
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_SRV t0 = the R11G11B10_FLOAT colour", true, sp::kOneMip } };
+    trhip_texture_t* color[1];
+    if (const int rc = sp::bindTextures(ctx, want, color, W, H, "m_SrcColorDims")) return rc;
     trhip_buffer_t* hist = ctx.buffer(TRHIP_BIND_STRUCTURED_UAV, 0);
     TRHIP_REQUIRE(hist && hist->byteSize >= kBins * 4, "%s: needs StructuredBuffer_UAV u0 = the histogram of at least 256 uint32", name);
-    HistogramArgs a;
-    memset(&a, 0, sizeof a);
-    a.color = (const uint32_t*)color->ptr;
+    HistogramArgs a = sp::zeroed<HistogramArgs>();
+    a.color = (const uint32_t*)color[0]->ptr;
     a.histogram = (uint32_t*)hist->ptr;
     a.texels = (uint64_t)W * H;
     a.minLog = k->m_MinLogLuminance; a.invRange = k->m_InverseLogLuminanceRange;
     a.width = W; a.height = H;
 #ifdef TR_HISTOGRAM_EXPERIMENT_REFERENCE_SHAPE
-    const dim3 grid((W + kHistGroupSide - 1) / kHistGroupSide, (H + kHistGroupSide - 1) / kHistGroupSide), block(kHistGroupSide, kHistGroupSide);
+    const dim3 grid = sp::tiles(W, H, kHistGroupSide, kHistGroupSide), block(kHistGroupSide, kHistGroupSide);
 #else
     const uint64_t trips = (a.texels / kHistTexelsPerLane + kBlock - 1) / kBlock, most = (uint64_t)ctx.computeUnits() * kHistGroupsPerCU;
     const dim3 grid((uint32_t)(trips < 1 ? 1 : trips < most ? trips : most)), block(kBlock);
 #endif
-    ctx.emit("main", [a, grid, block](hipStream_t s) {
-        TRHIP_LAUNCH(histogramKernel, grid, block, 0, s, a);
-        return trhip::launchStatus("histogramKernel"); });
+    sp::launch(ctx, histogramKernel, "histogramKernel", grid, block, a);
     return TRHIP_OK;
 }
 
@@ -232,19 +224,15 @@ int recordAdaptExposure(trhip::DispatchCtx& ctx)
     TRHIP_REQUIRE(hist && hist->byteSize >= kBins * 4, "%s: needs StructuredBuffer_SRV t0 = the histogram of at least 256 uint32", name);
     trhip_buffer_t* lum = ctx.buffer(TRHIP_BIND_STRUCTURED_UAV, 0);
     TRHIP_REQUIRE(lum && lum->byteSize >= 4, "%s: needs StructuredBuffer_UAV u0 = the luminance buffer of one float", name);
-    uint32_t mip = 0;
-    trhip_texture_t* exposure = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 1, &mip);
-    TRHIP_REQUIRE(exposure && exposure->format == TRHIP_FORMAT_R32_FLOAT && mip == 0, "%s: needs Texture_UAV u1 = the R32_FLOAT exposure texture, mip 0", name);
-    TRHIP_REQUIRE(exposure->width == 1 && exposure->height == 1, "%s: u1 is %ux%u, the exposure texture is 1x1", name, exposure->width, exposure->height);
-    AdaptArgs a;
-    memset(&a, 0, sizeof a);
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R32_FLOAT, "Texture_UAV u1 = the R32_FLOAT exposure texture, mip 0", true, sp::kAt0 } };
+    trhip_texture_t* exposure[1];
+    if (const int rc = sp::bindTextures(ctx, want, exposure, 1, 1, "the exposure texture")) return rc;
+    AdaptArgs a = sp::zeroed<AdaptArgs>();
     a.k = *k;
     a.histogram = (const uint32_t*)hist->ptr;
     a.luminance = (float*)lum->ptr;
-    a.exposure = (float*)exposure->ptr;
-    ctx.emit("main", [a](hipStream_t s) {
-        TRHIP_LAUNCH(adaptExposureKernel, dim3(1), dim3(kBlock), 0, s, a);
-        return trhip::launchStatus("adaptExposureKernel"); });
+    a.exposure = (float*)exposure[0]->ptr;
+    sp::launch(ctx, adaptExposureKernel, "adaptExposureKernel", dim3(1), dim3(kBlock), a);
     return TRHIP_OK;
 }
 
@@ -262,9 +250,9 @@ __device__ __forceinline__ float powGamma(float x) { return x > 0.0f ? softmath:
 __device__ __forceinline__ uint32_t unorm8(float c)
 {
 #ifdef TR_POST_EXPERIMENT_TRUNC_STORE          // negative control only (profiles/postprocess/): truncation instead of + 0.5f
-    return (uint32_t)(saturate_(c) * 255.0f);
+    return (uint32_t)(sp::saturate_(c) * 255.0f);
 #else
-    return (uint32_t)(saturate_(c) * 255.0f + 0.5f);
+    return (uint32_t)(sp::saturate_(c) * 255.0f + 0.5f);
 #endif
 }
 
@@ -283,12 +271,12 @@ __device__ __forceinline__ cm::F3 pbrNeutralToneMapping(cm::F3 c)               
     return { c.x + g * (newPeak - c.x), c.y + g * (newPeak - c.y), c.z + g * (newPeak - c.z) };
 }
 
-__global__ __launch_bounds__(kBlock) void postProcessKernel(PostArgs a)                       // postprocess.hlsl:44-69
+__global__ __launch_bounds__(sp::kBlock) void postProcessKernel(PostArgs a)                       // postprocess.hlsl:44-69
 {
     const uint32_t W = a.k.m_OutputDims.x, H = a.k.m_OutputDims.y;
-    const uint32_t px = blockIdx.x * kTileW + threadIdx.x, py = blockIdx.y * kTileH + threadIdx.y;
-    if (px >= W || py >= H) return;
-    const uint64_t i = (uint64_t)py * W + px;
+    const sp::Pixel at = sp::pixel();
+    if (!at.inside(W, H)) return;
+    const uint64_t i = at.index(W);
     const uint32_t word = a.color[i], bloomWord = a.bloom ? a.bloom[i] : 0u;
 #ifdef TR_POST_EXPERIMENT_STORE_ONLY            // attribution only (profiles/postprocess/): the pass's bytes without its arithmetic
     a.out[i] = word ^ bloomWord;
@@ -309,38 +297,24 @@ int recordPostProcess(trhip::DispatchCtx& ctx)
     const char* name = ctx.shaderName;
     const PostProcessParameters* k = (const PostProcessParameters*)ctx.constants(0, sizeof(PostProcessParameters));
     TRHIP_REQUIRE(k, "%s: b0 or push constants (PostProcessParameters, 24 bytes) missing", name);
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 8x8-pixel groups", name);
     const uint32_t W = k->m_OutputDims.x, H = k->m_OutputDims.y;
     TRHIP_REQUIRE(W && H, "%s: m_OutputDims %ux%u is empty", name, W, H);
-    TRHIP_REQUIRE((uint64_t)ctx.gx * kPostGroupSide >= W && (uint64_t)ctx.gy * kPostGroupSide >= H, "%s: a direct dispatch of 8x8-pixel groups covering %ux%u", name, W, H);
-    struct Want { uint32_t type, slot, format; const char* what; bool required; };
-    const Want wants[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_SRV t0 = the R11G11B10_FLOAT colour input", true },
-                           { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_SRV t2 = the R11G11B10_FLOAT bloom texture", false },
-                           { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_RGBA8_UNORM, "Texture_UAV u0 = the RGBA8_UNORM back buffer, mip 0", true } };
-    trhip_texture_t* tex[3] = {};
-    for (int j = 0; j < 3; ++j) {
-        const Want& w = wants[j];
-        uint32_t mip = 0;
-        trhip_texture_t* t = ctx.texture(w.type, w.slot, &mip);
-        if (!t && !w.required) continue;
-        TRHIP_REQUIRE(t && t->format == w.format && (w.type != TRHIP_BIND_TEXTURE_UAV || mip == 0), "%s: needs %s", name, w.what);
-        TRHIP_REQUIRE(t->width == W && t->height == H && (t->mips == 1 || (j == 1 && mip == 0)), "%s: %s is %ux%u, m_OutputDims is %ux%u", name, w.what, t->width, t->height, W, H);   // t2 may be the bloom chain: mip 0 is read
-        tex[j] = t;
-    }
+    if (const int rc = sp::requireCover(ctx, sp::kGroupSide, sp::kGroupSide, W, H)) return rc;
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_SRV t0 = the R11G11B10_FLOAT colour input", true, sp::kOneMip },
+                                 { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_SRV t2 = the R11G11B10_FLOAT bloom texture", false, sp::kOneMipOrAt0 },   // may be the bloom chain: mip 0 is read
+                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_RGBA8_UNORM, "Texture_UAV u0 = the RGBA8_UNORM back buffer, mip 0", true, sp::kOneMipAt0 } };
+    trhip_texture_t* tex[3];
+    if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "m_OutputDims")) return rc;
     trhip_buffer_t* lum = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 1);
     TRHIP_REQUIRE(!lum || lum->byteSize >= 4, "%s: StructuredBuffer_SRV t1 = the luminance buffer holds one float", name);
     TRHIP_REQUIRE(lum || k->m_ManualExposure != 0.0f, "%s: m_ManualExposure is 0: needs StructuredBuffer_SRV t1 = the luminance buffer", name);
-    PostArgs a;
-    memset(&a, 0, sizeof a);
+    PostArgs a = sp::zeroed<PostArgs>();
     a.k = *k;
     a.color = (const uint32_t*)tex[0]->ptr;
     a.luminance = lum ? (const float*)lum->ptr : nullptr;
     a.bloom = tex[1] ? (const uint32_t*)tex[1]->ptr : nullptr;
     a.out = (uint32_t*)tex[2]->ptr;
-    const dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(postProcessKernel, grid, dim3(kTileW, kTileH), 0, s, a);
-        return trhip::launchStatus("postProcessKernel"); });
+    sp::launch(ctx, postProcessKernel, "postProcessKernel", sp::tiles(W, H), dim3(sp::kTileW, sp::kTileH), a);
     return TRHIP_OK;
 }
 

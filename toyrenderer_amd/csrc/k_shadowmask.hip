@@ -13,7 +13,7 @@
 //
 // CONVENTION (tests/shadowmask_ref.c is the definition; the functions below repeat its functions word for word).  IEEE binary32,
 // no contraction, fma only where written, / and sqrt correctly rounded:
-//   worldPosition, UnpackGBuffer's normal, dot3, normalize as k_deferredlighting.hip states them (gbuffer_unpack.hip.h);
+//   worldPosition, dot3 as screen_pass.hip.h states them; UnpackGBuffer's normal, normalize as k_deferredlighting.hip (gbuffer_unpack.hip.h);
 //   noise = (float)byte / 255.0f of the blue noise texel's R and G at (px % 128, py % 128), + m_NoisePhase, fmod(x, 1) = x - trunc(x);
 //   MapToCone / CreateTangentVectors as the HLSL with softmath::cosSoft / sinSoft, RN(pi / 4) and RN(pi / 2), cross as cm::cross3,
 //             (n + u.x * t0) + u.y * t1; the direction is its normalize; origin = worldPosition + normal * m_RayStartOffset;
@@ -42,8 +42,8 @@
 // a lighting pass of 0.10 ms, the refit 35 us.  Untuned: correctness came first.
 #include "cull_math.hip.h"
 #include "gbuffer_unpack.hip.h"
+#include "screen_pass.hip.h"
 #include "soft_math.hip.h"
-#include "trhip_internal.h"
 
 namespace
 {
@@ -357,11 +357,14 @@ __global__ __launch_bounds__(kTileSide * kTileSide) void shadowMaskKernel(TraceA
 {
     const ShadowMaskConsts& k = a.k;
     const uint32_t W = k.m_OutputResolution.x, H = k.m_OutputResolution.y;
-    const uint32_t px = blockIdx.x * kTileSide + threadIdx.x, py = blockIdx.y * kTileSide + threadIdx.y;
-    if (px >= W || py >= H) return;
-    const uint64_t i = (uint64_t)py * W + px;
+    const sp::Pixel at = sp::pixel<kTileSide, kTileSide>();
+    if (!at.inside(W, H)) return;
+    const uint32_t px = at.x, py = at.y;
+    const uint64_t i = at.index(W);
     const float depth = a.depth[i];
     if (depth == 0.0f) { a.lvd[i] = 0x7BFFu; return; }                                             // kFarDepth: u1 = kFP16Max, u0 untouched
+    // sp::worldPosition's operations written out: through the call the compiler resolves this kernel's arguments differently, spills
+    // 45 scalar registers instead of 10, and the trace measured 1 % slower (profiles/shadowmask/README.md).  Keep the two alike.
     const float u = cm::div_((float)px + 0.5f, (float)W), v = cm::div_((float)py + 0.5f, (float)H);
     const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;                                      // UVToClipXY
     float h[4];
@@ -379,7 +382,7 @@ __global__ __launch_bounds__(kTileSide * kTileSide) void shadowMaskKernel(TraceA
     a.mask[i] = occ ? 0u : 255u;
     const F3 toCamera = { wp.x - k.m_CameraPosition[0], wp.y - k.m_CameraPosition[1], wp.z - k.m_CameraPosition[2] };
     const float len = cm::sqrt_(cm::dot3(toCamera, toCamera));
-    a.lvd[i] = len != len ? (uint16_t)0x7E00u : __builtin_bit_cast(uint16_t, (_Float16)len);
+    a.lvd[i] = sp::halfBits(len);
 }
 
 int recordShadowMask(trhip::DispatchCtx& ctx)
@@ -388,27 +391,17 @@ int recordShadowMask(trhip::DispatchCtx& ctx)
     const ShadowMaskConsts* k = (const ShadowMaskConsts*)ctx.constants(0, sizeof(ShadowMaskConsts));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (ShadowMaskConsts, 112 bytes) missing or short", name);
     TRHIP_REQUIRE(!k->m_bDoDenoising, "%s: m_bDoDenoising is set: the SIGMA denoiser and its penumbra packing are not built", name);
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 8x8-pixel groups", name);
     const uint32_t W = k->m_OutputResolution.x, H = k->m_OutputResolution.y;
     TRHIP_REQUIRE(W && H, "%s: m_OutputResolution %ux%u is empty", name, W, H);
-    TRHIP_REQUIRE((uint64_t)ctx.gx * kTileSide >= W && (uint64_t)ctx.gy * kTileSide >= H, "%s: a direct dispatch of 8x8-pixel groups covering %ux%u", name, W, H);
-    struct WantTex { uint32_t type, slot, format; const char* what; };
-    const WantTex wantTex[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R32_FLOAT, "Texture_SRV t0 = the R32_FLOAT depth buffer" },
-                                { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t2 = the RGBA32_UINT GBufferA" },
-                                { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R8_UNORM, "Texture_UAV u0 = the R8_UNORM shadow mask" },
-                                { TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R16_FLOAT, "Texture_UAV u1 = the R16_FLOAT linear view depth" } };
-    trhip_texture_t* tex[4] = {};
-    for (int j = 0; j < 4; ++j) {
-        uint32_t mip = 0;
-        trhip_texture_t* t = ctx.texture(wantTex[j].type, wantTex[j].slot, &mip);
-        TRHIP_REQUIRE(t && t->format == wantTex[j].format && mip == 0 && t->mips == 1, "%s: needs %s (one mip)", name, wantTex[j].what);
-        TRHIP_REQUIRE(t->width == W && t->height == H, "%s: %s is %ux%u, m_OutputResolution is %ux%u", name, wantTex[j].what, t->width, t->height, W, H);
-        tex[j] = t;
-    }
-    uint32_t noiseMip = 0;
-    trhip_texture_t* noise = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 8, &noiseMip);
-    TRHIP_REQUIRE(noise && noise->format == TRHIP_FORMAT_RGBA8_UNORM && noise->width == kBlueNoiseSize && noise->height == kBlueNoiseSize && noiseMip == 0 && noise->mips == 1,
-                  "%s: needs Texture_SRV t8 = the RGBA8_UNORM 128x128 blue noise", name);
+    if (const int rc = sp::requireCover(ctx, kTileSide, kTileSide, W, H)) return rc;
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R32_FLOAT, "Texture_SRV t0 = the R32_FLOAT depth buffer (one mip)", true, sp::kOneMipAt0 },
+                                 { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t2 = the RGBA32_UINT GBufferA (one mip)", true, sp::kOneMipAt0 },
+                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R8_UNORM, "Texture_UAV u0 = the R8_UNORM shadow mask (one mip)", true, sp::kOneMipAt0 },
+                                 { TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R16_FLOAT, "Texture_UAV u1 = the R16_FLOAT linear view depth (one mip)", true, sp::kOneMipAt0 } };
+    const sp::Binding wantNoise[] = { { TRHIP_BIND_TEXTURE_SRV, 8, TRHIP_FORMAT_RGBA8_UNORM, "Texture_SRV t8 = the RGBA8_UNORM 128x128 blue noise", true, sp::kOneMipAt0 } };
+    trhip_texture_t *tex[4], *noise[1];
+    if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "m_OutputResolution")) return rc;
+    if (const int rc = sp::bindTextures(ctx, wantNoise, noise, kBlueNoiseSize, kBlueNoiseSize, "the blue noise")) return rc;
     struct WantBuf { uint32_t slot, stride; const char* what; };
     const WantBuf wantBuf[] = { { 1, sizeof(trhip_accel_node), "t1 = the TLAS nodes" }, { 3, sizeof(BasePassInstanceConstants), "t3 = the instances" },
                                 { 4, sizeof(RawVertexFormat), "t4 = the vertices" }, { 5, sizeof(MaterialData), "t5 = the materials" }, { 6, 4, "t6 = the indices" },
@@ -423,11 +416,10 @@ int recordShadowMask(trhip::DispatchCtx& ctx)
         const uint64_t c = buf[j]->byteSize / wantBuf[j].stride;
         count[j] = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
     }
-    TraceArgs a;
-    memset(&a, 0, sizeof a);
+    TraceArgs a = sp::zeroed<TraceArgs>();
     a.k = *k;
     a.depth = (const float*)tex[0]->ptr; a.gbufferA = (const uint4*)tex[1]->ptr; a.mask = (uint8_t*)tex[2]->ptr; a.lvd = (uint16_t*)tex[3]->ptr;
-    a.noise = (const uint32_t*)noise->ptr;
+    a.noise = (const uint32_t*)noise[0]->ptr;
     a.tlasNodes = (const trhip_accel_node*)buf[0]->ptr; a.numTlasNodes = count[0];
     a.instances = (const BasePassInstanceConstants*)buf[1]->ptr; a.numInstances = count[1] < count[6] ? count[1] : count[6];
     a.vertices = (const uint8_t*)buf[2]->ptr; a.numVertices = count[2];
@@ -438,10 +430,7 @@ int recordShadowMask(trhip::DispatchCtx& ctx)
     a.headers = (const trhip_blas_header*)buf[7]->ptr;
     a.blasNodes = (const trhip_accel_node*)buf[8]->ptr; a.numBlasNodes = count[8];
     a.triOrder = (const uint32_t*)buf[9]->ptr; a.numTriOrder = count[9];
-    const dim3 grid((W + kTileSide - 1) / kTileSide, (H + kTileSide - 1) / kTileSide);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(shadowMaskKernel, grid, dim3(kTileSide, kTileSide), 0, s, a);
-        return trhip::launchStatus("shadowMaskKernel"); });
+    sp::launch(ctx, shadowMaskKernel, "shadowMaskKernel", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), a);
     return TRHIP_OK;
 }
 

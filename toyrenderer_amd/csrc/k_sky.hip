@@ -10,10 +10,9 @@
 // stand-in: a pixel is written iff its depth word satisfies depth <= 0.0f (+0, -0 and negative; NaN is skipped): the exact
 // complement of the lighting pass apart from NaN, which neither writes.  Every other texel of u0 keeps what it held.
 //
-// CONVENTION (parity unpinned; restated in tests/sky_ref.c and DESIGN.md 3).  IEEE binary32, no contraction, fma only where
-// written, / and sqrt correctly rounded:
-//   inUV, UVToClipXY, the 4-column product with m_ClipToWorld at depth 0.9f, xyz / w, normalize and dot3 exactly as
-//             k_deferredlighting.hip states them; V = normalize(worldPosition - m_CameraPosition);
+// CONVENTION (parity unpinned; restated in tests/sky_ref.c and DESIGN.md 3).  The shared part is stated in screen_pass.hip.h:
+//   worldPosition is its function at depth 0.9f over the bound target's size; V = normalize(worldPosition - m_CameraPosition),
+//             v / sqrt(dot3(v, v));
 //   cosTheta = fmin(fmax(V.y, 0), 1) (a NaN gives 0); cosGamma = dot3(V, m_SunLightDir); gamma = softmath::acosSoft(cosGamma):
 //             outside [-1, 1] or NaN gives NaN, which a view ray that meets the sun direction to the last bit can produce
 //             (dot3 of two unit vectors may round above 1); kept, as the reference's acos does the same;
@@ -27,21 +26,20 @@
 //
 // KERNEL: one thread per pixel, no LDS.  The depth word is read first and a drawn pixel ends there (4 B); a sky pixel stores
 // 4 B more.  Per sky pixel six exponentials, three 3/2 powers, an arc cosine, eight squarings and about ten correctly rounded
-// divisions and square roots: the arithmetic is the cost.  A workgroup is 256 threads covering kSkyTileW x kSkyTileH pixels, a
-// wave one kSkyTileW-wide row segment, as in the lighting kernel.  Code object and measurements: profiles/sky/README.md.
+// divisions and square roots: the arithmetic is the cost.  The tile is screen_pass.hip.h's.  Code object and measurements:
+// profiles/sky/README.md.
 #include "cull_math.hip.h"
 #include "r11g11b10.hip.h"
+#include "screen_pass.hip.h"
 #include "soft_math.hip.h"
-#include "trhip_internal.h"
 
 namespace
 {
 
 using namespace interop;
 
-constexpr uint32_t kSkyBlock = 256, kSkyTileW = 64, kSkyTileH = kSkyBlock / kSkyTileW;
-constexpr uint32_t kSkyGroupSide = 8;          // the reference's full-screen pass stands in as [numthreads(8, 8, 1)] groups, as the lighting entry's
-static_assert(kSkyTileW * kSkyTileH == kSkyBlock, "tile shape");
+constexpr uint32_t kSkyBlock = 256, kSkyTileW = 64;   // tests/test_gpu_sky.py takes its sizes from these names: pinned to the shared tile
+static_assert(kSkyBlock == sp::kBlock && kSkyTileW == sp::kTileW, "the sky pass runs in the shared tile");
 
 struct SkyArgs
 {
@@ -51,7 +49,7 @@ struct SkyArgs
     uint32_t W, H;
 };
 
-#ifdef TR_SKY_EXPERIMENT_HW_EXP                // negative control only (profiles/sky/): v_exp_f32 and approximate division
+#ifdef TR_SKY_EXPERIMENT_HW_EXP                // negative control only (profiles/sky/): v_exp_f32 and approximate division in the radiance (the world position is the shared one)
 __device__ __forceinline__ float sdiv(float a, float b) { return a * __builtin_amdgcn_rcpf(b); }
 __device__ __forceinline__ float exp_(float x) { return __builtin_amdgcn_exp2f(x * 0x1.715476p+0f); }
 #else
@@ -63,12 +61,8 @@ __device__ __forceinline__ float pow15(float b) { return b * cm::sqrt_(b); }
 __device__ __forceinline__ cm::F3 skyPixel(const SkyArgs& a, uint32_t px, uint32_t py)
 {
     const SkyPassParameters& k = a.k;
-    const float u = sdiv((float)px + 0.5f, (float)a.W), v = sdiv((float)py + 0.5f, (float)a.H);
-    const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;                                      // UVToClipXY
-    float h[4];
-    for (int j = 0; j < 4; ++j)
-        h[j] = cm::fma_(0.9f, k.m_ClipToWorld.m[2][j], cm::fma_(cy, k.m_ClipToWorld.m[1][j], cx * k.m_ClipToWorld.m[0][j])) + k.m_ClipToWorld.m[3][j];
-    const cm::F3 d = { sdiv(h[0], h[3]) - k.m_CameraPosition[0], sdiv(h[1], h[3]) - k.m_CameraPosition[1], sdiv(h[2], h[3]) - k.m_CameraPosition[2] };
+    const cm::F3 w = sp::worldPosition(k.m_ClipToWorld, px, py, a.W, a.H, 0.9f);
+    const cm::F3 d = { w.x - k.m_CameraPosition[0], w.y - k.m_CameraPosition[1], w.z - k.m_CameraPosition[2] };
     const float len = cm::sqrt_(cm::dot3(d, d));
     const cm::F3 V = { sdiv(d.x, len), sdiv(d.y, len), sdiv(d.z, len) };
     const float ct = cm::min_(cm::max_(V.y, 0.0f), 1.0f);
@@ -94,17 +88,17 @@ __device__ __forceinline__ cm::F3 skyPixel(const SkyArgs& a, uint32_t px, uint32
              channel(P[0].z, P[1].z, P[2].z, P[3].z, P[4].z, P[5].z, P[6].z, P[7].z, P[8].z, P[9].z) };
 }
 
-__global__ __launch_bounds__(kSkyBlock) void skyKernel(SkyArgs a)
+__global__ __launch_bounds__(sp::kBlock) void skyKernel(SkyArgs a)
 {
-    const uint32_t px = blockIdx.x * kSkyTileW + threadIdx.x, py = blockIdx.y * kSkyTileH + threadIdx.y;
-    if (px >= a.W || py >= a.H) return;
-    const uint64_t i = (uint64_t)py * a.W + px;
+    const sp::Pixel at = sp::pixel();
+    if (!at.inside(a.W, a.H)) return;
+    const uint64_t i = at.index(a.W);
     const float depth = a.depth[i];
     if (!(depth <= 0.0f)) return;                                                                  // drawn (or NaN): costs 4 B
 #ifdef TR_SKY_EXPERIMENT_STORE_ONLY             // attribution only (profiles/sky/): the pass's bytes without its arithmetic
-    a.out[i] = __builtin_bit_cast(uint32_t, depth) ^ px;
+    a.out[i] = __builtin_bit_cast(uint32_t, depth) ^ at.x;
 #else
-    const cm::F3 rgb = skyPixel(a, px, py);
+    const cm::F3 rgb = skyPixel(a, at.x, at.y);
     a.out[i] = trhip::packR11G11B10(rgb.x, rgb.y, rgb.z);
 #endif
 }
@@ -114,29 +108,19 @@ int recordSky(trhip::DispatchCtx& ctx)
     const char* name = ctx.shaderName;
     const SkyPassParameters* k = (const SkyPassParameters*)ctx.constants(0, sizeof(SkyPassParameters));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (SkyPassParameters, 256 bytes) missing or short", name);
-    TRHIP_REQUIRE(!ctx.indirect, "%s: needs a direct dispatch of 8x8-pixel groups", name);
-    uint32_t depthMip = 0, dstMip = 0;
-    trhip_texture_t* depth = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 0, &depthMip);
-    TRHIP_REQUIRE(depth && depth->format == TRHIP_FORMAT_R32_FLOAT, "%s: needs Texture_SRV t0 = the R32_FLOAT depth buffer", name);
-    TRHIP_REQUIRE(depthMip == 0 && depth->mips == 1, "%s: t0 mip %u: the depth buffer has one mip and is read at mip 0", name, depthMip);
-    trhip_texture_t* dst = ctx.texture(TRHIP_BIND_TEXTURE_UAV, 0, &dstMip);
-    TRHIP_REQUIRE(dst && dst->format == TRHIP_FORMAT_R11G11B10_FLOAT, "%s: needs Texture_UAV u0 = the R11G11B10_FLOAT LightingOutput, mip 0", name);
-    TRHIP_REQUIRE(dstMip == 0, "%s: u0 mip %u out of range: the pass writes mip 0", name, dstMip);
-    TRHIP_REQUIRE(depth->width == dst->width && depth->height == dst->height, "%s: t0 is %ux%u, u0 is %ux%u", name, depth->width, depth->height,
-                  dst->width, dst->height);
-    SkyArgs a;
-    memset(&a, 0, sizeof a);
+    const sp::Binding wantTarget[] = { { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R11G11B10_FLOAT, "Texture_UAV u0 = the R11G11B10_FLOAT LightingOutput, mip 0", true, sp::kAt0 } };
+    const sp::Binding wantDepth[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R32_FLOAT, "the R32_FLOAT depth buffer (one mip, read at mip 0) at Texture_SRV t0", true, sp::kOneMipAt0 } };
+    trhip_texture_t *dst[1], *depth[1];
+    if (const int rc = sp::bindTextures(ctx, wantTarget, dst)) return rc;                            // the resolution is the bound target's
+    if (const int rc = sp::bindTextures(ctx, wantDepth, depth, dst[0]->width, dst[0]->height, "u0")) return rc;
+    SkyArgs a = sp::zeroed<SkyArgs>();
     a.k = *k;
-    a.depth = (const float*)depth->ptr;
-    a.out = (uint32_t*)dst->mipPtr(0);
-    a.W = dst->width; a.H = dst->height;
+    a.depth = (const float*)depth[0]->ptr;
+    a.out = (uint32_t*)dst[0]->mipPtr(0);
+    a.W = dst[0]->width; a.H = dst[0]->height;
     TRHIP_REQUIRE(a.W && a.H, "%s: u0 is empty", name);
-    TRHIP_REQUIRE((uint64_t)ctx.gx * kSkyGroupSide >= a.W && (uint64_t)ctx.gy * kSkyGroupSide >= a.H, "%s: a direct dispatch of 8x8-pixel groups covering %ux%u",
-                  name, a.W, a.H);
-    const dim3 grid((a.W + kSkyTileW - 1) / kSkyTileW, (a.H + kSkyTileH - 1) / kSkyTileH);
-    ctx.emit("main", [a, grid](hipStream_t s) {
-        TRHIP_LAUNCH(skyKernel, grid, dim3(kSkyTileW, kSkyTileH), 0, s, a);
-        return trhip::launchStatus("skyKernel"); });
+    if (const int rc = sp::requireCover(ctx, sp::kGroupSide, sp::kGroupSide, a.W, a.H)) return rc;
+    sp::launch(ctx, skyKernel, "skyKernel", sp::tiles(a.W, a.H), dim3(sp::kTileW, sp::kTileH), a);
     return TRHIP_OK;
 }
 

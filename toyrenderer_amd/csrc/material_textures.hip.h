@@ -26,6 +26,7 @@
 #pragma once
 
 #include "../../include/trhip.h"
+#include "screen_pass.hip.h"
 #include "soft_math.hip.h"
 
 namespace mtex
@@ -69,7 +70,7 @@ __device__ __forceinline__ Axis axisOf(float u, uint32_t dim, bool wrap)
     return { (uint32_t)r, (uint32_t)r + 1u == dim ? 0u : (uint32_t)r + 1u, f };
 }
 
-__device__ __forceinline__ float lerp_(float x, float y, float s) { return x + s * (y - x); }
+using sp::lerp_;
 
 // rgbTable: the LDS table the colour bytes go through (sRGB or UNORM)
 __device__ __forceinline__ cm::F3 bilinear(const TableEntry& e, const float* rgbTable, uint32_t level, bool wrap, float u, float v)

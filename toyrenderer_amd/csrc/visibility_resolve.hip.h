@@ -40,6 +40,7 @@
 
 #include "material_textures.hip.h"
 #include "mesh_stage.hip.h"
+#include "screen_pass.hip.h"
 
 #include <type_traits>
 
@@ -50,7 +51,6 @@ using namespace mesh;
 
 constexpr uint32_t kTileW = 16, kTileH = 16;   // one workgroup per 16x16 pixels: a wave covers 16x4 neighbouring pixels
 constexpr uint32_t kBlock = kTileW * kTileH;
-constexpr uint32_t kGroupSide = 8;              // the reference entry's [numthreads(8, 8, 1)]: group counts cover the screen
 constexpr uint32_t kTexturedWaves = 4;          // waves per SIMD of the TEXTURED instantiation: 128 VGPRs (k_gbuffer.hip)
 
 struct ResolveArgs
@@ -73,15 +73,8 @@ struct TexturedArgs : ResolveArgs
     const float* srgb;                                           // 256 floats (trhip_device_t::srgbTable)
 };
 
-__device__ __forceinline__ uint32_t toHalfBits(float f)
-{
-    if (f != f) return 0x7E00u;                                                          // one NaN
-    const _Float16 h = (_Float16)f;                                                      // round to nearest even
-    return (uint32_t)__builtin_bit_cast(uint16_t, h);
-}
-
 // ---- the pack functions of GBufferA (packunpack.hlsli, lightingcommon.hlsli:28-34, random.hlsli:7-11) ----------------
-__device__ __forceinline__ float saturate_(float x) { return cm::min_(cm::max_(x, 0.0f), 1.0f); }
+using sp::saturate_;
 __device__ __forceinline__ uint32_t bitsOf(float f) { return __builtin_bit_cast(uint32_t, f); }
 __device__ __forceinline__ float floatOf(uint32_t u) { return __builtin_bit_cast(float, u); }
 
@@ -140,8 +133,6 @@ __device__ __forceinline__ cm::F3 unpackNormal(uint32_t packed)                 
     return { x * 2.0f - 1.0f, y * 2.0f - 1.0f, z * 2.0f - 1.0f };
 }
 
-__device__ __forceinline__ float halfLo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)); }
-__device__ __forceinline__ float halfHi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
 __device__ __forceinline__ cm::F3 normalize3(cm::F3 v)
 {
     const float len = cm::sqrt_(cm::dot3(v, v));
@@ -161,9 +152,10 @@ void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
         tables = lds;
     }
     const float halfW = 0.5f * (float)a.width, halfH = 0.5f * (float)a.height;
-    const uint32_t px = blockIdx.x * kTileW + threadIdx.x, py = blockIdx.y * kTileH + threadIdx.y;
-    if (px >= a.width || py >= a.height) return;
-    const uint64_t i = (uint64_t)py * a.width + px;
+    const sp::Pixel at = sp::pixel<kTileW, kTileH>();
+    if (!at.inside(a.width, a.height)) return;
+    const uint32_t px = at.x, py = at.y;
+    const uint64_t i = at.index(a.width);
     const unsigned long long texel = a.vis[i];
     if (!texel) return;
     const VisTexel id = unpackVisibility((uint32_t)texel);
@@ -226,7 +218,7 @@ void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
             mx = ux * (float)a.width - cx;
             my = uy * (float)a.height - cy;
         }
-        a.motion[i] = toHalfBits(mx) | toHalfBits(my) << 16;                            // SV_Target1
+        a.motion[i] = sp::halfBits(mx) | sp::halfBits(my) << 16;                            // SV_Target1
         if (GBUFFER) {                                                                   // SV_Target0
             const cm::F3 adj0 = cm::cross3(Wm.r1, Wm.r2), adj1 = cm::cross3(Wm.r2, Wm.r0), adj2 = cm::cross3(Wm.r0, Wm.r1);   // MakeAdjugateMatrix
             cm::F3 N[3];
@@ -250,8 +242,8 @@ void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
                 const float ey0 = sgn * edgeFn(sx[1], sy[1], sx[2], sy[2], cx, cy + 1.0f), ey1 = sgn * edgeFn(sx[2], sy[2], sx[0], sy[0], cx, cy + 1.0f), ey2 = sgn * edgeFn(sx[0], sy[0], sx[1], sy[1], cx, cy + 1.0f);
                 const float qx0 = ex0 / w[0], qx1 = ex1 / w[1], qx2 = ex2 / w[2], qy0 = ey0 / w[0], qy1 = ey1 / w[1], qy2 = ey2 / w[2];
                 const float sX = (qx0 + qx1) + qx2, sY = (qy0 + qy1) + qy2;
-                const float u0 = halfLo(texCoord[0]), u1 = halfLo(texCoord[1]), u2 = halfLo(texCoord[2]);
-                const float v0 = halfHi(texCoord[0]), v1 = halfHi(texCoord[1]), v2 = halfHi(texCoord[2]);
+                const float u0 = (float)sp::halfOf(texCoord[0]), u1 = (float)sp::halfOf(texCoord[1]), u2 = (float)sp::halfOf(texCoord[2]);
+                const float v0 = (float)sp::halfOf(texCoord[0] >> 16), v1 = (float)sp::halfOf(texCoord[1] >> 16), v2 = (float)sp::halfOf(texCoord[2] >> 16);
                 const float u = cm::fma_(q2, u2, cm::fma_(q1, u1, q0 * u0)) / s, v = cm::fma_(q2, v2, cm::fma_(q1, v1, q0 * v0)) / s;
                 const float dudx = cm::fma_(qx2, u2, cm::fma_(qx1, u1, qx0 * u0)) / sX - u, dvdx = cm::fma_(qx2, v2, cm::fma_(qx1, v1, qx0 * v0)) / sX - v;
                 const float dudy = cm::fma_(qy2, u2, cm::fma_(qy1, u1, qy0 * u0)) / sY - u, dvdy = cm::fma_(qy2, v2, cm::fma_(qy1, v1, qy0 * v0)) / sY - v;
@@ -297,8 +289,7 @@ int recordResolve(trhip::DispatchCtx& ctx)
 {
     const BasePassConstants* k = (const BasePassConstants*)ctx.constants(0, sizeof(BasePassConstants));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (BasePassConstants, 256 bytes) missing", ctx.shaderName);
-    TexturedArgs a;                                                                  // ResolveArgs + the table; sliced when none is bound
-    memset(&a, 0, sizeof a);
+    TexturedArgs a = sp::zeroed<TexturedArgs>();                                                                  // ResolveArgs + the table; sliced when none is bound
     a.k = *k;
     if (const int rc = bindGeometry(ctx, a.geo)) return rc;
     trhip_buffer_t* records[4];
@@ -326,8 +317,7 @@ int recordResolve(trhip::DispatchCtx& ctx)
         TRHIP_REQUIRE(gbufferA && gmip == 0 && gbufferA->format == TRHIP_FORMAT_RGBA32_UINT, "%s: needs Texture_UAV u0 = the RGBA32_UINT GBufferA, mip 0", ctx.shaderName);
         TRHIP_REQUIRE(gbufferA->width == W && gbufferA->height == H, "%s: GBufferA %ux%u must be m_OutputResolution %ux%u", ctx.shaderName, gbufferA->width, gbufferA->height, W, H);
     }
-    TRHIP_REQUIRE(!ctx.indirect && (uint64_t)ctx.gx * kGroupSide >= W && (uint64_t)ctx.gy * kGroupSide >= H,
-                  "%s: a direct dispatch of 8x8-pixel groups covering %ux%u", ctx.shaderName, W, H);
+    if (const int rc = sp::requireCover(ctx, sp::kGroupSide, sp::kGroupSide, W, H)) return rc;
     for (uint32_t s = 0; s < 4; ++s) {
         a.records[s] = (const MeshletAmplificationData*)records[s]->ptr;
         a.recordCapacity[s] = elements32(records[s], sizeof(MeshletAmplificationData));
@@ -342,7 +332,7 @@ int recordResolve(trhip::DispatchCtx& ctx)
         a.gbufferA = (uint4*)gbufferA->ptr;
     }
     a.width = W; a.height = H;
-    const dim3 grid((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH);
+    const dim3 grid = sp::tiles(W, H, kTileW, kTileH);
     if constexpr (GBUFFER) {
         if (trhip_texture_table_t* table = ctx.textureTable(19)) {                   // t19: the TEXTURED instantiation
             for (size_t d = 0; d < table->slots.size(); ++d)
