@@ -78,6 +78,14 @@ uint32_t    trhip_abi_version(void);
  * "basepass_MS_Main_visibility": the same bindings, plus u1 (texture) RG32_UINT visibility buffer (render resolution, mip 0) and
  * push constants {uint32 passSlot} (0..3); each covered sample also max-merges (depthBits << 32) | passSlot << 30 |
  * listPosition << 7 | triangle into u1 (equal depth: the larger payload wins).  Visible-list capacity at most 2^23 entries.
+ * "basepass_MS_Main_depth ALPHA_MASK_MODE=1" and "basepass_MS_Main_visibility ALPHA_MASK_MODE=1" (the permutation the reference
+ * draws alpha-mask primitives with, BasePassRenderers.cpp:489; basepass.hlsl:210-215): the bindings of the plain shader, plus t3
+ * MaterialData (124-byte stride, required) and t19 the texture table (TRHIP_BIND_TEXTURE_TABLE, optional).  A covered sample is
+ * discarded iff m_ConstAlbedo.w, times the alpha of the albedo texture (sampled as the resolve samples it, derivatives from the
+ * triangle's plane) when MaterialFlag_UseAlbedoTexture is set, is below m_AlphaCutoff; a NaN is kept.  Nothing of a triangle is
+ * drawn when its m_MaterialDataIdx is past the buffer, or the flag is set and no table is bound, the descriptor index is past the
+ * table, the entry is empty or of another format.  Refused at record time: t3 missing; a table that holds a texture created with
+ * the UAV or render-target bit.  The convention is stated in csrc/k_raster.hip and tests/alpha_test_ref.c.
  * "basepass_PS_Main_motion" (basepass.hlsl:226-237, GBufferMotion): a direct dispatch of [numthreads(8, 8, 1)] groups over
  * the screen; b0 BasePassConstants (m_PrevWorldToClip set), t0 t1 t2 t4 t5 t6 as above, t10..t13 the four slots' records,
  * t14..t17 their visible lists, t18 (texture) the visibility buffer, u0 (texture) RG16_FLOAT motion target: the screen-space
@@ -99,7 +107,8 @@ uint32_t    trhip_abi_version(void);
  * time: a table that holds a texture created with the UAV or render-target bit.
  * That check covers the table's contents when the dispatch is recorded: trhip_texture_table_set rewrites an entry in place, so a
  * UAV-capable texture set AFTERWARDS is sampled by the lists already recorded (read only; nothing is written through the table)
- * and is refused by the next recording.  A texture table bound to any other shader, or at another slot, is refused.
+ * and is refused by the next recording.  A texture table bound to a shader other than this one, the two ALPHA_MASK_MODE=1 rasters
+ * and "shadowmask_CS_ShadowMask", or at another slot, is refused.
  * "deferredlighting_PS_Main" and "deferredlighting_PS_Main_Debug" (deferredlighting.hlsl, DeferredLightingRenderer.cpp: the
  * directional light and the debug views, without DDGI): a direct dispatch of [numthreads(8, 8, 1)] groups over the screen;
  * b0 DeferredLightingConsts (112 bytes; m_bRTDDGIEnabled must be 0, m_DebugMode must not be 10), t0 (texture) RGBA32_UINT
@@ -369,7 +378,11 @@ int  trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics*
  * (112 bytes, a constant buffer; m_bDoDenoising must be 0), t0 (texture) R32_FLOAT depth, t1 the TLAS nodes, t2 (texture) GBufferA,
  * t3 instances, t4 vertices, t5 materials, t6 indices, t7 mesh data, t8 (texture) RGBA8_UNORM 128 x 128 blue noise, u0 (texture)
  * R8_UNORM mask, u1 (texture) R16_FLOAT linear view depth, and the structure's other buffers: t9 TLAS instances, t10 BLAS
- * headers, t11 BLAS nodes, t12 triangle order.  Samplers are accepted and ignored.  A texel of depth 0.0f gets u1 = 65504 and
+ * headers, t11 BLAS nodes, t12 triangle order, and optionally t19 the texture table: with it ("#textured" in the profile) a
+ * candidate on a ForceNonOpaque instance whose material has MaterialFlag_UseAlbedoTexture counts iff m_ConstAlbedo.w times the
+ * albedo texture's alpha at the hit (one bilinear fetch of mip 0 at InterpolateVertex's uv; a broken descriptor: it does not
+ * count) is at least m_AlphaCutoff; without it, and for texture-free materials, iff m_ConstAlbedo.w >= m_AlphaCutoff.
+ * Samplers are accepted and ignored.  A texel of depth 0.0f gets u1 = 65504 and
  * keeps u0; any other gets u0 = 0 (occluded) or 255 and u1 = fp16(|worldPosition - m_CameraPosition|).  An index read on the
  * device that leaves its buffer ends that instance's (or triangle's) test; it is never followed. */
 typedef struct { float lo[3]; uint32_t skip; float hi[3]; uint32_t leaf; } trhip_accel_node;

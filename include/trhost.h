@@ -94,6 +94,13 @@ int  trhost_load_materials(const void* materials, uint32_t count);
  * it fails with a message containing "texture".  The textures live until trhost_shutdown. */
 int  trhost_create_material_texture(uint32_t width, uint32_t height, uint32_t mips, uint32_t format, const void* data, uint64_t bytes);
 int  trhost_set_gbuffer(int enable);
+/* ALPHA_MASK_MODE's discard (basepass.hlsl:210-215), default 0 = off: alpha-mask primitives are drawn as solid triangles, as before.
+ * With 1 (needs the rasters: trhost_set_raster_depth, trhost_set_visibility_buffer or anything that implies them, and
+ * trhost_load_materials; fails otherwise) the alpha-mask pass slots draw through "basepass_MS_Main_depth ALPHA_MASK_MODE=1" or
+ * "basepass_MS_Main_visibility ALPHA_MASK_MODE=1" (include/trhip.h) with the materials at t3 and, when a loaded material is
+ * textured, the texture table at t19: a sample whose m_ConstAlbedo.w times its albedo texture's alpha is below m_AlphaCutoff is
+ * not drawn.  ShadowMaskRenderer then binds the table as well, and a textured cut-out casts the shadow of its kept texels. */
+int  trhost_set_alpha_test(int enabled);
 int  trhost_set_debug_view_mode(uint32_t mode);
 int  trhost_download_gbuffer_a(uint32_t* words, uint64_t bytes);
 /* Deferred lighting from GBufferA (DeferredLightingRenderer.cpp; implies the G-buffer, same refusals): after GBufferRenderer one

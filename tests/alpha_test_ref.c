@@ -1,0 +1,256 @@
+/* alpha_test_ref.c -- the definition of the alpha test: ALPHA_MASK_MODE's discard in the rasters ("basepass_MS_Main_depth
+ * ALPHA_MASK_MODE=1", "basepass_MS_Main_visibility ALPHA_MASK_MODE=1", csrc/k_raster.hip) and the textured alpha test of the sun
+ * rays ("shadowmask_CS_ShadowMask" with a texture table at t19, csrc/k_shadowmask.hip).  Compiled by the tests themselves with
+ * gcc -O2 -ffp-contract=off (tests/alpha_test_ref.py): only the fmaf calls written here fuse.
+ *
+ * It includes the two references it extends, unedited: tests/material_textures_ref.c (the sampler, the vertex arithmetic, the
+ * edge function, MaterialData) and tests/shadowmask_ref.c (the ray of a texel, the ray set-up, SmScene), the latter with the three
+ * helper names both files define renamed.
+ *
+ * ALPHA.  at_sample_alpha = component 3 of mt_sample: the footprint, tap count, lod, tap positions, trilinear and bilinear
+ *   arithmetic, addressing and summation order of the colour channels, applied to byte 3 of the texel, (float)byte / 255.0f in
+ *   both formats (alpha never goes through the sRGB table).  at_alpha_level0 = one bilinear fetch of mip 0.
+ *
+ * RASTER (at_raster).  vr_raster of tests/visibility_ref.c restated, with one step added.  A covered sample of a triangle (all
+ *   three edge values e_i >= 0, den > 0, d > 0) passes, before it is merged into either target:
+ *   1. q_i = e_i / w_i, s = (q0 + q1) + q2, from the sample's own edge values and the vertices' clip w;
+ *   2. uv = fmaf(q2, a2, fmaf(q1, a1, q0 * a0)) / s of m_TexCoord (half -> float, exact);
+ *   3. ddx(uv), ddy(uv) = the same interpolation of the same triangle with the edge functions re-evaluated at (cx + 1, cy) and
+ *      at (cx, cy + 1), minus the centre value (the formulas of the TEXTURED resolve, tests/material_textures_ref.c);
+ *   4. alpha = m_ConstAlbedo.w, times at_sample_alpha(albedo texture, m_IsWrapSampler, uv, ddx, ddy) if MaterialFlag_UseAlbedoTexture;
+ *   5. the sample is discarded iff alpha < m_AlphaCutoff (a NaN alpha is kept);
+ *   6. nothing of the triangle is drawn when m_MaterialDataIdx is past the buffer, or the albedo flag is set and no table is
+ *      given, the descriptor index is past the table, the entry is empty or of another format.
+ *   The surviving samples feed the same maxima, so the result does not depend on the draw order.  Parity with hardware unpinned.
+ *
+ * RAYS (at_trace).  occluded_brute of tests/shadowmask_ref.c restated: every triangle of every instance.  A candidate on a
+ *   ForceNonOpaque instance whose material has MaterialFlag_UseAlbedoTexture counts iff
+ *   m_ConstAlbedo.w * at_alpha_level0(albedo texture, m_IsWrapSampler, uv) >= m_AlphaCutoff, with InterpolateVertex's uv
+ *   (raytracingcommon.hlsli:24-36, :189): b1 = V / det, b2 = W / det of the watertight test's edge values, b0 = (1.0f - b1) - b2,
+ *   uv = ((0 + uv0 * b0) + uv1 * b1) + uv2 * b2, not fused.  A broken descriptor: the candidate does not count.  Texture-free
+ *   materials keep m_ConstAlbedo.w >= m_AlphaCutoff.  numTextures < 0: no table, every material by the texture-free rule (today's
+ *   kernel).  DEVIATION: the reference calls Sample in a compute shader, where the derivatives come from unrelated neighbouring
+ *   rays; this build reads mip 0.
+ */
+#include "material_textures_ref.c"
+
+#define float_of sm_float_of_
+#define bits_of sm_bits_of_
+#define normalize3 sm_normalize3_
+#include "shadowmask_ref.c"
+#undef float_of
+#undef bits_of
+#undef normalize3
+
+float at_sample_alpha(const MtTexture* t, int wrap, const float uv[2], const float dx[2], const float dy[2])
+{
+    float srgb[256], out[4];
+    mt_srgb_table(srgb);                                                         /* never read by component 3 */
+    mt_sample(t, srgb, wrap, uv, dx, dy, out, 0);
+    return out[3];
+}
+
+float at_alpha_level0(const MtTexture* t, int wrap, float u, float v)
+{
+    float srgb[256], out[4];
+    mt_srgb_table(srgb);
+    bilinear(t, srgb, 0, wrap, u, v, out);
+    return out[3];
+}
+
+static const MtTexture* table_entry(const MtTexture* textures, int64_t numTextures, uint32_t d)
+{
+    if (!textures || (int64_t)d >= numTextures || !textures[d].width) return 0;
+    if (textures[d].format != MT_FORMAT_RGBA8 && textures[d].format != MT_FORMAT_SRGBA8) return 0;
+    return &textures[d];
+}
+
+/* ---- the raster of one pass slot ---------------------------------------------------------------------------------------------
+ * alphaTest = 0: vr_raster.  counts (optional, uint64[4]): the covered samples (d > 0) of the slot's triangles that were kept and
+ * discarded, {kept, discarded} of the triangles whose bounding box has at most 1024 pixels (drawn in place by the kernel's main
+ * launch) and {kept, discarded} of the larger ones (queue, bin and tile launch). */
+void at_raster(const OrcBasePassConstants* k, const OrcBasePassInstanceConstants* instances, const OrcMeshData* meshData,
+               const OrcMeshletData* meshlets, const OrcRawVertexFormat* vertices, const uint32_t* vertexIds, const uint32_t* triangles,
+               const OrcMeshletAmplificationData* records, const uint32_t* list, uint32_t numVisible, uint32_t slot,
+               const unsigned char* materials, uint32_t numMaterials, const MtTexture* textures, int64_t numTextures, int alphaTest,
+               float* depth, uint64_t* vis, uint64_t* counts)
+{
+    const uint32_t W = k->m_OutputResolution[0], H = k->m_OutputResolution[1];
+    const float halfW = 0.5f * (float)W, halfH = 0.5f * (float)H;
+    for (uint32_t v = 0; v < numVisible; ++v) {
+        const OrcMeshletAmplificationData* rec = &records[list[v] >> 5];
+        const OrcBasePassInstanceConstants* inst = &instances[rec->m_InstanceConstIdx];
+        const uint32_t lodIdx = rec->m_MeshLOD < ORC_MAX_LODS ? rec->m_MeshLOD : ORC_MAX_LODS - 1;
+        const OrcMeshLODData* lod = &meshData[inst->m_MeshDataIdx].m_MeshLODDatas[lodIdx];
+        const OrcMeshletData* ml = &meshlets[lod->m_MeshletDataBufferIdx + rec->m_MeshletGroupOffset + (list[v] & 31u)];
+        MtMaterialData mat;
+        const MtTexture* tex = 0;
+        if (alphaTest) {
+            if (inst->m_MaterialDataIdx >= numMaterials) continue;
+            memcpy(&mat, materials + (uint64_t)inst->m_MaterialDataIdx * sizeof mat, sizeof mat);
+            if (mat.m_MaterialFlags & 1u) {
+                tex = table_entry(textures, numTextures, mat.m_Textures[0].m_DescriptorIndex);
+                if (!tex) continue;
+            }
+        }
+        uint32_t nv = ml->m_VertexAndTriangleCount & 0xFFu;
+        const uint32_t nt = (ml->m_VertexAndTriangleCount >> 8) & 0xFFu;
+        if (nv > 64u) nv = 64u;
+        float sx[64], sy[64], sd[64], sw[64], uv[64][2];
+        int ok[64];
+        for (uint32_t i = 0; i < nv; ++i) {
+            const OrcRawVertexFormat* vtx = &vertices[vertexIds[ml->m_MeshletVertexIDsBufferIdx + i]];
+            float wp[3], c[4];
+            mul_point3(vtx->m_Position, &inst->m_WorldMatrix, wp);
+            mul_point_4(wp, &k->m_WorldToClip, c);
+            sw[i] = c[3];
+            sx[i] = fmaf(c[0] / c[3], halfW, halfW);
+            sy[i] = fmaf(-(c[1] / c[3]), halfH, halfH);
+            sd[i] = c[2] / c[3];
+            ok[i] = c[3] > k->m_NearPlane;
+            uv[i][0] = mt_half_to_float(vtx->m_TexCoord[0]);
+            uv[i][1] = mt_half_to_float(vtx->m_TexCoord[1]);
+        }
+        for (uint32_t t = 0; t < nt; ++t) {
+            const uint32_t packed = triangles[ml->m_MeshletIndexIDsBufferIdx + t];
+            const uint32_t a = packed & 0xFFu, b = (packed >> 8) & 0xFFu, c = (packed >> 16) & 0xFFu;
+            if (a >= nv || b >= nv || c >= nv || !(ok[a] && ok[b] && ok[c])) continue;
+            const float area = edge(sx[a], sy[a], sx[b], sy[b], sx[c], sy[c]);
+            if (!(area != 0.0f)) continue;
+            const float sgn = area < 0.0f ? -1.0f : 1.0f;
+            const float minx = fminf(fminf(sx[a], sx[b]), sx[c]), maxx = fmaxf(fmaxf(sx[a], sx[b]), sx[c]);
+            const float miny = fminf(fminf(sy[a], sy[b]), sy[c]), maxy = fmaxf(fmaxf(sy[a], sy[b]), sy[c]);
+            if (!(maxx >= 0.0f && maxy >= 0.0f && minx <= (float)W && miny <= (float)H)) continue;
+            const int x0 = (int)fmaxf(floorf(minx), 0.0f), x1 = (int)fminf(ceilf(maxx), (float)(W - 1));
+            const int y0 = (int)fmaxf(floorf(miny), 0.0f), y1 = (int)fminf(ceilf(maxy), (float)(H - 1));
+            if (x1 < x0 || y1 < y0) continue;
+            const int big = (uint64_t)(x1 - x0 + 1) * (uint64_t)(y1 - y0 + 1) > 1024u;
+            const uint64_t payload = (uint64_t)slot << 30 | (uint64_t)v << 7 | t;
+            for (int py = y0; py <= y1; ++py)
+                for (int px = x0; px <= x1; ++px) {
+                    const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
+                    float q[3][3], s[3], tc[3][2];
+                    int covered = 1;
+                    for (int p = 0; p < (alphaTest && tex ? 3 : 1) && covered; ++p) {     /* the centre, (cx + 1, cy), (cx, cy + 1) */
+                        const float x = p == 1 ? cx + 1.0f : cx, y = p == 2 ? cy + 1.0f : cy;
+                        const float e0 = sgn * edge(sx[b], sy[b], sx[c], sy[c], x, y);
+                        const float e1 = sgn * edge(sx[c], sy[c], sx[a], sy[a], x, y);
+                        const float e2 = sgn * edge(sx[a], sy[a], sx[b], sy[b], x, y);
+                        if (p == 0) {
+                            covered = e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f && (e0 + e1) + e2 > 0.0f;
+                            if (!covered) break;
+                            q[0][0] = e0; q[0][1] = e1; q[0][2] = e2;                     /* kept for the depth below */
+                        }
+                        const float q0 = e0 / sw[a], q1 = e1 / sw[b], q2 = e2 / sw[c];
+                        s[p] = (q0 + q1) + q2;
+                        for (int j = 0; j < 2; ++j) tc[p][j] = fmaf(q2, uv[c][j], fmaf(q1, uv[b][j], q0 * uv[a][j])) / s[p];
+                    }
+                    if (!covered) continue;
+                    const float e0 = q[0][0], e1 = q[0][1], e2 = q[0][2];
+                    const float den = (e0 + e1) + e2;
+                    const float d = fmaf(e2, sd[c], fmaf(e1, sd[b], e0 * sd[a])) / den;
+                    if (!(d > 0.0f)) continue;
+                    if (alphaTest) {
+                        float alpha = mat.m_ConstAlbedo[3];
+                        if (tex) {
+                            const float dx[2] = { tc[1][0] - tc[0][0], tc[1][1] - tc[0][1] }, dy[2] = { tc[2][0] - tc[0][0], tc[2][1] - tc[0][1] };
+                            alpha = alpha * at_sample_alpha(tex, mat.m_Textures[0].m_IsWrapSampler != 0, tc[0], dx, dy);
+                        }
+                        const int discard = alpha < mat.m_AlphaCutoff;
+                        if (counts) ++counts[2 * big + discard];
+                        if (discard) continue;
+                    }
+                    const uint64_t i = (uint64_t)py * W + px;
+                    if (d > depth[i]) depth[i] = d;
+                    if (t < 128u) {
+                        const uint64_t texel = (uint64_t)bits_of(d) << 32 | payload;
+                        if (texel > vis[i]) vis[i] = texel;
+                    }
+                }
+        }
+    }
+}
+
+/* ---- the sun rays ------------------------------------------------------------------------------------------------------------ */
+/* sm_tri_hit, with the barycentrics of the second and third vertex */
+static int at_tri_hit(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax, float* b1, float* b2)
+{
+    const F3 A = { v0.x - r->o.x, v0.y - r->o.y, v0.z - r->o.z }, B = { v1.x - r->o.x, v1.y - r->o.y, v1.z - r->o.z }, C = { v2.x - r->o.x, v2.y - r->o.y, v2.z - r->o.z };
+    const float Akz = sel(A, r->kz), Bkz = sel(B, r->kz), Ckz = sel(C, r->kz);
+    const float Ax = sel(A, r->kx) - r->Sx * Akz, Ay = sel(A, r->ky) - r->Sy * Akz;
+    const float Bx = sel(B, r->kx) - r->Sx * Bkz, By = sel(B, r->ky) - r->Sy * Bkz;
+    const float Cx = sel(C, r->kx) - r->Sx * Ckz, Cy = sel(C, r->ky) - r->Sy * Ckz;
+    const float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f)) return 0;
+    const float det = (U + V) + W;
+    if (det == 0.0f) return 0;
+    const float Az = r->Sz * Akz, Bz = r->Sz * Bkz, Cz = r->Sz * Ckz;
+    const float T = (U * Az + V * Bz) + W * Cz;
+    const float t = T / det;
+    *b1 = V / det; *b2 = W / det;
+    return t > tmin && t < tmax;
+}
+
+static int at_commits(const SmScene* s, const MtTexture* textures, int64_t numTextures, uint32_t inst, uint32_t flags, const uint16_t tc[3][2], float b1, float b2)
+{
+    if (flags != 2u) return 1;
+    const uint32_t mi = s->instances[inst].material;
+    if (mi >= s->numMaterials) return 0;
+    MtMaterialData mat;
+    memcpy(&mat, &s->materials[mi], sizeof mat);
+    if (numTextures >= 0 && (mat.m_MaterialFlags & 1u)) {
+        const MtTexture* tex = table_entry(textures, numTextures, mat.m_Textures[0].m_DescriptorIndex);
+        if (!tex) return 0;
+        const float b0 = (1.0f - b1) - b2;
+        float uv[2];
+        for (int j = 0; j < 2; ++j)
+            uv[j] = ((0.0f + mt_half_to_float(tc[0][j]) * b0) + mt_half_to_float(tc[1][j]) * b1) + mt_half_to_float(tc[2][j]) * b2;
+        return mat.m_ConstAlbedo[3] * at_alpha_level0(tex, mat.m_Textures[0].m_IsWrapSampler != 0, uv[0], uv[1]) >= mat.m_AlphaCutoff;
+    }
+    return mat.m_ConstAlbedo[3] >= mat.m_AlphaCutoff;
+}
+
+static int at_occluded(const SmScene* s, const MtTexture* textures, int64_t numTextures, F3 o, F3 d, float tmin, float tmax)
+{
+    for (uint32_t i = 0; i < s->numInstances; ++i) {
+        const uint32_t flags = s->flags[i] & 3u, mesh = s->instances[i].mesh;
+        if (!flags || mesh >= s->numMeshes) continue;
+        float m[12];
+        sm_object_from_world(s->instances[i].world, m);
+        const SmRay r = make_ray(mul_point(o, m, 1), mul_point(d, m, 0));
+        for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t) {
+            const uint64_t base = (uint64_t)s->meshes[mesh].indexBase + 3ull * t;
+            if (base + 3u > s->numIndices) continue;
+            F3 v[3];
+            uint16_t tc[3][2];
+            int ok = 1;
+            for (int k = 0; ok && k < 3; ++k) {
+                const uint64_t vi = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + k];
+                ok = vi < s->numVertices;
+                if (!ok) break;
+                v[k] = vertex_of(s, vi);
+                ok = finite3(v[k]);
+                memcpy(tc[k], s->vertices + vi * 20u + 16u, 4);
+            }
+            float b1, b2;
+            if (ok && at_tri_hit(v[0], v[1], v[2], &r, tmin, tmax, &b1, &b2) && at_commits(s, textures, numTextures, i, flags, tc, b1, b2)) return 1;
+        }
+    }
+    return 0;
+}
+
+/* sm_trace, brute force, with the table.  numTextures < 0: no table (equals sm_trace mode 0). */
+void at_trace(const SmConsts* k, const SmScene* s, const MtTexture* textures, int64_t numTextures, const float* depth, const uint32_t* gbufferA,
+              const uint32_t* noise, uint8_t* mask, uint16_t* lvd)
+{
+    for (uint32_t py = 0; py < k->H; ++py)
+        for (uint32_t px = 0; px < k->W; ++px) {
+            const uint64_t i = (uint64_t)py * k->W + px;
+            float o[3], d[3], w[3];
+            if (!sm_texel_ray(k, px, py, depth[i], gbufferA + 4 * i, noise, o, d, w)) { lvd[i] = 0x7BFFu; continue; }
+            const F3 O = { o[0], o[1], o[2] }, D = { d[0], d[1], d[2] };
+            mask[i] = at_occluded(s, textures, numTextures, O, D, k->rayStartOffset, 1e10f) ? 0u : 255u;
+            const F3 v = { w[0] - k->camera[0], w[1] - k->camera[1], w[2] - k->camera[2] };
+            lvd[i] = sm_half_bits(sqrtf(dot3f(v, v)));
+        }
+}

@@ -1,0 +1,139 @@
+"""ctypes wrapper of tests/alpha_test_ref.c, the definition of the alpha test: the alpha sampler (sample_alpha, alpha_level0), the
+depth and visibility raster of one pass slot with ALPHA_MASK_MODE's discard (raster, frame_raster) and the brute-force shadow mask
+with textured alpha (trace).
+
+The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import material_textures_ref as MT
+import shadowmask_ref as SR
+from toyrenderer_amd import accel
+from toyrenderer_amd import interop as I
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+F = np.float32
+_LIB = {}
+Texture = MT.Texture
+
+
+def load(tmpdir) -> C.CDLL:
+    out = os.path.join(str(tmpdir), "libalpha_test_ref.so")
+    if out not in _LIB:
+        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "oracle"),
+                               os.path.join(HERE, "alpha_test_ref.c"), "-o", out, "-lm"])
+        lib = C.CDLL(out)
+        vp, u32, i64 = C.c_void_p, C.c_uint32, C.c_int64
+        lib.at_sample_alpha.argtypes = [vp, C.c_int, vp, vp, vp]
+        lib.at_sample_alpha.restype = C.c_float
+        lib.at_alpha_level0.argtypes = [vp, C.c_int, C.c_float, C.c_float]
+        lib.at_alpha_level0.restype = C.c_float
+        lib.at_raster.argtypes = [vp] * 9 + [u32, u32, vp, u32, vp, i64, C.c_int, vp, vp, vp]
+        lib.at_raster.restype = None
+        lib.at_trace.argtypes = [vp, C.POINTER(SR._Scene), vp, i64, vp, vp, vp, vp, vp]
+        lib.at_trace.restype = None
+        _LIB[out] = lib
+    return _LIB[out]
+
+
+def _p(a):
+    return a.ctypes.data if a is not None else None
+
+
+def table_of(textures):
+    """(ctypes array, [Texture]) of a list of (mips, format), Texture or None (an empty entry)."""
+    made = [t if t is None or isinstance(t, MT.Texture) else MT.Texture(*t) for t in textures]
+    table = (MT.MtTexture * max(len(made), 1))()
+    for i, t in enumerate(made):
+        if t is not None:
+            table[i] = t.c
+    return table, made
+
+
+def sample_alpha(lib, tex: MT.Texture, wrap, uv, ddx, ddy) -> np.float32:
+    uv, ddx, ddy = (np.ascontiguousarray(a, F) for a in (uv, ddx, ddy))
+    return F(lib.at_sample_alpha(C.addressof(tex.c), int(bool(wrap)), _p(uv), _p(ddx), _p(ddy)))
+
+
+def alpha_level0(lib, tex: MT.Texture, wrap, u, v) -> np.float32:
+    return F(lib.at_alpha_level0(C.addressof(tex.c), int(bool(wrap)), C.c_float(float(u)), C.c_float(float(v))))
+
+
+def raster(lib, consts, geo, records, visible_list, slot, depth, vis, materials, textures, alpha_test=True):
+    """Max-merges one slot's listed meshlets into depth (float32 [H, W]) and vis (uint64 [H, W]), in place, with the discard when
+    alpha_test.  textures: the table (a list of (mips, format), Texture or None), or None = no table bound.  Returns the counts
+    {main kept, main discarded, tiles kept, tiles discarded} (zeros without alpha_test)."""
+    k = np.ascontiguousarray(consts)
+    rec = np.ascontiguousarray(records)
+    lst = np.ascontiguousarray(visible_list, np.uint32)
+    mats = np.ascontiguousarray(materials, I.MaterialData)
+    assert depth.dtype == np.float32 and vis.dtype == np.uint64 and depth.flags.c_contiguous and vis.flags.c_contiguous
+    table, keep = table_of(textures if textures is not None else [])
+    counts = np.zeros(4, np.uint64)
+    lib.at_raster(_p(k), *geo.args(), _p(rec), _p(lst), len(lst), int(slot), _p(mats), len(mats), C.addressof(table) if textures is not None else None,
+                  len(textures) if textures is not None else -1, int(bool(alpha_test)), _p(depth), _p(vis), _p(counts))
+    del keep
+    return counts
+
+
+def frame_raster(lib, consts, geo, ref, W, H, materials, textures, alpha_test=True):
+    """(vis, depth, counts) of a pyoracle.frame result: slots 0 and 1 (opaque) without the discard, slots 2 and 3 (alpha mask)
+    with it when alpha_test."""
+    vis, depth, counts = np.zeros((H, W), np.uint64), np.zeros((H, W), np.float32), np.zeros(4, np.uint64)
+    for s in range(4):
+        if ref.passRan[s]:
+            n = min(int(ref.drawArgs[s][0]), len(ref.visibleList[s]))
+            counts += raster(lib, consts, geo, ref.records[s], ref.visibleList[s][:n], s, depth, vis, materials, textures, alpha_test and s >= 2)
+    return vis, depth, counts
+
+
+def trace(lib, k, acc: SR.Accel, depth, gbuffer, noise, textures, instances=None, mask=None, lvd=None):
+    """The brute-force pass over one image with the table `textures` (None: no table, today's rule): (mask uint8 [H, W], linear
+    view depth words uint16 [H, W])."""
+    sc = acc.scene
+    k = np.ascontiguousarray(k, I.ShadowMaskConsts)
+    W, H = (int(x) for x in k["m_OutputResolution"][0])
+    inst = np.ascontiguousarray(sc["instances"] if instances is None else instances, I.BasePassInstanceConstants)
+    nodes, records = acc.tlas["nodes"], acc.tlas["records"]
+    keep = [inst, np.ascontiguousarray(acc.flags, np.uint32), np.ascontiguousarray(sc["vertices"], I.RawVertexFormat), np.ascontiguousarray(sc["materials"], I.MaterialData),
+            np.ascontiguousarray(sc["indices"], np.uint32), np.ascontiguousarray(sc["meshData"], I.MeshData), np.ascontiguousarray(acc.blas["index_counts"], np.uint32),
+            np.ascontiguousarray(nodes, I.AccelNode), np.ascontiguousarray(records, I.TLASInstance), np.ascontiguousarray(acc.blas["headers"]),
+            np.ascontiguousarray(acc.blas["nodes"]), np.ascontiguousarray(acc.blas["tri_order"], np.uint32)]
+    p = [a.ctypes.data for a in keep]
+    s = SR._Scene(p[0], p[1], len(inst), p[2], len(keep[2]), p[3], len(keep[3]), p[4], len(keep[4]), p[5], p[6], len(keep[5]), p[7], len(keep[7]), p[8], p[9], p[10],
+                  len(keep[10]), p[11], len(keep[11]))
+    depth = np.ascontiguousarray(depth, F).reshape(H, W)
+    g = np.ascontiguousarray(gbuffer, np.uint32).reshape(H, W, 4)
+    nz = np.ascontiguousarray(accel.noise_words(noise))
+    mask = np.full((H, W), SR.SENTINEL8, np.uint8) if mask is None else np.ascontiguousarray(mask, np.uint8).copy()
+    lvd = np.full((H, W), SR.SENTINEL16, np.uint16) if lvd is None else np.ascontiguousarray(lvd, np.uint16).copy()
+    table, made = table_of(textures if textures is not None else [])
+    lib.at_trace(k.ctypes.data, C.byref(s), C.addressof(table) if textures is not None else None, len(textures) if textures is not None else -1,
+                 depth.ctypes.data, g.ctypes.data, nz.ctypes.data, mask.ctypes.data, lvd.ctypes.data)
+    del made
+    return mask, lvd
+
+
+def frames(oracle, lib, sc, view, flags, alpha_test=True, count=2, record_capacity=4096):
+    """[(pyoracle frame result, vis, depth)] of `count` consecutive frames of the scene dict `sc` (tests/alpha_test_scenes.py): the
+    oracle's cull, this reference's rasters on its lists, and, as the frame's last GenerateHZB does, the HZB of the next frame built
+    from the depth those rasters left (the oracle's own is built from solid cards)."""
+    from visibility_ref import Geometry
+    from visibility_scenes import consts
+    W, H = view.renderW, view.renderH
+    k = consts(view)
+    geo = Geometry(sc, sc["vertices"], sc["vertexIds"], sc["triangles"])
+    hzb = oracle.HzbTexture(*view.hzb_dims)
+    out = []
+    for _ in range(count):
+        ref = oracle.frame(sc, view.as_dict(), hzb, np.zeros((H, W), F), cullingFlags=flags, record_capacity=record_capacity,
+                           raster=(I.world_to_clip(view.worldToView, view.viewToClip), sc["vertices"], sc["vertexIds"], sc["triangles"]))
+        vis, depth, _ = frame_raster(lib, k, geo, ref, W, H, sc["materials"], sc["textures"], alpha_test)
+        if flags & 2:
+            hzb.build_from_depth(depth)
+        out.append((ref, vis, depth))
+    return out

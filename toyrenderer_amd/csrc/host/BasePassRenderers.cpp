@@ -420,13 +420,22 @@ public:
             rasterBindings.push_back(Item::StructuredBuffer_SRV(9, visibleListBuffer));
             rasterBindings.push_back(Item::Texture_UAV(0, m_CurrentDepthBuffer));
             rasterPass.m_CommandList = commandList;
-            rasterPass.m_ShaderName = "basepass_MS_Main_depth";
+            // :489, :690-691: alpha-mask primitives draw through the ALPHA_MASK_MODE=1 permutation, which reads the materials (t3)
+            // and, when a loaded material is textured, the descriptor table (t19)
+            const bool bAlphaTest = bAlphaMaskPrimitives && g_Scene->m_bAlphaTest;
+            if (bAlphaTest) {
+                check(g_Graphic.m_GlobalMaterialDataBuffer);
+                rasterBindings.push_back(Item::StructuredBuffer_SRV(3, g_Graphic.m_GlobalMaterialDataBuffer));
+                if (g_Graphic.m_bAnyMaterialTextured)
+                    rasterBindings.push_back(Item::DescriptorTable(19, g_Graphic.m_SrvUavCbvDescriptorTable));
+            }
+            rasterPass.m_ShaderName = bAlphaTest ? "basepass_MS_Main_depth ALPHA_MASK_MODE=1" : "basepass_MS_Main_depth";
             const uint32_t passSlot = (uint32_t)slot;
             if (g_Scene->m_bVisibilityBuffer) {                               // + the per-pixel identity: u1, push constant {passSlot}
                 check(m_VisibilityBuffer);
                 rasterBindings.push_back(Item::Texture_UAV(1, m_VisibilityBuffer));
                 rasterBindings.push_back(Item::PushConstants(1, sizeof(passSlot)));
-                rasterPass.m_ShaderName = "basepass_MS_Main_visibility";
+                rasterPass.m_ShaderName = bAlphaTest ? "basepass_MS_Main_visibility ALPHA_MASK_MODE=1" : "basepass_MS_Main_visibility";
                 rasterPass.m_PushConstantsData = &passSlot;
                 rasterPass.m_PushConstantsBytes = sizeof(passSlot);
             }

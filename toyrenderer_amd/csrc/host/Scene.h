@@ -97,6 +97,10 @@ public:
     // GBufferA (trhost_set_gbuffer; implies m_bVisibilityBuffer): "basepass_PS_Main_GBuffer" resolves GBufferA and
     // GBufferMotion in one dispatch in the place of "basepass_PS_Main_motion".  Needs LoadMaterials.
     bool m_bGBuffer = false;
+    // ALPHA_MASK_MODE's discard (trhost_set_alpha_test; needs m_bRasterDepth and LoadMaterials): the alpha-mask pass slots draw
+    // through "basepass_MS_Main_depth ALPHA_MASK_MODE=1" / "basepass_MS_Main_visibility ALPHA_MASK_MODE=1" (BasePassRenderers.cpp:489),
+    // and ShadowMaskRenderer binds the texture table.  Off: alpha-mask instances are drawn as solid triangles.
+    bool m_bAlphaTest = false;
     uint32_t m_DebugViewMode = 0;                    // Scene.h: feeds BasePassConstants::m_DebugMode (BasePassRenderers.cpp:455) and DeferredLightingConsts::m_DebugMode
     // Deferred lighting (trhost_set_deferred_lighting; implies m_bGBuffer): DeferredLightingRenderer runs after GBufferRenderer,
     // "deferredlighting_PS_Main" or, with m_DebugViewMode != 0, "deferredlighting_PS_Main_Debug", into its LightingOutput.

@@ -125,6 +125,8 @@ public:
             Item::Sampler(0, g_CommonResources.LinearClampSampler),           // accepted and ignored (texture-free materials)
             Item::Sampler(1, g_CommonResources.LinearClampSampler),
         };
+        if (g_Scene->m_bAlphaTest && g_Graphic.m_bAnyMaterialTextured)        // GetRayHitInstanceGBufferParams samples the albedo texture's alpha (t19)
+            p.m_BindingSetDesc.bindings.push_back(Item::DescriptorTable(19, g_Graphic.m_SrvUavCbvDescriptorTable));
         p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(passConstants.m_OutputResolution, 8);
         g_Graphic.AddComputePass(p);
     }

@@ -159,6 +159,17 @@ int trhost_set_gbuffer(int enable)
     });
 }
 
+int trhost_set_alpha_test(int enabled)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (enabled && !g_Scene->m_bRasterDepth)
+            throw nvrhi::Error("trhost_set_alpha_test: the rasters are off (trhost_set_raster_depth, trhost_set_visibility_buffer or trhost_set_gbuffer first): the test runs in them");
+        if (enabled && !g_Graphic.m_GlobalMaterialDataBuffer) throw nvrhi::Error("trhost_set_alpha_test: no materials (trhost_load_materials first)");
+        g_Scene->m_bAlphaTest = enabled != 0;
+    });
+}
+
 int trhost_set_debug_view_mode(uint32_t mode)
 {
     return guarded([&] {

@@ -38,6 +38,34 @@
 // kernels, launches, op names and arithmetic; the compiler schedules and allocates its registers slightly differently
 // (tiles: 58 VGPRs instead of 55).
 // tools/raster_time.py at 3840x2160, per launch, before / after the template: main 142.4 / 146.7 us, tiles 179.4 / 176.5 us.
+//
+// "basepass_MS_Main_depth ALPHA_MASK_MODE=1" and "basepass_MS_Main_visibility ALPHA_MASK_MODE=1": the permutation the reference
+// draws alpha-mask primitives with (BasePassRenderers.cpp:489, :690-691; its discard: basepass.hlsl:210-215), one more template
+// argument of the same two launches.  BINDINGS: those of the plain shader, plus t3 = the MaterialData buffer (required) and t19 =
+// the texture table (TRHIP_BIND_TEXTURE_TABLE, optional).  CONVENTION (parity unpinned, like the rest of the raster; restated in
+// tests/alpha_test_ref.c).  A covered sample of a triangle passes these steps after `d > 0` and before either atomic:
+//   1. q_i = e_i / w_i and s = (q0 + q1) + q2 from the sample's own edge values e_i and the vertices' clip w;
+//   2. uv = fma(q2, a2, fma(q1, a1, q0 * a0)) / s of m_TexCoord (half -> float, exact);
+//   3. ddx(uv), ddy(uv) from the same triangle's plane, re-evaluated at (cx + 1, cy) and at (cx, cy + 1), minus the centre value
+//      (steps 1 to 3: mesh::uvFootprint, the formulas of the TEXTURED resolve);
+//   4. alpha = m_ConstAlbedo.w, times mtex::sampleAlpha(...) with the albedo slot's m_IsWrapSampler if MaterialFlag_UseAlbedoTexture;
+//   5. the sample is discarded iff alpha < m_AlphaCutoff; a NaN alpha is kept, as `discard` under a false comparison keeps it;
+//   6. nothing of the triangle is drawn, like every broken chain here, when m_MaterialDataIdx is past the buffer, the albedo flag
+//      is set with no table bound, the descriptor index is past the table, or the entry is empty or of another format.
+// The surviving samples still feed a maximum, so the result stays independent of the draw order.  The material row and the table
+// entry are resolved once per meshlet in "main" (one instance, one material) and once per queued triangle in "tiles", never per
+// sample; a texture-free material is decided there for all its samples.  "main" keeps w and the packed m_TexCoord per vertex
+// beside sx, sy and sd in the wave's LDS slice; a queued triangle carries three w, three uv words and the material index in a
+// second scratch array beside queuePayload (AlphaTriangle, 32 bytes per entry), allocated by these instantiations only.
+// The four plain kernels keep their names and arithmetic, and the compiler reports the same resources for them as before the
+// template argument (VGPRs / SGPRs / LDS bytes / waves per SIMD, -Rpass-analysis=kernel-resource-usage): depth main 64 / 100 / 15360 /
+// 8, visibility main 68 / 103 / 15360 / 7, depth tiles 58 / 82 / 20500 / 7, visibility tiles 55 / 83 / 53272 / 3, no scratch: no
+// difference.  The new ones: depth main 141 / 106 / 25600 / 3, visibility main 144 / 106 / 25600 / 3, depth tiles 125 / 106 /
+// 20500 / 4, visibility tiles 127 / 106 / 53272 / 3, no scratch (profiles/alpha_test/README.md).
+// MEASURED (tools/alpha_test_cost.py, the generated city at 3840x2160 with 225 of 2251 instances alpha-masked and textured, the
+// alpha-mask list alone so that both sides draw the same lists, sides alternated three times on one MI355X): visibility main 304.4
+// us plain / 3433.3 us alpha-tested, tiles 268.4 / 2012.6 us.  Two thirds of it are the tap loop's bilinear fetches, run by the few lanes of a chunk that lie inside the triangle (attribution there).  Untuned: correctness came first.
+#include "material_textures.hip.h"
 #include "mesh_stage.hip.h"
 
 using namespace mesh;
@@ -105,11 +133,51 @@ struct VisArgs
     uint32_t slotBits;                                           // visSlotBits(passSlot)
 };
 
+// The alpha test's extra state (nullptr / 0 in the plain instantiations, where it is never read).
+struct AlphaTriangle                            // 32 bytes: what a queued triangle carries beside BigTriangle and queuePayload
+{
+    float w0, w1, w2;                           // clip w of the three vertices
+    uint32_t tc0, tc1, tc2;                     // m_TexCoord, half2
+    uint32_t material;                          // m_MaterialDataIdx of the triangle's instance
+    uint32_t pad;
+};
+
+struct AlphaArgs
+{
+    const char* materials; uint32_t numMaterials;                // t3: MaterialData, 124-byte stride
+    const mtex::TableEntry* table; uint32_t tableCount;          // t19, or nullptr / 0: no table bound
+    AlphaTriangle* queueAlpha;                                   // scratch: [kQueueCapacity]
+};
+
+// What the test needs of one triangle's material, resolved once per meshlet ("main") or per queued triangle ("tiles"), never
+// per sample.  draw == false: a broken chain, or a texture-free material whose constant alpha fails the test -- no sample of
+// the triangle is drawn.
+struct AlphaMaterial { bool draw; bool wrap; const mtex::TableEntry* tex; float alpha, cutoff; };
+
+__device__ __forceinline__ AlphaMaterial alphaMaterial(const AlphaArgs& aa, uint32_t materialIdx)
+{
+    AlphaMaterial m = { false, false, nullptr, 0.0f, 0.0f };
+    if (materialIdx >= aa.numMaterials) return m;
+    const MaterialData& md = *reinterpret_cast<const MaterialData*>(aa.materials + (uint64_t)materialIdx * sizeof(MaterialData));
+    m.alpha = md.m_ConstAlbedo.w; m.cutoff = md.m_AlphaCutoff;
+    if (md.m_MaterialFlags & MaterialFlag_UseAlbedoTexture) {
+        const uint32_t d = md.m_AlbedoTexture.m_DescriptorIndex;
+        if (d >= aa.tableCount || !mtex::sampled(aa.table[d])) return m;                  // no table, past it, empty, another format
+        m.tex = aa.table + d;
+        m.wrap = md.m_AlbedoTexture.m_IsWrapSampler != 0u;
+        m.draw = true;
+    } else {
+        m.draw = !(m.alpha < m.cutoff);                                                   // a NaN is kept
+    }
+    return m;
+}
+
 // One triangle over the pixels [bx0, bx1] x [by0, by1], `threads` lanes striding over them from `first`; every covered
-// pixel goes to `sink(px, py, depthBits)`.  The arithmetic of orc_raster_depth, operation for operation.
-template <typename Sink>
+// pixel that `keep(cx, cy, e0, e1, e2)` does not discard goes to `sink(px, py, depthBits)`.  The arithmetic of
+// orc_raster_depth, operation for operation; keep is constant true in the plain instantiations.
+template <typename Keep, typename Sink>
 __device__ __forceinline__ void coverBox(float x0, float y0, float d0, float x1, float y1, float d1, float x2, float y2, float d2, float sgn,
-                                         uint32_t bx0, uint32_t by0, uint32_t bw, uint32_t bh, uint32_t first, uint32_t threads, Sink sink)
+                                         uint32_t bx0, uint32_t by0, uint32_t bw, uint32_t bh, uint32_t first, uint32_t threads, Keep keep, Sink sink)
 {
     const uint64_t total = (uint64_t)bw * bh;
     for (uint64_t i = first; i < total; i += threads) {
@@ -121,17 +189,30 @@ __device__ __forceinline__ void coverBox(float x0, float y0, float d0, float x1,
         const float den = (e0 + e1) + e2;
         if (!(den > 0.0f)) continue;
         const float d = cm::fma_(e2, d2, cm::fma_(e1, d1, e0 * d0)) / den;
-        if (d > 0.0f) sink(px, py, __float_as_uint(d));                                   // GREATER test; NaN never passes
+        if (d > 0.0f && keep(cx, cy, e0, e1, e2)) sink(px, py, __float_as_uint(d));       // GREATER test; NaN never passes
     }
 }
 
-template <bool Vis>
-__device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& va)
+// ALPHA_MASK_MODE's discard at one covered sample of triangle (q, t) with material m (m.draw): see the header's CONVENTION.
+__device__ __forceinline__ bool alphaKeeps(const BigTriangle& q, const AlphaTriangle& t, const AlphaMaterial& m, float cx, float cy, float e0, float e1, float e2)
+{
+    if (!m.tex) return true;                                                              // constant alpha: decided with the material
+    const UvFootprint f = uvFootprint(q.x0, q.y0, q.x1, q.y1, q.x2, q.y2, q.sgn, t.w0, t.w1, t.w2, t.tc0, t.tc1, t.tc2, cx, cy, e0, e1, e2);
+    const float alpha = m.alpha * mtex::sampleAlpha(*m.tex, m.wrap, f.u, f.v, f.dudx, f.dvdx, f.dudy, f.dvdy);
+    return !(alpha < m.cutoff);                                                           // discard iff alpha < cutoff: a NaN is kept
+}
+
+template <bool Vis, bool Alpha>
+__device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& va, const AlphaArgs& aa)
 {
     __shared__ float s_x[kWaves][64], s_y[kWaves][64], s_d[kWaves][64];
     __shared__ BigTriangle s_tri[kWaves][64];
+    __shared__ float s_w[Alpha ? kWaves : 1][64];                                        // alpha test only: clip w and m_TexCoord per vertex,
+    __shared__ uint32_t s_tc[Alpha ? kWaves : 1][64];
+    __shared__ AlphaTriangle s_atri[Alpha ? kWaves : 1][64];                             // and per triangle drawn in place
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     float* sx = s_x[wave]; float* sy = s_y[wave]; float* sd = s_d[wave];
+    float* sw = s_w[Alpha ? wave : 0]; uint32_t* stc = s_tc[Alpha ? wave : 0];
     uint32_t V = a.drawArgs[0];
     V = V < a.listCapacity ? V : a.listCapacity;
     const uint32_t W = a.width, H = a.height;
@@ -140,6 +221,11 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
     for (uint32_t v = blockIdx.x * kWaves + wave; v < V; v += gridDim.x * kWaves) {
         withMeshlet(a.visibleList[v], a.records, a.recordCapacity, a.geo, [&](const Meshlet& ml) {   // the rest of the iteration, not indented
         const uint32_t nv = ml.nv, nt = ml.nt;
+        AlphaMaterial am = {};
+        if constexpr (Alpha) {
+            am = alphaMaterial(aa, ml.inst->m_MaterialDataIdx);                           // the whole meshlet's: one instance, one material
+            if (!am.draw) return;                                                        // wave-uniform, before the LDS slice is touched
+        }
         const cm::M43 Wm = cm::loadM43(ml.inst->m_WorldMatrix);
         // ---- vertices (:149-158): lane l transforms vertex l ------------------------------------------------
         bool ok = false;
@@ -150,6 +236,7 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
                 const ScreenVertex s = toScreen({ p[0], p[1], p[2] }, Wm, clipXYZ, a.k.m_WorldToClip, halfW, halfH);
                 ok = s.w > a.k.m_NearPlane;
                 sx[lane] = s.sx; sy[lane] = s.sy; sd[lane] = s.depth;
+                if constexpr (Alpha) { sw[lane] = s.w; stc[lane] = *reinterpret_cast<const uint32_t*>(vertexAt(a.geo, vid).m_TexCoord); }
             }
         }
         const unsigned long long okMask = __ballot(ok);
@@ -164,6 +251,7 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
             const uint32_t t = tb + lane;
             bool live = false;
             BigTriangle q = {};
+            AlphaTriangle qa = {};
             uint32_t bw = 0, bh = 0;
             if (t < nt) {
                 const uint32_t packed = a.geo.triangles[ml.trianglesAt + t];
@@ -171,6 +259,7 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
                 if (ia < nv && ib < nv && ic < nv && ((okMask >> ia) & (okMask >> ib) & (okMask >> ic) & 1ull)) {
                     q.x0 = sx[ia]; q.y0 = sy[ia]; q.x1 = sx[ib]; q.y1 = sy[ib]; q.x2 = sx[ic]; q.y2 = sy[ic];
                     q.d0 = sd[ia]; q.d1 = sd[ib]; q.d2 = sd[ic];
+                    if constexpr (Alpha) qa = { sw[ia], sw[ib], sw[ic], stc[ia], stc[ib], stc[ic], ml.inst->m_MaterialDataIdx, 0u };
                     const float area = edgeFn(q.x0, q.y0, q.x1, q.y1, q.x2, q.y2);
                     const float fminx = cm::min_(cm::min_(q.x0, q.x1), q.x2), fmaxx = cm::max_(cm::max_(q.x0, q.x1), q.x2);
                     const float fminy = cm::min_(cm::min_(q.y0, q.y1), q.y2), fmaxy = cm::max_(cm::max_(q.y0, q.y1), q.y2);
@@ -198,6 +287,7 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
                 if (big && slot < kQueueCapacity) {
                     a.queue[slot] = q;
                     if constexpr (Vis) va.queuePayload[slot] = t < kVisTriangles ? (1ull << 32) | packVisibility(va.slotBits, v, t) : 0ull;
+                    if constexpr (Alpha) aa.queueAlpha[slot] = qa;
                     // its index goes to every coarse bin the box touches
                     const uint32_t cx0 = (q.boxX & 0xFFFFu) >> kBinShift, cx1 = (q.boxX >> 16) >> kBinShift;
                     const uint32_t cy0 = (q.boxY & 0xFFFFu) >> kBinShift, cy1 = (q.boxY >> 16) >> kBinShift;
@@ -215,18 +305,22 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
             const unsigned long long smallMask = __ballot(live && !big);
             if (smallMask) {
                 st[lane] = q;
+                if constexpr (Alpha) s_atri[wave][lane] = qa;
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 uint32_t* depth = a.depth;
                 for (unsigned long long mrem = smallMask; mrem; mrem &= mrem - 1ull) {
                     const BigTriangle c = st[__builtin_ctzll(mrem)];
+                    AlphaTriangle ca = {};
+                    if constexpr (Alpha) ca = s_atri[wave][__builtin_ctzll(mrem)];
                     const uint32_t bx0 = c.boxX & 0xFFFFu, by0 = c.boxY & 0xFFFFu;
                     const uint32_t tri = tb + (uint32_t)__builtin_ctzll(mrem);
                     const bool texel = tri < kVisTriangles;
                     const unsigned long long payload = packVisibility(va.slotBits, v, tri);
                     unsigned long long* vis = va.vis;
                     coverBox(c.x0, c.y0, c.d0, c.x1, c.y1, c.d1, c.x2, c.y2, c.d2, c.sgn, bx0, by0, (c.boxX >> 16) - bx0 + 1u, (c.boxY >> 16) - by0 + 1u, lane, 64u,
+                             [&](float cx, float cy, float e0, float e1, float e2) { if constexpr (Alpha) return alphaKeeps(c, ca, am, cx, cy, e0, e1, e2); else return true; },
                              [=](uint32_t px, uint32_t py, uint32_t bits) {
                                  const uint64_t i = (uint64_t)py * W + px;
                                  atomicMax(&depth[i], bits);
@@ -244,15 +338,17 @@ __device__ __forceinline__ void rasterMain(const RasterArgs& a, const VisArgs& v
     }
 }
 
-__global__ __launch_bounds__(kBlock) void rasterDepthKernel(RasterArgs a) { rasterMain<false>(a, VisArgs{}); }
-__global__ __launch_bounds__(kBlock) void rasterVisibilityKernel(RasterArgs a, VisArgs va) { rasterMain<true>(a, va); }
+__global__ __launch_bounds__(kBlock) void rasterDepthKernel(RasterArgs a) { rasterMain<false, false>(a, VisArgs{}, AlphaArgs{}); }
+__global__ __launch_bounds__(kBlock) void rasterVisibilityKernel(RasterArgs a, VisArgs va) { rasterMain<true, false>(a, va, AlphaArgs{}); }
+__global__ __launch_bounds__(kBlock) void rasterDepthAlphaKernel(RasterArgs a, AlphaArgs aa) { rasterMain<false, true>(a, VisArgs{}, aa); }
+__global__ __launch_bounds__(kBlock) void rasterVisibilityAlphaKernel(RasterArgs a, VisArgs va, AlphaArgs aa) { rasterMain<true, true>(a, va, aa); }
 
 
 // The queued triangles, by screen tile.  Rounds of at most kTileList triangles: collect (all threads scan the queue,
 // LDS append), rasterise into the LDS tile, next round; then merge.  A tile is owned by one workgroup and this launch
 // follows "main" on the stream, so the merge needs no atomics.
-template <bool Vis>
-__device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& va)
+template <bool Vis, bool Alpha>
+__device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& va, const AlphaArgs& aa)
 {
     __shared__ uint32_t s_depth[kTile * kTile];
     __shared__ uint32_t s_list[kTileList];
@@ -304,6 +400,8 @@ __device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& 
             for (uint32_t k = 0; k < m; ++k) {
                 // Every 32 triangles: the farthest depth the tile holds so far.  A triangle none of whose samples can be
                 // nearer than that cannot change a maximum and is skipped: see kSkipMinDepth for the bound on its samples.
+                // With the alpha test the bound holds as it is: a discard only removes samples from both sides of the
+                // comparison's right hand (the skipped triangle's) and leaves holes at depth 0 on its left (tileFar = 0).
                 if ((k & 31u) == 0u && (k != 0u || any)) {
                     uint32_t mn = 0xFFFFFFFFu;
                     const uint32_t w = tx1 - tx0 + 1u, h = ty1 - ty0 + 1u;
@@ -330,7 +428,15 @@ __device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& 
                 if constexpr (Vis) qp = va.queuePayload[s_list[k]];
                 const bool texel = (qp >> 32) != 0ull;
                 const unsigned long long payload = qp & 0xFFFFFFFFull;
+                AlphaTriangle qa = {};
+                AlphaMaterial am = {};
+                if constexpr (Alpha) {
+                    qa = aa.queueAlpha[s_list[k]];
+                    am = alphaMaterial(aa, qa.material);
+                    if (!am.draw) continue;                                               // uniform over the workgroup; no barrier below in this iteration
+                }
                 coverBox(q.x0, q.y0, q.d0, q.x1, q.y1, q.d1, q.x2, q.y2, q.d2, q.sgn, bx0, by0, bx1 - bx0 + 1u, by1 - by0 + 1u, tid, kBlock,
+                         [&](float cx, float cy, float e0, float e1, float e2) { if constexpr (Alpha) return alphaKeeps(q, qa, am, cx, cy, e0, e1, e2); else return true; },
                          [=](uint32_t px, uint32_t py, uint32_t bits) {
                              const uint32_t i = (py - ty0) * kTile + (px - tx0);
                              atomicMax(&s_depth[i], bits);
@@ -354,10 +460,12 @@ __device__ __forceinline__ void rasterTiles(const RasterArgs& a, const VisArgs& 
     }
 }
 
-__global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a) { rasterTiles<false>(a, VisArgs{}); }
-__global__ __launch_bounds__(kBlock) void rasterVisibilityTilesKernel(RasterArgs a, VisArgs va) { rasterTiles<true>(a, va); }
+__global__ __launch_bounds__(kBlock) void rasterTilesKernel(RasterArgs a) { rasterTiles<false, false>(a, VisArgs{}, AlphaArgs{}); }
+__global__ __launch_bounds__(kBlock) void rasterVisibilityTilesKernel(RasterArgs a, VisArgs va) { rasterTiles<true, false>(a, va, AlphaArgs{}); }
+__global__ __launch_bounds__(kBlock) void rasterTilesAlphaKernel(RasterArgs a, AlphaArgs aa) { rasterTiles<false, true>(a, VisArgs{}, aa); }
+__global__ __launch_bounds__(kBlock) void rasterVisibilityTilesAlphaKernel(RasterArgs a, VisArgs va, AlphaArgs aa) { rasterTiles<true, true>(a, va, aa); }
 
-template <bool Vis>
+template <bool Vis, bool Alpha>
 int recordRaster(trhip::DispatchCtx& ctx)
 {
     // Binding set of BasePassRenderers.cpp:463-479 (the geometry of mesh_stage.hip.h, t7 amplification records) + the
@@ -411,6 +519,26 @@ int recordRaster(trhip::DispatchCtx& ctx)
         va.queuePayload = (unsigned long long*)ctx.scratch((size_t)kQueueCapacity * 8);
         TRHIP_REQUIRE(va.queuePayload, "%s: scratch allocation failed", ctx.shaderName);
     }
+    AlphaArgs aa = {};
+    if constexpr (Alpha) {
+        // + t3 = the MaterialData buffer (required), t19 = the texture table (optional: without it a material with
+        // MaterialFlag_UseAlbedoTexture draws nothing)
+        trhip_buffer_t* materials = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 3);
+        TRHIP_REQUIRE(materials, "%s: needs SRV t3 = the MaterialData buffer (124-byte stride): the alpha test reads m_ConstAlbedo.w, m_AlphaCutoff and the albedo texture",
+                      ctx.shaderName);
+        aa.materials = (const char*)materials->ptr;
+        aa.numMaterials = elements32(materials, sizeof(MaterialData));
+        if (trhip_texture_table_t* table = ctx.textureTable(19)) {
+            for (size_t d = 0; d < table->slots.size(); ++d)
+                TRHIP_REQUIRE(!table->slots[d] || !table->slots[d]->isUAV, "%s: the texture table at t19 holds '%s' at index %zu, created with the UAV or render-target bit: a sampled texture is read only",
+                              ctx.shaderName, table->slots[d]->name.c_str(), d);
+            TRHIP_REQUIRE(table->entries.ptr, "%s: the texture table at t19 has no device data", ctx.shaderName);
+            aa.table = (const mtex::TableEntry*)table->entries.ptr;
+            aa.tableCount = (uint32_t)table->slots.size();
+        }
+        aa.queueAlpha = (AlphaTriangle*)ctx.scratch((size_t)kQueueCapacity * sizeof(AlphaTriangle));
+        TRHIP_REQUIRE(aa.queueAlpha, "%s: scratch allocation failed", ctx.shaderName);
+    }
     a.binsX = (a.width + (1u << kBinShift) - 1u) >> kBinShift;
     a.binsY = (a.height + (1u << kBinShift) - 1u) >> kBinShift;
     const uint32_t bins = a.binsX * a.binsY;
@@ -423,7 +551,21 @@ int recordRaster(trhip::DispatchCtx& ctx)
     const uint32_t grid = ctx.computeUnits() * 4u;
     const uint32_t tiles = ((a.width + kTile - 1) / kTile) * ((a.height + kTile - 1) / kTile);
     const uint32_t tileGrid = tiles < ctx.computeUnits() * 8u ? tiles : ctx.computeUnits() * 8u;
-    if constexpr (Vis) {
+    if constexpr (Vis && Alpha) {
+        ctx.emit("main", [a, va, aa, grid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterVisibilityAlphaKernel, dim3(grid), dim3(kBlock), 0, s, a, va, aa);
+            return trhip::launchStatus("rasterVisibilityAlphaKernel"); });
+        ctx.emit("tiles", [a, va, aa, tileGrid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterVisibilityTilesAlphaKernel, dim3(tileGrid), dim3(kBlock), 0, s, a, va, aa);
+            return trhip::launchStatus("rasterVisibilityTilesAlphaKernel"); });
+    } else if constexpr (Alpha) {
+        ctx.emit("main", [a, aa, grid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterDepthAlphaKernel, dim3(grid), dim3(kBlock), 0, s, a, aa);
+            return trhip::launchStatus("rasterDepthAlphaKernel"); });
+        ctx.emit("tiles", [a, aa, tileGrid](hipStream_t s) {
+            TRHIP_LAUNCH(rasterTilesAlphaKernel, dim3(tileGrid), dim3(kBlock), 0, s, a, aa);
+            return trhip::launchStatus("rasterTilesAlphaKernel"); });
+    } else if constexpr (Vis) {
         ctx.emit("main", [a, va, grid](hipStream_t s) {
             TRHIP_LAUNCH(rasterVisibilityKernel, dim3(grid), dim3(kBlock), 0, s, a, va);
             return trhip::launchStatus("rasterVisibilityKernel"); });
@@ -441,7 +583,9 @@ int recordRaster(trhip::DispatchCtx& ctx)
     return TRHIP_OK;
 }
 
-trhip::ShaderRegistrar r0("basepass_MS_Main_depth", recordRaster<false>, 0);
-trhip::ShaderRegistrar r1("basepass_MS_Main_visibility", recordRaster<true>, 0);
+trhip::ShaderRegistrar r0("basepass_MS_Main_depth", recordRaster<false, false>, 0);
+trhip::ShaderRegistrar r1("basepass_MS_Main_visibility", recordRaster<true, false>, 0);
+trhip::ShaderRegistrar r2("basepass_MS_Main_depth ALPHA_MASK_MODE=1", recordRaster<false, true>, 0);
+trhip::ShaderRegistrar r3("basepass_MS_Main_visibility ALPHA_MASK_MODE=1", recordRaster<true, true>, 0);
 
 } // namespace

@@ -7,8 +7,8 @@
 //
 // BINDINGS of the trace: b0 ShadowMaskConsts (112 bytes), t0 R32_FLOAT depth, t1 the TLAS nodes, t2 GBufferA, t3 instances, t4
 // vertices, t5 materials, t6 indices, t7 mesh data, t8 RGBA8_UNORM 128 x 128 blue noise, u0 R8_UNORM mask, u1 R16_FLOAT linear view
-// depth; the structure's other buffers: t9 TLAS instances, t10 BLAS headers, t11 BLAS nodes, t12 triangle order.  Samplers are
-// accepted and ignored.  Of the refit: push constants RefitTLASConstants (12 bytes), t0 instances, t1 BLAS headers, t2 BLAS nodes,
+// depth; the structure's other buffers: t9 TLAS instances, t10 BLAS headers, t11 BLAS nodes, t12 triangle order; t19 the texture table (optional: see
+// `alpha` below).  Samplers are accepted and ignored.  Of the refit: push constants RefitTLASConstants (12 bytes), t0 instances, t1 BLAS headers, t2 BLAS nodes,
 // t3 level offsets, t4 level nodes, u0 the TLAS nodes, u1 the TLAS instances.
 //
 // CONVENTION (tests/shadowmask_ref.c is the definition; the functions below repeat its functions word for word).  IEEE binary32,
@@ -23,6 +23,10 @@
 //   triHit:   the watertight test of Woop, Benthin and Wald in binary32 without the double fallback; two-sided; hit iff
 //             TMin < t < TMax.  A candidate on a ForceNonOpaque instance counts iff m_ConstAlbedo.w >= m_AlphaCutoff of the
 //             candidate's instance's material (the reference reads Committed* there: shadowmask.hlsl:113-116);
+//   alpha:    without a table at t19 that is the whole rule and the kernel of before is launched unchanged.  With one, the TEXTURED
+//             instantiation ("#textured" in the profile): a candidate whose material has MaterialFlag_UseAlbedoTexture counts iff
+//             m_ConstAlbedo.w * alphaLevel0(uv) >= m_AlphaCutoff (tests/alpha_test_ref.c; see commits()).  Any-hit over independent
+//             per-candidate tests stays order-independent, so "equals brute force over every triangle" still holds;
 //   boxHit:   conservative: per axis a direction component without a finite reciprocal asks lo <= origin <= hi only (the default
 //             light (0, -1, 0) makes every ray axis-parallel, Cornell's walls are boxes of no thickness: no inf * 0 here); else
 //             the slab's interval with both ends moved outward by 2^-18 of themselves; node boxes are padded by the builder (2^-16
@@ -39,11 +43,16 @@
 // an indexed array.  Every index read on the device is checked against its buffer before it is followed.  A wave walks until its
 // last lane is done, and lanes that disagree on a box serialise both sides.  MEASURED (tools/shadowmask_cost.py, the generated city
 // of 2251 instances at 3840x2160, one MI355X; profiles/shadowmask/): the trace 1.92 ms with hard and 3.86 ms with soft shadows next to
-// a lighting pass of 0.10 ms, the refit 35 us.  Untuned: correctness came first.
+// a lighting pass of 0.10 ms, the refit 35 us.  Untuned: correctness came first.  The TEXTURED instantiation (tools/alpha_test_cost.py,
+// the same city with 225 alpha-masked, textured instances; profiles/alpha_test/): 2.48 ms beside 1.94 ms hard, 5.13 beside 3.90 ms soft;
+// 78 VGPRs instead of 57, no scratch.
 #include "cull_math.hip.h"
 #include "gbuffer_unpack.hip.h"
+#include "material_textures.hip.h"
 #include "screen_pass.hip.h"
 #include "soft_math.hip.h"
+
+#include <type_traits>
 
 namespace
 {
@@ -73,6 +82,12 @@ struct TraceArgs
     const trhip_blas_header* headers;
     const trhip_accel_node* blasNodes; uint32_t numBlasNodes;
     const uint32_t* triOrder; uint32_t numTriOrder;
+};
+
+// The TEXTURED instantiation's arguments: + the texture table bound at t19.
+struct TexturedTraceArgs : TraceArgs
+{
+    const mtex::TableEntry* table; uint32_t tableCount;
 };
 
 __device__ __forceinline__ float sel(F3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
@@ -246,7 +261,8 @@ __device__ __forceinline__ bool boxHit(const trhip_accel_node& n, const Ray& r)
     return tenter <= texit;
 }
 
-__device__ __forceinline__ bool triHit(F3 v0, F3 v1, F3 v2, const Ray& r, float tmin, float tmax)
+// b1, b2 (TEXTURED only): the edge values of the second and third vertex over det, InterpolateVertex's barycentrics
+__device__ __forceinline__ bool triHit(F3 v0, F3 v1, F3 v2, const Ray& r, float tmin, float tmax, float* b1 = nullptr, float* b2 = nullptr)
 {
     const F3 A = { v0.x - r.o.x, v0.y - r.o.y, v0.z - r.o.z }, B = { v1.x - r.o.x, v1.y - r.o.y, v1.z - r.o.z }, C = { v2.x - r.o.x, v2.y - r.o.y, v2.z - r.o.z };
     const float Akz = sel(A, r.kz), Bkz = sel(B, r.kz), Ckz = sel(C, r.kz);
@@ -260,6 +276,7 @@ __device__ __forceinline__ bool triHit(F3 v0, F3 v1, F3 v2, const Ray& r, float 
     const float Az = r.Sz * Akz, Bz = r.Sz * Bkz, Cz = r.Sz * Ckz;
     const float T = (U * Az + V * Bz) + W * Cz;
     const float t = cm::div_(T, det);
+    if (b1) { *b1 = cm::div_(V, det); *b2 = cm::div_(W, det); }
     return t > tmin && t < tmax;
 }
 
@@ -285,17 +302,37 @@ __device__ __forceinline__ F3 vertexOf(const TraceArgs& a, uint64_t i)
     return { p[0], p[1], p[2] };
 }
 
-// the candidate counts: ForceOpaque always, ForceNonOpaque by the alpha test of its instance's material (GetCommonGBufferParams without textures)
-__device__ __forceinline__ bool commits(const TraceArgs& a, uint32_t inst, uint32_t flags)
+// A candidate: the triangle's texture coordinates (packed half2) and the hit's barycentrics.  TEXTURED only.
+struct Candidate { uint32_t tc[3]; float b1, b2; };
+
+// the candidate counts: ForceOpaque always, ForceNonOpaque by the alpha test of its instance's material (GetCommonGBufferParams
+// without textures).  TEXTURED (tests/alpha_test_ref.c: at_commits): a material with MaterialFlag_UseAlbedoTexture counts iff
+// m_ConstAlbedo.w * alphaLevel0(uv) >= m_AlphaCutoff, uv as InterpolateVertex (raytracingcommon.hlsli:24-36, :189) has it:
+// b0 = (1.0f - b1) - b2, uv = ((0 + uv0 * b0) + uv1 * b1) + uv2 * b2, not fused.  DEVIATION: the reference calls Sample in a
+// compute shader, where the derivatives come from unrelated neighbouring rays; this build reads mip 0.  A descriptor index past
+// the table, an empty entry or one of another format: the candidate does not count.
+template <bool TEXTURED, typename Args>
+__device__ __forceinline__ bool commits(const Args& a, uint32_t inst, uint32_t flags, const Candidate& c)
 {
     if (flags != kTLASInstanceForceNonOpaque) return true;
     const uint32_t mat = a.instances[inst].m_MaterialDataIdx;
     if (mat >= a.numMaterials) return false;
     const MaterialData* m = reinterpret_cast<const MaterialData*>(a.materials + (uint64_t)mat * sizeof(MaterialData));
+    if constexpr (TEXTURED) {
+        if (m->m_MaterialFlags & MaterialFlag_UseAlbedoTexture) {
+            const uint32_t d = m->m_AlbedoTexture.m_DescriptorIndex;
+            if (d >= a.tableCount || !mtex::sampled(a.table[d])) return false;
+            const float b0 = (1.0f - c.b1) - c.b2;
+            const float u = ((0.0f + (float)sp::halfOf(c.tc[0]) * b0) + (float)sp::halfOf(c.tc[1]) * c.b1) + (float)sp::halfOf(c.tc[2]) * c.b2;
+            const float v = ((0.0f + (float)sp::halfOf(c.tc[0] >> 16) * b0) + (float)sp::halfOf(c.tc[1] >> 16) * c.b1) + (float)sp::halfOf(c.tc[2] >> 16) * c.b2;
+            return m->m_ConstAlbedo.w * mtex::alphaLevel0(a.table[d], m->m_AlbedoTexture.m_IsWrapSampler != 0u, u, v) >= m->m_AlphaCutoff;
+        }
+    }
     return m->m_ConstAlbedo.w >= m->m_AlphaCutoff;
 }
 
-__device__ __forceinline__ bool meshTriHit(const TraceArgs& a, const MeshData* md, uint32_t tri, const Ray& r, float tmin, float tmax)
+template <bool TEXTURED>
+__device__ __forceinline__ bool meshTriHit(const TraceArgs& a, const MeshData* md, uint32_t tri, const Ray& r, float tmin, float tmax, Candidate& c)
 {
     const uint64_t base = (uint64_t)md->m_GlobalIndexBufferIdx + 3ull * tri;
     if (base + 3u > a.numIndices) return false;
@@ -305,11 +342,14 @@ __device__ __forceinline__ bool meshTriHit(const TraceArgs& a, const MeshData* m
         const uint64_t vi = (uint64_t)md->m_GlobalVertexBufferIdx + a.indices[base + k];
         if (vi >= a.numVertices) return false;
         v[k] = vertexOf(a, vi);
+        if constexpr (TEXTURED) c.tc[k] = *reinterpret_cast<const uint32_t*>(a.vertices + vi * sizeof(RawVertexFormat) + offsetof(RawVertexFormat, m_TexCoord));
     }
-    return triHit(v[0], v[1], v[2], r, tmin, tmax);
+    if constexpr (TEXTURED) return triHit(v[0], v[1], v[2], r, tmin, tmax, &c.b1, &c.b2);
+    else return triHit(v[0], v[1], v[2], r, tmin, tmax);
 }
 
-__device__ bool occluded(const TraceArgs& a, F3 o, F3 d, float tmin, float tmax)                    // tests/shadowmask_ref.c: occluded_walk
+template <bool TEXTURED, typename Args>
+__device__ bool occluded(const Args& a, F3 o, F3 d, float tmin, float tmax)                         // tests/shadowmask_ref.c: occluded_walk
 {
     const Ray wr = makeRay(o, d);
     uint32_t node = 0;
@@ -339,7 +379,8 @@ __device__ bool occluded(const TraceArgs& a, F3 o, F3 d, float tmin, float tmax)
                                 for (uint32_t j = 0; j < cnt; ++j) {
                                     const uint64_t slot = (uint64_t)hd.tri_offset + first + j;
                                     if (first + j >= hd.num_tris || slot >= a.numTriOrder) break;
-                                    if (meshTriHit(a, md, a.triOrder[slot], r, tmin, tmax) && commits(a, inst, flags)) return true;
+                                    Candidate c;
+                                    if (meshTriHit<TEXTURED>(a, md, a.triOrder[slot], r, tmin, tmax, c) && commits<TEXTURED>(a, inst, flags, c)) return true;
                                 }
                             }
                         }
@@ -353,7 +394,9 @@ __device__ bool occluded(const TraceArgs& a, F3 o, F3 d, float tmin, float tmax)
     return false;
 }
 
-__global__ __launch_bounds__(kTileSide * kTileSide) void shadowMaskKernel(TraceArgs a)
+// TEXTURED: a texture table is bound at t19 and alpha-mask candidates read their albedo texture's alpha (commits).
+template <bool TEXTURED>
+__global__ __launch_bounds__(kTileSide * kTileSide) void shadowMaskKernel(std::conditional_t<TEXTURED, TexturedTraceArgs, TraceArgs> a)
 {
     const ShadowMaskConsts& k = a.k;
     const uint32_t W = k.m_OutputResolution.x, H = k.m_OutputResolution.y;
@@ -378,7 +421,7 @@ __global__ __launch_bounds__(kTileSide * kTileSide) void shadowMaskKernel(TraceA
     const F3 light = { k.m_DirectionalLightDirection[0], k.m_DirectionalLightDirection[1], k.m_DirectionalLightDirection[2] };
     const F3 d = gbuf::normalize_(mapToCone(sx, sy, light, k.m_TanSunAngularRadius));
     const F3 o = { wp.x + n.x * k.m_RayStartOffset, wp.y + n.y * k.m_RayStartOffset, wp.z + n.z * k.m_RayStartOffset };
-    const bool occ = occluded(a, o, d, k.m_RayStartOffset, 1e10f);
+    const bool occ = occluded<TEXTURED>(a, o, d, k.m_RayStartOffset, 1e10f);
     a.mask[i] = occ ? 0u : 255u;
     const F3 toCamera = { wp.x - k.m_CameraPosition[0], wp.y - k.m_CameraPosition[1], wp.z - k.m_CameraPosition[2] };
     const float len = cm::sqrt_(cm::dot3(toCamera, toCamera));
@@ -416,7 +459,7 @@ int recordShadowMask(trhip::DispatchCtx& ctx)
         const uint64_t c = buf[j]->byteSize / wantBuf[j].stride;
         count[j] = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
     }
-    TraceArgs a = sp::zeroed<TraceArgs>();
+    TexturedTraceArgs a = sp::zeroed<TexturedTraceArgs>();                                          // TraceArgs + the table; sliced when none is bound
     a.k = *k;
     a.depth = (const float*)tex[0]->ptr; a.gbufferA = (const uint4*)tex[1]->ptr; a.mask = (uint8_t*)tex[2]->ptr; a.lvd = (uint16_t*)tex[3]->ptr;
     a.noise = (const uint32_t*)noise[0]->ptr;
@@ -430,7 +473,18 @@ int recordShadowMask(trhip::DispatchCtx& ctx)
     a.headers = (const trhip_blas_header*)buf[7]->ptr;
     a.blasNodes = (const trhip_accel_node*)buf[8]->ptr; a.numBlasNodes = count[8];
     a.triOrder = (const uint32_t*)buf[9]->ptr; a.numTriOrder = count[9];
-    sp::launch(ctx, shadowMaskKernel, "shadowMaskKernel", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), a);
+    if (trhip_texture_table_t* table = ctx.textureTable(19)) {                                      // t19: the TEXTURED instantiation
+        for (size_t d = 0; d < table->slots.size(); ++d)
+            TRHIP_REQUIRE(!table->slots[d] || !table->slots[d]->isUAV, "%s: the texture table at t19 holds '%s' at index %zu, created with the UAV or render-target bit: a sampled texture is read only",
+                          name, table->slots[d]->name.c_str(), d);
+        TRHIP_REQUIRE(table->entries.ptr, "%s: the texture table at t19 has no device data", name);
+        a.table = (const mtex::TableEntry*)table->entries.ptr;
+        a.tableCount = (uint32_t)table->slots.size();
+        sp::launch(ctx, shadowMaskKernel<true>, "shadowMaskKernel<textured>", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), a, "textured");
+        return TRHIP_OK;
+    }
+    const TraceArgs plain = a;
+    sp::launch(ctx, shadowMaskKernel<false>, "shadowMaskKernel", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), plain);
     return TRHIP_OK;
 }
 

@@ -23,6 +23,12 @@
 //               before filtering, as D3D does; alpha stays linear (and is never read: GBufferA stores no alpha).
 // Both tables (sRGB, and byte / 255.0f) are staged in LDS by the workgroup: a texel costs one global load and three LDS reads.
 // Parity with D3D hardware's fixed-point, vendor-specific anisotropic filtering stays unpinned.
+//
+// ALPHA (sampleAlpha, alphaLevel0; restated in tests/alpha_test_ref.c): SampleMaterialValue(...).a for ALPHA_MASK_MODE's discard in
+// the rasters (k_raster.hip) and the alpha test of the sun rays (k_shadowmask.hip).  sampleAlpha is `sample` on bits 24-31 of the
+// texel: the same footprint, tap count, lod, tap positions, trilinear and bilinear arithmetic, addressing and summation order.  A
+// texel is (float)byte / 255.0f, one correctly rounded division, in both formats: alpha is linear in SRGBA8_UNORM too and never goes
+// through the sRGB table, so neither function needs the LDS tables.  alphaLevel0 is one bilinear fetch of mip 0.
 #pragma once
 
 #include "../../include/trhip.h"
@@ -114,5 +120,45 @@ __device__ __forceinline__ cm::F3 sample(const TableEntry& e, const float* lds, 
     }
     return { acc.x / fN, acc.y / fN, acc.z / fN };
 }
+
+// ---- the alpha channel (see ALPHA above) --------------------------------------------------------------------------------------
+__device__ __forceinline__ float alphaOf(uint32_t texel) { return cm::div_((float)(texel >> 24), 255.0f); }
+
+__device__ __forceinline__ float bilinearAlpha(const TableEntry& e, uint32_t level, bool wrap, float u, float v)
+{
+    const uint32_t w = (e.width >> level) ? (e.width >> level) : 1u, h = (e.height >> level) ? (e.height >> level) : 1u;
+    const Axis x = axisOf(u, w, wrap), y = axisOf(v, h, wrap);
+    const uint32_t* p = e.base + e.mipOffset[level];
+    const uint32_t w00 = p[y.i0 * w + x.i0], w10 = p[y.i0 * w + x.i1], w01 = p[y.i1 * w + x.i0], w11 = p[y.i1 * w + x.i1];
+    return lerp_(lerp_(alphaOf(w00), alphaOf(w10), x.f), lerp_(alphaOf(w01), alphaOf(w11), x.f), y.f);
+}
+
+// SampleMaterialValue(...).a.  e: sampled(e).  The lines of `sample` up to the loop, repeated: `sample` itself stays as it is.
+__device__ __forceinline__ float sampleAlpha(const TableEntry& e, bool wrap, float u, float v, float dudx, float dvdx, float dudy, float dvdy)
+{
+    const float W = (float)e.width, H = (float)e.height;
+    const float ax = dudx * W, ay = dvdx * H, bx = dudy * W, by = dvdy * H;
+    const float lenA = cm::sqrt_(cm::fma_(ay, ay, ax * ax)), lenB = cm::sqrt_(cm::fma_(by, by, bx * bx));
+    const bool aMajor = lenA >= lenB;
+    const float pmax = aMajor ? lenA : lenB, pmin = aMajor ? lenB : lenA;
+    const float mu = aMajor ? dudx : dudy, mv = aMajor ? dvdx : dvdy;
+    const float n = __builtin_ceilf(pmax / pmin);
+    const uint32_t N = n <= 16.0f ? (uint32_t)n : 16u;
+    const float fN = (float)N, x = pmax / fN, top = (float)(e.mips - 1u);
+    const float lod = cm::min_(cm::max_(x > 0.0f ? softmath::log2Soft(x) : 0.0f, 0.0f), top);
+    const float l0f = __builtin_floorf(lod), f = lod - l0f;
+    const uint32_t l0 = (uint32_t)l0f, l1 = l0 + 1u < e.mips ? l0 + 1u : e.mips - 1u;
+    float acc = 0.0f;
+#pragma unroll 1
+    for (uint32_t i = 0; i < N; ++i) {
+        const float k = ((float)i + 0.5f) / fN - 0.5f;
+        const float tu = u + mu * k, tv = v + mv * k;
+        acc = acc + lerp_(bilinearAlpha(e, l0, wrap, tu, tv), bilinearAlpha(e, l1, wrap, tu, tv), f);
+    }
+    return acc / fN;
+}
+
+// One bilinear fetch of mip 0: what a ray reads, which has no pixel quad to differentiate over (k_shadowmask.hip).
+__device__ __forceinline__ float alphaLevel0(const TableEntry& e, bool wrap, float u, float v) { return bilinearAlpha(e, 0u, wrap, u, v); }
 
 } // namespace mtex

@@ -7,6 +7,7 @@
 #pragma once
 
 #include "cull_math.hip.h"
+#include "screen_pass.hip.h"
 #include "trhip_internal.h"
 
 namespace mesh
@@ -96,6 +97,31 @@ __device__ __forceinline__ ScreenVertex toScreen(cm::F3 position, const cm::M43&
 }
 
 __device__ __forceinline__ float edgeFn(float ax, float ay, float bx, float by, float px, float py) { return cm::fma_(bx - ax, py - ay, -((by - ay) * (px - ax))); }
+
+// ---- m_TexCoord and its screen-space derivatives at one sample of a triangle (GetCommonGBufferParams' uv, ddx(uv), ddy(uv)) -----
+// The formulas of the TEXTURED resolve (visibility_resolve.hip.h, which keeps its own copy beside the world position it
+// interpolates through the same q: its registers are counted, k_gbuffer.hip), used by the rasters' alpha test (k_raster.hip).
+// (x_i, y_i, w_i): the vertices' screen positions and clip w; tc_i: the packed half2 m_TexCoord (half -> float is exact); e_i: the
+// sample's own signed edge values (e0 against the edge v1 v2, e1 against v2 v0, e2 against v0 v1).  q_i = e_i / w_i,
+// s = (q0 + q1) + q2, uv = fma(q2, a2, fma(q1, a1, q0 * a0)) / s; ddx and ddy: the same triangle's plane re-evaluated at
+// (cx + 1, cy) and at (cx, cy + 1), minus the centre value.
+struct UvFootprint { float u, v, dudx, dvdx, dudy, dvdy; };
+
+__device__ __forceinline__ UvFootprint uvFootprint(float x0, float y0, float x1, float y1, float x2, float y2, float sgn, float w0, float w1, float w2,
+                                                   uint32_t tc0, uint32_t tc1, uint32_t tc2, float cx, float cy, float e0, float e1, float e2)
+{
+    const float q0 = e0 / w0, q1 = e1 / w1, q2 = e2 / w2;
+    const float s = (q0 + q1) + q2;
+    const float ex0 = sgn * edgeFn(x1, y1, x2, y2, cx + 1.0f, cy), ex1 = sgn * edgeFn(x2, y2, x0, y0, cx + 1.0f, cy), ex2 = sgn * edgeFn(x0, y0, x1, y1, cx + 1.0f, cy);
+    const float ey0 = sgn * edgeFn(x1, y1, x2, y2, cx, cy + 1.0f), ey1 = sgn * edgeFn(x2, y2, x0, y0, cx, cy + 1.0f), ey2 = sgn * edgeFn(x0, y0, x1, y1, cx, cy + 1.0f);
+    const float qx0 = ex0 / w0, qx1 = ex1 / w1, qx2 = ex2 / w2, qy0 = ey0 / w0, qy1 = ey1 / w1, qy2 = ey2 / w2;
+    const float sX = (qx0 + qx1) + qx2, sY = (qy0 + qy1) + qy2;
+    const float u0 = (float)sp::halfOf(tc0), u1 = (float)sp::halfOf(tc1), u2 = (float)sp::halfOf(tc2);
+    const float v0 = (float)sp::halfOf(tc0 >> 16), v1 = (float)sp::halfOf(tc1 >> 16), v2 = (float)sp::halfOf(tc2 >> 16);
+    const float u = cm::fma_(q2, u2, cm::fma_(q1, u1, q0 * u0)) / s, v = cm::fma_(q2, v2, cm::fma_(q1, v1, q0 * v0)) / s;
+    return { u, v, cm::fma_(qx2, u2, cm::fma_(qx1, u1, qx0 * u0)) / sX - u, cm::fma_(qx2, v2, cm::fma_(qx1, v1, qx0 * v0)) / sX - v,
+             cm::fma_(qy2, u2, cm::fma_(qy1, u1, qy0 * u0)) / sY - u, cm::fma_(qy2, v2, cm::fma_(qy1, v1, qy0 * v0)) / sY - v };
+}
 
 // ---- visibility texel: (depthBits << 32) | slot << 30 | listPosition << 7 | triangle ---------------------------------
 constexpr uint32_t kVisTriangleBits = 7, kVisListBits = 23;

@@ -933,8 +933,14 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
             trhip_texture_table_t* t = (trhip_texture_table_t*)b[i].resource;
             if (!t) return fail(TRHIP_ERR_INVALID, "dispatch(%s): binding %u has no texture table", name, i);
             if (t->dev != cl->dev) return fail(TRHIP_ERR_INVALID, "dispatch(%s): the texture table belongs to another device", name);
-            if (strcmp(name, "basepass_PS_Main_GBuffer") != 0 || b[i].slot != 19u)           // the one shader that indexes ResourceDescriptorHeap[...]
-                return fail(TRHIP_ERR_INVALID, "dispatch(%s): a texture table at t%u: only basepass_PS_Main_GBuffer declares one, at t19", name, b[i].slot);
+            // the shaders that index ResourceDescriptorHeap[...]: the G-buffer resolve, the alpha-tested rasters and the sun rays
+            static const char* const kTableShaders[] = { "basepass_PS_Main_GBuffer", "basepass_MS_Main_depth ALPHA_MASK_MODE=1", "basepass_MS_Main_visibility ALPHA_MASK_MODE=1",
+                                                         "shadowmask_CS_ShadowMask" };
+            bool declares = false;
+            for (const char* n : kTableShaders) declares |= strcmp(name, n) == 0;
+            if (!declares || b[i].slot != 19u)
+                return fail(TRHIP_ERR_INVALID, "dispatch(%s): a texture table at t%u: only basepass_PS_Main_GBuffer, the ALPHA_MASK_MODE=1 rasters and shadowmask_CS_ShadowMask declare one, at t19",
+                            name, b[i].slot);
             trhip_texture_table_retain(t);
             cl->heldTables.push_back(t);
             for (trhip_texture_t* e : t->slots) cl->hold(e, false);

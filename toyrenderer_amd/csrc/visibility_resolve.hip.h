@@ -13,7 +13,8 @@
 //   normal  = fma(q2, N2, fma(q1, N1, q0 * N0)) / s per component, NOT renormalised (the reference does not);
 //   albedo  = m_ConstAlbedo.rgb, emissive = m_ConstEmissive, roughness = 1, metallic = 0 (Q13: m_ConstRoughness and
 //             m_ConstMetallic are never read by the reference's shader); texture flags are ignored, the upload paths
-//             refuse them; ALPHA_MASK_MODE's discard is not modelled (neither do the depth and visibility rasters);
+//             refuse them; ALPHA_MASK_MODE's discard is not modelled here: the ALPHA_MASK_MODE=1 rasters (k_raster.hip) apply it, and a
+//             discarded sample never becomes a texel;
 //   x = PackRGBA8(albedo, debugValue), y = PackUnorm2x16(PackOctadehron(normal)), z = PackR9G9B9E5(emissive),
 //   w = PackRGBA8(1, 0, 0, 0) = 0xFF  (lightingcommon.hlsli:28-34), saturate(x) = fmin(fmax(x, 0), 1) (a NaN gives 0),
 //             uint(x) truncates, round = round half to even;

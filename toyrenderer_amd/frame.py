@@ -158,7 +158,7 @@ class FrameDriver:
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
                  bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
-                 shadows=None):
+                 shadows=None, alpha_test: bool = False):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -221,7 +221,14 @@ class FrameDriver:
         matrices) and "shadowmask_CS_ShadowMask", and binds the mask as the lighting pass's t4.  The light direction is dir_light[0]
         as given, the camera position camera_origin, m_NoisePhase (self.frame_counter & 0xff) * 1.61803398875f, m_TanSunAngularRadius
         tan(radians(d / 2)) evaluated in double and rounded once (0 without soft).  self.shadow_consts holds the 112-byte
-        ShadowMaskConsts of the last record(); download_shadow_mask() reads the mask back."""
+        ShadowMaskConsts of the last record(); download_shadow_mask() reads the mask back.
+        alpha_test: False (the default) changes nothing: alpha-mask instances are drawn as solid triangles.  True (needs
+        raster_depth, which visibility and everything above imply, and GpuScene.set_materials()): ALPHA_MASK_MODE's discard
+        (basepass.hlsl:210-215).  Pass slots 2 and 3 dispatch "basepass_MS_Main_depth ALPHA_MASK_MODE=1" or
+        "basepass_MS_Main_visibility ALPHA_MASK_MODE=1" with the materials at t3 and, when a loaded material uses a texture, the
+        texture table at t19: a sample whose m_ConstAlbedo.w times the albedo texture's alpha is below m_AlphaCutoff is not drawn,
+        so depth, the HZB, the visibility buffer and everything resolved from it see through the cut-outs.  With shadows the
+        trace binds the table too and a textured cut-out casts the shadow of its kept texels (mip 0)."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -231,6 +238,11 @@ class FrameDriver:
             raise ValueError(("post=True" if post else "lighting=True" if lighting else "gbuffer=True") + " needs GpuScene.set_materials()")
         if lighting and int(debug_mode) == I.kDeferredLightingDebugMode_Ambient:
             raise ValueError("debug_mode 10 (Ambient) needs the DDGI volume, which is not built")
+        self.alpha_test = bool(alpha_test)
+        if self.alpha_test and not (raster_depth or visibility):
+            raise ValueError("alpha_test=True needs raster_depth=True (or visibility, gbuffer, lighting, post): the test runs in the rasters, and a frame without them draws nothing")
+        if self.alpha_test and scene.materials is None:
+            raise ValueError("alpha_test=True needs GpuScene.set_materials(): the test reads m_ConstAlbedo.w, m_AlphaCutoff and the albedo texture of each instance's material")
         self.gbuffer_on = bool(gbuffer)
         self.lighting_on = bool(lighting)
         self.post_on = bool(post)
@@ -458,11 +470,17 @@ class FrameDriver:
         cl.dispatch_indirect(f"basepass_AS_Main LATE_CULL={int(late)}", bindings, self.dispatchArgs[slot])   # :497-502
         if self.raster_depth:                                                            # the mesh + pixel stage of the same draw: depth only
             b = self._mesh_stage_bindings(cb) + [SRV(7, self.records[slot]), SRV(9, self.visibleList[slot]), TEX_UAV(0, self.depth, 0)]
+            permutation = ""
+            if alpha_mask and self.alpha_test:                                           # BasePassRenderers.cpp:489: + t3 materials, t19 the table
+                permutation = " ALPHA_MASK_MODE=1"
+                b.append(SRV(3, sc.materials))
+                if sc.textured:
+                    b.append(TEX_TABLE(sc.texture_table))
             if self.visibility_on:                                                       # + u1 = visibility buffer, push = pass slot
-                cl.dispatch_indirect("basepass_MS_Main_visibility", b + [TEX_UAV(1, self.visibility, 0), PUSH(1)], self.drawArgs[slot],
+                cl.dispatch_indirect("basepass_MS_Main_visibility" + permutation, b + [TEX_UAV(1, self.visibility, 0), PUSH(1)], self.drawArgs[slot],
                                      push=np.array([slot], np.uint32))
             else:
-                cl.dispatch_indirect("basepass_MS_Main_depth", b, self.drawArgs[slot])
+                cl.dispatch_indirect("basepass_MS_Main_depth" + permutation, b, self.drawArgs[slot])
 
     def _resolve_motion(self, cl):
         """GBufferMotion of every pixel the base pass drew (basepass.hlsl:226-237), once after the last slot."""
@@ -546,7 +564,8 @@ class FrameDriver:
                     [CB(0, cb), TEX_SRV(0, self.depth), SRV(1, rt["tlas_nodes"]), TEX_SRV(2, self.gbufferA), SRV(3, sc.instances), SRV(4, sc.vertices),
                      SRV(5, sc.materials), SRV(6, sc.indices), SRV(7, sc.meshData), TEX_SRV(8, self.blue_noise), TEX_UAV(0, self.shadow_mask_texture, 0),
                      TEX_UAV(1, self.linear_view_depth, 0), SRV(9, rt["tlas_instances"]), SRV(10, rt["headers"]), SRV(11, rt["blas_nodes"]),
-                     SRV(12, rt["tri_order"]), SAMPLER(0), SAMPLER(1)], ((W + 7) // 8, (H + 7) // 8, 1))
+                     SRV(12, rt["tri_order"]), SAMPLER(0), SAMPLER(1)] + ([TEX_TABLE(sc.texture_table)] if self.alpha_test and sc.textured else []),
+                    ((W + 7) // 8, (H + 7) // 8, 1))
 
     def download_shadow_mask(self) -> np.ndarray:
         """The bytes of the generated shadow mask, (H, W) uint8."""

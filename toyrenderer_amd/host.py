@@ -25,7 +25,7 @@ HOST_SYMBOLS = [
     "trhost_rccl_allgather", "trhost_exchange_create", "trhost_exchange_run", "trhost_exchange_wait", "trhost_exchange_outputs",
     "trhost_exchange_destroy", "trhost_load_geometry", "trhost_set_raster_depth", "trhost_download_depth",
     "trhost_set_visibility_buffer", "trhost_download_visibility", "trhost_download_motion",
-    "trhost_load_materials", "trhost_create_material_texture", "trhost_set_gbuffer", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
+    "trhost_load_materials", "trhost_create_material_texture", "trhost_set_gbuffer", "trhost_set_alpha_test", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
@@ -96,6 +96,7 @@ def load() -> C.CDLL:
     L.trhost_load_materials.argtypes = [vp, u32]
     L.trhost_create_material_texture.argtypes = [u32, u32, u32, u32, vp, u64]
     L.trhost_set_gbuffer.argtypes = [C.c_int]
+    L.trhost_set_alpha_test.argtypes = [C.c_int]
     L.trhost_set_debug_view_mode.argtypes = [u32]
     L.trhost_download_gbuffer_a.argtypes = [vp, u64]
     L.trhost_set_deferred_lighting.argtypes = [C.c_int]
@@ -307,6 +308,11 @@ class Renderer:
     def set_gbuffer(self, on: bool = True):
         """GBufferA + motion through one "basepass_PS_Main_GBuffer" dispatch (implies the visibility buffer)."""
         _check(load().trhost_set_gbuffer(int(on)))
+
+    def set_alpha_test(self, on: bool = True):
+        """ALPHA_MASK_MODE's discard in the alpha-mask pass slots' rasters and textured alpha in the sun rays (needs the rasters and
+        load_materials); off by default: alpha-mask instances are drawn as solid triangles."""
+        _check(load().trhost_set_alpha_test(int(on)))
 
     def set_debug_view_mode(self, mode: int):
         _check(load().trhost_set_debug_view_mode(int(mode)))
