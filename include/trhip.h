@@ -57,10 +57,13 @@ enum {
  * SRGBA8_UNORM (11) has RGBA8_UNORM's layout; a sampling pass decodes R, G and B through the sRGB transfer function before
  * filtering (trhip_srgb_table), alpha stays linear.  An RGBA8_UNORM or SRGBA8_UNORM texture created WITHOUT the UAV and
  * render-target bits (isUAV == 0: a material texture, sampled only) may have a mip chain, uploaded per mip through
- * trhip_texture_upload; one that a pass writes keeps one mip. */
+ * trhip_texture_upload; one that a pass writes keeps one mip.
+ * R10G10B10A2_UNORM (12: the DDGI probe irradiance; 4 bytes per texel, R in bits 0-9, G in bits 10-19, B in bits 20-29, A in bits
+ * 30-31) and RGBA16_FLOAT (13: the DDGI probe data; 8 bytes per texel, four binary16 x, y, z, w) have one mip; they are created,
+ * uploaded and downloaded, and both clears refuse them. */
 enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4,
        TRHIP_FORMAT_RGBA32_UINT = 5, TRHIP_FORMAT_R11G11B10_FLOAT = 6, TRHIP_FORMAT_R8_UNORM = 7, TRHIP_FORMAT_R8_UINT = 8,
-       TRHIP_FORMAT_RGBA8_UNORM = 10, TRHIP_FORMAT_SRGBA8_UNORM = 11 };
+       TRHIP_FORMAT_RGBA8_UNORM = 10, TRHIP_FORMAT_SRGBA8_UNORM = 11, TRHIP_FORMAT_R10G10B10A2_UNORM = 12, TRHIP_FORMAT_RGBA16_FLOAT = 13 };
 
 /* ---- error / introspection ---------------------------------------------------------------- */
 const char* trhip_last_error(void);          /* thread-local text of the last failure          */
@@ -110,13 +113,23 @@ uint32_t    trhip_abi_version(void);
  * and is refused by the next recording.  A texture table bound to a shader other than this one, the two ALPHA_MASK_MODE=1 rasters
  * and "shadowmask_CS_ShadowMask", or at another slot, is refused.
  * "deferredlighting_PS_Main" and "deferredlighting_PS_Main_Debug" (deferredlighting.hlsl, DeferredLightingRenderer.cpp: the
- * directional light and the debug views, without DDGI): a direct dispatch of [numthreads(8, 8, 1)] groups over the screen;
- * b0 DeferredLightingConsts (112 bytes; m_bRTDDGIEnabled must be 0, m_DebugMode must not be 10), t0 (texture) RGBA32_UINT
+ * directional light, the DDGI ambient term from a SUPPLIED probe volume, and the debug views): a direct dispatch of
+ * [numthreads(8, 8, 1)] groups over the screen; b0 DeferredLightingConsts (112 bytes), t0 (texture) RGBA32_UINT
  * GBufferA, t1 RG16_FLOAT GBufferMotion (required by _Debug only), t2 R32_FLOAT depth, t3 R8_UINT SSAO (optional: unbound
  * reads 255), t4 R8_UNORM shadow mask (optional: unbound reads 1.0), u0 (texture) R11G11B10_FLOAT LightingOutput; every
- * texture of the size m_LightingOutputResolution; samplers and bindings at t5..t8 are accepted and ignored.  A pixel is
+ * texture of the size m_LightingOutputResolution; samplers are accepted and ignored.  A pixel is
  * written iff its depth is > 0.0f (the stand-in for the reference's stencil test on the opaque bit); every other texel of u0
  * keeps its value.  The arithmetic convention is stated in csrc/k_deferredlighting.hip.
+ * DDGI (m_bRTDDGIEnabled != 0 in PS_Main: lighting += albedo / pi * irradiance, times ssao / 255 when m_SSAOEnabled; or
+ * m_DebugMode 10 in _Debug: the irradiance itself): t5 a structured buffer of at least 64 bytes holding a DDGIVolumeDesc
+ * (csrc/ShaderInterop.h: the project's own 64-byte descriptor, INTEGRATION.md names the SDK field behind each member), t6 the
+ * probe data (RGBA16_FLOAT array, counts.x x counts.z, counts.y slices), t7 the probe irradiance (R10G10B10A2_UNORM array,
+ * counts.x * 8 x counts.z * 8), t8 the probe distance (RG16_FLOAT array, counts.x * 16 x counts.z * 16), and b0 grows to 176
+ * bytes: the DeferredLightingConsts followed by a HOST COPY of the descriptor.  The record function checks the host copy
+ * (counts 1..1024, interior texel counts 6 and 14, spacing positive and finite, the three textures' formats, sizes and slice
+ * counts); the kernel reads t5.  It is the caller's promise that the two agree; where they do not, every fetch still stays
+ * inside the bound textures and the value is unspecified.  The query is csrc/ddgi_irradiance.hip.h's (tests/ddgi_ref.c).
+ * With m_bRTDDGIEnabled == 0 and another mode, bindings at t5..t8 and a longer b0 are accepted and ignored.
  * "adaptluminance_CS_GenerateLuminanceHistogram" (adaptluminance.hlsl, AdaptLuminanceRenderer.cpp): a direct dispatch of
  * [numthreads(16, 16, 1)] groups covering m_SrcColorDims; push constants GenerateLuminanceHistogramParameters (16 bytes), t0
  * (texture) the R11G11B10_FLOAT colour, u0 a structured UAV of at least 256 uint32.  It ADDS to u0: the caller clears it.
@@ -209,6 +222,17 @@ void* trhip_buffer_device_ptr(trhip_buffer buf);
 uint64_t trhip_buffer_size(trhip_buffer buf);
 
 int  trhip_texture_create(trhip_device dev, const trhip_texture_desc* desc, trhip_texture* out);
+/* A 2D ARRAY texture (Texture2DArray: the DDGI probe textures of RTXGI, GIRenderer.cpp): `arraySize` (1..2048) slices of
+ * desc's size and format, one mip.  trhip_texture_desc stays as it is.  Formats: R10G10B10A2_UNORM, RG16_FLOAT, RGBA16_FLOAT.
+ * Slice k is row-major at byte k * trhip_texture_slice_pitch(tex) of the allocation; the pitch is width * height * texel bytes
+ * rounded up to 256.  trhip_texture_array_size is 0 for a texture that is not an array (one of a single slice is still an
+ * array).  An array texture is uploaded and downloaded per slice (the mip calls refuse it); it cannot be a texture table
+ * entry, and every shader refuses one at any binding, naming itself, except "deferredlighting_PS_Main" / "_Debug" at t6..t8. */
+int  trhip_texture_create_array(trhip_device dev, const trhip_texture_desc* desc, uint32_t arraySize, trhip_texture* out);
+uint32_t trhip_texture_array_size(trhip_texture tex);
+uint64_t trhip_texture_slice_pitch(trhip_texture tex);
+int  trhip_texture_upload_slice(trhip_texture tex, uint32_t slice, const void* src, uint64_t bytes);
+int  trhip_texture_download_slice(trhip_texture tex, uint32_t slice, void* dst, uint64_t bytes);
 int  trhip_texture_memory_requirements(trhip_texture tex, uint64_t* size, uint64_t* alignment);
 int  trhip_texture_bind_memory(trhip_texture tex, trhip_heap heap, uint64_t offset);
 void trhip_texture_retain(trhip_texture tex);

@@ -105,7 +105,7 @@ int  trhost_set_debug_view_mode(uint32_t mode);
 int  trhost_download_gbuffer_a(uint32_t* words, uint64_t bytes);
 /* Deferred lighting from GBufferA (DeferredLightingRenderer.cpp; implies the G-buffer, same refusals): after GBufferRenderer one
  * "deferredlighting_PS_Main" dispatch ("deferredlighting_PS_Main_Debug" while trhost_set_debug_view_mode is not 0; mode 10 needs
- * the DDGI volume and fails the frame) writes LightingOutput (R11G11B10_FLOAT at render resolution, 4 bytes per texel, cleared to
+ * the DDGI volume, trhost_upload_ddgi_volume below, and is refused without it) writes LightingOutput (R11G11B10_FLOAT at render resolution, 4 bytes per texel, cleared to
  * 0 every frame; written where depth > 0).  trhost_set_directional_light sets Scene::m_DirLightVec, used as given, and
  * m_DirLightStrength (default (0, -1, 0), 1).  trhost_upload_shadow_mask uploads the R8_UNORM mask at render resolution
  * (width * height bytes); NULL means white.  trhost_get_deferred_lighting_consts copies the 112 bytes of DeferredLightingConsts
@@ -116,6 +116,18 @@ int  trhost_set_directional_light(const float vec[3], float strength);
 int  trhost_upload_shadow_mask(const uint8_t* texels, uint64_t bytes);
 int  trhost_download_lighting_output(uint32_t* words, uint64_t bytes);
 int  trhost_get_deferred_lighting_consts(void* out112);
+/* The DDGI ambient term from a SUPPLIED probe volume (Scene::m_RTDDGIVolume; tracing and blending the probes is not built).
+ * trhost_upload_ddgi_volume creates and fills the volume: desc64 is the 64-byte DDGIVolumeDesc (csrc/ShaderInterop.h), the three
+ * arrays are dense, slice (probe y) after slice: irradiance R10G10B10A2_UNORM words [counts.y][counts.z * 8][counts.x * 8],
+ * distance binary16 pairs [counts.y][counts.z * 16][counts.x * 16][2], data binary16 quadruples [counts.y][counts.z][counts.x][4];
+ * the byte sizes must match the counts.  desc64 = NULL drops the volume and switches DDGI off.  From then on the lighting pass
+ * binds the volume at t5..t8.  trhost_set_ddgi(1) makes Scene::IsDDGIEnabled() true: m_bRTDDGIEnabled = 1 in the consts
+ * trhost_get_deferred_lighting_consts shows, and LightingOutput gains albedo / pi * irradiance (times the SSAO texture when
+ * ambient occlusion is on).  Debug view 10 (Ambient) shows the irradiance, whatever trhost_set_ddgi says.  Without an uploaded
+ * volume trhost_set_ddgi(1) and view 10 are refused ("DDGI", "Ambient" in the text). */
+int  trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, uint64_t irradiance_bytes, const uint16_t* distance, uint64_t distance_bytes,
+                               const uint16_t* data, uint64_t data_bytes);
+int  trhost_set_ddgi(int enable);
 /* Auto exposure and tone mapping (AdaptLuminanceRenderer.cpp, PostProcessRenderer.cpp; implies deferred lighting, same refusals):
  * after DeferredLightingRenderer the frame clears the luminance histogram and runs "adaptluminance_CS_GenerateLuminanceHistogram"
  * and "adaptluminance_CS_AdaptExposure" (with a manual exposure > 0: one write of it into the luminance buffer instead), then

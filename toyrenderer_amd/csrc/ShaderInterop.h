@@ -132,6 +132,28 @@ static_assert(offsetof(DeferredLightingConsts, m_DebugMode) == 80 && offsetof(De
 static_assert(offsetof(DeferredLightingConsts, m_DirectionalLightStrength) == 96 && offsetof(DeferredLightingConsts, m_LightingOutputResolution) == 100 &&
               offsetof(DeferredLightingConsts, m_bRTDDGIEnabled) == 108, "DeferredLightingConsts");
 
+// The project's own: the DDGI volume as "deferredlighting_PS_Main" reads it at t5 (k_deferredlighting.hip, ddgi_irradiance.hip.h).
+// It stands in for the RTXGI SDK's DDGIVolumeDescGPUPacked, whose layout this project cannot check; INTEGRATION.md names the SDK
+// field behind each member.  No rotation and no scrolling (the reference's volume has neither, GIRenderer.cpp:71, :90);
+// coordinate system 0 (left-handed, Y up): a probe's tile sits at texel (x * N, z * N) of slice y, N = interior + 2.
+struct DDGIVolumeDesc
+{
+    float origin[3];
+    float probeNormalBias;
+    float probeSpacing[3];
+    float probeViewBias;
+    int32_t probeCounts[3];
+    float probeIrradianceEncodingGamma;
+    uint32_t numIrradianceInteriorTexels;    // 6 in the reference
+    uint32_t numDistanceInteriorTexels;      // 14 in the reference
+    uint32_t flags;                          // bit 0 relocation enabled, bit 1 classification enabled
+    uint32_t pad;
+};
+static_assert(sizeof(DDGIVolumeDesc) == 64 && offsetof(DDGIVolumeDesc, probeSpacing) == 16 && offsetof(DDGIVolumeDesc, probeCounts) == 32 &&
+              offsetof(DDGIVolumeDesc, numIrradianceInteriorTexels) == 48 && offsetof(DDGIVolumeDesc, flags) == 56, "DDGIVolumeDesc");
+static constexpr uint32_t kDDGIFlag_Relocation = 1u, kDDGIFlag_Classification = 2u;
+static constexpr uint32_t kDDGIIrradianceInteriorTexels = 6, kDDGIDistanceInteriorTexels = 14, kDDGIMaxProbeCount = 1024;
+
 // ShaderInterop.h:124-129: push constants of "adaptluminance_CS_GenerateLuminanceHistogram"
 struct GenerateLuminanceHistogramParameters
 {

@@ -2,8 +2,10 @@
 // full-screen pass that reads GBufferA, the motion target, the depth buffer and the shadow mask and writes LightingOutput,
 // "deferredlighting_PS_Main" or, under a debug view, "deferredlighting_PS_Main_Debug" (csrc/k_deferredlighting.hip).
 //
-// Out of scope, as in the back end: DDGI (m_bRTDDGIEnabled stays 0, the volume descriptors and probe textures at t5..t8 are not
-// bound).  The shadow mask at t4 is ShadowMaskRenderer's when that pass is scheduled, else an uploaded one
+// DDGI: m_bRTDDGIEnabled = g_Scene->IsDDGIEnabled(), as in the reference; the volume (g_Scene->m_RTDDGIVolume: descriptor at t5,
+// probe data, irradiance and distance at t6..t8) is SUPPLIED through trhost_upload_ddgi_volume, tracing and blending the probes
+// are not built.  With the volume bound the constant block carries the descriptor's host copy behind the DeferredLightingConsts
+// (include/trhip.h).  The shadow mask at t4 is ShadowMaskRenderer's when that pass is scheduled, else an uploaded one
 // (trhost_upload_shadow_mask), else t4 stays unbound: 1.0, the reference's WhiteTexture.  The full-screen triangle with its stencil test on the opaque
 // bit is a direct dispatch of 8x8 groups here; the kernel writes where depth > 0.
 #include "CommonResources.h"
@@ -68,19 +70,26 @@ public:
         passConstants.m_SSAOEnabled = m_SSAOTexture ? 1 : 0;               // :69, m_bEnableAO
         passConstants.m_LightingOutputResolution = g_Graphic.m_RenderResolution;
         passConstants.m_DebugMode = g_Scene->m_DebugViewMode;
-        passConstants.m_bRTDDGIEnabled = 0;
+        passConstants.m_bRTDDGIEnabled = g_Scene->IsDDGIEnabled() ? 1 : 0;   // :72
         m_LastConsts = passConstants;
         m_bHasLastConsts = true;
 
         // the reference's per-frame clear of the lighting output (Scene.cpp:42-70): the pass leaves sky texels alone
         commandList->clearTextureFloat(m_LightingOutput, nvrhi::AllSubresources, nvrhi::Color{ 0.0f });
 
+        // the volume's resources are bound whenever there is one (:78-82), its host copy with them; the back end looks at
+        // them with the flag or in view 10 only
+        const Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+        const bool bindVolume = volume.IsValid();
+        struct WithVolume { DeferredLightingConsts consts; DDGIVolumeDesc desc; } withVolume{ passConstants, volume.m_Desc };
+        static_assert(sizeof(WithVolume) == 176, "DeferredLightingConsts + DDGIVolumeDesc");
+
         using Item = nvrhi::BindingSetItem;
         Graphic::ComputePassParams p;                                         // :84-119
         p.m_CommandList = commandList;
         p.m_ShaderName = g_Scene->m_DebugViewMode != 0 ? "deferredlighting_PS_Main_Debug" : "deferredlighting_PS_Main";   // :109-110
         p.m_BindingSetDesc.bindings = {
-            Item::ConstantBuffer(0, g_Graphic.CreateConstantBuffer(commandList, passConstants)),
+            Item::ConstantBuffer(0, bindVolume ? g_Graphic.CreateConstantBuffer(commandList, withVolume) : g_Graphic.CreateConstantBuffer(commandList, passConstants)),
             Item::Texture_SRV(0, GetGBufferA()),
             Item::Texture_SRV(1, GetMotionBuffer()),
             Item::Texture_SRV(2, renderGraph.GetTexture(g_DepthStencilBufferRDGTextureHandle)),
@@ -88,6 +97,12 @@ public:
         };
         if (m_SSAOTexture) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(3, m_SSAOTexture));   // :77
         if (m_ShadowMask) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(4, m_ShadowMask));
+        if (bindVolume) {
+            p.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_SRV(5, volume.m_DescBuffer));
+            p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(6, volume.m_ProbeData));
+            p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(7, volume.m_ProbeIrradiance));
+            p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(8, volume.m_ProbeDistance));
+        }
         p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Graphic.m_RenderResolution, 8);
         g_Graphic.AddComputePass(p);
     }

@@ -328,6 +328,8 @@ void Scene::Shutdown()
     m_HZB = nullptr;
     m_SyntheticDepth = nullptr;
     m_ShadowMaskTexture = nullptr;
+    m_RTDDGIVolume = RTDDGIVolume{};
+    m_bEnableDDGI = false;
     m_TLAS.reset();
     m_BlueNoise = nullptr;
     m_BloomTexture = nullptr;

@@ -7,6 +7,7 @@
 #include <memory>
 #include <vector>
 
+#include "../ShaderInterop.h"
 #include "MathUtilities.h"
 #include "RenderGraph.h"
 #include "nvrhi_lite.h"
@@ -108,6 +109,17 @@ public:
     float m_DirLightVec[3] = { 0.0f, -1.0f, 0.0f };  // Scene.h:134-136: used as given (the reference derives it from two angles)
     float m_DirLightStrength = 1.0f;
     nvrhi::TextureHandle m_ShadowMaskTexture;        // R8_UNORM at render resolution, or null: the pass reads 1.0 (the reference's WhiteTexture)
+    // The DDGI volume DeferredLightingRenderer consumes (Scene.h: m_RTDDGIVolume, GIRenderer's in the reference).  Tracing and
+    // blending the probes is not built: trhost_upload_ddgi_volume supplies the descriptor and the three array textures.
+    struct RTDDGIVolume
+    {
+        interop::DDGIVolumeDesc m_Desc{};            // the host copy, appended to the pass's constant block
+        nvrhi::BufferHandle m_DescBuffer;            // t5
+        nvrhi::TextureHandle m_ProbeData, m_ProbeIrradiance, m_ProbeDistance;   // t6, t7, t8
+        bool IsValid() const { return m_DescBuffer && m_ProbeData && m_ProbeIrradiance && m_ProbeDistance; }
+    } m_RTDDGIVolume;
+    bool m_bEnableDDGI = false;                      // trhost_set_ddgi
+    bool IsDDGIEnabled() const { return m_bEnableDDGI && m_RTDDGIVolume.IsValid(); }
     // Auto exposure and tone mapping (trhost_set_post_process; implies m_bDeferredLighting): AdaptLuminanceRenderer and
     // PostProcessRenderer run after DeferredLightingRenderer and turn LightingOutput into the RGBA8_UNORM back buffer.
     bool m_bPostProcess = false;

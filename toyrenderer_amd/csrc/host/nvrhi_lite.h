@@ -93,7 +93,7 @@ private:
 using ResourceHandle = RefCountPtr<IResource>;
 
 // ---- enums / small structs -----------------------------------------------------------------------
-enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT, RGBA8_UNORM, SRGBA8_UNORM };   // GraphicConstants.h:24-28, :31 (lighting output), shadow mask, SSAO, the back buffer (GraphicRHI.cpp:214)
+enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT, RGBA8_UNORM, SRGBA8_UNORM, R10G10B10A2_UNORM, RGBA16_FLOAT };   // GraphicConstants.h:24-28, :31 (lighting output), shadow mask, SSAO, the back buffer (GraphicRHI.cpp:214)
 enum class ResourceStates : uint32_t { Unknown = 0, ShaderResource, UnorderedAccess, IndirectArgument, DepthRead, DepthWrite, CopyDest };
 enum class CommandQueue : uint8_t { Graphics = 0, Compute, Copy, Count };
 enum class HeapType : uint8_t { DeviceLocal };
@@ -126,11 +126,13 @@ struct BufferDesc
     ResourceStates initialState = ResourceStates::Unknown;
 };
 
+static constexpr uint8_t kTexture2DArray = 5;    // nvrhi::TextureDimension::Texture2DArray
+
 struct TextureDesc
 {
     uint32_t width = 1, height = 1, depth = 1, arraySize = 1, mipLevels = 1, sampleCount = 1, sampleQuality = 0;
     Format format = Format::UNKNOWN;
-    uint8_t dimension = 2;
+    uint8_t dimension = 2;                       // 2: Texture2D; kTexture2DArray: arraySize slices (the DDGI probe textures)
     std::string debugName;
     bool isRenderTarget = false, isUAV = false, isTypeless = false, isShadingRateSurface = false, isVirtual = false;
     Color clearValue;
@@ -466,9 +468,11 @@ public:
                  : d.format == Format::RG16_FLOAT ? TRHIP_FORMAT_RG16_FLOAT : d.format == Format::RGBA32_UINT ? TRHIP_FORMAT_RGBA32_UINT
                  : d.format == Format::R11G11B10_FLOAT ? TRHIP_FORMAT_R11G11B10_FLOAT : d.format == Format::R8_UNORM ? TRHIP_FORMAT_R8_UNORM
                  : d.format == Format::R8_UINT ? TRHIP_FORMAT_R8_UINT : d.format == Format::RGBA8_UNORM ? TRHIP_FORMAT_RGBA8_UNORM
-                 : d.format == Format::SRGBA8_UNORM ? TRHIP_FORMAT_SRGBA8_UNORM : TRHIP_FORMAT_R32_FLOAT;
+                 : d.format == Format::SRGBA8_UNORM ? TRHIP_FORMAT_SRGBA8_UNORM : d.format == Format::R10G10B10A2_UNORM ? TRHIP_FORMAT_R10G10B10A2_UNORM
+                 : d.format == Format::RGBA16_FLOAT ? TRHIP_FORMAT_RGBA16_FLOAT : TRHIP_FORMAT_R32_FLOAT;
         trhip_texture t = nullptr;
-        throwIfFailed(trhip_texture_create(m_Native, &n, &t), "IDevice::createTexture");
+        if (d.dimension == kTexture2DArray) throwIfFailed(trhip_texture_create_array(m_Native, &n, d.arraySize, &t), "IDevice::createTexture (array)");
+        else throwIfFailed(trhip_texture_create(m_Native, &n, &t), "IDevice::createTexture");
         return TextureHandle(new ITexture(t, d));
     }
     SamplerHandle createSampler(const SamplerDesc& d) { return SamplerHandle(new ISampler(d)); }

@@ -174,8 +174,8 @@ int trhost_set_debug_view_mode(uint32_t mode)
 {
     return guarded([&] {
         check(g_Scene);
-        if (mode == interop::kDeferredLightingDebugMode_Ambient && g_Scene->m_bDeferredLighting)
-            throw nvrhi::Error("trhost_set_debug_view_mode: mode 10 (Ambient) needs the DDGI volume, which deferredlighting_PS_Main_Debug does not have");
+        if (mode == interop::kDeferredLightingDebugMode_Ambient && g_Scene->m_bDeferredLighting && !g_Scene->m_RTDDGIVolume.IsValid())
+            throw nvrhi::Error("trhost_set_debug_view_mode: mode 10 (Ambient) needs the DDGI volume, which deferredlighting_PS_Main_Debug does not have (trhost_upload_ddgi_volume first)");
         g_Scene->m_DebugViewMode = mode;
     });
 }
@@ -187,7 +187,7 @@ int trhost_set_deferred_lighting(int enable)
         if (enable && !g_Graphic.m_GlobalMaterialDataBuffer) throw nvrhi::Error("trhost_set_deferred_lighting: no materials (trhost_load_materials first)");
         if (enable && g_Graphic.m_MaxMeshletGroups > (1u << 18))
             throw nvrhi::Error("trhost_set_deferred_lighting: max_meshlet_groups above 2^18 (list positions must stay below 2^23)");
-        if (enable && g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient)
+        if (enable && g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient && !g_Scene->m_RTDDGIVolume.IsValid())
             throw nvrhi::Error("trhost_set_deferred_lighting: debug view mode 10 (Ambient) needs the DDGI volume, which deferredlighting_PS_Main_Debug does not have");
         g_Scene->m_bDeferredLighting = enable != 0;
         if (enable) { g_Scene->m_bGBuffer = true; g_Scene->m_bVisibilityBuffer = true; g_Scene->m_bRasterDepth = true; }   // implies the G-buffer
@@ -220,6 +220,67 @@ int trhost_upload_shadow_mask(const uint8_t* texels, uint64_t bytes)
     });
 }
 
+int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, uint64_t irradiance_bytes, const uint16_t* distance, uint64_t distance_bytes,
+                              const uint16_t* data, uint64_t data_bytes)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!desc64) {                                                        // drop the volume
+            if (g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient && g_Scene->m_bDeferredLighting)
+                throw nvrhi::Error("trhost_upload_ddgi_volume: debug view mode 10 (Ambient) is showing the DDGI volume");
+            g_Scene->m_RTDDGIVolume = Scene::RTDDGIVolume{};
+            g_Scene->m_bEnableDDGI = false;
+            return;
+        }
+        check(irradiance && distance && data);
+        interop::DDGIVolumeDesc d;
+        memcpy(&d, desc64, sizeof d);
+        for (int a = 0; a < 3; ++a) {
+            if (d.probeCounts[a] < 1 || d.probeCounts[a] > (int)interop::kDDGIMaxProbeCount) throw nvrhi::Error("trhost_upload_ddgi_volume: a DDGI probe count is not in 1..1024");
+            if (!(d.probeSpacing[a] > 0.0f && d.probeSpacing[a] <= 3.402823466e38f)) throw nvrhi::Error("trhost_upload_ddgi_volume: a DDGI probe spacing is not positive and finite");
+        }
+        if (d.numIrradianceInteriorTexels != interop::kDDGIIrradianceInteriorTexels || d.numDistanceInteriorTexels != interop::kDDGIDistanceInteriorTexels)
+            throw nvrhi::Error("trhost_upload_ddgi_volume: the DDGI probe tiles have 6 (irradiance) and 14 (distance) interior texels");
+        const uint32_t cx = (uint32_t)d.probeCounts[0], cy = (uint32_t)d.probeCounts[1], cz = (uint32_t)d.probeCounts[2];
+        const uint64_t irrSlice = (uint64_t)cx * 8 * cz * 8 * 4, distSlice = (uint64_t)cx * 16 * cz * 16 * 4, dataSlice = (uint64_t)cx * cz * 8;
+        if (irradiance_bytes != irrSlice * cy || distance_bytes != distSlice * cy || data_bytes != dataSlice * cy)
+            throw nvrhi::Error("trhost_upload_ddgi_volume: the DDGI texture sizes do not match the probe counts (irradiance 8 x 8 x 4, distance 16 x 16 x 4, data 8 bytes per probe)");
+        Scene::RTDDGIVolume v;                                                // GIRenderer.cpp:129-133 CreateProbeTexture, kProbeTextureFormats
+        v.m_Desc = d;
+        auto make = [&](uint32_t perProbe, nvrhi::Format format, const char* name) {
+            nvrhi::TextureDesc desc;
+            desc.width = cx * perProbe; desc.height = cz * perProbe; desc.arraySize = cy;
+            desc.dimension = nvrhi::kTexture2DArray;
+            desc.format = format;
+            desc.debugName = name;
+            return g_Graphic.m_NVRHIDevice->createTexture(desc);
+        };
+        v.m_ProbeData = make(1, nvrhi::Format::RGBA16_FLOAT, "DDGI Probe Data");
+        v.m_ProbeIrradiance = make(8, nvrhi::Format::R10G10B10A2_UNORM, "DDGI Probe Irradiance");
+        v.m_ProbeDistance = make(16, nvrhi::Format::RG16_FLOAT, "DDGI Probe Distance");
+        nvrhi::BufferDesc bd;
+        bd.byteSize = sizeof d; bd.structStride = sizeof d; bd.debugName = "DDGI Volume Desc";
+        v.m_DescBuffer = g_Graphic.m_NVRHIDevice->createBuffer(bd);
+        nvrhi::throwIfFailed(trhip_buffer_upload(v.m_DescBuffer->native(), 0, &d, sizeof d), "trhost_upload_ddgi_volume");
+        for (uint32_t s = 0; s < cy; ++s) {
+            nvrhi::throwIfFailed(trhip_texture_upload_slice(v.m_ProbeData->native(), s, (const char*)data + s * dataSlice, dataSlice), "trhost_upload_ddgi_volume");
+            nvrhi::throwIfFailed(trhip_texture_upload_slice(v.m_ProbeIrradiance->native(), s, (const char*)irradiance + s * irrSlice, irrSlice), "trhost_upload_ddgi_volume");
+            nvrhi::throwIfFailed(trhip_texture_upload_slice(v.m_ProbeDistance->native(), s, (const char*)distance + s * distSlice, distSlice), "trhost_upload_ddgi_volume");
+        }
+        g_Scene->m_RTDDGIVolume = v;
+    });
+}
+
+int trhost_set_ddgi(int enable)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (enable && !g_Scene->m_RTDDGIVolume.IsValid())
+            throw nvrhi::Error("trhost_set_ddgi: no DDGI volume (trhost_upload_ddgi_volume first): the Ambient term needs its probes");
+        g_Scene->m_bEnableDDGI = enable != 0;
+    });
+}
+
 int trhost_download_lighting_output(uint32_t* words, uint64_t bytes)
 {
     return guarded([&] {
@@ -245,7 +306,7 @@ int trhost_set_post_process(int enable)
         if (enable && !g_Graphic.m_GlobalMaterialDataBuffer) throw nvrhi::Error("trhost_set_post_process: no materials (trhost_load_materials first)");
         if (enable && g_Graphic.m_MaxMeshletGroups > (1u << 18))
             throw nvrhi::Error("trhost_set_post_process: max_meshlet_groups above 2^18 (list positions must stay below 2^23)");
-        if (enable && g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient)
+        if (enable && g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient && !g_Scene->m_RTDDGIVolume.IsValid())
             throw nvrhi::Error("trhost_set_post_process: debug view mode 10 (Ambient) needs the DDGI volume, which deferredlighting_PS_Main_Debug does not have");
         g_Scene->m_bPostProcess = enable != 0;
         if (enable) { g_Scene->m_bDeferredLighting = true; g_Scene->m_bGBuffer = true; g_Scene->m_bVisibilityBuffer = true; g_Scene->m_bRasterDepth = true; }   // implies deferred lighting

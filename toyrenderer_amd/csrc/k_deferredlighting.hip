@@ -1,8 +1,9 @@
 // k_deferredlighting.hip -- "deferredlighting_PS_Main" and "deferredlighting_PS_Main_Debug": the reference's full-screen pass
 // after GBufferRenderer (source/DeferredLightingRenderer.cpp, source/shaders/deferredlighting.hlsl; EvaluateDirectionalLight,
-// DefaultLitBxDF and UnpackGBuffer of lightingcommon.hlsli), WITHOUT DDGI and with the shadow mask as an input: the directional
-// light and the debug views, closed arithmetic on GBufferA, depth, the motion target, the SSAO and the shadow-mask texels.
-// DDGI ambient is out of scope; the sky is k_sky.hip's, the SSAO texture k_ambientocclusion.hip's, the shadow mask
+// DefaultLitBxDF and UnpackGBuffer of lightingcommon.hlsli), with the shadow mask and the DDGI probe volume as inputs: the
+// directional light, the DDGI ambient term and the debug views, closed arithmetic on GBufferA, depth, the motion target, the SSAO
+// and the shadow-mask texels, plus the probe lookups of ddgi_irradiance.hip.h.  Tracing and blending the probes are out of scope
+// (DESIGN.md 12): the volume is supplied.  The sky is k_sky.hip's, the SSAO texture k_ambientocclusion.hip's, the shadow mask
 // k_shadowmask.hip's.
 //
 // WHICH PIXELS: the reference draws where the stencil equals the opaque bit.  The stand-in: a pixel is written iff its depth
@@ -33,7 +34,12 @@
 //             seed = uint(debugValue * 255.0f), three successive QuickRandomFloat; 4 albedo; 5 normal; 6 emissive; 7 metallic;
 //             8 roughness; 9 (float)ssao / 255.0f (unbound: 255); 11 shadowFactor; 12 kLODColors[uint(debugValue * 255.0f)], an
 //             index >= 8 gives (0, 0, 0) (the reference reads past its table there); 13 (motion.x / (float)W, motion.y / (float)H,
-//             0); any other mode (0, 0, 0).  Mode 10 (Ambient) needs the DDGI volume and is refused at record time;
+//             0); any other mode (0, 0, 0).  Mode 10 (Ambient) needs the DDGI volume and is refused at record time without it;
+//   DDGI:     (m_bRTDDGIEnabled in PS_Main, mode 10 in _Debug; the <*, ddgi> instantiations) irr = ddgi::irradiance(worldPosition,
+//             N, m_CameraOrigin), stated in ddgi_irradiance.hip.h and restated in tests/ddgi_ref.c.  PS_Main: ambient = (albedo *
+//             (1 / pi)) * irr per channel (albedo as unpacked, not times 1 - metallic: Diffuse_Lambert(m_Albedo)), then, when
+//             m_SSAOEnabled, ambient * ((float)ssao / 255.0f) (unbound: 255); rgb = the directional light's rgb (emissive
+//             included) + ambient.  Mode 10 stores irr itself;
 //   store:    R11G11B10_FLOAT as in r11g11b10.hip.h; alpha is dropped.
 //
 // KERNEL: one thread per pixel, no LDS.  The depth word is read first and a skipped pixel ends there (sky costs 4 B); a lit
@@ -46,8 +52,16 @@
 // build with approximate division and square root takes 56.0 us: the correctly rounded operations, which the bit-exact bar needs,
 // are 47 us of the 64 us of arithmetic.  The 16 x 4 wave mapping (TR_LIGHTING_TILE_W=16) measures 102.9 us, equal within the
 // spread, so the 64 x 1 row stays.  The debug entry in view 4: 47.6 us.  Code object: PS_Main 27 VGPRs, _Debug 22 VGPRs, 8 waves
-// per SIMD, no scratch, no LDS (-Rpass-analysis=kernel-resource-usage).
+// per SIMD, no scratch, no LDS (-Rpass-analysis=kernel-resource-usage).  The two DDGI instantiations (the 8 probe lookups of
+// ddgi_irradiance.hip.h): <lit, ddgi> 73 VGPRs, 6 waves per SIMD; <debug, ddgi> 71 VGPRs, 7 waves per SIMD; no scratch, no LDS.
+// MEASURED with DDGI (tools/ddgi_cost.py, the same city and call shape, a 26 x 14 x 37 volume, 17.3 MB of probe textures;
+// profiles/ddgi/): <lit, ddgi> 1060.7 us (spread 8.7) against 100.7 us (spread 1.2) for <lit> in the same call and 101.3 us (spread
+// 1.3) for the parent commit's <lit>: the query's about 200 correctly rounded divisions per lit pixel (12 per probe decode UNORM10
+// texels) against the directional light's 17 are the cost; the probe textures stay in L2.
+#include <type_traits>
+
 #include "cull_math.hip.h"
+#include "ddgi_irradiance.hip.h"
 #include "gbuffer_unpack.hip.h"
 #include "r11g11b10.hip.h"
 #include "screen_pass.hip.h"
@@ -73,6 +87,12 @@ struct LightingArgs
     const uint8_t* ssao;                       // R8_UINT or nullptr (255)
     const uint8_t* shadow;                     // R8_UNORM or nullptr (1.0)
     uint32_t* out;                             // R11G11B10_FLOAT
+};
+
+struct LightingDdgiArgs                        // the <*, ddgi> instantiations: the two plain ones keep LightingArgs, byte for byte
+{
+    LightingArgs base;
+    ddgi::Textures probes;
 };
 
 // exp2 for x <= 0; coefficients and error analysis: tests/lighting_ref.c (kExp2C)
@@ -167,9 +187,13 @@ __device__ __forceinline__ cm::F3 debugPixel(const LightingArgs& a, const GBuffe
     }
 }
 
-template <bool DEBUG>
-__global__ __launch_bounds__(sp::kBlock) void lightingKernel(LightingArgs a)
+__device__ __forceinline__ const LightingArgs& plain(const LightingArgs& a) { return a; }
+__device__ __forceinline__ const LightingArgs& plain(const LightingDdgiArgs& a) { return a.base; }
+
+template <bool DEBUG, bool DDGI = false>
+__global__ __launch_bounds__(sp::kBlock) void lightingKernel(std::conditional_t<DDGI, LightingDdgiArgs, LightingArgs> args)
 {
+    const LightingArgs& a = plain(args);
     const uint32_t W = a.k.m_LightingOutputResolution.x, H = a.k.m_LightingOutputResolution.y;
     const sp::Pixel at = sp::pixel<kTileW, kTileH>();
     if (!at.inside(W, H)) return;
@@ -182,7 +206,22 @@ __global__ __launch_bounds__(sp::kBlock) void lightingKernel(LightingArgs a)
     a.out[i] = g.x ^ g.y ^ g.z ^ g.w ^ __builtin_bit_cast(uint32_t, shadow);
 #else
     const GBufferParams p = unpackGBuffer(g);
-    const cm::F3 rgb = DEBUG ? debugPixel(a, p, i, shadow) : litPixel(a, p, at.x, at.y, depth, shadow);
+    cm::F3 rgb = DEBUG ? debugPixel(a, p, i, shadow) : litPixel(a, p, at.x, at.y, depth, shadow);
+    if constexpr (DDGI) {
+        const cm::F3 world = sp::worldPosition(a.k.m_ClipToWorld, at.x, at.y, W, H, depth);
+        const cm::F3 irr = ddgi::irradiance(args.probes, world, p.normal, { a.k.m_CameraOrigin[0], a.k.m_CameraOrigin[1], a.k.m_CameraOrigin[2] });
+        if (DEBUG) {
+            rgb = irr;                                                                             // mode 10, the only one recorded with <debug, ddgi>
+        } else {
+            const float kInvPi = 0x1.45f306p-2f;
+            cm::F3 ambient = { (p.albedo.x * kInvPi) * irr.x, (p.albedo.y * kInvPi) * irr.y, (p.albedo.z * kInvPi) * irr.z };
+            if (a.k.m_SSAOEnabled) {
+                const float ao = cm::div_((float)(a.ssao ? (uint32_t)a.ssao[i] : 255u), 255.0f);
+                ambient = { ambient.x * ao, ambient.y * ao, ambient.z * ao };
+            }
+            rgb = { rgb.x + ambient.x, rgb.y + ambient.y, rgb.z + ambient.z };
+        }
+    }
 #ifdef TR_LIGHTING_EXPERIMENT_TRUNC_STORE       // negative control only (profiles/lighting/): truncation instead of round to nearest even
     auto trunc = [](float v, uint32_t mbits) {
         const uint32_t u = __builtin_bit_cast(uint32_t, v), top = (31u << mbits) - 1u;
@@ -196,6 +235,52 @@ __global__ __launch_bounds__(sp::kBlock) void lightingKernel(LightingArgs a)
 #endif
 }
 
+// The DDGI bindings of either entry: t5 the descriptor, t6..t8 the probe textures, and the descriptor's host copy behind the
+// DeferredLightingConsts in b0.  Everything the kernel's addressing rests on is checked here, against the host copy.
+struct DdgiTexture { uint32_t slot, format, texelsPerProbe; const char* what; };
+constexpr DdgiTexture kDdgiTextures[3] = { { 6, TRHIP_FORMAT_RGBA16_FLOAT, 1, "Texture_SRV t6 = the RGBA16_FLOAT array of probe data" },
+                                           { 7, TRHIP_FORMAT_R10G10B10A2_UNORM, kDDGIIrradianceInteriorTexels + 2, "Texture_SRV t7 = the R10G10B10A2_UNORM array of probe irradiance" },
+                                           { 8, TRHIP_FORMAT_RG16_FLOAT, kDDGIDistanceInteriorTexels + 2, "Texture_SRV t8 = the RG16_FLOAT array of probe distance" } };
+
+int requireDdgi(const trhip::DispatchCtx& ctx, const char* why)
+{
+    const char* name = ctx.shaderName;
+    const uint8_t* block = (const uint8_t*)ctx.constants(0, sizeof(DeferredLightingConsts) + sizeof(DDGIVolumeDesc));
+    trhip_buffer_t* descBuffer = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 5);
+    bool all = block && descBuffer;
+    for (const DdgiTexture& w : kDdgiTextures) all = all && ctx.texture(TRHIP_BIND_TEXTURE_SRV, w.slot);
+    TRHIP_REQUIRE(all, "%s: %s needs the DDGI volume: t5 (the 64-byte DDGIVolumeDesc), t6 (probe data), t7 (probe irradiance), t8 (probe distance) and "
+                       "the descriptor's host copy behind the DeferredLightingConsts in b0 (176 bytes); not all of them are bound", name, why);
+    TRHIP_REQUIRE(descBuffer->byteSize >= sizeof(DDGIVolumeDesc), "%s: t5 holds %llu bytes, the DDGIVolumeDesc is 64", name, (unsigned long long)descBuffer->byteSize);
+    DDGIVolumeDesc D;
+    memcpy(&D, block + sizeof(DeferredLightingConsts), sizeof D);
+    for (int a = 0; a < 3; ++a) {
+        TRHIP_REQUIRE(D.probeCounts[a] >= 1 && D.probeCounts[a] <= (int)kDDGIMaxProbeCount, "%s: DDGIVolumeDesc probeCounts[%d] = %d, not in 1..1024", name, a, D.probeCounts[a]);
+        TRHIP_REQUIRE(D.probeSpacing[a] > 0.0f && D.probeSpacing[a] <= 3.402823466e38f, "%s: DDGIVolumeDesc probeSpacing[%d] = %g is not positive and finite", name, a, (double)D.probeSpacing[a]);
+    }
+    TRHIP_REQUIRE(D.numIrradianceInteriorTexels == kDDGIIrradianceInteriorTexels && D.numDistanceInteriorTexels == kDDGIDistanceInteriorTexels,
+                  "%s: DDGIVolumeDesc interior texel counts %u and %u; the probe tiles have 6 (irradiance) and 14 (distance)", name, D.numIrradianceInteriorTexels, D.numDistanceInteriorTexels);
+    for (const DdgiTexture& w : kDdgiTextures) {
+        const trhip_texture_t* t = ctx.texture(TRHIP_BIND_TEXTURE_SRV, w.slot);
+        TRHIP_REQUIRE(t->format == w.format, "%s: needs %s", name, w.what);
+        TRHIP_REQUIRE(t->arraySize != 0, "%s: needs %s; the texture bound is not an array texture", name, w.what);
+        const uint32_t tw = (uint32_t)D.probeCounts[0] * w.texelsPerProbe, th = (uint32_t)D.probeCounts[2] * w.texelsPerProbe;
+        TRHIP_REQUIRE(t->width == tw && t->height == th && t->arraySize == (uint32_t)D.probeCounts[1], "%s: %s is %ux%u with %u slices; probeCounts (%d, %d, %d) need %ux%u with %d slices", name, w.what,
+                      t->width, t->height, t->arraySize, D.probeCounts[0], D.probeCounts[1], D.probeCounts[2], tw, th, D.probeCounts[1]);
+    }
+    return TRHIP_OK;
+}
+
+void bindDdgi(const trhip::DispatchCtx& ctx, ddgi::Textures& p)
+{
+    const trhip_texture_t* data = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 6), * irr = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 7), * dist = ctx.texture(TRHIP_BIND_TEXTURE_SRV, 8);
+    p.desc = (const DDGIVolumeDesc*)ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, 5)->ptr;
+    p.data = (const uint2*)data->ptr; p.irradiance = (const uint32_t*)irr->ptr; p.distance = (const uint32_t*)dist->ptr;
+    p.dataW = data->width; p.dataH = data->height; p.irrW = irr->width; p.irrH = irr->height; p.distW = dist->width; p.distH = dist->height;
+    p.slices = data->arraySize;
+    p.dataPitch = (uint32_t)(data->slicePitch / data->texelBytes); p.irrPitch = (uint32_t)(irr->slicePitch / irr->texelBytes); p.distPitch = (uint32_t)(dist->slicePitch / dist->texelBytes);
+}
+
 // Records either entry: validates the bindings and emits one direct dispatch.
 template <bool DEBUG>
 int recordLighting(trhip::DispatchCtx& ctx)
@@ -203,8 +288,12 @@ int recordLighting(trhip::DispatchCtx& ctx)
     const char* name = ctx.shaderName;
     const DeferredLightingConsts* k = (const DeferredLightingConsts*)ctx.constants(0, sizeof(DeferredLightingConsts));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (DeferredLightingConsts, 112 bytes) missing", name);
-    TRHIP_REQUIRE(!k->m_bRTDDGIEnabled, "%s: m_bRTDDGIEnabled is set: DDGI ambient is not built", name);
-    TRHIP_REQUIRE(k->m_DebugMode != kDeferredLightingDebugMode_Ambient, "%s: m_DebugMode 10 (Ambient) needs the DDGI volume, which is not built", name);
+    // The flag or mode 10 at either entry needs the whole volume bound and valid; PS_Main then evaluates it with the flag, _Debug
+    // in mode 10.  With neither, t5..t8 are accepted and ignored.
+    const bool ambientView = k->m_DebugMode == kDeferredLightingDebugMode_Ambient;
+    if (k->m_bRTDDGIEnabled || ambientView)
+        if (const int rc = requireDdgi(ctx, k->m_bRTDDGIEnabled ? "m_bRTDDGIEnabled is set and" : "m_DebugMode 10 (Ambient)")) return rc;
+    const bool wantDdgi = DEBUG ? ambientView : k->m_bRTDDGIEnabled != 0;
     const uint32_t W = k->m_LightingOutputResolution.x, H = k->m_LightingOutputResolution.y;
     TRHIP_REQUIRE(W && H, "%s: m_LightingOutputResolution %ux%u is empty", name, W, H);
     if (const int rc = sp::requireCover(ctx, sp::kGroupSide, sp::kGroupSide, W, H)) return rc;
@@ -224,6 +313,13 @@ int recordLighting(trhip::DispatchCtx& ctx)
     a.ssao = tex[3] ? (const uint8_t*)tex[3]->ptr : nullptr;
     a.shadow = tex[4] ? (const uint8_t*)tex[4]->ptr : nullptr;
     a.out = (uint32_t*)tex[5]->ptr;
+    if (wantDdgi) {
+        LightingDdgiArgs d = sp::zeroed<LightingDdgiArgs>();
+        d.base = a;
+        bindDdgi(ctx, d.probes);
+        sp::launch(ctx, lightingKernel<DEBUG, true>, DEBUG ? "lightingKernel<debug, ddgi>" : "lightingKernel<lit, ddgi>", sp::tiles(W, H, kTileW, kTileH), dim3(kTileW, kTileH), d);
+        return TRHIP_OK;
+    }
     sp::launch(ctx, lightingKernel<DEBUG>, DEBUG ? "lightingKernel<debug>" : "lightingKernel<lit>", sp::tiles(W, H, kTileW, kTileH), dim3(kTileW, kTileH), a);
     return TRHIP_OK;
 }

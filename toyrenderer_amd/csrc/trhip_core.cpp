@@ -487,28 +487,39 @@ void trhip_buffer_release(trhip_buffer b)
 void* trhip_buffer_device_ptr(trhip_buffer b) { return b ? b->ptr : nullptr; }
 uint64_t trhip_buffer_size(trhip_buffer b) { return b ? b->byteSize : 0; }
 
-int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_texture* out)
+// arraySize 0: a plain texture (trhip_texture_create); >= 1: a 2D array of that many slices (trhip_texture_create_array)
+static int createTexture(trhip_device dev, const trhip_texture_desc* d, uint32_t arraySize, trhip_texture* out)
 {
-    if (!dev || !d || !out) return fail(TRHIP_ERR_INVALID, "texture_create: null argument");
     if (d->width == 0 || d->height == 0 || d->mipLevels == 0 || d->mipLevels > 16)
         return fail(TRHIP_ERR_INVALID, "texture_create: bad dimensions %ux%u mips %u", d->width, d->height, d->mipLevels);
-    if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && d->format != TRHIP_FORMAT_RGBA8_UNORM && d->format != TRHIP_FORMAT_SRGBA8_UNORM)
+    if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && (d->format < TRHIP_FORMAT_RGBA8_UNORM || d->format > TRHIP_FORMAT_RGBA16_FLOAT))
         return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u", d->format);
     const bool bloomChain = d->format == TRHIP_FORMAT_R11G11B10_FLOAT && (d->isUAV & TRHIP_TEXTURE_RENDER_TARGET);   // the bloom texture (BloomRenderer.cpp:41-50)
     const bool sampledChain = (d->format == TRHIP_FORMAT_RGBA8_UNORM || d->format == TRHIP_FORMAT_SRGBA8_UNORM) && d->isUAV == 0;   // a material texture
     if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && !bloomChain && !sampledChain && d->mipLevels != 1)
-        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT textures and RGBA8_UNORM / SRGBA8_UNORM textures that a pass writes have one mip, got %u", d->mipLevels);
+        return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT / R10G10B10A2_UNORM / RGBA16_FLOAT textures and RGBA8_UNORM / SRGBA8_UNORM textures that a pass writes have one mip, got %u", d->mipLevels);
+    if (arraySize) {
+        if (arraySize > 2048) return fail(TRHIP_ERR_INVALID, "texture_create_array: %u slices, at most 2048", arraySize);
+        if (d->format != TRHIP_FORMAT_R10G10B10A2_UNORM && d->format != TRHIP_FORMAT_RG16_FLOAT && d->format != TRHIP_FORMAT_RGBA16_FLOAT)
+            return fail(TRHIP_ERR_INVALID, "texture_create_array: format %u; an array texture is R10G10B10A2_UNORM, RG16_FLOAT or RGBA16_FLOAT", d->format);
+        if (d->mipLevels != 1) return fail(TRHIP_ERR_INVALID, "texture_create_array: an array texture has one mip, got %u", d->mipLevels);
+    }
     auto t = std::make_unique<trhip_texture_t>();
     t->dev = dev;
     t->width = d->width; t->height = d->height; t->mips = d->mipLevels; t->format = d->format;
-    t->texelBytes = d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT ? 8 : d->format == TRHIP_FORMAT_RGBA32_UINT ? 16 :
-                    d->format == TRHIP_FORMAT_R8_UNORM || d->format == TRHIP_FORMAT_R8_UINT ? 1 : 4;
+    t->texelBytes = d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT || d->format == TRHIP_FORMAT_RGBA16_FLOAT ? 8 :
+                    d->format == TRHIP_FORMAT_RGBA32_UINT ? 16 : d->format == TRHIP_FORMAT_R8_UNORM || d->format == TRHIP_FORMAT_R8_UINT ? 1 : 4;
     t->isUAV = d->isUAV != 0; t->isVirtual = d->isVirtual != 0;
     t->name = d->debugName ? d->debugName : "";
     uint64_t off = 0;
     for (uint32_t k = 0; k < t->mips; ++k) {
         t->mipOffset[k] = off;
         off += ((uint64_t)t->mipW(k) * t->mipH(k) * t->texelBytes + 255) & ~uint64_t(255);
+    }
+    if (arraySize) {                               // one mip: `off` is the 256-byte aligned size of a slice
+        t->arraySize = arraySize;
+        t->slicePitch = off;
+        off *= arraySize;
     }
     t->totalBytes = off;
     if (!t->isVirtual) {
@@ -519,6 +530,22 @@ int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_te
     *out = t.release();
     return TRHIP_OK;
 }
+
+int trhip_texture_create(trhip_device dev, const trhip_texture_desc* d, trhip_texture* out)
+{
+    if (!dev || !d || !out) return fail(TRHIP_ERR_INVALID, "texture_create: null argument");
+    return createTexture(dev, d, 0, out);
+}
+
+int trhip_texture_create_array(trhip_device dev, const trhip_texture_desc* d, uint32_t arraySize, trhip_texture* out)
+{
+    if (!dev || !d || !out) return fail(TRHIP_ERR_INVALID, "texture_create_array: null argument");
+    if (arraySize == 0) return fail(TRHIP_ERR_INVALID, "texture_create_array: an array texture has at least one slice");
+    return createTexture(dev, d, arraySize, out);
+}
+
+uint32_t trhip_texture_array_size(trhip_texture t) { return t ? t->arraySize : 0; }
+uint64_t trhip_texture_slice_pitch(trhip_texture t) { return t ? t->slicePitch : 0; }
 
 int trhip_texture_memory_requirements(trhip_texture t, uint64_t* size, uint64_t* alignment)
 {
@@ -611,6 +638,7 @@ int trhip_texture_upload(trhip_texture t, uint32_t mip, const void* src, uint64_
 {
     if (!t || !src || mip >= t->mips) return fail(TRHIP_ERR_INVALID, "texture_upload: bad argument");
     if (!t->ptr) return fail(TRHIP_ERR_STATE, "texture_upload(%s): no memory bound", t->name.c_str());
+    if (t->arraySize) return fail(TRHIP_ERR_INVALID, "texture_upload(%s): an array texture is uploaded per slice (trhip_texture_upload_slice)", t->name.c_str());
     uint64_t need = (uint64_t)t->mipW(mip) * t->mipH(mip) * t->texelBytes;
     if (bytes != need) return fail(TRHIP_ERR_INVALID, "texture_upload(%s): mip %u is %llu bytes, got %llu", t->name.c_str(), mip, (unsigned long long)need, (unsigned long long)bytes);
     int rc = syncCopy(t->dev, t->mipPtr(mip), src, bytes, hipMemcpyHostToDevice);
@@ -622,9 +650,36 @@ int trhip_texture_download(trhip_texture t, uint32_t mip, void* dst, uint64_t by
 {
     if (!t || !dst || mip >= t->mips) return fail(TRHIP_ERR_INVALID, "texture_download: bad argument");
     if (!t->ptr) return fail(TRHIP_ERR_STATE, "texture_download(%s): no memory bound", t->name.c_str());
+    if (t->arraySize) return fail(TRHIP_ERR_INVALID, "texture_download(%s): an array texture is downloaded per slice (trhip_texture_download_slice)", t->name.c_str());
     uint64_t need = (uint64_t)t->mipW(mip) * t->mipH(mip) * t->texelBytes;
     if (bytes != need) return fail(TRHIP_ERR_INVALID, "texture_download(%s): mip %u is %llu bytes, got %llu", t->name.c_str(), mip, (unsigned long long)need, (unsigned long long)bytes);
     return syncCopy(t->dev, dst, t->mipPtr(mip), bytes, hipMemcpyDeviceToHost);
+}
+
+static int sliceRange(trhip_texture t, uint32_t slice, uint64_t bytes, const char* what)
+{
+    if (!t->arraySize) return fail(TRHIP_ERR_INVALID, "%s(%s): not an array texture", what, t->name.c_str());
+    if (slice >= t->arraySize) return fail(TRHIP_ERR_INVALID, "%s(%s): slice %u, the texture has %u", what, t->name.c_str(), slice, t->arraySize);
+    if (!t->ptr) return fail(TRHIP_ERR_STATE, "%s(%s): no memory bound", what, t->name.c_str());
+    const uint64_t need = (uint64_t)t->width * t->height * t->texelBytes;
+    if (bytes != need) return fail(TRHIP_ERR_INVALID, "%s(%s): a slice is %llu bytes, got %llu", what, t->name.c_str(), (unsigned long long)need, (unsigned long long)bytes);
+    return TRHIP_OK;
+}
+
+int trhip_texture_upload_slice(trhip_texture t, uint32_t slice, const void* src, uint64_t bytes)
+{
+    if (!t || !src) return fail(TRHIP_ERR_INVALID, "texture_upload_slice: null argument");
+    if (const int rc = sliceRange(t, slice, bytes, "texture_upload_slice")) return rc;
+    const int rc = syncCopy(t->dev, (char*)t->ptr + slice * t->slicePitch, src, bytes, hipMemcpyHostToDevice);
+    t->version.fetch_add(1);
+    return rc;
+}
+
+int trhip_texture_download_slice(trhip_texture t, uint32_t slice, void* dst, uint64_t bytes)
+{
+    if (!t || !dst) return fail(TRHIP_ERR_INVALID, "texture_download_slice: null argument");
+    if (const int rc = sliceRange(t, slice, bytes, "texture_download_slice")) return rc;
+    return syncCopy(t->dev, dst, (char*)t->ptr + slice * t->slicePitch, bytes, hipMemcpyDeviceToHost);
 }
 
 // ---- texture table ---------------------------------------------------------------------------------
@@ -705,6 +760,7 @@ int trhip_texture_table_set(trhip_texture_table t, uint32_t index, trhip_texture
     if (tex->dev != t->dev) return fail(TRHIP_ERR_INVALID, "texture_table_set(%s): the texture belongs to another device", tex->name.c_str());
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "texture_table_set(%s): no memory bound", tex->name.c_str());
     if (tex->totalBytes / 4u > 0xFFFFFFFFull) return fail(TRHIP_ERR_INVALID, "texture_table_set(%s): more than 2^32 texels", tex->name.c_str());
+    if (tex->arraySize) return fail(TRHIP_ERR_INVALID, "texture_table_set(%s): an array texture cannot be a table entry", tex->name.c_str());
     return tableWrite(t, index, tex);
 }
 
@@ -803,6 +859,8 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_R10G10B10A2_UNORM || tex->format == TRHIP_FORMAT_RGBA16_FLOAT)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): an R10G10B10A2_UNORM / RGBA16_FLOAT texture has no clear: the DDGI probe textures are uploaded", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RG32_UINT || tex->format == TRHIP_FORMAT_RGBA32_UINT || tex->format == TRHIP_FORMAT_R8_UINT)
         return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): RG32_UINT / RGBA32_UINT / R8_UINT are cleared with clear_texture_u32", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RGBA8_UNORM || tex->format == TRHIP_FORMAT_SRGBA8_UNORM)
@@ -842,6 +900,8 @@ int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t va
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RGBA8_UNORM || tex->format == TRHIP_FORMAT_SRGBA8_UNORM)
         return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): an RGBA8_UNORM / SRGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
+    if (tex->format == TRHIP_FORMAT_R10G10B10A2_UNORM || tex->format == TRHIP_FORMAT_RGBA16_FLOAT)
+        return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): an R10G10B10A2_UNORM / RGBA16_FLOAT texture has no clear: the DDGI probe textures are uploaded", tex->name.c_str());
     if (tex->format != TRHIP_FORMAT_RG32_UINT && tex->format != TRHIP_FORMAT_RGBA32_UINT && tex->format != TRHIP_FORMAT_R8_UINT)
         return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): needs an RG32_UINT, RGBA32_UINT or R8_UINT texture", tex->name.c_str());
     void* p = tex->ptr;
@@ -887,7 +947,7 @@ int trhip_cmd_copy_texture(trhip_cmdlist cl, trhip_texture dst, trhip_texture sr
     TRHIP_RECORDING(cl);
     if (!dst || !src) return fail(TRHIP_ERR_INVALID, "copy_texture: null texture");
     if (!dst->ptr || !src->ptr) return fail(TRHIP_ERR_STATE, "copy_texture: a texture has no memory bound");
-    if (dst->width != src->width || dst->height != src->height || dst->mips != src->mips || dst->format != src->format)
+    if (dst->width != src->width || dst->height != src->height || dst->mips != src->mips || dst->format != src->format || dst->arraySize != src->arraySize)
         return fail(TRHIP_ERR_INVALID, "copy_texture(%s <- %s): descriptions differ", dst->name.c_str(), src->name.c_str());
     void* d = dst->ptr;
     const void* sp = src->ptr;
@@ -927,6 +987,10 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
             if (!t) return fail(TRHIP_ERR_INVALID, "dispatch(%s): binding %u has no texture", name, i);
             if (!t->ptr) return fail(TRHIP_ERR_STATE, "dispatch(%s): texture '%s' has no memory bound", name, t->name.c_str());
             if (b[i].type == TRHIP_BIND_TEXTURE_UAV && b[i].baseMip >= t->mips) return fail(TRHIP_ERR_INVALID, "dispatch(%s): UAV mip %u out of range", name, b[i].baseMip);
+            // the only pass that declares Texture2DArray bindings: the lighting pass's DDGI probe textures
+            if (t->arraySize && !(b[i].type == TRHIP_BIND_TEXTURE_SRV && b[i].slot >= 6u && b[i].slot <= 8u && strncmp(name, "deferredlighting_PS_Main", 24) == 0))
+                return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: only deferredlighting_PS_Main and deferredlighting_PS_Main_Debug declare array textures, at t6..t8",
+                            name, t->name.c_str(), b[i].type == TRHIP_BIND_TEXTURE_UAV ? 'u' : 't', b[i].slot);
             cl->hold(t, b[i].type == TRHIP_BIND_TEXTURE_UAV);
             break; }
         case TRHIP_BIND_TEXTURE_TABLE: {

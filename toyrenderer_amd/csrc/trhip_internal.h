@@ -171,6 +171,10 @@ struct trhip_texture_t
     uint32_t width = 0, height = 0, mips = 0, format = 0;
     uint32_t texelBytes = 0;
     bool isUAV = false, isVirtual = false;
+    // A 2D ARRAY texture (trhip_texture_create_array): arraySize slices of one mip, slice k at byte k * slicePitch (256-byte
+    // aligned).  0: not an array.  Only "deferredlighting_PS_Main" / "_Debug" take one, at t6..t8 (recordDispatch refuses the rest).
+    uint32_t arraySize = 0;
+    uint64_t slicePitch = 0;
     std::string name;
     uint64_t mipOffset[16] = {};
     uint64_t totalBytes = 0;

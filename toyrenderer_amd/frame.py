@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import accel as accelmod
+from . import ddgi as ddgimod
 from . import gtao as gtaomod
 from . import interop as I
 from . import rhi
@@ -158,7 +159,7 @@ class FrameDriver:
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
                  bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
-                 shadows=None, alpha_test: bool = False):
+                 shadows=None, alpha_test: bool = False, ddgi=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -207,8 +208,8 @@ class FrameDriver:
         and max(1, denoise_passes) "ambientocclusion_CS_XeGTAO_Denoise" dispatches ping-ponging between the working term and
         self.ssao_texture, the last with m_FinalApply = 1; as in the reference, with 2 passes the finally-applied image lands in
         the working term and self.ssao_texture holds the first pass's output.  With lighting the texture is the lighting pass's
-        t3 and m_SSAOEnabled is 1; only debug view 9 shows it (the non-debug pass multiplies the DDGI ambient term by it, and that
-        term is not built), so LightingOutput without a debug view does not change.  self.frame_counter (0; the caller may set it
+        t3 and m_SSAOEnabled is 1; debug view 9 shows it, and the non-debug pass multiplies the DDGI ambient term by it: with
+        ddgi= the texture changes LightingOutput, without it (no ambient term) it does not.  self.frame_counter (0; the caller may set it
         before record()) feeds NoiseIndex as g_Graphic.m_FrameCounter % 256 does; self.gtao_consts holds the 96-byte GTAOConstants
         of the last record(); download_ssao() reads self.ssao_texture back.
         shadows: None (the default) changes nothing.  A dict of settings: soft (True), sun_angular_diameter (0.533 degrees),
@@ -228,7 +229,13 @@ class FrameDriver:
         "basepass_MS_Main_visibility ALPHA_MASK_MODE=1" with the materials at t3 and, when a loaded material uses a texture, the
         texture table at t19: a sample whose m_ConstAlbedo.w times the albedo texture's alpha is below m_AlphaCutoff is not drawn,
         so depth, the HZB, the visibility buffer and everything resolved from it see through the cut-outs.  With shadows the
-        trace binds the table too and a textured cut-out casts the shadow of its kept texels (mip 0)."""
+        trace binds the table too and a textured cut-out casts the shadow of its kept texels (mip 0).
+        ddgi: None (the default) changes nothing: no ambient term, and debug_mode 10 (Ambient) is refused.  A ddgi.Volume (needs
+        lighting=True): the DDGI ambient term from a SUPPLIED probe volume (deferredlighting.hlsl:49-76; tracing and blending
+        the probes is not built, the caller fills the volume, e.g. ddgi.Volume.uniform).  The driver uploads the descriptor and
+        the three array textures at construction (self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance),
+        binds them as the lighting pass's t5..t8 with the linear wrap sampler, sets m_bRTDDGIEnabled = 1 and appends the
+        descriptor's host copy to the constant block; debug_mode 10 then shows the irradiance."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -236,8 +243,13 @@ class FrameDriver:
             raise ValueError(("post-processing" if post else "deferred lighting" if lighting else "G-buffer" if gbuffer else "visibility buffer") + " with a shard exchange: list positions are per rank, not global")
         if gbuffer and scene.materials is None:
             raise ValueError(("post=True" if post else "lighting=True" if lighting else "gbuffer=True") + " needs GpuScene.set_materials()")
-        if lighting and int(debug_mode) == I.kDeferredLightingDebugMode_Ambient:
-            raise ValueError("debug_mode 10 (Ambient) needs the DDGI volume, which is not built")
+        if lighting and int(debug_mode) == I.kDeferredLightingDebugMode_Ambient and ddgi is None:
+            raise ValueError("debug_mode 10 (Ambient) needs the DDGI volume: pass ddgi=ddgi.Volume(...)")
+        if ddgi is not None and not lighting:
+            raise ValueError("ddgi=... needs lighting=True: the lighting pass is what reads the probe volume")
+        if ddgi is not None and not isinstance(ddgi, ddgimod.Volume):
+            raise ValueError("ddgi: needs a ddgi.Volume")
+        self.ddgi = ddgi
         self.alpha_test = bool(alpha_test)
         if self.alpha_test and not (raster_depth or visibility):
             raise ValueError("alpha_test=True needs raster_depth=True (or visibility, gbuffer, lighting, post): the test runs in the rasters, and a frame without them draws nothing")
@@ -346,6 +358,9 @@ class FrameDriver:
             self.shadow_mask = self.shadow_mask_texture      # what the lighting pass binds as t4
         if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
+        self.ddgi_desc = self.ddgi_data = self.ddgi_irradiance = self.ddgi_distance = None
+        if self.ddgi is not None:                    # GIRenderer::Setup's textures (GIRenderer.cpp:129-133), filled by the caller
+            self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance = self.ddgi.upload(dev)
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
             self.gbufferA = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA32_UINT, "GBufferA")
         if self.visibility_on:                       # GBufferRenderer's visibility buffer + GBufferMotion, render resolution
@@ -509,13 +524,19 @@ class FrameDriver:
         k["m_DirectionalLightVector"] = self.dir_light[0]
         k["m_DirectionalLightStrength"] = self.dir_light[1]
         k["m_LightingOutputResolution"] = (v.renderW, v.renderH)
+        k["m_bRTDDGIEnabled"] = int(self.ddgi is not None)                               # IsDDGIEnabled() (DeferredLightingRenderer.cpp:72)
         return k
 
     def _deferred_lighting(self, cl):
         v = self.view
         self.lighting_consts = self._lighting_consts()
-        cb = cl.constant_buffer(self.lighting_consts, "DeferredLightingConsts")
+        block = self.lighting_consts
+        if self.ddgi is not None:                    # the descriptor's host copy: the constant block's second member (include/trhip.h)
+            block = np.frombuffer(self.lighting_consts.tobytes() + self.ddgi.desc().tobytes(), np.uint8)
+        cb = cl.constant_buffer(block, "DeferredLightingConsts")
         b = [CB(0, cb), TEX_SRV(0, self.gbufferA), TEX_SRV(1, self.motion), TEX_SRV(2, self.depth), TEX_UAV(0, self.lighting_output, 0), SAMPLER(0), SAMPLER(1)]
+        if self.ddgi is not None:
+            b += [SRV(5, self.ddgi_desc), TEX_SRV(6, self.ddgi_data), TEX_SRV(7, self.ddgi_irradiance), TEX_SRV(8, self.ddgi_distance)]
         if self.ssao is not None:
             b.append(TEX_SRV(3, self.ssao))
         if self.shadow_mask is not None:
@@ -759,6 +780,6 @@ class FrameDriver:
         self.hzb.release(); self.depth.release()
         for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
                   self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
-                  self.blue_noise):
+                  self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance):
             if t is not None:
                 t.release()

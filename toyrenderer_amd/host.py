@@ -29,7 +29,7 @@ HOST_SYMBOLS = [
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
-    "trhost_get_deferred_lighting_consts",
+    "trhost_get_deferred_lighting_consts", "trhost_upload_ddgi_volume", "trhost_set_ddgi",
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
@@ -104,6 +104,8 @@ def load() -> C.CDLL:
     L.trhost_upload_shadow_mask.argtypes = [vp, u64]
     L.trhost_download_lighting_output.argtypes = [vp, u64]
     L.trhost_get_deferred_lighting_consts.argtypes = [vp]
+    L.trhost_upload_ddgi_volume.argtypes = [vp, vp, u64, vp, u64, vp, u64]
+    L.trhost_set_ddgi.argtypes = [C.c_int]
     L.trhost_set_post_process.argtypes = [C.c_int]
     L.trhost_set_exposure.argtypes = [C.c_float, C.c_float]
     L.trhost_set_auto_exposure.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -352,6 +354,19 @@ class Renderer:
         k = np.zeros(1, I.DeferredLightingConsts)
         _check(load().trhost_get_deferred_lighting_consts(k.ctypes.data))
         return k
+
+    def upload_ddgi_volume(self, volume):
+        """A ddgi.Volume (descriptor and the three probe textures) as the lighting pass's t5..t8; None drops it (include/trhost.h)."""
+        if volume is None:
+            _check(load().trhost_upload_ddgi_volume(None, None, 0, None, 0, None, 0))
+            return
+        d = np.ascontiguousarray(volume.desc())
+        irr, dist, data = (np.ascontiguousarray(a) for a in (volume.irradiance, volume.distance, volume.data))
+        _check(load().trhost_upload_ddgi_volume(d.ctypes.data, irr.ctypes.data, irr.nbytes, dist.ctypes.data, dist.nbytes, data.ctypes.data, data.nbytes))
+
+    def set_ddgi(self, on: bool = True):
+        """Scene::IsDDGIEnabled(): the ambient term from the uploaded volume (needs upload_ddgi_volume)."""
+        _check(load().trhost_set_ddgi(int(on)))
 
     def set_post_process(self, on: bool = True):
         """AdaptLuminanceRenderer and PostProcessRenderer after DeferredLightingRenderer (implies deferred lighting; include/trhost.h)."""

@@ -23,7 +23,7 @@ kMaterialFlagAnyTexture = 0xF
 kDeferredLightingDebugMode_ColorizeInstances = 2            # ShaderInterop.h:27-37: the views that write GBufferA's debug byte
 kDeferredLightingDebugMode_ColorizeMeshlets = 3
 kDeferredLightingDebugMode_MeshLOD = 12
-kDeferredLightingDebugMode_Ambient = 10                     # needs the DDGI volume: refused by the lighting pass
+kDeferredLightingDebugMode_Ambient = 10                     # needs the DDGI volume: refused by the lighting pass without one
 
 BasePassInstanceConstants = np.dtype([
     ("m_WorldMatrix", np.float32, (4, 4)), ("m_PrevWorldMatrix", np.float32, (4, 4)),
@@ -109,6 +109,12 @@ kAccelInner = 0xFFFFFFFF
 kTLASInstanceForceOpaque, kTLASInstanceForceNonOpaque = 1, 2
 kBlueNoiseSize = 128
 kDeferredLightingDebugMode_ShadowMask = 11
+# csrc/ShaderInterop.h: the project's own 64-byte DDGI volume descriptor ("deferredlighting_PS_Main" t5)
+DDGIVolumeDesc = np.dtype([("origin", np.float32, (3,)), ("probeNormalBias", np.float32), ("probeSpacing", np.float32, (3,)), ("probeViewBias", np.float32),
+                           ("probeCounts", np.int32, (3,)), ("probeIrradianceEncodingGamma", np.float32), ("numIrradianceInteriorTexels", np.uint32),
+                           ("numDistanceInteriorTexels", np.uint32), ("flags", np.uint32), ("pad", np.uint32)])
+kDDGIFlag_Relocation, kDDGIFlag_Classification = 1, 2
+kDDGIIrradianceInteriorTexels, kDDGIDistanceInteriorTexels, kDDGIMaxProbeCount = 6, 14, 1024
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
@@ -118,7 +124,7 @@ SIZES = {
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
     "BloomConsts": 16, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
     "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
-    "ShadowMaskConsts": 112, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
+    "ShadowMaskConsts": 112, "DDGIVolumeDesc": 64, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)

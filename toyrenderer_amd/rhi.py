@@ -23,6 +23,8 @@ FORMAT_R8_UNORM = 7       # shadow mask: one byte per texel
 FORMAT_R8_UINT = 8        # SSAO texture: one byte per texel
 FORMAT_RGBA8_UNORM = 10   # back buffer: one u32 per texel, R in the low byte (9 is not a format)
 FORMAT_SRGBA8_UNORM = 11  # RGBA8_UNORM's layout; R, G, B decoded through the sRGB transfer function when sampled
+FORMAT_R10G10B10A2_UNORM = 12  # DDGI probe irradiance: one u32 per texel, R bits 0-9, G 10-19, B 20-29, A 30-31
+FORMAT_RGBA16_FLOAT = 13  # DDGI probe data: four fp16 per texel
 
 TEXTURE_RENDER_TARGET = 2   # or'ed into trhip_texture_desc.isUAV
 
@@ -40,6 +42,7 @@ ABI_SYMBOLS = [
     "trhip_texture_create", "trhip_texture_memory_requirements", "trhip_texture_bind_memory", "trhip_texture_retain",
     "trhip_texture_release", "trhip_texture_device_ptr", "trhip_texture_mip_info", "trhip_texture_size",
     "trhip_buffer_upload", "trhip_buffer_download", "trhip_texture_upload", "trhip_texture_download",
+    "trhip_texture_create_array", "trhip_texture_array_size", "trhip_texture_slice_pitch", "trhip_texture_upload_slice", "trhip_texture_download_slice",
     "trhip_buffer_mark_written", "trhip_texture_mark_written",
     "trhip_texture_table_create", "trhip_texture_table_retain", "trhip_texture_table_release", "trhip_texture_table_capacity",
     "trhip_texture_table_set", "trhip_texture_table_clear", "trhip_srgb_table",
@@ -157,6 +160,14 @@ def load() -> C.CDLL:
     L.trhip_buffer_download.argtypes = [vp, u64, vp, u64]
     L.trhip_texture_upload.argtypes = [vp, u32, vp, u64]
     L.trhip_texture_download.argtypes = [vp, u32, vp, u64]
+    if hasattr(L, "trhip_texture_create_array"):             # absent from an older build named by TRHIP_LIB (see above)
+        L.trhip_texture_create_array.argtypes = [vp, C.POINTER(TextureDesc), u32, C.POINTER(vp)]
+        L.trhip_texture_array_size.argtypes = [vp]
+        L.trhip_texture_array_size.restype = u32
+        L.trhip_texture_slice_pitch.argtypes = [vp]
+        L.trhip_texture_slice_pitch.restype = u64
+        L.trhip_texture_upload_slice.argtypes = [vp, u32, vp, u64]
+        L.trhip_texture_download_slice.argtypes = [vp, u32, vp, u64]
     L.trhip_cmd_create.argtypes = [vp, C.POINTER(vp)]
     L.trhip_cmd_open.argtypes = [vp]
     L.trhip_cmd_close.argtypes = [vp]
@@ -262,8 +273,9 @@ class Buffer:
 
 
 class Texture:
-    def __init__(self, dev: "Device", handle, w: int, h: int, mips: int, fmt: int, name: str):
+    def __init__(self, dev: "Device", handle, w: int, h: int, mips: int, fmt: int, name: str, array_size: int = 0):
         self.dev, self.h, self.w, self.hgt, self.mips, self.format, self.name = dev, handle, w, h, mips, fmt, name
+        self.array_size = array_size            # 0: not an array texture (trhip_texture_create_array)
 
     def mip_dims(self, k: int):
         return max(self.w >> k, 1), max(self.hgt >> k, 1)
@@ -271,10 +283,24 @@ class Texture:
     def _dtype(self):
         return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32,
                 FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8, FORMAT_RGBA8_UNORM: np.uint32,
-                FORMAT_SRGBA8_UNORM: np.uint32}.get(self.format, np.float32)
+                FORMAT_SRGBA8_UNORM: np.uint32, FORMAT_R10G10B10A2_UNORM: np.uint32, FORMAT_RGBA16_FLOAT: np.float16}.get(self.format, np.float32)
 
     def _shape(self, mw: int, mh: int):
-        return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw, 4) if self.format == FORMAT_RGBA32_UINT else (mh, mw)
+        return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw, 4) if self.format in (FORMAT_RGBA32_UINT, FORMAT_RGBA16_FLOAT) else (mh, mw)
+
+    def upload_slice(self, k: int, arr: np.ndarray):
+        """Slice k of an array texture (trhip_texture_upload_slice)."""
+        arr = np.ascontiguousarray(arr, self._dtype())
+        _check(load().trhip_texture_upload_slice(self.h, k, arr.ctypes.data, arr.nbytes))
+
+    def download_slice(self, k: int) -> np.ndarray:
+        out = np.empty(self._shape(self.w, self.hgt), self._dtype())
+        _check(load().trhip_texture_download_slice(self.h, k, out.ctypes.data, out.nbytes))
+        return out
+
+    @property
+    def slice_pitch(self) -> int:
+        return int(load().trhip_texture_slice_pitch(self.h))
 
     def upload_mip(self, k: int, arr: np.ndarray):
         if self.format in (FORMAT_RGBA8_UNORM, FORMAT_SRGBA8_UNORM) and np.asarray(arr).dtype == np.uint8:   # [h, w, 4] bytes R, G, B, A
@@ -494,6 +520,13 @@ class Device:
         hd = C.c_void_p()
         _check(load().trhip_texture_create(self.h, C.byref(d), C.byref(hd)))
         return Texture(self, hd, w, h, mips, fmt, name)
+
+    def create_texture_array(self, w: int, h: int, slices: int, fmt: int, name="", uav=False) -> Texture:
+        """trhip_texture_create_array: `slices` slices of w x h, one mip; R10G10B10A2_UNORM, RG16_FLOAT or RGBA16_FLOAT."""
+        d = TextureDesc(w, h, 1, fmt, int(bool(uav)), 0, name.encode())
+        hd = C.c_void_p()
+        _check(load().trhip_texture_create_array(self.h, C.byref(d), slices, C.byref(hd)))
+        return Texture(self, hd, w, h, 1, fmt, name, array_size=slices)
 
     def create_texture_table(self, capacity: int) -> TextureTable:
         h = C.c_void_p()
