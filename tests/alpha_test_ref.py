@@ -4,40 +4,33 @@ with textured alpha (trace).
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 import material_textures_ref as MT
+from ref_build import compile_ref
 import shadowmask_ref as SR
 from toyrenderer_amd import accel
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 F = np.float32
-_LIB = {}
 Texture = MT.Texture
 
 
+def _declare(lib):
+    vp, u32, i64 = C.c_void_p, C.c_uint32, C.c_int64
+    lib.at_sample_alpha.argtypes = [vp, C.c_int, vp, vp, vp]
+    lib.at_sample_alpha.restype = C.c_float
+    lib.at_alpha_level0.argtypes = [vp, C.c_int, C.c_float, C.c_float]
+    lib.at_alpha_level0.restype = C.c_float
+    lib.at_raster.argtypes = [vp] * 9 + [u32, u32, vp, u32, vp, i64, C.c_int, vp, vp, vp]
+    lib.at_raster.restype = None
+    lib.at_trace.argtypes = [vp, C.POINTER(SR._Scene), vp, i64, vp, vp, vp, vp, vp]
+    lib.at_trace.restype = None
+
+
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libalpha_test_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "oracle"),
-                               os.path.join(HERE, "alpha_test_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        vp, u32, i64 = C.c_void_p, C.c_uint32, C.c_int64
-        lib.at_sample_alpha.argtypes = [vp, C.c_int, vp, vp, vp]
-        lib.at_sample_alpha.restype = C.c_float
-        lib.at_alpha_level0.argtypes = [vp, C.c_int, C.c_float, C.c_float]
-        lib.at_alpha_level0.restype = C.c_float
-        lib.at_raster.argtypes = [vp] * 9 + [u32, u32, vp, u32, vp, i64, C.c_int, vp, vp, vp]
-        lib.at_raster.restype = None
-        lib.at_trace.argtypes = [vp, C.POINTER(SR._Scene), vp, i64, vp, vp, vp, vp, vp]
-        lib.at_trace.restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "alpha_test_ref", _declare, include_oracle=True)
 
 
 def _p(a):

@@ -4,37 +4,32 @@ tests share.
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 F = np.float32
-_LIB = {}
+
+
+def _declare(lib):
+    vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
+    lib.bl_unpack_ufloat.argtypes = [u32, u32]
+    lib.bl_unpack_ufloat.restype = f32
+    lib.bl_pack_ufloat.argtypes = [f32, u32]
+    lib.bl_pack_ufloat.restype = u32
+    lib.bl_axis.argtypes = [f32, u32, vp]
+    lib.bl_sample_n.argtypes = [vp, u32, u32, vp, u64, vp]
+    lib.bl_downsample.argtypes = [vp, u32, u32, u32, u32, f32, f32, u32, vp, vp]
+    lib.bl_upsample.argtypes = [vp, u32, u32, u32, u32, f32, vp, vp]
+    lib.bl_chain.argtypes = [vp, u32, u32, u32, f32, vp]
+    for n in ("bl_axis", "bl_sample_n", "bl_downsample", "bl_upsample", "bl_chain"):
+        getattr(lib, n).restype = None
 
 
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libbloom_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "bloom_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
-        lib.bl_unpack_ufloat.argtypes = [u32, u32]
-        lib.bl_unpack_ufloat.restype = f32
-        lib.bl_pack_ufloat.argtypes = [f32, u32]
-        lib.bl_pack_ufloat.restype = u32
-        lib.bl_axis.argtypes = [f32, u32, vp]
-        lib.bl_sample_n.argtypes = [vp, u32, u32, vp, u64, vp]
-        lib.bl_downsample.argtypes = [vp, u32, u32, u32, u32, f32, f32, u32, vp, vp]
-        lib.bl_upsample.argtypes = [vp, u32, u32, u32, u32, f32, vp, vp]
-        lib.bl_chain.argtypes = [vp, u32, u32, u32, f32, vp]
-        for n in ("bl_axis", "bl_sample_n", "bl_downsample", "bl_upsample", "bl_chain"):
-            getattr(lib, n).restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "bloom_ref", _declare)
 
 
 def _p(a):

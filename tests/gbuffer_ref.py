@@ -3,33 +3,25 @@
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = {}
+
+def _declare(lib):
+    lib.gr_gbuffer.argtypes = [C.c_void_p] * 14
+    lib.gr_gbuffer.restype = None
+    for n in ("gr_pack_rgba8_n", "gr_pack_oct_n", "gr_pack_r9g9b9e5_n", "gr_quick_random_float_n", "gr_mesh_lod_value_n", "gr_unpack_normal_n"):
+        getattr(lib, n).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        getattr(lib, n).restype = None
+    lib.gr_vertex_normal.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.gr_vertex_normal.restype = None
 
 
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libgbuffer_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "oracle"),
-                               os.path.join(HERE, "gbuffer_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        lib.gr_gbuffer.argtypes = [C.c_void_p] * 14
-        lib.gr_gbuffer.restype = None
-        for n in ("gr_pack_rgba8_n", "gr_pack_oct_n", "gr_pack_r9g9b9e5_n", "gr_quick_random_float_n", "gr_mesh_lod_value_n", "gr_unpack_normal_n"):
-            getattr(lib, n).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-            getattr(lib, n).restype = None
-        lib.gr_vertex_normal.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
-        lib.gr_vertex_normal.restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "gbuffer_ref", _declare, include_oracle=True)
 
 
 def _p(a):

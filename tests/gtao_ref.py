@@ -3,44 +3,39 @@ the software sine and cosine, and the constant blocks, depth images and G-buffer
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import gtao, synth
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 F = np.float32
-_LIB = {}
 SENTINEL8 = 0xA7                                   # pre-fill of the byte targets
 SENTINEL16 = 0xFE5A                                # pre-fill of the depth chain: a NaN word, which the prefilter never stores
 
 
+def _declare(lib):
+    vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
+    for n in ("gt_r16", "gt_sin", "gt_cos"):
+        getattr(lib, n).argtypes = [f32]
+        getattr(lib, n).restype = f32
+    for n in ("gt_r16_n", "gt_half_bits_n", "gt_half_value_n", "gt_sin_n", "gt_cos_n"):
+        getattr(lib, n).argtypes = [vp, u64, vp]
+        getattr(lib, n).restype = None
+    lib.gt_hilbert.argtypes = [u32, u32]
+    lib.gt_hilbert.restype = u32
+    lib.gt_chain_offset.argtypes = [u32, u32, u32]
+    lib.gt_chain_offset.restype = u64
+    lib.gt_prefilter.argtypes = [vp, u32, u32, vp, vp]
+    lib.gt_main.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
+    lib.gt_denoise.argtypes = [vp, u32, u32, u32, vp, vp, vp]
+    for n in ("gt_prefilter", "gt_main", "gt_denoise"):
+        getattr(lib, n).restype = None
+
+
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libgtao_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "gtao_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
-        for n in ("gt_r16", "gt_sin", "gt_cos"):
-            getattr(lib, n).argtypes = [f32]
-            getattr(lib, n).restype = f32
-        for n in ("gt_r16_n", "gt_half_bits_n", "gt_half_value_n", "gt_sin_n", "gt_cos_n"):
-            getattr(lib, n).argtypes = [vp, u64, vp]
-            getattr(lib, n).restype = None
-        lib.gt_hilbert.argtypes = [u32, u32]
-        lib.gt_hilbert.restype = u32
-        lib.gt_chain_offset.argtypes = [u32, u32, u32]
-        lib.gt_chain_offset.restype = u64
-        lib.gt_prefilter.argtypes = [vp, u32, u32, vp, vp]
-        lib.gt_main.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp]
-        lib.gt_denoise.argtypes = [vp, u32, u32, u32, vp, vp, vp]
-        for n in ("gt_prefilter", "gt_main", "gt_denoise"):
-            getattr(lib, n).restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "gtao_ref", _declare)
 
 
 def sincos_bound(lib) -> float:

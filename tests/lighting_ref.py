@@ -3,31 +3,25 @@
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = {}
+
+def _declare(lib):
+    lib.lr_lighting.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    lib.lr_lighting.restype = None
+    lib.lr_pack_ufloat_n.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+    lib.lr_pack_ufloat_n.restype = None
+    for n in ("lr_exp2_n", "lr_unpack_unorm8_n", "lr_unpack_unorm16_n", "lr_unpack_oct_n", "lr_unpack_r9g9b9e5_n"):
+        getattr(lib, n).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        getattr(lib, n).restype = None
 
 
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "liblighting_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "lighting_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        lib.lr_lighting.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        lib.lr_lighting.restype = None
-        lib.lr_pack_ufloat_n.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
-        lib.lr_pack_ufloat_n.restype = None
-        for n in ("lr_exp2_n", "lr_unpack_unorm8_n", "lr_unpack_unorm16_n", "lr_unpack_oct_n", "lr_unpack_r9g9b9e5_n"):
-            getattr(lib, n).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-            getattr(lib, n).restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "lighting_ref", _declare)
 
 
 def _p(a):

@@ -3,16 +3,12 @@
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = {}
 MAX_MIPS = 16
 FORMAT_RGBA8, FORMAT_SRGBA8 = 10, 11
 
@@ -22,24 +18,21 @@ class MtTexture(C.Structure):
                 ("mips", C.c_void_p * MAX_MIPS)]
 
 
+def _declare(lib):
+    lib.mt_gbuffer.argtypes = [C.c_void_p] * 16
+    lib.mt_gbuffer.restype = None
+    lib.mt_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mt_sample.restype = C.c_uint32
+    lib.mt_srgb_table.argtypes = [C.c_void_p]
+    lib.mt_srgb_table.restype = None
+    lib.mt_log2.argtypes = [C.c_float]
+    lib.mt_log2.restype = C.c_float
+    lib.mt_half_to_float.argtypes = [C.c_uint16]
+    lib.mt_half_to_float.restype = C.c_float
+
+
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libmaterial_textures_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "oracle"),
-                               os.path.join(HERE, "material_textures_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        lib.mt_gbuffer.argtypes = [C.c_void_p] * 16
-        lib.mt_gbuffer.restype = None
-        lib.mt_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mt_sample.restype = C.c_uint32
-        lib.mt_srgb_table.argtypes = [C.c_void_p]
-        lib.mt_srgb_table.restype = None
-        lib.mt_log2.argtypes = [C.c_float]
-        lib.mt_log2.restype = C.c_float
-        lib.mt_half_to_float.argtypes = [C.c_uint16]
-        lib.mt_half_to_float.restype = C.c_float
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "material_textures_ref", _declare, include_oracle=True)
 
 
 def _p(a):

@@ -4,37 +4,32 @@ CPU and the GPU tests share.
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 F = np.float32
-_LIB = {}
+
+
+def _declare(lib):
+    for n in ("pr_log2_n", "pr_exp2_n", "pr_exp2_reduced_n", "pr_pow_gamma_n", "pr_luminance_n"):
+        getattr(lib, n).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        getattr(lib, n).restype = None
+    lib.pr_unpack_ufloat_n.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
+    lib.pr_bin_n.argtypes = [C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_void_p]
+    lib.pr_histogram.argtypes = [C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_void_p]
+    lib.pr_adapt_exposure.argtypes = [C.c_void_p] * 4
+    lib.pr_post.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p]
+    lib.pr_tone_map_n.argtypes = [C.c_void_p, C.c_uint64]
+    lib.pr_constants.argtypes = [C.c_void_p]
+    for n in ("pr_unpack_ufloat_n", "pr_bin_n", "pr_histogram", "pr_adapt_exposure", "pr_post", "pr_tone_map_n", "pr_constants"):
+        getattr(lib, n).restype = None
 
 
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libpostprocess_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "postprocess_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        for n in ("pr_log2_n", "pr_exp2_n", "pr_exp2_reduced_n", "pr_pow_gamma_n", "pr_luminance_n"):
-            getattr(lib, n).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-            getattr(lib, n).restype = None
-        lib.pr_unpack_ufloat_n.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]
-        lib.pr_bin_n.argtypes = [C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_void_p]
-        lib.pr_histogram.argtypes = [C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_void_p]
-        lib.pr_adapt_exposure.argtypes = [C.c_void_p] * 4
-        lib.pr_post.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p]
-        lib.pr_tone_map_n.argtypes = [C.c_void_p, C.c_uint64]
-        lib.pr_constants.argtypes = [C.c_void_p]
-        for n in ("pr_unpack_ufloat_n", "pr_bin_n", "pr_histogram", "pr_adapt_exposure", "pr_post", "pr_tone_map_n", "pr_constants"):
-            getattr(lib, n).restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "postprocess_ref", _declare)
 
 
 def _p(a):

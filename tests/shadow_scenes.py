@@ -150,11 +150,11 @@ def cornell():
     walls coplanar and axis-aligned, so every wall's box has no thickness."""
     import json
 
-    from test_gltf_cornell import _fixture
+    from suite_support import cornell_fixture
     from toyrenderer_amd import cached_scene, gltf_lite
     with open(os.path.join(HERE, "golden", "cornell_materials.json")) as f:
         cm = json.load(f)
-    _, s, camera = _fixture()
+    _, s, camera = cornell_fixture()
     s.materials = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
     s.primMaterial = np.array(cm["primitiveMaterial"], np.uint32)
     inst = gltf_lite.apply_materials(s)

@@ -4,17 +4,14 @@ kernel's box test, and the refit.  The acceleration structure itself comes from 
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import accel
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 F = np.float32
-_LIB = {}
 SENTINEL8 = 0xA7                                   # pre-fill of the mask: neither 0 nor 255
 SENTINEL16 = 0xFE5A                                # pre-fill of the linear view depth: a NaN word, which the pass never stores
 BRUTE, WALK = 0, 1
@@ -32,23 +29,21 @@ class _Scene(C.Structure):
                 ("triOrder", C.c_void_p), ("numTriOrder", C.c_uint32)]
 
 
+def _declare(lib):
+    vp, u32 = C.c_void_p, C.c_uint32
+    lib.sm_half_bits.argtypes = [C.c_float]
+    lib.sm_half_bits.restype = C.c_uint16
+    lib.sm_object_from_world.argtypes = [vp, vp]
+    lib.sm_object_from_world.restype = None
+    lib.sm_refit.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, u32, vp]
+    lib.sm_refit.restype = None
+    lib.sm_texel_ray.argtypes = [vp, u32, u32, C.c_float, vp, vp, vp, vp, vp]
+    lib.sm_trace.argtypes = [vp, C.POINTER(_Scene), vp, vp, vp, C.c_int, vp, vp, vp]
+    lib.sm_trace.restype = None
+
+
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libshadowmask_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "shadowmask_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        vp, u32 = C.c_void_p, C.c_uint32
-        lib.sm_half_bits.argtypes = [C.c_float]
-        lib.sm_half_bits.restype = C.c_uint16
-        lib.sm_object_from_world.argtypes = [vp, vp]
-        lib.sm_object_from_world.restype = None
-        lib.sm_refit.argtypes = [vp, u32, vp, u32, vp, u32, vp, vp, u32, vp, u32, vp]
-        lib.sm_refit.restype = None
-        lib.sm_texel_ray.argtypes = [vp, u32, u32, C.c_float, vp, vp, vp, vp, vp]
-        lib.sm_trace.argtypes = [vp, C.POINTER(_Scene), vp, vp, vp, C.c_int, vp, vp, vp]
-        lib.sm_trace.restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "shadowmask_ref", _declare)
 
 
 class Accel:

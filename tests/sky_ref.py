@@ -5,40 +5,37 @@ The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) in
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import interop as I
 from toyrenderer_amd import sky
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "hosek_rgb.npz")
 F = np.float32
-_LIB = {}
 SENTINEL = 0x12345678                              # a word no sky pixel of the tests produces; checked where it is used
 
 
+def _declare(lib):
+    vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
+    lib.sk_acos.argtypes = [f32]
+    lib.sk_acos.restype = f32
+    lib.sk_acos_n.argtypes = [vp, u64, vp]
+    lib.sk_acos_max_error.argtypes = [u32, u32, vp]
+    lib.sk_acos_max_error.restype = C.c_double
+    lib.sk_sky.argtypes = [vp, u32, u32, vp, vp, vp, vp]
+    lib.sk_radiance.argtypes = [vp, vp, vp]
+    lib.sk_parameters.argtypes = [vp, vp, f32, vp, vp, vp]
+    lib.sk_helper.argtypes = [vp, C.c_int, f32, f32, f32]
+    lib.sk_helper.restype = C.c_double
+    for n in ("sk_acos_n", "sk_sky", "sk_radiance", "sk_parameters"):
+        getattr(lib, n).restype = None
+
+
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libsky_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "sky_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        vp, u32, u64, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
-        lib.sk_acos.argtypes = [f32]
-        lib.sk_acos.restype = f32
-        lib.sk_acos_n.argtypes = [vp, u64, vp]
-        lib.sk_acos_max_error.argtypes = [u32, u32, vp]
-        lib.sk_acos_max_error.restype = C.c_double
-        lib.sk_sky.argtypes = [vp, u32, u32, vp, vp, vp, vp]
-        lib.sk_radiance.argtypes = [vp, vp, vp]
-        lib.sk_parameters.argtypes = [vp, vp, f32, vp, vp, vp]
-        lib.sk_helper.argtypes = [vp, C.c_int, f32, f32, f32]
-        lib.sk_helper.restype = C.c_double
-        for n in ("sk_acos_n", "sk_sky", "sk_radiance", "sk_parameters"):
-            getattr(lib, n).restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "sky_ref", _declare)
 
 
 def acos_bound(lib) -> float:

@@ -15,21 +15,12 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import alpha_test_ref as AT  # noqa: E402
 import alpha_test_scenes as A  # noqa: E402
 import material_textures_ref as MT  # noqa: E402
+from suite_support import at, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 from visibility_scenes import consts  # noqa: E402
 
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def at(tmp_path_factory):
-    return AT.load(tmp_path_factory.mktemp("alpha_test_ref"))
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref_for_alpha"))
 
 
 def render(at, sc, alpha_test=True, textures="scene", with_alpha_instances=True):

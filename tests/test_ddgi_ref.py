@@ -4,7 +4,6 @@ reach, the descriptor's layout and the declarations.  tests/test_gpu_ddgi.py com
 import math
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +14,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ddgi_ref as DR  # noqa: E402
 import ddgi_scenes as DS  # noqa: E402
 import lighting_ref as LR  # noqa: E402
+from ref_build import layout_probe  # noqa: E402
+from suite_support import dg  # noqa: E402, F401
 from toyrenderer_amd import ddgi  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
@@ -26,11 +27,6 @@ F = np.float32
 # weight, so an input rounding reaches the result about tenfold.
 FLOAT64_BOUND = 9.1e-5
 LEFT_OUT_CAP = 0.01                              # at most 1 % of the lit pixels may decide a branch differently in float64
-
-
-@pytest.fixture(scope="module")
-def dg(tmp_path_factory):
-    return DR.load(tmp_path_factory.mktemp("ddgi_ref"))
 
 
 @pytest.fixture(scope="module")
@@ -307,14 +303,7 @@ def test_volume_desc_layout(tmp_path):
     """A g++-compiled probe prints sizeof / offsetof of interop::DDGIVolumeDesc (csrc/ShaderInterop.h): 64 bytes, every field
     where the numpy dtype and tests/ddgi_ref.c have it."""
     fields = list(I.DDGIVolumeDesc.names)
-    lines = ['#include <cstdio>', '#include "ShaderInterop.h"', "int main() {", '    printf("sizeof %zu\\n", sizeof(interop::DDGIVolumeDesc));']
-    lines += [f'    printf("{f} %zu\\n", offsetof(interop::DDGIVolumeDesc, {f}));' for f in fields]
-    lines += ["    return 0;", "}"]
-    src = tmp_path / "probe.cpp"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "toyrenderer_amd", "csrc"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    out = layout_probe(tmp_path, [("sizeof", "sizeof(interop::DDGIVolumeDesc)")] + [(f, f"offsetof(interop::DDGIVolumeDesc, {f})") for f in fields])
     assert int(out["sizeof"]) == 64 == I.DDGIVolumeDesc.itemsize
     want = dict(origin=0, probeNormalBias=12, probeSpacing=16, probeViewBias=28, probeCounts=32, probeIrradianceEncodingGamma=44,
                 numIrradianceInteriorTexels=48, numDistanceInteriorTexels=52, flags=56, pad=60)

@@ -5,7 +5,6 @@ material table, and the back end's and the facade's declarations."""
 import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +13,8 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import gbuffer_ref as GR  # noqa: E402
+from ref_build import layout_probe  # noqa: E402
+from suite_support import cornell_fixture, gr, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from gbuffer_scenes import hostile_materials, wall, with_normals_and_materials  # noqa: E402
 from scene_gen import all_meshlets_visible  # noqa: E402
@@ -23,16 +24,6 @@ from visibility_scenes import city, consts, hostile_soup  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def gr(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gbuffer_ref"))
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
 
 
 # ---- independent numpy restatements (float32 arrays) ------------------------------------------------------------------
@@ -227,10 +218,9 @@ def test_wall_normal_is_the_adjugate_transform_of_the_unpacked_word(gr, vr, word
 def test_cornell_fixture_shows_its_three_walls(gr, vr, oracle):
     """Every covered texel's albedo bytes are floor(c * 255) in float32 of one of the asset's three baseColorFactors
     (tests/golden/cornell_materials.json), z = 0, w = 0xFF, and all three colours occur."""
-    from test_gltf_cornell import _fixture
     with open(os.path.join(ROOT, "tests", "golden", "cornell_materials.json")) as f:
         cm = json.load(f)
-    _, s, camera = _fixture()
+    _, s, camera = cornell_fixture()
     assert cm["primitiveMaterial"] == [0, 1, 2] and len(cm["baseColorFactor"]) == 3 and len(s.instances) == 3
     mats = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
     s.materials, s.primMaterial = mats, np.array(cm["primitiveMaterial"], np.uint32)
@@ -387,16 +377,10 @@ def test_material_struct_layout_matches_numpy(tmp_path):
     """A g++-compiled probe prints sizeof / offsetof of interop::MaterialData and interop::TextureData (csrc/ShaderInterop.h):
     124 and 20 bytes, every field where the numpy dtype has it."""
     fields = [n for n in I.MaterialData.names]
-    lines = ['#include <cstdio>', '#include "ShaderInterop.h"', "int main() {",
-             '    printf("sizeof %zu\\n", sizeof(interop::MaterialData));', '    printf("texture %zu\\n", sizeof(interop::TextureData));']
-    lines += [f'    printf("{f} %zu\\n", offsetof(interop::MaterialData, {f}));' for f in fields]
-    lines += [f'    printf("t_{f} %zu\\n", offsetof(interop::TextureData, {f}));' for f in I.TextureData.names]
-    lines += ["    return 0;", "}"]
-    src = tmp_path / "probe.cpp"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "toyrenderer_amd", "csrc"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    prints = [("sizeof", "sizeof(interop::MaterialData)"), ("texture", "sizeof(interop::TextureData)")]
+    prints += [(f, f"offsetof(interop::MaterialData, {f})") for f in fields]
+    prints += [(f"t_{f}", f"offsetof(interop::TextureData, {f})") for f in I.TextureData.names]
+    out = layout_probe(tmp_path, prints)
     assert int(out["sizeof"]) == 124 == I.MaterialData.itemsize and int(out["texture"]) == 20 == I.TextureData.itemsize
     for f in fields:
         assert int(out[f]) == I.MaterialData.fields[f][1], f

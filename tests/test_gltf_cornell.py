@@ -7,44 +7,24 @@ is unpinned."""
 import json
 import os
 import struct
+import sys
 
 import numpy as np
 import pytest
 
-from toyrenderer_amd import gltf_lite
-from toyrenderer_amd import interop as I
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cornell_scene.npz")
-
-
-def _fixture():
-    z = np.load(GOLDEN)                                  # allow_pickle=False (default): plain arrays only
-    cam = z["camera"]
-    camera = gltf_lite.Camera("fixture", tuple(cam[0:3]), tuple(cam[3:7]), float(cam[7]), float(cam[8]), float(cam[9]))
-    scene = gltf_lite.LoadedScene(z["instances"].view(I.BasePassInstanceConstants).reshape(-1), z["meshData"].view(I.MeshData).reshape(-1),
-                                  z["meshlets"].view(I.MeshletData).reshape(-1), z["opaqueIds"], z["alphaMaskIds"],
-                                  z["nodes"].view(I.NodeLocalTransform).reshape(-1), z["primToNode"], [camera],
-                                  z["vertices"].view(I.RawVertexFormat).reshape(-1) if "vertices" in z.files else np.zeros(0, I.RawVertexFormat),
-                                  z["meshletVertexIds"] if "meshletVertexIds" in z.files else np.zeros(0, np.uint32),
-                                  z["meshletTriangles"] if "meshletTriangles" in z.files else np.zeros(0, np.uint32))
-    return z, scene, camera
-
-
-def _cull(oracle, scene, view, flags):
-    inst = scene.instances.copy()
-    oracle.update_instance_consts(scene.nodes, scene.primToNode, inst)
-    sc = dict(scene.as_oracle()); sc["instances"] = inst
-    hzb = oracle.HzbTexture(*view.hzb_dims)
-    depth = np.zeros((view.renderH, view.renderW), np.float32) if flags & 2 else None
-    return inst, oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=flags, maxGroups=65535, record_capacity=65535)
+from suite_support import cornell_fixture, cpu_cull  # noqa: E402
+from toyrenderer_amd import gltf_lite  # noqa: E402
+from toyrenderer_amd import interop as I  # noqa: E402
 
 
 @pytest.mark.parametrize("flags", [5, 7])
 def test_cornell_cpu_cull_matches_fixture(oracle, flags):
-    z, scene, camera = _fixture()
+    z, scene, camera = cornell_fixture()
     assert len(scene.instances) == 3 and 3 <= len(scene.meshlets) <= 4, "cornell: 3 primitives, 3-4 meshlets"
     view = gltf_lite.view_of(camera, (1920, 1080))
-    inst, ref = _cull(oracle, scene, view, flags)
+    inst, ref = cpu_cull(oracle, scene, view, flags)
     assert np.array_equal(inst["m_WorldMatrix"], z[f"world_{flags}"]), "node transforms -> world matrices"
     # node 0 of the asset is rotated by 90 degrees about x (quaternion (0.7071069, 0, 0, 0.7071066))
     assert abs(float(inst["m_WorldMatrix"][0][1][2]) - 1.0) < 1e-5 and abs(float(inst["m_WorldMatrix"][0][2][1]) + 1.0) < 1e-5
@@ -123,7 +103,7 @@ def _write_gltf_of_fixture(tmp_path, scene, camera):
 
 
 def test_fixture_is_what_the_loader_derives_from_its_geometry(tmp_path):
-    z, scene, camera = _fixture()
+    z, scene, camera = cornell_fixture()
     path, counts = _write_gltf_of_fixture(tmp_path, scene, camera)
     # the fixture against the asset as SURVEY.md section 4 describes it: one mesh of 3 primitives with 74 / 4 / 4 vertices and
     # 90 / 6 / 6 indices in a 2 816-byte buffer, node 0 rotated by (0.7071069, 0, 0, 0.7071066)
@@ -209,7 +189,7 @@ def test_loader_invariants_on_a_generated_file(tmp_path, oracle):
     cam = s.cameras[0]
     assert cam.position == (0.0, 0.0, 3.0) and abs(cam.aspect - 1.5) < 1e-9
     view = gltf_lite.view_of(cam, (1200, 800))
-    inst, ref = _cull(oracle, s, view, 5)
+    inst, ref = cpu_cull(oracle, s, view, 5)
     assert np.allclose(inst["m_WorldMatrix"][1][3][:3], [np.sqrt(2.0), 0.0, -10 - np.sqrt(2.0)], atol=1e-5), "child = parent TRS applied to (1,0,0)"
     lod = int(ref.records[0].view(I.MeshletAmplificationData)["m_MeshLOD"][0])     # the LOD the oracle selected for the grid at this distance
     n_lod = int(md["m_MeshLODDatas"]["m_NumMeshlets"][lod])
@@ -223,8 +203,6 @@ def test_lod_chain_contract(tmp_path):
     :488), every LOD's meshlets partition exactly that LOD's triangles, uses only the mesh's own vertices and stays
     within the relative error bound 0.1 of the original surface (measured: vertices of LOD 0 against the LOD's
     triangles' planes is not needed -- a collapse keeps a subset of the vertices, so the bound is on the moved ones)."""
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from scene_gen import _grid, _sphere
     for pos, idx in (_sphere(16, 10), _grid(24, 0.05), _grid(2, 0.0)):
         idx = idx.astype(np.uint32)
@@ -265,8 +243,6 @@ def test_loaded_scene_carries_the_lod_chain(tmp_path, oracle):
     """Generated city scene: the LODs land in MeshData (ranges, errors) and in the meshlet / geometry buffers; every LOD's
     meshlets cover exactly its triangles; the oracle's LOD selection (gpuculling.hlsl:39-57) picks coarser LODs for the
     far spheres than for the near ones."""
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from scene_gen import write_city_gltf
     s = gltf_lite.load(write_city_gltf(tmp_path))
     sphere = s.meshData[1]
@@ -290,7 +266,7 @@ def test_loaded_scene_carries_the_lod_chain(tmp_path, oracle):
         tri_counts.append(n_t)
     assert all(b < a * 0.85 for a, b in zip(tri_counts, tri_counts[1:]))
     view = gltf_lite.view_of(s.cameras[0], (1280, 720))
-    inst, ref = _cull(oracle, s, view, 1)
+    inst, ref = cpu_cull(oracle, s, view, 1)
     rec = ref.records[0].view(I.MeshletAmplificationData)
     sphere_rec = rec[s.instances["m_MeshDataIdx"][rec["m_InstanceConstIdx"]] == 1]
     assert len(np.unique(sphere_rec["m_MeshLOD"])) >= 2, "near and far spheres use different LODs"

@@ -18,6 +18,7 @@ import alpha_test_scenes as A  # noqa: E402
 import material_textures_ref as MT  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
+from suite_support import at, dev, mt, same, sm, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 from visibility_scenes import consts  # noqa: E402
@@ -25,43 +26,6 @@ from visibility_scenes import consts  # noqa: E402
 pytestmark = pytest.mark.gpu
 F = np.float32
 ALPHA = " ALPHA_MASK_MODE=1"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def at(tmp_path_factory):
-    return AT.load(tmp_path_factory.mktemp("alpha_test_ref"))
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref_for_alpha"))
-
-
-@pytest.fixture(scope="module")
-def mt(tmp_path_factory):
-    return MT.load(tmp_path_factory.mktemp("material_textures_ref_for_alpha"))
-
-
-@pytest.fixture(scope="module")
-def sm(tmp_path_factory):
-    return SR.load(tmp_path_factory.mktemp("shadowmask_ref_for_alpha"))
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} words differ, first at {first}: got {got[first]}, want {want[first]}")
 
 
 def _gpu_scene(dev, sc, raytracing=False):
@@ -128,15 +92,15 @@ def test_rasters_equal_the_reference(dev, oracle, at, mt, mode, flags):
         what = f"{mode}, flags {flags}, frame {f}"
         assert _raster_names(g["names"]) == {stem, stem + ALPHA}, g["names"]
         assert {n for n in g["names"] if n.startswith(stem + ALPHA)} == {stem + ALPHA + "#main", stem + ALPHA + "#tiles"}
-        _same(g["depth"], depth.view(np.uint32), what + ": depth")
+        same(g["depth"], depth.view(np.uint32), what + ": depth")
         if mode == "depth":
             continue
-        _same(g["vis"], vis, what + ": visibility texels")
+        same(g["vis"], vis, what + ": visibility texels")
         recs = [ref.records[s] if ref.passRan[s] else None for s in range(4)]
         lsts = [ref.visibleList[s] if ref.passRan[s] else None for s in range(4)]
         gb, m, taps = MT.gbuffer(mt, k, geo, recs, lsts, vis, sc["materials"], table)
-        _same(g["gbuffer"], gb, what + ": GBufferA")
-        _same(g["motion"], VR.to_half_bits(m), what + ": motion")
+        same(g["gbuffer"], gb, what + ": GBufferA")
+        same(g["motion"], VR.to_half_bits(m), what + ": motion")
         assert (taps[..., 0] > 0).sum() > 1500 and "basepass_PS_Main_GBuffer#textured" in g["names"]
 
 
@@ -149,7 +113,7 @@ def test_an_opaque_texture_changes_nothing(dev):
     on, = _frames(dev, sc, culling_flags=1, visibility=True, alpha_test=True)
     assert _raster_names(on["names"]) == {"basepass_MS_Main_visibility", "basepass_MS_Main_visibility" + ALPHA}
     for name in ("depth", "vis", "motion"):
-        _same(on[name], off[name], "all-255 textures: " + name)
+        same(on[name], off[name], "all-255 textures: " + name)
     assert (VR.decode(on["vis"])[1] == 2).sum() > 1500
 
 
@@ -161,7 +125,7 @@ def test_a_transparent_texture_removes_the_instances(dev):
     bare, = _frames(dev, A.without_alpha_instances(sc), culling_flags=1, visibility=True, alpha_test=True)
     assert _raster_names(bare["names"]) == {"basepass_MS_Main_visibility"}
     for name in ("depth", "vis", "motion"):
-        _same(on[name], bare[name], "all-0 textures: " + name)
+        same(on[name], bare[name], "all-0 textures: " + name)
 
 
 def test_the_tie_is_kept_and_the_next_cutoff_discards(dev):
@@ -171,8 +135,8 @@ def test_the_tie_is_kept_and_the_next_cutoff_discards(dev):
     a, = _frames(dev, kept, culling_flags=1, visibility=True, alpha_test=True)
     b, = _frames(dev, gone, culling_flags=1, visibility=True, alpha_test=True)
     for name in ("depth", "vis"):
-        _same(a[name], solid[name], "alpha == cutoff: kept whole: " + name)
-        _same(b[name], wall[name], "the next cutoff: gone whole: " + name)
+        same(a[name], solid[name], "alpha == cutoff: kept whole: " + name)
+        same(b[name], wall[name], "the next cutoff: gone whole: " + name)
     assert (VR.decode(a["vis"])[1] == 2).sum() > 2000
 
 
@@ -188,8 +152,8 @@ def test_option_off_draws_solid_cards(dev, oracle, at, vr, flags):
                        raster=(I.world_to_clip(view.worldToView, view.viewToClip), sc["vertices"], sc["vertexIds"], sc["triangles"]))
     geo = VR.Geometry(sc, sc["vertices"], sc["vertexIds"], sc["triangles"])
     vis, depth = VR.frame_visibility(vr, consts(view), geo, ref, *A.RENDER)
-    _same(got["vis"], vis, "texels"); _same(got["depth"], depth.view(np.uint32), "depth")
-    _same(got["motion"], VR.to_half_bits(VR.frame_motion(vr, consts(view), geo, ref, vis)), "motion")
+    same(got["vis"], vis, "texels"); same(got["depth"], depth.view(np.uint32), "depth")
+    same(got["motion"], VR.to_half_bits(VR.frame_motion(vr, consts(view), geo, ref, vis)), "motion")
 
 
 # ---- 4. shadows -------------------------------------------------------------------------------------------------------------------------------
@@ -218,11 +182,11 @@ def test_a_textured_cut_out_casts_the_shadow_of_its_kept_texels(dev, at, sm, sof
                 assert trace == ({"textured"} if alpha_test else {"main"}), g["names"]
                 depth, gb = drv.depth.download_mip(0), drv.gbufferA.download_mip(0)
                 want, want_lvd = AT.trace(at, drv.shadow_consts, acc, depth, gb, settings["noise"], sc["textures"] if alpha_test else None)
-                _same(drv.download_shadow_mask(), want, f"alpha_test {alpha_test}: mask")
-                _same(drv.linear_view_depth.download_mip(0), want_lvd, f"alpha_test {alpha_test}: linear view depth")
+                same(drv.download_shadow_mask(), want, f"alpha_test {alpha_test}: mask")
+                same(drv.linear_view_depth.download_mip(0), want_lvd, f"alpha_test {alpha_test}: linear view depth")
                 if not alpha_test:
                     today, _, _ = SR.trace(sm, drv.shadow_consts, acc, depth, gb, settings["noise"], SR.BRUTE)
-                    _same(want, today, "the reference without a table is today's")
+                    same(want, today, "the reference without a table is today's")
                 _, slot, _, _ = VR.decode(g["vis"])
                 masks[alpha_test] = (want, slot == 0)
             finally:
@@ -264,10 +228,10 @@ def test_host_path_equals_the_python_driver(dev):
         r.set_node_transforms(nodes)
         r.set_camera(view)
         r.frame(); r.results()
-        _same(r.instances(n)["m_WorldMatrix"], sc["instances"]["m_WorldMatrix"], "host: the identity nodes give the scene's matrices")
-        _same(r.download_depth().view(np.uint32), want["depth"], "host: depth")
-        _same(r.download_visibility(), want["vis"], "host: texels")
-        _same(r.download_gbuffer_a(), want["gbuffer"], "host: GBufferA")
+        same(r.instances(n)["m_WorldMatrix"], sc["instances"]["m_WorldMatrix"], "host: the identity nodes give the scene's matrices")
+        same(r.download_depth().view(np.uint32), want["depth"], "host: depth")
+        same(r.download_visibility(), want["vis"], "host: texels")
+        same(r.download_gbuffer_a(), want["gbuffer"], "host: GBufferA")
         r.set_alpha_test(False)
         r.frame(); r.results()
         assert np.count_nonzero(r.download_visibility() != want["vis"]) > 500, "off again: solid cards"

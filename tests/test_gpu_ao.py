@@ -12,6 +12,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import gtao_ref as GR  # noqa: E402
 import lighting_ref as LR  # noqa: E402
+import sky_ref as SK  # noqa: E402
+from suite_support import dev, gpu_scene, gt, host_renderer, lit_city, lit_cornell, lr, op_counts, recorded, same  # noqa: E402, F401
 from toyrenderer_amd import gltf_lite, gtao, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
@@ -23,31 +25,15 @@ DENOISE = "ambientocclusion_CS_XeGTAO_Denoise"
 SIZES = [(1, 1), (2, 2), (15, 15), (16, 16), (17, 17), (32, 8), (33, 9), (67, 35), (129, 3), (270, 135)]
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
+# the lit scenes of tests/test_gpu_sky.py, with its lights
+def _cornell(oracle):
+    *scene, camera = lit_cornell(oracle)
+    return (*scene, camera, dict(dir_light=(tuple(float(x) for x in SK.unit((0.3, 0.8, -0.52))), 3.0), camera_origin=tuple(float(x) for x in camera.position),
+                                 auto_exposure=(0.004, 12.0, 0.5)))
 
 
-@pytest.fixture(scope="module")
-def gt(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gtao_ref_gpu"))
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref_for_ao"))
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} words differ, first at {first}: got {got[first]}, want {want[first]}")
+def _city(oracle, tmp_path):
+    return (*lit_city(oracle, tmp_path), dict(dir_light=(tuple(float(x) for x in SK.unit((0.2, 0.35, -0.9))), 2.5)))
 
 
 class _Passes:
@@ -131,7 +117,7 @@ def test_single_passes_match_the_reference(dev, gt, size):
         for name, depth in images.items():
             chains[name] = GR.prefilter(gt, k, depth)
             assert not np.any(chains[name] == GR.SENTINEL16), name                     # every texel of every mip is written
-            _same(p.prefilter(k, depth), chains[name], f"{size} prefilter {name}")
+            same(p.prefilter(k, depth), chains[name], f"{size} prefilter {name}")
         assert len(MAIN_CASES[size]) >= 2
         outputs = []
         for quality, noise in MAIN_CASES[size]:
@@ -140,8 +126,8 @@ def test_single_passes_match_the_reference(dev, gt, size):
             for name in images:
                 want = GR.main_pass(gt, kq, GR.push(quality), W, H, chains[name], g)
                 got = p.main(kq, GR.push(quality), chains[name], g)
-                _same(got[1], want[1], f"{size} edges q{quality} n{noise} {name}")
-                _same(got[0], want[0], f"{size} working AO q{quality} n{noise} {name}")
+                same(got[1], want[1], f"{size} edges q{quality} n{noise} {name}")
+                same(got[0], want[0], f"{size} working AO q{quality} n{noise} {name}")
                 outputs.append(want)
         rng = np.random.default_rng(W * 7 + H)
         outputs.append((rng.integers(0, 256, (H, W)).astype(np.uint8), rng.integers(0, 256, (H, W)).astype(np.uint8)))
@@ -149,7 +135,7 @@ def test_single_passes_match_the_reference(dev, gt, size):
             for passes in range(4):
                 kd = GR.consts(W, H, dict(denoise_passes=passes))
                 for final in (0, 1):
-                    _same(p.denoise(kd, final, ao, edges), GR.denoise(gt, kd, final, ao, edges), f"{size} denoise final {final}, beta of {passes} passes")
+                    same(p.denoise(kd, final, ao, edges), GR.denoise(gt, kd, final, ao, edges), f"{size} denoise final {final}, beta of {passes} passes")
                 # the chain as the renderer records it, through the same two textures
                 working, ssao = ao, np.full((H, W), GR.SENTINEL8, np.uint8)
                 n = max(1, passes)
@@ -158,7 +144,7 @@ def test_single_passes_match_the_reference(dev, gt, size):
                     working, ssao = out, working
                 want_working, want_ssao = GR.denoise_chain(gt, kd, passes, ao, edges)
                 final_image = want_working if passes == 2 else want_ssao                # 2 passes: the final image lands in the working texture
-                _same(working, final_image, f"{size} chain of {passes}")
+                same(working, final_image, f"{size} chain of {passes}")
     finally:
         p.release()
 
@@ -183,13 +169,13 @@ def test_hostile_constant_blocks(dev, gt):
             for content in ("tilted", "checker", "nan_negative"):
                 depth = GR.depth_images(W, H, seed=11)[content]
                 chain = GR.prefilter(gt, k, depth)
-                _same(p.prefilter(k, depth), chain, f"{name} {content}: prefilter")
+                same(p.prefilter(k, depth), chain, f"{name} {content}: prefilter")
                 for push in (GR.push(3), GR.push(2, nan_matrix)):
                     want = GR.main_pass(gt, k, push, W, H, chain, g)
                     got = p.main(k, push, chain, g)
-                    _same(got[1], want[1], f"{name} {content}: edges")
-                    _same(got[0], want[0], f"{name} {content}: working AO")
-                    _same(p.denoise(k, 1, *want), GR.denoise(gt, k, 1, *want), f"{name} {content}: denoise")
+                    same(got[1], want[1], f"{name} {content}: edges")
+                    same(got[0], want[0], f"{name} {content}: working AO")
+                    same(p.denoise(k, 1, *want), GR.denoise(gt, k, 1, *want), f"{name} {content}: denoise")
     finally:
         p.release()
 
@@ -205,12 +191,10 @@ def test_frames_match_the_reference(dev, oracle, gt, lr, tmp_path, scene, render
     of the pass is equal; every texture of the pass equals the reference fed the frame's own depth and GBufferA, with 2 denoise
     passes the final image in the working texture; LightingOutput is the lighting reference fed that SSAO texture; without a debug
     view LightingOutput is the ao=None image."""
-    from test_gpu_lighting import _gpu_scene
-    from test_gpu_sky import _city, _cornell
     from toyrenderer_amd.frame import FrameDriver
     s, inst, vertices, mats, camera, kw = _cornell(oracle) if scene == "cornell" else _city(oracle, tmp_path)
     kw = {k: v for k, v in kw.items() if k in ("dir_light", "camera_origin")}
-    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    gs = gpu_scene(dev, s, inst, vertices, mats)
     view = gltf_lite.view_of(camera, render)
     W, H = render
     common = dict(record_capacity=4096, culling_flags=7, lighting=True, **kw)
@@ -228,26 +212,26 @@ def test_frames_match_the_reference(dev, oracle, gt, lr, tmp_path, scene, render
                 d.record(); d.run(); d.results()
             what = f"{scene} {render} frame {f}"
             for name in ("gbufferA", "visibility"):
-                _same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
+                same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
             depth, g = drv.depth.download_mip(0), drv.gbufferA.download_mip(0)
-            _same(depth.view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
-            _same(drv.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
+            same(depth.view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
+            same(drv.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
             k = gtao.update_constants(W, H, full, view.viewToClip, f)
             assert drv.gtao_consts.tobytes() == k.tobytes() and k["NoiseIndex"][0] == (f if full["denoise_passes"] else 0)
             ref = GR.frame(gt, k, gtao.main_pass_constants(view.worldToView, full["quality"]), depth, g, full["denoise_passes"])
             chain = np.concatenate([drv.ao_depth.download_mip(m).ravel() for m in range(gtao.DEPTH_MIP_LEVELS)])
-            _same(chain, ref["chain"], what + ": working depth chain")
-            _same(drv.ao_edges.download_mip(0), ref["edges"], what + ": edges")
-            _same(drv.ao_working.download_mip(0), ref["working"], what + ": working AO term")
+            same(chain, ref["chain"], what + ": working depth chain")
+            same(drv.ao_edges.download_mip(0), ref["edges"], what + ": edges")
+            same(drv.ao_working.download_mip(0), ref["working"], what + ": working AO term")
             ssao = drv.download_ssao()
-            _same(ssao, ref["ssao"], what + ": SSAO texture")
+            same(ssao, ref["ssao"], what + ": SSAO texture")
             if full["denoise_passes"] == 2:                                               # the reference's quirk, kept
-                _same(ssao, GR.denoise(gt, k, 0, ref["working_after_main"], ref["edges"]), what + ": the SSAO texture holds the first pass's output")
+                same(ssao, GR.denoise(gt, k, 0, ref["working_after_main"], ref["edges"]), what + ": the SSAO texture holds the first pass's output")
             assert drv.lighting_consts["m_SSAOEnabled"][0] == 1 and base.lighting_consts["m_SSAOEnabled"][0] == 0
-            _same(drv.lighting_output.download_mip(0), LR.lighting(lr, drv.lighting_consts, g, depth, ssao=ssao), what + ": LightingOutput, view 9")
+            same(drv.lighting_output.download_mip(0), LR.lighting(lr, drv.lighting_consts, g, depth, ssao=ssao), what + ": LightingOutput, view 9")
             if scene != "cornell" or f == 0:
                 assert np.count_nonzero(drv.lighting_output.download_mip(0) != base.lighting_output.download_mip(0)) > 0   # the view shows the generated image
-            _same(plain_ao.lighting_output.download_mip(0), plain.lighting_output.download_mip(0), what + ": LightingOutput without a debug view")
+            same(plain_ao.lighting_output.download_mip(0), plain.lighting_output.download_mip(0), what + ": LightingOutput without a debug view")
     finally:
         for d in (base, drv, plain, plain_ao):
             d.release()
@@ -258,13 +242,10 @@ def test_frames_match_the_reference(dev, oracle, gt, lr, tmp_path, scene, render
 def test_ao_adds_its_dispatches_in_front_of_the_lighting_dispatch(dev, oracle, tmp_path):
     """ao=None records the parent's list, command for command, and launches the same kernels; ao=... adds exactly 2 + max(1, passes)
     dispatches between the G-buffer resolve's frame (the last HZB build) and the lighting dispatch; the refusals raise."""
-    from test_gpu_bloom import _recorded
-    from test_gpu_lighting import _gpu_scene, _op_counts
-    from test_gpu_sky import _city
     from toyrenderer_amd.frame import FrameDriver
     s, inst, vertices, mats, camera, kw = _city(oracle, tmp_path)
     kw = {k: v for k, v in kw.items() if k in ("dir_light", "camera_origin")}
-    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    gs = gpu_scene(dev, s, inst, vertices, mats)
     view = gltf_lite.view_of(camera, (320, 180))
     seen, counts = {}, {}
     try:
@@ -272,13 +253,13 @@ def test_ao_adds_its_dispatches_in_front_of_the_lighting_dispatch(dev, oracle, t
         for name, extra in variants:
             drv = FrameDriver(dev, gs, view, record_capacity=4096, lighting=True, **extra, **kw)
             try:
-                counts[name] = _op_counts(dev, drv)
-                seen[name] = _recorded(drv)
+                counts[name] = op_counts(dev, drv)
+                seen[name] = recorded(drv)
             finally:
                 drv.release()
         drv = FrameDriver(dev, gs, view, record_capacity=4096, gbuffer=True, ao={})       # the G-buffer alone is enough
         try:
-            seen["gbuffer"] = _recorded(drv)
+            seen["gbuffer"] = recorded(drv)
         finally:
             drv.release()
         with pytest.raises(ValueError, match="gbuffer=True"):
@@ -320,12 +301,7 @@ def test_host_path_over_three_frames(oracle, gt, tmp_path):
     P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
     inst_in = s.instances.copy()
     inst_in["m_MaterialDataIdx"] = sc0["instances"]["m_MaterialDataIdx"]
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(inst_in, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(v, s.meshletVertexIds, s.meshletTriangles)
-        r.load_materials(mats)
+    with host_renderer(s, inst_in, (v, s.meshletVertexIds, s.meshletTriangles), mats, render=render, max_groups=4096) as r:
         with pytest.raises(host.HostError, match="G-buffer is off"):
             r.set_ambient_occlusion(True)
         with pytest.raises(host.HostError, match="did not run"):
@@ -367,9 +343,7 @@ def test_host_path_over_three_frames(oracle, gt, tmp_path):
             assert r.gtao_consts().tobytes() == k.tobytes(), f
             assert lk["m_SSAOEnabled"][0] == 1
             ref = GR.frame(gt, k, gtao.main_pass_constants(V, full["quality"]), r.download_depth(), r.download_gbuffer_a(), full["denoise_passes"])
-            _same(r.download_ssao(), ref["ssao"], f"frame {f}: SSAO texture")
-    finally:
-        r.shutdown()
+            same(r.download_ssao(), ref["ssao"], f"frame {f}: SSAO texture")
 
 
 # ---- 6. misuse at the back end --------------------------------------------------------------------------------------------------------
@@ -443,11 +417,11 @@ def test_misuse_is_refused(dev, gt):
         dev.profile_enable(False)
         depth, g = GR.depth_images(W, H, seed=9)["checker"], GR.random_gbuffer(W, H, seed=9)
         ref = GR.frame(gt, k, main_push, depth, g, 1)
-        _same(p.prefilter(k, depth), ref["chain"], "a good prefilter after the refusals")
+        same(p.prefilter(k, depth), ref["chain"], "a good prefilter after the refusals")
         got = p.main(k, main_push, ref["chain"], g)
-        _same(got[0], ref["working_after_main"], "a good main pass after the refusals")
-        _same(got[1], ref["edges"], "its edges")
-        _same(p.denoise(k, 1, ref["working_after_main"], ref["edges"]), ref["ssao"], "a good denoise after the refusals")
+        same(got[0], ref["working_after_main"], "a good main pass after the refusals")
+        same(got[1], ref["edges"], "its edges")
+        same(p.denoise(k, 1, ref["working_after_main"], ref["edges"]), ref["ssao"], "a good denoise after the refusals")
     finally:
         dev.profile_enable(False)
         cl.release(); args.release(); p.release()

@@ -2,9 +2,7 @@
 tests/bloom_ref.c: single passes through rhi bindings at sizes around every tile edge, constants through push constants and b0,
 sources and destinations at non-zero mips, whole chains through FrameDriver(post=True, bloom_mips=...) and the C++ host mirror
 with the existing post reference behind them, and misuse.  Destinations are pre-filled so that a skipped texel shows."""
-import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -15,44 +13,15 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bloom_ref as BR  # noqa: E402
 import postprocess_ref as PR  # noqa: E402
 from gbuffer_scenes import with_normals_and_materials  # noqa: E402
+from suite_support import bits, bl, dev, gpu_scene, host_renderer, kernel_constant, lit_city, lit_cornell, op_counts, post_chain_reference, pr, recorded, same  # noqa: E402, F401
 from toyrenderer_amd import gltf_lite, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 from visibility_scenes import city  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 SENTINEL = 0x12345678
 RADII = (0.001, 0.005, 0.1)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def bl(tmp_path_factory):
-    return BR.load(tmp_path_factory.mktemp("bloom_ref"))
-
-
-@pytest.fixture(scope="module")
-def pr(tmp_path_factory):
-    return PR.load(tmp_path_factory.mktemp("postprocess_ref_for_bloom"))
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
-
-
-def _kernel_constant(name):
-    src = open(os.path.join(ROOT, "toyrenderer_amd", "csrc", "k_bloom.hip")).read()
-    return int(re.search(r"\b" + name + r" = (\d+)", src).group(1))
 
 
 def _consts(kind, src_dims, radius):
@@ -95,7 +64,7 @@ def _contents(W, H, seed):
 def _tile_edge_sizes():
     """Destination sizes one below, at and one above each edge of the kernels' tile, in both axes, two tiles included (more than
     one workgroup in each axis)."""
-    tw, th = _kernel_constant("kBloomTileW"), _kernel_constant("kBloomTileH")
+    tw, th = kernel_constant("k_bloom.hip", "kBloomTileW"), kernel_constant("k_bloom.hip", "kBloomTileH")
     return [(tw - 1, th - 1), (tw, th), (tw + 1, th + 1), (2 * tw - 1, 2 * th + 1), (2 * tw + 1, 2 * th - 1)]
 
 
@@ -141,7 +110,7 @@ def test_single_passes_match_the_reference(dev, bl, case):
                 _dispatch(cl, kind, _consts(kind, src_dims, radius), src, 0, dst, 0, dst_dims)
                 cl.close()
                 dev.execute(cl); dev.wait_idle()
-                _same(dst.download_mip(0), _reference(bl, kind, words, dst_dims, radius), f"{kind} {radius} {src_dims} -> {dst_dims} {name}")
+                same(dst.download_mip(0), _reference(bl, kind, words, dst_dims, radius), f"{kind} {radius} {src_dims} -> {dst_dims} {name}")
     finally:
         cl.release()
         for t in textures.values():
@@ -169,7 +138,7 @@ def test_decoupled_constants_and_large_radius(dev, bl):
             cl.close()
             dev.execute(cl); dev.wait_idle()
             want = BR.upsample(bl, words, radius, dst_dims) if kind == "up" else BR.downsample(bl, words, kind == "first", dest=dst_dims, inv=inv)
-            _same(dst.download_mip(0), want, f"{kind} inv {inv} radius {radius}")
+            same(dst.download_mip(0), want, f"{kind} inv {inv} radius {radius}")
     finally:
         cl.release(); src.release(); dst.release()
 
@@ -198,30 +167,19 @@ def test_passes_between_mips_of_one_texture(dev, bl, via):
             dev.execute(cl); dev.wait_idle()
             for k in range(mips):
                 want = words if k == s else _reference(bl, kind, words, dims[d], radius) if k == d else fill[k]
-                _same(t.download_mip(k), want, f"{via} {kind} mip {s} -> {d}: mip {k}")
+                same(t.download_mip(k), want, f"{via} {kind} mip {s} -> {d}: mip {k}")
     finally:
         cl.release(); t.release()
 
 
 # ---- 3. whole chains through FrameDriver ---------------------------------------------------------------------------------------
 def _cornell(oracle):
-    from test_gltf_cornell import _fixture
-    with open(os.path.join(ROOT, "tests", "golden", "cornell_materials.json")) as f:
-        cm = json.load(f)
-    _, s, camera = _fixture()
-    mats = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
-    s.materials, s.primMaterial = mats, np.array(cm["primitiveMaterial"], np.uint32)
-    inst = gltf_lite.apply_materials(s)
-    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
-    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
-    return s, inst, s.vertices, mats, camera, dict(dir_light=((0.3, -0.8, -0.52), 3.0), camera_origin=tuple(float(x) for x in camera.position),
-                                                   auto_exposure=(0.004, 12.0, 0.5))
+    *scene, camera = lit_cornell(oracle)
+    return (*scene, camera, dict(dir_light=((0.3, -0.8, -0.52), 3.0), camera_origin=tuple(float(x) for x in camera.position), auto_exposure=(0.004, 12.0, 0.5)))
 
 
 def _city(oracle, tmp_path):
-    s, sc = city(tmp_path, oracle)
-    v, sc, mats = with_normals_and_materials(s, sc)
-    return s, sc["instances"], v, mats, s.cameras[0], dict(dir_light=((0.2, -1.0, 0.3), 2.5))
+    return (*lit_city(oracle, tmp_path), dict(dir_light=((0.2, -1.0, 0.3), 2.5)))
 
 
 CHAINS = [("cornell", (320, 180), 6, 0.005, 0.1), ("city", (540, 270), 6, 0.005, 0.1), ("city", (67, 35), 2, 0.02, 0.5), ("city", (67, 35), 6, 0.1, 1.0)]
@@ -232,11 +190,9 @@ def test_frames_match_the_reference_chain(dev, oracle, bl, pr, tmp_path, scene, 
     """Three frames of FrameDriver(post=True, bloom_mips=mips) next to a bloom_mips=0 driver: every bloom mip equals bloom_chain of
     LightingOutput, the back buffer the existing post reference fed mip 0, the luminance carried; everything up to LightingOutput,
     the histogram, the luminance and the pipeline statistics equal the bloom_mips=0 run; the back buffers differ."""
-    from test_gpu_lighting import _gpu_scene
-    from test_gpu_postprocess import _bits, _post_chain_reference
     from toyrenderer_amd.frame import FrameDriver
     s, inst, vertices, mats, camera, kw = _cornell(oracle) if scene == "cornell" else _city(oracle, tmp_path)
-    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    gs = gpu_scene(dev, s, inst, vertices, mats)
     view = gltf_lite.view_of(camera, render)
     base = FrameDriver(dev, gs, view, record_capacity=4096, culling_flags=7, post=True, **kw)
     drv = FrameDriver(dev, gs, view, record_capacity=4096, culling_flags=7, post=True, bloom_mips=mips, bloom_filter_radius=radius, bloom_strength=strength, **kw)
@@ -253,66 +209,39 @@ def test_frames_match_the_reference_chain(dev, oracle, bl, pr, tmp_path, scene, 
             what = f"{scene} {render} frame {f}"
             lit = base.lighting_output.download_mip(0)
             for name in ("gbufferA", "visibility", "lighting_output"):
-                _same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
-            _same(drv.motion.download_mip(0).view(np.uint16), base.motion.download_mip(0).view(np.uint16), what + ": motion")
-            _same(drv.depth.download_mip(0).view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
-            _same(drv.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
-            _same(drv.histogram.download(np.uint32, 256), base.histogram.download(np.uint32, 256), what + ": histogram")
+                same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
+            same(drv.motion.download_mip(0).view(np.uint16), base.motion.download_mip(0).view(np.uint16), what + ": motion")
+            same(drv.depth.download_mip(0).view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
+            same(drv.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
+            same(drv.histogram.download(np.uint32, 256), base.histogram.download(np.uint32, 256), what + ": histogram")
             assert qd.get() == qb.get(), what + ": pipeline statistics"
             assert drv.bloom_consts.tobytes() == BR.pass_consts(*render, mips, radius).tobytes()
             chain = BR.bloom_chain(bl, lit, *render, mips, radius)
             for k in range(mips):
-                _same(drv.download_bloom(k), chain[k], f"{what}: bloom mip {k}")
+                same(drv.download_bloom(k), chain[k], f"{what}: bloom mip {k}")
             assert drv.post_consts[2].tobytes() == PR.post_params(render, bloom_strength=strength).tobytes()
-            back, _, luminance, _ = _post_chain_reference(pr, drv, lit, luminance, bloom=chain[0])
-            _same(drv.back_buffer.download_mip(0), back, what + ": back buffer")
-            assert _bits(drv.luminance.download(F, 1)).tolist() == _bits(luminance).tolist() == _bits(base.luminance.download(F, 1)).tolist()
+            back, _, luminance, _ = post_chain_reference(pr, drv, lit, luminance, bloom=chain[0])
+            same(drv.back_buffer.download_mip(0), back, what + ": back buffer")
+            assert bits(drv.luminance.download(F, 1)).tolist() == bits(luminance).tolist() == bits(base.luminance.download(F, 1)).tolist()
             assert np.count_nonzero(drv.back_buffer.download_mip(0) != base.back_buffer.download_mip(0)) > 0
     finally:
         qb.release(); qd.release(); drv.release(); base.release(); gs.release()
 
 
-class _Recorder:
-    """A proxy of rhi.CommandList that notes (method, shader name or None) of every command in order."""
-    def __init__(self, cl):
-        self.cl, self.seen = cl, []
-
-    def __getattr__(self, name):
-        fn = getattr(self.cl, name)
-        if name in ("open", "close", "constant_buffer"):
-            return fn
-
-        def call(*a, **kw):
-            self.seen.append((name, a[0] if name.startswith("dispatch") else None))
-            return fn(*a, **kw)
-        return call
-
-
-def _recorded(drv):
-    cl = drv.cl
-    drv.cl = _Recorder(cl)
-    try:
-        drv.record()
-        return drv.cl.seen
-    finally:
-        drv.cl = cl
-
-
 def test_bloom_adds_its_dispatches_between_lighting_and_the_histogram_clear(dev, oracle, tmp_path):
     """bloom_mips = 0 records the post=True list of the parent commit, command for command, and launches the same kernels;
     bloom_mips = m adds exactly m - 1 downsamples and m - 1 upsamples behind the lighting dispatch, in front of the histogram clear."""
-    from test_gpu_lighting import _gpu_scene, _op_counts
     from toyrenderer_amd.frame import FrameDriver
     s, inst, vertices, mats, camera, kw = _city(oracle, tmp_path)
-    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    gs = gpu_scene(dev, s, inst, vertices, mats)
     view = gltf_lite.view_of(camera, (320, 180))
     seen, counts = {}, {}
     try:
         for name, extra in (("post", {}), ("zero", dict(bloom_mips=0, bloom_filter_radius=0.3, bloom_strength=0.9)), ("five", dict(bloom_mips=5))):
             drv = FrameDriver(dev, gs, view, record_capacity=4096, post=True, **extra, **kw)
             try:
-                counts[name] = _op_counts(dev, drv)
-                seen[name] = _recorded(drv)
+                counts[name] = op_counts(dev, drv)
+                seen[name] = recorded(drv)
                 if name == "zero":
                     assert drv.bloom_texture is None and drv.post_consts[2].tobytes() == PR.post_params((320, 180)).tobytes()
                     with pytest.raises(ValueError, match="bloom generation is off"):
@@ -334,7 +263,6 @@ def test_host_path_over_three_frames(oracle, bl, pr, tmp_path):
     """The C++ host mirror with a moving camera: frame 0 bloom on (6 mips), frame 1 off, frame 2 on with other parameters.
     trhost_download_bloom and the back buffer equal the reference chain of the frame's own LightingOutput, the luminance carried;
     trhost_get_bloom_consts is bit for bit; generation and an uploaded bloom texture refuse each other."""
-    from test_gpu_postprocess import _bits
     from toyrenderer_amd import host
     s, sc0 = city(tmp_path, oracle)
     v, sc0, mats = with_normals_and_materials(s, sc0)
@@ -344,12 +272,7 @@ def test_host_path_over_three_frames(oracle, bl, pr, tmp_path):
     inst_in = s.instances.copy()
     inst_in["m_MaterialDataIdx"] = sc0["instances"]["m_MaterialDataIdx"]
     uploaded = PR.seeded_finite_words(render[0] * render[1], 91).reshape(render[1], render[0])
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(inst_in, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(v, s.meshletVertexIds, s.meshletTriangles)
-        r.load_materials(mats)
+    with host_renderer(s, inst_in, (v, s.meshletVertexIds, s.meshletTriangles), mats, render=render, max_groups=4096) as r:
         with pytest.raises(host.HostError, match="post-processing is off"):
             r.set_bloom(True)
         r.set_post_process(True)
@@ -394,7 +317,7 @@ def test_host_path_over_three_frames(oracle, bl, pr, tmp_path):
             luminance, _ = PR.adapt_exposure(pr, ak, PR.histogram(pr, lit, hk), luminance)
             if setting is None:
                 assert pk.tobytes() == PR.post_params(render).tobytes()
-                _same(r.download_back_buffer(), PR.post(pr, pk, lit, luminance_in=luminance), f"frame {f}: back buffer without bloom")
+                same(r.download_back_buffer(), PR.post(pr, pk, lit, luminance_in=luminance), f"frame {f}: back buffer without bloom")
                 with pytest.raises(host.HostError, match="did not run"):
                     r.bloom_consts(1)
             else:
@@ -405,11 +328,9 @@ def test_host_path_over_three_frames(oracle, bl, pr, tmp_path):
                     r.bloom_consts(2 * (mips - 1) + 1)
                 chain = BR.bloom_chain(bl, lit, *render, mips, radius)
                 for k in range(mips):
-                    _same(r.download_bloom(k), chain[k], f"frame {f}: bloom mip {k}")
-                _same(r.download_back_buffer(), PR.post(pr, pk, lit, bloom=chain[0], luminance_in=luminance), f"frame {f}: back buffer")
-            assert _bits(r.scene_luminance()[0]).tolist() == _bits(luminance).tolist(), f
-    finally:
-        r.shutdown()
+                    same(r.download_bloom(k), chain[k], f"frame {f}: bloom mip {k}")
+                same(r.download_back_buffer(), PR.post(pr, pk, lit, bloom=chain[0], luminance_in=luminance), f"frame {f}: back buffer")
+            assert bits(r.scene_luminance()[0]).tolist() == bits(luminance).tolist(), f
 
 
 # ---- 5. misuse at the back end --------------------------------------------------------------------------------------------------
@@ -464,7 +385,7 @@ def test_misuse_is_refused(dev, bl):
         cl.dispatch("bloom_PS_Downsample", [PUSH(0), TEX_SRV(0, src), TEX_UAV(0, dst, 0), SAMPLER(0), SAMPLER(3)], groups, push=k)
         cl.close()
         dev.execute(cl); dev.wait_idle()
-        _same(dst.download_mip(0), BR.downsample(bl, words, False), "a good pass after the refusals")
+        same(dst.download_mip(0), BR.downsample(bl, words, False), "a good pass after the refusals")
     finally:
         dev.profile_enable(False)
         cl.release(); args.release()

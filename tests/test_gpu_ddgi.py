@@ -14,6 +14,8 @@ import ddgi_ref as DR  # noqa: E402
 import ddgi_scenes as DS  # noqa: E402
 import lighting_ref as LR  # noqa: E402
 import lighting_scenes as LS  # noqa: E402
+import sky_ref as SK  # noqa: E402
+from suite_support import dev, dg, gpu_scene, host_renderer, lit_cornell, lr, same  # noqa: E402, F401
 from toyrenderer_amd import ddgi, gltf_lite  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
@@ -22,27 +24,11 @@ F = np.float32
 LIGHT = ((0.3, -2.5, 1.0), 2.0)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def dg(tmp_path_factory):
-    return DR.load(tmp_path_factory.mktemp("ddgi_ref"))
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref"))
-
-
-def _same(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
+# the lit Cornell box of tests/test_gpu_sky.py, with its light
+def _cornell(oracle):
+    *scene, camera = lit_cornell(oracle)
+    return (*scene, camera, dict(dir_light=(tuple(float(x) for x in SK.unit((0.3, 0.8, -0.52))), 3.0), camera_origin=tuple(float(x) for x in camera.position),
+                                 auto_exposure=(0.004, 12.0, 0.5)))
 
 
 class Pass:
@@ -224,13 +210,13 @@ def test_synthetic_gbuffer_matches_the_reference(ps, dg, name):
                 k = ps.consts(debug_mode=10 if debug else 0, ssao_enabled=ssao_enabled, m_bRTDDGIEnabled=0 if debug else 1)
                 got = ps.run(k, debug, desc_copy=vol.desc(), volume=res, ssao=ssao_bound)
                 want = DR.lighting(dg, k, vol, ps.g, ps.depth, debug=debug, motion=ps.motion, ssao=ps.ssao if ssao_bound else None, shadow=ps.shadow, out_init=init)
-                _same(got, want, f"{name} debug={debug} ssao bound={ssao_bound} enabled={ssao_enabled}")
+                same(got, want, f"{name} debug={debug} ssao bound={ssao_bound} enabled={ssao_enabled}")
                 assert np.all(got[~lit] == LS.SENTINEL) and np.count_nonzero(got[lit] != LS.SENTINEL) > 1900
                 seen.add(got.tobytes())
     assert len(seen) == 3                    # view 10; PS_Main without AO (enabled 0, or unbound = 255); PS_Main with the SSAO texture
     # the flag set at the debug entry in another view: validated, then the view's own words
     k = ps.consts(debug_mode=4, m_bRTDDGIEnabled=1)
-    _same(ps.run(k, True, desc_copy=vol.desc(), volume=res), DR.lighting(dg, k, vol, ps.g, ps.depth, debug=True, motion=ps.motion, ssao=ps.ssao, shadow=ps.shadow, out_init=init), "view 4")
+    same(ps.run(k, True, desc_copy=vol.desc(), volume=res), DR.lighting(dg, k, vol, ps.g, ps.depth, debug=True, motion=ps.motion, ssao=ps.ssao, shadow=ps.shadow, out_init=init), "view 4")
 
 
 def test_relocation_and_classification_flags(ps, dg):
@@ -246,7 +232,7 @@ def test_relocation_and_classification_flags(ps, dg):
             res[0].upload(vol.desc().view(np.uint8))
             want = DR.lighting(dg, k, vol, ps.g, ps.depth, ssao=ps.ssao, shadow=ps.shadow, out_init=init)
             assert np.count_nonzero(want != base) > 100
-            _same(ps.run(k, False, desc_copy=vol.desc(), volume=res), want, f"relocation={reloc} classification={classify}")
+            same(ps.run(k, False, desc_copy=vol.desc(), volume=res), want, f"relocation={reloc} classification={classify}")
     finally:
         vol.relocation = vol.classification = True
         res[0].upload(vol.desc().view(np.uint8))
@@ -260,12 +246,12 @@ def test_ddgi_off_is_todays_pass(ps, lr):
     for debug, mode in ((False, 0), (True, 9), (True, 4)):
         k = ps.consts(debug_mode=mode, ssao_enabled=1)
         want = LR.lighting(lr, k, ps.g, ps.depth, debug=debug, motion=ps.motion, ssao=ps.ssao, shadow=ps.shadow, out_init=init)
-        _same(ps.run(k, debug, desc_copy=vol.desc(), volume=res), want, f"flag 0, mode {mode}, volume bound")
-        _same(ps.run(k, debug), want, f"flag 0, mode {mode}, nothing bound")
+        same(ps.run(k, debug, desc_copy=vol.desc(), volume=res), want, f"flag 0, mode {mode}, volume bound")
+        same(ps.run(k, debug), want, f"flag 0, mode {mode}, nothing bound")
         # a volume that would be refused is not looked at either
         bad = vol.desc().copy()
         bad["probeCounts"] = (0, 0, 0)
-        _same(ps.run(k, debug, desc_copy=bad, volume=res), want, f"flag 0, mode {mode}, bad descriptor ignored")
+        same(ps.run(k, debug, desc_copy=bad, volume=res), want, f"flag 0, mode {mode}, bad descriptor ignored")
 
 
 # ---- 3. misuse ------------------------------------------------------------------------------------------------------------------
@@ -343,12 +329,10 @@ def test_cornell_through_the_driver(dev, oracle, dg):
     """The cornell fixture at 160 x 90 through FrameDriver(lighting=True, ao={...}, ddgi=Volume.uniform(...)): LightingOutput equals
     the reference fed the frame's own depth, GBufferA and SSAO texture; m_bRTDDGIEnabled is 1; and with AO on LightingOutput
     differs from AO off, which it could not before the ambient term.  View 10 shows the irradiance."""
-    from test_gpu_lighting import _gpu_scene
-    from test_gpu_sky import _cornell
     from toyrenderer_amd.frame import FrameDriver
     s, inst, vertices, mats, camera, kw = _cornell(oracle)
     kw = {k: v for k, v in kw.items() if k in ("dir_light", "camera_origin")}
-    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    gs = gpu_scene(dev, s, inst, vertices, mats)
     render = (160, 90)
     view = gltf_lite.view_of(camera, render)
     vol = cornell_volume(camera)
@@ -369,9 +353,9 @@ def test_cornell_through_the_driver(dev, oracle, dg):
         depth, g, ssao = on.depth.download_mip(0), on.gbufferA.download_mip(0), on.download_ssao()
         assert on.lighting_consts["m_bRTDDGIEnabled"][0] == 1 and on.lighting_consts["m_SSAOEnabled"][0] == 1 and on.lighting_consts.nbytes == 112
         assert drivers["off"].lighting_consts["m_bRTDDGIEnabled"][0] == 0
-        _same(out["on"], DR.lighting(dg, on.lighting_consts, vol, g, depth, ssao=ssao), "cornell, AO and DDGI")
-        _same(out["no_ao"], DR.lighting(dg, drivers["no_ao"].lighting_consts, vol, g, depth), "cornell, DDGI without AO")
-        _same(out["view10"], DR.lighting(dg, drivers["view10"].lighting_consts, vol, g, depth, motion=drivers["view10"].motion.download_mip(0)), "cornell, view 10")
+        same(out["on"], DR.lighting(dg, on.lighting_consts, vol, g, depth, ssao=ssao), "cornell, AO and DDGI")
+        same(out["no_ao"], DR.lighting(dg, drivers["no_ao"].lighting_consts, vol, g, depth), "cornell, DDGI without AO")
+        same(out["view10"], DR.lighting(dg, drivers["view10"].lighting_consts, vol, g, depth, motion=drivers["view10"].motion.download_mip(0)), "cornell, view 10")
         lit = depth > 0
         assert lit.sum() > 0.2 * lit.size
         assert np.count_nonzero(out["on"][lit] != out["no_ao"][lit]) > 0, "the SSAO texture changes LightingOutput"
@@ -393,18 +377,12 @@ def test_cornell_through_the_host_mirror(oracle, dg):
     trhost_upload_ddgi_volume and trhost_set_ddgi(1) the consts show m_bRTDDGIEnabled = 1 and LightingOutput equals the reference fed
     the frame's own depth, GBufferA and SSAO texture; AO on differs from AO off; view 10 shows the irradiance; dropping the
     volume brings back the pass without the term."""
-    from test_gpu_sky import _cornell
     from toyrenderer_amd import host
     s, inst, vertices, mats, camera, kw = _cornell(oracle)
     render = (160, 90)
     view = gltf_lite.view_of(camera, render)
     vol = cornell_volume(camera)
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(gltf_lite.apply_materials(s), s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(s.vertices, s.meshletVertexIds, s.meshletTriangles)
-        r.load_materials(mats)
+    with host_renderer(s, gltf_lite.apply_materials(s), (s.vertices, s.meshletVertexIds, s.meshletTriangles), mats, render=render, max_groups=4096) as r:
         r.set_deferred_lighting(True)
         r.set_directional_light(*kw["dir_light"])
         r.set_culling(7)
@@ -427,20 +405,20 @@ def test_cornell_through_the_host_mirror(oracle, dg):
         r.upload_ddgi_volume(vol)
         r.frame(); r.results()
         assert r.deferred_lighting_consts()["m_bRTDDGIEnabled"][0] == 0                     # uploaded, not enabled: bound and ignored
-        _same(r.download_lighting_output(), off, "host: volume uploaded, DDGI off")
+        same(r.download_lighting_output(), off, "host: volume uploaded, DDGI off")
         r.set_ddgi(True)
         r.frame(); r.results()
         k = r.deferred_lighting_consts()
         assert k["m_bRTDDGIEnabled"][0] == 1 and k["m_SSAOEnabled"][0] == 0
         no_ao = r.download_lighting_output()
-        _same(no_ao, DR.lighting(dg, k, vol, g, depth), "host: DDGI without AO")
+        same(no_ao, DR.lighting(dg, k, vol, g, depth), "host: DDGI without AO")
         assert np.count_nonzero(no_ao[lit] != off[lit]) > 0.5 * lit.sum()
         r.set_ambient_occlusion(True, quality=1, denoise_passes=1)
         r.frame(); r.results()
         k = r.deferred_lighting_consts()
         assert k["m_bRTDDGIEnabled"][0] == 1 and k["m_SSAOEnabled"][0] == 1
         with_ao = r.download_lighting_output()
-        _same(with_ao, DR.lighting(dg, k, vol, g, depth, ssao=r.download_ssao()), "host: DDGI with AO")
+        same(with_ao, DR.lighting(dg, k, vol, g, depth, ssao=r.download_ssao()), "host: DDGI with AO")
         assert np.count_nonzero(with_ao[lit] != no_ao[lit]) > 0, "the SSAO texture changes LightingOutput"
         r.set_ambient_occlusion(False)
         r.set_debug_view_mode(10)
@@ -449,13 +427,11 @@ def test_cornell_through_the_host_mirror(oracle, dg):
         assert k["m_DebugMode"][0] == 10
         shown = r.download_lighting_output()
         want = DR.lighting(dg, k, vol, r.download_gbuffer_a(), depth, debug=True)
-        _same(shown, want, "host: view 10")
+        same(shown, want, "host: view 10")
         with pytest.raises(host.HostError, match="Ambient"):
             r.upload_ddgi_volume(None)
         r.set_debug_view_mode(0)
         r.upload_ddgi_volume(None)
         r.frame(); r.results()
         assert r.deferred_lighting_consts()["m_bRTDDGIEnabled"][0] == 0
-        _same(r.download_lighting_output(), off, "host: volume dropped")
-    finally:
-        r.shutdown()
+        same(r.download_lighting_output(), off, "host: volume dropped")

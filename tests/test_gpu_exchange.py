@@ -12,18 +12,11 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from exchange_ref import expand_masks_np, pack_shard_np, unpack_shards_np  # noqa: E402
+from suite_support import dev  # noqa: E402, F401
 
 from toyrenderer_amd import gather, synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
 
 
 def _pack_state(dev, slot_groups):

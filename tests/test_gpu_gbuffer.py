@@ -13,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import gbuffer_ref as GR  # noqa: E402
+from suite_support import compare_frame, dev, gpu_scene, gr, host_renderer, lit_cornell, op_counts, same, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from gbuffer_scenes import hostile_materials, wall, with_normals_and_materials  # noqa: E402
 from toyrenderer_amd import gltf_lite, synth  # noqa: E402
@@ -22,38 +23,6 @@ from visibility_scenes import city, consts, hostile_soup, inside_view, with_dupl
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEBUG_MODES = (0, 2, 3, 12)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
-
-
-@pytest.fixture(scope="module")
-def gr(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gbuffer_ref"))
-
-
-def _gpu_scene(dev, s, inst, vertices, materials):
-    from toyrenderer_amd.frame import GpuScene
-    gs = GpuScene(dev, inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-    gs.set_geometry(vertices, s.meshletVertexIds, s.meshletTriangles)
-    if materials is not None:
-        gs.set_materials(materials)
-    return gs
-
-
-def _same(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
 
 
 def _random_byte(seeds):
@@ -67,11 +36,10 @@ def test_frames_match_the_reference_under_every_flag(dev, oracle, vr, gr, tmp_pa
     """Two frames of a moving camera, one gbuffer=True driver per debug mode next to a visibility=True driver: GBufferA and
     motion equal the reference in every texel; the motion target, depth, HZB, every cull output, the visibility texels
     and the pipeline statistics equal the visibility=True run."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
     v, sc, mats = with_normals_and_materials(s, sc)
-    gs = _gpu_scene(dev, s, sc["instances"], v, mats)
+    gs = gpu_scene(dev, s, sc["instances"], v, mats)
     cam = s.cameras[0]
     render = (640, 360)
     P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
@@ -95,24 +63,24 @@ def test_frames_match_the_reference_under_every_flag(dev, oracle, vr, gr, tmp_pa
             got_base = base.results()
             ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=flags, record_capacity=4096,
                                raster=(I.world_to_clip(V, P), v, s.meshletVertexIds, s.meshletTriangles))
-            _compare_frame(got_base, ref)
+            compare_frame(got_base, ref)
             k = consts(view)
             vis_ref, _ = VR.frame_visibility(vr, k, geo, ref, *render)
             base_vis, base_depth, base_motion, base_hzb = base.visibility.download_mip(0), base.depth.download_mip(0), base.motion.download_mip(0), base.hzb.download_chain()
-            _same(base_vis, vis_ref, f"flags {flags} frame {f}: visibility=True texels")
+            same(base_vis, vis_ref, f"flags {flags} frame {f}: visibility=True texels")
             stats = queries[None].get()
             for m, d in drivers.items():
                 what = f"flags {flags} frame {f} debug mode {m}"
-                _compare_frame(d.results(), ref)
+                compare_frame(d.results(), ref)
                 g_ref, m_ref = GR.frame_gbuffer(gr, k, geo, ref, vis_ref, mats, m)
                 g = d.gbufferA.download_mip(0)
-                _same(g, g_ref, what + ": GBufferA")
+                same(g, g_ref, what + ": GBufferA")
                 mot = d.motion.download_mip(0).view(np.uint16)
-                _same(mot, VR.to_half_bits(m_ref), what + ": motion against the reference")
-                _same(mot, base_motion.view(np.uint16), what + ": motion against the visibility=True run")
-                _same(d.visibility.download_mip(0), base_vis, what + ": visibility texels")
-                _same(d.depth.download_mip(0).view(np.uint32), base_depth.view(np.uint32), what + ": depth")
-                _same(d.hzb.download_chain(), base_hzb, what + ": HZB")
+                same(mot, VR.to_half_bits(m_ref), what + ": motion against the reference")
+                same(mot, base_motion.view(np.uint16), what + ": motion against the visibility=True run")
+                same(d.visibility.download_mip(0), base_vis, what + ": visibility texels")
+                same(d.depth.download_mip(0).view(np.uint32), base_depth.view(np.uint32), what + ": depth")
+                same(d.hzb.download_chain(), base_hzb, what + ": HZB")
                 if flags & 2:
                     got = d.results()
                     assert got["lateCount"] == got_base["lateCount"] and np.array_equal(got["lateArgs"], got_base["lateArgs"])
@@ -219,7 +187,7 @@ def test_near_wall_with_exact_ties(dev, oracle, vr, gr, tmp_path):
     for mode in (3, 2):
         vis, g, mot, mot2, prof = _direct(dev, k, sc, v, s.meshletVertexIds, s.meshletTriangles, rec, lst, render, mats, slot=2, debug_mode=mode, profile=True)
         rvis, rg, rmot = _reference(vr, gr, k, sc, v, s.meshletVertexIds, s.meshletTriangles, rec, lst, render, mats, slot=2, debug_mode=mode)
-        _same(vis, rvis, "texels"); _same(g, rg, f"GBufferA, debug mode {mode}"); _same(mot, rmot, "motion"); _same(mot2, mot, "motion shader's words")
+        same(vis, rvis, "texels"); same(g, rg, f"GBufferA, debug mode {mode}"); same(mot, rmot, "motion"); same(mot2, mot, "motion shader's words")
         assert {n_ for n_ in prof if n_.startswith("basepass_PS")} == {"basepass_PS_Main_GBuffer#main", "basepass_PS_Main_motion#main"}
         assert prof["basepass_PS_Main_GBuffer#main"][0] == 1
     cov = vis != 0
@@ -245,7 +213,7 @@ def test_hostile_soup(dev, vr, gr, seed):
     k = consts(synth.make_view(render=render))
     vis, g, mot, mot2, _ = _direct(dev, k, sc, v, vid, tri, rec, lst, render, mats, slot=3, debug_mode=2, clear_to=0xABCD1234)
     rvis, rg, rmot = _reference(vr, gr, k, sc, v, vid, tri, rec, lst, render, mats, slot=3, debug_mode=2, clear_to=0xABCD1234)
-    _same(vis, rvis, "texels"); _same(g, rg, "GBufferA"); _same(mot, rmot, "motion")
+    same(vis, rvis, "texels"); same(g, rg, "GBufferA"); same(mot, rmot, "motion")
     cov = vis != 0
     assert cov.sum() > 1000 and np.all(g[~cov] == 0xABCD1234)
     _, _, pos, _ = VR.decode(vis)
@@ -253,10 +221,10 @@ def test_hostile_soup(dev, vr, gr, seed):
     assert second.any() and (cov & ~second).any()
     if seed % 2:
         assert np.all(g[second] == 0xABCD1234) and np.all(mot[second] == 0), "an out-of-range material index leaves both targets"
-        _same(mot[~second], mot2[~second], "motion shader's words")
+        same(mot[~second], mot2[~second], "motion shader's words")
     else:
         assert np.all(g[cov][:, 3] == 0xFF)
-        _same(mot, mot2, "motion shader's words")
+        same(mot, mot2, "motion shader's words")
 
 
 def test_degenerate_world_matrix_gives_nan_normals(dev, vr, gr):
@@ -269,7 +237,7 @@ def test_degenerate_world_matrix_gives_nan_normals(dev, vr, gr):
     mats = synth.materials(3, 4)
     vis, g, mot, mot2, _ = _direct(dev, k, sc, v, vid, tri, rec, lst, render, mats)
     rvis, rg, rmot = _reference(vr, gr, k, sc, v, vid, tri, rec, lst, render, mats)
-    _same(vis, rvis, "texels"); _same(g, rg, "GBufferA"); _same(mot, rmot, "motion"); _same(mot2, mot, "motion shader's words")
+    same(vis, rvis, "texels"); same(g, rg, "GBufferA"); same(mot, rmot, "motion"); same(mot2, mot, "motion shader's words")
     cov = vis != 0
     assert cov.sum() > 1000
     n = GR.vertex_normal(gr, 0x2FF7FDFF, sc["instances"]["m_WorldMatrix"][0])
@@ -286,7 +254,7 @@ def test_wall_normals_on_the_gpu(dev, vr, gr):
     mats = synth.materials(1, 4)
     vis, g, mot, mot2, _ = _direct(dev, k, sc, v, vid, tri, rec, lst, render, mats)
     rvis, rg, rmot = _reference(vr, gr, k, sc, v, vid, tri, rec, lst, render, mats)
-    _same(vis, rvis, "texels"); _same(g, rg, "GBufferA"); _same(mot, rmot, "motion")
+    same(vis, rvis, "texels"); same(g, rg, "GBufferA"); same(mot, rmot, "motion")
     cov = vis != 0
     u = np.array([(word >> 20) & 0x3FF, (word >> 10) & 0x3FF, word & 0x3FF], np.float64) / 1023.0 * 2.0 - 1.0
     Wm = sc["instances"]["m_WorldMatrix"][0].astype(np.float64)[:3, :3]
@@ -302,7 +270,7 @@ def test_animated_frames_with_alpha_mask_slots(dev, oracle, vr, gr, tmp_path):
     assert len(s.alphaMaskIds) > 0
     v, sc, mats = with_normals_and_materials(s, sc)
     inst0 = sc["instances"].copy()
-    gs = _gpu_scene(dev, s, inst0, v, mats)
+    gs = gpu_scene(dev, s, inst0, v, mats)
     cam = s.cameras[0]
     render = (640, 360)
     P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
@@ -330,26 +298,17 @@ def test_animated_frames_with_alpha_mask_slots(dev, oracle, vr, gr, tmp_path):
             k = consts(view)
             geo = VR.Geometry(scf, *geo_v)
             vis_ref, _ = VR.frame_visibility(vr, k, geo, ref, *render)
-            _same(drv.visibility.download_mip(0), vis_ref, f"frame {f}: texels")
+            same(drv.visibility.download_mip(0), vis_ref, f"frame {f}: texels")
             g_ref, m_ref = GR.frame_gbuffer(gr, k, geo, ref, vis_ref, mats, 3)
-            _same(drv.gbufferA.download_mip(0), g_ref, f"frame {f}: GBufferA")
+            same(drv.gbufferA.download_mip(0), g_ref, f"frame {f}: GBufferA")
             m = drv.motion.download_mip(0).view(np.uint16)
-            _same(m, VR.to_half_bits(m_ref), f"frame {f}: motion")
+            same(m, VR.to_half_bits(m_ref), f"frame {f}: motion")
             slots_seen |= set(np.unique(VR.decode(vis_ref[vis_ref != 0])[1]).tolist())
             if f > 0:
                 assert np.count_nonzero(m) > 0.2 * vis_ref.size
         assert {0, 2} <= slots_seen, slots_seen
     finally:
         drv.release(); gs.release()
-
-
-def _op_counts(dev, drv):
-    dev.profile_reset(); dev.profile_enable(True)
-    try:
-        drv.record(); drv.run(); drv.results()
-        return {n: c for n, (c, _) in dev.profile().items()}
-    finally:
-        dev.profile_enable(False)
 
 
 def test_lists_without_the_feature_record_the_same_ops(dev, oracle, tmp_path):
@@ -359,14 +318,14 @@ def test_lists_without_the_feature_record_the_same_ops(dev, oracle, tmp_path):
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
     v, sc, mats = with_normals_and_materials(s, sc)
-    gs = _gpu_scene(dev, s, sc["instances"], v, mats)
+    gs = gpu_scene(dev, s, sc["instances"], v, mats)
     view = gltf_lite.view_of(s.cameras[0], (320, 180))
     out = {}
     try:
         for name, kw in (("depth", dict(raster_depth=True)), ("visibility", dict(visibility=True)), ("gbuffer", dict(gbuffer=True))):
             drv = FrameDriver(dev, gs, view, record_capacity=4096, **kw)
             try:
-                out[name] = _op_counts(dev, drv)
+                out[name] = op_counts(dev, drv)
             finally:
                 drv.release()
     finally:
@@ -386,21 +345,15 @@ def test_lists_without_the_feature_record_the_same_ops(dev, oracle, tmp_path):
 def test_cornell_walls_through_the_driver_and_the_facade(dev, oracle, vr, gr):
     """FrameDriver(gbuffer=True) on the cornell fixture: GBufferA equals the reference, its albedo shows the white, red and
     green walls, and the host mirror's trhost_download_gbuffer_a returns the same words."""
-    from test_gltf_cornell import _fixture
     from toyrenderer_amd import host
     from toyrenderer_amd.frame import FrameDriver
+    s, inst, _, mats, camera = lit_cornell(oracle)
     with open(os.path.join(ROOT, "tests", "golden", "cornell_materials.json")) as f:
         cm = json.load(f)
-    _, s, camera = _fixture()
-    mats = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
-    s.materials, s.primMaterial = mats, np.array(cm["primitiveMaterial"], np.uint32)
-    inst = gltf_lite.apply_materials(s)
-    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
-    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
     sc = dict(s.as_oracle()); sc["instances"] = inst
     render = (320, 180)
     view = gltf_lite.view_of(camera, render)
-    gs = _gpu_scene(dev, s, inst, s.vertices, mats)
+    gs = gpu_scene(dev, s, inst, s.vertices, mats)
     drv = FrameDriver(dev, gs, view, record_capacity=4096, culling_flags=7, gbuffer=True)
     geo_v = (s.vertices, s.meshletVertexIds, s.meshletTriangles)
     try:
@@ -412,7 +365,7 @@ def test_cornell_walls_through_the_driver_and_the_facade(dev, oracle, vr, gr):
         vis_ref, _ = VR.frame_visibility(vr, k, geo, ref, *render)
         g_ref, _ = GR.frame_gbuffer(gr, k, geo, ref, vis_ref, mats)
         g = drv.gbufferA.download_mip(0)
-        _same(drv.visibility.download_mip(0), vis_ref, "texels"); _same(g, g_ref, "GBufferA")
+        same(drv.visibility.download_mip(0), vis_ref, "texels"); same(g, g_ref, "GBufferA")
     finally:
         drv.release(); gs.release()
     cov = vis_ref != 0
@@ -420,28 +373,20 @@ def test_cornell_walls_through_the_driver_and_the_facade(dev, oracle, vr, gr):
     got = GR.albedo_bytes(g[cov][:, 0])
     counts = [int(np.count_nonzero(np.all(got == np.array(c), axis=1))) for c in colours]
     assert sum(counts) == int(cov.sum()) and all(c > 1000 for c in counts), counts
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(gltf_lite.apply_materials(s), s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(*geo_v)
-        r.load_materials(mats)
+    with host_renderer(s, gltf_lite.apply_materials(s), geo_v, mats, render=render, max_groups=4096) as r:
         r.set_gbuffer(True)
         r.set_culling(7)
         r.set_node_transforms(s.nodes)
         r.set_camera(view)
         r.frame(); r.results()
-        _same(r.download_visibility(), vis_ref, "host: texels")
-        _same(r.download_gbuffer_a(), g, "host: GBufferA")
-    finally:
-        r.shutdown()
+        same(r.download_visibility(), vis_ref, "host: texels")
+        same(r.download_gbuffer_a(), g, "host: GBufferA")
 
 
 def test_host_path_with_animated_nodes(oracle, vr, gr, tmp_path):
     """The C++ host mirror (trhost_set_gbuffer): five frames with animated node transforms, a moving camera and a debug view
     mode that changes between frames.  GBufferA equals the reference computed from Renderer.instances() and each frame's
     view; motion too from the second frame on (the first frame's previous projection is the host's initial one)."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd import host
     s, sc0 = city(tmp_path, oracle)
     v, sc0, mats = with_normals_and_materials(s, sc0)
@@ -453,11 +398,7 @@ def test_host_path_with_animated_nodes(oracle, vr, gr, tmp_path):
     geo_v = (v, s.meshletVertexIds, s.meshletTriangles)
     inst_in = s.instances.copy()
     inst_in["m_MaterialDataIdx"] = sc0["instances"]["m_MaterialDataIdx"]
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(inst_in, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(*geo_v)
+    with host_renderer(s, inst_in, geo_v, render=render, max_groups=4096) as r:
         with pytest.raises(host.HostError, match="trhost_load_materials"):
             r.set_gbuffer(True)
         textured = mats.copy(); textured["m_MaterialFlags"][5] = I.MaterialFlag_UseNormalTexture
@@ -483,21 +424,19 @@ def test_host_path_with_animated_nodes(oracle, vr, gr, tmp_path):
             sc = dict(s.as_oracle()); sc["instances"] = inst
             ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=7, record_capacity=4096, maxGroups=4096,
                                raster=(I.world_to_clip(V, P), *geo_v))
-            _compare_frame(got, ref)
+            compare_frame(got, ref)
             k = consts(view)
             geo = VR.Geometry(sc, *geo_v)
             vis_ref, _ = VR.frame_visibility(vr, k, geo, ref, *render)
-            _same(r.download_visibility(), vis_ref, f"frame {f}: texels")
+            same(r.download_visibility(), vis_ref, f"frame {f}: texels")
             g_ref, m_ref = GR.frame_gbuffer(gr, k, geo, ref, vis_ref, mats, mode)
             g = r.download_gbuffer_a()
-            _same(g, g_ref, f"frame {f} (debug view {mode}): GBufferA")
+            same(g, g_ref, f"frame {f} (debug view {mode}): GBufferA")
             assert np.count_nonzero(g[..., 3]) > 0.2 * vis_ref.size
             if f > 0:
-                _same(r.download_motion().view(np.uint16), VR.to_half_bits(m_ref), f"frame {f}: motion")
+                same(r.download_motion().view(np.uint16), VR.to_half_bits(m_ref), f"frame {f}: motion")
         with pytest.raises(host.HostError, match="per rank"):
             host._check(host.load().trhost_exchange_create(ctypes.byref(host.ExchangeDesc())))
-    finally:
-        r.shutdown()
 
 
 def test_misuse_is_refused(dev, oracle, tmp_path):
@@ -560,7 +499,7 @@ def test_misuse_is_refused(dev, oracle, tmp_path):
         dev.create_texture(W, H, 2, rhi.FORMAT_RGBA32_UINT, "two mips")
     s, scc = city(tmp_path, oracle)
     v2, scc, mats = with_normals_and_materials(s, scc)
-    gs = _gpu_scene(dev, s, scc["instances"], v2, None)
+    gs = gpu_scene(dev, s, scc["instances"], v2, None)
     view = gltf_lite.view_of(s.cameras[0], (64, 32))
     try:
         with pytest.raises(ValueError, match="set_materials"):

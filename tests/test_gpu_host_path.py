@@ -216,9 +216,9 @@ def test_cornell_scene_through_the_drop_in_path(oracle, flags):
     import os
     import sys
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    from test_gltf_cornell import _cull, _fixture
+    from suite_support import cornell_fixture, cpu_cull
     from toyrenderer_amd import gltf_lite
-    z, scene, camera = _fixture()
+    z, scene, camera = cornell_fixture()
     view = gltf_lite.view_of(camera, (1920, 1080))
     with _Ctx((1920, 1080)) as r:
         r.load_scene(scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
@@ -232,7 +232,7 @@ def test_cornell_scene_through_the_drop_in_path(oracle, flags):
             r.frame()
         got = r.results()
         assert np.array_equal(r.instances(3)["m_WorldMatrix"], z[f"world_{flags}"])
-    inst, ref = _cull(oracle, scene, view, flags)
+    inst, ref = cpu_cull(oracle, scene, view, flags)
     for s in (0, 1):
         if f"f{flags}_s{s}_records" not in z.files:
             continue

@@ -23,10 +23,13 @@ import sys
 import numpy as np
 import pytest
 
-from toyrenderer_amd import interop as I
-from toyrenderer_amd import synth
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from . import hzb_ref as R
+from suite_support import dev  # noqa: E402, F401
+from toyrenderer_amd import interop as I  # noqa: E402
+from toyrenderer_amd import synth  # noqa: E402
+
+from . import hzb_ref as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -40,14 +43,6 @@ INST0 = "gpuculling_CS_GPUCulling LATE_CULL=0"
 AS0 = "basepass_AS_Main LATE_CULL=0"
 NO_FUSED = os.environ.get("TRHIP_NO_FUSED_INSTANCE") is not None
 TABLE_CAP = 1 << 19                                                     # record capacity of a table-using frame (smoke() uses the same)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
 
 
 def _ops(prof, shader):

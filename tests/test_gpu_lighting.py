@@ -2,7 +2,6 @@
 GPU, every word against tests/lighting_ref.c: uploaded inputs at sizes with partial tiles and waves, optional bindings, every
 debug view, full frames through FrameDriver(lighting=True), the cornell fixture through the driver and the facade, the host
 mirror over animated frames, and misuse.  LightingOutput is pre-filled with a sentinel so that a skipped texel shows."""
-import json
 import os
 import sys
 
@@ -14,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gbuffer_ref as GR  # noqa: E402
 import lighting_ref as LR  # noqa: E402
 import lighting_scenes as LS  # noqa: E402
+from suite_support import compare_frame, dev, frame_reference, gpu_scene, gr, halves_to_words, host_renderer, lit_cornell, lr, op_counts, recorded_kinds, same, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from gbuffer_scenes import with_normals_and_materials  # noqa: E402
 from toyrenderer_amd import gltf_lite, synth  # noqa: E402
@@ -24,34 +24,6 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 DEBUG_MODES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 14, 0xFFFFFFFF)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
-
-
-@pytest.fixture(scope="module")
-def gr(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gbuffer_ref"))
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref"))
-
-
-def _same(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
 
 
 class Images:
@@ -118,7 +90,7 @@ def test_uploaded_inputs_match_the_reference(dev, lr, size):
         for mat, light, strength, what in cases:
             k = LR.consts(mat, eye, light, strength, size)
             got, want = im.run(k, False), im.reference(lr, k, False)
-            _same(got, want, f"{W}x{H}, {what}")
+            same(got, want, f"{W}x{H}, {what}")
             skipped = ~(im.depth > 0)
             assert np.all(got[skipped] == LS.SENTINEL), "a texel whose depth is not > 0 keeps its value"
         if W * H > 16:
@@ -136,7 +108,7 @@ def test_roughness_metallic_ramp_matches_the_reference(dev, lr):
         for light, strength in ((LS.LIGHTS[1][1], 3.0), (LS.LIGHTS[2][1], 1.0)):
             k = LR.consts(m, eye, light, strength, size)
             got = im.run(k, False)
-            _same(got, im.reference(lr, k, False), f"ramp, strength {strength}")
+            same(got, im.reference(lr, k, False), f"ramp, strength {strength}")
         assert len(np.unique(got)) > 20000
     finally:
         im.release()
@@ -152,11 +124,11 @@ def test_unbound_optional_textures_read_as_white(dev, lr):
         for mode in (0, 1, 9, 11):
             k = LR.consts(m, eye, LS.LIGHTS[1][1], 2.0, size, debug_mode=mode)
             unbound = im.run(k, mode != 0, shadow="unbound", ssao="unbound")
-            _same(unbound, im.run(k, mode != 0, shadow="white", ssao="white"), f"mode {mode}: unbound against 255 bound")
-            _same(unbound, im.reference(lr, k, mode != 0, shadow=False, ssao=False), f"mode {mode}: unbound against the reference")
+            same(unbound, im.run(k, mode != 0, shadow="white", ssao="white"), f"mode {mode}: unbound against 255 bound")
+            same(unbound, im.reference(lr, k, mode != 0, shadow=False, ssao=False), f"mode {mode}: unbound against the reference")
             assert not np.array_equal(unbound, im.run(k, mode != 0)), f"mode {mode}: the bound textures must matter"
         k = LR.consts(m, eye, LS.LIGHTS[1][1], 2.0, size)
-        _same(im.run(k, False, motion=False), im.reference(lr, k, False), "PS_Main without t1")
+        same(im.run(k, False, motion=False), im.reference(lr, k, False), "PS_Main without t1")
     finally:
         im.release()
 
@@ -170,7 +142,7 @@ def test_debug_views_match_the_reference(dev, lr, mode):
         m, eye = LS.camera(size)
         k = LR.consts(m, eye, LS.LIGHTS[2][1], 1.0, size, debug_mode=mode)
         got = im.run(k, True)
-        _same(got, im.reference(lr, k, True), f"debug mode {mode}")
+        same(got, im.reference(lr, k, True), f"debug mode {mode}")
         written = got[im.depth > 0]
         if mode in (14, 0xFFFFFFFF):
             assert np.all(written == 0)
@@ -182,42 +154,15 @@ def test_debug_views_match_the_reference(dev, lr, mode):
 
 
 # ---- 4. full frames -----------------------------------------------------------------------------------------------------------
-def _gpu_scene(dev, s, inst, vertices, materials):
-    from toyrenderer_amd.frame import GpuScene
-    gs = GpuScene(dev, inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-    gs.set_geometry(vertices, s.meshletVertexIds, s.meshletTriangles)
-    gs.set_materials(materials)
-    return gs
-
-
-def _frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, flags, mode, lighting_consts, record_capacity=4096, **kw):
-    """gr_gbuffer followed by the lighting reference, from the oracle's frame."""
-    W, H = view.renderW, view.renderH
-    ref = oracle.frame(sc, view.as_dict(), oracle.HzbTexture(*view.hzb_dims), np.zeros((H, W), np.float32), cullingFlags=flags,
-                       record_capacity=record_capacity, raster=(I.world_to_clip(view.worldToView, view.viewToClip), *geo_v), **kw)
-    k = consts(view)
-    geo = VR.Geometry(sc, *geo_v)
-    vis, depth = VR.frame_visibility(vr, k, geo, ref, W, H)
-    g, m = GR.frame_gbuffer(gr, k, geo, ref, vis, mats, mode)
-    out = LR.lighting(lr, lighting_consts, g, depth, motion=_halves_to_words(VR.to_half_bits(m)))
-    return ref, vis, depth, g, m, out
-
-
-def _halves_to_words(h):
-    h = np.ascontiguousarray(h, np.uint16)
-    return (h[..., 0].astype(np.uint32) | h[..., 1].astype(np.uint32) << 16)
-
-
 @pytest.mark.parametrize("flags", [0, 7])
 def test_frames_match_the_reference(dev, oracle, vr, gr, lr, tmp_path, flags):
     """FrameDriver(lighting=True) on the generated city, debug modes 0, 2, 3 and 12, next to a gbuffer=True driver: LightingOutput
     equals gr_gbuffer followed by the lighting reference; GBufferA, motion, depth, HZB, cull outputs and pipeline statistics equal
     the gbuffer=True run word for word."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
     v, sc, mats = with_normals_and_materials(s, sc)
-    gs = _gpu_scene(dev, s, sc["instances"], v, mats)
+    gs = gpu_scene(dev, s, sc["instances"], v, mats)
     cam = s.cameras[0]
     render = (640, 360)
     eye = (0.4, 0.1, -0.3)
@@ -238,16 +183,16 @@ def test_frames_match_the_reference(dev, oracle, vr, gr, lr, tmp_path, flags):
             got_base, got = base.results(), lit.results()
             what = f"flags {flags} debug mode {mode}"
             assert lit.lighting_consts.tobytes() == LR.consts(I.clip_to_world(V, P), eye, *light, render, debug_mode=mode).tobytes() and lit.lighting_consts.nbytes == 112
-            ref, vis, depth, g, m, out = _frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, flags, mode, lit.lighting_consts)
-            _compare_frame(got, ref); _compare_frame(got_base, ref)
-            _same(lit.lighting_output.download_mip(0), out, what + ": LightingOutput")
-            _same(lit.gbufferA.download_mip(0), g, what + ": GBufferA against the reference")
+            ref, vis, depth, g, m, out = frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, flags, mode, lit.lighting_consts)
+            compare_frame(got, ref); compare_frame(got_base, ref)
+            same(lit.lighting_output.download_mip(0), out, what + ": LightingOutput")
+            same(lit.gbufferA.download_mip(0), g, what + ": GBufferA against the reference")
             for name in ("gbufferA", "visibility"):
-                _same(getattr(lit, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
-            _same(lit.motion.download_mip(0).view(np.uint16), base.motion.download_mip(0).view(np.uint16), what + ": motion")
-            _same(lit.depth.download_mip(0).view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
-            _same(lit.depth.download_mip(0).view(np.uint32), depth.view(np.uint32), what + ": depth against the reference")
-            _same(lit.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
+                same(getattr(lit, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
+            same(lit.motion.download_mip(0).view(np.uint16), base.motion.download_mip(0).view(np.uint16), what + ": motion")
+            same(lit.depth.download_mip(0).view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
+            same(lit.depth.download_mip(0).view(np.uint32), depth.view(np.uint32), what + ": depth against the reference")
+            same(lit.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
             if flags & 2:                                                                          # without occlusion culling nothing writes them
                 assert got["lateCount"] == got_base["lateCount"] and np.array_equal(got["lateArgs"], got_base["lateArgs"])
             assert ql.get() == qb.get(), what + ": pipeline statistics"
@@ -261,30 +206,21 @@ def test_frames_match_the_reference(dev, oracle, vr, gr, lr, tmp_path, flags):
         gs.release()
 
 
-def _op_counts(dev, drv):
-    dev.profile_reset(); dev.profile_enable(True)
-    try:
-        drv.record(); drv.run(); drv.results()
-        return {n: c for n, (c, _) in dev.profile().items()}
-    finally:
-        dev.profile_enable(False)
-
-
 def test_lighting_adds_one_clear_and_one_dispatch(dev, oracle, tmp_path):
     """The op names and launch counts of a gbuffer=True driver are those of the parent commit; lighting=True adds exactly one
     dispatch (and the clear of LightingOutput, counted in the recorded list)."""
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
     v, sc, mats = with_normals_and_materials(s, sc)
-    gs = _gpu_scene(dev, s, sc["instances"], v, mats)
+    gs = gpu_scene(dev, s, sc["instances"], v, mats)
     view = gltf_lite.view_of(s.cameras[0], (320, 180))
     out, kinds = {}, {}
     try:
         for name, kw in (("gbuffer", dict(gbuffer=True)), ("lighting", dict(lighting=True)), ("debug", dict(lighting=True, debug_mode=4))):
             drv = FrameDriver(dev, gs, view, record_capacity=4096, **kw)
             try:
-                out[name] = _op_counts(dev, drv)
-                kinds[name] = _recorded_kinds(drv)
+                out[name] = op_counts(dev, drv)
+                kinds[name] = recorded_kinds(drv)
             finally:
                 drv.release()
     finally:
@@ -298,29 +234,6 @@ def test_lighting_adds_one_clear_and_one_dispatch(dev, oracle, tmp_path):
     assert out["debug"] == {**parent, "deferredlighting_PS_Main_Debug#main": 1}
     added = {k: n - kinds["gbuffer"].get(k, 0) for k, n in kinds["lighting"].items() if n != kinds["gbuffer"].get(k, 0)}
     assert kinds["lighting"] == kinds["debug"] and added == {"clear_texture": 1, "dispatch": 1, "constant_buffer": 1}, added   # the dispatch and its b0
-
-
-def _recorded_kinds(drv):
-    """Counts of the commands FrameDriver.record() issues, by rhi.CommandList method, taken by recording once more through a
-    counting proxy."""
-    counts = {}
-    cl = drv.cl
-
-    class Proxy:
-        def __getattr__(self, name):
-            fn = getattr(cl, name)
-
-            def call(*a, **kw):
-                key = "clear_texture" if name.startswith("clear_texture") else "dispatch" if name.startswith("dispatch") else name
-                counts[key] = counts.get(key, 0) + 1
-                return fn(*a, **kw)
-            return call
-    drv.cl = Proxy()
-    try:
-        drv.record()
-    finally:
-        drv.cl = cl
-    return counts
 
 
 # ---- 5. cornell fixture and host mirror -----------------------------------------------------------------------------------------
@@ -343,24 +256,16 @@ def test_cornell_through_the_driver_and_the_facade(dev, oracle, vr, gr, lr):
     """The cornell fixture with tests/golden/cornell_materials.json: FrameDriver(lighting=True) and the host mirror's
     trhost_download_lighting_output both equal the reference fed their own 112 bytes of constants; the lit walls show the three
     wall colours' hues (red wall: R above G and B, green wall: G above R and B)."""
-    from test_gltf_cornell import _fixture
     from toyrenderer_amd import host
     from toyrenderer_amd.frame import FrameDriver
-    with open(os.path.join(ROOT, "tests", "golden", "cornell_materials.json")) as f:
-        cm = json.load(f)
-    _, s, camera = _fixture()
-    mats = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
-    s.materials, s.primMaterial = mats, np.array(cm["primitiveMaterial"], np.uint32)
-    inst = gltf_lite.apply_materials(s)
-    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
-    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
+    s, inst, _, mats, camera = lit_cornell(oracle)
     sc = dict(s.as_oracle()); sc["instances"] = inst
     render = (320, 180)
     view = gltf_lite.view_of(camera, render)
     eye = tuple(float(x) for x in camera.position)
     light = ((0.3, -0.8, -0.52), 3.0)
     shadow = LS.byte_image(*render, 4)
-    gs = _gpu_scene(dev, s, inst, s.vertices, mats)
+    gs = gpu_scene(dev, s, inst, s.vertices, mats)
     from toyrenderer_amd import rhi
     t_shadow = dev.create_texture(*render, 1, rhi.FORMAT_R8_UNORM, "ShadowMask")
     t_shadow.upload_mip(0, shadow)
@@ -373,10 +278,10 @@ def test_cornell_through_the_driver_and_the_facade(dev, oracle, vr, gr, lr):
         for lx in (0.3, -0.3):                                                                         # the two side walls face each other: one light each
             drv.dir_light = ((lx, light[0][1], light[0][2]), light[1])
             drv.record(); drv.run(); drv.results()
-            ref, vis, depth, g, m, _ = _frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, 7, 0, drv.lighting_consts)
+            ref, vis, depth, g, m, _ = frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, 7, 0, drv.lighting_consts)
             want = LR.lighting(lr, drv.lighting_consts, g, depth, shadow=shadow)
             got = drv.lighting_output.download_mip(0)
-            _same(drv.gbufferA.download_mip(0), g, "GBufferA"); _same(got, want, "LightingOutput through the driver")
+            same(drv.gbufferA.download_mip(0), g, "GBufferA"); same(got, want, "LightingOutput through the driver")
             cov = depth > 0
             assert cov.sum() > 0.5 * cov.size and np.all(got[~cov] == 0)
             albedo = GR.albedo_bytes(g[..., 0]).astype(np.int64)
@@ -387,12 +292,7 @@ def test_cornell_through_the_driver_and_the_facade(dev, oracle, vr, gr, lr):
     finally:
         drv.release(); t_shadow.release(); gs.release()
     assert lit_red > 500 and lit_green > 500, (lit_red, lit_green)
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(gltf_lite.apply_materials(s), s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(*geo_v)
-        r.load_materials(mats)
+    with host_renderer(s, gltf_lite.apply_materials(s), geo_v, mats, render=render, max_groups=4096) as r:
         r.set_deferred_lighting(True)
         r.set_directional_light(*light)
         r.upload_shadow_mask(shadow)
@@ -403,13 +303,11 @@ def test_cornell_through_the_driver_and_the_facade(dev, oracle, vr, gr, lr):
         k = r.deferred_lighting_consts()
         _check_clip_to_world(k, view)
         assert np.allclose(k["m_CameraOrigin"][0], eye, atol=1e-5) and k["m_DirectionalLightStrength"][0] == F(3.0) and k["m_DebugMode"][0] == 0
-        _same(r.download_gbuffer_a(), g, "host: GBufferA")
-        _same(r.download_lighting_output(), LR.lighting(lr, k, g, depth, shadow=shadow), "host: LightingOutput")
+        same(r.download_gbuffer_a(), g, "host: GBufferA")
+        same(r.download_lighting_output(), LR.lighting(lr, k, g, depth, shadow=shadow), "host: LightingOutput")
         r.upload_shadow_mask(None)                                                                     # back to white
         r.frame(); r.results()
-        _same(r.download_lighting_output(), LR.lighting(lr, r.deferred_lighting_consts(), g, depth), "host: LightingOutput, white shadow mask")
-    finally:
-        r.shutdown()
+        same(r.download_lighting_output(), LR.lighting(lr, r.deferred_lighting_consts(), g, depth), "host: LightingOutput, white shadow mask")
 
 
 def test_host_path_with_animated_nodes(oracle, vr, gr, lr, tmp_path):
@@ -418,7 +316,6 @@ def test_host_path_with_animated_nodes(oracle, vr, gr, lr, tmp_path):
     reference, fed the constants of trhost_get_deferred_lighting_consts; m_ClipToWorld is checked in every frame; misuse at
     the facade."""
     import ctypes
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd import host
     s, sc0 = city(tmp_path, oracle)
     v, sc0, mats = with_normals_and_materials(s, sc0)
@@ -431,12 +328,8 @@ def test_host_path_with_animated_nodes(oracle, vr, gr, lr, tmp_path):
     inst_in = s.instances.copy()
     inst_in["m_MaterialDataIdx"] = sc0["instances"]["m_MaterialDataIdx"]
     shadow = LS.byte_image(*render, 8)
-    r = host.Renderer(render=render, max_groups=4096)
     one_ulp = 0
-    try:
-        r.load_scene(inst_in, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(*geo_v)
+    with host_renderer(s, inst_in, geo_v, render=render, max_groups=4096) as r:
         with pytest.raises(host.HostError, match="trhost_load_materials"):
             r.set_deferred_lighting(True)
         with pytest.raises(host.HostError, match="deferred lighting"):
@@ -471,26 +364,24 @@ def test_host_path_with_animated_nodes(oracle, vr, gr, lr, tmp_path):
             sc = dict(s.as_oracle()); sc["instances"] = inst
             ref = oracle.frame(sc, view.as_dict(), hzb, depth0, cullingFlags=7, record_capacity=4096, maxGroups=4096,
                                raster=(I.world_to_clip(V, P), *geo_v))
-            _compare_frame(got, ref)
+            compare_frame(got, ref)
             kb = consts(view)
             geo = VR.Geometry(sc, *geo_v)
             vis_ref, depth = VR.frame_visibility(vr, kb, geo, ref, *render)
             g_ref, m_ref = GR.frame_gbuffer(gr, kb, geo, ref, vis_ref, mats, mode)
-            _same(r.download_gbuffer_a(), g_ref, f"frame {f} (debug view {mode}): GBufferA")
+            same(r.download_gbuffer_a(), g_ref, f"frame {f} (debug view {mode}): GBufferA")
             k = r.deferred_lighting_consts()
             one_ulp += _check_clip_to_world(k, view)
             assert k["m_DebugMode"][0] == mode and k["m_DirectionalLightStrength"][0] == F(1.0 + f) and tuple(k["m_LightingOutputResolution"][0]) == render
             assert np.allclose(k["m_CameraOrigin"][0], eye, atol=1e-5) and k["m_bRTDDGIEnabled"][0] == 0
-            want = LR.lighting(lr, k, g_ref, depth, motion=_halves_to_words(VR.to_half_bits(m_ref)), shadow=shadow if f % 2 else None)
+            want = LR.lighting(lr, k, g_ref, depth, motion=halves_to_words(VR.to_half_bits(m_ref)), shadow=shadow if f % 2 else None)
             out = r.download_lighting_output()
-            _same(out, want, f"frame {f} (debug view {mode}): LightingOutput")
+            same(out, want, f"frame {f} (debug view {mode}): LightingOutput")
             cov = depth > 0
             assert cov.sum() > 0.2 * cov.size and np.all(out[~cov] == 0) and len(np.unique(out[cov])) > {0: 100, 2: 8, 13: 100, 12: 1}[mode]
         print("m_ClipToWorld elements 1 ulp from LAPACK's inverse over 5 frames:", one_ulp, "of 80; straddling interop.clip_to_world: 0")
         with pytest.raises(host.HostError, match="per rank"):
             host._check(host.load().trhost_exchange_create(ctypes.byref(host.ExchangeDesc())))
-    finally:
-        r.shutdown()
 
 
 # ---- 6. misuse ----------------------------------------------------------------------------------------------------------------

@@ -12,40 +12,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gbuffer_ref as GR  # noqa: E402
 import material_texture_scenes as S  # noqa: E402
 import material_textures_ref as MT  # noqa: E402
+from suite_support import dev, gr, host_renderer, mt, same, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 from visibility_scenes import consts  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FILL = 0xABCD1234
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
-
-
-@pytest.fixture(scope="module")
-def mt(tmp_path_factory):
-    return MT.load(tmp_path_factory.mktemp("material_textures_ref"))
-
-
-@pytest.fixture(scope="module")
-def gr(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gbuffer_ref"))
-
-
-def _same(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
 
 
 def _upload(dev, textures, capacity=None):
@@ -128,9 +101,9 @@ def _both(dev, vr, mt, k, scene, materials, textures, render=S.RENDER, what="", 
         for t in made:
             t.release()
     rvis, rg, rmot, taps = _reference(vr, mt, k, scene, render, materials, textures[:capacity] if capacity else textures)
-    _same(vis, rvis, what + ": visibility texels")
-    _same(g, rg, what + ": GBufferA")
-    _same(mot, rmot, what + ": motion")
+    same(vis, rvis, what + ": visibility texels")
+    same(g, rg, what + ": GBufferA")
+    same(mot, rmot, what + ": motion")
     assert names == ["basepass_PS_Main_GBuffer#textured"], names
     return vis, g, taps
 
@@ -228,7 +201,7 @@ def test_uniform_textures_tie_to_the_texture_free_kernel(dev, vr, mt):
         mats = S.material(flags=S.ALBEDO | S.MR | S.EMISSIVE, indices=(0, S.NONE, 1, 0), emissive=EMIT)
         vis1, g1, mot1, names1 = _dispatch(dev, k, scene, S.RENDER, mats, table)
         assert names1 == ["basepass_PS_Main_GBuffer#textured"]
-        _same(vis1, vis0, "texels"); _same(g1, g0, "GBufferA against the texture-free kernel"); _same(mot1, mot0, "motion")
+        same(vis1, vis0, "texels"); same(g1, g0, "GBufferA against the texture-free kernel"); same(mot1, mot0, "motion")
         cov = vis0 != 0
         assert cov.sum() > 1500
         for index, decode in ((2, rhi.srgb_table()), (3, (np.arange(256, dtype=np.float32) / np.float32(255.0)))):
@@ -284,7 +257,7 @@ def test_indices_past_the_table_and_cleared_entries_leave_their_pixels(dev, vr, 
             for t in made:
                 t.release()
         rvis, rg, rmot, _ = _reference(vr, mt, k, scene, S.RENDER, mats, textures[:6] + [None, None])
-        _same(vis, rvis, "texels"); _same(g, rg, f"GBufferA, index {bad}"); _same(mot, rmot, "motion")
+        same(vis, rvis, "texels"); same(g, rg, f"GBufferA, index {bad}"); same(mot, rmot, "motion")
         _, _, pos, _ = VR.decode(vis)
         owner = np.where(vis != 0, scene[4]["m_InstanceConstIdx"][scene[5][pos] >> 5], 99)
         assert all((owner == i).sum() > 100 for i in range(3))
@@ -332,7 +305,7 @@ def test_misuse_is_refused_at_record_time_and_the_next_dispatch_is_correct(dev, 
         for t in made:
             t.release()
     rvis, rg, rmot, _ = _reference(vr, mt, k, scene, S.RENDER, mats, textures + [None])
-    _same(vis, rvis, "texels"); _same(g, rg, "GBufferA after the refusals"); _same(mot, rmot, "motion")
+    same(vis, rvis, "texels"); same(g, rg, "GBufferA after the refusals"); same(mot, rmot, "motion")
 
 
 # ---- through the glTF loader, FrameDriver and the host mirror -------------------------------------------------------------------
@@ -385,16 +358,12 @@ def test_a_textured_gltf_through_the_driver_and_the_facade(dev, oracle, vr, mt):
         finally:
             dev.profile_enable(False)
         assert names == {"basepass_PS_Main_GBuffer#textured"}
-        _same(drv.visibility.download_mip(0), vis_ref, "driver: texels")
-        _same(drv.gbufferA.download_mip(0), g_ref, "driver: GBufferA")
-        _same(drv.motion.download_mip(0).view(np.uint16), m_ref, "driver: motion")
+        same(drv.visibility.download_mip(0), vis_ref, "driver: texels")
+        same(drv.gbufferA.download_mip(0), g_ref, "driver: GBufferA")
+        same(drv.motion.download_mip(0).view(np.uint16), m_ref, "driver: motion")
     finally:
         drv.release(); gs.release()
-    r = host.Renderer(render=S.RENDER, max_groups=4096)
-    try:
-        r.load_scene(inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(s.vertices, s.meshletVertexIds, s.meshletTriangles)
+    with host_renderer(s, inst, (s.vertices, s.meshletVertexIds, s.meshletTriangles), render=S.RENDER, max_groups=4096) as r:
         with pytest.raises(host.HostError, match="texture"):
             r.load_materials(s.materials)                                # no texture created yet
         with pytest.raises(host.HostError, match="format"):
@@ -411,13 +380,11 @@ def test_a_textured_gltf_through_the_driver_and_the_facade(dev, oracle, vr, mt):
         r.set_node_transforms(s.nodes)
         r.set_camera(view)
         r.frame(); r.results()
-        _same(r.download_visibility(), vis_ref, "host: texels")
-        _same(r.download_gbuffer_a(), g_ref, "host: GBufferA")
+        same(r.download_visibility(), vis_ref, "host: texels")
+        same(r.download_gbuffer_a(), g_ref, "host: GBufferA")
         r.frame(); r.results()                                           # a second frame: the previous projection is this camera's
-        _same(r.download_gbuffer_a(), g_ref, "host: GBufferA, second frame")
-        _same(r.download_motion().view(np.uint16).reshape(m_ref.shape), m_ref, "host: motion")
-    finally:
-        r.shutdown()
+        same(r.download_gbuffer_a(), g_ref, "host: GBufferA, second frame")
+        same(r.download_motion().view(np.uint16).reshape(m_ref.shape), m_ref, "host: motion")
 
 
 def test_frames_without_textures_record_the_texture_free_kernel(dev, oracle, vr, mt, gr):
@@ -457,7 +424,7 @@ def test_frames_without_textures_record_the_texture_free_kernel(dev, oracle, vr,
     geo = VR.Geometry(sc, *geo_v)
     vis_ref, _ = VR.frame_visibility(vr, k, geo, ref, *S.RENDER)
     g_ref, _ = GR.frame_gbuffer(gr, k, geo, ref, vis_ref, plain)
-    _same(g, g_ref, "GBufferA of the texture-free frame")
+    same(g, g_ref, "GBufferA of the texture-free frame")
     r = host.Renderer(render=S.RENDER, max_groups=4096)
     try:
         r.load_scene(inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)

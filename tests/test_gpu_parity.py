@@ -4,48 +4,19 @@ Bar: bit-exact (integer / index / fp16-texel outputs).  PARITY UNPINNED with res
 reference itself (no reference fixtures exist): the oracle is the scalar restatement
 of the HLSL in oracle/tr_oracle.c.  Everything here needs a real MI355X.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from toyrenderer_amd import interop as I
-from toyrenderer_amd import synth
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from suite_support import SMALL, compare_frame, dev, oracle_hzb, upload_hzb  # noqa: E402, F401
+from toyrenderer_amd import interop as I  # noqa: E402
+from toyrenderer_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-def _oracle_hzb(oracle, view, depth):
-    hw, hh = view.hzb_dims
-    h = oracle.HzbTexture(hw, hh)
-    if depth is not None:
-        h.build_from_depth(depth)
-    return h
-
-
-def _upload_hzb(driver, hzb):
-    driver.hzb.upload_chain(hzb.texels, hzb.offsets)
-
-
-def _compare_frame(got, ref, slots=(0, 1, 2, 3)):
-    for s in slots:
-        if not ref.passRan[s]:
-            assert got[s] is None, f"slot {s} ran on the GPU but not in the oracle"
-            continue
-        g = got[s]
-        assert g is not None, f"slot {s} did not run on the GPU"
-        assert np.array_equal(g["dispatchArgs"], ref.dispatchArgs[s]), (s, g["dispatchArgs"], ref.dispatchArgs[s])
-        assert g["validRecords"] == int(ref.validRecords[s]), s
-        assert np.array_equal(g["records"].view(np.uint32), ref.records[s].view(np.uint32)), f"slot {s}: records differ"
-        assert np.array_equal(g["visMask"], ref.visMask[s]), f"slot {s}: visibility masks differ"
-        assert np.array_equal(g["drawArgs"], ref.drawArgs[s]), (s, g["drawArgs"], ref.drawArgs[s])
-        assert np.array_equal(g["visibleList"], ref.visibleList[s]), f"slot {s}: visible lists differ"
 
 
 def _run_case(dev, oracle, spec, view, *, flags=7, forced=-1, max_groups=65535, depth_prev=None, depth_cur=None,
@@ -55,9 +26,9 @@ def _run_case(dev, oracle, spec, view, *, flags=7, forced=-1, max_groups=65535, 
     gs = GpuScene(dev, scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
     drv = FrameDriver(dev, gs, view, record_capacity=max_groups, culling_flags=flags, force_mesh_lod=forced,
                       freeze_culling_camera=freeze)
-    hzb = _oracle_hzb(oracle, view, depth_prev)
+    hzb = oracle_hzb(oracle, view, depth_prev)
     if depth_prev is not None:
-        _upload_hzb(drv, hzb)
+        upload_hzb(drv, hzb)
     if depth_cur is not None:
         drv.depth.upload_mip(0, depth_cur)
     try:
@@ -67,7 +38,7 @@ def _run_case(dev, oracle, spec, view, *, flags=7, forced=-1, max_groups=65535, 
             got = drv.results()
             ref = oracle.frame(scene.as_oracle(), view.as_dict(), hzb, depth_cur, cullingFlags=flags, forceMeshLOD=forced,
                                freeze=freeze, maxGroups=max_groups, record_capacity=max_groups)
-            _compare_frame(got, ref)
+            compare_frame(got, ref)
             if flags & 2:
                 assert got["lateCount"] == int(ref.lateCount[1] if scene.alphaMaskIds.size else ref.lateCount[0])
             # the HZB the frame leaves behind (consumed by the next frame's early pass)
@@ -77,10 +48,6 @@ def _run_case(dev, oracle, spec, view, *, flags=7, forced=-1, max_groups=65535, 
     finally:
         drv.release()
         gs.release()
-
-
-SMALL = synth.SceneSpec(num_meshes=24, num_instances=300, meshlets_lod0=70, jitter_meshlets=True, max_lods=5,
-                        alpha_mask_fraction=0.15, seed=1234)
 
 
 @pytest.mark.parametrize("flags", range(8))
@@ -171,9 +138,9 @@ def test_cone_unorm_all_byte_values(dev, oracle):
     try:
         drv.record(); drv.run()
         got = drv.results()
-        hzb = _oracle_hzb(oracle, view, None)
+        hzb = oracle_hzb(oracle, view, None)
         ref = oracle.frame(scene.as_oracle(), view.as_dict(), hzb, None, cullingFlags=4, maxGroups=4096, record_capacity=4096)
-        _compare_frame(got, ref, slots=(0,))
+        compare_frame(got, ref, slots=(0,))
         assert 0 < ref.drawArgs[0][0] < ref.meshletsTested[0]
     finally:
         drv.release(); gs.release()
@@ -198,7 +165,7 @@ def test_hzb_build(dev, oracle, render):
         cl.open(); drv._generate_hzb(cl); cl.close()
         dev.execute(cl)
         dev.wait_idle()
-        ref = _oracle_hzb(oracle, view, depth)
+        ref = oracle_hzb(oracle, view, depth)
         assert np.array_equal(drv.hzb.download_chain(), ref.texels)
     finally:
         drv.release(); gs.release()
@@ -353,11 +320,11 @@ def test_zero_weight_hzb_lookups_take_the_texel_path(dev, oracle):
     inst, md, ml = _zero_weight_lookup_scene(oracle, view)
     ids = np.arange(len(inst), dtype=np.uint32)
     d_prev = synth.gen_depth(view, 120, seed=5, scale=2.0)
-    hzb = _oracle_hzb(oracle, view, d_prev)
+    hzb = oracle_hzb(oracle, view, d_prev)
     cap = 1 << 19
     gs = GpuScene(dev, inst, md, ml, ids, np.zeros(0, np.uint32))
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=7)
-    _upload_hzb(drv, hzb)
+    upload_hzb(drv, hzb)
     drv.depth.upload_mip(0, d_prev)
     try:
         for frame in range(2):
@@ -366,7 +333,7 @@ def test_zero_weight_hzb_lookups_take_the_texel_path(dev, oracle):
             got = drv.results()
             scene = dict(instances=inst, meshData=md, meshlets=ml, opaqueIds=ids, alphaMaskIds=np.zeros(0, np.uint32))
             ref = oracle.frame(scene, view.as_dict(), hzb, d_prev, cullingFlags=7, maxGroups=cap, record_capacity=cap)
-            _compare_frame(got, ref, slots=(0, 1))
+            compare_frame(got, ref, slots=(0, 1))
             assert int(ref.dispatchArgs[0][0]) == len(inst), "every instance submitted in the early phase"
             vis = int(ref.drawArgs[0][0])
             assert 0 < vis < 32 * len(inst), "the HZB decides: some of the deferred lookups pass, some fail"
@@ -473,15 +440,15 @@ def test_meshlet_buffer_rewritten_between_frames(dev, oracle, table):
     spec = synth.SceneSpec(num_meshes=30, num_instances=500, meshlets_lod0=70, jitter_meshlets=True, max_lods=2, seed=313)
     scene = synth.make_scene(spec)
     d = synth.gen_depth(view, num_occluders=50, seed=9, scale=3.0)
-    hzb = _oracle_hzb(oracle, view, d)
+    hzb = oracle_hzb(oracle, view, d)
     gs = GpuScene(dev, scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
     drv = FrameDriver(dev, gs, view, record_capacity=(1 << 19) if table else 65535, culling_flags=7)
-    _upload_hzb(drv, hzb)
+    upload_hzb(drv, hzb)
     drv.depth.upload_mip(0, d)
     cap = (1 << 19) if table else 65535
     try:
         drv.record(); drv.run()
-        _compare_frame(drv.results(), oracle.frame(scene.as_oracle(), view.as_dict(), hzb, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
+        compare_frame(drv.results(), oracle.frame(scene.as_oracle(), view.as_dict(), hzb, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
         # new meshlets: spheres moved and resized, cone words permuted
         rng = np.random.default_rng(5)
         ml2 = scene.meshlets.copy()
@@ -494,9 +461,9 @@ def test_meshlet_buffer_rewritten_between_frames(dev, oracle, table):
         pre.open(); pre.write_buffer(gs.meshlets, ml2[half:], offset=half * ml2.dtype.itemsize); pre.close()
         dev.execute(pre); pre.release()
         scene2 = scene.as_oracle(); scene2["meshlets"] = ml2
-        hzb2 = _oracle_hzb(oracle, view, d)                                   # the HZB frame 1 left behind = built from d
+        hzb2 = oracle_hzb(oracle, view, d)                                   # the HZB frame 1 left behind = built from d
         drv.record(); drv.run()
-        _compare_frame(drv.results(), oracle.frame(scene2, view.as_dict(), hzb2, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
+        compare_frame(drv.results(), oracle.frame(scene2, view.as_dict(), hzb2, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
     finally:
         drv.release()
         gs.release()
@@ -513,16 +480,16 @@ def test_meshlet_and_instance_buffers_written_out_of_band_then_marked(dev, oracl
     spec = synth.SceneSpec(num_meshes=24, num_instances=400, meshlets_lod0=66, jitter_meshlets=True, max_lods=2, seed=717)
     scene = synth.make_scene(spec)
     d = synth.gen_depth(view, num_occluders=40, seed=3, scale=3.0)
-    hzb = _oracle_hzb(oracle, view, d)
+    hzb = oracle_hzb(oracle, view, d)
     gs = GpuScene(dev, scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
     cap = (1 << 19) if table else 65535
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=7)
-    _upload_hzb(drv, hzb)
+    upload_hzb(drv, hzb)
     drv.depth.upload_mip(0, d)
     alias_m = alias_i = None
     try:
         drv.record(); drv.run()
-        _compare_frame(drv.results(), oracle.frame(scene.as_oracle(), view.as_dict(), hzb, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
+        compare_frame(drv.results(), oracle.frame(scene.as_oracle(), view.as_dict(), hzb, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
         rng = np.random.default_rng(11)
         ml2 = scene.meshlets.copy()
         ml2["m_BoundingSphere"][:, :3] += rng.uniform(-0.4, 0.4, (len(ml2), 3)).astype(np.float32)
@@ -538,9 +505,9 @@ def test_meshlet_and_instance_buffers_written_out_of_band_then_marked(dev, oracl
         gs.meshlets.mark_written()
         gs.instances.mark_written()
         scene2 = scene.as_oracle(); scene2["meshlets"] = ml2; scene2["instances"] = inst2
-        hzb2 = _oracle_hzb(oracle, view, d)
+        hzb2 = oracle_hzb(oracle, view, d)
         drv.record(); drv.run()
-        _compare_frame(drv.results(), oracle.frame(scene2, view.as_dict(), hzb2, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
+        compare_frame(drv.results(), oracle.frame(scene2, view.as_dict(), hzb2, d, cullingFlags=7, maxGroups=cap, record_capacity=cap))
     finally:
         for b in (alias_m, alias_i):
             if b is not None:
@@ -564,7 +531,7 @@ def test_instance_pass_continues_from_nonzero_counters(dev, oracle, flags, mid_c
                            alpha_mask_fraction=0.4, seed=91)
     scene = synth.make_scene(spec)
     d_prev = synth.gen_depth(view, num_occluders=70, seed=5, scale=3.0)
-    hzb = _oracle_hzb(oracle, view, d_prev)
+    hzb = oracle_hzb(oracle, view, d_prev)
     gs = GpuScene(dev, scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
     lists = [(gs.opaqueIds, gs.numOpaque, scene.opaqueIds), (gs.alphaMaskIds, gs.numAlphaMask, scene.alphaMaskIds)]
     assert all(n > 0 for _, n, _ in lists)
@@ -584,7 +551,7 @@ def test_instance_pass_continues_from_nonzero_counters(dev, oracle, flags, mid_c
     recs, o_args, o_late, o_ids, xs, valid = oracle_passes(cap)
     probe.release()
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=flags)
-    _upload_hzb(drv, hzb)
+    upload_hzb(drv, hzb)
     try:
         cl = drv.cl
         cl.open()
@@ -706,8 +673,8 @@ def test_hostile_operands_take_the_exact_arithmetic_path(dev, oracle, flags, tab
     cap = 1 << 19 if table else 65535
     gs = GpuScene(dev, inst, scene.meshData, ml, scene.opaqueIds, scene.alphaMaskIds)
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=flags)
-    hzb = _oracle_hzb(oracle, view, d_prev)
-    _upload_hzb(drv, hzb)
+    hzb = oracle_hzb(oracle, view, d_prev)
+    upload_hzb(drv, hzb)
     drv.depth.upload_mip(0, d_cur)
     try:
         with np.errstate(all="ignore"):
@@ -716,7 +683,7 @@ def test_hostile_operands_take_the_exact_arithmetic_path(dev, oracle, flags, tab
                 drv.run()
                 got = drv.results()
                 ref = oracle.frame(scene.as_oracle(), view.as_dict(), hzb, d_cur, cullingFlags=flags, maxGroups=cap, record_capacity=cap)
-                _compare_frame(got, ref)
+                compare_frame(got, ref)
         assert int(ref.meshletsTested[0]) > 5000 and 0 < int(ref.drawArgs[0][0]) < int(ref.meshletsTested[0])
     finally:
         drv.release()
@@ -771,15 +738,15 @@ def test_cone_test_at_its_decision_boundary(dev, oracle, flags, table):
     cap = 1 << 19 if table else 65535
     gs = GpuScene(dev, inst, md, ml, scene.opaqueIds, scene.alphaMaskIds)
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=flags)
-    hzb = _oracle_hzb(oracle, view, d_prev)
-    _upload_hzb(drv, hzb)
+    hzb = oracle_hzb(oracle, view, d_prev)
+    upload_hzb(drv, hzb)
     drv.depth.upload_mip(0, d_cur)
     try:
         drv.record()
         drv.run()
         got = drv.results()
         ref = oracle.frame(scene.as_oracle(), view.as_dict(), hzb, d_cur, cullingFlags=flags, maxGroups=cap, record_capacity=cap)
-        _compare_frame(got, ref)
+        compare_frame(got, ref)
         assert int(ref.meshletsTested[0]) > 5000 and 0 < int(ref.drawArgs[0][0]) < int(ref.meshletsTested[0])
     finally:
         drv.release()
@@ -894,14 +861,14 @@ def test_projection_filter_at_its_decision_boundaries(dev, oracle, kind, flags):
     cap = 1 << 19                                                                                   # the footprint-table kernel
     gs = GpuScene(dev, inst, md, ml, scene.opaqueIds, scene.alphaMaskIds)
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=flags)
-    _upload_hzb(drv, hzb)
+    upload_hzb(drv, hzb)
     drv.depth.upload_mip(0, d_cur)
     try:
         drv.record()
         drv.run()
         got = drv.results()
         ref = oracle.frame(scene.as_oracle(), view.as_dict(), hzb, d_cur, cullingFlags=flags, maxGroups=cap, record_capacity=cap)
-        _compare_frame(got, ref)
+        compare_frame(got, ref)
         assert int(ref.meshletsTested[0]) > (1000 if kind == "depth" else 5000) and 0 < int(ref.drawArgs[0][0]) < int(ref.meshletsTested[0])
     finally:
         drv.release()

@@ -1,13 +1,18 @@
 """Pipeline statistics queries (include/trhip.h trhip_pipeline_stats_*) on the GPU: every counter equals, exactly, what
 tests/pipeline_stats_ref.py derives from the CPU oracle's frame and the scene arrays; and a frame recorded without a query
 is the frame of before (no stats command, the same output words)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
-from toyrenderer_amd import synth
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from . import pipeline_stats_ref as psr
-from .test_gpu_parity import SMALL, _compare_frame, _oracle_hzb, _upload_hzb
+from suite_support import SMALL, compare_frame, dev, oracle_hzb, upload_hzb  # noqa: E402, F401
+from toyrenderer_amd import synth  # noqa: E402
+
+from . import pipeline_stats_ref as psr  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -16,22 +21,14 @@ D_PREV = synth.gen_depth(VIEW, num_occluders=60, seed=11, scale=3.0)
 D_CUR = synth.gen_depth(VIEW, num_occluders=40, seed=12, scale=3.0)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
 def _setup(dev, oracle, spec_or_scene, cap, flags, depth_prev, depth_cur, view=VIEW, **kw):
     from toyrenderer_amd.frame import FrameDriver, GpuScene
     scene = synth.make_scene(spec_or_scene) if isinstance(spec_or_scene, synth.SceneSpec) else spec_or_scene
     gs = GpuScene(dev, scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=flags, **kw)
-    hzb = _oracle_hzb(oracle, view, depth_prev)
+    hzb = oracle_hzb(oracle, view, depth_prev)
     if depth_prev is not None:
-        _upload_hzb(drv, hzb)
+        upload_hzb(drv, hzb)
     if depth_cur is not None:
         drv.depth.upload_mip(0, depth_cur)
     return scene, gs, drv, hzb
@@ -60,7 +57,7 @@ def _case(dev, oracle, spec, cap, flags, depth_prev=D_PREV, depth_cur=D_CUR, vie
     finally:
         q.release(); drv.release(); gs.release()
     ref, want = _expected(oracle, scene.as_oracle(), view, hzb, depth_cur, cap, flags)
-    _compare_frame(got, ref)
+    compare_frame(got, ref)
     assert stats == want, {k: (stats[k], want[k]) for k in psr.FIELDS if stats[k] != want[k]}
     return stats, want, ref, prof
 
@@ -131,7 +128,7 @@ def test_meshlet_buffer_rewritten_between_frames(dev, oracle, how):
             alias.upload(ml2)
             gs.meshlets.mark_written()
         scene2 = scene.as_oracle(); scene2["meshlets"] = ml2
-        hzb2 = _oracle_hzb(oracle, VIEW, D_CUR)
+        hzb2 = oracle_hzb(oracle, VIEW, D_CUR)
         drv.record(q); drv.run(); drv.results()
         s2 = q.get()
         _, w2 = _expected(oracle, scene2, VIEW, hzb2, D_CUR, 65535, 7)
@@ -290,7 +287,7 @@ def test_host_path_reads_the_query_of_two_frames_earlier(oracle):
             r.frame()
             got = r.results()
             ref, w = _expected(oracle, scene.as_oracle(), view, hzb, d_cur, 65535, 7)
-            _compare_frame(got, ref)
+            compare_frame(got, ref)
             want.append(w)
             shown, latest = r.pipeline_statistics()
             assert shown == (want[f - 2] if f >= 2 else psr.zeros()), f

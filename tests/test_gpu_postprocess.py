@@ -2,9 +2,7 @@
 "postprocess_PS_PostProcess", csrc/k_postprocess.hip), every word against tests/postprocess_ref.c: uploaded inputs at sizes with
 partial vectors, trips, tiles and waves; constructed histograms; full frames through FrameDriver(post=True) over five frames with
 the luminance carried along; and misuse.  Outputs are pre-filled so that a skipped texel or an overwritten count shows."""
-import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -16,6 +14,7 @@ import gbuffer_ref as GR  # noqa: E402
 import lighting_ref as LR  # noqa: E402
 import lighting_scenes as LS  # noqa: E402
 import postprocess_ref as PR  # noqa: E402
+from suite_support import bits, compare_frame, dev, frame_reference, gpu_scene, gr, halves_to_words, host_renderer, kernel_constant, lit_cornell, lr, op_counts, post_chain_reference, pr, recorded_kinds, same, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from gbuffer_scenes import with_normals_and_materials  # noqa: E402
 from toyrenderer_amd import gltf_lite, synth  # noqa: E402
@@ -29,50 +28,7 @@ SENTINEL = 0x12345678
 HIST_INIT = (np.arange(256, dtype=np.uint32) * np.uint32(7) + np.uint32(3))
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def pr(tmp_path_factory):
-    return PR.load(tmp_path_factory.mktemp("postprocess_ref"))
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
-
-
-@pytest.fixture(scope="module")
-def gr(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gbuffer_ref"))
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref"))
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
-
-
-def _bits(x):
-    return np.asarray(x, F).reshape(-1).view(np.uint32)
-
-
 # ---- 1. the histogram ---------------------------------------------------------------------------------------------------------
-def _kernel_constant(name):
-    src = open(os.path.join(ROOT, "toyrenderer_amd", "csrc", "k_postprocess.hip")).read()
-    return int(re.search(r"\b" + name + r" = (\d+)", src).group(1))
-
-
 def _two_trip_size(dev):
     """The smallest image at which every workgroup of the histogram kernel takes at least two trips and the last trip is partial.
     The kernel runs min(ceil(vectors / kBlock), kHistGroupsPerCU * CUs) workgroups of kBlock lanes; lane t of workgroup b takes the
@@ -80,7 +36,7 @@ def _two_trip_size(dev):
     vector G * kBlock + (G - 1) * kBlock, so vectors = (2 G - 1) * kBlock + 1 is the smallest count at which its lane 0 (and so a
     lane of every workgroup) takes two trips; that trip has one lane of kBlock, the most partial it can be.  Three more texels
     make W * H mod 4 = 3, so the tail path runs as well.  The count is laid out as 5 rows when it divides, else one row."""
-    block, per_cu, per_lane = _kernel_constant("kBlock"), _kernel_constant("kHistGroupsPerCU"), _kernel_constant("kHistTexelsPerLane")
+    block, per_cu, per_lane = kernel_constant("k_postprocess.hip", "kBlock"), kernel_constant("k_postprocess.hip", "kHistGroupsPerCU"), kernel_constant("k_postprocess.hip", "kHistTexelsPerLane")
     grid = per_cu * dev.compute_units
     texels = ((2 * grid - 1) * block + 1) * per_lane + (per_lane - 1)
     return (texels // 5, 5) if texels % 5 == 0 else (texels, 1)
@@ -122,7 +78,7 @@ def test_histogram_matches_the_reference(dev, pr, size):
             cl.close()
             dev.execute(cl); dev.wait_idle()
             got = hist.download(np.uint32, 256)
-            _same(got, PR.histogram(pr, words, k, HIST_INIT), f"{W}x{H} {name}")
+            same(got, PR.histogram(pr, words, k, HIST_INIT), f"{W}x{H} {name}")
             assert int((got - HIST_INIT).astype(np.uint64).sum()) == W * H, "the kernel adds to u0, and the counts sum to W * H"
             if name == "one value":
                 assert np.count_nonzero(got != HIST_INIT) == 1
@@ -161,7 +117,7 @@ def test_adapt_exposure_matches_the_reference(dev, pr):
                     exposure.upload_mip(0, np.array([[-1.0]], F))
                     got = step(k)
                     want = PR.adapt_exposure(pr, k, h, last)
-                    assert _bits(got).tolist() == _bits(want).tolist(), (name, speed, last, got, want)
+                    assert bits(got).tolist() == bits(want).tolist(), (name, speed, last, got, want)
         h, n = PR.ADAPT_HISTOGRAMS["mid bins"]
         hist.upload(h)
         k = PR.adapt_params(n, 0.04)
@@ -170,7 +126,7 @@ def test_adapt_exposure_matches_the_reference(dev, pr):
         for i in range(20):
             got = step(k)
             want_lum, want_exp = PR.adapt_exposure(pr, k, h, want_lum)
-            assert _bits(got).tolist() == _bits((want_lum, want_exp)).tolist(), i
+            assert bits(got).tolist() == bits((want_lum, want_exp)).tolist(), i
         assert want_lum != F(1.0)
     finally:
         cl.release(); hist.release(); lum.release(); exposure.release()
@@ -227,7 +183,7 @@ def test_post_process_matches_the_reference(dev, pr, size):
             dev.execute(cl); dev.wait_idle()
             got = t_out.download_mip(0)
             what = f"{W}x{H} manual {manual} luminance {luminance} bloom {'bound' if b is not None else 'unbound'} strength {strength}"
-            _same(got, PR.post(pr, k, colour, bloom=b, luminance_in=luminance), what)
+            same(got, PR.post(pr, k, colour, bloom=b, luminance_in=luminance), what)
             assert np.all(got >> 24 == 255) and not np.any(got == SENTINEL), what
             if luminance == 0.0 and manual == 0.0:
                 assert np.all(got == 0xFF000000), "a zero luminance stores black"
@@ -238,32 +194,19 @@ def test_post_process_matches_the_reference(dev, pr, size):
 
 
 # ---- 4. full frames -----------------------------------------------------------------------------------------------------------
-def _post_chain_reference(pr, drv, lighting_output, luminance, bloom=None):
-    """One frame of the reference chain behind LightingOutput, from the driver's own parameter structs.  Returns (back buffer,
-    histogram or None, luminance, exposure or None)."""
-    hk, ak, pk = drv.post_consts
-    hist = exposure = None
-    if hk is not None:
-        hist = PR.histogram(pr, lighting_output, hk)
-        luminance, exposure = PR.adapt_exposure(pr, ak, hist, luminance)
-    else:
-        luminance = F(pk["m_ManualExposure"][0])
-    return PR.post(pr, pk, lighting_output, bloom=bloom, luminance_in=luminance), hist, luminance, exposure
-
-
 def _check_post_frames(dev, pr, post, lighting_output, what, frames=5, bloom=None):
     """`frames` frames of a post=True driver against the reference chain, the luminance carried from frame to frame."""
     luminance = F(1.0)
     seen = []
     for f in range(frames):
         post.record(); post.run(); post.results()
-        back, hist, luminance, exposure = _post_chain_reference(pr, post, lighting_output, luminance, bloom)
-        _same(post.lighting_output.download_mip(0), lighting_output, f"{what} frame {f}: LightingOutput")
-        _same(post.back_buffer.download_mip(0), back, f"{what} frame {f}: back buffer")
-        assert _bits(post.luminance.download(F, 1)).tolist() == _bits(luminance).tolist(), (what, f)
+        back, hist, luminance, exposure = post_chain_reference(pr, post, lighting_output, luminance, bloom)
+        same(post.lighting_output.download_mip(0), lighting_output, f"{what} frame {f}: LightingOutput")
+        same(post.back_buffer.download_mip(0), back, f"{what} frame {f}: back buffer")
+        assert bits(post.luminance.download(F, 1)).tolist() == bits(luminance).tolist(), (what, f)
         if hist is not None:
-            _same(post.histogram.download(np.uint32, 256), hist, f"{what} frame {f}: histogram")
-            assert _bits(post.exposure_texture.download_mip(0)).tolist() == _bits(exposure).tolist(), (what, f)
+            same(post.histogram.download(np.uint32, 256), hist, f"{what} frame {f}: histogram")
+            assert bits(post.exposure_texture.download_mip(0)).tolist() == bits(exposure).tolist(), (what, f)
             assert int(hist.sum()) == lighting_output.size
         seen.append(float(luminance))
     return seen
@@ -274,12 +217,10 @@ def test_frames_match_the_reference(dev, oracle, vr, gr, lr, pr, tmp_path, flags
     """FrameDriver(post=True) on the generated city, debug modes 0 and 4, next to a lighting=True driver, five frames each: back
     buffer, histogram, luminance and exposure equal gr_gbuffer -> lighting reference -> post reference; depth, HZB, cull outputs,
     GBufferA, motion, LightingOutput and pipeline statistics equal the lighting=True run word for word."""
-    from test_gpu_lighting import _frame_reference, _gpu_scene
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
     v, sc, mats = with_normals_and_materials(s, sc)
-    gs = _gpu_scene(dev, s, sc["instances"], v, mats)
+    gs = gpu_scene(dev, s, sc["instances"], v, mats)
     cam = s.cameras[0]
     render = (640, 360)
     eye = (0.4, 0.1, -0.3)
@@ -301,13 +242,13 @@ def test_frames_match_the_reference(dev, oracle, vr, gr, lr, pr, tmp_path, flags
             got_lit, got = lit.results(), post.results()
             what = f"flags {flags} debug mode {mode}"
             assert post.lighting_consts.tobytes() == lit.lighting_consts.tobytes()
-            ref, vis, depth, g, m, out = _frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, flags, mode, post.lighting_consts)
-            _compare_frame(got, ref); _compare_frame(got_lit, ref)
+            ref, vis, depth, g, m, out = frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, flags, mode, post.lighting_consts)
+            compare_frame(got, ref); compare_frame(got_lit, ref)
             for name in ("gbufferA", "visibility", "lighting_output"):
-                _same(getattr(post, name).download_mip(0), getattr(lit, name).download_mip(0), what + ": " + name)
-            _same(post.motion.download_mip(0).view(np.uint16), lit.motion.download_mip(0).view(np.uint16), what + ": motion")
-            _same(post.depth.download_mip(0).view(np.uint32), lit.depth.download_mip(0).view(np.uint32), what + ": depth")
-            _same(post.hzb.download_chain(), lit.hzb.download_chain(), what + ": HZB")
+                same(getattr(post, name).download_mip(0), getattr(lit, name).download_mip(0), what + ": " + name)
+            same(post.motion.download_mip(0).view(np.uint16), lit.motion.download_mip(0).view(np.uint16), what + ": motion")
+            same(post.depth.download_mip(0).view(np.uint32), lit.depth.download_mip(0).view(np.uint32), what + ": depth")
+            same(post.hzb.download_chain(), lit.hzb.download_chain(), what + ": HZB")
             if flags & 2:
                 assert got["lateCount"] == got_lit["lateCount"] and np.array_equal(got["lateArgs"], got_lit["lateArgs"])
             assert qp.get() == ql.get(), what + ": pipeline statistics"
@@ -330,12 +271,11 @@ def test_post_adds_one_clear_and_three_dispatches(dev, oracle, pr, tmp_path):
     """The op names and launch counts of a lighting=True driver are those of the parent commit; post=True adds exactly one buffer
     clear and three dispatches, and with a manual exposure one buffer write and one dispatch.  The manual frame's back buffer and
     luminance equal the reference's; exposure and bloom parameters reach the constants."""
-    from test_gpu_lighting import _gpu_scene, _op_counts, _recorded_kinds
     from toyrenderer_amd import rhi
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
     v, sc, mats = with_normals_and_materials(s, sc)
-    gs = _gpu_scene(dev, s, sc["instances"], v, mats)
+    gs = gpu_scene(dev, s, sc["instances"], v, mats)
     view = gltf_lite.view_of(s.cameras[0], (320, 180))
     bloom_words = _post_image(320, 180, 77)
     t_bloom = dev.create_texture(320, 180, 1, rhi.FORMAT_R11G11B10_FLOAT, "Bloom")
@@ -345,8 +285,8 @@ def test_post_adds_one_clear_and_three_dispatches(dev, oracle, pr, tmp_path):
         for name, kw in (("lighting", dict(lighting=True)), ("post", dict(post=True)), ("manual", dict(post=True, exposure=(2.5, 0.25), bloom=(t_bloom, 0.2)))):
             drv = FrameDriver(dev, gs, view, record_capacity=4096, **kw)
             try:
-                out[name] = _op_counts(dev, drv)
-                kinds[name] = _recorded_kinds(drv)
+                out[name] = op_counts(dev, drv)
+                kinds[name] = recorded_kinds(drv)
                 if name == "manual":
                     hk, ak, pk = drv.post_consts
                     assert hk is None and ak is None and pk.tobytes() == PR.post_params((320, 180), manual=2.5, middle_gray=0.25, bloom_strength=0.2).tobytes()
@@ -376,28 +316,19 @@ def test_post_adds_one_clear_and_three_dispatches(dev, oracle, pr, tmp_path):
 def test_cornell_through_the_driver(dev, oracle, vr, gr, lr, pr):
     """The cornell fixture with tests/golden/cornell_materials.json through FrameDriver(post=True), five frames: the reference
     chain's words; the lit red wall is red in the back buffer and the green wall green."""
-    from test_gltf_cornell import _fixture
-    from test_gpu_lighting import _frame_reference, _gpu_scene
     from toyrenderer_amd.frame import FrameDriver
-    with open(os.path.join(ROOT, "tests", "golden", "cornell_materials.json")) as f:
-        cm = json.load(f)
-    _, s, camera = _fixture()
-    mats = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
-    s.materials, s.primMaterial = mats, np.array(cm["primitiveMaterial"], np.uint32)
-    inst = gltf_lite.apply_materials(s)
-    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
-    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
+    s, inst, _, mats, camera = lit_cornell(oracle)
     sc = dict(s.as_oracle()); sc["instances"] = inst
     render = (320, 180)
     view = gltf_lite.view_of(camera, render)
     eye = tuple(float(x) for x in camera.position)
-    gs = _gpu_scene(dev, s, inst, s.vertices, mats)
+    gs = gpu_scene(dev, s, inst, s.vertices, mats)
     drv = FrameDriver(dev, gs, view, record_capacity=4096, culling_flags=7, post=True, dir_light=((0.3, -0.8, -0.52), 3.0), camera_origin=eye,
                       auto_exposure=(0.004, 12.0, 0.5))
     geo_v = (s.vertices, s.meshletVertexIds, s.meshletTriangles)
     try:
         drv.record()
-        _, _, depth, g, _, out = _frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, 7, 0, drv.lighting_consts)
+        _, _, depth, g, _, out = frame_reference(oracle, vr, gr, lr, sc, geo_v, view, mats, 7, 0, drv.lighting_consts)
         _check_post_frames(dev, pr, drv, out, "cornell")
         back = drv.back_buffer.download_mip(0)
         albedo = GR.albedo_bytes(g[..., 0]).astype(np.int64)
@@ -415,7 +346,6 @@ def test_host_path_over_five_frames(oracle, vr, gr, lr, pr, tmp_path):
     frame 1, a manual exposure switched on in frame 3 and off again in frame 4.  The back buffer equals gr_gbuffer -> lighting
     reference -> post reference fed the structs of trhost_get_post_process_consts, the luminance carried from frame to frame;
     trhost_get_scene_luminance is compared bit for bit; trhost_reset_exposure returns the state to 1.0; misuse at the facade."""
-    from test_gpu_lighting import _halves_to_words
     from toyrenderer_amd import host
     from visibility_scenes import consts
     s, sc0 = city(tmp_path, oracle)
@@ -429,11 +359,7 @@ def test_host_path_over_five_frames(oracle, vr, gr, lr, pr, tmp_path):
     inst_in = s.instances.copy()
     inst_in["m_MaterialDataIdx"] = sc0["instances"]["m_MaterialDataIdx"]
     bloom = PR.seeded_finite_words(render[0] * render[1], 91).reshape(render[1], render[0])
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(inst_in, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(*geo_v)
+    with host_renderer(s, inst_in, geo_v, render=render, max_groups=4096) as r:
         with pytest.raises(host.HostError, match="trhost_load_materials"):
             r.set_post_process(True)
         for call in (r.download_back_buffer, r.post_process_consts, r.scene_luminance):
@@ -472,8 +398,8 @@ def test_host_path_over_five_frames(oracle, vr, gr, lr, pr, tmp_path):
             geo = VR.Geometry(sc, *geo_v)
             vis_ref, depth = VR.frame_visibility(vr, kb, geo, ref, *render)
             g_ref, m_ref = GR.frame_gbuffer(gr, kb, geo, ref, vis_ref, mats, 0)
-            lit = LR.lighting(lr, r.deferred_lighting_consts(), g_ref, depth, motion=_halves_to_words(VR.to_half_bits(m_ref)))
-            _same(r.download_lighting_output(), lit, f"frame {f}: LightingOutput")
+            lit = LR.lighting(lr, r.deferred_lighting_consts(), g_ref, depth, motion=halves_to_words(VR.to_half_bits(m_ref)))
+            same(r.download_lighting_output(), lit, f"frame {f}: LightingOutput")
             hk, ak, pk = r.post_process_consts()
             want_bloom = bloom if 1 <= f < 4 else None
             assert pk.tobytes() == PR.post_params(render, manual=manual, middle_gray=0.18 + 0.01 * f, bloom_strength=0.25 if want_bloom is not None else 0.0).tobytes()
@@ -484,16 +410,14 @@ def test_host_path_over_five_frames(oracle, vr, gr, lr, pr, tmp_path):
                 assert hk.tobytes() == PR.histogram_params(render).tobytes()
                 assert ak.tobytes() == PR.adapt_params(render[0] * render[1], F(0.0025) * F(16.0), middle_gray=0.18 + 0.01 * f).tobytes()
                 luminance, exposure = PR.adapt_exposure(pr, ak, PR.histogram(pr, lit, hk), luminance)
-            _same(r.download_back_buffer(), PR.post(pr, pk, lit, bloom=want_bloom, luminance_in=luminance), f"frame {f}: back buffer")
+            same(r.download_back_buffer(), PR.post(pr, pk, lit, bloom=want_bloom, luminance_in=luminance), f"frame {f}: back buffer")
             got_lum, got_exp = r.scene_luminance()
-            assert _bits(got_lum).tolist() == _bits(luminance).tolist(), f
+            assert bits(got_lum).tolist() == bits(luminance).tolist(), f
             if exposure is not None:
-                assert _bits(got_exp).tolist() == _bits(exposure).tolist(), f
+                assert bits(got_exp).tolist() == bits(exposure).tolist(), f
         assert luminance != F(1.0)
         r.reset_exposure()
-        assert _bits(r.scene_luminance()).tolist() == _bits((1.0, 1.0)).tolist()
-    finally:
-        r.shutdown()
+        assert bits(r.scene_luminance()).tolist() == bits((1.0, 1.0)).tolist()
 
 
 # ---- 6. misuse ----------------------------------------------------------------------------------------------------------------

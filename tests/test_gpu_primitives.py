@@ -14,17 +14,19 @@ checked by the scene-level parity tests.
 import ctypes as C
 import os
 import struct
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from suite_support import PROBE_LAUNCHERS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE_PATH = os.path.join(ROOT, "toyrenderer_amd", "lib", "libtrhip_probe.so")
 
 # every launcher this file binds (tests/test_probe_ref.py checks that the library exports them)
-PROBE_LAUNCHERS = ["probe_unary", "probe_div2", "probe_quotient", "probe_levels", "probe_step", "probe_filtered",
-                   "probe_result_size"]
-
 RSQ, RCP, SQRTSEQ1, SQRTSEQ2, SQRT2, SQRT2_LANE0_OUT = range(6)
 BYTES, HZB_LEVEL, FREXP_LEVEL = range(3)
 

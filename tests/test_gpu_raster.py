@@ -11,18 +11,11 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from scene_gen import all_meshlets_visible, write_city_gltf  # noqa: E402
+from suite_support import compare_frame, cornell_fixture, dev, gpu_scene, host_renderer  # noqa: E402, F401
 from toyrenderer_amd import gltf_lite, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
 
 
 def _world(oracle, s):
@@ -30,13 +23,6 @@ def _world(oracle, s):
     oracle.update_instance_consts(s.nodes, s.primToNode, inst)
     sc = dict(s.as_oracle()); sc["instances"] = inst
     return inst, sc
-
-
-def _gpu_scene(dev, s, inst):
-    from toyrenderer_amd.frame import GpuScene
-    gs = GpuScene(dev, inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-    gs.set_geometry(s.vertices, s.meshletVertexIds, s.meshletTriangles)
-    return gs
 
 
 def _consts(view):
@@ -51,7 +37,7 @@ def _raster_everything(dev, oracle, s, view, eye=None):
     from toyrenderer_amd import rhi
     from toyrenderer_amd.rhi import CB, SRV, TEX_UAV
     inst, sc = _world(oracle, s)
-    gs = _gpu_scene(dev, s, inst)
+    gs = gpu_scene(dev, s, inst)
     rec, lst = all_meshlets_visible(s)
     k = _consts(view)
     ref = np.zeros((view.renderH, view.renderW), np.float32)
@@ -79,8 +65,7 @@ def _raster_everything(dev, oracle, s, view, eye=None):
 
 @pytest.mark.parametrize("render", [(1920, 1080), (257, 131)])
 def test_cornell_depth_matches_the_oracle(dev, oracle, render):
-    from test_gltf_cornell import _fixture
-    z, s, camera = _fixture()
+    z, s, camera = cornell_fixture()
     assert len(s.vertices) and len(s.meshletTriangles), "fixture carries the geometry (tests/golden/make_cornell.py)"
     view = gltf_lite.view_of(camera, render)
     got, ref = _raster_everything(dev, oracle, s, view)
@@ -112,11 +97,10 @@ def test_camera_inside_the_geometry(dev, oracle, tmp_path):
 def test_two_phase_frames_on_own_depth(dev, oracle, tmp_path, flags):
     """Four frames of a moving camera, HZB built from the depth the frame rasterised: every list, the depth buffer and
     the HZB chain equal the oracle's after every frame."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd.frame import FrameDriver
     s = gltf_lite.load(write_city_gltf(tmp_path))
     inst, sc = _world(oracle, s)
-    gs = _gpu_scene(dev, s, inst)
+    gs = gpu_scene(dev, s, inst)
     cam = s.cameras[0]
     render = (1280, 720)
     P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
@@ -136,7 +120,7 @@ def test_two_phase_frames_on_own_depth(dev, oracle, tmp_path, flags):
             got = drv.results()
             geo = (I.world_to_clip(V, P), s.vertices, s.meshletVertexIds, s.meshletTriangles)
             ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=flags, record_capacity=4096, raster=geo)
-            _compare_frame(got, ref)
+            compare_frame(got, ref)
             assert np.array_equal(drv.depth.download_mip(0).view(np.uint32), depth.view(np.uint32)), f"frame {f}: depth differs"
             assert np.array_equal(drv.hzb.download_chain(), hzb.texels), f"frame {f}: HZB chain differs"
             late_seen |= bool(ref.lateCount[0] > 0 and ref.drawArgs[1][0] > 0)
@@ -149,7 +133,6 @@ def test_two_phase_frames_on_own_depth(dev, oracle, tmp_path, flags):
 def test_drop_in_path_renders_its_own_depth(oracle, tmp_path):
     """The same loop through the C++ host mirror (RenderGraph / GBufferRenderer over the C ABI): node transforms on the
     GPU, cull, depth of the visible meshlets, HZB -- four frames, moving camera, everything equal to the oracle."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd import host
     s = gltf_lite.load(write_city_gltf(tmp_path))
     inst, sc = _world(oracle, s)
@@ -158,11 +141,7 @@ def test_drop_in_path_renders_its_own_depth(oracle, tmp_path):
     P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
     hzb = oracle.HzbTexture(*I.hzb_dims(*render))
     depth = np.zeros((render[1], render[0]), np.float32)
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(s.instances, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(s.vertices, s.meshletVertexIds, s.meshletTriangles)
+    with host_renderer(s, s.instances, (s.vertices, s.meshletVertexIds, s.meshletTriangles), render=render, max_groups=4096) as r:
         r.set_raster_depth(True)
         r.set_culling(7)
         prevV = synth.world_to_view((0.0, 0.0, 0.0), cam.orientation)
@@ -176,14 +155,12 @@ def test_drop_in_path_renders_its_own_depth(oracle, tmp_path):
             got = r.results()
             geo = (I.world_to_clip(V, P), s.vertices, s.meshletVertexIds, s.meshletTriangles)
             ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=7, record_capacity=4096, maxGroups=4096, raster=geo)
-            _compare_frame(got, ref)
+            compare_frame(got, ref)
             if f == 0:   # the ingested scene carries its own LOD chain (gltf_lite.build_lod_chain): LOD selection picks from it
                 assert len(np.unique(got[0]["records"]["m_MeshLOD"])) >= 2 and int(s.meshData["m_NumLODs"].max()) >= 3
             assert np.array_equal(r.download_depth().view(np.uint32), depth.view(np.uint32)), f"frame {f}: depth differs"
             assert np.array_equal(r.download_hzb(), hzb.texels), f"frame {f}: HZB chain differs"
         assert np.count_nonzero(depth) > 0.2 * depth.size
-    finally:
-        r.shutdown()
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
@@ -256,7 +233,6 @@ def test_scene_from_the_cached_data_file_through_the_native_reader(oracle, tmp_p
     """glTF -> `<scene>_CachedData.bin` v3 (cached_scene.write) -> the host library's own reader
     (trhost_load_scene_cached: meshes, meshlets, vertices, meshlet index buffers from the file) -> two frames with
     self-rendered depth: equal to the oracle on the in-memory scene.  A wrong version is refused."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd import cached_scene, host
     s = gltf_lite.load(write_city_gltf(tmp_path))
     path = str(tmp_path / "city_CachedData.bin")
@@ -279,7 +255,7 @@ def test_scene_from_the_cached_data_file_through_the_native_reader(oracle, tmp_p
             r.set_camera(view)
             r.frame()
             ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=7, record_capacity=4096, maxGroups=4096, raster=geo)
-            _compare_frame(r.results(), ref)
+            compare_frame(r.results(), ref)
             assert np.array_equal(r.download_depth().view(np.uint32), depth.view(np.uint32))
         raw = bytearray(open(path, "rb").read()); raw[0] = 2
         open(path, "wb").write(raw)

@@ -16,23 +16,10 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import raster_path_scenes as S  # noqa: E402
-import visibility_ref as VR  # noqa: E402
+from suite_support import dev, vr  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 K = S.K
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
 
 
 def _dispatch(dev, s, texels):

@@ -14,39 +14,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lighting_ref as LR  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
+from suite_support import dev, gpu_scene, lr, op_counts, recorded, same, shadow_case_reference, sm  # noqa: E402, F401
 from toyrenderer_amd import accel, cached_scene, gltf_lite, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 TRACE, REFIT = "shadowmask_CS_ShadowMask", "raytracing_CS_RefitTLAS"
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def sm(tmp_path_factory):
-    return SR.load(tmp_path_factory.mktemp("shadowmask_ref_gpu"))
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref_for_shadows"))
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        first = tuple(int(i) for i in bad[0])
-        raise AssertionError(f"{what}: {len(bad)} of {got.size} words differ, first at {first}: got {got[first]}, want {want[first]}")
 
 
 def _gpu_scene(dev, sc):
@@ -121,10 +95,9 @@ class _Pass:
 # ---- 1. the cases -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", SS.CASES, ids=lambda c: c[0])
 def test_cases_match_brute_force(dev, sm, case):
-    """The refit's node boxes and matrices equal the reference's bit for bit; every texel of the mask and of the linear view depth
+    """The refit's node boxes and matrices equal the shadow_case_reference's bit for bit; every texel of the mask and of the linear view depth
     equals brute force; far texels keep the mask's sentinel."""
-    from test_shadowmask_ref import reference
-    sc, acc, k, depth, g, noise, mask, lvd = reference(sm, case)
+    sc, acc, k, depth, g, noise, mask, lvd = shadow_case_reference(sm, case)
     W, H = case[2]
     gs = _gpu_scene(dev, sc)
     p = _Pass(dev, gs, W, H, noise)
@@ -134,8 +107,8 @@ def test_cases_match_brute_force(dev, sm, case):
         want_nodes, want_records = SR.refit(sm, acc)
         assert nodes.tobytes() == want_nodes.tobytes(), f"{case[0]}: TLAS nodes after the refit"
         assert records.tobytes() == want_records.tobytes(), f"{case[0]}: TLAS instances after the refit"
-        _same(got_mask, mask, f"{case[0]}: mask")
-        _same(got_lvd, lvd, f"{case[0]}: linear view depth")
+        same(got_mask, mask, f"{case[0]}: mask")
+        same(got_lvd, lvd, f"{case[0]}: linear view depth")
         assert np.all(got_mask[depth == 0] == SR.SENTINEL8)
     finally:
         p.release(); gs.release()
@@ -165,8 +138,8 @@ def test_alpha_test_of_the_candidates_instance(dev, sm):
         p = _Pass(dev, gs, W, H, noise)
         try:
             got, got_lvd = p.run(k, depth, g)
-            _same(got, want, f"{lst} alpha {alpha} cutoff {cutoff}: mask")
-            _same(got_lvd, want_lvd, "linear view depth")
+            same(got, want, f"{lst} alpha {alpha} cutoff {cutoff}: mask")
+            same(got_lvd, want_lvd, "linear view depth")
         finally:
             p.release(); gs.release()
 
@@ -192,15 +165,14 @@ def test_far_depth_and_distant_texels(dev, sm):
     p = _Pass(dev, gs, W, H, noise)
     try:
         got, got_lvd = p.run(k, depth, g)
-        _same(got_lvd, want_lvd, "linear view depth")
-        _same(got, want, "mask")
+        same(got_lvd, want_lvd, "linear view depth")
+        same(got, want, "mask")
     finally:
         p.release(); gs.release()
 
 
 # ---- 4. frames through FrameDriver --------------------------------------------------------------------------------------------------------------
 def _cornell_gpu(dev, oracle):
-    from test_gpu_lighting import _gpu_scene as lighting_scene
     sc = SS.cornell()
     s = sc["loaded"]
     inst = sc["instances"].copy()
@@ -208,7 +180,7 @@ def _cornell_gpu(dev, oracle):
     inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
     sc["instances"] = inst
     s.meshData = sc["meshData"]                                                  # with m_GlobalIndexBufferIdx
-    gs = lighting_scene(dev, s, inst, s.vertices, sc["materials"])
+    gs = gpu_scene(dev, s, inst, s.vertices, sc["materials"])
     gs.set_raytracing(sc["indices"], sc["cached"].meshSpecific)
     return sc, gs
 
@@ -227,7 +199,7 @@ def _frame_reference(sm, sc, drv, instances, frame):
 def test_cornell_frames_with_animation(dev, oracle, sm, lr, debug_mode):
     """Two frames of FrameDriver(lighting=True, shadows=...) on the Cornell box next to a shadows=None driver, one wall moved inwards
     and the other far outside its rest box between them: everything in front of the pass equals the shadows=None run, the
-    mask and the linear view depth equal brute force with the frame's own matrices, LightingOutput equals the lighting reference
+    mask and the linear view depth equal brute force with the frame's own matrices, LightingOutput equals the lighting shadow_case_reference
     fed that mask, and debug view 11 shows it."""
     from toyrenderer_amd.frame import FrameDriver
     sc, gs = _cornell_gpu(dev, oracle)
@@ -259,15 +231,15 @@ def test_cornell_frames_with_animation(dev, oracle, sm, lr, debug_mode):
                 d.record(); d.run(); d.results()
             what = f"cornell view {debug_mode} frame {f}"
             for name in ("gbufferA", "visibility"):
-                _same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
+                same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
             k, depth, g, mask, lvd = _frame_reference(sm, sc, drv, instances, f)
-            _same(depth.view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
-            _same(drv.download_shadow_mask(), mask, what + ": mask")
-            _same(drv.linear_view_depth.download_mip(0), lvd, what + ": linear view depth")
+            same(depth.view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
+            same(drv.download_shadow_mask(), mask, what + ": mask")
+            same(drv.linear_view_depth.download_mip(0), lvd, what + ": linear view depth")
             assert np.any(mask == 0) and np.any(mask == 255)
-            _same(drv.lighting_output.download_mip(0), LR.lighting(lr, drv.lighting_consts, g, depth, shadow=mask, motion=drv.motion.download_mip(0)),
+            same(drv.lighting_output.download_mip(0), LR.lighting(lr, drv.lighting_consts, g, depth, shadow=mask, motion=drv.motion.download_mip(0)),
                   what + ": LightingOutput")
-            _same(base.lighting_output.download_mip(0), LR.lighting(lr, base.lighting_consts, g, depth, motion=base.motion.download_mip(0)), what + ": LightingOutput, shadows=None")
+            same(base.lighting_output.download_mip(0), LR.lighting(lr, base.lighting_consts, g, depth, motion=base.motion.download_mip(0)), what + ": LightingOutput, shadows=None")
             assert np.count_nonzero(drv.lighting_output.download_mip(0) != base.lighting_output.download_mip(0)) > 50
             seen.append(mask)
         assert np.count_nonzero(seen[0] != seen[1]) > 20                          # the moved boxes moved their shadows
@@ -277,7 +249,7 @@ def test_cornell_frames_with_animation(dev, oracle, sm, lr, debug_mode):
 
 def test_a_moved_instance_grows_its_ancestors(dev, sm):
     """The single passes on a scattered scene whose instance 5 is moved far outside its rest box after set_raytracing(): the refit
-    arrays equal the reference's and the mask equals brute force with the new matrices."""
+    arrays equal the shadow_case_reference's and the mask equals brute force with the new matrices."""
     sc = SS.scattered(65)
     acc = SR.Accel(sc)
     W, H = 67, 35
@@ -290,15 +262,15 @@ def test_a_moved_instance_grows_its_ancestors(dev, sm):
     p = _Pass(dev, gs, W, H, noise)
     try:
         first, _ = p.run(k, depth, g)
-        _same(first, SR.trace(sm, k, acc, depth, g, noise, SR.BRUTE)[0], "rest: mask")
+        same(first, SR.trace(sm, k, acc, depth, g, noise, SR.BRUTE)[0], "rest: mask")
         gs.instances.upload(moved)
         got, got_lvd = p.run(k, depth, g)
         want, want_lvd, _ = SR.trace(sm, k, acc, depth, g, noise, SR.BRUTE, instances=moved)
         nodes, records = p.structure()
         want_nodes, want_records = SR.refit(sm, acc, moved)
         assert nodes.tobytes() == want_nodes.tobytes() and records.tobytes() == want_records.tobytes()
-        _same(got, want, "moved: mask")
-        _same(got_lvd, want_lvd, "moved: linear view depth")
+        same(got, want, "moved: mask")
+        same(got_lvd, want_lvd, "moved: linear view depth")
         assert np.count_nonzero(got != first) > 100
     finally:
         p.release(); gs.release()
@@ -307,14 +279,13 @@ def test_a_moved_instance_grows_its_ancestors(dev, sm):
 def test_city_frame(dev, oracle, sm, lr, tmp_path):
     """The generated city at 48 x 27 through FrameDriver(lighting=True, ao, shadows): mask, linear view depth and LightingOutput."""
     from gbuffer_scenes import with_normals_and_materials
-    from test_gpu_lighting import _gpu_scene as lighting_scene
     from toyrenderer_amd.frame import FrameDriver
     from visibility_scenes import city
     s, sc0 = city(tmp_path, oracle, lods=False)
     v, sc0, mats = with_normals_and_materials(s, sc0)
     c = cached_scene.from_scene(s)
     s.meshData = c.meshData
-    gs = lighting_scene(dev, s, sc0["instances"], v, mats)
+    gs = gpu_scene(dev, s, sc0["instances"], v, mats)
     gs.set_raytracing(c.indices, c.meshSpecific)
     sc = dict(vertices=v, indices=c.indices, meshData=c.meshData, index_counts=c.meshSpecific["m_NumIndices"], instances=sc0["instances"], opaqueIds=s.opaqueIds,
               alphaMaskIds=s.alphaMaskIds, materials=mats)
@@ -328,10 +299,10 @@ def test_city_frame(dev, oracle, sm, lr, tmp_path):
         drv.record(); drv.run(); drv.results()
         k, depth, g, mask, lvd = _frame_reference(sm, sc, drv, sc0["instances"], 300)
         assert k["m_NoisePhase"][0] == F(300 & 0xFF) * F(1.61803398875)
-        _same(drv.download_shadow_mask(), mask, "city: mask")
-        _same(drv.linear_view_depth.download_mip(0), lvd, "city: linear view depth")
+        same(drv.download_shadow_mask(), mask, "city: mask")
+        same(drv.linear_view_depth.download_mip(0), lvd, "city: linear view depth")
         assert np.any(mask == 0) and np.any(mask == 255)
-        _same(drv.lighting_output.download_mip(0), LR.lighting(lr, drv.lighting_consts, g, depth, shadow=mask, ssao=drv.download_ssao()), "city: LightingOutput")
+        same(drv.lighting_output.download_mip(0), LR.lighting(lr, drv.lighting_consts, g, depth, shadow=mask, ssao=drv.download_ssao()), "city: LightingOutput")
     finally:
         drv.release(); gs.release()
 
@@ -340,8 +311,6 @@ def test_city_frame(dev, oracle, sm, lr, tmp_path):
 def test_shadows_add_two_dispatches_in_front_of_the_lighting_dispatch(dev, oracle):
     """shadows=None records the parent's list, command for command, and launches the same kernels; shadows=... adds exactly the refit
     and the trace between the AO passes and the lighting dispatch."""
-    from test_gpu_bloom import _recorded
-    from test_gpu_lighting import _op_counts
     from toyrenderer_amd.frame import FrameDriver
     sc, gs = _cornell_gpu(dev, oracle)
     view = gltf_lite.view_of(sc["camera"], (64, 36))
@@ -351,13 +320,13 @@ def test_shadows_add_two_dispatches_in_front_of_the_lighting_dispatch(dev, oracl
         for name, extra in (("parent", {}), ("none", dict(shadows=None)), ("shadows", dict(shadows=settings)), ("ao", dict(ao={})), ("both", dict(ao={}, shadows=settings))):
             drv = FrameDriver(dev, gs, view, record_capacity=4096, lighting=True, **extra)
             try:
-                counts[name] = _op_counts(dev, drv)
-                seen[name] = _recorded(drv)
+                counts[name] = op_counts(dev, drv)
+                seen[name] = recorded(drv)
             finally:
                 drv.release()
         drv = FrameDriver(dev, gs, view, record_capacity=4096, gbuffer=True, shadows=settings)                # the G-buffer alone is enough
         try:
-            seen["gbuffer"] = _recorded(drv)
+            seen["gbuffer"] = recorded(drv)
         finally:
             drv.release()
     finally:
@@ -453,7 +422,7 @@ def test_host_path_over_three_frames(oracle, sm, tmp_path):
             depth = r.download_depth()
             got = r.download_shadow_mask()
             mask, _, _ = SR.trace(sm, k, acc, depth, r.download_gbuffer_a(), noise, SR.BRUTE, mask=got)   # far texels keep what the mirror's texture held
-            _same(got, mask, f"frame {f}: mask")
+            same(got, mask, f"frame {f}: mask")
     finally:
         r.shutdown()
 
@@ -524,8 +493,8 @@ def test_misuse_is_refused(dev, sm):
         depth, g = SS.images(W, H, 12)
         want, want_lvd, _ = SR.trace(sm, k, acc, depth, g, noise, SR.BRUTE)
         got, got_lvd = p.run(k, depth, g)
-        _same(got, want, "a good pass after the refusals: mask")
-        _same(got_lvd, want_lvd, "its linear view depth")
+        same(got, want, "a good pass after the refusals: mask")
+        same(got_lvd, want_lvd, "its linear view depth")
     finally:
         dev.profile_enable(False)
         cl.release(); args.release(); p.release(); gs.release()

@@ -2,7 +2,7 @@
 
 Every case sits on one side of one switch -- the last length before it or the first after it, or just past a tile or chunk
 edge -- builds a scene whose list length is exactly that number, runs a frame through the C ABI and compares every output
-word with the CPU oracle (tests/test_gpu_parity.py::_compare_frame: records, masks, visible lists, dispatch and draw
+word with the CPU oracle (tests/test_gpu_parity.py::compare_frame: records, masks, visible lists, dispatch and draw
 arguments; late count and HZB).  Each case also asserts the path it took: from the "<shader>#<op>" names of the device
 profile where the paths are separate launches.  Where they are one launch that branches on the device (binned order and its
 guard, short pass, texel vs table kernel) the branch is not observed: the case is put on its side by construction, from the
@@ -19,9 +19,11 @@ import sys
 import numpy as np
 import pytest
 
-from toyrenderer_amd import synth
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from .test_gpu_parity import _compare_frame, _oracle_hzb, _upload_hzb
+from suite_support import compare_frame, dev, oracle_hzb, upload_hzb  # noqa: E402, F401
+from toyrenderer_amd import synth  # noqa: E402
+
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "toyrenderer_amd", "csrc")
@@ -139,14 +141,6 @@ def _spec(n, *, meshlets=32, seed=1, **kw):
     return synth.SceneSpec(num_meshes=16, num_instances=n, meshlets_lod0=meshlets, max_lods=1, seed=seed, **kw)
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
 VIEW = synth.make_view(eye=(0.3, 0.1, 0.5), yaw=0.02, prev_eye=(0.0, 0.0, 0.0), prev_yaw=0.0, render=(640, 360))
 D_PREV = synth.gen_depth(VIEW, num_occluders=60, seed=11, scale=3.0)
 D_CUR = synth.gen_depth(VIEW, num_occluders=40, seed=12, scale=3.0)
@@ -158,10 +152,10 @@ def _frame(dev, oracle, spec, cap, flags, *, depth_prev=None, depth_cur=None, vi
     scene = synth.make_scene(spec)
     gs = GpuScene(dev, scene.instances, scene.meshData, scene.meshlets, scene.opaqueIds, scene.alphaMaskIds)
     drv = FrameDriver(dev, gs, view, record_capacity=cap, culling_flags=flags)
-    hzb = _oracle_hzb(oracle, view, depth_prev)
+    hzb = oracle_hzb(oracle, view, depth_prev)
     try:
         if depth_prev is not None:
-            _upload_hzb(drv, hzb)
+            upload_hzb(drv, hzb)
         if depth_cur is not None:
             drv.depth.upload_mip(0, depth_cur)
         dev.profile_reset()
@@ -178,7 +172,7 @@ def _frame(dev, oracle, spec, cap, flags, *, depth_prev=None, depth_cur=None, vi
         drv.release()
         gs.release()
     ref = oracle.frame(scene.as_oracle(), view.as_dict(), hzb, depth_cur, cullingFlags=flags, maxGroups=cap, record_capacity=cap)
-    _compare_frame(got, ref)
+    compare_frame(got, ref)
     if flags & 2:
         assert got["lateCount"] == int(ref.lateCount[0])
     if hzb_got is not None:

@@ -2,9 +2,7 @@
 bindings at sizes around every tile edge with every depth content, special directions, hostile constant blocks, whole frames
 through FrameDriver(sky=...) with the existing bloom and post references behind them, the C++ host mirror, and misuse.  The target
 is pre-filled with a sentinel so that a texel the pass must leave alone shows."""
-import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -14,56 +12,16 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import bloom_ref as BR  # noqa: E402
 import lighting_ref as LR  # noqa: E402
-import postprocess_ref as PR  # noqa: E402
 import sky_ref as SR  # noqa: E402
 from gbuffer_scenes import with_normals_and_materials  # noqa: E402
+from suite_support import bits, bl, dev, gpu_scene, host_renderer, kernel_constant, lit_city, lit_cornell, lr, op_counts, post_chain_reference, pr, recorded, same, sk  # noqa: E402, F401
 from toyrenderer_amd import gltf_lite, sky, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 from visibility_scenes import city  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 SENTINEL = SR.SENTINEL
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def sk(tmp_path_factory):
-    return SR.load(tmp_path_factory.mktemp("sky_ref_gpu"))
-
-
-@pytest.fixture(scope="module")
-def bl(tmp_path_factory):
-    return BR.load(tmp_path_factory.mktemp("bloom_ref_for_sky"))
-
-
-@pytest.fixture(scope="module")
-def pr(tmp_path_factory):
-    return PR.load(tmp_path_factory.mktemp("postprocess_ref_for_sky"))
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref_for_sky"))
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    assert np.array_equal(got, want), f"{what}: {int(np.count_nonzero(got != want))} of {got.size} words differ"
-
-
-def _kernel_constant(name):
-    src = open(os.path.join(ROOT, "toyrenderer_amd", "csrc", "k_sky.hip")).read()
-    return int(re.search(r"\b" + name + r" = (\d+)", src).group(1))
 
 
 class _Pass:
@@ -96,7 +54,7 @@ class _Pass:
 def _sizes():
     """One below, at and one above the kernel's tile in both axes, two tiles each way (more than one workgroup in each axis), and
     the issue's list."""
-    tw, th = _kernel_constant("kSkyTileW"), _kernel_constant("kSkyBlock") // _kernel_constant("kSkyTileW")
+    tw, th = kernel_constant("k_sky.hip", "kSkyTileW"), kernel_constant("k_sky.hip", "kSkyBlock") // kernel_constant("k_sky.hip", "kSkyTileW")
     assert (tw, th) == (64, 4)
     return [(tw - 1, th - 1), (tw, th), (tw + 1, th + 1), (2 * tw, 2 * th), (1, 1), (2, 2), (67, 35), (129, 3), (270, 135)]
 
@@ -119,14 +77,14 @@ def test_single_passes_match_the_reference(dev, sk, size):
             with np.errstate(invalid="ignore"):
                 written = depth <= 0.0
             assert np.array_equal(want == SENTINEL, ~written), name             # no sky word of the reference equals the sentinel
-            _same(p.run(k, depth), want, f"{W}x{H} depth {name}")
+            same(p.run(k, depth), want, f"{W}x{H} depth {name}")
         zero = np.zeros((H, W), F)
         for c, pitch, down in _cameras():
             k = SR.block(SR.CONFIGS[c], W, H, pitch, down=down)
             want, view = SR.sky_pass(sk, k, zero, want_view=True)
             if down:
                 assert np.all(view[..., 1] < 0)                                 # every V.y is clamped to 0
-            _same(p.run(k, zero), want, f"{W}x{H} configuration {c} pitch {pitch} down {down}")
+            same(p.run(k, zero), want, f"{W}x{H} configuration {c} pitch {pitch} down {down}")
     finally:
         p.release()
 
@@ -137,7 +95,7 @@ def test_samplers_are_accepted_and_ignored(dev, sk):
     try:
         k = SR.block(SR.CONFIGS[1], 67, 35)
         depth = SR.depth_images(67, 35)["mix"]
-        _same(p.run(k, depth, extra=(SAMPLER(0), SAMPLER(3))), SR.sky_pass(sk, k, depth), "with samplers")
+        same(p.run(k, depth, extra=(SAMPLER(0), SAMPLER(3))), SR.sky_pass(sk, k, depth), "with samplers")
     finally:
         p.release()
 
@@ -163,7 +121,7 @@ def test_special_directions(dev, sk):
             else:
                 finite_seen += 1
                 assert np.all(rgb[py, px] >= 0.49)                              # the disc term: 0.5 cos^256 with cos within 2^-23 of 1
-            _same(p.run(k, zero), want, f"sun along the view vector of pixel ({px}, {py})")
+            same(p.run(k, zero), want, f"sun along the view vector of pixel ({px}, {py})")
             if nan_seen and finite_seen and nan_seen + finite_seen >= 12:
                 break
         assert nan_seen and finite_seen, (nan_seen, finite_seen)                # both outcomes occur and both are pinned
@@ -174,19 +132,19 @@ def test_special_directions(dev, sk):
         k["m_ClipToWorld"] = c2w
         want, view = SR.sky_pass(sk, k, zero, want_view=True)
         assert np.all(view[H // 2, :, 1] == 0.0)
-        _same(p.run(k, zero), want, "a row with V.y = 0")
+        same(p.run(k, zero), want, "a row with V.y = 0")
         # the sun behind the camera: gamma > 90 degrees everywhere
         k = SR.block(SR.CONFIGS[0], W, H, 0.0)
         k["m_SunLightDir"] = SR.unit((0.0, 0.3, 1.0))
         want, view = SR.sky_pass(sk, k, zero, want_view=True)
         assert np.all(view.reshape(-1, 3).astype(np.float64) @ k["m_SunLightDir"][0].astype(np.float64) < 0)
-        _same(p.run(k, zero), want, "gamma > 90 degrees")
+        same(p.run(k, zero), want, "gamma > 90 degrees")
         # the sun perpendicular to the central column's rays: cos gamma is tiny, of either sign, along it
         k["m_SunLightDir"] = (1.0, 0.0, 0.0)
         want, view = SR.sky_pass(sk, k, zero, want_view=True)
         cg = view[..., 0]
         assert np.any((cg > 0) & (cg < 0.05)) and np.any(cg < 0)
-        _same(p.run(k, zero), want, "small cos gamma")
+        same(p.run(k, zero), want, "small cos gamma")
     finally:
         p.release()
 
@@ -223,30 +181,20 @@ def test_hostile_blocks(dev, sk):
         k["m_CameraPosition"] = (np.inf, 0.0, 0.0)
         blocks["camera at infinity"] = k
         for name, k in blocks.items():
-            _same(p.run(k, depth), SR.sky_pass(sk, k, depth), name)
+            same(p.run(k, depth), SR.sky_pass(sk, k, depth), name)
     finally:
         p.release()
 
 
 # ---- 4. frames ------------------------------------------------------------------------------------------------------------------
 def _cornell(oracle):
-    from test_gltf_cornell import _fixture
-    with open(os.path.join(ROOT, "tests", "golden", "cornell_materials.json")) as f:
-        cm = json.load(f)
-    _, s, camera = _fixture()
-    mats = gltf_lite.material_table([{"pbrMetallicRoughness": {"baseColorFactor": c, "metallicFactor": 0}} for c in cm["baseColorFactor"]])
-    s.materials, s.primMaterial = mats, np.array(cm["primitiveMaterial"], np.uint32)
-    inst = gltf_lite.apply_materials(s)
-    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
-    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
-    return s, inst, s.vertices, mats, camera, dict(dir_light=(tuple(float(x) for x in SR.unit((0.3, 0.8, -0.52))), 3.0),
-                                                   camera_origin=tuple(float(x) for x in camera.position), auto_exposure=(0.004, 12.0, 0.5))
+    *scene, camera = lit_cornell(oracle)
+    return (*scene, camera, dict(dir_light=(tuple(float(x) for x in SR.unit((0.3, 0.8, -0.52))), 3.0), camera_origin=tuple(float(x) for x in camera.position),
+                                 auto_exposure=(0.004, 12.0, 0.5)))
 
 
 def _city(oracle, tmp_path):
-    s, sc = city(tmp_path, oracle)
-    v, sc, mats = with_normals_and_materials(s, sc)
-    return s, sc["instances"], v, mats, s.cameras[0], dict(dir_light=(tuple(float(x) for x in SR.unit((0.2, 0.35, -0.9))), 2.5))
+    return (*lit_city(oracle, tmp_path), dict(dir_light=(tuple(float(x) for x in SR.unit((0.2, 0.35, -0.9))), 2.5)))
 
 
 FRAMES = [("cornell", (320, 180), (2.0, (0.1, 0.1, 0.1))), ("city", (540, 270), (2.0, (0.1, 0.1, 0.1))), ("city", (67, 35), (4.0, (0.3, 0.2, 0.1)))]
@@ -257,11 +205,9 @@ def test_frames_match_the_reference(dev, oracle, sk, bl, pr, tmp_path, scene, re
     """Three frames of FrameDriver(lighting, post, bloom_mips=6, sky) next to a sky=None driver: everything in front of the pass is
     equal; LightingOutput is the sky=None image where depth > 0 and the reference sky elsewhere, nowhere 0 where the reference is
     not; the histogram, the luminance, the bloom mips and the back buffer are the existing references fed that LightingOutput."""
-    from test_gpu_lighting import _gpu_scene
-    from test_gpu_postprocess import _bits, _post_chain_reference
     from toyrenderer_amd.frame import FrameDriver
     s, inst, vertices, mats, camera, kw = _cornell(oracle) if scene == "cornell" else _city(oracle, tmp_path)
-    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    gs = gpu_scene(dev, s, inst, vertices, mats)
     view = gltf_lite.view_of(camera, render)
     mips = min(6, BR.max_mips(*render))
     common = dict(record_capacity=4096, culling_flags=7, lighting=True, post=True, bloom_mips=mips, **kw)
@@ -275,11 +221,11 @@ def test_frames_match_the_reference(dev, oracle, sk, bl, pr, tmp_path, scene, re
                 d.record(q); d.run(); d.results()
             what = f"{scene} {render} frame {f}"
             for name in ("gbufferA", "visibility"):
-                _same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
-            _same(drv.motion.download_mip(0).view(np.uint16), base.motion.download_mip(0).view(np.uint16), what + ": motion")
+                same(getattr(drv, name).download_mip(0), getattr(base, name).download_mip(0), what + ": " + name)
+            same(drv.motion.download_mip(0).view(np.uint16), base.motion.download_mip(0).view(np.uint16), what + ": motion")
             depth = drv.depth.download_mip(0)
-            _same(depth.view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
-            _same(drv.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
+            same(depth.view(np.uint32), base.depth.download_mip(0).view(np.uint32), what + ": depth")
+            same(drv.hzb.download_chain(), base.hzb.download_chain(), what + ": HZB")
             assert qd.get() == qb.get(), what + ": pipeline statistics"
             sun = np.asarray(kw["dir_light"][0], F)
             k = sky.pass_parameters(drv.lighting_consts["m_ClipToWorld"][0], sun, kw.get("camera_origin", (0.0, 0.0, 0.0)), sky.sky_parameters(SR.dataset(), setting[0], setting[1], sun))
@@ -287,18 +233,18 @@ def test_frames_match_the_reference(dev, oracle, sk, bl, pr, tmp_path, scene, re
             lit = base.lighting_output.download_mip(0)
             want = SR.sky_pass(sk, k, depth, dest=lit)
             got = drv.lighting_output.download_mip(0)
-            _same(got, want, what + ": LightingOutput")
-            _same(got[depth > 0], lit[depth > 0], what + ": lit texels")
+            same(got, want, what + ": LightingOutput")
+            same(got[depth > 0], lit[depth > 0], what + ": lit texels")
             assert not np.any((got == 0) & (want != 0))
             if scene == "city":
                 assert np.count_nonzero(depth <= 0) > 0 and np.count_nonzero(got[depth <= 0]) > 0      # the view sees past the geometry
             chain = BR.bloom_chain(bl, want, *render, mips, drv.bloom_filter_radius)
             for m in range(mips):
-                _same(drv.download_bloom(m), chain[m], f"{what}: bloom mip {m}")
-            back, hist, luminance, _ = _post_chain_reference(pr, drv, want, luminance, bloom=chain[0])
-            _same(drv.histogram.download(np.uint32, 256), hist, what + ": histogram")
-            _same(drv.back_buffer.download_mip(0), back, what + ": back buffer")
-            assert _bits(drv.luminance.download(F, 1)).tolist() == _bits(luminance).tolist(), what
+                same(drv.download_bloom(m), chain[m], f"{what}: bloom mip {m}")
+            back, hist, luminance, _ = post_chain_reference(pr, drv, want, luminance, bloom=chain[0])
+            same(drv.histogram.download(np.uint32, 256), hist, what + ": histogram")
+            same(drv.back_buffer.download_mip(0), back, what + ": back buffer")
+            assert bits(drv.luminance.download(F, 1)).tolist() == bits(luminance).tolist(), what
             if np.count_nonzero(depth <= 0):
                 assert np.count_nonzero(drv.back_buffer.download_mip(0) != base.back_buffer.download_mip(0)) > 0
     finally:
@@ -308,11 +254,9 @@ def test_frames_match_the_reference(dev, oracle, sk, bl, pr, tmp_path, scene, re
 def test_sky_adds_one_dispatch_behind_the_lighting_dispatch(dev, oracle, tmp_path):
     """sky=None records the parent's list, command for command, and launches the same kernels; sky=... adds exactly one dispatch
     directly behind the lighting dispatch, in front of bloom and the histogram clear, under a debug view too."""
-    from test_gpu_bloom import _recorded
-    from test_gpu_lighting import _gpu_scene, _op_counts
     from toyrenderer_amd.frame import FrameDriver
     s, inst, vertices, mats, camera, kw = _city(oracle, tmp_path)
-    gs = _gpu_scene(dev, s, inst, vertices, mats)
+    gs = gpu_scene(dev, s, inst, vertices, mats)
     view = gltf_lite.view_of(camera, (320, 180))
     seen, counts = {}, {}
     try:
@@ -321,8 +265,8 @@ def test_sky_adds_one_dispatch_behind_the_lighting_dispatch(dev, oracle, tmp_pat
         for name, extra in variants:
             drv = FrameDriver(dev, gs, view, record_capacity=4096, post=True, bloom_mips=5, **extra, **kw)
             try:
-                counts[name] = _op_counts(dev, drv)
-                seen[name] = _recorded(drv)
+                counts[name] = op_counts(dev, drv)
+                seen[name] = recorded(drv)
             finally:
                 drv.release()
         with pytest.raises(ValueError, match="lighting=True"):
@@ -354,12 +298,7 @@ def test_host_path_over_three_frames(oracle, sk, lr, tmp_path):
     inst_in = s.instances.copy()
     inst_in["m_MaterialDataIdx"] = sc0["instances"]["m_MaterialDataIdx"]
     ds = SR.dataset()
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(inst_in, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(v, s.meshletVertexIds, s.meshletTriangles)
-        r.load_materials(mats)
+    with host_renderer(s, inst_in, (v, s.meshletVertexIds, s.meshletTriangles), mats, render=render, max_groups=4096) as r:
         with pytest.raises(host.HostError, match="no dataset"):
             r.set_sky(True)
         r.load_sky_dataset(ds)
@@ -402,15 +341,13 @@ def test_host_path_over_three_frames(oracle, sk, lr, tmp_path):
             if setting is None:
                 with pytest.raises(host.HostError, match="did not run"):
                     r.sky_consts()
-                _same(got, lit, f"frame {f}: LightingOutput without the sky")
+                same(got, lit, f"frame {f}: LightingOutput without the sky")
                 assert np.count_nonzero(got[depth <= 0]) == 0
             else:
                 k = sky.pass_parameters(lk["m_ClipToWorld"][0], sun, lk["m_CameraOrigin"][0], sky.sky_parameters(ds, setting[0], setting[1], sun))
                 assert r.sky_consts().tobytes() == k.tobytes(), f
-                _same(got, SR.sky_pass(sk, k, depth, dest=lit), f"frame {f}: LightingOutput")
+                same(got, SR.sky_pass(sk, k, depth, dest=lit), f"frame {f}: LightingOutput")
                 assert np.count_nonzero(depth <= 0) > 0 and np.count_nonzero(got[depth <= 0]) > 0
-    finally:
-        r.shutdown()
 
 
 # ---- 6. misuse at the back end --------------------------------------------------------------------------------------------------
@@ -464,7 +401,7 @@ def test_misuse_is_refused(dev, sk):
         cl.dispatch(name, [CB(0, cl.constant_buffer(k, "SkyPassParameters")), TEX_SRV(0, depth), TEX_UAV(0, target, 0)], groups)
         cl.close()
         dev.execute(cl); dev.wait_idle()
-        _same(target.download_mip(0), SR.sky_pass(sk, k, d), "a good pass after the refusals")
+        same(target.download_mip(0), SR.sky_pass(sk, k, d), "a good pass after the refusals")
         # mip 0 of a render-target chain is a valid target; its other mips keep their words
         for m in range(3):
             chain.upload_mip(m, np.full((H >> m, W >> m), SENTINEL + m, np.uint32))
@@ -472,7 +409,7 @@ def test_misuse_is_refused(dev, sk):
         cl.dispatch(name, [CB(0, cl.constant_buffer(k, "SkyPassParameters")), TEX_SRV(0, depth), TEX_UAV(0, chain, 0)], groups)
         cl.close()
         dev.execute(cl); dev.wait_idle()
-        _same(chain.download_mip(0), SR.sky_pass(sk, k, d), "mip 0 of a chain")
+        same(chain.download_mip(0), SR.sky_pass(sk, k, d), "mip 0 of a chain")
         for m in (1, 2):
             assert np.all(chain.download_mip(m) == SENTINEL + m)
     finally:

@@ -11,32 +11,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from suite_support import compare_frame, dev, gpu_scene, host_renderer, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from toyrenderer_amd import gltf_lite, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 from visibility_scenes import city, consts, hostile_soup, inside_view, with_duplicates  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    from toyrenderer_amd import rhi
-    d = rhi.Device(0)
-    yield d
-    d.destroy()
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
-
-
-def _gpu_scene(dev, s, inst):
-    from toyrenderer_amd.frame import GpuScene
-    gs = GpuScene(dev, inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-    gs.set_geometry(s.vertices, s.meshletVertexIds, s.meshletTriangles)
-    return gs
 
 
 def _check_buffers(drv, vr, k, geo, ref, W, H, what):
@@ -55,10 +36,9 @@ def _check_buffers(drv, vr, k, geo, ref, W, H, what):
 def test_frames_match_the_reference_under_every_flag(dev, oracle, vr, tmp_path, flags):
     """Two frames of a moving camera: visibility buffer and motion equal the reference; depth, HZB and every cull output
     are bit-identical to a raster_depth=True run without the visibility buffer."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
-    gs = _gpu_scene(dev, s, sc["instances"])
+    gs = gpu_scene(dev, s, sc["instances"])
     cam = s.cameras[0]
     render = (640, 360)
     P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
@@ -81,8 +61,8 @@ def test_frames_match_the_reference_under_every_flag(dev, oracle, vr, tmp_path, 
             got, got_base = drv.results(), base.results()
             ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=flags, record_capacity=4096,
                                raster=(I.world_to_clip(V, P), s.vertices, s.meshletVertexIds, s.meshletTriangles))
-            _compare_frame(got, ref)
-            _compare_frame(got_base, ref)
+            compare_frame(got, ref)
+            compare_frame(got_base, ref)
             assert np.array_equal(drv.depth.download_mip(0).view(np.uint32), base.depth.download_mip(0).view(np.uint32))
             assert np.array_equal(drv.depth.download_mip(0).view(np.uint32), depth.view(np.uint32))
             assert np.array_equal(drv.hzb.download_chain(), base.hzb.download_chain())
@@ -205,7 +185,7 @@ def test_animated_frames_with_alpha_mask_slots(dev, oracle, vr, tmp_path):
     s, sc = city(tmp_path, oracle)
     assert len(s.alphaMaskIds) > 0
     inst0 = sc["instances"].copy()
-    gs = _gpu_scene(dev, s, inst0)
+    gs = gpu_scene(dev, s, inst0)
     cam = s.cameras[0]
     render = (640, 360)
     P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
@@ -243,7 +223,7 @@ def test_animated_frames_with_alpha_mask_slots(dev, oracle, vr, tmp_path):
 def test_pipeline_statistics_are_unchanged(dev, oracle, tmp_path):
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
-    gs = _gpu_scene(dev, s, sc["instances"])
+    gs = gpu_scene(dev, s, sc["instances"])
     view = gltf_lite.view_of(s.cameras[0], (640, 360))
     out = []
     try:
@@ -306,7 +286,7 @@ def test_misuse_is_refused(dev, oracle, tmp_path):
         dev.create_texture(W, H, 2, rhi.FORMAT_RG32_UINT, "two mips")
     # a shard exchange with the visibility buffer fails loudly: list positions are per rank
     s, scc = city(tmp_path, oracle)
-    gs = _gpu_scene(dev, s, scc["instances"])
+    gs = gpu_scene(dev, s, scc["instances"])
     try:
         with pytest.raises(ValueError, match="shard"):
             FrameDriver(dev, gs, gltf_lite.view_of(s.cameras[0], (64, 32)), record_capacity=64, visibility=True,
@@ -319,7 +299,7 @@ def test_depth_only_list_records_the_same_ops(dev, oracle, tmp_path):
     """Without the switch the frame still dispatches basepass_MS_Main_depth (main, tiles) and nothing new."""
     from toyrenderer_amd.frame import FrameDriver
     s, sc = city(tmp_path, oracle)
-    gs = _gpu_scene(dev, s, sc["instances"])
+    gs = gpu_scene(dev, s, sc["instances"])
     drv = FrameDriver(dev, gs, gltf_lite.view_of(s.cameras[0], (320, 180)), record_capacity=4096, raster_depth=True)
     try:
         dev.profile_reset(); dev.profile_enable(True)
@@ -381,7 +361,6 @@ def test_host_path_with_animated_nodes(oracle, vr, tmp_path):
     """The C++ host mirror (trhost_set_visibility_buffer): five frames with animated node transforms and a moving camera.
     Texels equal the reference computed from Renderer.instances() and each frame's view; motion too from the second
     frame on (the first frame's previous projection is the host's initial one, not the test's).  Then the refusals."""
-    from test_gpu_parity import _compare_frame
     from toyrenderer_amd import host
     s, _ = city(tmp_path, oracle)
     cam = s.cameras[0]
@@ -390,11 +369,7 @@ def test_host_path_with_animated_nodes(oracle, vr, tmp_path):
     hzb = oracle.HzbTexture(*I.hzb_dims(*render))
     depth = np.zeros((render[1], render[0]), np.float32)
     geo_v = (s.vertices, s.meshletVertexIds, s.meshletTriangles)
-    r = host.Renderer(render=render, max_groups=4096)
-    try:
-        r.load_scene(s.instances, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-        r.load_nodes(s.nodes, s.primToNode)
-        r.load_geometry(*geo_v)
+    with host_renderer(s, s.instances, geo_v, render=render, max_groups=4096) as r:
         r.set_visibility_buffer(True)
         r.set_culling(7)
         prevV = synth.world_to_view((0.0, 0.0, 0.0), cam.orientation)
@@ -413,7 +388,7 @@ def test_host_path_with_animated_nodes(oracle, vr, tmp_path):
             sc = dict(s.as_oracle()); sc["instances"] = inst
             ref = oracle.frame(sc, view.as_dict(), hzb, depth, cullingFlags=7, record_capacity=4096, maxGroups=4096,
                                raster=(I.world_to_clip(V, P), *geo_v))
-            _compare_frame(got, ref)
+            compare_frame(got, ref)
             k = consts(view)
             g = VR.Geometry(sc, *geo_v)
             vis_ref, _ = VR.frame_visibility(vr, k, g, ref, *render)
@@ -433,8 +408,6 @@ def test_host_path_with_animated_nodes(oracle, vr, tmp_path):
             host._check(host.load().trhost_set_limits(1 << 19, 0))
         with pytest.raises(host.HostError, match="per rank"):
             host._check(host.load().trhost_exchange_create(ctypes.byref(host.ExchangeDesc())))
-    finally:
-        r.shutdown()
 
 
 def test_host_path_refuses_a_shard_exchange_and_large_limits(oracle, tmp_path):

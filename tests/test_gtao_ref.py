@@ -12,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import gtao_ref as GR  # noqa: E402
+from suite_support import gt  # noqa: E402, F401
 from toyrenderer_amd import gtao, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
@@ -22,11 +23,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # between the binary16 reference and the float64 restatement, per quality level
 MEASURED_MAX = {0: 8, 1: 5, 2: 5, 3: 5}
 MEASURED_MEAN = {0: 0.360, 1: 0.403, 2: 0.358, 3: 0.434}             # recorded, not asserted
-
-
-@pytest.fixture(scope="module")
-def gt(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gtao_ref"))
 
 
 # ---- 1. rounding ------------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,6 @@ restatement written from the HLSL, the debug views against closed forms, and the
 import math
 import os
 import re
-import subprocess
 import sys
 from fractions import Fraction
 
@@ -17,20 +16,12 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gbuffer_ref as GR  # noqa: E402
 import lighting_ref as LR  # noqa: E402
 import lighting_scenes as LS  # noqa: E402
+from ref_build import layout_probe  # noqa: E402
+from suite_support import gr, lr  # noqa: E402, F401
 from toyrenderer_amd import interop as I  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref"))
-
-
-@pytest.fixture(scope="module")
-def gr(tmp_path_factory):
-    return GR.load(tmp_path_factory.mktemp("gbuffer_ref"))
 
 
 # ---- the R11G11B10_FLOAT store -------------------------------------------------------------------------------------------
@@ -322,14 +313,7 @@ def test_deferred_lighting_consts_layout(tmp_path):
     """A g++-compiled probe prints sizeof / offsetof of interop::DeferredLightingConsts (csrc/ShaderInterop.h): 112 bytes, every
     field where the numpy dtype and tests/lighting_ref.c have it."""
     fields = list(I.DeferredLightingConsts.names)
-    lines = ['#include <cstdio>', '#include "ShaderInterop.h"', "int main() {", '    printf("sizeof %zu\\n", sizeof(interop::DeferredLightingConsts));']
-    lines += [f'    printf("{f} %zu\\n", offsetof(interop::DeferredLightingConsts, {f}));' for f in fields]
-    lines += ["    return 0;", "}"]
-    src = tmp_path / "probe.cpp"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "toyrenderer_amd", "csrc"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    out = layout_probe(tmp_path, [("sizeof", "sizeof(interop::DeferredLightingConsts)")] + [(f, f"offsetof(interop::DeferredLightingConsts, {f})") for f in fields])
     assert int(out["sizeof"]) == 112 == I.DeferredLightingConsts.itemsize
     want = dict(m_ClipToWorld=0, m_CameraOrigin=64, m_SSAOEnabled=76, m_DebugMode=80, m_DirectionalLightVector=84, m_DirectionalLightStrength=96,
                 m_LightingOutputResolution=100, m_bRTDDGIEnabled=108)

@@ -11,16 +11,12 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import material_texture_scenes as S  # noqa: E402
 import material_textures_ref as MT  # noqa: E402
+from suite_support import mt  # noqa: E402, F401
 from toyrenderer_amd import gltf_lite  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def mt(tmp_path_factory):
-    return MT.load(tmp_path_factory.mktemp("material_textures_ref"))
 
 
 def test_srgb_table_is_the_float64_formula_rounded_once(mt):

@@ -5,28 +5,23 @@ HLSL in numpy float64), exact integers for the histogram sum, and a g++ probe fo
 import math
 import os
 import subprocess
+import sys
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from tests import lighting_ref as LR
-from tests import postprocess_ref as PR
-from toyrenderer_amd import interop as I
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import lighting_ref as LR  # noqa: E402
+import postprocess_ref as PR  # noqa: E402
+from ref_build import layout_probe  # noqa: E402
+from suite_support import lr, pr  # noqa: E402, F401
+from toyrenderer_amd import interop as I  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 U = 2.0 ** -24                                                   # binary32 unit roundoff
-
-
-@pytest.fixture(scope="module")
-def pr(tmp_path_factory):
-    return PR.load(tmp_path_factory.mktemp("postprocess_ref"))
-
-
-@pytest.fixture(scope="module")
-def lr(tmp_path_factory):
-    return LR.load(tmp_path_factory.mktemp("lighting_ref_for_post"))
 
 
 # ---- the load ---------------------------------------------------------------------------------------------------------------
@@ -435,16 +430,11 @@ WANT_LAYOUT = {
 def test_parameter_struct_layouts(tmp_path):
     """A g++-compiled probe prints sizeof / offsetof of the three structs of csrc/ShaderInterop.h: every field where the numpy
     dtypes and tests/postprocess_ref.c have it."""
-    lines = ['#include <cstdio>', '#include "ShaderInterop.h"', "int main() {"]
+    prints = []
     for s, (_, fields) in WANT_LAYOUT.items():
-        lines.append(f'    printf("{s} %zu\\n", sizeof(interop::{s}));')
-        lines += [f'    printf("{s}.{f} %zu\\n", offsetof(interop::{s}, {f}));' for f in fields]
-    lines += ["    return 0;", "}"]
-    src = tmp_path / "probe.cpp"
-    src.write_text("\n".join(lines) + "\n")
-    exe = tmp_path / "probe"
-    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "toyrenderer_amd", "csrc"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+        prints.append((s, f"sizeof(interop::{s})"))
+        prints += [(f"{s}.{f}", f"offsetof(interop::{s}, {f})") for f in fields]
+    out = layout_probe(tmp_path, prints)
     for s, (size, fields) in WANT_LAYOUT.items():
         dt = getattr(I, s)
         assert int(out[s]) == size == dt.itemsize == I.SIZES[s]

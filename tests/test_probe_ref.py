@@ -5,10 +5,15 @@ import os
 import random
 import re
 import subprocess
+import sys
 from decimal import Decimal, getcontext
 from fractions import Fraction
 
 import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from suite_support import PROBE_LAUNCHERS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "toyrenderer_amd", "csrc")
@@ -236,7 +241,6 @@ def test_probe_built_with_the_product_flags():
 
 
 def test_probe_exports_every_bound_launcher():
-    from tests.test_gpu_primitives import PROBE_LAUNCHERS
     lib = C.CDLL(PROBE_PATH)
     for name in PROBE_LAUNCHERS:
         assert hasattr(lib, name), name

@@ -11,16 +11,11 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import raster_path_scenes as S  # noqa: E402
-import visibility_ref as VR  # noqa: E402
+from suite_support import vr  # noqa: E402, F401
 
 K = S.K
 MI355X_CUS = 256                                     # the GPU test uses the device's own count
 ROUNDS = [K["kTileList"] - K["kBlock"], K["kTileList"], K["kTileList"] + 1, 2 * K["kTileList"] + 1]
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
 
 
 OWNER_SCENES = ([(f"a-{kind}", lambda kind=kind: S.small_box_scene(kind), 1) for kind in ("box1024", "box1025", "box33x32", "edge_clamped")]

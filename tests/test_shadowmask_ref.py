@@ -14,16 +14,12 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
+from suite_support import shadow_case_reference, sm  # noqa: E402, F401
 from toyrenderer_amd import accel, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
 F = np.float32
 INNER = I.kAccelInner
-
-
-@pytest.fixture(scope="module")
-def sm(tmp_path_factory):
-    return SR.load(tmp_path_factory.mktemp("shadowmask_ref"))
 
 
 # ---- 1. the builder ---------------------------------------------------------------------------------------------------------------------
@@ -129,23 +125,10 @@ def test_tlas_invariants(n):
 
 
 # ---- 2. the walk against brute force -------------------------------------------------------------------------------------------------------
-_REF = {}
-
-
-def reference(sm, case):
-    """(scene, accel, consts, depth, gbuffer, noise, brute-force mask, linear view depth) of one case, computed once."""
-    if case[0] not in _REF:
-        sc, k, depth, g, noise = SS.case_inputs(case)
-        acc = SR.Accel(sc)
-        mask, lvd, _ = SR.trace(sm, k, acc, depth, g, noise, SR.BRUTE)
-        _REF[case[0]] = (sc, acc, k, depth, g, noise, mask, lvd)
-    return _REF[case[0]]
-
-
 @pytest.mark.parametrize("case", SS.CASES, ids=lambda c: c[0])
 def test_walk_equals_brute_force(sm, case):
     """Every texel: 0 differing.  Far texels keep the mask's sentinel and get 0x7BFF; no other texel keeps a sentinel."""
-    sc, acc, k, depth, g, noise, mask, lvd = reference(sm, case)
+    sc, acc, k, depth, g, noise, mask, lvd = shadow_case_reference(sm, case)
     got, got_lvd, (boxes, tris) = SR.trace(sm, k, acc, depth, g, noise, SR.WALK)
     far = depth == 0
     print(f"{case[0]}: occluded {int((mask == 0).sum())} of {int((~far).sum())} traced texels, {boxes} box tests, {tris} triangle tests")

@@ -12,16 +12,12 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import sky_ref as SR  # noqa: E402
+from suite_support import sk  # noqa: E402, F401
 from toyrenderer_amd import interop as I  # noqa: E402
 from toyrenderer_amd import sky  # noqa: E402
 
 F = np.float32
 W, H = 67, 35
-
-
-@pytest.fixture(scope="module")
-def sk(tmp_path_factory):
-    return SR.load(tmp_path_factory.mktemp("sky_ref"))
 
 
 def _bits(a):

@@ -11,17 +11,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from suite_support import cornell_fixture, vr  # noqa: E402, F401
 import visibility_ref as VR  # noqa: E402
 from scene_gen import all_meshlets_visible  # noqa: E402
 from toyrenderer_amd import gltf_lite, synth  # noqa: E402
 from visibility_scenes import city, consts, hostile_soup, inside_view, with_duplicates  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def vr(tmp_path_factory):
-    return VR.load(tmp_path_factory.mktemp("visibility_ref"))
 
 
 def _both(oracle, vr, k, sc, v, vid, tri, rec, lst, slot=0, order=None):
@@ -34,8 +30,7 @@ def _both(oracle, vr, k, sc, v, vid, tri, rec, lst, slot=0, order=None):
 
 
 def test_depth_words_equal_the_oracle_on_the_cornell_fixture(oracle, vr):
-    from test_gltf_cornell import _fixture
-    _, s, camera = _fixture()
+    _, s, camera = cornell_fixture()
     inst = s.instances.copy()
     oracle.update_instance_consts(s.nodes, s.primToNode, inst)
     sc = dict(s.as_oracle()); sc["instances"] = inst

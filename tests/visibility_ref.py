@@ -2,30 +2,22 @@
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from ref_build import compile_ref
 from toyrenderer_amd import interop as I
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_LIB = {}
+
+def _declare(lib):
+    lib.vr_raster.argtypes = [C.c_void_p] * 9 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.vr_raster.restype = None
+    lib.vr_motion.argtypes = [C.c_void_p] * 11
+    lib.vr_motion.restype = None
 
 
 def load(tmpdir) -> C.CDLL:
-    out = os.path.join(str(tmpdir), "libvisibility_ref.so")
-    if out not in _LIB:
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", os.path.join(ROOT, "oracle"),
-                               os.path.join(HERE, "visibility_ref.c"), "-o", out, "-lm"])
-        lib = C.CDLL(out)
-        lib.vr_raster.argtypes = [C.c_void_p] * 9 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        lib.vr_raster.restype = None
-        lib.vr_motion.argtypes = [C.c_void_p] * 11
-        lib.vr_motion.restype = None
-        _LIB[out] = lib
-    return _LIB[out]
+    return compile_ref(tmpdir, "visibility_ref", _declare, include_oracle=True)
 
 
 def _p(a):

@@ -11,46 +11,26 @@ process, on one device:
            alpha_test=False beside "#textured" with alpha_test=True, hard and soft.  The rays of the two sides start from the
            depth their own rasters left (solid cards, cut-out cards), as they would in a frame.
 usage: python tools/alpha_test_cost.py [num_spheres] [width height] [--rounds=N]"""
-import os
-import sys
-import tempfile
-from pathlib import Path
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cost_common as cc
+
 VIS, TRACE = "basepass_MS_Main_visibility", "shadowmask_CS_ShadowMask"
 ALPHA = " ALPHA_MASK_MODE=1"
 
 
 def city(n, render):
-    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from scene_gen import write_city_gltf
-    from toyrenderer_amd import cached_scene, gltf_lite, rhi, synth
+    from toyrenderer_amd import cached_scene, rhi, synth
     from toyrenderer_amd import interop as I
     from toyrenderer_amd.frame import GpuScene
-    with tempfile.TemporaryDirectory() as d:
-        s = gltf_lite.load(write_city_gltf(Path(d), num_spheres=n, num_cutouts=n // 8))
-    inst = s.instances.copy()                       # world matrices on the host: the transform pass is timed elsewhere
-    for i in range(len(inst)):
-        k = int(s.primToNode[i])
-        M = np.eye(4, dtype=np.float64)
-        while k != 0xFFFFFFFF:
-            t = s.nodes[k]
-            L = np.diag(list(t["m_Scale"]) + [1.0]) @ synth.quat_to_matrix(tuple(t["m_Rotation"]))
-            L[3, :3] = t["m_Position"]
-            M = M @ L
-            k = int(t["m_ParentNodeIdx"])
-        inst["m_WorldMatrix"][i] = M.astype(np.float32)
-    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
+    s, inst = cc.load_city(n)
     rng = np.random.default_rng(7)
     ids = np.arange(len(inst), dtype=np.uint32)
     alpha = ids[ids % 10 == 3]                      # a tenth of the instances: alpha-masked and textured (materials 0..15)
     opaque = ids[ids % 10 != 3]
     inst["m_MaterialDataIdx"] = rng.integers(16, 64, len(inst), dtype=np.uint32)
     inst["m_MaterialDataIdx"][alpha] = rng.integers(0, 16, len(alpha), dtype=np.uint32)
-    v = s.vertices.copy()                           # the generated city has neither NORMAL nor TEXCOORD_0: seeded
-    v["m_PackedNormal"] = rng.integers(0, 1 << 30, len(v), dtype=np.uint64).astype(np.uint32)
+    v = cc.seeded_normals(s, rng)                   # the generated city has no TEXCOORD_0 either: seeded from the positions
     v["m_TexCoord"] = (v["m_Position"][:, [0, 2]] * np.float32(2.0) + v["m_Position"][:, [1, 1]]).astype(np.float16).view(np.uint16)
     textures = [(I.make_mips(rng.integers(0, 256, (256, 256, 4), dtype=np.uint16).astype(np.uint8), srgb=True), rhi.FORMAT_SRGBA8_UNORM) for _ in range(16)]
     mats = synth.materials(7)
@@ -69,20 +49,11 @@ def city(n, render):
         gs.set_materials(mats)
         scenes.append(gs)
     scenes[0].set_raytracing(c.indices, c.meshSpecific)
-    cam = s.cameras[0]
-    P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
-    V = synth.world_to_view((0.0, 0.0, 0.0), cam.orientation)
-    Vp = synth.world_to_view((-0.05, 0.0, 0.02), cam.orientation)
-    return dev, scenes, synth.View(V, Vp, P, float(np.float32(cam.znear)), *render), len(inst), len(alpha)
+    return dev, scenes, cc.city_view(s, render), len(inst), len(alpha)
 
 
-def timed(dev, drv, names, frames=20):
-    dev.profile_reset(); dev.profile_enable(True)
-    for _ in range(frames):
-        drv.run()
-    dev.wait_idle()
-    prof = dev.profile()
-    dev.profile_enable(False)
+def timed(dev, drv, names, frames=cc.FRAMES):
+    prof = cc.profile(dev, drv.run, frames)
     return [prof[k][1] / frames * 1e3 if k in prof else float("nan") for k in names]
 
 
@@ -100,17 +71,13 @@ def compare(dev, make, sides, rounds, rows):
             us[i].append(timed(dev, drv, names))
     for j, row in enumerate(rows):
         for i, (label, _, names) in enumerate(sides):
-            t = np.array([r[j] for r in us[i]])
-            print(f"    {row:6s} {label:6s} {names[j]:52s}: {' '.join(f'{x:.1f}' for x in t)} us; median {np.median(t):.1f}, spread {t.max() - t.min():.1f}")
+            print(f"    {row:6s} {label:6s} {names[j]:52s}: {cc.spread([r[j] for r in us[i]])}")
     return drivers
 
 
 def main():
-    opts = [a for a in sys.argv[1:] if a.startswith("--")]
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    n = int(args[0]) if args else 2000
-    render = (int(args[1]), int(args[2])) if len(args) > 2 else (3840, 2160)
-    rounds = int(next((a.split("=", 1)[1] for a in opts if a.startswith("--rounds=")), 3))
+    n, render, opt, _ = cc.parse_args()
+    rounds = int(opt("rounds", 3))
     dev, (whole, alone), view, ninst, nalpha = city(n, render)
     from toyrenderer_amd.frame import FrameDriver
     print(f"{ninst} instances, {nalpha} of them alpha-masked and textured, render {render[0]}x{render[1]}, {rounds} rounds of 20 frames, sides alternated")

@@ -7,70 +7,32 @@ would take at the box's stream rate (tools/membw, given with --membw=GB/s) and n
 builds alternate `rounds` times (default 3) in one call, so that the differences are taken on one box in one state.
 usage: python tools/lighting_cost.py [num_spheres] [width height] [--rounds=N] [--membw=GBps] [--variant=NAME=PATH ...] [--debug-mode=M]
        python tools/lighting_cost.py --child [--dump=FILE.npy] ...   one run in this process (TRHIP_LIB picks the build); --dump saves LightingOutput"""
-import os
 import re
-import subprocess
-import sys
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cost_common as cc
+
+LIGHTING_US = r"deferredlighting_PS_Main\w*#main\s+([0-9.]+) us"
 
 
 def run(n: int, render, debug_mode: int, dump=None):
-    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from scene_gen import write_city_gltf
-    from toyrenderer_amd import gltf_lite, rhi, synth
-    from toyrenderer_amd.frame import FrameDriver, GpuScene
-    with tempfile.TemporaryDirectory() as d:
-        s = gltf_lite.load(write_city_gltf(Path(d), num_spheres=n, num_cutouts=n // 8))
-    inst = s.instances.copy()                       # world matrices on the host: the transform pass is timed elsewhere
-    for i in range(len(inst)):
-        k = int(s.primToNode[i])
-        M = np.eye(4, dtype=np.float64)
-        while k != 0xFFFFFFFF:
-            t = s.nodes[k]
-            L = np.diag(list(t["m_Scale"]) + [1.0]) @ synth.quat_to_matrix(tuple(t["m_Rotation"]))
-            L[3, :3] = t["m_Position"]
-            M = M @ L
-            k = int(t["m_ParentNodeIdx"])
-        inst["m_WorldMatrix"][i] = M.astype(np.float32)
-    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
-    rng = np.random.default_rng(7)
-    inst["m_MaterialDataIdx"] = rng.integers(0, 64, len(inst), dtype=np.uint32)
-    v = s.vertices.copy()                           # the generated city has no NORMAL attribute: seeded packed normals
-    v["m_PackedNormal"] = rng.integers(0, 1 << 30, len(v), dtype=np.uint64).astype(np.uint32)
-    dev = rhi.Device(0)
-    gs = GpuScene(dev, inst, s.meshData, s.meshlets, s.opaqueIds, s.alphaMaskIds)
-    gs.set_geometry(v, s.meshletVertexIds, s.meshletTriangles)
-    gs.set_materials(synth.materials(7))
-    cam = s.cameras[0]
-    P = synth.perspective_rh_reverse_z_infinite(cam.yfov, render[0] / render[1], cam.znear)
-    V = synth.world_to_view((0.0, 0.0, 0.0), cam.orientation)
-    Vp = synth.world_to_view((-0.05, 0.0, 0.02), cam.orientation)
-    view = synth.View(V, Vp, P, float(np.float32(cam.znear)), *render)
+    from toyrenderer_amd import rhi
+    from toyrenderer_amd.frame import FrameDriver
+    c = cc.city(n, render)
+    dev, gs = c.dev, c.gs
     shadow = dev.create_texture(render[0], render[1], 1, rhi.FORMAT_R8_UNORM, "ShadowMask")
-    shadow.upload_mip(0, rng.integers(0, 256, (render[1], render[0]), dtype=np.uint64).astype(np.uint8))
-    drv = FrameDriver(dev, gs, view, record_capacity=1 << 16, culling_flags=7, lighting=True, debug_mode=debug_mode,
+    shadow.upload_mip(0, c.rng.integers(0, 256, (render[1], render[0]), dtype=np.uint64).astype(np.uint8))
+    drv = FrameDriver(dev, gs, c.view, record_capacity=1 << 16, culling_flags=7, lighting=True, debug_mode=debug_mode,
                       dir_light=((0.3, -0.8, 0.52), 3.0), camera_origin=(0.0, 0.0, 0.0), shadow_mask=shadow)
     drv.record()
-    for _ in range(5):
-        drv.run()
-    dev.wait_idle()
-    dev.profile_reset(); dev.profile_enable(True)
-    frames = 20
-    for _ in range(frames):
-        drv.run()
-    dev.wait_idle()
-    prof = dev.profile()
-    dev.profile_enable(False)
+    frames = cc.FRAMES
+    prof = cc.steady_profile(dev, drv.run)
     lit = int(np.count_nonzero(drv.depth.download_mip(0) > 0))
     words = drv.lighting_output.download_mip(0)
     if dump:
         np.save(dump, words)
-    print(f"{len(inst)} instances, render {render[0]}x{render[1]}, {frames} frames, {lit} lit pixels of {render[0] * render[1]}, "
+    print(f"{len(c.inst)} instances, render {render[0]}x{render[1]}, {frames} frames, {lit} lit pixels of {render[0] * render[1]}, "
           f"output checksum {int(words.astype(np.uint64).sum()):#x}")
     for name, (cnt, ms) in sorted(prof.items()):
         if name.startswith("deferredlighting_PS_Main") or name.startswith("basepass_PS_Main"):
@@ -79,39 +41,18 @@ def run(n: int, render, debug_mode: int, dump=None):
 
 
 if __name__ == "__main__":
-    opts = [a for a in sys.argv[1:] if a.startswith("--")]
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    n = int(args[0]) if args else 2000
-    render = (int(args[1]), int(args[2])) if len(args) > 2 else (3840, 2160)
-    opt = lambda key, default=None: next((a.split("=", 1)[1] for a in opts if a.startswith(f"--{key}=")), default)   # noqa: E731
+    n, render, opt, opts = cc.parse_args()
     debug_mode = int(opt("debug-mode", 0))
     if "--child" in opts:
         run(n, render, debug_mode, opt("dump"))
     else:
         rounds = int(opt("rounds", 3))
         membw = float(opt("membw", 0)) or None
-        builds = [("product", None)] + [tuple(a.split("=", 2)[1:]) for a in opts if a.startswith("--variant=")]
-        times = {name: [] for name, _ in builds}
-        lit = 0
-        for r in range(rounds):
-            for name, path in builds:
-                env = dict(os.environ)
-                if path:
-                    env["TRHIP_LIB"] = os.path.abspath(path)
-                else:
-                    env.pop("TRHIP_LIB", None)
-                out = subprocess.check_output([sys.executable, os.path.abspath(__file__), "--child", f"--debug-mode={debug_mode}", str(n), str(render[0]), str(render[1])],
-                                              env=env).decode()
-                sys.stdout.write(f"[{name}] " + out); sys.stdout.flush()
-                times[name].append(float(re.search(r"deferredlighting_PS_Main\w*#main\s+([0-9.]+) us", out).group(1)))
-                lit = int(re.search(r"(\d+) lit pixels", out).group(1))
+        builds = cc.variants(opts)
+        outs = cc.alternate(__file__, builds, rounds, [f"--debug-mode={debug_mode}", n, *render])
         for name, _ in builds:
-            t = np.array(times[name])
-            print(f"{name:10s}: {' '.join(f'{x:.1f}' for x in t)} us; median {np.median(t):.1f}, spread {t.max() - t.min():.1f}")
+            print(f"{name:10s}: {cc.spread(cc.figures(outs[name], LIGHTING_US))}")
+        lit = int(re.search(r"(\d+) lit pixels", outs[builds[-1][0]][-1]).group(1))
         nbytes = 4 * render[0] * render[1] + lit * (16 + 1 + 4)          # depth for every pixel; GBufferA, the shadow byte and the store for a lit one
         line = f"bytes moved: {nbytes / 1e6:.1f} MB ({lit} lit pixels x 21 B + {render[0] * render[1]} x 4 B of depth)"
-        if membw:
-            line += f": {nbytes / membw / 1e3:.1f} us at the box's {membw:.0f} GB/s"
-        else:
-            line += "; stream rate not given (--membw), bound not computed"
-        print(line)
+        print(line + cc.stream_bound(nbytes, membw, ": ", "; stream rate not given (--membw), bound not computed"))
