@@ -66,18 +66,20 @@ static const MtTexture* table_entry(const MtTexture* textures, int64_t numTextur
 }
 
 /* ---- the raster of one pass slot ---------------------------------------------------------------------------------------------
- * alphaTest = 0: vr_raster.  counts (optional, uint64[4]): the covered samples (d > 0) of the slot's triangles that were kept and
+ * alphaTest = 0: vr_raster.  order: NULL, or numVisible positions of `list` to draw (the payload carries the position, so disjoint
+ * slices of a list drawn into images of their own and max-merged give the image of the whole list).  counts (optional, uint64[4]): the covered samples (d > 0) of the slot's triangles that were kept and
  * discarded, {kept, discarded} of the triangles whose bounding box has at most 1024 pixels (drawn in place by the kernel's main
  * launch) and {kept, discarded} of the larger ones (queue, bin and tile launch). */
 void at_raster(const OrcBasePassConstants* k, const OrcBasePassInstanceConstants* instances, const OrcMeshData* meshData,
                const OrcMeshletData* meshlets, const OrcRawVertexFormat* vertices, const uint32_t* vertexIds, const uint32_t* triangles,
-               const OrcMeshletAmplificationData* records, const uint32_t* list, uint32_t numVisible, uint32_t slot,
+               const OrcMeshletAmplificationData* records, const uint32_t* list, uint32_t numVisible, const uint32_t* order, uint32_t slot,
                const unsigned char* materials, uint32_t numMaterials, const MtTexture* textures, int64_t numTextures, int alphaTest,
                float* depth, uint64_t* vis, uint64_t* counts)
 {
     const uint32_t W = k->m_OutputResolution[0], H = k->m_OutputResolution[1];
     const float halfW = 0.5f * (float)W, halfH = 0.5f * (float)H;
-    for (uint32_t v = 0; v < numVisible; ++v) {
+    for (uint32_t n = 0; n < numVisible; ++n) {
+        const uint32_t v = order ? order[n] : n;
         const OrcMeshletAmplificationData* rec = &records[list[v] >> 5];
         const OrcBasePassInstanceConstants* inst = &instances[rec->m_InstanceConstIdx];
         const uint32_t lodIdx = rec->m_MeshLOD < ORC_MAX_LODS ? rec->m_MeshLOD : ORC_MAX_LODS - 1;

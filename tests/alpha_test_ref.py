@@ -23,7 +23,7 @@ def _declare(lib):
     lib.at_sample_alpha.restype = C.c_float
     lib.at_alpha_level0.argtypes = [vp, C.c_int, C.c_float, C.c_float]
     lib.at_alpha_level0.restype = C.c_float
-    lib.at_raster.argtypes = [vp] * 9 + [u32, u32, vp, u32, vp, i64, C.c_int, vp, vp, vp]
+    lib.at_raster.argtypes = [vp] * 9 + [u32, vp, u32, vp, u32, vp, i64, C.c_int, vp, vp, vp]
     lib.at_raster.restype = None
     lib.at_trace.argtypes = [vp, C.POINTER(SR._Scene), vp, i64, vp, vp, vp, vp, vp]
     lib.at_trace.restype = None
@@ -56,18 +56,20 @@ def alpha_level0(lib, tex: MT.Texture, wrap, u, v) -> np.float32:
     return F(lib.at_alpha_level0(C.addressof(tex.c), int(bool(wrap)), C.c_float(float(u)), C.c_float(float(v))))
 
 
-def raster(lib, consts, geo, records, visible_list, slot, depth, vis, materials, textures, alpha_test=True):
+def raster(lib, consts, geo, records, visible_list, slot, depth, vis, materials, textures, alpha_test=True, order=None):
     """Max-merges one slot's listed meshlets into depth (float32 [H, W]) and vis (uint64 [H, W]), in place, with the discard when
-    alpha_test.  textures: the table (a list of (mips, format), Texture or None), or None = no table bound.  Returns the counts
-    {main kept, main discarded, tiles kept, tiles discarded} (zeros without alpha_test)."""
+    alpha_test.  textures: the table (a list of (mips, format), Texture or None), or None = no table bound.  order: the list
+    positions to draw (default: all); the payload carries the position, so slices merge.  Returns the counts {main kept, main
+    discarded, tiles kept, tiles discarded} (zeros without alpha_test)."""
     k = np.ascontiguousarray(consts)
     rec = np.ascontiguousarray(records)
     lst = np.ascontiguousarray(visible_list, np.uint32)
     mats = np.ascontiguousarray(materials, I.MaterialData)
     assert depth.dtype == np.float32 and vis.dtype == np.uint64 and depth.flags.c_contiguous and vis.flags.c_contiguous
     table, keep = table_of(textures if textures is not None else [])
+    order = None if order is None else np.ascontiguousarray(order, np.uint32)
     counts = np.zeros(4, np.uint64)
-    lib.at_raster(_p(k), *geo.args(), _p(rec), _p(lst), len(lst), int(slot), _p(mats), len(mats), C.addressof(table) if textures is not None else None,
+    lib.at_raster(_p(k), *geo.args(), _p(rec), _p(lst), len(lst) if order is None else len(order), _p(order), int(slot), _p(mats), len(mats), C.addressof(table) if textures is not None else None,
                   len(textures) if textures is not None else -1, int(bool(alpha_test)), _p(depth), _p(vis), _p(counts))
     del keep
     return counts

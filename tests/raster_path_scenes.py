@@ -1,5 +1,6 @@
 """Scenes that put the compute rasteriser (csrc/k_raster.hip) on both sides of each of its path switches, with the
-counts the kernel's own rules predict for them (tests/test_raster_path_scenes.py, tests/test_gpu_raster_paths.py).
+counts the kernel's own rules predict for them (tests/test_raster_path_scenes.py, tests/test_gpu_raster_paths.py), and, in the
+file's second half, their variants for the alpha-tested instantiations (tests/test_gpu_alpha_raster_paths.py).
 
 Every scene is authored in pixel space: m_WorldToClip is the identity (w = 1, depth = object-space z), m_NearPlane is 0.5
 and a vertex at pixel position (px, py) is stored as x = px / halfW - 1, y = 1 - py / halfH.  With a power-of-two render
@@ -339,24 +340,24 @@ def early_out_scene(kind):
 
 
 # ---- references ------------------------------------------------------------------------------------------------------
-def reference(oracle, vr, s, threads=1, texels=True):
+def reference(oracle, vr, s, threads=1, texels=True, positions=None):
     """(depth from orc_raster_depth, texels from tests/visibility_ref.c or None).  threads > 1: disjoint slices of the list
     into arrays of their own, from one thread each, max-merged -- exactly the references' semantics, because both
-    results are maxima."""
+    results are maxima.  positions: the list positions to draw (default: all of them)."""
     import visibility_ref as VR
     from concurrent.futures import ThreadPoolExecutor
     W, H = s.render
     geo = VR.Geometry(s.sc, s.v, s.vid, s.tri)
     lst = np.ascontiguousarray(s.lst, np.uint32)
-    bounds = np.linspace(0, len(lst), threads + 1).astype(np.int64)
+    positions = np.arange(len(lst), dtype=np.uint32) if positions is None else np.ascontiguousarray(positions, np.uint32)
+    bounds = np.linspace(0, len(positions), threads + 1).astype(np.int64)
 
     def one(i):
-        lo, hi = int(bounds[i]), int(bounds[i + 1])
+        order = np.ascontiguousarray(positions[int(bounds[i]):int(bounds[i + 1])])   # list positions: the payload carries them
         depth = np.zeros((H, W), np.float32)
-        oracle.raster_depth(s.k, s.sc, s.v, s.vid, s.tri, s.rec, lst[lo:hi], depth)
+        oracle.raster_depth(s.k, s.sc, s.v, s.vid, s.tri, s.rec, lst[order], depth)
         vis = None
         if texels:
-            order = np.arange(lo, hi, dtype=np.uint32)                    # list positions: the payload carries them
             vdepth, vis = np.zeros((H, W), np.float32), np.zeros((H, W), np.uint64)
             vr.vr_raster(s.k.ctypes.data, *geo.args(), s.rec.ctypes.data, lst.ctypes.data, len(order), order.ctypes.data, SLOT,
                          vdepth.ctypes.data, vis.ctypes.data)
@@ -374,3 +375,303 @@ def reference(oracle, vr, s, threads=1, texels=True):
         if texels:
             np.maximum(vis, t, out=vis)
     return depth, vis
+
+
+# ---- the alpha-tested rasters: the same geometry with texture coordinates, materials and a table ---------------------------
+# (tests/test_raster_path_scenes.py proves what these scenes claim, tests/test_gpu_alpha_raster_paths.py uses them.)
+# An alpha scene is a built scene with m_TexCoord filled in, m_MaterialDataIdx per instance, .materials (MaterialData rows)
+# and .textures: the table, a list of (mips, format), None (an empty entry) or OTHER_FORMAT; .textures = None: no table bound.
+# The scenes have w = 1, so uv is affine in the pixel position: with uv = (offset from the apex) / 16 a pixel is half a texel
+# of the 8 x 8 checker (cells of 4 x 4 pixels, lod 0); with uv = offset / 4 a pixel is two texels (one cell a pixel, lod 1,
+# where the checker is still a checker).
+OTHER_FORMAT = "a texture of a format the sampler does not take"
+OWNER_UV, SLIVER_UV = 1.0 / 16.0, 1.0 / 4.0
+SLIVER_LEGS = (520.0, 0.5 + 2.0 ** -9)               # box 521 x 2 = 1042 pixels > kSmallBox; the centres at +0.5 and +1.5 are covered
+
+
+def _scenes():
+    import alpha_test_scenes as A
+    import material_texture_scenes as MS
+    return A, MS
+
+
+def set_alpha(s, uv, materials, textures, material_of_instance, exact=True):
+    """Completes a built scene: uv [n_triangles, 3, 2] per vertex (exact halves unless exact=False)."""
+    uv = np.asarray(uv, np.float64).reshape(-1, 2)
+    h = uv.astype(np.float16)
+    assert len(h) == len(s.v) and (not exact or np.array_equal(h.astype(np.float64), uv)), "a texture coordinate is not a half"
+    s.v["m_TexCoord"] = h.view(np.uint16)
+    s.sc["instances"]["m_MaterialDataIdx"] = np.broadcast_to(np.asarray(material_of_instance, np.uint32), (len(s.sc["instances"]),))
+    s.materials, s.textures = materials, textures
+    return s
+
+
+def apex_uv(tris, scale):
+    """[n, 3, 2]: (pixel offset from the triangle's first vertex) * scale."""
+    t = np.asarray(tris, np.float64)
+    return (t[:, :, :2] - t[:, :1, :2]) * scale
+
+
+# Where owner triangles lie a pixel apart (the round cases), an interior triangle owns its apex texel alone, and with uv = offset / 16
+# every apex sample is kept: only the triangles on the block's rim would show their discard, and every triangle would carry the
+# same AlphaTriangle, so that one drawn with another's would show nothing.  In these scenes the triangles of the even rows shift
+# the checker by (7, 1.5) pixels: their apex sample (0.5, 0.5) then lies a quarter texel inside a cell below the cutoff (alpha
+# 80 / 255) and the sample right of it (1.5, 0.5) a quarter texel inside the next cell (180 / 255).  A triangle of an even row
+# loses its apex texel to its left neighbour, which keeps it (a witness: a forgotten discard hides that neighbour); a triangle
+# of an odd row keeps and owns its apex.  Drawn with the texture coordinates of the other kind, either changes the image.
+ROUND_PHASE = (7.0 / 16.0, 1.5 / 16.0)
+
+
+def _row_phase(tris):
+    """[n, 1, 2]: ROUND_PHASE for the triangles whose apex lies in an even pixel row, 0 for the others."""
+    even = np.asarray(tris, np.float64)[:, 0, 1] % 2 == 0
+    return np.where(even[:, None, None], np.asarray(ROUND_PHASE)[None, None], 0.0)
+
+
+def textured(s, tris, scale=OWNER_UV, exact=True, phase=(0.0, 0.0)):
+    """Every instance draws with the 8 x 8 checker under the wrap sampler (alpha_test_scenes.M_CHECKER, cutoff 0.5)."""
+    A, _ = _scenes()
+    return set_alpha(s, apex_uv(tris, scale) + np.asarray(phase), A.materials(), A.textures(), A.M_CHECKER, exact)
+
+
+def sliver_tris(apex):
+    """Owner slivers whose depth FALLS with X: z = 0.25 + (Y - X) * 2^-14.  Triangle (X, Y) covers the centres of the pixels
+    (X, Y) and (X + 1, Y); under the checker at SLIVER_UV the first is kept and the second discarded.  Without the discard
+    triangle X would win pixel X + 1 and hide triangle X + 1; with it every triangle owns its apex."""
+    apex = np.asarray(apex, np.float64).reshape(-1, 2)
+    return owner_tris(apex, SLIVER_LEGS, z=0.25 + (apex[:, 1] - apex[:, 0]) * 2.0 ** -14)
+
+
+M_ABOVE, M_BELOW, M_BROKEN = 0, 1, 2                 # constant_alpha()'s cycle
+
+
+def constant_alpha(s):
+    """Instances cycle through a texture-free material above the cutoff, one below it and a broken chain (the albedo flag with
+    a descriptor past the table).  .kept_positions: the list positions of the instances the convention keeps."""
+    A, MS = _scenes()
+    m = np.concatenate([MS.material(albedo=(0.2, 0.9, 0.2, 0.75)), MS.material(albedo=(0.9, 0.2, 0.2, 0.25)),
+                        MS.material(flags=MS.ALBEDO, indices=(9, MS.NONE, MS.NONE, MS.NONE))])
+    m["m_AlphaCutoff"] = A.CUTOFF
+    n_inst = len(s.sc["instances"])
+    set_alpha(s, np.zeros((len(s.v) // 3, 3, 2)), m, A.textures(), np.arange(n_inst) % 3)
+    per = len(s.lst) // n_inst
+    s.kept_positions = np.flatnonzero((np.arange(len(s.lst)) // per) % 3 == M_ABOVE).astype(np.uint32)
+    return s
+
+
+def small_box_alpha(kind):
+    s = small_box_scene(kind)
+    bw, bh = {"box1024": (32, 32), "box1025": (41, 25), "box33x32": (33, 32), "edge_clamped": (33, 32)}[kind]
+    uv = np.zeros((s.n_triangles, 3, 2)); uv[:, 1, 0] = (bw - 1) * OWNER_UV; uv[:, 2, 1] = (bh - 1) * OWNER_UV
+    A, _ = _scenes()
+    return set_alpha(s, uv, A.materials(), A.textures(), A.M_CHECKER)
+
+
+def tile_round_alpha(count):
+    t = owner_tris(_pixels_of(64, 64, count))
+    return textured(build((512, 512), t), t, phase=_row_phase(t))
+
+
+def sparse_tile_alpha(matching=1000):
+    a, b = _pixels_of(0, 0, matching), _pixels_of(128, 0, 2 * matching)
+    apex = np.zeros((3 * matching, 2))
+    apex[0::3], apex[1::3], apex[2::3] = a, b[0::2], b[1::2]                 # sparse_tile_scene()'s corners
+    t = owner_tris(apex)
+    return textured(build((512, 512), t), t, phase=_row_phase(t))
+
+
+def _sliver_bin_tris(extra):
+    side = 1 << K["kBinShift"]
+    assert side * side == K["kBinCapacity"]
+    t = sliver_tris(_pixels_of(0, 0, side * side, side))
+    if extra:
+        # one more entry of bin (0, 0): its box begins in the bin's last column, its covered centres are in the next bin;
+        # nearer than everything there
+        e = owner_tris([(side - 0.25, 10.0)], SLIVER_LEGS, z=np.array([0.25 + 2000 * 2.0 ** -14]))
+        t = np.concatenate([t, e])
+    return t
+
+
+def sliver_bin_alpha(extra=False, per_meshlet=15):
+    """1024 x 512 (wide and high enough that no box is clamped back to kSmallBox): one sliver per pixel of bin (0, 0)."""
+    t = _sliver_bin_tris(extra)
+    s = textured(build((1024, 512), t, per_meshlet=per_meshlet), t, SLIVER_UV)
+    s.tris_px, s.cells = t, [(0, 0)]
+    return s
+
+
+def sliver_queue_alpha(per_meshlet=21):
+    """4096 x 1024: the full bin of slivers under enough instances, a bin apart, to queue kQueueCapacity + 4096 triangles;
+    no sliver reaches the last column or row."""
+    W, H = 4096, 1024
+    side = 1 << K["kBinShift"]
+    need = -(-(K["kQueueCapacity"] + 4096) // K["kBinCapacity"])
+    # every other bin column: the second sample of a row's last sliver is contested by no other instance, so its discard shows too
+    cells = [(bx * side, by * side) for by in range(H // side - 1) for bx in range(0, (W - 521) // side, 2)]
+    assert need <= len(cells)
+    t = _sliver_bin_tris(False)
+    s = textured(build((W, H), t, per_meshlet=per_meshlet, instances=cells[:need]), t, SLIVER_UV)
+    s.tris_px, s.cells = t, cells[:need]
+    return s
+
+
+def queue_constant_alpha(per_meshlet=21):
+    return constant_alpha(queue_scene(per_meshlet))
+
+
+def stride_alpha(compute_units):
+    s = stride_scene(compute_units)
+    first = s.v["m_Position"].astype(np.float64).reshape(-1, 3, 3)
+    W, H = s.render
+    px = np.stack([(first[..., 0] + 1.0) * 0.5 * W, (1.0 - first[..., 1]) * 0.5 * H], 2)
+    A, _ = _scenes()
+    return set_alpha(s, (px - px[:, :1]) * OWNER_UV, A.materials(), A.textures(), A.M_CHECKER, exact=False)
+
+
+def merge(a, b):
+    """The scene that draws a's list and then b's: two meshes, b's instances, records and list positions after a's.  The
+    predictions add up; .part: 0 / 1 per listed triangle."""
+    assert a.render == b.render
+    nv, nt, nm, ni, nr, nl = len(a.v), len(a.tri), len(a.sc["meshlets"]), len(a.sc["instances"]), len(a.rec), len(a.lst)
+    mlb = b.sc["meshlets"].copy()
+    mlb["m_MeshletVertexIDsBufferIdx"] += len(a.vid); mlb["m_MeshletIndexIDsBufferIdx"] += nt
+    mdb = b.sc["meshData"].copy()
+    mdb["m_MeshLODDatas"]["m_MeshletDataBufferIdx"][0][0] = nm
+    ib = b.sc["instances"].copy(); ib["m_MeshDataIdx"] = 1
+    rb = b.rec.copy(); rb["m_InstanceConstIdx"] += ni
+    sc = dict(instances=np.concatenate([a.sc["instances"], ib]), meshData=np.concatenate([a.sc["meshData"], mdb]),
+              meshlets=np.concatenate([a.sc["meshlets"], mlb]))
+    shift = np.uint64(nl) << np.uint64(7)
+    return SimpleNamespace(render=a.render, k=a.k, sc=sc, v=np.concatenate([a.v, b.v]), vid=np.concatenate([a.vid, b.vid + np.uint32(nv)]),
+                           tri=np.concatenate([a.tri, b.tri]), rec=np.concatenate([a.rec, rb]),
+                           lst=np.concatenate([a.lst, (b.lst + np.uint32(nr << 5)).astype(np.uint32)]),
+                           payloads=np.concatenate([a.payloads, b.payloads + shift]), n_triangles=a.n_triangles + b.n_triangles,
+                           live=np.concatenate([a.live, b.live]), box_pixels=np.concatenate([a.box_pixels, b.box_pixels]),
+                           queued=np.concatenate([a.queued, b.queued]), queue_length=a.queue_length + b.queue_length,
+                           bin_counts=a.bin_counts + b.bin_counts, tile_candidates=a.tile_candidates + b.tile_candidates, tiles=a.tiles,
+                           part=np.concatenate([np.zeros(a.n_triangles, np.int64), np.ones(b.n_triangles, np.int64)]),
+                           positions=(np.arange(nl, dtype=np.uint32), np.arange(nl, nl + len(b.lst), dtype=np.uint32)))
+
+
+EARLY_OUT_COVERS = ("checker", "opaque", "below")
+
+
+def early_out_alpha(cover, tiles=8, slivers=23, cover_instances=4):
+    """512x512, one case per 64x64 tile as in early_out_scene("normal"): the cover 0, 2 .. 14 float32 steps above the first sliver's
+    constant depth 0.3 (both sides of the factor, which is about 10 steps there).  The covers (8 quads a tile) are an instance of
+    their own, listed first and drawn `cover_instances` times; the 23 slivers of a tile lie at 23 different places, are texture-free
+    and kept, and sliver j lies j * 2^-10 behind the first: whatever order the queue has, a tile's farthest sliver mostly comes after
+    32 nearer entries, and a far depth that took the covers' holes for covered would be nearer than it.
+    cover: "checker" (uv = offset from the tile's corner / 16: a tile with holes has far depth 0), "opaque" (the same with every
+    alpha byte 255) or "below" (constant alpha below the cutoff)."""
+    A, MS = _scenes()
+    z = np.float32(0.3)
+    cases = [(step(z, 2 * i), (z, z, z)) for i in range(tiles)]
+    t, flags = [], []
+    for i, (cv, d) in enumerate(cases):
+        tt, ff = _tile_content(64 * (i % 8), 64 * (i // 8), cv, d, n_slivers=slivers, n_quads=8)
+        t += tt; flags += ff
+    t, flags = np.array(t, np.float64), np.array(flags)
+    c, sl = t[flags], t[~flags]
+    sl[:, :, 2] -= (np.arange(len(sl)) % slivers)[:, None] * 2.0 ** -10
+    s = merge(build((512, 512), c, instances=((0, 0),) * cover_instances), build((512, 512), sl))
+    corner = np.floor(c[:, :, :2].min(1) / 64.0) * 64.0
+    uv = np.concatenate([(c[:, :, :2] - corner[:, None]) * OWNER_UV, np.zeros((len(sl), 3, 2))])
+    tex = A.textures() if cover != "opaque" else A.with_uniform_alpha(A.textures(), 255)
+    set_alpha(s, uv, A.materials(), tex, [A.M_CONST_BELOW if cover == "below" else A.M_CHECKER] * cover_instances + [A.M_CONST_ABOVE])
+    s.cases, s.n_tiles, s.slivers_per_tile, s.n_cover_triangles = cases, tiles, slivers, cover_instances * len(c)
+    return s
+
+
+# (g) rules 5 and 6: one instance per material; (name, kept)
+RULE_CASES = [("checker", True), ("index past the buffer", False), ("descriptor past the table", False), ("empty entry", False),
+              ("another format", False), ("NaN alpha", True), ("NaN alpha, textured", True), ("NaN cutoff", True),
+              ("NaN cutoff, textured", True), ("cutoff +inf", False), ("cutoff +inf, textured", False), ("alpha == cutoff", True),
+              ("cutoff the next float", False), ("texel == cutoff", True), ("texel below the next cutoff", False)]
+RULE_TIE = np.float32(128) / np.float32(255)
+
+
+def rules_alpha(path, table=True):
+    """512 x 512: five owner triangles (legs 31 x 31 = a 1024-pixel box for path "main", 32 x 31 for "tiles"; one of them across
+    a tile corner) under one instance per case of RULE_CASES, 80 and 100 pixels apart: no two instances share a pixel.
+    table=False: no table is bound, and every material with the albedo flag draws nothing (.kept says which remain)."""
+    A, MS = _scenes()
+    legs = {"main": (31, 31), "tiles": (32, 31)}[path]
+    t = owner_tris([(10, 10), (11, 10), (10, 11), (13, 12), (40, 50)], legs)
+    cells = [(80 * (i % 6), 100 * (i // 6)) for i in range(len(RULE_CASES))]
+    s = build((512, 512), t, instances=cells)
+    nan, inf, nxt = np.float32(np.nan), np.float32(np.inf), np.nextafter(np.float32(0.5), np.float32(1))
+    ck = dict(flags=MS.ALBEDO, indices=(A.CHECKER, MS.NONE, MS.NONE, MS.NONE))
+    un = dict(flags=MS.ALBEDO, indices=(A.UNIFORM, MS.NONE, MS.NONE, MS.NONE))
+    rows = [(MS.material(albedo=(1, 1, 1, 1.0), **ck), 0.5),
+            (MS.material(flags=MS.ALBEDO, indices=(9, MS.NONE, MS.NONE, MS.NONE)), 0.5),
+            (MS.material(flags=MS.ALBEDO, indices=(3, MS.NONE, MS.NONE, MS.NONE)), 0.5),
+            (MS.material(flags=MS.ALBEDO, indices=(4, MS.NONE, MS.NONE, MS.NONE)), 0.5),
+            (MS.material(albedo=(1, 1, 1, nan)), 0.5), (MS.material(albedo=(1, 1, 1, nan), **ck), 0.5),
+            (MS.material(albedo=(1, 1, 1, 0.25)), nan), (MS.material(albedo=(1, 1, 1, 1.0), **ck), nan),
+            (MS.material(albedo=(1, 1, 1, 1.0)), inf), (MS.material(albedo=(1, 1, 1, 1.0), **ck), inf),
+            (MS.material(albedo=(1, 1, 1, 0.5)), 0.5), (MS.material(albedo=(1, 1, 1, 0.5)), nxt),
+            (MS.material(albedo=(1, 1, 1, 1.0), **un), RULE_TIE), (MS.material(albedo=(1, 1, 1, 1.0), **un), np.nextafter(RULE_TIE, np.float32(1)))]
+    mats = np.concatenate([m for m, _ in rows])
+    mats["m_AlphaCutoff"] = np.array([c for _, c in rows], np.float32)
+    index = [0, len(mats) + 5] + list(range(1, len(mats)))           # case 1 names a row past the buffer
+    tex = A.textures(uniform=128) + [None, OTHER_FORMAT]              # descriptors 3 (empty) and 4 (another format) of a table of 5
+    set_alpha(s, apex_uv(t, OWNER_UV), mats, tex if table else None, index)
+    flagged = [bool(mats["m_MaterialFlags"][i] & MS.ALBEDO) if i < len(mats) else False for i in index]
+    s.kept = [k and (table or not f) for (_, k), f in zip(RULE_CASES, flagged)]
+    return s
+
+
+def ref_textures(textures):
+    """The table as tests/alpha_test_ref.py takes it: OTHER_FORMAT becomes an entry whose format is neither RGBA8 nor sRGBA8."""
+    import material_textures_ref as MT
+    if textures is None:
+        return None
+    return [MT.Texture([np.zeros((4, 4, 4), np.uint8)], 1) if t is OTHER_FORMAT else t for t in textures]
+
+
+def alpha_reference(at, s, threads=1, alpha_test=True, positions=None):
+    """(depth, texels, counts) of tests/alpha_test_ref.c's at_raster: disjoint slices of the list (or of `positions`) into arrays
+    of their own, from one thread each, max-merged, the four counts summed."""
+    import alpha_test_ref as AT
+    import visibility_ref as VR
+    from concurrent.futures import ThreadPoolExecutor
+    W, H = s.render
+    geo = VR.Geometry(s.sc, s.v, s.vid, s.tri)
+    tex = ref_textures(s.textures)
+    positions = np.arange(len(s.lst), dtype=np.uint32) if positions is None else np.ascontiguousarray(positions, np.uint32)
+    bounds = np.linspace(0, len(positions), threads + 1).astype(np.int64)
+
+    def one(i):
+        depth, vis = np.zeros((H, W), np.float32), np.zeros((H, W), np.uint64)
+        counts = AT.raster(at, s.k, geo, s.rec, s.lst, SLOT, depth, vis, s.materials, tex, alpha_test, order=positions[int(bounds[i]):int(bounds[i + 1])])
+        return depth, vis, counts
+
+    if threads == 1:
+        return one(0)
+    with ThreadPoolExecutor(threads) as pool:
+        parts = list(pool.map(one, range(threads)))
+    depth, vis, counts = parts[0]
+    for d, t, c in parts[1:]:
+        np.maximum(depth, d, out=depth); np.maximum(vis, t, out=vis)
+        counts = counts + c
+    return depth, vis, counts
+
+
+# name -> (maker(compute_units), the launch whose counts the reference must show, flavour, reference threads): the owner scenes
+# of tests/test_gpu_alpha_raster_paths.py, whose preconditions tests/test_raster_path_scenes.py proves
+ALPHA_OWNER_SCENES = dict(
+    [(f"a-{kind}", (lambda cu, kind=kind: small_box_alpha(kind), "main" if kind in ("box1024", "edge_clamped") else "tiles", "textured", 1))
+     for kind in ("box1024", "box1025", "box33x32", "edge_clamped")]
+    + [(f"b-{n}", (lambda cu, n=n: tile_round_alpha(n), "tiles", "textured", 16))
+       for n in (K["kTileList"] - K["kBlock"], K["kTileList"], K["kTileList"] + 1, 2 * K["kTileList"] + 1)]
+    + [("b-sparse", (lambda cu: sparse_tile_alpha(), "tiles", "textured", 16)),
+       ("c-full", (lambda cu: sliver_bin_alpha(False), "tiles", "sliver", 16)), ("c-over", (lambda cu: sliver_bin_alpha(True), "tiles", "sliver", 16)),
+       ("d-slivers", (lambda cu: sliver_queue_alpha(), "tiles", "sliver", 16)),
+       ("e-stride", (lambda cu: stride_alpha(cu), "tiles", "textured", 4))])
+
+
+def triangle_of(s, payloads):
+    """The index into s.payloads (instance-major, then triangle) of each payload."""
+    order = np.argsort(s.payloads)
+    return order[np.searchsorted(s.payloads[order], payloads)]

@@ -92,6 +92,61 @@ def kernel_constant(source_file, name):
     return int(re.search(r"\b" + name + r" = (\d+)", src).group(1))
 
 
+def raster_dispatch(dev, s, texels, alpha=False, table=True, slot=1):
+    """One direct dispatch of the depth (texels=False) or the visibility instantiation of the compute rasteriser on a scene of
+    tests/raster_path_scenes.py into cleared textures: (depth, vis or None).  alpha: the ALPHA_MASK_MODE=1 instantiation, with
+    s.materials at t3 and, unless table=False or s.textures is None, s.textures at t19 (None: an entry left empty;
+    raster_path_scenes.OTHER_FORMAT: an R8_UNORM texture)."""
+    from toyrenderer_amd import rhi
+    from toyrenderer_amd.rhi import CB, PUSH, SRV, TEX_TABLE, TEX_UAV
+    W, H = s.render
+    bufs = [dev.buffer_from(s.sc["instances"], "inst", uav=False), dev.buffer_from(s.v, "v", uav=False, min_bytes=20),
+            dev.buffer_from(s.sc["meshData"], "md", uav=False), dev.buffer_from(s.sc["meshlets"], "ml", uav=False, min_bytes=32),
+            dev.buffer_from(s.vid, "vid", uav=False), dev.buffer_from(s.tri, "tri", uav=False), dev.buffer_from(s.rec, "rec", min_bytes=12),
+            dev.buffer_from(s.lst, "lst")]
+    args = dev.create_buffer(12, "drawArgs", stride=12, indirect=True)
+    args.upload(np.array([len(s.lst), 1, 1], np.uint32))
+    depth = dev.create_texture(W, H, 1, rhi.FORMAT_R32_FLOAT, "Depth Buffer")
+    vis = dev.create_texture(W, H, 1, rhi.FORMAT_RG32_UINT, "VisibilityBuffer") if texels else None
+    made, tex_table, extra = [], None, []
+    cl = dev.create_command_list()
+    try:
+        if alpha:
+            bufs.append(dev.buffer_from(np.ascontiguousarray(s.materials, I.MaterialData), "materials", uav=False, min_bytes=124))
+            extra.append(SRV(3, bufs[-1]))
+            if table and s.textures is not None:
+                tex_table = dev.create_texture_table(max(len(s.textures), 1))
+                for i, t in enumerate(s.textures):
+                    if t is None:
+                        continue
+                    made.append(dev.create_sampled_texture(t[0], t[1], f"material texture {i}") if isinstance(t, tuple)
+                                else dev.create_texture(4, 4, 1, rhi.FORMAT_R8_UNORM, "another format", uav=False))
+                    tex_table.set(i, made[-1])
+                extra.append(TEX_TABLE(tex_table))
+        name = "basepass_MS_Main_" + ("visibility" if texels else "depth") + (" ALPHA_MASK_MODE=1" if alpha else "")
+        cl.open()
+        cl.clear_texture_f32(depth, 0.0)
+        cb = cl.constant_buffer(s.k, "BasePassConstants")
+        geo = [CB(0, cb), SRV(0, bufs[0]), SRV(1, bufs[1]), SRV(2, bufs[2]), SRV(4, bufs[3]), SRV(5, bufs[4]), SRV(6, bufs[5]), SRV(7, bufs[6]),
+               SRV(9, bufs[7]), TEX_UAV(0, depth, 0)] + extra
+        if texels:
+            cl.clear_texture_u32(vis, 0)
+            cl.dispatch_indirect(name, geo + [TEX_UAV(1, vis, 0), PUSH(1)], args, push=np.array([slot], np.uint32))
+        else:
+            cl.dispatch_indirect(name, geo, args)
+        cl.close()
+        dev.execute(cl); dev.wait_idle()
+        return depth.download_mip(0), vis.download_mip(0) if texels else None
+    finally:
+        cl.release(); depth.release(); args.release()
+        if vis is not None:
+            vis.release()
+        if tex_table is not None:
+            tex_table.release()
+        for b in bufs + made:
+            b.release()
+
+
 # ---- scenes -------------------------------------------------------------------------------------------------------------------
 def cornell_fixture():
     """(npz, LoadedScene, camera) of tests/golden/cornell_scene.npz."""

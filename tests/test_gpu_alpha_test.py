@@ -2,9 +2,9 @@
 (csrc/k_raster.hip) and the textured alpha test of "shadowmask_CS_ShadowMask" (csrc/k_shadowmask.hip), through
 FrameDriver(alpha_test=True) and the host mirror, every word of every pixel against tests/alpha_test_ref.c.
 
-NOT REACHABLE AT TEST SIZE: the queue-overflow path of the rasters.  A triangle that finds the queue full (2^20 entries) is drawn
-in place through the same sink and the same test as the small ones, which these scenes do exercise; no test queues a million
-triangles."""
+The rasters' path switches under the alpha test (kSmallBox, the tile rounds, kBinCapacity, the queue-overflow path with 2^20 +
+65 536 queued triangles, the grid stride, the early-out under discards) and rules 5 and 6 of the convention are in
+tests/test_gpu_alpha_raster_paths.py; this file's scenes have one bin, one collect round and nothing near a capacity."""
 import os
 import sys
 

@@ -16,7 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import raster_path_scenes as S  # noqa: E402
-from suite_support import dev, vr  # noqa: E402, F401
+from suite_support import dev, raster_dispatch, vr  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 K = S.K
@@ -24,38 +24,7 @@ K = S.K
 
 def _dispatch(dev, s, texels):
     """One direct dispatch of the depth (texels=False) or the visibility instantiation into cleared textures: (depth, vis or None)."""
-    from toyrenderer_amd import rhi
-    from toyrenderer_amd.rhi import CB, PUSH, SRV, TEX_UAV
-    W, H = s.render
-    bufs = [dev.buffer_from(s.sc["instances"], "inst", uav=False), dev.buffer_from(s.v, "v", uav=False, min_bytes=20),
-            dev.buffer_from(s.sc["meshData"], "md", uav=False), dev.buffer_from(s.sc["meshlets"], "ml", uav=False, min_bytes=32),
-            dev.buffer_from(s.vid, "vid", uav=False), dev.buffer_from(s.tri, "tri", uav=False), dev.buffer_from(s.rec, "rec", min_bytes=12),
-            dev.buffer_from(s.lst, "lst")]
-    args = dev.create_buffer(12, "drawArgs", stride=12, indirect=True)
-    args.upload(np.array([len(s.lst), 1, 1], np.uint32))
-    depth = dev.create_texture(W, H, 1, rhi.FORMAT_R32_FLOAT, "Depth Buffer")
-    vis = dev.create_texture(W, H, 1, rhi.FORMAT_RG32_UINT, "VisibilityBuffer") if texels else None
-    cl = dev.create_command_list()
-    try:
-        cl.open()
-        cl.clear_texture_f32(depth, 0.0)
-        cb = cl.constant_buffer(s.k, "BasePassConstants")
-        geo = [CB(0, cb), SRV(0, bufs[0]), SRV(1, bufs[1]), SRV(2, bufs[2]), SRV(4, bufs[3]), SRV(5, bufs[4]), SRV(6, bufs[5]), SRV(7, bufs[6]),
-               SRV(9, bufs[7]), TEX_UAV(0, depth, 0)]
-        if texels:
-            cl.clear_texture_u32(vis, 0)
-            cl.dispatch_indirect("basepass_MS_Main_visibility", geo + [TEX_UAV(1, vis, 0), PUSH(1)], args, push=np.array([S.SLOT], np.uint32))
-        else:
-            cl.dispatch_indirect("basepass_MS_Main_depth", geo, args)
-        cl.close()
-        dev.execute(cl); dev.wait_idle()
-        return depth.download_mip(0), vis.download_mip(0) if texels else None
-    finally:
-        cl.release(); depth.release(); args.release()
-        if vis is not None:
-            vis.release()
-        for b in bufs:
-            b.release()
+    return raster_dispatch(dev, s, texels, slot=S.SLOT)
 
 
 def _check(dev, oracle, vr, s, what, threads=1):
