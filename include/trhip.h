@@ -130,6 +130,15 @@ uint32_t    trhip_abi_version(void);
  * counts); the kernel reads t5.  It is the caller's promise that the two agree; where they do not, every fetch still stays
  * inside the bound textures and the value is unspecified.  The query is csrc/ddgi_irradiance.hip.h's (tests/ddgi_ref.c).
  * With m_bRTDDGIEnabled == 0 and another mode, bindings at t5..t8 and a longer b0 are accepted and ignored.
+ *
+ * "giprobetrace_CS_ProbeTrace", "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1" and "... =0"
+ * (GIRenderer::RenderDDGI: the probe update that fills that volume; csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip, which state
+ * the bindings and the arithmetic; tests/ddgi_update_ref.c is the definition).  b0 of all three: the 96-byte DDGIUpdateConsts
+ * (csrc/ShaderInterop.h) with the DDGIVolumeDesc's host copy behind it, 160 bytes.  Trace: t0 the descriptor, t1..t3 the probe
+ * textures, t4..t13 the scene and its acceleration structure, u0 a structured buffer float4[numProbes * 256] of ray records; a
+ * direct dispatch of (4, counts.x * counts.z, counts.y) groups.  Blends: t1 the ray records, t3 the probe data, u1 the
+ * irradiance (radiance blend) or u2 the distance (distance blend) array, created with the UAV bit; (counts.x, counts.z,
+ * counts.y) groups.  An array texture is accepted only at a binding that a pass declares, in the declared format.
  * "adaptluminance_CS_GenerateLuminanceHistogram" (adaptluminance.hlsl, AdaptLuminanceRenderer.cpp): a direct dispatch of
  * [numthreads(16, 16, 1)] groups covering m_SrcColorDims; push constants GenerateLuminanceHistogramParameters (16 bytes), t0
  * (texture) the R11G11B10_FLOAT colour, u0 a structured UAV of at least 256 uint32.  It ADDS to u0: the caller clears it.

@@ -116,7 +116,7 @@ int  trhost_set_directional_light(const float vec[3], float strength);
 int  trhost_upload_shadow_mask(const uint8_t* texels, uint64_t bytes);
 int  trhost_download_lighting_output(uint32_t* words, uint64_t bytes);
 int  trhost_get_deferred_lighting_consts(void* out112);
-/* The DDGI ambient term from a SUPPLIED probe volume (Scene::m_RTDDGIVolume; tracing and blending the probes is not built).
+/* The DDGI ambient term from a SUPPLIED probe volume (Scene::m_RTDDGIVolume; trhost_set_ddgi_update below lets it fill itself).
  * trhost_upload_ddgi_volume creates and fills the volume: desc64 is the 64-byte DDGIVolumeDesc (csrc/ShaderInterop.h), the three
  * arrays are dense, slice (probe y) after slice: irradiance R10G10B10A2_UNORM words [counts.y][counts.z * 8][counts.x * 8],
  * distance binary16 pairs [counts.y][counts.z * 16][counts.x * 16][2], data binary16 quadruples [counts.y][counts.z][counts.x][4];
@@ -128,6 +128,20 @@ int  trhost_get_deferred_lighting_consts(void* out112);
 int  trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, uint64_t irradiance_bytes, const uint16_t* distance, uint64_t distance_bytes,
                                const uint16_t* data, uint64_t data_bytes);
 int  trhost_set_ddgi(int enable);
+/* The probe update, GIRenderer::RenderDDGI (csrc/host/GIRenderer.cpp): with trhost_set_ddgi_update(1, seed) every frame with
+ * deferred lighting on records, behind the TLAS refit (which then runs with or without trhost_set_shadow_mask) and in front of
+ * DeferredLightingRenderer, "giprobetrace_CS_ProbeTrace" and the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes on the uploaded
+ * volume, which so fills itself from what it holds; the n-th update after the call takes its ray rotation from (seed, n).  It
+ * needs trhost_upload_ddgi_volume and trhost_load_raytracing and is refused without them; dropping the volume switches it off.
+ * The settings are the reference's (hysteresis 0.5, distance exponent 50, thresholds 0.2 and 0.1; probeMaxRayDistance 1e10).
+ * trhost_reset_ddgi_volume clears irradiance and distance to zero words, the reference's start (GIRenderer.cpp:457-458);
+ * trhost_download_ddgi_volume reads the three textures back in trhost_upload_ddgi_volume's layout;
+ * trhost_get_ddgi_update_consts copies the 96 bytes of DDGIUpdateConsts (csrc/ShaderInterop.h) the last frame's update ran with,
+ * the rotation among them, and fails if no update ran in it. */
+int  trhost_set_ddgi_update(int enabled, uint32_t seed);
+int  trhost_reset_ddgi_volume(void);
+int  trhost_download_ddgi_volume(uint32_t* irradiance, uint64_t irradiance_bytes, uint16_t* distance, uint64_t distance_bytes, uint16_t* data, uint64_t data_bytes);
+int  trhost_get_ddgi_update_consts(void* out96);
 /* Auto exposure and tone mapping (AdaptLuminanceRenderer.cpp, PostProcessRenderer.cpp; implies deferred lighting, same refusals):
  * after DeferredLightingRenderer the frame clears the luminance histogram and runs "adaptluminance_CS_GenerateLuminanceHistogram"
  * and "adaptluminance_CS_AdaptExposure" (with a manual exposure > 0: one write of it into the luminance buffer instead), then

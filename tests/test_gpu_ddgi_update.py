@@ -1,0 +1,434 @@
+"""The DDGI probe update on the GPU ("giprobetrace_CS_ProbeTrace" and the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes;
+csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip), every word against tests/ddgi_update_ref.c: the trace over the Cornell fixture
+with cleared and seeded volumes, each blend from a supplied ray buffer, three chained updates through FrameDriver(ddgi_update=...),
+and misuse."""
+import inspect
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import ddgi_ref as DR  # noqa: E402
+import ddgi_update_ref as DU  # noqa: E402
+import ddgi_update_scenes as US  # noqa: E402
+import shadow_scenes as SS  # noqa: E402
+import shadowmask_ref as SR  # noqa: E402
+from suite_support import dev, dg, gpu_scene, ref_library, same, sm  # noqa: E402, F401
+from toyrenderer_amd import ddgi, gltf_lite  # noqa: E402
+from toyrenderer_amd import interop as I  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+du = ref_library(DU)
+TRACE = "giprobetrace_CS_ProbeTrace"
+BLEND_RADIANCE = "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1"
+BLEND_DISTANCE = "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0"
+SENTINEL = F(7.5)                                 # pre-fill of the ray records: an inactive probe's keep it
+
+
+def _cornell_gpu(dev, oracle):
+    """The Cornell fixture as the frames of the other tests have it, with its acceleration structure: (scene dict, GpuScene)."""
+    sc = SS.cornell()
+    s = sc["loaded"]
+    inst = sc["instances"].copy()
+    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
+    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
+    sc["instances"] = inst
+    s.meshData = sc["meshData"]
+    gs = gpu_scene(dev, s, inst, s.vertices, sc["materials"])
+    gs.set_raytracing(sc["indices"], sc["cached"].meshSpecific)
+    return sc, gs
+
+
+@pytest.fixture(scope="module")
+def cornell(dev, oracle, sm):
+    sc, gs = _cornell_gpu(dev, oracle)
+    yield sc, gs, DU.Scene(sm, SR.Accel(sc))
+    gs.release()
+
+
+class Update:
+    """One volume's device resources and the three passes through rhi bindings."""
+
+    def __init__(self, dev, vol, gs=None, uav=True):
+        self.dev, self.vol, self.gs = dev, vol, gs
+        self.desc, self.data, self.irr, self.dist = vol.upload(dev, uav=uav)
+        self.n = int(np.prod(vol.counts))
+        self.rays = dev.create_buffer(self.n * DU.RAYS * 16, "DDGI Ray Data", stride=16)
+        self.cl = dev.create_command_list()
+
+    def block(self, k):
+        return np.frombuffer(np.ascontiguousarray(k, I.DDGIUpdateConsts).tobytes() + self.vol.desc().tobytes(), np.uint8)
+
+    def trace_bindings(self, cb):
+        from toyrenderer_amd.rhi import CB, SAMPLER, SRV, TEX_SRV, UAV
+        gs, rt = self.gs, self.gs.rt
+        return [CB(0, cb), SRV(0, self.desc), TEX_SRV(1, self.data), TEX_SRV(2, self.irr), TEX_SRV(3, self.dist), SRV(4, rt["tlas_nodes"]), SRV(5, gs.instances),
+                SRV(6, gs.vertices), SRV(7, gs.materials), SRV(8, gs.indices), SRV(9, gs.meshData), SRV(10, rt["tlas_instances"]), SRV(11, rt["headers"]),
+                SRV(12, rt["blas_nodes"]), SRV(13, rt["tri_order"]), UAV(0, self.rays), SAMPLER(0), SAMPLER(1), SAMPLER(2)]
+
+    def trace_groups(self):
+        cx, cy, cz = self.vol.counts
+        return (DU.RAYS // 64, cx * cz, cy)
+
+    def blend_bindings(self, cb, radiance):
+        from toyrenderer_amd.rhi import CB, SRV, TEX_SRV, TEX_UAV
+        return [CB(0, cb), SRV(1, self.rays), TEX_SRV(3, self.data), TEX_UAV(1, self.irr, 0) if radiance else TEX_UAV(2, self.dist, 0)]
+
+    def blend_groups(self):
+        cx, cy, cz = self.vol.counts
+        return (cx, cz, cy)
+
+    def refit(self):
+        from toyrenderer_amd.rhi import PUSH, SRV, UAV
+        gs, rt = self.gs, self.gs.rt
+        k = np.zeros(1, I.RefitTLASConstants)
+        k["m_NumInstances"], k["m_NumNodes"], k["m_NumLevels"] = gs.numInstances, len(rt["tlas"]["nodes"]), rt["tlas"]["num_levels"]
+        self.cl.dispatch("raytracing_CS_RefitTLAS", [PUSH(0), SRV(0, gs.instances), SRV(1, rt["headers"]), SRV(2, rt["blas_nodes"]), SRV(3, rt["level_offsets"]),
+                                                     SRV(4, rt["level_nodes"]), UAV(0, rt["tlas_nodes"]), UAV(1, rt["tlas_instances"])],
+                         ((gs.numInstances + 63) // 64, 1, 1), push=k)
+
+    def run_trace(self, k):
+        self.rays.upload(np.full(self.n * DU.RAYS * 4, SENTINEL, F))
+        self.cl.open()
+        self.refit()
+        self.cl.dispatch(TRACE, self.trace_bindings(self.cl.constant_buffer(self.block(k), "DDGIUpdateConsts")), self.trace_groups())
+        self.cl.close()
+        self.dev.execute(self.cl); self.dev.wait_idle()
+        return self.rays.download(F).reshape(self.n, DU.RAYS, 4)
+
+    def run_blends(self, k, rays):
+        self.rays.upload(np.ascontiguousarray(rays, F).reshape(-1))
+        self.cl.open()
+        cb = self.cl.constant_buffer(self.block(k), "DDGIUpdateConsts")
+        self.cl.dispatch(BLEND_RADIANCE, self.blend_bindings(cb, True), self.blend_groups())
+        self.cl.dispatch(BLEND_DISTANCE, self.blend_bindings(cb, False), self.blend_groups())
+        self.cl.close()
+        self.dev.execute(self.cl); self.dev.wait_idle()
+        return self.textures()
+
+    def textures(self):
+        cy = self.vol.counts[1]
+        irr = np.stack([self.irr.download_slice(s) for s in range(cy)])
+        dist = np.stack([self.dist.download_slice(s) for s in range(cy)]).reshape(self.vol.distance.shape)
+        return irr, dist
+
+    def release(self):
+        self.cl.release()
+        for r in (self.desc, self.data, self.irr, self.dist, self.rays):
+            r.release()
+
+
+# ---- 1. the trace --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seeded", [False, True], ids=["cleared", "seeded"])
+@pytest.mark.parametrize("name", list(US.CORNELL_VOLUMES))
+def test_trace_matches_the_reference(dev, du, cornell, name, seeded):
+    """Every word of the 256-ray records of every probe equals the reference, over a cleared volume and over seeded contents (a
+    non-zero recursive term, relocated probes and, in "3x2x4", inactive ones, whose records keep what they held)."""
+    sc, gs, scene = cornell
+    vol = US.cornell_volume(name, seeded)
+    k = DU.consts(light=US.LIGHT, rotation=US.rotation(7))
+    u = Update(dev, vol, gs, uav=False)                                  # the trace only reads the probe textures
+    try:
+        got = u.run_trace(k)
+        want, kinds = DU.trace(du, k, vol, scene, DU.WALK, np.full(got.shape, SENTINEL, F))
+        same(got.view(np.uint32), want.view(np.uint32), f"{name} seeded={seeded}: ray records")
+        assert len(np.unique(kinds)) >= 3
+        other = DU.consts(light=US.LIGHT, rotation=US.rotation(8))
+        moved = np.any(u.run_trace(other).view(np.uint32) != got.view(np.uint32), axis=-1)        # a record differs in its distance at least
+        _, inactive = DU.probe_positions(du, vol)
+        assert np.count_nonzero(moved) > np.count_nonzero(~inactive) * DU.RAYS // 2, "the rotation comes from the constant block"
+    finally:
+        u.release()
+
+
+# ---- 2. the blends ---------------------------------------------------------------------------------------------------------------------
+def test_blends_match_the_reference_from_a_supplied_ray_buffer(dev, du):
+    """Each blend from a seeded ray buffer (no trace): negative distances, a probe at 24 and one at 25 back faces, an inactive
+    probe, an all-miss and an all-dark probe, previously zero and non-zero texels.  Every word of both textures equals the
+    reference, borders included; a second update on top of the first does too."""
+    vol = US.blend_volume()
+    rays = US.blend_rays(vol)
+    u = Update(dev, vol)
+    try:
+        for step, seed in enumerate((2, 6)):
+            k = DU.consts(rotation=US.rotation(seed), hysteresis=0.5 if step == 0 else 0.9)
+            irr, dist = u.run_blends(k, rays)
+            want_irr, want_dist = DU.blend(du, k, vol, rays)
+            same(irr, want_irr, f"update {step}: irradiance")
+            same(dist.view(np.uint16), want_dist.view(np.uint16), f"update {step}: distance")
+            for p in (US.BLEND_INACTIVE, US.BLEND_25_BACK):
+                x, y, z = p % 3, p // 6, (p // 3) % 2
+                assert np.array_equal(irr[y, z * 8:z * 8 + 8, x * 8:x * 8 + 8], vol.irradiance[y, z * 8:z * 8 + 8, x * 8:x * 8 + 8])
+            assert np.count_nonzero(irr != vol.irradiance) > 300 and np.count_nonzero(dist.view(np.uint16) != vol.distance.view(np.uint16)) > 2000
+            vol.irradiance, vol.distance = want_irr, want_dist           # the next update starts from this one
+            rays = rays[:, ::-1].copy()
+    finally:
+        u.release()
+
+
+def test_blend_of_a_single_probe_and_of_many(dev, du):
+    """The smallest volume (one workgroup) and one of 5 x 3 x 4 probes whose tiles cross the textures' row pitch."""
+    for counts in ((1, 1, 1), (5, 3, 4)):
+        vol = DU.seeded_volume(ddgi.Volume((0.0, 0.0, 0.0), (1.0, 0.7, 1.3), counts, normal_bias=0.02, view_bias=0.1), 9, inactive=(0,) if counts != (1, 1, 1) else ())
+        rays = US.blend_rays(vol, seed=counts[0]) if counts != (1, 1, 1) else US.blend_rays(ddgi.Volume((0, 0, 0), (1, 1, 1), (3, 2, 2), 0.02, 0.1))[:1]
+        k = DU.consts(rotation=US.rotation(counts[0]))
+        u = Update(dev, vol)
+        try:
+            irr, dist = u.run_blends(k, rays)
+            want_irr, want_dist = DU.blend(du, k, vol, rays)
+            same(irr, want_irr, f"{counts}: irradiance")
+            same(dist.view(np.uint16), want_dist.view(np.uint16), f"{counts}: distance")
+        finally:
+            u.release()
+
+
+# ---- 3. frames --------------------------------------------------------------------------------------------------------------------------
+def _driver_volume():
+    return ddgi.Volume((0.03, 0.95, 0.05), (0.45, 0.45, 0.45), (4, 4, 4), normal_bias=0.02, view_bias=0.1, relocation=False, classification=False).reset()
+
+
+def test_three_chained_updates_through_the_driver(dev, oracle, du, dg, cornell):
+    """Cornell at 160 x 90 through FrameDriver(ddgi=volume, ddgi_update=...): three record() / run() pairs with distinct rotations.
+    After each, download_ddgi() equals the reference update of the state before, the ray records equal the reference trace, and
+    LightingOutput equals tests/ddgi_ref.c fed the downloaded volume.  The volume keeps changing: irradiance after update 3
+    differs from update 1 on more than half of the interior texels."""
+    from toyrenderer_amd.frame import FrameDriver
+    sc, gs, scene = cornell
+    cam = sc["camera"]
+    view = gltf_lite.view_of(cam, (160, 90))
+    vol = _driver_volume()
+    common = dict(record_capacity=4096, culling_flags=7, lighting=True, dir_light=US.LIGHT, camera_origin=tuple(float(x) for x in cam.position))
+    drv = FrameDriver(dev, gs, view, ddgi=vol, ddgi_update=dict(seed=11, hysteresis=0.6), **common)
+    try:
+        state = vol.copy()
+        seen, rotations = [], []
+        for n in range(3):
+            drv.record(); drv.run(); drv.results()
+            k = drv.ddgi_update_consts
+            assert drv.ddgi_updates == n + 1 and k["probeHysteresis"][0] == F(0.6) and k["probeDistanceExponent"][0] == 50.0
+            same(k["rayRotation"][0, :, :3], ddgi.random_rotation(np.random.default_rng([11, n])), f"update {n}: rotation")
+            assert tuple(k["m_DirectionalLightVector"][0]) == tuple(F(x) for x in US.LIGHT[0]) and k["m_DirectionalLightStrength"][0] == 3.0
+            rotations.append(k["rayRotation"].tobytes())
+            want_rays = DU.update(du, k, state, scene)                   # state: one reference update further
+            same(drv.download_ddgi_rays().view(np.uint32), want_rays.view(np.uint32), f"update {n}: ray records")
+            got = drv.download_ddgi()
+            same(got.irradiance, state.irradiance, f"update {n}: irradiance")
+            same(got.distance.view(np.uint16), state.distance.view(np.uint16), f"update {n}: distance")
+            same(got.data.view(np.uint16), state.data.view(np.uint16), f"update {n}: probe data")
+            depth, g = drv.depth.download_mip(0), drv.gbufferA.download_mip(0)
+            same(drv.lighting_output.download_mip(0), DR.lighting(dg, drv.lighting_consts, got, g, depth), f"update {n}: LightingOutput")
+            seen.append(got.irradiance.copy())
+        assert len(set(rotations)) == 3
+        inner = np.broadcast_to(DU.interior_mask(seen[0].shape[1:], 8), seen[0].shape)
+        assert np.count_nonzero(seen[2][inner] != seen[0][inner]) > inner.sum() // 2
+        assert np.count_nonzero(seen[0][inner] & 0x3FFFFFFF) > inner.sum() // 2, "the first update lit the probes"
+    finally:
+        drv.release()
+
+
+def test_the_update_with_shadows_refits_once_and_without_it_changes_nothing(dev, oracle, cornell):
+    """ddgi_update=None records what it recorded before; with it the refit, the trace and the two blends appear between the
+    shadow pass and the lighting pass, and the refit is recorded once whether shadows= is on or not."""
+    from suite_support import recorded
+    from toyrenderer_amd.frame import FrameDriver
+    sc, gs, scene = cornell
+    view = gltf_lite.view_of(sc["camera"], (64, 36))
+    common = dict(record_capacity=4096, culling_flags=7, lighting=True, dir_light=US.LIGHT)
+    shadows = dict(noise=SS.noise_image(4))
+    made = [FrameDriver(dev, gs, view, ddgi=_driver_volume(), **common), FrameDriver(dev, gs, view, ddgi=_driver_volume(), ddgi_update={}, **common),
+            FrameDriver(dev, gs, view, ddgi=_driver_volume(), ddgi_update={}, shadows=shadows, **common), FrameDriver(dev, gs, view, ddgi=_driver_volume(), shadows=shadows, **common)]
+    try:
+        plain, update, both, shadowed = ([shader for _, shader in recorded(d) if shader] for d in made)
+        new = ["raytracing_CS_RefitTLAS", TRACE, BLEND_RADIANCE, BLEND_DISTANCE]
+        at = plain.index("deferredlighting_PS_Main")
+        assert update == plain[:at] + new + plain[at:]
+        at = shadowed.index("deferredlighting_PS_Main")
+        assert shadowed[at - 2:at] == ["raytracing_CS_RefitTLAS", "shadowmask_CS_ShadowMask"]
+        assert both == shadowed[:at] + new[1:] + shadowed[at:]
+    finally:
+        for d in made:
+            d.release()
+
+
+def test_one_update_through_the_host_mirror(oracle, du, dg, sm):
+    """The same through host.Renderer: trhost_set_ddgi_update is refused without a volume or an acceleration structure; with them
+    one frame's update, under the rotation trhost_get_ddgi_update_consts shows, leaves the volume the reference leaves, and
+    LightingOutput equals tests/ddgi_ref.c fed the downloaded volume; a second frame takes another rotation;
+    trhost_reset_ddgi_volume clears."""
+    from suite_support import host_renderer
+    from toyrenderer_amd import host
+    sc = SS.cornell()
+    s = sc["loaded"]
+    inst = sc["instances"].copy()
+    oracle.update_instance_consts(s.nodes, s.primToNode, inst)
+    inst["m_PrevWorldMatrix"] = inst["m_WorldMatrix"]
+    ref = dict(sc); ref["instances"] = inst
+    scene = DU.Scene(sm, SR.Accel(ref))
+    s.meshData = sc["meshData"]
+    render = (160, 90)
+    view = gltf_lite.view_of(sc["camera"], render)
+    vol = _driver_volume()
+    with host_renderer(s, gltf_lite.apply_materials(s), (s.vertices, s.meshletVertexIds, s.meshletTriangles), sc["materials"], render=render, max_groups=4096) as r:
+        r.set_deferred_lighting(True)
+        r.set_directional_light(*US.LIGHT)
+        r.set_culling(7)
+        r.set_node_transforms(s.nodes)
+        r.set_camera(view)
+        with pytest.raises(host.HostError, match="trhost_set_ddgi_update: no DDGI volume.*giprobetrace_CS_ProbeTrace"):
+            r.set_ddgi_update(True)
+        r.upload_ddgi_volume(vol)
+        with pytest.raises(host.HostError, match="trhost_set_ddgi_update: no acceleration structure.*giprobetrace_CS_ProbeTrace"):
+            r.set_ddgi_update(True)
+        r.load_raytracing(sc["indices"], sc["cached"].meshSpecific)
+        r.set_ddgi(True)
+        r.frame(); r.results()
+        with pytest.raises(host.HostError, match="no probe update"):
+            r.ddgi_update_consts()
+        same(r.download_ddgi_volume(vol).irradiance, vol.irradiance, "host: no update, the volume stays")
+        r.set_ddgi_update(True, seed=5)
+        state = vol.copy()
+        rotations = []
+        for n in range(2):
+            r.frame(); r.results()
+            k = r.ddgi_update_consts()
+            rot = k["rayRotation"][0, :, :3].astype(np.float64)
+            assert np.allclose(rot @ rot.T, np.eye(3), atol=1e-6) and np.linalg.det(rot) > 0.999 and np.all(k["rayRotation"][0, :, 3] == 0)
+            assert k["probeHysteresis"][0] == 0.5 and k["probeDistanceExponent"][0] == 50.0 and k["probeIrradianceThreshold"][0] == F(0.2) and k["probeBrightnessThreshold"][0] == F(0.1)
+            assert tuple(k["m_DirectionalLightVector"][0]) == tuple(F(x) for x in US.LIGHT[0]) and k["m_DirectionalLightStrength"][0] == 3.0
+            rotations.append(k["rayRotation"].tobytes())
+            DU.update(du, k, state, scene)
+            got = r.download_ddgi_volume(vol)
+            same(got.irradiance, state.irradiance, f"host update {n}: irradiance")
+            same(got.distance.view(np.uint16), state.distance.view(np.uint16), f"host update {n}: distance")
+            lk = r.deferred_lighting_consts()
+            assert lk["m_bRTDDGIEnabled"][0] == 1
+            same(r.download_lighting_output(), DR.lighting(dg, lk, got, r.download_gbuffer_a(), r.download_depth()), f"host update {n}: LightingOutput")
+        assert rotations[0] != rotations[1] and np.count_nonzero(state.irradiance) > state.irradiance.size // 2
+        r.set_ddgi_update(False)
+        r.reset_ddgi_volume()
+        cleared = r.download_ddgi_volume(vol)
+        assert not cleared.irradiance.any() and not cleared.distance.view(np.uint16).any()
+        r.frame(); r.results()
+        assert not r.download_ddgi_volume(vol).irradiance.any(), "the update is off: the volume stays cleared"
+        r.upload_ddgi_volume(None)
+        with pytest.raises(host.HostError, match="no DDGI volume"):
+            r.reset_ddgi_volume()
+
+
+# ---- 4. misuse --------------------------------------------------------------------------------------------------------------------------
+def test_the_driver_refuses_an_update_it_cannot_run(dev, oracle, cornell):
+    from toyrenderer_amd.frame import FrameDriver
+    sc, gs, scene = cornell
+    view = gltf_lite.view_of(sc["camera"], (64, 36))
+    common = dict(record_capacity=4096, culling_flags=7, dir_light=US.LIGHT)
+    with pytest.raises(ValueError, match="ddgi_update=.*needs lighting=True and ddgi="):
+        FrameDriver(dev, gs, view, lighting=True, ddgi_update={}, **common)
+    with pytest.raises(ValueError, match="ddgi_update=.*needs lighting=True and ddgi="):
+        FrameDriver(dev, gs, view, gbuffer=True, ddgi_update={}, **common)
+    with pytest.raises(ValueError, match="ddgi_update: unknown settings"):
+        FrameDriver(dev, gs, view, lighting=True, ddgi=_driver_volume(), ddgi_update=dict(speed=1), **common)
+    s = sc["loaded"]
+    bare = gpu_scene(dev, s, sc["instances"], s.vertices, sc["materials"])              # no set_raytracing()
+    try:
+        with pytest.raises(ValueError, match="ddgi_update=.*needs GpuScene.set_raytracing"):
+            FrameDriver(dev, bare, view, lighting=True, ddgi=_driver_volume(), ddgi_update={}, **common)
+    finally:
+        bare.release()
+    drv = FrameDriver(dev, gs, view, lighting=True, ddgi=_driver_volume(), **common)
+    try:
+        with pytest.raises(ValueError, match="ddgi_update=None"):
+            drv.download_ddgi_rays()
+    finally:
+        drv.release()
+
+
+def test_misuse_of_the_passes_is_refused(dev, cornell):
+    """A short constant block, a ray buffer of the wrong size, probe textures without the UAV bit or of another size, format or
+    kind, wrong group counts and a bad descriptor: each is refused with the pass's name."""
+    from toyrenderer_amd import rhi
+    from toyrenderer_amd.rhi import CB, SRV, TEX_SRV, TEX_UAV, UAV
+    sc, gs, scene = cornell
+    vol = US.cornell_volume("3x2x4", True)
+    u, ro = Update(dev, vol, gs), Update(dev, vol, gs, uav=False)
+    made = []
+    cl = u.cl
+    k = DU.consts()
+    cl.open()
+    try:
+        cb = cl.constant_buffer(u.block(k), "DDGIUpdateConsts")
+        short = cl.constant_buffer(u.block(k)[:96], "short")
+        small = dev.create_buffer(u.n * DU.RAYS * 16 - 16, "small rays", stride=16); made.append(small)
+        plain = dev.create_texture(24, 32, 1, rhi.FORMAT_R10G10B10A2_UNORM, "plain"); made.append(plain)
+        other = dev.create_texture_array(32, 32, 2, rhi.FORMAT_R10G10B10A2_UNORM, "other size", uav=True); made.append(other)
+        rg = dev.create_texture_array(24, 32, 2, rhi.FORMAT_RG16_FLOAT, "wrong format", uav=True); made.append(rg)
+
+        def swap(bindings, kind, slot, new):
+            return [b for b in bindings if not (b.type == kind and b.slot == slot)] + ([new] if new is not None else [])
+
+        def block_with(**fields):
+            d = vol.desc().copy()
+            for f, x in fields.items():
+                d[f] = x
+            return cl.constant_buffer(np.frombuffer(k.tobytes() + d.tobytes(), np.uint8), "bad")
+
+        passes = ((TRACE, u.trace_bindings, u.trace_groups()), (BLEND_RADIANCE, lambda c: u.blend_bindings(c, True), u.blend_groups()),
+                  (BLEND_DISTANCE, lambda c: u.blend_bindings(c, False), u.blend_groups()))
+        for name, bindings, groups in passes:
+            cases = [("160 bytes", swap(bindings(cb), rhi.BIND_CONSTANT_BUFFER, 0, CB(0, short)), groups),
+                     ("160 bytes", swap(bindings(cb), rhi.BIND_CONSTANT_BUFFER, 0, None), groups),
+                     ("direct dispatch of", bindings(cb), (groups[0], groups[1], groups[2] + 1)),
+                     ("direct dispatch of", bindings(cb), (groups[0] + 1, groups[1], groups[2])),
+                     ("not in 1..1024", bindings(block_with(probeCounts=(3, 0, 4))), groups),
+                     ("interior texel counts", bindings(block_with(numIrradianceInteriorTexels=8)), groups),
+                     ("not positive and finite", bindings(block_with(probeSpacing=(1.0, float("nan"), 1.0))), groups),
+                     ("probeCounts", bindings(block_with(probeCounts=(4, 2, 3))), (groups[0], 12, 2) if name == TRACE else (4, 3, 2))]
+            if name == TRACE:
+                cases += [("the ray records at u0 hold", swap(bindings(cb), rhi.BIND_STRUCTURED_UAV, 0, UAV(0, small)), groups),
+                          ("u0 = the ray records", swap(bindings(cb), rhi.BIND_STRUCTURED_UAV, 0, None), groups),
+                          ("t0 = the 64-byte DDGIVolumeDesc", swap(bindings(cb), rhi.BIND_STRUCTURED_SRV, 0, None), groups),
+                          ("t12 = the BLAS nodes", swap(bindings(cb), rhi.BIND_STRUCTURED_SRV, 12, None), groups),
+                          ("t2 = the R10G10B10A2_UNORM", swap(bindings(cb), rhi.BIND_TEXTURE_SRV, 2, None), groups),
+                          ("not an array", swap(bindings(cb), rhi.BIND_TEXTURE_SRV, 2, TEX_SRV(2, plain)), groups),
+                          ("is 32x32 with 2 slices", swap(bindings(cb), rhi.BIND_TEXTURE_SRV, 2, TEX_SRV(2, other)), groups),
+                          ("array texture", swap(bindings(cb), rhi.BIND_TEXTURE_SRV, 2, TEX_SRV(2, rg)), groups)]
+            else:
+                radiance = name == BLEND_RADIANCE
+                slot, target, ro_target = (1, u.irr, ro.irr) if radiance else (2, u.dist, ro.dist)
+                cases += [("the ray records at t1 hold", swap(bindings(cb), rhi.BIND_STRUCTURED_SRV, 1, SRV(1, small)), groups),
+                          ("t1 = the ray records", swap(bindings(cb), rhi.BIND_STRUCTURED_SRV, 1, None), groups),
+                          ("t3 = the RGBA16_FLOAT", swap(bindings(cb), rhi.BIND_TEXTURE_SRV, 3, None), groups),
+                          (f"u{slot} = the", swap(bindings(cb), rhi.BIND_TEXTURE_UAV, slot, None), groups),
+                          ("without the UAV bit", swap(bindings(cb), rhi.BIND_TEXTURE_UAV, slot, TEX_UAV(slot, ro_target, 0)), groups),
+                          ("array texture", swap(bindings(cb), rhi.BIND_TEXTURE_UAV, slot, TEX_UAV(slot, u.dist if radiance else u.irr, 0)), groups),
+                          ("array texture", bindings(cb) + [TEX_UAV(3 - slot, u.dist if radiance else u.irr, 0)], groups)]
+                if radiance:
+                    cases.append(("is 32x32 with 2 slices", swap(bindings(cb), rhi.BIND_TEXTURE_UAV, 1, TEX_UAV(1, other, 0)), groups))
+            for match, b, g in cases:
+                with pytest.raises(rhi.TrhipError, match=match) as e:
+                    cl.dispatch(name, b, g)
+                assert name in str(e.value), (match, str(e.value))
+    finally:
+        cl.close()
+        for r in made:
+            r.release()
+        u.release(); ro.release()
+
+
+# ---- 5. what fails without this feature -----------------------------------------------------------------------------------------------------
+def test_the_feature_is_there():
+    from toyrenderer_amd import rhi
+    from toyrenderer_amd.frame import FrameDriver
+    names = rhi.shader_names()
+    for n in (TRACE, BLEND_RADIANCE, BLEND_DISTANCE):
+        assert n in names
+    params = inspect.signature(FrameDriver.__init__).parameters
+    assert "ddgi_update" in params and hasattr(FrameDriver, "download_ddgi")
+    assert "uav" in inspect.signature(ddgi.Volume.upload).parameters
+    from toyrenderer_amd import host
+    lib = host.load()
+    for sym in ("trhost_set_ddgi_update", "trhost_reset_ddgi_volume", "trhost_download_ddgi_volume", "trhost_get_ddgi_update_consts"):
+        assert sym in host.HOST_SYMBOLS and hasattr(lib, sym)

@@ -154,6 +154,29 @@ static_assert(sizeof(DDGIVolumeDesc) == 64 && offsetof(DDGIVolumeDesc, probeSpac
 static constexpr uint32_t kDDGIFlag_Relocation = 1u, kDDGIFlag_Classification = 2u;
 static constexpr uint32_t kDDGIIrradianceInteriorTexels = 6, kDDGIDistanceInteriorTexels = 14, kDDGIMaxProbeCount = 1024;
 
+// The project's own: b0 of "giprobetrace_CS_ProbeTrace" and of the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes
+// (k_giprobetrace.hip, k_giprobeblend.hip).  It begins with the reference's GIProbeTraceConsts (ShaderInterop.h:243-247) and
+// goes on with what the SDK keeps in its volume descriptor and this project's 64-byte DDGIVolumeDesc does not hold: the frame's
+// ray rotation (rows of a 3 x 3 matrix, rotated = (dot3(row0, d), dot3(row1, d), dot3(row2, d))) and the update's settings.
+// Defaults: GIRenderer.cpp:79 (the scene's bounding radius), :111-118.  The passes read the volume's descriptor from a host copy
+// that follows this block in b0 (160 bytes together), as the lighting pass does.
+struct DDGIUpdateConsts
+{
+    float m_DirectionalLightVector[3];
+    float m_DirectionalLightStrength;
+    float rayRotation[3][4];                 // three rows; the fourth column is padding
+    float probeMaxRayDistance;
+    float probeHysteresis;                   // 0.5
+    float probeDistanceExponent;             // 50
+    float probeIrradianceThreshold;          // 0.2
+    float probeBrightnessThreshold;          // 0.1
+    uint32_t pad[3];
+};
+static_assert(sizeof(DDGIUpdateConsts) == 96 && offsetof(DDGIUpdateConsts, rayRotation) == 16 && offsetof(DDGIUpdateConsts, probeMaxRayDistance) == 64 &&
+              offsetof(DDGIUpdateConsts, probeBrightnessThreshold) == 80, "DDGIUpdateConsts");
+static constexpr uint32_t kDDGIRaysPerProbe = 256;              // RTXGI_DDGI_BLEND_RAYS_PER_PROBE
+static constexpr uint32_t kDDGIBackfaceRayLimit = 25;           // (uint)(256 * probeRandomRayBackfaceThreshold), 0.1f: GIRenderer.cpp:120
+
 // ShaderInterop.h:124-129: push constants of "adaptluminance_CS_GenerateLuminanceHistogram"
 struct GenerateLuminanceHistogramParameters
 {

@@ -3,8 +3,8 @@
 // "deferredlighting_PS_Main" or, under a debug view, "deferredlighting_PS_Main_Debug" (csrc/k_deferredlighting.hip).
 //
 // DDGI: m_bRTDDGIEnabled = g_Scene->IsDDGIEnabled(), as in the reference; the volume (g_Scene->m_RTDDGIVolume: descriptor at t5,
-// probe data, irradiance and distance at t6..t8) is SUPPLIED through trhost_upload_ddgi_volume, tracing and blending the probes
-// are not built.  With the volume bound the constant block carries the descriptor's host copy behind the DeferredLightingConsts
+// probe data, irradiance and distance at t6..t8) comes from trhost_upload_ddgi_volume and, with trhost_set_ddgi_update, is filled by
+// GIRenderer (GIRenderer.cpp) in front of this pass.  With the volume bound the constant block carries the descriptor's host copy behind the DeferredLightingConsts
 // (include/trhip.h).  The shadow mask at t4 is ShadowMaskRenderer's when that pass is scheduled, else an uploaded one
 // (trhost_upload_shadow_mask), else t4 stays unbound: 1.0, the reference's WhiteTexture.  The full-screen triangle with its stencil test on the opaque
 // bit is a direct dispatch of 8x8 groups here; the kernel writes where depth > 0.
@@ -55,6 +55,10 @@ public:
         m_ShadowMask = GetScheduledShadowMaskTexture();                        // :46-49
         if (!m_ShadowMask) m_ShadowMask = g_Scene->m_ShadowMaskTexture;
         if (m_ShadowMask) renderGraph.AddExternalReadDependency(m_ShadowMask.Get());
+        if (g_Scene->m_bDDGIUpdate && g_Scene->m_RTDDGIVolume.IsValid()) {    // GIRenderer, scheduled in front, writes the two textures this pass reads
+            renderGraph.AddExternalReadDependency(g_Scene->m_RTDDGIVolume.m_ProbeIrradiance.Get());
+            renderGraph.AddExternalReadDependency(g_Scene->m_RTDDGIVolume.m_ProbeDistance.Get());
+        }
         renderGraph.AddExternalWriteDependency(m_LightingOutput.Get());
         return true;
     }

@@ -2,15 +2,25 @@
 // culling dispatch of GIDebugRenderer (source/GIRenderer.cpp:598-808; Setup :612-657, RenderDDGIDebug :672-735), the
 // second consumer of FrustumCull / OcclusionCull and of compaction into indirect draw arguments.
 //
-// The DDGI volume itself (probe tracing / blending, RTXGI SDK) is out of scope: the probes' world positions and states
-// arrive as two buffers (Scene::LoadGIProbes) where the reference binds the volume descriptors (t10) and the probe-data
-// texture array (u10).  The draw of the unit spheres that consumes the indirect arguments (:737-806) is pixel work.
+// The debug renderer does not read the DDGI volume: the probes' world positions and states arrive as two buffers
+// (Scene::LoadGIProbes) where the reference binds the volume descriptors (t10) and the probe-data texture array (u10).  The draw
+// of the unit spheres that consumes the indirect arguments (:737-806) is pixel work.
+//
+// And GIRenderer (source/GIRenderer.cpp: RenderDDGI): the probe update of Scene::m_RTDDGIVolume, "giprobetrace_CS_ProbeTrace" and
+// the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes (csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip), behind the TLAS refit and
+// in front of DeferredLightingRenderer.  The RTXGI SDK is not part of this project: the passes are the project's own, with one
+// constant block (DDGIUpdateConsts, the descriptor's host copy behind it).  Relocation, classification and variability are not
+// built.  The frame's ray rotation is a uniformly distributed rotation (Shoemake's three-uniform form) from a splitmix64 stream
+// keyed by (seed, update count), evaluated in double and rounded once; trhost_get_ddgi_update_consts shows the block that ran.
 #include "CommonResources.h"
 #include "Graphic.h"
 #include "RenderGraph.h"
 #include "Scene.h"
 #include "VisibilityOutputs.h"
 #include "../ShaderInterop.h"
+
+#include <cmath>
+#include <cstring>
 
 using namespace interop;
 
@@ -115,6 +125,125 @@ public:
     enum { Positions = kPositions, DrawArgs = kDrawArgs, InstanceToProbe = kInstanceToProbe };
 };
 DEFINE_RENDERER(GIDebugRenderer);
+
+class GIRenderer : public IRenderer
+{
+    static double Uniform(uint64_t& state)                                     // splitmix64, 53 bits
+    {
+        uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        return (double)((z ^ (z >> 31)) >> 11) * (1.0 / 9007199254740992.0);
+    }
+
+    static void RandomRotation(uint32_t seed, uint32_t count, float rows[3][4])
+    {
+        uint64_t state = (uint64_t)seed << 32 | count;
+        const double kTwoPi = 6.28318530717958647692;
+        const double u1 = Uniform(state), u2 = Uniform(state), u3 = Uniform(state);
+        const double a = std::sqrt(1.0 - u1), b = std::sqrt(u1);
+        const double x = a * std::sin(kTwoPi * u2), y = a * std::cos(kTwoPi * u2), z = b * std::sin(kTwoPi * u3), w = b * std::cos(kTwoPi * u3);
+        const double m[3][3] = { { 1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w) },
+                                 { 2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w) },
+                                 { 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y) } };
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) rows[i][j] = (float)m[i][j];
+            rows[i][3] = 0.0f;
+        }
+    }
+
+public:
+    GIRenderer() : IRenderer("GIRenderer") {}
+
+    DDGIUpdateConsts m_LastConsts{};
+    bool m_bRanLastFrame = false;
+
+    bool Setup(RenderGraph& renderGraph) override
+    {
+        m_bRanLastFrame = false;
+        const Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+        if (!g_Scene->m_bDDGIUpdate || !g_Scene->m_bDeferredLighting || !volume.IsValid() || !volume.m_RayData || !g_Scene->m_TLAS || g_Scene->m_NumPrimitives == 0) return false;
+        renderGraph.AddExternalReadDependency(g_Scene->m_InstanceConstsBuffer.Get());
+        renderGraph.AddExternalWriteDependency(volume.m_ProbeIrradiance.Get());
+        renderGraph.AddExternalWriteDependency(volume.m_ProbeDistance.Get());
+        return true;
+    }
+
+    void Render(nvrhi::CommandListHandle commandList, const RenderGraph&) override
+    {
+        using Item = nvrhi::BindingSetItem;
+        const Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+        const nvrhi::rt::AccelStruct& as = *g_Scene->m_TLAS;
+        if (!GetScheduledShadowMaskTexture()) RecordRefitTLAS(commandList);   // ShadowMaskRenderer, scheduled in front, refits otherwise
+
+        struct Block { DDGIUpdateConsts k; DDGIVolumeDesc desc; } block{};
+        static_assert(sizeof(Block) == 160, "DDGIUpdateConsts + DDGIVolumeDesc");
+        DDGIUpdateConsts& k = block.k;
+        memcpy(k.m_DirectionalLightVector, g_Scene->m_DirLightVec, sizeof g_Scene->m_DirLightVec);   // GIRenderer.cpp: GIProbeTraceConsts
+        k.m_DirectionalLightStrength = g_Scene->m_DirLightStrength;
+        RandomRotation(g_Scene->m_DDGIUpdateSeed, g_Scene->m_DDGIUpdateCount++, k.rayRotation);
+        k.probeMaxRayDistance = 1e10f;                                        // :79 passes the scene's bounding radius; this mirror has none
+        k.probeHysteresis = 0.5f;                                             // :115
+        k.probeDistanceExponent = 50.0f;                                      // :118
+        k.probeIrradianceThreshold = 0.2f;                                    // :111
+        k.probeBrightnessThreshold = 0.1f;                                    // :112
+        block.desc = volume.m_Desc;
+        m_LastConsts = k;
+        m_bRanLastFrame = true;
+        nvrhi::BufferHandle cb = g_Graphic.CreateConstantBuffer(commandList, block);
+        const uint32_t cx = (uint32_t)volume.m_Desc.probeCounts[0], cy = (uint32_t)volume.m_Desc.probeCounts[1], cz = (uint32_t)volume.m_Desc.probeCounts[2];
+
+        Graphic::ComputePassParams trace;
+        trace.m_CommandList = commandList;
+        trace.m_ShaderName = "giprobetrace_CS_ProbeTrace";
+        trace.m_BindingSetDesc.bindings = {
+            Item::ConstantBuffer(0, cb),
+            Item::StructuredBuffer_SRV(0, volume.m_DescBuffer),
+            Item::Texture_SRV(1, volume.m_ProbeData),
+            Item::Texture_SRV(2, volume.m_ProbeIrradiance),
+            Item::Texture_SRV(3, volume.m_ProbeDistance),
+            Item::RayTracingAccelStruct(4, g_Scene->m_TLAS.get()),
+            Item::StructuredBuffer_SRV(5, g_Scene->m_InstanceConstsBuffer),
+            Item::StructuredBuffer_SRV(6, g_Graphic.m_GlobalVertexBuffer),
+            Item::StructuredBuffer_SRV(7, g_Graphic.m_GlobalMaterialDataBuffer),
+            Item::StructuredBuffer_SRV(8, g_Graphic.m_GlobalIndexBuffer),
+            Item::StructuredBuffer_SRV(9, g_Graphic.m_GlobalMeshDataBuffer),
+            Item::StructuredBuffer_SRV(10, as.instances),                     // the structure's other buffers (include/trhip.h)
+            Item::StructuredBuffer_SRV(11, as.blasHeaders),
+            Item::StructuredBuffer_SRV(12, as.blasNodes),
+            Item::StructuredBuffer_SRV(13, as.triOrder),
+            Item::StructuredBuffer_UAV(0, volume.m_RayData),
+            Item::Sampler(0, g_CommonResources.LinearClampSampler),           // accepted and ignored
+            Item::Sampler(1, g_CommonResources.LinearClampSampler),
+            Item::Sampler(2, g_CommonResources.LinearClampSampler),
+        };
+        trace.m_DispatchGroupSize = Vector3U{ kDDGIRaysPerProbe / 64, cx * cz, cy };          // groups of 64 rays: the pass's wave
+        g_Graphic.AddComputePass(trace);
+
+        for (int radiance = 1; radiance >= 0; --radiance) {
+            Graphic::ComputePassParams blend;
+            blend.m_CommandList = commandList;
+            blend.m_ShaderName = radiance ? "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1" : "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0";
+            blend.m_BindingSetDesc.bindings = {
+                Item::ConstantBuffer(0, cb),
+                Item::StructuredBuffer_SRV(1, volume.m_RayData),
+                Item::Texture_SRV(3, volume.m_ProbeData),
+                radiance ? Item::Texture_UAV(1, volume.m_ProbeIrradiance) : Item::Texture_UAV(2, volume.m_ProbeDistance),
+            };
+            blend.m_DispatchGroupSize = Vector3U{ cx, cz, cy };
+            g_Graphic.AddComputePass(blend);
+        }
+    }
+};
+DEFINE_RENDERER(GIRenderer);
+
+bool GetLastDDGIUpdateConsts(void* out96)
+{
+    const GIRenderer* r = static_cast<const GIRenderer*>(g_GIRenderer);
+    if (!g_Scene->m_bDDGIUpdate || !r->m_bRanLastFrame) return false;
+    memcpy(out96, &r->m_LastConsts, sizeof r->m_LastConsts);
+    return true;
+}
 
 bool GetGIProbeCullBuffers(nvrhi::BufferHandle* positions, nvrhi::BufferHandle* drawArgs, nvrhi::BufferHandle* instanceToProbe)
 {

@@ -114,6 +114,7 @@ void Graphic::Shutdown()
     m_GlobalMeshDataBuffer = nullptr;
     m_GlobalMeshletDataBuffer = nullptr;
     m_GlobalVertexBuffer = nullptr; m_GlobalMeshletVertexOffsetsBuffer = nullptr; m_GlobalMeshletIndicesBuffer = nullptr;
+    m_GlobalIndexBuffer = nullptr;                                            // Scene::LoadRaytracing's: left behind, the next session would release it after its device
     m_GlobalMaterialDataBuffer = nullptr;
     m_SrvUavCbvDescriptorTable = nullptr;
     m_Textures.clear();

@@ -24,6 +24,7 @@ extern IRenderer* g_BloomRenderer;
 extern IRenderer* g_AdaptLuminanceRenderer;
 extern IRenderer* g_PostProcessRenderer;
 extern IRenderer* g_GIDebugRenderer;
+extern IRenderer* g_GIRenderer;
 
 void View::Update()
 {
@@ -305,6 +306,7 @@ void Scene::Update()
         m_RenderGraph->AddRenderer(g_GBufferRenderer);
         if (m_bGBuffer && m_bEnableAO) m_RenderGraph->AddRenderer(g_AmbientOcclusionRenderer);   // :499
         if (m_bGBuffer && m_bEnableShadows) m_RenderGraph->AddRenderer(g_ShadowMaskRenderer);    // :500
+        if (m_bDeferredLighting && m_bDDGIUpdate) m_RenderGraph->AddRenderer(g_GIRenderer);      // behind the TLAS refit, in front of lighting
         if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
         if (m_bDeferredLighting && m_bEnableSky) m_RenderGraph->AddRenderer(g_SkyRenderer);  // :502
         if (m_bPostProcess && m_bEnableBloom) m_RenderGraph->AddRenderer(g_BloomRenderer);   // :503
@@ -329,7 +331,8 @@ void Scene::Shutdown()
     m_SyntheticDepth = nullptr;
     m_ShadowMaskTexture = nullptr;
     m_RTDDGIVolume = RTDDGIVolume{};
-    m_bEnableDDGI = false;
+    m_bEnableDDGI = m_bDDGIUpdate = false;
+    m_DDGIUpdateCount = 0;
     m_TLAS.reset();
     m_BlueNoise = nullptr;
     m_BloomTexture = nullptr;

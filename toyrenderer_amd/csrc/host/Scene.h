@@ -109,15 +109,21 @@ public:
     float m_DirLightVec[3] = { 0.0f, -1.0f, 0.0f };  // Scene.h:134-136: used as given (the reference derives it from two angles)
     float m_DirLightStrength = 1.0f;
     nvrhi::TextureHandle m_ShadowMaskTexture;        // R8_UNORM at render resolution, or null: the pass reads 1.0 (the reference's WhiteTexture)
-    // The DDGI volume DeferredLightingRenderer consumes (Scene.h: m_RTDDGIVolume, GIRenderer's in the reference).  Tracing and
-    // blending the probes is not built: trhost_upload_ddgi_volume supplies the descriptor and the three array textures.
+    // The DDGI volume DeferredLightingRenderer consumes (Scene.h: m_RTDDGIVolume, GIRenderer's in the reference).
+    // trhost_upload_ddgi_volume supplies the descriptor and the three array textures; with trhost_set_ddgi_update GIRenderer
+    // (GIRenderer.cpp) traces and blends the probes into them every frame, from what they hold.
     struct RTDDGIVolume
     {
         interop::DDGIVolumeDesc m_Desc{};            // the host copy, appended to the pass's constant block
         nvrhi::BufferHandle m_DescBuffer;            // t5
         nvrhi::TextureHandle m_ProbeData, m_ProbeIrradiance, m_ProbeDistance;   // t6, t7, t8
+        nvrhi::BufferHandle m_RayData;               // float4[numProbes * 256]: the trace's u0, the blends' t1
         bool IsValid() const { return m_DescBuffer && m_ProbeData && m_ProbeIrradiance && m_ProbeDistance; }
     } m_RTDDGIVolume;
+    // GIRenderer::RenderDDGI (trhost_set_ddgi_update; needs the volume, m_TLAS and m_bDeferredLighting): frame n's ray rotation
+    // comes from (m_DDGIUpdateSeed, m_DDGIUpdateCount = n); the settings are GIRenderer.cpp:111-118's.
+    bool m_bDDGIUpdate = false;
+    uint32_t m_DDGIUpdateSeed = 0, m_DDGIUpdateCount = 0;
     bool m_bEnableDDGI = false;                      // trhost_set_ddgi
     bool IsDDGIEnabled() const { return m_bEnableDDGI && m_RTDDGIVolume.IsValid(); }
     // Auto exposure and tone mapping (trhost_set_post_process; implies m_bDeferredLighting): AdaptLuminanceRenderer and

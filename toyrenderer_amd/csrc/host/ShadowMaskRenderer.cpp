@@ -24,6 +24,32 @@ using namespace interop;
 
 extern RenderGraph::ResourceHandle g_DepthStencilBufferRDGTextureHandle;
 
+// "raytracing_CS_RefitTLAS" on the instance buffer's current matrices: recorded by the first consumer of the structure in a frame
+// (this renderer, or GIRenderer when shadows are off).
+void RecordRefitTLAS(nvrhi::CommandListHandle commandList)
+{
+    using Item = nvrhi::BindingSetItem;
+    const nvrhi::rt::AccelStruct& as = *g_Scene->m_TLAS;
+    RefitTLASConstants k{ g_Scene->m_NumPrimitives, as.numNodes, as.numLevels };
+    Graphic::ComputePassParams p;
+    p.m_CommandList = commandList;
+    p.m_ShaderName = "raytracing_CS_RefitTLAS";
+    p.m_BindingSetDesc.bindings = {
+        Item::PushConstants(0, sizeof(k)),
+        Item::StructuredBuffer_SRV(0, g_Scene->m_InstanceConstsBuffer),
+        Item::StructuredBuffer_SRV(1, as.blasHeaders),
+        Item::StructuredBuffer_SRV(2, as.blasNodes),
+        Item::StructuredBuffer_SRV(3, as.levelOffsets),
+        Item::StructuredBuffer_SRV(4, as.levelNodes),
+        Item::StructuredBuffer_UAV(0, as.nodes),
+        Item::StructuredBuffer_UAV(1, as.instances),
+    };
+    p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Scene->m_NumPrimitives, 64);
+    p.m_PushConstantsData = &k;
+    p.m_PushConstantsBytes = sizeof(k);
+    g_Graphic.AddComputePass(p);
+}
+
 class ShadowMaskRenderer : public IRenderer
 {
 public:
@@ -67,26 +93,7 @@ public:
     {
         using Item = nvrhi::BindingSetItem;
         const nvrhi::rt::AccelStruct& as = *g_Scene->m_TLAS;
-        {                                                                     // the TLAS of this frame's matrices
-            RefitTLASConstants k{ g_Scene->m_NumPrimitives, as.numNodes, as.numLevels };
-            Graphic::ComputePassParams p;
-            p.m_CommandList = commandList;
-            p.m_ShaderName = "raytracing_CS_RefitTLAS";
-            p.m_BindingSetDesc.bindings = {
-                Item::PushConstants(0, sizeof(k)),
-                Item::StructuredBuffer_SRV(0, g_Scene->m_InstanceConstsBuffer),
-                Item::StructuredBuffer_SRV(1, as.blasHeaders),
-                Item::StructuredBuffer_SRV(2, as.blasNodes),
-                Item::StructuredBuffer_SRV(3, as.levelOffsets),
-                Item::StructuredBuffer_SRV(4, as.levelNodes),
-                Item::StructuredBuffer_UAV(0, as.nodes),
-                Item::StructuredBuffer_UAV(1, as.instances),
-            };
-            p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Scene->m_NumPrimitives, 64);
-            p.m_PushConstantsData = &k;
-            p.m_PushConstantsBytes = sizeof(k);
-            g_Graphic.AddComputePass(p);
-        }
+        RecordRefitTLAS(commandList);                                         // the TLAS of this frame's matrices
 
         const View& view = g_Scene->m_View;
         ShadowMaskConsts passConstants{};                                     // :264-274

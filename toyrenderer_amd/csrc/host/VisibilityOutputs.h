@@ -72,6 +72,10 @@ nvrhi::TextureHandle GetShadowMaskTexture();
 nvrhi::TextureHandle GetScheduledShadowMaskTexture();
 bool GetLastShadowMaskConsts(void* out112);
 void ReleaseShadowMaskOutputs();
+// the TLAS refit, recorded by the structure's first consumer in a frame (ShadowMaskRenderer.cpp)
+void RecordRefitTLAS(nvrhi::CommandListHandle commandList);
+// GIRenderer: the 96 bytes of DDGIUpdateConsts the last frame's probe update ran with (false if it did not run in it)
+bool GetLastDDGIUpdateConsts(void* out96);
 // The SkyPassParameters SkyRenderer uploaded in the last frame; false if the pass did not run in it.
 bool GetLastSkyConsts(void* out256);
 void ReleaseSkyOutputs();

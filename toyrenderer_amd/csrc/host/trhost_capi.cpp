@@ -7,6 +7,7 @@
 #include <cstring>
 #include <exception>
 #include <string>
+#include <vector>
 
 #include "../../../include/trhost.h"
 #include "Graphic.h"
@@ -229,7 +230,7 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
             if (g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient && g_Scene->m_bDeferredLighting)
                 throw nvrhi::Error("trhost_upload_ddgi_volume: debug view mode 10 (Ambient) is showing the DDGI volume");
             g_Scene->m_RTDDGIVolume = Scene::RTDDGIVolume{};
-            g_Scene->m_bEnableDDGI = false;
+            g_Scene->m_bEnableDDGI = g_Scene->m_bDDGIUpdate = false;
             return;
         }
         check(irradiance && distance && data);
@@ -253,6 +254,7 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
             desc.dimension = nvrhi::kTexture2DArray;
             desc.format = format;
             desc.debugName = name;
+            desc.isUAV = perProbe != 1;                                       // the two probe blends write irradiance and distance
             return g_Graphic.m_NVRHIDevice->createTexture(desc);
         };
         v.m_ProbeData = make(1, nvrhi::Format::RGBA16_FLOAT, "DDGI Probe Data");
@@ -267,7 +269,75 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
             nvrhi::throwIfFailed(trhip_texture_upload_slice(v.m_ProbeIrradiance->native(), s, (const char*)irradiance + s * irrSlice, irrSlice), "trhost_upload_ddgi_volume");
             nvrhi::throwIfFailed(trhip_texture_upload_slice(v.m_ProbeDistance->native(), s, (const char*)distance + s * distSlice, distSlice), "trhost_upload_ddgi_volume");
         }
+        {                                                                     // the ray data of GIRenderer::Setup, as float4 records; zero-filled
+            const uint64_t rayBytes = (uint64_t)cx * cy * cz * interop::kDDGIRaysPerProbe * 16;
+            nvrhi::BufferDesc rd;
+            rd.byteSize = rayBytes; rd.structStride = 16; rd.canHaveUAVs = true; rd.debugName = "DDGI Ray Data";
+            v.m_RayData = g_Graphic.m_NVRHIDevice->createBuffer(rd);
+            const std::vector<uint8_t> zeros(rayBytes, 0);
+            nvrhi::throwIfFailed(trhip_buffer_upload(v.m_RayData->native(), 0, zeros.data(), rayBytes), "trhost_upload_ddgi_volume");
+        }
         g_Scene->m_RTDDGIVolume = v;
+        g_Scene->m_DDGIUpdateCount = 0;
+    });
+}
+
+int trhost_set_ddgi_update(int enabled, uint32_t seed)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (enabled && !g_Scene->m_RTDDGIVolume.IsValid())
+            throw nvrhi::Error("trhost_set_ddgi_update: no DDGI volume (trhost_upload_ddgi_volume first): giprobetrace_CS_ProbeTrace and the probe blends have nothing to fill");
+        if (enabled && !g_Scene->m_TLAS)
+            throw nvrhi::Error("trhost_set_ddgi_update: no acceleration structure (trhost_load_raytracing first): giprobetrace_CS_ProbeTrace has nothing to trace");
+        g_Scene->m_bDDGIUpdate = enabled != 0;
+        g_Scene->m_DDGIUpdateSeed = seed;
+        g_Scene->m_DDGIUpdateCount = 0;
+    });
+}
+
+int trhost_reset_ddgi_volume(void)
+{
+    return guarded([&] {
+        check(g_Scene);
+        const Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        if (!v.IsValid()) throw nvrhi::Error("trhost_reset_ddgi_volume: no DDGI volume (trhost_upload_ddgi_volume first)");
+        g_Graphic.m_NVRHIDevice->waitForIdle();
+        const uint32_t cx = (uint32_t)v.m_Desc.probeCounts[0], cy = (uint32_t)v.m_Desc.probeCounts[1], cz = (uint32_t)v.m_Desc.probeCounts[2];
+        const uint64_t irrSlice = (uint64_t)cx * 8 * cz * 8 * 4, distSlice = (uint64_t)cx * 16 * cz * 16 * 4;
+        const std::vector<uint8_t> zeros(distSlice, 0);                       // GIRenderer.cpp:457-458: both cleared
+        for (uint32_t s = 0; s < cy; ++s) {
+            nvrhi::throwIfFailed(trhip_texture_upload_slice(v.m_ProbeIrradiance->native(), s, zeros.data(), irrSlice), "trhost_reset_ddgi_volume");
+            nvrhi::throwIfFailed(trhip_texture_upload_slice(v.m_ProbeDistance->native(), s, zeros.data(), distSlice), "trhost_reset_ddgi_volume");
+        }
+    });
+}
+
+int trhost_download_ddgi_volume(uint32_t* irradiance, uint64_t irradiance_bytes, uint16_t* distance, uint64_t distance_bytes, uint16_t* data, uint64_t data_bytes)
+{
+    return guarded([&] {
+        check(g_Scene);
+        const Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        if (!v.IsValid()) throw nvrhi::Error("trhost_download_ddgi_volume: no DDGI volume (trhost_upload_ddgi_volume first)");
+        check(irradiance && distance && data);
+        const uint32_t cx = (uint32_t)v.m_Desc.probeCounts[0], cy = (uint32_t)v.m_Desc.probeCounts[1], cz = (uint32_t)v.m_Desc.probeCounts[2];
+        const uint64_t irrSlice = (uint64_t)cx * 8 * cz * 8 * 4, distSlice = (uint64_t)cx * 16 * cz * 16 * 4, dataSlice = (uint64_t)cx * cz * 8;
+        if (irradiance_bytes != irrSlice * cy || distance_bytes != distSlice * cy || data_bytes != dataSlice * cy)
+            throw nvrhi::Error("trhost_download_ddgi_volume: the sizes do not match the probe counts (irradiance 8 x 8 x 4, distance 16 x 16 x 4, data 8 bytes per probe)");
+        g_Graphic.m_NVRHIDevice->waitForIdle();
+        for (uint32_t s = 0; s < cy; ++s) {
+            nvrhi::throwIfFailed(trhip_texture_download_slice(v.m_ProbeData->native(), s, (char*)data + s * dataSlice, dataSlice), "trhost_download_ddgi_volume");
+            nvrhi::throwIfFailed(trhip_texture_download_slice(v.m_ProbeIrradiance->native(), s, (char*)irradiance + s * irrSlice, irrSlice), "trhost_download_ddgi_volume");
+            nvrhi::throwIfFailed(trhip_texture_download_slice(v.m_ProbeDistance->native(), s, (char*)distance + s * distSlice, distSlice), "trhost_download_ddgi_volume");
+        }
+    });
+}
+
+int trhost_get_ddgi_update_consts(void* out96)
+{
+    return guarded([&] {
+        check(g_Scene && out96);
+        if (!GetLastDDGIUpdateConsts(out96)) throw nvrhi::Error("trhost_get_ddgi_update_consts: the last frame ran no probe update (trhost_set_ddgi_update, deferred lighting on)");
     });
 }
 

@@ -2,8 +2,8 @@
 // after GBufferRenderer (source/DeferredLightingRenderer.cpp, source/shaders/deferredlighting.hlsl; EvaluateDirectionalLight,
 // DefaultLitBxDF and UnpackGBuffer of lightingcommon.hlsli), with the shadow mask and the DDGI probe volume as inputs: the
 // directional light, the DDGI ambient term and the debug views, closed arithmetic on GBufferA, depth, the motion target, the SSAO
-// and the shadow-mask texels, plus the probe lookups of ddgi_irradiance.hip.h.  Tracing and blending the probes are out of scope
-// (DESIGN.md 12): the volume is supplied.  The sky is k_sky.hip's, the SSAO texture k_ambientocclusion.hip's, the shadow mask
+// and the shadow-mask texels, plus the probe lookups of ddgi_irradiance.hip.h.  The volume is an input here: supplied, or filled
+// by k_giprobetrace.hip and k_giprobeblend.hip in front of this pass.  The sky is k_sky.hip's, the SSAO texture k_ambientocclusion.hip's, the shadow mask
 // k_shadowmask.hip's.
 //
 // WHICH PIXELS: the reference draws where the stencil equals the opaque bit.  The stand-in: a pixel is written iff its depth
@@ -25,6 +25,7 @@
 //             resolution; unbound: 1.0f);
 //   EnvBRDFApprox: r4 = r * (-1, -0.0275f, -0.572f, 0.022f) + (1, 0.0425f, 1.04f, -0.04f); a004 = fmin(r4.x * r4.x,
 //             exp2(-9.28f * NdotV)) * r4.x + r4.y; AB = (-1.04f, 1.04f) * a004 + r4.zw; f0 * AB.x + AB.y;
+//   (PS_Main's directional light, EnvBRDFApprox and exp2 below are written in direct_light.hip.h, which the probe trace shares.)
 //   exp2:     v_exp_f32 is good to 1 ulp only and cannot be restated on a CPU, so it is software, for x <= 0: i = ceil(x),
 //             f = x - i in (-1, 0], a degree-7 Horner polynomial in fma, then ldexp(p, i).  ceil, not floor: with floor f = x + 1
 //             is inexact for -1 < x < 0; with ceil f is exact everywhere (|x| < 1: f = x; else x and i are multiples of ulp(x)
@@ -62,6 +63,7 @@
 
 #include "cull_math.hip.h"
 #include "ddgi_irradiance.hip.h"
+#include "direct_light.hip.h"
 #include "gbuffer_unpack.hip.h"
 #include "r11g11b10.hip.h"
 #include "screen_pass.hip.h"
@@ -95,61 +97,19 @@ struct LightingDdgiArgs                        // the <*, ddgi> instantiations: 
     ddgi::Textures probes;
 };
 
-// exp2 for x <= 0; coefficients and error analysis: tests/lighting_ref.c (kExp2C)
-__device__ __forceinline__ float exp2Soft(float x)
-{
-#ifdef TR_LIGHTING_EXPERIMENT_HW_EXP2          // negative control only (profiles/lighting/): the hardware's v_exp_f32
-    return __builtin_amdgcn_exp2f(x);
-#else
-    const float i = __builtin_ceilf(x), f = x - i;
-    float p = 0x1.7b4b46p-17f;
-    p = cm::fma_(p, f, 0x1.383ffcp-13f);
-    p = cm::fma_(p, f, 0x1.5ca2c2p-10f);
-    p = cm::fma_(p, f, 0x1.3b20d4p-7f);
-    p = cm::fma_(p, f, 0x1.c6b024p-5f);
-    p = cm::fma_(p, f, 0x1.ebfbdep-3f);
-    p = cm::fma_(p, f, 0x1.62e430p-1f);
-    p = cm::fma_(p, f, 1.0f);
-    return __builtin_ldexpf(p, (int)i);
-#endif
-}
-
 __device__ __forceinline__ float quickRandomFloat(uint32_t& seed)                                  // random.hlsli:7-11
 {
     seed = 1664525u * seed + 1013904223u;
     return (float)(seed & 0x00FFFFFFu) / 16777216.0f;
 }
 
+// EvaluateDirectionalLight with the camera as viewer: direct_light.hip.h, which the probe trace shares.
 __device__ __forceinline__ cm::F3 litPixel(const LightingArgs& a, const GBufferParams& p, uint32_t px, uint32_t py, float depth, float shadow)
 {
     const DeferredLightingConsts& k = a.k;
     const cm::F3 world = sp::worldPosition(k.m_ClipToWorld, px, py, k.m_LightingOutputResolution.x, k.m_LightingOutputResolution.y, depth);
-    const float oneMinusMetal = 1.0f - p.metallic, dielectric = 0.08f * 0.5f;
-    const cm::F3 diffuse = { p.albedo.x * oneMinusMetal, p.albedo.y * oneMinusMetal, p.albedo.z * oneMinusMetal };
-    const cm::F3 f0 = { dielectric + p.metallic * (p.albedo.x - dielectric), dielectric + p.metallic * (p.albedo.y - dielectric), dielectric + p.metallic * (p.albedo.z - dielectric) };
-    const cm::F3 V = normalize_({ k.m_CameraOrigin[0] - world.x, k.m_CameraOrigin[1] - world.y, k.m_CameraOrigin[2] - world.z });
-    const cm::F3 L = { k.m_DirectionalLightVector[0], k.m_DirectionalLightVector[1], k.m_DirectionalLightVector[2] };
-    const cm::F3 H = normalize_({ V.x + L.x, V.y + L.y, V.z + L.z });
-    const float NdotV = sp::saturate_(__builtin_fabsf(cm::dot3(p.normal, V)) + 1e-5f), NdotL = sp::saturate_(cm::dot3(p.normal, L));
-    const float NdotH = sp::saturate_(cm::dot3(p.normal, H)), VdotH = sp::saturate_(cm::dot3(V, H));
-    const float al = p.roughness * p.roughness, a2 = cm::min_(cm::max_(al * al, 0.0001f), 1.0f);
-    const float d = (NdotH * a2 - NdotH) * NdotH + 1.0f;                                            // D_GGX
-    const float D = cm::div_(a2, (0x1.921fb6p+1f * d) * d);
-    const float smithV = NdotL * (NdotV * (1.0f - a2) + a2), smithL = NdotV * (NdotL * (1.0f - a2) + a2);   // Vis_SmithJointApprox
-    const float Vis = 0.5f * cm::div_(1.0f, smithV + smithL);
-    const float x = 1.0f - VdotH, xx = x * x, Fc = (xx * xx) * x;                                   // F_Schlick
-    const float DVis = D * Vis;
-    const float r = p.roughness;                                                                    // EnvBRDFApprox
-    const float rx = r * -1.0f + 1.0f, ry = r * -0.0275f + 0.0425f, rz = r * -0.572f + 1.04f, rw = r * 0.022f + -0.04f;
-    const float a004 = cm::min_(rx * rx, exp2Soft(-9.28f * NdotV)) * rx + ry;
-    const float A = -1.04f * a004 + rz, B = 1.04f * a004 + rw;
-    const float strength = k.m_DirectionalLightStrength, kInvPi = 0x1.45f306p-2f;
-    auto channel = [&](float diff, float f0c, float emissive) {
-        const float F = Fc + (1.0f - Fc) * f0c;
-        const float spec = DVis * F + (f0c * A + B);
-        return (((diff * kInvPi + spec) * NdotL) * strength) * shadow + emissive;
-    };
-    return { channel(diffuse.x, f0.x, p.emissive.x), channel(diffuse.y, f0.y, p.emissive.y), channel(diffuse.z, f0.z, p.emissive.z) };
+    return dl::litSurface(p, { k.m_CameraOrigin[0], k.m_CameraOrigin[1], k.m_CameraOrigin[2] }, world,
+                          { k.m_DirectionalLightVector[0], k.m_DirectionalLightVector[1], k.m_DirectionalLightVector[2] }, k.m_DirectionalLightStrength, shadow);
 }
 
 __device__ __forceinline__ cm::F3 debugPixel(const LightingArgs& a, const GBufferParams& p, uint64_t i, float shadow)

@@ -49,6 +49,7 @@
 #include "cull_math.hip.h"
 #include "gbuffer_unpack.hip.h"
 #include "material_textures.hip.h"
+#include "ray_walk.hip.h"
 #include "screen_pass.hip.h"
 #include "soft_math.hip.h"
 
@@ -59,12 +60,13 @@ namespace
 
 using namespace interop;
 using cm::F3;
+using namespace rw;                            // Ray, makeRay, boxHit, triHit, sel, M34, mulPoint, vertexOf, SceneArgs: ray_walk.hip.h
 
 constexpr uint32_t kTileSide = 8;               // [numthreads(8, 8, 1)]
 constexpr uint32_t kRefitBlock = 64;
-constexpr float kSlack = 0x1p-18f, kTlasPad = 0x1p-12f, kFloatMax = 3.402823466e38f;
+constexpr float kTlasPad = 0x1p-12f;
 
-struct TraceArgs
+struct TraceTargets
 {
     ShadowMaskConsts k;
     const float* depth;                        // R32_FLOAT
@@ -72,25 +74,14 @@ struct TraceArgs
     const uint32_t* noise;                     // RGBA8_UNORM, 128 x 128
     uint8_t* mask;                             // R8_UNORM
     uint16_t* lvd;                             // R16_FLOAT
-    const BasePassInstanceConstants* instances; uint32_t numInstances;
-    const uint8_t* vertices; uint32_t numVertices;            // 20-byte stride
-    const uint8_t* materials; uint32_t numMaterials;          // 124-byte stride
-    const uint32_t* indices; uint32_t numIndices;
-    const uint8_t* meshes; uint32_t numMeshes;                // 156-byte stride
-    const trhip_accel_node* tlasNodes; uint32_t numTlasNodes;
-    const trhip_tlas_instance* tlasInstances;
-    const trhip_blas_header* headers;
-    const trhip_accel_node* blasNodes; uint32_t numBlasNodes;
-    const uint32_t* triOrder; uint32_t numTriOrder;
 };
+struct TraceArgs : TraceTargets, SceneArgs {}; // the members in the order they always had: the scene's pointers follow the targets
 
 // The TEXTURED instantiation's arguments: + the texture table bound at t19.
 struct TexturedTraceArgs : TraceArgs
 {
     const mtex::TableEntry* table; uint32_t tableCount;
 };
-
-__device__ __forceinline__ float sel(F3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
 
 // rows r0 r1 r2 r3 of p_object = (p_world, 1) * M, from the rows of m_WorldMatrix
 __device__ __forceinline__ void objectFromWorld(const float* w, float* out)
@@ -108,16 +99,6 @@ __device__ __forceinline__ void objectFromWorld(const float* w, float* out)
         for (int j = 0; j < 3; ++j) out[3 * i + j] = inv[i][j];
 #pragma unroll
     for (int j = 0; j < 3; ++j) out[9 + j] = -((t.x * inv[0][j] + t.y * inv[1][j]) + t.z * inv[2][j]);
-}
-
-struct M34 { float m[12]; };
-
-__device__ __forceinline__ F3 mulPoint(F3 p, const M34& M, bool translate)
-{
-    const float* m = M.m;
-    F3 r = { cm::fma_(p.z, m[6], cm::fma_(p.y, m[3], p.x * m[0])), cm::fma_(p.z, m[7], cm::fma_(p.y, m[4], p.x * m[1])), cm::fma_(p.z, m[8], cm::fma_(p.y, m[5], p.x * m[2])) };
-    if (translate) { r.x = r.x + m[9]; r.y = r.y + m[10]; r.z = r.z + m[11]; }
-    return r;
 }
 
 // ---- "raytracing_CS_RefitTLAS" --------------------------------------------------------------------------------------------------
@@ -222,64 +203,7 @@ int recordRefit(trhip::DispatchCtx& ctx)
     return TRHIP_OK;
 }
 
-// ---- the two tests (tests/shadowmask_ref.c: make_ray, sm_box_hit, sm_tri_hit) ---------------------------------------------------
-struct Ray { F3 o, d, inv; int kx, ky, kz; float Sx, Sy, Sz; };
-
-__device__ __forceinline__ Ray makeRay(F3 o, F3 d)
-{
-    Ray r;
-    r.o = o; r.d = d;
-    r.inv.x = cm::div_(1.0f, d.x); r.inv.y = cm::div_(1.0f, d.y); r.inv.z = cm::div_(1.0f, d.z);
-    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
-    int kz = 0;
-    float m = ax;
-    if (ay > m) { kz = 1; m = ay; }
-    if (az > m) { kz = 2; }
-    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
-    const float dz = sel(d, kz);
-    if (dz < 0.0f) { const int s = kx; kx = ky; ky = s; }
-    r.kx = kx; r.ky = ky; r.kz = kz;
-    r.Sx = cm::div_(sel(d, kx), dz); r.Sy = cm::div_(sel(d, ky), dz); r.Sz = cm::div_(1.0f, dz);
-    return r;
-}
-
-__device__ __forceinline__ bool boxHit(const trhip_accel_node& n, const Ray& r)
-{
-    float tenter = 0.0f, texit = __builtin_inff();
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float o = sel(r.o, a), inv = sel(r.inv, a);
-        if (!(__builtin_fabsf(inv) <= kFloatMax)) {
-            if (!(o >= n.lo[a] && o <= n.hi[a])) return false;
-        } else {
-            const float t0 = (n.lo[a] - o) * inv, t1 = (n.hi[a] - o) * inv;
-            float tn = cm::min_(t0, t1), tf = cm::max_(t0, t1);
-            tn = tn - __builtin_fabsf(tn) * kSlack; tf = tf + __builtin_fabsf(tf) * kSlack;
-            tenter = cm::max_(tenter, tn); texit = cm::min_(texit, tf);
-        }
-    }
-    return tenter <= texit;
-}
-
-// b1, b2 (TEXTURED only): the edge values of the second and third vertex over det, InterpolateVertex's barycentrics
-__device__ __forceinline__ bool triHit(F3 v0, F3 v1, F3 v2, const Ray& r, float tmin, float tmax, float* b1 = nullptr, float* b2 = nullptr)
-{
-    const F3 A = { v0.x - r.o.x, v0.y - r.o.y, v0.z - r.o.z }, B = { v1.x - r.o.x, v1.y - r.o.y, v1.z - r.o.z }, C = { v2.x - r.o.x, v2.y - r.o.y, v2.z - r.o.z };
-    const float Akz = sel(A, r.kz), Bkz = sel(B, r.kz), Ckz = sel(C, r.kz);
-    const float Ax = sel(A, r.kx) - r.Sx * Akz, Ay = sel(A, r.ky) - r.Sy * Akz;
-    const float Bx = sel(B, r.kx) - r.Sx * Bkz, By = sel(B, r.ky) - r.Sy * Bkz;
-    const float Cx = sel(C, r.kx) - r.Sx * Ckz, Cy = sel(C, r.ky) - r.Sy * Ckz;
-    const float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f)) return false;
-    const float det = (U + V) + W;
-    if (det == 0.0f) return false;
-    const float Az = r.Sz * Akz, Bz = r.Sz * Bkz, Cz = r.Sz * Ckz;
-    const float T = (U * Az + V * Bz) + W * Cz;
-    const float t = cm::div_(T, det);
-    if (b1) { *b1 = cm::div_(V, det); *b2 = cm::div_(W, det); }
-    return t > tmin && t < tmax;
-}
-
+// ---- the two tests (makeRay, boxHit, triHit) are ray_walk.hip.h's --------------------------------------------------------------
 __device__ __forceinline__ float fmod1(float x) { return x - __builtin_truncf(x); }
 
 __device__ __forceinline__ F3 mapToCone(float sx, float sy, F3 n, float radius)                     // shadowmask.hlsl:24-63
@@ -294,12 +218,6 @@ __device__ __forceinline__ F3 mapToCone(float sx, float sy, F3 n, float radius) 
     const F3 up = { zUp ? 0.0f : 1.0f, 0.0f, zUp ? 1.0f : 0.0f };
     const F3 t0 = gbuf::normalize_(cm::cross3(up, n)), t1 = cm::cross3(n, t0);
     return { (n.x + ux * t0.x) + uy * t1.x, (n.y + ux * t0.y) + uy * t1.y, (n.z + ux * t0.z) + uy * t1.z };
-}
-
-__device__ __forceinline__ F3 vertexOf(const TraceArgs& a, uint64_t i)
-{
-    const float* p = reinterpret_cast<const float*>(a.vertices + i * sizeof(RawVertexFormat));
-    return { p[0], p[1], p[2] };
 }
 
 // A candidate: the triangle's texture coordinates (packed half2) and the hit's barycentrics.  TEXTURED only.

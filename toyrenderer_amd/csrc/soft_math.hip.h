@@ -2,7 +2,7 @@
 // (k_postprocess.hip) and the sky pass (k_sky.hip; tests/sky_ref.c restates acosSoft word for word as sk_acos).
 // v_log_f32 and v_exp_f32 are good to 1 ulp only and cannot be restated on a CPU; these can, and tests/postprocess_ref.c
 // restates them word for word (pr_log2, pr_exp2) next to the derivation of the coefficients and of the error bounds.  The
-// lighting pass keeps its own exp2Soft (k_deferredlighting.hip): that one is proven for x <= 0 only and its words must not move.
+// lighting pass keeps its own exp2Soft (direct_light.hip.h): that one is proven for x <= 0 only and its words must not move.
 //
 //   log2Soft(x), x > 0 (the callers test; +inf gives +inf): a subnormal x is first scaled by 2^24 (exact).  The bits are split
 //             at sqrt(1/2): k = exponent, m in [0x1.6a09e6p-1, 0x1.6a09e6p+0), f = m - 1 (exact, Sterbenz), P the degree-9 Horner

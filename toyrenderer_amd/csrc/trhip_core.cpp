@@ -958,6 +958,36 @@ int trhip_cmd_copy_texture(trhip_cmdlist cl, trhip_texture dst, trhip_texture sr
     return TRHIP_OK;
 }
 
+// The Texture2DArray bindings that passes declare.  An array texture bound anywhere else is refused here, whatever the pass
+// would have made of it; one of another format than the declaration names is refused as well (format 0: the pass checks the
+// format itself, in its own words).  `pass` is compared over its own length, so one line covers an entry and its variants.
+struct ArrayBindingDecl { const char* pass; uint32_t type, slot, format; const char* formatName; };
+static const ArrayBindingDecl kArrayBindings[] = {
+    { "deferredlighting_PS_Main", TRHIP_BIND_TEXTURE_SRV, 6, 0, "" },      // and _Debug: probe data, irradiance, distance (k_deferredlighting.hip)
+    { "deferredlighting_PS_Main", TRHIP_BIND_TEXTURE_SRV, 7, 0, "" },
+    { "deferredlighting_PS_Main", TRHIP_BIND_TEXTURE_SRV, 8, 0, "" },
+    { "giprobetrace_CS_ProbeTrace", TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
+    { "giprobetrace_CS_ProbeTrace", TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_R10G10B10A2_UNORM, "R10G10B10A2_UNORM" },
+    { "giprobetrace_CS_ProbeTrace", TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_RG16_FLOAT, "RG16_FLOAT" },
+    { "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1", TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R10G10B10A2_UNORM, "R10G10B10A2_UNORM" },
+    { "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0", TRHIP_BIND_TEXTURE_UAV, 2, TRHIP_FORMAT_RG16_FLOAT, "RG16_FLOAT" },
+    { "ProbeBlendingCS_DDGIProbeBlendingCS", TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
+};
+
+static int checkArrayBinding(const char* name, const trhip_binding& b, const trhip_texture_t* t)
+{
+    const char kind = b.type == TRHIP_BIND_TEXTURE_UAV ? 'u' : 't';
+    for (const ArrayBindingDecl& d : kArrayBindings) {
+        if (d.type != b.type || d.slot != b.slot || strncmp(name, d.pass, strlen(d.pass)) != 0) continue;
+        if (d.format && t->format != d.format)
+            return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: the pass declares an %s array texture there", name, t->name.c_str(), kind, b.slot,
+                        d.formatName);
+        return TRHIP_OK;
+    }
+    return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: the pass declares no array texture there (deferredlighting_PS_Main and _Debug: t6..t8; "
+                                   "giprobetrace_CS_ProbeTrace: t1..t3; the probe blends: t3 and u1 (radiance) or u2 (distance))", name, t->name.c_str(), kind, b.slot);
+}
+
 static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_binding* b, uint32_t nb, const void* push, uint32_t pushBytes,
                           bool indirect, trhip_buffer args, uint32_t argsOff, uint32_t gx, uint32_t gy, uint32_t gz)
 {
@@ -987,10 +1017,8 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
             if (!t) return fail(TRHIP_ERR_INVALID, "dispatch(%s): binding %u has no texture", name, i);
             if (!t->ptr) return fail(TRHIP_ERR_STATE, "dispatch(%s): texture '%s' has no memory bound", name, t->name.c_str());
             if (b[i].type == TRHIP_BIND_TEXTURE_UAV && b[i].baseMip >= t->mips) return fail(TRHIP_ERR_INVALID, "dispatch(%s): UAV mip %u out of range", name, b[i].baseMip);
-            // the only pass that declares Texture2DArray bindings: the lighting pass's DDGI probe textures
-            if (t->arraySize && !(b[i].type == TRHIP_BIND_TEXTURE_SRV && b[i].slot >= 6u && b[i].slot <= 8u && strncmp(name, "deferredlighting_PS_Main", 24) == 0))
-                return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: only deferredlighting_PS_Main and deferredlighting_PS_Main_Debug declare array textures, at t6..t8",
-                            name, t->name.c_str(), b[i].type == TRHIP_BIND_TEXTURE_UAV ? 'u' : 't', b[i].slot);
+            if (t->arraySize)
+                if (const int rc = checkArrayBinding(name, b[i], t)) return rc;
             cl->hold(t, b[i].type == TRHIP_BIND_TEXTURE_UAV);
             break; }
         case TRHIP_BIND_TEXTURE_TABLE: {

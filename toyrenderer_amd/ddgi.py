@@ -1,8 +1,10 @@
 """The DDGI probe volume the deferred lighting pass consumes (csrc/ddgi_irradiance.hip.h): descriptor, the three probe
 textures as numpy arrays, and the helpers a caller needs to fill them.
 
-Tracing and blending probes is not part of this project yet: a Volume is an INPUT, filled by the caller (an engine's probe
-update, a bake, or Volume.uniform for a constant ambient).  Layout, coordinate system 0 (left-handed, Y up):
+A Volume is filled by the caller (an engine's probe update, a bake, or Volume.uniform for a constant ambient) or by the
+project's own probe update (FrameDriver(ddgi=volume, ddgi_update={...}): "giprobetrace_CS_ProbeTrace" and the two
+"ProbeBlendingCS_DDGIProbeBlendingCS" passes; csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip), which starts from the volume's arrays
+(Volume.reset() for the reference's cleared start).  Layout, coordinate system 0 (left-handed, Y up):
   irradiance  uint32 [counts.y, counts.z * 8, counts.x * 8]       R10G10B10A2_UNORM words, probe (x, y, z)'s tile at [y, z * 8, x * 8]
   distance    float16 [counts.y, counts.z * 16, counts.x * 16, 2]  (mean distance / 2, mean squared distance / 2)
   data        float16 [counts.y, counts.z, counts.x, 4]            xyz relocation offset in units of the spacing, w state (1 = inactive)
@@ -67,6 +69,39 @@ def pack_unorm10(texels) -> np.ndarray:
     return q[..., 0] | q[..., 1] << np.uint32(10) | q[..., 2] << np.uint32(20) | np.uint32(3 << 30)
 
 
+def random_rotation(rng) -> np.ndarray:
+    """A uniformly distributed rotation, float32 [3, 3], from rng (a numpy Generator): the unit quaternion of four normal draws.
+    Its rows are what DDGIUpdateConsts.rayRotation takes: a ray's direction becomes (row0 . d, row1 . d, row2 . d)."""
+    q = rng.normal(size=4)
+    x, y, z, w = q / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], np.float32)
+
+
+UPDATE_DEFAULTS = dict(seed=0, hysteresis=0.5, distance_exponent=50.0, irradiance_threshold=0.2, brightness_threshold=0.1,     # GIRenderer.cpp:111-118
+                       max_ray_distance=1e10)                                                                                # :79 passes the scene's bounding radius
+
+
+def check_update_settings(settings) -> dict:
+    """The probe update's settings with the defaults filled in (UPDATE_DEFAULTS); an unknown key or a value out of range raises."""
+    u = dict(UPDATE_DEFAULTS)
+    unknown = set(settings) - set(u)
+    if unknown:
+        raise ValueError(f"ddgi_update: unknown settings {sorted(unknown)}; known: {sorted(u)}")
+    u.update(settings)
+    u["seed"] = int(u["seed"])
+    if u["seed"] < 0:
+        raise ValueError("ddgi_update: seed must not be negative")
+    for name in ("hysteresis", "distance_exponent", "irradiance_threshold", "brightness_threshold", "max_ray_distance"):
+        u[name] = float(u[name])
+        if not (math.isfinite(u[name]) and u[name] >= 0.0):
+            raise ValueError(f"ddgi_update: {name} = {u[name]} is not finite and >= 0")
+    if u["hysteresis"] > 1.0:
+        raise ValueError(f"ddgi_update: hysteresis = {u['hysteresis']} is not in [0, 1]")
+    return u
+
+
 class Volume:
     def __init__(self, origin, spacing, counts, normal_bias: float, view_bias: float, gamma: float = DEFAULT_GAMMA, relocation: bool = True,
                  classification: bool = True):
@@ -110,6 +145,18 @@ class Volume:
         v.distance[..., 1] = np.float16(min(float(d) * float(d) * 2.0, 65504.0))
         return v
 
+    def reset(self) -> "Volume":
+        """Irradiance and distance cleared to zero words, as GIRenderer.cpp:457-458 clears them before the first update (the probe
+        data stays).  Returns self."""
+        self.irradiance[...] = 0
+        self.distance[...] = 0
+        return self
+
+    def copy(self) -> "Volume":
+        v = Volume(self.origin, self.spacing, self.counts, self.normal_bias, self.view_bias, self.gamma, self.relocation, self.classification)
+        v.irradiance, v.distance, v.data = self.irradiance.copy(), self.distance.copy(), self.data.copy()
+        return v
+
     def fill_borders(self) -> "Volume":
         fill_borders(self.irradiance, I.kDDGIIrradianceInteriorTexels)
         fill_borders(self.distance, I.kDDGIDistanceInteriorTexels)
@@ -140,15 +187,16 @@ class Volume:
         return np.ascontiguousarray(pos.reshape(-1, 3), f), np.ascontiguousarray(self.data[..., 3].astype(f).reshape(-1))
 
     # ---- device side ---------------------------------------------------------------------------------------------------
-    def upload(self, dev):
+    def upload(self, dev, uav: bool = False):
         """Creates and fills the descriptor buffer and the three array textures: (desc, data, irradiance, distance), what the
-        lighting pass binds at t5..t8.  The caller releases them."""
+        lighting pass binds at t5..t8.  uav: the irradiance and distance textures get the UAV bit, which the two probe blends
+        need to write them.  The caller releases them."""
         from . import rhi
         cx, cy, cz = self.counts
         desc = dev.buffer_from(self.desc().view(np.uint8), "DDGI Volume Desc", uav=False)
         data = dev.create_texture_array(cx, cz, cy, rhi.FORMAT_RGBA16_FLOAT, "DDGI Probe Data")
-        irr = dev.create_texture_array(cx * IRRADIANCE_TEXELS, cz * IRRADIANCE_TEXELS, cy, rhi.FORMAT_R10G10B10A2_UNORM, "DDGI Probe Irradiance")
-        dist = dev.create_texture_array(cx * DISTANCE_TEXELS, cz * DISTANCE_TEXELS, cy, rhi.FORMAT_RG16_FLOAT, "DDGI Probe Distance")
+        irr = dev.create_texture_array(cx * IRRADIANCE_TEXELS, cz * IRRADIANCE_TEXELS, cy, rhi.FORMAT_R10G10B10A2_UNORM, "DDGI Probe Irradiance", uav=uav)
+        dist = dev.create_texture_array(cx * DISTANCE_TEXELS, cz * DISTANCE_TEXELS, cy, rhi.FORMAT_RG16_FLOAT, "DDGI Probe Distance", uav=uav)
         for s in range(cy):
             data.upload_slice(s, self.data[s])
             irr.upload_slice(s, self.irradiance[s])

@@ -159,7 +159,7 @@ class FrameDriver:
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
                  bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
-                 shadows=None, alpha_test: bool = False, ddgi=None):
+                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -231,11 +231,20 @@ class FrameDriver:
         so depth, the HZB, the visibility buffer and everything resolved from it see through the cut-outs.  With shadows the
         trace binds the table too and a textured cut-out casts the shadow of its kept texels (mip 0).
         ddgi: None (the default) changes nothing: no ambient term, and debug_mode 10 (Ambient) is refused.  A ddgi.Volume (needs
-        lighting=True): the DDGI ambient term from a SUPPLIED probe volume (deferredlighting.hlsl:49-76; tracing and blending
-        the probes is not built, the caller fills the volume, e.g. ddgi.Volume.uniform).  The driver uploads the descriptor and
+        lighting=True): the DDGI ambient term from a SUPPLIED probe volume (deferredlighting.hlsl:49-76; the caller
+        fills the volume, e.g. ddgi.Volume.uniform, or ddgi_update= below lets it fill itself).  The driver uploads the descriptor and
         the three array textures at construction (self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance),
         binds them as the lighting pass's t5..t8 with the linear wrap sampler, sets m_bRTDDGIEnabled = 1 and appends the
-        descriptor's host copy to the constant block; debug_mode 10 then shows the irradiance."""
+        descriptor's host copy to the constant block; debug_mode 10 then shows the irradiance.
+        ddgi_update: None (the default) changes nothing: the volume stays as supplied.  A dict of settings (needs lighting=True, ddgi=
+        and GpuScene.set_raytracing()): GIRenderer::RenderDDGI, the volume fills itself.  Every record() records, behind the TLAS
+        refit (which then runs with or without shadows=) and in front of the lighting pass, "giprobetrace_CS_ProbeTrace" and the two
+        "ProbeBlendingCS_DDGIProbeBlendingCS" passes with a new ray rotation: ddgi.random_rotation(default_rng([seed, n])) for the
+        n-th record() (self.ddgi_updates counts them); the block they ran with is self.ddgi_update_consts.  Settings: seed (0),
+        hysteresis (0.5), distance_exponent (50), irradiance_threshold (0.2), brightness_threshold (0.1), max_ray_distance (1e10;
+        the reference passes the scene's bounding radius).  The probe textures are then created with the UAV bit, the volume's host
+        arrays are the INITIAL state (ddgi.Volume.reset() clears them as the reference does), and download_ddgi() reads the
+        current one back.  Relocation and classification are not built: the supplied data texture is honoured as it is."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -250,6 +259,14 @@ class FrameDriver:
         if ddgi is not None and not isinstance(ddgi, ddgimod.Volume):
             raise ValueError("ddgi: needs a ddgi.Volume")
         self.ddgi = ddgi
+        self.ddgi_update = self.ddgi_update_consts = None
+        self.ddgi_updates = 0
+        if ddgi_update is not None:
+            if not lighting or ddgi is None:
+                raise ValueError("ddgi_update=... needs lighting=True and ddgi=ddgi.Volume(...): the volume the update fills and the pass that reads it")
+            if scene.rt is None:
+                raise ValueError("ddgi_update=... needs GpuScene.set_raytracing(): the acceleration structure the probe rays walk")
+            self.ddgi_update = ddgimod.check_update_settings(ddgi_update)
         self.alpha_test = bool(alpha_test)
         if self.alpha_test and not (raster_depth or visibility):
             raise ValueError("alpha_test=True needs raster_depth=True (or visibility, gbuffer, lighting, post): the test runs in the rasters, and a frame without them draws nothing")
@@ -360,7 +377,11 @@ class FrameDriver:
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         self.ddgi_desc = self.ddgi_data = self.ddgi_irradiance = self.ddgi_distance = None
         if self.ddgi is not None:                    # GIRenderer::Setup's textures (GIRenderer.cpp:129-133), filled by the caller
-            self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance = self.ddgi.upload(dev)
+            self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance = self.ddgi.upload(dev, uav=self.ddgi_update is not None)
+        self.ddgi_rays = None
+        if self.ddgi_update is not None:             # the ray data of GIRenderer::Setup, as a structured buffer of float4 records
+            self.ddgi_rays = dev.create_buffer(int(np.prod(self.ddgi.counts)) * I.kDDGIRaysPerProbe * 16, "DDGI Ray Data", stride=16)
+            self.ddgi_rays.upload(np.zeros(self.ddgi_rays.size // 4, np.float32))     # an inactive probe's records keep what they hold
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
             self.gbufferA = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA32_UINT, "GBufferA")
         if self.visibility_on:                       # GBufferRenderer's visibility buffer + GBufferMotion, render resolution
@@ -570,14 +591,18 @@ class FrameDriver:
         return self.ssao_texture.download_mip(0)
 
     # ---- the TLAS refit (BasePassRenderers.cpp:159-160) + ShadowMaskRenderer::TraceShadows (ShadowMaskRenderer.cpp:253-305) ---------
-    def _shadow_mask(self, cl):
-        v, sc, W, H = self.view, self.scene, self.view.renderW, self.view.renderH
+    def _refit_tlas(self, cl):
+        sc = self.scene
         rt = sc.rt
         k = np.zeros(1, I.RefitTLASConstants)
         k["m_NumInstances"], k["m_NumNodes"], k["m_NumLevels"] = sc.numInstances, len(rt["tlas"]["nodes"]), rt["tlas"]["num_levels"]
         cl.dispatch("raytracing_CS_RefitTLAS",
                     [PUSH(0), SRV(0, sc.instances), SRV(1, rt["headers"]), SRV(2, rt["blas_nodes"]), SRV(3, rt["level_offsets"]), SRV(4, rt["level_nodes"]),
                      UAV(0, rt["tlas_nodes"]), UAV(1, rt["tlas_instances"])], (max((sc.numInstances + 63) // 64, 1), 1, 1), push=k)
+
+    def _shadow_mask(self, cl):
+        v, sc, W, H = self.view, self.scene, self.view.renderW, self.view.renderH
+        rt = sc.rt
         self.shadow_consts = accelmod.shadow_consts(I.clip_to_world(v.worldToView, v.viewToClip), self.dir_light[0], self.camera_origin, W, H, self.shadows,
                                                     self.frame_counter)
         cb = cl.constant_buffer(self.shadow_consts, "ShadowMaskConsts")
@@ -587,6 +612,48 @@ class FrameDriver:
                      TEX_UAV(1, self.linear_view_depth, 0), SRV(9, rt["tlas_instances"]), SRV(10, rt["headers"]), SRV(11, rt["blas_nodes"]),
                      SRV(12, rt["tri_order"]), SAMPLER(0), SAMPLER(1)] + ([TEX_TABLE(sc.texture_table)] if self.alpha_test and sc.textured else []),
                     ((W + 7) // 8, (H + 7) // 8, 1))
+
+    # ---- GIRenderer::RenderDDGI (GIRenderer.cpp): the probe trace and the two blends ---------------------------------------------
+    def _ddgi_update(self, cl):
+        sc, vol, u = self.scene, self.ddgi, self.ddgi_update
+        rt = sc.rt
+        k = np.zeros(1, I.DDGIUpdateConsts)
+        k["m_DirectionalLightVector"], k["m_DirectionalLightStrength"] = self.dir_light
+        k["rayRotation"][0, :, :3] = ddgimod.random_rotation(np.random.default_rng([u["seed"], self.ddgi_updates]))
+        k["probeMaxRayDistance"], k["probeHysteresis"], k["probeDistanceExponent"] = u["max_ray_distance"], u["hysteresis"], u["distance_exponent"]
+        k["probeIrradianceThreshold"], k["probeBrightnessThreshold"] = u["irradiance_threshold"], u["brightness_threshold"]
+        self.ddgi_update_consts = k
+        self.ddgi_updates += 1
+        cb = cl.constant_buffer(np.frombuffer(k.tobytes() + vol.desc().tobytes(), np.uint8), "DDGIUpdateConsts")
+        cx, cy, cz = vol.counts
+        cl.dispatch("giprobetrace_CS_ProbeTrace",
+                    [CB(0, cb), SRV(0, self.ddgi_desc), TEX_SRV(1, self.ddgi_data), TEX_SRV(2, self.ddgi_irradiance), TEX_SRV(3, self.ddgi_distance), SRV(4, rt["tlas_nodes"]),
+                     SRV(5, sc.instances), SRV(6, sc.vertices), SRV(7, sc.materials), SRV(8, sc.indices), SRV(9, sc.meshData), SRV(10, rt["tlas_instances"]),
+                     SRV(11, rt["headers"]), SRV(12, rt["blas_nodes"]), SRV(13, rt["tri_order"]), UAV(0, self.ddgi_rays), SAMPLER(0), SAMPLER(1), SAMPLER(2)],
+                    (I.kDDGIRaysPerProbe // 64, cx * cz, cy))
+        cl.dispatch("ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1",
+                    [CB(0, cb), SRV(1, self.ddgi_rays), TEX_SRV(3, self.ddgi_data), TEX_UAV(1, self.ddgi_irradiance, 0)], (cx, cz, cy))
+        cl.dispatch("ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0",
+                    [CB(0, cb), SRV(1, self.ddgi_rays), TEX_SRV(3, self.ddgi_data), TEX_UAV(2, self.ddgi_distance, 0)], (cx, cz, cy))
+
+    def download_ddgi(self):
+        """A copy of the driver's ddgi.Volume with the probe textures as they are on the device now."""
+        if self.ddgi is None:
+            raise ValueError("download_ddgi: there is no volume (ddgi=None)")
+        self.dev.wait_idle()
+        vol = self.ddgi.copy()
+        for s in range(vol.counts[1]):
+            vol.irradiance[s] = self.ddgi_irradiance.download_slice(s)
+            vol.distance[s] = self.ddgi_distance.download_slice(s).reshape(vol.distance[s].shape)
+            vol.data[s] = self.ddgi_data.download_slice(s).reshape(vol.data[s].shape)
+        return vol
+
+    def download_ddgi_rays(self) -> np.ndarray:
+        """The ray records of the last update, float32 [numProbes, 256, 4]."""
+        if self.ddgi_rays is None:
+            raise ValueError("download_ddgi_rays: the probe update is off (ddgi_update=None)")
+        self.dev.wait_idle()
+        return self.ddgi_rays.download(np.float32).reshape(-1, I.kDDGIRaysPerProbe, 4)
 
     def download_shadow_mask(self) -> np.ndarray:
         """The bytes of the generated shadow mask, (H, W) uint8."""
@@ -734,8 +801,12 @@ class FrameDriver:
             cl.end_pipeline_stats(query)
         if self.ao is not None:                                                          # Scene.cpp's order: behind GBufferRenderer, in front of lighting
             self._ambient_occlusion(cl)
+        if self.shadows is not None or self.ddgi_update is not None:                     # the TLAS of this frame's instance buffer
+            self._refit_tlas(cl)
         if self.shadows is not None:                                                     # Scene.cpp:500: behind AO, in front of lighting
             self._shadow_mask(cl)
+        if self.ddgi_update is not None:                                                 # behind the refit, in front of lighting
+            self._ddgi_update(cl)
         if self.lighting_on:
             self._deferred_lighting(cl)
         if self.sky is not None:                                                         # Scene.cpp:502: between lighting and bloom
@@ -780,6 +851,6 @@ class FrameDriver:
         self.hzb.release(); self.depth.release()
         for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
                   self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
-                  self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance):
+                  self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays):
             if t is not None:
                 t.release()

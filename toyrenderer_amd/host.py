@@ -30,6 +30,7 @@ HOST_SYMBOLS = [
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
     "trhost_get_deferred_lighting_consts", "trhost_upload_ddgi_volume", "trhost_set_ddgi",
+    "trhost_set_ddgi_update", "trhost_reset_ddgi_volume", "trhost_download_ddgi_volume", "trhost_get_ddgi_update_consts",
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
@@ -106,6 +107,10 @@ def load() -> C.CDLL:
     L.trhost_get_deferred_lighting_consts.argtypes = [vp]
     L.trhost_upload_ddgi_volume.argtypes = [vp, vp, u64, vp, u64, vp, u64]
     L.trhost_set_ddgi.argtypes = [C.c_int]
+    L.trhost_set_ddgi_update.argtypes = [C.c_int, C.c_uint32]
+    L.trhost_reset_ddgi_volume.argtypes = []
+    L.trhost_download_ddgi_volume.argtypes = [vp, u64, vp, u64, vp, u64]
+    L.trhost_get_ddgi_update_consts.argtypes = [vp]
     L.trhost_set_post_process.argtypes = [C.c_int]
     L.trhost_set_exposure.argtypes = [C.c_float, C.c_float]
     L.trhost_set_auto_exposure.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -367,6 +372,28 @@ class Renderer:
     def set_ddgi(self, on: bool = True):
         """Scene::IsDDGIEnabled(): the ambient term from the uploaded volume (needs upload_ddgi_volume)."""
         _check(load().trhost_set_ddgi(int(on)))
+
+    def set_ddgi_update(self, on: bool = True, seed: int = 0):
+        """GIRenderer::RenderDDGI: the probe trace and the two blends fill the uploaded volume every frame (needs upload_ddgi_volume,
+        load_raytracing and deferred lighting; include/trhost.h)."""
+        _check(load().trhost_set_ddgi_update(int(on), int(seed)))
+
+    def reset_ddgi_volume(self):
+        """Irradiance and distance cleared to zero words, the reference's start."""
+        _check(load().trhost_reset_ddgi_volume())
+
+    def download_ddgi_volume(self, volume):
+        """A copy of `volume` (the ddgi.Volume that was uploaded: its descriptor gives the shapes) with the three textures as the
+        device holds them now."""
+        v = volume.copy()
+        _check(load().trhost_download_ddgi_volume(v.irradiance.ctypes.data, v.irradiance.nbytes, v.distance.ctypes.data, v.distance.nbytes, v.data.ctypes.data, v.data.nbytes))
+        return v
+
+    def ddgi_update_consts(self) -> np.ndarray:
+        """The DDGIUpdateConsts of the last frame's probe update, the ray rotation among them; raises if none ran in it."""
+        k = np.zeros(1, I.DDGIUpdateConsts)
+        _check(load().trhost_get_ddgi_update_consts(k.ctypes.data))
+        return k
 
     def set_post_process(self, on: bool = True):
         """AdaptLuminanceRenderer and PostProcessRenderer after DeferredLightingRenderer (implies deferred lighting; include/trhost.h)."""

@@ -115,6 +115,11 @@ DDGIVolumeDesc = np.dtype([("origin", np.float32, (3,)), ("probeNormalBias", np.
                            ("numDistanceInteriorTexels", np.uint32), ("flags", np.uint32), ("pad", np.uint32)])
 kDDGIFlag_Relocation, kDDGIFlag_Classification = 1, 2
 kDDGIIrradianceInteriorTexels, kDDGIDistanceInteriorTexels, kDDGIMaxProbeCount = 6, 14, 1024
+# csrc/ShaderInterop.h: the project's own b0 of the probe trace and the two probe blends; the DDGIVolumeDesc follows it in b0
+DDGIUpdateConsts = np.dtype([("m_DirectionalLightVector", np.float32, (3,)), ("m_DirectionalLightStrength", np.float32), ("rayRotation", np.float32, (3, 4)),
+                             ("probeMaxRayDistance", np.float32), ("probeHysteresis", np.float32), ("probeDistanceExponent", np.float32),
+                             ("probeIrradianceThreshold", np.float32), ("probeBrightnessThreshold", np.float32), ("pad", np.uint32, (3,))])
+kDDGIRaysPerProbe, kDDGIBackfaceRayLimit = 256, 25
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
@@ -124,7 +129,7 @@ SIZES = {
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
     "BloomConsts": 16, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
     "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
-    "ShadowMaskConsts": 112, "DDGIVolumeDesc": 64, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
+    "ShadowMaskConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96,"RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)
