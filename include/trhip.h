@@ -139,6 +139,14 @@ uint32_t    trhip_abi_version(void);
  * direct dispatch of (4, counts.x * counts.z, counts.y) groups.  Blends: t1 the ray records, t3 the probe data, u1 the
  * irradiance (radiance blend) or u2 the distance (distance blend) array, created with the UAV bit; (counts.x, counts.z,
  * counts.y) groups.  An array texture is accepted only at a binding that a pass declares, in the declared format.
+ * "giprobetrace_CS_ProbeTraceFixedRays", "ProbeRelocationCS_DDGIProbeRelocationCS" and
+ * "ProbeClassificationCS_DDGIProbeClassificationCS" (GIRenderer.cpp:513-527: probe relocation and classification behind the blends;
+ * csrc/k_giprobeplacement.hip states the bindings and the arithmetic, tests/ddgi_placement_ref.c is the definition).  b0 of all
+ * three: the same 160 bytes.  Fixed rays: t0 the descriptor, t1 the probe data, t4..t6 and t8..t13 the scene and its structure in
+ * the trace's slots (no materials), u0 a structured buffer float[numProbes * 32]; a direct dispatch of ceil(numProbes * 32 / 64)
+ * groups.  Relocation, classification: u0 those distances, u3 (texture) the RGBA16_FLOAT data array, created with the UAV bit; a
+ * direct dispatch of ceil(numProbes / 32) groups; refused unless the descriptor's flags have bit 0 (relocation) or bit 1
+ * (classification).
  * "adaptluminance_CS_GenerateLuminanceHistogram" (adaptluminance.hlsl, AdaptLuminanceRenderer.cpp): a direct dispatch of
  * [numthreads(16, 16, 1)] groups covering m_SrcColorDims; push constants GenerateLuminanceHistogramParameters (16 bytes), t0
  * (texture) the R11G11B10_FLOAT colour, u0 a structured UAV of at least 256 uint32.  It ADDS to u0: the caller clears it.

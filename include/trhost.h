@@ -137,8 +137,17 @@ int  trhost_set_ddgi(int enable);
  * trhost_reset_ddgi_volume clears irradiance and distance to zero words, the reference's start (GIRenderer.cpp:457-458);
  * trhost_download_ddgi_volume reads the three textures back in trhost_upload_ddgi_volume's layout;
  * trhost_get_ddgi_update_consts copies the 96 bytes of DDGIUpdateConsts (csrc/ShaderInterop.h) the last frame's update ran with,
- * the rotation among them, and fails if no update ran in it. */
+ * the rotation among them, and fails if no update ran in it.
+ * trhost_set_ddgi_probe_placement(relocation, classification, min_frontface_distance, fixed_ray_backface_threshold): the reference's
+ * probe relocation and classification (GIRenderer.cpp:80-83, :513-527), off by default here.  With either on, every update records
+ * behind the blends "giprobetrace_CS_ProbeTraceFixedRays" (32 unrotated rays from every probe, active or not) and then
+ * "ProbeRelocationCS_DDGIProbeRelocationCS" and / or "ProbeClassificationCS_DDGIProbeClassificationCS", which rewrite the data
+ * texture's xyz (offsets in units of the spacing) and w (1: switched off); the lighting pass of the same frame reads the new data.
+ * The reference's values are 0.1 (scene radius below 3) or 0.3, and 0.25; they show in trhost_get_ddgi_update_consts' bytes 84..91,
+ * which are 0 while both passes are off.  It needs the volume, and each pass its flag in the volume's descriptor; uploading a
+ * volume whose flags do not allow what was set switches both off. */
 int  trhost_set_ddgi_update(int enabled, uint32_t seed);
+int  trhost_set_ddgi_probe_placement(int relocation, int classification, float min_frontface_distance, float fixed_ray_backface_threshold);
 int  trhost_reset_ddgi_volume(void);
 int  trhost_download_ddgi_volume(uint32_t* irradiance, uint64_t irradiance_bytes, uint16_t* distance, uint64_t distance_bytes, uint16_t* data, uint64_t data_bytes);
 int  trhost_get_ddgi_update_consts(void* out96);

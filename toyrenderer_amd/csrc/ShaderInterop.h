@@ -154,8 +154,8 @@ static_assert(sizeof(DDGIVolumeDesc) == 64 && offsetof(DDGIVolumeDesc, probeSpac
 static constexpr uint32_t kDDGIFlag_Relocation = 1u, kDDGIFlag_Classification = 2u;
 static constexpr uint32_t kDDGIIrradianceInteriorTexels = 6, kDDGIDistanceInteriorTexels = 14, kDDGIMaxProbeCount = 1024;
 
-// The project's own: b0 of "giprobetrace_CS_ProbeTrace" and of the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes
-// (k_giprobetrace.hip, k_giprobeblend.hip).  It begins with the reference's GIProbeTraceConsts (ShaderInterop.h:243-247) and
+// The project's own: b0 of "giprobetrace_CS_ProbeTrace", of the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes and of the three
+// placement passes (k_giprobetrace.hip, k_giprobeblend.hip, k_giprobeplacement.hip).  It begins with the reference's GIProbeTraceConsts (ShaderInterop.h:243-247) and
 // goes on with what the SDK keeps in its volume descriptor and this project's 64-byte DDGIVolumeDesc does not hold: the frame's
 // ray rotation (rows of a 3 x 3 matrix, rotated = (dot3(row0, d), dot3(row1, d), dot3(row2, d))) and the update's settings.
 // Defaults: GIRenderer.cpp:79 (the scene's bounding radius), :111-118.  The passes read the volume's descriptor from a host copy
@@ -170,12 +170,16 @@ struct DDGIUpdateConsts
     float probeDistanceExponent;             // 50
     float probeIrradianceThreshold;          // 0.2
     float probeBrightnessThreshold;          // 0.1
-    uint32_t pad[3];
+    float probeMinFrontfaceDistance;         // relocation and classification (k_giprobeplacement.hip): 0.1 for a scene radius below 3, else 0.3
+    float probeFixedRayBackfaceThreshold;    // 0.25 (GIRenderer.cpp:121); both are 0 when neither of the two passes is on
+    uint32_t pad;
 };
 static_assert(sizeof(DDGIUpdateConsts) == 96 && offsetof(DDGIUpdateConsts, rayRotation) == 16 && offsetof(DDGIUpdateConsts, probeMaxRayDistance) == 64 &&
-              offsetof(DDGIUpdateConsts, probeBrightnessThreshold) == 80, "DDGIUpdateConsts");
+              offsetof(DDGIUpdateConsts, probeBrightnessThreshold) == 80 && offsetof(DDGIUpdateConsts, probeMinFrontfaceDistance) == 84 &&
+              offsetof(DDGIUpdateConsts, probeFixedRayBackfaceThreshold) == 88, "DDGIUpdateConsts");
 static constexpr uint32_t kDDGIRaysPerProbe = 256;              // RTXGI_DDGI_BLEND_RAYS_PER_PROBE
 static constexpr uint32_t kDDGIBackfaceRayLimit = 25;           // (uint)(256 * probeRandomRayBackfaceThreshold), 0.1f: GIRenderer.cpp:120
+static constexpr uint32_t kDDGIFixedRays = 32;                  // RTXGI_DDGI_NUM_FIXED_RAYS: the unrotated rays of relocation and classification
 
 // ShaderInterop.h:124-129: push constants of "adaptluminance_CS_GenerateLuminanceHistogram"
 struct GenerateLuminanceHistogramParameters

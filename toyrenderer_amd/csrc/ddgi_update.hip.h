@@ -1,6 +1,7 @@
-// ddgi_update.hip.h -- what "giprobetrace_CS_ProbeTrace" (k_giprobetrace.hip) and the two "ProbeBlendingCS_DDGIProbeBlendingCS"
-// passes (k_giprobeblend.hip) share: the constant block, a probe's coordinates and position, a ray's direction, the octahedral
-// decode, and the record-time checks of the block and of the probe textures.  The RTXGI SDK is not part of this project; this is
+// ddgi_update.hip.h -- what "giprobetrace_CS_ProbeTrace" (k_giprobetrace.hip), the two "ProbeBlendingCS_DDGIProbeBlendingCS"
+// passes (k_giprobeblend.hip) and the three placement passes (k_giprobeplacement.hip) share: the constant block, a probe's
+// coordinates and position, a ray's direction (of the 256 and of the 32 fixed ones), the octahedral decode, and the record-time
+// checks of the block, of the probe textures, of the scene's buffers and of the fixed-ray distances.  The RTXGI SDK is not part of this project; this is
 // the project's own statement of the published update (Majercik et al., JCGT 2019) and tests/ddgi_update_ref.c restates it word
 // for word.  The query's conventions (ddgi_irradiance.hip.h) hold here too: binary32, no contraction, fma only in dot3 and the
 // polynomials, / and sqrt correctly rounded.
@@ -18,6 +19,7 @@
 
 #include "cull_math.hip.h"
 #include "ddgi_irradiance.hip.h"
+#include "ray_walk.hip.h"
 #include "screen_pass.hip.h"
 #include "soft_math.hip.h"
 
@@ -68,6 +70,16 @@ __device__ __forceinline__ cm::F3 rayDirection(uint32_t i, const interop::DDGIUp
     return ddgi::normalize(r);
 }
 
+// Fixed ray i of kDDGIFixedRays = 32, the rays of relocation and classification (k_giprobeplacement.hip): rayDirection's formula
+// with 32 in place of 256 and no rotation (d itself is normalised, not its product with a matrix).
+__device__ __forceinline__ cm::F3 fixedRayDirection(uint32_t i)
+{
+    const float f = (float)i * 0.618034f, phi = 0x1.921fb6p+2f * (f - __builtin_floorf(f));
+    const float c = 1.0f - cm::div_((float)(2u * i + 1u), (float)interop::kDDGIFixedRays), s = cm::sqrt_(sp::saturate_(1.0f - c * c));
+    const cm::F3 d = { softmath::cosSoft(phi) * s, softmath::sinSoft(phi) * s, c };
+    return ddgi::normalize(d);
+}
+
 __device__ __forceinline__ cm::F3 octDecode(float ox, float oy)
 {
     cm::F3 v = { ox, oy, (1.0f - __builtin_fabsf(ox)) - __builtin_fabsf(oy) };
@@ -113,6 +125,61 @@ inline int requireProbeTexture(const trhip::DispatchCtx& ctx, uint32_t type, uin
     TRHIP_REQUIRE(t->width == tw && t->height == th && t->arraySize == (uint32_t)D.probeCounts[1], "%s: %s is %ux%u with %u slices; probeCounts (%d, %d, %d) need %ux%u with %d slices", name, what,
                   t->width, t->height, t->arraySize, D.probeCounts[0], D.probeCounts[1], D.probeCounts[2], tw, th, D.probeCounts[1]);
     TRHIP_REQUIRE(type != TRHIP_BIND_TEXTURE_UAV || t->isUAV, "%s: %s was created without the UAV bit; the pass writes it", name, what);
+    return TRHIP_OK;
+}
+
+// The scene and its acceleration structure in the probe trace's slots: t4 the TLAS nodes, t5 instances, t6 vertices, t7 materials
+// (asked for only where the pass shades its hits), t8 indices, t9 mesh data, t10 TLAS instances, t11 BLAS headers, t12 BLAS nodes,
+// t13 triangle order.
+inline int requireScene(const trhip::DispatchCtx& ctx, bool materials, rw::SceneArgs& s)
+{
+    const char* name = ctx.shaderName;
+    struct WantBuf { uint32_t slot, stride; const char* what; };
+    const WantBuf wantBuf[] = { { 4, sizeof(trhip_accel_node), "t4 = the TLAS nodes" }, { 5, sizeof(interop::BasePassInstanceConstants), "t5 = the instances" },
+                                { 6, sizeof(interop::RawVertexFormat), "t6 = the vertices" }, { 7, sizeof(interop::MaterialData), "t7 = the materials" }, { 8, 4, "t8 = the indices" },
+                                { 9, sizeof(interop::MeshData), "t9 = the mesh data" }, { 10, sizeof(trhip_tlas_instance), "t10 = the TLAS instances" },
+                                { 11, sizeof(trhip_blas_header), "t11 = the BLAS headers" }, { 12, sizeof(trhip_accel_node), "t12 = the BLAS nodes" },
+                                { 13, 4, "t13 = the triangle order" } };
+    trhip_buffer_t* buf[10] = {};
+    uint32_t count[10] = {};
+    for (int j = 0; j < 10; ++j) {
+        if (wantBuf[j].slot == 7 && !materials) continue;
+        buf[j] = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, wantBuf[j].slot);
+        TRHIP_REQUIRE(buf[j], "%s: needs StructuredBuffer_SRV %s", name, wantBuf[j].what);
+        const uint64_t n = buf[j]->byteSize / wantBuf[j].stride;
+        count[j] = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
+    }
+    s.tlasNodes = (const trhip_accel_node*)buf[0]->ptr; s.numTlasNodes = count[0];
+    s.instances = (const interop::BasePassInstanceConstants*)buf[1]->ptr; s.numInstances = count[1] < count[6] ? count[1] : count[6];
+    s.vertices = (const uint8_t*)buf[2]->ptr; s.numVertices = count[2];
+    s.materials = materials ? (const uint8_t*)buf[3]->ptr : nullptr; s.numMaterials = count[3];
+    s.indices = (const uint32_t*)buf[4]->ptr; s.numIndices = count[4];
+    s.meshes = (const uint8_t*)buf[5]->ptr; s.numMeshes = count[5] < count[7] ? count[5] : count[7];
+    s.tlasInstances = (const trhip_tlas_instance*)buf[6]->ptr;
+    s.headers = (const trhip_blas_header*)buf[7]->ptr;
+    s.blasNodes = (const trhip_accel_node*)buf[8]->ptr; s.numBlasNodes = count[8];
+    s.triOrder = (const uint32_t*)buf[9]->ptr; s.numTriOrder = count[9];
+    return TRHIP_OK;
+}
+
+// ---- what the three placement passes share (k_giprobeplacement.hip) --------------------------------------------------------------
+// u0 of all three: the fixed-ray distances, float[numProbes * 32]
+inline int requireFixedRayDistances(const trhip::DispatchCtx& ctx, uint32_t probes, float*& out)
+{
+    const char* name = ctx.shaderName;
+    trhip_buffer_t* d = ctx.buffer(TRHIP_BIND_STRUCTURED_UAV, 0);
+    TRHIP_REQUIRE(d, "%s: needs StructuredBuffer_UAV u0 = the fixed-ray distances, float[numProbes * 32]", name);
+    TRHIP_REQUIRE(d->byteSize == (uint64_t)probes * interop::kDDGIFixedRays * sizeof(float), "%s: the fixed-ray distances at u0 hold %llu bytes; %u probes of 32 floats are %llu", name,
+                  (unsigned long long)d->byteSize, probes, (unsigned long long)probes * interop::kDDGIFixedRays * sizeof(float));
+    out = (float*)d->ptr;
+    return TRHIP_OK;
+}
+
+// A direct dispatch of (ceil(threads / perGroup), 1, 1) groups
+inline int requireLinearDispatch(const trhip::DispatchCtx& ctx, uint64_t threads, uint32_t perGroup, const char* what)
+{
+    const uint32_t groups = (uint32_t)((threads + perGroup - 1) / perGroup);
+    TRHIP_REQUIRE(!ctx.indirect && ctx.gx == groups && ctx.gy == 1 && ctx.gz == 1, "%s: needs a direct dispatch of (%s, 1, 1) = (%u, 1, 1) groups", ctx.shaderName, what, groups);
     return TRHIP_OK;
 }
 

@@ -9,8 +9,10 @@
 // And GIRenderer (source/GIRenderer.cpp: RenderDDGI): the probe update of Scene::m_RTDDGIVolume, "giprobetrace_CS_ProbeTrace" and
 // the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes (csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip), behind the TLAS refit and
 // in front of DeferredLightingRenderer.  The RTXGI SDK is not part of this project: the passes are the project's own, with one
-// constant block (DDGIUpdateConsts, the descriptor's host copy behind it).  Relocation, classification and variability are not
-// built.  The frame's ray rotation is a uniformly distributed rotation (Shoemake's three-uniform form) from a splitmix64 stream
+// constant block (DDGIUpdateConsts, the descriptor's host copy behind it).  With trhost_set_ddgi_probe_placement the reference's
+// relocation and classification (:513-527) follow the blends: "giprobetrace_CS_ProbeTraceFixedRays", the project's own trace of 32
+// unrotated rays from every probe, then "ProbeRelocationCS_DDGIProbeRelocationCS" and "ProbeClassificationCS_DDGIProbeClassificationCS"
+// (csrc/k_giprobeplacement.hip).  Variability is not built.  The frame's ray rotation is a uniformly distributed rotation (Shoemake's three-uniform form) from a splitmix64 stream
 // keyed by (seed, update count), evaluated in double and rounded once; trhost_get_ddgi_update_consts shows the block that ran.
 #include "CommonResources.h"
 #include "Graphic.h"
@@ -166,6 +168,7 @@ public:
         renderGraph.AddExternalReadDependency(g_Scene->m_InstanceConstsBuffer.Get());
         renderGraph.AddExternalWriteDependency(volume.m_ProbeIrradiance.Get());
         renderGraph.AddExternalWriteDependency(volume.m_ProbeDistance.Get());
+        if (g_Scene->m_bDDGIProbeRelocation || g_Scene->m_bDDGIProbeClassification) renderGraph.AddExternalWriteDependency(volume.m_ProbeData.Get());
         return true;
     }
 
@@ -187,6 +190,11 @@ public:
         k.probeDistanceExponent = 50.0f;                                      // :118
         k.probeIrradianceThreshold = 0.2f;                                    // :111
         k.probeBrightnessThreshold = 0.1f;                                    // :112
+        const bool placement = g_Scene->m_bDDGIProbeRelocation || g_Scene->m_bDDGIProbeClassification;
+        if (placement) {                                                      // both stay 0 when neither pass runs
+            k.probeMinFrontfaceDistance = g_Scene->m_DDGIMinFrontfaceDistance;
+            k.probeFixedRayBackfaceThreshold = g_Scene->m_DDGIFixedRayBackfaceThreshold;
+        }
         block.desc = volume.m_Desc;
         m_LastConsts = k;
         m_bRanLastFrame = true;
@@ -232,6 +240,42 @@ public:
             };
             blend.m_DispatchGroupSize = Vector3U{ cx, cz, cy };
             g_Graphic.AddComputePass(blend);
+        }
+        if (!placement) return;
+
+        const uint32_t numProbes = cx * cy * cz;                              // :513-527: relocation and classification behind the blends
+        Graphic::ComputePassParams fixed;
+        fixed.m_CommandList = commandList;
+        fixed.m_ShaderName = "giprobetrace_CS_ProbeTraceFixedRays";
+        fixed.m_BindingSetDesc.bindings = {
+            Item::ConstantBuffer(0, cb),
+            Item::StructuredBuffer_SRV(0, volume.m_DescBuffer),
+            Item::Texture_SRV(1, volume.m_ProbeData),
+            Item::RayTracingAccelStruct(4, g_Scene->m_TLAS.get()),
+            Item::StructuredBuffer_SRV(5, g_Scene->m_InstanceConstsBuffer),
+            Item::StructuredBuffer_SRV(6, g_Graphic.m_GlobalVertexBuffer),
+            Item::StructuredBuffer_SRV(8, g_Graphic.m_GlobalIndexBuffer),
+            Item::StructuredBuffer_SRV(9, g_Graphic.m_GlobalMeshDataBuffer),
+            Item::StructuredBuffer_SRV(10, as.instances),
+            Item::StructuredBuffer_SRV(11, as.blasHeaders),
+            Item::StructuredBuffer_SRV(12, as.blasNodes),
+            Item::StructuredBuffer_SRV(13, as.triOrder),
+            Item::StructuredBuffer_UAV(0, volume.m_FixedRayData),
+        };
+        fixed.m_DispatchGroupSize = Vector3U{ (numProbes * kDDGIFixedRays + 63) / 64, 1, 1 };
+        g_Graphic.AddComputePass(fixed);
+        for (int relocation = 1; relocation >= 0; --relocation) {
+            if (!(relocation ? g_Scene->m_bDDGIProbeRelocation : g_Scene->m_bDDGIProbeClassification)) continue;
+            Graphic::ComputePassParams place;
+            place.m_CommandList = commandList;
+            place.m_ShaderName = relocation ? "ProbeRelocationCS_DDGIProbeRelocationCS" : "ProbeClassificationCS_DDGIProbeClassificationCS";
+            place.m_BindingSetDesc.bindings = {
+                Item::ConstantBuffer(0, cb),
+                Item::StructuredBuffer_UAV(0, volume.m_FixedRayData),
+                Item::Texture_UAV(3, volume.m_ProbeData),
+            };
+            place.m_DispatchGroupSize = Vector3U{ (numProbes + 31) / 32, 1, 1 };   // the reference's group count
+            g_Graphic.AddComputePass(place);
         }
     }
 };

@@ -331,7 +331,7 @@ void Scene::Shutdown()
     m_SyntheticDepth = nullptr;
     m_ShadowMaskTexture = nullptr;
     m_RTDDGIVolume = RTDDGIVolume{};
-    m_bEnableDDGI = m_bDDGIUpdate = false;
+    m_bEnableDDGI = m_bDDGIUpdate = m_bDDGIProbeRelocation = m_bDDGIProbeClassification = false;
     m_DDGIUpdateCount = 0;
     m_TLAS.reset();
     m_BlueNoise = nullptr;

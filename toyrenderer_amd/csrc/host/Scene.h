@@ -118,12 +118,17 @@ public:
         nvrhi::BufferHandle m_DescBuffer;            // t5
         nvrhi::TextureHandle m_ProbeData, m_ProbeIrradiance, m_ProbeDistance;   // t6, t7, t8
         nvrhi::BufferHandle m_RayData;               // float4[numProbes * 256]: the trace's u0, the blends' t1
+        nvrhi::BufferHandle m_FixedRayData;          // float[numProbes * 32]: u0 of the fixed-ray trace, of relocation and of classification
         bool IsValid() const { return m_DescBuffer && m_ProbeData && m_ProbeIrradiance && m_ProbeDistance; }
     } m_RTDDGIVolume;
     // GIRenderer::RenderDDGI (trhost_set_ddgi_update; needs the volume, m_TLAS and m_bDeferredLighting): frame n's ray rotation
     // comes from (m_DDGIUpdateSeed, m_DDGIUpdateCount = n); the settings are GIRenderer.cpp:111-118's.
     bool m_bDDGIUpdate = false;
     uint32_t m_DDGIUpdateSeed = 0, m_DDGIUpdateCount = 0;
+    // trhost_set_ddgi_probe_placement: GIRenderer.cpp:513-527's relocation and classification behind the blends (off by default; the
+    // reference's :80-83 switch both on), with probeMinFrontfaceDistance (:98, :106) and probeFixedRayBackfaceThreshold (:121).
+    bool m_bDDGIProbeRelocation = false, m_bDDGIProbeClassification = false;
+    float m_DDGIMinFrontfaceDistance = 0.3f, m_DDGIFixedRayBackfaceThreshold = 0.25f;
     bool m_bEnableDDGI = false;                      // trhost_set_ddgi
     bool IsDDGIEnabled() const { return m_bEnableDDGI && m_RTDDGIVolume.IsValid(); }
     // Auto exposure and tone mapping (trhost_set_post_process; implies m_bDeferredLighting): AdaptLuminanceRenderer and

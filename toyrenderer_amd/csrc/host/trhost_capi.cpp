@@ -230,7 +230,7 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
             if (g_Scene->m_DebugViewMode == interop::kDeferredLightingDebugMode_Ambient && g_Scene->m_bDeferredLighting)
                 throw nvrhi::Error("trhost_upload_ddgi_volume: debug view mode 10 (Ambient) is showing the DDGI volume");
             g_Scene->m_RTDDGIVolume = Scene::RTDDGIVolume{};
-            g_Scene->m_bEnableDDGI = g_Scene->m_bDDGIUpdate = false;
+            g_Scene->m_bEnableDDGI = g_Scene->m_bDDGIUpdate = g_Scene->m_bDDGIProbeRelocation = g_Scene->m_bDDGIProbeClassification = false;
             return;
         }
         check(irradiance && distance && data);
@@ -254,7 +254,7 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
             desc.dimension = nvrhi::kTexture2DArray;
             desc.format = format;
             desc.debugName = name;
-            desc.isUAV = perProbe != 1;                                       // the two probe blends write irradiance and distance
+            desc.isUAV = true;                                                // the blends write irradiance and distance, relocation and classification the data
             return g_Graphic.m_NVRHIDevice->createTexture(desc);
         };
         v.m_ProbeData = make(1, nvrhi::Format::RGBA16_FLOAT, "DDGI Probe Data");
@@ -277,6 +277,16 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
             const std::vector<uint8_t> zeros(rayBytes, 0);
             nvrhi::throwIfFailed(trhip_buffer_upload(v.m_RayData->native(), 0, zeros.data(), rayBytes), "trhost_upload_ddgi_volume");
         }
+        {                                                                     // the distances of every probe's 32 fixed rays; zero-filled
+            const uint64_t bytes = (uint64_t)cx * cy * cz * interop::kDDGIFixedRays * 4;
+            nvrhi::BufferDesc fd;
+            fd.byteSize = bytes; fd.structStride = 4; fd.canHaveUAVs = true; fd.debugName = "DDGI Fixed Ray Distances";
+            v.m_FixedRayData = g_Graphic.m_NVRHIDevice->createBuffer(fd);
+            const std::vector<uint8_t> zeros(bytes, 0);
+            nvrhi::throwIfFailed(trhip_buffer_upload(v.m_FixedRayData->native(), 0, zeros.data(), bytes), "trhost_upload_ddgi_volume");
+        }
+        if ((g_Scene->m_bDDGIProbeRelocation && !(d.flags & interop::kDDGIFlag_Relocation)) || (g_Scene->m_bDDGIProbeClassification && !(d.flags & interop::kDDGIFlag_Classification)))
+            g_Scene->m_bDDGIProbeRelocation = g_Scene->m_bDDGIProbeClassification = false;     // the new volume's flags do not allow what was set
         g_Scene->m_RTDDGIVolume = v;
         g_Scene->m_DDGIUpdateCount = 0;
     });
@@ -293,6 +303,27 @@ int trhost_set_ddgi_update(int enabled, uint32_t seed)
         g_Scene->m_bDDGIUpdate = enabled != 0;
         g_Scene->m_DDGIUpdateSeed = seed;
         g_Scene->m_DDGIUpdateCount = 0;
+    });
+}
+
+int trhost_set_ddgi_probe_placement(int relocation, int classification, float min_frontface_distance, float fixed_ray_backface_threshold)
+{
+    return guarded([&] {
+        check(g_Scene);
+        const Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        if ((relocation || classification) && !v.IsValid())
+            throw nvrhi::Error("trhost_set_ddgi_probe_placement: no DDGI volume (trhost_upload_ddgi_volume first): ProbeRelocationCS_DDGIProbeRelocationCS and "
+                               "ProbeClassificationCS_DDGIProbeClassificationCS have no probes to place");
+        if (relocation && !(v.m_Desc.flags & interop::kDDGIFlag_Relocation))
+            throw nvrhi::Error("trhost_set_ddgi_probe_placement: the volume's flags have relocation (bit 0) off: nothing would read what ProbeRelocationCS_DDGIProbeRelocationCS writes");
+        if (classification && !(v.m_Desc.flags & interop::kDDGIFlag_Classification))
+            throw nvrhi::Error("trhost_set_ddgi_probe_placement: the volume's flags have classification (bit 1) off: nothing would read what ProbeClassificationCS_DDGIProbeClassificationCS writes");
+        if (!(min_frontface_distance >= 0.0f && min_frontface_distance <= 3.402823466e38f) || !(fixed_ray_backface_threshold >= 0.0f && fixed_ray_backface_threshold <= 1.0f))
+            throw nvrhi::Error("trhost_set_ddgi_probe_placement: min_frontface_distance must be finite and >= 0, fixed_ray_backface_threshold in [0, 1]");
+        g_Scene->m_bDDGIProbeRelocation = relocation != 0;
+        g_Scene->m_bDDGIProbeClassification = classification != 0;
+        g_Scene->m_DDGIMinFrontfaceDistance = min_frontface_distance;
+        g_Scene->m_DDGIFixedRayBackfaceThreshold = fixed_ray_backface_threshold;
     });
 }
 

@@ -13,7 +13,7 @@
 //
 // CONVENTION (binary32, no contraction, fma only where written, / and sqrt correctly rounded).  Per (ray i, probe p):
 //   probe     position and state as ddgi_update.hip.h has them; with flags bit 1 a probe whose data.w == 1.0f traces nothing and its
-//             256 records keep what they held (fixed rays exist for relocation and classification only, which are not built);
+//             256 records keep what they held (the 32 fixed rays that can wake it are a pass of their own, k_giprobeplacement.hip);
 //   ray       origin the probe, direction ddgiu::rayDirection(i), TMin 0, TMax probeMaxRayDistance; rw::closestHit (ray_walk.hip.h);
 //   miss      record (1, 1, 1, 1e27f) (giprobetrace.hlsl:67: the sky's radiance is the reference's own TODO);
 //   back face record (0, 0, 0, -0.2f * t);
@@ -138,31 +138,7 @@ int recordProbeTrace(trhip::DispatchCtx& ctx)
     TRHIP_REQUIRE(rays, "%s: needs StructuredBuffer_UAV u0 = the ray records, float4[numProbes * 256]", name);
     TRHIP_REQUIRE(rays->byteSize == (uint64_t)probes * kDDGIRaysPerProbe * sizeof(float4), "%s: the ray records at u0 hold %llu bytes; %u probes of 256 float4 records are %llu", name,
                   (unsigned long long)rays->byteSize, probes, (unsigned long long)probes * kDDGIRaysPerProbe * sizeof(float4));
-    struct WantBuf { uint32_t slot, stride; const char* what; };
-    const WantBuf wantBuf[] = { { 4, sizeof(trhip_accel_node), "t4 = the TLAS nodes" }, { 5, sizeof(BasePassInstanceConstants), "t5 = the instances" },
-                                { 6, sizeof(RawVertexFormat), "t6 = the vertices" }, { 7, sizeof(MaterialData), "t7 = the materials" }, { 8, 4, "t8 = the indices" },
-                                { 9, sizeof(MeshData), "t9 = the mesh data" }, { 10, sizeof(trhip_tlas_instance), "t10 = the TLAS instances" },
-                                { 11, sizeof(trhip_blas_header), "t11 = the BLAS headers" }, { 12, sizeof(trhip_accel_node), "t12 = the BLAS nodes" },
-                                { 13, 4, "t13 = the triangle order" } };
-    trhip_buffer_t* buf[10] = {};
-    uint32_t count[10] = {};
-    for (int j = 0; j < 10; ++j) {
-        buf[j] = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, wantBuf[j].slot);
-        TRHIP_REQUIRE(buf[j], "%s: needs StructuredBuffer_SRV %s", name, wantBuf[j].what);
-        const uint64_t n = buf[j]->byteSize / wantBuf[j].stride;
-        count[j] = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
-    }
-    rw::SceneArgs& s = a.scene;
-    s.tlasNodes = (const trhip_accel_node*)buf[0]->ptr; s.numTlasNodes = count[0];
-    s.instances = (const BasePassInstanceConstants*)buf[1]->ptr; s.numInstances = count[1] < count[6] ? count[1] : count[6];
-    s.vertices = (const uint8_t*)buf[2]->ptr; s.numVertices = count[2];
-    s.materials = (const uint8_t*)buf[3]->ptr; s.numMaterials = count[3];
-    s.indices = (const uint32_t*)buf[4]->ptr; s.numIndices = count[4];
-    s.meshes = (const uint8_t*)buf[5]->ptr; s.numMeshes = count[5] < count[7] ? count[5] : count[7];
-    s.tlasInstances = (const trhip_tlas_instance*)buf[6]->ptr;
-    s.headers = (const trhip_blas_header*)buf[7]->ptr;
-    s.blasNodes = (const trhip_accel_node*)buf[8]->ptr; s.numBlasNodes = count[8];
-    s.triOrder = (const uint32_t*)buf[9]->ptr; s.numTriOrder = count[9];
+    if (const int rc = ddgiu::requireScene(ctx, true, a.scene)) return rc;
     ddgi::Textures& p = a.probes;
     p.desc = (const DDGIVolumeDesc*)descBuffer->ptr;
     p.data = (const uint2*)data->ptr; p.irradiance = (const uint32_t*)irr->ptr; p.distance = (const uint32_t*)dist->ptr;

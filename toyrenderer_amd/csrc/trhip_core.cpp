@@ -960,7 +960,8 @@ int trhip_cmd_copy_texture(trhip_cmdlist cl, trhip_texture dst, trhip_texture sr
 
 // The Texture2DArray bindings that passes declare.  An array texture bound anywhere else is refused here, whatever the pass
 // would have made of it; one of another format than the declaration names is refused as well (format 0: the pass checks the
-// format itself, in its own words).  `pass` is compared over its own length, so one line covers an entry and its variants.
+// format itself, in its own words).  `pass` is compared over its own length and must end there or go on with ' ' or '_', so one
+// line covers an entry and its variants ("..._Debug", "... RTXGI_DDGI_BLEND_RADIANCE=1") and no pass whose name merely begins alike.
 struct ArrayBindingDecl { const char* pass; uint32_t type, slot, format; const char* formatName; };
 static const ArrayBindingDecl kArrayBindings[] = {
     { "deferredlighting_PS_Main", TRHIP_BIND_TEXTURE_SRV, 6, 0, "" },      // and _Debug: probe data, irradiance, distance (k_deferredlighting.hip)
@@ -972,20 +973,25 @@ static const ArrayBindingDecl kArrayBindings[] = {
     { "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1", TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R10G10B10A2_UNORM, "R10G10B10A2_UNORM" },
     { "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0", TRHIP_BIND_TEXTURE_UAV, 2, TRHIP_FORMAT_RG16_FLOAT, "RG16_FLOAT" },
     { "ProbeBlendingCS_DDGIProbeBlendingCS", TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
+    { "giprobetrace_CS_ProbeTraceFixedRays", TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },      // k_giprobeplacement.hip
+    { "ProbeRelocationCS_DDGIProbeRelocationCS", TRHIP_BIND_TEXTURE_UAV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
+    { "ProbeClassificationCS_DDGIProbeClassificationCS", TRHIP_BIND_TEXTURE_UAV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
 };
 
 static int checkArrayBinding(const char* name, const trhip_binding& b, const trhip_texture_t* t)
 {
     const char kind = b.type == TRHIP_BIND_TEXTURE_UAV ? 'u' : 't';
     for (const ArrayBindingDecl& d : kArrayBindings) {
-        if (d.type != b.type || d.slot != b.slot || strncmp(name, d.pass, strlen(d.pass)) != 0) continue;
+        const size_t n = strlen(d.pass);
+        if (d.type != b.type || d.slot != b.slot || strncmp(name, d.pass, n) != 0 || (name[n] != '\0' && name[n] != ' ' && name[n] != '_')) continue;
         if (d.format && t->format != d.format)
             return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: the pass declares an %s array texture there", name, t->name.c_str(), kind, b.slot,
                         d.formatName);
         return TRHIP_OK;
     }
     return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: the pass declares no array texture there (deferredlighting_PS_Main and _Debug: t6..t8; "
-                                   "giprobetrace_CS_ProbeTrace: t1..t3; the probe blends: t3 and u1 (radiance) or u2 (distance))", name, t->name.c_str(), kind, b.slot);
+                                   "giprobetrace_CS_ProbeTrace: t1..t3; the probe blends: t3 and u1 (radiance) or u2 (distance); giprobetrace_CS_ProbeTraceFixedRays: t1; "
+                                   "probe relocation and classification: u3)", name, t->name.c_str(), kind, b.slot);
 }
 
 static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_binding* b, uint32_t nb, const void* push, uint32_t pushBytes,

@@ -4,7 +4,8 @@ textures as numpy arrays, and the helpers a caller needs to fill them.
 A Volume is filled by the caller (an engine's probe update, a bake, or Volume.uniform for a constant ambient) or by the
 project's own probe update (FrameDriver(ddgi=volume, ddgi_update={...}): "giprobetrace_CS_ProbeTrace" and the two
 "ProbeBlendingCS_DDGIProbeBlendingCS" passes; csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip), which starts from the volume's arrays
-(Volume.reset() for the reference's cleared start).  Layout, coordinate system 0 (left-handed, Y up):
+(Volume.reset() for the reference's cleared start).  With ddgi_update=dict(relocate=True, classify=True) the update also moves the
+probes off the geometry and switches off the ones that light nothing: it rewrites `data` (csrc/k_giprobeplacement.hip).  Layout, coordinate system 0 (left-handed, Y up):
   irradiance  uint32 [counts.y, counts.z * 8, counts.x * 8]       R10G10B10A2_UNORM words, probe (x, y, z)'s tile at [y, z * 8, x * 8]
   distance    float16 [counts.y, counts.z * 16, counts.x * 16, 2]  (mean distance / 2, mean squared distance / 2)
   data        float16 [counts.y, counts.z, counts.x, 4]            xyz relocation offset in units of the spacing, w state (1 = inactive)
@@ -80,7 +81,10 @@ def random_rotation(rng) -> np.ndarray:
 
 
 UPDATE_DEFAULTS = dict(seed=0, hysteresis=0.5, distance_exponent=50.0, irradiance_threshold=0.2, brightness_threshold=0.1,     # GIRenderer.cpp:111-118
-                       max_ray_distance=1e10)                                                                                # :79 passes the scene's bounding radius
+                       max_ray_distance=1e10,                                                                                # :79 passes the scene's bounding radius
+                       relocate=False, classify=False,                # :80-83 switches both on; here they are options
+                       min_frontface_distance=0.3,                    # :98, :106: 0.1 for a scene radius below 3, else 0.3
+                       fixed_ray_backface_threshold=0.25)             # :121
 
 
 def check_update_settings(settings) -> dict:
@@ -93,12 +97,15 @@ def check_update_settings(settings) -> dict:
     u["seed"] = int(u["seed"])
     if u["seed"] < 0:
         raise ValueError("ddgi_update: seed must not be negative")
-    for name in ("hysteresis", "distance_exponent", "irradiance_threshold", "brightness_threshold", "max_ray_distance"):
+    u["relocate"], u["classify"] = bool(u["relocate"]), bool(u["classify"])
+    for name in ("hysteresis", "distance_exponent", "irradiance_threshold", "brightness_threshold", "max_ray_distance", "min_frontface_distance",
+                 "fixed_ray_backface_threshold"):
         u[name] = float(u[name])
         if not (math.isfinite(u[name]) and u[name] >= 0.0):
             raise ValueError(f"ddgi_update: {name} = {u[name]} is not finite and >= 0")
-    if u["hysteresis"] > 1.0:
-        raise ValueError(f"ddgi_update: hysteresis = {u['hysteresis']} is not in [0, 1]")
+    for name in ("hysteresis", "fixed_ray_backface_threshold"):
+        if u[name] > 1.0:
+            raise ValueError(f"ddgi_update: {name} = {u[name]} is not in [0, 1]")
     return u
 
 
@@ -187,14 +194,15 @@ class Volume:
         return np.ascontiguousarray(pos.reshape(-1, 3), f), np.ascontiguousarray(self.data[..., 3].astype(f).reshape(-1))
 
     # ---- device side ---------------------------------------------------------------------------------------------------
-    def upload(self, dev, uav: bool = False):
+    def upload(self, dev, uav: bool = False, data_uav: bool = False):
         """Creates and fills the descriptor buffer and the three array textures: (desc, data, irradiance, distance), what the
         lighting pass binds at t5..t8.  uav: the irradiance and distance textures get the UAV bit, which the two probe blends
-        need to write them.  The caller releases them."""
+        need to write them; data_uav: the data texture gets it, which probe relocation and classification need.  The caller
+        releases them."""
         from . import rhi
         cx, cy, cz = self.counts
         desc = dev.buffer_from(self.desc().view(np.uint8), "DDGI Volume Desc", uav=False)
-        data = dev.create_texture_array(cx, cz, cy, rhi.FORMAT_RGBA16_FLOAT, "DDGI Probe Data")
+        data = dev.create_texture_array(cx, cz, cy, rhi.FORMAT_RGBA16_FLOAT, "DDGI Probe Data", uav=data_uav)
         irr = dev.create_texture_array(cx * IRRADIANCE_TEXELS, cz * IRRADIANCE_TEXELS, cy, rhi.FORMAT_R10G10B10A2_UNORM, "DDGI Probe Irradiance", uav=uav)
         dist = dev.create_texture_array(cx * DISTANCE_TEXELS, cz * DISTANCE_TEXELS, cy, rhi.FORMAT_RG16_FLOAT, "DDGI Probe Distance", uav=uav)
         for s in range(cy):

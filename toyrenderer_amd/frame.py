@@ -244,7 +244,15 @@ class FrameDriver:
         hysteresis (0.5), distance_exponent (50), irradiance_threshold (0.2), brightness_threshold (0.1), max_ray_distance (1e10;
         the reference passes the scene's bounding radius).  The probe textures are then created with the UAV bit, the volume's host
         arrays are the INITIAL state (ddgi.Volume.reset() clears them as the reference does), and download_ddgi() reads the
-        current one back.  Relocation and classification are not built: the supplied data texture is honoured as it is."""
+        current one back.  relocate (False) and classify (False) add GIRenderer.cpp:513-527's probe placement behind the blends:
+        "giprobetrace_CS_ProbeTraceFixedRays" (32 unrotated rays from EVERY probe into self.ddgi_fixed_rays; recorded when either is
+        on), then "ProbeRelocationCS_DDGIProbeRelocationCS" (rewrites data.xyz: probes leave the geometry) and
+        "ProbeClassificationCS_DDGIProbeClassificationCS" (rewrites data.w: probes that see mostly back faces, or nothing within a
+        cell, are switched off and wake up when that changes), with min_frontface_distance (0.3; the reference takes 0.1 for a
+        scene radius below 3) and fixed_ray_backface_threshold (0.25).  Each needs its flag on the volume (ddgi.Volume(relocation=,
+        classification=), on by default) and gives the data texture the UAV bit; the lighting pass of the same frame sees the new
+        data; download_ddgi_fixed_rays() reads the distances back.  With both off the supplied data texture is honoured as it is
+        and the update records what it recorded before (csrc/k_giprobeplacement.hip)."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -267,6 +275,9 @@ class FrameDriver:
             if scene.rt is None:
                 raise ValueError("ddgi_update=... needs GpuScene.set_raytracing(): the acceleration structure the probe rays walk")
             self.ddgi_update = ddgimod.check_update_settings(ddgi_update)
+            for option, flag, word in (("relocate", ddgi.relocation, "relocation"), ("classify", ddgi.classification, "classification")):
+                if self.ddgi_update[option] and not flag:
+                    raise ValueError(f"ddgi_update: {option}=True needs ddgi.Volume({word}=True): with the flag off nothing reads what the pass writes")
         self.alpha_test = bool(alpha_test)
         if self.alpha_test and not (raster_depth or visibility):
             raise ValueError("alpha_test=True needs raster_depth=True (or visibility, gbuffer, lighting, post): the test runs in the rasters, and a frame without them draws nothing")
@@ -376,12 +387,16 @@ class FrameDriver:
         if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         self.ddgi_desc = self.ddgi_data = self.ddgi_irradiance = self.ddgi_distance = None
+        placement = self.ddgi_update is not None and (self.ddgi_update["relocate"] or self.ddgi_update["classify"])
         if self.ddgi is not None:                    # GIRenderer::Setup's textures (GIRenderer.cpp:129-133), filled by the caller
-            self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance = self.ddgi.upload(dev, uav=self.ddgi_update is not None)
-        self.ddgi_rays = None
+            self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance = self.ddgi.upload(dev, uav=self.ddgi_update is not None, data_uav=placement)
+        self.ddgi_rays = self.ddgi_fixed_rays = None
         if self.ddgi_update is not None:             # the ray data of GIRenderer::Setup, as a structured buffer of float4 records
             self.ddgi_rays = dev.create_buffer(int(np.prod(self.ddgi.counts)) * I.kDDGIRaysPerProbe * 16, "DDGI Ray Data", stride=16)
             self.ddgi_rays.upload(np.zeros(self.ddgi_rays.size // 4, np.float32))     # an inactive probe's records keep what they hold
+            if placement:                            # the distances of the 32 fixed rays of every probe
+                self.ddgi_fixed_rays = dev.create_buffer(int(np.prod(self.ddgi.counts)) * I.kDDGIFixedRays * 4, "DDGI Fixed Ray Distances", stride=4)
+                self.ddgi_fixed_rays.upload(np.zeros(self.ddgi_fixed_rays.size // 4, np.float32))
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
             self.gbufferA = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA32_UINT, "GBufferA")
         if self.visibility_on:                       # GBufferRenderer's visibility buffer + GBufferMotion, render resolution
@@ -622,6 +637,8 @@ class FrameDriver:
         k["rayRotation"][0, :, :3] = ddgimod.random_rotation(np.random.default_rng([u["seed"], self.ddgi_updates]))
         k["probeMaxRayDistance"], k["probeHysteresis"], k["probeDistanceExponent"] = u["max_ray_distance"], u["hysteresis"], u["distance_exponent"]
         k["probeIrradianceThreshold"], k["probeBrightnessThreshold"] = u["irradiance_threshold"], u["brightness_threshold"]
+        if u["relocate"] or u["classify"]:
+            k["probeMinFrontfaceDistance"], k["probeFixedRayBackfaceThreshold"] = u["min_frontface_distance"], u["fixed_ray_backface_threshold"]
         self.ddgi_update_consts = k
         self.ddgi_updates += 1
         cb = cl.constant_buffer(np.frombuffer(k.tobytes() + vol.desc().tobytes(), np.uint8), "DDGIUpdateConsts")
@@ -635,6 +652,16 @@ class FrameDriver:
                     [CB(0, cb), SRV(1, self.ddgi_rays), TEX_SRV(3, self.ddgi_data), TEX_UAV(1, self.ddgi_irradiance, 0)], (cx, cz, cy))
         cl.dispatch("ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0",
                     [CB(0, cb), SRV(1, self.ddgi_rays), TEX_SRV(3, self.ddgi_data), TEX_UAV(2, self.ddgi_distance, 0)], (cx, cz, cy))
+        if not (u["relocate"] or u["classify"]):
+            return
+        n = cx * cy * cz                             # GIRenderer.cpp:513-527: relocation and classification behind the blends
+        cl.dispatch("giprobetrace_CS_ProbeTraceFixedRays",
+                    [CB(0, cb), SRV(0, self.ddgi_desc), TEX_SRV(1, self.ddgi_data), SRV(4, rt["tlas_nodes"]), SRV(5, sc.instances), SRV(6, sc.vertices), SRV(8, sc.indices),
+                     SRV(9, sc.meshData), SRV(10, rt["tlas_instances"]), SRV(11, rt["headers"]), SRV(12, rt["blas_nodes"]), SRV(13, rt["tri_order"]),
+                     UAV(0, self.ddgi_fixed_rays)], ((n * I.kDDGIFixedRays + 63) // 64, 1, 1))
+        for on, name in ((u["relocate"], "ProbeRelocationCS_DDGIProbeRelocationCS"), (u["classify"], "ProbeClassificationCS_DDGIProbeClassificationCS")):
+            if on:
+                cl.dispatch(name, [CB(0, cb), UAV(0, self.ddgi_fixed_rays), TEX_UAV(3, self.ddgi_data, 0)], ((n + 31) // 32, 1, 1))
 
     def download_ddgi(self):
         """A copy of the driver's ddgi.Volume with the probe textures as they are on the device now."""
@@ -654,6 +681,13 @@ class FrameDriver:
             raise ValueError("download_ddgi_rays: the probe update is off (ddgi_update=None)")
         self.dev.wait_idle()
         return self.ddgi_rays.download(np.float32).reshape(-1, I.kDDGIRaysPerProbe, 4)
+
+    def download_ddgi_fixed_rays(self) -> np.ndarray:
+        """The fixed-ray distances of the last update, float32 [numProbes, 32]: t for a front face, -0.2 t for a back face, 1e27 for a miss."""
+        if self.ddgi_fixed_rays is None:
+            raise ValueError("download_ddgi_fixed_rays: probe placement is off (ddgi_update without relocate=True or classify=True)")
+        self.dev.wait_idle()
+        return self.ddgi_fixed_rays.download(np.float32).reshape(-1, I.kDDGIFixedRays)
 
     def download_shadow_mask(self) -> np.ndarray:
         """The bytes of the generated shadow mask, (H, W) uint8."""
@@ -851,6 +885,6 @@ class FrameDriver:
         self.hzb.release(); self.depth.release()
         for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
                   self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
-                  self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays):
+                  self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays, self.ddgi_fixed_rays):
             if t is not None:
                 t.release()

@@ -30,7 +30,7 @@ HOST_SYMBOLS = [
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
     "trhost_get_deferred_lighting_consts", "trhost_upload_ddgi_volume", "trhost_set_ddgi",
-    "trhost_set_ddgi_update", "trhost_reset_ddgi_volume", "trhost_download_ddgi_volume", "trhost_get_ddgi_update_consts",
+    "trhost_set_ddgi_update", "trhost_set_ddgi_probe_placement", "trhost_reset_ddgi_volume", "trhost_download_ddgi_volume", "trhost_get_ddgi_update_consts",
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
@@ -108,6 +108,7 @@ def load() -> C.CDLL:
     L.trhost_upload_ddgi_volume.argtypes = [vp, vp, u64, vp, u64, vp, u64]
     L.trhost_set_ddgi.argtypes = [C.c_int]
     L.trhost_set_ddgi_update.argtypes = [C.c_int, C.c_uint32]
+    L.trhost_set_ddgi_probe_placement.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float]
     L.trhost_reset_ddgi_volume.argtypes = []
     L.trhost_download_ddgi_volume.argtypes = [vp, u64, vp, u64, vp, u64]
     L.trhost_get_ddgi_update_consts.argtypes = [vp]
@@ -377,6 +378,11 @@ class Renderer:
         """GIRenderer::RenderDDGI: the probe trace and the two blends fill the uploaded volume every frame (needs upload_ddgi_volume,
         load_raytracing and deferred lighting; include/trhost.h)."""
         _check(load().trhost_set_ddgi_update(int(on), int(seed)))
+
+    def set_ddgi_probe_placement(self, relocate: bool = True, classify: bool = True, min_frontface_distance: float = 0.3, fixed_ray_backface_threshold: float = 0.25):
+        """Probe relocation and classification behind the blends of every update (needs the volume and, per pass, its flag in the
+        volume's descriptor; include/trhost.h)."""
+        _check(load().trhost_set_ddgi_probe_placement(int(relocate), int(classify), float(min_frontface_distance), float(fixed_ray_backface_threshold)))
 
     def reset_ddgi_volume(self):
         """Irradiance and distance cleared to zero words, the reference's start."""

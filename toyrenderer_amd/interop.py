@@ -118,8 +118,9 @@ kDDGIIrradianceInteriorTexels, kDDGIDistanceInteriorTexels, kDDGIMaxProbeCount =
 # csrc/ShaderInterop.h: the project's own b0 of the probe trace and the two probe blends; the DDGIVolumeDesc follows it in b0
 DDGIUpdateConsts = np.dtype([("m_DirectionalLightVector", np.float32, (3,)), ("m_DirectionalLightStrength", np.float32), ("rayRotation", np.float32, (3, 4)),
                              ("probeMaxRayDistance", np.float32), ("probeHysteresis", np.float32), ("probeDistanceExponent", np.float32),
-                             ("probeIrradianceThreshold", np.float32), ("probeBrightnessThreshold", np.float32), ("pad", np.uint32, (3,))])
-kDDGIRaysPerProbe, kDDGIBackfaceRayLimit = 256, 25
+                             ("probeIrradianceThreshold", np.float32), ("probeBrightnessThreshold", np.float32), ("probeMinFrontfaceDistance", np.float32),
+                             ("probeFixedRayBackfaceThreshold", np.float32), ("pad", np.uint32)])
+kDDGIRaysPerProbe, kDDGIBackfaceRayLimit, kDDGIFixedRays = 256, 25, 32
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
