@@ -203,6 +203,16 @@ def gpu_scene(dev, s, inst, vertices=None, materials=None):
     return gs
 
 
+def bare_gpu_scene(dev, sc):
+    """A GpuScene of a tests/shadow_scenes.py dict: no meshlets (the single passes need none), geometry, materials, the structure."""
+    from toyrenderer_amd.frame import GpuScene
+    gs = GpuScene(dev, sc["instances"], sc["meshData"], None, sc["opaqueIds"], sc["alphaMaskIds"], num_meshlets=1)
+    gs.set_geometry(sc["vertices"], np.zeros(1, np.uint32), np.zeros(1, np.uint32))
+    gs.set_materials(sc["materials"])
+    gs.set_raytracing(sc["indices"], sc["index_counts"])
+    return gs
+
+
 @contextlib.contextmanager
 def host_renderer(s, instances, geometry=None, materials=None, **kw):
     """A host.Renderer(**kw) with the scene, its nodes and, if given, geometry and materials loaded; shut down on exit."""

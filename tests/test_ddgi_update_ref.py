@@ -10,9 +10,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import ddgi_placement_ref as DP  # noqa: E402
 import ddgi_update_ref as DU  # noqa: E402
 import ddgi_update_scenes as US  # noqa: E402
+import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
+from ddgi_passes import city_trace_scene, city_volume, trace_case, unflagged_leaves  # noqa: E402
 from ref_build import layout_probe  # noqa: E402
 from suite_support import ref_library, same, sm  # noqa: E402, F401
 from toyrenderer_amd import ddgi  # noqa: E402
@@ -20,6 +23,7 @@ from toyrenderer_amd import interop as I  # noqa: E402
 
 F = np.float32
 du = ref_library(DU)
+dp = ref_library(DP)                              # holds tests/ddgi_update_ref.c too: the trace cases share one handle with the GPU file
 AXES = np.array([(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (-0.0, 0, -1)], F)
 
 # Float64 agreement (test_blends_agree_with_float64): the largest differences MEASURED with US.blend_volume(seed 3) and
@@ -134,6 +138,175 @@ def test_trace_walk_equals_brute_force_and_takes_every_branch(du, scenes):
                 cleared, kinds0 = DU.trace(du, k, vol.copy().reset(), scene, DU.WALK, init)     # the same probes over cleared textures
                 assert np.array_equal(kinds0, kinds) and np.count_nonzero(walk[front][:, :3] != cleared[front][:, :3]) > 100, "the recursive term is there"
     assert seen == {DU.KIND_MISS, DU.KIND_BACK, DU.KIND_LIT, DU.KIND_SHADOWED}
+
+
+# ---- 2b. preconditions of the GPU trace cases (US.TRACE_CASES), on the reference alone --------------------------------------------
+# What tests/test_gpu_ddgi_trace_scenes.py can tell apart depends on what the reference's rays meet.  These are conditions on the
+# inputs, not measurements of the kernels: a scene that misses one is changed, not the bound.  KINDS: KIND_MISS, KIND_BACK, KIND_LIT,
+# KIND_SHADOWED.
+BIG = ["tlas 64", "tlas 65", "tlas 257"]
+ROTATED, SCALED, MIRRORED, ALPHA = (lambda i: i % 3 != 0), (lambda i: i % 4 == 1), (lambda i: i % 5 == 2), (lambda i: i % 10 == 7)      # SS.scattered's rules
+
+
+def _kinds(kinds):
+    return [int(np.count_nonzero(kinds == x)) for x in (DU.KIND_MISS, DU.KIND_BACK, DU.KIND_LIT, DU.KIND_SHADOWED)]
+
+
+def _front(kinds):
+    return (kinds == DU.KIND_LIT) | (kinds == DU.KIND_SHADOWED)
+
+
+def _on(hits, rule):
+    """bool like hits: the ray's hit is on an instance for which rule(index) holds."""
+    inst = hits["inst"]
+    table = np.array([bool(rule(i)) for i in range(int(inst[inst != DU.MISS].max()) + 1 if np.any(inst != DU.MISS) else 1)])
+    return (inst != DU.MISS) & table[np.where(inst != DU.MISS, inst, 0)]
+
+
+@pytest.mark.parametrize("name", list(US.TRACE_CASES))
+def test_trace_cases_walk_equals_brute_force(sm, dp, name):
+    """Every case of US.TRACE_CASES: the records of the walk over the refitted node arrays equal brute force over every triangle,
+    word for word, and so do the closest hits of the probes' own rays.  MEASURED: true in all 18 cases."""
+    c = trace_case(sm, dp, name)
+    brute, kinds = DU.trace(dp, c.k, c.volume(), c.scene, DU.BRUTE, c.init)
+    same(c.rays.view(np.uint32), brute.view(np.uint32), f"{name}: records, walk against brute force")
+    assert np.array_equal(kinds, c.kinds)
+    same(c.hits(dp, DU.WALK).view(np.uint32), c.hits(dp, DU.BRUTE).view(np.uint32), f"{name}: hits, walk against brute force")
+    print(f"{name}: kinds {_kinds(c.kinds)}")
+
+
+@pytest.mark.parametrize("name", BIG)
+def test_trace_cases_large_scattered_scenes_meet_every_kind_of_instance(sm, dp, name):
+    """At least 50 records of each kind; at least 100 front-face hits each on rotated and on non-uniformly scaled instances, 50 on
+    mirrored ones, 30 on alpha-list ones; at least 40 distinct instances hit.  MEASURED (miss / back / lit / shadowed; front hits
+    on rotated / scaled / mirrored / alpha; distinct): tlas 64: 3568 / 379 / 483 / 178; 296 / 261 / 120 / 61; 60.
+    tlas 65: 3552 / 279 / 639 / 138; 254 / 264 / 130 / 61; 62.  tlas 257: 2172 / 740 / 881 / 815; 661 / 504 / 298 / 96; 216."""
+    c = trace_case(sm, dp, name)
+    hits, front = c.hits(dp), _front(c.kinds)
+    counts = [int(np.count_nonzero(front & _on(hits, rule))) for rule in (ROTATED, SCALED, MIRRORED, ALPHA)]
+    distinct = len(np.unique(hits["inst"][hits["inst"] != DU.MISS]))
+    print(f"{name}: kinds {_kinds(c.kinds)}, front hits on rotated / scaled / mirrored / alpha {counts}, {distinct} distinct instances")
+    assert min(_kinds(c.kinds)) >= 50, _kinds(c.kinds)
+    assert counts[0] >= 100 and counts[1] >= 100 and counts[2] >= 50 and counts[3] >= 30, counts
+    assert distinct >= 40
+    assert np.array_equal(front, (hits["inst"] != DU.MISS) & (hits["front"] == 1)) and np.array_equal(c.kinds == DU.KIND_MISS, hits["inst"] == DU.MISS)
+
+
+@pytest.mark.parametrize("name", ["tlas 1", "tlas 2", "tlas 3"])
+def test_trace_cases_small_scattered_scenes_are_hit(sm, dp, name):
+    """At least one hit.  MEASURED: 13, 75, 73."""
+    c = trace_case(sm, dp, name)
+    n = int(np.count_nonzero(c.kinds != DU.KIND_MISS))
+    print(f"{name}: {n} hits")
+    assert n >= 1
+
+
+def test_trace_case_moved_differs_from_the_rest_pose(sm, dp):
+    """At least 300 records differ from the trace of the same scene at rest.  MEASURED: 699; 22 of the 65 instances moved, each out
+    of the box its TLAS leaf was built with."""
+    c, rest = trace_case(sm, dp, "moved"), trace_case(sm, dp, "tlas 65")
+    n = int(np.count_nonzero(np.any(c.rays.view(np.uint32) != rest.rays.view(np.uint32), axis=-1)))
+    moved = np.flatnonzero(np.any(c.inst["m_WorldMatrix"] != c.sc["instances"]["m_WorldMatrix"], axis=(1, 2)))
+    print(f"moved: {n} records differ, {len(moved)} instances moved")
+    assert n >= 300 and len(moved) == 22
+    assert not np.array_equal(SR.refit(sm, c.acc, c.inst)[0]["lo"], SR.refit(sm, c.acc)[0]["lo"]), "the refit moved the boxes"
+
+
+def test_trace_case_shared_planes_ties_and_the_tie_shows(sm, dp):
+    """At least 100 rays meet instances 0 and 1 at the same t (found by tracing once more with instance 0 in no list: a ray whose
+    hit is instance 0 at t and then instance 1 at the same t); on at least 50 of them the record changes when instance 1 wins
+    (another triangle: other normals; the volume is seeded so that the recursive term shows them).  MEASURED: 292 ties, 102 of
+    them with a record that changes, all front faces."""
+    c = trace_case(sm, dp, "shared planes")
+    sc = dict(c.sc)
+    sc["opaqueIds"] = np.array([1], np.uint32)                           # instance 0 in no list: flags == 0
+    other = DU.Scene(sm, SR.Accel(sc))
+    first, second = c.hits(dp), c.hits(dp, scene=other)
+    tie = (first["inst"] == 0) & (second["inst"] == 1) & (first["t"] == second["t"])
+    alt, _ = DU.trace(dp, c.k, c.volume(), other, DU.WALK, c.init)
+    shows = tie & np.any(alt.view(np.uint32) != c.rays.view(np.uint32), axis=-1)
+    print(f"shared planes: {int(tie.sum())} ties, {int(shows.sum())} show, {int((shows & _front(c.kinds)).sum())} of them front faces")
+    assert tie.sum() >= 100 and shows.sum() >= 50
+
+
+def test_trace_case_attributes_reaches_every_attribute(sm, dp):
+    """Front-face hits: at least 50 on instances whose material index is past the buffer, 100 on the emissive material and 100 on
+    the one with a NaN albedo; at least 8 rays would end on an instance the case takes out of the lists were it listed, none does,
+    and no record holds a NaN.  MEASURED: 115 / 267 / 326 front hits (and 16 on the material with an infinite emissive), 15 rays."""
+    c = trace_case(sm, dp, "attributes")
+    hits, front = c.hits(dp), _front(c.kinds)
+    mat = c.sc["instances"]["m_MaterialDataIdx"]
+    counts = [int(np.count_nonzero(front & _on(hits, rule))) for rule in (US.ATTR_PAST, lambda i: mat[i] == 1, lambda i: mat[i] == 0, lambda i: mat[i] == 4)]
+    listed = DU.Scene(sm, SR.Accel(US.attributes(listed=True)))
+    would = int(np.count_nonzero(_on(c.hits(dp, scene=listed), US.ATTR_UNLISTED)))
+    print(f"attributes: front hits on past-the-buffer / emissive / NaN albedo / infinite emissive {counts}, {would} rays would end on an unlisted instance")
+    assert sorted(set(int(m) for m in mat[[i for i in range(len(mat)) if US.ATTR_PAST(i)]])) == [5, 0xFFFFFFFF] and len(c.sc["materials"]) == 5
+    assert counts[0] >= 50 and counts[1] >= 100 and counts[2] >= 100 and counts[3] >= 1, counts
+    assert would >= 8
+    assert np.count_nonzero(_on(hits, US.ATTR_UNLISTED)) == 0
+    assert not np.isnan(c.rays).any()
+
+
+def test_unflagged_leaves_are_skipped_and_would_be_hit(sm, dp):
+    """The builder leaves an instance that is in neither list out of the tree, so in "attributes" no leaf names one and the walk's
+    `flags == 0` rule decides nothing there.  ddgi_passes.unflagged_leaves is the structure where it decides: 7 instances keep
+    their leaves, boxes and matrices and lose their flags.  The walk over it equals brute force and equals the "attributes"
+    records word for word (another tree, the same answer), and every one of the 7 has a leaf whose box the refit left alone.
+    MEASURED: the 15 rays of the test above are the ones that would end on them."""
+    c = trace_case(sm, dp, "attributes")
+    sc, acc, off = unflagged_leaves(sm)
+    scene = DU.Scene(sm, acc)
+    assert len(off) == 7 and np.all(scene.records["flags"][off] == 0) and np.all(scene.records["leaf_node"][off] < len(scene.nodes))
+    assert np.all(scene.nodes["leaf"][scene.records["leaf_node"][off]] == off) and np.all(np.any(scene.records["object_from_world"][off] != 0, axis=(1, 2)))
+    assert scene.nodes.tobytes() == acc.tlas["nodes"].tobytes() and scene.records.tobytes() == acc.tlas["records"].tobytes(), "a second refit changes nothing"
+    for mode in (DU.WALK, DU.BRUTE):
+        rays, _ = DU.trace(dp, c.k, c.volume(), scene, mode, c.init)
+        same(rays.view(np.uint32), c.rays.view(np.uint32), f"unflagged leaves, mode {mode}: the records of attributes")
+
+
+@pytest.mark.parametrize("tmax", [2.0, 4.0])
+def test_trace_cases_tmax_cuts_hits_off(sm, dp, tmax):
+    """At least 100 rays that hit in the unbounded trace at t >= tmax are misses here.  MEASURED: 601 and 328."""
+    c, free = trace_case(sm, dp, f"tmax {tmax:g}"), trace_case(sm, dp, "tlas 65")
+    far = free.hits(dp)
+    cut = (far["inst"] != DU.MISS) & (far["t"] >= F(tmax))
+    print(f"tmax {tmax:g}: {int(cut.sum())} hits cut off")
+    assert cut.sum() >= 100 and np.all(c.kinds[cut] == DU.KIND_MISS) and np.array_equal(c.kinds[~cut], free.kinds[~cut])
+
+
+def test_trace_case_light_x_has_both_front_kinds(sm, dp):
+    """An axis-parallel shadow ray (boxHit's branch without a reciprocal): at least 100 lit and 100 shadowed records.
+    MEASURED: 395 and 382."""
+    c = trace_case(sm, dp, "light x")
+    print(f"light x: kinds {_kinds(c.kinds)}")
+    assert _kinds(c.kinds)[2] >= 100 and _kinds(c.kinds)[3] >= 100
+    assert tuple(c.k["m_DirectionalLightVector"][0]) == (1.0, 0.0, 0.0)
+
+
+def test_fixed_ray_volume_over_tlas_65_meets_every_kind(sm, dp):
+    """The 33-probe volume of the GPU file's fixed-ray cases over "tlas 65": at least 50 misses, 50 back faces and 50 front faces
+    among its 1056 distances, and the walk equals brute force.  MEASURED: 645 / 116 / 295."""
+    c = trace_case(sm, dp, "tlas 65")
+    k, vol = DP.consts(rotation=US.rotation(3)), US.fixed_ray_volume()
+    d = DP.trace_fixed(dp, k, vol, c.scene)
+    same(d.view(np.uint32), DP.trace_fixed(dp, k, vol, c.scene, DU.BRUTE).view(np.uint32), "fixed rays: walk against brute force")
+    counts = [int(np.count_nonzero(d == DP.MISS_DISTANCE)), int(np.count_nonzero(d < 0)), int(np.count_nonzero((d > 0) & (d != DP.MISS_DISTANCE)))]
+    print(f"fixed rays over tlas 65: miss / back / front {counts}")
+    assert d.shape == (33, DP.FIXED) and min(counts) >= 50 and sum(counts) == d.size
+
+
+def test_city_trace_walk_equals_brute_force(sm, dp, oracle, tmp_path):
+    """The first frame of the GPU file's city case (137 instances at rest, the cleared 3 x 2 x 3 volume over the city's bounds, all
+    4608 rays): the walk the GPU is held to equals brute force.  The whole first frame is used, not a one-probe volume: brute force
+    takes about 5 s.  MEASURED kinds: 4215 / 14 / 305 / 74."""
+    s, c, v, mats, sc, bounds = city_trace_scene(tmp_path, oracle)
+    scene, vol = DU.Scene(sm, SR.Accel(sc)), city_volume(bounds)
+    k = DU.consts(light=(SS.unit((0.2, 0.35, -0.9)), 2.5), rotation=ddgi.random_rotation(np.random.default_rng([21, 0])), hysteresis=0.7)
+    walk, kinds = DU.trace(dp, k, vol, scene, DU.WALK)
+    brute, _ = DU.trace(dp, k, vol, scene, DU.BRUTE)
+    print(f"city: kinds {_kinds(kinds)}")
+    same(walk.view(np.uint32), brute.view(np.uint32), "city: records, walk against brute force")
+    assert min(_kinds(kinds)) >= 5
 
 
 # ---- 3. the encodings ------------------------------------------------------------------------------------------------------------------

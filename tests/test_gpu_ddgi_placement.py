@@ -18,19 +18,16 @@ import ddgi_update_ref as DU  # noqa: E402
 import ddgi_update_scenes as US  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
-from suite_support import dev, gpu_scene, recorded, ref_library, same, sm  # noqa: E402, F401
+from ddgi_passes import CLASSIFICATION, FIXED, RELOCATION, Placement  # noqa: E402
+from suite_support import bare_gpu_scene, dev, gpu_scene, recorded, ref_library, same, sm  # noqa: E402, F401
 from toyrenderer_amd import ddgi, gltf_lite  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 dp = ref_library(DP)
-FIXED = "giprobetrace_CS_ProbeTraceFixedRays"
-RELOCATION = "ProbeRelocationCS_DDGIProbeRelocationCS"
-CLASSIFICATION = "ProbeClassificationCS_DDGIProbeClassificationCS"
 UPDATE = ["giprobetrace_CS_ProbeTrace", "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1", "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0"]
 CORNELL_MIN_FRONT = 0.1                           # GIRenderer.cpp:98: the fixture's bounding radius is below 3
-SENTINEL = F(-7.5)                                # pre-fill of the distances: the trace writes every word
 
 
 def _bits(data):
@@ -55,86 +52,10 @@ def cornell(dev, oracle, sm):
 
 @pytest.fixture(scope="module")
 def closed_cube(dev, sm):
-    from toyrenderer_amd.frame import GpuScene
     sc = US.closed_cube()
-    gs = GpuScene(dev, sc["instances"], sc["meshData"], None, sc["opaqueIds"], sc["alphaMaskIds"], num_meshlets=1)
-    gs.set_geometry(sc["vertices"], np.zeros(1, np.uint32), np.zeros(1, np.uint32))
-    gs.set_materials(sc["materials"])
-    gs.set_raytracing(sc["indices"], sc["index_counts"])
+    gs = bare_gpu_scene(dev, sc)
     yield sc, gs, DU.Scene(sm, SR.Accel(sc))
     gs.release()
-
-
-class Placement:
-    """One volume's device resources and the three passes through rhi bindings."""
-
-    def __init__(self, dev, vol, gs=None, data_uav=True):
-        self.dev, self.vol, self.gs = dev, vol, gs
-        self.desc, self.data, self.irr, self.dist = vol.upload(dev, data_uav=data_uav)
-        self.n = int(np.prod(vol.counts))
-        self.distances = dev.create_buffer(self.n * DP.FIXED * 4, "DDGI Fixed Ray Distances", stride=4)
-        self.cl = dev.create_command_list()
-
-    def block(self, k):
-        return np.frombuffer(np.ascontiguousarray(k, I.DDGIUpdateConsts).tobytes() + self.vol.desc().tobytes(), np.uint8)
-
-    def fixed_bindings(self, cb):
-        from toyrenderer_amd.rhi import CB, SRV, TEX_SRV, UAV
-        gs, rt = self.gs, self.gs.rt
-        return [CB(0, cb), SRV(0, self.desc), TEX_SRV(1, self.data), SRV(4, rt["tlas_nodes"]), SRV(5, gs.instances), SRV(6, gs.vertices), SRV(8, gs.indices), SRV(9, gs.meshData),
-                SRV(10, rt["tlas_instances"]), SRV(11, rt["headers"]), SRV(12, rt["blas_nodes"]), SRV(13, rt["tri_order"]), UAV(0, self.distances)]
-
-    def fixed_groups(self):
-        return ((self.n * DP.FIXED + 63) // 64, 1, 1)
-
-    def place_bindings(self, cb):
-        from toyrenderer_amd.rhi import CB, TEX_UAV, UAV
-        return [CB(0, cb), UAV(0, self.distances), TEX_UAV(3, self.data, 0)]
-
-    def place_groups(self):
-        return ((self.n + 31) // 32, 1, 1)
-
-    def refit(self):
-        from toyrenderer_amd.rhi import PUSH, SRV, UAV
-        gs, rt = self.gs, self.gs.rt
-        k = np.zeros(1, I.RefitTLASConstants)
-        k["m_NumInstances"], k["m_NumNodes"], k["m_NumLevels"] = gs.numInstances, len(rt["tlas"]["nodes"]), rt["tlas"]["num_levels"]
-        self.cl.dispatch("raytracing_CS_RefitTLAS", [PUSH(0), SRV(0, gs.instances), SRV(1, rt["headers"]), SRV(2, rt["blas_nodes"]), SRV(3, rt["level_offsets"]),
-                                                     SRV(4, rt["level_nodes"]), UAV(0, rt["tlas_nodes"]), UAV(1, rt["tlas_instances"])],
-                         ((gs.numInstances + 63) // 64, 1, 1), push=k)
-
-    def run_fixed(self, k):
-        self.distances.upload(np.full(self.n * DP.FIXED, SENTINEL, F))
-        self.cl.open()
-        self.refit()
-        self.cl.dispatch(FIXED, self.fixed_bindings(self.cl.constant_buffer(self.block(k), "DDGIUpdateConsts")), self.fixed_groups())
-        self.cl.close()
-        self.dev.execute(self.cl); self.dev.wait_idle()
-        return self.distances.download(F).reshape(self.n, DP.FIXED)
-
-    def run_place(self, k, names, distances=None):
-        """Dispatches the passes of `names` in order on what the data texture holds (and `distances`, if given); returns the data."""
-        if distances is not None:
-            self.distances.upload(np.ascontiguousarray(distances, F).reshape(-1))
-        self.cl.open()
-        cb = self.cl.constant_buffer(self.block(k), "DDGIUpdateConsts")
-        for name in names:
-            self.cl.dispatch(name, self.place_bindings(cb), self.place_groups())
-        self.cl.close()
-        self.dev.execute(self.cl); self.dev.wait_idle()
-        return self.download_data()
-
-    def upload_data(self, data):
-        for s in range(self.vol.counts[1]):
-            self.data.upload_slice(s, np.ascontiguousarray(data[s]))
-
-    def download_data(self):
-        return np.stack([self.data.download_slice(s) for s in range(self.vol.counts[1])]).reshape(self.vol.data.shape)
-
-    def release(self):
-        self.cl.release()
-        for r in (self.desc, self.data, self.irr, self.dist, self.distances):
-            r.release()
 
 
 # ---- 1. each pass, dispatched directly ----------------------------------------------------------------------------------------------------

@@ -16,6 +16,8 @@ import ddgi_update_ref as DU  # noqa: E402
 import ddgi_update_scenes as US  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
+from ddgi_passes import BLEND_DISTANCE, BLEND_RADIANCE, TRACE, Update  # noqa: E402
+from ddgi_passes import RAY_SENTINEL as SENTINEL  # noqa: E402
 from suite_support import dev, dg, gpu_scene, ref_library, same, sm  # noqa: E402, F401
 from toyrenderer_amd import ddgi, gltf_lite  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
@@ -23,10 +25,6 @@ from toyrenderer_amd import interop as I  # noqa: E402
 pytestmark = pytest.mark.gpu
 F = np.float32
 du = ref_library(DU)
-TRACE = "giprobetrace_CS_ProbeTrace"
-BLEND_RADIANCE = "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1"
-BLEND_DISTANCE = "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0"
-SENTINEL = F(7.5)                                 # pre-fill of the ray records: an inactive probe's keep it
 
 
 def _cornell_gpu(dev, oracle):
@@ -48,78 +46,6 @@ def cornell(dev, oracle, sm):
     sc, gs = _cornell_gpu(dev, oracle)
     yield sc, gs, DU.Scene(sm, SR.Accel(sc))
     gs.release()
-
-
-class Update:
-    """One volume's device resources and the three passes through rhi bindings."""
-
-    def __init__(self, dev, vol, gs=None, uav=True):
-        self.dev, self.vol, self.gs = dev, vol, gs
-        self.desc, self.data, self.irr, self.dist = vol.upload(dev, uav=uav)
-        self.n = int(np.prod(vol.counts))
-        self.rays = dev.create_buffer(self.n * DU.RAYS * 16, "DDGI Ray Data", stride=16)
-        self.cl = dev.create_command_list()
-
-    def block(self, k):
-        return np.frombuffer(np.ascontiguousarray(k, I.DDGIUpdateConsts).tobytes() + self.vol.desc().tobytes(), np.uint8)
-
-    def trace_bindings(self, cb):
-        from toyrenderer_amd.rhi import CB, SAMPLER, SRV, TEX_SRV, UAV
-        gs, rt = self.gs, self.gs.rt
-        return [CB(0, cb), SRV(0, self.desc), TEX_SRV(1, self.data), TEX_SRV(2, self.irr), TEX_SRV(3, self.dist), SRV(4, rt["tlas_nodes"]), SRV(5, gs.instances),
-                SRV(6, gs.vertices), SRV(7, gs.materials), SRV(8, gs.indices), SRV(9, gs.meshData), SRV(10, rt["tlas_instances"]), SRV(11, rt["headers"]),
-                SRV(12, rt["blas_nodes"]), SRV(13, rt["tri_order"]), UAV(0, self.rays), SAMPLER(0), SAMPLER(1), SAMPLER(2)]
-
-    def trace_groups(self):
-        cx, cy, cz = self.vol.counts
-        return (DU.RAYS // 64, cx * cz, cy)
-
-    def blend_bindings(self, cb, radiance):
-        from toyrenderer_amd.rhi import CB, SRV, TEX_SRV, TEX_UAV
-        return [CB(0, cb), SRV(1, self.rays), TEX_SRV(3, self.data), TEX_UAV(1, self.irr, 0) if radiance else TEX_UAV(2, self.dist, 0)]
-
-    def blend_groups(self):
-        cx, cy, cz = self.vol.counts
-        return (cx, cz, cy)
-
-    def refit(self):
-        from toyrenderer_amd.rhi import PUSH, SRV, UAV
-        gs, rt = self.gs, self.gs.rt
-        k = np.zeros(1, I.RefitTLASConstants)
-        k["m_NumInstances"], k["m_NumNodes"], k["m_NumLevels"] = gs.numInstances, len(rt["tlas"]["nodes"]), rt["tlas"]["num_levels"]
-        self.cl.dispatch("raytracing_CS_RefitTLAS", [PUSH(0), SRV(0, gs.instances), SRV(1, rt["headers"]), SRV(2, rt["blas_nodes"]), SRV(3, rt["level_offsets"]),
-                                                     SRV(4, rt["level_nodes"]), UAV(0, rt["tlas_nodes"]), UAV(1, rt["tlas_instances"])],
-                         ((gs.numInstances + 63) // 64, 1, 1), push=k)
-
-    def run_trace(self, k):
-        self.rays.upload(np.full(self.n * DU.RAYS * 4, SENTINEL, F))
-        self.cl.open()
-        self.refit()
-        self.cl.dispatch(TRACE, self.trace_bindings(self.cl.constant_buffer(self.block(k), "DDGIUpdateConsts")), self.trace_groups())
-        self.cl.close()
-        self.dev.execute(self.cl); self.dev.wait_idle()
-        return self.rays.download(F).reshape(self.n, DU.RAYS, 4)
-
-    def run_blends(self, k, rays):
-        self.rays.upload(np.ascontiguousarray(rays, F).reshape(-1))
-        self.cl.open()
-        cb = self.cl.constant_buffer(self.block(k), "DDGIUpdateConsts")
-        self.cl.dispatch(BLEND_RADIANCE, self.blend_bindings(cb, True), self.blend_groups())
-        self.cl.dispatch(BLEND_DISTANCE, self.blend_bindings(cb, False), self.blend_groups())
-        self.cl.close()
-        self.dev.execute(self.cl); self.dev.wait_idle()
-        return self.textures()
-
-    def textures(self):
-        cy = self.vol.counts[1]
-        irr = np.stack([self.irr.download_slice(s) for s in range(cy)])
-        dist = np.stack([self.dist.download_slice(s) for s in range(cy)]).reshape(self.vol.distance.shape)
-        return irr, dist
-
-    def release(self):
-        self.cl.release()
-        for r in (self.desc, self.data, self.irr, self.dist, self.rays):
-            r.release()
 
 
 # ---- 1. the trace --------------------------------------------------------------------------------------------------------------------

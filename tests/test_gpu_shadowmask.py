@@ -14,23 +14,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lighting_ref as LR  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
-from suite_support import dev, gpu_scene, lr, op_counts, recorded, same, shadow_case_reference, sm  # noqa: E402, F401
+from suite_support import bare_gpu_scene as _gpu_scene, dev, gpu_scene, lr, op_counts, recorded, same, shadow_case_reference, sm  # noqa: E402, F401
 from toyrenderer_amd import accel, cached_scene, gltf_lite, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 TRACE, REFIT = "shadowmask_CS_ShadowMask", "raytracing_CS_RefitTLAS"
-
-
-def _gpu_scene(dev, sc):
-    """A GpuScene of a tests/shadow_scenes.py dict: no meshlets (the single passes need none), geometry, materials, the structure."""
-    from toyrenderer_amd.frame import GpuScene
-    gs = GpuScene(dev, sc["instances"], sc["meshData"], None, sc["opaqueIds"], sc["alphaMaskIds"], num_meshlets=1)
-    gs.set_geometry(sc["vertices"], np.zeros(1, np.uint32), np.zeros(1, np.uint32))
-    gs.set_materials(sc["materials"])
-    gs.set_raytracing(sc["indices"], sc["index_counts"])
-    return gs
 
 
 class _Pass:
