@@ -1,5 +1,5 @@
 """What the DDGI GPU test modules share (tests/test_gpu_ddgi_update.py, tests/test_gpu_ddgi_placement.py,
-tests/test_gpu_ddgi_trace_scenes.py): the passes of the probe update and of probe placement through rhi
+tests/test_gpu_ddgi_trace_scenes.py, tests/test_gpu_ddgi_blend_rules.py): the passes of the probe update and of probe placement through rhi
 bindings, and the references of tests/ddgi_update_scenes.py TRACE_CASES, computed once
 per process.  Not a test module: every assert here says what it compared."""
 import numpy as np

@@ -315,21 +315,47 @@ void du_probe_positions(const DgDesc* D, const uint16_t* data, float* pos, uint3
 static float sign1(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
 static float max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
+/* One word of rule bits per interior texel, written by du_blend_radiance_rules / du_blend_distance_rules: the decisions the
+ * functions below took, in their own binary32.  A NULL `rules` changes nothing: the arithmetic is stated once. */
+enum { DU_R_LEFT_ALONE = 1u << 0, DU_R_PREV_ZERO = 1u << 1, DU_R_IRRADIANCE = 1u << 2, DU_R_BRIGHTNESS = 1u << 3, DU_R_DARKER = 1u << 4,
+       DU_R_FLOOR = 1u << 5, DU_R_CAP = 1u << 8, DU_R_SIGN_ZERO = 1u << 11,           /* << channel: the floor gives the step, |delta| gives it, sign(step) == 0 */
+       DU_R_CLAMP_ONE = 1u << 14, DU_R_CLAMP_ZERO = 1u << 17,                         /* << channel: saturate clamped the store */
+       DU_R_NAN = 1u << 20,                                                           /* a NaN in sum, res or the store */
+       DU_R_MAX_SHIFT = 21,                                                           /* two bits: 1 + the channel whose |delta| is the fmax of the three (0: not eased) */
+       DU_R_SUM_NAN = 1u << 23 };
+enum { DU_D_LEFT_ALONE = 1u << 0, DU_D_PREV_ZERO = 1u << 1, DU_D_SUMW_FLOOR = 1u << 2, DU_D_STORE_INF = 1u << 3, DU_D_STORE_NAN = 1u << 4, DU_D_STORE_SUBNORMAL = 1u << 5,
+       DU_D_PREV_INF = 1u << 6, DU_D_PREV_NAN = 1u << 7, DU_D_CLIPPED_SHIFT = 16 };   /* bits 16..24: rays with !(|w| <= maxDistance) */
+
 /* floorRule 0 leaves the 1/1024 rule out: only for the test that shows what it is for */
-void du_ease_radiance(const DuConsts* k, const float res[3], const float prev[3], int floorRule, float out[3])
+static void ease_radiance(const DuConsts* k, const float res[3], const float prev[3], int floorRule, float out[3], uint32_t* rules)
 {
-    if (prev[0] == 0.0f && prev[1] == 0.0f && prev[2] == 0.0f) { memcpy(out, res, 12); return; }
+    if (prev[0] == 0.0f && prev[1] == 0.0f && prev[2] == 0.0f) { memcpy(out, res, 12); if (rules) *rules |= DU_R_PREV_ZERO; return; }
     float h = k->hysteresis;
     float delta[3] = { res[0] - prev[0], res[1] - prev[1], res[2] - prev[2] };
-    if (max3(fabsf(delta[0]), fabsf(delta[1]), fabsf(delta[2])) > k->irradianceThreshold) h = fmaxf(0.0f, h - 0.75f);
-    if (sqrtf(dot3(delta, delta)) > k->brightnessThreshold) { delta[0] = delta[0] * 0.25f; delta[1] = delta[1] * 0.25f; delta[2] = delta[2] * 0.25f; }
+    if (rules) {
+        const float m = max3(fabsf(delta[0]), fabsf(delta[1]), fabsf(delta[2]));
+        *rules |= (fabsf(delta[0]) == m ? 1u : fabsf(delta[1]) == m ? 2u : fabsf(delta[2]) == m ? 3u : 0u) << DU_R_MAX_SHIFT;
+    }
+    if (max3(fabsf(delta[0]), fabsf(delta[1]), fabsf(delta[2])) > k->irradianceThreshold) { h = fmaxf(0.0f, h - 0.75f); if (rules) *rules |= DU_R_IRRADIANCE; }
+    if (sqrtf(dot3(delta, delta)) > k->brightnessThreshold) { delta[0] = delta[0] * 0.25f; delta[1] = delta[1] * 0.25f; delta[2] = delta[2] * 0.25f; if (rules) *rules |= DU_R_BRIGHTNESS; }
     float step[3] = { (1.0f - h) * delta[0], (1.0f - h) * delta[1], (1.0f - h) * delta[2] };
     if (floorRule && max3(prev[0] + delta[0], prev[1] + delta[1], prev[2] + delta[2]) < max3(prev[0], prev[1], prev[2])) {
         const float t = 1.0f / 1024.0f;
+        if (rules) {
+            *rules |= DU_R_DARKER;
+            for (int c = 0; c < 3; ++c) {
+                const float floored = fmaxf(t, fabsf(step[c]));
+                if (fminf(floored, fabsf(delta[c])) != floored) *rules |= DU_R_CAP << c;
+                else if (floored != fabsf(step[c])) *rules |= DU_R_FLOOR << c;
+                if (sign1(step[c]) == 0.0f) *rules |= DU_R_SIGN_ZERO << c;
+            }
+        }
         for (int c = 0; c < 3; ++c) step[c] = fminf(fmaxf(t, fabsf(step[c])), fabsf(delta[c])) * sign1(step[c]);
     }
     for (int c = 0; c < 3; ++c) out[c] = prev[c] + step[c];
 }
+
+void du_ease_radiance(const DuConsts* k, const float res[3], const float prev[3], int floorRule, float out[3]) { ease_radiance(k, res, prev, floorRule, out, NULL); }
 
 uint32_t du_unorm10(float v) { return (uint32_t)rintf(saturate(v) * 1023.0f); }
 
@@ -356,7 +382,7 @@ static int blend_setup(const DuBlock* b, const uint16_t* data, const float* rays
 }
 
 /* irradiance: uint32 [slices][cz * 8][cx * 8], read and written */
-void du_blend_radiance(const DuBlock* b, const uint16_t* data, const float* rays, uint32_t* irradiance)
+static void blend_radiance(const DuBlock* b, const uint16_t* data, const float* rays, uint32_t* irradiance, uint32_t* rules)
 {
     const DgDesc* D = &b->D;
     const uint32_t N = 8u, W = (uint32_t)D->probeCounts[0] * N, H = (uint32_t)D->probeCounts[2] * N;
@@ -365,7 +391,7 @@ void du_blend_radiance(const DuBlock* b, const uint16_t* data, const float* rays
     for (uint32_t p = 0; p < probes; ++p) {
         int32_t c[3];
         float dir[DU_RAYS][3];
-        if (blend_setup(b, data, rays, p, c, dir)) continue;
+        if (blend_setup(b, data, rays, p, c, dir)) { if (rules) for (uint32_t t = 0; t < 36u; ++t) rules[(uint64_t)p * 36u + t] = DU_R_LEFT_ALONE; continue; }
         uint32_t* tile = irradiance + (uint64_t)c[1] * W * H + (uint64_t)((uint32_t)c[2] * N) * W + (uint32_t)c[0] * N;
         for (uint32_t ty = 1; ty <= N - 2u; ++ty)
             for (uint32_t tx = 1; tx <= N - 2u; ++tx) {
@@ -384,7 +410,16 @@ void du_blend_radiance(const DuBlock* b, const uint16_t* data, const float* rays
                     res[ch] = dg_pow(sum[ch] / den, invGamma);
                     prev[ch] = (float)((old >> (10 * ch)) & 1023u) / 1023.0f;
                 }
-                du_ease_radiance(&b->k, res, prev, 1, out);
+                uint32_t* rule = rules ? rules + (uint64_t)p * 36u + (ty - 1u) * 6u + (tx - 1u) : NULL;
+                if (rule) *rule = 0u;
+                ease_radiance(&b->k, res, prev, 1, out, rule);
+                if (rule)
+                    for (int ch = 0; ch < 3; ++ch) {
+                        if (out[ch] > 1.0f) *rule |= DU_R_CLAMP_ONE << ch;
+                        if (out[ch] < 0.0f) *rule |= DU_R_CLAMP_ZERO << ch;
+                        if (sum[ch] != sum[ch]) *rule |= DU_R_SUM_NAN | DU_R_NAN;
+                        if (res[ch] != res[ch] || out[ch] != out[ch]) *rule |= DU_R_NAN;
+                    }
                 tile[ty * W + tx] = du_unorm10(out[0]) | du_unorm10(out[1]) << 10 | du_unorm10(out[2]) << 20 | 3u << 30;
             }
         for (uint32_t ty = 0; ty < N; ++ty)
@@ -397,8 +432,12 @@ void du_blend_radiance(const DuBlock* b, const uint16_t* data, const float* rays
     }
 }
 
+void du_blend_radiance(const DuBlock* b, const uint16_t* data, const float* rays, uint32_t* irradiance) { blend_radiance(b, data, rays, irradiance, NULL); }
+/* the same, and rules: uint32 [numProbes][6][6], one word of DU_R_* bits per interior texel */
+void du_blend_radiance_rules(const DuBlock* b, const uint16_t* data, const float* rays, uint32_t* irradiance, uint32_t* rules) { blend_radiance(b, data, rays, irradiance, rules); }
+
 /* distance: uint16 [slices][cz * 16][cx * 16][2], read and written */
-void du_blend_distance(const DuBlock* b, const uint16_t* data, const float* rays, uint16_t* distance)
+static void blend_distance(const DuBlock* b, const uint16_t* data, const float* rays, uint16_t* distance, uint32_t* rules)
 {
     const DgDesc* D = &b->D;
     const uint32_t N = 16u, W = (uint32_t)D->probeCounts[0] * N, H = (uint32_t)D->probeCounts[2] * N;
@@ -407,7 +446,7 @@ void du_blend_distance(const DuBlock* b, const uint16_t* data, const float* rays
     for (uint32_t p = 0; p < probes; ++p) {
         int32_t c[3];
         float dir[DU_RAYS][3];
-        if (blend_setup(b, data, rays, p, c, dir)) continue;
+        if (blend_setup(b, data, rays, p, c, dir)) { if (rules) for (uint32_t t = 0; t < 196u; ++t) rules[(uint64_t)p * 196u + t] = DU_D_LEFT_ALONE; continue; }
         uint16_t* tile = distance + ((uint64_t)c[1] * W * H + (uint64_t)((uint32_t)c[2] * N) * W + (uint32_t)c[0] * N) * 2u;
         for (uint32_t ty = 1; ty <= N - 2u; ++ty)
             for (uint32_t tx = 1; tx <= N - 2u; ++tx) {
@@ -424,6 +463,21 @@ void du_blend_distance(const DuBlock* b, const uint16_t* data, const float* rays
                 uint16_t* t = tile + ((uint64_t)ty * W + tx) * 2u;
                 const float px = half_to_float(t[0]), py = half_to_float(t[1]);
                 const float h = (px == 0.0f && py == 0.0f) ? 0.0f : b->k.hysteresis;
+                if (rules) {
+                    uint32_t word = 0u, clipped = 0u;
+                    for (uint32_t r = 0; r < DU_RAYS; ++r) clipped += !(fabsf(rays[((uint64_t)p * DU_RAYS + r) * 4u + 3u]) <= maxDistance) ? 1u : 0u;
+                    if (px == 0.0f && py == 0.0f) word |= DU_D_PREV_ZERO;
+                    if (!(sumW >= 1e-9f * 256.0f)) word |= DU_D_SUMW_FLOOR;
+                    for (int ch = 0; ch < 2; ++ch) {
+                        const uint32_t before = t[ch] & 0x7FFFu, after = sm_half_bits(lerp1(ch ? ry : rx, ch ? py : px, h)) & 0x7FFFu;
+                        if (before == 0x7C00u) word |= DU_D_PREV_INF;
+                        if (before > 0x7C00u) word |= DU_D_PREV_NAN;
+                        if (after == 0x7C00u) word |= DU_D_STORE_INF;
+                        if (after > 0x7C00u) word |= DU_D_STORE_NAN;
+                        if (after != 0u && after < 0x0400u) word |= DU_D_STORE_SUBNORMAL;
+                    }
+                    rules[(uint64_t)p * 196u + (ty - 1u) * 14u + (tx - 1u)] = word | clipped << DU_D_CLIPPED_SHIFT;
+                }
                 t[0] = sm_half_bits(lerp1(rx, px, h)); t[1] = sm_half_bits(lerp1(ry, py, h));
             }
         for (uint32_t ty = 0; ty < N; ++ty)
@@ -435,3 +489,7 @@ void du_blend_distance(const DuBlock* b, const uint16_t* data, const float* rays
             }
     }
 }
+
+void du_blend_distance(const DuBlock* b, const uint16_t* data, const float* rays, uint16_t* distance) { blend_distance(b, data, rays, distance, NULL); }
+/* the same, and rules: uint32 [numProbes][14][14], one word of DU_D_* bits per interior texel */
+void du_blend_distance_rules(const DuBlock* b, const uint16_t* data, const float* rays, uint16_t* distance, uint32_t* rules) { blend_distance(b, data, rays, distance, rules); }

@@ -1,6 +1,7 @@
 """ctypes wrapper of tests/ddgi_update_ref.c, the definition of "giprobetrace_CS_ProbeTrace" and of the two
 "ProbeBlendingCS_DDGIProbeBlendingCS" passes (csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip, csrc/ray_walk.hip.h), and a numpy
-float64 restatement of the two blends for the precision check.
+float64 restatement of the two blends for the precision check.  blend_rules() also returns the rule the reference took at every
+interior texel (du_blend_radiance_rules, du_blend_distance_rules: the R_* and D_* bits below).
 
 The library is compiled by the test that needs it (gcc -O2 -ffp-contract=off) into a pytest temporary directory."""
 import ctypes as C
@@ -35,9 +36,11 @@ def _declare(lib):
     lib.du_unorm10.restype = u32
     lib.du_blend_radiance.argtypes = [vp] * 4
     lib.du_blend_distance.argtypes = [vp] * 4
+    lib.du_blend_radiance_rules.argtypes = [vp] * 5
+    lib.du_blend_distance_rules.argtypes = [vp] * 5
     lib.dg_oct_n.argtypes = [vp, u64, vp]
     for n in ("du_ray_direction", "du_oct_decode", "du_texel_direction", "du_closest_n", "du_trace", "du_probe_positions", "du_ease_radiance", "du_blend_radiance",
-              "du_blend_distance", "dg_oct_n"):
+              "du_blend_distance", "du_blend_radiance_rules", "du_blend_distance_rules", "dg_oct_n"):
         getattr(lib, n).restype = None
 
 
@@ -148,6 +151,34 @@ def blend(lib, k, vol, rays):
     return irr, dist
 
 
+# the rule bits of du_blend_radiance_rules and du_blend_distance_rules (tests/ddgi_update_ref.c: DU_R_*, DU_D_*); the per-channel
+# ones are shifted left by the channel
+R_LEFT_ALONE, R_PREV_ZERO, R_IRRADIANCE, R_BRIGHTNESS, R_DARKER = 1 << 0, 1 << 1, 1 << 2, 1 << 3, 1 << 4
+R_FLOOR, R_CAP, R_SIGN_ZERO, R_CLAMP_ONE, R_CLAMP_ZERO = 1 << 5, 1 << 8, 1 << 11, 1 << 14, 1 << 17
+R_NAN, R_MAX_SHIFT, R_SUM_NAN = 1 << 20, 21, 1 << 23
+D_LEFT_ALONE, D_PREV_ZERO, D_SUMW_FLOOR, D_STORE_INF, D_STORE_NAN, D_STORE_SUBNORMAL, D_PREV_INF, D_PREV_NAN = (1 << i for i in range(8))
+D_CLIPPED_SHIFT = 16
+
+
+def any_channel(bit):
+    return bit | bit << 1 | bit << 2
+
+
+def blend_rules(lib, k, vol, rays):
+    """blend(), and the rule the reference took at every interior texel: (irradiance, distance, radiance rules uint32
+    [numProbes, 6, 6], distance rules uint32 [numProbes, 14, 14]).  The same function bodies: the textures equal blend()'s."""
+    b = block(k, vol)
+    rays = np.ascontiguousarray(rays, F)
+    n = int(np.prod(vol.counts))
+    assert rays.size == n * RAYS * 4
+    irr, dist = np.ascontiguousarray(vol.irradiance, np.uint32).copy(), np.ascontiguousarray(vol.distance, np.float16).copy()
+    rr, dr = np.full((n, 6, 6), 0xFFFFFFFF, np.uint32), np.full((n, 14, 14), 0xFFFFFFFF, np.uint32)
+    data = _data16(vol)
+    lib.du_blend_radiance_rules(_p(b), _p(data), _p(rays), _p(irr), _p(rr))
+    lib.du_blend_distance_rules(_p(b), _p(data), _p(rays), _p(dist.view(np.uint16)), _p(dr))
+    return irr, dist, rr, dr
+
+
 def update(lib, k, vol, scene: Scene, rays_init=None):
     """One whole update of `vol` in place (trace, then both blends); returns the ray records."""
     rays, _ = trace(lib, k, vol, scene, WALK, rays_init)
@@ -163,10 +194,12 @@ def ease_radiance(lib, k, res, prev, floor_rule=True) -> np.ndarray:
 
 
 # ---- the float64 restatement of the two blends -------------------------------------------------------------------------------
-def blend64(lib, k, vol, rays):
+def blend64(lib, k, vol, rays, decisions=False):
     """The two blends in float64 from the same float32 inputs (ray records, ray and texel directions as the reference rounds them,
     the previous texels): (irradiance codes float64 [.., 3] before rounding, distance float64 [.., 2] before rounding, touched
-    bool per probe).  Texels of probes that are left alone hold NaN."""
+    bool per probe).  Texels of probes that are left alone hold NaN.  decisions=True adds two arrays of the irradiance texture's
+    shape: the R_IRRADIANCE | R_BRIGHTNESS bits as float64 decides them (uint32), and how far the nearer of the two compared
+    quantities is from its threshold (float64; inf where prev == 0 decides nothing)."""
     f8 = np.float64
     k = np.ascontiguousarray(k, I.DDGIUpdateConsts)
     cx, cy, cz = vol.counts
@@ -181,6 +214,7 @@ def blend64(lib, k, vol, rays):
     _, inactive = probe_positions(lib, vol)
     irr_out = np.full(vol.irradiance.shape + (3,), np.nan)
     dist_out = np.full(vol.distance.shape, np.nan)
+    taken, margin = np.zeros(vol.irradiance.shape, np.uint32), np.full(vol.irradiance.shape, np.inf)
     touched = np.zeros(n, bool)
     t6, t14 = texel_directions(lib, 6).astype(f8), texel_directions(lib, 14).astype(f8)
     for p in range(n):
@@ -199,7 +233,13 @@ def blend64(lib, k, vol, rays):
         prev = np.stack([((old >> s_) & 1023).astype(f8) / 1023.0 for s_ in (0, 10, 20)], -1)
         delta = res - prev
         h = np.where(np.abs(delta).max(-1) > thr_i, max(0.0, h0 - 0.75), h0)
-        delta = np.where((np.sqrt((delta * delta).sum(-1)) > thr_b)[..., None], delta * 0.25, delta)
+        length = np.sqrt((delta * delta).sum(-1))
+        eased = ~(prev == 0).all(-1)
+        with np.errstate(invalid="ignore"):
+            near = np.minimum(np.abs(np.abs(delta).max(-1) - thr_i), np.abs(length - thr_b))
+        taken[y, z * 8 + 1:z * 8 + 7, x * 8 + 1:x * 8 + 7] = np.where(eased, (np.abs(delta).max(-1) > thr_i) * R_IRRADIANCE | (length > thr_b) * R_BRIGHTNESS, 0)
+        margin[y, z * 8 + 1:z * 8 + 7, x * 8 + 1:x * 8 + 7] = np.where(eased, np.nan_to_num(near, nan=np.inf), np.inf)
+        delta = np.where((length > thr_b)[..., None], delta * 0.25, delta)
         step = (1 - h)[..., None] * delta
         darker = (prev + delta).max(-1) < prev.max(-1)
         floored = np.minimum(np.maximum(1.0 / 1024.0, np.abs(step)), np.abs(delta)) * np.sign(step)
@@ -215,7 +255,7 @@ def blend64(lib, k, vol, rays):
         oldd = vol.distance[y, z * 16 + 1:z * 16 + 15, x * 16 + 1:x * 16 + 15].astype(f8)
         hd = np.where((oldd == 0).all(-1), 0.0, h0)[..., None]
         dist_out[y, z * 16 + 1:z * 16 + 15, x * 16 + 1:x * 16 + 15] = r + hd * (oldd - r)
-    return irr_out, dist_out, touched
+    return (irr_out, dist_out, touched, taken, margin) if decisions else (irr_out, dist_out, touched)
 
 
 def interior_mask(shape_hw, n):

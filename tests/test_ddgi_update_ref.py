@@ -1,7 +1,9 @@
 """tests/ddgi_update_ref.c on the CPU: the definition of the DDGI probe update ("giprobetrace_CS_ProbeTrace" and the two
 "ProbeBlendingCS_DDGIProbeBlendingCS" passes).  The closest-hit walk of the product's node arrays against brute force over every
 triangle, the face rule, the encodings the lighting pass's query assumes, the hysteresis, which probes are left alone, the
-borders, and a float64 restatement of the two blends.  tests/test_gpu_ddgi_update.py holds the kernels to the same reference."""
+borders, a float64 restatement of the two blends, and what the cases of tests/ddgi_blend_scenes.py reach, counted from the
+reference's own rule words.  tests/test_gpu_ddgi_update.py, tests/test_gpu_ddgi_trace_scenes.py and
+tests/test_gpu_ddgi_blend_rules.py hold the kernels to the same reference."""
 import os
 import sys
 
@@ -10,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import ddgi_blend_scenes as BS  # noqa: E402
 import ddgi_placement_ref as DP  # noqa: E402
 import ddgi_update_ref as DU  # noqa: E402
 import ddgi_update_scenes as US  # noqa: E402
@@ -31,6 +34,16 @@ AXES = np.array([(1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 0, 1), (-0.0,
 # (profiles/ddgi/README.md records them).
 MEASURED_IRRADIANCE_CODES = 1                  # 7 of 1080 channels differ, each by one code
 MEASURED_DISTANCE_STEPS = 0.501                # of a binary16 step: the store's own rounding and no more
+# test_blend_cases_agree_with_float64 leaves out texels whose compared quantity is this close to a threshold: the float32 chain's
+# reach (256 products and sums at 2^-24 each, the soft pow at 2^-22 relative, on values below 1)
+FLOAT32_REACH = 2e-5
+
+
+class _Words:
+    """Lets BS.irradiance_tile address a plain array of the irradiance texture's shape."""
+
+    def __init__(self, irradiance, counts):
+        self.irradiance, self.counts = irradiance, counts
 
 
 @pytest.fixture(scope="module")
@@ -453,6 +466,239 @@ def test_blends_agree_with_float64(du, blended):
     assert m8.sum() == touched.sum() * 36 and m16.sum() == touched.sum() * 196
     assert diff.max() <= MEASURED_IRRADIANCE_CODES + 1
     assert ulps.max() <= MEASURED_DISTANCE_STEPS + 1
+
+
+# ---- 5b. the blends on both sides of every rule: what the cases of tests/ddgi_blend_scenes.py reach ------------------------------------------
+# Every count below comes from the rule words of DU.blend_rules: the reference's own binary32 decisions.
+def _count(rules, bit):
+    return int(np.count_nonzero(np.asarray(rules) & np.uint32(bit)))
+
+
+def _radiance_rules(du, names):
+    return [step[4] for name in names for step in BS.blend_case(du, name).steps]
+
+
+def test_rule_exports_leave_the_textures_as_the_blends_do(du, blended):
+    """du_blend_radiance_rules and du_blend_distance_rules are the blends' own function bodies: the textures equal DU.blend's word
+    for word, every rule word is written, and the left-alone bit is set on exactly the two probes that are left alone."""
+    vol, rays, k, irr, dist = blended
+    irr2, dist2, rr, dr = DU.blend_rules(du, k, vol, rays)
+    same(irr2, irr, "irradiance"); same(dist2.view(np.uint16), dist.view(np.uint16), "distance")
+    assert not np.any(rr == 0xFFFFFFFF) and not np.any(dr == 0xFFFFFFFF)
+    for rules in (rr, dr):
+        left = np.flatnonzero(rules.reshape(len(rules), -1)[:, 0] & 1)
+        assert list(left) == [US.BLEND_INACTIVE, US.BLEND_25_BACK] and np.all((rules[left] == 1)) and not np.any(np.delete(rules, left, 0) & 1)
+
+
+def test_blend_cases_ladders_put_texels_one_code_apart_on_both_sides_of_each_threshold(du):
+    """Pairs of texels of one tile whose previous codes on the ladder's channel differ by one and of which one takes the
+    threshold and the other does not: at least 8 per threshold; each channel decides the fmax of the three |delta| on at least
+    16 texels; with both thresholds 0 every texel takes both, with both infinite none does.  MEASURED over the 16 ladder cases:
+    84 pairs at the irradiance threshold, 84 at the brightness threshold (6 per case with finite thresholds: one per tile whose
+    ladder straddles it); x / y / z decide 3464 / 3454 / 3450 texels; the 1/1024 floor gives the step on 1553 texels and |delta|
+    on 6600."""
+    pairs = {DU.R_IRRADIANCE: 0, DU.R_BRIGHTNESS: 0}
+    decides = np.zeros(4, np.int64)
+    floor = cap = 0
+    for name in BS.LADDER_CASES:
+        c = BS.blend_case(du, name)
+        k, rays, irr, dist, rr, dr = c.steps[0]
+        decides += np.bincount((rr >> DU.R_MAX_SHIFT & 3).reshape(-1), minlength=4)
+        floor, cap = floor + _count(rr, DU.any_channel(DU.R_FLOOR)), cap + _count(rr, DU.any_channel(DU.R_CAP))
+        for p in range(len(rr)):
+            codes = DU.unpack10(BS.irradiance_tile(c.vol, p)).reshape(36, 3)[:, p // len(BS.LADDER_OFFSETS)]
+            order = np.argsort(codes)
+            assert np.all(np.diff(codes[order]) == 1)
+            for bit in pairs:
+                pairs[bit] += int(np.count_nonzero(np.diff((rr[p].reshape(36)[order] & bit).astype(np.int64))))
+        if "thresholds 0" in name:
+            assert _count(rr, DU.R_IRRADIANCE) == _count(rr, DU.R_BRIGHTNESS) == rr.size
+        if "thresholds inf" in name:
+            assert _count(rr, DU.R_IRRADIANCE) == _count(rr, DU.R_BRIGHTNESS) == 0
+    print(f"ladders: pairs one code apart on opposite sides: irradiance {pairs[DU.R_IRRADIANCE]}, brightness {pairs[DU.R_BRIGHTNESS]}; fmax decided by x / y / z on {[int(d) for d in decides[1:]]} texels; "
+          f"floor binds on {floor} texels, |delta| on {cap}")
+    assert pairs[DU.R_IRRADIANCE] >= 8 and pairs[DU.R_BRIGHTNESS] >= 8
+    assert decides[0] == 0 and decides[1:].min() >= 16
+    assert floor >= 16 and cap >= 16
+
+
+def test_blend_case_dark_reaches_black(du):
+    """Radiance 0 for 12 updates at h = 0.97: every previous code of BS.DARK_CODES is there; under "darker" a channel whose delta is
+    exactly 0 has sign(step) == 0, and the floor gives the step; after the last update every non-black channel has fallen by at
+    least one code per update (or reached 0).  MEASURED at update 0: darker on 684 of 720 texels (the 36 others are the cleared
+    tile), sign(step) == 0 on 648, the floor binding on 432; after 12 updates the codes are 0 but for 512 -> 166 and 1023 -> 177."""
+    c = BS.blend_case(du, "dark")
+    assert len(c.steps) == BS.DARK_UPDATES == 12
+    before = DU.unpack10(c.vol.irradiance)
+    assert {tuple(int(v) for v in DU.unpack10(BS.irradiance_tile(c.vol, p))[0, 0]) for p in range(20)} == set(BS.DARK_CODES)
+    rr = c.steps[0][4]
+    print(f"dark, update 0: darker {_count(rr, DU.R_DARKER)}, sign 0 {_count(rr, DU.any_channel(DU.R_SIGN_ZERO))}, floor {_count(rr, DU.any_channel(DU.R_FLOOR))}")
+    assert _count(rr, DU.R_DARKER) >= 600 and _count(rr, DU.any_channel(DU.R_SIGN_ZERO)) >= 600 and _count(rr, DU.any_channel(DU.R_FLOOR)) >= 100
+    prev = before
+    for step in c.steps:
+        now = DU.unpack10(step[2])
+        assert np.all(now <= np.maximum(prev - 1, 0)), "one code per update at least"
+        prev = now
+    assert np.all(prev <= np.maximum(before - 12, 0))
+    print(f"dark, after 12 updates: 512 -> {sorted(set(prev[before == 512]))}, 1023 -> {sorted(set(prev[before == 1023]))}, largest of the others {prev[before <= 8].max()}")
+    assert prev[before <= 8].max() == 0
+
+
+def test_blend_cases_bright_and_below_zero_reach_both_clamps(du):
+    """Stores above 1 over cleared tiles (the estimate whole), seeded tiles and tiles at code 1023, an estimate of 1e6 and more, a
+    negative sum, and stores below 0.  MEASURED (texels with a channel clamped at 1, per update): gamma 5: 222 / 228 / 0 / 324 of 324,
+    gamma 1: 259 / 298 / 0 / 324 (43 of them on the seeded tiles in update 0; 6 at gamma 5); the negative sums give res == 0 exactly on all 324; "below zero" clamps 280 of 324 texels at 0."""
+    for name in ("bright gamma 5", "bright gamma 1"):
+        c = BS.blend_case(du, name)
+        one = [_count(s[4], DU.any_channel(DU.R_CLAMP_ONE)) for s in c.steps]
+        print(f"{name}: texels clamped at 1 per update {one}")
+        assert c.steps[0][4][:3].all() and all(_count(c.steps[0][4][p], DU.R_PREV_ZERO) == 36 for p in range(3)), "cleared tiles"
+        assert all(_count(c.steps[0][4][p], DU.R_CLAMP_ONE << p) == 36 for p in range(3)), "the cleared tiles store res > 1 on the bright channel"
+        seeded = _count(c.steps[0][4][3:6], DU.any_channel(DU.R_CLAMP_ONE))
+        print(f"{name}: {seeded} texels of the seeded tiles eased to above 1 in update 0")
+        assert (seeded >= 16 or name != "bright gamma 1") and _count(c.steps[0][4][6:], DU.any_channel(DU.R_CLAMP_ONE)) == 108
+        assert one[3] == 324 and one[2] == 0 and _count(c.steps[2][4], DU.R_DARKER) == 324
+        assert not np.any(DU.unpack10(c.steps[2][2])[DU.unpack10(c.steps[1][2]) == 0]), "a negative sum is black, not a NaN"
+    zero = _count(BS.blend_case(du, "below zero").steps[0][4], DU.any_channel(DU.R_CLAMP_ZERO))
+    print(f"below zero: {zero} texels clamped at 0")
+    assert zero >= 16
+
+
+def test_blend_cases_records_reach_nan_sums_and_the_back_face_limit(du):
+    """The ten probes of BS.records: only the one with exactly 25 records of -2^-149 is left alone (the ones with -0.0 are blended);
+    NaN sums on at least 16 texels.  MEASURED: 54 texels with a NaN sum per update (36 behind the NaN radiance channel, 18 facing away
+    from the infinite ray), 72 with a NaN anywhere; the smallest sumW the skip leaves, on the texel whose 24 nearest rays are back
+    faces: 42.3 against 64.0 without the skip (the floor is 2.56e-7: see DESIGN.md 9, unreachable)."""
+    for name in ("records cleared", "records seeded"):
+        c = BS.blend_case(du, name)
+        for i, (k, rays, irr, dist, rr, dr) in enumerate(c.steps):
+            assert list(np.flatnonzero(rr[:, 0, 0] & 1)) == [BS.REC_25_SUBNORMAL] == list(np.flatnonzero(dr[:, 0, 0] & 1))
+            assert np.count_nonzero(rays[BS.REC_25_SUBNORMAL, :, 3] < 0) == 25 and np.count_nonzero(rays[BS.REC_24_AND_NEG_ZERO, :, 3] < 0) == 24
+            assert np.count_nonzero(np.signbit(rays[BS.REC_24_AND_NEG_ZERO, :, 3])) == 34 and np.count_nonzero(rays[BS.REC_24_NEAREST, :, 3] < 0) == 24
+            print(f"{name}, update {i}: NaN sums {_count(rr, DU.R_SUM_NAN)}, any NaN {_count(rr, DU.R_NAN)}")
+            assert _count(rr, DU.R_SUM_NAN) >= 16 and _count(rr[BS.REC_INF], DU.R_SUM_NAN) >= 8 and _count(rr[BS.REC_NAN_CHANNEL], DU.R_SUM_NAN) == 36
+            assert _count(dr[BS.REC_NAN_W], 1 << DU.D_CLIPPED_SHIFT | 0x1FF << DU.D_CLIPPED_SHIFT) == 196 and np.all(dr[BS.REC_ZERO_W] >> DU.D_CLIPPED_SHIFT == 0)
+    c = BS.blend_case(du, "records cleared")
+    k, rays = c.steps[0][0], c.steps[0][1]
+    w = np.maximum(0.0, DU.texel_directions(du, 6).astype(np.float64) @ DU.ray_directions(du, k).astype(np.float64).T)
+    kept = (w * ~(rays[BS.REC_24_NEAREST, :, 3] < 0)).sum(-1)
+    print(f"records: sumW at texel {BS.REC_TEXEL} with its 24 nearest rays skipped {kept[BS.REC_TEXEL[1], BS.REC_TEXEL[0]]:.2f}, unskipped {w.sum(-1)[BS.REC_TEXEL[1], BS.REC_TEXEL[0]]:.2f}")
+    assert kept.argmin() == BS.REC_TEXEL[1] * 6 + BS.REC_TEXEL[0] and kept.min() > 16.0
+
+
+def test_blend_cases_distance_range_leaves_binary16_at_both_ends(du):
+    """"distance far": at least 100 infinite halves after update 1; after update 2 (index 1) the infinities survive
+    (res + 0.9 * (inf - res)); update index 2, at h = 0, turns them into 0x7E00 (0 * inf) and the next eases from NaN texels.
+    "distance tiny": at least 100 subnormal halves.  "distance huge": the squared distance is a NaN everywhere.  "distance exponents": the (0, v) and (v, 0) texels are not cleared texels,
+    (-0.0, -0.0) is, and at exponent 30000 sumW is at its floor.  MEASURED: far: texels with an infinite half 328 / 342 / 93 / 96,
+    with a NaN half 0 / 0 / 342 / 342 (of 784); a SURVIVING INFINITY after update 2, no 0x7E00 before h = 0; tiny: all 784 texels
+    subnormal in both updates; huge: every texel holds (inf, NaN); exponents: sumW at its floor on 0 / 0 / 0 / 0 / 736 texels."""
+    far = BS.blend_case(du, "distance far")
+    inf, nan = [_count(s[5], DU.D_STORE_INF) for s in far.steps], [_count(s[5], DU.D_STORE_NAN) for s in far.steps]
+    print(f"distance far: texels with an infinite half {inf}, with a NaN half {nan}")
+    halves = far.steps[0][3].view(np.uint16)
+    assert np.count_nonzero((halves & 0x7FFF) == 0x7C00) >= 100 and inf[0] >= 100
+    assert _count(far.steps[1][5], DU.D_PREV_INF) >= 100 and inf[1] >= 100 and nan[1] == 0, "the infinity survives an update at h = 0.9"
+    assert nan[2] >= 100 and np.count_nonzero(far.steps[2][3].view(np.uint16) == 0x7E00) >= 100 and _count(far.steps[3][5], DU.D_PREV_NAN) >= 100
+    assert 0 < inf[0] < far.steps[0][5].size, "finite and infinite texels side by side"
+    tiny = BS.blend_case(du, "distance tiny")
+    sub = [_count(s[5], DU.D_STORE_SUBNORMAL) for s in tiny.steps]
+    print(f"distance tiny: texels with a subnormal half {sub}")
+    assert min(sub) >= 100
+    ex = BS.blend_case(du, "distance exponents")
+    floor = [_count(s[5], DU.D_SUMW_FLOOR) for s in ex.steps]
+    print(f"distance exponents: sumW at its floor on {floor} texels")
+    assert [float(s[0]["probeDistanceExponent"][0]) for s in ex.steps] == list(BS.EXPONENTS)
+    assert [_count(ex.steps[0][5][p], DU.D_PREV_ZERO) for p in range(4)] == [0, 0, 196, 0]
+    assert floor[4] >= 100 and floor[3] == 0
+    huge = BS.blend_case(du, "distance huge")
+    halves = huge.steps[0][3].view(np.uint16)[DU.interior_mask(huge.steps[0][3].shape[1:3], 16)[None]]
+    assert np.all(halves[..., 0] == 0x7C00) and np.all(halves[..., 1] == 0x7E00), "d * d overflows binary32: (d * d) * w is inf * 0 on the rays that face away"
+    clipped = [int((s[5] >> DU.D_CLIPPED_SHIFT).max()) for s in far.steps]
+    assert min(clipped) >= 1, "rays beyond maxDistance"
+
+
+def test_every_radiance_rule_is_taken_and_not_taken_across_the_blend_cases(du):
+    """Every radiance rule bit is set on at least 16 texels and clear on at least 16 across BS.BLEND_CASES; every distance bit
+    likewise.  MEASURED of 25 092 radiance words: left alone 144, prev == 0 5130, irradiance 6725, brightness 11 494, darker 12 900, NaN 288, floor
+    1232 / 1329 / 1396 (x / y / z), |delta| 7404 / 7337 / 6882, sign 0 3695 / 3714 / 3695, clamped at 1 554 / 549 / 552, at 0 153 / 165 / 163; of
+    136 612 distance words: sumW floor 736, store infinite 1643, NaN 1468, subnormal 1568, prev infinite 1155, prev NaN 734; the radiance sumW floor has no bit: it is unreachable
+    (DESIGN.md 9)."""
+    rr = np.concatenate([s[4].reshape(-1) for name in BS.BLEND_CASES for s in BS.blend_case(du, name).steps])
+    dr = np.concatenate([s[5].reshape(-1) for name in BS.BLEND_CASES for s in BS.blend_case(du, name).steps])
+    bits = [("left alone", DU.R_LEFT_ALONE), ("prev == 0", DU.R_PREV_ZERO), ("irradiance threshold", DU.R_IRRADIANCE), ("brightness threshold", DU.R_BRIGHTNESS), ("darker", DU.R_DARKER),
+            ("NaN", DU.R_NAN), ("NaN sum", DU.R_SUM_NAN)]
+    for what, bit in (("floor", DU.R_FLOOR), ("|delta| cap", DU.R_CAP), ("sign 0", DU.R_SIGN_ZERO), ("clamped at 1", DU.R_CLAMP_ONE), ("clamped at 0", DU.R_CLAMP_ZERO)):
+        bits += [(f"{what} {'xyz'[c]}", bit << c) for c in range(3)]
+    for what, bit in bits:
+        n = _count(rr, bit)
+        print(f"radiance, {what}: {n} of {rr.size}")
+        assert 16 <= n <= rr.size - 16, what
+    for what, bit in (("left alone", DU.D_LEFT_ALONE), ("prev == (0, 0)", DU.D_PREV_ZERO), ("sumW floor", DU.D_SUMW_FLOOR), ("store inf", DU.D_STORE_INF), ("store NaN", DU.D_STORE_NAN),
+                      ("store subnormal", DU.D_STORE_SUBNORMAL), ("prev inf", DU.D_PREV_INF), ("prev NaN", DU.D_PREV_NAN)):
+        n = _count(dr, bit)
+        print(f"distance, {what}: {n} of {dr.size}")
+        assert 16 <= n <= dr.size - 16, what
+
+
+@pytest.mark.parametrize("name", BS.TRACED)
+def test_blend_cases_behind_the_traces_meet_saturated_records_and_nothing_beyond(sm, dp, name):
+    """Three chained reference updates of the trace case under a light of strength 8.  The floors first set for this case (an
+    infinite record and 16 NaN sums in "attributes", 16 channels stored above 1) CANNOT be met behind the project's own trace,
+    whatever the scene or the light: a record is saturate(rgb), so an infinite emissive arrives as 1.0 and a NaN as 0.0, no sum
+    holds a NaN, and an estimate is at most (1 / 2) ^ (1 / gamma) = 0.871, code 891.  Hostile records reach the blends
+    from a supplied buffer only (BS.records, BS.bright).  What the strong light does reach is asserted instead: at least 16
+    record channels saturated at exactly 1.0 per update, every record finite and within [0, 1], no rule bit for a NaN or a clamp,
+    and both thresholds taken and not taken.  MEASURED per update, record channels at 1.0 (the misses' (1, 1, 1)
+    among them): attributes 11027 / 11063 / 11091, tlas 65 10652 / 10678 / 10732 of 13824; thresholds taken on 442 to 540 of 648 texels."""
+    c = trace_case(sm, dp, name)
+    state = c.volume()
+    rules = []
+    for step in range(BS.TRACED_UPDATES):
+        k = BS.traced_consts(name, step)
+        rays, _ = DU.trace(dp, k, state, c.scene, DU.WALK, c.init)
+        irr, dist, rr, dr = DU.blend_rules(dp, k, state, rays)
+        state.irradiance, state.distance = irr, dist
+        ones = int(np.count_nonzero(rays[..., :3] == 1.0))
+        print(f"{name}, update {step}: {ones} record channels at 1.0, thresholds taken {_count(rr, DU.R_IRRADIANCE)} / {_count(rr, DU.R_BRIGHTNESS)} of {rr.size}")
+        assert np.isfinite(rays).all() and rays[..., :3].min() >= 0.0 and rays[..., :3].max() <= 1.0 and ones >= 16
+        assert _count(rr, DU.R_NAN | DU.any_channel(DU.R_CLAMP_ONE) | DU.any_channel(DU.R_CLAMP_ZERO)) == 0
+        rules.append(rr)
+    rules = np.concatenate(rules)
+    for bit in (DU.R_IRRADIANCE, DU.R_BRIGHTNESS):
+        assert 16 <= _count(rules, bit) <= rules.size - 16
+
+
+@pytest.mark.parametrize("name", BS.FINITE_CASES)
+def test_blend_cases_agree_with_float64(du, name):
+    """The float64 restatement on the finite cases (the ladders, "dark", "bright" below 1e30, "below zero"), every update from the
+    state the reference left: stored codes within MEASURED_IRRADIANCE_CODES + 1 and distances within MEASURED_DISTANCE_STEPS + 1
+    binary16 steps.  Left out: texels at which float64 decides a threshold otherwise than the reference's rule bits say, or
+    within FLOAT32_REACH of one; at most 5 % of a case's texels (a condition: the ladders put few codes that close)."""
+    c = BS.blend_case(du, name)
+    texels = left_out = 0
+    worst = worst_d = 0.0
+    for step, (k, rays, irr, dist, rr, dr) in enumerate(c.steps):
+        if np.abs(rays[..., :3]).max() >= 1e30:
+            continue
+        vol = c.before(step)
+        irr64, dist64, touched, taken, margin = DU.blend64(du, k, vol, rays, decisions=True)
+        assert touched.all()
+        m8 = np.broadcast_to(DU.interior_mask(irr.shape[1:], 8), irr.shape)
+        ref_bits = np.zeros(irr.shape, np.uint32)
+        for p in range(len(rr)):
+            BS.irradiance_tile(_Words(ref_bits, vol.counts), p)[...] = rr[p] & (DU.R_IRRADIANCE | DU.R_BRIGHTNESS)
+        out = m8 & ((taken != ref_bits) | (margin < FLOAT32_REACH))
+        keep = m8 & ~out
+        texels, left_out = texels + int(m8.sum()), left_out + int(out.sum())
+        worst = max(worst, float(np.abs(DU.unpack10(irr)[keep] - np.rint(irr64[keep])).max()))
+        m16 = np.broadcast_to(DU.interior_mask(dist.shape[1:3], 16), dist.shape[:3])
+        got, want = dist[m16].astype(np.float64), dist64[m16]
+        worst_d = max(worst_d, float((np.abs(got - want) / 2.0 ** (np.floor(np.log2(np.maximum(np.abs(want), 2.0 ** -14))) - 10)).max()))
+    print(f"{name}: float64 agreement: irradiance max {worst:.0f} codes over {texels - left_out} texels, {left_out} left out; distance max {worst_d:.3f} binary16 steps")
+    assert left_out <= texels * 0.05
+    assert worst <= MEASURED_IRRADIANCE_CODES + 1
+    assert worst_d <= MEASURED_DISTANCE_STEPS + 1
 
 
 # ---- 6. the interface ------------------------------------------------------------------------------------------------------------------
