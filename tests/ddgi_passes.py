@@ -231,21 +231,3 @@ def city_trace_scene(tmp_path, oracle):
 def city_volume(bounds):
     """3 x 2 x 3 probes, the first and the last in opposite corners of the city's bounds; cleared."""
     return US.trace_volume((3, 2, 3), bounds[0], bounds[1], seeded=False)
-
-
-# ---- leaves that name an instance without flags -----------------------------------------------------------------------------------------------
-def unflagged_leaves(sm):
-    """The builder gives an instance that is in neither id list no leaf, so on a structure it built the walk's `flags == 0` rule never
-    decides.  This is the structure on which it does: "attributes" built with every instance listed and refitted once, then the
-    instances of US.ATTR_UNLISTED lose their flags in the TLAS records (and in the flags brute force reads), keeping their leaves,
-    boxes and object-from-world rows; a refit leaves such a record alone.  Returns (scene dict, SR.Accel with these arrays, the
-    instances that lost their flags)."""
-    sc = US.attributes(listed=True)
-    acc = SR.Accel(sc)
-    nodes, records = SR.refit(sm, acc)
-    off = [i for i in range(len(records)) if US.ATTR_UNLISTED(i)]
-    records["flags"][off] = 0
-    acc.tlas["nodes"], acc.tlas["records"] = nodes, records
-    acc.flags = np.array(acc.flags, np.uint32)
-    acc.flags[off] = 0
-    return sc, acc, off

@@ -3,11 +3,15 @@ on the GPU): a few hundred triangles at most, so that brute force over every tex
 
 A scene is a dict: vertices (RawVertexFormat), indices (uint32, per mesh relative to its first vertex), meshData (m_GlobalVertexBufferIdx
 and m_GlobalIndexBufferIdx set), index_counts (uint32 per mesh), instances (BasePassInstanceConstants), opaqueIds, alphaMaskIds,
-materials (MaterialData).  CASES lists what both test files run."""
+materials (MaterialData).  CASES lists what both test files run.
+
+WALK_CASES are the directed scenes of tests/test_gpu_shadow_walk_scenes.py: each sits on one rule of the any-hit walk (occluded() in
+csrc/k_shadowmask.hip) or of the refit, where the seeded CASES do not; tests/test_shadowmask_ref.py asserts that it does."""
 import os
 
 import numpy as np
 
+import shadowmask_ref as SR
 from toyrenderer_amd import accel, synth
 from toyrenderer_amd import interop as I
 
@@ -261,3 +265,176 @@ def case_inputs(case):
     else:
         k = consts(W, H, LIGHTS[light], soft, frame)
     return sc, k, depth, g, noise_image()
+
+
+# ---- the directed scenes of the walk ---------------------------------------------------------------------------------------------------------
+# name -> maker(sm) -> dict(sc, k, depth, g, noise, moved: the instances uploaded after the structure was built or None, singular: the
+# instances whose world matrix has no inverse, info: what the preconditions need).  sm is tests/shadowmask_ref.c's library: the TMin
+# ladder is built from the texels' own rays.
+TMIN = 0.25                                         # the ladder's m_RayStartOffset
+RUNGS = (0.25, 0.5, 0.9, 1.1, 2.0, 4.0)             # a rung's triangles lie at t = rung * TMIN on their texel's ray
+PER_RUNG = 24
+LADDER_INSTANCES = {"scale 1": dict(), "scale 0.25": dict(scale=(0.25, 0.25, 0.25)), "scale 4": dict(scale=(4.0, 4.0, 4.0)),
+                    "rotated": dict(axis=(0.3, 1.0, 0.2), angle=0.9), "mirrored": dict(scale=(1.0, -1.0, 1.0), axis=(0.1, 0.2, 1.0), angle=0.3)}
+LADDER_SCALE = {"scale 1": 1.0, "scale 0.25": 0.25, "scale 4": 4.0, "rotated": 1.0, "mirrored": 1.0}
+
+
+def _walk_case(sc, W, H, light, soft, name, ray_start_offset=0.01, frame=3, **extra):
+    depth, g = images(W, H, sum(ord(c) for c in name))
+    return dict(sc=sc, k=consts(W, H, light, soft, frame, ray_start_offset=ray_start_offset), depth=depth, g=g, noise=noise_image(), moved=None, singular=(), info={}, **extra)
+
+
+def ladder(sm, variant, soft):
+    """One triangle of circumradius 0.01 per chosen texel, across that texel's own ray (SR.texel_rays) at t = rung * TMIN, PER_RUNG
+    texels per rung, all in one instance placed by LADDER_INSTANCES[variant].  A texel is chosen only if its triangle's centre is
+    farther than 0.03 from every other texel's ray, so a ray meets its own triangle or none."""
+    name = f"ladder {variant} soft {soft}"
+    W, H = 67, 35
+    c = _walk_case(None, W, H, LIGHTS["generic"], soft, "ladder", ray_start_offset=TMIN)
+    valid, o, d, _ = SR.texel_rays(sm, c["k"], c["depth"], c["g"], c["noise"])
+    at = np.flatnonzero(valid.reshape(-1))
+    O, D = o.reshape(-1, 3)[at].astype(np.float64), d.reshape(-1, 3)[at].astype(np.float64)
+    rng = np.random.default_rng([41, int(soft)])
+    chosen, rungs, tris = [], [], []
+    for i in rng.permutation(len(at)):
+        rung = RUNGS[len(chosen) % len(RUNGS)]
+        centre = O[i] + rung * TMIN * D[i]
+        v = centre - O
+        off = np.linalg.norm(v - np.sum(v * D, 1, keepdims=True) * D / np.sum(D * D, 1, keepdims=True), axis=1)
+        off[i] = np.inf
+        if off.min() < 0.03:
+            continue
+        e = np.eye(3)[np.argmin(np.abs(D[i]))]
+        u = np.cross(D[i], e); u /= np.linalg.norm(u)
+        w = np.cross(D[i], u); w /= np.linalg.norm(w)
+        a = rng.uniform(0, 2 * np.pi) + np.arange(3) * (2 * np.pi / 3)
+        tris.append(centre + 0.01 * (np.cos(a)[:, None] * u + np.sin(a)[:, None] * w))
+        chosen.append(int(at[i])); rungs.append(rung)
+        if len(chosen) == PER_RUNG * len(RUNGS):
+            break
+    assert len(chosen) == PER_RUNG * len(RUNGS), f"{name}: only {len(chosen)} texels stand clear of their neighbours"
+    Wm = world_matrix(position=(0.5, 1.0, -5.0), **LADDER_INSTANCES[variant])
+    M = Wm.astype(np.float64)
+    p = ((np.concatenate(tris) - M[3, :3]) @ np.linalg.inv(M[:3, :3])).astype(F)
+    c["sc"] = make_scene([(p, np.arange(len(p), dtype=np.uint32))], [(0, Wm, 0, "opaque")])
+    c["info"] = dict(texels=np.array(chosen), rungs=np.array(rungs), scale=LADDER_SCALE[variant])
+    return c
+
+
+def far_roof(height, inner_scale, soft):
+    """Two triangles 2e11 wide at `height` over everything, the light straight up: the mesh 2e11 / inner_scale wide in an instance
+    of scale inner_scale (1e11: the unit quad, scaled in its plane only, as the alpha test's roof is)."""
+    if inner_scale == 1e11:
+        mesh, scale = quad(1.0), (1e11, 1.0, 1e11)
+    else:
+        mesh, scale = quad(1e11 / inner_scale), (inner_scale,) * 3
+    sc = make_scene([mesh], [(0, world_matrix(scale=scale, position=(0.0, height, 0.0)), 0, "opaque")])
+    return _walk_case(sc, 33, 17, LIGHTS["up"], soft, "far roof")
+
+
+SINGULAR = {"scale (1, 0, 1)": (1.0, 0.0, 1.0), "scale 0": (0.0, 0.0, 0.0), "scale 1e-20": (1e-20,) * 3, "scale 1e15": (1e15,) * 3}
+SINGULAR_INSTANCE = 3
+
+
+def singular(which, lst, soft):
+    """scattered(8) with instance 3's world matrix replaced by a scale that has no inverse in binary32 (or, 1e15, a barely finite
+    one) at the instance's place; lst "alpha": that instance in the alpha-mask list with material 3, which passes the alpha test."""
+    sc = scattered(8)
+    i = SINGULAR_INSTANCE
+    pos = sc["instances"]["m_WorldMatrix"][i][3, :3].copy()
+    sc["instances"]["m_WorldMatrix"][i] = sc["instances"]["m_PrevWorldMatrix"][i] = world_matrix(scale=SINGULAR[which], position=pos)
+    if lst == "alpha":
+        sc["opaqueIds"] = sc["opaqueIds"][sc["opaqueIds"] != i]
+        sc["alphaMaskIds"] = np.sort(np.append(sc["alphaMaskIds"], np.uint32(i))).astype(np.uint32)
+        sc["instances"]["m_MaterialDataIdx"][i] = 3
+    c = _walk_case(sc, 33, 17, LIGHTS["generic"], soft, "singular")
+    c["singular"] = (i,) if which != "scale 1e15" else ()
+    return c
+
+
+def chain(n=64):
+    """The hostile scene of the TLAS's depth: instances along the light's direction from the world's origin (binary32 keeps small
+    distances apart there), in groups whose distance grows by 2.4 from group to group, each group an eighth of what is left below it
+    (at least one): the builder's midpoint split peels one group per level for as long as it trusts its heuristic.  Mirrors
+    collinear_growing() for the BLAS.  Unrotated tetrahedra and quads: their boxes are symmetric, so a box's centre is the instance's
+    position whatever its scale, which stays between 0.05 and 1.5 although the nearest group is 1e-6 from the origin: instances
+    that shrink with their distance would be far smaller than any shadow ray can resolve (profiles/shadowmask/README.md, "An open
+    question")."""
+    sizes, left = [], n
+    while left:
+        sizes.append(max(left // 8, 1)); left -= sizes[-1]
+    sizes = sizes[::-1]                                                       # the nearest group first
+    rng = np.random.default_rng([13, n])
+    light = np.array(LIGHTS["generic"], np.float64)
+    placements, dist = [], 1e4 * 2.4 ** -len(sizes)
+    for size in sizes:
+        dist *= 2.4
+        for j in range(size):
+            d = dist * (1.0 + 0.02 * j)
+            jitter = 0.05 * d * rng.uniform(-1, 1, 2)
+            k = len(placements)
+            W = world_matrix(scale=np.array([1.0, 1.0, 1.0]) * float(np.clip(0.1 * d, 0.05, 1.5)), position=light * d + np.array([jitter[0], 0.0, jitter[1]]))
+            placements.append((k % 2, W, k % 2, "opaque"))
+    return make_scene([tetrahedron(), quad(1.0)], placements)
+
+
+def moved_tenth(sc, seed=17):
+    """The scene's instances with every tenth one (i % 10 == 3) carried 10 to 20 units away, out of its rest box."""
+    rng = np.random.default_rng([seed, len(sc["instances"])])
+    moved = sc["instances"].copy()
+    for i in range(3, len(moved), 10):
+        v = rng.normal(size=3)
+        moved["m_PrevWorldMatrix"][i] = moved["m_WorldMatrix"][i]
+        moved["m_WorldMatrix"][i][3, :3] += (v / np.linalg.norm(v) * rng.uniform(10.0, 20.0)).astype(F)
+    return moved
+
+
+def large(which, moved, soft):
+    """scattered(513), scattered(1025) (a refit level of 378 inner nodes: the one workgroup of 256 threads strides it twice) or the
+    chain; moved: moved_tenth() is uploaded after the structure was built, so the refit changes boxes on every level."""
+    sc = chain() if which == "chain" else scattered(int(which))
+    c = _walk_case(sc, 33, 17, LIGHTS["generic"], soft, "large")
+    if moved:
+        c["moved"] = moved_tenth(sc)
+    return c
+
+
+PAST_MATERIALS = {"numMaterials": 4, "0xFFFFFFFF": 0xFFFFFFFF}
+
+
+def past_material_roof(lst, which, soft):
+    """The alpha test's roof over everything with a material index past the 4 materials: in the alpha-mask list it casts nothing
+    (material 0, which a clamped index would read, passes the alpha test), in the opaque list the index is never read."""
+    roof = world_matrix(scale=(60.0, 1.0, 60.0), position=(0.0, 30.0, 0.0))
+    speck = world_matrix(scale=(0.01, 0.01, 0.01), position=(0.0, -50.0, 0.0))
+    sc = make_scene([quad(1.0), tetrahedron()], [(1, speck, 0, "opaque"), (0, roof, PAST_MATERIALS[which], lst)])
+    return _walk_case(sc, 33, 17, LIGHTS["up"], soft, "past material")
+
+
+EDGE_LIGHTS = {"zero": (0.0, 0.0, 0.0), "two equal largest": unit((1.0, 1.0, 0.0))}
+
+
+def edge_light(which, soft):
+    """scattered(65) under the zero vector (every ray is NaN) or under a light whose two largest components are equal (the
+    triangle test's choice of the ray's largest axis meets a tie)."""
+    return _walk_case(scattered(65), 33, 17, EDGE_LIGHTS[which], soft, "edge light")
+
+
+WALK_CASES = {}
+for _soft in (False, True):
+    _s = "soft" if _soft else "hard"
+    for _v in LADDER_INSTANCES:
+        WALK_CASES[f"ladder {_v} {_s}"] = (lambda sm, v=_v, soft=_soft: ladder(sm, v, soft))
+    for _n, (_h, _i) in {"tmax roof at 5e9": (5e9, 1e11), "tmax roof at 2e10": (2e10, 1e11), "tmax roof at 5e9 scale 1e3": (5e9, 1e3),
+                      "tmax roof at 2e10 scale 1e3": (2e10, 1e3)}.items():
+        WALK_CASES[f"{_n} {_s}"] = (lambda sm, h=_h, i=_i, soft=_soft: far_roof(h, i, soft))
+    for _w in SINGULAR:
+        for _l in ("opaque", "alpha"):
+            WALK_CASES[f"singular {_w} {_l} {_s}"] = (lambda sm, w=_w, lst=_l, soft=_soft: singular(w, lst, soft))
+    for _w, _m in (("513", False), ("1025", False), ("1025", True), ("chain", False), ("chain", True)):
+        WALK_CASES[f"tlas {_w}{' moved' if _m else ''} {_s}"] = (lambda sm, w=_w, m=_m, soft=_soft: large(w, m, soft))
+    for _l in ("alpha", "opaque"):
+        for _w in PAST_MATERIALS:
+            WALK_CASES[f"material {_w} {_l} {_s}"] = (lambda sm, lst=_l, w=_w, soft=_soft: past_material_roof(lst, w, soft))
+    WALK_CASES[f"light zero {_s}"] = (lambda sm, soft=_soft: edge_light("zero", soft))
+WALK_CASES["light two equal largest hard"] = (lambda sm: edge_light("two equal largest", False))

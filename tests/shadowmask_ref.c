@@ -215,7 +215,8 @@ int sm_box_hit(const float* lo, const float* hi, const SmRay* r)
     return tenter <= texit;
 }
 
-int sm_tri_hit(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax)
+/* the edge test and det != 0 of sm_tri_hit: 1 with the candidate's t, which sm_tri_hit then holds against the ray's interval */
+static int tri_candidate(F3 v0, F3 v1, F3 v2, const SmRay* r, float* tOut)
 {
     const F3 A = { v0.x - r->o.x, v0.y - r->o.y, v0.z - r->o.z }, B = { v1.x - r->o.x, v1.y - r->o.y, v1.z - r->o.z }, C = { v2.x - r->o.x, v2.y - r->o.y, v2.z - r->o.z };
     const float Akz = sel(A, r->kz), Bkz = sel(B, r->kz), Ckz = sel(C, r->kz);
@@ -228,7 +229,14 @@ int sm_tri_hit(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax)
     if (det == 0.0f) return 0;
     const float Az = r->Sz * Akz, Bz = r->Sz * Bkz, Cz = r->Sz * Ckz;
     const float T = (U * Az + V * Bz) + W * Cz;
-    const float t = T / det;
+    *tOut = T / det;
+    return 1;
+}
+
+int sm_tri_hit(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax)
+{
+    float t;
+    if (!tri_candidate(v0, v1, v2, r, &t)) return 0;
     return t > tmin && t < tmax;
 }
 
@@ -369,6 +377,46 @@ static int occluded_walk(const SmScene* s, F3 o, F3 d, float tmin, float tmax, u
         node = next;
     }
     return 0;
+}
+
+/* The candidates of every texel's ray, for the tests' preconditions: brute force's loop over every triangle of every instance with
+ * flags, WITHOUT the interval test and without the alpha test: each triangle that passes the edge test with det != 0, as (texel,
+ * instance, t).  The direction is not normalised in object space, so t is the world's.  Returns how many there are; the first
+ * `capacity` of them are stored. */
+uint32_t sm_candidates(const SmConsts* k, const SmScene* s, const float* depth, const uint32_t* gbufferA, const uint32_t* noise, uint32_t capacity, uint32_t* texels,
+                       uint32_t* insts, float* ts)
+{
+    uint32_t n = 0;
+    for (uint32_t py = 0; py < k->H; ++py)
+        for (uint32_t px = 0; px < k->W; ++px) {
+            const uint64_t at = (uint64_t)py * k->W + px;
+            float o[3], d[3], w[3];
+            if (!sm_texel_ray(k, px, py, depth[at], gbufferA + 4 * at, noise, o, d, w)) continue;
+            const F3 O = { o[0], o[1], o[2] }, D = { d[0], d[1], d[2] };
+            for (uint32_t i = 0; i < s->numInstances; ++i) {
+                const uint32_t mesh = s->instances[i].mesh;
+                if (!(s->flags[i] & 3u) || mesh >= s->numMeshes) continue;
+                float m[12];
+                sm_object_from_world(s->instances[i].world, m);
+                const SmRay r = make_ray(mul_point(O, m, 1), mul_point(D, m, 0));
+                for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t) {
+                    const uint64_t base = (uint64_t)s->meshes[mesh].indexBase + 3ull * t;
+                    if (base + 3u > s->numIndices) continue;
+                    F3 v[3];
+                    int ok = 1;
+                    for (int j = 0; ok && j < 3; ++j) {
+                        const uint64_t vi = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + j];
+                        ok = vi < s->numVertices;
+                        if (ok) { v[j] = vertex_of(s, vi); ok = finite3(v[j]); }
+                    }
+                    float tc;
+                    if (!ok || !tri_candidate(v[0], v[1], v[2], &r, &tc)) continue;
+                    if (n < capacity) { texels[n] = (uint32_t)at; insts[n] = i; ts[n] = tc; }
+                    ++n;
+                }
+            }
+        }
+    return n;
 }
 
 /* The pass over a whole image.  mode 0: brute force, 1: the walk.  mask and lvd hold what the targets held before. */

@@ -40,6 +40,8 @@ def _declare(lib):
     lib.sm_texel_ray.argtypes = [vp, u32, u32, C.c_float, vp, vp, vp, vp, vp]
     lib.sm_trace.argtypes = [vp, C.POINTER(_Scene), vp, vp, vp, C.c_int, vp, vp, vp]
     lib.sm_trace.restype = None
+    lib.sm_candidates.argtypes = [vp, C.POINTER(_Scene), vp, vp, vp, u32, vp, vp, vp]
+    lib.sm_candidates.restype = u32
 
 
 def load(tmpdir) -> C.CDLL:
@@ -66,6 +68,18 @@ def refit(lib, acc: Accel, instances=None):
     return nodes, records
 
 
+def _scene(acc: Accel, inst, nodes, records):
+    """(the _Scene of `acc` with these instances and TLAS arrays, the arrays it points into: keep them alive)."""
+    sc = acc.scene
+    keep = [inst, np.ascontiguousarray(acc.flags, np.uint32), np.ascontiguousarray(sc["vertices"], I.RawVertexFormat), np.ascontiguousarray(sc["materials"], I.MaterialData),
+            np.ascontiguousarray(sc["indices"], np.uint32), np.ascontiguousarray(sc["meshData"], I.MeshData), np.ascontiguousarray(acc.blas["index_counts"], np.uint32),
+            np.ascontiguousarray(nodes, I.AccelNode), np.ascontiguousarray(records, I.TLASInstance), np.ascontiguousarray(acc.blas["headers"]),
+            np.ascontiguousarray(acc.blas["nodes"]), np.ascontiguousarray(acc.blas["tri_order"], np.uint32)]
+    p = [a.ctypes.data for a in keep]
+    return _Scene(p[0], p[1], len(inst), p[2], len(keep[2]), p[3], len(keep[3]), p[4], len(keep[4]), p[5], p[6], len(keep[5]), p[7], len(keep[7]), p[8], p[9], p[10],
+               len(keep[10]), p[11], len(keep[11])), keep
+
+
 def trace(lib, k, acc: Accel, depth, gbuffer, noise, mode, instances=None, nodes=None, records=None, mask=None, lvd=None):
     """The pass over one image: (mask uint8 [H, W], linear view depth words uint16 [H, W], (box tests, triangle tests)).  mode BRUTE
     is the definition; WALK walks `nodes` / `records` (default: the refit of `instances`)."""
@@ -77,13 +91,7 @@ def trace(lib, k, acc: Accel, depth, gbuffer, noise, mode, instances=None, nodes
         nodes, records = refit(lib, acc, inst)
     if nodes is None:
         nodes, records = acc.tlas["nodes"], acc.tlas["records"]
-    keep = [inst, np.ascontiguousarray(acc.flags, np.uint32), np.ascontiguousarray(sc["vertices"], I.RawVertexFormat), np.ascontiguousarray(sc["materials"], I.MaterialData),
-            np.ascontiguousarray(sc["indices"], np.uint32), np.ascontiguousarray(sc["meshData"], I.MeshData), np.ascontiguousarray(acc.blas["index_counts"], np.uint32),
-            np.ascontiguousarray(nodes, I.AccelNode), np.ascontiguousarray(records, I.TLASInstance), np.ascontiguousarray(acc.blas["headers"]),
-            np.ascontiguousarray(acc.blas["nodes"]), np.ascontiguousarray(acc.blas["tri_order"], np.uint32)]
-    p = [a.ctypes.data for a in keep]
-    s = _Scene(p[0], p[1], len(inst), p[2], len(keep[2]), p[3], len(keep[3]), p[4], len(keep[4]), p[5], p[6], len(keep[5]), p[7], len(keep[7]), p[8], p[9], p[10],
-               len(keep[10]), p[11], len(keep[11]))
+    s, keep = _scene(acc, inst, nodes, records)
     depth = np.ascontiguousarray(depth, F).reshape(H, W)
     g = np.ascontiguousarray(gbuffer, np.uint32).reshape(H, W, 4)
     nz = np.ascontiguousarray(accel.noise_words(noise))
@@ -107,3 +115,23 @@ def texel_rays(lib, k, depth, gbuffer, noise):
             valid[y, x] = bool(lib.sm_texel_ray(k.ctypes.data, x, y, C.c_float(float(depth[y, x])), g[y, x].ctypes.data, nz.ctypes.data, o[y, x].ctypes.data,
                                                 d[y, x].ctypes.data, w[y, x].ctypes.data))
     return valid, o, d, w
+
+
+def candidates(lib, k, acc: Accel, depth, gbuffer, noise, instances=None):
+    """Every triangle of an instance with flags that a texel's ray meets anywhere on its line (the edge test and det != 0 of the
+    triangle test, WITHOUT TMin < t < TMax and without the alpha test), by brute force: (texel index y * W + x uint32 [n], instance
+    uint32 [n], world-space t float32 [n])."""
+    k = np.ascontiguousarray(k, I.ShadowMaskConsts)
+    W, H = (int(x) for x in k["m_OutputResolution"][0])
+    inst = np.ascontiguousarray(acc.scene["instances"] if instances is None else instances, I.BasePassInstanceConstants)
+    s, keep = _scene(acc, inst, acc.tlas["nodes"], acc.tlas["records"])
+    depth = np.ascontiguousarray(depth, F).reshape(H, W)
+    g = np.ascontiguousarray(gbuffer, np.uint32).reshape(H, W, 4)
+    nz = np.ascontiguousarray(accel.noise_words(noise))
+    cap = 1 << 16
+    while True:
+        texels, insts, ts = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, F)
+        n = int(lib.sm_candidates(k.ctypes.data, C.byref(s), depth.ctypes.data, g.ctypes.data, nz.ctypes.data, cap, texels.ctypes.data, insts.ctypes.data, ts.ctypes.data))
+        if n <= cap:
+            return texels[:n].copy(), insts[:n].copy(), ts[:n].copy()
+        cap = n

@@ -342,3 +342,22 @@ def shadow_case_reference(sm, case):
         mask, lvd, _ = SM.trace(sm, k, acc, depth, g, noise, SM.BRUTE)
         _SHADOW_REF[case[0]] = (sc, acc, k, depth, g, noise, mask, lvd)
     return _SHADOW_REF[case[0]]
+
+
+# ---- leaves that name an instance without flags -----------------------------------------------------------------------------------------------
+def unflagged_leaves(sm):
+    """The builder gives an instance that is in neither id list no leaf, so on a structure it built the walk's `flags == 0` rule never
+    decides.  This is the structure on which it does: "attributes" built with every instance listed and refitted once, then the
+    instances of ddgi_update_scenes.ATTR_UNLISTED lose their flags in the TLAS records (and in the flags brute force reads), keeping their leaves,
+    boxes and object-from-world rows; a refit leaves such a record alone.  Returns (scene dict, SM.Accel with these arrays, the
+    instances that lost their flags)."""
+    import ddgi_update_scenes as US
+    sc = US.attributes(listed=True)
+    acc = SM.Accel(sc)
+    nodes, records = SM.refit(sm, acc)
+    off = [i for i in range(len(records)) if US.ATTR_UNLISTED(i)]
+    records["flags"][off] = 0
+    acc.tlas["nodes"], acc.tlas["records"] = nodes, records
+    acc.flags = np.array(acc.flags, np.uint32)
+    acc.flags[off] = 0
+    return sc, acc, off

@@ -18,9 +18,9 @@ import ddgi_update_ref as DU  # noqa: E402
 import ddgi_update_scenes as US  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
-from ddgi_passes import city_trace_scene, city_volume, trace_case, unflagged_leaves  # noqa: E402
+from ddgi_passes import city_trace_scene, city_volume, trace_case  # noqa: E402
 from ref_build import layout_probe  # noqa: E402
-from suite_support import ref_library, same, sm  # noqa: E402, F401
+from suite_support import ref_library, same, sm, unflagged_leaves  # noqa: E402, F401
 from toyrenderer_amd import ddgi  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
@@ -262,7 +262,7 @@ def test_trace_case_attributes_reaches_every_attribute(sm, dp):
 
 def test_unflagged_leaves_are_skipped_and_would_be_hit(sm, dp):
     """The builder leaves an instance that is in neither list out of the tree, so in "attributes" no leaf names one and the walk's
-    `flags == 0` rule decides nothing there.  ddgi_passes.unflagged_leaves is the structure where it decides: 7 instances keep
+    `flags == 0` rule decides nothing there.  suite_support.unflagged_leaves is the structure where it decides: 7 instances keep
     their leaves, boxes and matrices and lose their flags.  The walk over it equals brute force and equals the "attributes"
     records word for word (another tree, the same answer), and every one of the 7 has a leaf whose box the refit left alone.
     MEASURED: the 15 rays of the test above are the ones that would end on them."""

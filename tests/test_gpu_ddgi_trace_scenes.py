@@ -20,8 +20,8 @@ import ddgi_update_ref as DU  # noqa: E402
 import ddgi_update_scenes as US  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
-from ddgi_passes import CLASSIFICATION, RAY_SENTINEL, RELOCATION, Placement, Update, city_trace_scene, city_volume, refitted_structure, trace_case, unflagged_leaves  # noqa: E402
-from suite_support import bare_gpu_scene, dev, gpu_scene, ref_library, same, sm  # noqa: E402, F401
+from ddgi_passes import CLASSIFICATION, RAY_SENTINEL, RELOCATION, Placement, Update, city_trace_scene, city_volume, refitted_structure, trace_case  # noqa: E402
+from suite_support import bare_gpu_scene, dev, gpu_scene, ref_library, same, sm, unflagged_leaves  # noqa: E402, F401
 from toyrenderer_amd import gltf_lite  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -116,7 +116,7 @@ def test_fixed_ray_trace_matches_the_reference(dev, sm, dp, name, volume):
 
 @pytest.mark.parametrize("which", ["probe trace", "fixed rays"])
 def test_a_leaf_whose_instance_has_no_flags_is_skipped(dev, sm, dp, which):
-    """ddgi_passes.unflagged_leaves: 7 instances of "attributes" keep their leaves, boxes and object-from-world rows and lose their
+    """suite_support.unflagged_leaves: 7 instances of "attributes" keep their leaves, boxes and object-from-world rows and lose their
     flags (the builder gives such an instance no leaf, so in "attributes" itself the walk's `flags == 0` rule decides nothing).  The
     arrays are uploaded over the ones set_raytracing() built; the refit in front of the trace leaves those records alone (asserted:
     the structure read back equals the reference's, byte for byte).  Each trace skips them: the ray records equal the reference,

@@ -14,74 +14,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import lighting_ref as LR  # noqa: E402
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
+from shadow_passes import REFIT, TRACE, Pass as _Pass  # noqa: E402
 from suite_support import bare_gpu_scene as _gpu_scene, dev, gpu_scene, lr, op_counts, recorded, same, shadow_case_reference, sm  # noqa: E402, F401
 from toyrenderer_amd import accel, cached_scene, gltf_lite, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-TRACE, REFIT = "shadowmask_CS_ShadowMask", "raytracing_CS_RefitTLAS"
-
-
-class _Pass:
-    """The textures of one size over one GpuScene: refit + trace through rhi bindings, targets pre-filled."""
-
-    def __init__(self, dev, gs, W, H, noise):
-        from toyrenderer_amd import rhi
-        self.dev, self.gs, self.W, self.H = dev, gs, W, H
-        self.depth = dev.create_texture(W, H, 1, rhi.FORMAT_R32_FLOAT, "Depth Buffer")
-        self.gbuffer = dev.create_texture(W, H, 1, rhi.FORMAT_RGBA32_UINT, "GBufferA")
-        self.mask = dev.create_texture(W, H, 1, rhi.FORMAT_R8_UNORM, "Shadow Mask Texture")
-        self.lvd = dev.create_texture(W, H, 1, rhi.FORMAT_R16_FLOAT, "Linear View Depth")
-        self.noise = dev.create_texture(128, 128, 1, rhi.FORMAT_RGBA8_UNORM, "Blue Noise", uav=False)
-        self.noise.upload_mip(0, accel.noise_words(noise))
-        self.cl = dev.create_command_list()
-
-    def refit_bindings(self):
-        from toyrenderer_amd.rhi import PUSH, SRV, UAV
-        gs, rt = self.gs, self.gs.rt
-        return [PUSH(0), SRV(0, gs.instances), SRV(1, rt["headers"]), SRV(2, rt["blas_nodes"]), SRV(3, rt["level_offsets"]), SRV(4, rt["level_nodes"]),
-                UAV(0, rt["tlas_nodes"]), UAV(1, rt["tlas_instances"])]
-
-    def refit_push(self):
-        k = np.zeros(1, I.RefitTLASConstants)
-        k["m_NumInstances"], k["m_NumNodes"], k["m_NumLevels"] = self.gs.numInstances, len(self.gs.rt["tlas"]["nodes"]), self.gs.rt["tlas"]["num_levels"]
-        return k
-
-    def trace_bindings(self, cb):
-        from toyrenderer_amd.rhi import CB, SAMPLER, SRV, TEX_SRV, TEX_UAV
-        gs, rt = self.gs, self.gs.rt
-        return [CB(0, cb), TEX_SRV(0, self.depth), SRV(1, rt["tlas_nodes"]), TEX_SRV(2, self.gbuffer), SRV(3, gs.instances), SRV(4, gs.vertices), SRV(5, gs.materials),
-                SRV(6, gs.indices), SRV(7, gs.meshData), TEX_SRV(8, self.noise), TEX_UAV(0, self.mask, 0), TEX_UAV(1, self.lvd, 0), SRV(9, rt["tlas_instances"]),
-                SRV(10, rt["headers"]), SRV(11, rt["blas_nodes"]), SRV(12, rt["tri_order"]), SAMPLER(0), SAMPLER(1)]
-
-    def groups(self):
-        return ((self.W + 7) // 8, (self.H + 7) // 8, 1)
-
-    def run(self, k, depth, g, refit=True):
-        self.depth.upload_mip(0, np.ascontiguousarray(depth, F))
-        self.gbuffer.upload_mip(0, np.ascontiguousarray(g, np.uint32))
-        self.mask.upload_mip(0, np.full((self.H, self.W), SR.SENTINEL8, np.uint8))
-        self.lvd.upload_mip(0, np.full((self.H, self.W), SR.SENTINEL16, np.uint16))
-        self.cl.open()
-        if refit:
-            self.cl.dispatch(REFIT, self.refit_bindings(), ((self.gs.numInstances + 63) // 64, 1, 1), push=self.refit_push())
-        cb = self.cl.constant_buffer(np.ascontiguousarray(k, I.ShadowMaskConsts), "ShadowMaskConsts")
-        self.cl.dispatch(TRACE, self.trace_bindings(cb), self.groups())
-        self.cl.close()
-        self.dev.execute(self.cl); self.dev.wait_idle()
-        return self.mask.download_mip(0), self.lvd.download_mip(0)
-
-    def structure(self):
-        rt = self.gs.rt
-        return rt["tlas_nodes"].download(I.AccelNode, len(rt["tlas"]["nodes"])), rt["tlas_instances"].download(I.TLASInstance, self.gs.numInstances)
-
-    def release(self):
-        self.cl.release()
-        for t in (self.depth, self.gbuffer, self.mask, self.lvd, self.noise):
-            t.release()
-
-
 # ---- 1. the cases -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", SS.CASES, ids=lambda c: c[0])
 def test_cases_match_brute_force(dev, sm, case):

@@ -1,7 +1,9 @@
 """The ray-traced shadow mask on the CPU: the builder's invariants (csrc/accel_build.cpp through toyrenderer_amd/accel.py), the walk of the
 product's node arrays against brute force over every triangle for every texel of every case the GPU tests run (tests/shadow_scenes.py
 CASES; zero differing texels allowed: a difference is a box that rejected a triangle the triangle test accepts), brute force against
-an analytic shadow, the pieces of the convention, the constant block and the driver's refusals.  No GPU."""
+an analytic shadow, the pieces of the convention, the constant block and the driver's refusals; and the preconditions of the directed
+scenes (tests/shadow_scenes.py WALK_CASES, which tests/test_gpu_shadow_walk_scenes.py runs on the GPU): each is shown here to sit on both
+sides of the rule it is for, so a case that drifts off its rule fails here instead of passing silently there.  No GPU."""
 import math
 import os
 import sys
@@ -14,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import shadow_scenes as SS  # noqa: E402
 import shadowmask_ref as SR  # noqa: E402
+from shadow_passes import unflagged_case, walk_case  # noqa: E402
 from suite_support import shadow_case_reference, sm  # noqa: E402, F401
 from toyrenderer_amd import accel, synth  # noqa: E402
 from toyrenderer_amd import interop as I  # noqa: E402
@@ -294,3 +297,156 @@ def test_registry_and_abi_list_the_feature():
     for n in ("trhip_blas_build", "trhip_tlas_build", "trhip_accel_max_depth", "trhip_blas_leaf_capacity", "trhip_accel_max_nodes"):
         assert n in rhi.ABI_SYMBOLS and hasattr(rhi.load(), n)
     assert rhi.load().trhip_abi_version() == 1
+
+
+# ---- 6. the directed scenes of the walk: what each must show ---------------------------------------------------------------------------------
+TMAX = 1e10
+
+
+@pytest.mark.parametrize("name", list(SS.WALK_CASES))
+def test_walk_case_walk_equals_brute_force(sm, name):
+    """Every directed case: the walk of the refitted arrays equals brute force, 0 differing texels; far texels keep the sentinel."""
+    c = walk_case(sm, name)
+    got, got_lvd, _ = SR.trace(sm, c.k, c.acc, c.depth, c.g, c.noise, SR.WALK, instances=c.inst)
+    print(f"{name}: occluded {int((c.mask == 0).sum())} of {int((~c.far).sum())} traced texels")
+    assert int(np.count_nonzero(got != c.mask)) == 0
+    assert np.array_equal(got_lvd, c.lvd)
+    assert np.all(c.mask[c.far] == SR.SENTINEL8) and np.all(np.isin(c.mask[~c.far], (0, 255)))
+
+
+def _lone_candidates(sm, c):
+    """(texel, t) of the texels whose ray meets exactly one triangle anywhere on its line, and every candidate's t."""
+    texels, _, ts = SR.candidates(sm, c.k, c.acc, c.depth, c.g, c.noise, instances=c.inst)
+    lone = np.bincount(texels, minlength=c.W * c.H)[texels] == 1
+    return texels[lone], ts[lone].astype(np.float64), ts.astype(np.float64)
+
+
+@pytest.mark.parametrize("name", [n for n in SS.WALK_CASES if n.startswith("ladder")])
+def test_the_ladder_stands_on_both_sides_of_tmin(sm, name):
+    """Each chosen texel's ray meets its own triangle and no other, at t = rung * TMin to 1e-4; at least 16 texels have their only
+    candidate in (0, TMin) and are lit, at least 16 in (TMin, 2 TMin) and are occluded; no candidate of any texel lies within 1 % of
+    TMin or TMax.  In an instance of uniform scale s != 1 at least 16 texels on each side of TMin would get the other verdict if t
+    were measured in object space (t * s or t / s: a walk that normalises the object-space direction measures t / s; both are
+    asked for, so the case does not depend on which way the transform is read)."""
+    c = walk_case(sm, name)
+    texels, t, every = _lone_candidates(sm, c)
+    tmin = float(c.k["m_RayStartOffset"][0])
+    assert tmin == SS.TMIN
+    order = np.argsort(c.info["texels"])
+    assert np.array_equal(texels, c.info["texels"][order]), "the chosen texels are the ones with a lone candidate"
+    assert np.allclose(t, c.info["rungs"][order] * tmin, rtol=1e-4, atol=0)
+    assert not np.any(np.abs(every / tmin - 1.0) < 0.01) and not np.any(np.abs(every / TMAX - 1.0) < 0.01)
+    below, above = (t > 0) & (t < tmin), (t > tmin) & (t < 2 * tmin)
+    print(f"{name}: {int(below.sum())} lone candidates in (0, TMin), {int(above.sum())} in (TMin, 2 TMin), {int((t > 2 * tmin).sum())} beyond")
+    assert below.sum() >= 16 and above.sum() >= 16
+    flat = c.mask.reshape(-1)
+    assert np.all(flat[texels[t < tmin]] == 255) and np.all(flat[texels[t > tmin]] == 0)
+    s = c.info["scale"]
+    if s != 1.0:
+        def hit(x):
+            return (x > tmin) & (x < TMAX)
+        flips = (hit(t * s) != hit(t)) | (hit(t / s) != hit(t))
+        lit, dark = int((flips & (t < tmin)).sum()), int((flips & (t > tmin)).sum())
+        print(f"{name}: measured in object space {lit} lit and {dark} occluded texels would change verdict")
+        assert lit >= 16 and dark >= 16
+
+
+@pytest.mark.parametrize("name", [n for n in SS.WALK_CASES if n.startswith("tmax")])
+def test_the_far_roofs_stand_on_both_sides_of_tmax(sm, name):
+    """The roof at 5e9 occludes every traced texel, the one at 2e10 none; every traced texel's ray meets the roof (both triangles where
+    it passes through the diagonal they share), at the roof's height to 1 %, which is not within 1 % of TMax, and meets nothing else;
+    inside the instance of scale 1e3 the roof at 5e9 lies at an object-space distance of 5e6 and the one at 2e10 at 2e7: every
+    traced texel of the latter is lit because t is the world's, and would be occluded if t were measured in object space."""
+    c = walk_case(sm, name)
+    texels, _, t = SR.candidates(sm, c.k, c.acc, c.depth, c.g, c.noise)
+    t = t.astype(np.float64)
+    height = 2e10 if "2e10" in name else 5e9
+    assert np.array_equal(np.unique(texels), np.flatnonzero(~c.far.reshape(-1)))
+    assert np.all(np.abs(t / height - 1.0) < 0.01) and not np.any(np.abs(t / TMAX - 1.0) < 0.01)
+    assert np.all(c.mask[~c.far] == (255 if height > TMAX else 0))
+    if "scale 1e3" in name:
+        tmin = float(c.k["m_RayStartOffset"][0])
+        inside = (t / 1e3 > tmin) & (t / 1e3 < TMAX)                              # the verdict on the object-space distance
+        assert np.all(inside) and np.all(np.abs(t / 1e3 / (height / 1e3) - 1.0) < 0.01)
+        if height > TMAX:
+            assert not np.any((t > tmin) & (t < TMAX)) and len(np.unique(texels)) >= 16      # every traced texel would flip
+
+
+@pytest.mark.parametrize("name", [n for n in SS.WALK_CASES if n.startswith("singular")])
+def test_the_singular_instances_have_no_inverse(sm, name):
+    """The reference's record of the instance holds NaNs where its determinant is 0 in binary32 (0 / 0 on the host gives 0xFFC00000,
+    its negation 0x7FC00000) and finite words for scale 1e15; the other instances still cast: the mask shows both outcomes."""
+    c = walk_case(sm, name)
+    _, records = SR.refit(sm, c.acc, c.inst)
+    m = records["object_from_world"][SS.SINGULAR_INSTANCE]
+    if c.singular:
+        assert c.singular == (SS.SINGULAR_INSTANCE,) and np.any(np.isnan(m)), m
+        words = m.view(np.uint32)[np.isnan(m)]
+        assert set(words.tolist()) <= {0xFFC00000, 0x7FC00000}
+    else:
+        assert np.all(np.isfinite(m))
+    assert np.any(c.mask == 0) and np.any(c.mask == 255)
+
+
+def _heights(acc):
+    """{node: height} of the inner nodes, from the refit's levels."""
+    off, lv = acc.tlas["level_offsets"], acc.tlas["level_nodes"]
+    return {int(n): h for h in range(acc.tlas["num_levels"]) for n in lv[off[h]:off[h + 1]]}
+
+
+@pytest.mark.parametrize("name", [n for n in SS.WALK_CASES if n.startswith("tlas") and n.endswith("hard")])
+def test_the_large_structures_reach_the_refit_s_second_trip_and_the_depth_bound(sm, name):
+    """scattered(1025) has a level of more than 256 inner nodes, which the refit's one workgroup of 256 threads strides twice
+    (scattered(513): 196, recorded); the chain is 26 levels deep with 64 instances: the 24 levels over which the builder trusts
+    its heuristic, and two halvings of the three instances left (trhip_accel_max_depth() = 56 needs 2^32 of them).  Moved: every
+    tenth instance's refitted leaf box lies outside its rest box, on every level of the refit a box differs from the rest
+    structure's, and the mask differs from the rest scene's."""
+    c = walk_case(sm, name)
+    widths = np.diff(c.acc.tlas["level_offsets"][:c.acc.tlas["num_levels"] + 1].astype(np.int64))
+    _, deepest = _walk_tree(c.acc.tlas["nodes"], 1)
+    print(f"{name}: {len(c.inst)} instances, depth {deepest}, {len(widths)} levels, widest {int(widths.max())}")
+    if "1025" in name:
+        assert widths.max() > 256
+    if "chain" in name:
+        assert deepest == 26 and len(widths) == deepest and deepest <= accel.max_depth()
+    if c.moved is not None:
+        rest, _ = SR.refit(sm, c.acc)
+        nodes, records = SR.refit(sm, c.acc, c.moved)
+        which = np.arange(3, len(c.inst), 10)
+        leaves = records["leaf_node"][which]
+        assert len(which) >= len(c.inst) // 10
+        assert np.all(np.any((nodes["lo"][leaves] > rest["hi"][leaves]) | (nodes["hi"][leaves] < rest["lo"][leaves]), axis=1))
+        changed = np.any(nodes["lo"] != rest["lo"], axis=1) | np.any(nodes["hi"] != rest["hi"], axis=1)
+        heights = _heights(c.acc)
+        assert {heights[int(n)] for n in np.flatnonzero(changed) if int(n) in heights} == set(range(len(widths)))
+        _walk_tree(nodes, 1)
+        assert np.count_nonzero(c.mask != SR.trace(sm, c.k, c.acc, c.depth, c.g, c.noise, SR.BRUTE)[0]) > 0
+
+
+@pytest.mark.parametrize("name", [n for n in SS.WALK_CASES if n.startswith(("material", "light zero"))])
+def test_what_casts_nothing_casts_nothing(sm, name):
+    """A material index past the buffer on the alpha-masked roof: every traced texel is lit; the same roof in the opaque list
+    occludes them all.  The zero vector as light: every ray is NaN and every traced texel is lit, over a scene that shadows a
+    part of the image under any other light."""
+    c = walk_case(sm, name)
+    assert np.all(c.mask[~c.far] == (0 if " opaque " in name else 255))
+    if name.startswith("light zero"):
+        valid, _, d, _ = SR.texel_rays(sm, c.k, c.depth, c.g, c.noise)
+        assert np.all(np.isnan(d[valid]))
+        lit = walk_case(sm, "light two equal largest hard")
+        assert np.any(lit.mask == 0) and np.any(lit.mask == 255)
+        dl = np.abs(np.array(SS.EDGE_LIGHTS["two equal largest"]))
+        assert dl[0] == dl[1] > dl[2]
+
+
+@pytest.mark.parametrize("soft", [False, True])
+def test_leaves_without_flags_are_skipped_by_the_sun(sm, soft):
+    """suite_support.unflagged_leaves: the walk over the uploaded arrays equals brute force, and at least 16 texels are lit only
+    because the leaves without flags are skipped: brute force with those flags restored occludes them."""
+    c = unflagged_case(sm, soft)
+    walk, walk_lvd, _ = SR.trace(sm, c.k, c.acc, c.depth, c.g, c.noise, SR.WALK, nodes=c.acc.tlas["nodes"], records=c.acc.tlas["records"])
+    assert int(np.count_nonzero(walk != c.mask)) == 0 and np.array_equal(walk_lvd, c.lvd)
+    only = (c.mask == 255) & (c.restored == 0)
+    print(f"unflagged leaves soft {soft}: {int(only.sum())} texels are lit only because {len(c.off)} leaves are skipped")
+    assert only.sum() >= 16 and not np.any((c.mask == 0) & (c.restored == 255))
+    assert np.all(c.acc.tlas["records"]["flags"][c.off] == 0) and np.all(c.acc.tlas["records"]["leaf_node"][c.off] != INNER)
