@@ -147,6 +147,20 @@ uint32_t    trhip_abi_version(void);
  * groups.  Relocation, classification: u0 those distances, u3 (texture) the RGBA16_FLOAT data array, created with the UAV bit; a
  * direct dispatch of ceil(numProbes / 32) groups; refused unless the descriptor's flags have bit 0 (relocation) or bit 1
  * (classification).
+ * "giprobevisualization_CS_LoadGIProbes" and "giprobevisualization_PS_VisualizeGIProbes" (GIDebugRenderer: the probes of that volume
+ * drawn as spheres behind the cull "giprobevisualization_CS_VisualizeGIProbesCulling"; csrc/k_giprobedraw.hip states the rules,
+ * tests/ddgi_probe_draw_ref.c is the definition).  LoadGIProbes, the project's own: b0 the 64-byte DDGIVolumeDesc (the host copy the
+ * record function checks), t0 the descriptor, t1 the probe data, u0 a structured buffer float3[numProbes] of positions, u1
+ * float[numProbes] of states (data.w when the flags have bit 1, else 0); a direct dispatch of ceil(numProbes / 32) groups; a probe
+ * count larger than either output is refused.  The cull takes u0 and u1 at its t10 and t11.  The draw: b0 the 96-byte
+ * GIProbeVisualizationConsts (the reference's 80 bytes, then m_NearPlane) with the descriptor's host copy behind it, 160 bytes; the
+ * reference's registers t0 the culled positions, t1 / t2 / t3 the probe data / irradiance / distance arrays (the distance is not
+ * read), t4 the descriptor, t5 instance -> probe index; and the project's own: t6 the DrawIndexedIndirectArguments (m_InstanceCount
+ * is read on the device and clamped to the capacities of t0 and t5; m_IndexCount is not read), t7 the unit sphere's vertices
+ * (UncompressedRawVertexFormat, 32 bytes; at most 128), t8 its indices (uint32; at most 256 triangles), u0 (texture) the R32_FLOAT
+ * depth buffer, read and written, u1 (texture) the RGBA8_UNORM back buffer of the same size, and optionally u2 (texture) an RG32_UINT
+ * texture of that size that then holds the per-texel winner words (depth bits << 32 | instance << 8 | triangle; 0: no sphere)
+ * instead of the list's scratch.  Any direct dispatch: the two launches size themselves.  Texels no sphere wins keep colour and depth.
  * "adaptluminance_CS_GenerateLuminanceHistogram" (adaptluminance.hlsl, AdaptLuminanceRenderer.cpp): a direct dispatch of
  * [numthreads(16, 16, 1)] groups covering m_SrcColorDims; push constants GenerateLuminanceHistogramParameters (16 bytes), t0
  * (texture) the R11G11B10_FLOAT colour, u0 a structured UAV of at least 256 uint32.  It ADDS to u0: the caller clears it.
@@ -372,7 +386,7 @@ int  trhip_timer_get_ms(trhip_timer t, float* ms);   /* waits for the end event 
  *   MSPrimitives   the same dispatch: sum over its visible meshlets of (m_VertexAndTriangleCount >> 8) & 0xFF
  *   CSInvocations  groups x the reference entry's [numthreads]: gpuculling_CS_GPUCulling 32 (the late pass is indirect: its
  *                  groups are read on the device), gpuculling_CS_BuildLateCullIndirectArgs 1, minmaxdownsample_CS_Main 64,
- *                  ffx_spd_downsample_pass_CS * 256, updateinstanceconsts_* 32, giprobevisualization_* 32
+ *                  ffx_spd_downsample_pass_CS * 256, updateinstanceconsts_* 32, giprobevisualization_CS_* 32
  *   all others     0: no fixed-function stage is modelled; basepass_MS_Main_depth adds nothing (its mesh work is counted by
  *                  the AS dispatch that fed it), nor do the back end's own visibility_CS_* shaders.
  * Begin zeroes the counters when it executes, so a list executed twice yields the same values again.  Begin and end must be

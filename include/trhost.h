@@ -151,6 +151,22 @@ int  trhost_set_ddgi_probe_placement(int relocation, int classification, float m
 int  trhost_reset_ddgi_volume(void);
 int  trhost_download_ddgi_volume(uint32_t* irradiance, uint64_t irradiance_bytes, uint16_t* distance, uint64_t distance_bytes, uint16_t* data, uint64_t data_bytes);
 int  trhost_get_ddgi_update_consts(void* out96);
+
+/* The probe visualisation: GIDebugRenderer (source/GIRenderer.cpp:598-808) on the DDGI volume as it is on the device this frame.
+ * trhost_set_ddgi_probe_visualization(enable, probe_radius, hide_inactive): off by default.  On, every frame records behind
+ * PostProcessRenderer "giprobevisualization_CS_LoadGIProbes" (every probe's position and state from the live volume),
+ * "giprobevisualization_CS_VisualizeGIProbesCulling" on what it wrote, and "giprobevisualization_PS_VisualizeGIProbes", which draws
+ * the surviving probes as spheres of probe_radius shaded with their own irradiance into the back buffer, depth-tested against the
+ * frame's depth buffer, which it also writes (include/trhip.h).  hide_inactive: the cull drops probes whose state is 1 (honoured only
+ * when the volume's classification flag is set).  It needs a volume (trhost_upload_ddgi_volume) and post-processing
+ * (trhost_set_post_process): with either missing, trhost_frame fails and says which.  trhost_gi_probe_buffers reads the cull's three
+ * outputs as for trhost_load_gi_probes, whose supplied-buffer path keeps its single dispatch and draws nothing; m_IndexCount is 468 here.
+ * trhost_get_ddgi_probe_visualization_consts copies the 96 bytes of GIProbeVisualizationConsts (csrc/ShaderInterop.h) the last
+ * frame's draw ran with.  trhost_unit_sphere copies the sphere that is drawn, CommonResources' UnitSphere: 91 vertices of 32 bytes
+ * (position, normal, texcoord) and 468 uint32 indices; it needs no device. */
+int  trhost_set_ddgi_probe_visualization(int enable, float probe_radius, int hide_inactive);
+int  trhost_get_ddgi_probe_visualization_consts(void* out96);
+int  trhost_unit_sphere(void* vertices, uint64_t vertices_bytes, uint32_t* indices, uint64_t indices_bytes);
 /* Auto exposure and tone mapping (AdaptLuminanceRenderer.cpp, PostProcessRenderer.cpp; implies deferred lighting, same refusals):
  * after DeferredLightingRenderer the frame clears the luminance histogram and runs "adaptluminance_CS_GenerateLuminanceHistogram"
  * and "adaptluminance_CS_AdaptExposure" (with a manual exposure > 0: one write of it into the luminance buffer instead), then

@@ -412,6 +412,30 @@ struct GIProbeVisualizationUpdateConsts
 };
 static_assert(sizeof(GIProbeVisualizationUpdateConsts) == 124 && offsetof(GIProbeVisualizationUpdateConsts, m_WorldToView) == 32, "GIProbeVisualizationUpdateConsts");
 
+// ShaderInterop.h:263-268, b0 of "giprobevisualization_PS_VisualizeGIProbes" (k_giprobedraw.hip): the reference's 80 bytes, layout
+// unchanged, then the project's own near plane (the raster drops a triangle with a vertex at w <= near) and padding.  The
+// descriptor's host copy follows the block in b0 (160 bytes together), as it follows the constants of the other DDGI passes.
+struct GIProbeVisualizationConsts
+{
+    Matrix m_WorldToClip;
+    float m_CameraDirection[3];
+    float m_ProbeRadius;
+    float m_NearPlane;                       // the project's own from here
+    uint32_t pad[3];
+};
+static_assert(sizeof(GIProbeVisualizationConsts) == 96 && offsetof(GIProbeVisualizationConsts, m_CameraDirection) == 64 && offsetof(GIProbeVisualizationConsts, m_ProbeRadius) == 76 &&
+              offsetof(GIProbeVisualizationConsts, m_NearPlane) == 80, "GIProbeVisualizationConsts");
+
+// ShaderInterop.h:270-276: the vertex of the unit sphere (CommonResources.cpp:40-102), 91 of them with 468 indices (uint32_t)
+struct UncompressedRawVertexFormat
+{
+    float m_Position[3];
+    float m_Normal[3];
+    float m_TexCoord[2];
+};
+static_assert(sizeof(UncompressedRawVertexFormat) == 32 && offsetof(UncompressedRawVertexFormat, m_Normal) == 12, "UncompressedRawVertexFormat");
+static constexpr uint32_t kUnitSphereVertices = 91, kUnitSphereIndices = 468;
+
 // ShaderInterop.h:214-218
 struct MinMaxDownsampleConsts
 {

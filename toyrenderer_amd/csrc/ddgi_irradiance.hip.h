@@ -101,6 +101,29 @@ __device__ __forceinline__ float probeCoord(int c, uint32_t interior, float o, u
 
 __device__ __forceinline__ uint32_t sliceOf(int y, uint32_t slices) { return (uint32_t)(y < 0 ? 0 : y) < slices ? (uint32_t)(y < 0 ? 0 : y) : slices - 1u; }
 
+// bilinear(irradiance, probeUV(c, (u, v), 6)): the four texels of probe c's irradiance tile around the direction whose oct() is (u, v),
+// and channel(shift, halfGamma) = pow(their filtered channel, halfGamma).  The query's tap, and what the probe spheres are shaded
+// with (k_giprobedraw.hip).
+struct IrradianceTap
+{
+    uint32_t w00, w10, w01, w11;
+    float fx, fy;
+    __device__ __forceinline__ float channel(uint32_t shift, float halfGamma) const
+    {
+        const float t00 = cm::div_((float)((w00 >> shift) & 1023u), 1023.0f), t10 = cm::div_((float)((w10 >> shift) & 1023u), 1023.0f);
+        const float t01 = cm::div_((float)((w01 >> shift) & 1023u), 1023.0f), t11 = cm::div_((float)((w11 >> shift) & 1023u), 1023.0f);
+        return powSoft(sp::lerp_(sp::lerp_(t00, t10, fx), sp::lerp_(t01, t11, fx), fy), halfGamma);
+    }
+};
+
+__device__ __forceinline__ IrradianceTap irradianceTap(const Textures& t, int cx, int cz, uint32_t slice, float u, float v)
+{
+    const Axis ax = axisOf(probeCoord(cx, interop::kDDGIIrradianceInteriorTexels, u, t.irrW), t.irrW);
+    const Axis ay = axisOf(probeCoord(cz, interop::kDDGIIrradianceInteriorTexels, v, t.irrH), t.irrH);
+    const uint32_t* s = t.irradiance + (uint64_t)slice * t.irrPitch;
+    return { s[ay.i0 * t.irrW + ax.i0], s[ay.i0 * t.irrW + ax.i1], s[ay.i1 * t.irrW + ax.i0], s[ay.i1 * t.irrW + ax.i1], ax.f, ay.f };
+}
+
 __device__ __forceinline__ cm::F3 irradiance(const Textures& t, cm::F3 world, cm::F3 N, cm::F3 cameraOrigin)
 {
     const interop::DDGIVolumeDesc& D = *t.desc;
@@ -181,18 +204,10 @@ __device__ __forceinline__ cm::F3 irradiance(const Textures& t, cm::F3 world, cm
         if (w < 0.2f) w = w * ((w * w) * (1.0f / (0.2f * 0.2f)));
         w = w * ((triX * triY) * triZ);
         {
-            const Axis ax = axisOf(probeCoord(c.x, interop::kDDGIIrradianceInteriorTexels, nu, t.irrW), t.irrW);
-            const Axis ay = axisOf(probeCoord(c.z, interop::kDDGIIrradianceInteriorTexels, nv, t.irrH), t.irrH);
-            const uint32_t* s = t.irradiance + (uint64_t)slice * t.irrPitch;
-            const uint32_t w00 = s[ay.i0 * t.irrW + ax.i0], w10 = s[ay.i0 * t.irrW + ax.i1], w01 = s[ay.i1 * t.irrW + ax.i0], w11 = s[ay.i1 * t.irrW + ax.i1];
-            auto channel = [&](uint32_t shift) {
-                const float t00 = cm::div_((float)((w00 >> shift) & 1023u), 1023.0f), t10 = cm::div_((float)((w10 >> shift) & 1023u), 1023.0f);
-                const float t01 = cm::div_((float)((w01 >> shift) & 1023u), 1023.0f), t11 = cm::div_((float)((w11 >> shift) & 1023u), 1023.0f);
-                return powSoft(sp::lerp_(sp::lerp_(t00, t10, ax.f), sp::lerp_(t01, t11, ax.f), ay.f), halfGamma);
-            };
-            sum.x = sum.x + w * channel(0u);
-            sum.y = sum.y + w * channel(10u);
-            sum.z = sum.z + w * channel(20u);
+            const IrradianceTap tap = irradianceTap(t, c.x, c.z, slice, nu, nv);
+            sum.x = sum.x + w * tap.channel(0u, halfGamma);
+            sum.y = sum.y + w * tap.channel(10u, halfGamma);
+            sum.z = sum.z + w * tap.channel(20u, halfGamma);
         }
         wsum = wsum + w;
     }

@@ -91,14 +91,10 @@ __device__ __forceinline__ cm::F3 octDecode(float ox, float oy)
 }
 
 // ---- record side -------------------------------------------------------------------------------------------------------------
-// b0: the 160-byte block; the descriptor's host copy is checked as the lighting pass checks its own.
-inline int requireBlock(const trhip::DispatchCtx& ctx, Block& out)
+// The descriptor's host copy, checked as the lighting pass checks its own, wherever a pass keeps it (the probe visualisation's passes,
+// k_giprobedraw.hip, have blocks of their own).
+inline int requireDesc(const char* name, const interop::DDGIVolumeDesc& D)
 {
-    const char* name = ctx.shaderName;
-    const void* block = ctx.constants(0, sizeof(Block));
-    TRHIP_REQUIRE(block, "%s: constant buffer b0 (the 96-byte DDGIUpdateConsts and the 64-byte DDGIVolumeDesc behind it, 160 bytes) missing or short", name);
-    memcpy(&out, block, sizeof out);
-    const interop::DDGIVolumeDesc& D = out.D;
     for (int a = 0; a < 3; ++a) {
         TRHIP_REQUIRE(D.probeCounts[a] >= 1 && D.probeCounts[a] <= (int)interop::kDDGIMaxProbeCount, "%s: DDGIVolumeDesc probeCounts[%d] = %d, not in 1..1024", name, a, D.probeCounts[a]);
         TRHIP_REQUIRE(D.probeSpacing[a] > 0.0f && D.probeSpacing[a] <= 3.402823466e38f, "%s: DDGIVolumeDesc probeSpacing[%d] = %g is not positive and finite", name, a, (double)D.probeSpacing[a]);
@@ -108,6 +104,16 @@ inline int requireBlock(const trhip::DispatchCtx& ctx, Block& out)
     TRHIP_REQUIRE((uint64_t)D.probeCounts[0] * (uint64_t)D.probeCounts[1] * (uint64_t)D.probeCounts[2] <= (1u << 22), "%s: %d x %d x %d probes; the update takes at most 2^22", name,
                   D.probeCounts[0], D.probeCounts[1], D.probeCounts[2]);
     return TRHIP_OK;
+}
+
+// b0: the 160-byte block
+inline int requireBlock(const trhip::DispatchCtx& ctx, Block& out)
+{
+    const char* name = ctx.shaderName;
+    const void* block = ctx.constants(0, sizeof(Block));
+    TRHIP_REQUIRE(block, "%s: constant buffer b0 (the 96-byte DDGIUpdateConsts and the 64-byte DDGIVolumeDesc behind it, 160 bytes) missing or short", name);
+    memcpy(&out, block, sizeof out);
+    return requireDesc(name, out.D);
 }
 
 inline uint32_t numProbes(const interop::DDGIVolumeDesc& D) { return (uint32_t)D.probeCounts[0] * (uint32_t)D.probeCounts[1] * (uint32_t)D.probeCounts[2]; }

@@ -1,10 +1,13 @@
-// GIRenderer.cpp -- the one pass of the reference's GI debug renderer that belongs to the visibility path: the probe
-// culling dispatch of GIDebugRenderer (source/GIRenderer.cpp:598-808; Setup :612-657, RenderDDGIDebug :672-735), the
-// second consumer of FrustumCull / OcclusionCull and of compaction into indirect draw arguments.
+// GIRenderer.cpp -- the reference's GI debug renderer, GIDebugRenderer (source/GIRenderer.cpp:598-808; Setup :612-657,
+// RenderDDGIDebug :672-808): the probe culling dispatch, the second consumer of FrustumCull / OcclusionCull and of compaction into
+// indirect draw arguments, and the draw of the unit spheres that consumes those arguments (:737-806).
 //
-// The debug renderer does not read the DDGI volume: the probes' world positions and states arrive as two buffers
-// (Scene::LoadGIProbes) where the reference binds the volume descriptors (t10) and the probe-data texture array (u10).  The draw
-// of the unit spheres that consumes the indirect arguments (:737-806) is pixel work.
+// Two paths.  With trhost_set_ddgi_probe_visualization the renderer works on Scene::m_RTDDGIVolume as it is on the device this
+// frame: "giprobevisualization_CS_LoadGIProbes" (the project's own: the reference reads the volume inline through SDK functions)
+// writes every probe's position and state into two transient buffers, the cull takes them at t10 / t11, and
+// "giprobevisualization_PS_VisualizeGIProbes" (csrc/k_giprobedraw.hip) draws the survivors into PostProcessRenderer's back buffer
+// and the frame's depth buffer; m_IndexCount is the unit sphere's 468.  With Scene::LoadGIProbes alone the positions and states are
+// two supplied buffers, the cull is the one dispatch, its arguments carry 2880 and nothing is drawn.
 //
 // And GIRenderer (source/GIRenderer.cpp: RenderDDGI): the probe update of Scene::m_RTDDGIVolume, "giprobetrace_CS_ProbeTrace" and
 // the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes (csrc/k_giprobetrace.hip, csrc/k_giprobeblend.hip), behind the TLAS refit and
@@ -16,6 +19,7 @@
 // keyed by (seed, update count), evaluated in double and rounded once; trhost_get_ddgi_update_consts shows the block that ran.
 #include "CommonResources.h"
 #include "Graphic.h"
+#include "MathUtilities.h"
 #include "RenderGraph.h"
 #include "Scene.h"
 #include "VisibilityOutputs.h"
@@ -25,6 +29,8 @@
 #include <cstring>
 
 using namespace interop;
+
+extern RenderGraph::ResourceHandle g_DepthStencilBufferRDGTextureHandle;
 
 class GIDebugRenderer : public IRenderer
 {
@@ -45,11 +51,21 @@ class GIDebugRenderer : public IRenderer
         { "Instance ID to Probe Index", sizeof(uint32_t), true, false, {}, nullptr },
     };
 
-    static GIProbeVisualizationUpdateConsts ConstantsOf(const Scene& scene)     // :687-708
+    // the live path's two inputs of the cull, written by LoadGIProbes
+    RenderGraph::ResourceHandle m_LivePositions, m_LiveStates;
+    bool m_bLive = false;
+
+    static uint32_t LiveProbeCount(const Scene& scene)
+    {
+        const DDGIVolumeDesc& d = scene.m_RTDDGIVolume.m_Desc;
+        return (uint32_t)d.probeCounts[0] * (uint32_t)d.probeCounts[1] * (uint32_t)d.probeCounts[2];
+    }
+
+    static GIProbeVisualizationUpdateConsts ConstantsOf(const Scene& scene, bool live)     // :687-708
     {
         const View& view = scene.m_View;
         GIProbeVisualizationUpdateConsts k{};
-        k.m_NumProbes = scene.m_NumGIProbes;
+        k.m_NumProbes = live ? LiveProbeCount(scene) : scene.m_NumGIProbes;
         // :701 m_CameraOrigin = m_View.m_Eye.  This mirror takes the camera as a world-to-view matrix (Scene.h, View::SetCamera):
         // the eye is the point that maps to the view-space origin, -t * R^T for the rigid transform [R | t] a camera is.
         // (The culling shader does not read the field; it is filled so that the uploaded block equals the reference's.)
@@ -62,22 +78,43 @@ class GIDebugRenderer : public IRenderer
         k.m_P00 = view.m_ViewToClip.m[0][0];
         k.m_P11 = view.m_ViewToClip.m[1][1];
         k.m_NearPlane = view.m_ZNearP;
-        k.m_ProbeRadius = scene.m_GIProbeRadius;
-        k.m_bHideInactiveProbes = scene.m_bHideInactiveGIProbes;
+        k.m_ProbeRadius = live ? scene.m_DDGIProbeVisualizationRadius : scene.m_GIProbeRadius;
+        k.m_bHideInactiveProbes = live ? scene.m_bDDGIProbeVisualizationHideInactive : scene.m_bHideInactiveGIProbes;
         return k;
     }
 
 public:
     GIDebugRenderer() : IRenderer("GIDebugRenderer") {}
 
+    GIProbeVisualizationConsts m_LastDrawConsts{};
+    bool m_bDrewLastFrame = false;
+
     nvrhi::BufferHandle LastOutput(int which) const { return m_Outputs[which].last; }
     void DropLastOutputs() { for (Output& o : m_Outputs) o.last = nullptr; }
 
     bool Setup(RenderGraph& renderGraph) override
     {
-        const uint32_t numProbes = g_Scene->m_NumGIProbes;
-        if (numProbes == 0 || !g_Scene->m_bShowGIProbes) return false;          // :661-670: only with DDGI and the debug view on
+        m_bDrewLastFrame = false;
+        // trhost_frame has refused a frame with the switch on and no volume or no post-processing (CheckDDGIProbeVisualization)
+        m_bLive = g_Scene->m_bDDGIProbeVisualization && g_Scene->m_RTDDGIVolume.IsValid() && g_Scene->m_bPostProcess && g_Scene->m_NumPrimitives != 0;
+        const uint32_t numProbes = m_bLive ? LiveProbeCount(*g_Scene) : g_Scene->m_NumGIProbes;
+        if (numProbes == 0 || !(m_bLive || g_Scene->m_bShowGIProbes)) return false;   // :661-670: only with DDGI and the debug view on
         renderGraph.AddExternalReadDependency(g_Scene->m_HZB.Get());            // where the reference declares the volume descriptors (:652)
+        if (m_bLive) {
+            const Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+            renderGraph.AddExternalReadDependency(volume.m_ProbeData.Get());    // GIRenderer, scheduled in front, may have rewritten all three
+            renderGraph.AddExternalReadDependency(volume.m_ProbeIrradiance.Get());
+            renderGraph.AddExternalReadDependency(volume.m_ProbeDistance.Get());
+            renderGraph.AddExternalWriteDependency(GetBackBuffer().Get());      // PostProcessRenderer::Setup, scheduled in front, has created it
+            renderGraph.AddWriteDependency(g_DepthStencilBufferRDGTextureHandle);
+            nvrhi::BufferDesc desc;
+            desc.canHaveUAVs = true;
+            desc.initialState = nvrhi::ResourceStates::ShaderResource;
+            desc.debugName = "GI Probe World Positions"; desc.structStride = sizeof(float) * 3; desc.byteSize = (uint64_t)desc.structStride * numProbes;
+            renderGraph.CreateTransientResource(m_LivePositions, desc);
+            desc.debugName = "GI Probe States"; desc.structStride = sizeof(float); desc.byteSize = (uint64_t)desc.structStride * numProbes;
+            renderGraph.CreateTransientResource(m_LiveStates, desc);
+        }
         for (Output& o : m_Outputs) {
             nvrhi::BufferDesc desc;
             desc.debugName = o.debugName;
@@ -96,13 +133,32 @@ public:
         nvrhi::BufferHandle out[kNumOutputs];
         for (int i = 0; i < kNumOutputs; ++i) out[i] = renderGraph.GetBuffer(m_Outputs[i].handle);      // :678-681
 
+        using Item = nvrhi::BindingSetItem;
+        const Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+        nvrhi::BufferHandle positions = g_Scene->m_GIProbePositionsBuffer, states = g_Scene->m_GIProbeStatesBuffer;
+        if (m_bLive) {                                                          // where the reference calls DDGILoadProbeState / DDGIGetProbeWorldPosition (:29-37)
+            positions = renderGraph.GetBuffer(m_LivePositions);
+            states = renderGraph.GetBuffer(m_LiveStates);
+            Graphic::ComputePassParams load;
+            load.m_CommandList = commandList;
+            load.m_ShaderName = "giprobevisualization_CS_LoadGIProbes";
+            load.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(LiveProbeCount(*g_Scene), kNumThreadsPerWave);
+            load.m_BindingSetDesc.bindings = {
+                Item::ConstantBuffer(0, g_Graphic.CreateConstantBuffer(commandList, volume.m_Desc)),
+                Item::StructuredBuffer_SRV(0, volume.m_DescBuffer),
+                Item::Texture_SRV(1, volume.m_ProbeData),
+                Item::StructuredBuffer_UAV(0, positions),
+                Item::StructuredBuffer_UAV(1, states),
+            };
+            g_Graphic.AddComputePass(load);
+        }
+
         // the draw the culling feeds: unit-sphere indices, instance count 0 until the shader has counted (:683-685)
         DrawIndexedIndirectArguments sphereDraw{};
-        sphereDraw.m_IndexCount = g_Scene->m_GIProbeSphereIndexCount;           // g_CommonResources.UnitSphere.m_NumIndices in the reference
+        sphereDraw.m_IndexCount = m_bLive ? g_CommonResources.UnitSphere.m_NumIndices : g_Scene->m_GIProbeSphereIndexCount;
         commandList->writeBuffer(out[kDrawArgs], &sphereDraw, sizeof sphereDraw);
 
-        const GIProbeVisualizationUpdateConsts consts = ConstantsOf(*g_Scene);
-        using Item = nvrhi::BindingSetItem;
+        const GIProbeVisualizationUpdateConsts consts = ConstantsOf(*g_Scene, m_bLive);
         Graphic::ComputePassParams pass;                                        // :710-733
         pass.m_CommandList = commandList;
         pass.m_ShaderName = "giprobevisualization_CS_VisualizeGIProbesCulling";
@@ -113,8 +169,8 @@ public:
             Item::Sampler(0, g_CommonResources.LinearClampMinReductionSampler),
             // t10 / t11: probe positions and states, where the reference binds the DDGI volume descriptors (t10) and
             // the probe-data texture array (u10)
-            Item::StructuredBuffer_SRV(10, g_Scene->m_GIProbePositionsBuffer),
-            Item::StructuredBuffer_SRV(11, g_Scene->m_GIProbeStatesBuffer),
+            Item::StructuredBuffer_SRV(10, positions),
+            Item::StructuredBuffer_SRV(11, states),
             Item::StructuredBuffer_UAV(0, out[kPositions]),
             Item::StructuredBuffer_UAV(1, out[kDrawArgs]),
             Item::StructuredBuffer_UAV(2, out[kInstanceToProbe]),
@@ -122,6 +178,38 @@ public:
         g_Graphic.AddComputePass(pass);
 
         for (int i = 0; i < kNumOutputs; ++i) m_Outputs[i].last = out[i];
+        if (!m_bLive) return;
+
+        struct Block { GIProbeVisualizationConsts k; DDGIVolumeDesc desc; } block{};    // :745-752
+        static_assert(sizeof(Block) == 160, "GIProbeVisualizationConsts + DDGIVolumeDesc");
+        const View& view = g_Scene->m_View;
+        block.k.m_WorldToClip = MultiplyNoFMA(view.m_WorldToView, view.m_ViewToClip);
+        for (int j = 0; j < 3; ++j) block.k.m_CameraDirection[j] = -view.m_WorldToView.m[j][2];     // the view looks down -Z; the draw does not read it
+        block.k.m_ProbeRadius = g_Scene->m_DDGIProbeVisualizationRadius;
+        block.k.m_NearPlane = view.m_ZNearP;
+        block.desc = volume.m_Desc;
+        m_LastDrawConsts = block.k;
+        m_bDrewLastFrame = true;
+        Graphic::ComputePassParams draw;                                        // :754-806
+        draw.m_CommandList = commandList;
+        draw.m_ShaderName = "giprobevisualization_PS_VisualizeGIProbes";
+        draw.m_DispatchGroupSize = Vector3U{ 1, 1, 1 };                        // the launches size themselves
+        draw.m_BindingSetDesc.bindings = {
+            Item::ConstantBuffer(0, g_Graphic.CreateConstantBuffer(commandList, block)),
+            Item::StructuredBuffer_SRV(0, out[kPositions]),
+            Item::Texture_SRV(1, volume.m_ProbeData),
+            Item::Texture_SRV(2, volume.m_ProbeIrradiance),
+            Item::Texture_SRV(3, volume.m_ProbeDistance),
+            Item::StructuredBuffer_SRV(4, volume.m_DescBuffer),
+            Item::StructuredBuffer_SRV(5, out[kInstanceToProbe]),
+            Item::StructuredBuffer_SRV(6, out[kDrawArgs]),                      // the project's own slots from here (include/trhip.h)
+            Item::StructuredBuffer_SRV(7, g_CommonResources.UnitSphere.m_VertexBuffer),
+            Item::StructuredBuffer_SRV(8, g_CommonResources.UnitSphere.m_IndexBuffer),
+            Item::Texture_UAV(0, renderGraph.GetTexture(g_DepthStencilBufferRDGTextureHandle)),
+            Item::Texture_UAV(1, GetBackBuffer()),
+            Item::Sampler(0, g_CommonResources.LinearClampSampler),             // the reference's g_LinearWrapSampler: accepted and ignored
+        };
+        g_Graphic.AddComputePass(draw);
     }
 
     enum { Positions = kPositions, DrawArgs = kDrawArgs, InstanceToProbe = kInstanceToProbe };
@@ -286,6 +374,14 @@ bool GetLastDDGIUpdateConsts(void* out96)
     const GIRenderer* r = static_cast<const GIRenderer*>(g_GIRenderer);
     if (!g_Scene->m_bDDGIUpdate || !r->m_bRanLastFrame) return false;
     memcpy(out96, &r->m_LastConsts, sizeof r->m_LastConsts);
+    return true;
+}
+
+bool GetLastDDGIProbeVisualizationConsts(void* out96)
+{
+    const GIDebugRenderer* r = static_cast<const GIDebugRenderer*>(g_GIDebugRenderer);
+    if (!r->m_bDrewLastFrame) return false;
+    memcpy(out96, &r->m_LastDrawConsts, sizeof r->m_LastDrawConsts);
     return true;
 }
 

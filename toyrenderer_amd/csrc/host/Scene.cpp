@@ -340,4 +340,5 @@ void Scene::Shutdown()
     m_ExposureTexture = nullptr;
     m_GIProbePositionsBuffer = m_GIProbeStatesBuffer = nullptr;
     m_NumGIProbes = 0; m_bShowGIProbes = false;
+    m_bDDGIProbeVisualization = false;
 }

@@ -180,14 +180,20 @@ public:
     void LoadGeometry(const void* vertices, uint64_t numVertices, const uint32_t* meshletVertexIds, uint64_t numVertexIds,
                       const uint32_t* meshletTriangles, uint64_t numTriangles);
 
-    // GI debug view (GIRenderer.cpp:598-808): the probes' world positions and states as the DDGI volume would give them
-    // (inputs here: the RTXGI SDK is absent), culled every frame by GIDebugRenderer when m_bShowGIProbes is set.
+    // GI debug view (GIRenderer.cpp:598-808), from supplied buffers: the probes' world positions and states as a DDGI volume would
+    // give them, culled every frame by GIDebugRenderer when m_bShowGIProbes is set.  This path has no draw (the buffers belong to no
+    // volume whose irradiance could shade the spheres); trhost_set_ddgi_probe_visualization below is the whole pass.
     void LoadGIProbes(const float* positions, const float* states, uint32_t numProbes, float probeRadius, bool hideInactive);
     nvrhi::BufferHandle m_GIProbePositionsBuffer, m_GIProbeStatesBuffer;
     uint32_t m_NumGIProbes = 0;
     float m_GIProbeRadius = 0.1f;
     bool m_bHideInactiveGIProbes = false, m_bShowGIProbes = false;
-    uint32_t m_GIProbeSphereIndexCount = 2880;       // index count of CommonResources' unit sphere mesh (draw side, out of scope)
+    uint32_t m_GIProbeSphereIndexCount = 2880;       // m_IndexCount the supplied-buffer path writes (its arguments have no consumer); the live path writes UnitSphere's 468
+    // trhost_set_ddgi_probe_visualization: GIDebugRenderer on m_RTDDGIVolume as it is on the device this frame -- "giprobevisualization_
+    // CS_LoadGIProbes", the cull, then "giprobevisualization_PS_VisualizeGIProbes" into PostProcessRenderer's back buffer and the
+    // frame's depth buffer (csrc/k_giprobedraw.hip).  Needs the volume and m_bPostProcess: a frame without either fails and says which.
+    bool m_bDDGIProbeVisualization = false, m_bDDGIProbeVisualizationHideInactive = false;
+    float m_DDGIProbeVisualizationRadius = 0.1f;
 
     std::shared_ptr<RenderGraph> m_RenderGraph;
     tf::Executor m_Executor{ 4 };                    // Engine.cpp:19,110-116 (default 12 workers)

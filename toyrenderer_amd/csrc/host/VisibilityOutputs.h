@@ -76,6 +76,7 @@ void ReleaseShadowMaskOutputs();
 void RecordRefitTLAS(nvrhi::CommandListHandle commandList);
 // GIRenderer: the 96 bytes of DDGIUpdateConsts the last frame's probe update ran with (false if it did not run in it)
 bool GetLastDDGIUpdateConsts(void* out96);
+bool GetLastDDGIProbeVisualizationConsts(void* out96);   // GIDebugRenderer: the 96-byte GIProbeVisualizationConsts of the last frame's draw
 // The SkyPassParameters SkyRenderer uploaded in the last frame; false if the pass did not run in it.
 bool GetLastSkyConsts(void* out256);
 void ReleaseSkyOutputs();

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../../include/trhost.h"
+#include "CommonResources.h"
 #include "Graphic.h"
 #include "GraphicConstants.h"
 #include "RenderGraph.h"
@@ -325,6 +326,52 @@ int trhost_set_ddgi_probe_placement(int relocation, int classification, float mi
         g_Scene->m_DDGIMinFrontfaceDistance = min_frontface_distance;
         g_Scene->m_DDGIFixedRayBackfaceThreshold = fixed_ray_backface_threshold;
     });
+}
+
+int trhost_set_ddgi_probe_visualization(int enable, float probe_radius, int hide_inactive)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (enable && !(probe_radius > 0.0f && probe_radius <= 3.402823466e38f))
+            throw nvrhi::Error("trhost_set_ddgi_probe_visualization: probe_radius must be positive and finite");
+        g_Scene->m_bDDGIProbeVisualization = enable != 0;                     // what it needs is checked when a frame is asked for
+        g_Scene->m_DDGIProbeVisualizationRadius = probe_radius;
+        g_Scene->m_bDDGIProbeVisualizationHideInactive = hide_inactive != 0;
+    });
+}
+
+int trhost_get_ddgi_probe_visualization_consts(void* out96)
+{
+    return guarded([&] {
+        check(g_Scene && out96);
+        if (!GetLastDDGIProbeVisualizationConsts(out96))
+            throw nvrhi::Error("trhost_get_ddgi_probe_visualization_consts: the last frame drew no probes (trhost_set_ddgi_probe_visualization)");
+    });
+}
+
+int trhost_unit_sphere(void* vertices, uint64_t vertices_bytes, uint32_t* indices, uint64_t indices_bytes)
+{
+    return guarded([&] {
+        std::vector<interop::UncompressedRawVertexFormat> v;
+        std::vector<uint32_t> i;
+        CommonResources::BuildUnitSphere(v, i);
+        if (!vertices || !indices || vertices_bytes != v.size() * sizeof v[0] || indices_bytes != i.size() * sizeof i[0])
+            throw nvrhi::Error("trhost_unit_sphere: needs 91 vertices of 32 bytes and 468 uint32 indices");
+        memcpy(vertices, v.data(), vertices_bytes);
+        memcpy(indices, i.data(), indices_bytes);
+    });
+}
+
+// A frame with the probe visualisation on and nothing to draw from or into says which is missing.
+static void CheckDDGIProbeVisualization()
+{
+    if (!g_Scene || !g_Scene->m_bDDGIProbeVisualization) return;
+    if (!g_Scene->m_RTDDGIVolume.IsValid())
+        throw nvrhi::Error("the probe visualisation is on (trhost_set_ddgi_probe_visualization) and there is no DDGI volume (trhost_upload_ddgi_volume): "
+                           "giprobevisualization_CS_LoadGIProbes has no probes to load");
+    if (!g_Scene->m_bPostProcess)
+        throw nvrhi::Error("the probe visualisation is on (trhost_set_ddgi_probe_visualization) and post-processing is off (trhost_set_post_process): "
+                           "giprobevisualization_PS_VisualizeGIProbes has no back buffer to draw into");
 }
 
 int trhost_reset_ddgi_volume(void)
@@ -798,7 +845,7 @@ int trhost_hzb_info(uint32_t* width, uint32_t* height, uint32_t* mips)
     });
 }
 
-int trhost_frame(void) { return guarded([&] { g_Graphic.Update(); }); }
+int trhost_frame(void) { return guarded([&] { CheckDDGIProbeVisualization(); g_Graphic.Update(); }); }
 
 int trhost_wait_idle(void) { return guarded([&] { g_Graphic.m_NVRHIDevice->waitForIdle(); }); }
 

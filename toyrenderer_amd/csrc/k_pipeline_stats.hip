@@ -143,7 +143,7 @@ uint32_t statsCSThreads(const char* name)
     if (!strcmp(name, "minmaxdownsample_CS_Main")) return 64;               // [numthreads(8, 8, 1)]
     if (startsWith(name, "ffx_spd_downsample_pass_CS")) return 256;         // SPD's 256-thread groups
     if (startsWith(name, "updateinstanceconsts_")) return 32;
-    if (startsWith(name, "giprobevisualization_")) return 32;
+    if (startsWith(name, "giprobevisualization_CS_")) return 32;            // the cull and LoadGIProbes; the draw (_PS_) is no compute shader
     return 0;
 }
 

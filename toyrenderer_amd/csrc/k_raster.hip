@@ -172,26 +172,7 @@ __device__ __forceinline__ AlphaMaterial alphaMaterial(const AlphaArgs& aa, uint
     return m;
 }
 
-// One triangle over the pixels [bx0, bx1] x [by0, by1], `threads` lanes striding over them from `first`; every covered
-// pixel that `keep(cx, cy, e0, e1, e2)` does not discard goes to `sink(px, py, depthBits)`.  The arithmetic of
-// orc_raster_depth, operation for operation; keep is constant true in the plain instantiations.
-template <typename Keep, typename Sink>
-__device__ __forceinline__ void coverBox(float x0, float y0, float d0, float x1, float y1, float d1, float x2, float y2, float d2, float sgn,
-                                         uint32_t bx0, uint32_t by0, uint32_t bw, uint32_t bh, uint32_t first, uint32_t threads, Keep keep, Sink sink)
-{
-    const uint64_t total = (uint64_t)bw * bh;
-    for (uint64_t i = first; i < total; i += threads) {
-        const uint32_t row = (uint32_t)(i / bw), col = (uint32_t)(i - (uint64_t)row * bw);
-        const uint32_t px = bx0 + col, py = by0 + row;
-        const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
-        const float e0 = sgn * edgeFn(x1, y1, x2, y2, cx, cy), e1 = sgn * edgeFn(x2, y2, x0, y0, cx, cy), e2 = sgn * edgeFn(x0, y0, x1, y1, cx, cy);
-        if (!(e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f)) continue;
-        const float den = (e0 + e1) + e2;
-        if (!(den > 0.0f)) continue;
-        const float d = cm::fma_(e2, d2, cm::fma_(e1, d1, e0 * d0)) / den;
-        if (d > 0.0f && keep(cx, cy, e0, e1, e2)) sink(px, py, __float_as_uint(d));       // GREATER test; NaN never passes
-    }
-}
+// coverBox, one triangle over the pixels of its box: mesh_stage.hip.h (the probe spheres' draw, k_giprobedraw.hip, shares it).
 
 // ALPHA_MASK_MODE's discard at one covered sample of triangle (q, t) with material m (m.draw): see the header's CONVENTION.
 __device__ __forceinline__ bool alphaKeeps(const BigTriangle& q, const AlphaTriangle& t, const AlphaMaterial& m, float cx, float cy, float e0, float e1, float e2)

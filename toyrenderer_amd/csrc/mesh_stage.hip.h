@@ -88,15 +88,41 @@ __device__ __forceinline__ const RawVertexFormat& vertexAt(const Geometry& g, ui
 // ---- object space -> screen (basepass.hlsl:149-158; the operations of orc_raster_depth, one for one) ----------------
 struct ScreenVertex { float sx, sy, depth, w; };
 
-__device__ __forceinline__ ScreenVertex toScreen(cm::F3 position, const cm::M43& world, const cm::M43& clipXYZ, const Matrix& worldToClip, float halfW, float halfH)
+// world space -> screen: toScreen behind its world transform (the probe spheres' vertices are made in world space, k_giprobedraw.hip)
+__device__ __forceinline__ ScreenVertex worldToScreen(cm::F3 wp, const cm::M43& clipXYZ, const Matrix& worldToClip, float halfW, float halfH)
 {
-    const cm::F3 wp = cm::mulPoint(position, world);
     const cm::F3 c = cm::mulPoint(wp, clipXYZ);
     const float w = cm::fma_(wp.z, worldToClip.m[2][3], cm::fma_(wp.y, worldToClip.m[1][3], wp.x * worldToClip.m[0][3])) + worldToClip.m[3][3];
     return { cm::fma_(c.x / w, halfW, halfW), cm::fma_(-(c.y / w), halfH, halfH), c.z / w, w };
 }
 
+__device__ __forceinline__ ScreenVertex toScreen(cm::F3 position, const cm::M43& world, const cm::M43& clipXYZ, const Matrix& worldToClip, float halfW, float halfH)
+{
+    return worldToScreen(cm::mulPoint(position, world), clipXYZ, worldToClip, halfW, halfH);
+}
+
 __device__ __forceinline__ float edgeFn(float ax, float ay, float bx, float by, float px, float py) { return cm::fma_(bx - ax, py - ay, -((by - ay) * (px - ax))); }
+
+// One triangle over the pixels [bx0, bx1] x [by0, by1], `threads` lanes striding over them from `first`; every covered
+// pixel that `keep(cx, cy, e0, e1, e2)` does not discard goes to `sink(px, py, depthBits)`.  The arithmetic of
+// orc_raster_depth, operation for operation; keep is constant true in the rasters' plain instantiations.
+template <typename Keep, typename Sink>
+__device__ __forceinline__ void coverBox(float x0, float y0, float d0, float x1, float y1, float d1, float x2, float y2, float d2, float sgn,
+                                         uint32_t bx0, uint32_t by0, uint32_t bw, uint32_t bh, uint32_t first, uint32_t threads, Keep keep, Sink sink)
+{
+    const uint64_t total = (uint64_t)bw * bh;
+    for (uint64_t i = first; i < total; i += threads) {
+        const uint32_t row = (uint32_t)(i / bw), col = (uint32_t)(i - (uint64_t)row * bw);
+        const uint32_t px = bx0 + col, py = by0 + row;
+        const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
+        const float e0 = sgn * edgeFn(x1, y1, x2, y2, cx, cy), e1 = sgn * edgeFn(x2, y2, x0, y0, cx, cy), e2 = sgn * edgeFn(x0, y0, x1, y1, cx, cy);
+        if (!(e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f)) continue;
+        const float den = (e0 + e1) + e2;
+        if (!(den > 0.0f)) continue;
+        const float d = cm::fma_(e2, d2, cm::fma_(e1, d1, e0 * d0)) / den;
+        if (d > 0.0f && keep(cx, cy, e0, e1, e2)) sink(px, py, __float_as_uint(d));       // GREATER test; NaN never passes
+    }
+}
 
 // ---- m_TexCoord and its screen-space derivatives at one sample of a triangle (GetCommonGBufferParams' uv, ddx(uv), ddy(uv)) -----
 // The formulas of the TEXTURED resolve (visibility_resolve.hip.h, which keeps its own copy beside the world position it

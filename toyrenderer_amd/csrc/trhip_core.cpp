@@ -976,6 +976,10 @@ static const ArrayBindingDecl kArrayBindings[] = {
     { "giprobetrace_CS_ProbeTraceFixedRays", TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },      // k_giprobeplacement.hip
     { "ProbeRelocationCS_DDGIProbeRelocationCS", TRHIP_BIND_TEXTURE_UAV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
     { "ProbeClassificationCS_DDGIProbeClassificationCS", TRHIP_BIND_TEXTURE_UAV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
+    { "giprobevisualization_CS_LoadGIProbes", TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },         // k_giprobedraw.hip
+    { "giprobevisualization_PS_VisualizeGIProbes", TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
+    { "giprobevisualization_PS_VisualizeGIProbes", TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_R10G10B10A2_UNORM, "R10G10B10A2_UNORM" },
+    { "giprobevisualization_PS_VisualizeGIProbes", TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_RG16_FLOAT, "RG16_FLOAT" },
 };
 
 static int checkArrayBinding(const char* name, const trhip_binding& b, const trhip_texture_t* t)
@@ -991,7 +995,7 @@ static int checkArrayBinding(const char* name, const trhip_binding& b, const trh
     }
     return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: the pass declares no array texture there (deferredlighting_PS_Main and _Debug: t6..t8; "
                                    "giprobetrace_CS_ProbeTrace: t1..t3; the probe blends: t3 and u1 (radiance) or u2 (distance); giprobetrace_CS_ProbeTraceFixedRays: t1; "
-                                   "probe relocation and classification: u3)", name, t->name.c_str(), kind, b.slot);
+                                   "probe relocation and classification: u3; giprobevisualization_CS_LoadGIProbes: t1; giprobevisualization_PS_VisualizeGIProbes: t1..t3)", name, t->name.c_str(), kind, b.slot);
 }
 
 static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_binding* b, uint32_t nb, const void* push, uint32_t pushBytes,

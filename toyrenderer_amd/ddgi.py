@@ -109,6 +109,28 @@ def check_update_settings(settings) -> dict:
     return u
 
 
+def unit_sphere():
+    """The unit sphere the probe visualisation draws (CommonResources.cpp:40-102, tessellation 6, winding reversed): (vertices
+    UncompressedRawVertexFormat [91], indices uint32 [468]).  Every angle is a multiple of pi / 6, so the sines are exactly 0, 1/2,
+    RN(sqrt(3) / 2) and 1 with the quadrant's sign: no libm, and the poles and the seam column are exactly degenerate (120 of the 156
+    triangles have area).  Byte for byte csrc/host/CommonResources.cpp's UnitSphere and tests/ddgi_probe_draw_ref.c's table."""
+    f = np.float32
+    r = f(float.fromhex("0x1.bb67aep-1"))                                  # RN(sqrt(3) / 2)
+    s = np.array([0.0, 0.5, r, 1.0, r, 0.5, 0.0, -0.5, -r, -1.0, -r, -0.5], f)
+    v = np.zeros(I.kUnitSphereVertices, I.UncompressedRawVertexFormat)
+    for i in range(7):
+        dy, dxz = s[(i + 9) % 12], s[i]
+        for j in range(13):
+            n = np.array([s[j % 12] * dxz, dy, s[(j + 3) % 12] * dxz], f)
+            v[i * 13 + j] = (n * f(0.5), n, (f(1.0) - f(j) / f(12.0), f(1.0) - f(i) / f(6.0)))
+    ix = []
+    for i in range(6):
+        for j in range(13):
+            n = (j + 1) % 13
+            ix += [i * 13 + n, (i + 1) * 13 + j, i * 13 + j, (i + 1) * 13 + n, (i + 1) * 13 + j, i * 13 + n]
+    return v, np.asarray(ix, np.uint32)
+
+
 class Volume:
     def __init__(self, origin, spacing, counts, normal_bias: float, view_bias: float, gamma: float = DEFAULT_GAMMA, relocation: bool = True,
                  classification: bool = True):

@@ -159,7 +159,7 @@ class FrameDriver:
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
                  bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
-                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None):
+                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None, probes=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -252,7 +252,15 @@ class FrameDriver:
         scene radius below 3) and fixed_ray_backface_threshold (0.25).  Each needs its flag on the volume (ddgi.Volume(relocation=,
         classification=), on by default) and gives the data texture the UAV bit; the lighting pass of the same frame sees the new
         data; download_ddgi_fixed_rays() reads the distances back.  With both off the supplied data texture is honoured as it is
-        and the update records what it recorded before (csrc/k_giprobeplacement.hip)."""
+        and the update records what it recorded before (csrc/k_giprobeplacement.hip).
+        probes: None (the default) changes nothing.  A dict (needs ddgi= and post=True) draws the volume's probes into the back buffer
+        behind the post pass, GIDebugRenderer's three dispatches (csrc/k_giprobedraw.hip, csrc/k_giprobe.hip): "giprobevisualization_
+        CS_LoadGIProbes" writes every probe's position and state from the LIVE volume into self.probe_positions and
+        self.probe_states, "giprobevisualization_CS_VisualizeGIProbesCulling" culls them against the frame's HZB into
+        self.probe_culled_positions, self.probe_draw_args and self.probe_instance_to_probe, and "giprobevisualization_PS_
+        VisualizeGIProbes" draws the survivors as spheres shaded with their own irradiance, depth-tested against self.depth, which it
+        also writes.  Settings: radius (0.1, GIRenderer.cpp's m_ProbeRadius) and hide_inactive (False).  The block the draw ran with
+        is self.probe_draw_consts; download_probes() and download_probe_winners() read the results back."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -278,6 +286,16 @@ class FrameDriver:
             for option, flag, word in (("relocate", ddgi.relocation, "relocation"), ("classify", ddgi.classification, "classification")):
                 if self.ddgi_update[option] and not flag:
                     raise ValueError(f"ddgi_update: {option}=True needs ddgi.Volume({word}=True): with the flag off nothing reads what the pass writes")
+        self.probes = None
+        if probes is not None:
+            if ddgi is None or not post:
+                raise ValueError("probes=... needs " + ("ddgi=ddgi.Volume(...): the volume whose probes are drawn" if ddgi is None else "post=True: the spheres are drawn into the back buffer"))
+            unknown = set(probes) - {"radius", "hide_inactive"}
+            if unknown:
+                raise ValueError(f"probes: unknown settings {sorted(unknown)}; known: ['hide_inactive', 'radius']")
+            self.probes = dict(radius=float(probes.get("radius", 0.1)), hide_inactive=bool(probes.get("hide_inactive", False)))
+            if not (np.isfinite(self.probes["radius"]) and self.probes["radius"] > 0.0):
+                raise ValueError(f"probes: radius = {self.probes['radius']} is not positive and finite")
         self.alpha_test = bool(alpha_test)
         if self.alpha_test and not (raster_depth or visibility):
             raise ValueError("alpha_test=True needs raster_depth=True (or visibility, gbuffer, lighting, post): the test runs in the rasters, and a frame without them draws nothing")
@@ -397,6 +415,19 @@ class FrameDriver:
             if placement:                            # the distances of the 32 fixed rays of every probe
                 self.ddgi_fixed_rays = dev.create_buffer(int(np.prod(self.ddgi.counts)) * I.kDDGIFixedRays * 4, "DDGI Fixed Ray Distances", stride=4)
                 self.ddgi_fixed_rays.upload(np.zeros(self.ddgi_fixed_rays.size // 4, np.float32))
+        self.probe_positions = self.probe_states = self.probe_culled_positions = self.probe_draw_args = self.probe_instance_to_probe = None
+        self.probe_sphere_vertices = self.probe_sphere_indices = self.probe_winners = self.probe_draw_consts = self.probe_cull_consts = None
+        if self.probes is not None:                  # GIDebugRenderer::Setup (GIRenderer.cpp:612-657) + CommonResources' UnitSphere
+            n_probes = int(np.prod(self.ddgi.counts))
+            self.probe_positions = dev.create_buffer(12 * n_probes, "GI Probe Positions", stride=12)
+            self.probe_states = dev.create_buffer(4 * n_probes, "GI Probe States")
+            self.probe_culled_positions = dev.create_buffer(12 * n_probes, "Probe Positions", stride=12)
+            self.probe_draw_args = dev.create_buffer(20, "Probe Draw Indirect Args", stride=20, indirect=True)
+            self.probe_instance_to_probe = dev.create_buffer(4 * n_probes, "Instance ID to Probe Index")
+            sphere_v, sphere_i = ddgimod.unit_sphere()
+            self.probe_sphere_vertices = dev.buffer_from(sphere_v, "Unit Sphere Vertex Buffer", uav=False)
+            self.probe_sphere_indices = dev.buffer_from(sphere_i, "Unit Sphere Index Buffer", uav=False)
+            self.probe_winners = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RG32_UINT, "Probe Draw Winners")
         if self.gbuffer_on:                          # GBufferA (GraphicConstants.h:24), created in GBufferRenderer::Setup (:622-632)
             self.gbufferA = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA32_UINT, "GBufferA")
         if self.visibility_on:                       # GBufferRenderer's visibility buffer + GBufferMotion, render resolution
@@ -775,6 +806,59 @@ class FrameDriver:
         cl.dispatch("postprocess_PS_PostProcess", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1), push=pk)
         self.post_consts = (hk, ak, pk)
 
+    # ---- GIDebugRenderer::RenderDDGIDebug (GIRenderer.cpp:672-808) ------------------------------
+    def _probe_visualization(self, cl):
+        v, vol = self.view, self.ddgi
+        n = int(np.prod(vol.counts))
+        desc = vol.desc()
+        cl.dispatch("giprobevisualization_CS_LoadGIProbes",
+                    [CB(0, cl.constant_buffer(np.frombuffer(desc.tobytes(), np.uint8), "DDGIVolumeDesc")), SRV(0, self.ddgi_desc), TEX_SRV(1, self.ddgi_data),
+                     UAV(0, self.probe_positions), UAV(1, self.probe_states)], ((n + 31) // 32, 1, 1))
+        args = np.zeros(1, I.DrawIndexedIndirectArguments)                               # :683-689: the sphere's indices, no instance yet
+        args["m_IndexCount"] = I.kUnitSphereIndices
+        cl.write_buffer(self.probe_draw_args, args)
+        ck = np.zeros(1, I.GIProbeVisualizationUpdateConsts)                             # :687-708
+        ck["m_NumProbes"] = n
+        ck["m_CameraOrigin"] = self.camera_origin
+        ck["m_Frustum"] = culling_frustum(v.viewToClip)
+        ck["m_WorldToView"] = v.worldToView
+        ck["m_HZBDimensions"] = (self.hzb_w, self.hzb_h)
+        ck["m_P00"], ck["m_P11"] = v.viewToClip[0, 0], v.viewToClip[1, 1]
+        ck["m_NearPlane"] = v.nearPlane
+        ck["m_ProbeRadius"] = self.probes["radius"]
+        ck["m_bHideInactiveProbes"] = int(self.probes["hide_inactive"])
+        cl.dispatch("giprobevisualization_CS_VisualizeGIProbesCulling",
+                    [CB(0, cl.constant_buffer(ck, "GIProbeVisualizationUpdateConsts")), TEX_SRV(0, self.hzb), SRV(10, self.probe_positions), SRV(11, self.probe_states),
+                     UAV(0, self.probe_culled_positions), UAV(1, self.probe_draw_args), UAV(2, self.probe_instance_to_probe), SAMPLER(0)], ((n + 31) // 32, 1, 1))
+        dk = np.zeros(1, I.GIProbeVisualizationConsts)                                   # :745-752
+        dk["m_WorldToClip"] = I.world_to_clip(v.worldToView, v.viewToClip)
+        dk["m_CameraDirection"] = -np.asarray(v.worldToView, np.float32)[:3, 2]          # the view looks down -Z; the draw does not read it
+        dk["m_ProbeRadius"] = self.probes["radius"]
+        dk["m_NearPlane"] = v.nearPlane
+        block = np.frombuffer(dk.tobytes() + desc.tobytes(), np.uint8)
+        cl.dispatch("giprobevisualization_PS_VisualizeGIProbes",
+                    [CB(0, cl.constant_buffer(block, "GIProbeVisualizationConsts")), SRV(0, self.probe_culled_positions), TEX_SRV(1, self.ddgi_data),
+                     TEX_SRV(2, self.ddgi_irradiance), TEX_SRV(3, self.ddgi_distance), SRV(4, self.ddgi_desc), SRV(5, self.probe_instance_to_probe),
+                     SRV(6, self.probe_draw_args), SRV(7, self.probe_sphere_vertices), SRV(8, self.probe_sphere_indices), TEX_UAV(0, self.depth, 0),
+                     TEX_UAV(1, self.back_buffer, 0), TEX_UAV(2, self.probe_winners, 0), SAMPLER(0)], (1, 1, 1))
+        self.probe_cull_consts, self.probe_draw_consts = ck, dk
+
+    def download_probes(self):
+        """(count, culled positions float32 [count, 3], instance -> probe index uint32 [count]) of the last frame run."""
+        if self.probes is None:
+            raise ValueError("download_probes: the probe visualisation is off (probes=None)")
+        self.dev.wait_idle()
+        n = int(np.prod(self.ddgi.counts))
+        count = min(int(self.probe_draw_args.download(np.uint32, 5)[1]), n)
+        return count, self.probe_culled_positions.download(np.float32, 3 * n).reshape(n, 3)[:count], self.probe_instance_to_probe.download(np.uint32, n)[:count]
+
+    def download_probe_winners(self) -> np.ndarray:
+        """The draw's winner words of the last frame run, uint64 [H, W]: (depth bits << 32) | instance << 8 | triangle, 0 = no sphere."""
+        if self.probes is None:
+            raise ValueError("download_probe_winners: the probe visualisation is off (probes=None)")
+        self.dev.wait_idle()
+        return self.probe_winners.download_mip(0)
+
     # ---- BasePassRenderer::GenerateHZB (:505-542) + SPD::Execute (FFXHelpers.cpp:36-115) --------
     def _generate_hzb(self, cl):
         if self.freeze:
@@ -849,6 +933,8 @@ class FrameDriver:
             self._bloom(cl)
         if self.post_on:                                                                 # Scene.cpp's order: adapt luminance, then post
             self._post_process(cl)
+        if self.probes is not None:                                                      # Scene.cpp:317: GIDebugRenderer, behind PostProcessRenderer
+            self._probe_visualization(cl)
         cl.close()
         return cl
 
@@ -885,6 +971,8 @@ class FrameDriver:
         self.hzb.release(); self.depth.release()
         for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
                   self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
-                  self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays, self.ddgi_fixed_rays):
+                  self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays, self.ddgi_fixed_rays,
+                  self.probe_positions, self.probe_states, self.probe_culled_positions, self.probe_draw_args, self.probe_instance_to_probe, self.probe_sphere_vertices,
+                  self.probe_sphere_indices, self.probe_winners):
             if t is not None:
                 t.release()

@@ -31,6 +31,7 @@ HOST_SYMBOLS = [
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
     "trhost_get_deferred_lighting_consts", "trhost_upload_ddgi_volume", "trhost_set_ddgi",
     "trhost_set_ddgi_update", "trhost_set_ddgi_probe_placement", "trhost_reset_ddgi_volume", "trhost_download_ddgi_volume", "trhost_get_ddgi_update_consts",
+    "trhost_set_ddgi_probe_visualization", "trhost_get_ddgi_probe_visualization_consts", "trhost_unit_sphere",
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
@@ -112,6 +113,9 @@ def load() -> C.CDLL:
     L.trhost_reset_ddgi_volume.argtypes = []
     L.trhost_download_ddgi_volume.argtypes = [vp, u64, vp, u64, vp, u64]
     L.trhost_get_ddgi_update_consts.argtypes = [vp]
+    L.trhost_set_ddgi_probe_visualization.argtypes = [C.c_int, C.c_float, C.c_int]
+    L.trhost_get_ddgi_probe_visualization_consts.argtypes = [vp]
+    L.trhost_unit_sphere.argtypes = [vp, u64, vp, u64]
     L.trhost_set_post_process.argtypes = [C.c_int]
     L.trhost_set_exposure.argtypes = [C.c_float, C.c_float]
     L.trhost_set_auto_exposure.argtypes = [C.c_float, C.c_float, C.c_float]
@@ -180,6 +184,14 @@ def _download(handle, dtype, count):
         if rc != 0:
             raise HostError(rhi.load().trhip_last_error().decode())
     return out
+
+
+def unit_sphere():
+    """(vertices UncompressedRawVertexFormat [91], indices uint32 [468]) of the host library's CommonResources::UnitSphere, the sphere
+    GIDebugRenderer draws a probe as.  Needs no device."""
+    v, ix = np.zeros(I.kUnitSphereVertices, I.UncompressedRawVertexFormat), np.zeros(I.kUnitSphereIndices, np.uint32)
+    _check(load().trhost_unit_sphere(v.ctypes.data, v.nbytes, ix.ctypes.data, ix.nbytes))
+    return v, ix
 
 
 class Renderer:
@@ -399,6 +411,18 @@ class Renderer:
         """The DDGIUpdateConsts of the last frame's probe update, the ray rotation among them; raises if none ran in it."""
         k = np.zeros(1, I.DDGIUpdateConsts)
         _check(load().trhost_get_ddgi_update_consts(k.ctypes.data))
+        return k
+
+    def set_ddgi_probe_visualization(self, enable: bool = True, probe_radius: float = 0.1, hide_inactive: bool = False):
+        """GIDebugRenderer on the live volume: LoadGIProbes, the cull, and the draw of the surviving probes as spheres into the back
+        buffer behind the post pass (needs the volume and set_post_process: the next frame() raises and says which is missing;
+        include/trhost.h).  gi_probe_results() reads the cull's outputs."""
+        _check(load().trhost_set_ddgi_probe_visualization(int(enable), float(probe_radius), int(hide_inactive)))
+
+    def ddgi_probe_visualization_consts(self) -> np.ndarray:
+        """The GIProbeVisualizationConsts of the last frame's probe draw; raises if it drew none."""
+        k = np.zeros(1, I.GIProbeVisualizationConsts)
+        _check(load().trhost_get_ddgi_probe_visualization_consts(k.ctypes.data))
         return k
 
     def set_post_process(self, on: bool = True):

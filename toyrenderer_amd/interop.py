@@ -59,6 +59,11 @@ GIProbeVisualizationUpdateConsts = np.dtype([                                   
     ("m_NumProbes", np.uint32), ("m_CameraOrigin", np.float32, (3,)), ("m_Frustum", np.float32, (4,)), ("m_WorldToView", np.float32, (4, 4)),
     ("m_HZBDimensions", np.uint32, (2,)), ("m_P00", np.float32), ("m_P11", np.float32), ("m_NearPlane", np.float32), ("m_ProbeRadius", np.float32),
     ("m_bHideInactiveProbes", np.uint32)])
+GIProbeVisualizationConsts = np.dtype([                                                                                    # ShaderInterop.h:263-268, then the project's own
+    ("m_WorldToClip", np.float32, (4, 4)), ("m_CameraDirection", np.float32, (3,)), ("m_ProbeRadius", np.float32), ("m_NearPlane", np.float32),
+    ("pad", np.uint32, (3,))])
+UncompressedRawVertexFormat = np.dtype([("m_Position", np.float32, (3,)), ("m_Normal", np.float32, (3,)), ("m_TexCoord", np.float32, (2,))])   # ShaderInterop.h:270-276
+kUnitSphereVertices, kUnitSphereIndices = 91, 468
 NodeLocalTransform = np.dtype([
     ("m_ParentNodeIdx", np.uint32), ("m_Position", np.float32, (3,)), ("m_Rotation", np.float32, (4,)),
     ("m_Scale", np.float32, (3,)), ("PAD0", np.uint32)])
@@ -130,7 +135,7 @@ SIZES = {
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
     "BloomConsts": 16, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
     "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
-    "ShadowMaskConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96,"RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
+    "ShadowMaskConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96, "GIProbeVisualizationConsts": 96, "UncompressedRawVertexFormat": 32, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)
