@@ -23,7 +23,8 @@
  *      given, the descriptor index is past the table, the entry is empty or of another format.
  *   The surviving samples feed the same maxima, so the result does not depend on the draw order.  Parity with hardware unpinned.
  *
- * RAYS (at_trace).  occluded_brute of tests/shadowmask_ref.c restated: every triangle of every instance.  A candidate on a
+ * RAYS (at_trace).  occluded_brute of tests/shadowmask_ref.c restated with that file's fetch_tri and tri_candidate: every triangle of
+ *   every instance, a loop of its own.  A candidate on a
  *   ForceNonOpaque instance whose material has MaterialFlag_UseAlbedoTexture counts iff
  *   m_ConstAlbedo.w * at_alpha_level0(albedo texture, m_IsWrapSampler, uv) >= m_AlphaCutoff, with InterpolateVertex's uv
  *   (raytracingcommon.hlsli:24-36, :189): b1 = V / det, b2 = W / det of the watertight test's edge values, b0 = (1.0f - b1) - b2,
@@ -174,25 +175,6 @@ void at_raster(const OrcBasePassConstants* k, const OrcBasePassInstanceConstants
 }
 
 /* ---- the sun rays ------------------------------------------------------------------------------------------------------------ */
-/* sm_tri_hit, with the barycentrics of the second and third vertex */
-static int at_tri_hit(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax, float* b1, float* b2)
-{
-    const F3 A = { v0.x - r->o.x, v0.y - r->o.y, v0.z - r->o.z }, B = { v1.x - r->o.x, v1.y - r->o.y, v1.z - r->o.z }, C = { v2.x - r->o.x, v2.y - r->o.y, v2.z - r->o.z };
-    const float Akz = sel(A, r->kz), Bkz = sel(B, r->kz), Ckz = sel(C, r->kz);
-    const float Ax = sel(A, r->kx) - r->Sx * Akz, Ay = sel(A, r->ky) - r->Sy * Akz;
-    const float Bx = sel(B, r->kx) - r->Sx * Bkz, By = sel(B, r->ky) - r->Sy * Bkz;
-    const float Cx = sel(C, r->kx) - r->Sx * Ckz, Cy = sel(C, r->ky) - r->Sy * Ckz;
-    const float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f)) return 0;
-    const float det = (U + V) + W;
-    if (det == 0.0f) return 0;
-    const float Az = r->Sz * Akz, Bz = r->Sz * Bkz, Cz = r->Sz * Ckz;
-    const float T = (U * Az + V * Bz) + W * Cz;
-    const float t = T / det;
-    *b1 = V / det; *b2 = W / det;
-    return t > tmin && t < tmax;
-}
-
 static int at_commits(const SmScene* s, const MtTexture* textures, int64_t numTextures, uint32_t inst, uint32_t flags, const uint16_t tc[3][2], float b1, float b2)
 {
     if (flags != 2u) return 1;
@@ -221,21 +203,12 @@ static int at_occluded(const SmScene* s, const MtTexture* textures, int64_t numT
         sm_object_from_world(s->instances[i].world, m);
         const SmRay r = make_ray(mul_point(o, m, 1), mul_point(d, m, 0));
         for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t) {
-            const uint64_t base = (uint64_t)s->meshes[mesh].indexBase + 3ull * t;
-            if (base + 3u > s->numIndices) continue;
-            F3 v[3];
+            SmTri T;
+            SmTriHit h;
             uint16_t tc[3][2];
-            int ok = 1;
-            for (int k = 0; ok && k < 3; ++k) {
-                const uint64_t vi = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + k];
-                ok = vi < s->numVertices;
-                if (!ok) break;
-                v[k] = vertex_of(s, vi);
-                ok = finite3(v[k]);
-                memcpy(tc[k], s->vertices + vi * 20u + 16u, 4);
-            }
-            float b1, b2;
-            if (ok && at_tri_hit(v[0], v[1], v[2], &r, tmin, tmax, &b1, &b2) && at_commits(s, textures, numTextures, i, flags, tc, b1, b2)) return 1;
+            if (!fetch_tri(s, mesh, t, 1, &T) || !tri_candidate(T.v[0], T.v[1], T.v[2], &r, &h) || !(h.t > tmin && h.t < tmax)) continue;
+            for (int k = 0; k < 3; ++k) memcpy(tc[k], s->vertices + T.i[k] * 20u + 16u, 4);
+            if (at_commits(s, textures, numTextures, i, flags, tc, h.b1, h.b2)) return 1;
         }
     }
     return 0;

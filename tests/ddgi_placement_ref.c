@@ -3,8 +3,8 @@
  * repeat the functions below word for word.  Compile with gcc -O2 -ffp-contract=off (tests/ddgi_placement_ref.py).
  *
  * The RTXGI SDK is not part of this project: the three passes are the project's own statement of the published probe relocation
- * and classification, and this file is what the tests pin.  It includes tests/ddgi_update_ref.c for the closest hit (brute force
- * and the walk), a probe's position and the constant block.
+ * and classification, and this file is what the tests pin.  It includes tests/ddgi_update_ref.c for the closest hit (closest():
+ * brute force, or the one walk of tests/shadowmask_ref.c), a probe's position and the constant block.
  *
  * CONVENTION.  binary32 throughout, no contraction, fmaf only in dot3, / and sqrtf correctly rounded; S the spacing.
  *   fixed ray i   of 32: f = (float)i * 0.618034f; phi = RN(2 pi) * (f - floorf(f)); c = 1.0f - (float)(2 * i + 1) / 32.0f; s =
@@ -50,7 +50,7 @@ void dp_trace_fixed(const DuBlock* b, const SmScene* s, const uint16_t* data, in
             float dir[3];
             dp_fixed_direction(r, dir);
             const F3 Dir = { dir[0], dir[1], dir[2] };
-            const DuHit hit = mode ? closest_walk(s, O, Dir, 0.0f, b->k.maxRayDistance) : closest_brute(s, O, Dir, 0.0f, b->k.maxRayDistance, &ties);
+            const DuHit hit = closest(s, O, Dir, 0.0f, b->k.maxRayDistance, mode, &ties);
             distances[(uint64_t)p * DP_FIXED_RAYS + r] = hit.inst == 0xFFFFFFFFu ? 1e27f : (hit.front ? hit.t : -0.2f * hit.t);
         }
     }

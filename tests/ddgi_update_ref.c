@@ -5,7 +5,8 @@
  * The RTXGI SDK is not part of this project: the update is the project's own statement of the published algorithm (Majercik et
  * al., JCGT 2019) with the settings GIRenderer.cpp:74-121 configures, and this file is what the tests pin.
  *
- * It includes tests/shadowmask_ref.c for the ray, the box test, the watertight triangle test and the scene's arrays, and
+ * It includes tests/shadowmask_ref.c for the ray, the box test, the watertight triangle test, the triangle fetch, the walk (sm_walk,
+ * whose visitor closest_walk below is; closest_brute stays a loop of its own over every triangle) and the scene's arrays, and
  * tests/ddgi_ref.c (and through it tests/lighting_ref.c) for the irradiance query, the soft pow and the directional light's pieces.
  *
  * CONVENTION.  binary32 throughout, no contraction, fmaf only where written, / and sqrtf correctly rounded.
@@ -92,104 +93,52 @@ void du_texel_direction(uint32_t ix, uint32_t iy, uint32_t n, float out[3])
 }
 
 /* ---- the closest hit ------------------------------------------------------------------------------------------------------------ */
-static int tri_hit_closest(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax, float* t, float* b1, float* b2, uint32_t* front)
-{
-    const F3 A = { v0.x - r->o.x, v0.y - r->o.y, v0.z - r->o.z }, B = { v1.x - r->o.x, v1.y - r->o.y, v1.z - r->o.z }, C = { v2.x - r->o.x, v2.y - r->o.y, v2.z - r->o.z };
-    const float Akz = sel(A, r->kz), Bkz = sel(B, r->kz), Ckz = sel(C, r->kz);
-    const float Ax = sel(A, r->kx) - r->Sx * Akz, Ay = sel(A, r->ky) - r->Sy * Akz;
-    const float Bx = sel(B, r->kx) - r->Sx * Bkz, By = sel(B, r->ky) - r->Sy * Bkz;
-    const float Cx = sel(C, r->kx) - r->Sx * Ckz, Cy = sel(C, r->ky) - r->Sy * Ckz;
-    const float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
-    if ((U < 0.0f || V < 0.0f || W < 0.0f) && (U > 0.0f || V > 0.0f || W > 0.0f)) return 0;
-    const float det = (U + V) + W;
-    if (det == 0.0f) return 0;
-    const float Az = r->Sz * Akz, Bz = r->Sz * Bkz, Cz = r->Sz * Ckz;
-    const float T = (U * Az + V * Bz) + W * Cz;
-    *t = T / det;
-    *b1 = V / det; *b2 = W / det;
-    *front = det > 0.0f ? 1u : 0u;
-    return *t > tmin && *t < tmax;
-}
+typedef struct { SmInterval in; DuHit best; } DuClosest;
 
-/* triangle `tri` of mesh `mesh` against the object-space ray, offered to `best` under the tie rule; with requireFinite a
+/* triangle `tri` of mesh `mesh` against the object-space ray, offered to c->best under the tie rule; with requireFinite a
  * triangle with a non-finite vertex is left out (the builder leaves it out of the tree).  Returns 1 on equal t with another
  * candidate (a tie that the rule decided). */
-static int offer(const SmScene* s, uint32_t inst, uint32_t mesh, uint32_t tri, const SmRay* r, float tmin, float tmax, int requireFinite, DuHit* best)
+static int offer(const SmScene* s, uint32_t inst, uint32_t mesh, uint32_t tri, const SmRay* r, int requireFinite, DuClosest* c)
 {
-    const uint64_t base = (uint64_t)s->meshes[mesh].indexBase + 3ull * tri;
-    if (base + 3u > s->numIndices) return 0;
-    F3 v[3];
-    for (int k = 0; k < 3; ++k) {
-        const uint64_t vi = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + k];
-        if (vi >= s->numVertices) return 0;
-        v[k] = vertex_of(s, vi);
-        if (requireFinite && !finite3(v[k])) return 0;
-    }
-    float t, b1, b2;
-    uint32_t front;
-    if (!tri_hit_closest(v[0], v[1], v[2], r, tmin, tmax, &t, &b1, &b2, &front)) return 0;
-    const int first = best->inst == 0xFFFFFFFFu, tie = !first && t == best->t;
-    if (first || t < best->t || (tie && (inst < best->inst || (inst == best->inst && tri < best->tri)))) {
-        const DuHit h = { inst, tri, t, b1, b2, front };
-        *best = h;
+    SmTri T;
+    SmTriHit h;
+    if (!fetch_tri(s, mesh, tri, requireFinite, &T) || !tri_candidate(T.v[0], T.v[1], T.v[2], r, &h) || !(h.t > c->in.tmin && h.t < c->in.tmax)) return 0;
+    DuHit* best = &c->best;
+    const int first = best->inst == 0xFFFFFFFFu, tie = !first && h.t == best->t;
+    if (first || h.t < best->t || (tie && (inst < best->inst || (inst == best->inst && tri < best->tri)))) {
+        const DuHit won = { inst, tri, h.t, h.b1, h.b2, h.front };
+        *best = won;
     }
     return tie;
 }
 
-static DuHit closest_brute(const SmScene* s, F3 o, F3 d, float tmin, float tmax, uint64_t* ties)
+static void closest_brute(const SmScene* s, F3 o, F3 d, DuClosest* c, uint64_t* ties)
 {
-    DuHit best = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0.0f, 0u };
     for (uint32_t i = 0; i < s->numInstances; ++i) {
         const uint32_t flags = s->flags[i] & 3u, mesh = s->instances[i].mesh;
         if (!flags || mesh >= s->numMeshes) continue;
         float m[12];
         sm_object_from_world(s->instances[i].world, m);
         const SmRay r = make_ray(mul_point(o, m, 1), mul_point(d, m, 0));
-        for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t) *ties += (uint64_t)offer(s, i, mesh, t, &r, tmin, tmax, 1, &best);
+        for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t) *ties += (uint64_t)offer(s, i, mesh, t, &r, 1, c);
     }
-    return best;
 }
 
-static DuHit closest_walk(const SmScene* s, F3 o, F3 d, float tmin, float tmax)
+/* the closest hit's visitor of sm_walk (tests/shadowmask_ref.c); ctx: the ray's DuClosest.  Never stops the walk. */
+static int closest_walk(void* ctx, const SmScene* s, uint32_t inst, uint32_t flags, uint32_t mesh, uint32_t tri, const SmRay* r)
 {
-    DuHit best = { 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0.0f, 0u };
-    const SmRay wr = make_ray(o, d);
-    uint32_t node = 0;
-    while (node < s->numTlasNodes) {
-        const SmNode* n = &s->tlasNodes[node];
-        uint32_t next = n->skip > node ? n->skip : s->numTlasNodes;
-        if (sm_box_hit(n->lo, n->hi, &wr)) {
-            if (n->leaf == SM_INNER) next = node + 1;
-            else if (n->leaf < s->numInstances) {
-                const uint32_t inst = n->leaf, flags = s->tlasInstances[inst].flags, mesh = s->instances[inst].mesh;
-                if (flags && mesh < s->numMeshes) {
-                    const SmHeader hd = s->headers[mesh];
-                    const float* m = s->tlasInstances[inst].m;
-                    const SmRay r = make_ray(mul_point(o, m, 1), mul_point(d, m, 0));
-                    const uint32_t count = (uint64_t)hd.node_offset + hd.num_nodes <= s->numBlasNodes ? hd.num_nodes : 0u;
-                    uint32_t b = 0;
-                    while (b < count) {
-                        const SmNode* bn = &s->blasNodes[hd.node_offset + b];
-                        uint32_t bnext = bn->skip > b ? bn->skip : count;
-                        if (sm_box_hit(bn->lo, bn->hi, &r)) {
-                            if (bn->leaf == SM_INNER) bnext = b + 1;
-                            else {
-                                const uint32_t first = bn->leaf & 0x3FFFFFFFu, cnt = (bn->leaf >> 30) + 1u;
-                                for (uint32_t j = 0; j < cnt; ++j) {
-                                    const uint64_t slot = (uint64_t)hd.tri_offset + first + j;
-                                    if (first + j >= hd.num_tris || slot >= s->numTriOrder) break;
-                                    offer(s, inst, mesh, s->triOrder[slot], &r, tmin, tmax, 0, &best);
-                                }
-                            }
-                        }
-                        b = bnext;
-                    }
-                }
-            }
-        }
-        node = next;
-    }
-    return best;
+    (void)flags;
+    offer(s, inst, mesh, tri, r, 0, (DuClosest*)ctx);
+    return 0;
+}
+
+/* mode 0: brute force, 1: the walk.  ties: the equal-t decisions brute force met (added to). */
+static DuHit closest(const SmScene* s, F3 o, F3 d, float tmin, float tmax, int mode, uint64_t* ties)
+{
+    DuClosest c = { { tmin, tmax }, { 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0f, 0.0f, 0.0f, 0u } };
+    if (mode) sm_walk(s, o, d, closest_walk, &c, NULL);
+    else closest_brute(s, o, d, &c, ties);
+    return c.best;
 }
 
 /* n rays; mode 0: brute force, 1: the walk.  ties: uint64[1] or NULL, the equal-t decisions brute force met (added to). */
@@ -198,7 +147,7 @@ void du_closest_n(const SmScene* s, const float* o, const float* d, uint64_t n, 
     uint64_t local = 0;
     for (uint64_t i = 0; i < n; ++i) {
         const F3 O = { o[3 * i], o[3 * i + 1], o[3 * i + 2] }, Dir = { d[3 * i], d[3 * i + 1], d[3 * i + 2] };
-        out[i] = mode ? closest_walk(s, O, Dir, tmin, tmax) : closest_brute(s, O, Dir, tmin, tmax, &local);
+        out[i] = closest(s, O, Dir, tmin, tmax, mode, &local);
     }
     if (ties) *ties += local;
 }
@@ -250,19 +199,17 @@ static void trace_ray(const DuBlock* b, const SmScene* s, const uint16_t* data, 
     float dir[3];
     du_ray_direction(&b->k, ray, dir);
     const F3 O = { origin[0], origin[1], origin[2] }, Dir = { dir[0], dir[1], dir[2] }, L = { b->k.light[0], b->k.light[1], b->k.light[2] };
-    const DuHit hit = mode ? closest_walk(s, O, Dir, 0.0f, b->k.maxRayDistance) : closest_brute(s, O, Dir, 0.0f, b->k.maxRayDistance, &ties);
+    const DuHit hit = closest(s, O, Dir, 0.0f, b->k.maxRayDistance, mode, &ties);
     if (hit.inst == 0xFFFFFFFFu) { rec[0] = rec[1] = rec[2] = 1.0f; rec[3] = 1e27f; if (kind) *kind = 0; return; }
     if (!hit.front) { rec[0] = rec[1] = rec[2] = 0.0f; rec[3] = -0.2f * hit.t; if (kind) *kind = 1; return; }
     const SmInstance* inst = &s->instances[hit.inst];
-    const SmMesh* md = &s->meshes[inst->mesh];
-    const uint64_t base = (uint64_t)md->indexBase + 3ull * hit.tri;
-    F3 v[3];
+    SmTri T;
+    if (!fetch_tri(s, inst->mesh, hit.tri, 0, &T)) return;                   /* cannot fail: the closest hit fetched this triangle */
+    const F3* v = T.v;
     float n[3][3];
     for (int j = 0; j < 3; ++j) {
-        const uint64_t vi = (uint64_t)md->vertexBase + s->indices[base + j];
         uint32_t packed;
-        v[j] = vertex_of(s, vi);
-        memcpy(&packed, s->vertices + vi * 20u + 12u, 4);
+        memcpy(&packed, s->vertices + T.i[j] * 20u + 12u, 4);
         unpack_vertex_normal(packed, n[j]);
     }
     const float b1 = hit.b1, b2 = hit.b2, b0 = (1.0f - b1) - b2;
@@ -278,8 +225,7 @@ static void trace_ray(const DuBlock* b, const SmScene* s, const uint16_t* data, 
         memcpy(g.emissive, s->materials[inst->material].emissive, sizeof g.emissive);
     }
     g.roughness = 1.0f; g.metallic = 0.0f;
-    const DuHit blocker = mode ? closest_walk(s, O, L, 0.0f, 1e10f) : closest_brute(s, O, L, 0.0f, 1e10f, &ties);
-    const int occluded = blocker.inst != 0xFFFFFFFFu;
+    const int occluded = closest(s, O, L, 0.0f, 1e10f, mode, &ties).inst != 0xFFFFFFFFu;
     float lit[3], irr[3];
     lit_surface(&g, origin, world, b->k.light, b->k.strength, occluded ? 0.0f : 1.0f, lit);
     dg_irradiance(&b->D, data, irradiance, distance, world, g.normal, origin, irr, NULL);

@@ -1,5 +1,7 @@
-/* shadowmask_ref.c -- the definition of "shadowmask_CS_ShadowMask" and "raytracing_CS_RefitTLAS" (csrc/k_shadowmask.hip), which
- * repeats the functions below word for word.  Compile with gcc -O2 -ffp-contract=off (tests/shadowmask_ref.py).
+/* shadowmask_ref.c -- the definition of "shadowmask_CS_ShadowMask" and "raytracing_CS_RefitTLAS" (csrc/k_shadowmask.hip) and of the
+ * ray walk that every tracing pass shares (csrc/ray_walk.hip.h): the walk (sm_walk), the triangle test (tri_candidate) and the
+ * triangle fetch (fetch_tri) are stated ONCE here, and tests/ddgi_update_ref.c, tests/alpha_test_ref.c and
+ * tests/ddgi_placement_ref.c include this file for them.  Compile with gcc -O2 -ffp-contract=off (tests/shadowmask_ref.py).
  *
  * TWO EVALUATORS of one texel's occlusion:
  *   brute force (mode 0): every triangle of every instance's index list.  This is the definition of the mask.
@@ -215,8 +217,11 @@ int sm_box_hit(const float* lo, const float* hi, const SmRay* r)
     return tenter <= texit;
 }
 
-/* the edge test and det != 0 of sm_tri_hit: 1 with the candidate's t, which sm_tri_hit then holds against the ray's interval */
-static int tri_candidate(F3 v0, F3 v1, F3 v2, const SmRay* r, float* tOut)
+/* THE triangle test (csrc/ray_walk.hip.h: triTest): the edge test and det != 0; 1 with the candidate's t, which the caller holds against
+ * the ray's interval, b1 = V / det and b2 = W / det (InterpolateVertex's barycentrics of the second and third vertex) and front = det > 0 */
+typedef struct { float t, b1, b2; uint32_t front; } SmTriHit;
+
+static int tri_candidate(F3 v0, F3 v1, F3 v2, const SmRay* r, SmTriHit* h)
 {
     const F3 A = { v0.x - r->o.x, v0.y - r->o.y, v0.z - r->o.z }, B = { v1.x - r->o.x, v1.y - r->o.y, v1.z - r->o.z }, C = { v2.x - r->o.x, v2.y - r->o.y, v2.z - r->o.z };
     const float Akz = sel(A, r->kz), Bkz = sel(B, r->kz), Ckz = sel(C, r->kz);
@@ -229,15 +234,16 @@ static int tri_candidate(F3 v0, F3 v1, F3 v2, const SmRay* r, float* tOut)
     if (det == 0.0f) return 0;
     const float Az = r->Sz * Akz, Bz = r->Sz * Bkz, Cz = r->Sz * Ckz;
     const float T = (U * Az + V * Bz) + W * Cz;
-    *tOut = T / det;
+    h->t = T / det;
+    h->b1 = V / det; h->b2 = W / det;
+    h->front = det > 0.0f ? 1u : 0u;
     return 1;
 }
 
 int sm_tri_hit(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax)
 {
-    float t;
-    if (!tri_candidate(v0, v1, v2, r, &t)) return 0;
-    return t > tmin && t < tmax;
+    SmTriHit h;
+    return tri_candidate(v0, v1, v2, r, &h) && h.t > tmin && h.t < tmax;
 }
 
 /* ---- one texel's ray: 0 for a far texel, else origin and direction ------------------------------------------------------------- */
@@ -300,21 +306,34 @@ static int commits(const SmScene* s, uint32_t inst, uint32_t flags)
     return s->materials[mat].albedo[3] >= s->materials[mat].alphaCutoff;
 }
 
-/* triangle `tri` of mesh `mesh` against the object-space ray; 0 as well when an index leaves its buffer */
-static int mesh_tri_hit(const SmScene* s, uint32_t mesh, uint32_t tri, const SmRay* r, float tmin, float tmax)
+/* THE triangle fetch (csrc/ray_walk.hip.h: fetchTri): the three vertex indices and positions of triangle `tri` of mesh `mesh`; 0 when an
+ * index leaves its buffer, and with requireFinite (the brute-force evaluators: the builder leaves such a triangle out of the tree)
+ * when a vertex is not finite */
+typedef struct { uint64_t i[3]; F3 v[3]; } SmTri;
+
+static int fetch_tri(const SmScene* s, uint32_t mesh, uint32_t tri, int requireFinite, SmTri* out)
 {
     const uint64_t base = (uint64_t)s->meshes[mesh].indexBase + 3ull * tri;
     if (base + 3u > s->numIndices) return 0;
-    F3 v[3];
     for (int k = 0; k < 3; ++k) {
-        const uint64_t vi = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + k];
-        if (vi >= s->numVertices) return 0;
-        v[k] = vertex_of(s, vi);
+        out->i[k] = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + k];
+        if (out->i[k] >= s->numVertices) return 0;
+        out->v[k] = vertex_of(s, out->i[k]);
+        if (requireFinite && !finite3(out->v[k])) return 0;
     }
-    return sm_tri_hit(v[0], v[1], v[2], r, tmin, tmax);
+    return 1;
 }
 
-static int occluded_brute(const SmScene* s, F3 o, F3 d, float tmin, float tmax)
+typedef struct { float tmin, tmax; } SmInterval;
+
+/* triangle `tri` of mesh `mesh` against the object-space ray */
+static int mesh_tri_hit(const SmScene* s, uint32_t mesh, uint32_t tri, int requireFinite, const SmRay* r, const SmInterval* in)
+{
+    SmTri T;
+    return fetch_tri(s, mesh, tri, requireFinite, &T) && sm_tri_hit(T.v[0], T.v[1], T.v[2], r, in->tmin, in->tmax);
+}
+
+static int occluded_brute(const SmScene* s, F3 o, F3 d, const SmInterval* in)
 {
     for (uint32_t i = 0; i < s->numInstances; ++i) {
         const uint32_t flags = s->flags[i] & 3u, mesh = s->instances[i].mesh;
@@ -322,21 +341,21 @@ static int occluded_brute(const SmScene* s, F3 o, F3 d, float tmin, float tmax)
         float m[12];
         sm_object_from_world(s->instances[i].world, m);
         const SmRay r = make_ray(mul_point(o, m, 1), mul_point(d, m, 0));
-        for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t) {
-            const uint64_t base = (uint64_t)s->meshes[mesh].indexBase + 3ull * t;
-            int ok = base + 3u <= s->numIndices;
-            for (int k = 0; ok && k < 3; ++k) {
-                const uint64_t vi = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + k];
-                ok = vi < s->numVertices && finite3(vertex_of(s, vi));
-            }
-            if (ok && mesh_tri_hit(s, mesh, t, &r, tmin, tmax) && commits(s, i, flags)) return 1;
-        }
+        for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t)
+            if (mesh_tri_hit(s, mesh, t, 1, &r, in) && commits(s, i, flags)) return 1;
     }
     return 0;
 }
 
-static int occluded_walk(const SmScene* s, F3 o, F3 d, float tmin, float tmax, uint64_t* boxTests, uint64_t* triTests)
+/* THE walk (csrc/ray_walk.hip.h: walk, which states its rules): every candidate slot is handed to visit(ctx, s, instance, flags, mesh,
+ * the mesh's triangle number, the object-space ray); a visit that answers 1 stops the walk, and the walk answers whether it was
+ * stopped.  counters: NULL, or { box tests, candidate slots }, added to. */
+typedef int (*SmVisit)(void* ctx, const SmScene* s, uint32_t inst, uint32_t flags, uint32_t mesh, uint32_t tri, const SmRay* r);
+
+static int sm_walk(const SmScene* s, F3 o, F3 d, SmVisit visit, void* ctx, uint64_t* counters)
 {
+    uint64_t unread[2] = { 0, 0 };
+    uint64_t *boxTests = counters ? &counters[0] : &unread[0], *triTests = counters ? &counters[1] : &unread[1];
     const SmRay wr = make_ray(o, d);
     uint32_t node = 0;
     while (node < s->numTlasNodes) {
@@ -365,7 +384,7 @@ static int occluded_walk(const SmScene* s, F3 o, F3 d, float tmin, float tmax, u
                                     const uint64_t slot = (uint64_t)hd.tri_offset + first + j;
                                     if (first + j >= hd.num_tris || slot >= s->numTriOrder) break;
                                     ++*triTests;
-                                    if (mesh_tri_hit(s, mesh, s->triOrder[slot], &r, tmin, tmax) && commits(s, inst, flags)) return 1;
+                                    if (visit(ctx, s, inst, flags, mesh, s->triOrder[slot], &r)) return 1;
                                 }
                             }
                         }
@@ -377,6 +396,12 @@ static int occluded_walk(const SmScene* s, F3 o, F3 d, float tmin, float tmax, u
         node = next;
     }
     return 0;
+}
+
+/* the sun's any-hit visitor; ctx: the ray's SmInterval */
+static int occluded_walk(void* ctx, const SmScene* s, uint32_t inst, uint32_t flags, uint32_t mesh, uint32_t tri, const SmRay* r)
+{
+    return mesh_tri_hit(s, mesh, tri, 0, r, (const SmInterval*)ctx) && commits(s, inst, flags);
 }
 
 /* The candidates of every texel's ray, for the tests' preconditions: brute force's loop over every triangle of every instance with
@@ -400,18 +425,10 @@ uint32_t sm_candidates(const SmConsts* k, const SmScene* s, const float* depth, 
                 sm_object_from_world(s->instances[i].world, m);
                 const SmRay r = make_ray(mul_point(O, m, 1), mul_point(D, m, 0));
                 for (uint32_t t = 0; t < s->meshIndexCounts[mesh] / 3u; ++t) {
-                    const uint64_t base = (uint64_t)s->meshes[mesh].indexBase + 3ull * t;
-                    if (base + 3u > s->numIndices) continue;
-                    F3 v[3];
-                    int ok = 1;
-                    for (int j = 0; ok && j < 3; ++j) {
-                        const uint64_t vi = (uint64_t)s->meshes[mesh].vertexBase + s->indices[base + j];
-                        ok = vi < s->numVertices;
-                        if (ok) { v[j] = vertex_of(s, vi); ok = finite3(v[j]); }
-                    }
-                    float tc;
-                    if (!ok || !tri_candidate(v[0], v[1], v[2], &r, &tc)) continue;
-                    if (n < capacity) { texels[n] = (uint32_t)at; insts[n] = i; ts[n] = tc; }
+                    SmTri T;
+                    SmTriHit h;
+                    if (!fetch_tri(s, mesh, t, 1, &T) || !tri_candidate(T.v[0], T.v[1], T.v[2], &r, &h)) continue;
+                    if (n < capacity) { texels[n] = (uint32_t)at; insts[n] = i; ts[n] = h.t; }
                     ++n;
                 }
             }
@@ -423,17 +440,17 @@ uint32_t sm_candidates(const SmConsts* k, const SmScene* s, const float* depth, 
 void sm_trace(const SmConsts* k, const SmScene* s, const float* depth, const uint32_t* gbufferA, const uint32_t* noise, int mode, uint8_t* mask, uint16_t* lvd,
               uint64_t* counters)
 {
-    uint64_t boxTests = 0, triTests = 0;
+    SmInterval in = { k->rayStartOffset, 1e10f };
+    if (counters) counters[0] = counters[1] = 0;
     for (uint32_t py = 0; py < k->H; ++py)
         for (uint32_t px = 0; px < k->W; ++px) {
             const uint64_t i = (uint64_t)py * k->W + px;
             float o[3], d[3], w[3];
             if (!sm_texel_ray(k, px, py, depth[i], gbufferA + 4 * i, noise, o, d, w)) { lvd[i] = 0x7BFFu; continue; }
             const F3 O = { o[0], o[1], o[2] }, D = { d[0], d[1], d[2] };
-            const int occ = mode ? occluded_walk(s, O, D, k->rayStartOffset, 1e10f, &boxTests, &triTests) : occluded_brute(s, O, D, k->rayStartOffset, 1e10f);
+            const int occ = mode ? sm_walk(s, O, D, occluded_walk, &in, counters) : occluded_brute(s, O, D, &in);
             mask[i] = occ ? 0u : 255u;
             const F3 v = { w[0] - k->camera[0], w[1] - k->camera[1], w[2] - k->camera[2] };
             lvd[i] = sm_half_bits(sqrtf(dot3f(v, v)));
         }
-    if (counters) { counters[0] = boxTests; counters[1] = triTests; }
 }

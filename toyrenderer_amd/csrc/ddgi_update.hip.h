@@ -1,7 +1,7 @@
 // ddgi_update.hip.h -- what "giprobetrace_CS_ProbeTrace" (k_giprobetrace.hip), the two "ProbeBlendingCS_DDGIProbeBlendingCS"
 // passes (k_giprobeblend.hip) and the three placement passes (k_giprobeplacement.hip) share: the constant block, a probe's
 // coordinates and position, a ray's direction (of the 256 and of the 32 fixed ones), the octahedral decode, and the record-time
-// checks of the block, of the probe textures, of the scene's buffers and of the fixed-ray distances.  The RTXGI SDK is not part of this project; this is
+// checks of the block, of the probe textures and of the fixed-ray distances (the scene's buffers: rw::bindScene).  The RTXGI SDK is not part of this project; this is
 // the project's own statement of the published update (Majercik et al., JCGT 2019) and tests/ddgi_update_ref.c restates it word
 // for word.  The query's conventions (ddgi_irradiance.hip.h) hold here too: binary32, no contraction, fma only in dot3 and the
 // polynomials, / and sqrt correctly rounded.
@@ -136,37 +136,8 @@ inline int requireProbeTexture(const trhip::DispatchCtx& ctx, uint32_t type, uin
 
 // The scene and its acceleration structure in the probe trace's slots: t4 the TLAS nodes, t5 instances, t6 vertices, t7 materials
 // (asked for only where the pass shades its hits), t8 indices, t9 mesh data, t10 TLAS instances, t11 BLAS headers, t12 BLAS nodes,
-// t13 triangle order.
-inline int requireScene(const trhip::DispatchCtx& ctx, bool materials, rw::SceneArgs& s)
-{
-    const char* name = ctx.shaderName;
-    struct WantBuf { uint32_t slot, stride; const char* what; };
-    const WantBuf wantBuf[] = { { 4, sizeof(trhip_accel_node), "t4 = the TLAS nodes" }, { 5, sizeof(interop::BasePassInstanceConstants), "t5 = the instances" },
-                                { 6, sizeof(interop::RawVertexFormat), "t6 = the vertices" }, { 7, sizeof(interop::MaterialData), "t7 = the materials" }, { 8, 4, "t8 = the indices" },
-                                { 9, sizeof(interop::MeshData), "t9 = the mesh data" }, { 10, sizeof(trhip_tlas_instance), "t10 = the TLAS instances" },
-                                { 11, sizeof(trhip_blas_header), "t11 = the BLAS headers" }, { 12, sizeof(trhip_accel_node), "t12 = the BLAS nodes" },
-                                { 13, 4, "t13 = the triangle order" } };
-    trhip_buffer_t* buf[10] = {};
-    uint32_t count[10] = {};
-    for (int j = 0; j < 10; ++j) {
-        if (wantBuf[j].slot == 7 && !materials) continue;
-        buf[j] = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, wantBuf[j].slot);
-        TRHIP_REQUIRE(buf[j], "%s: needs StructuredBuffer_SRV %s", name, wantBuf[j].what);
-        const uint64_t n = buf[j]->byteSize / wantBuf[j].stride;
-        count[j] = n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
-    }
-    s.tlasNodes = (const trhip_accel_node*)buf[0]->ptr; s.numTlasNodes = count[0];
-    s.instances = (const interop::BasePassInstanceConstants*)buf[1]->ptr; s.numInstances = count[1] < count[6] ? count[1] : count[6];
-    s.vertices = (const uint8_t*)buf[2]->ptr; s.numVertices = count[2];
-    s.materials = materials ? (const uint8_t*)buf[3]->ptr : nullptr; s.numMaterials = count[3];
-    s.indices = (const uint32_t*)buf[4]->ptr; s.numIndices = count[4];
-    s.meshes = (const uint8_t*)buf[5]->ptr; s.numMeshes = count[5] < count[7] ? count[5] : count[7];
-    s.tlasInstances = (const trhip_tlas_instance*)buf[6]->ptr;
-    s.headers = (const trhip_blas_header*)buf[7]->ptr;
-    s.blasNodes = (const trhip_accel_node*)buf[8]->ptr; s.numBlasNodes = count[8];
-    s.triOrder = (const uint32_t*)buf[9]->ptr; s.numTriOrder = count[9];
-    return TRHIP_OK;
-}
+// t13 triangle order: rw::bindScene's slot table.
+constexpr uint32_t kSceneSlots[10] = { 4, 5, 6, 7, 8, 9, 10, 11, 12, 13 };
 
 // ---- what the three placement passes share (k_giprobeplacement.hip) --------------------------------------------------------------
 // u0 of all three: the fixed-ray distances, float[numProbes * 32]

@@ -38,14 +38,15 @@
 //                   the first ray with d <= plane makes the state 0; if none does, the state is 1.  The store is data.w = binary16 of
 //                   the state; xyz keeps its bits.
 //
-// KERNELS.  The fixed-ray trace is the probe trace without its shading: one closestHit per thread, no shadow ray, no query.
+// KERNELS.  The fixed-ray trace is the probe trace without its shading: one rw::closestHit per thread (ray_walk.hip.h states the
+// walk, the triangle test and the fetch once for every tracing pass), no shadow ray, no query.
 // Relocation and classification run one thread per probe.  The dispatch has the reference's ceil(numProbes / 32) groups; the launch
 // packs the probes into workgroups of one full wave, 64 probes each, whose first 32 threads compute the 32 directions once into
 // LDS (384 bytes).  A probe reads 128 bytes of distances and one 8-byte texel: the work is tiny next to the traces.  UNTUNED.
-// Code objects (-Rpass-analysis=kernel-resource-usage): fixedRayTraceKernel 57 VGPRs, occupancy 7 waves per SIMD; placementKernel
-// <relocation> 17 and <classification> 44 VGPRs, occupancy 8, LDS 384 bytes; no spills and no scratch in any.  MEASURED
-// (tools/ddgi_placement_cost.py, the generated city of 2251 instances, 13 468 probes, one MI355X; profiles/ddgi/): 11.2 ms, 9.7 us and
-// 14.6 us per update, next to 47.6 ms for the probe trace of the 8 966 probes still active.  The fixed-ray trace is above an eighth
+// Code objects (-Rpass-analysis=kernel-resource-usage): fixedRayTraceKernel 56 VGPRs, 4 spilled scalar registers, occupancy 7 waves
+// per SIMD; placementKernel <relocation> 17 and <classification> 44 VGPRs, occupancy 8, LDS 384 bytes, no spills; no scratch in any.
+// MEASURED (tools/ddgi_placement_cost.py, the generated city of 2251 instances, 13 468 probes, one MI355X; profiles/ray_walk/): 10.8
+// ms, 9.7 us and 14.6 us per update, next to 45.5 ms for the probe trace of the 8 966 probes still active.  The fixed-ray trace is above an eighth
 // of the probe trace: its 6 734 waves are a single resident set, so it lasts as long as its slowest walks (profiles/ddgi/README.md).
 #include "ddgi_update.hip.h"
 
@@ -186,7 +187,7 @@ int recordFixedRayTrace(trhip::DispatchCtx& ctx)
     trhip_texture_t* data;
     if (const int rc = ddgiu::requireProbeTexture(ctx, TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RGBA16_FLOAT, 1, "Texture_SRV t1 = the RGBA16_FLOAT array of probe data", D, data)) return rc;
     if (const int rc = ddgiu::requireFixedRayDistances(ctx, probes, a.distances)) return rc;
-    if (const int rc = ddgiu::requireScene(ctx, false, a.scene)) return rc;
+    if (const int rc = rw::bindScene(ctx, ddgiu::kSceneSlots, false, a.scene)) return rc;
     a.data = (const uint2*)data->ptr; a.dataW = data->width; a.dataPitch = (uint32_t)(data->slicePitch / data->texelBytes);
     sp::launch(ctx, fixedRayTraceKernel, "fixedRayTraceKernel", dim3((probes * kDDGIFixedRays + kWave - 1) / kWave), dim3(kWave), a);
     return TRHIP_OK;

@@ -31,11 +31,13 @@
 //             record (saturate(rgb), t).
 //
 // KERNEL.  One thread per (ray, probe); a wave is 64 consecutive rays of one probe, so its lanes start at one point and fan out.
-// No stack, no LDS, no per-lane array (ray_walk.hip.h).  UNTUNED, as the sun's trace is: correctness came first.  closestHit does
-// not prune against the best hit, front-face rays walk the structure twice (the shadow ray) and then run the query's eight probe
-// lookups.  Code object (-Rpass-analysis=kernel-resource-usage): 79 VGPRs, occupancy 6 waves per SIMD, 33 spilled scalar registers, no
-// scratch, no LDS.  MEASURED (tools/ddgi_update_cost.py, the generated city of 2251 instances, 13 468 probes = 3.45 M rays, one
-// MI355X; profiles/ddgi/): 64.4 ms per update, next to 0.10 and 0.49 ms for the two blends.
+// The walk, the triangle test and the triangle fetch are ray_walk.hip.h's (rw::walk, whose visitor closestHit is; the hit's
+// attributes are read through rw::fetchTri): no stack, no LDS, no per-lane array.  UNTUNED, as the sun's trace is: correctness came
+// first.  closestHit does not prune against the best hit, front-face rays walk the structure twice (the shadow ray: a closest hit
+// too, not an any-hit ray) and then run the query's eight probe lookups.  Code object (-Rpass-analysis=kernel-resource-usage): 79
+// VGPRs, occupancy 6 waves per SIMD, 41 spilled scalar registers, no scratch, no LDS.  MEASURED (tools/ddgi_update_cost.py, the
+// generated city of 2251 instances, 13 468 probes = 3.45 M rays, one MI355X; profiles/ray_walk/README.md): 61.8 ms per update, next
+// to 0.10 and 0.49 ms for the two blends.
 #include "ddgi_irradiance.hip.h"
 #include "ddgi_update.hip.h"
 #include "direct_light.hip.h"
@@ -81,17 +83,15 @@ __global__ __launch_bounds__(kWave) void probeTraceKernel(ProbeTraceArgs a)
     if (hit.inst == 0xFFFFFFFFu) { *out = make_float4(1.0f, 1.0f, 1.0f, 1e27f); return; }
     if (!hit.front) { *out = make_float4(0.0f, 0.0f, 0.0f, -0.2f * hit.t); return; }
 
-    // the hit's attributes: closestHit followed these indices already, so they are inside their buffers
+    // the hit's attributes: closestHit's visitor passed this (mesh, triangle) through the same rw::fetchTri on the same buffers, so
+    // the fetch cannot answer false here and the return below is never taken (tests/ddgi_update_ref.c says the same of its refetch)
     const BasePassInstanceConstants& inst = a.scene.instances[hit.inst];
-    const MeshData* md = reinterpret_cast<const MeshData*>(a.scene.meshes + (uint64_t)inst.m_MeshDataIdx * sizeof(MeshData));
-    const uint64_t base = (uint64_t)md->m_GlobalIndexBufferIdx + 3ull * hit.tri;
-    F3 v[3], n[3];
+    rw::Tri T;
+    if (!rw::fetchTri(a.scene, reinterpret_cast<const MeshData*>(a.scene.meshes + (uint64_t)inst.m_MeshDataIdx * sizeof(MeshData)), hit.tri, T)) return;
+    const F3* v = T.v;
+    F3 n[3];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const uint64_t vi = (uint64_t)md->m_GlobalVertexBufferIdx + a.scene.indices[base + j];
-        v[j] = rw::vertexOf(a.scene, vi);
-        n[j] = unpackNormal(*reinterpret_cast<const uint32_t*>(a.scene.vertices + vi * sizeof(RawVertexFormat) + offsetof(RawVertexFormat, m_PackedNormal)));
-    }
+    for (int j = 0; j < 3; ++j) n[j] = unpackNormal(*reinterpret_cast<const uint32_t*>(a.scene.vertices + T.i[j] * sizeof(RawVertexFormat) + offsetof(RawVertexFormat, m_PackedNormal)));
     const float b1 = hit.b1, b2 = hit.b2, b0 = (1.0f - b1) - b2;
     const F3 p = { bary(v[0].x, v[1].x, v[2].x, b0, b1, b2), bary(v[0].y, v[1].y, v[2].y, b0, b1, b2), bary(v[0].z, v[1].z, v[2].z, b0, b1, b2) };
     gbuf::GBufferParams s;
@@ -138,7 +138,7 @@ int recordProbeTrace(trhip::DispatchCtx& ctx)
     TRHIP_REQUIRE(rays, "%s: needs StructuredBuffer_UAV u0 = the ray records, float4[numProbes * 256]", name);
     TRHIP_REQUIRE(rays->byteSize == (uint64_t)probes * kDDGIRaysPerProbe * sizeof(float4), "%s: the ray records at u0 hold %llu bytes; %u probes of 256 float4 records are %llu", name,
                   (unsigned long long)rays->byteSize, probes, (unsigned long long)probes * kDDGIRaysPerProbe * sizeof(float4));
-    if (const int rc = ddgiu::requireScene(ctx, true, a.scene)) return rc;
+    if (const int rc = rw::bindScene(ctx, ddgiu::kSceneSlots, true, a.scene)) return rc;
     ddgi::Textures& p = a.probes;
     p.desc = (const DDGIVolumeDesc*)descBuffer->ptr;
     p.data = (const uint2*)data->ptr; p.irradiance = (const uint32_t*)irr->ptr; p.distance = (const uint32_t*)dist->ptr;

@@ -11,16 +11,17 @@
 // `alpha` below).  Samplers are accepted and ignored.  Of the refit: push constants RefitTLASConstants (12 bytes), t0 instances, t1 BLAS headers, t2 BLAS nodes,
 // t3 level offsets, t4 level nodes, u0 the TLAS nodes, u1 the TLAS instances.
 //
-// CONVENTION (tests/shadowmask_ref.c is the definition; the functions below repeat its functions word for word).  IEEE binary32,
-// no contraction, fma only where written, / and sqrt correctly rounded:
+// CONVENTION (tests/shadowmask_ref.c is the definition; the walk, the two tests and the triangle fetch are stated once on the device,
+// in ray_walk.hip.h, and occluded() below is a visitor of rw::walk).  IEEE binary32, no contraction, fma only where written, / and
+// sqrt correctly rounded:
 //   worldPosition, dot3 as screen_pass.hip.h states them; UnpackGBuffer's normal, normalize as k_deferredlighting.hip (gbuffer_unpack.hip.h);
 //   noise = (float)byte / 255.0f of the blue noise texel's R and G at (px % 128, py % 128), + m_NoisePhase, fmod(x, 1) = x - trunc(x);
 //   MapToCone / CreateTangentVectors as the HLSL with softmath::cosSoft / sinSoft, RN(pi / 4) and RN(pi / 2), cross as cm::cross3,
 //             (n + u.x * t0) + u.y * t1; the direction is its normalize; origin = worldPosition + normal * m_RayStartOffset;
 //             TMin = m_RayStartOffset, TMax = 1e10f;
-//   the ray is moved to object space once per instance (mulPoint with the refit's object-from-world rows; the direction without the
-//             translation and not normalised); objectFromWorld: cofactors / determinant in the order written there;
-//   triHit:   the watertight test of Woop, Benthin and Wald in binary32 without the double fallback; two-sided; hit iff
+//   the walk: rw::walk (ray_walk.hip.h states its rules: skip links, index checks, flags, the move to object space once per instance);
+//             objectFromWorld: cofactors / determinant in the order written there;
+//   triTest:  the watertight test of Woop, Benthin and Wald in binary32 without the double fallback; two-sided; hit iff
 //             TMin < t < TMax.  A candidate on a ForceNonOpaque instance counts iff m_ConstAlbedo.w >= m_AlphaCutoff of the
 //             candidate's instance's material (the reference reads Committed* there: shadowmask.hlsl:113-116);
 //   alpha:    without a table at t19 that is the whole rule and the kernel of before is launched unchanged.  With one, the TEXTURED
@@ -32,7 +33,7 @@
 //             the slab's interval with both ends moved outward by 2^-18 of themselves; node boxes are padded by the builder (2^-16
 //             of the mesh's largest |coordinate|) and by the refit (2^-12 of the leaf's largest |coordinate|).  Any-hit over all
 //             triangles is order-independent, so the mask equals brute force for any tree as long as boxHit never rejects what
-//             triHit accepts: tests/test_shadowmask_ref.py walks the same arrays on the CPU and allows no differing texel;
+//             triTest accepts: tests/test_shadowmask_ref.py walks the same arrays on the CPU and allows no differing texel;
 //   output:   depth == 0.0f: u1 = 0x7BFF, u0 untouched; else u0 = occluded ? 0 : 255, u1 = binary16 RNE of
 //             length(worldPosition - m_CameraPosition) (a NaN is stored as 0x7E00).
 //
@@ -42,10 +43,10 @@
 // forward ends the walk (a corrupt buffer cannot spin).  Runtime-chosen vector components go through sel() (selects), not through
 // an indexed array.  Every index read on the device is checked against its buffer before it is followed.  A wave walks until its
 // last lane is done, and lanes that disagree on a box serialise both sides.  MEASURED (tools/shadowmask_cost.py, the generated city
-// of 2251 instances at 3840x2160, one MI355X; profiles/shadowmask/): the trace 1.92 ms with hard and 3.86 ms with soft shadows next to
-// a lighting pass of 0.10 ms, the refit 35 us.  Untuned: correctness came first.  The TEXTURED instantiation (tools/alpha_test_cost.py,
-// the same city with 225 alpha-masked, textured instances; profiles/alpha_test/): 2.48 ms beside 1.94 ms hard, 5.13 beside 3.90 ms soft;
-// 78 VGPRs instead of 57, no scratch.
+// of 2251 instances at 3840x2160, one MI355X; profiles/ray_walk/README.md): the trace 1.77 ms with hard and 3.51 ms with soft shadows
+// next to a lighting pass of 0.10 ms, the refit 35 us.  Untuned: correctness came first.  The TEXTURED instantiation
+// (tools/alpha_test_cost.py, the same city with 225 alpha-masked, textured instances): 2.38 ms beside 1.80 ms hard, 4.81 beside 3.55 ms
+// soft; 69 VGPRs instead of 58, no scratch.
 #include "cull_math.hip.h"
 #include "gbuffer_unpack.hip.h"
 #include "material_textures.hip.h"
@@ -60,7 +61,7 @@ namespace
 
 using namespace interop;
 using cm::F3;
-using namespace rw;                            // Ray, makeRay, boxHit, triHit, sel, M34, mulPoint, vertexOf, SceneArgs: ray_walk.hip.h
+using namespace rw;                            // Ray, walk, fetchTri, triTest, bindScene, SceneArgs: ray_walk.hip.h
 
 constexpr uint32_t kTileSide = 8;               // [numthreads(8, 8, 1)]
 constexpr uint32_t kRefitBlock = 64;
@@ -203,7 +204,7 @@ int recordRefit(trhip::DispatchCtx& ctx)
     return TRHIP_OK;
 }
 
-// ---- the two tests (makeRay, boxHit, triHit) are ray_walk.hip.h's --------------------------------------------------------------
+// ---- the ray of one pixel -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float fmod1(float x) { return x - __builtin_truncf(x); }
 
 __device__ __forceinline__ F3 mapToCone(float sx, float sy, F3 n, float radius)                     // shadowmask.hlsl:24-63
@@ -252,64 +253,24 @@ __device__ __forceinline__ bool commits(const Args& a, uint32_t inst, uint32_t f
 template <bool TEXTURED>
 __device__ __forceinline__ bool meshTriHit(const TraceArgs& a, const MeshData* md, uint32_t tri, const Ray& r, float tmin, float tmax, Candidate& c)
 {
-    const uint64_t base = (uint64_t)md->m_GlobalIndexBufferIdx + 3ull * tri;
-    if (base + 3u > a.numIndices) return false;
-    F3 v[3];
+    Tri T;
+    TriHit h;
+    if (!fetchTri(a, md, tri, T) || !triTest(T.v[0], T.v[1], T.v[2], r, tmin, tmax, h)) return false;
+    if constexpr (TEXTURED) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint64_t vi = (uint64_t)md->m_GlobalVertexBufferIdx + a.indices[base + k];
-        if (vi >= a.numVertices) return false;
-        v[k] = vertexOf(a, vi);
-        if constexpr (TEXTURED) c.tc[k] = *reinterpret_cast<const uint32_t*>(a.vertices + vi * sizeof(RawVertexFormat) + offsetof(RawVertexFormat, m_TexCoord));
+        for (int k = 0; k < 3; ++k) c.tc[k] = *reinterpret_cast<const uint32_t*>(a.vertices + T.i[k] * sizeof(RawVertexFormat) + offsetof(RawVertexFormat, m_TexCoord));
+        c.b1 = h.b1; c.b2 = h.b2;
     }
-    if constexpr (TEXTURED) return triHit(v[0], v[1], v[2], r, tmin, tmax, &c.b1, &c.b2);
-    else return triHit(v[0], v[1], v[2], r, tmin, tmax);
+    return true;
 }
 
+// The any-hit visitor of rw::walk (tests/shadowmask_ref.c: occluded_walk): the first candidate that is hit and counts ends the walk.
 template <bool TEXTURED, typename Args>
-__device__ bool occluded(const Args& a, F3 o, F3 d, float tmin, float tmax)                         // tests/shadowmask_ref.c: occluded_walk
+__device__ bool occluded(const Args& a, F3 o, F3 d, float tmin, float tmax)
 {
-    const Ray wr = makeRay(o, d);
-    uint32_t node = 0;
-    while (node < a.numTlasNodes) {
-        const trhip_accel_node n = a.tlasNodes[node];
-        uint32_t next = n.skip > node ? n.skip : a.numTlasNodes;
-        if (boxHit(n, wr)) {
-            if (n.leaf == kAccelInner) next = node + 1;
-            else if (n.leaf < a.numInstances) {
-                const uint32_t inst = n.leaf, flags = a.tlasInstances[inst].flags, mesh = a.instances[inst].m_MeshDataIdx;
-                if (flags && mesh < a.numMeshes) {
-                    const trhip_blas_header hd = a.headers[mesh];
-                    const MeshData* md = reinterpret_cast<const MeshData*>(a.meshes + (uint64_t)mesh * sizeof(MeshData));
-                    M34 M;
-#pragma unroll
-                    for (int j = 0; j < 12; ++j) M.m[j] = a.tlasInstances[inst].object_from_world[j];
-                    const Ray r = makeRay(mulPoint(o, M, true), mulPoint(d, M, false));
-                    const uint32_t count = (uint64_t)hd.node_offset + hd.num_nodes <= a.numBlasNodes ? hd.num_nodes : 0u;
-                    uint32_t b = 0;
-                    while (b < count) {
-                        const trhip_accel_node bn = a.blasNodes[hd.node_offset + b];
-                        uint32_t bnext = bn.skip > b ? bn.skip : count;
-                        if (boxHit(bn, r)) {
-                            if (bn.leaf == kAccelInner) bnext = b + 1;
-                            else {
-                                const uint32_t first = bn.leaf & 0x3FFFFFFFu, cnt = (bn.leaf >> 30) + 1u;
-                                for (uint32_t j = 0; j < cnt; ++j) {
-                                    const uint64_t slot = (uint64_t)hd.tri_offset + first + j;
-                                    if (first + j >= hd.num_tris || slot >= a.numTriOrder) break;
-                                    Candidate c;
-                                    if (meshTriHit<TEXTURED>(a, md, a.triOrder[slot], r, tmin, tmax, c) && commits<TEXTURED>(a, inst, flags, c)) return true;
-                                }
-                            }
-                        }
-                        b = bnext;
-                    }
-                }
-            }
-        }
-        node = next;
-    }
-    return false;
+    return walk(a, o, d, [&](uint32_t inst, uint32_t flags, const MeshData* md, uint32_t tri, const Ray& r) {
+        Candidate c;
+        return meshTriHit<TEXTURED>(a, md, tri, r, tmin, tmax, c) && commits<TEXTURED>(a, inst, flags, c); });
 }
 
 // TEXTURED: a texture table is bound at t19 and alpha-mask candidates read their albedo texture's alpha (commits).
@@ -363,34 +324,11 @@ int recordShadowMask(trhip::DispatchCtx& ctx)
     trhip_texture_t *tex[4], *noise[1];
     if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "m_OutputResolution")) return rc;
     if (const int rc = sp::bindTextures(ctx, wantNoise, noise, kBlueNoiseSize, kBlueNoiseSize, "the blue noise")) return rc;
-    struct WantBuf { uint32_t slot, stride; const char* what; };
-    const WantBuf wantBuf[] = { { 1, sizeof(trhip_accel_node), "t1 = the TLAS nodes" }, { 3, sizeof(BasePassInstanceConstants), "t3 = the instances" },
-                                { 4, sizeof(RawVertexFormat), "t4 = the vertices" }, { 5, sizeof(MaterialData), "t5 = the materials" }, { 6, 4, "t6 = the indices" },
-                                { 7, sizeof(MeshData), "t7 = the mesh data" }, { 9, sizeof(trhip_tlas_instance), "t9 = the TLAS instances" },
-                                { 10, sizeof(trhip_blas_header), "t10 = the BLAS headers" }, { 11, sizeof(trhip_accel_node), "t11 = the BLAS nodes" },
-                                { 12, 4, "t12 = the triangle order" } };
-    trhip_buffer_t* buf[10] = {};
-    uint32_t count[10] = {};
-    for (int j = 0; j < 10; ++j) {
-        buf[j] = ctx.buffer(TRHIP_BIND_STRUCTURED_SRV, wantBuf[j].slot);
-        TRHIP_REQUIRE(buf[j], "%s: needs StructuredBuffer_SRV %s", name, wantBuf[j].what);
-        const uint64_t c = buf[j]->byteSize / wantBuf[j].stride;
-        count[j] = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
-    }
     TexturedTraceArgs a = sp::zeroed<TexturedTraceArgs>();                                          // TraceArgs + the table; sliced when none is bound
+    if (const int rc = bindScene(ctx, { 1, 3, 4, 5, 6, 7, 9, 10, 11, 12 }, true, a)) return rc;
     a.k = *k;
     a.depth = (const float*)tex[0]->ptr; a.gbufferA = (const uint4*)tex[1]->ptr; a.mask = (uint8_t*)tex[2]->ptr; a.lvd = (uint16_t*)tex[3]->ptr;
     a.noise = (const uint32_t*)noise[0]->ptr;
-    a.tlasNodes = (const trhip_accel_node*)buf[0]->ptr; a.numTlasNodes = count[0];
-    a.instances = (const BasePassInstanceConstants*)buf[1]->ptr; a.numInstances = count[1] < count[6] ? count[1] : count[6];
-    a.vertices = (const uint8_t*)buf[2]->ptr; a.numVertices = count[2];
-    a.materials = (const uint8_t*)buf[3]->ptr; a.numMaterials = count[3];
-    a.indices = (const uint32_t*)buf[4]->ptr; a.numIndices = count[4];
-    a.meshes = (const uint8_t*)buf[5]->ptr; a.numMeshes = count[5] < count[7] ? count[5] : count[7];
-    a.tlasInstances = (const trhip_tlas_instance*)buf[6]->ptr;
-    a.headers = (const trhip_blas_header*)buf[7]->ptr;
-    a.blasNodes = (const trhip_accel_node*)buf[8]->ptr; a.numBlasNodes = count[8];
-    a.triOrder = (const uint32_t*)buf[9]->ptr; a.numTriOrder = count[9];
     if (trhip_texture_table_t* table = ctx.textureTable(19)) {                                      // t19: the TEXTURED instantiation
         for (size_t d = 0; d < table->slots.size(); ++d)
             TRHIP_REQUIRE(!table->slots[d] || !table->slots[d]->isUAV, "%s: the texture table at t19 holds '%s' at index %zu, created with the UAV or render-target bit: a sampled texture is read only",
