@@ -3,16 +3,15 @@
  * rays ("shadowmask_CS_ShadowMask" with a texture table at t19, csrc/k_shadowmask.hip).  Compiled by the tests themselves with
  * gcc -O2 -ffp-contract=off (tests/alpha_test_ref.py): only the fmaf calls written here fuse.
  *
- * It includes the two references it extends, unedited: tests/material_textures_ref.c (the sampler, the vertex arithmetic, the
- * edge function, MaterialData) and tests/shadowmask_ref.c (the ray of a texel, the ray set-up, SmScene), the latter with the three
- * helper names both files define renamed.
+ * It includes the two references it extends, unedited: tests/material_textures_ref.c (the sampler, MaterialData, and through it the
+ * mesh stage of tests/ref_mesh_stage.h) and tests/shadowmask_ref.c (the ray of a texel, the ray set-up, SmScene).
  *
  * ALPHA.  at_sample_alpha = component 3 of mt_sample: the footprint, tap count, lod, tap positions, trilinear and bilinear
  *   arithmetic, addressing and summation order of the colour channels, applied to byte 3 of the texel, (float)byte / 255.0f in
  *   both formats (alpha never goes through the sRGB table).  at_alpha_level0 = one bilinear fetch of mip 0.
  *
- * RASTER (at_raster).  vr_raster of tests/visibility_ref.c restated, with one step added.  A covered sample of a triangle (all
- *   three edge values e_i >= 0, den > 0, d > 0) passes, before it is merged into either target:
+ * RASTER (at_raster).  The raster of tests/ref_mesh_stage.h (vr_raster) with its keep hook supplied: one step added.  A covered
+ *   sample of a triangle (all three edge values e_i >= 0, den > 0, d > 0) passes, before it is merged into either target:
  *   1. q_i = e_i / w_i, s = (q0 + q1) + q2, from the sample's own edge values and the vertices' clip w;
  *   2. uv = fmaf(q2, a2, fmaf(q1, a1, q0 * a0)) / s of m_TexCoord (half -> float, exact);
  *   3. ddx(uv), ddy(uv) = the same interpolation of the same triangle with the edge functions re-evaluated at (cx + 1, cy) and
@@ -34,14 +33,7 @@
  *   rays; this build reads mip 0.
  */
 #include "material_textures_ref.c"
-
-#define float_of sm_float_of_
-#define bits_of sm_bits_of_
-#define normalize3 sm_normalize3_
 #include "shadowmask_ref.c"
-#undef float_of
-#undef bits_of
-#undef normalize3
 
 float at_sample_alpha(const MtTexture* t, int wrap, const float uv[2], const float dx[2], const float dy[2])
 {
@@ -66,111 +58,54 @@ static const MtTexture* table_entry(const MtTexture* textures, int64_t numTextur
     return &textures[d];
 }
 
-/* ---- the raster of one pass slot ---------------------------------------------------------------------------------------------
- * alphaTest = 0: vr_raster.  order: NULL, or numVisible positions of `list` to draw (the payload carries the position, so disjoint
- * slices of a list drawn into images of their own and max-merged give the image of the whole list).  counts (optional, uint64[4]): the covered samples (d > 0) of the slot's triangles that were kept and
- * discarded, {kept, discarded} of the triangles whose bounding box has at most 1024 pixels (drawn in place by the kernel's main
- * launch) and {kept, discarded} of the larger ones (queue, bin and tile launch). */
+/* ---- the raster of one pass slot --------------------------------------------------------------------------------------------- */
+typedef struct { MtMaterialData mat; const MtTexture* tex; uint64_t* counts; } AtKeep;
+
+/* steps 1 to 5 for one covered sample: the raster's keep hook (tests/ref_mesh_stage.h) */
+static int at_keep(void* ctx, const MsTriangle* T, float cx, float cy, uint64_t boxPixels)
+{
+    const AtKeep* a = (const AtKeep*)ctx;
+    float alpha = a->mat.m_ConstAlbedo[3];
+    if (a->tex) {
+        float uv[3][2], tc[3][2], q[3];
+        for (int j = 0; j < 3; ++j) { uv[j][0] = half_to_float(T->vtx[j]->m_TexCoord[0]); uv[j][1] = half_to_float(T->vtx[j]->m_TexCoord[1]); }
+        for (int p = 0; p < 3; ++p) {                                                /* the centre, (cx + 1, cy), (cx, cy + 1) */
+            const float s = ms_weights(T, p == 1 ? cx + 1.0f : cx, p == 2 ? cy + 1.0f : cy, q);
+            for (int j = 0; j < 2; ++j) tc[p][j] = ms_interp(q, s, uv[0][j], uv[1][j], uv[2][j]);
+        }
+        const float dx[2] = { tc[1][0] - tc[0][0], tc[1][1] - tc[0][1] }, dy[2] = { tc[2][0] - tc[0][0], tc[2][1] - tc[0][1] };
+        alpha = alpha * at_sample_alpha(a->tex, a->mat.m_Textures[0].m_IsWrapSampler != 0, tc[0], dx, dy);
+    }
+    const int discard = alpha < a->mat.m_AlphaCutoff;
+    if (a->counts) ++a->counts[2 * (boxPixels > 1024u) + discard];
+    return !discard;
+}
+
+/* alphaTest = 0: vr_raster.  order: NULL, or numVisible positions of `list` to draw (the payload carries the position, so disjoint
+ * slices of a list drawn into images of their own and max-merged give the image of the whole list).  counts (optional, uint64[4]):
+ * the covered samples (d > 0) of the slot's triangles that were kept and discarded, {kept, discarded} of the triangles whose
+ * bounding box has at most 1024 pixels (drawn in place by the kernel's main launch) and {kept, discarded} of the larger ones
+ * (queue, bin and tile launch). */
 void at_raster(const OrcBasePassConstants* k, const OrcBasePassInstanceConstants* instances, const OrcMeshData* meshData,
                const OrcMeshletData* meshlets, const OrcRawVertexFormat* vertices, const uint32_t* vertexIds, const uint32_t* triangles,
                const OrcMeshletAmplificationData* records, const uint32_t* list, uint32_t numVisible, const uint32_t* order, uint32_t slot,
                const unsigned char* materials, uint32_t numMaterials, const MtTexture* textures, int64_t numTextures, int alphaTest,
                float* depth, uint64_t* vis, uint64_t* counts)
 {
-    const uint32_t W = k->m_OutputResolution[0], H = k->m_OutputResolution[1];
-    const float halfW = 0.5f * (float)W, halfH = 0.5f * (float)H;
+    const MsBuffers b = { instances, meshData, meshlets, vertices, vertexIds, triangles };
     for (uint32_t n = 0; n < numVisible; ++n) {
         const uint32_t v = order ? order[n] : n;
-        const OrcMeshletAmplificationData* rec = &records[list[v] >> 5];
-        const OrcBasePassInstanceConstants* inst = &instances[rec->m_InstanceConstIdx];
-        const uint32_t lodIdx = rec->m_MeshLOD < ORC_MAX_LODS ? rec->m_MeshLOD : ORC_MAX_LODS - 1;
-        const OrcMeshLODData* lod = &meshData[inst->m_MeshDataIdx].m_MeshLODDatas[lodIdx];
-        const OrcMeshletData* ml = &meshlets[lod->m_MeshletDataBufferIdx + rec->m_MeshletGroupOffset + (list[v] & 31u)];
-        MtMaterialData mat;
-        const MtTexture* tex = 0;
+        AtKeep a = { .tex = 0, .counts = counts };
         if (alphaTest) {
+            const OrcBasePassInstanceConstants* inst = &instances[records[list[v] >> 5].m_InstanceConstIdx];
             if (inst->m_MaterialDataIdx >= numMaterials) continue;
-            memcpy(&mat, materials + (uint64_t)inst->m_MaterialDataIdx * sizeof mat, sizeof mat);
-            if (mat.m_MaterialFlags & 1u) {
-                tex = table_entry(textures, numTextures, mat.m_Textures[0].m_DescriptorIndex);
-                if (!tex) continue;
+            memcpy(&a.mat, materials + (uint64_t)inst->m_MaterialDataIdx * sizeof a.mat, sizeof a.mat);
+            if (a.mat.m_MaterialFlags & 1u) {
+                a.tex = table_entry(textures, numTextures, a.mat.m_Textures[0].m_DescriptorIndex);
+                if (!a.tex) continue;
             }
         }
-        uint32_t nv = ml->m_VertexAndTriangleCount & 0xFFu;
-        const uint32_t nt = (ml->m_VertexAndTriangleCount >> 8) & 0xFFu;
-        if (nv > 64u) nv = 64u;
-        float sx[64], sy[64], sd[64], sw[64], uv[64][2];
-        int ok[64];
-        for (uint32_t i = 0; i < nv; ++i) {
-            const OrcRawVertexFormat* vtx = &vertices[vertexIds[ml->m_MeshletVertexIDsBufferIdx + i]];
-            float wp[3], c[4];
-            mul_point3(vtx->m_Position, &inst->m_WorldMatrix, wp);
-            mul_point_4(wp, &k->m_WorldToClip, c);
-            sw[i] = c[3];
-            sx[i] = fmaf(c[0] / c[3], halfW, halfW);
-            sy[i] = fmaf(-(c[1] / c[3]), halfH, halfH);
-            sd[i] = c[2] / c[3];
-            ok[i] = c[3] > k->m_NearPlane;
-            uv[i][0] = mt_half_to_float(vtx->m_TexCoord[0]);
-            uv[i][1] = mt_half_to_float(vtx->m_TexCoord[1]);
-        }
-        for (uint32_t t = 0; t < nt; ++t) {
-            const uint32_t packed = triangles[ml->m_MeshletIndexIDsBufferIdx + t];
-            const uint32_t a = packed & 0xFFu, b = (packed >> 8) & 0xFFu, c = (packed >> 16) & 0xFFu;
-            if (a >= nv || b >= nv || c >= nv || !(ok[a] && ok[b] && ok[c])) continue;
-            const float area = edge(sx[a], sy[a], sx[b], sy[b], sx[c], sy[c]);
-            if (!(area != 0.0f)) continue;
-            const float sgn = area < 0.0f ? -1.0f : 1.0f;
-            const float minx = fminf(fminf(sx[a], sx[b]), sx[c]), maxx = fmaxf(fmaxf(sx[a], sx[b]), sx[c]);
-            const float miny = fminf(fminf(sy[a], sy[b]), sy[c]), maxy = fmaxf(fmaxf(sy[a], sy[b]), sy[c]);
-            if (!(maxx >= 0.0f && maxy >= 0.0f && minx <= (float)W && miny <= (float)H)) continue;
-            const int x0 = (int)fmaxf(floorf(minx), 0.0f), x1 = (int)fminf(ceilf(maxx), (float)(W - 1));
-            const int y0 = (int)fmaxf(floorf(miny), 0.0f), y1 = (int)fminf(ceilf(maxy), (float)(H - 1));
-            if (x1 < x0 || y1 < y0) continue;
-            const int big = (uint64_t)(x1 - x0 + 1) * (uint64_t)(y1 - y0 + 1) > 1024u;
-            const uint64_t payload = (uint64_t)slot << 30 | (uint64_t)v << 7 | t;
-            for (int py = y0; py <= y1; ++py)
-                for (int px = x0; px <= x1; ++px) {
-                    const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
-                    float q[3][3], s[3], tc[3][2];
-                    int covered = 1;
-                    for (int p = 0; p < (alphaTest && tex ? 3 : 1) && covered; ++p) {     /* the centre, (cx + 1, cy), (cx, cy + 1) */
-                        const float x = p == 1 ? cx + 1.0f : cx, y = p == 2 ? cy + 1.0f : cy;
-                        const float e0 = sgn * edge(sx[b], sy[b], sx[c], sy[c], x, y);
-                        const float e1 = sgn * edge(sx[c], sy[c], sx[a], sy[a], x, y);
-                        const float e2 = sgn * edge(sx[a], sy[a], sx[b], sy[b], x, y);
-                        if (p == 0) {
-                            covered = e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f && (e0 + e1) + e2 > 0.0f;
-                            if (!covered) break;
-                            q[0][0] = e0; q[0][1] = e1; q[0][2] = e2;                     /* kept for the depth below */
-                        }
-                        const float q0 = e0 / sw[a], q1 = e1 / sw[b], q2 = e2 / sw[c];
-                        s[p] = (q0 + q1) + q2;
-                        for (int j = 0; j < 2; ++j) tc[p][j] = fmaf(q2, uv[c][j], fmaf(q1, uv[b][j], q0 * uv[a][j])) / s[p];
-                    }
-                    if (!covered) continue;
-                    const float e0 = q[0][0], e1 = q[0][1], e2 = q[0][2];
-                    const float den = (e0 + e1) + e2;
-                    const float d = fmaf(e2, sd[c], fmaf(e1, sd[b], e0 * sd[a])) / den;
-                    if (!(d > 0.0f)) continue;
-                    if (alphaTest) {
-                        float alpha = mat.m_ConstAlbedo[3];
-                        if (tex) {
-                            const float dx[2] = { tc[1][0] - tc[0][0], tc[1][1] - tc[0][1] }, dy[2] = { tc[2][0] - tc[0][0], tc[2][1] - tc[0][1] };
-                            alpha = alpha * at_sample_alpha(tex, mat.m_Textures[0].m_IsWrapSampler != 0, tc[0], dx, dy);
-                        }
-                        const int discard = alpha < mat.m_AlphaCutoff;
-                        if (counts) ++counts[2 * big + discard];
-                        if (discard) continue;
-                    }
-                    const uint64_t i = (uint64_t)py * W + px;
-                    if (d > depth[i]) depth[i] = d;
-                    if (t < 128u) {
-                        const uint64_t texel = (uint64_t)bits_of(d) << 32 | payload;
-                        if (texel > vis[i]) vis[i] = texel;
-                    }
-                }
-        }
+        ms_raster_entry(k, &b, records, list, v, slot, alphaTest ? at_keep : NULL, &a, depth, vis);
     }
 }
 

@@ -21,41 +21,11 @@
  *              i + 1 of size (W >> (i + 1), H >> (i + 1)) with m_InvSourceResolution = 1.0f / (W >> i, H >> i)), then mips - 1
  *              upsamples from mip mips - 1 - i into the next finer one.  Mip 0 is written by the last upsample only.
  */
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "ref_formats.h"
 
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-
-/* ---- the format --------------------------------------------------------------------------------------------------------- */
-float bl_unpack_ufloat(uint32_t c, uint32_t mbits)
-{
-    const uint32_t e = c >> mbits, m = c & ((1u << mbits) - 1u);
-    if (e == 0u) return (float)m * (1.0f / (float)(1u << (14u + mbits)));
-    return float_of((e == 31u ? 0x7F800000u : (e + 112u) << 23) | m << (23u - mbits));
-}
-
-uint32_t bl_pack_ufloat(float v, uint32_t mbits)
-{
-    const uint32_t shift = 23u - mbits, inf = 31u << mbits, maxFinite = inf - 1u, u = bits_of(v);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return inf | ((1u << mbits) - 1u);
-    if (u >> 31) return 0u;
-    if (u == 0x7F800000u) return inf;
-    if (u >= 0x38800000u) {
-        const uint32_t r = u - (112u << 23);
-        const uint32_t q = (r + ((1u << (shift - 1)) - 1u) + ((r >> shift) & 1u)) >> shift;
-        return q < maxFinite ? q : maxFinite;
-    }
-    return (uint32_t)rintf(v * (float)(1u << (14u + mbits)));
-}
-
-static void unpack(uint32_t w, float rgb[3])
-{
-    rgb[0] = bl_unpack_ufloat(w & 0x7FFu, 6); rgb[1] = bl_unpack_ufloat((w >> 11) & 0x7FFu, 6); rgb[2] = bl_unpack_ufloat(w >> 22, 5);
-}
-
-static uint32_t pack(const float rgb[3]) { return bl_pack_ufloat(rgb[0], 6) | bl_pack_ufloat(rgb[1], 6) << 11 | bl_pack_ufloat(rgb[2], 5) << 22; }
+/* ---- the format of tests/ref_formats.h under this library's names --------------------------------------------------------- */
+float bl_unpack_ufloat(uint32_t c, uint32_t mbits) { return unpack_ufloat(c, mbits); }
+uint32_t bl_pack_ufloat(float v, uint32_t mbits) { return pack_ufloat(v, mbits); }
 
 /* ---- the sampler -------------------------------------------------------------------------------------------------------- */
 typedef struct { uint32_t i0, i1; float f; } Axis;
@@ -77,14 +47,12 @@ void bl_axis(float uv, uint32_t dim, uint32_t out[3])
     out[0] = a.i0; out[1] = a.i1; out[2] = bits_of(a.f);
 }
 
-static float lerp(float x, float y, float s) { return x + s * (y - x); }
-
 static void sample(const uint32_t* src, uint32_t W, uint32_t H, float u, float v, float out[3])
 {
     const Axis x = axis_of(u, W), y = axis_of(v, H);
     float t00[3], t10[3], t01[3], t11[3];
-    unpack(src[(uint64_t)y.i0 * W + x.i0], t00); unpack(src[(uint64_t)y.i0 * W + x.i1], t10);
-    unpack(src[(uint64_t)y.i1 * W + x.i0], t01); unpack(src[(uint64_t)y.i1 * W + x.i1], t11);
+    unpack_r11g11b10(src[(uint64_t)y.i0 * W + x.i0], t00); unpack_r11g11b10(src[(uint64_t)y.i0 * W + x.i1], t10);
+    unpack_r11g11b10(src[(uint64_t)y.i1 * W + x.i0], t01); unpack_r11g11b10(src[(uint64_t)y.i1 * W + x.i1], t11);
     for (int c = 0; c < 3; ++c) out[c] = lerp(lerp(t00[c], t10[c], x.f), lerp(t01[c], t11[c], x.f), y.f);
 }
 
@@ -150,7 +118,7 @@ void bl_downsample(const uint32_t* src, uint32_t sW, uint32_t sH, uint32_t dW, u
         for (uint32_t px = 0; px < dW; ++px) {
             float c[3];
             downsample_texel(src, sW, sH, dW, dH, invX, invY, first, px, py, c);
-            out[(uint64_t)py * dW + px] = pack(c);
+            out[(uint64_t)py * dW + px] = pack_r11g11b10(c[0], c[1], c[2]);
             if (rgb) memcpy(rgb + 3 * ((uint64_t)py * dW + px), c, 12);
         }
 }
@@ -161,7 +129,7 @@ void bl_upsample(const uint32_t* src, uint32_t sW, uint32_t sH, uint32_t dW, uin
         for (uint32_t px = 0; px < dW; ++px) {
             float c[3];
             upsample_texel(src, sW, sH, dW, dH, radius, px, py, c);
-            out[(uint64_t)py * dW + px] = pack(c);
+            out[(uint64_t)py * dW + px] = pack_r11g11b10(c[0], c[1], c[2]);
             if (rgb) memcpy(rgb + 3 * ((uint64_t)py * dW + px), c, 12);
         }
 }

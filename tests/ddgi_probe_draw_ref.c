@@ -71,18 +71,11 @@ void pd_unit_sphere(float* vertices, uint32_t* indices)
         }
 }
 
-static void pd_coords(const DgDesc* D, uint32_t p, int32_t c[3])
-{
-    const uint32_t cx = (uint32_t)D->probeCounts[0], cz = (uint32_t)D->probeCounts[2];
-    c[0] = (int32_t)(p % cx); c[2] = (int32_t)((p / cx) % cz); c[1] = (int32_t)(p / (cx * cz));
-}
-
+/* LOAD of probe p (tests/ddgi_ref.c probe_at) */
 static void pd_probe(const DgDesc* D, const uint16_t* data, uint32_t p, int32_t c[3], float pos[3], float* state)
 {
-    float ext[3], w;
-    for (int a = 0; a < 3; ++a) ext[a] = (D->probeSpacing[a] * (float)(D->probeCounts[a] - 1)) * 0.5f;
-    pd_coords(D, p, c);
-    probe_pos(D, ext, data, c, pos, &w, NULL);
+    float w;
+    probe_at(D, data, p, c, pos, &w);
     *state = (D->flags & 2u) ? w : 0.0f;
 }
 
@@ -111,8 +104,6 @@ static PdVertex pd_vertex(const PdConsts* k, const float pos[3], const float nor
     v.d = clip[2] / v.w;
     return v;
 }
-
-static float pd_edge(float ax, float ay, float bx, float by, float px, float py) { return fmaf(bx - ax, py - ay, -((by - ay) * (px - ax))); }
 
 static uint32_t pd_unorm8(float c) { return (uint32_t)(saturate(c) * 255.0f + 0.5f); }
 
@@ -164,7 +155,7 @@ void pd_draw(const PdConsts* k, const DgDesc* D, const uint16_t* data, const uin
                 const PdVertex v0 = pd_vertex(k, positions + 3u * inst, vertices + 8u * ia + 3u, W, H), v1 = pd_vertex(k, positions + 3u * inst, vertices + 8u * ib + 3u, W, H),
                                v2 = pd_vertex(k, positions + 3u * inst, vertices + 8u * ic + 3u, W, H);
                 if (!(v0.w > k->nearPlane && v1.w > k->nearPlane && v2.w > k->nearPlane)) { n[PD_NEAR_DROPPED] += pass == 0; continue; }
-                const float area = pd_edge(v0.sx, v0.sy, v1.sx, v1.sy, v2.sx, v2.sy);
+                const float area = edge(v0.sx, v0.sy, v1.sx, v1.sy, v2.sx, v2.sy);
                 if (!(area < 0.0f)) { n[area > 0.0f ? PD_BACK_CULLED : PD_NO_AREA] += pass == 0; continue; }
                 const float minx = fminf(fminf(v0.sx, v1.sx), v2.sx), maxx = fmaxf(fmaxf(v0.sx, v1.sx), v2.sx);
                 const float miny = fminf(fminf(v0.sy, v1.sy), v2.sy), maxy = fmaxf(fmaxf(v0.sy, v1.sy), v2.sy);
@@ -177,8 +168,8 @@ void pd_draw(const PdConsts* k, const DgDesc* D, const uint16_t* data, const uin
                 for (uint32_t py = (uint32_t)loy; py <= (uint32_t)hiy; ++py)
                     for (uint32_t px = (uint32_t)lox; px <= (uint32_t)hix; ++px) {
                         const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
-                        const float e0 = -pd_edge(v1.sx, v1.sy, v2.sx, v2.sy, cx, cy), e1 = -pd_edge(v2.sx, v2.sy, v0.sx, v0.sy, cx, cy),
-                                    e2 = -pd_edge(v0.sx, v0.sy, v1.sx, v1.sy, cx, cy);
+                        const float e0 = -edge(v1.sx, v1.sy, v2.sx, v2.sy, cx, cy), e1 = -edge(v2.sx, v2.sy, v0.sx, v0.sy, cx, cy),
+                                    e2 = -edge(v0.sx, v0.sy, v1.sx, v1.sy, cx, cy);
                         if (!(e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f)) continue;
                         const float den = (e0 + e1) + e2;
                         if (!(den > 0.0f)) continue;
@@ -213,7 +204,7 @@ void pd_draw(const PdConsts* k, const DgDesc* D, const uint16_t* data, const uin
         const PdVertex v0 = pd_vertex(k, positions + 3u * inst, vertices + 8u * ia + 3u, W, H), v1 = pd_vertex(k, positions + 3u * inst, vertices + 8u * ib + 3u, W, H),
                        v2 = pd_vertex(k, positions + 3u * inst, vertices + 8u * ic + 3u, W, H);
         const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
-        const float e0 = -pd_edge(v1.sx, v1.sy, v2.sx, v2.sy, cx, cy), e1 = -pd_edge(v2.sx, v2.sy, v0.sx, v0.sy, cx, cy), e2 = -pd_edge(v0.sx, v0.sy, v1.sx, v1.sy, cx, cy);
+        const float e0 = -edge(v1.sx, v1.sy, v2.sx, v2.sy, cx, cy), e1 = -edge(v2.sx, v2.sy, v0.sx, v0.sy, cx, cy), e2 = -edge(v0.sx, v0.sy, v1.sx, v1.sy, cx, cy);
         color[i] = pd_shade(k, D, data, irradiance, instanceToProbe[inst], &v0, &v1, &v2, e0, e1, e2);
         depth[i] = float_of((uint32_t)(winners[i] >> 32));
     }

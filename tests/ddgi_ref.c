@@ -31,13 +31,13 @@
  *   bilinear  : t = uv * (float)dim - 0.5f; t0 = floorf(t); f = t - t0; i = (int)fminf(fmaxf(t0, -1), (float)dim); texels
  *               (i + dim) % dim and (i + 1 + dim) % dim (wrap); lerp(lerp(t00, t10, fx), lerp(t01, t11, fx), fy), lerp(x, y, s) = x + s * (y - x);
  *   texels    : UNORM10 (float)v / 1023.0f; binary16 exact;
- *   pow(x, e) : x > 0: dg_exp2(e * dg_log2(x)), the two software functions of csrc/soft_math.hip.h restated below (their
- *               coefficients and error bounds are derived in tests/postprocess_ref.c); otherwise 0.
+ *   pow(x, e) : x > 0: dg_exp2(e * dg_log2(x)), the two software functions of tests/ref_soft_math.h; otherwise 0.
  *   PS_Main   : ambient = (albedo * (1 / pi)) * irr, times (float)ssao / 255.0f when m_SSAOEnabled (unbound: 255);
  *               rgb = lr_lit's rgb + ambient.  Debug view 10: irr.
  * A pixel exactly on a probe divides 0 by 0 and follows binary32 rules; the tests keep surfaces off probes.
  */
 #include "lighting_ref.c"
+#include "ref_soft_math.h"
 
 typedef struct
 {
@@ -67,47 +67,17 @@ typedef struct
 enum { DG_BLEND_ONE, DG_BLEND_PARTIAL, DG_BLEND_ZERO, DG_SKIPPED_SOME, DG_SKIPPED_ALL, DG_RELOCATED, DG_CHEB_TAKEN, DG_CHEB_NOT, DG_CRUSH_TAKEN, DG_CRUSH_NOT,
        DG_FOLD_TAKEN, DG_FOLD_NOT, DG_CLAMPED, DG_COUNTERS };
 
-static const float kDgLog2C[10] = { 0x1.715476p+0f, -0x1.715470p-1f, 0x1.ec70aap-2f, -0x1.715a70p-2f, 0x1.277a52p-2f,
-                                    -0x1.eab7a8p-3f, 0x1.a38c64p-3f, -0x1.87f6aap-3f, 0x1.7a63c4p-3f, -0x1.b84fe0p-4f };
-static const float kDgExp2C[7] = { 0x1.000000p+0f, 0x1.62e430p-1f, 0x1.ebfbe0p-3f, 0x1.c6af6cp-5f, 0x1.3b2a54p-7f, 0x1.5f0890p-10f, 0x1.44138ap-13f };
-
-float dg_log2(float x)
-{
-    uint32_t u = bits_of(x);
-    if (u == 0x7F800000u) return x;
-    int bias = -127;
-    if (u < 0x00800000u) { u = bits_of(x * 0x1p24f); bias = -151; }
-    u += 0x3F800000u - 0x3F3504F3u;
-    const int k = (int)(u >> 23) + bias;
-    const float f = float_of((u & 0x007FFFFFu) + 0x3F3504F3u) - 1.0f;
-    float p = kDgLog2C[9];
-    for (int j = 8; j >= 0; --j) p = fmaf(p, f, kDgLog2C[j]);
-    return fmaf(f, p, (float)k);
-}
-
-float dg_exp2(float x)
-{
-    const float i = rintf(x), f = x - i;
-    float p = kDgExp2C[6];
-    for (int j = 5; j >= 0; --j) p = fmaf(p, f, kDgExp2C[j]);
-    return ldexpf(p, (int)fminf(fmaxf(i, -300.0f), 300.0f));
-}
-
-float dg_pow(float x, float e) { return x > 0.0f ? dg_exp2(e * dg_log2(x)) : 0.0f; }
-
-static float lerp1(float x, float y, float s) { return x + s * (y - x); }
+float dg_log2(float x) { return log2_soft(x); }
+float dg_exp2(float x) { return exp2_signed(x); }
+float dg_pow(float x, float e) { return pow_soft(x, e); }
 
 /* returns 1 when the fold (d.z < 0) was taken */
 static int dg_oct(const float d[3], float uv[2])
 {
     const float l = (fabsf(d[0]) + fabsf(d[1])) + fabsf(d[2]);
     uv[0] = d[0] / l; uv[1] = d[1] / l;
-    if (d[2] < 0.0f) {
-        const float fu = (1.0f - fabsf(uv[1])) * (uv[0] >= 0.0f ? 1.0f : -1.0f), fv = (1.0f - fabsf(uv[0])) * (uv[1] >= 0.0f ? 1.0f : -1.0f);
-        uv[0] = fu; uv[1] = fv;
-        return 1;
-    }
-    return 0;
+    if (d[2] < 0.0f) oct_fold(uv[0], uv[1], uv);
+    return d[2] < 0.0f;
 }
 void dg_oct_n(const float* d, uint64_t n, float* uv) { for (uint64_t i = 0; i < n; ++i) dg_oct(d + 3 * i, uv + 2 * i); }
 
@@ -137,7 +107,7 @@ void dg_fetch_irradiance(const DgDesc* D, const uint32_t* irradiance, const int3
         const uint32_t sh = 10u * ch;
         const float t00 = (float)((w00 >> sh) & 1023u) / 1023.0f, t10 = (float)((w10 >> sh) & 1023u) / 1023.0f;
         const float t01 = (float)((w01 >> sh) & 1023u) / 1023.0f, t11 = (float)((w11 >> sh) & 1023u) / 1023.0f;
-        rgb[ch] = lerp1(lerp1(t00, t10, ax.f), lerp1(t01, t11, ax.f), ay.f);
+        rgb[ch] = lerp(lerp(t00, t10, ax.f), lerp(t01, t11, ax.f), ay.f);
     }
 }
 
@@ -150,8 +120,20 @@ void dg_fetch_distance(const DgDesc* D, const uint16_t* distance, const int32_t 
     for (uint32_t ch = 0; ch < 2; ++ch) {
         const float t00 = half_to_float(s[(ay.i0 * W + ax.i0) * 2u + ch]), t10 = half_to_float(s[(ay.i0 * W + ax.i1) * 2u + ch]);
         const float t01 = half_to_float(s[(ay.i1 * W + ax.i0) * 2u + ch]), t11 = half_to_float(s[(ay.i1 * W + ax.i1) * 2u + ch]);
-        rg[ch] = lerp1(lerp1(t00, t10, ax.f), lerp1(t01, t11, ax.f), ay.f);
+        rg[ch] = lerp(lerp(t00, t10, ax.f), lerp(t01, t11, ax.f), ay.f);
     }
+}
+
+/* the volume's half extent, and probe number p's coordinates: p = (y * counts.z + z) * counts.x + x */
+static void probe_extent(const DgDesc* D, float ext[3])
+{
+    for (int a = 0; a < 3; ++a) ext[a] = (D->probeSpacing[a] * (float)(D->probeCounts[a] - 1)) * 0.5f;
+}
+
+static inline void probe_coords(const DgDesc* D, uint32_t probe, int32_t c[3])
+{
+    const uint32_t cx = (uint32_t)D->probeCounts[0], cz = (uint32_t)D->probeCounts[2];
+    c[0] = (int32_t)(probe % cx); c[1] = (int32_t)(probe / (cx * cz)); c[2] = (int32_t)((probe / cx) % cz);
 }
 
 static void probe_pos(const DgDesc* D, const float ext[3], const uint16_t* data, const int32_t c[3], float pp[3], float* state, int* relocated)
@@ -165,6 +147,15 @@ static void probe_pos(const DgDesc* D, const float ext[3], const uint16_t* data,
     if (relocated) *relocated = (D->flags & 1u) && ((d[0] | d[1] | d[2]) & 0x7FFFu) != 0;
 }
 
+/* coordinates, position and data.w of probe number `probe`, for the references that include this file */
+static inline void probe_at(const DgDesc* D, const uint16_t* data, uint32_t probe, int32_t c[3], float pos[3], float* state)
+{
+    float ext[3];
+    probe_extent(D, ext);
+    probe_coords(D, probe, c);
+    probe_pos(D, ext, data, c, pos, state, NULL);
+}
+
 void dg_irradiance(const DgDesc* D, const uint16_t* data, const uint32_t* irradiance, const uint16_t* distance, const float world[3], const float N[3],
                    const float cameraOrigin[3], float out[3], DgTrace* tr)
 {
@@ -174,9 +165,9 @@ void dg_irradiance(const DgDesc* D, const uint16_t* data, const uint32_t* irradi
     out[0] = out[1] = out[2] = 0.0f;
     float ext[3], toPoint[3], viewDir[3], delta[3], P[3], basePos[3], alpha[3], state;
     int32_t last[3], base[3];
+    probe_extent(D, ext);
     for (int a = 0; a < 3; ++a) {
         last[a] = D->probeCounts[a] - 1;
-        ext[a] = (D->probeSpacing[a] * (float)last[a]) * 0.5f;
         toPoint[a] = world[a] - cameraOrigin[a];
     }
     normalize3(toPoint, viewDir);

@@ -29,13 +29,7 @@
  *             shadow = occluded ? 0 : 1) (lr_lit's words, emissive included) + (fminf(albedo, 0.9f) * kInvPi) * dg_irradiance(world,
  *             normal, cameraOrigin = probe); record (saturate(rgb), t).  An inactive probe's records keep what they held;
  *   blends    stated in csrc/k_giprobeblend.hip ("CONVENTION") in the words of the functions below. */
-#define float_of sm_float_of
-#define bits_of sm_bits_of
-#define normalize3 sm_normalize3
 #include "shadowmask_ref.c"
-#undef float_of
-#undef bits_of
-#undef normalize3
 #include "ddgi_ref.c"
 
 typedef struct
@@ -52,19 +46,11 @@ typedef struct { uint32_t inst, tri; float t, b1, b2; uint32_t front; } DuHit;  
 #define DU_BACKFACE_LIMIT 25u
 
 /* ---- probes, rays, texels ---------------------------------------------------------------------------------------------------- */
-static void probe_coords(const DgDesc* D, uint32_t probe, int32_t c[3])
-{
-    const uint32_t cx = (uint32_t)D->probeCounts[0], cz = (uint32_t)D->probeCounts[2];
-    c[0] = (int32_t)(probe % cx); c[1] = (int32_t)(probe / (cx * cz)); c[2] = (int32_t)((probe / cx) % cz);
-}
-
-/* position and state of one probe; returns 1 when it is inactive */
+/* position and state of one probe (tests/ddgi_ref.c probe_at); returns 1 when it is inactive */
 static int probe_of(const DgDesc* D, const uint16_t* data, uint32_t probe, int32_t c[3], float pos[3])
 {
-    float ext[3], state;
-    probe_coords(D, probe, c);
-    for (int a = 0; a < 3; ++a) ext[a] = (D->probeSpacing[a] * (float)(D->probeCounts[a] - 1)) * 0.5f;
-    probe_pos(D, ext, data, c, pos, &state, NULL);
+    float state;
+    probe_at(D, data, probe, c, pos, &state);
     return (D->flags & 2u) && state == 1.0f;
 }
 
@@ -80,10 +66,7 @@ void du_ray_direction(const DuConsts* k, uint32_t i, float out[3])
 void du_oct_decode(float ox, float oy, float out[3])
 {
     float v[3] = { ox, oy, (1.0f - fabsf(ox)) - fabsf(oy) };
-    if (v[2] < 0.0f) {
-        v[0] = (1.0f - fabsf(oy)) * (ox >= 0.0f ? 1.0f : -1.0f);
-        v[1] = (1.0f - fabsf(ox)) * (oy >= 0.0f ? 1.0f : -1.0f);
-    }
+    if (v[2] < 0.0f) oct_fold(ox, oy, v);
     normalize3(v, out);
 }
 
@@ -153,12 +136,6 @@ void du_closest_n(const SmScene* s, const float* o, const float* d, uint64_t n, 
 }
 
 /* ---- the trace ------------------------------------------------------------------------------------------------------------------ */
-static void unpack_vertex_normal(uint32_t packed, float o[3])
-{
-    const float x = (float)((packed >> 20) & 0x3FFu) / 1023.0f, y = (float)((packed >> 10) & 0x3FFu) / 1023.0f, z = (float)(packed & 0x3FFu) / 1023.0f;
-    o[0] = x * 2.0f - 1.0f; o[1] = y * 2.0f - 1.0f; o[2] = z * 2.0f - 1.0f;
-}
-
 static float bary(float v0, float v1, float v2, float b0, float b1, float b2) { return ((0.0f + v0 * b0) + v1 * b1) + v2 * b2; }
 
 /* lr_lit's words (tests/lighting_ref.c) for a surface given outright, seen from `viewer` */
@@ -210,7 +187,7 @@ static void trace_ray(const DuBlock* b, const SmScene* s, const uint16_t* data, 
     for (int j = 0; j < 3; ++j) {
         uint32_t packed;
         memcpy(&packed, s->vertices + T.i[j] * 20u + 12u, 4);
-        unpack_vertex_normal(packed, n[j]);
+        unpack_normal10(packed, n[j]);
     }
     const float b1 = hit.b1, b2 = hit.b2, b0 = (1.0f - b1) - b2;
     const float p[3] = { bary(v[0].x, v[1].x, v[2].x, b0, b1, b2), bary(v[0].y, v[1].y, v[2].y, b0, b1, b2), bary(v[0].z, v[1].z, v[2].z, b0, b1, b2) };
@@ -415,7 +392,7 @@ static void blend_distance(const DuBlock* b, const uint16_t* data, const float* 
                     if (px == 0.0f && py == 0.0f) word |= DU_D_PREV_ZERO;
                     if (!(sumW >= 1e-9f * 256.0f)) word |= DU_D_SUMW_FLOOR;
                     for (int ch = 0; ch < 2; ++ch) {
-                        const uint32_t before = t[ch] & 0x7FFFu, after = sm_half_bits(lerp1(ch ? ry : rx, ch ? py : px, h)) & 0x7FFFu;
+                        const uint32_t before = t[ch] & 0x7FFFu, after = sm_half_bits(lerp(ch ? ry : rx, ch ? py : px, h)) & 0x7FFFu;
                         if (before == 0x7C00u) word |= DU_D_PREV_INF;
                         if (before > 0x7C00u) word |= DU_D_PREV_NAN;
                         if (after == 0x7C00u) word |= DU_D_STORE_INF;
@@ -424,7 +401,7 @@ static void blend_distance(const DuBlock* b, const uint16_t* data, const float* 
                     }
                     rules[(uint64_t)p * 196u + (ty - 1u) * 14u + (tx - 1u)] = word | clipped << DU_D_CLIPPED_SHIFT;
                 }
-                t[0] = sm_half_bits(lerp1(rx, px, h)); t[1] = sm_half_bits(lerp1(ry, py, h));
+                t[0] = sm_half_bits(lerp(rx, px, h)); t[1] = sm_half_bits(lerp(ry, py, h));
             }
         for (uint32_t ty = 0; ty < N; ++ty)
             for (uint32_t tx = 0; tx < N; ++tx) {

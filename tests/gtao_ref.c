@@ -35,11 +35,10 @@
  *   special   : whatever these rules give.  With the project's projection DepthUnpackConsts = (-near, +0): a depth word of +0
  *               gives -near / (0 - 0) = -inf, which the clamp turns into view depth 0; a NaN depth gives 0 likewise.
  */
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "ref_formats.h"
+#include "ref_soft_math.h"
 
-typedef float hf;                                  /* a binary16 value, carried exactly */
+typedef float hf;                                 /* a binary16 value, carried exactly */
 typedef struct { int32_t ViewportSize[2]; float ViewportPixelSize[2]; float DepthUnpackConsts[2]; float CameraTanHalfFOV[2];
                  float NDCToViewMul[2]; float NDCToViewAdd[2]; float NDCToViewMul_x_PixelSize[2]; float EffectRadius, EffectFalloffRange;
                  float RadiusMultiplier, Padding0, FinalValuePower, DenoiseBlurBeta;
@@ -48,9 +47,6 @@ typedef struct { float m[4][4]; uint32_t quality; } GtMainPush;
 typedef struct { hf x, y, z; } H3;
 typedef struct { hf x, y, z, w; } H4;
 typedef struct { float x, y, z; } F3;
-
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
 /* ---- binary32 -> binary16, round to nearest even ------------------------------------------------------------------------ */
 float gt_r16(float x)
@@ -66,22 +62,9 @@ float gt_r16(float x)
 }
 #define r16 gt_r16
 
-uint16_t gt_half_bits(float h)                                             /* the word of an exact binary16 value */
-{
-    const uint32_t u = bits_of(h), s = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
-    if (a > 0x7F800000u) return 0x7E00u;                                   /* every NaN is stored as this word: its sign never shows */
-    if (a == 0x7F800000u) return (uint16_t)(s | 0x7C00u);
-    if (a < 0x38800000u) return (uint16_t)(s | (uint32_t)(float_of(a) * 0x1p24f));
-    return (uint16_t)(s | ((a - 0x38000000u) >> 13));
-}
-
-float gt_half_value(uint16_t w)
-{
-    const uint32_t s = (uint32_t)(w & 0x8000u) << 16, e = (w >> 10) & 31u, m = w & 0x3FFu;
-    if (e == 0u) return float_of(s | bits_of((float)m * 0x1p-24f));
-    if (e == 31u) return float_of(s | 0x7F800000u | m << 13);
-    return float_of(s | (e + 112u) << 23 | m << 13);
-}
+/* the word of a binary16 value and back: the conversions of tests/ref_base.h (the passes hand gt_half_bits exact values only) */
+uint16_t gt_half_bits(float h) { return float_to_half(h); }
+float gt_half_value(uint16_t w) { return half_to_float(w); }
 
 static hf hadd(hf a, hf b) { return r16(a + b); }
 static hf hsub(hf a, hf b) { return r16(a - b); }
@@ -175,33 +158,8 @@ float gt_sin(float x) { return sincos_soft(x, 0); }
 float gt_cos(float x) { return sincos_soft(x, 1); }
 static hf hsin(hf x) { return r16(gt_sin(x)); }
 static hf hcos(hf x) { return r16(gt_cos(x)); }
-
-/* ---- log2Soft and exp2Signed of csrc/soft_math.hip.h (derivation: tests/postprocess_ref.c) --------------------------------- */
-static const float kLog2C[10] = { 0x1.715476p+0f, -0x1.715470p-1f, 0x1.ec70aap-2f, -0x1.715a70p-2f, 0x1.277a52p-2f,
-                                  -0x1.eab7a8p-3f, 0x1.a38c64p-3f, -0x1.87f6aap-3f, 0x1.7a63c4p-3f, -0x1.b84fe0p-4f };
-static const float kExp2C[7] = { 0x1.000000p+0f, 0x1.62e430p-1f, 0x1.ebfbe0p-3f, 0x1.c6af6cp-5f, 0x1.3b2a54p-7f, 0x1.5f0890p-10f, 0x1.44138ap-13f };
-static float log2_soft(float x)                                            /* x > 0 */
-{
-    uint32_t u = bits_of(x);
-    if (u == 0x7F800000u) return x;
-    int bias = -127;
-    if (u < 0x00800000u) { u = bits_of(x * 0x1p24f); bias = -151; }
-    u += 0x3F800000u - 0x3F3504F3u;
-    const int k = (int)(u >> 23) + bias;
-    const float f = float_of((u & 0x007FFFFFu) + 0x3F3504F3u) - 1.0f;
-    float p = kLog2C[9];
-    for (int j = 8; j >= 0; --j) p = fmaf(p, f, kLog2C[j]);
-    return fmaf(f, p, (float)k);
-}
-static float exp2_signed(float x)
-{
-    const float i = rintf(x), f = x - i;
-    float p = kExp2C[6];
-    for (int j = 5; j >= 0; --j) p = fmaf(p, f, kExp2C[j]);
-    return ldexpf(p, (int)fminf(fmaxf(i, -300.0f), 300.0f));
-}
 static hf hlog2(hf x) { return x > 0.0f ? r16(log2_soft(x)) : -INFINITY; }
-static hf hpow(hf v, hf p) { return v > 0.0f ? r16(exp2_signed(p * log2_soft(v))) : 0.0f; }
+static hf hpow(hf v, hf p) { return r16(pow_soft(v, p)); }
 
 /* ---- XeGTAO_FastSqrt, XeGTAO_FastACos ------------------------------------------------------------------------------------ */
 static hf fast_sqrt(float x) { return r16(float_of(0x1FBD1DF5u + (uint32_t)((int32_t)bits_of(x) >> 1))); }
@@ -334,19 +292,13 @@ static float sample_level(const uint16_t* chain, uint32_t W, uint32_t H, float u
     return gt_half_value(chain[gt_chain_offset(W, H, (uint32_t)level) + (uint64_t)y * w + x]);
 }
 
-/* the view-space normal of a GBufferA texel: UnpackOctadehron of .y as the lighting pass states it, the row vector (n, 1) times
+/* the view-space normal of a GBufferA texel: UnpackOctadehron of .y (tests/ref_formats.h unpack_oct), the row vector (n, 1) times
  * the matrix, z negated, all in binary32 */
 static F3 view_normal(const uint32_t g[4], const GtMainPush* p)
 {
-    const float fx = (float)(g[1] & 0xFFFFu) * (1.0f / 65535.0f) * 2.0f - 1.0f, fy = (float)(g[1] >> 16) * (1.0f / 65535.0f) * 2.0f - 1.0f;
-    F3 n = { fx, fy, (1.0f - fabsf(fx)) - fabsf(fy) };
-    const float t = fminf(fmaxf(-n.z, 0.0f), 1.0f);
-    n.x += n.x >= 0.0f ? -t : t;
-    n.y += n.y >= 0.0f ? -t : t;
-    const float len = sqrtf(dot3f(n, n));
-    n.x = n.x / len; n.y = n.y / len; n.z = n.z / len;
-    float o[3];
-    for (int j = 0; j < 3; ++j) o[j] = fmaf(n.z, p->m[2][j], fmaf(n.y, p->m[1][j], n.x * p->m[0][j])) + p->m[3][j];
+    float n[3], o[3];
+    unpack_oct(g[1], n);
+    for (int j = 0; j < 3; ++j) o[j] = fmaf(n[2], p->m[2][j], fmaf(n[1], p->m[1][j], n[0] * p->m[0][j])) + p->m[3][j];
     const F3 r = { o[0], o[1], o[2] * -1.0f };
     return r;
 }

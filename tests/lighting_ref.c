@@ -7,7 +7,7 @@
  *   written   : a pixel is written iff its depth is > 0.0f (NaN, +-0 and negative depths leave u0 as it is);
  *   dot3      : fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x));  normalize(v) = v / sqrtf(dot3(v, v));  rcp(x) = 1.0f / x;
  *   saturate  : fminf(fmaxf(x, 0), 1) (a NaN gives 0);  lerp(x, y, s) = x + s * (y - x);  uint(x) truncates;
- *   unpack    : RGBA8 byte * (1.0f / 255.0f); unorm16 u * (1.0f / 65535.0f) (one multiply by a constant each); octahedral
+ *   unpack    : RGBA8 byte * (1.0f / 255.0f); unorm16 likewise by 1 / 65535 (one multiply by a constant each; tests/ref_formats.h); octahedral
  *               f = f * 2 - 1, z = (1 - |fx|) - |fy|, t = saturate(-z), x += (x >= 0 ? -t : t), same for y, normalize;
  *               R9G9B9E5 ldexpf(mantissa, E - 24) (exact);
  *   position  : uv = (px + 0.5f, py + 0.5f) / (float)resolution; clip = (u * 2 + -1, v * -2 + 1); the row vector
@@ -32,37 +32,15 @@
  *   store     : R11G11B10_FLOAT per channel: NaN -> exponent and mantissa all ones, negative and -0 -> 0, +inf -> infinity,
  *               finite above the largest finite -> the largest finite, else round to nearest even, subnormals included.
  */
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "ref_formats.h"
 
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static float saturate(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
-static float dot3(const float a[3], const float b[3]) { return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])); }
-static void normalize3(const float v[3], float o[3])
-{
-    const float len = sqrtf(dot3(v, v));
-    o[0] = v[0] / len; o[1] = v[1] / len; o[2] = v[2] / len;
-}
-
-/* ---- the R11G11B10_FLOAT store ------------------------------------------------------------------------------------- */
-uint32_t lr_pack_ufloat(float v, uint32_t mbits)
-{
-    const uint32_t shift = 23u - mbits, inf = 31u << mbits, maxFinite = inf - 1u;
-    const uint32_t u = bits_of(v);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return inf | ((1u << mbits) - 1u);
-    if (u >> 31) return 0u;
-    if (u == 0x7F800000u) return inf;
-    if (u >= 0x38800000u) {
-        const uint32_t r = u - (112u << 23);
-        const uint32_t q = (r + ((1u << (shift - 1)) - 1u) + ((r >> shift) & 1u)) >> shift;
-        return q < maxFinite ? q : maxFinite;
-    }
-    return (uint32_t)rintf(v * (float)(1u << (14u + mbits)));
-}
-
-uint32_t lr_pack_r11g11b10(float r, float g, float b) { return lr_pack_ufloat(r, 6) | lr_pack_ufloat(g, 6) << 11 | lr_pack_ufloat(b, 5) << 22; }
+/* ---- the formats of tests/ref_formats.h under this library's names ------------------------------------------------------ */
+uint32_t lr_pack_ufloat(float v, uint32_t mbits) { return pack_ufloat(v, mbits); }
+uint32_t lr_pack_r11g11b10(float r, float g, float b) { return pack_r11g11b10(r, g, b); }
+float lr_unpack_unorm8(uint32_t byte) { return unpack_unorm8(byte); }
+float lr_unpack_unorm16(uint32_t u) { return unpack_unorm16(u); }
+void lr_unpack_oct(uint32_t word, float o[3]) { unpack_oct(word, o); }
+void lr_unpack_r9g9b9e5(uint32_t v, float o[3]) { unpack_r9g9b9e5(v, o); }
 
 /* ---- software exp2 for x <= 0 -----------------------------------------------------------------------------------------
  * 2^f on [-1, 0] as 1 + f * g(f), g the degree-6 interpolant of (2^f - 1) / f at the Chebyshev nodes of [-1, 0], coefficients
@@ -75,51 +53,18 @@ uint32_t lr_pack_r11g11b10(float r, float g, float b) { return lr_pack_ufloat(r,
  *               [0.5, 1]: 2^-25.  Sum (1 + 1 + 2^-2 + 2^-4 + 2^-6 + 2^-9 + 2^-12) * 2^-25 = 2.3304 * 2^-25;
  *   bound     : LR_EXP2_BOUND = 2.46 * 2^-25 (7.33e-8) >= 2.3304 * 2^-25 + 0.112 * 2^-25, times 2^i; that is 1.23 ulp of a result
  *               in [0.5, 1).  f = 0 gives exactly 1, so integers give exact powers of two. */
-static const float kExp2C[8] = { 0x1.000000p+0f, 0x1.62e430p-1f, 0x1.ebfbdep-3f, 0x1.c6b024p-5f, 0x1.3b20d4p-7f, 0x1.5ca2c2p-10f, 0x1.383ffcp-13f, 0x1.7b4b46p-17f };
+static const float kExp2CeilC[8] = { 0x1.000000p+0f, 0x1.62e430p-1f, 0x1.ebfbdep-3f, 0x1.c6b024p-5f, 0x1.3b20d4p-7f, 0x1.5ca2c2p-10f, 0x1.383ffcp-13f, 0x1.7b4b46p-17f };
 const double LR_EXP2_BOUND = 2.46 * 0x1p-25;
 
 float lr_exp2(float x)
 {
     const float i = ceilf(x), f = x - i;
-    float p = kExp2C[7];
-    for (int k = 6; k >= 0; --k) p = fmaf(p, f, kExp2C[k]);
+    float p = kExp2CeilC[7];
+    for (int k = 6; k >= 0; --k) p = fmaf(p, f, kExp2CeilC[k]);
     return ldexpf(p, (int)i);
 }
 
 /* ---- UnpackGBuffer ---------------------------------------------------------------------------------------------------- */
-float lr_unpack_unorm8(uint32_t byte) { return (float)byte * (1.0f / 255.0f); }
-float lr_unpack_unorm16(uint32_t u) { return (float)u * (1.0f / 65535.0f); }
-
-void lr_unpack_oct(uint32_t word, float o[3])
-{
-    const float fx = lr_unpack_unorm16(word & 0xFFFFu) * 2.0f - 1.0f, fy = lr_unpack_unorm16(word >> 16) * 2.0f - 1.0f;
-    float n[3] = { fx, fy, (1.0f - fabsf(fx)) - fabsf(fy) };
-    const float t = saturate(-n[2]);
-    n[0] += n[0] >= 0.0f ? -t : t;
-    n[1] += n[1] >= 0.0f ? -t : t;
-    normalize3(n, o);
-}
-
-void lr_unpack_r9g9b9e5(uint32_t v, float o[3])
-{
-    const int e = (int)(v >> 27) - 24;
-    o[0] = ldexpf((float)(v & 0x1FFu), e); o[1] = ldexpf((float)((v >> 9) & 0x1FFu), e); o[2] = ldexpf((float)((v >> 18) & 0x1FFu), e);
-}
-
-static float quick_random_float(uint32_t* seed)
-{
-    *seed = 1664525u * *seed + 1013904223u;
-    return (float)(*seed & 0x00FFFFFFu) / 16777216.0f;
-}
-
-static float half_to_float(uint32_t h)
-{
-    const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3FFu;
-    if (e == 31u) return float_of(s | 0x7F800000u | m << 13);
-    if (e == 0u) return (s ? -1.0f : 1.0f) * ldexpf((float)m, -24);
-    return float_of(s | (e + 112u) << 23 | m << 13);
-}
-
 typedef struct
 {
     float m_ClipToWorld[4][4];

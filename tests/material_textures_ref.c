@@ -1,14 +1,15 @@
 /* material_textures_ref.c -- test reference of the TEXTURED G-buffer resolve (visibility_resolve.hip.h, "basepass_PS_Main_GBuffer"
  * with a texture table bound at t19): the software sampler, the analytic derivatives, GetCommonGBufferParams
  * (lightingcommon.hlsli:435-493) and tangent-free normal mapping (toyrenderer_common.hlsli:226-247) in scalar C.  Compiled by
- * the tests themselves with gcc -O2 -ffp-contract=off: only the fmaf calls written here fuse.
+ * the tests themselves with gcc -O2 -ffp-contract=off: only the fmaf calls written here and in the headers fuse.
  *
- * The resolve up to q_i = e_i / w_i, s = (q0 + q1) + q2, the motion words, the interpolated normal, the debug byte and the
- * pack functions are those of tests/gbuffer_ref.c, restated.  Added per covered pixel:
+ * The resolve is the checked texel decode, the weights q_i, s and the motion of tests/ref_mesh_stage.h; the interpolated normal
+ * and the debug byte are as in tests/gbuffer_ref.c, the packs and the vertex normal those of tests/ref_formats.h, log2Soft that
+ * of tests/ref_soft_math.h.  Added per covered pixel:
  *   interp(a)  = fmaf(q2, a2, fmaf(q1, a1, q0 * a0)) / s, for the texture coordinate (m_TexCoord, half2 -> float, exact) and
  *                the world position mul(pos, World);
- *   ddx, ddy   = interp of the SAME triangle with the edge functions evaluated at (cx + 1, cy) and at (cx, cy + 1) (the
- *                triangle's plane extended), minus the centre value;
+ *   ddx, ddy   = interp of the SAME triangle with the weights taken at (cx + 1, cy) and at (cx, cy + 1) (the triangle's
+ *                plane extended), minus the centre value: three sample points of one weights function;
  *   sample(T)  : W, H = T's mip-0 size.  A = ddx(uv) * (W, H), B = ddy(uv) * (W, H); |A| = sqrtf(fmaf(A.y, A.y, A.x * A.x));
  *                A is the major axis iff |A| >= |B| (a NaN picks B); Pmax, Pmin the major and the other length;
  *                n = ceilf(Pmax / Pmin); N = n <= 16 ? n : 16 (Pmin = 0 and NaN give 16);
@@ -26,7 +27,7 @@
  *                table (the sRGB transfer function in double precision, rounded once to float), A as UNORM;
  *   params     : albedo = m_ConstAlbedo * sample, roughness = mr.g, metallic = mr.b (defaults 1, 0), emissive = m_ConstEmissive
  *                * sample.rgb; with a normal map xy = 2.0f * n.xy - 1.0f, z = sqrtf(1.0f - fmaf(y, y, x * x)) (a NaN is kept),
- *                TBN of CalculateTBNWithoutTangent from ddx / ddy of the world position and of uv (cross as in gbuffer_ref.c,
+ *                TBN of CalculateTBNWithoutTangent from ddx / ddy of the world position and of uv (cross3 of tests/ref_base.h,
  *                the float2 x float2x3 product fmaf(b, r1, a * r0), normalize = v / sqrtf(dot3)), normal =
  *                normalize(fmaf(u.z, n, fmaf(u.y, b, u.x * t))) with n the interpolated, not renormalised geometric normal;
  *   w          = RGBA8(roughness, metallic, 0, 0).
@@ -34,126 +35,12 @@
  * of another format is left as it is in both outputs.
  * Parity with D3D hardware's fixed-point, vendor-specific anisotropic filtering stays unpinned.
  */
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "ref_formats.h"
+#include "ref_mesh_stage.h"
+#include "ref_soft_math.h"
 
-#include "tr_oracle.h"
-
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static float saturate(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
-
-/* ---- restated from tests/gbuffer_ref.c ---------------------------------------------------------------------------------- */
-static uint32_t pack_rgba8(float r, float g, float b, float a)
-{
-    return (uint32_t)(saturate(r) * 255.0f) | (uint32_t)(saturate(g) * 255.0f) << 8 | (uint32_t)(saturate(b) * 255.0f) << 16 |
-           (uint32_t)(saturate(a) * 255.0f) << 24;
-}
-
-static uint32_t pack_oct(float nx, float ny, float nz)
-{
-    const float l1 = (fabsf(nx) + fabsf(ny)) + fabsf(nz);
-    const float x = nx / l1, y = ny / l1, z = nz / l1;
-    float ox = x, oy = y;
-    if (!(z >= 0.0f)) {
-        ox = (1.0f - fabsf(y)) * (x >= 0.0f ? 1.0f : -1.0f);
-        oy = (1.0f - fabsf(x)) * (y >= 0.0f ? 1.0f : -1.0f);
-    }
-    ox = ox * 0.5f + 0.5f;
-    oy = oy * 0.5f + 0.5f;
-    const uint32_t ux = (uint32_t)rintf(saturate(ox) * 65535.0f), uy = (uint32_t)rintf(saturate(oy) * 65535.0f);
-    return ux | uy << 16;
-}
-
-static uint32_t pack_r9g9b9e5(float r, float g, float b)
-{
-    const float kMaxVal = float_of(0x477F8000u), kMinVal = float_of(0x37800000u);
-    r = fminf(fmaxf(r, 0.0f), kMaxVal);
-    g = fminf(fmaxf(g, 0.0f), kMaxVal);
-    b = fminf(fmaxf(b, 0.0f), kMaxVal);
-    const float maxChannel = fmaxf(fmaxf(kMinVal, r), fmaxf(g, b));
-    const float bias = float_of((bits_of(maxChannel) + 0x07804000u) & 0x7F800000u);
-    const uint32_t R = bits_of(r + bias), G = bits_of(g + bias), B = bits_of(b + bias);
-    const uint32_t E = (bits_of(bias) << 4) + 0x10000000u;
-    return E | B << 18 | G << 9 | (R & 0x1FFu);
-}
-
-static float quick_random_float(uint32_t seed)
-{
-    seed = 1664525u * seed + 1013904223u;
-    return (float)(seed & 0x00FFFFFFu) / 16777216.0f;
-}
-
-static void cross3(const float a[3], const float b[3], float o[3])
-{
-    o[0] = fmaf(a[1], b[2], -(a[2] * b[1]));
-    o[1] = fmaf(a[2], b[0], -(a[0] * b[2]));
-    o[2] = fmaf(a[0], b[1], -(a[1] * b[0]));
-}
-
-static float dot3(const float a[3], const float b[3]) { return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])); }
-
-static void normalize3(const float v[3], float o[3])
-{
-    const float len = sqrtf(dot3(v, v));
-    for (int j = 0; j < 3; ++j) o[j] = v[j] / len;
-}
-
-static void vertex_normal(uint32_t word, const OrcMatrix* world, float o[3])
-{
-    float u[3], r0[3], r1[3], r2[3], n[3];
-    const float x = (float)((word >> 20) & 0x3FFu) / 1023.0f, y = (float)((word >> 10) & 0x3FFu) / 1023.0f, z = (float)(word & 0x3FFu) / 1023.0f;
-    u[0] = x * 2.0f - 1.0f; u[1] = y * 2.0f - 1.0f; u[2] = z * 2.0f - 1.0f;
-    cross3(world->m[1], world->m[2], r0);
-    cross3(world->m[2], world->m[0], r1);
-    cross3(world->m[0], world->m[1], r2);
-    for (int j = 0; j < 3; ++j) n[j] = fmaf(u[2], r2[j], fmaf(u[1], r1[j], u[0] * r0[j]));
-    normalize3(n, o);
-}
-
-static void mul_point3(const float p[3], const OrcMatrix* M, float o[3])
-{
-    for (int j = 0; j < 3; ++j) o[j] = fmaf(p[2], M->m[2][j], fmaf(p[1], M->m[1][j], p[0] * M->m[0][j])) + M->m[3][j];
-}
-
-static void mul_point_4(const float p[3], const OrcMatrix* M, float o[4])
-{
-    for (int j = 0; j < 4; ++j) o[j] = fmaf(p[2], M->m[2][j], fmaf(p[1], M->m[1][j], p[0] * M->m[0][j])) + M->m[3][j];
-}
-
-static float edge(float ax, float ay, float bx, float by, float px, float py)
-{
-    return fmaf(bx - ax, py - ay, -((by - ay) * (px - ax)));
-}
-
-/* ---- restated from soft_math.hip.h (log2Soft) --------------------------------------------------------------------------- */
-static const float kLog2C[10] = { 0x1.715476p+0f, -0x1.715470p-1f, 0x1.ec70aap-2f, -0x1.715a70p-2f, 0x1.277a52p-2f,
-                                  -0x1.eab7a8p-3f, 0x1.a38c64p-3f, -0x1.87f6aap-3f, 0x1.7a63c4p-3f, -0x1.b84fe0p-4f };
-
-float mt_log2(float x)
-{
-    uint32_t u = bits_of(x);
-    if (u == 0x7F800000u) return x;
-    int bias = -127;
-    if (u < 0x00800000u) { u = bits_of(x * 0x1p24f); bias = -151; }
-    u += 0x3F800000u - 0x3F3504F3u;
-    const int k = (int)(u >> 23) + bias;
-    const float f = float_of((u & 0x007FFFFFu) + 0x3F3504F3u) - 1.0f;
-    float p = kLog2C[9];
-    for (int j = 8; j >= 0; --j) p = fmaf(p, f, kLog2C[j]);
-    return fmaf(f, p, (float)k);
-}
-
-/* ---- half -> float, exact ---------------------------------------------------------------------------------------------- */
-float mt_half_to_float(uint16_t h)
-{
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
-    if (e == 0x1Fu) return float_of(sign | 0x7F800000u | m << 13);
-    if (e) return float_of(sign | (e + 112u) << 23 | m << 13);
-    const float v = (float)m * 0x1p-24f;                                         /* subnormal or zero */
-    return sign ? -v : v;
-}
+float mt_log2(float x) { return log2_soft(x); }
+float mt_half_to_float(uint16_t h) { return half_to_float(h); }
 
 /* ---- the sRGB table ---------------------------------------------------------------------------------------------------- */
 void mt_srgb_table(float out[256])
@@ -183,8 +70,6 @@ static void texel(const MtTexture* t, const float* srgb, uint32_t level, uint32_
     for (int c = 0; c < 4; ++c)
         o[c] = (t->format == MT_FORMAT_SRGBA8 && c < 3) ? srgb[p[c]] : (float)p[c] / 255.0f;
 }
-
-static float lerp(float x, float y, float s) { return x + s * (y - x); }
 
 static void axis(float u, uint32_t dim, int wrap, uint32_t* i0, uint32_t* i1, float* f)
 {
@@ -254,7 +139,7 @@ typedef struct {
     float m_ConstRoughness, m_ConstMetallic;
 } MtMaterialData;
 
-/* limits: as gr_gbuffer's (15 values) + numTextures.  gbuffer: uint32[H*W*4]; motion: float[H*W*2] (before the fp16 store);
+/* limits: ms_decode's (15 values) + numTextures.  gbuffer: uint32[H*W*4]; motion: float[H*W*2] (before the fp16 store);
  * aniso (optional): uint8[H*W*4], the N of the albedo, normal, metallic-roughness and emissive sample of each written pixel
  * (0: not sampled).  Pixels without a texel, or whose chain leaves a buffer or the table, are left as they are. */
 void mt_gbuffer(const OrcBasePassConstants* k, const OrcBasePassInstanceConstants* instances, const OrcMeshData* meshData,
@@ -264,39 +149,16 @@ void mt_gbuffer(const OrcBasePassConstants* k, const OrcBasePassInstanceConstant
 {
     float srgb[256];
     mt_srgb_table(srgb);
+    const MsBuffers b = { instances, meshData, meshlets, vertices, vertexIds, triangles };
     const uint32_t W = k->m_OutputResolution[0], H = k->m_OutputResolution[1];
-    const float halfW = 0.5f * (float)W, halfH = 0.5f * (float)H;
-    const uint64_t numInstances = limits[0], numMeshes = limits[1], numMeshlets = limits[2], numVertices = limits[3],
-                   numVertexIds = limits[4], numTriangles = limits[5], numMaterials = limits[6], numTextures = limits[15];
-    const uint64_t* recordCapacity = limits + 7;
-    const uint64_t* listCapacity = limits + 11;
+    const uint64_t numTextures = limits[15];
     for (uint32_t py = 0; py < H; ++py)
         for (uint32_t px = 0; px < W; ++px) {
             const uint64_t i = (uint64_t)py * W + px;
-            if (!vis[i]) continue;
-            const uint32_t payload = (uint32_t)vis[i];
-            const uint32_t slot = payload >> 30, v = (payload >> 7) & 0x7FFFFFu, t = payload & 127u;
-            if (v >= listCapacity[slot]) continue;
-            const uint32_t e = lists[slot][v], g = e >> 5, lane = e & 31u;
-            if (g >= recordCapacity[slot]) continue;
-            const OrcMeshletAmplificationData* rec = &records[slot][g];
-            if (rec->m_InstanceConstIdx >= numInstances) continue;
-            const OrcBasePassInstanceConstants* inst = &instances[rec->m_InstanceConstIdx];
-            if (inst->m_MeshDataIdx >= numMeshes || inst->m_MaterialDataIdx >= numMaterials) continue;
-            const uint32_t lodIdx = rec->m_MeshLOD < ORC_MAX_LODS ? rec->m_MeshLOD : ORC_MAX_LODS - 1;
-            const OrcMeshLODData* lod = &meshData[inst->m_MeshDataIdx].m_MeshLODDatas[lodIdx];
-            const uint64_t mi = (uint64_t)lod->m_MeshletDataBufferIdx + rec->m_MeshletGroupOffset + lane;
-            if (mi >= numMeshlets) continue;
-            const OrcMeshletData* ml = &meshlets[mi];
-            uint32_t nv = ml->m_VertexAndTriangleCount & 0xFFu;
-            const uint32_t nt = (ml->m_VertexAndTriangleCount >> 8) & 0xFFu;
-            if (nv > 64u) nv = 64u;
-            if (t >= nt || (uint64_t)ml->m_MeshletIndexIDsBufferIdx + nt > numTriangles || (uint64_t)ml->m_MeshletVertexIDsBufferIdx + nv > numVertexIds) continue;
-            const uint32_t packed = triangles[ml->m_MeshletIndexIDsBufferIdx + t];
-            const uint32_t idx[3] = { packed & 0xFFu, (packed >> 8) & 0xFFu, (packed >> 16) & 0xFFu };
-            if (idx[0] >= nv || idx[1] >= nv || idx[2] >= nv) continue;
+            MsTriangle T;
+            if (!vis[i] || !ms_decode(k, &b, records, lists, limits, (uint32_t)vis[i], &T)) continue;
             MtMaterialData mat;
-            memcpy(&mat, materials + (uint64_t)inst->m_MaterialDataIdx * sizeof mat, sizeof mat);
+            memcpy(&mat, materials + (uint64_t)T.inst->m_MaterialDataIdx * sizeof mat, sizeof mat);
             const MtTexture* tex[4] = { 0, 0, 0, 0 };
             int ok = 1;
             for (int c = 0; c < 4; ++c) {
@@ -306,55 +168,27 @@ void mt_gbuffer(const OrcBasePassConstants* k, const OrcBasePassInstanceConstant
                 tex[c] = &textures[d];
             }
             if (!ok) continue;
-            float sx[3], sy[3], w[3], prev[3][3], N[3][3], wp[3][3], uv[3][2];
+            float N[3][3], uv[3][2];
             for (int j = 0; j < 3; ++j) {
-                const uint32_t vid = vertexIds[ml->m_MeshletVertexIDsBufferIdx + idx[j]];
-                if (vid >= numVertices) { ok = 0; break; }
-                const float* pos = vertices[vid].m_Position;
-                float c[4];
-                mul_point3(pos, &inst->m_WorldMatrix, wp[j]);
-                mul_point_4(wp[j], &k->m_WorldToClip, c);
-                w[j] = c[3];
-                sx[j] = fmaf(c[0] / c[3], halfW, halfW);
-                sy[j] = fmaf(-(c[1] / c[3]), halfH, halfH);
-                mul_point3(pos, &inst->m_PrevWorldMatrix, prev[j]);
-                vertex_normal(vertices[vid].m_PackedNormal, &inst->m_WorldMatrix, N[j]);
-                uv[j][0] = mt_half_to_float(vertices[vid].m_TexCoord[0]);
-                uv[j][1] = mt_half_to_float(vertices[vid].m_TexCoord[1]);
+                vertex_normal(T.vtx[j]->m_PackedNormal, T.inst->m_WorldMatrix.m, N[j]);
+                uv[j][0] = half_to_float(T.vtx[j]->m_TexCoord[0]);
+                uv[j][1] = half_to_float(T.vtx[j]->m_TexCoord[1]);
             }
-            if (!ok) continue;
             const float cx = (float)px + 0.5f, cy = (float)py + 0.5f;
-            const float area = edge(sx[0], sy[0], sx[1], sy[1], sx[2], sy[2]);
-            const float sgn = area < 0.0f ? -1.0f : 1.0f;
             /* point 0: the centre; 1: (cx + 1, cy); 2: (cx, cy + 1) */
-            float q[3][3], s[3], tc[3][2], pw[3][3];
+            float q[3][3], s[3], tc[3][2], pw[3][3], n[3];
             for (int p = 0; p < 3; ++p) {
-                const float x = p == 1 ? cx + 1.0f : cx, y = p == 2 ? cy + 1.0f : cy;
-                const float e0 = sgn * edge(sx[1], sy[1], sx[2], sy[2], x, y);
-                const float e1 = sgn * edge(sx[2], sy[2], sx[0], sy[0], x, y);
-                const float e2 = sgn * edge(sx[0], sy[0], sx[1], sy[1], x, y);
-                q[p][0] = e0 / w[0]; q[p][1] = e1 / w[1]; q[p][2] = e2 / w[2];
-                s[p] = (q[p][0] + q[p][1]) + q[p][2];
-                for (int c = 0; c < 2; ++c) tc[p][c] = fmaf(q[p][2], uv[2][c], fmaf(q[p][1], uv[1][c], q[p][0] * uv[0][c])) / s[p];
-                for (int c = 0; c < 3; ++c) pw[p][c] = fmaf(q[p][2], wp[2][c], fmaf(q[p][1], wp[1][c], q[p][0] * wp[0][c])) / s[p];
+                s[p] = ms_weights(&T, p == 1 ? cx + 1.0f : cx, p == 2 ? cy + 1.0f : cy, q[p]);
+                for (int c = 0; c < 2; ++c) tc[p][c] = ms_interp(q[p], s[p], uv[0][c], uv[1][c], uv[2][c]);
+                for (int c = 0; c < 3; ++c) pw[p][c] = ms_interp(q[p], s[p], T.world[0][c], T.world[1][c], T.world[2][c]);
             }
-            const float q0 = q[0][0], q1 = q[0][1], q2 = q[0][2], s0 = s[0];
-            float P[3], clip[4], n[3];
-            for (int c = 0; c < 3; ++c) P[c] = fmaf(q2, prev[2][c], fmaf(q1, prev[1][c], q0 * prev[0][c])) / s0;
-            mul_point_4(P, &k->m_PrevWorldToClip, clip);
-            float mx = 0.0f, my = 0.0f;
-            if (clip[3] > 0.0f) {
-                const float ux = (clip[0] / clip[3]) * 0.5f + 0.5f, uy = (clip[1] / clip[3]) * -0.5f + 0.5f;
-                mx = ux * (float)W - cx;
-                my = uy * (float)H - cy;
-            }
-            motion[2 * i] = mx;
-            motion[2 * i + 1] = my;
-            for (int c = 0; c < 3; ++c) n[c] = fmaf(q2, N[2][c], fmaf(q1, N[1][c], q0 * N[0][c])) / s0;
+            ms_motion(k, &T, q[0], s[0], cx, cy, motion + 2 * i);
+            for (int c = 0; c < 3; ++c) n[c] = ms_interp(q[0], s[0], N[0][c], N[1][c], N[2][c]);
             float debugValue = 0.0f;
-            if (k->m_DebugMode == 2u) debugValue = quick_random_float(rec->m_InstanceConstIdx);
-            else if (k->m_DebugMode == 3u) debugValue = quick_random_float(rec->m_MeshletGroupOffset + lane);
-            else if (k->m_DebugMode == 12u) debugValue = (float)rec->m_MeshLOD / 255.0f;
+            uint32_t instanceSeed = T.rec->m_InstanceConstIdx, meshletSeed = T.rec->m_MeshletGroupOffset + T.lane;
+            if (k->m_DebugMode == 2u) debugValue = quick_random_float(&instanceSeed);
+            else if (k->m_DebugMode == 3u) debugValue = quick_random_float(&meshletSeed);
+            else if (k->m_DebugMode == 12u) debugValue = (float)T.rec->m_MeshLOD / 255.0f;
             const float duvdx[2] = { tc[1][0] - tc[0][0], tc[1][1] - tc[0][1] }, duvdy[2] = { tc[2][0] - tc[0][0], tc[2][1] - tc[0][1] };
             /* GetCommonGBufferParams */
             float smp[4][4] = { { 1.0f, 1.0f, 1.0f, 1.0f }, { 0.5f, 0.5f, 1.0f, 0.0f }, { 0.0f, 1.0f, 0.0f, 0.0f }, { 1.0f, 1.0f, 1.0f, 0.0f } };
@@ -367,7 +201,7 @@ void mt_gbuffer(const OrcBasePassConstants* k, const OrcBasePassInstanceConstant
             if (tex[1]) {
                 const float x = 2.0f * smp[1][0] - 1.0f, y = 2.0f * smp[1][1] - 1.0f;
                 const float un[3] = { x, y, sqrtf(1.0f - fmaf(y, y, x * x)) };
-                float dp1[3], dp2[3], m2[3], inv0[3], inv1[3], tv[3], bv[3], T[3], B[3], r[3];
+                float dp1[3], dp2[3], m2[3], inv0[3], inv1[3], tv[3], bv[3], Tn[3], B[3], r[3];
                 for (int c = 0; c < 3; ++c) { dp1[c] = pw[1][c] - pw[0][c]; dp2[c] = pw[2][c] - pw[0][c]; }
                 cross3(dp1, dp2, m2);
                 cross3(dp2, m2, inv0);
@@ -376,9 +210,9 @@ void mt_gbuffer(const OrcBasePassConstants* k, const OrcBasePassInstanceConstant
                     tv[c] = fmaf(duvdy[0], inv1[c], duvdx[0] * inv0[c]);
                     bv[c] = fmaf(duvdy[1], inv1[c], duvdx[1] * inv0[c]);
                 }
-                normalize3(tv, T);
+                normalize3(tv, Tn);
                 normalize3(bv, B);
-                for (int c = 0; c < 3; ++c) r[c] = fmaf(un[2], n[c], fmaf(un[1], B[c], un[0] * T[c]));
+                for (int c = 0; c < 3; ++c) r[c] = fmaf(un[2], n[c], fmaf(un[1], B[c], un[0] * Tn[c]));
                 normalize3(r, normal);
             }
             gbuffer[4 * i] = pack_rgba8(mat.m_ConstAlbedo[0] * smp[0][0], mat.m_ConstAlbedo[1] * smp[0][1], mat.m_ConstAlbedo[2] * smp[0][2], debugValue);

@@ -25,84 +25,16 @@
  *   A zero scene luminance makes the scale +inf: a nonzero colour becomes +inf, which the curve turns into NaN (inf * (1 / inf));
  *   a zero colour is 0 * inf = NaN at once.  Both are stored as bytes 0, 0, 0, 255.
  */
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "ref_formats.h"
+#include "ref_soft_math.h"
 
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static float saturate(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
-
-/* ---- the R11G11B10_FLOAT load ------------------------------------------------------------------------------------------ */
-float pr_unpack_ufloat(uint32_t c, uint32_t mbits)
-{
-    const uint32_t e = c >> mbits, m = c & ((1u << mbits) - 1u);
-    if (e == 0u) return (float)m * (1.0f / (float)(1u << (14u + mbits)));
-    return float_of((e == 31u ? 0x7F800000u : (e + 112u) << 23) | m << (23u - mbits));
-}
-
-static void unpack_r11g11b10(uint32_t w, float rgb[3])
-{
-    rgb[0] = pr_unpack_ufloat(w & 0x7FFu, 6); rgb[1] = pr_unpack_ufloat((w >> 11) & 0x7FFu, 6); rgb[2] = pr_unpack_ufloat(w >> 22, 5);
-}
-
-/* ---- software log2 for x > 0 ---------------------------------------------------------------------------------------------
- * x = 2^k * m with m in [sqrt(1/2), sqrt(2)): the bits are split at 0x3F3504F3 (a subnormal x is scaled by 2^24 first, exact).
- * f = m - 1 in [-0.29290, 0.41422) is exact (Sterbenz).  log2(1 + f) = f * P(f), P the degree-9 interpolant of log2(1 + f) / f
- * at the Chebyshev nodes of that interval, coefficients rounded to binary32; the result is fmaf(f, P, (float)k).
- * ERROR, absolute, of f * P(f) against log2(1 + f):
- *   truncation, coefficient rounding included (the polynomial in exact arithmetic on 4001 points): 9.35e-9 = 0.314 * 2^-25;
- *   Horner    : every fmaf rounds once, by at most half an ulp of its result; the error of partial j reaches the value times
- *               |f|^(j+1), |f| <= 0.41422.  The partials lie in p0 [1.207, 1.708) p1 [0.568, 0.903) p2 [0.368, 0.620)
- *               p3 [0.271, 0.473) p4 [0.214, 0.383) p5 [0.177, 0.322) p6 [0.149, 0.280) p7 [0.133, 0.255) p8 [0.140, 0.217),
- *               half ulps 2^-24, 2^-25, 2^-25, 2^-26 (p3 .. p7), 2^-27: sum (0.8284 + 0.1716 + 0.0711 + 0.0147 + 0.0061 +
- *               0.0025 + 0.0010 + 0.0004 + 0.0001) * 2^-25 = 1.096 * 2^-25;
- *   last fmaf : rounds the result r once: half an ulp of r, at most 2^-24 * |r|;
- *   bound     : |pr_log2(x) - log2(x)| <= PR_LOG2_BOUND + 2^-24 * |pr_log2(x)| with PR_LOG2_BOUND = 1.45 * 2^-25 (4.32e-8)
- *               >= (0.314 + 1.096) * 2^-25.  f = 0 gives exactly k: powers of two are exact. */
-static const float kLog2C[10] = { 0x1.715476p+0f, -0x1.715470p-1f, 0x1.ec70aap-2f, -0x1.715a70p-2f, 0x1.277a52p-2f,
-                                  -0x1.eab7a8p-3f, 0x1.a38c64p-3f, -0x1.87f6aap-3f, 0x1.7a63c4p-3f, -0x1.b84fe0p-4f };
-const double PR_LOG2_BOUND = 1.45 * 0x1p-25;
-
-float pr_log2(float x)
-{
-    uint32_t u = bits_of(x);
-    if (u == 0x7F800000u) return x;
-    int bias = -127;
-    if (u < 0x00800000u) { u = bits_of(x * 0x1p24f); bias = -151; }
-    u += 0x3F800000u - 0x3F3504F3u;
-    const int k = (int)(u >> 23) + bias;
-    const float f = float_of((u & 0x007FFFFFu) + 0x3F3504F3u) - 1.0f;
-    float p = kLog2C[9];
-    for (int j = 8; j >= 0; --j) p = fmaf(p, f, kLog2C[j]);
-    return fmaf(f, p, (float)k);
-}
-
-/* ---- software exp2, either sign ------------------------------------------------------------------------------------------
- * i = rintf(x), f = x - i in [-0.5, 0.5].  EXACT on both sides of zero: for |x| < 0.5, i = 0 and f = x; otherwise i != 0,
- * x and i are both multiples of ulp(x), and |f| <= 0.5 <= |x|, so f is a multiple of ulp(x) no larger than x: representable.
- * (The lighting pass's x - ceilf(x) is exact for x <= 0 only: for 0 < x < 0.5 it is x - 1, which needs more bits than x has.)
- * 2^f = 1 + f * g(f), g the degree-5 interpolant of (2^f - 1) / f at the Chebyshev nodes of [-0.5, 0.5], coefficients rounded
- * to binary32; the result is ldexpf(p, i), exact unless subnormal.  i is clamped to [-300, 300] before the conversion so that
- * NaN and huge arguments are defined (a NaN p stays NaN; 2^300 p overflows to +inf; 2^-300 p is 0).
- * ERROR, absolute, of p against 2^f in [0.7071, 1.4143] (the result scales both by 2^i):
- *   truncation, coefficient rounding included: 6.96e-9 = 0.234 * 2^-25;
- *   Horner    : partials p0 [0.707, 1.415) p1 [0.585, 0.829) p2 [0.214, 0.271) p3 [0.0510, 0.0607) p4 [0.00898, 0.01033)
- *               p5 [0.00126, 0.00142), half ulps 2^-24, 2^-25, 2^-26 (p2 reaches 0.27 > 0.25), 2^-29, 2^-31, 2^-34, each
- *               reaching p times |f|^j <= 2^-j: (2 + 0.5 + 0.125 + 0.0078 + 0.0010 + 0.0001) * 2^-25 = 2.634 * 2^-25;
- *   bound     : PR_EXP2_BOUND = 2.9 * 2^-25 (8.64e-8) >= (0.234 + 2.634) * 2^-25, times 2^i.  f = 0 gives exactly 1. */
-static const float kExp2C[7] = { 0x1.000000p+0f, 0x1.62e430p-1f, 0x1.ebfbe0p-3f, 0x1.c6af6cp-5f, 0x1.3b2a54p-7f, 0x1.5f0890p-10f, 0x1.44138ap-13f };
-const double PR_EXP2_BOUND = 2.9 * 0x1p-25;
-
+/* ---- the load of tests/ref_formats.h and the software log2 and exp2 of tests/ref_soft_math.h (which derives the two bounds)
+ * under this library's names ------------------------------------------------------------------------------------------------ */
+float pr_unpack_ufloat(uint32_t c, uint32_t mbits) { return unpack_ufloat(c, mbits); }
+const double PR_LOG2_BOUND = LOG2_SOFT_BOUND, PR_EXP2_BOUND = EXP2_SIGNED_BOUND;
+float pr_log2(float x) { return log2_soft(x); }
+float pr_exp2(float x) { return exp2_signed(x); }
 float pr_exp2_reduced(float x) { return x - rintf(x); }
-
-float pr_exp2(float x)
-{
-    const float i = rintf(x), f = x - i;
-    float p = kExp2C[6];
-    for (int j = 5; j >= 0; --j) p = fmaf(p, f, kExp2C[j]);
-    return ldexpf(p, (int)fminf(fmaxf(i, -300.0f), 300.0f));
-}
 
 /* ---- pow(x, 1 / 2.2f) ----------------------------------------------------------------------------------------------------
  * y = kInvGamma * l, l = pr_log2(x) <= 0 on (0, 1].  ERROR of the result on (0, 1], relative: the exponent y is off by at most
@@ -114,7 +46,7 @@ float pr_exp2(float x)
 static const float kInvGamma = 1.0f / 2.2f;                                  /* 0x1.d1745cp-2f */
 const double PR_POW_BOUND_A = 1.37e-7, PR_POW_BOUND_B = 3.8e-8;
 
-float pr_pow_gamma(float x) { return x > 0.0f ? pr_exp2(kInvGamma * pr_log2(x)) : 0.0f; }
+float pr_pow_gamma(float x) { return pow_soft(x, kInvGamma); }
 
 /* ---- the histogram ------------------------------------------------------------------------------------------------------- */
 static const float kLumR = 0.212671f, kLumG = 0.715160f, kLumB = 0.072169f;

@@ -10,7 +10,7 @@
  * a box whose triangle sm_tri_hit accepts; tests/test_shadowmask_ref.py demands zero differing texels.
  *
  * CONVENTION.  IEEE binary32, no contraction, fmaf only where written, / and sqrtf correctly rounded.
- *   worldPosition, UnpackGBuffer's normal, dot3, normalize: as tests/lighting_ref.c (csrc/k_deferredlighting.hip) states them;
+ *   worldPosition as tests/lighting_ref.c (csrc/k_deferredlighting.hip) states it; UnpackGBuffer's normal: tests/ref_formats.h unpack_oct;
  *   cross(a, b) = (fma(a.y, b.z, -(a.z * b.y)), fma(a.z, b.x, -(a.x * b.z)), fma(a.x, b.y, -(a.y * b.x)));
  *   noise:    (float)byte / 255.0f of the texel's R and G bytes at (px % 128, py % 128), + m_NoisePhase, then fmod(x, 1) = x - truncf(x);
  *   MapToCone: offset = 2 * s - 1; both 0: n.  |ox| > |oy|: r = ox, theta = RN(pi / 4) * (oy / ox); else r = oy,
@@ -34,9 +34,7 @@
  *             intervals are intersected with [0, inf).  Node boxes are already padded (include/trhip.h);
  *   output:   depth == 0.0f: u1 = 0x7BFF (65504), u0 kept.  Else u0 = occluded ? 0 : 255, u1 = binary16 round-to-nearest-even of
  *             length(worldPosition - m_CameraPosition) (overflow gives infinity, every NaN is stored as 0x7E00). */
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "ref_formats.h"
 
 typedef struct { float x, y, z; } F3;
 typedef struct { float lo[3]; uint32_t skip; float hi[3]; uint32_t leaf; } SmNode;
@@ -68,12 +66,10 @@ typedef struct
 #define SM_INNER 0xFFFFFFFFu
 static const float kSlack = 0x1p-18f, kTlasPad = 0x1p-12f;
 
-static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+/* the by-value forms of ref_base.h's dot3, cross3 and normalize3: the same operations on an F3 */
 static float dot3f(F3 a, F3 b) { return fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)); }
 static F3 cross3f(F3 a, F3 b) { F3 r = { fmaf(a.y, b.z, -(a.z * b.y)), fmaf(a.z, b.x, -(a.x * b.z)), fmaf(a.x, b.y, -(a.y * b.x)) }; return r; }
-static F3 normalize3(F3 v) { const float len = sqrtf(dot3f(v, v)); F3 r = { v.x / len, v.y / len, v.z / len }; return r; }
-static float saturatef(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+static F3 normalize3f(F3 v) { const float len = sqrtf(dot3f(v, v)); F3 r = { v.x / len, v.y / len, v.z / len }; return r; }
 static float sel(F3 v, int k) { return k == 0 ? v.x : (k == 1 ? v.y : v.z); }
 
 /* ---- sinSoft / cosSoft of csrc/soft_math.hip.h (derivation: tests/gtao_ref.c) ------------------------------------------------ */
@@ -101,22 +97,7 @@ static float sincos_soft(float x, int quarter)
     return (q & 2) ? -v : v;
 }
 
-/* binary32 -> binary16, round to nearest even, overflow to infinity, every NaN to 0x7E00 */
-uint16_t sm_half_bits(float f)
-{
-    const uint32_t u = bits_of(f), sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;
-    if (a > 0x7F800000u) return 0x7E00u;
-    if (a >= 0x47800000u) return (uint16_t)(sign | 0x7C00u);                  /* >= 65536, or infinite; 65520..65536 round up below */
-    if (a < 0x33000000u) return (uint16_t)sign;                               /* < 2^-25: zero (2^-25 itself ties to even = 0, handled below) */
-    const int e = (int)(a >> 23) - 127;
-    uint32_t m = (a & 0x007FFFFFu) | 0x00800000u;                             /* 24-bit significand */
-    int shift = e >= -14 ? 13 : 13 + (-14 - e);                               /* bits dropped */
-    if (shift > 24) return (uint16_t)sign;
-    const uint32_t kept = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-    uint32_t h = e >= -14 ? ((uint32_t)(e + 15) << 10) + (kept - 0x400u) : kept;
-    if (rem > half || (rem == half && (h & 1u))) ++h;                         /* a carry moves into the exponent, up to 0x7C00 */
-    return (uint16_t)(sign | h);
-}
+uint16_t sm_half_bits(float f) { return float_to_half(f); }
 
 /* ---- the object-from-world 3x4 of one instance: rows r0 r1 r2 r3 of p_object = (p_world, 1) * M ------------------------------ */
 void sm_object_from_world(const float* w, float* out)
@@ -247,16 +228,6 @@ int sm_tri_hit(F3 v0, F3 v1, F3 v2, const SmRay* r, float tmin, float tmax)
 }
 
 /* ---- one texel's ray: 0 for a far texel, else origin and direction ------------------------------------------------------------- */
-static F3 unpack_normal(uint32_t w)
-{
-    const float fx = ((float)(w & 0xFFFFu) * (1.0f / 65535.0f)) * 2.0f - 1.0f, fy = ((float)(w >> 16) * (1.0f / 65535.0f)) * 2.0f - 1.0f;
-    F3 n = { fx, fy, (1.0f - fabsf(fx)) - fabsf(fy) };
-    const float t = saturatef(-n.z);
-    n.x += n.x >= 0.0f ? -t : t;
-    n.y += n.y >= 0.0f ? -t : t;
-    return normalize3(n);
-}
-
 static float fmod1(float x) { return x - truncf(x); }
 
 static F3 map_to_cone(float sx, float sy, F3 n, float radius)
@@ -268,7 +239,7 @@ static F3 map_to_cone(float sx, float sy, F3 n, float radius)
     else { r = oy; theta = 0x1.921fb6p+0f * (1.0f - 0.5f * (ox / oy)); }
     const float ux = (radius * r) * sincos_soft(theta, 1), uy = (radius * r) * sincos_soft(theta, 0);
     const F3 up = { fabsf(n.z) < 0.99999f ? 0.0f : 1.0f, 0.0f, fabsf(n.z) < 0.99999f ? 1.0f : 0.0f };
-    const F3 t0 = normalize3(cross3f(up, n)), t1 = cross3f(n, t0);
+    const F3 t0 = normalize3f(cross3f(up, n)), t1 = cross3f(n, t0);
     const F3 d = { (n.x + ux * t0.x) + uy * t1.x, (n.y + ux * t0.y) + uy * t1.y, (n.z + ux * t0.z) + uy * t1.z };
     return d;
 }
@@ -282,12 +253,13 @@ int sm_texel_ray(const SmConsts* k, uint32_t px, uint32_t py, float depth, const
     float h[4];
     for (int j = 0; j < 4; ++j) h[j] = fmaf(depth, m[8 + j], fmaf(cy, m[4 + j], cx * m[j])) + m[12 + j];
     const F3 wp = { h[0] / h[3], h[1] / h[3], h[2] / h[3] };
-    const F3 n = unpack_normal(g[1]);
+    float n[3];
+    unpack_oct(g[1], n);
     const uint32_t texel = noise[(py % 128u) * 128u + (px % 128u)];
     const float sx = fmod1((float)(texel & 0xFFu) / 255.0f + k->noisePhase), sy = fmod1((float)((texel >> 8) & 0xFFu) / 255.0f + k->noisePhase);
     const F3 light = { k->light[0], k->light[1], k->light[2] };
-    const F3 d = normalize3(map_to_cone(sx, sy, light, k->tanSunAngularRadius));
-    origin[0] = wp.x + n.x * k->rayStartOffset; origin[1] = wp.y + n.y * k->rayStartOffset; origin[2] = wp.z + n.z * k->rayStartOffset;
+    const F3 d = normalize3f(map_to_cone(sx, sy, light, k->tanSunAngularRadius));
+    origin[0] = wp.x + n[0] * k->rayStartOffset; origin[1] = wp.y + n[1] * k->rayStartOffset; origin[2] = wp.z + n[2] * k->rayStartOffset;
     direction[0] = d.x; direction[1] = d.y; direction[2] = d.z;
     world[0] = wp.x; world[1] = wp.y; world[2] = wp.z;
     return 1;

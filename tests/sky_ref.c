@@ -12,12 +12,12 @@
  *               dot3 = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)), normalize(v) = v / sqrtf(dot3(v, v));
  *   angles    : cosTheta = fminf(fmaxf(V.y, 0), 1) (a NaN gives 0); cosGamma = dot3(V, m_SunLightDir); gamma = sk_acos(cosGamma)
  *               (NaN outside [-1, 1]: a view ray that meets the sun direction to the last bit can give that);
- *   exp(x)    : sk_exp2(x * 0x1.715476p+0f), sk_exp2 = the post pass's two-sided exp2 (tests/postprocess_ref.c pr_exp2), word
+ *   exp(x)    : sk_exp2(x * 0x1.715476p+0f), sk_exp2 = the two-sided exp2 of tests/ref_soft_math.h (exp2_signed), word
  *               for word; pow(b, 1.5) = b * sqrtf(b) (negative base: NaN); pow(c, 256), c > 0: eight squarings;
  *   channel   : chi = (1 + cg * cg) / pow((1 + H * H) - ((2 * cg) * H), 1.5);
  *               hw = (1 + A * exp(B / (cosTheta + 0.01f))) * ((((C + D * exp(E * gamma)) + F * (cg * cg)) + G * chi) + I * sqrtf(cosTheta));
  *               R = (-Z) * hw; if (cg > 0) R = R + pow(cg, 256) * 0.5f;
- *   store     : R11G11B10_FLOAT per channel as tests/lighting_ref.c states it; alpha is dropped.
+ *   store     : R11G11B10_FLOAT per channel as tests/ref_formats.h states it; alpha is dropped.
  *
  * RADIOMETRIC BOUND (tests/test_sky_ref.py evaluates it per pixel and channel).  u = 2^-24.  Against the same formula in
  * binary64 from the same binary32 V, parameters and constants (0.01f, 0.9f are the binary32 numbers):
@@ -37,78 +37,19 @@
  *               S = |Z| (1 + |A e1|) sum |T| + sun, sun = 0.5 cg^256 with dsun = sun (256 u + 256 dcg / cg) + 2^-149.
  *   First order; the test multiplies the whole by 1.01 for the second-order terms it drops.
  */
-#include <math.h>
-#include <stdint.h>
 #include <stdio.h>
-#include <string.h>
 
-static uint32_t bits_of(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
-static float float_of(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-static float dot3(const float a[3], const float b[3]) { return fmaf(a[2], b[2], fmaf(a[1], b[1], a[0] * b[0])); }
+#include "ref_formats.h"
+#include "ref_soft_math.h"
 
-/* ---- the R11G11B10_FLOAT store (tests/lighting_ref.c lr_pack_ufloat, word for word) ---------------------------------- */
-uint32_t sk_pack_ufloat(float v, uint32_t mbits)
-{
-    const uint32_t shift = 23u - mbits, inf = 31u << mbits, maxFinite = inf - 1u;
-    const uint32_t u = bits_of(v);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return inf | ((1u << mbits) - 1u);
-    if (u >> 31) return 0u;
-    if (u == 0x7F800000u) return inf;
-    if (u >= 0x38800000u) {
-        const uint32_t r = u - (112u << 23);
-        const uint32_t q = (r + ((1u << (shift - 1)) - 1u) + ((r >> shift) & 1u)) >> shift;
-        return q < maxFinite ? q : maxFinite;
-    }
-    return (uint32_t)rintf(v * (float)(1u << (14u + mbits)));
-}
-uint32_t sk_pack_r11g11b10(float r, float g, float b) { return sk_pack_ufloat(r, 6) | sk_pack_ufloat(g, 6) << 11 | sk_pack_ufloat(b, 5) << 22; }
-
-/* ---- two-sided exp2 (tests/postprocess_ref.c pr_exp2; derivation and PR_EXP2_BOUND = 2.9 * 2^-25 * 2^i there) ----------- */
-static const float kExp2C[7] = { 0x1.000000p+0f, 0x1.62e430p-1f, 0x1.ebfbe0p-3f, 0x1.c6af6cp-5f, 0x1.3b2a54p-7f, 0x1.5f0890p-10f, 0x1.44138ap-13f };
-float sk_exp2(float x)
-{
-    const float i = rintf(x), f = x - i;
-    float p = kExp2C[6];
-    for (int j = 5; j >= 0; --j) p = fmaf(p, f, kExp2C[j]);
-    return ldexpf(p, (int)fminf(fmaxf(i, -300.0f), 300.0f));
-}
+/* ---- the store of tests/ref_formats.h, the two-sided exp2 and the arc cosine of tests/ref_soft_math.h (which derives
+ * SK_ACOS_BOUND) under this library's names ------------------------------------------------------------------------------- */
+uint32_t sk_pack_ufloat(float v, uint32_t mbits) { return pack_ufloat(v, mbits); }
+uint32_t sk_pack_r11g11b10(float r, float g, float b) { return pack_r11g11b10(r, g, b); }
+float sk_exp2(float x) { return exp2_signed(x); }
 static float sk_exp(float x) { return sk_exp2(x * 0x1.715476p+0f); }
-
-/* ---- software arc cosine -------------------------------------------------------------------------------------------------
- * asin(s) = s + s * z * P(z), z = s * s in [0, 0.25]; P is the degree-4 weighted least-squares fit of (asin(sqrt z) / sqrt z
- * - 1) / z at 400 Chebyshev nodes of [0, 0.25] (weight s z, so that the error of the sum is what is minimised), coefficients
- * rounded to binary32.  |s + s z P(z) - asin s| <= 0.038 * 2^-24 on 400 001 points, coefficients as rounded.
- *   |x| <= 0.5: z = x * x, t = fmaf(x * z, P, x), result RN(pi / 2) - t;
- *   |x| >  0.5: z = (1 - |x|) * 0.5 (exact: Sterbenz, then a power of two), s = sqrtf(z) <= 0.5, t = fmaf(s * z, P, s), r = 2 t
- *               (exact); x > 0: r, else RN(pi) - r.  acos(1) = 0 and acos(-1) = RN(pi) exactly; !(|x| <= 1) gives NaN.
- * ERROR, absolute, in units of 2^-24.  t: its fmaf rounds once, t <= 0.5236: 0.5; the product s * z carries two roundings and
- * multiplies P <= 0.1875, the term is <= 0.0236: 0.047; P's four fmaf round by <= 2^-26 together, times |s z| <= 0.125: 0.03;
- * truncation 0.038: t within 0.62.  For |x| > 0.5 add sqrtf's half ulp 2^-26 times asin' <= 1.1547: 0.289, and P read at z
- * rather than RN(s)^2, 2^-23 relative: 0.054; t within 0.963, r within 1.93.  The last subtraction rounds by <= 2^-23 (results
- * in [2, pi]): 2; RN(pi / 2) is off by 0.733 and RN(pi) by 1.467.  So |x| <= 0.5: 3.36; x > 0.5: 1.93; x < -0.5: 5.4.
- * SK_ACOS_BOUND = 5.5 * 2^-24 (3.28e-7). */
-static const float kAcosC[5] = { 0x1.555626p-3f, 0x1.32ea80p-4f, 0x1.766edcp-5f, 0x1.7b4b14p-6f, 0x1.665bcap-5f };
-const double SK_ACOS_BOUND = 5.5 * 0x1p-24;
-
-static float acos_poly(float z)
-{
-    float p = kAcosC[4];
-    for (int j = 3; j >= 0; --j) p = fmaf(p, z, kAcosC[j]);
-    return p;
-}
-
-float sk_acos(float x)
-{
-    const float a = fabsf(x);
-    if (!(a <= 1.0f)) return nanf("");
-    if (a <= 0.5f) {
-        const float z = x * x;
-        return 0x1.921fb6p+0f - fmaf(x * z, acos_poly(z), x);
-    }
-    const float z = (1.0f - a) * 0.5f, s = sqrtf(z);
-    const float r = 2.0f * fmaf(s * z, acos_poly(z), s);
-    return x > 0.0f ? r : 0x1.921fb6p+1f - r;
-}
+const double SK_ACOS_BOUND = ACOS_SOFT_BOUND;
+float sk_acos(float x) { return acos_soft(x); }
 
 /* max |sk_acos - acos| over every binary32 whose bits lie in [lo, hi] (one sign); *at receives the argument */
 double sk_acos_max_error(uint32_t lo, uint32_t hi, float* at)

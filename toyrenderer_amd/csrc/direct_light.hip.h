@@ -11,7 +11,7 @@
 namespace dl
 {
 
-// exp2 for x <= 0; coefficients and error analysis: tests/lighting_ref.c (kExp2C)
+// exp2 for x <= 0; coefficients and error analysis: tests/lighting_ref.c (kExp2CeilC)
 __device__ __forceinline__ float exp2Soft(float x)
 {
 #ifdef TR_LIGHTING_EXPERIMENT_HW_EXP2          // negative control only (profiles/lighting/): the hardware's v_exp_f32

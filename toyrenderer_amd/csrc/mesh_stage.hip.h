@@ -3,7 +3,7 @@
 // them, how a visible-list entry leads to its meshlet, how a vertex gets to the screen, what the edge function is, and
 // what a visibility texel means.  GBufferMotion and GBufferA are bit-exact because the resolve recomputes the winning
 // triangle with the raster's operations; they are the raster's operations because both call these.
-// Restated independently, on purpose, in oracle/tr_oracle.c, tests/visibility_ref.c and tests/gbuffer_ref.c.
+// Restated independently, on purpose, in oracle/tr_oracle.c and tests/ref_mesh_stage.h (for the C references of tests/).
 #pragma once
 
 #include "cull_math.hip.h"

@@ -3,13 +3,13 @@
 // and device: the clear command (trhip_core.cpp) and the lighting kernels (k_deferredlighting.hip) store the same words; the
 // passes behind LightingOutput (k_postprocess.hip) load them.
 //
-// CONVENTION (restated in tests/lighting_ref.c), per channel: a NaN gives exponent and mantissa all ones;
+// CONVENTION (restated in tests/ref_formats.h), per channel: a NaN gives exponent and mantissa all ones;
 // negative values and -0 give 0; +inf gives the infinity pattern; a finite value above the largest finite (65024 with 6
 // mantissa bits, 64512 with 5) gives that largest finite; everything else rounds to nearest, ties to even, subnormals
 // (below 2^-14) included.
 // The load is exact (every value of the format is a binary32 number): exponent 0 gives mantissa * 2^(-14 - MBITS), subnormals
 // included; exponent 31 gives +inf for mantissa 0 and otherwise a NaN that carries the mantissa in its top bits; everything
-// else (1 + mantissa / 2^MBITS) * 2^(exponent - 15).  pack(unpack(c)) == c for every code (restated in tests/postprocess_ref.c).
+// else (1 + mantissa / 2^MBITS) * 2^(exponent - 15).  pack(unpack(c)) == c for every code (restated in tests/ref_formats.h).
 #pragma once
 
 #include <cstdint>

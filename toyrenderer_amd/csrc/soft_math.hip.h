@@ -1,7 +1,7 @@
 // soft_math.hip.h -- log2, a two-sided exp2 and an arc cosine in software, for the passes behind LightingOutput
-// (k_postprocess.hip) and the sky pass (k_sky.hip; tests/sky_ref.c restates acosSoft word for word as sk_acos).
-// v_log_f32 and v_exp_f32 are good to 1 ulp only and cannot be restated on a CPU; these can, and tests/postprocess_ref.c
-// restates them word for word (pr_log2, pr_exp2) next to the derivation of the coefficients and of the error bounds.  The
+// (k_postprocess.hip) and the sky pass (k_sky.hip).  v_log_f32 and v_exp_f32 are good to 1 ulp only and cannot be restated
+// on a CPU; these can, and tests/ref_soft_math.h restates the three word for word (log2_soft, exp2_signed, acos_soft) next
+// to the derivation of the coefficients and of the error bounds, once for every C reference under tests/.  The
 // lighting pass keeps its own exp2Soft (direct_light.hip.h): that one is proven for x <= 0 only and its words must not move.
 //
 //   log2Soft(x), x > 0 (the callers test; +inf gives +inf): a subnormal x is first scaled by 2^24 (exact).  The bits are split
