@@ -188,6 +188,17 @@ int  trhost_unit_sphere(void* vertices, uint64_t vertices_bytes, uint32_t* indic
  * generation is on trhost_upload_bloom refuses a texture.  trhost_set_bloom(0, ...) switches it off.  trhost_download_bloom
  * waits and copies one mip ((W >> mip) x (H >> mip) words); trhost_get_bloom_consts copies the 16 bytes of BloomConsts of pass
  * `pass` < 2 * (nbMips - 1) of the last frame, downsamples first.
+ * Temporal anti-aliasing (TAARenderer.cpp; off by default).  trhost_set_taa(1, minBlend, maxSampleCount) (0.1 and 64 are usual)
+ * makes View::Update jitter the projection by Graphic::ComputeCurrentJitterOffset's Halton offset (Scene.cpp:113-131) and schedules
+ * TAARenderer between AdaptLuminanceRenderer and PostProcessRenderer: one "taa_CS_TemporalResolve" dispatch (csrc/k_taa.hip) from
+ * LightingOutput, the depth buffer, the motion target and the history of the frame before into the other history texture and
+ * g_AntiAliasedLightingOutput, which "postprocess_PS_PostProcess" then reads at t0; bloom and the histogram keep reading
+ * LightingOutput.  m_PrevWorldToClip is then last frame's jittered world-to-clip.  The first frame with it on resets the history,
+ * and so does the frame after trhost_reset_taa_history.  Refused: post-processing off; minBlend outside [0, 1]; maxSampleCount
+ * outside [1, 65504].  trhost_set_taa(0, ...) switches it off.  trhost_download_anti_aliased_output waits and copies the W x H
+ * words, trhost_download_taa_history the W x H x 4 binary16 of the history texture written last (xyz colour, w sample count),
+ * trhost_get_taa_consts the 32 bytes of TAAConsts of the last frame and its current and previous jitter offsets in pixels (2 floats
+ * each; any pointer may be NULL); all three refuse if the resolve did not run in the last frame.
  * The sky pass (SkyRenderer.cpp; off by default).  trhost_load_sky_dataset copies the Hosek-Wilkie RGB dataset, an input and not
  * part of this library: rgb = 3 x 1080 doubles (per channel 2 albedos x 10 turbidities x 6 control points x 9 parameters), rad =
  * 3 x 120 doubles; NULL unloads it and switches the pass off.  trhost_set_sky(1, turbidity, groundAlbedo) schedules SkyRenderer
@@ -223,6 +234,11 @@ int  trhost_upload_bloom(const uint32_t* words, uint64_t bytes, float strength);
 int  trhost_set_bloom(int enable, uint32_t nb_mips, float filter_radius, float strength);
 int  trhost_download_bloom(uint32_t mip, uint32_t* words, uint64_t bytes);
 int  trhost_get_bloom_consts(uint32_t pass, void* out16);
+int  trhost_set_taa(int enable, float min_blend, float max_sample_count);
+int  trhost_reset_taa_history(void);
+int  trhost_download_anti_aliased_output(uint32_t* words, uint64_t bytes);
+int  trhost_download_taa_history(void* halves, uint64_t bytes);
+int  trhost_get_taa_consts(void* out32, float* current_jitter, float* prev_jitter);
 int  trhost_load_sky_dataset(const double* rgb, const double* rad);
 int  trhost_set_sky(int enable, float turbidity, const float ground_albedo[3]);
 int  trhost_get_sky_consts(void* out256);

@@ -221,6 +221,19 @@ struct BloomConsts
 };
 static_assert(sizeof(BloomConsts) == 16 && offsetof(BloomConsts, m_InvSourceResolution) == 0 && offsetof(BloomConsts, m_FilterRadius) == 8 && offsetof(BloomConsts, m_bIsFirstDownsample) == 12, "BloomConsts");
 
+// Push constants (or b0) of "taa_CS_TemporalResolve" (k_taa.hip).  The project's own: the reference's TAARenderer hands its
+// parameters to the DLSS / FSR SDKs, which are not in its tree.
+struct TAAConsts
+{
+    Vector2U m_OutputDims;
+    Vector2 m_JitterDelta;                  // previous minus current jitter offset, in pixels
+    float m_MinBlend;                       // the least weight of the current colour
+    float m_MaxSampleCount;                 // the accumulated count's cap
+    uint32_t m_bResetHistory;               // 1: no texel's history is valid
+    uint32_t PAD0;
+};
+static_assert(sizeof(TAAConsts) == 32 && offsetof(TAAConsts, m_JitterDelta) == 8 && offsetof(TAAConsts, m_MinBlend) == 16 && offsetof(TAAConsts, m_bResetHistory) == 24, "TAAConsts");
+
 // ShaderInterop.h:146-149, 297-305: the constant buffer b0 of "sky_PS_HosekWilkieSky".  Rows A B C D E F G H I Z; the shader
 // reads .xyz, .w is written as 0.
 struct HosekWilkieSkyParameters

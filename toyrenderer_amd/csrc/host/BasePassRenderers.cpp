@@ -340,7 +340,13 @@ public:
 
     // The matrix the raster used the frame before: the reference's m_PrevWorldToClip = m_WorldToClip (Scene.cpp:116-118)
     // applied to this build's raster camera.
-    static Matrix PrevWorldToClip() { return MultiplyNoFMA(g_Scene->m_View.m_CullingPrevWorldToView, g_Scene->m_View.m_PrevViewToClip); }
+    // With TAA the matrix is View::Update's kept m_PrevWorldToClip (Scene.cpp:119): last frame's camera times last frame's jittered
+    // projection, whose jitter TAARenderer takes out again through m_JitterDelta.
+    static Matrix PrevWorldToClip()
+    {
+        if (g_Scene->IsTAAEnabled()) return g_Scene->m_View.m_PrevWorldToClip;
+        return MultiplyNoFMA(g_Scene->m_View.m_CullingPrevWorldToView, g_Scene->m_View.m_PrevViewToClip);
+    }
 
     // What the mesh stage reads wherever it runs (csrc/mesh_stage.hip.h): b0 and the geometry at t0, t1, t2, t4, t5, t6.
     // The rasters and the resolve append their own.

@@ -141,6 +141,30 @@ void Graphic::Update()
     m_LastSubmitMs = std::chrono::duration<float, std::milli>(t2 - t1).count();
 }
 
+Vector2 Graphic::ComputeCurrentJitterOffset()
+{
+    // Graphic.cpp:971-997: the Halton branch (the MSAA-8 table and the white noise are `if constexpr (false)` there)
+    auto GetJitterPhaseCount = [](uint32_t renderWidth, uint32_t displayWidth) {
+        const float kBasePhaseCount = 8.0f;
+        const float ratio = float(displayWidth) / renderWidth;
+        return (uint32_t)(kBasePhaseCount * (ratio * ratio));                // pow(x, 2.0f); render = display: 8
+    };
+    auto VanDerCorput = [](size_t base, size_t index) {
+        float ret = 0.0f;
+        float denominator = float(base);
+        while (index > 0) {
+            size_t multiplier = index % base;
+            ret += float(multiplier) / denominator;
+            index = index / base;
+            denominator *= base;
+        }
+        return ret;
+    };
+    const uint32_t phaseCount = GetJitterPhaseCount(m_RenderResolution.x, m_RenderResolution.x);
+    const uint32_t index = (m_FrameCounter % phaseCount) + 1;
+    return Vector2{ VanDerCorput(2, index) - 0.5f, VanDerCorput(3, index) - 0.5f };
+}
+
 bool Graphic::HasShader(std::string_view shaderBinName) const
 {
     return trhip_shader_exists(std::string(shaderBinName).c_str()) != 0;

@@ -103,6 +103,7 @@ public:
 
     Vector2U m_RenderResolution{ 0, 0 };
     uint32_t m_FrameCounter = 0;
+    Vector2 ComputeCurrentJitterOffset();                                     // Graphic.cpp:949-998, the Halton branch
     int m_DeviceIndex = 0;
     bool m_bPipelineStatistics = false;                                       // the base pass's statistics queries (trhost_set_pipeline_statistics); off by default
     bool m_bEnableGPUTimers = true;                                          // per-renderer timer queries (RenderGraph.cpp:262-281); instrumentation only

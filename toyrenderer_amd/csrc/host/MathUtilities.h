@@ -8,6 +8,7 @@
 #include "../ShaderInterop.h"
 
 using interop::Matrix;
+using interop::Vector2;
 using interop::Vector2U;
 using interop::Vector3U;
 using interop::Vector4;

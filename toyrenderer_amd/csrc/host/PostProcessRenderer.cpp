@@ -2,7 +2,7 @@
 // PBRNeutralToneMapping and LinearToSRGB from LightingOutput into the RGBA8_UNORM back buffer, "postprocess_PS_PostProcess"
 // (csrc/k_postprocess.hip).
 //
-// Out of scope, as in the back end: TAA (the input is always LightingOutput).  The bloom texture at t2 is BloomRenderer's when
+// The input at t0 is TAARenderer's g_AntiAliasedLightingOutput when TAA is enabled, else LightingOutput (:25-27, :52).  The bloom texture at t2 is BloomRenderer's when
 // generation is on (trhost_set_bloom), else the uploaded one (trhost_upload_bloom); without either t2 stays unbound: black, the
 // reference's BlackTexture, and the strength is 0.  There is no
 // swap chain: the back buffer is a texture owned here, read back by trhost_download_back_buffer.  The full-screen triangle is a
@@ -30,6 +30,7 @@ public:
     PostProcessParameters m_LastParams{};
     bool m_bHasLastParams = false;
 
+    nvrhi::TextureHandle m_Input;                    // this frame's t0
     static nvrhi::TextureHandle BloomTexture() { return g_Scene->m_bEnableBloom ? GetGeneratedBloomTexture() : g_Scene->m_BloomTexture; }
 
     bool Setup(RenderGraph& renderGraph) override
@@ -45,7 +46,9 @@ public:
             m_BackBuffer = g_Graphic.m_NVRHIDevice->createTexture(desc);
         }
         if (BloomTexture()) renderGraph.AddExternalReadDependency(BloomTexture().Get());   // :20-23
-        renderGraph.AddExternalReadDependency(GetLightingOutput().Get());     // :29-32
+        m_Input = GetScheduledAntiAliasedLightingOutput();                    // :25-27: g_Scene->IsTAAEnabled() ? g_AntiAliasedLightingOutput : g_LightingOutput
+        if (!m_Input) m_Input = GetLightingOutput();
+        renderGraph.AddExternalReadDependency(m_Input.Get());                 // :29-32
         renderGraph.AddExternalReadDependency(g_Scene->m_LuminanceBuffer.Get());
         renderGraph.AddExternalWriteDependency(m_BackBuffer.Get());
         return true;
@@ -67,7 +70,7 @@ public:
         Graphic::ComputePassParams p;                                         // :55-73
         p.m_CommandList = commandList;
         p.m_ShaderName = "postprocess_PS_PostProcess";
-        p.m_BindingSetDesc.bindings = { Item::PushConstants(0, sizeof(passParameters)), Item::Texture_SRV(0, GetLightingOutput()),
+        p.m_BindingSetDesc.bindings = { Item::PushConstants(0, sizeof(passParameters)), Item::Texture_SRV(0, m_Input),
                                         Item::StructuredBuffer_SRV(1, g_Scene->m_LuminanceBuffer), Item::Texture_UAV(0, m_BackBuffer) };
         if (bloom) p.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(2, bloomTexture));
         p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Graphic.m_RenderResolution, 8);
@@ -92,7 +95,7 @@ bool GetLastPostProcessConsts(void* histogram16, void* adapt20, void* post24, in
 void ReleasePostProcessOutputs()
 {
     PostProcessRenderer* r = static_cast<PostProcessRenderer*>(g_PostProcessRenderer);
-    r->m_BackBuffer = nullptr;
+    r->m_BackBuffer = r->m_Input = nullptr;
     r->m_bHasLastParams = false;
     ReleaseAdaptLuminanceOutputs();
 }

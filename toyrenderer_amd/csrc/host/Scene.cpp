@@ -22,12 +22,18 @@ extern IRenderer* g_DeferredLightingRenderer;
 extern IRenderer* g_SkyRenderer;
 extern IRenderer* g_BloomRenderer;
 extern IRenderer* g_AdaptLuminanceRenderer;
+extern IRenderer* g_TAARenderer;
 extern IRenderer* g_PostProcessRenderer;
 extern IRenderer* g_GIDebugRenderer;
 extern IRenderer* g_GIRenderer;
 
 void View::Update()
 {
+    const bool bTAA = g_Scene->IsTAAEnabled();
+    m_PrevJitterOffset = m_CurrentJitterOffset;                               // Scene.cpp:113-114
+    m_CurrentJitterOffset = bTAA ? g_Graphic.ComputeCurrentJitterOffset() : Vector2{ 0.0f, 0.0f };
+    m_PrevWorldToClip = m_WorldToClip;                                        // :119
+
     // Scene.cpp:116-118: keep last frame's matrices
     m_PrevWorldToView = m_WorldToView;
     m_PrevViewToClip = m_ViewToClip;
@@ -38,7 +44,22 @@ void View::Update()
         m_ViewToClip = CreatePerspectiveFieldOfView(m_FOV, m_AspectRatio, m_ZNearP, kKindaBigNumber);
         ModifyPerspectiveMatrix(m_ViewToClip, m_ZNearP, kKindaBigNumber, GraphicConstants::kInversedDepthBuffer, GraphicConstants::kInfiniteDepthBuffer);
     }
-    // TAA jitter (:127-131) is out of scope (no TAA renderer)
+    else m_ViewToClip = m_ExplicitViewToClip;                                 // the application's, without last frame's jitter
+    if (bTAA) {                                                               // :127-131: m_ViewToClip *= CreateTranslation(2 jx / W, -2 jy / H, 0)
+        Matrix pixelOffsetMatrix{};
+        for (int i = 0; i < 4; ++i) pixelOffsetMatrix.m[i][i] = 1.0f;
+        pixelOffsetMatrix.m[3][0] = 2.0f * m_CurrentJitterOffset.x / g_Graphic.m_RenderResolution.x;
+        pixelOffsetMatrix.m[3][1] = -2.0f * m_CurrentJitterOffset.y / g_Graphic.m_RenderResolution.y;
+        m_ViewToClip = MultiplyNoFMA(m_ViewToClip, pixelOffsetMatrix);
+    }
+    m_WorldToClip = MultiplyNoFMA(m_WorldToView, m_ViewToClip);               // :133
+    if (!bTAA) m_bHasTAAHistory = false;
+    else if (!m_bHasTAAHistory) {                                             // the first frame with TAA on: nothing earlier to refer to
+        m_PrevJitterOffset = m_CurrentJitterOffset;
+        m_PrevWorldToClip = m_WorldToClip;
+        m_bHasTAAHistory = true;
+        g_Scene->m_bResetTAAHistory = true;
+    }
 
     for (int j = 0; j < 3; ++j)                                               // m_Eye (:133): see Scene.h; the sum GIRenderer.cpp's constants use
         m_Eye[j] = -(m_WorldToView.m[3][0] * m_WorldToView.m[j][0] + m_WorldToView.m[3][1] * m_WorldToView.m[j][1] + m_WorldToView.m[3][2] * m_WorldToView.m[j][2]);
@@ -310,8 +331,9 @@ void Scene::Update()
         if (m_bDeferredLighting) m_RenderGraph->AddRenderer(g_DeferredLightingRenderer);   // :497, the next pass after the G-buffer
         if (m_bDeferredLighting && m_bEnableSky) m_RenderGraph->AddRenderer(g_SkyRenderer);  // :502
         if (m_bPostProcess && m_bEnableBloom) m_RenderGraph->AddRenderer(g_BloomRenderer);   // :503
-        if (m_bPostProcess) {                                                 // :505, :507 (transparents and TAA between them are not built)
+        if (m_bPostProcess) {                                                 // :505-507 (the transparents between them are a stub in the reference)
             m_RenderGraph->AddRenderer(g_AdaptLuminanceRenderer);
+            m_RenderGraph->AddRenderer(g_TAARenderer);                        // :506; Setup returns false unless IsTAAEnabled()
             m_RenderGraph->AddRenderer(g_PostProcessRenderer);
         }
         m_RenderGraph->AddRenderer(g_GIDebugRenderer);                        // :509 (after the base pass: it reads this frame's HZB)

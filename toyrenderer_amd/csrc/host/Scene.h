@@ -38,6 +38,13 @@ public:
     // Tests need an explicit previous-frame matrix for frame 0.
     void SetPrevCamera(const Matrix& prevWorldToView) { m_WorldToView = prevWorldToView; }
     bool m_bUseExplicitProjection = false;           // keep m_ViewToClip as set by the application
+    Matrix m_ExplicitViewToClip{};                   // that projection, unjittered: what Update starts from every frame
+
+    // Temporal anti-aliasing (Scene.h:57-58, Scene.cpp:113-119, :127-131), kept while Scene::IsTAAEnabled(): the jitter offsets in
+    // pixels and the jittered world-to-clip of this frame and the last.  On the first such frame the previous ones are this frame's.
+    Vector2 m_PrevJitterOffset{ 0.0f, 0.0f }, m_CurrentJitterOffset{ 0.0f, 0.0f };
+    Matrix m_WorldToClip{}, m_PrevWorldToClip{};
+    bool m_bHasTAAHistory = false;                   // a frame ran with TAA on since it was switched on
 
 private:
     Matrix m_PendingWorldToView{};
@@ -144,6 +151,12 @@ public:
     // Bloom generation (trhost_set_bloom; needs m_bPostProcess, excludes an uploaded m_BloomTexture): BloomRenderer runs between
     // DeferredLightingRenderer and AdaptLuminanceRenderer and PostProcessRenderer binds its texture.  The mip count and the
     // radius are members of the renderer in the reference (BloomRenderer.cpp:16-17, defaults 6 and 0.005f).
+    // Temporal anti-aliasing (trhost_set_taa; needs m_bPostProcess): View::Update jitters the projection and TAARenderer runs between
+    // AdaptLuminanceRenderer and PostProcessRenderer, which then reads its g_AntiAliasedLightingOutput (Scene.cpp:505-507).
+    bool m_bEnableTAA = false;
+    float m_TAAMinBlend = 0.1f, m_TAAMaxSampleCount = 64.0f;
+    bool m_bResetTAAHistory = true;                  // the next frame's resolve starts every texel again (the first frame; trhost_reset_taa_history)
+    bool IsTAAEnabled() const { return m_bEnableTAA && m_bPostProcess; }
     bool m_bEnableBloom = false;
     uint32_t m_NbBloomMips = 6;
     float m_BloomFilterRadius = 0.005f;

@@ -60,6 +60,13 @@ void ReleasePostProcessOutputs();
 nvrhi::TextureHandle GetGeneratedBloomTexture();
 bool GetLastBloomConsts(uint32_t pass, void* out16);
 void ReleaseBloomOutputs();
+// TAARenderer: g_AntiAliasedLightingOutput of the last frame and the history texture it wrote (null if the resolve did not run in it),
+// the output the frame being set up will write (null if TAA is off), the TAAConsts the last frame ran with and View's jitter offsets.
+nvrhi::TextureHandle GetAntiAliasedLightingOutput();
+nvrhi::TextureHandle GetScheduledAntiAliasedLightingOutput();
+nvrhi::TextureHandle GetTAAHistory();
+bool GetLastTAAConsts(void* out32, float* currentJitter2, float* prevJitter2);
+void ReleaseTAAOutputs();
 // AmbientOcclusionRenderer: the SSAO texture of the last frame (null if the pass did not run in it), the one the frame being set
 // up will write (null if the pass is not scheduled in it), and the GTAOConstants the last frame uploaded.
 nvrhi::TextureHandle GetSSAOTexture();

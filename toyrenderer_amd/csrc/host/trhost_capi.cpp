@@ -64,6 +64,7 @@ void trhost_shutdown(void)
         ReleaseDeferredLightingOutputs();
         ReleasePostProcessOutputs();
         ReleaseBloomOutputs();
+        ReleaseTAAOutputs();
         ReleaseSkyOutputs();
         ReleaseAmbientOcclusionOutputs();
         ReleaseShadowMaskOutputs();
@@ -540,6 +541,56 @@ int trhost_get_bloom_consts(uint32_t pass, void* out16)
     });
 }
 
+int trhost_set_taa(int enable, float min_blend, float max_sample_count)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!enable) { g_Scene->m_bEnableTAA = false; return; }               // the projection is the camera's again and the post pass reads LightingOutput
+        if (!g_Scene->m_bPostProcess) throw nvrhi::Error("trhost_set_taa: post-processing is off (trhost_set_post_process first): nothing would read the anti-aliased output");
+        if (!(min_blend >= 0.0f && min_blend <= 1.0f)) throw nvrhi::Error("trhost_set_taa: min_blend must be in [0, 1]");
+        if (!(max_sample_count >= 1.0f && max_sample_count <= 65504.0f)) throw nvrhi::Error("trhost_set_taa: max_sample_count must be in [1, 65504]: the count is stored as a binary16");
+        g_Scene->m_bEnableTAA = true;
+        g_Scene->m_TAAMinBlend = min_blend;
+        g_Scene->m_TAAMaxSampleCount = max_sample_count;
+    });
+}
+
+int trhost_reset_taa_history(void)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!g_Scene->IsTAAEnabled()) throw nvrhi::Error("trhost_reset_taa_history: temporal anti-aliasing is off (trhost_set_taa first)");
+        g_Scene->m_bResetTAAHistory = true;
+    });
+}
+
+int trhost_download_anti_aliased_output(uint32_t* words, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetAntiAliasedLightingOutput();
+        if (!t) throw nvrhi::Error("trhost_download_anti_aliased_output: the last frame ran without temporal anti-aliasing");
+        check(words);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, words, bytes), "trhost_download_anti_aliased_output");
+    });
+}
+
+int trhost_download_taa_history(void* halves, uint64_t bytes)
+{
+    return guarded([&] {
+        nvrhi::TextureHandle t = GetTAAHistory();
+        if (!t) throw nvrhi::Error("trhost_download_taa_history: the last frame ran without temporal anti-aliasing");
+        check(halves);
+        nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, halves, bytes), "trhost_download_taa_history");
+    });
+}
+
+int trhost_get_taa_consts(void* out32, float* current_jitter, float* prev_jitter)
+{
+    return guarded([&] {
+        if (!GetLastTAAConsts(out32, current_jitter, prev_jitter)) throw nvrhi::Error("trhost_get_taa_consts: the last frame ran without temporal anti-aliasing");
+    });
+}
+
 int trhost_load_sky_dataset(const double* rgb, const double* rad)
 {
     return guarded([&] {
@@ -771,7 +822,7 @@ int trhost_set_camera(const float* world_to_view, const float* prev_world_to_vie
         View& v = g_Scene->m_View;
         if (prev_world_to_view) v.SetPrevCamera(toMatrix(prev_world_to_view));
         v.SetCamera(toMatrix(world_to_view));
-        if (view_to_clip) { v.m_ViewToClip = toMatrix(view_to_clip); v.m_bUseExplicitProjection = true; }
+        if (view_to_clip) { v.m_ViewToClip = v.m_ExplicitViewToClip = toMatrix(view_to_clip); v.m_bUseExplicitProjection = true; }
         v.m_ZNearP = near_plane;
     });
 }

@@ -66,20 +66,8 @@ struct BloomArgs
     BloomConsts k;
 };
 
-// One axis of SampleLevel(LinearClamp): the two texel indices and the weight of the second.
-struct Axis { uint32_t i0, i1; float f; };
-
-__device__ __forceinline__ Axis axisOf(float uv, uint32_t dim)
-{
-    const float t = uv * (float)dim - 0.5f, t0 = __builtin_floorf(t), last = (float)(dim - 1u);
-#ifdef TR_BLOOM_EXPERIMENT_FIXED_POINT         // negative control only (profiles/bloom/): a fixed-point sampler weight
-    const float f = (float)(uint32_t)((t - t0) * 256.0f) / 256.0f;
-#else
-    const float f = t - t0;
-#endif
-    return { (uint32_t)cm::min_(cm::max_(t0, 0.0f), last), (uint32_t)cm::min_(cm::max_(t0 + 1.0f, 0.0f), last), f };
-}
-
+using sp::Axis;                                 // one axis of SampleLevel(LinearClamp): screen_pass.hip.h, shared with k_taa.hip
+using sp::axisOf;
 using sp::lerp_;
 __device__ __forceinline__ cm::F3 add(cm::F3 a, cm::F3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
 __device__ __forceinline__ cm::F3 mul(cm::F3 a, float s) { return { a.x * s, a.y * s, a.z * s }; }

@@ -51,6 +51,22 @@ __device__ __forceinline__ cm::F3 worldPosition(const interop::Matrix& clipToWor
 
 __device__ __forceinline__ float saturate_(float x) { return cm::min_(cm::max_(x, 0.0f), 1.0f); }
 __device__ __forceinline__ float lerp_(float x, float y, float s) { return x + s * (y - x); }
+
+// One axis of SampleLevel(LinearClamp, uv, 0) on a mip `dim` texels wide (k_bloom.hip's CONVENTION states it; the temporal resolve
+// reads its history through the same words): the two texel indices and the weight of the second.
+struct Axis { uint32_t i0, i1; float f; };
+
+__device__ __forceinline__ Axis axisOf(float uv, uint32_t dim)
+{
+    const float t = uv * (float)dim - 0.5f, t0 = __builtin_floorf(t), last = (float)(dim - 1u);
+#ifdef TR_BLOOM_EXPERIMENT_FIXED_POINT         // negative control only (profiles/bloom/): a fixed-point sampler weight
+    const float f = (float)(uint32_t)((t - t0) * 256.0f) / 256.0f;
+#else
+    const float f = t - t0;
+#endif
+    return { (uint32_t)cm::min_(cm::max_(t0, 0.0f), last), (uint32_t)cm::min_(cm::max_(t0 + 1.0f, 0.0f), last), f };
+}
+
 __device__ __forceinline__ _Float16 halfOf(uint32_t low16) { return __builtin_bit_cast(_Float16, (uint16_t)low16); }
 __device__ __forceinline__ uint32_t halfBits(float f) { return f != f ? 0x7E00u : (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f); }
 

@@ -16,6 +16,7 @@ from . import gtao as gtaomod
 from . import interop as I
 from . import rhi
 from . import sky as skymod
+from . import taa as taamod
 from .rhi import CB, PUSH, SAMPLER, SRV, TEX_SRV, TEX_TABLE, TEX_UAV, UAV
 
 SLOT_NAMES = ("early_opaque", "late_opaque", "early_alphamask", "late_alphamask")
@@ -159,7 +160,7 @@ class FrameDriver:
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
                  bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
-                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None, probes=None):
+                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None, probes=None, taa=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -260,7 +261,21 @@ class FrameDriver:
         self.probe_culled_positions, self.probe_draw_args and self.probe_instance_to_probe, and "giprobevisualization_PS_
         VisualizeGIProbes" draws the survivors as spheres shaded with their own irradiance, depth-tested against self.depth, which it
         also writes.  Settings: radius (0.1, GIRenderer.cpp's m_ProbeRadius) and hide_inactive (False).  The block the draw ran with
-        is self.probe_draw_consts; download_probes() and download_probe_winners() read the results back."""
+        is self.probe_draw_consts; download_probes() and download_probe_winners() read the results back.
+        taa: None (the default) changes nothing.  A dict of settings (needs post=True): min_blend (0.1), max_sample_count (64) and
+        jitter (True): temporal anti-aliasing, the place of the reference's TAARenderer (csrc/k_taa.hip, taa.py).  Every record() is
+        then one frame of a sequence: the jitter is Graphic::ComputeCurrentJitterOffset's Halton offset of self.frame_counter
+        ((0, 0) with jitter=False), the frame's projection is view.viewToClip times the pixel offset matrix (Scene.cpp:127-131), and
+        that jittered projection is what the cull, the rasters, the resolve, AO, the shadows, lighting, the sky and the probe draw
+        see; m_PrevWorldToClip is the previous record()'s jittered world-to-clip (this frame's on the first record), as
+        View::Update keeps it.  One "taa_CS_TemporalResolve" dispatch behind the exposure passes and in front of
+        "postprocess_PS_PostProcess" reads LightingOutput, self.depth, self.motion and the history written by the previous
+        record(), and writes the other of the two self.taa_history textures (RGBA16_FLOAT) and self.anti_aliased_output
+        (R11G11B10_FLOAT), which the post pass then reads in the place of LightingOutput; bloom and the histogram keep reading
+        LightingOutput.  The first record() and the one after reset_taa() run with m_bResetHistory = 1.  self.taa_consts holds
+        the TAAConsts of the last record(), self.taa_written the index of the history texture it wrote, self.taa_jitter its (current, previous) offsets in pixels, self.taa_view the jittered
+        View it rendered with and self.taa_prev_world_to_clip its m_PrevWorldToClip; download_anti_aliased_output() and
+        download_taa_history() (the texture written last) read the results back."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -296,6 +311,11 @@ class FrameDriver:
             self.probes = dict(radius=float(probes.get("radius", 0.1)), hide_inactive=bool(probes.get("hide_inactive", False)))
             if not (np.isfinite(self.probes["radius"]) and self.probes["radius"] > 0.0):
                 raise ValueError(f"probes: radius = {self.probes['radius']} is not positive and finite")
+        self.taa = self.taa_consts = self.taa_jitter = self.taa_view = self.taa_prev_world_to_clip = None
+        if taa is not None:
+            if not post:
+                raise ValueError("taa=... needs post=True: the post pass is what reads the anti-aliased output")
+            self.taa = taamod.check_settings(taa)
         self.alpha_test = bool(alpha_test)
         if self.alpha_test and not (raster_depth or visibility):
             raise ValueError("alpha_test=True needs raster_depth=True (or visibility, gbuffer, lighting, post): the test runs in the rasters, and a frame without them draws nothing")
@@ -388,6 +408,11 @@ class FrameDriver:
         if self.bloom_mips:                          # BloomRenderer::Setup (BloomRenderer.cpp:41-50)
             self.bloom_texture = dev.create_texture(view.renderW, view.renderH, self.bloom_mips, rhi.FORMAT_R11G11B10_FLOAT, "Bloom Texture",
                                                     render_target=True)
+        self.taa_history = self.anti_aliased_output = None
+        self._taa_reset, self.taa_written, self._taa_last = True, 1, None
+        if self.taa is not None:                     # TAARenderer::Initialize (TAARenderer.cpp:263-271) + the two histories of the resolve
+            self.taa_history = [dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_RGBA16_FLOAT, f"TAA History {i}") for i in (0, 1)]
+            self.anti_aliased_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Anti-Aliased Lighting Output")
         self.ao_depth = self.ao_working = self.ao_edges = self.ssao_texture = None
         if self.ao is not None:                      # AmbientOcclusionRenderer::Setup (AmbientOcclusionRenderer.cpp:85-127)
             self.ao_depth = dev.create_texture(view.renderW, view.renderH, gtaomod.DEPTH_MIP_LEVELS, rhi.FORMAT_R16_FLOAT, "XeGTAO Working Depth Buffer")
@@ -487,7 +512,7 @@ class FrameDriver:
         k["m_NearPlane"] = v.nearPlane
         k["m_OutputResolution"] = (v.renderW, v.renderH)
         if self.visibility_on:                                                           # Scene.cpp:116-118 on this build's raster camera
-            k["m_PrevWorldToClip"] = I.world_to_clip(v.prevWorldToView, v.viewToClip)
+            k["m_PrevWorldToClip"] = I.world_to_clip(v.prevWorldToView, v.viewToClip) if self.taa is None else self.taa_prev_world_to_clip   # TAA: Scene.cpp:119
         if self.gbuffer_on:
             k["m_DebugMode"] = self.debug_mode                                           # BasePassRenderers.cpp:455
         return k
@@ -794,17 +819,55 @@ class FrameDriver:
             ak["m_MiddleGray"] = self.middle_gray
             cl.dispatch("adaptluminance_CS_AdaptExposure", [PUSH(0), SRV(0, self.histogram), UAV(0, self.luminance), TEX_UAV(1, self.exposure_texture, 0)],
                         (1, 1, 1), push=ak)
+        if self.taa is not None:                                                         # Scene.cpp:506: between adapt luminance and post
+            self._taa_resolve(cl)
         pk = np.zeros(1, I.PostProcessParameters)
         pk["m_OutputDims"] = dims
         pk["m_ManualExposure"] = self.manual_exposure
         pk["m_MiddleGray"] = self.middle_gray
         bloom = self.bloom_texture if self.bloom_texture is not None else self.bloom     # generated, or the caller's
         pk["m_BloomStrength"] = self.bloom_strength if bloom is not None else 0.0       # m_bEnableBloom ? m_BloomStrength : 0
-        b = [PUSH(0), TEX_SRV(0, self.lighting_output), SRV(1, self.luminance), TEX_UAV(0, self.back_buffer, 0), SAMPLER(0)]
+        colour = self.anti_aliased_output if self.taa is not None else self.lighting_output   # PostProcessRenderer.cpp:25-27, :52
+        b = [PUSH(0), TEX_SRV(0, colour), SRV(1, self.luminance), TEX_UAV(0, self.back_buffer, 0), SAMPLER(0)]
         if bloom is not None:
             b.append(TEX_SRV(2, bloom))
         cl.dispatch("postprocess_PS_PostProcess", b, ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1), push=pk)
         self.post_consts = (hk, ak, pk)
+
+    # ---- TAARenderer::Render's place (TAARenderer.cpp:273-275 for the inputs; the resolve is csrc/k_taa.hip) ---------------------
+    def _taa_begin(self):
+        """The frame's jitter, its jittered View and m_PrevWorldToClip (View::Update, Scene.cpp:113-133)."""
+        self.taa_view, self.taa_jitter, self.taa_prev_world_to_clip, self._taa_last = taamod.begin_frame(self.view, self.frame_counter, self.taa, self._taa_last)
+        return self.taa_view
+
+    def _taa_resolve(self, cl):
+        v = self.view
+        self.taa_consts = taamod.consts(v.renderW, v.renderH, self.taa, *self.taa_jitter, self._taa_reset)
+        read, write = self.taa_history[self.taa_written], self.taa_history[1 - self.taa_written]
+        cl.dispatch("taa_CS_TemporalResolve",
+                    [PUSH(0), TEX_SRV(0, self.lighting_output), TEX_SRV(1, self.depth), TEX_SRV(2, self.motion), TEX_SRV(3, read), TEX_UAV(0, write, 0),
+                     TEX_UAV(1, self.anti_aliased_output, 0), SAMPLER(0)], ((v.renderW + 7) // 8, (v.renderH + 7) // 8, 1), push=self.taa_consts)
+        self.taa_written, self._taa_reset = 1 - self.taa_written, False
+
+    def reset_taa(self):
+        """The next record() runs the resolve with m_bResetHistory = 1: every texel starts again from its current colour."""
+        if self.taa is None:
+            raise ValueError("reset_taa: temporal anti-aliasing is off (taa=None)")
+        self._taa_reset = True
+
+    def download_anti_aliased_output(self) -> np.ndarray:
+        """The words of AntiAliasedLightingOutput, (H, W) uint32."""
+        if self.taa is None:
+            raise ValueError("download_anti_aliased_output: temporal anti-aliasing is off (taa=None)")
+        self.dev.wait_idle()
+        return self.anti_aliased_output.download_mip(0)
+
+    def download_taa_history(self) -> np.ndarray:
+        """The history texture written last, (H, W, 4) float16: xyz the colour, w the accumulated sample count."""
+        if self.taa is None:
+            raise ValueError("download_taa_history: temporal anti-aliasing is off (taa=None)")
+        self.dev.wait_idle()
+        return self.taa_history[self.taa_written].download_mip(0)
 
     # ---- GIDebugRenderer::RenderDDGIDebug (GIRenderer.cpp:672-808) ------------------------------
     def _probe_visualization(self, cl):
@@ -881,6 +944,16 @@ class FrameDriver:
     def record(self, query: rhi.PipelineStatsQuery | None = None):
         """query: a pipeline statistics query bracketing the whole list (begin after open, end before close), as the
         reference brackets RenderBasePass (:546-549); None records the list without one."""
+        if self.taa is None:
+            return self._record_frame(query)
+        view = self.view
+        self.view = self._taa_begin()                                                    # every pass of the frame sees the jittered projection
+        try:
+            return self._record_frame(query)
+        finally:
+            self.view = view
+
+    def _record_frame(self, query):
         cl = self.cl
         cl.open()
         if query is not None:
@@ -973,6 +1046,6 @@ class FrameDriver:
                   self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
                   self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays, self.ddgi_fixed_rays,
                   self.probe_positions, self.probe_states, self.probe_culled_positions, self.probe_draw_args, self.probe_instance_to_probe, self.probe_sphere_vertices,
-                  self.probe_sphere_indices, self.probe_winners):
+                  self.probe_sphere_indices, self.probe_winners, self.anti_aliased_output, *(self.taa_history or ())):
             if t is not None:
                 t.release()

@@ -35,6 +35,7 @@ HOST_SYMBOLS = [
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
     "trhost_set_bloom", "trhost_download_bloom", "trhost_get_bloom_consts",
+    "trhost_set_taa", "trhost_reset_taa_history", "trhost_download_anti_aliased_output", "trhost_download_taa_history", "trhost_get_taa_consts",
     "trhost_load_sky_dataset", "trhost_set_sky", "trhost_get_sky_consts",
     "trhost_set_ambient_occlusion", "trhost_download_ssao", "trhost_get_gtao_consts",
     "trhost_load_raytracing", "trhost_upload_blue_noise", "trhost_set_shadow_mask", "trhost_download_shadow_mask", "trhost_get_shadow_mask_consts",
@@ -125,6 +126,11 @@ def load() -> C.CDLL:
     L.trhost_set_bloom.argtypes = [C.c_int, u32, C.c_float, C.c_float]
     L.trhost_download_bloom.argtypes = [u32, vp, u64]
     L.trhost_get_bloom_consts.argtypes = [u32, vp]
+    L.trhost_set_taa.argtypes = [C.c_int, C.c_float, C.c_float]
+    L.trhost_reset_taa_history.argtypes = []
+    L.trhost_download_anti_aliased_output.argtypes = [vp, u64]
+    L.trhost_download_taa_history.argtypes = [vp, u64]
+    L.trhost_get_taa_consts.argtypes = [vp, vp, vp]
     L.trhost_load_sky_dataset.argtypes = [vp, vp]
     L.trhost_set_sky.argtypes = [C.c_int, C.c_float, vp]
     L.trhost_get_sky_consts.argtypes = [vp]
@@ -456,6 +462,34 @@ class Renderer:
         w = np.empty((self.render[1] >> mip, self.render[0] >> mip), np.uint32)
         _check(load().trhost_download_bloom(int(mip), w.ctypes.data, w.nbytes))
         return w
+
+    def set_taa(self, enable: bool, min_blend: float = 0.1, max_sample_count: float = 64.0):
+        """TAARenderer and the jittered projection on or off (needs set_post_process(True))."""
+        _check(load().trhost_set_taa(int(bool(enable)), float(min_blend), float(max_sample_count)))
+
+    def reset_taa_history(self):
+        """The next frame's resolve starts every texel again from its current colour."""
+        _check(load().trhost_reset_taa_history())
+
+    def download_anti_aliased_output(self) -> np.ndarray:
+        """The last frame's AntiAliasedLightingOutput: uint32 [H, W] R11G11B10_FLOAT words."""
+        self.wait_idle()
+        w = np.empty((self.render[1], self.render[0]), np.uint32)
+        _check(load().trhost_download_anti_aliased_output(w.ctypes.data, w.nbytes))
+        return w
+
+    def download_taa_history(self) -> np.ndarray:
+        """The history texture the last frame wrote: float16 [H, W, 4], xyz the colour, w the accumulated sample count."""
+        self.wait_idle()
+        h = np.empty((self.render[1], self.render[0], 4), np.float16)
+        _check(load().trhost_download_taa_history(h.ctypes.data, h.nbytes))
+        return h
+
+    def taa_consts(self):
+        """(TAAConsts of the last frame, its current jitter offset, its previous one), the offsets float32 [2] in pixels."""
+        k, current, previous = np.zeros(1, I.TAAConsts), np.zeros(2, np.float32), np.zeros(2, np.float32)
+        _check(load().trhost_get_taa_consts(k.ctypes.data, current.ctypes.data, previous.ctypes.data))
+        return k, current, previous
 
     def load_sky_dataset(self, dataset):
         """A sky.HosekDataset (the Hosek-Wilkie RGB tables, an input of the integrator); None unloads it and switches the pass off."""

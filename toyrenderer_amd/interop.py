@@ -88,6 +88,8 @@ PostProcessParameters = np.dtype([                                              
     ("m_OutputDims", np.uint32, (2,)), ("m_ManualExposure", np.float32), ("m_MiddleGray", np.float32), ("m_WhitePoint", np.float32),
     ("m_BloomStrength", np.float32)])
 BloomConsts = np.dtype([("m_InvSourceResolution", np.float32, (2,)), ("m_FilterRadius", np.float32), ("m_bIsFirstDownsample", np.uint32)])   # ShaderInterop.h:79-84
+TAAConsts = np.dtype([("m_OutputDims", np.uint32, (2,)), ("m_JitterDelta", np.float32, (2,)), ("m_MinBlend", np.float32), ("m_MaxSampleCount", np.float32),   # the project's own (csrc/k_taa.hip)
+                      ("m_bResetHistory", np.uint32), ("PAD0", np.uint32)])
 HosekWilkieSkyParameters = np.dtype([("m_Params", np.float32, (10, 4))])                                                    # ShaderInterop.h:146-149
 SkyPassParameters = np.dtype([                                                                                             # ShaderInterop.h:297-305
     ("m_ClipToWorld", np.float32, (4, 4)), ("m_SunLightDir", np.float32, (3,)), ("PAD0", np.uint32), ("m_CameraPosition", np.float32, (3,)),
@@ -133,7 +135,7 @@ SIZES = {
     "BasePassConstants": 256, "MinMaxDownsampleConsts": 12, "NodeLocalTransform": 48,
     "TextureData": 20, "MaterialData": 124, "DeferredLightingConsts": 112,
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
-    "BloomConsts": 16, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
+    "BloomConsts": 16, "TAAConsts": 32, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
     "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
     "ShadowMaskConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96, "GIProbeVisualizationConsts": 96, "UncompressedRawVertexFormat": 32, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
 }
