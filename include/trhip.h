@@ -430,7 +430,7 @@ int  trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics*
  * object-from-world 3x4 (rows of p_object = (p_world, 1) * M) and the leaf's box: the BLAS root box's 8 corners through
  * m_WorldMatrix, moved outward by 2^-12 times the largest |coordinate|; then every inner box, height by height.
  * "shadowmask_CS_ShadowMask": a direct dispatch of [numthreads(8, 8, 1)] groups covering m_OutputResolution; b0 ShadowMaskConsts
- * (112 bytes, a constant buffer; m_bDoDenoising must be 0), t0 (texture) R32_FLOAT depth, t1 the TLAS nodes, t2 (texture) GBufferA,
+ * (112 bytes, a constant buffer; m_bDoDenoising: see the shadow denoiser below), t0 (texture) R32_FLOAT depth, t1 the TLAS nodes, t2 (texture) GBufferA,
  * t3 instances, t4 vertices, t5 materials, t6 indices, t7 mesh data, t8 (texture) RGBA8_UNORM 128 x 128 blue noise, u0 (texture)
  * R8_UNORM mask, u1 (texture) R16_FLOAT linear view depth, and the structure's other buffers: t9 TLAS instances, t10 BLAS
  * headers, t11 BLAS nodes, t12 triangle order, and optionally t19 the texture table: with it ("#textured" in the profile) a
@@ -439,7 +439,20 @@ int  trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics*
  * count) is at least m_AlphaCutoff; without it, and for texture-free materials, iff m_ConstAlbedo.w >= m_AlphaCutoff.
  * Samplers are accepted and ignored.  A texel of depth 0.0f gets u1 = 65504 and
  * keeps u0; any other gets u0 = 0 (occluded) or 255 and u1 = fp16(|worldPosition - m_CameraPosition|).  An index read on the
- * device that leaves its buffer ends that instance's (or triangle's) test; it is never followed. */
+ * device that leaves its buffer ends that instance's (or triangle's) test; it is never followed.
+ * THE SHADOW DENOISER (ShadowMaskRenderer::DenoiseShadows; csrc/k_sigma.hip states every rule, tests/sigma_ref.c defines them).
+ * "shadowmask_CS_ShadowMask" with m_bDoDenoising != 0: u0 is an R16_FLOAT penumbra texture (the R8_UNORM mask there is refused): no
+ * occluder 65504, else min(0.5 * t * m_TanSunAngularRadius, 32768) of the CLOSEST committing candidate; "#penumbra" /
+ * "#textured_penumbra" in the profile; u1 and far texels as above.  "shadowmask_CS_PackNormalAndRoughness": groups of 8 x 8 covering
+ * m_OutputResolution; b0 or push constants { m_OutputResolution } (8 bytes), t2 GBufferA, u0 an R10G10B10A2_UNORM texture: the
+ * octahedral normal in x and y, roughness in z, w = 0, every texel.  The four entries behind them share b0 or push constants
+ * SigmaConsts (112 bytes, csrc/ShaderInterop.h) and an R8_UINT tile texture of ceil(W / 16) x ceil(H / 16):
+ * "SIGMA_Shadow_ClassifyTiles.cs" (groups of 16 x 16): t0 penumbra, t1 R16_FLOAT linear view depth, u0 tiles, u1 RG16_FLOAT shadow data;
+ * "SIGMA_Shadow_Blur.cs" (m_Pass 0) and "SIGMA_Shadow_PostBlur.cs" (m_Pass 1), groups of 8 x 8: t0 shadow data in, t1 linear view
+ * depth, t2 R32_FLOAT depth, t3 the normal roughness texture, t4 tiles, u0 shadow data out (another texture than t0);
+ * "SIGMA_Shadow_TemporalStabilization.cs" (8 x 8): t0 shadow data, t1 linear view depth, t2 the RG16_FLOAT motion target, t3 the previous
+ * R16_FLOAT history, t4 tiles, u0 the new history (another texture than t3), u1 the R8_UNORM shadow mask the lighting pass binds.
+ * All textures one mip at m_OutputDims; every dispatch direct; each refusal happens at record time. */
 typedef struct { float lo[3]; uint32_t skip; float hi[3]; uint32_t leaf; } trhip_accel_node;
 typedef struct { uint32_t node_offset, num_nodes, tri_offset, num_tris; } trhip_blas_header;
 typedef struct { float object_from_world[12]; uint32_t flags, leaf_node, reserved[2]; } trhip_tlas_instance;

@@ -251,6 +251,21 @@ int  trhost_upload_blue_noise(const uint8_t* rgba, uint64_t bytes);
 int  trhost_set_shadow_mask(int enable, int soft, float sun_angular_diameter, float ray_start_offset);
 int  trhost_download_shadow_mask(uint8_t* bytes, uint64_t size);
 int  trhost_get_shadow_mask_consts(void* out112);
+/* The shadow denoiser (ShadowMaskRenderer::DenoiseShadows; csrc/k_sigma.hip; off by default).  trhost_set_shadow_denoising(1,
+ * plane_distance_sensitivity, stabilization_strength, sigma_scale) (0.02 and 5/6: NRD's defaults; 2: this project's choice): the
+ * trace then writes the penumbra texture, and "shadowmask_CS_PackNormalAndRoughness" and the four "SIGMA_Shadow_*" dispatches turn it
+ * into the mask the lighting pass binds.  Refused: the shadow mask off; a sensitivity that is not finite and > 0, a strength outside
+ * [0, 1], a scale that is not finite and >= 0.  trhost_set_shadow_mask(0, ...) switches it off too.  The first frame, the first after
+ * it was switched on and the one after trhost_reset_shadow_history run with m_bResetHistory = 1.  The downloads wait and copy the
+ * W x H binary16 words of the penumbra texture, the ceil(W / 16) x ceil(H / 16) tile bytes and the W x H binary16 words of the
+ * history the last frame wrote; trhost_get_sigma_consts copies the 112 bytes of SigmaConsts (m_Pass 0) of the last frame; all
+ * refuse if the denoiser did not run in it.  m_DenoisingRange is 100: the mirror keeps no bounding sphere. */
+int  trhost_set_shadow_denoising(int enable, float plane_distance_sensitivity, float stabilization_strength, float sigma_scale);
+int  trhost_reset_shadow_history(void);
+int  trhost_download_shadow_penumbra(void* halves, uint64_t bytes);
+int  trhost_download_shadow_tiles(uint8_t* tiles, uint64_t bytes);
+int  trhost_download_shadow_history(void* halves, uint64_t bytes);
+int  trhost_get_sigma_consts(void* out112);
 int  trhost_download_back_buffer(uint32_t* words, uint64_t bytes);
 int  trhost_get_scene_luminance(float* luminance, float* exposure);
 int  trhost_reset_exposure(void);

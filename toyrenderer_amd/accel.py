@@ -143,8 +143,9 @@ def noise_words(noise: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(noise, np.uint8).reshape(I.kBlueNoiseSize, I.kBlueNoiseSize, 4).view("<u4").reshape(I.kBlueNoiseSize, I.kBlueNoiseSize)
 
 
-def shadow_consts(clip_to_world, light_direction, camera_position, W: int, H: int, settings: dict, frame_counter: int) -> np.ndarray:
-    """ShadowMaskConsts of one frame (ShadowMaskRenderer.cpp:266-274) with m_bDoDenoising = 0."""
+def shadow_consts(clip_to_world, light_direction, camera_position, W: int, H: int, settings: dict, frame_counter: int, denoise: bool = False) -> np.ndarray:
+    """ShadowMaskConsts of one frame (ShadowMaskRenderer.cpp:266-274).  m_bDoDenoising = 0 unless denoise: the trace then writes the
+    R16_FLOAT penumbra texture in place of the mask (csrc/k_shadowmask.hip)."""
     k = np.zeros(1, I.ShadowMaskConsts)
     k["m_ClipToWorld"] = clip_to_world
     k["m_DirectionalLightDirection"] = light_direction
@@ -153,4 +154,58 @@ def shadow_consts(clip_to_world, light_direction, camera_position, W: int, H: in
     k["m_TanSunAngularRadius"] = tan_sun_angular_radius(settings)
     k["m_OutputResolution"] = (W, H)
     k["m_RayStartOffset"] = np.float32(settings["ray_start_offset"])
+    if denoise:
+        k["m_bDoDenoising"] = 1
+    return k
+
+
+# ---- the shadow denoiser's settings and constants (csrc/k_sigma.hip) -----------------------------------------------------------------
+# plane_distance_sensitivity and stabilization_strength: NRD's published defaults.  sigma_scale: this project's choice (csrc/k_sigma.hip,
+# SETTINGS).  Nobody has judged any of them on a picture from this build.
+DENOISE_DEFAULTS = dict(plane_distance_sensitivity=0.02, stabilization_strength=5.0 / 6.0, sigma_scale=2.0, scene_radius=0.0)
+kSigmaTile = 16
+
+
+def check_denoise_settings(settings) -> dict:
+    """The dict FrameDriver(shadow_denoise=...) takes, completed with DENOISE_DEFAULTS and checked: plane_distance_sensitivity > 0,
+    stabilization_strength in [0, 1], sigma_scale >= 0, scene_radius >= 0 (m_DenoisingRange = max(100, 2 * scene_radius)), all finite."""
+    if not isinstance(settings, dict):
+        raise ValueError("shadow_denoise: needs a dict of settings (plane_distance_sensitivity, stabilization_strength, sigma_scale, scene_radius)")
+    unknown = set(settings) - set(DENOISE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"shadow_denoise: unknown setting {sorted(unknown)[0]!r}")
+    s = {k: float(v) for k, v in {**DENOISE_DEFAULTS, **settings}.items()}
+    if not (math.isfinite(s["plane_distance_sensitivity"]) and s["plane_distance_sensitivity"] > 0.0):
+        raise ValueError(f"shadow_denoise: plane_distance_sensitivity = {s['plane_distance_sensitivity']}: needs a finite value > 0")
+    if not 0.0 <= s["stabilization_strength"] <= 1.0:
+        raise ValueError(f"shadow_denoise: stabilization_strength = {s['stabilization_strength']}: needs a value in [0, 1]")
+    if not (math.isfinite(s["sigma_scale"]) and s["sigma_scale"] >= 0.0):
+        raise ValueError(f"shadow_denoise: sigma_scale = {s['sigma_scale']}: needs a finite value >= 0")
+    if not (math.isfinite(s["scene_radius"]) and s["scene_radius"] >= 0.0):
+        raise ValueError(f"shadow_denoise: scene_radius = {s['scene_radius']}: needs a finite value >= 0")
+    return s
+
+
+def sigma_tiles(W: int, H: int):
+    """(width, height) of the denoiser's R8_UINT tile texture."""
+    return (W + kSigmaTile - 1) // kSigmaTile, (H + kSigmaTile - 1) // kSigmaTile
+
+
+def sigma_consts(clip_to_world, view_to_clip, W: int, H: int, settings: dict, frame_index: int, pass_index: int = 0, reset_history: bool = False,
+                 jitter_delta=(0.0, 0.0)) -> np.ndarray:
+    """SigmaConsts of one dispatch.  m_PixelUnproject = 2 / (m_ViewToClip[1][1] * H) in binary32: the world height of one pixel at
+    unit distance; m_DenoisingRange = max(100, 2 * scene_radius) (ShadowMaskRenderer.cpp:368)."""
+    F = np.float32
+    k = np.zeros(1, I.SigmaConsts)
+    k["m_ClipToWorld"] = clip_to_world
+    k["m_OutputDims"] = (W, H)
+    k["m_JitterDelta"] = jitter_delta
+    k["m_PixelUnproject"] = F(2.0) / (F(np.asarray(view_to_clip, F).reshape(4, 4)[1, 1]) * F(H))
+    k["m_DenoisingRange"] = max(F(100.0), F(2.0) * F(settings["scene_radius"]))
+    k["m_PlaneDistanceSensitivity"] = F(settings["plane_distance_sensitivity"])
+    k["m_StabilizationStrength"] = F(settings["stabilization_strength"])
+    k["m_SigmaScale"] = F(settings["sigma_scale"])
+    k["m_FrameIndex"] = int(frame_index) & 0xFFFFFFFF
+    k["m_Pass"] = pass_index
+    k["m_bResetHistory"] = 1 if reset_history else 0
     return k

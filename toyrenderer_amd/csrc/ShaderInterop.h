@@ -299,13 +299,41 @@ struct ShadowMaskConsts
     float m_CameraPosition[3];
     float m_TanSunAngularRadius;            // 0: hard shadows
     Vector2U m_OutputResolution;
-    uint32_t m_bDoDenoising;                // must be 0: the SIGMA denoiser is not built
+    uint32_t m_bDoDenoising;                // != 0: u0 is the R16_FLOAT penumbra texture that the shadow denoiser reads (k_sigma.hip)
     float m_RayStartOffset;                 // the origin's offset along the normal, and TMin
 };
 static_assert(sizeof(ShadowMaskConsts) == 112 && offsetof(ShadowMaskConsts, m_DirectionalLightDirection) == 64 && offsetof(ShadowMaskConsts, m_NoisePhase) == 76 &&
               offsetof(ShadowMaskConsts, m_CameraPosition) == 80 && offsetof(ShadowMaskConsts, m_TanSunAngularRadius) == 92 &&
               offsetof(ShadowMaskConsts, m_OutputResolution) == 96 && offsetof(ShadowMaskConsts, m_bDoDenoising) == 104 &&
               offsetof(ShadowMaskConsts, m_RayStartOffset) == 108, "ShadowMaskConsts");
+
+// ShaderInterop.h:229-232: push constants (or b0) of "shadowmask_CS_PackNormalAndRoughness" (k_shadowmask.hip)
+struct PackNormalAndRoughnessConsts
+{
+    Vector2U m_OutputResolution;
+};
+static_assert(sizeof(PackNormalAndRoughnessConsts) == 8, "PackNormalAndRoughnessConsts");
+
+// b0 (or push constants) of the three shadow denoiser entries "SIGMA_Shadow_*" (k_sigma.hip).  The project's own: the reference
+// hands its settings to NRD, which is not in its tree.
+struct SigmaConsts
+{
+    Matrix m_ClipToWorld;
+    Vector2U m_OutputDims;
+    Vector2 m_JitterDelta;                  // previous minus current jitter offset in pixels (TAAConsts carries the same); (0, 0) without TAA
+    float m_PixelUnproject;                 // the world size of one pixel at unit distance, from m_ViewToClip
+    float m_DenoisingRange;                 // max(100, 2 * scene radius): a texel at or beyond it is sky
+    float m_PlaneDistanceSensitivity;
+    float m_StabilizationStrength;          // the history's weight
+    float m_SigmaScale;                     // the history clamp's half width in standard deviations
+    uint32_t m_FrameIndex;                  // turns the tap rotation
+    uint32_t m_Pass;                        // 0: Blur, 1: PostBlur; the other entries ignore it
+    uint32_t m_bResetHistory;               // 1: no texel's history is valid
+};
+static_assert(sizeof(SigmaConsts) == 112 && offsetof(SigmaConsts, m_OutputDims) == 64 && offsetof(SigmaConsts, m_JitterDelta) == 72 &&
+              offsetof(SigmaConsts, m_PixelUnproject) == 80 && offsetof(SigmaConsts, m_DenoisingRange) == 84 && offsetof(SigmaConsts, m_PlaneDistanceSensitivity) == 88 &&
+              offsetof(SigmaConsts, m_StabilizationStrength) == 92 && offsetof(SigmaConsts, m_SigmaScale) == 96 && offsetof(SigmaConsts, m_FrameIndex) == 100 &&
+              offsetof(SigmaConsts, m_Pass) == 104 && offsetof(SigmaConsts, m_bResetHistory) == 108, "SigmaConsts");
 
 // this build's own (not in the reference): push constants of "raytracing_CS_RefitTLAS" (include/trhip.h, "acceleration structure")
 struct RefitTLASConstants

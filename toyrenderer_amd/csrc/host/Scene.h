@@ -182,6 +182,11 @@ public:
     nvrhi::TextureHandle m_BlueNoise;                // CommonResources::BlueNoise: RGBA8_UNORM 128 x 128, an input
     bool m_bEnableShadows = false, m_bEnableSoftShadows = true;
     float m_SunAngularDiameter = 0.533f, m_ShadowRayStartOffset = 0.1f;
+    // The shadow denoiser (trhost_set_shadow_denoising; needs m_bEnableShadows; the reference's m_bEnableShadowDenoising): ShadowMaskRenderer
+    // then runs DenoiseShadows behind the trace.  The first two defaults are NRD's, the third this project's (csrc/k_sigma.hip, SETTINGS).
+    bool m_bEnableShadowDenoising = false;
+    float m_ShadowPlaneDistanceSensitivity = 0.02f, m_ShadowStabilizationStrength = 5.0f / 6.0f, m_ShadowSigmaScale = 2.0f;
+    bool m_bResetShadowHistory = true;               // the next frame's stabilisation reads no history (the first frame; trhost_reset_shadow_history)
     nvrhi::BufferHandle m_LuminanceBuffer;           // Scene.h: one float, the adapted luminance; survives across frames
     nvrhi::TextureHandle m_ExposureTexture;          // 1 x 1 R32_FLOAT
     // SceneLoader's m_GlobalMaterialData upload (SceneLoading.cpp:516-537, 1016-1088); a textured material names textures of Graphic::CreateMaterialTexture.

@@ -78,6 +78,10 @@ void ReleaseAmbientOcclusionOutputs();
 nvrhi::TextureHandle GetShadowMaskTexture();
 nvrhi::TextureHandle GetScheduledShadowMaskTexture();
 bool GetLastShadowMaskConsts(void* out112);
+// the shadow denoiser's outputs of the last frame (which 0: the penumbra texture, 1: the tiles, 2: the history written) and its
+// SigmaConsts (m_Pass 0); null / false if it did not run
+nvrhi::TextureHandle GetShadowDenoiserTexture(int which);
+bool GetLastSigmaConsts(void* out112);
 void ReleaseShadowMaskOutputs();
 // the TLAS refit, recorded by the structure's first consumer in a frame (ShadowMaskRenderer.cpp)
 void RecordRefitTLAS(nvrhi::CommandListHandle commandList);

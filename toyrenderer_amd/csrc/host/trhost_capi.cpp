@@ -697,7 +697,7 @@ int trhost_set_shadow_mask(int enable, int soft, float sun_angular_diameter, flo
 {
     return guarded([&] {
         check(g_Scene);
-        if (!enable) { g_Scene->m_bEnableShadows = false; return; }
+        if (!enable) { g_Scene->m_bEnableShadows = g_Scene->m_bEnableShadowDenoising = false; return; }   // the denoiser has nothing to denoise
         if (!g_Scene->m_bGBuffer) throw nvrhi::Error("trhost_set_shadow_mask: the G-buffer is off (trhost_set_gbuffer or trhost_set_deferred_lighting first): the rays start at its positions and normals");
         if (!g_Scene->m_TLAS) throw nvrhi::Error("trhost_set_shadow_mask: no acceleration structure (trhost_load_raytracing first)");
         if (!g_Scene->m_BlueNoise) throw nvrhi::Error("trhost_set_shadow_mask: no blue noise (trhost_upload_blue_noise first)");
@@ -726,6 +726,52 @@ int trhost_get_shadow_mask_consts(void* out112)
     return guarded([&] {
         check(out112);
         if (!GetLastShadowMaskConsts(out112)) throw nvrhi::Error("trhost_get_shadow_mask_consts: the shadow mask pass did not run in the last frame");
+    });
+}
+
+int trhost_set_shadow_denoising(int enable, float plane_distance_sensitivity, float stabilization_strength, float sigma_scale)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!enable) { g_Scene->m_bEnableShadowDenoising = false; return; }
+        if (!g_Scene->m_bEnableShadows) throw nvrhi::Error("trhost_set_shadow_denoising: the shadow mask is off (trhost_set_shadow_mask first): there is nothing to denoise");
+        if (!(std::isfinite(plane_distance_sensitivity) && plane_distance_sensitivity > 0.0f)) throw nvrhi::Error("trhost_set_shadow_denoising: the plane distance sensitivity must be finite and > 0");
+        if (!(stabilization_strength >= 0.0f && stabilization_strength <= 1.0f)) throw nvrhi::Error("trhost_set_shadow_denoising: the stabilization strength must be in [0, 1]");
+        if (!(std::isfinite(sigma_scale) && sigma_scale >= 0.0f)) throw nvrhi::Error("trhost_set_shadow_denoising: the sigma scale must be finite and >= 0");
+        if (!g_Scene->m_bEnableShadowDenoising) g_Scene->m_bResetShadowHistory = true;   // switched on: whatever the histories hold is from another time
+        g_Scene->m_bEnableShadowDenoising = true;
+        g_Scene->m_ShadowPlaneDistanceSensitivity = plane_distance_sensitivity;
+        g_Scene->m_ShadowStabilizationStrength = stabilization_strength;
+        g_Scene->m_ShadowSigmaScale = sigma_scale;
+    });
+}
+
+int trhost_reset_shadow_history(void)
+{
+    return guarded([&] {
+        check(g_Scene);
+        if (!g_Scene->m_bEnableShadows || !g_Scene->m_bEnableShadowDenoising) throw nvrhi::Error("trhost_reset_shadow_history: shadow denoising is off (trhost_set_shadow_denoising first)");
+        g_Scene->m_bResetShadowHistory = true;
+    });
+}
+
+static void downloadDenoiserTexture(int which, void* out, uint64_t bytes, const char* who)
+{
+    nvrhi::TextureHandle t = GetShadowDenoiserTexture(which);
+    if (!t) throw nvrhi::Error(std::string(who) + ": the shadow denoiser did not run in the last frame");
+    check(out);
+    nvrhi::throwIfFailed(trhip_texture_download(t->native(), 0, out, bytes), who);
+}
+
+int trhost_download_shadow_penumbra(void* halves, uint64_t bytes) { return guarded([&] { downloadDenoiserTexture(0, halves, bytes, "trhost_download_shadow_penumbra"); }); }
+int trhost_download_shadow_tiles(uint8_t* tiles, uint64_t bytes) { return guarded([&] { downloadDenoiserTexture(1, tiles, bytes, "trhost_download_shadow_tiles"); }); }
+int trhost_download_shadow_history(void* halves, uint64_t bytes) { return guarded([&] { downloadDenoiserTexture(2, halves, bytes, "trhost_download_shadow_history"); }); }
+
+int trhost_get_sigma_consts(void* out112)
+{
+    return guarded([&] {
+        check(out112);
+        if (!GetLastSigmaConsts(out112)) throw nvrhi::Error("trhost_get_sigma_consts: the shadow denoiser did not run in the last frame");
     });
 }
 

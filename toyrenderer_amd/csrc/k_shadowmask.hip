@@ -2,8 +2,10 @@
 // :253-305, source/shaders/shadowmask.hlsl CS_ShadowMask): one ray per pixel towards the sun through the scene's acceleration
 // structure; and "raytracing_CS_RefitTLAS", this build's stand-in for buildTopLevelAccelStructFromBuffer (BasePassRenderers.cpp
 // :159-160): the per-frame refit of that structure's top level.  The structure is the project's own (include/trhip.h,
-// "acceleration structure"; built on the host by accel_build.cpp).  DenoiseShadows, CS_PackNormalAndRoughness and the
-// penumbra packing are NRD and not built: a constant block with m_bDoDenoising != 0 is refused.
+// "acceleration structure"; built on the host by accel_build.cpp).  With m_bDoDenoising != 0 the trace writes the
+// penumbra texture that the shadow denoiser reads (k_sigma.hip: DenoiseShadows' place), and "shadowmask_CS_PackNormalAndRoughness"
+// (shadowmask.hlsl:147-167) is here too: push constants or b0 PackNormalAndRoughnessConsts (8 bytes), t2 GBufferA, u0
+// R10G10B10A2_UNORM, groups of 8 x 8.
 //
 // BINDINGS of the trace: b0 ShadowMaskConsts (112 bytes), t0 R32_FLOAT depth, t1 the TLAS nodes, t2 GBufferA, t3 instances, t4
 // vertices, t5 materials, t6 indices, t7 mesh data, t8 RGBA8_UNORM 128 x 128 blue noise, u0 R8_UNORM mask, u1 R16_FLOAT linear view
@@ -35,7 +37,17 @@
 //             triangles is order-independent, so the mask equals brute force for any tree as long as boxHit never rejects what
 //             triTest accepts: tests/test_shadowmask_ref.py walks the same arrays on the CPU and allows no differing texel;
 //   output:   depth == 0.0f: u1 = 0x7BFF, u0 untouched; else u0 = occluded ? 0 : 255, u1 = binary16 RNE of
-//             length(worldPosition - m_CameraPosition) (a NaN is stored as 0x7E00).
+//             length(worldPosition - m_CameraPosition) (a NaN is stored as 0x7E00);
+//   penumbra: m_bDoDenoising != 0 (tests/sigma_ref.c is the definition): u0 must be an R16_FLOAT texture, the R8_UNORM mask is refused.
+//             u0 = SIGMA_FrontEnd_PackPenumbra(occluded ? t : kFP16Max, m_TanSunAngularRadius), which NRD's absent header leaves to this
+//             project: no occluder 0x7BFF (65504), else binary16 of min(0.5f * (t * m_TanSunAngularRadius), 32768.0f); u1 and far
+//             texels as above.  DEVIATION: the reference traces with ACCEPT_FIRST_HIT_AND_END_SEARCH and packs CommittedRayT() of
+//             whichever hit came first (its own comment quotes NVIDIA: wrong, long distances); here t is that of the CLOSEST
+//             committing candidate: closestCommit(), the third visitor of rw::walk, hands the best t so far to triTest as tmax,
+//             runs commits() on what it accepts and never stops.  Only t leaves it: no tie rule, and it equals brute force for any
+//             tree.  Profile labels "#penumbra" and "#textured_penumbra"; the two kernels of before keep name, arguments and label;
+//   pack:     x, y = the octahedral encoding of UnpackGBuffer's normal (packOctUnorm2x16's mapping with cm::div_) before any 16-bit
+//             store, z = roughness, w = 0, each (uint)rint(saturate(v) * 1023.0f) as k_giprobeblend.hip stores UNORM10; every texel.
 //
 // KERNEL: one thread per pixel, a workgroup is one wave covering the reference's 8 x 8 tile, so the 64 rays of a wave start next
 // to each other.  NO STACK: the nodes are in depth-first preorder with skip links (trhip.h), the walk is `hit an inner box ->
@@ -46,7 +58,11 @@
 // of 2251 instances at 3840x2160, one MI355X; profiles/ray_walk/README.md): the trace 1.77 ms with hard and 3.51 ms with soft shadows
 // next to a lighting pass of 0.10 ms, the refit 35 us.  Untuned: correctness came first.  The TEXTURED instantiation
 // (tools/alpha_test_cost.py, the same city with 225 alpha-masked, textured instances): 2.38 ms beside 1.80 ms hard, 4.81 beside 3.55 ms
-// soft; 69 VGPRs instead of 58, no scratch.
+// soft; 69 VGPRs instead of 58, no scratch.  The penumbra instantiations (-Rpass-analysis=kernel-resource-usage): 56 and 69 VGPRs, the
+// pack kernel 23, none with scratch or LDS.  MEASURED (tools/sigma_cost.py, the same city, soft, both traces alternated in one session; profiles/sigma/):
+// the penumbra trace 46453 us (spread 71) beside the any-hit trace's 3516 us (6): 13.2 times.  On that scene every ray is occluded:
+// the any-hit walk ends at its first committing candidate, the closest-commit walk visits every box the ray's line touches, because
+// rw::walk does not prune against the best t so far (ray_walk.hip.h).  Untuned; off by default.
 #include "cull_math.hip.h"
 #include "gbuffer_unpack.hip.h"
 #include "material_textures.hip.h"
@@ -251,11 +267,12 @@ __device__ __forceinline__ bool commits(const Args& a, uint32_t inst, uint32_t f
 }
 
 template <bool TEXTURED>
-__device__ __forceinline__ bool meshTriHit(const TraceArgs& a, const MeshData* md, uint32_t tri, const Ray& r, float tmin, float tmax, Candidate& c)
+__device__ __forceinline__ bool meshTriHit(const TraceArgs& a, const MeshData* md, uint32_t tri, const Ray& r, float tmin, float tmax, Candidate& c, float& t)
 {
     Tri T;
     TriHit h;
     if (!fetchTri(a, md, tri, T) || !triTest(T.v[0], T.v[1], T.v[2], r, tmin, tmax, h)) return false;
+    t = h.t;
     if constexpr (TEXTURED) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) c.tc[k] = *reinterpret_cast<const uint32_t*>(a.vertices + T.i[k] * sizeof(RawVertexFormat) + offsetof(RawVertexFormat, m_TexCoord));
@@ -270,7 +287,8 @@ __device__ bool occluded(const Args& a, F3 o, F3 d, float tmin, float tmax)
 {
     return walk(a, o, d, [&](uint32_t inst, uint32_t flags, const MeshData* md, uint32_t tri, const Ray& r) {
         Candidate c;
-        return meshTriHit<TEXTURED>(a, md, tri, r, tmin, tmax, c) && commits<TEXTURED>(a, inst, flags, c); });
+        float t;
+        return meshTriHit<TEXTURED>(a, md, tri, r, tmin, tmax, c, t) && commits<TEXTURED>(a, inst, flags, c); });
 }
 
 // TEXTURED: a texture table is bound at t19 and alpha-mask candidates read their albedo texture's alpha (commits).
@@ -307,23 +325,83 @@ __global__ __launch_bounds__(kTileSide * kTileSide) void shadowMaskKernel(std::c
     a.lvd[i] = sp::halfBits(len);
 }
 
+// The closest-commit visitor of rw::walk (tests/sigma_ref.c: closest_commit_walk): every candidate that triTest accepts below the best t
+// so far and that commits() replaces it; the walk is never stopped.  Only t leaves, so no tie rule is needed and the answer is
+// brute force's minimum whatever the tree.  Returns tmax when nothing commits.
+template <bool TEXTURED, typename Args>
+__device__ float closestCommit(const Args& a, F3 o, F3 d, float tmin, float tmax)
+{
+    float best = tmax;
+    walk(a, o, d, [&](uint32_t inst, uint32_t flags, const MeshData* md, uint32_t tri, const Ray& r) {
+        Candidate c;
+        float t;
+        if (meshTriHit<TEXTURED>(a, md, tri, r, tmin, best, c, t) && commits<TEXTURED>(a, inst, flags, c)) best = t;
+        return false; });
+    return best;
+}
+
+// m_bDoDenoising != 0: u0 (a.mask) is the R16_FLOAT penumbra texture.  The texel's ray is shadowMaskKernel's, statement for statement,
+// and written out for the reason given there: with the ray in one shared __forceinline__ function the compiler spills 40 and 53 scalar
+// registers in the two mask kernels instead of 4 and 18, and 11 and 27 in these two instead of 0 and 2 (-Rpass-analysis=kernel-
+// resource-usage).  Keep the two alike.  The candidate's test IS shared: meshTriHit hands back t.
+template <bool TEXTURED>
+__global__ __launch_bounds__(kTileSide * kTileSide) void shadowPenumbraKernel(std::conditional_t<TEXTURED, TexturedTraceArgs, TraceArgs> a)
+{
+    const ShadowMaskConsts& k = a.k;
+    const uint32_t W = k.m_OutputResolution.x, H = k.m_OutputResolution.y;
+    const sp::Pixel at = sp::pixel<kTileSide, kTileSide>();
+    if (!at.inside(W, H)) return;
+    const uint32_t px = at.x, py = at.y;
+    const uint64_t i = at.index(W);
+    const float depth = a.depth[i];
+    if (depth == 0.0f) { a.lvd[i] = 0x7BFFu; return; }
+    const float u = cm::div_((float)px + 0.5f, (float)W), v = cm::div_((float)py + 0.5f, (float)H);
+    const float cx = u * 2.0f + -1.0f, cy = v * -2.0f + 1.0f;
+    float h[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        h[j] = cm::fma_(depth, k.m_ClipToWorld.m[2][j], cm::fma_(cy, k.m_ClipToWorld.m[1][j], cx * k.m_ClipToWorld.m[0][j])) + k.m_ClipToWorld.m[3][j];
+    const F3 wp = { cm::div_(h[0], h[3]), cm::div_(h[1], h[3]), cm::div_(h[2], h[3]) };
+    const F3 n = gbuf::unpackGBuffer(a.gbufferA[i]).normal;
+    const uint32_t texel = a.noise[(py % kBlueNoiseSize) * kBlueNoiseSize + (px % kBlueNoiseSize)];
+    const float sx = fmod1(cm::div_((float)(texel & 0xFFu), 255.0f) + k.m_NoisePhase), sy = fmod1(cm::div_((float)((texel >> 8) & 0xFFu), 255.0f) + k.m_NoisePhase);
+    const F3 light = { k.m_DirectionalLightDirection[0], k.m_DirectionalLightDirection[1], k.m_DirectionalLightDirection[2] };
+    const F3 d = gbuf::normalize_(mapToCone(sx, sy, light, k.m_TanSunAngularRadius));
+    const F3 o = { wp.x + n.x * k.m_RayStartOffset, wp.y + n.y * k.m_RayStartOffset, wp.z + n.z * k.m_RayStartOffset };
+    const float tmax = 1e10f;
+#ifdef TR_SIGMA_MUTATE_FIRST_HIT               // negative control only (profiles/sigma/mutations.txt): the first committing candidate's t, as the reference takes it
+    float t = tmax;
+    walk(a, o, d, [&](uint32_t inst, uint32_t flags, const MeshData* md, uint32_t tri, const Ray& r) {
+        Candidate c;
+        return meshTriHit<TEXTURED>(a, md, tri, r, k.m_RayStartOffset, tmax, c, t) && commits<TEXTURED>(a, inst, flags, c); }) || (t = tmax);
+#else
+    const float t = closestCommit<TEXTURED>(a, o, d, k.m_RayStartOffset, tmax);
+#endif
+    // SIGMA_FrontEnd_PackPenumbra as this project fixes it: no occluder 65504, else min(0.5f * (t * tan), 32768)
+    reinterpret_cast<uint16_t*>(a.mask)[i] = (uint16_t)(t < tmax ? sp::halfBits(cm::min_(0.5f * (t * k.m_TanSunAngularRadius), 32768.0f)) : 0x7BFFu);
+    const F3 toCamera = { wp.x - k.m_CameraPosition[0], wp.y - k.m_CameraPosition[1], wp.z - k.m_CameraPosition[2] };
+    a.lvd[i] = sp::halfBits(cm::sqrt_(cm::dot3(toCamera, toCamera)));
+}
+
 int recordShadowMask(trhip::DispatchCtx& ctx)
 {
     const char* name = ctx.shaderName;
     const ShadowMaskConsts* k = (const ShadowMaskConsts*)ctx.constants(0, sizeof(ShadowMaskConsts));
     TRHIP_REQUIRE(k, "%s: constant buffer b0 (ShadowMaskConsts, 112 bytes) missing or short", name);
-    TRHIP_REQUIRE(!k->m_bDoDenoising, "%s: m_bDoDenoising is set: the SIGMA denoiser and its penumbra packing are not built", name);
+    const bool penumbra = k->m_bDoDenoising != 0u;                                                  // u0 is then the R16_FLOAT penumbra texture (ShadowMaskRenderer.cpp:259)
     const uint32_t W = k->m_OutputResolution.x, H = k->m_OutputResolution.y;
     TRHIP_REQUIRE(W && H, "%s: m_OutputResolution %ux%u is empty", name, W, H);
     if (const int rc = sp::requireCover(ctx, kTileSide, kTileSide, W, H)) return rc;
     const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 0, TRHIP_FORMAT_R32_FLOAT, "Texture_SRV t0 = the R32_FLOAT depth buffer (one mip)", true, sp::kOneMipAt0 },
                                  { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t2 = the RGBA32_UINT GBufferA (one mip)", true, sp::kOneMipAt0 },
-                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R8_UNORM, "Texture_UAV u0 = the R8_UNORM shadow mask (one mip)", true, sp::kOneMipAt0 },
+                                 penumbra ? sp::Binding{ TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R16_FLOAT, "Texture_UAV u0 = the R16_FLOAT shadow penumbra texture, which m_bDoDenoising != 0 writes in place of the mask (one mip)", true, sp::kOneMipAt0 }
+                                          : sp::Binding{ TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R8_UNORM, "Texture_UAV u0 = the R8_UNORM shadow mask (one mip)", true, sp::kOneMipAt0 },
                                  { TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R16_FLOAT, "Texture_UAV u1 = the R16_FLOAT linear view depth (one mip)", true, sp::kOneMipAt0 } };
     const sp::Binding wantNoise[] = { { TRHIP_BIND_TEXTURE_SRV, 8, TRHIP_FORMAT_RGBA8_UNORM, "Texture_SRV t8 = the RGBA8_UNORM 128x128 blue noise", true, sp::kOneMipAt0 } };
     trhip_texture_t *tex[4], *noise[1];
     if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "m_OutputResolution")) return rc;
     if (const int rc = sp::bindTextures(ctx, wantNoise, noise, kBlueNoiseSize, kBlueNoiseSize, "the blue noise")) return rc;
+    TRHIP_REQUIRE(tex[2] != tex[3], "%s: u0 and u1 are the same texture '%s'", name, tex[2]->name.c_str());
     TexturedTraceArgs a = sp::zeroed<TexturedTraceArgs>();                                          // TraceArgs + the table; sliced when none is bound
     if (const int rc = bindScene(ctx, { 1, 3, 4, 5, 6, 7, 9, 10, 11, 12 }, true, a)) return rc;
     a.k = *k;
@@ -336,15 +414,62 @@ int recordShadowMask(trhip::DispatchCtx& ctx)
         TRHIP_REQUIRE(table->entries.ptr, "%s: the texture table at t19 has no device data", name);
         a.table = (const mtex::TableEntry*)table->entries.ptr;
         a.tableCount = (uint32_t)table->slots.size();
-        sp::launch(ctx, shadowMaskKernel<true>, "shadowMaskKernel<textured>", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), a, "textured");
+        if (penumbra)
+            sp::launch(ctx, shadowPenumbraKernel<true>, "shadowPenumbraKernel<textured>", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), a, "textured_penumbra");
+        else
+            sp::launch(ctx, shadowMaskKernel<true>, "shadowMaskKernel<textured>", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), a, "textured");
         return TRHIP_OK;
     }
     const TraceArgs plain = a;
+    if (penumbra) {
+        sp::launch(ctx, shadowPenumbraKernel<false>, "shadowPenumbraKernel", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), plain, "penumbra");
+        return TRHIP_OK;
+    }
     sp::launch(ctx, shadowMaskKernel<false>, "shadowMaskKernel", sp::tiles(W, H, kTileSide, kTileSide), dim3(kTileSide, kTileSide), plain);
+    return TRHIP_OK;
+}
+
+// ---- "shadowmask_CS_PackNormalAndRoughness" (shadowmask.hlsl:147-167) -------------------------------------------------------------
+struct PackArgs { const uint4* gbufferA; uint32_t* out; uint32_t W, H; };
+
+__device__ __forceinline__ uint32_t unorm10(float v) { return (uint32_t)__builtin_rintf(sp::saturate_(v) * 1023.0f); }    // k_giprobeblend.hip's store rule
+
+__global__ __launch_bounds__(sp::kBlock) void packNormalRoughnessKernel(PackArgs a)
+{
+    const sp::Pixel at = sp::pixel();
+    if (!at.inside(a.W, a.H)) return;
+    const uint64_t i = at.index(a.W);
+    const gbuf::GBufferParams p = gbuf::unpackGBuffer(a.gbufferA[i]);
+    const F3 n = p.normal;
+    const float l1 = (__builtin_fabsf(n.x) + __builtin_fabsf(n.y)) + __builtin_fabsf(n.z);
+    const float x = cm::div_(n.x, l1), y = cm::div_(n.y, l1), z = cm::div_(n.z, l1);
+    float ox = x, oy = y;
+    if (!(z >= 0.0f)) {                                                                              // the lower hemisphere folds over
+        ox = (1.0f - __builtin_fabsf(y)) * (x >= 0.0f ? 1.0f : -1.0f);
+        oy = (1.0f - __builtin_fabsf(x)) * (y >= 0.0f ? 1.0f : -1.0f);
+    }
+    a.out[i] = unorm10(ox * 0.5f + 0.5f) | unorm10(oy * 0.5f + 0.5f) << 10 | unorm10(p.roughness) << 20;      // w = 0
+}
+
+int recordPackNormalRoughness(trhip::DispatchCtx& ctx)
+{
+    const char* name = ctx.shaderName;
+    const PackNormalAndRoughnessConsts* k = (const PackNormalAndRoughnessConsts*)ctx.constants(0, sizeof(PackNormalAndRoughnessConsts));
+    TRHIP_REQUIRE(k, "%s: b0 or push constants (PackNormalAndRoughnessConsts, 8 bytes) missing", name);
+    const uint32_t W = k->m_OutputResolution.x, H = k->m_OutputResolution.y;
+    TRHIP_REQUIRE(W && H, "%s: m_OutputResolution %ux%u is empty", name, W, H);
+    if (const int rc = sp::requireCover(ctx, kTileSide, kTileSide, W, H)) return rc;
+    const sp::Binding want[] = { { TRHIP_BIND_TEXTURE_SRV, 2, TRHIP_FORMAT_RGBA32_UINT, "Texture_SRV t2 = the RGBA32_UINT GBufferA (one mip)", true, sp::kOneMipAt0 },
+                                 { TRHIP_BIND_TEXTURE_UAV, 0, TRHIP_FORMAT_R10G10B10A2_UNORM, "Texture_UAV u0 = the R10G10B10A2_UNORM normal roughness texture (one mip)", true, sp::kOneMipAt0 } };
+    trhip_texture_t* tex[2];
+    if (const int rc = sp::bindTextures(ctx, want, tex, W, H, "m_OutputResolution")) return rc;
+    const PackArgs a = { (const uint4*)tex[0]->ptr, (uint32_t*)tex[1]->ptr, W, H };
+    sp::launch(ctx, packNormalRoughnessKernel, "packNormalRoughnessKernel", sp::tiles(W, H), dim3(sp::kTileW, sp::kTileH), a);
     return TRHIP_OK;
 }
 
 trhip::ShaderRegistrar r0("shadowmask_CS_ShadowMask", recordShadowMask, 0);
 trhip::ShaderRegistrar r1("raytracing_CS_RefitTLAS", recordRefit, 0);
+trhip::ShaderRegistrar r2("shadowmask_CS_PackNormalAndRoughness", recordPackNormalRoughness, 0);
 
 } // namespace

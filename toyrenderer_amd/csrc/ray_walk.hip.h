@@ -2,7 +2,8 @@
 // "acceleration structure"): the scene's pointers and their binding, the ray, the box test, the watertight triangle
 // test, the bounds-checked triangle fetch and walk(), the stackless two-level skip-link walk.  The sun's any-hit rays
 // (k_shadowmask.hip: occluded(), which needs the material textures) are one visitor of that walk, closestHit() below (the probe
-// trace, its shadow ray and the placement's fixed rays: k_giprobetrace.hip, k_giprobeplacement.hip) is the other.
+// trace, its shadow ray and the placement's fixed rays: k_giprobetrace.hip, k_giprobeplacement.hip) is another, and the sun's
+// penumbra rays (k_shadowmask.hip: closestCommit(), the smallest t among the candidates that pass the alpha test) are the third.
 // tests/shadowmask_ref.c holds the same pieces once in C (sm_walk, tri_candidate, fetch_tri) and is the definition;
 // k_shadowmask.hip states the arithmetic convention.
 //

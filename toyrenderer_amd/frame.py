@@ -160,7 +160,7 @@ class FrameDriver:
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
                  bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
-                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None, probes=None, taa=None):
+                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None, probes=None, taa=None, shadow_denoise=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -275,7 +275,21 @@ class FrameDriver:
         LightingOutput.  The first record() and the one after reset_taa() run with m_bResetHistory = 1.  self.taa_consts holds
         the TAAConsts of the last record(), self.taa_written the index of the history texture it wrote, self.taa_jitter its (current, previous) offsets in pixels, self.taa_view the jittered
         View it rendered with and self.taa_prev_world_to_clip its m_PrevWorldToClip; download_anti_aliased_output() and
-        download_taa_history() (the texture written last) read the results back."""
+        download_taa_history() (the texture written last) read the results back.
+
+        shadow_denoise: None (the default) changes nothing.  A dict of settings (needs shadows=...): plane_distance_sensitivity (0.02),
+        stabilization_strength (5 / 6), sigma_scale (2) and scene_radius (0: m_DenoisingRange = max(100, 2 * scene_radius)):
+        ShadowMaskRenderer::DenoiseShadows (ShadowMaskRenderer.cpp:337-500), whose NRD calls are this project's own passes
+        (csrc/k_sigma.hip; accel.py).  The trace then runs with m_bDoDenoising = 1 and writes self.shadow_penumbra (R16_FLOAT) in
+        place of the mask, and five more dispatches follow it in front of the lighting pass: "shadowmask_CS_PackNormalAndRoughness"
+        into self.normal_roughness, "SIGMA_Shadow_ClassifyTiles.cs" into self.shadow_tiles (R8_UINT) and self.shadow_data[0],
+        "SIGMA_Shadow_Blur.cs" into self.shadow_data[1], "SIGMA_Shadow_PostBlur.cs" back into self.shadow_data[0] and
+        "SIGMA_Shadow_TemporalStabilization.cs", which reads the motion target and the shadow history the previous record() wrote and
+        writes the other of the two self.shadow_history textures (R16_FLOAT) and the shadow mask the lighting pass binds.
+        m_FrameIndex is self.frame_counter, m_JitterDelta the value TAAConsts carries ((0, 0) without taa=).  The first record() and
+        the one after reset_shadow_history() run with m_bResetHistory = 1.  self.sigma_consts holds the SigmaConsts of the last
+        record() (m_Pass 0), self.shadow_history_written the index of the history texture it wrote; download_shadow_penumbra(),
+        download_shadow_tiles() and download_shadow_history() (the texture written last) read the results back."""
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
         visibility = bool(visibility) or bool(gbuffer)
@@ -372,6 +386,11 @@ class FrameDriver:
             if scene.rt is None:
                 raise ValueError("shadows=... needs GpuScene.set_raytracing(): the acceleration structure the rays walk")
             self.shadows = accelmod.check_settings(shadows)
+        self.shadow_denoise = self.sigma_consts = None
+        if shadow_denoise is not None:
+            if self.shadows is None:
+                raise ValueError("shadow_denoise=... needs shadows=...: it denoises the mask those settings trace")
+            self.shadow_denoise = accelmod.check_denoise_settings(shadow_denoise)
         self.dir_light = (tuple(float(x) for x in dir_light[0]), float(dir_light[1]))
         self.camera_origin = tuple(float(x) for x in camera_origin)
         self.shadow_mask, self.ssao = shadow_mask, ssao
@@ -427,6 +446,15 @@ class FrameDriver:
             self.blue_noise = dev.create_texture(I.kBlueNoiseSize, I.kBlueNoiseSize, 1, rhi.FORMAT_RGBA8_UNORM, "Blue Noise", uav=False)
             self.blue_noise.upload_mip(0, accelmod.noise_words(self.shadows["noise"]))
             self.shadow_mask = self.shadow_mask_texture      # what the lighting pass binds as t4
+        self.shadow_penumbra = self.normal_roughness = self.shadow_tiles = self.shadow_data = self.shadow_history = None
+        self._shadow_history_reset, self.shadow_history_written = True, 1
+        if self.shadow_denoise is not None:          # ShadowMaskRenderer::Setup's textures for the denoiser (ShadowMaskRenderer.cpp:205-233) and the two histories
+            W, H = view.renderW, view.renderH
+            self.shadow_penumbra = dev.create_texture(W, H, 1, rhi.FORMAT_R16_FLOAT, "Shadow Penumbra Texture")
+            self.normal_roughness = dev.create_texture(W, H, 1, rhi.FORMAT_R10G10B10A2_UNORM, "Normal Roughness Texture")
+            self.shadow_tiles = dev.create_texture(*accelmod.sigma_tiles(W, H), 1, rhi.FORMAT_R8_UINT, "Shadow Tiles")
+            self.shadow_data = [dev.create_texture(W, H, 1, rhi.FORMAT_RG16_FLOAT, f"Shadow Data {i}") for i in (0, 1)]
+            self.shadow_history = [dev.create_texture(W, H, 1, rhi.FORMAT_R16_FLOAT, f"Shadow History {i}") for i in (0, 1)]
         if self.lighting_on:                         # DeferredLightingRenderer::Setup (DeferredLightingRenderer.cpp:23-34)
             self.lighting_output = dev.create_texture(view.renderW, view.renderH, 1, rhi.FORMAT_R11G11B10_FLOAT, "Lighting Output")
         self.ddgi_desc = self.ddgi_data = self.ddgi_irradiance = self.ddgi_distance = None
@@ -674,15 +702,65 @@ class FrameDriver:
     def _shadow_mask(self, cl):
         v, sc, W, H = self.view, self.scene, self.view.renderW, self.view.renderH
         rt = sc.rt
+        denoise = self.shadow_denoise is not None
         self.shadow_consts = accelmod.shadow_consts(I.clip_to_world(v.worldToView, v.viewToClip), self.dir_light[0], self.camera_origin, W, H, self.shadows,
-                                                    self.frame_counter)
+                                                    self.frame_counter, denoise)
         cb = cl.constant_buffer(self.shadow_consts, "ShadowMaskConsts")
         cl.dispatch("shadowmask_CS_ShadowMask",
                     [CB(0, cb), TEX_SRV(0, self.depth), SRV(1, rt["tlas_nodes"]), TEX_SRV(2, self.gbufferA), SRV(3, sc.instances), SRV(4, sc.vertices),
-                     SRV(5, sc.materials), SRV(6, sc.indices), SRV(7, sc.meshData), TEX_SRV(8, self.blue_noise), TEX_UAV(0, self.shadow_mask_texture, 0),
+                     SRV(5, sc.materials), SRV(6, sc.indices), SRV(7, sc.meshData), TEX_SRV(8, self.blue_noise),
+                     TEX_UAV(0, self.shadow_penumbra if denoise else self.shadow_mask_texture, 0),
                      TEX_UAV(1, self.linear_view_depth, 0), SRV(9, rt["tlas_instances"]), SRV(10, rt["headers"]), SRV(11, rt["blas_nodes"]),
                      SRV(12, rt["tri_order"]), SAMPLER(0), SAMPLER(1)] + ([TEX_TABLE(sc.texture_table)] if self.alpha_test and sc.textured else []),
                     ((W + 7) // 8, (H + 7) // 8, 1))
+
+    # ---- ShadowMaskRenderer::DenoiseShadows (ShadowMaskRenderer.cpp:337-500): PackNormalRoughness and the denoiser's four dispatches ----
+    def _denoise_shadows(self, cl):
+        v, W, H = self.view, self.view.renderW, self.view.renderH
+        groups = ((W + 7) // 8, (H + 7) // 8, 1)
+        pk = np.zeros(1, I.PackNormalAndRoughnessConsts)
+        pk["m_OutputResolution"] = (W, H)
+        cl.dispatch("shadowmask_CS_PackNormalAndRoughness", [PUSH(0), TEX_SRV(2, self.gbufferA), TEX_UAV(0, self.normal_roughness, 0)], groups, push=pk)
+        delta = taamod.jitter_delta(*self.taa_jitter) if self.taa is not None else (0.0, 0.0)
+        k = [accelmod.sigma_consts(I.clip_to_world(v.worldToView, v.viewToClip), v.viewToClip, W, H, self.shadow_denoise, self.frame_counter, p,
+                                   self._shadow_history_reset, delta) for p in (0, 1)]
+        self.sigma_consts = k[0]
+        cb = [cl.constant_buffer(x, "SigmaConsts") for x in k]
+        lvd, tiles, data = self.linear_view_depth, self.shadow_tiles, self.shadow_data
+        tw, th = accelmod.sigma_tiles(W, H)
+        cl.dispatch("SIGMA_Shadow_ClassifyTiles.cs", [CB(0, cb[0]), TEX_SRV(0, self.shadow_penumbra), TEX_SRV(1, lvd), TEX_UAV(0, tiles, 0), TEX_UAV(1, data[0], 0)], (tw, th, 1))
+        for p, name in enumerate(("SIGMA_Shadow_Blur.cs", "SIGMA_Shadow_PostBlur.cs")):
+            cl.dispatch(name, [CB(0, cb[p]), TEX_SRV(0, data[p]), TEX_SRV(1, lvd), TEX_SRV(2, self.depth), TEX_SRV(3, self.normal_roughness), TEX_SRV(4, tiles),
+                               TEX_UAV(0, data[1 - p], 0)], groups)
+        read, write = self.shadow_history[self.shadow_history_written], self.shadow_history[1 - self.shadow_history_written]
+        cl.dispatch("SIGMA_Shadow_TemporalStabilization.cs",
+                    [CB(0, cb[0]), TEX_SRV(0, data[0]), TEX_SRV(1, lvd), TEX_SRV(2, self.motion), TEX_SRV(3, read), TEX_SRV(4, tiles), TEX_UAV(0, write, 0),
+                     TEX_UAV(1, self.shadow_mask_texture, 0)], groups)
+        self.shadow_history_written, self._shadow_history_reset = 1 - self.shadow_history_written, False
+
+    def reset_shadow_history(self):
+        """The next record() runs the stabilisation with m_bResetHistory = 1: no texel's shadow history is valid."""
+        if self.shadow_denoise is None:
+            raise ValueError("reset_shadow_history: shadow denoising is off (shadow_denoise=None)")
+        self._shadow_history_reset = True
+
+    def _denoise_download(self, what, tex):
+        if self.shadow_denoise is None:
+            raise ValueError(f"{what}: shadow denoising is off (shadow_denoise=None)")
+        self.dev.wait_idle()
+        return tex().download_mip(0)
+
+    def download_shadow_penumbra(self) -> np.ndarray:
+        """The binary16 words of the penumbra texture the trace wrote, (H, W) uint16."""
+        return self._denoise_download("download_shadow_penumbra", lambda: self.shadow_penumbra)
+
+    def download_shadow_tiles(self) -> np.ndarray:
+        """The tile bytes of the last record(), (ceil(H / 16), ceil(W / 16)) uint8."""
+        return self._denoise_download("download_shadow_tiles", lambda: self.shadow_tiles)
+
+    def download_shadow_history(self) -> np.ndarray:
+        """The binary16 words of the shadow history the last record() wrote, (H, W) uint16."""
+        return self._denoise_download("download_shadow_history", lambda: self.shadow_history[self.shadow_history_written])
 
     # ---- GIRenderer::RenderDDGI (GIRenderer.cpp): the probe trace and the two blends ---------------------------------------------
     def _ddgi_update(self, cl):
@@ -996,6 +1074,8 @@ class FrameDriver:
             self._refit_tlas(cl)
         if self.shadows is not None:                                                     # Scene.cpp:500: behind AO, in front of lighting
             self._shadow_mask(cl)
+            if self.shadow_denoise is not None:
+                self._denoise_shadows(cl)
         if self.ddgi_update is not None:                                                 # behind the refit, in front of lighting
             self._ddgi_update(cl)
         if self.lighting_on:
@@ -1046,6 +1126,7 @@ class FrameDriver:
                   self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
                   self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays, self.ddgi_fixed_rays,
                   self.probe_positions, self.probe_states, self.probe_culled_positions, self.probe_draw_args, self.probe_instance_to_probe, self.probe_sphere_vertices,
-                  self.probe_sphere_indices, self.probe_winners, self.anti_aliased_output, *(self.taa_history or ())):
+                  self.probe_sphere_indices, self.probe_winners, self.anti_aliased_output, *(self.taa_history or ()), self.shadow_penumbra, self.normal_roughness,
+                  self.shadow_tiles, *(self.shadow_data or ()), *(self.shadow_history or ())):
             if t is not None:
                 t.release()

@@ -39,6 +39,8 @@ HOST_SYMBOLS = [
     "trhost_load_sky_dataset", "trhost_set_sky", "trhost_get_sky_consts",
     "trhost_set_ambient_occlusion", "trhost_download_ssao", "trhost_get_gtao_consts",
     "trhost_load_raytracing", "trhost_upload_blue_noise", "trhost_set_shadow_mask", "trhost_download_shadow_mask", "trhost_get_shadow_mask_consts",
+    "trhost_set_shadow_denoising", "trhost_reset_shadow_history", "trhost_download_shadow_penumbra", "trhost_download_shadow_tiles", "trhost_download_shadow_history",
+    "trhost_get_sigma_consts",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p)   # trhost_allgather_fn
@@ -142,6 +144,12 @@ def load() -> C.CDLL:
     L.trhost_set_shadow_mask.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float]
     L.trhost_download_shadow_mask.argtypes = [vp, u64]
     L.trhost_get_shadow_mask_consts.argtypes = [vp]
+    L.trhost_set_shadow_denoising.argtypes = [C.c_int, C.c_float, C.c_float, C.c_float]
+    L.trhost_reset_shadow_history.argtypes = []
+    L.trhost_download_shadow_penumbra.argtypes = [vp, u64]
+    L.trhost_download_shadow_tiles.argtypes = [vp, u64]
+    L.trhost_download_shadow_history.argtypes = [vp, u64]
+    L.trhost_get_sigma_consts.argtypes = [vp]
     L.trhost_get_scene_luminance.argtypes = [vp, vp]
     L.trhost_reset_exposure.argtypes = []
     L.trhost_get_post_process_consts.argtypes = [vp, vp, vp, vp]
@@ -557,6 +565,40 @@ class Renderer:
         """The ShadowMaskConsts of the last frame; raises if the pass did not run in it."""
         k = np.zeros(1, I.ShadowMaskConsts)
         _check(load().trhost_get_shadow_mask_consts(k.ctypes.data))
+        return k
+
+
+    def set_shadow_denoising(self, enable: bool, plane_distance_sensitivity: float = 0.02, stabilization_strength: float = 5.0 / 6.0, sigma_scale: float = 2.0):
+        """ShadowMaskRenderer's DenoiseShadows on or off (needs set_shadow_mask(True)): the pack pass and the four dispatches of
+        csrc/k_sigma.hip behind the trace."""
+        _check(load().trhost_set_shadow_denoising(int(bool(enable)), float(plane_distance_sensitivity), float(stabilization_strength), float(sigma_scale)))
+
+    def reset_shadow_history(self):
+        """The next frame's stabilisation reads no history."""
+        _check(load().trhost_reset_shadow_history())
+
+    def _download_denoiser(self, fn, shape, dtype) -> np.ndarray:
+        self.wait_idle()
+        out = np.empty(shape, dtype)
+        _check(fn(out.ctypes.data, out.nbytes))
+        return out
+
+    def download_shadow_penumbra(self) -> np.ndarray:
+        """The last frame's penumbra texture: binary16 words uint16 [H, W]; raises if the denoiser did not run in it."""
+        return self._download_denoiser(load().trhost_download_shadow_penumbra, (self.render[1], self.render[0]), np.uint16)
+
+    def download_shadow_tiles(self) -> np.ndarray:
+        """The last frame's tile bytes: uint8 [ceil(H / 16), ceil(W / 16)]."""
+        return self._download_denoiser(load().trhost_download_shadow_tiles, ((self.render[1] + 15) // 16, (self.render[0] + 15) // 16), np.uint8)
+
+    def download_shadow_history(self) -> np.ndarray:
+        """The shadow history the last frame wrote: binary16 words uint16 [H, W]."""
+        return self._download_denoiser(load().trhost_download_shadow_history, (self.render[1], self.render[0]), np.uint16)
+
+    def sigma_consts(self) -> np.ndarray:
+        """The SigmaConsts (m_Pass 0) of the last frame; raises if the denoiser did not run in it."""
+        k = np.zeros(1, I.SigmaConsts)
+        _check(load().trhost_get_sigma_consts(k.ctypes.data))
         return k
 
     def bloom_consts(self, passes: int) -> np.ndarray:

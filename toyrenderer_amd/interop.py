@@ -107,6 +107,11 @@ ShadowMaskConsts = np.dtype([                                                   
     ("m_ClipToWorld", np.float32, (4, 4)), ("m_DirectionalLightDirection", np.float32, (3,)), ("m_NoisePhase", np.float32),
     ("m_CameraPosition", np.float32, (3,)), ("m_TanSunAngularRadius", np.float32), ("m_OutputResolution", np.uint32, (2,)),
     ("m_bDoDenoising", np.uint32), ("m_RayStartOffset", np.float32)])
+PackNormalAndRoughnessConsts = np.dtype([("m_OutputResolution", np.uint32, (2,))])                                        # ShaderInterop.h:229-232
+SigmaConsts = np.dtype([                                                                                                   # the project's own (csrc/k_sigma.hip)
+    ("m_ClipToWorld", np.float32, (4, 4)), ("m_OutputDims", np.uint32, (2,)), ("m_JitterDelta", np.float32, (2,)), ("m_PixelUnproject", np.float32),
+    ("m_DenoisingRange", np.float32), ("m_PlaneDistanceSensitivity", np.float32), ("m_StabilizationStrength", np.float32), ("m_SigmaScale", np.float32),
+    ("m_FrameIndex", np.uint32), ("m_Pass", np.uint32), ("m_bResetHistory", np.uint32)])
 # this build's acceleration structure (include/trhip.h, "acceleration structure")
 RefitTLASConstants = np.dtype([("m_NumInstances", np.uint32), ("m_NumNodes", np.uint32), ("m_NumLevels", np.uint32)])
 AccelNode = np.dtype([("lo", np.float32, (3,)), ("skip", np.uint32), ("hi", np.float32, (3,)), ("leaf", np.uint32)])
@@ -137,7 +142,7 @@ SIZES = {
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
     "BloomConsts": 16, "TAAConsts": 32, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
     "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
-    "ShadowMaskConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96, "GIProbeVisualizationConsts": 96, "UncompressedRawVertexFormat": 32, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
+    "ShadowMaskConsts": 112, "PackNormalAndRoughnessConsts": 8, "SigmaConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96, "GIProbeVisualizationConsts": 96, "UncompressedRawVertexFormat": 32, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)

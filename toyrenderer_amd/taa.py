@@ -60,10 +60,15 @@ def begin_frame(view, frame_counter: int, settings: dict, last):
     return jittered, (current, previous), prev_world_to_clip, (current, world_to_clip)
 
 
+def jitter_delta(current, previous):
+    """m_JitterDelta: the previous minus the current jitter offset in pixels, in binary32 (TAAConsts and SigmaConsts carry it)."""
+    return (F(F(previous[0]) - F(current[0])), F(F(previous[1]) - F(current[1])))
+
+
 def consts(W: int, H: int, settings: dict, current, previous, reset: bool) -> np.ndarray:
     k = np.zeros(1, I.TAAConsts)
     k["m_OutputDims"] = (W, H)
-    k["m_JitterDelta"] = (F(F(previous[0]) - F(current[0])), F(F(previous[1]) - F(current[1])))
+    k["m_JitterDelta"] = jitter_delta(current, previous)
     k["m_MinBlend"] = settings["min_blend"]
     k["m_MaxSampleCount"] = settings["max_sample_count"]
     k["m_bResetHistory"] = int(bool(reset))
