@@ -34,6 +34,7 @@ typedef struct trhip_cmdlist_t* trhip_cmdlist;
 typedef struct trhip_timer_t*   trhip_timer;
 typedef struct trhip_pipeline_stats_t* trhip_pipeline_stats;
 typedef struct trhip_texture_table_t* trhip_texture_table;
+typedef struct trhip_readback_t* trhip_readback;
 
 enum {
     TRHIP_OK = 0,
@@ -139,6 +140,13 @@ uint32_t    trhip_abi_version(void);
  * direct dispatch of (4, counts.x * counts.z, counts.y) groups.  Blends: t1 the ray records, t3 the probe data, u1 the
  * irradiance (radiance blend) or u2 the distance (distance blend) array, created with the UAV bit; (counts.x, counts.z,
  * counts.y) groups.  An array texture is accepted only at a binding that a pass declares, in the declared format.
+ * With the descriptor's flags bit 2 (kDDGIFlag_Variability) the radiance blend also writes u4, a structured buffer
+ * float[counts.y][6 * counts.z][6 * counts.x] of probe variability (a coefficient of variation per interior texel), and
+ * "ReductionCS_DDGIReductionCS REDUCTION=1" / "ReductionCS_DDGIExtraReductionCS" (GIRenderer.cpp:542-573; csrc/k_ddgireduction.hip
+ * states the bindings and the order of every addition, tests/ddgi_variability_ref.c is the definition) average it: push constants
+ * b1 the SDK's 24-byte DDGIRootConstants, t4 the input, u5 a structured buffer of float2 (average, weight) per workgroup, a direct
+ * dispatch of ceil(input / (16, 16, 4)) groups; the first pass also takes b0 (the same 160 bytes) and t3 the probe data.  Every
+ * other pass accepts bit 2 and ignores it.
  * "giprobetrace_CS_ProbeTraceFixedRays", "ProbeRelocationCS_DDGIProbeRelocationCS" and
  * "ProbeClassificationCS_DDGIProbeClassificationCS" (GIRenderer.cpp:513-527: probe relocation and classification behind the blends;
  * csrc/k_giprobeplacement.hip states the bindings and the arithmetic, tests/ddgi_placement_ref.c is the definition).  b0 of all
@@ -404,6 +412,23 @@ int  trhip_cmd_end_pipeline_stats(trhip_cmdlist cl, trhip_pipeline_stats q);    
 /* getPipelineStatistics: waits for the end of the last executed end; TRHIP_ERR_STATE if the query was never ended in an
  * executed list. */
 int  trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics* out);
+
+/* ---- read-back: nvrhi::StagingTexture / a CpuAccessMode::Read buffer (GIRenderer.cpp:531-540, :575) ----------------------
+ * Pinned host memory of `slots` slots of bytes_per_slot bytes, one event per slot.  trhip_cmd_copy_to_readback records an
+ * asynchronous device-to-host copy of `bytes` (<= bytes_per_slot) from src_buffer at src_offset into the slot, on the list's
+ * stream, and the slot's event behind it.  trhip_readback_read (mapStagingTexture) waits for THAT SLOT'S event only -- never for
+ * the device, so a frame that reads what it copied two frames ago does not wait for the frame in flight -- and copies
+ * min(bytes, what the slot's last executed copy wrote) to dst; *written receives that count.  A slot that no executed list has
+ * written yet gives *written = 0 and `bytes` zero bytes in dst.  A slot is the caller's to pace: a copy into a slot that is
+ * being read is not ordered against the read.  trhip_readback_reset waits for the device and marks every slot as never
+ * written (the events and the memory stay, so a recorded list that names the resource stays valid).  Release waits for the
+ * device; a recorded list holds the source buffer but NOT the read-back resource: every list that names it must have been
+ * re-opened or released before it is released. */
+int  trhip_readback_create(trhip_device dev, uint64_t bytes_per_slot, uint32_t slots, trhip_readback* out);
+void trhip_readback_release(trhip_readback rb);
+int  trhip_readback_reset(trhip_readback rb);
+int  trhip_cmd_copy_to_readback(trhip_cmdlist cl, trhip_readback rb, uint32_t slot, trhip_buffer src_buffer, uint64_t src_offset, uint64_t bytes);
+int  trhip_readback_read(trhip_readback rb, uint32_t slot, void* dst, uint64_t bytes, uint64_t* written);
 
 /* ---- acceleration structure: nvrhi::rt::AccelStruct (Visual.cpp:509-542 Mesh::BuildBLAS, Scene.cpp:430-470 the TLAS) ----------
  * DXR's structure is opaque; this one is the project's own and lives in ordinary structured buffers that the caller creates,

@@ -151,6 +151,30 @@ int  trhost_set_ddgi_probe_placement(int relocation, int classification, float m
 int  trhost_reset_ddgi_volume(void);
 int  trhost_download_ddgi_volume(uint32_t* irradiance, uint64_t irradiance_bytes, uint16_t* distance, uint64_t distance_bytes, uint16_t* data, uint64_t data_bytes);
 int  trhost_get_ddgi_update_consts(void* out96);
+/* Probe variability, the reference's convergence early-out (GIRenderer.cpp:84, :158-190, :466-470, :529-576;
+ * csrc/host/DDGIVariability.h is the rule, DESIGN.md 12's eighteenth amendment the reasoning).  An option, off by default.
+ * trhost_set_ddgi_probe_variability(enable, stddev_threshold) needs the probe update on (refused without it) and a threshold that
+ * is finite and >= 0 (the reference's is 0.001).  On, the volume's descriptor gains flags bit 2 on the host and on the device,
+ * the radiance blend writes a coefficient of variation per interior texel, the reduction passes average it over the active
+ * probes, and the average goes into one of two read-back slots; every update call first runs the rule on the ring of the last
+ * 16 averages (the one read is two calls old, 0 before that) and, once the ring's standard deviation is below the threshold
+ * -- on the 18th call at the earliest --, records NOTHING: no refit, trace, blend, placement, reduction or copy.  Lighting goes
+ * on reading the volume.  A converged volume never wakes by itself, as in the reference; waking on a light or transform change
+ * is not built: trhost_reset_ddgi_variability re-arms it (the whole tracker and the variability buffer start again), and so do
+ * trhost_reset_ddgi_volume and every call of trhost_set_ddgi_probe_variability.  trhost_upload_ddgi_volume installs a fresh volume
+ * with the option OFF (it strips flags bit 2 from the descriptor it is given): call trhost_set_ddgi_probe_variability again.  A skipped update does not advance
+ * the ray rotation's count.  trhost_get_ddgi_variability: the last average read, the ring's standard deviation, the verdict, the
+ * rule's sample count and the number of skipped updates (any pointer may be null).
+ * trhost_ddgi_variability_run touches no device: it runs the rule over averages[0..n) from a fresh tracker -- per element one
+ * Update and, unless that Update found the ring converged (the driver then records nothing and stores nothing), one
+ * SetVariabilityForCurrentFrame -- and writes the verdict and the deviation after each Update.
+ * trhost_download_ddgi_variability reads the variability buffer back (counts.y x 6 counts.z x 6 counts.x floats; it waits for the
+ * device, so it is for tests and tools, not for the frame path). */
+int  trhost_set_ddgi_probe_variability(int enable, float stddev_threshold);
+int  trhost_get_ddgi_variability(float* average, float* stddev, int* converged, uint32_t* samples, uint32_t* skipped);
+int  trhost_reset_ddgi_variability(void);
+int  trhost_ddgi_variability_run(const float* averages, uint32_t n, float threshold, uint8_t* converged, float* stddev);
+int  trhost_download_ddgi_variability(float* variability, uint64_t variability_bytes);
 
 /* The probe visualisation: GIDebugRenderer (source/GIRenderer.cpp:598-808) on the DDGI volume as it is on the device this frame.
  * trhost_set_ddgi_probe_visualization(enable, probe_radius, hide_inactive): off by default.  On, every frame records behind

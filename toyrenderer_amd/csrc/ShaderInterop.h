@@ -146,12 +146,12 @@ struct DDGIVolumeDesc
     float probeIrradianceEncodingGamma;
     uint32_t numIrradianceInteriorTexels;    // 6 in the reference
     uint32_t numDistanceInteriorTexels;      // 14 in the reference
-    uint32_t flags;                          // bit 0 relocation enabled, bit 1 classification enabled
+    uint32_t flags;                          // bit 0 relocation enabled, bit 1 classification enabled, bit 2 probe variability (the radiance blend writes u4)
     uint32_t pad;
 };
 static_assert(sizeof(DDGIVolumeDesc) == 64 && offsetof(DDGIVolumeDesc, probeSpacing) == 16 && offsetof(DDGIVolumeDesc, probeCounts) == 32 &&
               offsetof(DDGIVolumeDesc, numIrradianceInteriorTexels) == 48 && offsetof(DDGIVolumeDesc, flags) == 56, "DDGIVolumeDesc");
-static constexpr uint32_t kDDGIFlag_Relocation = 1u, kDDGIFlag_Classification = 2u;
+static constexpr uint32_t kDDGIFlag_Relocation = 1u, kDDGIFlag_Classification = 2u, kDDGIFlag_Variability = 4u;
 static constexpr uint32_t kDDGIIrradianceInteriorTexels = 6, kDDGIDistanceInteriorTexels = 14, kDDGIMaxProbeCount = 1024;
 
 // The project's own: b0 of "giprobetrace_CS_ProbeTrace", of the two "ProbeBlendingCS_DDGIProbeBlendingCS" passes and of the three
@@ -180,6 +180,22 @@ static_assert(sizeof(DDGIUpdateConsts) == 96 && offsetof(DDGIUpdateConsts, rayRo
 static constexpr uint32_t kDDGIRaysPerProbe = 256;              // RTXGI_DDGI_BLEND_RAYS_PER_PROBE
 static constexpr uint32_t kDDGIBackfaceRayLimit = 25;           // (uint)(256 * probeRandomRayBackfaceThreshold), 0.1f: GIRenderer.cpp:120
 static constexpr uint32_t kDDGIFixedRays = 32;                  // RTXGI_DDGI_NUM_FIXED_RAYS: the unrotated rays of relocation and classification
+
+// The RTXGI SDK's DDGIRootConstants (rtxgi/ddgi/DDGIRootConstants.h; GIRenderer.cpp:483, :553-555): push constants of the two
+// reduction passes (k_ddgireduction.hip), which read the three input sizes; the three indices are accepted and ignored.
+struct DDGIRootConstants
+{
+    uint32_t volumeIndex;
+    uint32_t volumeConstantsIndex;
+    uint32_t volumeResourceIndicesIndex;
+    uint32_t reductionInputSizeX;
+    uint32_t reductionInputSizeY;
+    uint32_t reductionInputSizeZ;
+};
+static_assert(sizeof(DDGIRootConstants) == 24 && offsetof(DDGIRootConstants, reductionInputSizeX) == 12, "DDGIRootConstants");
+// Probe variability (GIRenderer.cpp:158-190, :542-573): the ring's length, and the reduction's group and per-thread footprint
+static constexpr uint32_t kDDGIMinimumVariabilitySamples = 16;
+static constexpr uint32_t kDDGIReductionThreadsX = 4, kDDGIReductionThreadsY = 8, kDDGIReductionThreadsZ = 4, kDDGIReductionFootprintX = 4, kDDGIReductionFootprintY = 2;
 
 // ShaderInterop.h:124-129: push constants of "adaptluminance_CS_GenerateLuminanceHistogram"
 struct GenerateLuminanceHistogramParameters

@@ -15,7 +15,11 @@
 // constant block (DDGIUpdateConsts, the descriptor's host copy behind it).  With trhost_set_ddgi_probe_placement the reference's
 // relocation and classification (:513-527) follow the blends: "giprobetrace_CS_ProbeTraceFixedRays", the project's own trace of 32
 // unrotated rays from every probe, then "ProbeRelocationCS_DDGIProbeRelocationCS" and "ProbeClassificationCS_DDGIProbeClassificationCS"
-// (csrc/k_giprobeplacement.hip).  Variability is not built.  The frame's ray rotation is a uniformly distributed rotation (Shoemake's three-uniform form) from a splitmix64 stream
+// (csrc/k_giprobeplacement.hip).  With trhost_set_ddgi_probe_variability the reference's probe variability (:158-190, :466-470, :529-576): the
+// radiance blend also writes a coefficient of variation per interior texel (u4), "ReductionCS_DDGIReductionCS REDUCTION=1" and
+// "ReductionCS_DDGIExtraReductionCS" (csrc/k_ddgireduction.hip) average it over the active probes, element 0 goes into one of two
+// read-back slots, the slot written two updates earlier feeds the ring of DDGIVariability.h, and an update that finds the ring
+// converged records nothing.  The frame's ray rotation is a uniformly distributed rotation (Shoemake's three-uniform form) from a splitmix64 stream
 // keyed by (seed, update count), evaluated in double and rounded once; trhost_get_ddgi_update_consts shows the block that ran.
 #include "CommonResources.h"
 #include "Graphic.h"
@@ -263,8 +267,19 @@ public:
     void Render(nvrhi::CommandListHandle commandList, const RenderGraph&) override
     {
         using Item = nvrhi::BindingSetItem;
-        const Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+        Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
         const nvrhi::rt::AccelStruct& as = *g_Scene->m_TLAS;
+        DDGIVariability& tracker = volume.m_Variability;
+        const bool variability = tracker.m_bProbeVariabilityEnabled;
+        uint32_t call = 0;                                                    // this update call's number since the last reset
+        if (variability) {                                                    // :464-470
+            tracker.Update();
+            call = volume.m_NumUpdateCalls++;
+            if (tracker.bIsConverged) {                                       // nothing of the update is recorded, the refit included
+                ++volume.m_NumUpdatesSkipped;
+                return;
+            }
+        }
         if (!GetScheduledShadowMaskTexture()) RecordRefitTLAS(commandList);   // ShadowMaskRenderer, scheduled in front, refits otherwise
 
         struct Block { DDGIUpdateConsts k; DDGIVolumeDesc desc; } block{};
@@ -326,11 +341,19 @@ public:
                 Item::Texture_SRV(3, volume.m_ProbeData),
                 radiance ? Item::Texture_UAV(1, volume.m_ProbeIrradiance) : Item::Texture_UAV(2, volume.m_ProbeDistance),
             };
+            if (radiance && variability) blend.m_BindingSetDesc.bindings.push_back(Item::StructuredBuffer_UAV(4, volume.m_ProbeVariability));
             blend.m_DispatchGroupSize = Vector3U{ cx, cz, cy };
             g_Graphic.AddComputePass(blend);
         }
-        if (!placement) return;
+        if (placement) RecordPlacement(commandList, cb, cx, cy, cz);
+        if (variability) RecordVariability(commandList, cb, call, cx, cy, cz);
+    }
 
+    void RecordPlacement(nvrhi::CommandListHandle commandList, nvrhi::BufferHandle cb, uint32_t cx, uint32_t cy, uint32_t cz)
+    {
+        using Item = nvrhi::BindingSetItem;
+        const Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+        const nvrhi::rt::AccelStruct& as = *g_Scene->m_TLAS;
         const uint32_t numProbes = cx * cy * cz;                              // :513-527: relocation and classification behind the blends
         Graphic::ComputePassParams fixed;
         fixed.m_CommandList = commandList;
@@ -365,6 +388,53 @@ public:
             place.m_DispatchGroupSize = Vector3U{ (numProbes + 31) / 32, 1, 1 };   // the reference's group count
             g_Graphic.AddComputePass(place);
         }
+    }
+
+    // :529-576: the sample of two update calls ago goes into the ring, then this call's reductions and the copy of their result
+    void RecordVariability(nvrhi::CommandListHandle commandList, nvrhi::BufferHandle cb, uint32_t call, uint32_t cx, uint32_t cy, uint32_t cz)
+    {
+        using Item = nvrhi::BindingSetItem;
+        Scene::RTDDGIVolume& volume = g_Scene->m_RTDDGIVolume;
+        const uint32_t slot = call % 2;                                       // g_Graphic.m_FrameCounter % 2
+        float readback = 0.0f;                                                // a slot never written reads 0
+        g_Graphic.m_NVRHIDevice->readStagingBuffer(volume.m_ProbeVariabilityReadback, slot, &readback, sizeof readback);
+        volume.m_Variability.m_AverageVariability = readback;
+        volume.m_Variability.SetVariabilityForCurrentFrame(readback);
+
+        const Vector3U kNumThreadsInGroup = { kDDGIReductionThreadsX, kDDGIReductionThreadsY, kDDGIReductionThreadsZ };
+        const Vector2U kThreadSampleFootprint = { kDDGIReductionFootprintX, kDDGIReductionFootprintY };
+        uint32_t inputTexelsX = cx * kDDGIIrradianceInteriorTexels, inputTexelsY = cz * kDDGIIrradianceInteriorTexels, inputTexelsZ = cy;
+        DDGIRootConstants rootConsts{};
+        bool bIsFirstPass = true;
+        uint32_t numPasses = 0;
+        while (inputTexelsX > 1 || inputTexelsY > 1 || inputTexelsZ > 1) {
+            const uint32_t outputTexelsX = (inputTexelsX + kNumThreadsInGroup.x * kThreadSampleFootprint.x - 1) / (kNumThreadsInGroup.x * kThreadSampleFootprint.x);
+            const uint32_t outputTexelsY = (inputTexelsY + kNumThreadsInGroup.y * kThreadSampleFootprint.y - 1) / (kNumThreadsInGroup.y * kThreadSampleFootprint.y);
+            const uint32_t outputTexelsZ = (inputTexelsZ + kNumThreadsInGroup.z - 1) / kNumThreadsInGroup.z;
+            rootConsts.reductionInputSizeX = inputTexelsX;
+            rootConsts.reductionInputSizeY = inputTexelsY;
+            rootConsts.reductionInputSizeZ = inputTexelsZ;
+            Graphic::ComputePassParams reduce;
+            reduce.m_CommandList = commandList;
+            reduce.m_ShaderName = bIsFirstPass ? "ReductionCS_DDGIReductionCS REDUCTION=1" : "ReductionCS_DDGIExtraReductionCS";
+            reduce.m_BindingSetDesc.bindings = {                              // the averages ping-pong: a pass never reads the buffer it writes
+                Item::PushConstants(1, sizeof rootConsts),
+                Item::StructuredBuffer_SRV(4, bIsFirstPass ? volume.m_ProbeVariability : volume.m_ProbeVariabilityAverage[(numPasses + 1) % 2]),
+                Item::StructuredBuffer_UAV(5, volume.m_ProbeVariabilityAverage[numPasses % 2]),
+            };
+            if (bIsFirstPass) {                                               // which probes classification has switched off
+                reduce.m_BindingSetDesc.bindings.push_back(Item::ConstantBuffer(0, cb));
+                reduce.m_BindingSetDesc.bindings.push_back(Item::Texture_SRV(3, volume.m_ProbeData));
+            }
+            reduce.m_PushConstantsData = &rootConsts;
+            reduce.m_PushConstantsBytes = sizeof rootConsts;
+            reduce.m_DispatchGroupSize = Vector3U{ outputTexelsX, outputTexelsY, outputTexelsZ };
+            g_Graphic.AddComputePass(reduce);
+            inputTexelsX = outputTexelsX; inputTexelsY = outputTexelsY; inputTexelsZ = outputTexelsZ;
+            bIsFirstPass = false;
+            ++numPasses;
+        }
+        commandList->copyToStagingBuffer(volume.m_ProbeVariabilityReadback, slot, volume.m_ProbeVariabilityAverage[(numPasses + 1) % 2], 0, sizeof(float));
     }
 };
 DEFINE_RENDERER(GIRenderer);

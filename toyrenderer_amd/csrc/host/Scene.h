@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../ShaderInterop.h"
+#include "DDGIVariability.h"
 #include "MathUtilities.h"
 #include "RenderGraph.h"
 #include "nvrhi_lite.h"
@@ -126,6 +127,14 @@ public:
         nvrhi::TextureHandle m_ProbeData, m_ProbeIrradiance, m_ProbeDistance;   // t6, t7, t8
         nvrhi::BufferHandle m_RayData;               // float4[numProbes * 256]: the trace's u0, the blends' t1
         nvrhi::BufferHandle m_FixedRayData;          // float[numProbes * 32]: u0 of the fixed-ray trace, of relocation and of classification
+        // Probe variability (trhost_set_ddgi_probe_variability; GIRenderer.cpp:158-190, :529-576): the radiance blend's u4,
+        // float[counts.y][6 * counts.z][6 * counts.x], zero on creation and after a reset; the reductions' two average buffers
+        // (float2 per workgroup, ping-pong); the two-slot read-back of element 0; and the convergence rule with its counters.
+        nvrhi::BufferHandle m_ProbeVariability, m_ProbeVariabilityAverage[2];
+        nvrhi::StagingBufferHandle m_ProbeVariabilityReadback;
+        DDGIVariability m_Variability;
+        uint32_t m_NumUpdateCalls = 0;               // update calls since the last reset: the read-back slot is this % 2
+        uint32_t m_NumUpdatesSkipped = 0;            // of them, the converged ones, which recorded nothing
         bool IsValid() const { return m_DescBuffer && m_ProbeData && m_ProbeIrradiance && m_ProbeDistance; }
     } m_RTDDGIVolume;
     // GIRenderer::RenderDDGI (trhost_set_ddgi_update; needs the volume, m_TLAS and m_bDeferredLighting): frame n's ray rotation

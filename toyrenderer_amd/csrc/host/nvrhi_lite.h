@@ -265,6 +265,20 @@ private:
     trhip_pipeline_stats m_Native;
 };
 
+// nvrhi's staging resource (IStagingTexture, a CpuAccessMode::Read buffer): trhip_readback, `slots` slots of pinned host memory.
+class IStagingBuffer : public IResource
+{
+public:
+    IStagingBuffer(trhip_readback rb, uint64_t bytesPerSlot, uint32_t slots) : m_BytesPerSlot(bytesPerSlot), m_Slots(slots), m_Native(rb) {}
+    ~IStagingBuffer() override { trhip_readback_release(m_Native); }
+    trhip_readback native() const { return m_Native; }
+    const uint64_t m_BytesPerSlot;
+    const uint32_t m_Slots;
+
+private:
+    trhip_readback m_Native;
+};
+
 using HeapHandle = RefCountPtr<IHeap>;
 using BufferHandle = RefCountPtr<IBuffer>;
 using TextureHandle = RefCountPtr<ITexture>;
@@ -272,6 +286,7 @@ using SamplerHandle = RefCountPtr<ISampler>;
 using DescriptorTableHandle = RefCountPtr<IDescriptorTable>;
 using TimerQueryHandle = RefCountPtr<ITimerQuery>;
 using PipelineStatisticsQueryHandle = RefCountPtr<IPipelineStatisticsQuery>;
+using StagingBufferHandle = RefCountPtr<IStagingBuffer>;
 
 // ---- nvrhi::rt::AccelStruct (Scene.h:157 m_TLAS, Visual.h m_BLAS): DXR's structure is opaque; this one is the back end's own
 // (include/trhip.h, "acceleration structure") and lives in ordinary buffers.  One object holds the whole scene's structure: the TLAS
@@ -356,6 +371,12 @@ public:
     {
         keep(dst); keep(src);
         throwIfFailed(trhip_cmd_copy_buffer(m_Native, dst->native(), dstOff, src->native(), srcOff, bytes), "ICommandList::copyBuffer");
+    }
+    // copyTexture into a staging texture (GIRenderer.cpp:575): an asynchronous copy into one slot, the slot's event behind it
+    void copyToStagingBuffer(IStagingBuffer* dst, uint32_t slot, IBuffer* src, uint64_t srcOff, uint64_t bytes)
+    {
+        keep(dst); keep(src);
+        throwIfFailed(trhip_cmd_copy_to_readback(m_Native, dst->native(), slot, src->native(), srcOff, bytes), "ICommandList::copyToStagingBuffer");
     }
     // Multi-GPU hook (trhip_cmd_host_callback): not part of NVRHI.
     void hostCallback(trhip_host_fn fn, void* user) { throwIfFailed(trhip_cmd_host_callback(m_Native, fn, user), "ICommandList::hostCallback"); }
@@ -569,6 +590,23 @@ public:
         if (!q || !q->m_Recorded) return s;
         if (trhip_pipeline_stats_get(q->native(), reinterpret_cast<trhip_pipeline_statistics*>(&s)) != TRHIP_OK) return PipelineStatistics{};
         return s;
+    }
+
+    StagingBufferHandle createStagingBuffer(uint64_t bytesPerSlot, uint32_t slots)
+    {
+        trhip_readback rb = nullptr;
+        throwIfFailed(trhip_readback_create(m_Native, bytesPerSlot, slots, &rb), "IDevice::createStagingBuffer");
+        return StagingBufferHandle(new IStagingBuffer(rb, bytesPerSlot, slots));
+    }
+    // every slot back to "never written"; waits for the device (not part of NVRHI: a volume reset's)
+    void resetStagingBuffer(IStagingBuffer* b) { throwIfFailed(trhip_readback_reset(b->native()), "IDevice::resetStagingBuffer"); }
+    // mapStagingTexture + the read + unmapStagingTexture (GIRenderer.cpp:531-540): waits for that slot's copy only, never for the
+    // device; returns the bytes the slot's last executed copy wrote (0, and zeros in dst, for a slot never written)
+    uint64_t readStagingBuffer(IStagingBuffer* b, uint32_t slot, void* dst, uint64_t bytes)
+    {
+        uint64_t written = 0;
+        throwIfFailed(trhip_readback_read(b->native(), slot, dst, bytes, &written), "IDevice::readStagingBuffer");
+        return written;
     }
 
 private:

@@ -238,6 +238,7 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
         check(irradiance && distance && data);
         interop::DDGIVolumeDesc d;
         memcpy(&d, desc64, sizeof d);
+        d.flags &= ~interop::kDDGIFlag_Variability;                           // trhost_set_ddgi_probe_variability's to set, with the buffers the bit needs
         for (int a = 0; a < 3; ++a) {
             if (d.probeCounts[a] < 1 || d.probeCounts[a] > (int)interop::kDDGIMaxProbeCount) throw nvrhi::Error("trhost_upload_ddgi_volume: a DDGI probe count is not in 1..1024");
             if (!(d.probeSpacing[a] > 0.0f && d.probeSpacing[a] <= 3.402823466e38f)) throw nvrhi::Error("trhost_upload_ddgi_volume: a DDGI probe spacing is not positive and finite");
@@ -289,8 +290,108 @@ int trhost_upload_ddgi_volume(const void* desc64, const uint32_t* irradiance, ui
         }
         if ((g_Scene->m_bDDGIProbeRelocation && !(d.flags & interop::kDDGIFlag_Relocation)) || (g_Scene->m_bDDGIProbeClassification && !(d.flags & interop::kDDGIFlag_Classification)))
             g_Scene->m_bDDGIProbeRelocation = g_Scene->m_bDDGIProbeClassification = false;     // the new volume's flags do not allow what was set
-        g_Scene->m_RTDDGIVolume = v;
+        g_Scene->m_RTDDGIVolume = v;                                          // a fresh tracker with it: probe variability is off on a new volume
         g_Scene->m_DDGIUpdateCount = 0;
+    });
+}
+
+// The variability buffer zeroed, the read-back's pending slots dropped, the whole tracker re-initialised (the reference resets
+// only the count); the switch and the threshold stay.  The caller has drained the device.
+static void ResetDDGIVariability(Scene::RTDDGIVolume& v)
+{
+    v.m_Variability.Reset();
+    v.m_NumUpdateCalls = v.m_NumUpdatesSkipped = 0;
+    if (!v.m_ProbeVariability) return;
+    const std::vector<uint8_t> zeros(v.m_ProbeVariability->getDesc().byteSize, 0);
+    nvrhi::throwIfFailed(trhip_buffer_upload(v.m_ProbeVariability->native(), 0, zeros.data(), zeros.size()), "the probe variability");
+    if (v.m_ProbeVariabilityReadback) g_Graphic.m_NVRHIDevice->resetStagingBuffer(v.m_ProbeVariabilityReadback);     // the frame's list may still name it
+    else v.m_ProbeVariabilityReadback = g_Graphic.m_NVRHIDevice->createStagingBuffer(sizeof(float), 2);
+}
+
+int trhost_set_ddgi_probe_variability(int enable, float stddev_threshold)
+{
+    return guarded([&] {
+        check(g_Scene);
+        Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        if (enable && !(g_Scene->m_bDDGIUpdate && v.IsValid()))
+            throw nvrhi::Error("trhost_set_ddgi_probe_variability: the probe update is off (trhost_set_ddgi_update first): ReductionCS_DDGIReductionCS has no blend whose variability it could average");
+        if (enable && !(stddev_threshold >= 0.0f && stddev_threshold <= 3.402823466e38f))
+            throw nvrhi::Error("trhost_set_ddgi_probe_variability: stddev_threshold must be finite and >= 0");
+        if (!v.IsValid()) return;                                             // nothing to switch off
+        g_Graphic.m_NVRHIDevice->waitForIdle();
+        if (enable && !v.m_ProbeVariability) {
+            const uint64_t cx = (uint64_t)v.m_Desc.probeCounts[0], cy = (uint64_t)v.m_Desc.probeCounts[1], cz = (uint64_t)v.m_Desc.probeCounts[2];
+            const uint64_t texels = cx * cy * cz * 36;
+            if (texels > (1ull << 24)) throw nvrhi::Error("trhost_set_ddgi_probe_variability: the volume has more than 2^24 interior irradiance texels; the reduction counts them in a float");
+            nvrhi::BufferDesc bd;
+            bd.byteSize = texels * sizeof(float); bd.structStride = sizeof(float); bd.canHaveUAVs = true; bd.debugName = "DDGI Probe Variability";
+            v.m_ProbeVariability = g_Graphic.m_NVRHIDevice->createBuffer(bd);
+            nvrhi::BufferDesc ad;                                             // the first pass's outputs; every later pass has fewer
+            ad.byteSize = ((cx * 6 + 15) / 16) * ((cz * 6 + 15) / 16) * ((cy + 3) / 4) * 2 * sizeof(float); ad.structStride = 2 * sizeof(float); ad.canHaveUAVs = true;
+            ad.debugName = "DDGI Probe Variability Average 0";
+            v.m_ProbeVariabilityAverage[0] = g_Graphic.m_NVRHIDevice->createBuffer(ad);
+            ad.debugName = "DDGI Probe Variability Average 1";
+            v.m_ProbeVariabilityAverage[1] = g_Graphic.m_NVRHIDevice->createBuffer(ad);
+        }
+        v.m_Variability.m_bProbeVariabilityEnabled = enable != 0;
+        if (enable) v.m_Variability.m_VariabilityStdDevThreshold = stddev_threshold;
+        // the descriptor's bit 2, on the host and on the device alike
+        v.m_Desc.flags = enable ? (v.m_Desc.flags | interop::kDDGIFlag_Variability) : (v.m_Desc.flags & ~interop::kDDGIFlag_Variability);
+        nvrhi::throwIfFailed(trhip_buffer_upload(v.m_DescBuffer->native(), 0, &v.m_Desc, sizeof v.m_Desc), "trhost_set_ddgi_probe_variability");
+        ResetDDGIVariability(v);
+    });
+}
+
+int trhost_get_ddgi_variability(float* average, float* stddev, int* converged, uint32_t* samples, uint32_t* skipped)
+{
+    return guarded([&] {
+        check(g_Scene);
+        const Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        if (average) *average = v.m_Variability.m_AverageVariability;
+        if (stddev) *stddev = v.m_Variability.m_VariabilityStdDev;
+        if (converged) *converged = v.m_Variability.bIsConverged ? 1 : 0;
+        if (samples) *samples = v.m_Variability.m_NumVolumeVariabilitySamples;
+        if (skipped) *skipped = v.m_NumUpdatesSkipped;
+    });
+}
+
+int trhost_reset_ddgi_variability(void)
+{
+    return guarded([&] {
+        check(g_Scene);
+        Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        if (!v.IsValid()) throw nvrhi::Error("trhost_reset_ddgi_variability: no DDGI volume (trhost_upload_ddgi_volume first)");
+        g_Graphic.m_NVRHIDevice->waitForIdle();
+        ResetDDGIVariability(v);
+    });
+}
+
+int trhost_ddgi_variability_run(const float* averages, uint32_t n, float threshold, uint8_t* converged, float* stddev)
+{
+    return guarded([&] {
+        check((averages && converged && stddev) || n == 0);
+        DDGIVariability t;
+        t.m_bProbeVariabilityEnabled = true;
+        t.m_VariabilityStdDevThreshold = threshold;
+        for (uint32_t i = 0; i < n; ++i) {
+            t.Update();
+            converged[i] = t.bIsConverged ? 1 : 0;
+            stddev[i] = t.m_VariabilityStdDev;
+            if (!t.bIsConverged) t.SetVariabilityForCurrentFrame(averages[i]);
+        }
+    });
+}
+
+int trhost_download_ddgi_variability(float* variability, uint64_t variability_bytes)
+{
+    return guarded([&] {
+        check(g_Scene);
+        const Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        if (!v.m_ProbeVariability) throw nvrhi::Error("trhost_download_ddgi_variability: probe variability was never switched on (trhost_set_ddgi_probe_variability)");
+        if (!variability || variability_bytes != v.m_ProbeVariability->getDesc().byteSize)
+            throw nvrhi::Error("trhost_download_ddgi_variability: needs counts.y x 6 counts.z x 6 counts.x floats");
+        g_Graphic.m_NVRHIDevice->waitForIdle();
+        nvrhi::throwIfFailed(trhip_buffer_download(v.m_ProbeVariability->native(), 0, variability, variability_bytes), "trhost_download_ddgi_variability");
     });
 }
 
@@ -379,9 +480,10 @@ int trhost_reset_ddgi_volume(void)
 {
     return guarded([&] {
         check(g_Scene);
-        const Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
+        Scene::RTDDGIVolume& v = g_Scene->m_RTDDGIVolume;
         if (!v.IsValid()) throw nvrhi::Error("trhost_reset_ddgi_volume: no DDGI volume (trhost_upload_ddgi_volume first)");
         g_Graphic.m_NVRHIDevice->waitForIdle();
+        ResetDDGIVariability(v);
         const uint32_t cx = (uint32_t)v.m_Desc.probeCounts[0], cy = (uint32_t)v.m_Desc.probeCounts[1], cz = (uint32_t)v.m_Desc.probeCounts[2];
         const uint64_t irrSlice = (uint64_t)cx * 8 * cz * 8 * 4, distSlice = (uint64_t)cx * 16 * cz * 16 * 4;
         const std::vector<uint8_t> zeros(distSlice, 0);                       // GIRenderer.cpp:457-458: both cleared

@@ -7,7 +7,9 @@
 // BINDINGS.  b0 ddgiu::Block (DDGIUpdateConsts, then the DDGIVolumeDesc's host copy; 160 bytes); StructuredBuffer_SRV t1 the ray
 // records, float4[numProbes * 256] (rgb radiance, w distance: < 0 marks a back face); Texture_SRV t3 the RGBA16_FLOAT array of probe
 // data; radiance: Texture_UAV u1 the R10G10B10A2_UNORM irradiance array; distance: Texture_UAV u2 the RG16_FLOAT distance array.  A
-// direct dispatch of (counts.x, counts.z, counts.y) groups, one per probe.
+// direct dispatch of (counts.x, counts.z, counts.y) groups, one per probe.  With DDGIVolumeDesc::flags bit 2 (kDDGIFlag_Variability) the
+// radiance pass also needs StructuredBuffer_UAV u4 = the probe variability, float[counts.y][6 * counts.z][6 * counts.x]: the interior
+// texels of the irradiance array in that array's order, without borders; with the bit clear u4 is not looked at.
 //
 // CONVENTION (ddgi_update.hip.h states the ray direction, the octahedral decode and a probe's index).
 //   left alone: with flags bit 1 (classification) a probe whose data.w == 1.0f, and any probe with kDDGIBackfaceRayLimit = 25 or more
@@ -21,6 +23,11 @@
 //             when fmax of (prev + delta) < fmax of prev (darker): step = fmin(fmax(1.0f / 1024.0f, |step|), |delta|) * sign(step) per
 //             channel, sign(0) = 0: without it ten bits never reach black; the store is prev + step;
 //             code = (uint)rint(saturate(store) * 1023.0f) (round to nearest even; a NaN gives 0), alpha 3;
+//   variability (flags bit 2; tests/ddgi_variability_ref.c: dv_texel): per channel s2 = (res - prev) * (res - out), out the eased value
+//             before saturate and the 10-bit store; L = (0.2126f, 0.7152f, 0.0722f); lumS2 = dot3(s2, L); lumMean = dot3(out, L);
+//             the value is (lumMean <= 1.0f / 1024.0f || !(lumS2 > 0.0f)) ? 0.0f : sqrt(lumS2) / lumMean, the coefficient of variation.
+//             The floor of one 10-bit code and the > 0 guard are the project's own: a channel product can be negative, and no NaN
+//             is born here.  A probe that is left alone writes none of its 36 values;
 //   distance  : w = powSoft(fmax(0, dot3(texelDir, rayDir)), probeDistanceExponent); d = fmin(|record.w|, 1.5f * sqrt(dot3(spacing,
 //             spacing))); sum.x += d * w; sum.y += (d * d) * w; sumW += w; res = sum / (2.0f * fmax(sumW, 1e-9f * 256.0f));
 //             prev = the binary16 texel; h = prev == (0, 0) ? 0 : probeHysteresis; the store is lerp(res, prev, h) = res + h * (prev -
@@ -34,7 +41,7 @@
 // the host copy of the descriptor, which the record function checked against the bound textures and the ray buffer's size.
 // UNTUNED: correctness came first.  Every interior thread walks all 256 rays; the distance pass's powSoft per ray and texel is its cost.
 // Code object (-Rpass-analysis=kernel-resource-usage): radiance 21 VGPRs, occupancy 6 waves per SIMD (64-thread groups), LDS 7424 bytes;
-// distance 20 VGPRs, occupancy 8, LDS 8192 bytes; no scratch in either.
+// distance 20 VGPRs, occupancy 8, LDS 8192 bytes; radiance with variability 25 VGPRs, occupancy 6, LDS 7424 bytes; no scratch in any.
 #include "ddgi_update.hip.h"
 
 namespace
@@ -49,6 +56,7 @@ struct BlendArgs
     const float4* rays;                        // t1
     const uint2* data; uint32_t dataW, dataPitch;       // t3 RGBA16_FLOAT array; texels per row and per slice
     uint32_t* tex; uint32_t texW, texPitch;             // u1 R10G10B10A2_UNORM or u2 RG16_FLOAT array
+    float* variability;                        // u4 (VARIABILITY only): float[counts.y][6 * counts.z][6 * counts.x]
 };
 
 __device__ __forceinline__ float sign_(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
@@ -74,7 +82,7 @@ __device__ __forceinline__ F3 easeRadiance(F3 res, F3 prev, const DDGIUpdateCons
 
 __device__ __forceinline__ uint32_t unorm10(float v) { return (uint32_t)__builtin_rintf(sp::saturate_(v) * 1023.0f); }
 
-template <bool RADIANCE>
+template <bool RADIANCE, bool VARIABILITY>
 __global__ __launch_bounds__(RADIANCE ? 64 : 256) void blendKernel(BlendArgs a)
 {
     constexpr uint32_t N = (RADIANCE ? kDDGIIrradianceInteriorTexels : kDDGIDistanceInteriorTexels) + 2u, kThreads = N * N, kRays = kDDGIRaysPerProbe;
@@ -116,6 +124,14 @@ __global__ __launch_bounds__(RADIANCE ? 64 : 256) void blendKernel(BlendArgs a)
             const F3 prev = { cm::div_((float)(old & 1023u), 1023.0f), cm::div_((float)((old >> 10) & 1023u), 1023.0f), cm::div_((float)((old >> 20) & 1023u), 1023.0f) };
             const F3 out = easeRadiance(res, prev, k);
             word = unorm10(out.x) | unorm10(out.y) << 10 | unorm10(out.z) << 20 | 3u << 30;
+            if constexpr (VARIABILITY) {                                                             // tests/ddgi_variability_ref.c: dv_texel
+                const F3 s2 = { (res.x - prev.x) * (res.x - out.x), (res.y - prev.y) * (res.y - out.y), (res.z - prev.z) * (res.z - out.z) };
+                const F3 L = { 0.2126f, 0.7152f, 0.0722f };
+                const float lumS2 = cm::dot3(s2, L), lumMean = cm::dot3(out, L);
+                const float cov = (lumMean <= 1.0f / 1024.0f || !(lumS2 > 0.0f)) ? 0.0f : cm::div_(cm::sqrt_(lumS2), lumMean);
+                const uint32_t I = N - 2u, vw = (uint32_t)D.probeCounts[0] * I, vh = (uint32_t)D.probeCounts[2] * I;
+                a.variability[((uint64_t)c.y * vh + ((uint32_t)c.z * I + (ty - 1u))) * vw + ((uint32_t)c.x * I + (tx - 1u))] = cov;
+            }
         } else {
             const F3 spacing = { D.probeSpacing[0], D.probeSpacing[1], D.probeSpacing[2] };
             const float maxDistance = 1.5f * cm::sqrt_(cm::dot3(spacing, spacing));
@@ -162,6 +178,14 @@ int recordBlend(trhip::DispatchCtx& ctx)
                   (unsigned long long)rays->byteSize, probes, (unsigned long long)probes * kDDGIRaysPerProbe * sizeof(float4));
     trhip_texture_t *data, *target;
     if (const int rc = ddgiu::requireProbeTexture(ctx, TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_RGBA16_FLOAT, 1, "Texture_SRV t3 = the RGBA16_FLOAT array of probe data", D, data)) return rc;
+    const bool variability = RADIANCE && (D.flags & kDDGIFlag_Variability) != 0u;
+    if (variability) {
+        trhip_buffer_t* v = ctx.buffer(TRHIP_BIND_STRUCTURED_UAV, 4);
+        const uint64_t bytes = (uint64_t)probes * kDDGIIrradianceInteriorTexels * kDDGIIrradianceInteriorTexels * sizeof(float);
+        TRHIP_REQUIRE(v, "%s: DDGIVolumeDesc flags = %u have probe variability on: needs StructuredBuffer_UAV u4 = the probe variability, float[counts.y][6 * counts.z][6 * counts.x]", name, D.flags);
+        TRHIP_REQUIRE(v->byteSize == bytes, "%s: the probe variability at u4 holds %llu bytes; %u probes of 36 floats are %llu", name, (unsigned long long)v->byteSize, probes, (unsigned long long)bytes);
+        a.variability = (float*)v->ptr;
+    }
     if (RADIANCE) {
         if (const int rc = ddgiu::requireProbeTexture(ctx, TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R10G10B10A2_UNORM, kDDGIIrradianceInteriorTexels + 2,
                                                       "Texture_UAV u1 = the R10G10B10A2_UNORM array of probe irradiance", D, target)) return rc;
@@ -172,7 +196,8 @@ int recordBlend(trhip::DispatchCtx& ctx)
     a.rays = (const float4*)rays->ptr;
     a.data = (const uint2*)data->ptr; a.dataW = data->width; a.dataPitch = (uint32_t)(data->slicePitch / data->texelBytes);
     a.tex = (uint32_t*)target->ptr; a.texW = target->width; a.texPitch = (uint32_t)(target->slicePitch / target->texelBytes);
-    sp::launch(ctx, blendKernel<RADIANCE>, RADIANCE ? "blendKernel<radiance>" : "blendKernel<distance>", dim3(probes), dim3(RADIANCE ? 64 : 256), a);
+    if (variability) sp::launch(ctx, blendKernel<RADIANCE, RADIANCE>, "blendKernel<radiance, variability>", dim3(probes), dim3(64), a);
+    else sp::launch(ctx, blendKernel<RADIANCE, false>, RADIANCE ? "blendKernel<radiance>" : "blendKernel<distance>", dim3(probes), dim3(RADIANCE ? 64 : 256), a);
     return TRHIP_OK;
 }
 

@@ -973,6 +973,7 @@ static const ArrayBindingDecl kArrayBindings[] = {
     { "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1", TRHIP_BIND_TEXTURE_UAV, 1, TRHIP_FORMAT_R10G10B10A2_UNORM, "R10G10B10A2_UNORM" },
     { "ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0", TRHIP_BIND_TEXTURE_UAV, 2, TRHIP_FORMAT_RG16_FLOAT, "RG16_FLOAT" },
     { "ProbeBlendingCS_DDGIProbeBlendingCS", TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
+    { "ReductionCS_DDGIReductionCS", TRHIP_BIND_TEXTURE_SRV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },                 // k_ddgireduction.hip: the first pass
     { "giprobetrace_CS_ProbeTraceFixedRays", TRHIP_BIND_TEXTURE_SRV, 1, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },      // k_giprobeplacement.hip
     { "ProbeRelocationCS_DDGIProbeRelocationCS", TRHIP_BIND_TEXTURE_UAV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
     { "ProbeClassificationCS_DDGIProbeClassificationCS", TRHIP_BIND_TEXTURE_UAV, 3, TRHIP_FORMAT_RGBA16_FLOAT, "RGBA16_FLOAT" },
@@ -994,7 +995,7 @@ static int checkArrayBinding(const char* name, const trhip_binding& b, const trh
         return TRHIP_OK;
     }
     return fail(TRHIP_ERR_INVALID, "dispatch(%s): the array texture '%s' at %c%u: the pass declares no array texture there (deferredlighting_PS_Main and _Debug: t6..t8; "
-                                   "giprobetrace_CS_ProbeTrace: t1..t3; the probe blends: t3 and u1 (radiance) or u2 (distance); giprobetrace_CS_ProbeTraceFixedRays: t1; "
+                                   "giprobetrace_CS_ProbeTrace: t1..t3; the probe blends: t3 and u1 (radiance) or u2 (distance); ReductionCS_DDGIReductionCS: t3; giprobetrace_CS_ProbeTraceFixedRays: t1; "
                                    "probe relocation and classification: u3; giprobevisualization_CS_LoadGIProbes: t1; giprobevisualization_PS_VisualizeGIProbes: t1..t3)", name, t->name.c_str(), kind, b.slot);
 }
 
@@ -1360,6 +1361,91 @@ int trhip_pipeline_stats_get(trhip_pipeline_stats q, trhip_pipeline_statistics* 
     TRHIP_HIP(hipSetDevice(q->dev->index));
     TRHIP_HIP(hipEventSynchronize(q->done));
     TRHIP_HIP(hipMemcpy(out, q->counters, sizeof(trhip_pipeline_statistics), hipMemcpyDeviceToHost));
+    return TRHIP_OK;
+}
+
+// ---- read-back ---------------------------------------------------------------------------------------
+int trhip_readback_create(trhip_device dev, uint64_t bytes_per_slot, uint32_t slots, trhip_readback* out)
+{
+    if (!dev || !out) return fail(TRHIP_ERR_INVALID, "readback_create: null argument");
+    if (!bytes_per_slot || !slots || slots > 64 || bytes_per_slot > (1ull << 30) / slots) return fail(TRHIP_ERR_INVALID, "readback_create: needs 1..64 slots of at least one byte, 1 GiB in all at most");
+    TRHIP_HIP(hipSetDevice(dev->index));
+    auto rb = std::make_unique<trhip_readback_t>();
+    rb->dev = dev;
+    rb->bytesPerSlot = bytes_per_slot;
+    TRHIP_HIP(hipHostMalloc((void**)&rb->host, (size_t)(bytes_per_slot * slots), hipHostMallocDefault));
+    memset(rb->host, 0, (size_t)(bytes_per_slot * slots));
+    rb->written.assign(slots, 0);
+    for (uint32_t i = 0; i < slots; ++i) {
+        hipEvent_t e = nullptr;
+        hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+        if (err != hipSuccess) {
+            for (hipEvent_t d : rb->done) (void)hipEventDestroy(d);
+            (void)hipHostFree(rb->host);
+            return hipfail(err, "hipEventCreateWithFlags");
+        }
+        rb->done.push_back(e);
+    }
+    *out = rb.release();
+    return TRHIP_OK;
+}
+
+void trhip_readback_release(trhip_readback rb)
+{
+    if (!rb) return;
+    (void)hipSetDevice(rb->dev->index);
+    (void)rb->dev->syncAll();                    // executed lists may still copy into it
+    for (hipEvent_t e : rb->done) (void)hipEventDestroy(e);
+    (void)hipHostFree(rb->host);
+    delete rb;
+}
+
+int trhip_readback_reset(trhip_readback rb)
+{
+    if (!rb) return fail(TRHIP_ERR_INVALID, "readback_reset: null argument");
+    TRHIP_HIP(hipSetDevice(rb->dev->index));
+    const int rc = rb->dev->syncAll();           // executed lists may still copy into it
+    if (rc != TRHIP_OK) return rc;
+    std::fill(rb->written.begin(), rb->written.end(), 0);
+    memset(rb->host, 0, (size_t)(rb->bytesPerSlot * rb->written.size()));
+    return TRHIP_OK;
+}
+
+int trhip_cmd_copy_to_readback(trhip_cmdlist cl, trhip_readback rb, uint32_t slot, trhip_buffer src, uint64_t srcOff, uint64_t bytes)
+{
+    TRHIP_RECORDING(cl);
+    if (!rb || !src) return fail(TRHIP_ERR_INVALID, "copy_to_readback: null argument");
+    if (rb->dev != cl->dev) return fail(TRHIP_ERR_INVALID, "copy_to_readback: the read-back resource belongs to another device");
+    if (!src->ptr) return fail(TRHIP_ERR_STATE, "copy_to_readback(%s): no memory bound", src->name.c_str());
+    if (slot >= rb->done.size()) return fail(TRHIP_ERR_INVALID, "copy_to_readback(%s): slot %u of %zu", src->name.c_str(), slot, rb->done.size());
+    if (!bytes || bytes > rb->bytesPerSlot || srcOff > src->byteSize || bytes > src->byteSize - srcOff)
+        return fail(TRHIP_ERR_INVALID, "copy_to_readback(%s): %llu bytes from offset %llu; the buffer holds %llu and a slot %llu", src->name.c_str(), (unsigned long long)bytes,
+                    (unsigned long long)srcOff, (unsigned long long)src->byteSize, (unsigned long long)rb->bytesPerSlot);
+    void* d = rb->host + (uint64_t)slot * rb->bytesPerSlot;
+    const void* sp = (const char*)src->ptr + srcOff;
+    cl->hold(src, false);
+    cl->ops.push_back({ "", [rb, slot, d, sp, bytes](hipStream_t s) {
+        TRHIP_HIP(hipMemcpyAsync(d, sp, (size_t)bytes, hipMemcpyDeviceToHost, s));
+        TRHIP_HIP(hipEventRecord(rb->done[slot], s));
+        rb->written[slot] = bytes;
+        return (int)TRHIP_OK; } });
+    cl->ops.back().kind = "copy_to_readback";
+    return TRHIP_OK;
+}
+
+int trhip_readback_read(trhip_readback rb, uint32_t slot, void* dst, uint64_t bytes, uint64_t* written)
+{
+    if (!rb || !dst || !written) return fail(TRHIP_ERR_INVALID, "readback_read: null argument");
+    if (slot >= rb->done.size()) return fail(TRHIP_ERR_INVALID, "readback_read: slot %u of %zu", slot, rb->done.size());
+    if (bytes > rb->bytesPerSlot) return fail(TRHIP_ERR_INVALID, "readback_read: %llu bytes; a slot holds %llu", (unsigned long long)bytes, (unsigned long long)rb->bytesPerSlot);
+    memset(dst, 0, (size_t)bytes);
+    *written = 0;
+    if (!rb->written[slot]) return TRHIP_OK;
+    TRHIP_HIP(hipSetDevice(rb->dev->index));
+    TRHIP_HIP(hipEventSynchronize(rb->done[slot]));      // this slot's copy only: the device goes on with what was submitted behind it
+    const uint64_t n = bytes < rb->written[slot] ? bytes : rb->written[slot];
+    memcpy(dst, rb->host + (uint64_t)slot * rb->bytesPerSlot, (size_t)n);
+    *written = n;
     return TRHIP_OK;
 }
 

@@ -226,6 +226,17 @@ struct trhip_pipeline_stats_t
     bool began = false, ended = false;
 };
 
+// A read-back resource (include/trhip.h): `slots` slots of bytesPerSlot pinned host bytes; done[k] is recorded behind slot k's
+// last copy, written[k] is what that copy wrote (0: no executed list has written the slot).
+struct trhip_readback_t
+{
+    trhip_device_t* dev = nullptr;
+    uint8_t* host = nullptr;
+    uint64_t bytesPerSlot = 0;
+    std::vector<hipEvent_t> done;
+    std::vector<uint64_t> written;
+};
+
 namespace trhip
 {
 

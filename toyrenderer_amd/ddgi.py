@@ -84,7 +84,9 @@ UPDATE_DEFAULTS = dict(seed=0, hysteresis=0.5, distance_exponent=50.0, irradianc
                        max_ray_distance=1e10,                                                                                # :79 passes the scene's bounding radius
                        relocate=False, classify=False,                # :80-83 switches both on; here they are options
                        min_frontface_distance=0.3,                    # :98, :106: 0.1 for a scene radius below 3, else 0.3
-                       fixed_ray_backface_threshold=0.25)             # :121
+                       fixed_ray_backface_threshold=0.25,             # :121
+                       variability=False,                             # :84 switches it on; here it is an option
+                       variability_threshold=0.001)                   # :211 m_VariabilityStdDevThreshold
 
 
 def check_update_settings(settings) -> dict:
@@ -97,9 +99,9 @@ def check_update_settings(settings) -> dict:
     u["seed"] = int(u["seed"])
     if u["seed"] < 0:
         raise ValueError("ddgi_update: seed must not be negative")
-    u["relocate"], u["classify"] = bool(u["relocate"]), bool(u["classify"])
+    u["relocate"], u["classify"], u["variability"] = bool(u["relocate"]), bool(u["classify"]), bool(u["variability"])
     for name in ("hysteresis", "distance_exponent", "irradiance_threshold", "brightness_threshold", "max_ray_distance", "min_frontface_distance",
-                 "fixed_ray_backface_threshold"):
+                 "fixed_ray_backface_threshold", "variability_threshold"):
         u[name] = float(u[name])
         if not (math.isfinite(u[name]) and u[name] >= 0.0):
             raise ValueError(f"ddgi_update: {name} = {u[name]} is not finite and >= 0")
@@ -107,6 +109,63 @@ def check_update_settings(settings) -> dict:
         if u[name] > 1.0:
             raise ValueError(f"ddgi_update: {name} = {u[name]} is not in [0, 1]")
     return u
+
+
+class VariabilityTracker:
+    """RTDDGIVolume::Update and SetVariabilityForCurrentFrame (GIRenderer.cpp:158-190) in numpy float32: csrc/host/DDGIVariability.h
+    restated, bit for bit.  A ring of the last 16 volume-average variabilities; update() advances the cursor (converged or not),
+    takes mean and variance / 16 over the ring in index order, stddev = sqrt(variance / 16) and converged = enabled and
+    (samples++ > 16) and stddev < threshold: the 18th update at the earliest.  set() stores 0 for a value that is not normal
+    (0, a denormal, inf, NaN).  Nothing wakes a converged tracker but reset(), which re-initialises everything but the switch and the
+    threshold."""
+    SAMPLES = I.kDDGIMinimumVariabilitySamples
+
+    def __init__(self, threshold: float = 0.001, enabled: bool = True):
+        self.threshold, self.enabled = np.float32(threshold), bool(enabled)
+        self.reset()
+
+    def reset(self):
+        self.ring = np.zeros(self.SAMPLES, np.float32)
+        self.cursor, self.samples = 0, 0
+        self.average, self.stddev, self.converged = np.float32(0.0), np.float32(1e10), False
+
+    def update(self) -> bool:
+        f = np.float32
+        self.cursor = (self.cursor + 1) % self.SAMPLES
+        total = f(0.0)
+        for v in self.ring:
+            total = f(total + v)
+        mean = f(total / f(self.SAMPLES))
+        variance = f(0.0)
+        for v in self.ring:
+            diff = f(v - mean)
+            variance = f(variance + f(diff * diff))
+        self.stddev = f(np.sqrt(f(variance / f(self.SAMPLES))))
+        self.converged = False
+        if self.enabled:
+            n = self.samples
+            self.samples += 1
+            self.converged = bool(n > self.SAMPLES and self.stddev < self.threshold)
+        return self.converged
+
+    def set(self, v):
+        v = np.float32(v)
+        tiny = np.finfo(np.float32).tiny
+        self.average = v
+        self.ring[self.cursor] = v if (np.isfinite(v) and abs(v) >= tiny) else np.float32(0.0)
+
+    @classmethod
+    def run(cls, averages, threshold: float = 0.001):
+        """(converged bool [n], stddev float32 [n]) after each update() over a sequence, as trhost_ddgi_variability_run runs it:
+        per element one update() and, unless it found the ring converged, one set()."""
+        t = cls(threshold)
+        conv, dev = [], []
+        for a in np.asarray(averages, np.float32):
+            conv.append(t.update())
+            dev.append(t.stddev)
+            if not t.converged:
+                t.set(a)
+        return np.asarray(conv, bool), np.asarray(dev, np.float32)
 
 
 def unit_sphere():
@@ -133,7 +192,7 @@ def unit_sphere():
 
 class Volume:
     def __init__(self, origin, spacing, counts, normal_bias: float, view_bias: float, gamma: float = DEFAULT_GAMMA, relocation: bool = True,
-                 classification: bool = True):
+                 classification: bool = True, variability: bool = False):
         self.origin = tuple(float(np.float32(x)) for x in origin)
         self.spacing = tuple(float(np.float32(x)) for x in spacing)
         self.counts = tuple(int(x) for x in counts)
@@ -145,6 +204,7 @@ class Volume:
             raise ValueError(f"Volume: probe spacing {self.spacing} is not positive and finite")
         self.normal_bias, self.view_bias, self.gamma = float(normal_bias), float(view_bias), float(gamma)
         self.relocation, self.classification = bool(relocation), bool(classification)
+        self.variability = bool(variability)         # flags bit 2: FrameDriver(ddgi_update=dict(variability=True)) sets it, with the buffer the bit needs
         cx, cy, cz = self.counts
         self.irradiance = np.zeros((cy, cz * IRRADIANCE_TEXELS, cx * IRRADIANCE_TEXELS), np.uint32)
         self.distance = np.zeros((cy, cz * DISTANCE_TEXELS, cx * DISTANCE_TEXELS, 2), np.float16)
@@ -182,7 +242,7 @@ class Volume:
         return self
 
     def copy(self) -> "Volume":
-        v = Volume(self.origin, self.spacing, self.counts, self.normal_bias, self.view_bias, self.gamma, self.relocation, self.classification)
+        v = Volume(self.origin, self.spacing, self.counts, self.normal_bias, self.view_bias, self.gamma, self.relocation, self.classification, self.variability)
         v.irradiance, v.distance, v.data = self.irradiance.copy(), self.distance.copy(), self.data.copy()
         return v
 
@@ -197,7 +257,8 @@ class Volume:
         d["origin"], d["probeSpacing"], d["probeCounts"] = self.origin, self.spacing, self.counts
         d["probeNormalBias"], d["probeViewBias"], d["probeIrradianceEncodingGamma"] = self.normal_bias, self.view_bias, self.gamma
         d["numIrradianceInteriorTexels"], d["numDistanceInteriorTexels"] = I.kDDGIIrradianceInteriorTexels, I.kDDGIDistanceInteriorTexels
-        d["flags"] = (I.kDDGIFlag_Relocation if self.relocation else 0) | (I.kDDGIFlag_Classification if self.classification else 0)
+        d["flags"] = ((I.kDDGIFlag_Relocation if self.relocation else 0) | (I.kDDGIFlag_Classification if self.classification else 0) |
+                      (I.kDDGIFlag_Variability if self.variability else 0))
         return d
 
     def probe_positions_and_states(self):

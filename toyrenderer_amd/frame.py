@@ -253,7 +253,18 @@ class FrameDriver:
         scene radius below 3) and fixed_ray_backface_threshold (0.25).  Each needs its flag on the volume (ddgi.Volume(relocation=,
         classification=), on by default) and gives the data texture the UAV bit; the lighting pass of the same frame sees the new
         data; download_ddgi_fixed_rays() reads the distances back.  With both off the supplied data texture is honoured as it is
-        and the update records what it recorded before (csrc/k_giprobeplacement.hip).
+        and the update records what it recorded before (csrc/k_giprobeplacement.hip).  variability (False) with
+        variability_threshold (0.001) adds the reference's convergence early-out (GIRenderer.cpp:158-190, :466-470, :529-576): the
+        driver sets flags bit 2 on a COPY of the volume (self.ddgi; host and device copy of the descriptor alike; the caller's Volume is
+        not touched, and one that already carries the bit is refused without the option), the radiance
+        blend also writes a coefficient of variation per interior texel (u4 = self.ddgi_variability_buffer), "ReductionCS_
+        DDGIReductionCS REDUCTION=1" and "ReductionCS_DDGIExtraReductionCS" average it over the active probes, and element 0 goes
+        into slot n % 2 of a two-slot read-back.  Update call n first runs ddgi.VariabilityTracker.update() and, converged, records
+        NOTHING of the update (no refit unless shadows= needs it, no trace, blend, placement, reduction or copy; self.
+        ddgi_updates_skipped counts them, self.ddgi_updates does not); else it stores what call n - 2 copied (0 before that:
+        read without waiting for the device) into the ring.  It needs record() per frame, as the rotation does.  self.
+        ddgi_variability shows average, stddev, converged and samples; download_ddgi_variability() reads the buffer;
+        reset_ddgi_variability() re-arms a converged volume (nothing else does: waking on a light or transform change is not built).
         probes: None (the default) changes nothing.  A dict (needs ddgi= and post=True) draws the volume's probes into the back buffer
         behind the post pass, GIDebugRenderer's three dispatches (csrc/k_giprobedraw.hip, csrc/k_giprobe.hip): "giprobevisualization_
         CS_LoadGIProbes" writes every probe's position and state from the LIVE volume into self.probe_positions and
@@ -312,6 +323,14 @@ class FrameDriver:
             if scene.rt is None:
                 raise ValueError("ddgi_update=... needs GpuScene.set_raytracing(): the acceleration structure the probe rays walk")
             self.ddgi_update = ddgimod.check_update_settings(ddgi_update)
+            if self.ddgi_update["variability"]:
+                if int(np.prod(ddgi.counts)) * 36 > 1 << 24:
+                    raise ValueError("ddgi_update: variability=True with more than 2^24 interior irradiance texels; the reduction counts them in a float")
+                ddgi = self.ddgi = ddgi.copy()       # the caller's Volume stays as it is: the bit is the driver's, on its own copy
+                ddgi.variability = True              # the descriptor's bit 2, before the volume is uploaded
+            elif ddgi.variability:
+                raise ValueError("ddgi_update: the ddgi.Volume has variability=True (flags bit 2) and ddgi_update has variability=False: the radiance blend would "
+                                 "need the variability buffer at u4; clear the flag or pass variability=True")
             for option, flag, word in (("relocate", ddgi.relocation, "relocation"), ("classify", ddgi.classification, "classification")):
                 if self.ddgi_update[option] and not flag:
                     raise ValueError(f"ddgi_update: {option}=True needs ddgi.Volume({word}=True): with the flag off nothing reads what the pass writes")
@@ -462,6 +481,17 @@ class FrameDriver:
         if self.ddgi is not None:                    # GIRenderer::Setup's textures (GIRenderer.cpp:129-133), filled by the caller
             self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance = self.ddgi.upload(dev, uav=self.ddgi_update is not None, data_uav=placement)
         self.ddgi_rays = self.ddgi_fixed_rays = None
+        self.ddgi_variability_buffer = self.ddgi_variability_readback = self._ddgi_tracker = None
+        self.ddgi_variability_average = None
+        self.ddgi_updates_skipped = self._ddgi_update_calls = 0
+        if self.ddgi_update is not None and self.ddgi_update["variability"]:
+            cx, cy, cz = self.ddgi.counts
+            self.ddgi_variability_buffer = dev.create_buffer(cx * cy * cz * 36 * 4, "DDGI Probe Variability", stride=4)
+            self.ddgi_variability_buffer.upload(np.zeros(cx * cy * cz * 36, np.float32))
+            groups = -(-6 * cx // 16) * -(-6 * cz // 16) * -(-cy // 4)       # the first pass's outputs; every later pass has fewer
+            self.ddgi_variability_average = [dev.create_buffer(groups * 8, f"DDGI Probe Variability Average {i}", stride=8) for i in range(2)]
+            self.ddgi_variability_readback = dev.create_readback(4, 2)
+            self._ddgi_tracker = ddgimod.VariabilityTracker(self.ddgi_update["variability_threshold"])
         if self.ddgi_update is not None:             # the ray data of GIRenderer::Setup, as a structured buffer of float4 records
             self.ddgi_rays = dev.create_buffer(int(np.prod(self.ddgi.counts)) * I.kDDGIRaysPerProbe * 16, "DDGI Ray Data", stride=16)
             self.ddgi_rays.upload(np.zeros(self.ddgi_rays.size // 4, np.float32))     # an inactive probe's records keep what they hold
@@ -763,6 +793,64 @@ class FrameDriver:
         return self._denoise_download("download_shadow_history", lambda: self.shadow_history[self.shadow_history_written])
 
     # ---- GIRenderer::RenderDDGI (GIRenderer.cpp): the probe trace and the two blends ---------------------------------------------
+    def _ddgi_begin_update(self):
+        """RenderDDGI's opening (GIRenderer.cpp:464-470), once per record(): True when this call records nothing of the update."""
+        if self._ddgi_tracker is None:
+            return False
+        self._ddgi_call = self._ddgi_update_calls        # this call's number since the last reset: its read-back slot is this % 2
+        self._ddgi_update_calls += 1
+        skip = self._ddgi_tracker.update()
+        self.ddgi_updates_skipped += int(skip)
+        return skip
+
+    def _ddgi_variability(self, cl, cb):
+        """GIRenderer.cpp:529-576: the sample of two calls ago into the ring, this call's reductions, the copy of their result."""
+        cx, cy, cz = self.ddgi.counts
+        slot = self._ddgi_call % 2
+        got, _ = self.ddgi_variability_readback.read(slot, np.float32, 1)   # waits for that slot's copy only; 0 for a slot never written
+        self._ddgi_tracker.set(got[0])
+        size, n = (6 * cx, 6 * cz, cy), 0
+        while n == 0 or max(size) > 1:
+            out = tuple(-(-s // g) for s, g in zip(size, I.kDDGIReductionGroup))
+            push = np.zeros(1, I.DDGIRootConstants)
+            push["reductionInputSizeX"], push["reductionInputSizeY"], push["reductionInputSizeZ"] = size
+            src, dst = self.ddgi_variability_average[(n + 1) % 2], self.ddgi_variability_average[n % 2]   # ping-pong: a pass never reads what it writes
+            if n == 0:
+                cl.dispatch("ReductionCS_DDGIReductionCS REDUCTION=1", [CB(0, cb), PUSH(1), TEX_SRV(3, self.ddgi_data), SRV(4, self.ddgi_variability_buffer), UAV(5, dst)], out, push=push)
+            else:
+                cl.dispatch("ReductionCS_DDGIExtraReductionCS", [PUSH(1), SRV(4, src), UAV(5, dst)], out, push=push)
+            size, n = out, n + 1
+        cl.copy_to_readback(self.ddgi_variability_readback, slot, self.ddgi_variability_average[(n + 1) % 2], 0, 4)
+
+    @property
+    def ddgi_variability(self):
+        """dict(average, stddev, converged, samples) of the convergence rule, or None with variability off."""
+        t = self._ddgi_tracker
+        return None if t is None else dict(average=t.average, stddev=t.stddev, converged=t.converged, samples=t.samples)
+
+    @property
+    def ddgi_variability_ring(self):
+        """A copy of the rule's ring of the last 16 stored averages (float32 [16], in index order), or None with variability off."""
+        return None if self._ddgi_tracker is None else self._ddgi_tracker.ring.copy()
+
+    def download_ddgi_variability(self) -> np.ndarray:
+        """The variability buffer, float32 [counts.y, 6 counts.z, 6 counts.x]."""
+        if self.ddgi_variability_buffer is None:
+            raise ValueError("download_ddgi_variability: probe variability is off (ddgi_update without variability=True)")
+        self.dev.wait_idle()
+        cx, cy, cz = self.ddgi.counts
+        return self.ddgi_variability_buffer.download(np.float32).reshape(cy, 6 * cz, 6 * cx)
+
+    def reset_ddgi_variability(self):
+        """Re-arms the update: the whole tracker starts again, the pending read-back slots are dropped and the variability buffer is zeroed."""
+        if self._ddgi_tracker is None:
+            raise ValueError("reset_ddgi_variability: probe variability is off (ddgi_update without variability=True)")
+        self.dev.wait_idle()
+        self._ddgi_tracker.reset()
+        self._ddgi_update_calls = self.ddgi_updates_skipped = 0
+        self.ddgi_variability_buffer.upload(np.zeros(self.ddgi_variability_buffer.size // 4, np.float32))
+        self.ddgi_variability_readback.reset()       # kept: the list recorded last still names it
+
     def _ddgi_update(self, cl):
         sc, vol, u = self.scene, self.ddgi, self.ddgi_update
         rt = sc.rt
@@ -783,11 +871,19 @@ class FrameDriver:
                      SRV(11, rt["headers"]), SRV(12, rt["blas_nodes"]), SRV(13, rt["tri_order"]), UAV(0, self.ddgi_rays), SAMPLER(0), SAMPLER(1), SAMPLER(2)],
                     (I.kDDGIRaysPerProbe // 64, cx * cz, cy))
         cl.dispatch("ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=1",
-                    [CB(0, cb), SRV(1, self.ddgi_rays), TEX_SRV(3, self.ddgi_data), TEX_UAV(1, self.ddgi_irradiance, 0)], (cx, cz, cy))
+                    [CB(0, cb), SRV(1, self.ddgi_rays), TEX_SRV(3, self.ddgi_data), TEX_UAV(1, self.ddgi_irradiance, 0)] +
+                    ([UAV(4, self.ddgi_variability_buffer)] if u["variability"] else []), (cx, cz, cy))
         cl.dispatch("ProbeBlendingCS_DDGIProbeBlendingCS RTXGI_DDGI_BLEND_RADIANCE=0",
                     [CB(0, cb), SRV(1, self.ddgi_rays), TEX_SRV(3, self.ddgi_data), TEX_UAV(2, self.ddgi_distance, 0)], (cx, cz, cy))
-        if not (u["relocate"] or u["classify"]):
-            return
+        if u["relocate"] or u["classify"]:
+            self._ddgi_placement(cl, cb)
+        if u["variability"]:
+            self._ddgi_variability(cl, cb)
+
+    def _ddgi_placement(self, cl, cb):
+        sc, u = self.scene, self.ddgi_update
+        rt = sc.rt
+        cx, cy, cz = self.ddgi.counts
         n = cx * cy * cz                             # GIRenderer.cpp:513-527: relocation and classification behind the blends
         cl.dispatch("giprobetrace_CS_ProbeTraceFixedRays",
                     [CB(0, cb), SRV(0, self.ddgi_desc), TEX_SRV(1, self.ddgi_data), SRV(4, rt["tlas_nodes"]), SRV(5, sc.instances), SRV(6, sc.vertices), SRV(8, sc.indices),
@@ -1070,13 +1166,14 @@ class FrameDriver:
             cl.end_pipeline_stats(query)
         if self.ao is not None:                                                          # Scene.cpp's order: behind GBufferRenderer, in front of lighting
             self._ambient_occlusion(cl)
-        if self.shadows is not None or self.ddgi_update is not None:                     # the TLAS of this frame's instance buffer
+        ddgi_skip = self.ddgi_update is not None and self._ddgi_begin_update()           # converged: nothing of the update, its refit included
+        if self.shadows is not None or (self.ddgi_update is not None and not ddgi_skip):  # the TLAS of this frame's instance buffer
             self._refit_tlas(cl)
         if self.shadows is not None:                                                     # Scene.cpp:500: behind AO, in front of lighting
             self._shadow_mask(cl)
             if self.shadow_denoise is not None:
                 self._denoise_shadows(cl)
-        if self.ddgi_update is not None:                                                 # behind the refit, in front of lighting
+        if self.ddgi_update is not None and not ddgi_skip:                               # behind the refit, in front of lighting
             self._ddgi_update(cl)
         if self.lighting_on:
             self._deferred_lighting(cl)
@@ -1125,6 +1222,7 @@ class FrameDriver:
         for t in (self.visibility, self.motion, self.gbufferA, self.lighting_output, self.back_buffer, self.exposure_texture, self.luminance, self.histogram,
                   self.bloom_texture, self.ao_depth, self.ao_working, self.ao_edges, self.ssao_texture, self.shadow_mask_texture, self.linear_view_depth,
                   self.blue_noise, self.ddgi_desc, self.ddgi_data, self.ddgi_irradiance, self.ddgi_distance, self.ddgi_rays, self.ddgi_fixed_rays,
+                  self.ddgi_variability_buffer, self.ddgi_variability_readback, *(self.ddgi_variability_average or ()),
                   self.probe_positions, self.probe_states, self.probe_culled_positions, self.probe_draw_args, self.probe_instance_to_probe, self.probe_sphere_vertices,
                   self.probe_sphere_indices, self.probe_winners, self.anti_aliased_output, *(self.taa_history or ()), self.shadow_penumbra, self.normal_roughness,
                   self.shadow_tiles, *(self.shadow_data or ()), *(self.shadow_history or ())):

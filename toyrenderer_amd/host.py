@@ -31,6 +31,7 @@ HOST_SYMBOLS = [
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
     "trhost_get_deferred_lighting_consts", "trhost_upload_ddgi_volume", "trhost_set_ddgi",
     "trhost_set_ddgi_update", "trhost_set_ddgi_probe_placement", "trhost_reset_ddgi_volume", "trhost_download_ddgi_volume", "trhost_get_ddgi_update_consts",
+    "trhost_set_ddgi_probe_variability", "trhost_get_ddgi_variability", "trhost_reset_ddgi_variability", "trhost_ddgi_variability_run", "trhost_download_ddgi_variability",
     "trhost_set_ddgi_probe_visualization", "trhost_get_ddgi_probe_visualization_consts", "trhost_unit_sphere",
     "trhost_set_post_process", "trhost_set_exposure", "trhost_set_auto_exposure", "trhost_set_frame_time_ms", "trhost_upload_bloom",
     "trhost_download_back_buffer", "trhost_get_scene_luminance", "trhost_reset_exposure", "trhost_get_post_process_consts",
@@ -116,6 +117,11 @@ def load() -> C.CDLL:
     L.trhost_reset_ddgi_volume.argtypes = []
     L.trhost_download_ddgi_volume.argtypes = [vp, u64, vp, u64, vp, u64]
     L.trhost_get_ddgi_update_consts.argtypes = [vp]
+    L.trhost_set_ddgi_probe_variability.argtypes = [C.c_int, C.c_float]
+    L.trhost_get_ddgi_variability.argtypes = [vp] * 5
+    L.trhost_reset_ddgi_variability.argtypes = []
+    L.trhost_ddgi_variability_run.argtypes = [vp, C.c_uint32, C.c_float, vp, vp]
+    L.trhost_download_ddgi_variability.argtypes = [vp, u64]
     L.trhost_set_ddgi_probe_visualization.argtypes = [C.c_int, C.c_float, C.c_int]
     L.trhost_get_ddgi_probe_visualization_consts.argtypes = [vp]
     L.trhost_unit_sphere.argtypes = [vp, u64, vp, u64]
@@ -420,6 +426,28 @@ class Renderer:
         v = volume.copy()
         _check(load().trhost_download_ddgi_volume(v.irradiance.ctypes.data, v.irradiance.nbytes, v.distance.ctypes.data, v.distance.nbytes, v.data.ctypes.data, v.data.nbytes))
         return v
+
+    def set_ddgi_probe_variability(self, enable: bool = True, stddev_threshold: float = 0.001):
+        """The reference's probe variability: the update stops recording once the volume's average variability has settled
+        (needs set_ddgi_update; include/trhost.h)."""
+        _check(load().trhost_set_ddgi_probe_variability(int(enable), float(stddev_threshold)))
+
+    def ddgi_variability(self) -> dict:
+        """average (the last one read back), stddev (of the ring), converged, samples, skipped (updates that recorded nothing)."""
+        a, s, c, n, k = C.c_float(), C.c_float(), C.c_int(), C.c_uint32(), C.c_uint32()
+        _check(load().trhost_get_ddgi_variability(C.byref(a), C.byref(s), C.byref(c), C.byref(n), C.byref(k)))
+        return dict(average=np.float32(a.value), stddev=np.float32(s.value), converged=bool(c.value), samples=int(n.value), skipped=int(k.value))
+
+    def reset_ddgi_variability(self):
+        """Re-arms a converged volume: the whole tracker and the variability buffer start again."""
+        _check(load().trhost_reset_ddgi_variability())
+
+    def download_ddgi_variability(self, volume) -> np.ndarray:
+        """The variability buffer, float32 [counts.y, 6 counts.z, 6 counts.x] of `volume` (the ddgi.Volume that was uploaded)."""
+        cx, cy, cz = volume.counts
+        out = np.zeros((cy, 6 * cz, 6 * cx), np.float32)
+        _check(load().trhost_download_ddgi_variability(out.ctypes.data, out.nbytes))
+        return out
 
     def ddgi_update_consts(self) -> np.ndarray:
         """The DDGIUpdateConsts of the last frame's probe update, the ray rotation among them; raises if none ran in it."""
@@ -740,3 +768,12 @@ class Renderer:
 
     def shutdown(self):
         load().trhost_shutdown()
+
+
+def ddgi_variability_run(averages, threshold: float = 0.001):
+    """csrc/host/DDGIVariability.h's rule over a sequence of averages, no device: (converged bool [n], stddev float32 [n]) after
+    each Update (trhost_ddgi_variability_run, include/trhost.h)."""
+    a = np.ascontiguousarray(averages, np.float32)
+    conv, dev = np.zeros(len(a), np.uint8), np.zeros(len(a), np.float32)
+    _check(load().trhost_ddgi_variability_run(a.ctypes.data, len(a), float(threshold), conv.ctypes.data, dev.ctypes.data))
+    return conv.astype(bool), dev

@@ -125,7 +125,7 @@ kDeferredLightingDebugMode_ShadowMask = 11
 DDGIVolumeDesc = np.dtype([("origin", np.float32, (3,)), ("probeNormalBias", np.float32), ("probeSpacing", np.float32, (3,)), ("probeViewBias", np.float32),
                            ("probeCounts", np.int32, (3,)), ("probeIrradianceEncodingGamma", np.float32), ("numIrradianceInteriorTexels", np.uint32),
                            ("numDistanceInteriorTexels", np.uint32), ("flags", np.uint32), ("pad", np.uint32)])
-kDDGIFlag_Relocation, kDDGIFlag_Classification = 1, 2
+kDDGIFlag_Relocation, kDDGIFlag_Classification, kDDGIFlag_Variability = 1, 2, 4
 kDDGIIrradianceInteriorTexels, kDDGIDistanceInteriorTexels, kDDGIMaxProbeCount = 6, 14, 1024
 # csrc/ShaderInterop.h: the project's own b0 of the probe trace and the two probe blends; the DDGIVolumeDesc follows it in b0
 DDGIUpdateConsts = np.dtype([("m_DirectionalLightVector", np.float32, (3,)), ("m_DirectionalLightStrength", np.float32), ("rayRotation", np.float32, (3, 4)),
@@ -133,6 +133,11 @@ DDGIUpdateConsts = np.dtype([("m_DirectionalLightVector", np.float32, (3,)), ("m
                              ("probeIrradianceThreshold", np.float32), ("probeBrightnessThreshold", np.float32), ("probeMinFrontfaceDistance", np.float32),
                              ("probeFixedRayBackfaceThreshold", np.float32), ("pad", np.uint32)])
 kDDGIRaysPerProbe, kDDGIBackfaceRayLimit, kDDGIFixedRays = 256, 25, 32
+# csrc/ShaderInterop.h: the SDK's DDGIRootConstants, push constants of the two reduction passes (csrc/k_ddgireduction.hip)
+DDGIRootConstants = np.dtype([("volumeIndex", np.uint32), ("volumeConstantsIndex", np.uint32), ("volumeResourceIndicesIndex", np.uint32),
+                              ("reductionInputSizeX", np.uint32), ("reductionInputSizeY", np.uint32), ("reductionInputSizeZ", np.uint32)])
+kDDGIMinimumVariabilitySamples = 16
+kDDGIReductionGroup = (16, 16, 4)                 # inputs per workgroup: 4 x 8 x 4 threads of 4 x 2 inputs each
 
 SIZES = {
     "BasePassInstanceConstants": 144, "MeshLODData": 16, "MeshData": 156, "MeshletData": 32,
@@ -142,7 +147,7 @@ SIZES = {
     "GenerateLuminanceHistogramParameters": 16, "AdaptExposureParameters": 20, "PostProcessParameters": 24,
     "BloomConsts": 16, "TAAConsts": 32, "HosekWilkieSkyParameters": 160, "SkyPassParameters": 256,
     "GTAOConstants": 96, "XeGTAOMainPassConstantBuffer": 68, "XeGTAODenoiseConstants": 4,
-    "ShadowMaskConsts": 112, "PackNormalAndRoughnessConsts": 8, "SigmaConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96, "GIProbeVisualizationConsts": 96, "UncompressedRawVertexFormat": 32, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
+    "ShadowMaskConsts": 112, "PackNormalAndRoughnessConsts": 8, "SigmaConsts": 112, "DDGIVolumeDesc": 64, "DDGIUpdateConsts": 96, "DDGIRootConstants": 24, "GIProbeVisualizationConsts": 96, "UncompressedRawVertexFormat": 32, "RefitTLASConstants": 12, "AccelNode": 32, "BLASHeader": 16, "TLASInstance": 64,
 }
 for _n, _s in SIZES.items():
     assert globals()[_n].itemsize == _s, (_n, globals()[_n].itemsize, _s)

@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "trhip_timer_create", "trhip_timer_release", "trhip_timer_get_ms",
     "trhip_pipeline_stats_create", "trhip_pipeline_stats_release", "trhip_cmd_begin_pipeline_stats",
     "trhip_cmd_end_pipeline_stats", "trhip_pipeline_stats_get",
+    "trhip_readback_create", "trhip_readback_release", "trhip_readback_reset", "trhip_cmd_copy_to_readback", "trhip_readback_read",
     "trhip_profile_enable", "trhip_profile_filter", "trhip_profile_reset", "trhip_profile_count", "trhip_profile_entry",
     "trhip_launch_shard_late_info",
     "trhip_accel_max_depth", "trhip_blas_leaf_capacity", "trhip_accel_max_nodes", "trhip_blas_build", "trhip_tlas_build",
@@ -204,6 +205,13 @@ def load() -> C.CDLL:
     L.trhip_cmd_begin_pipeline_stats.argtypes = [vp, vp]
     L.trhip_cmd_end_pipeline_stats.argtypes = [vp, vp]
     L.trhip_pipeline_stats_get.argtypes = [vp, C.POINTER(PipelineStatistics)]
+    if hasattr(L, "trhip_readback_create"):              # an experiment build (TRHIP_LIB) from before the read-back has none
+        L.trhip_readback_create.argtypes = [vp, C.c_uint64, u32, C.POINTER(vp)]
+        L.trhip_readback_release.argtypes = [vp]
+        L.trhip_readback_release.restype = None
+        L.trhip_readback_reset.argtypes = [vp]
+        L.trhip_cmd_copy_to_readback.argtypes = [vp, vp, u32, vp, C.c_uint64, C.c_uint64]
+        L.trhip_readback_read.argtypes = [vp, u32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.trhip_profile_enable.argtypes = [vp, i32]
     L.trhip_profile_filter.argtypes = [vp, C.c_char_p]
     L.trhip_profile_reset.argtypes = [vp]
@@ -399,6 +407,30 @@ class PipelineStatsQuery:
             self.h = None
 
 
+class Readback:
+    """nvrhi's staging resource: trhip_readback (include/trhip.h), `slots` slots of pinned host memory with one event each."""
+    def __init__(self, dev, handle, bytes_per_slot: int, slots: int):
+        self.dev, self.h, self.bytes_per_slot, self.slots = dev, handle, int(bytes_per_slot), int(slots)
+
+    def read(self, slot: int, dtype=np.uint8, count: int | None = None):
+        """(array, bytes written): waits for that slot's copy only.  A slot never written gives zeros and 0."""
+        dt = np.dtype(dtype)
+        out = np.zeros(self.bytes_per_slot // dt.itemsize if count is None else int(count), dt)
+        written = C.c_uint64()
+        _check(load().trhip_readback_read(self.h, int(slot), out.ctypes.data, out.nbytes, C.byref(written)))
+        return out, int(written.value)
+
+    def reset(self):
+        """Waits for the device and marks every slot as never written; recorded lists that name the resource stay valid."""
+        _check(load().trhip_readback_reset(self.h))
+
+    def release(self):
+        """Every list that names the resource must have been re-opened or released first (include/trhip.h)."""
+        if self.h:
+            load().trhip_readback_release(self.h)
+            self.h = None
+
+
 class CommandList:
     def __init__(self, dev: "Device", handle):
         self.dev, self.h = dev, handle
@@ -463,6 +495,8 @@ class CommandList:
     def end_timer(self, t: Timer): _check(load().trhip_cmd_end_timer(self.h, t.h))
     def begin_pipeline_stats(self, q: PipelineStatsQuery): _check(load().trhip_cmd_begin_pipeline_stats(self.h, q.h))
     def end_pipeline_stats(self, q: PipelineStatsQuery): _check(load().trhip_cmd_end_pipeline_stats(self.h, q.h))
+    def copy_to_readback(self, rb: Readback, slot: int, src: Buffer, offset: int, nbytes: int):
+        _check(load().trhip_cmd_copy_to_readback(self.h, rb.h, int(slot), src.h, int(offset), int(nbytes)))
     def begin_marker(self, name: str): _check(load().trhip_cmd_begin_marker(self.h, name.encode()))
     def end_marker(self): _check(load().trhip_cmd_end_marker(self.h))
 
@@ -566,6 +600,13 @@ class Device:
         h = C.c_void_p()
         _check(load().trhip_pipeline_stats_create(self.h, C.byref(h)))
         return PipelineStatsQuery(self, h)
+
+    def create_readback(self, bytes_per_slot: int, slots: int) -> Readback:
+        h = C.c_void_p()
+        if not hasattr(load(), "trhip_readback_create"):
+            raise TrhipError(f"{LIB_PATH} has no read-back: a build from before probe variability")
+        _check(load().trhip_readback_create(self.h, int(bytes_per_slot), int(slots), C.byref(h)))
+        return Readback(self, h, bytes_per_slot, slots)
 
     def execute(self, *lists: CommandList):
         arr = (C.c_void_p * len(lists))(*[cl.h for cl in lists])
