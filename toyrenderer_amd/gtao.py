@@ -6,6 +6,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import interop as I
+from . import rhi
+from .rhi import CB, PUSH, SAMPLER, TEX_SRV, TEX_UAV
 
 F = np.float32
 # AmbientOcclusionRenderer::Initialize sets quality 3 (Ultra) and 3 denoise passes; the rest are GTAOSettings' defaults
@@ -80,3 +82,60 @@ def denoise_constants(final_apply: bool) -> np.ndarray:
     k = np.zeros(1, I.XeGTAODenoiseConstants)
     k["m_FinalApply"] = int(final_apply)
     return k
+
+
+class AmbientOcclusionPass:
+    """ao: None (the default) changes nothing.  A dict of settings, any of quality (0..3: Low, Medium, High, Ultra), denoise_passes
+    (0..3), radius, falloff_range, final_value_power, depth_mip_sampling_offset (the reference's defaults: 3, 3, 0.5, 0.615, 2.2,
+    3.3; needs gbuffer=True, which lighting implies; not together with an external ssao=): AmbientOcclusionRenderer
+    (AmbientOcclusionRenderer.cpp, XeGTAO).  The driver owns the working depth chain (R16_FLOAT, 5 mips), the working AO term
+    (R8_UINT), the edges (R8_UNORM) and self.ssao_texture (R8_UINT); after the G-buffer resolve and in front of the lighting
+    dispatch it records "ambientocclusion_CS_XeGTAO_PrefilterDepths", "ambientocclusion_CS_XeGTAO_MainPass DEBUG_OUTPUT_MODE=0"
+    and max(1, denoise_passes) "ambientocclusion_CS_XeGTAO_Denoise" dispatches ping-ponging between the working term and
+    self.ssao_texture, the last with m_FinalApply = 1; as in the reference, with 2 passes the finally-applied image lands in
+    the working term and self.ssao_texture holds the first pass's output.  With lighting the texture is the lighting pass's
+    t3 and m_SSAOEnabled is 1; debug view 9 shows it, and the non-debug pass multiplies the DDGI ambient term by it: with
+    ddgi= the texture changes LightingOutput, without it (no ambient term) it does not.  self.frame_counter (0; the caller may set it
+    before record()) feeds NoiseIndex as g_Graphic.m_FrameCounter % 256 does; self.gtao_consts holds the 96-byte GTAOConstants
+    of the last record(); download_ssao() reads self.ssao_texture back."""
+    ao = gtao_consts = ao_depth = ao_working = ao_edges = ssao_texture = None
+
+    def _check_ao(self, ao, gbuffer, ssao):
+        if ao is not None:
+            if not gbuffer:
+                raise ValueError("ao=... needs gbuffer=True (or lighting=True): the main pass reads the normals of GBufferA")
+            if ssao is not None:
+                raise ValueError("ao=... together with an external ssao= texture: the driver generates the texture itself")
+            self.ao = check_settings(ao)
+
+    def _create_ao(self):                            # AmbientOcclusionRenderer::Setup (AmbientOcclusionRenderer.cpp:85-127)
+        dev, W, H = self.dev, self.view.renderW, self.view.renderH
+        if self.ao is not None:
+            self.ao_depth = self._own(dev.create_texture(W, H, DEPTH_MIP_LEVELS, rhi.FORMAT_R16_FLOAT, "XeGTAO Working Depth Buffer"))
+            self.ssao_texture = self._own(dev.create_texture(W, H, 1, rhi.FORMAT_R8_UINT, "SSAO Buffer"))
+            self.ao_working = self._own(dev.create_texture(W, H, 1, rhi.FORMAT_R8_UINT, "Working SSAO Texture"))
+            self.ao_edges = self._own(dev.create_texture(W, H, 1, rhi.FORMAT_R8_UNORM, "Working Edges Texture"))
+            self.ssao = self.ssao_texture            # what the lighting pass binds as t3
+
+    # ---- AmbientOcclusionRenderer::Render (AmbientOcclusionRenderer.cpp:129-248) ------------------------------------------
+    def _ambient_occlusion(self, cl):
+        v, W, H = self.view, self.view.renderW, self.view.renderH
+        self.gtao_consts = update_constants(W, H, self.ao, v.viewToClip, int(self.frame_counter) % 256)
+        cb = cl.constant_buffer(self.gtao_consts, "GTAOConstants")
+        cl.dispatch("ambientocclusion_CS_XeGTAO_PrefilterDepths",
+                    [CB(0, cb), TEX_SRV(0, self.depth), *[TEX_UAV(m, self.ao_depth, m) for m in range(DEPTH_MIP_LEVELS)], SAMPLER(0)],
+                    ((W + 15) // 16, (H + 15) // 16, 1))
+        cl.dispatch("ambientocclusion_CS_XeGTAO_MainPass DEBUG_OUTPUT_MODE=0",
+                    [CB(0, cb), PUSH(1), TEX_SRV(0, self.ao_depth), TEX_SRV(2, self.gbufferA), TEX_UAV(0, self.ao_working, 0), TEX_UAV(1, self.ao_edges, 0), SAMPLER(0)],
+                    I.groups8(W, H), push=main_pass_constants(v.worldToView, self.ao["quality"]))
+        ping_pong = [self.ao_working, self.ssao_texture]
+        passes = max(1, self.ao["denoise_passes"])   # without denoising one last pass still writes the term into the output texture
+        for i in range(passes):
+            cl.dispatch("ambientocclusion_CS_XeGTAO_Denoise",
+                        [CB(0, cb), PUSH(1), TEX_SRV(0, ping_pong[0]), TEX_SRV(1, self.ao_edges), TEX_UAV(0, ping_pong[1], 0), SAMPLER(0)],
+                        ((W + 15) // 16, (H + 7) // 8, 1), push=denoise_constants(i == passes - 1))
+            ping_pong.reverse()
+
+    def download_ssao(self) -> np.ndarray:
+        """The bytes of the generated SSAO texture, (H, W) uint8."""
+        return self._download("download_ssao", self.ssao_texture, "AO generation is off (ao=None)", lambda: self.ssao_texture.download_mip(0))

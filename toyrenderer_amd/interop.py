@@ -228,6 +228,11 @@ def hzb_dims(render_w: int, render_h: int):
     return get_next_pow2(render_w) >> 1, get_next_pow2(render_h) >> 1
 
 
+def groups8(w: int, h: int):
+    """The group counts of a dispatch of 8 x 8 threads per group over w x h texels."""
+    return (w + 7) // 8, (h + 7) // 8, 1
+
+
 def hzb_layout(w: int, h: int):
     """Linear R16F mip chain used on the HIP side and by the oracle: mip k = max(w>>k,1) x
     max(h>>k,1) texels, row-major, mips packed back to back.  Returns (mips, offsets, total)."""

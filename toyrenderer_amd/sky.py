@@ -19,6 +19,7 @@ import re
 import numpy as np
 
 from . import interop as I
+from .rhi import CB, TEX_SRV, TEX_UAV
 
 F = np.float32
 DEFAULT_TURBIDITY = 2.0
@@ -140,3 +141,36 @@ def pass_parameters(clip_to_world, sun_direction, camera_position, params) -> np
     k["m_CameraPosition"] = np.asarray(camera_position, F).reshape(3)
     k["m_HosekParams"]["m_Params"][0, :, :3] = np.asarray(params, F).reshape(10, 3)
     return k
+
+
+class SkyPass:
+    """sky: None (the default) changes nothing.  (dataset,) or (dataset, turbidity, ground_albedo) with a sky.HosekDataset
+    (needs lighting=True; the reference's defaults are turbidity 2.0 and ground albedo (0.1, 0.1, 0.1)): SkyRenderer
+    (SkyRenderer.cpp).  One "sky_PS_HosekWilkieSky" dispatch directly behind the lighting dispatch, in front of bloom and the
+    histogram clear, whatever debug_mode is, fills every texel of LightingOutput whose depth is <= 0.  The sun direction is
+    dir_light[0] as given, the camera position camera_origin, the matrix the lighting pass's m_ClipToWorld.
+    self.sky_consts holds the 256-byte SkyPassParameters of the last record()."""
+    sky = sky_consts = None
+
+    def _check_sky(self, sky, lighting):
+        if sky is None:
+            return
+        if not lighting:
+            raise ValueError("sky=... needs lighting=True: the pass fills the texels of LightingOutput the lighting pass leaves")
+        sky = tuple(sky)
+        if not (1 <= len(sky) <= 3) or not isinstance(sky[0], HosekDataset):
+            raise ValueError("sky: needs (dataset, turbidity, ground_albedo) with a sky.HosekDataset first")
+        turbidity = sky[1] if len(sky) > 1 else DEFAULT_TURBIDITY
+        albedo = sky[2] if len(sky) > 2 else DEFAULT_GROUND_ALBEDO
+        check_settings(turbidity, albedo)
+        self.sky = (sky[0], np.float32(turbidity), tuple(np.float32(x) for x in albedo))
+
+    # ---- SkyRenderer::Render (SkyRenderer.cpp:163-208) -------------------------------------------------------------------
+    def _sky(self, cl):
+        v = self.view
+        dataset, turbidity, albedo = self.sky
+        sun = np.asarray(self.dir_light[0], np.float32)
+        params = sky_parameters(dataset, turbidity, albedo, sun)
+        self.sky_consts = pass_parameters(self.lighting_consts["m_ClipToWorld"][0], sun, self.camera_origin, params)
+        cb = cl.constant_buffer(self.sky_consts, "SkyPassParameters")
+        cl.dispatch("sky_PS_HosekWilkieSky", [CB(0, cb), TEX_SRV(0, self.depth), TEX_UAV(0, self.lighting_output, 0)], I.groups8(v.renderW, v.renderH))
