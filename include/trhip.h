@@ -61,10 +61,23 @@ enum {
  * trhip_texture_upload; one that a pass writes keeps one mip.
  * R10G10B10A2_UNORM (12: the DDGI probe irradiance; 4 bytes per texel, R in bits 0-9, G in bits 10-19, B in bits 20-29, A in bits
  * 30-31) and RGBA16_FLOAT (13: the DDGI probe data; 8 bytes per texel, four binary16 x, y, z, w) have one mip; they are created,
- * uploaded and downloaded, and both clears refuse them. */
+ * uploaded and downloaded, and both clears refuse them.
+ * BLOCK-COMPRESSED formats (14..21: BC1, BC2, BC3 with their _SRGB variants, BC4, BC5; all UNORM) are material textures only: created
+ * with isUAV == 0, with up to a full mip chain, never as an array.  Level k of max(w >> k, 1) x max(h >> k, 1) texels is stored as
+ * ceil(w_k / 4) x ceil(h_k / 4) blocks of trhip_format_block_bytes(format) bytes, row-major, at the 256-byte aligned offset
+ * trhip_texture_mip_info answers; any width and height >= 1 are accepted, and the texels of an edge block beyond the level's size
+ * are never read.  trhip_texture_upload / _download move the block bytes of one whole level.  Such a texture reaches a kernel
+ * through the texture table only: both clears, a copy to a texture of another format and every Texture_SRV / Texture_UAV binding
+ * refuse it.  A sampling pass decodes one texel per fetch, byte-exactly (csrc/material_textures.hip.h states the decode, DESIGN.md
+ * 3 restates it); the _SRGB variants send the decoded R, G and B through trhip_srgb_table, alpha stays linear.  BC4 decodes to
+ * (R, 0, 0, 255), BC5 to (R, G, 0, 255).  There is no encoder, and BC6H, BC7 and the SNORM variants are not supported. */
 enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4,
        TRHIP_FORMAT_RGBA32_UINT = 5, TRHIP_FORMAT_R11G11B10_FLOAT = 6, TRHIP_FORMAT_R8_UNORM = 7, TRHIP_FORMAT_R8_UINT = 8,
-       TRHIP_FORMAT_RGBA8_UNORM = 10, TRHIP_FORMAT_SRGBA8_UNORM = 11, TRHIP_FORMAT_R10G10B10A2_UNORM = 12, TRHIP_FORMAT_RGBA16_FLOAT = 13 };
+       TRHIP_FORMAT_RGBA8_UNORM = 10, TRHIP_FORMAT_SRGBA8_UNORM = 11, TRHIP_FORMAT_R10G10B10A2_UNORM = 12, TRHIP_FORMAT_RGBA16_FLOAT = 13,
+       TRHIP_FORMAT_BC1_UNORM = 14, TRHIP_FORMAT_BC1_UNORM_SRGB = 15, TRHIP_FORMAT_BC2_UNORM = 16, TRHIP_FORMAT_BC2_UNORM_SRGB = 17,
+       TRHIP_FORMAT_BC3_UNORM = 18, TRHIP_FORMAT_BC3_UNORM_SRGB = 19, TRHIP_FORMAT_BC4_UNORM = 20, TRHIP_FORMAT_BC5_UNORM = 21 };
+/* Bytes of one 4 x 4 block: 8 (BC1, BC4) or 16 (BC2, BC3, BC5); 0 for every format that is not block-compressed.  No device needed. */
+uint32_t    trhip_format_block_bytes(uint32_t format);
 
 /* ---- error / introspection ---------------------------------------------------------------- */
 const char* trhip_last_error(void);          /* thread-local text of the last failure          */
@@ -107,7 +120,7 @@ uint32_t    trhip_abi_version(void);
  * GetCommonGBufferParams (lightingcommon.hlsli:435-493) with derivatives from the triangle's plane, tangent-free normal mapping,
  * u0.w = PackRGBA8(roughness, metallic, 0, 0).  The convention is stated in csrc/material_textures.hip.h and
  * csrc/visibility_resolve.hip.h.  A flagged slot whose descriptor index is at or past the table's capacity, names an empty entry
- * or an entry of a format other than RGBA8_UNORM / SRGBA8_UNORM leaves the pixel as it is in both targets.  Refused at record
+ * or an entry of a format other than RGBA8_UNORM / SRGBA8_UNORM / the BC formats leaves the pixel as it is in both targets.  Refused at record
  * time: a table that holds a texture created with the UAV or render-target bit.
  * That check covers the table's contents when the dispatch is recorded: trhip_texture_table_set rewrites an entry in place, so a
  * UAV-capable texture set AFTERWARDS is sampled by the lists already recorded (read only; nothing is written through the table)
@@ -278,7 +291,8 @@ void trhip_texture_retain(trhip_texture tex);
 void trhip_texture_release(trhip_texture tex);
 void* trhip_texture_device_ptr(trhip_texture tex);
 /* Layout in HBM: one linear allocation, mip k row-major max(w>>k,1) x max(h>>k,1) texels at
- * byte offset mip_offset(k); offsets are 256-byte aligned. */
+ * byte offset mip_offset(k); offsets are 256-byte aligned.  A block-compressed texture answers the same sizes in texels; its
+ * level k holds ceil(w_k / 4) x ceil(h_k / 4) blocks, row-major. */
 int  trhip_texture_mip_info(trhip_texture tex, uint32_t mip, uint32_t* w, uint32_t* h, uint64_t* byte_offset);
 uint64_t trhip_texture_size(trhip_texture tex);
 
@@ -305,6 +319,22 @@ int  trhip_texture_table_clear(trhip_texture_table table, uint32_t index);
  * in double precision (c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4)), rounded once to float.  The device keeps a
  * copy from its first texture table on. */
 int  trhip_srgb_table(float* out);
+
+/* ---- DDS container (no device needed; written from the public description of the format) ---------------------------------------
+ * trhip_dds_parse reads the header of a .dds file held in memory and answers what the file says: size, mip count, format, and
+ * where each level's bytes lie in the file (levels follow the header back to back, without padding; a level of a block format
+ * is ceil(w_k / 4) * ceil(h_k / 4) blocks, one of RGBA8 is w_k * h_k * 4 bytes).  Accepted: the legacy fourCCs DXT1 (BC1), DXT2
+ * and DXT3 (BC2), DXT4 and DXT5 (BC3), ATI1 and BC4U (BC4), ATI2 and BC5U (BC5), and a DX10 header with DXGI format 71 / 72
+ * (BC1 / BC1_SRGB), 74 / 75 (BC2), 77 / 78 (BC3), 80 (BC4), 83 (BC5), 28 / 29 (RGBA8_UNORM / SRGBA8_UNORM).  Refused, each with
+ * a message that names it: a bad magic or header size, mipMapCount == 0, more than 16 levels, an array size other than 1, cube
+ * and volume textures, the SNORM variants, BC6H and BC7, every other pixel format, a file shorter than its levels.  A legacy
+ * fourCC says nothing about sRGB: the loaders choose the variant by material slot (trhost_create_material_texture_dds,
+ * gltf_lite.load), where the reference forces every BC1 file to sRGB. */
+typedef struct {
+    uint32_t width, height, mipLevels, format;                 /* format: TRHIP_FORMAT_* */
+    uint64_t levelOffset[16], levelBytes[16];                  /* from the start of the file */
+} trhip_dds_info;
+int  trhip_dds_parse(const void* file, uint64_t bytes, trhip_dds_info* out);
 
 /* Contents changed behind the back end's back.  The back end keeps derived, private copies of some bound resources (the
  * instance cull cache, the meshlet cull stream of the buffer bound at t4 of basepass_AS_Main and, once a pipeline statistics

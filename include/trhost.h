@@ -86,13 +86,19 @@ int  trhost_download_motion(uint16_t* halves, uint64_t bytes);
 int  trhost_load_materials(const void* materials, uint32_t count);
 /* Textured materials.  trhost_create_material_texture uploads one material texture (format TRHIP_FORMAT_RGBA8_UNORM or
  * TRHIP_FORMAT_SRGBA8_UNORM; `data`: the mips back to back, level k of max(width >> k, 1) x max(height >> k, 1) texels of 4 bytes
- * R, G, B, A; `bytes` their sum) and returns its descriptor index (0, 1, ... in call order; -1 and trhost_last_error on failure):
+ * R, G, B, A; `bytes` their sum; or one of TRHIP_FORMAT_BC1_UNORM .. TRHIP_FORMAT_BC5_UNORM: level k is then ceil(w_k / 4) x
+ * ceil(h_k / 4) blocks of trhip_format_block_bytes(format) bytes, `bytes` the sum of the levels' block bytes) and returns its descriptor index (0, 1, ... in call order; -1 and trhost_last_error on failure):
  * the value a flagged TextureData::m_DescriptorIndex names.  The host owns the texture table (the stand-in of the bindless heap,
  * 4096 entries) and binds it at t19 of "basepass_PS_Main_GBuffer" whenever a loaded material has a texture flag; the resolve then
  * samples (include/trhip.h).  trhost_load_materials accepts a textured material when every flagged slot's m_DescriptorIndex names a
  * texture created before it and its m_FeedbackTextureDescriptorIndex and m_MinMapTextureDescriptorIndex are 0xFFFFFFFF; otherwise
  * it fails with a message containing "texture".  The textures live until trhost_shutdown. */
 int  trhost_create_material_texture(uint32_t width, uint32_t height, uint32_t mips, uint32_t format, const void* data, uint64_t bytes);
+/* Texture::LoadFromFile (TextureLoading.cpp) for a .dds file held in memory: trhip_dds_parse, then trhost_create_material_texture
+ * on the file's levels; returns the descriptor index, or -1 (the parser's message in trhost_last_error).  `srgb` is the material
+ * slot's choice (base colour and emissive: 1; normal and metallic-roughness: 0): it picks between a format and its _SRGB twin
+ * whatever the file says, and is ignored for BC4 and BC5.  The reference instead forces every BC1 file to sRGB. */
+int  trhost_create_material_texture_dds(const void* file, uint64_t bytes, int srgb);
 int  trhost_set_gbuffer(int enable);
 /* ALPHA_MASK_MODE's discard (basepass.hlsl:210-215), default 0 = off: alpha-mask primitives are drawn as solid triangles, as before.
  * With 1 (needs the rasters: trhost_set_raster_depth, trhost_set_visibility_buffer or anything that implies them, and

@@ -70,15 +70,27 @@ void Graphic::PostSceneLoad()
     ExecuteAllCommandLists();
 }
 
-// Texture::LoadFromFile + the SRV's slot in the bindless table (Visual.cpp, Graphic.h:111-113), from decoded texels: `data` holds
-// the mips back to back, level k of max(width >> k, 1) x max(height >> k, 1) x 4 bytes.  Returns the descriptor index.
+// Texture::LoadFromFile + the SRV's slot in the bindless table (Visual.cpp, Graphic.h:111-113), from decoded texels or from the
+// blocks of a block-compressed format: `data` holds the mips back to back, level k of max(width >> k, 1) x max(height >> k, 1) x 4
+// bytes, or of ceil(w_k / 4) x ceil(h_k / 4) blocks of 8 (BC1, BC4) or 16 bytes.  Returns the descriptor index.
+static uint32_t BlockBytes(nvrhi::Format format)
+{
+    if (format < nvrhi::Format::BC1_UNORM || format > nvrhi::Format::BC5_UNORM) return 0;
+    return format == nvrhi::Format::BC1_UNORM || format == nvrhi::Format::BC1_UNORM_SRGB || format == nvrhi::Format::BC4_UNORM ? 8u : 16u;
+}
+
 uint32_t Graphic::CreateMaterialTexture(uint32_t width, uint32_t height, uint32_t mips, nvrhi::Format format, const void* data, uint64_t bytes)
 {
-    if (format != nvrhi::Format::RGBA8_UNORM && format != nvrhi::Format::SRGBA8_UNORM)
-        throw nvrhi::Error("material texture: the format must be RGBA8_UNORM or SRGBA8_UNORM (block-compressed formats are not supported)");
+    const uint32_t blockBytes = BlockBytes(format);
+    if (format != nvrhi::Format::RGBA8_UNORM && format != nvrhi::Format::SRGBA8_UNORM && !blockBytes)
+        throw nvrhi::Error("material texture: the format must be RGBA8_UNORM, SRGBA8_UNORM or one of BC1 to BC5 (BC6H and BC7 are not supported)");
+    auto levelBytes = [&](uint32_t k) {
+        const uint64_t w = std::max(width >> k, 1u), h = std::max(height >> k, 1u);
+        return blockBytes ? ((w + 3) / 4) * ((h + 3) / 4) * blockBytes : w * h * 4u;
+    };
     if (!width || !height || !mips || mips > 16 || !data) throw nvrhi::Error("material texture: bad dimensions, mip count or data");
     uint64_t need = 0;
-    for (uint32_t k = 0; k < mips; ++k) need += (uint64_t)std::max(width >> k, 1u) * std::max(height >> k, 1u) * 4u;
+    for (uint32_t k = 0; k < mips; ++k) need += levelBytes(k);
     if (bytes != need) throw nvrhi::Error("material texture: " + std::to_string(mips) + " mips of " + std::to_string(width) + " x " + std::to_string(height) + " are " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
     if (m_Textures.size() >= kMaxMaterialTextures) throw nvrhi::Error("material texture: the descriptor table is full");
     if (!m_SrvUavCbvDescriptorTable) m_SrvUavCbvDescriptorTable = m_NVRHIDevice->createDescriptorTable(kMaxMaterialTextures);
@@ -89,7 +101,7 @@ uint32_t Graphic::CreateMaterialTexture(uint32_t width, uint32_t height, uint32_
     nvrhi::TextureHandle t = m_NVRHIDevice->createTexture(d);
     const uint8_t* p = (const uint8_t*)data;
     for (uint32_t k = 0; k < mips; ++k) {
-        const uint64_t n = (uint64_t)std::max(width >> k, 1u) * std::max(height >> k, 1u) * 4u;
+        const uint64_t n = levelBytes(k);
         nvrhi::throwIfFailed(trhip_texture_upload(t->native(), k, p, n), "material texture upload");
         p += n;
     }

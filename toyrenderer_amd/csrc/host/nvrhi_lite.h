@@ -93,7 +93,8 @@ private:
 using ResourceHandle = RefCountPtr<IResource>;
 
 // ---- enums / small structs -----------------------------------------------------------------------
-enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT, RGBA8_UNORM, SRGBA8_UNORM, R10G10B10A2_UNORM, RGBA16_FLOAT };   // GraphicConstants.h:24-28, :31 (lighting output), shadow mask, SSAO, the back buffer (GraphicRHI.cpp:214)
+enum class Format : uint8_t { UNKNOWN, R16_FLOAT, R32_FLOAT, D24S8, RG32_UINT, RG16_FLOAT, RGBA32_UINT, R11G11B10_FLOAT, R8_UNORM, R8_UINT, RGBA8_UNORM, SRGBA8_UNORM, R10G10B10A2_UNORM, RGBA16_FLOAT,
+                            BC1_UNORM, BC1_UNORM_SRGB, BC2_UNORM, BC2_UNORM_SRGB, BC3_UNORM, BC3_UNORM_SRGB, BC4_UNORM, BC5_UNORM };   // GraphicConstants.h:24-28; the BC names: material textures (TextureLoading.cpp:29-56), :31 (lighting output), shadow mask, SSAO, the back buffer (GraphicRHI.cpp:214)
 enum class ResourceStates : uint32_t { Unknown = 0, ShaderResource, UnorderedAccess, IndirectArgument, DepthRead, DepthWrite, CopyDest };
 enum class CommandQueue : uint8_t { Graphics = 0, Compute, Copy, Count };
 enum class HeapType : uint8_t { DeviceLocal };
@@ -490,7 +491,9 @@ public:
                  : d.format == Format::R11G11B10_FLOAT ? TRHIP_FORMAT_R11G11B10_FLOAT : d.format == Format::R8_UNORM ? TRHIP_FORMAT_R8_UNORM
                  : d.format == Format::R8_UINT ? TRHIP_FORMAT_R8_UINT : d.format == Format::RGBA8_UNORM ? TRHIP_FORMAT_RGBA8_UNORM
                  : d.format == Format::SRGBA8_UNORM ? TRHIP_FORMAT_SRGBA8_UNORM : d.format == Format::R10G10B10A2_UNORM ? TRHIP_FORMAT_R10G10B10A2_UNORM
-                 : d.format == Format::RGBA16_FLOAT ? TRHIP_FORMAT_RGBA16_FLOAT : TRHIP_FORMAT_R32_FLOAT;
+                 : d.format == Format::RGBA16_FLOAT ? TRHIP_FORMAT_RGBA16_FLOAT
+                 : d.format >= Format::BC1_UNORM && d.format <= Format::BC5_UNORM ? (decltype(TRHIP_FORMAT_R32_FLOAT))(TRHIP_FORMAT_BC1_UNORM + ((uint32_t)d.format - (uint32_t)Format::BC1_UNORM))   // the same order in both enums
+                 : TRHIP_FORMAT_R32_FLOAT;
         trhip_texture t = nullptr;
         if (d.dimension == kTexture2DArray) throwIfFailed(trhip_texture_create_array(m_Native, &n, d.arraySize, &t), "IDevice::createTexture (array)");
         else throwIfFailed(trhip_texture_create(m_Native, &n, &t), "IDevice::createTexture");

@@ -138,14 +138,40 @@ int trhost_load_materials(const void* materials, uint32_t count)
     });
 }
 
+// nvrhi::Format of a TRHIP_FORMAT_* that a material texture may have
+static nvrhi::Format MaterialTextureFormat(const char* who, uint32_t format)
+{
+    if (format == TRHIP_FORMAT_RGBA8_UNORM) return nvrhi::Format::RGBA8_UNORM;
+    if (format == TRHIP_FORMAT_SRGBA8_UNORM) return nvrhi::Format::SRGBA8_UNORM;
+    if (format >= TRHIP_FORMAT_BC1_UNORM && format <= TRHIP_FORMAT_BC5_UNORM) return (nvrhi::Format)((uint32_t)nvrhi::Format::BC1_UNORM + (format - TRHIP_FORMAT_BC1_UNORM));
+    throw nvrhi::Error(std::string(who) + ": format " + std::to_string(format) + ": a material texture is TRHIP_FORMAT_RGBA8_UNORM, TRHIP_FORMAT_SRGBA8_UNORM or one of TRHIP_FORMAT_BC1_UNORM .. TRHIP_FORMAT_BC5_UNORM");
+}
+
 int trhost_create_material_texture(uint32_t width, uint32_t height, uint32_t mips, uint32_t format, const void* data, uint64_t bytes)
 {
     int index = -1;
     int rc = guarded([&] {
         check(g_Scene);
-        if (format != TRHIP_FORMAT_RGBA8_UNORM && format != TRHIP_FORMAT_SRGBA8_UNORM)
-            throw nvrhi::Error("trhost_create_material_texture: format " + std::to_string(format) + ": a material texture is TRHIP_FORMAT_RGBA8_UNORM or TRHIP_FORMAT_SRGBA8_UNORM");
-        index = (int)g_Graphic.CreateMaterialTexture(width, height, mips, format == TRHIP_FORMAT_SRGBA8_UNORM ? nvrhi::Format::SRGBA8_UNORM : nvrhi::Format::RGBA8_UNORM, data, bytes);
+        index = (int)g_Graphic.CreateMaterialTexture(width, height, mips, MaterialTextureFormat("trhost_create_material_texture", format), data, bytes);
+    });
+    return rc == 0 ? index : -1;
+}
+
+int trhost_create_material_texture_dds(const void* file, uint64_t bytes, int srgb)
+{
+    int index = -1;
+    int rc = guarded([&] {
+        check(g_Scene && file);
+        trhip_dds_info info;
+        nvrhi::throwIfFailed(trhip_dds_parse(file, bytes, &info), "trhost_create_material_texture_dds");
+        // the material slot decides between a format and its _SRGB twin, whatever the file says (the pairs are adjacent values)
+        uint32_t format = info.format;
+        const bool pair = format == TRHIP_FORMAT_RGBA8_UNORM || format == TRHIP_FORMAT_SRGBA8_UNORM || (format >= TRHIP_FORMAT_BC1_UNORM && format <= TRHIP_FORMAT_BC3_UNORM_SRGB);
+        if (pair) format = ((format - TRHIP_FORMAT_RGBA8_UNORM) & ~1u) + TRHIP_FORMAT_RGBA8_UNORM + (srgb ? 1u : 0u);
+        uint64_t total = 0;
+        for (uint32_t k = 0; k < info.mipLevels; ++k) total += info.levelBytes[k];                  // the levels are contiguous in the file
+        index = (int)g_Graphic.CreateMaterialTexture(info.width, info.height, info.mipLevels, MaterialTextureFormat("trhost_create_material_texture_dds", format),
+                                                     (const uint8_t*)file + info.levelOffset[0], total);
     });
     return rc == 0 ? index : -1;
 }

@@ -18,17 +18,33 @@
 //               lerp(lerp(t00, t10, fx), lerp(t01, t11, fx), fy) with lerp(x, y, s) = x + s * (y - x);
 //   addressing: clamp: each column as a float through fmin(fmax(., 0), w - 1) (a NaN gives column 0);
 //               wrap : i = (int)fmin(fmax(x0, -2^30), 2^30), the column is i mod w floored, the next one that + 1, or 0 behind the last;
-//   texel     : one 4-byte load, R in the low byte.  RGBA8_UNORM: (float)byte / 255.0f.  SRGBA8_UNORM: R, G, B through the device's
-//               256-entry table (the sRGB transfer function evaluated in double precision on the host, rounded once to float),
-//               before filtering, as D3D does; alpha stays linear (and is never read: GBufferA stores no alpha).
+//   texel     : one 4-byte word, R in the low byte (the fetch: one load per texel of RGBA8_UNORM / SRGBA8_UNORM, the decode below for
+//               the block-compressed formats).  UNORM: (float)byte / 255.0f.  SRGBA8_UNORM and the _SRGB block formats: R, G, B
+//               through the device's 256-entry table (the sRGB transfer function evaluated in double precision on the host, rounded
+//               once to float), before filtering, as D3D does; alpha stays linear (and is never read: GBufferA stores no alpha).
 // Both tables (sRGB, and byte / 255.0f) are staged in LDS by the workgroup: a texel costs one global load and three LDS reads.
+//
+// BLOCK-COMPRESSED FORMATS (BC1, BC2, BC3, their _SRGB variants, BC4, BC5; restated in tests/bc_ref.c).  A BC texture
+// samples exactly as the RGBA8_UNORM (or SRGBA8_UNORM) texture of its decoded words would: nothing above changes.  Level k is
+// ceil(w_k / 4) x ceil(h_k / 4) blocks, row-major, from mipOffset[k]; texel (x, y) is texel i = 4 * (y & 3) + (x & 3) of block
+// (x >> 2, y >> 2).  A texel costs one aligned 8- or 16-byte load of its block (shared by the texels of the footprint that lie in
+// the same block) and the decode of that one texel; texels of an edge block beyond the level are never addressed.  The decode is
+// integer, every division truncates, all fields are little-endian:
+//   colour block (8 bytes): c0, c1 RGB565 at bytes 0-1 and 2-3, texel i's index at bits 2i of bytes 4-7; endpoints to 8 bits by bit
+//               replication (r5 << 3 | r5 >> 2, g6 << 2 | g6 >> 4); four-colour mode: p2 = (2 p0 + p1) / 3, p3 = (p0 + 2 p1) / 3,
+//               alpha 255; three-colour mode: p2 = (p0 + p1) / 2, p3 = (0, 0, 0, 0).  BC1: four-colour iff c0 > c1; BC2, BC3: always.
+//   alpha block (8 bytes; BC3's alpha, BC4, each half of BC5): a0, a1, texel i's index at bits 3i of the 48 bits that follow;
+//               a0 > a1: p[k] = ((8 - k) a0 + (k - 1) a1) / 7, k = 2..7; else p[k] = ((6 - k) a0 + (k - 1) a1) / 5, k = 2..5, p6 = 0, p7 = 255.
+//   BC2: bytes 0-7 sixteen 4-bit alphas (texel i at bits 4i, times 17), then the colour block.  BC3: alpha block, colour block.
+//   BC4: (R, 0, 0, 255).  BC5: the R block, the G block: (R, G, 0, 255).
+// The format branch sits inside the fetch (fetchQuad, fetchQuads): lanes of one wave hold entries of different formats.
 // Parity with D3D hardware's fixed-point, vendor-specific anisotropic filtering stays unpinned.
 //
 // ALPHA (sampleAlpha, alphaLevel0; restated in tests/alpha_test_ref.c): SampleMaterialValue(...).a for ALPHA_MASK_MODE's discard in
 // the rasters (k_raster.hip) and the alpha test of the sun rays (k_shadowmask.hip).  sampleAlpha is `sample` on bits 24-31 of the
 // texel: the same footprint, tap count, lod, tap positions, trilinear and bilinear arithmetic, addressing and summation order.  A
-// texel is (float)byte / 255.0f, one correctly rounded division, in both formats: alpha is linear in SRGBA8_UNORM too and never goes
-// through the sRGB table, so neither function needs the LDS tables.  alphaLevel0 is one bilinear fetch of mip 0.
+// texel is (float)byte / 255.0f, one correctly rounded division, in every format: alpha is linear in SRGBA8_UNORM and the _SRGB block
+// formats too and never goes through the sRGB table, so neither function needs the LDS tables.  The texels come from the same fetchQuad.  alphaLevel0 is one bilinear fetch of mip 0.
 #pragma once
 
 #include "../../include/trhip.h"
@@ -43,7 +59,7 @@ struct TableEntry
 {
     const uint32_t* base;
     uint32_t width, height, mips, format;
-    uint32_t mipOffset[16];                    // first texel of level k, in texels
+    uint32_t mipOffset[16];                    // first texel (or block) of level k, in 4-byte words from base
     uint32_t pad[2];
 };
 static_assert(sizeof(TableEntry) == 96, "the host fills 96-byte entries");
@@ -58,7 +74,15 @@ __device__ __forceinline__ void stageTables(float* lds, const float* srgb, uint3
     __syncthreads();
 }
 
-__device__ __forceinline__ bool sampled(const TableEntry& e) { return e.base && (e.format == TRHIP_FORMAT_RGBA8_UNORM || e.format == TRHIP_FORMAT_SRGBA8_UNORM); }
+__device__ __forceinline__ bool blockCompressed(uint32_t format) { return format >= TRHIP_FORMAT_BC1_UNORM && format <= TRHIP_FORMAT_BC5_UNORM; }
+__device__ __forceinline__ bool srgbDecoded(uint32_t format)
+{
+    return format == TRHIP_FORMAT_SRGBA8_UNORM || format == TRHIP_FORMAT_BC1_UNORM_SRGB || format == TRHIP_FORMAT_BC2_UNORM_SRGB || format == TRHIP_FORMAT_BC3_UNORM_SRGB;
+}
+__device__ __forceinline__ bool sampled(const TableEntry& e)
+{
+    return e.base && (e.format == TRHIP_FORMAT_RGBA8_UNORM || e.format == TRHIP_FORMAT_SRGBA8_UNORM || blockCompressed(e.format));
+}
 
 struct Axis { uint32_t i0, i1; float f; };
 
@@ -78,13 +102,116 @@ __device__ __forceinline__ Axis axisOf(float u, uint32_t dim, bool wrap)
 
 using sp::lerp_;
 
-// rgbTable: the LDS table the colour bytes go through (sRGB or UNORM)
-__device__ __forceinline__ cm::F3 bilinear(const TableEntry& e, const float* rgbTable, uint32_t level, bool wrap, float u, float v)
+// ---- the texel fetch (see BLOCK-COMPRESSED FORMATS above) --------------------------------------------------------------------
+// One block in four words.  An 8-byte block is held twice, so that a colour block is always w[2], w[3] and the first (or only)
+// alpha block always w[0], w[1].
+struct Block { uint32_t w[4]; };
+
+__device__ __forceinline__ Block loadBlock(const uint32_t* level, uint32_t index, bool wide)
+{
+    if (wide) {
+        const uint4 v = *(const uint4*)(level + 4u * index);
+        return { { v.x, v.y, v.z, v.w } };
+    }
+    const uint2 v = *(const uint2*)(level + 2u * index);
+    return { { v.x, v.y, v.x, v.y } };
+}
+
+// texel i of a colour block: R, G, B in bits 0-23, alpha 255 or (three-colour mode, index 3) 0 in bits 24-31
+__device__ __forceinline__ uint32_t colourTexel(uint32_t ends, uint32_t indices, uint32_t i, bool bc1)
+{
+    const uint32_t c0 = ends & 0xFFFFu, c1 = ends >> 16, k = (indices >> (2u * i)) & 3u;
+    const bool four = !bc1 || c0 > c1;
+    const uint32_t r0 = c0 >> 11, g0 = (c0 >> 5) & 63u, b0 = c0 & 31u, r1 = c1 >> 11, g1 = (c1 >> 5) & 63u, b1 = c1 & 31u;
+    auto mix = [&](uint32_t p0, uint32_t p1) {
+        return k == 0u ? p0 : k == 1u ? p1 : four ? (k == 2u ? (2u * p0 + p1) / 3u : (p0 + 2u * p1) / 3u) : (k == 2u ? (p0 + p1) / 2u : 0u);
+    };
+    const uint32_t r = mix(r0 << 3 | r0 >> 2, r1 << 3 | r1 >> 2), g = mix(g0 << 2 | g0 >> 4, g1 << 2 | g1 >> 4), b = mix(b0 << 3 | b0 >> 2, b1 << 3 | b1 >> 2);
+    return r | g << 8 | b << 16 | (!four && k == 3u ? 0u : 0xFF000000u);
+}
+
+// texel i of an alpha block (lo: bytes 0-3, hi: bytes 4-7)
+__device__ __forceinline__ uint32_t alphaTexel(uint32_t lo, uint32_t hi, uint32_t i)
+{
+    const uint32_t a0 = lo & 0xFFu, a1 = (lo >> 8) & 0xFFu;
+    const uint32_t k = (uint32_t)((((uint64_t)hi << 32 | lo) >> 16) >> (3u * i)) & 7u;
+    const uint32_t eight = ((8u - k) * a0 + (k - 1u) * a1) / 7u, six = k == 6u ? 0u : k == 7u ? 255u : ((6u - k) * a0 + (k - 1u) * a1) / 5u;
+    return k == 0u ? a0 : k == 1u ? a1 : a0 > a1 ? eight : six;
+}
+
+// the RGBA8 word of texel i of a block of `format`
+__device__ __forceinline__ uint32_t decodeTexel(uint32_t format, const Block& b, uint32_t i)
+{
+    if (format <= TRHIP_FORMAT_BC3_UNORM_SRGB) {
+        const uint32_t c = colourTexel(b.w[2], b.w[3], i, format <= TRHIP_FORMAT_BC1_UNORM_SRGB);
+        if (format <= TRHIP_FORMAT_BC1_UNORM_SRGB) return c;
+        const uint32_t a = format <= TRHIP_FORMAT_BC2_UNORM_SRGB ? ((uint32_t)(((uint64_t)b.w[1] << 32 | b.w[0]) >> (4u * i)) & 15u) * 17u : alphaTexel(b.w[0], b.w[1], i);
+        return (c & 0xFFFFFFu) | a << 24;
+    }
+    const uint32_t g = format == TRHIP_FORMAT_BC5_UNORM ? alphaTexel(b.w[2], b.w[3], i) : 0u;
+    return alphaTexel(b.w[0], b.w[1], i) | g << 8 | 0xFF000000u;
+}
+
+// The four RGBA8 words of a bilinear footprint, and where it lies: columns and rows of a level w texels wide.
+struct Quad { uint32_t w00, w10, w01, w11; };
+struct Footprint { uint32_t level, w; Axis x, y; };
+
+__device__ __forceinline__ Footprint footprintOf(const TableEntry& e, uint32_t level, bool wrap, float u, float v)
 {
     const uint32_t w = (e.width >> level) ? (e.width >> level) : 1u, h = (e.height >> level) ? (e.height >> level) : 1u;
-    const Axis x = axisOf(u, w, wrap), y = axisOf(v, h, wrap);
-    const uint32_t* p = e.base + e.mipOffset[level];
-    const uint32_t w00 = p[y.i0 * w + x.i0], w10 = p[y.i0 * w + x.i1], w01 = p[y.i1 * w + x.i0], w11 = p[y.i1 * w + x.i1];
+    return { level, w, axisOf(u, w, wrap), axisOf(v, h, wrap) };
+}
+
+__device__ __forceinline__ Quad plainQuad(const TableEntry& e, const Footprint& f)
+{
+    const uint32_t* p = e.base + e.mipOffset[f.level];
+    return { p[f.y.i0 * f.w + f.x.i0], p[f.y.i0 * f.w + f.x.i1], p[f.y.i1 * f.w + f.x.i0], p[f.y.i1 * f.w + f.x.i1] };
+}
+
+__device__ __forceinline__ Quad blockQuad(const TableEntry& e, const Footprint& f)
+{
+    const uint32_t* p = e.base + e.mipOffset[f.level];
+    const uint32_t format = e.format, w = f.w;
+    const Axis &x = f.x, &y = f.y;
+    const bool wide = format != TRHIP_FORMAT_BC1_UNORM && format != TRHIP_FORMAT_BC1_UNORM_SRGB && format != TRHIP_FORMAT_BC4_UNORM;
+    const uint32_t bw = (w + 3u) >> 2;
+    const uint32_t bx0 = x.i0 >> 2, bx1 = x.i1 >> 2, row0 = (y.i0 >> 2) * bw, row1 = (y.i1 >> 2) * bw;
+    const uint32_t tx0 = x.i0 & 3u, tx1 = x.i1 & 3u, ty0 = 4u * (y.i0 & 3u), ty1 = 4u * (y.i1 & 3u);
+    Quad q;
+    Block left = loadBlock(p, row0 + bx0, wide), right = left;
+    if (bx1 != bx0) right = loadBlock(p, row0 + bx1, wide);
+    q.w00 = decodeTexel(format, left, ty0 + tx0);
+    q.w10 = decodeTexel(format, right, ty0 + tx1);
+    if (row1 != row0) {
+        left = loadBlock(p, row1 + bx0, wide);
+        right = left;
+        if (bx1 != bx0) right = loadBlock(p, row1 + bx1, wide);
+    }
+    q.w01 = decodeTexel(format, left, ty1 + tx0);
+    q.w11 = decodeTexel(format, right, ty1 + tx1);
+    return q;
+}
+
+// THE TEXEL FETCH, for every sampled format, which bilinear and bilinearAlpha share: the words of one footprint, or of the two
+// footprints of a trilinear tap under one format branch, so that the eight loads of an RGBA8 tap are issued together as before.
+// `blocks`: blockCompressed(e.format), which a caller with a tap loop evaluates once.  The block path is laid out of line.
+__device__ __forceinline__ Quad fetchQuad(const TableEntry& e, bool blocks, const Footprint& f)
+{
+    if (__builtin_expect(blocks, 0)) return blockQuad(e, f);
+    return plainQuad(e, f);
+}
+
+__device__ __forceinline__ void fetchQuads(const TableEntry& e, bool blocks, const Footprint& f0, const Footprint& f1, Quad& q0, Quad& q1)
+{
+    if (__builtin_expect(blocks, 0)) { q0 = blockQuad(e, f0); q1 = blockQuad(e, f1); }
+    else { q0 = plainQuad(e, f0); q1 = plainQuad(e, f1); }
+}
+
+// rgbTable: the LDS table the colour bytes go through (sRGB or UNORM)
+__device__ __forceinline__ cm::F3 bilinear(const Quad& q, const Footprint& fp, const float* rgbTable)
+{
+    const Axis &x = fp.x, &y = fp.y;
+    const uint32_t w00 = q.w00, w10 = q.w10, w01 = q.w01, w11 = q.w11;
     cm::F3 o;
     o.x = lerp_(lerp_(rgbTable[w00 & 0xFFu], rgbTable[w10 & 0xFFu], x.f), lerp_(rgbTable[w01 & 0xFFu], rgbTable[w11 & 0xFFu], x.f), y.f);
     o.y = lerp_(lerp_(rgbTable[(w00 >> 8) & 0xFFu], rgbTable[(w10 >> 8) & 0xFFu], x.f), lerp_(rgbTable[(w01 >> 8) & 0xFFu], rgbTable[(w11 >> 8) & 0xFFu], x.f), y.f);
@@ -107,13 +234,17 @@ __device__ __forceinline__ cm::F3 sample(const TableEntry& e, const float* lds, 
     const float lod = cm::min_(cm::max_(x > 0.0f ? softmath::log2Soft(x) : 0.0f, 0.0f), top);
     const float l0f = __builtin_floorf(lod), f = lod - l0f;
     const uint32_t l0 = (uint32_t)l0f, l1 = l0 + 1u < e.mips ? l0 + 1u : e.mips - 1u;
-    const float* rgbTable = lds + (e.format == TRHIP_FORMAT_SRGBA8_UNORM ? 0u : 256u);
+    const float* rgbTable = lds + (srgbDecoded(e.format) ? 0u : 256u);
+    const bool blocks = blockCompressed(e.format);
     cm::F3 acc = { 0.0f, 0.0f, 0.0f };
 #pragma unroll 1
     for (uint32_t i = 0; i < N; ++i) {
         const float k = ((float)i + 0.5f) / fN - 0.5f;
         const float tu = u + mu * k, tv = v + mv * k;
-        const cm::F3 b0 = bilinear(e, rgbTable, l0, wrap, tu, tv), b1 = bilinear(e, rgbTable, l1, wrap, tu, tv);
+        const Footprint f0 = footprintOf(e, l0, wrap, tu, tv), f1 = footprintOf(e, l1, wrap, tu, tv);
+        Quad q0, q1;
+        fetchQuads(e, blocks, f0, f1, q0, q1);
+        const cm::F3 b0 = bilinear(q0, f0, rgbTable), b1 = bilinear(q1, f1, rgbTable);
         acc.x = acc.x + lerp_(b0.x, b1.x, f);
         acc.y = acc.y + lerp_(b0.y, b1.y, f);
         acc.z = acc.z + lerp_(b0.z, b1.z, f);
@@ -124,12 +255,10 @@ __device__ __forceinline__ cm::F3 sample(const TableEntry& e, const float* lds, 
 // ---- the alpha channel (see ALPHA above) --------------------------------------------------------------------------------------
 __device__ __forceinline__ float alphaOf(uint32_t texel) { return cm::div_((float)(texel >> 24), 255.0f); }
 
-__device__ __forceinline__ float bilinearAlpha(const TableEntry& e, uint32_t level, bool wrap, float u, float v)
+__device__ __forceinline__ float bilinearAlpha(const Quad& q, const Footprint& fp)
 {
-    const uint32_t w = (e.width >> level) ? (e.width >> level) : 1u, h = (e.height >> level) ? (e.height >> level) : 1u;
-    const Axis x = axisOf(u, w, wrap), y = axisOf(v, h, wrap);
-    const uint32_t* p = e.base + e.mipOffset[level];
-    const uint32_t w00 = p[y.i0 * w + x.i0], w10 = p[y.i0 * w + x.i1], w01 = p[y.i1 * w + x.i0], w11 = p[y.i1 * w + x.i1];
+    const Axis &x = fp.x, &y = fp.y;
+    const uint32_t w00 = q.w00, w10 = q.w10, w01 = q.w01, w11 = q.w11;
     return lerp_(lerp_(alphaOf(w00), alphaOf(w10), x.f), lerp_(alphaOf(w01), alphaOf(w11), x.f), y.f);
 }
 
@@ -148,17 +277,25 @@ __device__ __forceinline__ float sampleAlpha(const TableEntry& e, bool wrap, flo
     const float lod = cm::min_(cm::max_(x > 0.0f ? softmath::log2Soft(x) : 0.0f, 0.0f), top);
     const float l0f = __builtin_floorf(lod), f = lod - l0f;
     const uint32_t l0 = (uint32_t)l0f, l1 = l0 + 1u < e.mips ? l0 + 1u : e.mips - 1u;
+    const bool blocks = blockCompressed(e.format);
     float acc = 0.0f;
 #pragma unroll 1
     for (uint32_t i = 0; i < N; ++i) {
         const float k = ((float)i + 0.5f) / fN - 0.5f;
         const float tu = u + mu * k, tv = v + mv * k;
-        acc = acc + lerp_(bilinearAlpha(e, l0, wrap, tu, tv), bilinearAlpha(e, l1, wrap, tu, tv), f);
+        const Footprint f0 = footprintOf(e, l0, wrap, tu, tv), f1 = footprintOf(e, l1, wrap, tu, tv);
+        Quad q0, q1;
+        fetchQuads(e, blocks, f0, f1, q0, q1);
+        acc = acc + lerp_(bilinearAlpha(q0, f0), bilinearAlpha(q1, f1), f);
     }
     return acc / fN;
 }
 
 // One bilinear fetch of mip 0: what a ray reads, which has no pixel quad to differentiate over (k_shadowmask.hip).
-__device__ __forceinline__ float alphaLevel0(const TableEntry& e, bool wrap, float u, float v) { return bilinearAlpha(e, 0u, wrap, u, v); }
+__device__ __forceinline__ float alphaLevel0(const TableEntry& e, bool wrap, float u, float v)
+{
+    const Footprint f = footprintOf(e, 0u, wrap, u, v);
+    return bilinearAlpha(fetchQuad(e, blockCompressed(e.format), f), f);
+}
 
 } // namespace mtex

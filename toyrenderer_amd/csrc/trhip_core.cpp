@@ -487,15 +487,28 @@ void trhip_buffer_release(trhip_buffer b)
 void* trhip_buffer_device_ptr(trhip_buffer b) { return b ? b->ptr : nullptr; }
 uint64_t trhip_buffer_size(trhip_buffer b) { return b ? b->byteSize : 0; }
 
+uint32_t trhip_format_block_bytes(uint32_t format)
+{
+    switch (format) {
+    case TRHIP_FORMAT_BC1_UNORM: case TRHIP_FORMAT_BC1_UNORM_SRGB: case TRHIP_FORMAT_BC4_UNORM: return 8;
+    case TRHIP_FORMAT_BC2_UNORM: case TRHIP_FORMAT_BC2_UNORM_SRGB: case TRHIP_FORMAT_BC3_UNORM: case TRHIP_FORMAT_BC3_UNORM_SRGB: case TRHIP_FORMAT_BC5_UNORM: return 16;
+    default: return 0;
+    }
+}
+
 // arraySize 0: a plain texture (trhip_texture_create); >= 1: a 2D array of that many slices (trhip_texture_create_array)
 static int createTexture(trhip_device dev, const trhip_texture_desc* d, uint32_t arraySize, trhip_texture* out)
 {
     if (d->width == 0 || d->height == 0 || d->mipLevels == 0 || d->mipLevels > 16)
         return fail(TRHIP_ERR_INVALID, "texture_create: bad dimensions %ux%u mips %u", d->width, d->height, d->mipLevels);
-    if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && (d->format < TRHIP_FORMAT_RGBA8_UNORM || d->format > TRHIP_FORMAT_RGBA16_FLOAT))
+    if ((d->format < TRHIP_FORMAT_R16_FLOAT || d->format > TRHIP_FORMAT_R8_UINT) && (d->format < TRHIP_FORMAT_RGBA8_UNORM || d->format > TRHIP_FORMAT_BC5_UNORM))
         return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u", d->format);
+    const uint32_t blockBytes = trhip_format_block_bytes(d->format);
+    if (blockBytes && arraySize) return fail(TRHIP_ERR_INVALID, "texture_create_array: format %u is block-compressed; a block-compressed texture cannot be an array", d->format);
+    if (blockBytes && d->isUAV)
+        return fail(TRHIP_ERR_INVALID, "texture_create: unsupported format %u for a texture that a pass writes: a block-compressed texture is sampled only and takes no UAV or render-target bit", d->format);
     const bool bloomChain = d->format == TRHIP_FORMAT_R11G11B10_FLOAT && (d->isUAV & TRHIP_TEXTURE_RENDER_TARGET);   // the bloom texture (BloomRenderer.cpp:41-50)
-    const bool sampledChain = (d->format == TRHIP_FORMAT_RGBA8_UNORM || d->format == TRHIP_FORMAT_SRGBA8_UNORM) && d->isUAV == 0;   // a material texture
+    const bool sampledChain = (d->format == TRHIP_FORMAT_RGBA8_UNORM || d->format == TRHIP_FORMAT_SRGBA8_UNORM || blockBytes) && d->isUAV == 0;   // a material texture
     if (d->format != TRHIP_FORMAT_R16_FLOAT && d->format != TRHIP_FORMAT_R32_FLOAT && !bloomChain && !sampledChain && d->mipLevels != 1)
         return fail(TRHIP_ERR_INVALID, "texture_create: RG32_UINT / RG16_FLOAT / RGBA32_UINT / R11G11B10_FLOAT / R8_UNORM / R8_UINT / R10G10B10A2_UNORM / RGBA16_FLOAT textures and RGBA8_UNORM / SRGBA8_UNORM textures that a pass writes have one mip, got %u", d->mipLevels);
     if (arraySize) {
@@ -507,14 +520,15 @@ static int createTexture(trhip_device dev, const trhip_texture_desc* d, uint32_t
     auto t = std::make_unique<trhip_texture_t>();
     t->dev = dev;
     t->width = d->width; t->height = d->height; t->mips = d->mipLevels; t->format = d->format;
-    t->texelBytes = d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT || d->format == TRHIP_FORMAT_RGBA16_FLOAT ? 8 :
+    t->texelBytes = blockBytes ? 0 : d->format == TRHIP_FORMAT_R16_FLOAT ? 2 : d->format == TRHIP_FORMAT_RG32_UINT || d->format == TRHIP_FORMAT_RGBA16_FLOAT ? 8 :
                     d->format == TRHIP_FORMAT_RGBA32_UINT ? 16 : d->format == TRHIP_FORMAT_R8_UNORM || d->format == TRHIP_FORMAT_R8_UINT ? 1 : 4;
+    t->blockBytes = blockBytes;
     t->isUAV = d->isUAV != 0; t->isVirtual = d->isVirtual != 0;
     t->name = d->debugName ? d->debugName : "";
     uint64_t off = 0;
     for (uint32_t k = 0; k < t->mips; ++k) {
         t->mipOffset[k] = off;
-        off += ((uint64_t)t->mipW(k) * t->mipH(k) * t->texelBytes + 255) & ~uint64_t(255);
+        off += (t->mipBytes(k) + 255) & ~uint64_t(255);
     }
     if (arraySize) {                               // one mip: `off` is the 256-byte aligned size of a slice
         t->arraySize = arraySize;
@@ -639,7 +653,7 @@ int trhip_texture_upload(trhip_texture t, uint32_t mip, const void* src, uint64_
     if (!t || !src || mip >= t->mips) return fail(TRHIP_ERR_INVALID, "texture_upload: bad argument");
     if (!t->ptr) return fail(TRHIP_ERR_STATE, "texture_upload(%s): no memory bound", t->name.c_str());
     if (t->arraySize) return fail(TRHIP_ERR_INVALID, "texture_upload(%s): an array texture is uploaded per slice (trhip_texture_upload_slice)", t->name.c_str());
-    uint64_t need = (uint64_t)t->mipW(mip) * t->mipH(mip) * t->texelBytes;
+    uint64_t need = t->mipBytes(mip);
     if (bytes != need) return fail(TRHIP_ERR_INVALID, "texture_upload(%s): mip %u is %llu bytes, got %llu", t->name.c_str(), mip, (unsigned long long)need, (unsigned long long)bytes);
     int rc = syncCopy(t->dev, t->mipPtr(mip), src, bytes, hipMemcpyHostToDevice);
     t->version.fetch_add(1);                   // everything submitted has completed: later submissions see the new contents
@@ -651,7 +665,7 @@ int trhip_texture_download(trhip_texture t, uint32_t mip, void* dst, uint64_t by
     if (!t || !dst || mip >= t->mips) return fail(TRHIP_ERR_INVALID, "texture_download: bad argument");
     if (!t->ptr) return fail(TRHIP_ERR_STATE, "texture_download(%s): no memory bound", t->name.c_str());
     if (t->arraySize) return fail(TRHIP_ERR_INVALID, "texture_download(%s): an array texture is downloaded per slice (trhip_texture_download_slice)", t->name.c_str());
-    uint64_t need = (uint64_t)t->mipW(mip) * t->mipH(mip) * t->texelBytes;
+    uint64_t need = t->mipBytes(mip);
     if (bytes != need) return fail(TRHIP_ERR_INVALID, "texture_download(%s): mip %u is %llu bytes, got %llu", t->name.c_str(), mip, (unsigned long long)need, (unsigned long long)bytes);
     return syncCopy(t->dev, dst, t->mipPtr(mip), bytes, hipMemcpyDeviceToHost);
 }
@@ -859,6 +873,7 @@ int trhip_cmd_clear_texture_f32(trhip_cmdlist cl, trhip_texture tex, float value
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
+    if (tex->blockBytes) return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): a block-compressed texture has no clear: its blocks are uploaded", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_R10G10B10A2_UNORM || tex->format == TRHIP_FORMAT_RGBA16_FLOAT)
         return fail(TRHIP_ERR_INVALID, "clear_texture_f32(%s): an R10G10B10A2_UNORM / RGBA16_FLOAT texture has no clear: the DDGI probe textures are uploaded", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RG32_UINT || tex->format == TRHIP_FORMAT_RGBA32_UINT || tex->format == TRHIP_FORMAT_R8_UINT)
@@ -898,6 +913,7 @@ int trhip_cmd_clear_texture_u32(trhip_cmdlist cl, trhip_texture tex, uint32_t va
     TRHIP_RECORDING(cl);
     if (!tex) return fail(TRHIP_ERR_INVALID, "clear_texture: null texture");
     if (!tex->ptr) return fail(TRHIP_ERR_STATE, "clear_texture(%s): no memory bound", tex->name.c_str());
+    if (tex->blockBytes) return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): a block-compressed texture has no clear: its blocks are uploaded", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_RGBA8_UNORM || tex->format == TRHIP_FORMAT_SRGBA8_UNORM)
         return fail(TRHIP_ERR_INVALID, "clear_texture_u32(%s): an RGBA8_UNORM / SRGBA8_UNORM texture has no clear: postprocess_PS_PostProcess writes every texel", tex->name.c_str());
     if (tex->format == TRHIP_FORMAT_R10G10B10A2_UNORM || tex->format == TRHIP_FORMAT_RGBA16_FLOAT)
@@ -947,6 +963,9 @@ int trhip_cmd_copy_texture(trhip_cmdlist cl, trhip_texture dst, trhip_texture sr
     TRHIP_RECORDING(cl);
     if (!dst || !src) return fail(TRHIP_ERR_INVALID, "copy_texture: null texture");
     if (!dst->ptr || !src->ptr) return fail(TRHIP_ERR_STATE, "copy_texture: a texture has no memory bound");
+    if ((dst->blockBytes || src->blockBytes) && dst->format != src->format)
+        return fail(TRHIP_ERR_INVALID, "copy_texture(%s <- %s): a block-compressed texture is copied to one of its own format only (formats %u <- %u)", dst->name.c_str(), src->name.c_str(),
+                    dst->format, src->format);
     if (dst->width != src->width || dst->height != src->height || dst->mips != src->mips || dst->format != src->format || dst->arraySize != src->arraySize)
         return fail(TRHIP_ERR_INVALID, "copy_texture(%s <- %s): descriptions differ", dst->name.c_str(), src->name.c_str());
     void* d = dst->ptr;
@@ -1028,6 +1047,9 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
             if (!t) return fail(TRHIP_ERR_INVALID, "dispatch(%s): binding %u has no texture", name, i);
             if (!t->ptr) return fail(TRHIP_ERR_STATE, "dispatch(%s): texture '%s' has no memory bound", name, t->name.c_str());
             if (b[i].type == TRHIP_BIND_TEXTURE_UAV && b[i].baseMip >= t->mips) return fail(TRHIP_ERR_INVALID, "dispatch(%s): UAV mip %u out of range", name, b[i].baseMip);
+            if (t->blockBytes)
+                return fail(TRHIP_ERR_INVALID, "dispatch(%s): the block-compressed texture '%s' at %c%u: a block-compressed texture reaches a kernel through the texture table only", name,
+                            t->name.c_str(), b[i].type == TRHIP_BIND_TEXTURE_UAV ? 'u' : 't', b[i].slot);
             if (t->arraySize)
                 if (const int rc = checkArrayBinding(name, b[i], t)) return rc;
             cl->hold(t, b[i].type == TRHIP_BIND_TEXTURE_UAV);

@@ -170,6 +170,7 @@ struct trhip_texture_t
     trhip_device_t* dev = nullptr;
     uint32_t width = 0, height = 0, mips = 0, format = 0;
     uint32_t texelBytes = 0;
+    uint32_t blockBytes = 0;                   // trhip_format_block_bytes(format): nonzero for a block-compressed texture, whose texelBytes is 0
     bool isUAV = false, isVirtual = false;
     // A 2D ARRAY texture (trhip_texture_create_array): arraySize slices of one mip, slice k at byte k * slicePitch (256-byte
     // aligned).  0: not an array.  Only "deferredlighting_PS_Main" / "_Debug" take one, at t6..t8 (recordDispatch refuses the rest).
@@ -194,6 +195,11 @@ struct trhip_texture_t
     uint32_t mipW(uint32_t k) const { return (width >> k) ? (width >> k) : 1u; }
     uint32_t mipH(uint32_t k) const { return (height >> k) ? (height >> k) : 1u; }
     void* mipPtr(uint32_t k) const { return (char*)ptr + mipOffset[k]; }
+    // bytes of level k without its padding: texels, or 4 x 4 blocks of a block-compressed format
+    uint64_t mipBytes(uint32_t k) const
+    {
+        return blockBytes ? (uint64_t)((mipW(k) + 3u) / 4u) * ((mipH(k) + 3u) / 4u) * blockBytes : (uint64_t)mipW(k) * mipH(k) * texelBytes;
+    }
 };
 
 // The texture table (include/trhip.h): the stand-in of ResourceDescriptorHeap[...].  slots[i] is the retained texture behind

@@ -69,7 +69,8 @@ class GpuScene:
     def set_textures(self, textures):
         """The material textures and their table (the stand-in of ResourceDescriptorHeap[...], include/trhip.h): `textures` is a
         list of (mips, format), mips a list of uint8 [h_k, w_k, 4] arrays (level k of max(w >> k, 1) x max(h >> k, 1); interop.make_mips
-        makes them from an image), format rhi.FORMAT_RGBA8_UNORM or rhi.FORMAT_SRGBA8_UNORM.  Returns their descriptor indices, which
+        makes them from an image), format rhi.FORMAT_RGBA8_UNORM or rhi.FORMAT_SRGBA8_UNORM; or mips an interop.BlockMips (the levels' raw
+        block bytes, as interop.parse_dds gives them) with one of rhi.BC_FORMATS.  Returns their descriptor indices, which
         m_DescriptorIndex of a flagged TextureData names.  Replaces an earlier set; call it before set_materials()."""
         self.release_textures()
         if len(textures) == 0:

@@ -391,11 +391,15 @@ def material_table(gltf_materials: list, gltf: dict | None = None, images=None, 
     emissiveTexture set their flag, m_GlobalIndex (the glTF texture index), m_IsWrapSampler (the texture's sampler: REPEAT 1,
     CLAMP_TO_EDGE 0, none 1 as Visual.h:124; mirrored or mixed modes raise as the reference asserts) and m_DescriptorIndex: the
     position in `textures`, to which each (glTF texture, format) pair is appended once as (mips, format) -- base colour and
-    emissive SRGBA8_UNORM, the others RGBA8_UNORM; an image given without mips gets interop.make_mips'.  The
+    emissive SRGBA8_UNORM, the others RGBA8_UNORM; an image given without mips gets interop.make_mips'.  An image given as the
+    `bytes` of a .dds file (interop.parse_dds) keeps the file's mips and block format, as (interop.BlockMips, format) for BC1 to BC5,
+    with the _SRGB variant for base colour and emissive and the UNORM one for the others, whatever the file states (the reference
+    instead forces every BC1 file to sRGB); BC4 and BC5 have one form.  Nothing is encoded or decoded here.  The
     specular-glossiness textures stay refused."""
     n = len(gltf_materials)
     out = np.zeros(n + 1, I.MaterialData)
     loaded = {}                                            # (glTF texture, format) -> descriptor index
+    parsed = {}                                            # glTF image given as a .dds file -> interop.parse_dds of it
 
     def bind(row, slot, flag, view, key, srgb, i, name):
         tex = (gltf or {}).get("textures", [])
@@ -411,10 +415,18 @@ def material_table(gltf_materials: list, gltf: dict | None = None, images=None, 
             if ws != wt or ws not in (_GLTF_REPEAT, _GLTF_CLAMP_TO_EDGE):
                 raise ValueError(f"glTF-lite: material {i} [{name}]: {key}: sampler {t['sampler']} wraps {ws} / {wt}: REPEAT or CLAMP_TO_EDGE on both axes only")
             wrap = int(ws == _GLTF_REPEAT)
-        fmt = _FORMAT_SRGBA8_UNORM if srgb else _FORMAT_RGBA8_UNORM
+        img = images[t["source"]]
+        dds = None
+        if isinstance(img, (bytes, bytearray, memoryview)):                       # a .dds file: its own mips and format, sRGB by slot
+            dds = parsed.get(t["source"]) or parsed.setdefault(t["source"], I.parse_dds(img))
+            fmt = I.srgb_variant(dds[1], srgb)
+        else:
+            fmt = _FORMAT_SRGBA8_UNORM if srgb else _FORMAT_RGBA8_UNORM
         if (view["index"], fmt) not in loaded:
-            img = images[t["source"]]
-            mips = [np.ascontiguousarray(m, np.uint8) for m in img] if isinstance(img, (list, tuple)) else I.make_mips(img, srgb)
+            if dds is not None:
+                mips = dds[0]
+            else:
+                mips = [np.ascontiguousarray(m, np.uint8) for m in img] if isinstance(img, (list, tuple)) else I.make_mips(img, srgb)
             loaded[(view["index"], fmt)] = len(textures)
             textures.append((mips, fmt))
         row["m_MaterialFlags"] |= flag
@@ -479,7 +491,8 @@ def apply_materials(scene: "LoadedScene") -> np.ndarray:
 # ----------------------------------------------------------------------------------------------- loader
 def load(path_or_gltf, blobs=None, lods: bool = True, images=None) -> LoadedScene:
     """lods=False: LOD 0 only (no simplification).  images: one decoded image per glTF image (uint8 [h, w, 4], or its list of
-    mips); decoding PNG or JPEG is the caller's business.  With it the textured materials load (material_table) and
+    mips), or the `bytes` of a .dds file (the reference's own asset format: BC1 to BC5 or RGBA8, kept compressed; there is no
+    encoder); decoding PNG or JPEG is the caller's business.  With it the textured materials load (material_table) and
     LoadedScene.textures lists what to upload; without it a material that names a texture raises."""
     if isinstance(path_or_gltf, dict):
         g = path_or_gltf

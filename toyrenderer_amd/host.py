@@ -25,7 +25,7 @@ HOST_SYMBOLS = [
     "trhost_rccl_allgather", "trhost_exchange_create", "trhost_exchange_run", "trhost_exchange_wait", "trhost_exchange_outputs",
     "trhost_exchange_destroy", "trhost_load_geometry", "trhost_set_raster_depth", "trhost_download_depth",
     "trhost_set_visibility_buffer", "trhost_download_visibility", "trhost_download_motion",
-    "trhost_load_materials", "trhost_create_material_texture", "trhost_set_gbuffer", "trhost_set_alpha_test", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
+    "trhost_load_materials", "trhost_create_material_texture", "trhost_create_material_texture_dds", "trhost_set_gbuffer", "trhost_set_alpha_test", "trhost_set_debug_view_mode", "trhost_download_gbuffer_a",
     "trhost_load_scene_cached", "trhost_scene_list_sizes", "trhost_rccl_allreduce_max_u32", "trhost_load_gi_probes", "trhost_gi_probe_buffers",
     "trhost_set_renderer_queue", "trhost_render_graph_frame_stats",
     "trhost_set_deferred_lighting", "trhost_set_directional_light", "trhost_upload_shadow_mask", "trhost_download_lighting_output",
@@ -101,6 +101,7 @@ def load() -> C.CDLL:
     L.trhost_download_motion.argtypes = [vp, u64]
     L.trhost_load_materials.argtypes = [vp, u32]
     L.trhost_create_material_texture.argtypes = [u32, u32, u32, u32, vp, u64]
+    L.trhost_create_material_texture_dds.argtypes = [vp, u64, C.c_int]
     L.trhost_set_gbuffer.argtypes = [C.c_int]
     L.trhost_set_alpha_test.argtypes = [C.c_int]
     L.trhost_set_debug_view_mode.argtypes = [u32]
@@ -326,12 +327,29 @@ class Renderer:
 
     def create_material_texture(self, mips, fmt: int) -> int:
         """One material texture from its mips (uint8 [h_k, w_k, 4] arrays), fmt rhi.FORMAT_RGBA8_UNORM or FORMAT_SRGBA8_UNORM; returns
-        the descriptor index a flagged TextureData.m_DescriptorIndex names (include/trhost.h)."""
+        the descriptor index a flagged TextureData.m_DescriptorIndex names (include/trhost.h).  For one of rhi.BC_FORMATS mips is an
+        interop.BlockMips: the levels' raw block bytes, uploaded as they are (there is no encoder)."""
+        if hasattr(mips, "width"):
+            data = np.concatenate([np.frombuffer(bytes(m), np.uint8) if isinstance(m, (bytes, bytearray, memoryview)) else np.ascontiguousarray(m).reshape(-1).view(np.uint8)
+                                   for m in mips])
+            index = load().trhost_create_material_texture(mips.width, mips.height, len(mips), int(fmt), data.ctypes.data, data.nbytes)
+            if index < 0:
+                _check(-1)
+            return index
         mips = [np.ascontiguousarray(m, np.uint8) for m in mips]
         if not mips or any(m.ndim != 3 or m.shape[2] != 4 for m in mips):
             raise ValueError("mips: a non-empty list of uint8 [h, w, 4] arrays")
         data = np.concatenate([m.reshape(-1) for m in mips])
         index = load().trhost_create_material_texture(mips[0].shape[1], mips[0].shape[0], len(mips), int(fmt), data.ctypes.data, data.nbytes)
+        if index < 0:
+            _check(-1)
+        return index
+
+    def create_material_texture_dds(self, data, srgb: bool) -> int:
+        """One material texture from the bytes of a .dds file (trhost_create_material_texture_dds): srgb is the material slot's choice
+        between a format and its _SRGB twin.  Returns the descriptor index."""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        index = load().trhost_create_material_texture_dds(buf.ctypes.data if len(buf) else None, len(buf), int(bool(srgb)))
         if index < 0:
             _check(-1)
         return index

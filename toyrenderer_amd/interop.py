@@ -293,3 +293,125 @@ def make_mips(image, srgb: bool, levels: int | None = None):
             enc[..., :3] = linear_to_srgb(enc[..., :3])
         out.append(np.rint(np.clip(enc, 0.0, 1.0) * 255.0).astype(np.uint8))
     return out
+
+
+# ----------------------------------------------------------------------------------------------- block-compressed textures
+_FORMAT_RGBA8_UNORM, _FORMAT_SRGBA8_UNORM = 10, 11            # rhi.FORMAT_*
+_BC1, _BC1_SRGB, _BC2, _BC2_SRGB, _BC3, _BC3_SRGB, _BC4, _BC5 = range(14, 22)
+_BC_BLOCK_BYTES = {_BC1: 8, _BC1_SRGB: 8, _BC2: 16, _BC2_SRGB: 16, _BC3: 16, _BC3_SRGB: 16, _BC4: 8, _BC5: 16}
+
+
+class BlockMips(list):
+    """The mip chain of a block-compressed texture: a list of the levels' raw block bytes (bytes or uint8 arrays; level k holds
+    ceil(w_k / 4) x ceil(h_k / 4) blocks, row-major, w_k = max(width >> k, 1)) that also carries the size of level 0 in texels,
+    which the bytes alone do not tell.  What rhi.Device.create_sampled_texture, GpuScene.set_textures and
+    host.Renderer.load_textures take as `mips` for one of rhi.BC_FORMATS.  There is no encoder: the blocks come from parse_dds
+    or from another tool."""
+    def __init__(self, levels, width: int, height: int):
+        super().__init__(levels)
+        self.width, self.height = int(width), int(height)
+        if self.width < 1 or self.height < 1 or len(self) == 0:
+            raise ValueError("BlockMips: at least one level, width and height >= 1")
+
+
+def bc_level_bytes(w: int, h: int, fmt: int, level: int = 0) -> int:
+    """Bytes of level `level` of a w x h texture of a block-compressed format."""
+    mw, mh = max(w >> level, 1), max(h >> level, 1)
+    return ((mw + 3) // 4) * ((mh + 3) // 4) * _BC_BLOCK_BYTES[fmt]
+
+
+def _bc_colour(blk, bc1: bool):
+    """uint8 [n, 8] colour blocks -> uint8 [n, 16, 4]."""
+    b = blk.astype(np.uint32)
+    c0, c1 = b[:, 0] | b[:, 1] << 8, b[:, 2] | b[:, 3] << 8
+    idx = b[:, 4] | b[:, 5] << 8 | b[:, 6] << 16 | b[:, 7] << 24
+    k = (idx[:, None] >> (2 * np.arange(16, dtype=np.uint32))[None, :]) & 3
+
+    def ends(c):
+        r, g, bl = c >> 11, (c >> 5) & 63, c & 31
+        return np.stack([r << 3 | r >> 2, g << 2 | g >> 4, bl << 3 | bl >> 2], 1)
+    p0, p1 = ends(c0), ends(c1)
+    four = ((c0 > c1) | (not bc1))[:, None]
+    pal = np.zeros((len(b), 4, 4), np.uint32)
+    pal[:, 0, :3], pal[:, 1, :3] = p0, p1
+    pal[:, 2, :3] = np.where(four, (2 * p0 + p1) // 3, (p0 + p1) // 2)
+    pal[:, 3, :3] = np.where(four, (p0 + 2 * p1) // 3, 0)
+    pal[:, :3, 3] = 255
+    pal[:, 3, 3] = np.where(four[:, 0], 255, 0)
+    return np.take_along_axis(pal, np.broadcast_to(k[:, :, None], (len(b), 16, 4)), 1).astype(np.uint8)
+
+
+def _bc_alpha(blk):
+    """uint8 [n, 8] alpha blocks -> uint8 [n, 16]."""
+    b = blk.astype(np.uint64)
+    a0, a1 = b[:, 0].astype(np.uint32), b[:, 1].astype(np.uint32)
+    bits = sum(b[:, 2 + j] << np.uint64(8 * j) for j in range(6))
+    k = ((bits[:, None] >> (3 * np.arange(16, dtype=np.uint64))[None, :]) & np.uint64(7)).astype(np.intp)
+    pal = np.zeros((len(b), 8), np.uint32)
+    pal[:, 0], pal[:, 1] = a0, a1
+    eight = a0 > a1
+    for j in range(2, 8):
+        short = ((6 - j) * a0 + (j - 1) * a1) // 5 if j < 6 else np.full(len(b), 0 if j == 6 else 255, np.uint32)
+        pal[:, j] = np.where(eight, ((8 - j) * a0 + (j - 1) * a1) // 7, short)
+    return np.take_along_axis(pal, k, 1).astype(np.uint8)
+
+
+def bc_decode(blocks, w: int, h: int, fmt: int) -> np.ndarray:
+    """uint8 [h, w, 4] (R, G, B, A) of one level of a block-compressed texture: `blocks` are its ceil(w / 4) x ceil(h / 4) blocks,
+    row-major (bytes or a uint8 array), fmt one of rhi.BC_FORMATS (a _SRGB variant decodes to the same bytes as its UNORM twin).
+    A vectorised statement of the decode csrc/material_textures.hip.h performs per texel (integer, truncating divisions; BC4 gives
+    (R, 0, 0, 255), BC5 (R, G, 0, 255)), for viewing and for tools/material_texture_cost.py: the product samples the blocks on the
+    GPU and has no CPU fallback.  There is no encoder."""
+    if fmt not in _BC_BLOCK_BYTES:
+        raise ValueError(f"bc_decode: format {fmt} is not block-compressed")
+    nb = _BC_BLOCK_BYTES[fmt]
+    bw, bh = (w + 3) // 4, (h + 3) // 4
+    raw = np.frombuffer(blocks, np.uint8) if isinstance(blocks, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blocks, np.uint8).reshape(-1)
+    if w < 1 or h < 1 or raw.size != bw * bh * nb:
+        raise ValueError(f"bc_decode: {w} x {h} texels of format {fmt} are {bw * bh * nb} bytes, got {raw.size}")
+    blk = raw.reshape(bw * bh, nb)
+    out = np.zeros((bw * bh, 16, 4), np.uint8)
+    out[..., 3] = 255
+    if fmt in (_BC1, _BC1_SRGB):
+        out = _bc_colour(blk, True)
+    elif fmt in (_BC2, _BC2_SRGB, _BC3, _BC3_SRGB):
+        out = _bc_colour(blk[:, 8:], False)
+        if fmt in (_BC2, _BC2_SRGB):
+            nib = np.stack([blk[:, :8] & 15, blk[:, :8] >> 4], 2).reshape(-1, 16)
+            out[..., 3] = nib * 17
+        else:
+            out[..., 3] = _bc_alpha(blk[:, :8])
+    else:
+        out[..., 0] = _bc_alpha(blk[:, :8])
+        if fmt == _BC5:
+            out[..., 1] = _bc_alpha(blk[:, 8:])
+    img = out.reshape(bh, bw, 4, 4, 4).transpose(0, 2, 1, 3, 4).reshape(bh * 4, bw * 4, 4)
+    return np.ascontiguousarray(img[:h, :w])
+
+
+def bc_decode_mips(mips: BlockMips, fmt: int):
+    """The decoded twin of a BlockMips: its levels as uint8 [h_k, w_k, 4] arrays (bc_decode per level)."""
+    return [bc_decode(m, max(mips.width >> k, 1), max(mips.height >> k, 1), fmt) for k, m in enumerate(mips)]
+
+
+def parse_dds(data):
+    """(mips, format, width, height) of the bytes of a .dds file, through trhip_dds_parse (include/trhip.h: what is accepted and
+    refused; raises rhi.TrhipError with the parser's message).  format is the rhi.FORMAT_* the file states; the sRGB choice by
+    material slot is the loader's (gltf_lite.load, trhost_create_material_texture_dds).  mips: a BlockMips of the levels' block
+    bytes for a block-compressed format, uint8 [h_k, w_k, 4] arrays for RGBA8.  Nothing is decoded or encoded here."""
+    from . import rhi
+    data = bytes(data)
+    info = rhi.dds_parse(data)
+    levels = [data[int(info.levelOffset[k]):int(info.levelOffset[k]) + int(info.levelBytes[k])] for k in range(info.mipLevels)]
+    w, h, fmt = int(info.width), int(info.height), int(info.format)
+    if fmt in _BC_BLOCK_BYTES:
+        return BlockMips(levels, w, h), fmt, w, h
+    mips = [np.frombuffer(m, np.uint8).reshape(max(h >> k, 1), max(w >> k, 1), 4).copy() for k, m in enumerate(levels)]
+    return mips, fmt, w, h
+
+
+def srgb_variant(fmt: int, srgb: bool) -> int:
+    """The format of the pair (RGBA8, BC1, BC2, BC3: UNORM / _SRGB) that a material slot wants; BC4 and BC5 have one form."""
+    if fmt in (_FORMAT_RGBA8_UNORM, _FORMAT_SRGBA8_UNORM) or _BC1 <= fmt <= _BC3_SRGB:
+        return ((fmt - _FORMAT_RGBA8_UNORM) & ~1) + _FORMAT_RGBA8_UNORM + int(bool(srgb))
+    return fmt

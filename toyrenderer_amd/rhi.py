@@ -25,6 +25,17 @@ FORMAT_RGBA8_UNORM = 10   # back buffer: one u32 per texel, R in the low byte (9
 FORMAT_SRGBA8_UNORM = 11  # RGBA8_UNORM's layout; R, G, B decoded through the sRGB transfer function when sampled
 FORMAT_R10G10B10A2_UNORM = 12  # DDGI probe irradiance: one u32 per texel, R bits 0-9, G 10-19, B 20-29, A 30-31
 FORMAT_RGBA16_FLOAT = 13  # DDGI probe data: four fp16 per texel
+# Block-compressed material textures (include/trhip.h): 4 x 4 texel blocks of 8 (BC1, BC4) or 16 bytes, sampled through the texture
+# table only, decoded one texel per fetch.  There is no encoder: the blocks come from files (interop.parse_dds) or other tools.
+FORMAT_BC1_UNORM = 14
+FORMAT_BC1_UNORM_SRGB = 15
+FORMAT_BC2_UNORM = 16
+FORMAT_BC2_UNORM_SRGB = 17
+FORMAT_BC3_UNORM = 18
+FORMAT_BC3_UNORM_SRGB = 19
+FORMAT_BC4_UNORM = 20     # decodes to (R, 0, 0, 255)
+FORMAT_BC5_UNORM = 21     # decodes to (R, G, 0, 255)
+BC_FORMATS = tuple(range(FORMAT_BC1_UNORM, FORMAT_BC5_UNORM + 1))
 
 TEXTURE_RENDER_TARGET = 2   # or'ed into trhip_texture_desc.isUAV
 
@@ -45,7 +56,7 @@ ABI_SYMBOLS = [
     "trhip_texture_create_array", "trhip_texture_array_size", "trhip_texture_slice_pitch", "trhip_texture_upload_slice", "trhip_texture_download_slice",
     "trhip_buffer_mark_written", "trhip_texture_mark_written",
     "trhip_texture_table_create", "trhip_texture_table_retain", "trhip_texture_table_release", "trhip_texture_table_capacity",
-    "trhip_texture_table_set", "trhip_texture_table_clear", "trhip_srgb_table",
+    "trhip_texture_table_set", "trhip_texture_table_clear", "trhip_srgb_table", "trhip_format_block_bytes", "trhip_dds_parse",
     "trhip_cmd_create", "trhip_cmd_release", "trhip_cmd_open", "trhip_cmd_close", "trhip_cmd_write_buffer",
     "trhip_cmd_clear_buffer_u32", "trhip_cmd_clear_texture_f32", "trhip_cmd_clear_texture_u32", "trhip_cmd_copy_buffer", "trhip_cmd_copy_texture", "trhip_cmd_host_callback", "trhip_cmd_dispatch", "trhip_cmd_dispatch_indirect",
     "trhip_cmd_begin_timer", "trhip_cmd_end_timer", "trhip_cmd_begin_marker", "trhip_cmd_end_marker",
@@ -73,6 +84,12 @@ class BufferDesc(C.Structure):
 class TextureDesc(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mipLevels", C.c_uint32), ("format", C.c_uint32),
                 ("isUAV", C.c_uint32), ("isVirtual", C.c_uint32), ("debugName", C.c_char_p)]
+
+
+class DdsInfo(C.Structure):
+    """trhip_dds_info (include/trhip.h)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mipLevels", C.c_uint32), ("format", C.c_uint32),
+                ("levelOffset", C.c_uint64 * 16), ("levelBytes", C.c_uint64 * 16)]
 
 
 class Binding(C.Structure):
@@ -169,6 +186,10 @@ def load() -> C.CDLL:
         L.trhip_texture_slice_pitch.restype = u64
         L.trhip_texture_upload_slice.argtypes = [vp, u32, vp, u64]
         L.trhip_texture_download_slice.argtypes = [vp, u32, vp, u64]
+    if hasattr(L, "trhip_dds_parse"):                       # absent from an older build named by TRHIP_LIB (see above)
+        L.trhip_format_block_bytes.argtypes = [u32]
+        L.trhip_format_block_bytes.restype = u32
+        L.trhip_dds_parse.argtypes = [vp, u64, C.POINTER(DdsInfo)]
     L.trhip_cmd_create.argtypes = [vp, C.POINTER(vp)]
     L.trhip_cmd_open.argtypes = [vp]
     L.trhip_cmd_close.argtypes = [vp]
@@ -243,6 +264,23 @@ def srgb_table() -> np.ndarray:
     return out
 
 
+def format_block_bytes(fmt: int) -> int:
+    """trhip_format_block_bytes: 8 or 16 for one of BC_FORMATS, 0 for every other format (no device needed)."""
+    if not hasattr(load(), "trhip_format_block_bytes"):
+        raise TrhipError(f"{LIB_PATH} has no trhip_format_block_bytes: a build from before block-compressed textures")
+    return int(load().trhip_format_block_bytes(int(fmt)))
+
+
+def dds_parse(data) -> DdsInfo:
+    """trhip_dds_parse on the bytes of a .dds file: what the file says (no device needed); raises TrhipError with the parser's message."""
+    if not hasattr(load(), "trhip_dds_parse"):
+        raise TrhipError(f"{LIB_PATH} has no trhip_dds_parse: a build from before block-compressed textures")
+    buf = np.frombuffer(bytes(data), np.uint8)
+    info = DdsInfo()
+    _check(load().trhip_dds_parse(buf.ctypes.data if len(buf) else None, len(buf), C.byref(info)))
+    return info
+
+
 def shader_names():
     L = load()
     return [L.trhip_shader_name(i).decode() for i in range(L.trhip_shader_count())]
@@ -288,6 +326,12 @@ class Texture:
     def mip_dims(self, k: int):
         return max(self.w >> k, 1), max(self.hgt >> k, 1)
 
+    def mip_info(self, k: int):
+        """(width, height, byte offset) of level k (trhip_texture_mip_info)."""
+        w, h, off = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        _check(load().trhip_texture_mip_info(self.h, k, C.byref(w), C.byref(h), C.byref(off)))
+        return int(w.value), int(h.value), int(off.value)
+
     def _dtype(self):
         return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32,
                 FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8, FORMAT_RGBA8_UNORM: np.uint32,
@@ -310,14 +354,25 @@ class Texture:
     def slice_pitch(self) -> int:
         return int(load().trhip_texture_slice_pitch(self.h))
 
-    def upload_mip(self, k: int, arr: np.ndarray):
+    def upload_mip(self, k: int, arr):
+        """Level k.  A block-compressed texture takes the level's raw block bytes (bytes, or an array of any shape): ceil(w_k / 4) x
+        ceil(h_k / 4) blocks of format_block_bytes(format) bytes, row-major; a wrong byte count is refused."""
+        if self.format in BC_FORMATS:
+            arr = np.frombuffer(arr, np.uint8) if isinstance(arr, (bytes, bytearray, memoryview)) else np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
+            _check(load().trhip_texture_upload(self.h, k, arr.ctypes.data, arr.nbytes))
+            return
         if self.format in (FORMAT_RGBA8_UNORM, FORMAT_SRGBA8_UNORM) and np.asarray(arr).dtype == np.uint8:   # [h, w, 4] bytes R, G, B, A
             arr = np.ascontiguousarray(arr).reshape(-1).view(np.uint32)
         arr = np.ascontiguousarray(arr, self._dtype())
         _check(load().trhip_texture_upload(self.h, k, arr.ctypes.data, arr.nbytes))
 
     def download_mip(self, k: int) -> np.ndarray:
+        """Level k; of a block-compressed texture its raw block bytes, uint8 [ceil(h_k / 4), ceil(w_k / 4), block bytes]."""
         mw, mh = self.mip_dims(k)
+        if self.format in BC_FORMATS:
+            out = np.empty(((mh + 3) // 4, (mw + 3) // 4, format_block_bytes(self.format)), np.uint8)
+            _check(load().trhip_texture_download(self.h, k, out.ctypes.data, out.nbytes))
+            return out
         out = np.empty(self._shape(mw, mh), self._dtype())
         _check(load().trhip_texture_download(self.h, k, out.ctypes.data, out.nbytes))
         return out
@@ -571,9 +626,22 @@ class Device:
 
     def create_sampled_texture(self, mips, fmt: int, name="") -> Texture:
         """A material texture from its mip chain: mips = uint8 arrays [h_k, w_k, 4] (R, G, B, A), level k of
-        max(w >> k, 1) x max(h >> k, 1); fmt = FORMAT_RGBA8_UNORM or FORMAT_SRGBA8_UNORM.  Created without the UAV bit."""
+        max(w >> k, 1) x max(h >> k, 1); fmt = FORMAT_RGBA8_UNORM or FORMAT_SRGBA8_UNORM.  Created without the UAV bit.
+        For one of BC_FORMATS mips is an interop.BlockMips: the raw block bytes of every level with the size of level 0 in texels
+        (any size >= 1); the blocks are uploaded as they are -- there is no encoder."""
+        if fmt in BC_FORMATS:
+            if not hasattr(mips, "width") or len(mips) == 0:
+                raise ValueError("a block-compressed texture takes an interop.BlockMips (the levels' block bytes and the size in texels)")
+            t = self.create_texture(int(mips.width), int(mips.height), len(mips), fmt, name, uav=False)
+            try:
+                for k, m in enumerate(mips):
+                    t.upload_mip(k, m)
+            except Exception:
+                t.release()
+                raise
+            return t
         if fmt not in (FORMAT_RGBA8_UNORM, FORMAT_SRGBA8_UNORM):
-            raise ValueError(f"a sampled texture is RGBA8_UNORM or SRGBA8_UNORM, not format {fmt}")
+            raise ValueError(f"a sampled texture is RGBA8_UNORM, SRGBA8_UNORM or one of BC_FORMATS, not format {fmt}")
         mips = [np.ascontiguousarray(m, np.uint8) for m in mips]
         if not mips or any(m.ndim != 3 or m.shape[2] != 4 for m in mips):
             raise ValueError("mips: a non-empty list of uint8 [h, w, 4] arrays")
