@@ -73,6 +73,7 @@ enum {
  * (R, 0, 0, 255), BC5 to (R, G, 0, 255).  There is no encoder, and BC6H, BC7 and the SNORM variants are not supported. */
 enum { TRHIP_FORMAT_R16_FLOAT = 1, TRHIP_FORMAT_R32_FLOAT = 2, TRHIP_FORMAT_RG32_UINT = 3, TRHIP_FORMAT_RG16_FLOAT = 4,
        TRHIP_FORMAT_RGBA32_UINT = 5, TRHIP_FORMAT_R11G11B10_FLOAT = 6, TRHIP_FORMAT_R8_UNORM = 7, TRHIP_FORMAT_R8_UINT = 8,
+       TRHIP_SAMPLER_FEEDBACK_FORMAT = 9,   /* opaque: made by trhip_sampler_feedback_create only */
        TRHIP_FORMAT_RGBA8_UNORM = 10, TRHIP_FORMAT_SRGBA8_UNORM = 11, TRHIP_FORMAT_R10G10B10A2_UNORM = 12, TRHIP_FORMAT_RGBA16_FLOAT = 13,
        TRHIP_FORMAT_BC1_UNORM = 14, TRHIP_FORMAT_BC1_UNORM_SRGB = 15, TRHIP_FORMAT_BC2_UNORM = 16, TRHIP_FORMAT_BC2_UNORM_SRGB = 17,
        TRHIP_FORMAT_BC3_UNORM = 18, TRHIP_FORMAT_BC3_UNORM_SRGB = 19, TRHIP_FORMAT_BC4_UNORM = 20, TRHIP_FORMAT_BC5_UNORM = 21 };
@@ -320,6 +321,46 @@ int  trhip_texture_table_clear(trhip_texture_table table, uint32_t index);
  * copy from its first texture table on. */
 int  trhip_srgb_table(float* out);
 
+/* ---- texture streaming: the min-mip clamp and sampler feedback of SampleMaterialValue (lightingcommon.hlsli:358-406) -----------
+ * OPT-IN: a table without a min-mip or feedback entry records exactly the launches it always did.
+ *
+ * A material texture (RGBA8_UNORM, SRGBA8_UNORM or block-compressed, no UAV bit) becomes STREAMABLE by
+ * trhip_texture_set_streaming_region: region_w x region_h texels, both powers of two >= 4 (a BC block never straddles a region),
+ * both dividing the size of mip 0.  0 x 0 asks for D3D's 64 KB tile shape of the format: 128 x 128 (RGBA8), 512 x 256 (BC1, BC4),
+ * 256 x 256 (BC2, BC3, BC5).  A texture that the region does not divide is refused: it is "not tiled", stays fully resident and
+ * takes no maps.  Level k is STANDARD when it and every finer level are whole tiles, that is when (w >> j) and (h >> j) are
+ * multiples (>= 1) of the region for every j <= k (a size that is no power of two stops early: 24 x 24 with 8 x 8 has one standard
+ * level, 48 x 32 two), and k is not the last level: the levels after the last standard one are the PACKED TAIL, which is always
+ * resident and always holds at least the last level.  The region is part of the texture's table entry: set it before trhip_texture_table_set.
+ *
+ * MIN-MIP MAP: an ordinary R8_UINT texture of (w / region_w) x (h / region_h) texels, one per mip-0 region, set into the same
+ * table; a material names it in TextureData::m_MinMapTextureDescriptorIndex.  The resolve reads the texel of the region that holds
+ * the mip-0 texel under uv (point, wrapped or clamped as the slot's sampler) and samples at
+ * fmin(fmax(lod, (float)minMip), mips - 1); the tap count and the tap positions do not change.
+ *
+ * FEEDBACK MAP: an opaque texture (TRHIP_SAMPLER_FEEDBACK_FORMAT; one 32-bit word per region, 0xFFFFFFFF = never sampled) made
+ * by trhip_sampler_feedback_create against its streamable material texture, set into the table and named by
+ * m_FeedbackTextureDescriptorIndex.  With BasePassConstants::m_bWriteSamplerFeedback != 0 the resolve lowers, for every sample
+ * of the slot, the word of every region that the UNCLAMPED sample would read to the finest level it would read it at (atomic
+ * min; material_textures.hip.h states the marks).  trhip_cmd_clear_sampler_feedback resets every word,
+ * trhip_cmd_decode_sampler_feedback writes one byte per region (row-major; the level, 0xFF = never sampled) into a buffer, from
+ * where trhip_cmd_copy_to_readback takes it to the host.
+ *
+ * A flagged slot whose min-mip or feedback index is not 0xFFFFFFFF and names no such map of that very texture (past the table,
+ * empty, another format, another size, a texture that is not streamable) ends the pixel untouched, like every other broken chain.
+ * "basepass_PS_Main_GBuffer" records its #streamed kernel iff the bound table holds at least one R8_UINT or feedback entry.
+ *
+ * trhip_cmd_write_texture_region (writeTexture with a TextureSlice): a rectangle of one mip of a sampled material texture (or of an
+ * R8_UINT min-mip map created without the UAV bit), in texels; for a block-compressed texture x, y, w and h are multiples of 4 (w and h may instead end at the level's edge) and src
+ * holds the rectangle's blocks.  src is row-major without padding and is copied when the command is recorded. */
+int  trhip_texture_set_streaming_region(trhip_texture tex, uint32_t region_w, uint32_t region_h);
+int  trhip_texture_streaming_region(trhip_texture tex, uint32_t* region_w, uint32_t* region_h);   /* 0 x 0: not streamable */
+int  trhip_sampler_feedback_create(trhip_device dev, trhip_texture paired, const char* debug_name, trhip_texture* out);
+int  trhip_cmd_clear_sampler_feedback(trhip_cmdlist cl, trhip_texture feedback);
+int  trhip_cmd_decode_sampler_feedback(trhip_cmdlist cl, trhip_buffer dst, uint64_t dst_offset, trhip_texture feedback);
+int  trhip_cmd_write_texture_region(trhip_cmdlist cl, trhip_texture tex, uint32_t mip, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
+                                    const void* src, uint64_t bytes);
+
 /* ---- DDS container (no device needed; written from the public description of the format) ---------------------------------------
  * trhip_dds_parse reads the header of a .dds file held in memory and answers what the file says: size, mip count, format, and
  * where each level's bytes lie in the file (levels follow the header back to back, without padding; a level of a block format
@@ -459,6 +500,9 @@ void trhip_readback_release(trhip_readback rb);
 int  trhip_readback_reset(trhip_readback rb);
 int  trhip_cmd_copy_to_readback(trhip_cmdlist cl, trhip_readback rb, uint32_t slot, trhip_buffer src_buffer, uint64_t src_offset, uint64_t bytes);
 int  trhip_readback_read(trhip_readback rb, uint32_t slot, void* dst, uint64_t bytes, uint64_t* written);
+/* Never waits: *ready = 1 when trhip_readback_read of that slot would return at once (its last copy has completed, or no executed
+ * list has written it), else 0. */
+int  trhip_readback_poll(trhip_readback rb, uint32_t slot, int* ready);
 
 /* ---- acceleration structure: nvrhi::rt::AccelStruct (Visual.cpp:509-542 Mesh::BuildBLAS, Scene.cpp:430-470 the TLAS) ----------
  * DXR's structure is opaque; this one is the project's own and lives in ordinary structured buffers that the caller creates,

@@ -418,6 +418,35 @@ int  trhost_renderer_times(const char* renderer_name, float* cpu_ms, float* gpu_
  * ops[i] < 0: Free(results[-ops[i]-1]). */
 int  trhost_heap_sim(uint64_t heap_size, const int64_t* ops, uint32_t num_ops, uint64_t* results, uint64_t* used, uint64_t* peak, uint32_t* num_blocks);
 
+/* TEXTURE STREAMING (csrc/host/TextureFeedbackManager.h; include/trhip.h "texture streaming"; opt-in, off by default).  Switched on
+ * BEFORE the first trhost_create_material_texture: a texture created afterwards whose size is a multiple of the region (default: D3D's
+ * 64 KB tile shape of its format; trhost_set_texture_streaming_region gives another, and then a size that is no multiple is refused)
+ * keeps its mips on the host and only its packed tail on the device, with the rest filled with 0xFF00FFFF when poison != 0;
+ * trhost_load_materials fills the two map indices of its slots in, accepts them when they name the maps of that very texture and
+ * refuses anything else.  Every frame with the G-buffer resolve then runs TextureFeedbackManager::BeginFrame (what earlier frames
+ * decoded and has arrived -- polled, never waited for --, the residency rule, tile uploads, min-mip rewrites, round-robin over
+ * textures_per_frame textures, clear) and EndFrame (decode, copy to the read-back).  A tile that none of the last evict_after
+ * processed feedbacks of its texture required is unmapped.  Refused together with trhost_set_alpha_test.
+ * stats: tiles total, tiles resident, tiles uploaded by the last frame, bytes uploaded by the last frame, textures processed by it.
+ * trhost_download_min_mip: the device's min-mip map of a streamed texture (one byte per region, row-major); dst NULL asks for the
+ * size alone. */
+int  trhost_set_texture_streaming(int enable, uint32_t textures_per_frame, uint32_t evict_after, int poison);
+int  trhost_set_texture_streaming_region(uint32_t region_w, uint32_t region_h);
+int  trhost_get_texture_streaming_stats(uint64_t stats[5]);
+int  trhost_download_min_mip(uint32_t texture, uint8_t* dst, uint64_t bytes, uint32_t* regions_x, uint32_t* regions_y);
+
+/* The residency rule of texture streaming (csrc/host/TextureResidency.h states it; no GPU, no initialised host needed): one round
+ * of one streamable texture of width x height texels and `mips` levels with regions of region_w x region_h texels.  feedback: one
+ * decoded byte per region (0xFF = never sampled).  resident (bytes) and idle (words): one entry per tile, levels 0 .. S - 1 one
+ * after the other, row-major; updated in place.  mapped, unmapped: one byte per tile, set for the tiles this round maps / unmaps.
+ * min_mip: one byte per region, rewritten.  stats: tiles total, tiles resident, tiles mapped, tiles unmapped, bytes uploaded
+ * (tiles mapped x tile_bytes).  num_tiles: the length of the per-tile arrays, which must be the texture's tile count
+ * (trhost_residency_tiles). */
+int  trhost_residency_tiles(uint32_t width, uint32_t height, uint32_t mips, uint32_t region_w, uint32_t region_h, uint32_t* standard_levels, uint32_t* num_tiles);
+int  trhost_residency_round(uint32_t width, uint32_t height, uint32_t mips, uint32_t region_w, uint32_t region_h, uint32_t tile_bytes,
+                            const uint8_t* feedback, uint32_t evict_after, uint32_t num_tiles, uint8_t* resident, uint32_t* idle,
+                            uint8_t* mapped, uint8_t* unmapped, uint8_t* min_mip, uint64_t stats[5]);
+
 #ifdef __cplusplus
 }
 #endif

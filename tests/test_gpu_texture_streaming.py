@@ -1,0 +1,230 @@
+"""Texture streaming on the GPU, the shader half: "basepass_PS_Main_GBuffer" with a min-mip or feedback map in the table at t19
+(the #streamed instantiation; csrc/material_textures.hip.h, csrc/visibility_resolve.hip.h).  Every word of GBufferA, of the motion
+target and of the decoded feedback against tests/texture_streaming_ref.c, through raw dispatches at 80 x 56 pixels, over textures
+of 32 x 32, 64 x 32 and 16 x 64 texels with regions of 8 x 8 in RGBA8, sRGBA8, BC1 and BC3."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import bc_blocks as B  # noqa: E402
+import bc_ref  # noqa: E402
+import material_texture_scenes as S  # noqa: E402
+import texture_streaming_ref as TS  # noqa: E402
+import texture_streaming_scenes as X  # noqa: E402
+from suite_support import dev, ref_library, same, vr  # noqa: E402, F401
+from visibility_scenes import consts  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ts = ref_library(TS)
+ALL = S.ALBEDO | S.NORMAL | S.MR | S.EMISSIVE
+EMIT = (2.0, 0.5, 4.0)
+STREAMED, TEXTURED = ["basepass_PS_Main_GBuffer#streamed"], ["basepass_PS_Main_GBuffer#textured"]
+
+
+@pytest.fixture(scope="module")
+def bc(tmp_path_factory):
+    return bc_ref.load(tmp_path_factory.mktemp("bc_ref"))
+
+
+def _both(dev, vr, ts, bc, scene, mats, table, what, feedback=True, visualize=False, names=STREAMED):
+    """The scene on the GPU and in the reference: every word of the three outputs equal.  Returns (vis, GBufferA, {entry: feedback bytes})."""
+    k = consts(S.view())
+    vis, g, mot, got_names, fb = X.gpu(dev, k, scene, mats, table, feedback, visualize)
+    rvis, rg, rmot, rfb = X.reference(vr, ts, bc, k, scene, mats, table, feedback, visualize)
+    same(vis, rvis, what + ": visibility texels")
+    same(g, rg, what + ": GBufferA")
+    same(mot, rmot, what + ": motion")
+    assert sorted(fb) == sorted(rfb), (sorted(fb), sorted(rfb))
+    for i in fb:
+        same(fb[i], rfb[i], what + f": decoded feedback of entry {i}")
+    assert got_names == names, got_names
+    assert np.all(g[vis == 0] == X.FILL), what + ": nothing drawn, nothing written"
+    return vis, g, fb
+
+
+def _wrap_and_clamp_quads():
+    """uv in [-1.5, 2.5] on both: wrap repeats the texture four times, so footprints wrap across its edge; clamp smears its border."""
+    return [S.facing(z=-3.0, half=0.55, uv_lo=-1.5, uv_hi=2.5, material=0, centre=(-0.6, 0.0), world=X.turn()),
+            S.facing(z=-3.0, half=0.55, uv_lo=-1.5, uv_hi=2.5, material=1, centre=(0.65, 0.05), world=X.turn())]
+
+
+@pytest.mark.parametrize("size, fmt", [((32, 32), S.SRGBA8), ((64, 32), B.BC1), ((16, 64), B.BC3), ((64, 32), S.RGBA8), ((32, 32), B.BC3_SRGB)],
+                         ids=["32x32 sRGBA8", "64x32 BC1", "16x64 BC3", "64x32 RGBA8", "32x32 BC3_SRGB"])
+def test_wrap_and_clamp_under_a_random_min_mip_map(dev, vr, ts, bc, size, fmt):
+    """Two rotated quads with uv outside [0, 1], one wrapped and one clamped, over one texture whose min-mip texels are random in
+    0 .. 5: below, at and above the level a pixel wants, so the clamp is active on a part of each quad and idle on the rest."""
+    w, h = size
+    textures = [X.texture(40, w, h, fmt)]
+    mm = X.random_minmip(7, w, h)
+    table, where = X.with_maps(textures, minmips={0: mm})
+    mats = np.concatenate([X.material(where, S.ALBEDO, (0, S.NONE, S.NONE, S.NONE)), X.material(where, S.ALBEDO, (0, S.NONE, S.NONE, S.NONE), wrap=(0, 0, 0, 0))])
+    scene = S.build(_wrap_and_clamp_quads())
+    vis, g, fb = _both(dev, vr, ts, bc, scene, mats, table, f"{w} x {h}")
+    zero, _ = X.with_maps(textures)
+    _, g0, fb0 = _both(dev, vr, ts, bc, scene, mats, zero, f"{w} x {h}, min-mip 0")
+    cov = vis != 0
+    changed = (g[cov][:, 0] != g0[cov][:, 0]).mean()
+    assert cov.sum() > 1200 and 0.1 < changed < 0.95, changed                 # clamped on a part, not on all of it
+    same(fb[where[0][1]], fb0[where[0][1]], "feedback does not depend on the min-mip map")
+    asked = fb[where[0][1]]
+    assert np.all(asked != TS.NEVER), asked                                    # wrap reaches every region
+
+
+def test_magnified_tail_minified_and_anisotropic(dev, vr, ts, bc):
+    """A quad so near that lod = 0, one so far that it samples the packed tail alone (it asks for no standard level), and the grazing
+    floor, whose taps span several regions; min-mip maps random."""
+    quads, textures, mats = X.loop_scene("three")
+    table, where = X.with_maps(textures, minmips={i: X.random_minmip(9 + i, *X.size_of(t[1])) for i, t in enumerate(textures)})
+    vis, g, fb = _both(dev, vr, ts, bc, S.build(quads), mats(where), table, "near, turned, far")
+    assert fb[where[0][1]].min() == 0, "the magnified quad asks for level 0"
+    far = fb[where[2][1]]
+    assert (far >= 2).sum() >= 4 and (far == TS.NEVER).sum() >= 1, far       # 16 x 64 has 2 standard levels: the far quad asks for the tail only
+    quads, textures, mats = X.loop_scene("floor")
+    table, where = X.with_maps(textures, minmips={i: X.random_minmip(19 + i, *X.size_of(t[1])) for i, t in enumerate(textures)})
+    _both(dev, vr, ts, bc, S.build(quads), mats(where), table, "floor")
+
+
+def test_feedback_flag_off_and_partial_maps(dev, vr, ts, bc):
+    """With the maps bound and m_bWriteSamplerFeedback = 0 no feedback word moves.  A texture with a min-mip map and no feedback entry
+    is clamped and asks for nothing; one with a feedback entry and no map is sampled as before and still asks."""
+    textures = [X.texture(50, 32, 32, S.RGBA8), X.texture(51, 64, 32, B.BC1)]
+    scene = S.build(_wrap_and_clamp_quads())
+    mm = {0: X.random_minmip(3, 32, 32), 1: X.random_minmip(4, 64, 32)}
+    table, where = X.with_maps(textures, minmips=mm)
+    mats = np.concatenate([X.material(where, S.ALBEDO | S.MR, (0, S.NONE, 1, S.NONE)), X.material(where, S.ALBEDO | S.MR, (1, S.NONE, 0, S.NONE), wrap=(0, 1, 0, 1))])
+    _, g_on, fb_on = _both(dev, vr, ts, bc, scene, mats, table, "flag on")
+    _, g_off, fb_off = _both(dev, vr, ts, bc, scene, mats, table, "flag off", feedback=False)
+    same(g_off, g_on, "GBufferA does not depend on the feedback flag")
+    assert all(np.all(b == TS.NEVER) for b in fb_off.values()) and all(np.any(b != TS.NEVER) for b in fb_on.values())
+    only_map, w_map = X.with_maps(textures, minmips=mm, feedback=False)
+    _, g_map, fb_map = _both(dev, vr, ts, bc, scene, np.concatenate([X.material(w_map, S.ALBEDO | S.MR, (0, S.NONE, 1, S.NONE)),
+                                                                    X.material(w_map, S.ALBEDO | S.MR, (1, S.NONE, 0, S.NONE), wrap=(0, 1, 0, 1))]), only_map, "maps alone")
+    same(g_map, g_on, "the clamp needs no feedback entry")
+    assert fb_map == {}
+    only_fb, w_fb = X.with_maps(textures, minmip=False)
+    plain = np.concatenate([S.material(flags=S.ALBEDO | S.MR, indices=(0, S.NONE, 1, S.NONE)), S.material(flags=S.ALBEDO | S.MR, indices=(1, S.NONE, 0, S.NONE), wrap=(0, 1, 0, 1))])
+    with_fb = np.concatenate([X.material(w_fb, S.ALBEDO | S.MR, (0, S.NONE, 1, S.NONE)), X.material(w_fb, S.ALBEDO | S.MR, (1, S.NONE, 0, S.NONE), wrap=(0, 1, 0, 1))])
+    _, g_fb, fb_fb = _both(dev, vr, ts, bc, scene, with_fb, only_fb, "feedback alone")
+    for i in (0, 1):
+        same(fb_fb[w_fb[i][1]], fb_on[where[i][1]], "feedback without a map")
+    # the same table under materials that name no map: still #streamed (the table decides), and the words of the textured kernel
+    _, g_plain, _ = _both(dev, vr, ts, bc, scene, plain, only_fb, "no index named")
+    same(g_fb, g_plain, "a feedback entry changes no word of GBufferA")
+
+
+def test_two_materials_share_one_texture_and_all_four_slots_stream(dev, vr, ts, bc):
+    """Overlapping marks from two quads (and, in the first, from all four slots) on the same words: min is order-independent, the
+    words are the reference's.  The second material reads the shared texture through the other sampler."""
+    textures = [X.texture(60, 32, 32, S.SRGBA8), X.texture(61, 64, 32, S.RGBA8, normal=True), X.texture(62, 16, 64, B.BC3), X.texture(63, 32, 32, B.BC1_SRGB)]
+    table, where = X.with_maps(textures, minmips={i: X.random_minmip(29 + i, *X.size_of(t[1]), hi=4) for i, t in enumerate(textures)})
+    mats = np.concatenate([X.material(where, ALL, (0, 1, 2, 3), emissive=EMIT), X.material(where, ALL, (3, 1, 0, 0), emissive=EMIT, wrap=(0, 0, 1, 0))])
+    quads = [S.facing(z=-3.0, half=0.6, uv_lo=-1.5, uv_hi=2.5, material=0, centre=(-0.6, 0.0), world=X.turn()),
+             S.facing(z=-2.0, half=0.5, uv_lo=0.1, uv_hi=0.9, material=1, centre=(0.55, 0.1), world=X.turn(-0.2))]
+    vis, g, fb = _both(dev, vr, ts, bc, S.build(quads), mats, table, "shared")
+    assert all(np.any(b != TS.NEVER) for b in fb.values()) and len(fb) == 4
+    assert len(np.unique(g[vis != 0][:, 3])) > 50 and len(np.unique(g[vis != 0][:, 2])) > 50, "roughness, metallic and emissive vary"
+
+
+def test_visualize_min_mip_on_albedo(dev, vr, ts, bc):
+    """m_bVisualizeMinMipTilesOnAlbedoOutput: the albedo of a slot with a min-mip map is kMipColors[minMip] times m_ConstAlbedo; the quad
+    whose material names no map keeps its texture; the other three channels do not move."""
+    textures = [X.texture(70, 32, 32, S.SRGBA8)]
+    mm = (np.arange(16, dtype=np.uint8).reshape(4, 4) * 5) % 19            # 0 .. 18: also beyond the sixteen colours
+    table, where = X.with_maps(textures, minmips={0: mm})
+    mats = np.concatenate([X.material(where, S.ALBEDO | S.MR, (0, S.NONE, 0, S.NONE), albedo=(1.0, 1.0, 1.0, 1.0)),
+                           S.material(flags=S.ALBEDO, indices=(0, S.NONE, S.NONE, S.NONE), wrap=(0, 0, 0, 0))])
+    scene = S.build(_wrap_and_clamp_quads())
+    vis, g, _ = _both(dev, vr, ts, bc, scene, mats, table, "visualize", visualize=True)
+    _, g0, _ = _both(dev, vr, ts, bc, scene, mats, table, "visualize off")
+    same(g[..., 1:], g0[..., 1:], "normal, emissive, roughness and metallic")
+    colours = {int(x) for x in np.unique(g[vis != 0][:, 0] & 0xFFFFFF)}
+    assert 0xFFFFFF in colours and (63 | 255 << 8 | 63 << 16) in colours, "kMipColors[0] = white and [2] = light green show"
+    assert np.any(g[..., 0] != g0[..., 0]) and np.any((g[..., 0] == g0[..., 0]) & (vis != 0)), "the map-free quad is unchanged"
+
+
+def test_a_table_without_a_map_records_the_textured_kernel(dev, vr, ts, bc):
+    """Exactly #textured, and today's words, when the table holds no map -- also when its textures are streamable and when a min-mip
+    entry was set and cleared again.  A slot that names a map that is none of its texture's leaves the pixel untouched."""
+    textures = [X.texture(80, 32, 32, S.SRGBA8), X.texture(81, 64, 32, B.BC1)]
+    mats = np.concatenate([S.material(flags=S.ALBEDO, indices=(0, S.NONE, S.NONE, S.NONE)), S.material(flags=S.ALBEDO, indices=(1, S.NONE, S.NONE, S.NONE), wrap=(0, 0, 0, 0))])
+    scene = S.build(_wrap_and_clamp_quads())
+    _, g, fb = _both(dev, vr, ts, bc, scene, mats, list(textures), "no map", names=TEXTURED)
+    assert fb == {}
+    zero, where = X.with_maps(textures)
+    named = np.concatenate([X.material(where, S.ALBEDO, (0, S.NONE, S.NONE, S.NONE)), X.material(where, S.ALBEDO, (1, S.NONE, S.NONE, S.NONE), wrap=(0, 0, 0, 0))])
+    _, gz, _ = _both(dev, vr, ts, bc, scene, named, zero, "zero maps", feedback=False)
+    same(gz, g, "#streamed under zero maps against #textured")
+    k = consts(S.view())
+    tt, made = X.upload(dev, zero)
+    try:
+        for i, e in enumerate(zero):
+            if e[0] != "texture":
+                tt.clear(i)
+        import bc_passes as P
+        _, gc, _, names = P.resolve(dev, k, scene, S.RENDER, mats, tt)
+    finally:
+        X.release(tt, made)
+    assert names == TEXTURED, names
+    same(gc, g, "after the maps were cleared")
+    # the second material names the FIRST texture's maps (4 x 4 regions against 8 x 4): its pixels stay as they were
+    crossed = named.copy()
+    for f in ("m_MinMapTextureDescriptorIndex", "m_FeedbackTextureDescriptorIndex"):
+        crossed["m_AlbedoTexture"][f][1] = named["m_AlbedoTexture"][f][0]
+    vis, gx, _ = _both(dev, vr, ts, bc, scene, crossed, zero, "another texture's maps")
+    assert np.any(gx[vis != 0][:, 0] == X.FILL) and np.any(gx[vis != 0][:, 0] != X.FILL)
+
+
+def test_region_writes_decode_and_refusals(dev):
+    """trhip_cmd_write_texture_region against whole-mip uploads (RGBA8 rectangles, BC blocks, an edge), and the refusals by name."""
+    from toyrenderer_amd import rhi
+    mips = S.random_mips(90, 32, 16, 3)
+    t = dev.create_sampled_texture(mips, rhi.FORMAT_RGBA8_UNORM, "plain")
+    blocks = B.block_mips(91, 24, 16, 2, B.BC3)
+    b = dev.create_sampled_texture(blocks, B.BC3, "blocks")
+    cl = dev.create_command_list()
+    try:
+        new = S.random_mips(92, 32, 16, 3)
+        cl.open()
+        cl.write_texture_region(t, 0, 8, 4, 16, 8, new[0][4:12, 8:24])
+        cl.write_texture_region(t, 2, 7, 3, 1, 1, new[2][3:4, 7:8])
+        raw = np.frombuffer(bytes(B.block_mips(93, 24, 16, 2, B.BC3)[0]), np.uint8).reshape(4, 6, 16)
+        cl.write_texture_region(b, 0, 8, 4, 16, 12, raw[1:4, 2:6])
+        for bad, match in ((lambda: cl.write_texture_region(t, 0, 24, 0, 16, 4, new[0][:4, :16]), "leave mip"),
+                           (lambda: cl.write_texture_region(t, 3, 0, 0, 1, 1, new[0][:1, :1]), "mip 3"),
+                           (lambda: cl.write_texture_region(t, 0, 0, 0, 4, 4, new[0][:4, :5]), "bytes"),
+                           (lambda: cl.write_texture_region(b, 0, 2, 0, 4, 4, raw[:1, :1]), "whole 4 x 4 blocks")):
+            with pytest.raises(rhi.TrhipError, match=match):
+                bad()
+        cl.close()
+        dev.execute(cl); dev.wait_idle()
+        want = mips[0].copy(); want[4:12, 8:24] = new[0][4:12, 8:24]
+        same(t.download_mip(0), want.reshape(-1).view(np.uint32).reshape(16, 32), "RGBA8 rectangle")
+        want2 = mips[2].copy(); want2[3, 7] = new[2][3, 7]
+        same(t.download_mip(2), want2.reshape(-1).view(np.uint32).reshape(4, 8), "one texel of mip 2")
+        same(t.download_mip(1), mips[1].reshape(-1).view(np.uint32).reshape(8, 16), "mip 1 untouched")
+        wantb = np.frombuffer(bytes(blocks[0]), np.uint8).reshape(4, 6, 16).copy(); wantb[1:4, 2:6] = raw[1:4, 2:6]
+        same(b.download_mip(0), wantb, "BC3 blocks")
+        with pytest.raises(rhi.TrhipError, match="not a multiple"):
+            t.set_streaming_region(64, 8)
+        with pytest.raises(rhi.TrhipError, match="powers of two"):
+            t.set_streaming_region(8, 2)
+        with pytest.raises(rhi.TrhipError, match="not streamable"):
+            dev.create_sampler_feedback(t)
+        with pytest.raises(rhi.TrhipError, match="not a multiple"):
+            t.set_streaming_region()                                      # the default 128 x 128 does not divide 32 x 16
+        assert t.streaming_region() == (0, 0) and t.set_streaming_region(16, 8) == (16, 8)
+        fb = dev.create_sampler_feedback(t, "fb")
+        try:
+            assert (fb.w, fb.hgt) == (2, 2) and fb.streaming_region() == (16, 8)
+            same(fb.download_mip(0), np.full((2, 2), 0xFFFFFFFF, np.uint32), "created as never sampled")
+            with pytest.raises(rhi.TrhipError, match="feedback map"):
+                cl.open().clear_sampler_feedback(t)
+            cl.close()
+        finally:
+            fb.release()
+    finally:
+        cl.release(); t.release(); b.release()

@@ -24,6 +24,7 @@
 #include "GraphicConstants.h"
 #include "RenderGraph.h"
 #include "Scene.h"
+#include "TextureFeedbackManager.h"
 #include "VisibilityOutputs.h"
 #include "../ShaderInterop.h"
 
@@ -472,6 +473,11 @@ public:
         k.m_NearPlane = g_Scene->m_View.m_ZNearP;
         k.m_OutputResolution = g_Graphic.m_RenderResolution;
         if (bGBuffer) k.m_DebugMode = g_Scene->m_DebugViewMode;
+        const bool bStreaming = bGBuffer && g_TextureFeedbackManager.m_bEnabled && !g_TextureFeedbackManager.m_Textures.empty();
+        if (bStreaming) {                                                     // BasePassRenderers.cpp:458; TextureFeedbackManager::BeginFrame
+            k.m_bWriteSamplerFeedback = 1;
+            g_TextureFeedbackManager.BeginFrame(commandList);
+        }
         Graphic::ComputePassParams p;
         p.m_CommandList = commandList;
         p.m_ShaderName = bGBuffer ? "basepass_PS_Main_GBuffer" : "basepass_PS_Main_motion";
@@ -492,6 +498,7 @@ public:
         }
         p.m_DispatchGroupSize = ComputeShaderUtils::GetGroupCount(g_Graphic.m_RenderResolution, 8);
         g_Graphic.AddComputePass(p);
+        if (bStreaming) g_TextureFeedbackManager.EndFrame(commandList);      // decode + copy to the read-back
     }
 
     void GenerateHZB(nvrhi::CommandListHandle commandList, const RenderGraph& renderGraph, const RenderBasePassParams& params)

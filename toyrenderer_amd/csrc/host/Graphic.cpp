@@ -3,6 +3,7 @@
 #include <unordered_map>
 
 #include "Graphic.h"
+#include "TextureFeedbackManager.h"
 
 #include <algorithm>
 
@@ -94,6 +95,16 @@ uint32_t Graphic::CreateMaterialTexture(uint32_t width, uint32_t height, uint32_
     if (bytes != need) throw nvrhi::Error("material texture: " + std::to_string(mips) + " mips of " + std::to_string(width) + " x " + std::to_string(height) + " are " + std::to_string(need) + " bytes, got " + std::to_string(bytes));
     if (m_Textures.size() >= kMaxMaterialTextures) throw nvrhi::Error("material texture: the descriptor table is full");
     if (!m_SrvUavCbvDescriptorTable) m_SrvUavCbvDescriptorTable = m_NVRHIDevice->createDescriptorTable(kMaxMaterialTextures);
+    const uint32_t index = (uint32_t)m_Textures.size();
+    if (g_TextureFeedbackManager.m_bEnabled) {                                // a streamable texture: tail only, its maps beside it (TextureFeedbackManager.h)
+        nvrhi::TextureHandle streamed;
+        if (g_TextureFeedbackManager.AddTexture(m_NVRHIDevice, m_SrvUavCbvDescriptorTable, kMaxMaterialTextures, index, width, height, mips, format, blockBytes,
+                                                (const uint8_t*)data, streamed)) {
+            m_NVRHIDevice->writeDescriptorTable(m_SrvUavCbvDescriptorTable, index, streamed);
+            m_Textures.push_back(streamed);
+            return index;
+        }
+    }
     nvrhi::TextureDesc d;
     d.width = width; d.height = height; d.mipLevels = mips; d.format = format;
     d.debugName = "Material Texture " + std::to_string(m_Textures.size());
@@ -105,7 +116,6 @@ uint32_t Graphic::CreateMaterialTexture(uint32_t width, uint32_t height, uint32_
         nvrhi::throwIfFailed(trhip_texture_upload(t->native(), k, p, n), "material texture upload");
         p += n;
     }
-    const uint32_t index = (uint32_t)m_Textures.size();
     m_NVRHIDevice->writeDescriptorTable(m_SrvUavCbvDescriptorTable, index, t);
     m_Textures.push_back(t);
     return index;
@@ -129,6 +139,7 @@ void Graphic::Shutdown()
     m_GlobalIndexBuffer = nullptr;                                            // Scene::LoadRaytracing's: left behind, the next session would release it after its device
     m_GlobalMaterialDataBuffer = nullptr;
     m_SrvUavCbvDescriptorTable = nullptr;
+    g_TextureFeedbackManager.Shutdown();
     m_Textures.clear();
     m_bAnyMaterialTextured = false;
     m_PendingCommandLists.clear();

@@ -1,5 +1,6 @@
 // Scene.cpp -- see Scene.h.  Cites are to the reference's source/Scene.cpp.
 #include "Scene.h"
+#include "TextureFeedbackManager.h"
 
 #include <cstdio>
 #include <stdexcept>
@@ -247,18 +248,31 @@ void Scene::LoadRaytracing(const uint32_t* indices, uint64_t numIndices, const u
 
 void Scene::LoadMaterials(const void* materials, uint32_t numMaterials)
 {
-    // a textured material: every flagged slot names a loaded texture (trhost_create_material_texture) and no streaming textures
-    const interop::MaterialData* m = (const interop::MaterialData*)materials;
+    // a textured material: every flagged slot names a loaded texture (trhost_create_material_texture); the two map indices are
+    // 0xFFFFFFFF, or -- with streaming on -- name the maps of that very texture, and are filled in for a streamed texture that names none
+    std::vector<interop::MaterialData> filled((const interop::MaterialData*)materials, (const interop::MaterialData*)materials + numMaterials);
+    interop::MaterialData* m = filled.data();
+    materials = filled.data();
     bool anyTextured = false;
     for (uint32_t i = 0; i < numMaterials; ++i) {
-        const interop::TextureData* slots = &m[i].m_AlbedoTexture;
+        interop::TextureData* slots = &m[i].m_AlbedoTexture;
         for (uint32_t c = 0; c < 4; ++c) {
             if (!(m[i].m_MaterialFlags & (1u << c))) continue;
             if (slots[c].m_DescriptorIndex >= g_Graphic.m_Textures.size())
                 throw std::runtime_error("materials: material " + std::to_string(i) + " uses a texture (m_MaterialFlags bit " + std::to_string(c) + ", m_DescriptorIndex " +
                                          std::to_string(slots[c].m_DescriptorIndex) + ") that is not loaded: " + std::to_string(g_Graphic.m_Textures.size()) + " material textures");
-            if (slots[c].m_FeedbackTextureDescriptorIndex != 0xFFFFFFFFu || slots[c].m_MinMapTextureDescriptorIndex != 0xFFFFFFFFu)
-                throw std::runtime_error("materials: material " + std::to_string(i) + " names a sampler-feedback or min-mip texture: texture streaming is not supported");
+            const TextureFeedbackManager::Streamed* streamed = g_TextureFeedbackManager.m_bEnabled ? g_TextureFeedbackManager.Find(slots[c].m_DescriptorIndex) : nullptr;
+            const uint32_t fb = slots[c].m_FeedbackTextureDescriptorIndex, mm = slots[c].m_MinMapTextureDescriptorIndex;
+            if (!streamed && (fb != 0xFFFFFFFFu || mm != 0xFFFFFFFFu))
+                throw std::runtime_error("materials: material " + std::to_string(i) + " names a sampler-feedback or min-mip texture, and its texture is not streamed: texture streaming is "
+                                         "on for textures created after trhost_set_texture_streaming only");
+            if (streamed) {
+                if ((fb != 0xFFFFFFFFu && fb != streamed->m_FeedbackIndex) || (mm != 0xFFFFFFFFu && mm != streamed->m_MinMipIndex))
+                    throw std::runtime_error("materials: material " + std::to_string(i) + " names a sampler-feedback or min-mip index that is not the map of its own texture " +
+                                             std::to_string(slots[c].m_DescriptorIndex));
+                slots[c].m_FeedbackTextureDescriptorIndex = streamed->m_FeedbackIndex;
+                slots[c].m_MinMapTextureDescriptorIndex = streamed->m_MinMipIndex;
+            }
             anyTextured = true;
         }
     }

@@ -15,6 +15,8 @@
 #include "GraphicConstants.h"
 #include "RenderGraph.h"
 #include "Scene.h"
+#include "TextureFeedbackManager.h"
+#include "TextureResidency.h"
 #include "VisibilityOutputs.h"
 #include "../ShaderInterop.h"
 
@@ -195,7 +197,57 @@ int trhost_set_alpha_test(int enabled)
         if (enabled && !g_Scene->m_bRasterDepth)
             throw nvrhi::Error("trhost_set_alpha_test: the rasters are off (trhost_set_raster_depth, trhost_set_visibility_buffer or trhost_set_gbuffer first): the test runs in them");
         if (enabled && !g_Graphic.m_GlobalMaterialDataBuffer) throw nvrhi::Error("trhost_set_alpha_test: no materials (trhost_load_materials first)");
+        if (enabled && g_TextureFeedbackManager.m_bEnabled)
+            throw nvrhi::Error("trhost_set_alpha_test: texture streaming is on, and the alpha-tested rasters and the sun rays do not honour the min-mip map yet");
         g_Scene->m_bAlphaTest = enabled != 0;
+    });
+}
+
+int trhost_set_texture_streaming(int enable, uint32_t textures_per_frame, uint32_t evict_after, int poison)
+{
+    return guarded([&] {
+        check(g_Scene);
+        TextureFeedbackManager& m = g_TextureFeedbackManager;
+        if (enable && g_Scene->m_bAlphaTest)
+            throw nvrhi::Error("trhost_set_texture_streaming: alpha_test is on, and the alpha-tested rasters and the sun rays do not honour the min-mip map yet");
+        if (enable && (!textures_per_frame || !evict_after)) throw nvrhi::Error("trhost_set_texture_streaming: textures_per_frame and evict_after are at least 1");
+        if ((enable != 0) != m.m_bEnabled && !g_Graphic.m_Textures.empty() && (enable || !m.m_Textures.empty()))
+            throw nvrhi::Error("trhost_set_texture_streaming: material textures exist already; streaming is switched before the first trhost_create_material_texture");
+        m.m_bEnabled = enable != 0;
+        if (enable) { m.m_TexturesPerFrame = textures_per_frame; m.m_EvictAfter = evict_after; m.m_bPoison = poison != 0; }
+    });
+}
+
+int trhost_set_texture_streaming_region(uint32_t region_w, uint32_t region_h)
+{
+    return guarded([&] {
+        check(g_Scene);
+        auto pow2 = [](uint32_t v) { return v >= 4u && (v & (v - 1u)) == 0u; };
+        if ((region_w || region_h) && (!pow2(region_w) || !pow2(region_h))) throw nvrhi::Error("trhost_set_texture_streaming_region: the sides of a region are powers of two, at least 4 (0 x 0: the format's default)");
+        g_TextureFeedbackManager.m_RegionW = region_w; g_TextureFeedbackManager.m_RegionH = region_h;
+    });
+}
+
+int trhost_get_texture_streaming_stats(uint64_t stats[5])
+{
+    return guarded([&] {
+        check(g_Scene && stats);
+        const TextureFeedbackManager::Stats& s = g_TextureFeedbackManager.m_Stats;
+        stats[0] = s.tilesTotal; stats[1] = s.tilesResident; stats[2] = s.tilesUploaded; stats[3] = s.bytesUploaded; stats[4] = s.texturesProcessed;
+    });
+}
+
+int trhost_download_min_mip(uint32_t texture, uint8_t* dst, uint64_t bytes, uint32_t* regions_x, uint32_t* regions_y)
+{
+    return guarded([&] {
+        check(g_Scene);
+        const TextureFeedbackManager::Streamed* s = g_TextureFeedbackManager.Find(texture);
+        if (!s) throw nvrhi::Error("trhost_download_min_mip: texture " + std::to_string(texture) + " is not streamed");
+        if (regions_x) *regions_x = s->m_Tiled.regionsX();
+        if (regions_y) *regions_y = s->m_Tiled.regionsY();
+        if (!dst) return;
+        if (bytes != s->m_MinMipBytes.size()) throw nvrhi::Error("trhost_download_min_mip: the map is " + std::to_string(s->m_MinMipBytes.size()) + " bytes, got " + std::to_string(bytes));
+        nvrhi::throwIfFailed(trhip_texture_download(s->m_MinMip->native(), 0, dst, bytes), "trhost_download_min_mip");
     });
 }
 
@@ -1196,6 +1248,50 @@ int trhost_renderer_times(const char* renderer_name, float* cpu_ms, float* gpu_m
                 return;
             }
         throw nvrhi::Error(std::string("unknown renderer ") + renderer_name);
+    });
+}
+
+static residency::Tiled tiledOf(uint32_t width, uint32_t height, uint32_t mips, uint32_t region_w, uint32_t region_h, uint32_t tile_bytes)
+{
+    auto pow2 = [](uint32_t v) { return v >= 4u && (v & (v - 1u)) == 0u; };
+    if (!width || !height || !mips || mips > 16u) throw nvrhi::Error("residency: a texture has a size and 1 .. 16 mips");
+    if (!pow2(region_w) || !pow2(region_h)) throw nvrhi::Error("residency: the sides of a region are powers of two, at least 4");
+    if (width % region_w || height % region_h) throw nvrhi::Error("residency: the texture's size is not a multiple of the region: the texture is not tiled");
+    residency::Tiled t;
+    t.width = width; t.height = height; t.mips = mips; t.regionW = region_w; t.regionH = region_h; t.tileBytes = tile_bytes;
+    return t;
+}
+
+int trhost_residency_tiles(uint32_t width, uint32_t height, uint32_t mips, uint32_t region_w, uint32_t region_h, uint32_t* standard_levels, uint32_t* num_tiles)
+{
+    return guarded([&] {
+        const residency::Tiled t = tiledOf(width, height, mips, region_w, region_h, 0);
+        if (standard_levels) *standard_levels = t.standardLevels();
+        if (num_tiles) *num_tiles = t.tileOffset(t.standardLevels());
+    });
+}
+
+int trhost_residency_round(uint32_t width, uint32_t height, uint32_t mips, uint32_t region_w, uint32_t region_h, uint32_t tile_bytes,
+                           const uint8_t* feedback, uint32_t evict_after, uint32_t num_tiles, uint8_t* resident, uint32_t* idle,
+                           uint8_t* mapped, uint8_t* unmapped, uint8_t* min_mip, uint64_t stats[5])
+{
+    return guarded([&] {
+        const residency::Tiled t = tiledOf(width, height, mips, region_w, region_h, tile_bytes);
+        const uint32_t total = t.tileOffset(t.standardLevels());
+        if (num_tiles != total) throw nvrhi::Error("residency: the per-tile arrays hold " + std::to_string(num_tiles) + " tiles, the texture has " + std::to_string(total));
+        if (!feedback || !min_mip || !stats || (total && (!resident || !idle))) throw nvrhi::Error("residency: null argument");
+        if (!evict_after) throw nvrhi::Error("residency: evict_after is at least 1");
+        residency::State state;
+        state.resident.assign(resident, resident + total);
+        state.idle.assign(idle, idle + total);
+        std::vector<uint32_t> in, out;
+        const residency::Stats s = residency::round(t, feedback, evict_after, state, in, out);
+        std::copy(state.resident.begin(), state.resident.end(), resident);
+        std::copy(state.idle.begin(), state.idle.end(), idle);
+        if (mapped) { std::fill(mapped, mapped + total, 0); for (uint32_t i : in) mapped[i] = 1; }
+        if (unmapped) { std::fill(unmapped, unmapped + total, 0); for (uint32_t i : out) unmapped[i] = 1; }
+        residency::minMip(t, state, min_mip);
+        stats[0] = s.tilesTotal; stats[1] = s.tilesResident; stats[2] = s.tilesMapped; stats[3] = s.tilesUnmapped; stats[4] = s.bytesUploaded;
     });
 }
 

@@ -7,9 +7,12 @@
 // words are those of "basepass_PS_Main_motion" (k_motion.hip).  There is no GBufferA-only variant: nothing would call it.
 //
 // The kernel is the GBUFFER = true instantiation of the resolve in visibility_resolve.hip.h; the convention is stated
-// there, restated in tests/gbuffer_ref.c, tests/material_textures_ref.c and in DESIGN.md 3.  Sampler feedback and min-mip streaming
-// are out of scope.  ALPHA_MASK_MODE's discard is not this kernel's: it changes depth, so it runs in the rasters
-// (k_raster.hip, the ALPHA_MASK_MODE=1 shader names); the resolve shades whatever texels they left.
+// there, restated in tests/gbuffer_ref.c, tests/material_textures_ref.c and in DESIGN.md 3.  With a min-mip or feedback map in the table
+// the STREAMED instantiation runs (#streamed; material_textures.hip.h, tests/texture_streaming_ref.c, DESIGN.md 12, twentieth amendment):
+// 128 VGPRs, 64 bytes of scratch per lane, 4 waves per SIMD; the four samples are taken by one rolled loop so that the sampler with
+// its marks exists once in the code object.  #main and #textured are instruction for instruction what they were before it.
+// ALPHA_MASK_MODE's discard is not this kernel's: it changes depth, so it runs in the rasters (k_raster.hip, the ALPHA_MASK_MODE=1
+// shader names); the resolve shades whatever texels they left.
 //
 // Cost: on top of the motion resolve the addition has to move 16 B per pixel stored (133 MB at 3840x2160), 24 B of
 // material per covered pixel (lines shared by a wave's pixels) and three 4-byte normals from vertex records that are

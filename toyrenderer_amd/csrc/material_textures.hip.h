@@ -1,7 +1,7 @@
 // material_textures.hip.h -- the texture table (the stand-in of ResourceDescriptorHeap[...]) and the software sampler of
 // SampleMaterialValue (lightingcommon.hlsli:340-406), for the TEXTURED instantiation of the resolve (visibility_resolve.hip.h).
-// Only the `Sample` branch with minMip = 0 is reachable from the base pass: no min-mip texture, no sampler feedback, no
-// SampleLevel / SampleGrad overrides (they stay out with texture streaming).  The samplers are the reference's 16x
+// `sample` is the `Sample` branch with minMip = 0; `sampleStreamed` (below, "texture streaming") adds the min-mip clamp and the feedback
+// marks for the STREAMED instantiation.  No SampleLevel / SampleGrad overrides.  The samplers are the reference's 16x
 // anisotropic wrap and clamp samplers (CommonResources.cpp:292-293), selected by m_IsWrapSampler.
 //
 // CONVENTION (restated in tests/material_textures_ref.c).  For a texture of W x H texels at mip 0 and `mips` levels,
@@ -250,6 +250,155 @@ __device__ __forceinline__ cm::F3 sample(const TableEntry& e, const float* lds, 
         acc.z = acc.z + lerp_(b0.z, b1.z, f);
     }
     return { acc.x / fN, acc.y / fN, acc.z / fN };
+}
+
+// ---- texture streaming: the min-mip clamp and the feedback marks (the STREAMED instantiation of the resolve) -----------------------
+// CONVENTION (restated in tests/texture_streaming_ref.c).  A streamable texture has a region of 2^sx x 2^sy texels of
+// mip 0 (TableEntry::pad); region (rx, ry) is word or byte ry * (W >> sx) + rx of a map.
+//   point     : the mip-0 texel under u on an axis of `dim` texels: t0 = floor(u * (float)dim); clamp: (uint)fmin(fmax(t0, 0), dim - 1)
+//               (a NaN gives 0); wrap: (int)fmin(fmax(t0, -2^30), 2^30) mod dim, floored.  The region under uv is (point(u) >> sx,
+//               point(v) >> sy): PointWrap / PointClampMaxReductionSampler on a map of one texel per region.
+//   clamp     : with lodWanted = `sample`'s clamped lod and minMip the byte of the region under uv, lod = fmin(fmax(lodWanted,
+//               (float)minMip), mips - 1); l0, l1 and f come from this lod; N and the tap positions are `sample`'s (they come from the
+//               footprint).  Without a map lod = lodWanted: `sample` itself.
+//   feedback  : (WriteSamplerFeedback; the project's own statement, D3D's is implementation-defined.)  l0w = floor(lodWanted), l1w =
+//               min(l0w + 1, mips - 1).  The region under uv is marked with l0w.  For every tap, each of the four texels (columns i0,
+//               i1 x rows i0, i1) of the level-l0w footprint marks the region of its mip-0 origin, ((x << l0w) >> sx, (y << l0w) >> sy),
+//               with l0w, and each of the four of the level-l1w footprint marks its region with l1w.  A mark is word = min(word, level).
+//               The footprints are those of the UNCLAMPED levels: feedback does not depend on residency.  No texel is fetched for it.
+// THE WRITE.  Marking as stated is up to 1 + 16 x 8 atomics per sample, nearly all of them to one or two words, from 64 lanes that
+// mostly look at the same regions.  min is idempotent and order-independent, so marks may be dropped and merged freely: a lane drops
+// a mark that repeats a region of the same footprint or that its last mark already covers (same word, level not lower); what is left
+// is merged across the wave before the atomic goes out: the first lane still to be served issues the one atomic for all the lanes that
+// hold its (word, level), until no lane is left: one atomic per wave and distinct (word, level).  -DTRHIP_FEEDBACK_NAIVE builds the per-mark atomic, for tools/texture_streaming_cost.py.
+struct Stream
+{
+    const uint8_t* minMip;                     // the slot's min-mip map, or nullptr
+    uint32_t* feedback;                        // the slot's feedback map when feedback is written, or nullptr
+    uint32_t shiftX, shiftY, regionsX;
+};
+
+__device__ __forceinline__ uint32_t pointOf(float u, uint32_t dim, bool wrap)
+{
+    const float t0 = __builtin_floorf(u * (float)dim);
+    if (!wrap) return (uint32_t)cm::min_(cm::max_(t0, 0.0f), (float)(dim - 1u));
+    const int i = (int)cm::min_(cm::max_(t0, -0x1p30f), 0x1p30f);
+    int r;
+    if ((dim & (dim - 1u)) == 0u) r = i & (int)(dim - 1u);
+    else { r = i % (int)dim; if (r < 0) r += (int)dim; }
+    return (uint32_t)r;
+}
+
+__device__ __forceinline__ uint32_t regionUnder(const TableEntry& e, const Stream& st, bool wrap, float u, float v)
+{
+    return (pointOf(v, e.height, wrap) >> st.shiftY) * st.regionsX + (pointOf(u, e.width, wrap) >> st.shiftX);
+}
+
+// one atomic per distinct (word, level) among the lanes that call it together
+__device__ __forceinline__ void emitMark(uint32_t* words, uint32_t index, uint32_t level)
+{
+#ifdef TRHIP_FEEDBACK_NAIVE
+    atomicMin(words + index, level);
+#else
+    // A loop over a wave-uniform mask of the lanes still to be served, which every calling lane runs to its end: the loop that each
+    // lane leaves as soon as it matches the first active lane is folded by the compiler into "the first lane alone" (seen in the
+    // assembly), which loses marks.
+    uint32_t* p = words + index;
+    const uint32_t lo = (uint32_t)(uintptr_t)p, hi = (uint32_t)((uintptr_t)p >> 32), lane = __lane_id();
+    uint64_t todo = __builtin_amdgcn_ballot_w64(true);
+    while (todo) {
+        const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
+        const bool same = (lo == (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)leader)) & (hi == (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)leader)) &
+                          (level == (uint32_t)__builtin_amdgcn_readlane((int)level, (int)leader));
+        if (lane == leader) atomicMin(p, level);
+        todo &= ~__builtin_amdgcn_ballot_w64(same);
+    }
+#endif
+}
+
+struct Marker
+{
+    uint32_t* words; uint32_t lastIndex, lastLevel;
+    __device__ __forceinline__ void mark(uint32_t index, uint32_t level)
+    {
+#ifndef TRHIP_FEEDBACK_NAIVE
+        if (index == lastIndex && level >= lastLevel) return;                           // the last mark covers it
+#endif
+        emitMark(words, index, level);
+        lastIndex = index; lastLevel = level;
+    }
+    // the four texels of a footprint of level f.level
+    __device__ __forceinline__ void markFootprint(const Stream& st, const Footprint& f)
+    {
+        const uint32_t rx0 = (f.x.i0 << f.level) >> st.shiftX, rx1 = (f.x.i1 << f.level) >> st.shiftX;
+        const uint32_t r0 = ((f.y.i0 << f.level) >> st.shiftY) * st.regionsX, r1 = ((f.y.i1 << f.level) >> st.shiftY) * st.regionsX;
+#ifdef TRHIP_FEEDBACK_NAIVE
+        mark(r0 + rx0, f.level); mark(r0 + rx1, f.level); mark(r1 + rx0, f.level); mark(r1 + rx1, f.level);
+#else
+        mark(r0 + rx0, f.level);
+        if (rx1 != rx0) mark(r0 + rx1, f.level);
+        if (r1 != r0) {
+            mark(r1 + rx0, f.level);
+            if (rx1 != rx0) mark(r1 + rx1, f.level);
+        }
+#endif
+    }
+};
+
+// SampleMaterialValue(...).rgb with a min-mip map and / or a feedback map.  minMipOut: the byte read (0 without a map).
+__device__ __forceinline__ cm::F3 sampleStreamed(const TableEntry& e, const Stream& st, const float* lds, bool wrap, float u, float v, float dudx, float dvdx, float dudy, float dvdy,
+                                                 uint32_t& minMipOut)
+{
+    const float W = (float)e.width, H = (float)e.height;
+    const float ax = dudx * W, ay = dvdx * H, bx = dudy * W, by = dvdy * H;
+    const float lenA = cm::sqrt_(cm::fma_(ay, ay, ax * ax)), lenB = cm::sqrt_(cm::fma_(by, by, bx * bx));
+    const bool aMajor = lenA >= lenB;
+    const float pmax = aMajor ? lenA : lenB, pmin = aMajor ? lenB : lenA;
+    const float mu = aMajor ? dudx : dudy, mv = aMajor ? dvdx : dvdy;
+    const float n = __builtin_ceilf(pmax / pmin);
+    const uint32_t N = n <= 16.0f ? (uint32_t)n : 16u;
+    const float fN = (float)N, x = pmax / fN, top = (float)(e.mips - 1u);
+    const float lodWanted = cm::min_(cm::max_(x > 0.0f ? softmath::log2Soft(x) : 0.0f, 0.0f), top);
+    const bool mapped = st.minMip || st.feedback;
+    const uint32_t under = mapped ? regionUnder(e, st, wrap, u, v) : 0u;
+    const uint32_t minMip = st.minMip ? st.minMip[under] : 0u;
+    minMipOut = minMip;
+    const float lod = cm::min_(cm::max_(lodWanted, (float)minMip), top);
+    const float l0f = __builtin_floorf(lod), f = lod - l0f;
+    const uint32_t l0 = (uint32_t)l0f, l1 = l0 + 1u < e.mips ? l0 + 1u : e.mips - 1u;
+    const uint32_t l0w = (uint32_t)__builtin_floorf(lodWanted), l1w = l0w + 1u < e.mips ? l0w + 1u : e.mips - 1u;
+    Marker marker = { st.feedback, 0xFFFFFFFFu, 0u };
+    if (st.feedback) marker.mark(under, l0w);
+    const float* rgbTable = lds + (srgbDecoded(e.format) ? 0u : 256u);
+    const bool blocks = blockCompressed(e.format);
+    cm::F3 acc = { 0.0f, 0.0f, 0.0f };
+#pragma unroll 1
+    for (uint32_t i = 0; i < N; ++i) {
+        const float k = ((float)i + 0.5f) / fN - 0.5f;
+        const float tu = u + mu * k, tv = v + mv * k;
+        const Footprint f0 = footprintOf(e, l0, wrap, tu, tv), f1 = footprintOf(e, l1, wrap, tu, tv);
+        Quad q0, q1;
+        fetchQuads(e, blocks, f0, f1, q0, q1);
+        if (st.feedback) {                                                              // address arithmetic only, while the texels are in flight
+            marker.markFootprint(st, l0w == l0 ? f0 : footprintOf(e, l0w, wrap, tu, tv));
+            marker.markFootprint(st, l1w == l1 ? f1 : l1w == l0 ? f0 : footprintOf(e, l1w, wrap, tu, tv));
+        }
+        const cm::F3 b0 = bilinear(q0, f0, rgbTable), b1 = bilinear(q1, f1, rgbTable);
+        acc.x = acc.x + lerp_(b0.x, b1.x, f);
+        acc.y = acc.y + lerp_(b0.y, b1.y, f);
+        acc.z = acc.z + lerp_(b0.z, b1.z, f);
+    }
+    return { acc.x / fN, acc.y / fN, acc.z / fN };
+}
+
+// kMipColors (toyrenderer_common.hlsli:9-28): albedo of m_bVisualizeMinMipTilesOnAlbedoOutput, by min(minMip, 15)
+__device__ __forceinline__ cm::F3 mipColour(uint32_t minMip)
+{
+    static constexpr float c[16][3] = { { 1.0f, 1.0f, 1.0f }, { 1.0f, 0.25f, 0.25f }, { 0.25f, 1.0f, 0.25f }, { 0.25f, 0.25f, 1.0f }, { 1.0f, 0.25f, 1.0f }, { 1.0f, 1.0f, 0.25f },
+                                        { 0.25f, 1.0f, 1.0f }, { 0.9f, 0.5f, 0.2f }, { 0.59f, 0.48f, 0.8f }, { 0.53f, 0.25f, 0.11f }, { 0.8f, 0.48f, 0.53f }, { 0.64f, 0.8f, 0.48f },
+                                        { 0.48f, 0.75f, 0.8f }, { 0.5f, 0.25f, 0.75f }, { 0.99f, 0.68f, 0.42f }, { 0.4f, 0.5f, 0.6f } };
+    const uint32_t i = minMip < 15u ? minMip : 15u;
+    return { c[i][0], c[i][1], c[i][2] };
 }
 
 // ---- the alpha channel (see ALPHA above) --------------------------------------------------------------------------------------

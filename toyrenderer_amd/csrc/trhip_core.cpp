@@ -246,6 +246,15 @@ __global__ __launch_bounds__(256) void multiClearKernel(ClearKernelArgs a)
         for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < a.words[k]; i += stride) p[i] = v;
     }
 }
+
+// trhip_cmd_decode_sampler_feedback: one byte per region, the level the region was asked for at, 0xFF = never sampled
+__global__ __launch_bounds__(256) void decodeFeedbackKernel(const uint32_t* words, uint8_t* out, uint32_t regions)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= regions) return;
+    const uint32_t w = words[i];
+    out[i] = (uint8_t)(w < 0xFFu ? w : 0xFFu);
+}
 }
 
 int trhip_cmdlist_t::recordClearWords(void* ptr, uint64_t words, uint32_t value, bool fresh)
@@ -591,6 +600,7 @@ void trhip_texture_release(trhip_texture t)
         if (t->owns && t->ptr) { (void)hipSetDevice(t->dev->index); (void)hipFree(t->ptr); }
         trhip::freeDerived(t->dev, { &t->quad });
         if (t->heap) trhip_heap_release(t->heap);
+        if (t->paired) trhip_texture_release(t->paired);
         delete t;
     }
 }
@@ -758,9 +768,13 @@ static int tableWrite(trhip_texture_table_t* t, uint32_t index, trhip_texture_t*
         e.base = (const uint32_t*)tex->ptr;
         e.width = tex->width; e.height = tex->height; e.mips = tex->mips; e.format = tex->format;
         for (uint32_t k = 0; k < tex->mips; ++k) e.mipOffset[k] = (uint32_t)(tex->mipOffset[k] / 4u);
+        e.pad[0] = tex->regionShiftX; e.pad[1] = tex->regionShiftY;            // a streamable texture's, or its feedback map's
     }
     int rc = syncCopy(t->dev, (char*)t->entries.ptr + (uint64_t)index * sizeof e, &e, sizeof e, hipMemcpyHostToDevice);   // drains the device: nothing in flight reads the old entry
     if (rc != TRHIP_OK) return rc;
+    auto streams = [](const trhip_texture_t* x) { return x && (x->format == TRHIP_FORMAT_R8_UINT || x->format == TRHIP_SAMPLER_FEEDBACK_FORMAT) ? 1u : 0u; };
+    t->streamEntries += streams(tex);
+    t->streamEntries -= streams(t->slots[index]);
     trhip_texture_retain(tex);
     trhip_texture_release(t->slots[index]);
     t->slots[index] = tex;
@@ -783,6 +797,63 @@ int trhip_texture_table_clear(trhip_texture_table t, uint32_t index)
     if (!t) return fail(TRHIP_ERR_INVALID, "texture_table_clear: null argument");
     if (index >= t->slots.size()) return fail(TRHIP_ERR_INVALID, "texture_table_clear: index %u at or past the capacity %zu", index, t->slots.size());
     return tableWrite(t, index, nullptr);
+}
+
+// ---- texture streaming (include/trhip.h) -----------------------------------------------------------
+static bool materialTexture(const trhip_texture_t* t)
+{
+    return (t->format == TRHIP_FORMAT_RGBA8_UNORM || t->format == TRHIP_FORMAT_SRGBA8_UNORM || t->blockBytes) && !t->isUAV && !t->arraySize;
+}
+
+int trhip_texture_set_streaming_region(trhip_texture tex, uint32_t rw, uint32_t rh)
+{
+    if (!tex) return fail(TRHIP_ERR_INVALID, "texture_set_streaming_region: null argument");
+    if (!materialTexture(tex)) return fail(TRHIP_ERR_INVALID, "texture_set_streaming_region(%s): format %u; a streamable texture is a sampled RGBA8_UNORM, SRGBA8_UNORM or block-compressed texture", tex->name.c_str(), tex->format);
+    if (rw == 0 && rh == 0) {                                       // D3D's 64 KB tile shapes
+        if (!tex->blockBytes) rw = rh = 128;
+        else if (tex->blockBytes == 8) { rw = 512; rh = 256; }
+        else rw = rh = 256;
+    }
+    auto pow2 = [](uint32_t v) { return v >= 4u && (v & (v - 1u)) == 0u; };
+    if (!pow2(rw) || !pow2(rh)) return fail(TRHIP_ERR_INVALID, "texture_set_streaming_region(%s): region %u x %u; both sides are powers of two, at least 4", tex->name.c_str(), rw, rh);
+    if (tex->width % rw || tex->height % rh)
+        return fail(TRHIP_ERR_INVALID, "texture_set_streaming_region(%s): %u x %u texels are not a multiple of the region %u x %u: the texture is not tiled and stays fully resident",
+                    tex->name.c_str(), tex->width, tex->height, rw, rh);
+    tex->regionShiftX = (uint32_t)__builtin_ctz(rw);
+    tex->regionShiftY = (uint32_t)__builtin_ctz(rh);
+    return TRHIP_OK;
+}
+
+int trhip_texture_streaming_region(trhip_texture tex, uint32_t* rw, uint32_t* rh)
+{
+    if (!tex) return fail(TRHIP_ERR_INVALID, "texture_streaming_region: null argument");
+    const trhip_texture_t* t = tex->paired ? tex->paired : tex;
+    if (rw) *rw = t->regionShiftX ? 1u << t->regionShiftX : 0u;
+    if (rh) *rh = t->regionShiftY ? 1u << t->regionShiftY : 0u;
+    return TRHIP_OK;
+}
+
+int trhip_sampler_feedback_create(trhip_device dev, trhip_texture paired, const char* debugName, trhip_texture* out)
+{
+    if (!dev || !paired || !out) return fail(TRHIP_ERR_INVALID, "sampler_feedback_create: null argument");
+    if (paired->dev != dev) return fail(TRHIP_ERR_INVALID, "sampler_feedback_create(%s): the texture belongs to another device", paired->name.c_str());
+    if (!paired->regionShiftX) return fail(TRHIP_ERR_INVALID, "sampler_feedback_create(%s): the texture is not streamable (trhip_texture_set_streaming_region)", paired->name.c_str());
+    auto t = std::make_unique<trhip_texture_t>();
+    t->dev = dev;
+    t->width = paired->width >> paired->regionShiftX; t->height = paired->height >> paired->regionShiftY;
+    t->mips = 1; t->format = TRHIP_SAMPLER_FEEDBACK_FORMAT; t->texelBytes = 4;
+    t->regionShiftX = paired->regionShiftX; t->regionShiftY = paired->regionShiftY;
+    t->name = debugName ? debugName : "";                            // no UAV bit: only the #streamed resolve writes it, through the table
+    t->totalBytes = (t->mipBytes(0) + 255) & ~uint64_t(255);
+    TRHIP_HIP(hipSetDevice(dev->index));
+    TRHIP_HIP(hipMalloc(&t->ptr, (size_t)t->totalBytes));
+    t->owns = true;
+    hipError_t e = hipMemset(t->ptr, 0xFF, (size_t)t->totalBytes);                // never sampled
+    if (e != hipSuccess) { (void)hipFree(t->ptr); return hipfail(e, "hipMemset(sampler feedback)"); }
+    trhip_texture_retain(paired);
+    t->paired = paired;
+    *out = t.release();
+    return TRHIP_OK;
 }
 
 // ---- command lists -------------------------------------------------------------------------------
@@ -1068,7 +1139,7 @@ static int recordDispatch(trhip_cmdlist cl, const char* name, const trhip_bindin
                             name, b[i].slot);
             trhip_texture_table_retain(t);
             cl->heldTables.push_back(t);
-            for (trhip_texture_t* e : t->slots) cl->hold(e, false);
+            for (trhip_texture_t* e : t->slots) cl->hold(e, e && e->format == TRHIP_SAMPLER_FEEDBACK_FORMAT);   // deliberately broad: only the #streamed resolve writes a feedback map, but every shader that binds the table holds it as written (conservative for the fork rule, and the rasters and the sun rays run beside nothing that reads one)
             break; }
         case TRHIP_BIND_PUSH_CONSTANTS: case TRHIP_BIND_SAMPLER: break;
         default: return fail(TRHIP_ERR_INVALID, "dispatch(%s): binding %u has unknown type %u", name, i, b[i].type);
@@ -1452,6 +1523,77 @@ int trhip_cmd_copy_to_readback(trhip_cmdlist cl, trhip_readback rb, uint32_t slo
         rb->written[slot] = bytes;
         return (int)TRHIP_OK; } });
     cl->ops.back().kind = "copy_to_readback";
+    return TRHIP_OK;
+}
+
+int trhip_readback_poll(trhip_readback rb, uint32_t slot, int* ready)
+{
+    if (!rb || !ready) return fail(TRHIP_ERR_INVALID, "readback_poll: null argument");
+    if (slot >= rb->done.size()) return fail(TRHIP_ERR_INVALID, "readback_poll: slot %u of %zu", slot, rb->done.size());
+    *ready = 1;
+    if (!rb->written[slot]) return TRHIP_OK;
+    TRHIP_HIP(hipSetDevice(rb->dev->index));
+    const hipError_t e = hipEventQuery(rb->done[slot]);
+    if (e == hipErrorNotReady) { *ready = 0; return TRHIP_OK; }
+    return e == hipSuccess ? TRHIP_OK : hipfail(e, "hipEventQuery");
+}
+
+// ---- texture streaming: commands (include/trhip.h) ---------------------------------------------------
+int trhip_cmd_clear_sampler_feedback(trhip_cmdlist cl, trhip_texture fb)
+{
+    TRHIP_RECORDING(cl);
+    if (!fb || fb->format != TRHIP_SAMPLER_FEEDBACK_FORMAT) return fail(TRHIP_ERR_INVALID, "clear_sampler_feedback: needs a feedback map (trhip_sampler_feedback_create)");
+    void* p = fb->ptr;
+    const size_t n = (size_t)fb->width * fb->height;
+    cl->hold(fb, true);
+    cl->ops.push_back({ "", [p, n](hipStream_t s) { TRHIP_HIP(hipMemsetD32Async((hipDeviceptr_t)p, (int)0xFFFFFFFFu, n, s)); return (int)TRHIP_OK; } });
+    cl->ops.back().kind = "clear_texture";
+    return TRHIP_OK;
+}
+
+int trhip_cmd_decode_sampler_feedback(trhip_cmdlist cl, trhip_buffer dst, uint64_t dstOff, trhip_texture fb)
+{
+    TRHIP_RECORDING(cl);
+    if (!dst || !fb || fb->format != TRHIP_SAMPLER_FEEDBACK_FORMAT) return fail(TRHIP_ERR_INVALID, "decode_sampler_feedback: needs a buffer and a feedback map (trhip_sampler_feedback_create)");
+    if (!dst->ptr) return fail(TRHIP_ERR_STATE, "decode_sampler_feedback(%s): no memory bound", dst->name.c_str());
+    const uint32_t regions = fb->width * fb->height;
+    if (dstOff > dst->byteSize || regions > dst->byteSize - dstOff)
+        return fail(TRHIP_ERR_INVALID, "decode_sampler_feedback(%s): %u regions at offset %llu exceed the buffer's %llu bytes", dst->name.c_str(), regions, (unsigned long long)dstOff, (unsigned long long)dst->byteSize);
+    const uint32_t* words = (const uint32_t*)fb->ptr;
+    uint8_t* out = (uint8_t*)dst->ptr + dstOff;
+    cl->hold(fb, false); cl->hold(dst, true);
+    cl->ops.push_back({ "decode_sampler_feedback", [words, out, regions](hipStream_t s) {
+        TRHIP_LAUNCH(decodeFeedbackKernel, dim3((regions + 255u) / 256u), dim3(256), 0, s, words, out, regions);
+        return trhip::launchStatus("decodeFeedbackKernel"); } });
+    return TRHIP_OK;
+}
+
+int trhip_cmd_write_texture_region(trhip_cmdlist cl, trhip_texture tex, uint32_t mip, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const void* src, uint64_t bytes)
+{
+    TRHIP_RECORDING(cl);
+    if (!tex || !src) return fail(TRHIP_ERR_INVALID, "write_texture_region: null argument");
+    const bool minMipMap = tex->format == TRHIP_FORMAT_R8_UINT && !tex->isUAV && !tex->arraySize;      // a min-mip map is rewritten the same way
+    if (!materialTexture(tex) && !minMipMap)
+        return fail(TRHIP_ERR_INVALID, "write_texture_region(%s): format %u; only a sampled RGBA8_UNORM, SRGBA8_UNORM or block-compressed texture, or an R8_UINT min-mip map without the UAV bit, is written by region", tex->name.c_str(), tex->format);
+    if (!tex->ptr) return fail(TRHIP_ERR_STATE, "write_texture_region(%s): no memory bound", tex->name.c_str());
+    if (mip >= tex->mips) return fail(TRHIP_ERR_INVALID, "write_texture_region(%s): mip %u of %u", tex->name.c_str(), mip, tex->mips);
+    const uint32_t mw = tex->mipW(mip), mh = tex->mipH(mip);
+    if (!w || !h || x >= mw || y >= mh || w > mw - x || h > mh - y)
+        return fail(TRHIP_ERR_INVALID, "write_texture_region(%s): %u x %u texels at (%u, %u) leave mip %u of %u x %u", tex->name.c_str(), w, h, x, y, mip, mw, mh);
+    const uint32_t bb = tex->blockBytes;
+    if (bb && ((x | y) & 3u || (w & 3u && x + w != mw) || (h & 3u && y + h != mh)))
+        return fail(TRHIP_ERR_INVALID, "write_texture_region(%s): %u x %u texels at (%u, %u): a block-compressed texture is written in whole 4 x 4 blocks", tex->name.c_str(), w, h, x, y);
+    const size_t tb = tex->texelBytes;
+    const size_t rowBytes = bb ? (size_t)((w + 3u) / 4u) * bb : (size_t)w * tb, rows = bb ? (h + 3u) / 4u : h;
+    const size_t pitch = bb ? (size_t)((mw + 3u) / 4u) * bb : (size_t)mw * tb;
+    if (bytes != rowBytes * rows) return fail(TRHIP_ERR_INVALID, "write_texture_region(%s): the rectangle is %zu bytes, got %llu", tex->name.c_str(), rowBytes * rows, (unsigned long long)bytes);
+    char* dst = (char*)tex->mipPtr(mip) + (bb ? (size_t)(y / 4u) * pitch + (size_t)(x / 4u) * bb : (size_t)y * pitch + (size_t)x * tb);
+    auto staged = std::make_shared<std::vector<uint8_t>>((const uint8_t*)src, (const uint8_t*)src + bytes);
+    cl->hold(tex, true);
+    cl->ops.push_back({ "", [staged, dst, pitch, rowBytes, rows](hipStream_t s) {
+        TRHIP_HIP(hipMemcpy2DAsync(dst, pitch, staged->data(), rowBytes, rowBytes, rows, hipMemcpyHostToDevice, s));
+        return (int)TRHIP_OK; } });
+    cl->ops.back().kind = "write_texture";
     return TRHIP_OK;
 }
 

@@ -176,6 +176,10 @@ struct trhip_texture_t
     // aligned).  0: not an array.  Only "deferredlighting_PS_Main" / "_Debug" take one, at t6..t8 (recordDispatch refuses the rest).
     uint32_t arraySize = 0;
     uint64_t slicePitch = 0;
+    // Texture streaming (include/trhip.h).  A streamable material texture: log2 of its region size (0: not streamable).  A feedback
+    // map (TRHIP_SAMPLER_FEEDBACK_FORMAT): `paired` is its material texture, retained; the shifts are that texture's.
+    uint32_t regionShiftX = 0, regionShiftY = 0;
+    trhip_texture_t* paired = nullptr;
     std::string name;
     uint64_t mipOffset[16] = {};
     uint64_t totalBytes = 0;
@@ -210,6 +214,7 @@ struct trhip_texture_table_t
     trhip_device_t* dev = nullptr;
     std::vector<trhip_texture_t*> slots;
     trhip::DerivedData entries;
+    uint32_t streamEntries = 0;                // min-mip (R8_UINT) and feedback entries among `slots`: nonzero selects the #streamed resolve
     std::atomic<int> rc{1};
 };
 

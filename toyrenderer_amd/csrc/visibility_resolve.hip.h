@@ -140,12 +140,41 @@ __device__ __forceinline__ cm::F3 normalize3(cm::F3 v)
     return { v.x / len, v.y / len, v.z / len };
 }
 
+// STREAMED: the maps of slot `s`, which samples table entry `t` (material_textures.hip.h).  false: an index that is not 0xFFFFFFFF and
+// names no map of a texture like `t`: past the table, empty, another format or size, or `t` is not streamable.  The sizes checked
+// here are what keeps every map access inside its allocation.
+__device__ __forceinline__ bool streamOf(const TexturedArgs& a, const TextureData& s, const mtex::TableEntry& t, mtex::Stream& st)
+{
+    st = { nullptr, nullptr, t.pad[0], t.pad[1], 0u };
+    const uint32_t mm = s.m_MinMapTextureDescriptorIndex, fb = s.m_FeedbackTextureDescriptorIndex;
+    if (mm == 0xFFFFFFFFu && fb == 0xFFFFFFFFu) return true;
+    if (!st.shiftX || !st.shiftY) return false;
+    const uint32_t rw = t.width >> st.shiftX, rh = t.height >> st.shiftY;
+    st.regionsX = rw;
+    if (mm != 0xFFFFFFFFu) {
+        if (mm >= a.tableCount) return false;
+        const mtex::TableEntry& m = a.table[mm];
+        if (!m.base || m.format != TRHIP_FORMAT_R8_UINT || m.width != rw || m.height != rh) return false;
+        st.minMip = reinterpret_cast<const uint8_t*>(m.base);
+    }
+    if (fb != 0xFFFFFFFFu) {
+        if (fb >= a.tableCount) return false;
+        const mtex::TableEntry& m = a.table[fb];
+        if (!m.base || m.format != TRHIP_SAMPLER_FEEDBACK_FORMAT || m.width != rw || m.height != rh || m.pad[0] != st.shiftX || m.pad[1] != st.shiftY) return false;
+        if (a.k.m_bWriteSamplerFeedback) st.feedback = const_cast<uint32_t*>(m.base);
+    }
+    return true;
+}
+
 // TEXTURED (with GBUFFER only): GetCommonGBufferParams with its four material textures; see the CONVENTION above.
-template <bool GBUFFER, bool TEXTURED = false>
+// STREAMED (with TEXTURED only): + the min-mip clamp, the feedback marks and the min-mip colours (material_textures.hip.h, "texture
+// streaming"); recorded only when the table holds a map, so the other two instantiations are what they were.
+template <bool GBUFFER, bool TEXTURED = false, bool STREAMED = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(TEXTURED ? kTexturedWaves : GBUFFER ? 8 : 1, TEXTURED ? kTexturedWaves : 8)))
 void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
 {
     static_assert(GBUFFER || !TEXTURED, "the motion resolve samples nothing");
+    static_assert(TEXTURED || !STREAMED, "streaming is the textured resolve's");
     const float* tables = nullptr;
     if constexpr (TEXTURED) {                                                            // before anyone leaves: a barrier inside
         __shared__ float lds[mtex::kLdsFloats];
@@ -176,6 +205,10 @@ void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
                 const uint32_t d = slots[c].m_DescriptorIndex;
                 if (d >= a.tableCount || !mtex::sampled(a.table[d])) return;             // past the table, empty, another format
                 tex[c] = a.table + d;
+                if constexpr (STREAMED) {
+                    mtex::Stream st;
+                    if (!streamOf(a, slots[c], a.table[d], st)) return;                  // a map index that names no map of this texture
+                }
             }
         }
         const cm::M43 Wm = cm::loadM43(inst.m_WorldMatrix), Pm = cm::loadM43(inst.m_PrevWorldMatrix);
@@ -251,9 +284,31 @@ void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
                 const MaterialData& m = *reinterpret_cast<const MaterialData*>(mat);
                 const TextureData* slots = &m.m_AlbedoTexture;
                 cm::F3 albedo = { 1.0f, 1.0f, 1.0f }, mr = { 0.0f, 1.0f, 0.0f }, emissive = { 1.0f, 1.0f, 1.0f }, shaded = normal;
-                if (tex[0]) albedo = mtex::sample(*tex[0], tables, slots[0].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                // SampleMaterialValue of slot c; STREAMED: through the slot's maps (checked above), the albedo slot's min-mip colour if asked for
+                // (STREAMED: the four samples are taken by one rolled loop, so that the sampler with its marks exists once in the code object.
+                // streamOf runs again here, its result known to be true from the check above: the kernel sits at its 128-VGPR bound, and
+                // holding 4 x 5 words of Stream across the interpolation costs more than two loads of a line the check just touched.)
+                cm::F3 streamed0 = albedo, streamed1 = albedo, streamed2 = albedo, streamed3 = albedo;
+                if constexpr (STREAMED) {
+#pragma unroll 1
+                    for (int c = 0; c < 4; ++c) {
+                        const mtex::TableEntry* t = c == 0 ? tex[0] : c == 1 ? tex[1] : c == 2 ? tex[2] : tex[3];
+                        if (!t) continue;
+                        mtex::Stream st;
+                        streamOf(a, slots[c], *t, st);
+                        uint32_t minMip;
+                        cm::F3 value = mtex::sampleStreamed(*t, st, tables, slots[c].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy, minMip);
+                        if (c == 0 && a.k.m_bVisualizeMinMipTilesOnAlbedoOutput && st.minMip) value = mtex::mipColour(minMip);
+                        if (c == 0) streamed0 = value; else if (c == 1) streamed1 = value; else if (c == 2) streamed2 = value; else streamed3 = value;
+                    }
+                }
+                auto sampleSlot = [&](int c) {
+                    if constexpr (STREAMED) return c == 0 ? streamed0 : c == 1 ? streamed1 : c == 2 ? streamed2 : streamed3;
+                    else return mtex::sample(*tex[c], tables, slots[c].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                };
+                if (tex[0]) albedo = sampleSlot(0);
                 if (tex[1]) {
-                    const cm::F3 ns = mtex::sample(*tex[1], tables, slots[1].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                    const cm::F3 ns = sampleSlot(1);
                     const float nx = 2.0f * ns.x - 1.0f, ny = 2.0f * ns.y - 1.0f;                   // TwoChannelNormalX2
                     const cm::F3 unpacked = { nx, ny, cm::sqrt_(1.0f - cm::fma_(ny, ny, nx * nx)) };
                     cm::F3 pc, pxx, pyy;                                                             // the world position at the three points
@@ -266,8 +321,8 @@ void resolveKernel(std::conditional_t<TEXTURED, TexturedArgs, ResolveArgs> a)
                     const cm::F3 b = normalize3({ cm::fma_(dvdy, inv1.x, dvdx * inv0.x), cm::fma_(dvdy, inv1.y, dvdx * inv0.y), cm::fma_(dvdy, inv1.z, dvdx * inv0.z) });
                     shaded = normalize3(cm::mulVec(unpacked, t, b, normal));
                 }
-                if (tex[2]) mr = mtex::sample(*tex[2], tables, slots[2].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
-                if (tex[3]) emissive = mtex::sample(*tex[3], tables, slots[3].m_IsWrapSampler != 0u, u, v, dudx, dvdx, dudy, dvdy);
+                if (tex[2]) mr = sampleSlot(2);
+                if (tex[3]) emissive = sampleSlot(3);
                 out.x = packRGBA8(mat[0] * albedo.x, mat[1] * albedo.y, mat[2] * albedo.z, debugValue);
                 out.y = packOctUnorm2x16(shaded);
                 out.z = packR9G9B9E5(mat[4] * emissive.x, mat[5] * emissive.y, mat[6] * emissive.z);
@@ -343,6 +398,14 @@ int recordResolve(trhip::DispatchCtx& ctx)
             a.table = (const mtex::TableEntry*)table->entries.ptr;
             a.tableCount = (uint32_t)table->slots.size();
             a.srgb = (const float*)ctx.cl->dev->srgbTable.ptr;
+            // An R8_UINT or feedback entry selects the STREAMED instantiation.  The table cannot tell a min-mip map from another R8_UINT
+            // texture, so any R8_UINT entry selects it: harmless (materials that name no map get the textured kernel's words), if surprising.
+            if (table->streamEntries) {
+                ctx.emit("streamed", [a, grid](hipStream_t s) {
+                    TRHIP_LAUNCH((resolveKernel<true, true, true>), grid, dim3(kTileW, kTileH), 0, s, a);
+                    return trhip::launchStatus("resolveKernel<gbuffer, textured, streamed>"); });
+                return TRHIP_OK;
+            }
             ctx.emit("textured", [a, grid](hipStream_t s) {
                 TRHIP_LAUNCH((resolveKernel<true, true>), grid, dim3(kTileW, kTileH), 0, s, a);
                 return trhip::launchStatus("resolveKernel<gbuffer, textured>"); });

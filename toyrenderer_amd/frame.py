@@ -19,6 +19,7 @@ from .gtao import AmbientOcclusionPass
 from .post import BloomPass, PostPass
 from .rhi import CB, PUSH, SAMPLER, SRV, TEX_SRV, TEX_TABLE, TEX_UAV, UAV
 from .sky import SkyPass
+from .streaming import TextureStreamingPass, check_materials, create_streamed
 from .taa import TemporalAAPass
 
 SLOT_NAMES = ("early_opaque", "late_opaque", "early_alphamask", "late_alphamask")
@@ -57,6 +58,7 @@ class GpuScene:
         self.vertices = self.meshletVertexIds = self.meshletTriangles = None
         self.materials = None
         self.textures, self.texture_table, self.textured = [], None, False
+        self.streams = []                      # streaming.StreamedTexture of every streamable texture (set_textures(streaming=...))
         self.indices = self.rt = None
 
     def set_geometry(self, vertices, meshletVertexIds, meshletTriangles):
@@ -66,42 +68,60 @@ class GpuScene:
         self.meshletVertexIds = self.dev.buffer_from(np.ascontiguousarray(meshletVertexIds, np.uint32), "GlobalMeshletVertexIdxOffsetsBuffer", uav=False)
         self.meshletTriangles = self.dev.buffer_from(np.ascontiguousarray(meshletTriangles, np.uint32), "GlobalMeshletIndicesBuffer", uav=False)
 
-    def set_textures(self, textures):
+    def set_textures(self, textures, streaming=None):
         """The material textures and their table (the stand-in of ResourceDescriptorHeap[...], include/trhip.h): `textures` is a
         list of (mips, format), mips a list of uint8 [h_k, w_k, 4] arrays (level k of max(w >> k, 1) x max(h >> k, 1); interop.make_mips
         makes them from an image), format rhi.FORMAT_RGBA8_UNORM or rhi.FORMAT_SRGBA8_UNORM; or mips an interop.BlockMips (the levels' raw
         block bytes, as interop.parse_dds gives them) with one of rhi.BC_FORMATS.  Returns their descriptor indices, which
-        m_DescriptorIndex of a flagged TextureData names.  Replaces an earlier set; call it before set_materials()."""
+        m_DescriptorIndex of a flagged TextureData names.  Replaces an earlier set; call it before set_materials().
+        streaming=dict(region=(w, h) or None, poison=word or None): texture streaming (streaming.py, FrameDriver(streaming=...)).  Every
+        texture whose size is a multiple of the region (None: D3D's 64 KB tile shape of its format; a size that is no multiple of a
+        GIVEN region is refused, of the default one it stays fully resident) becomes streamable: its mips stay on the host, only its
+        packed tail is uploaded, the rest of its storage is filled with the poison word if one is given, and a min-mip map and a
+        feedback map of it follow the textures in the table (self.streams; set_materials fills their indices in)."""
         self.release_textures()
         if len(textures) == 0:
             return []
-        self.texture_table = self.dev.create_texture_table(len(textures))
+        made = [create_streamed(self.dev, i, mips, fmt, streaming, f"Material Texture {i}") if streaming is not None else None for i, (mips, fmt) in enumerate(textures)]
+        self.streams = [s for s in made if s is not None]
+        self.texture_table = self.dev.create_texture_table(len(textures) + 2 * len(self.streams))
         for i, (mips, fmt) in enumerate(textures):
-            self.textures.append(self.dev.create_sampled_texture(mips, fmt, f"Material Texture {i}"))
+            self.textures.append(made[i].texture if made[i] is not None else self.dev.create_sampled_texture(mips, fmt, f"Material Texture {i}"))
             self.texture_table.set(i, self.textures[-1])
+        for j, s in enumerate(self.streams):
+            s.min_mip_index, s.feedback_index = len(textures) + 2 * j, len(textures) + 2 * j + 1
+            self.texture_table.set(s.min_mip_index, s.min_mip_map)
+            self.texture_table.set(s.feedback_index, s.feedback)
         return list(range(len(textures)))
 
     def release_textures(self):
         if self.texture_table is not None:
             self.texture_table.release()
+        streamed = {id(s.texture) for s in self.streams}
         for t in self.textures:
-            t.release()
-        self.textures, self.texture_table = [], None
+            if id(t) not in streamed:
+                t.release()
+        for s in self.streams:
+            s.release()
+        self.textures, self.texture_table, self.streams = [], None, []
 
     def set_materials(self, materials):
         """The MaterialData buffer (basepass.hlsl t3, Graphic::m_GlobalMaterialDataBuffer) that FrameDriver(gbuffer=True)
         resolves GBufferA from.  A material may use textures (m_MaterialFlags) when every flagged slot's m_DescriptorIndex names a
-        texture of set_textures() and its feedback and min-mip indices are 0xFFFFFFFF (no texture streaming); FrameDriver then binds
-        the texture table and the resolve samples them."""
-        materials = np.ascontiguousarray(materials, I.MaterialData)
+        texture of set_textures() and its feedback and min-mip indices are 0xFFFFFFFF; FrameDriver then binds the texture table and
+        the resolve samples them.  With set_textures(streaming=...) a slot of a streamable texture gets that texture's two map indices
+        filled in, and may name them itself; an index that names anything else is refused."""
+        materials = np.ascontiguousarray(materials, I.MaterialData).copy()
         for bit, slot in enumerate(("m_AlbedoTexture", "m_NormalTexture", "m_MetallicRoughnessTexture", "m_EmissiveTexture")):
             flagged = (materials["m_MaterialFlags"] >> bit) & 1 != 0
             t = materials[slot][flagged]
             if np.any(t["m_DescriptorIndex"] >= len(self.textures)):
                 raise ValueError(f"set_materials: a material uses a texture ({slot}.m_DescriptorIndex {int(t['m_DescriptorIndex'][t['m_DescriptorIndex'] >= len(self.textures)][0]):#x}) "
                                  f"that set_textures() has not loaded ({len(self.textures)} textures)")
-            if np.any(t["m_FeedbackTextureDescriptorIndex"] != 0xFFFFFFFF) or np.any(t["m_MinMapTextureDescriptorIndex"] != 0xFFFFFFFF):
+            if not self.streams and (np.any(t["m_FeedbackTextureDescriptorIndex"] != 0xFFFFFFFF) or np.any(t["m_MinMapTextureDescriptorIndex"] != 0xFFFFFFFF)):
                 raise ValueError(f"set_materials: a material's texture ({slot}) names a sampler-feedback or min-mip texture: texture streaming is not supported")
+        if self.streams:
+            check_materials(materials, self.streams, len(self.textures))
         if self.materials is not None:
             self.materials.release()
         self.materials = self.dev.buffer_from(materials, "GlobalMaterialDataBuffer", uav=False, min_bytes=124)
@@ -154,7 +174,7 @@ class GpuScene:
                 b.release()
 
 
-class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, SkyPass, BloomPass, TemporalAAPass, PostPass):
+class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, SkyPass, BloomPass, TemporalAAPass, PostPass, TextureStreamingPass):
     """BasePassRenderer (Setup + RenderBasePass) over rhi.  One command list per frame.
 
     The cull, the rasters, the motion / G-buffer resolve, the HZB, deferred lighting and the frame's order are here.  Every optional
@@ -176,7 +196,8 @@ class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, 
                  debug_mode: int = 0, lighting: bool = False, dir_light=((0.0, -1.0, 0.0), 1.0), camera_origin=(0.0, 0.0, 0.0),
                  shadow_mask=None, ssao=None, post: bool = False, exposure=(0.0, 0.18), auto_exposure=(0.004, 12.0, 0.04),
                  bloom=(None, 0.0), bloom_mips: int = 0, bloom_filter_radius: float = 0.005, bloom_strength: float = 0.1, sky=None, ao=None,
-                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None, probes=None, taa=None, shadow_denoise=None):
+                 shadows=None, alpha_test: bool = False, ddgi=None, ddgi_update=None, probes=None, taa=None, shadow_denoise=None,
+                 streaming=None):
         """alloc(nbytes, name, stride, indirect) -> rhi.Buffer or None: lets the caller own the memory of the
         output buffers (e.g. torch tensors handed to RCCL, gather.py); None -> device allocation.
         shard_late(hip_stream, late_count_ptr, shard_info_ptr, bucket, phase): multi-GPU hook, called while the
@@ -205,7 +226,8 @@ class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, 
         shadows, shadow_denoise: see accel.SunShadowPass.
         ddgi, ddgi_update: see ddgi.DDGIPass.
         probes: see ddgi.ProbeDrawPass.
-        taa: see taa.TemporalAAPass."""
+        taa: see taa.TemporalAAPass.
+        streaming: see streaming.TextureStreamingPass."""
         self.dev, self.scene, self.view, self._owned = dev, scene, view, []
         lighting = bool(lighting) or bool(post)
         gbuffer = bool(gbuffer) or bool(lighting)
@@ -222,6 +244,7 @@ class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, 
             raise ValueError("alpha_test=True needs raster_depth=True (or visibility, gbuffer, lighting, post): the test runs in the rasters, and a frame without them draws nothing")
         if self.alpha_test and scene.materials is None:
             raise ValueError("alpha_test=True needs GpuScene.set_materials(): the test reads m_ConstAlbedo.w, m_AlphaCutoff and the albedo texture of each instance's material")
+        self._check_streaming(streaming, gbuffer)
         self._check_post(post, exposure, auto_exposure, bloom)
         self._check_bloom(bloom_mips, bloom_filter_radius, bloom_strength, bloom, post)
         self._check_sky(sky, lighting)
@@ -289,6 +312,7 @@ class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, 
         self._create_shadows()
         self._create_ddgi()
         self._create_probes()
+        self._create_streaming()
 
     def _own(self, resource):
         """Registers a resource the driver created (or was handed by alloc) for release(); returns it."""
@@ -341,6 +365,8 @@ class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, 
             k["m_PrevWorldToClip"] = I.world_to_clip(v.prevWorldToView, v.viewToClip) if self.taa is None else self.taa_prev_world_to_clip   # TAA: Scene.cpp:119
         if self.gbuffer_on:
             k["m_DebugMode"] = self.debug_mode                                           # BasePassRenderers.cpp:455
+            if self.streaming is not None:                                               # BasePassRenderers.cpp:458
+                k["m_bWriteSamplerFeedback"], k["m_bVisualizeMinMipTilesOnAlbedoOutput"] = 1, int(self.streaming["visualize"])
         return k
 
     # ---- BasePassRenderer::GPUCulling (:298-404) ------------------------------------------------
@@ -499,6 +525,8 @@ class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, 
             cl.begin_pipeline_stats(query)
         occ = bool(self.flags & 2)
         self.ran = [False] * 4
+        if self.streaming is not None:                                                   # TextureFeedbackManager::BeginFrame
+            self._streaming_begin_frame(cl)
 
         if self.raster_depth:
             cl.clear_texture_f32(self.depth, 0.0)                                        # depth cleared to far at the start of the base pass
@@ -529,6 +557,8 @@ class FrameDriver(AmbientOcclusionPass, SunShadowPass, DDGIPass, ProbeDrawPass, 
                 self._resolve_motion(cl)
         if query is not None:
             cl.end_pipeline_stats(query)
+        if self.streaming is not None:                                                   # TextureFeedbackManager::EndFrame
+            self._streaming_end_frame(cl)
         if self.ao is not None:                                                          # Scene.cpp's order: behind GBufferRenderer, in front of lighting
             self._ambient_occlusion(cl)
         ddgi_skip = self.ddgi_update is not None and self._ddgi_begin_update()           # converged: nothing of the update, its refit included

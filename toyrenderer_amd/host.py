@@ -20,7 +20,8 @@ HOST_SYMBOLS = [
     "trhost_set_node_transforms", "trhost_set_instance_update_range", "trhost_set_camera", "trhost_set_culling", "trhost_set_limits", "trhost_upload_depth",
     "trhost_upload_hzb_mip", "trhost_download_hzb_mip", "trhost_hzb_info", "trhost_frame", "trhost_wait_idle",
     "trhost_pass_buffers", "trhost_instance_buffer", "trhost_device", "trhost_render_graph_stats", "trhost_renderer_times",
-    "trhost_heap_sim", "trhost_set_shard_late_exchange", "trhost_set_gpu_timers",
+    "trhost_heap_sim", "trhost_residency_tiles", "trhost_residency_round",
+    "trhost_set_texture_streaming", "trhost_set_texture_streaming_region", "trhost_get_texture_streaming_stats", "trhost_download_min_mip", "trhost_set_shard_late_exchange", "trhost_set_gpu_timers",
     "trhost_set_pipeline_statistics", "trhost_pipeline_statistics",
     "trhost_rccl_allgather", "trhost_exchange_create", "trhost_exchange_run", "trhost_exchange_wait", "trhost_exchange_outputs",
     "trhost_exchange_destroy", "trhost_load_geometry", "trhost_set_raster_depth", "trhost_download_depth",
@@ -180,6 +181,12 @@ def load() -> C.CDLL:
     L.trhost_exchange_outputs.argtypes = [u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.trhost_set_shard_late_exchange.argtypes = [SHARD_LATE_FN, vp]
     L.trhost_heap_sim.argtypes = [u64, vp, u32, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]
+    L.trhost_set_texture_streaming.argtypes = [C.c_int, u32, u32, C.c_int]
+    L.trhost_set_texture_streaming_region.argtypes = [u32, u32]
+    L.trhost_get_texture_streaming_stats.argtypes = [vp]
+    L.trhost_download_min_mip.argtypes = [u32, vp, u64, C.POINTER(u32), C.POINTER(u32)]
+    L.trhost_residency_tiles.argtypes = [u32, u32, u32, u32, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.trhost_residency_round.argtypes = [u32, u32, u32, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -187,6 +194,34 @@ def load() -> C.CDLL:
 def _check(rc):
     if rc != 0:
         raise HostError(load().trhost_last_error().decode(errors="replace"))
+
+
+RESIDENCY_STATS = ("tilesTotal", "tilesResident", "tilesMapped", "tilesUnmapped", "bytesUploaded")
+
+
+def residency_tiles(size, region):
+    """(standard levels S, tiles over levels 0 .. S - 1) of a streamable texture: size = (width, height, mips), region = (w, h)."""
+    s, n = C.c_uint32(), C.c_uint32()
+    _check(load().trhost_residency_tiles(int(size[0]), int(size[1]), int(size[2]), int(region[0]), int(region[1]), C.byref(s), C.byref(n)))
+    return int(s.value), int(n.value)
+
+
+def residency_round(size, region, tile_bytes: int, feedback, evict_after: int, resident, idle):
+    """One round of THE RESIDENCY RULE (csrc/host/TextureResidency.h; no GPU): feedback = the decoded bytes, uint8 [regions y, regions
+    x]; resident (uint8) and idle (uint32) per tile.  Returns dict(resident, idle, mapped, unmapped (uint8 per tile), min_mip (uint8
+    [regions y, regions x]), stats {RESIDENCY_STATS})."""
+    _, n = residency_tiles(size, region)
+    fb = np.ascontiguousarray(feedback, np.uint8)
+    if fb.shape != (size[1] // region[1], size[0] // region[0]):
+        raise ValueError(f"residency_round: the feedback is {fb.shape}, the texture has {(size[1] // region[1], size[0] // region[0])} regions")
+    m = max(n, 1)
+    res, idl = np.zeros(m, np.uint8), np.zeros(m, np.uint32)
+    res[:n], idl[:n] = np.asarray(resident, np.uint8)[:n], np.asarray(idle, np.uint32)[:n]
+    mapped, unmapped, min_mip, stats = np.zeros(m, np.uint8), np.zeros(m, np.uint8), np.zeros(fb.shape, np.uint8), np.zeros(5, np.uint64)
+    _check(load().trhost_residency_round(int(size[0]), int(size[1]), int(size[2]), int(region[0]), int(region[1]), int(tile_bytes), fb.ctypes.data,
+                                         int(evict_after), n, res.ctypes.data, idl.ctypes.data, mapped.ctypes.data, unmapped.ctypes.data,
+                                         min_mip.ctypes.data, stats.ctypes.data))
+    return dict(resident=res, idle=idl, mapped=mapped, unmapped=unmapped, min_mip=min_mip, stats={k: int(v) for k, v in zip(RESIDENCY_STATS, stats)})
 
 
 def heap_sim(heap_size: int, ops):
@@ -353,6 +388,28 @@ class Renderer:
         if index < 0:
             _check(-1)
         return index
+
+    def set_texture_streaming(self, enable=True, textures_per_frame=1, evict_after=4, poison=False, region=None):
+        """trhost_set_texture_streaming (+ _region): before the first create_material_texture / load_textures.  region=(w, h) or None =
+        the format's default tile shape; poison: the non-resident storage and unmapped tiles are filled with 0xFF00FFFF."""
+        if region is not None:
+            _check(load().trhost_set_texture_streaming_region(int(region[0]), int(region[1])))
+        _check(load().trhost_set_texture_streaming(int(bool(enable)), int(textures_per_frame), int(evict_after), int(bool(poison))))
+
+    @property
+    def streaming_stats(self) -> dict:
+        s = np.zeros(5, np.uint64)
+        _check(load().trhost_get_texture_streaming_stats(s.ctypes.data))
+        return dict(zip(("tilesTotal", "tilesResident", "tilesUploaded", "bytesUploaded", "texturesProcessed"), (int(x) for x in s)))
+
+    def download_min_mip(self, texture: int) -> np.ndarray:
+        """uint8 [regions y, regions x]: the min-mip map of a streamed texture on the device."""
+        self.wait_idle()
+        rx, ry = C.c_uint32(), C.c_uint32()
+        _check(load().trhost_download_min_mip(int(texture), None, 0, C.byref(rx), C.byref(ry)))
+        out = np.empty((ry.value, rx.value), np.uint8)
+        _check(load().trhost_download_min_mip(int(texture), out.ctypes.data, out.nbytes, None, None))
+        return out
 
     def load_textures(self, textures):
         """[(mips, format)] -> descriptor indices, as GpuScene.set_textures; before load_materials."""

@@ -21,7 +21,8 @@ FORMAT_RGBA32_UINT = 5    # GBufferA: four u32 per texel (x, y, z, w)
 FORMAT_R11G11B10_FLOAT = 6  # LightingOutput: one u32 per texel, R bits 0-10, G 11-21, B 22-31
 FORMAT_R8_UNORM = 7       # shadow mask: one byte per texel
 FORMAT_R8_UINT = 8        # SSAO texture: one byte per texel
-FORMAT_RGBA8_UNORM = 10   # back buffer: one u32 per texel, R in the low byte (9 is not a format)
+SAMPLER_FEEDBACK_FORMAT = 9  # a feedback map: one u32 per region; made by Device.create_sampler_feedback only (create_texture refuses it)
+FORMAT_RGBA8_UNORM = 10   # back buffer: one u32 per texel, R in the low byte
 FORMAT_SRGBA8_UNORM = 11  # RGBA8_UNORM's layout; R, G, B decoded through the sRGB transfer function when sampled
 FORMAT_R10G10B10A2_UNORM = 12  # DDGI probe irradiance: one u32 per texel, R bits 0-9, G 10-19, B 20-29, A 30-31
 FORMAT_RGBA16_FLOAT = 13  # DDGI probe data: four fp16 per texel
@@ -57,6 +58,8 @@ ABI_SYMBOLS = [
     "trhip_buffer_mark_written", "trhip_texture_mark_written",
     "trhip_texture_table_create", "trhip_texture_table_retain", "trhip_texture_table_release", "trhip_texture_table_capacity",
     "trhip_texture_table_set", "trhip_texture_table_clear", "trhip_srgb_table", "trhip_format_block_bytes", "trhip_dds_parse",
+    "trhip_texture_set_streaming_region", "trhip_texture_streaming_region", "trhip_sampler_feedback_create",
+    "trhip_cmd_clear_sampler_feedback", "trhip_cmd_decode_sampler_feedback", "trhip_cmd_write_texture_region",
     "trhip_cmd_create", "trhip_cmd_release", "trhip_cmd_open", "trhip_cmd_close", "trhip_cmd_write_buffer",
     "trhip_cmd_clear_buffer_u32", "trhip_cmd_clear_texture_f32", "trhip_cmd_clear_texture_u32", "trhip_cmd_copy_buffer", "trhip_cmd_copy_texture", "trhip_cmd_host_callback", "trhip_cmd_dispatch", "trhip_cmd_dispatch_indirect",
     "trhip_cmd_begin_timer", "trhip_cmd_end_timer", "trhip_cmd_begin_marker", "trhip_cmd_end_marker",
@@ -64,7 +67,7 @@ ABI_SYMBOLS = [
     "trhip_timer_create", "trhip_timer_release", "trhip_timer_get_ms",
     "trhip_pipeline_stats_create", "trhip_pipeline_stats_release", "trhip_cmd_begin_pipeline_stats",
     "trhip_cmd_end_pipeline_stats", "trhip_pipeline_stats_get",
-    "trhip_readback_create", "trhip_readback_release", "trhip_readback_reset", "trhip_cmd_copy_to_readback", "trhip_readback_read",
+    "trhip_readback_create", "trhip_readback_release", "trhip_readback_reset", "trhip_cmd_copy_to_readback", "trhip_readback_read", "trhip_readback_poll",
     "trhip_profile_enable", "trhip_profile_filter", "trhip_profile_reset", "trhip_profile_count", "trhip_profile_entry",
     "trhip_launch_shard_late_info",
     "trhip_accel_max_depth", "trhip_blas_leaf_capacity", "trhip_accel_max_nodes", "trhip_blas_build", "trhip_tlas_build",
@@ -190,6 +193,13 @@ def load() -> C.CDLL:
         L.trhip_format_block_bytes.argtypes = [u32]
         L.trhip_format_block_bytes.restype = u32
         L.trhip_dds_parse.argtypes = [vp, u64, C.POINTER(DdsInfo)]
+    if hasattr(L, "trhip_sampler_feedback_create"):         # absent from an older build named by TRHIP_LIB (see above)
+        L.trhip_texture_set_streaming_region.argtypes = [vp, u32, u32]
+        L.trhip_texture_streaming_region.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+        L.trhip_sampler_feedback_create.argtypes = [vp, vp, C.c_char_p, C.POINTER(vp)]
+        L.trhip_cmd_clear_sampler_feedback.argtypes = [vp, vp]
+        L.trhip_cmd_decode_sampler_feedback.argtypes = [vp, vp, u64, vp]
+        L.trhip_cmd_write_texture_region.argtypes = [vp, vp, u32, u32, u32, u32, u32, vp, u64]
     L.trhip_cmd_create.argtypes = [vp, C.POINTER(vp)]
     L.trhip_cmd_open.argtypes = [vp]
     L.trhip_cmd_close.argtypes = [vp]
@@ -233,6 +243,8 @@ def load() -> C.CDLL:
         L.trhip_readback_reset.argtypes = [vp]
         L.trhip_cmd_copy_to_readback.argtypes = [vp, vp, u32, vp, C.c_uint64, C.c_uint64]
         L.trhip_readback_read.argtypes = [vp, u32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        if hasattr(L, "trhip_readback_poll"):
+            L.trhip_readback_poll.argtypes = [vp, u32, C.POINTER(C.c_int)]
     L.trhip_profile_enable.argtypes = [vp, i32]
     L.trhip_profile_filter.argtypes = [vp, C.c_char_p]
     L.trhip_profile_reset.argtypes = [vp]
@@ -335,10 +347,23 @@ class Texture:
     def _dtype(self):
         return {FORMAT_R16_FLOAT: np.uint16, FORMAT_RG32_UINT: np.uint64, FORMAT_RG16_FLOAT: np.float16, FORMAT_RGBA32_UINT: np.uint32,
                 FORMAT_R11G11B10_FLOAT: np.uint32, FORMAT_R8_UNORM: np.uint8, FORMAT_R8_UINT: np.uint8, FORMAT_RGBA8_UNORM: np.uint32,
-                FORMAT_SRGBA8_UNORM: np.uint32, FORMAT_R10G10B10A2_UNORM: np.uint32, FORMAT_RGBA16_FLOAT: np.float16}.get(self.format, np.float32)
+                FORMAT_SRGBA8_UNORM: np.uint32, FORMAT_R10G10B10A2_UNORM: np.uint32, FORMAT_RGBA16_FLOAT: np.float16,
+                SAMPLER_FEEDBACK_FORMAT: np.uint32}.get(self.format, np.float32)
 
     def _shape(self, mw: int, mh: int):
         return (mh, mw, 2) if self.format == FORMAT_RG16_FLOAT else (mh, mw, 4) if self.format in (FORMAT_RGBA32_UINT, FORMAT_RGBA16_FLOAT) else (mh, mw)
+
+    def set_streaming_region(self, region_w: int = 0, region_h: int = 0):
+        """trhip_texture_set_streaming_region: makes a material texture streamable with regions of region_w x region_h texels
+        (0, 0: D3D's 64 KB tile shape of the format); refused when the size of mip 0 is no multiple of it.  Before TextureTable.set."""
+        _check(load().trhip_texture_set_streaming_region(self.h, int(region_w), int(region_h)))
+        return self.streaming_region()
+
+    def streaming_region(self):
+        """(region_w, region_h) in texels, (0, 0) for a texture that is not streamable; a feedback map answers its texture's."""
+        w, h = C.c_uint32(), C.c_uint32()
+        _check(load().trhip_texture_streaming_region(self.h, C.byref(w), C.byref(h)))
+        return int(w.value), int(h.value)
 
     def upload_slice(self, k: int, arr: np.ndarray):
         """Slice k of an array texture (trhip_texture_upload_slice)."""
@@ -475,6 +500,12 @@ class Readback:
         _check(load().trhip_readback_read(self.h, int(slot), out.ctypes.data, out.nbytes, C.byref(written)))
         return out, int(written.value)
 
+    def ready(self, slot: int) -> bool:
+        """trhip_readback_poll: never waits; True when read(slot) would return at once."""
+        r = C.c_int(0)
+        _check(load().trhip_readback_poll(self.h, int(slot), C.byref(r)))
+        return bool(r.value)
+
     def reset(self):
         """Waits for the device and marks every slot as never written; recorded lists that name the resource stay valid."""
         _check(load().trhip_readback_reset(self.h))
@@ -552,6 +583,17 @@ class CommandList:
     def end_pipeline_stats(self, q: PipelineStatsQuery): _check(load().trhip_cmd_end_pipeline_stats(self.h, q.h))
     def copy_to_readback(self, rb: Readback, slot: int, src: Buffer, offset: int, nbytes: int):
         _check(load().trhip_cmd_copy_to_readback(self.h, rb.h, int(slot), src.h, int(offset), int(nbytes)))
+    def clear_sampler_feedback(self, feedback: Texture): _check(load().trhip_cmd_clear_sampler_feedback(self.h, feedback.h))
+    def decode_sampler_feedback(self, dst: Buffer, feedback: Texture, offset: int = 0):
+        """One byte per region of the feedback map into dst at `offset` (row-major; the level asked for, 0xFF = never sampled)."""
+        _check(load().trhip_cmd_decode_sampler_feedback(self.h, dst.h, int(offset), feedback.h))
+
+    def write_texture_region(self, tex: Texture, mip: int, x: int, y: int, w: int, h: int, data):
+        """trhip_cmd_write_texture_region: a w x h texel rectangle of one mip of a material texture at (x, y); data: uint8 [h, w, 4], or
+        the rectangle's blocks (bytes or any array) for a block-compressed texture.  Copied when recorded."""
+        arr = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+        _check(load().trhip_cmd_write_texture_region(self.h, tex.h, int(mip), int(x), int(y), int(w), int(h), arr.ctypes.data, arr.nbytes))
+
     def begin_marker(self, name: str): _check(load().trhip_cmd_begin_marker(self.h, name.encode()))
     def end_marker(self): _check(load().trhip_cmd_end_marker(self.h))
 
@@ -653,6 +695,16 @@ class Device:
         for k, m in enumerate(mips):
             t.upload_mip(k, m)
         return t
+
+    def create_sampler_feedback(self, paired: Texture, name="") -> Texture:
+        """trhip_sampler_feedback_create: the feedback map of a streamable material texture, one 32-bit word per region, created
+        as never sampled (0xFFFFFFFF).  download_mip(0) gives the raw words, CommandList.decode_sampler_feedback the bytes."""
+        if not hasattr(load(), "trhip_sampler_feedback_create"):
+            raise TrhipError(f"{LIB_PATH} has no sampler feedback: a build from before texture streaming")
+        h = C.c_void_p()
+        _check(load().trhip_sampler_feedback_create(self.h, paired.h, name.encode(), C.byref(h)))
+        rw, rh = paired.streaming_region()
+        return Texture(self, h, paired.w // rw, paired.hgt // rh, 1, SAMPLER_FEEDBACK_FORMAT, name)
 
     def create_command_list(self) -> CommandList:
         h = C.c_void_p()
