@@ -9,13 +9,14 @@ ROOT = os.path.dirname(HERE)
 _LIB = {}
 
 
-def compile_ref(tmpdir, name, declare, include_oracle=False):
-    """tests/<name>.c as lib<name>.so in tmpdir (gcc -O2 -ffp-contract=off; include_oracle: -I oracle), loaded and handed to
-    declare(lib) for its argtypes / restype once; cached by output path."""
-    out = os.path.join(str(tmpdir), f"lib{name}.so")
+def compile_ref(tmpdir, name, declare, include_oracle=False, defines=()):
+    """tests/<name>.c as lib<name>.so in tmpdir (gcc -O2 -ffp-contract=off; include_oracle: -I oracle; defines: names for -D, which
+    become a part of the output's name), loaded and handed to declare(lib) for its argtypes / restype once; cached by output path."""
+    out = os.path.join(str(tmpdir), "lib" + "-".join([name, *defines]) + ".so")
     if out not in _LIB:
         include = ["-I", os.path.join(ROOT, "oracle")] if include_oracle else []
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", *include, os.path.join(HERE, name + ".c"), "-o", out, "-lm"])
+        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", *include, *["-D" + d for d in defines], os.path.join(HERE, name + ".c"), "-o", out,
+                               "-lm"])
         lib = C.CDLL(out)
         declare(lib)
         _LIB[out] = lib

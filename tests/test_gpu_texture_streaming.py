@@ -1,7 +1,8 @@
 """Texture streaming on the GPU, the shader half: "basepass_PS_Main_GBuffer" with a min-mip or feedback map in the table at t19
 (the #streamed instantiation; csrc/material_textures.hip.h, csrc/visibility_resolve.hip.h).  Every word of GBufferA, of the motion
 target and of the decoded feedback against tests/texture_streaming_ref.c, through raw dispatches at 80 x 56 pixels, over textures
-of 32 x 32, 64 x 32 and 16 x 64 texels with regions of 8 x 8 in RGBA8, sRGBA8, BC1 and BC3."""
+of 32 x 32, 64 x 32 and 16 x 64 texels with regions of 8 x 8 in RGBA8, sRGBA8, BC1 and BC3.  Regions that are not 8 x 8 or not square,
+textures whose sides are no powers of two and the scenes that tell one feedback rule from another: tests/test_gpu_texture_streaming_rules.py."""
 import os
 import sys
 
@@ -22,7 +23,7 @@ pytestmark = pytest.mark.gpu
 ts = ref_library(TS)
 ALL = S.ALBEDO | S.NORMAL | S.MR | S.EMISSIVE
 EMIT = (2.0, 0.5, 4.0)
-STREAMED, TEXTURED = ["basepass_PS_Main_GBuffer#streamed"], ["basepass_PS_Main_GBuffer#textured"]
+STREAMED, TEXTURED = X.STREAMED, X.TEXTURED
 
 
 @pytest.fixture(scope="module")
@@ -30,20 +31,7 @@ def bc(tmp_path_factory):
     return bc_ref.load(tmp_path_factory.mktemp("bc_ref"))
 
 
-def _both(dev, vr, ts, bc, scene, mats, table, what, feedback=True, visualize=False, names=STREAMED):
-    """The scene on the GPU and in the reference: every word of the three outputs equal.  Returns (vis, GBufferA, {entry: feedback bytes})."""
-    k = consts(S.view())
-    vis, g, mot, got_names, fb = X.gpu(dev, k, scene, mats, table, feedback, visualize)
-    rvis, rg, rmot, rfb = X.reference(vr, ts, bc, k, scene, mats, table, feedback, visualize)
-    same(vis, rvis, what + ": visibility texels")
-    same(g, rg, what + ": GBufferA")
-    same(mot, rmot, what + ": motion")
-    assert sorted(fb) == sorted(rfb), (sorted(fb), sorted(rfb))
-    for i in fb:
-        same(fb[i], rfb[i], what + f": decoded feedback of entry {i}")
-    assert got_names == names, got_names
-    assert np.all(g[vis == 0] == X.FILL), what + ": nothing drawn, nothing written"
-    return vis, g, fb
+_both = X.both
 
 
 def _wrap_and_clamp_quads():

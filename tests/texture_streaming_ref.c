@@ -29,6 +29,20 @@
  *              not required by any of the last evict_after rounds;
  *   minMip   : per region, the finest level m such that its covering tiles are resident at every standard level >= m; S if none.
  * A frame in which the texture's feedback is not processed changes nothing.
+ *
+ * NEGATIVE CONTROLS (tests/test_texture_streaming_rule_scenes.py; never defined by any other build).  -DTS_REF_MUTATE_<RULE> breaks one
+ * rule of the sampler, so that the test can show that the rule scenes (tests/texture_streaming_rule_scenes.py) tell the broken rule
+ * from the stated one.  Every mutant keeps its word and byte indices inside the maps (the two SWAP mutants by taking the index modulo
+ * the region count).
+ *   SWAP_REGION_FOOTPRINT  the footprint marks divide x by RH and y by RW          NO_ORIGIN_SHIFT   a texel marks (x / RW, y / RH): no << level
+ *   SWAP_REGION_UNDER      the region under uv divides x by RH and y by RW         NO_L1W            no marks of the level-l1w footprint
+ *   NO_L0W_FOOTPRINT       no marks of the level-l0w footprint                     NO_UNDER          no mark of the region under uv
+ *   CLAMPED_LEVELS         the footprints of l0, l1 are marked (with l0, l1)       CENTRE_FOOTPRINT  every tap marks the footprints at uv itself
+ *   ONE_TEXEL              texel (x0, y0) of a footprint marks alone               UNDER_CLAMP_MODE  the point under uv is always clamped
+ *   CLAMP_REPLACES         lod = minMip != 0 ? minMip : lodWanted (no max)         UNDER_ROUNDS      point: t0 = floorf(u * dim + 0.5f)
+ * -DTS_REF_LANE_DROP is no mutant: it marks through the kernel's per-lane drop (Marker in csrc/material_textures.hip.h) instead of
+ * mark by mark, and must give the same words; with it, -DTS_REF_MUTATE_DROP_BY_INDEX drops on the word index alone, as the kernel's
+ * negative control TR_STREAM_MUTATE_DROP_BY_INDEX does.
  */
 #include "material_textures_ref.c"
 
@@ -44,7 +58,14 @@ static const float ts_mip_colours[16][3] = { { 1.0f, 1.0f, 1.0f }, { 1.0f, 0.25f
 
 static uint32_t ts_point(float u, uint32_t dim, int wrap)
 {
+#ifdef TS_REF_MUTATE_UNDER_ROUNDS
+    const float t0 = floorf(u * (float)dim + 0.5f);
+#else
     const float t0 = floorf(u * (float)dim);
+#endif
+#ifdef TS_REF_MUTATE_UNDER_CLAMP_MODE
+    wrap = 0;
+#endif
     if (!wrap) return (uint32_t)fminf(fmaxf(t0, 0.0f), (float)(dim - 1u));
     const int i = (int)fminf(fmaxf(t0, -0x1p30f), 0x1p30f);
     int r = i % (int)dim;
@@ -52,17 +73,56 @@ static uint32_t ts_point(float u, uint32_t dim, int wrap)
     return (uint32_t)r;
 }
 
-static void ts_mark(uint32_t* words, uint32_t index, uint32_t level) { if (level < words[index]) words[index] = level; }
+/* The marks of one sample.  lastIndex, lastLevel: the per-lane drop's state (TS_REF_LANE_DROP), one per sample as in the kernel. */
+typedef struct { uint32_t* words; uint32_t lastIndex, lastLevel; } TsMarker;
 
-static void ts_mark_footprint(const MtTexture* t, uint32_t level, int wrap, float u, float v, uint32_t rw, uint32_t rh, uint32_t* words)
+static void ts_mark(TsMarker* m, uint32_t index, uint32_t level)
+{
+#ifdef TS_REF_LANE_DROP
+#ifdef TS_REF_MUTATE_DROP_BY_INDEX
+    if (index == m->lastIndex) return;
+#else
+    if (index == m->lastIndex && level >= m->lastLevel) return;
+#endif
+    m->lastIndex = index; m->lastLevel = level;
+#endif
+    if (level < m->words[index]) m->words[index] = level;
+}
+
+/* word of the region of mip-0 texel (x, y) */
+static uint32_t ts_region(const MtTexture* t, uint32_t x, uint32_t y, uint32_t rw, uint32_t rh, int footprint)
+{
+#if defined(TS_REF_MUTATE_SWAP_REGION_FOOTPRINT) || defined(TS_REF_MUTATE_SWAP_REGION_UNDER)
+#ifdef TS_REF_MUTATE_SWAP_REGION_FOOTPRINT
+    const int swap = footprint;
+#else
+    const int swap = !footprint;
+#endif
+    if (swap) return ((y / rw) * (t->width / rw) + x / rh) % ((t->width / rw) * (t->height / rh));
+#endif
+    (void)footprint;
+    return (y / rh) * (t->width / rw) + x / rw;
+}
+
+static void ts_mark_footprint(const MtTexture* t, uint32_t level, int wrap, float u, float v, uint32_t rw, uint32_t rh, TsMarker* m)
 {
     uint32_t x[2], y[2];
     float f;
     axis(u, mip_dim(t->width, level), wrap, &x[0], &x[1], &f);
     axis(v, mip_dim(t->height, level), wrap, &y[0], &y[1], &f);
-    for (int j = 0; j < 2; ++j)
-        for (int i = 0; i < 2; ++i)
-            ts_mark(words, ((y[j] << level) / rh) * (t->width / rw) + (x[i] << level) / rw, level);
+#ifdef TS_REF_MUTATE_NO_ORIGIN_SHIFT
+    const uint32_t shift = 0;
+#else
+    const uint32_t shift = level;
+#endif
+#ifdef TS_REF_MUTATE_ONE_TEXEL
+    const int texels = 1;
+#else
+    const int texels = 2;
+#endif
+    for (int j = 0; j < texels; ++j)
+        for (int i = 0; i < texels; ++i)
+            ts_mark(m, ts_region(t, x[i] << shift, y[j] << shift, rw, rh, 1), level);
 }
 
 /* The streamed sampler.  minMip (bytes) and feedback (words) may each be NULL; rw, rh: the region.  Returns N; *minMipOut: the byte read. */
@@ -80,14 +140,26 @@ uint32_t ts_sample(const MtTexture* t, const float* srgb, int wrap, const float 
     const float fN = (float)N, x = pmax / fN, top = (float)(t->mipCount - 1u);
     const float lodWanted = fminf(fmaxf(x > 0.0f ? mt_log2(x) : 0.0f, 0.0f), top);
     uint32_t under = 0, minMip = 0;
-    if (minMipMap || feedback) under = (ts_point(uv[1], t->height, wrap) / rh) * (t->width / rw) + ts_point(uv[0], t->width, wrap) / rw;
+    if (minMipMap || feedback) under = ts_region(t, ts_point(uv[0], t->width, wrap), ts_point(uv[1], t->height, wrap), rw, rh, 0);
     if (minMipMap) minMip = minMipMap[under];
     if (minMipOut) *minMipOut = minMip;
+#ifdef TS_REF_MUTATE_CLAMP_REPLACES
+    const float lod = fminf(minMip != 0u ? (float)minMip : lodWanted, top);
+#else
     const float lod = fminf(fmaxf(lodWanted, (float)minMip), top);
+#endif
     const float l0f = floorf(lod), f = lod - l0f;
     const uint32_t l0 = (uint32_t)l0f, l1 = l0 + 1u < t->mipCount ? l0 + 1u : t->mipCount - 1u;
     const uint32_t l0w = (uint32_t)floorf(lodWanted), l1w = l0w + 1u < t->mipCount ? l0w + 1u : t->mipCount - 1u;
-    if (feedback) ts_mark(feedback, under, l0w);
+#ifdef TS_REF_MUTATE_CLAMPED_LEVELS
+    const uint32_t m0 = l0, m1 = l1;
+#else
+    const uint32_t m0 = l0w, m1 = l1w;
+#endif
+    TsMarker marker = { feedback, 0xFFFFFFFFu, 0u };
+#ifndef TS_REF_MUTATE_NO_UNDER
+    if (feedback) ts_mark(&marker, under, l0w);
+#endif
     float acc[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     for (uint32_t i = 0; i < N; ++i) {
         const float k = ((float)i + 0.5f) / fN - 0.5f;
@@ -97,8 +169,17 @@ uint32_t ts_sample(const MtTexture* t, const float* srgb, int wrap, const float 
         bilinear(t, srgb, l1, wrap, u, v, b1);
         for (int c = 0; c < 4; ++c) acc[c] = acc[c] + lerp(b0[c], b1[c], f);
         if (feedback) {
-            ts_mark_footprint(t, l0w, wrap, u, v, rw, rh, feedback);
-            ts_mark_footprint(t, l1w, wrap, u, v, rw, rh, feedback);
+#ifdef TS_REF_MUTATE_CENTRE_FOOTPRINT
+            const float mu = uv[0], mv = uv[1];
+#else
+            const float mu = u, mv = v;
+#endif
+#ifndef TS_REF_MUTATE_NO_L0W_FOOTPRINT
+            ts_mark_footprint(t, m0, wrap, mu, mv, rw, rh, &marker);
+#endif
+#ifndef TS_REF_MUTATE_NO_L1W
+            ts_mark_footprint(t, m1, wrap, mu, mv, rw, rh, &marker);
+#endif
         }
     }
     for (int c = 0; c < 4; ++c) out[c] = acc[c] / fN;

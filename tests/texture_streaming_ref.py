@@ -37,8 +37,9 @@ def _declare(lib):
     lib.ts_residency_round.restype = None
 
 
-def load(tmpdir) -> C.CDLL:
-    return compile_ref(tmpdir, "texture_streaming_ref", _declare, include_oracle=True)
+def load(tmpdir, defines=()) -> C.CDLL:
+    """defines: the reference's negative-control switches (TS_REF_MUTATE_*, TS_REF_LANE_DROP); none for the reference itself."""
+    return compile_ref(tmpdir, "texture_streaming_ref", _declare, include_oracle=True, defines=tuple(defines))
 
 
 def _p(a):

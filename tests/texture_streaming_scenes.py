@@ -1,6 +1,8 @@
 """Scenes, tables and the two runners (GPU, reference) that the texture-streaming tests share (tests/test_texture_streaming_ref.py,
 tests/test_gpu_texture_streaming.py, tests/test_gpu_texture_streaming_loop.py): the quads of tests/material_texture_scenes.py at
 80 x 56 pixels over streamable textures of 32 x 32, 64 x 32 and 16 x 64 texels with regions of 8 x 8 (3, 3 and 2 standard levels).
+The rule scenes (tests/texture_streaming_rule_scenes.py) bring the regions that are not 8 x 8 and not square, and the textures whose
+sides are no powers of two.
 
 A TABLE here is a list of entries in descriptor order: ("texture", mips, format, region or None), ("minmip", texture index, uint8
 [ry, rx]) and ("feedback", texture index).  Not a test module: every assert says what it compared."""
@@ -18,6 +20,7 @@ SIZES = [(32, 32), (64, 32), (16, 64)]
 FORMATS = [S.RGBA8, S.SRGBA8, B.BC1, B.BC3]
 FILL = 0xABCD1234
 SRGB_BC = (B.BC1_SRGB, B.BC2_SRGB, B.BC3_SRGB)
+STREAMED, TEXTURED = ["basepass_PS_Main_GBuffer#streamed"], ["basepass_PS_Main_GBuffer#textured"]
 
 
 def full_chain(w, h):
@@ -173,6 +176,25 @@ def gpu(dev, k, scene, materials, table, feedback=True, visualize=False, render=
         return vis, g, mot, names, decoded_feedback(dev, table, made)
     finally:
         release(tt, made)
+
+
+def both(dev, vr, ts, bc, scene, mats, table, what, feedback=True, visualize=False, names=STREAMED):
+    """The scene on the GPU and in the reference: every word of the three outputs and every decoded feedback byte equal.  Returns
+    (vis, GBufferA, {entry: feedback bytes})."""
+    from suite_support import same
+    from visibility_scenes import consts
+    k = consts(S.view())
+    vis, g, mot, got_names, fb = gpu(dev, k, scene, mats, table, feedback, visualize)
+    rvis, rg, rmot, rfb = reference(vr, ts, bc, k, scene, mats, table, feedback, visualize)
+    same(vis, rvis, what + ": visibility texels")
+    same(g, rg, what + ": GBufferA")
+    same(mot, rmot, what + ": motion")
+    assert sorted(fb) == sorted(rfb), (sorted(fb), sorted(rfb))
+    for i in fb:
+        same(fb[i], rfb[i], what + f": decoded feedback of entry {i}")
+    assert got_names == names, got_names
+    assert np.all(g[vis == 0] == FILL), what + ": nothing drawn, nothing written"
+    return vis, g, fb
 
 
 # ---- the scenes of the loop tests (a static camera; the CPU test proves convergence on each before the GPU test relies on it) ---------

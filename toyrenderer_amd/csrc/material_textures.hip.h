@@ -271,6 +271,11 @@ __device__ __forceinline__ cm::F3 sample(const TableEntry& e, const float* lds, 
 // a mark that repeats a region of the same footprint or that its last mark already covers (same word, level not lower); what is left
 // is merged across the wave before the atomic goes out: the first lane still to be served issues the one atomic for all the lanes that
 // hold its (word, level), until no lane is left: one atomic per wave and distinct (word, level).  -DTRHIP_FEEDBACK_NAIVE builds the per-mark atomic, for tools/texture_streaming_cost.py.
+// Negative controls (profiles/gbuffer/streaming_mutations.txt): eleven -D builds that each break one rule of the clamp, of the marks or
+// of the write (TR_STREAM_MUTATE_*) fail tests/test_gpu_texture_streaming_rules.py.  Each changes a value or a choice between in-range
+// indices only: a mark that is left out, a level between 0 and mips - 1, a texel of the level's own footprint, an origin that is NOT
+// shifted up (so never beyond the shifted one).  None touches a loop bound, a barrier, an early return or an index beyond a map, and
+// the merge loop of emitMark still ends under MERGE_BY_WORD, because the leader always matches itself.
 struct Stream
 {
     const uint8_t* minMip;                     // the slot's min-mip map, or nullptr
@@ -280,7 +285,11 @@ struct Stream
 
 __device__ __forceinline__ uint32_t pointOf(float u, uint32_t dim, bool wrap)
 {
+#ifdef TR_STREAM_MUTATE_UNDER_ROUNDS            // negative control only: the nearest texel boundary, not the texel under u (clamped or wrapped below as before)
+    const float t0 = __builtin_floorf(u * (float)dim + 0.5f);
+#else
     const float t0 = __builtin_floorf(u * (float)dim);
+#endif
     if (!wrap) return (uint32_t)cm::min_(cm::max_(t0, 0.0f), (float)(dim - 1u));
     const int i = (int)cm::min_(cm::max_(t0, -0x1p30f), 0x1p30f);
     int r;
@@ -308,8 +317,12 @@ __device__ __forceinline__ void emitMark(uint32_t* words, uint32_t index, uint32
     uint64_t todo = __builtin_amdgcn_ballot_w64(true);
     while (todo) {
         const uint32_t leader = (uint32_t)__builtin_ctzll(todo);
+#ifdef TR_STREAM_MUTATE_MERGE_BY_WORD           // negative control only: the leader's level goes out for every lane on its word
+        const bool same = (lo == (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)leader)) & (hi == (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)leader));
+#else
         const bool same = (lo == (uint32_t)__builtin_amdgcn_readlane((int)lo, (int)leader)) & (hi == (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)leader)) &
                           (level == (uint32_t)__builtin_amdgcn_readlane((int)level, (int)leader));
+#endif
         if (lane == leader) atomicMin(p, level);
         todo &= ~__builtin_amdgcn_ballot_w64(same);
     }
@@ -321,7 +334,9 @@ struct Marker
     uint32_t* words; uint32_t lastIndex, lastLevel;
     __device__ __forceinline__ void mark(uint32_t index, uint32_t level)
     {
-#ifndef TRHIP_FEEDBACK_NAIVE
+#if defined(TR_STREAM_MUTATE_DROP_BY_INDEX)     // negative control only: a lower level that follows a higher one to the same word is dropped
+        if (index == lastIndex) return;
+#elif !defined(TRHIP_FEEDBACK_NAIVE)
         if (index == lastIndex && level >= lastLevel) return;                           // the last mark covers it
 #endif
         emitMark(words, index, level);
@@ -330,9 +345,16 @@ struct Marker
     // the four texels of a footprint of level f.level
     __device__ __forceinline__ void markFootprint(const Stream& st, const Footprint& f)
     {
-        const uint32_t rx0 = (f.x.i0 << f.level) >> st.shiftX, rx1 = (f.x.i1 << f.level) >> st.shiftX;
-        const uint32_t r0 = ((f.y.i0 << f.level) >> st.shiftY) * st.regionsX, r1 = ((f.y.i1 << f.level) >> st.shiftY) * st.regionsX;
-#ifdef TRHIP_FEEDBACK_NAIVE
+#ifdef TR_STREAM_MUTATE_NO_ORIGIN_SHIFT         // negative control only: the level texel's own index, never beyond its mip-0 origin
+        const uint32_t up = 0u;
+#else
+        const uint32_t up = f.level;
+#endif
+        const uint32_t rx0 = (f.x.i0 << up) >> st.shiftX, rx1 = (f.x.i1 << up) >> st.shiftX;
+        const uint32_t r0 = ((f.y.i0 << up) >> st.shiftY) * st.regionsX, r1 = ((f.y.i1 << up) >> st.shiftY) * st.regionsX;
+#if defined(TR_STREAM_MUTATE_ONE_TEXEL)         // negative control only: texel (i0, i0) marks alone
+        mark(r0 + rx0, f.level);
+#elif defined(TRHIP_FEEDBACK_NAIVE)
         mark(r0 + rx0, f.level); mark(r0 + rx1, f.level); mark(r1 + rx0, f.level); mark(r1 + rx1, f.level);
 #else
         mark(r0 + rx0, f.level);
@@ -363,12 +385,22 @@ __device__ __forceinline__ cm::F3 sampleStreamed(const TableEntry& e, const Stre
     const uint32_t under = mapped ? regionUnder(e, st, wrap, u, v) : 0u;
     const uint32_t minMip = st.minMip ? st.minMip[under] : 0u;
     minMipOut = minMip;
+#ifdef TR_STREAM_MUTATE_CLAMP_REPLACES          // negative control only: a min-mip byte that is not 0 replaces the lod instead of bounding it
+    const float lod = cm::min_(minMip != 0u ? (float)minMip : lodWanted, top);
+#else
     const float lod = cm::min_(cm::max_(lodWanted, (float)minMip), top);
+#endif
     const float l0f = __builtin_floorf(lod), f = lod - l0f;
     const uint32_t l0 = (uint32_t)l0f, l1 = l0 + 1u < e.mips ? l0 + 1u : e.mips - 1u;
-    const uint32_t l0w = (uint32_t)__builtin_floorf(lodWanted), l1w = l0w + 1u < e.mips ? l0w + 1u : e.mips - 1u;
+#ifdef TR_STREAM_MUTATE_CLAMPED_LEVELS          // negative control only: the footprints of the clamped levels are marked
+    const uint32_t l0w = (uint32_t)__builtin_floorf(lodWanted), m0 = l0, m1 = l1;
+#else
+    const uint32_t l0w = (uint32_t)__builtin_floorf(lodWanted), l1w = l0w + 1u < e.mips ? l0w + 1u : e.mips - 1u, m0 = l0w, m1 = l1w;
+#endif
     Marker marker = { st.feedback, 0xFFFFFFFFu, 0u };
+#ifndef TR_STREAM_MUTATE_NO_UNDER               // negative control only: no mark of the region under uv
     if (st.feedback) marker.mark(under, l0w);
+#endif
     const float* rgbTable = lds + (srgbDecoded(e.format) ? 0u : 256u);
     const bool blocks = blockCompressed(e.format);
     cm::F3 acc = { 0.0f, 0.0f, 0.0f };
@@ -380,8 +412,17 @@ __device__ __forceinline__ cm::F3 sampleStreamed(const TableEntry& e, const Stre
         Quad q0, q1;
         fetchQuads(e, blocks, f0, f1, q0, q1);
         if (st.feedback) {                                                              // address arithmetic only, while the texels are in flight
-            marker.markFootprint(st, l0w == l0 ? f0 : footprintOf(e, l0w, wrap, tu, tv));
-            marker.markFootprint(st, l1w == l1 ? f1 : l1w == l0 ? f0 : footprintOf(e, l1w, wrap, tu, tv));
+#ifdef TR_STREAM_MUTATE_CENTRE_FOOTPRINT        // negative control only: every tap marks the footprints at uv itself
+            marker.markFootprint(st, footprintOf(e, m0, wrap, u, v));
+            marker.markFootprint(st, footprintOf(e, m1, wrap, u, v));
+#else
+#ifndef TR_STREAM_MUTATE_NO_L0W_FOOTPRINT       // negative control only: no marks of the level-l0w footprint
+            marker.markFootprint(st, m0 == l0 ? f0 : footprintOf(e, m0, wrap, tu, tv));
+#endif
+#ifndef TR_STREAM_MUTATE_NO_L1W                 // negative control only: no marks of the level-l1w footprint
+            marker.markFootprint(st, m1 == l1 ? f1 : m1 == l0 ? f0 : footprintOf(e, m1, wrap, tu, tv));
+#endif
+#endif
         }
         const cm::F3 b0 = bilinear(q0, f0, rgbTable), b1 = bilinear(q1, f1, rgbTable);
         acc.x = acc.x + lerp_(b0.x, b1.x, f);
